@@ -88,7 +88,14 @@ def parse_args(argv=None):
     ap.add_argument("--cluster-leg-rows", type=int, default=1_000_000, help="rows per device of the in-process orr_cluster leg of a multi-GPU run; 0 = skip")
     ap.add_argument("--set-option", action="append", default=[], metavar="NAME=VALUE",
                     help="orr_index_set_option on every shard before the run (e.g. two_stage=0)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last timed step returned (rows, scores, counts of every "
+                         "query) as DIR/<name>.npy in float64; the inputs are a pure function of the arguments, so two builds "
+                         "run with the same arguments can be compared output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------
@@ -259,8 +266,9 @@ class Leg:
         self.rows_per_gpu, self.n_total, self.batch, self.terms = rows_per_gpu, n_total, batch, terms
 
 
-def run_leg(leg, args, env, idx, front, gen, overlap=False):
-    """Returns the leg's result dict on every rank (timings are the max over ranks)."""
+def run_leg(leg, args, env, idx, front, gen, overlap=False, outputs=None):
+    """Returns the leg's result dict on every rank (timings are the max over ranks).  `outputs` (a dict): receives what the
+    last timed step returned."""
     P, torch, dist, dev, world, rank = env["P"], env["torch"], env["dist"], env["dev"], env["world"], env["rank"]
     k, dim, B = args.topk, args.dim, leg.batch
     n_steps_total = args.warmup + args.steps
@@ -305,6 +313,8 @@ def run_leg(leg, args, env, idx, front, gen, overlap=False):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if outputs is not None:
+        outputs.update(zip(OUTPUT_NAMES, last))
     stats = idx.kernel_stats()
     sstats = idx.search_stats()
     idx.set_profiling(1)
@@ -554,7 +564,7 @@ def cluster_child(args, n_dev):
             "rank1_is_planted_row": doc.get("rank1_is_planted_row"), "rccl_exchanges": doc.get("rccl_exchanges"), "child_total_s": doc.get("total_s")}
 
 
-def run_cluster_leg(args, env, gen, devices, rows_per_dev, B, terms=True, workload=None, exchange="host"):
+def run_cluster_leg(args, env, gen, devices, rows_per_dev, B, terms=True, workload=None, exchange="host", outputs=None):
     """ONE process, every device: orr_cluster (one shard per device, a host thread per shard, records through pinned host
     memory, host merge) -- the multi-GPU form of the C ABI that a C# host binds.  Queries are host-resident by contract."""
     P, torch = env["P"], env["torch"]
@@ -595,6 +605,8 @@ def run_cluster_leg(args, env, gen, devices, rows_per_dev, B, terms=True, worklo
     for s_ in range(args.warmup, n_steps_total):
         last = cl.search(q_steps[s_], term_steps[s_], gen.NOW_TICKS, k, candidate_limit=n_total)
     dt = time.perf_counter() - t1
+    if outputs is not None:
+        outputs.update(zip(OUTPUT_NAMES, last))
     planted = gen.planted_rows((n_steps_total - 1) * B, B, n_total)
     res = {"workload": workload or ("orr_cluster (one process, %d devices): %d chunks x %d-d, %d per device, batch=%d, top-k=%d, %s" %
                                     (G, n_total, dim, rows_per_dev, B, k, "full hybrid" if terms else "cosine + recency")),
@@ -607,6 +619,18 @@ def run_cluster_leg(args, env, gen, devices, rows_per_dev, B, terms=True, worklo
     res["rccl_exchanges"] = res["search_stats"].get("rccl_exchanges", 0)
     cl.close()
     return res
+
+
+# what a search returns: rows [B, k] int64 (-1 past the count), scores [B, k] fp64, counts [B] int32
+OUTPUT_NAMES = ("rows", "scores", "counts")
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: one float64 .npy per returned array (row ids stay exact below 2^53; a few KB for any batch)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name in OUTPUT_NAMES:
+        np.save(os.path.join(path, name + ".npy"), np.asarray(outputs[name], dtype=np.float64))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -793,6 +817,12 @@ def run(args, probe, state, cluster_mode, world, rank):
         except Exception as exc:
             leg_errors[name] = ("%s: %s" % (type(exc).__name__, exc))[:300]
 
+    head_out = {}                                  # what the headline's last timed step returned
+
+    def dump_head():
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, head_out)
+
     if cluster_mode:
         # ---- ONE process, all devices, through orr_cluster: the C5 per-GPU shape on every device
         rows = args.rows_per_gpu or 12_500_000
@@ -800,7 +830,8 @@ def run(args, probe, state, cluster_mode, world, rank):
         n_total = rows * args.gpus
         head = run_cluster_leg(args, env, syn, [g % max(1, n_visible) for g in range(args.gpus)], rows, B, terms=not args.no_terms,
                                workload=workload_label(rows, dim, B, k, not args.no_terms, args.gpus).replace("row-sharded over", "orr_cluster, one process, over"),
-                               exchange=args.cluster_exchange)
+                               exchange=args.cluster_exchange, outputs=head_out)
+        dump_head()
         head["exchange_mode"] = args.cluster_exchange
         head["row_scores_per_sec"] = head["value"] * n_total
         if n_visible < args.gpus:
@@ -845,7 +876,8 @@ def run(args, probe, state, cluster_mode, world, rank):
         pmc = probe.get("pmc") or {}
         if "error" not in pmc:
             MEASURED_TRAFFIC.update(pmc)                # (the children ran the headline's shape: only this leg may quote them)
-        head = run_leg(head_leg, args, env, idx, None, syn, overlap=not args.no_overlap_leg)
+        head = run_leg(head_leg, args, env, idx, None, syn, overlap=not args.no_overlap_leg, outputs=head_out)
+        dump_head()
         MEASURED_TRAFFIC.clear()
         if head.get("roofline") is not None:
             head["roofline"]["traffic_measured_in_this_run"] = bool(pmc) and "error" not in pmc and head["roofline"].get("traffic") is not None
@@ -864,7 +896,8 @@ def run(args, probe, state, cluster_mode, world, rank):
         front.always_collect = bool(args.dist_rehearsal)
         ranks_seen = front.rccl_ranks_seen()
         head_leg = Leg("headline", workload_label(rows, dim, B, k, not args.no_terms, world), rows, n_total, B, terms=not args.no_terms)
-        head = run_leg(head_leg, args, env, idx, front, syn)
+        head = run_leg(head_leg, args, env, idx, front, syn, outputs=head_out)
+        dump_head()
         head["rccl_ranks_seen"] = ranks_seen if args.backend == "nccl" else 0
         head["backend"] = args.backend + (" (RCCL over xGMI)" if args.backend == "nccl" else f" (rehearsal: {world} ranks, {n_visible} card(s))")
         head["collectives_per_step"] = front.collectives / max(1, args.warmup + args.steps + min(5, args.steps))

@@ -4,6 +4,9 @@ import copy
 import json
 import os
 
+import numpy as np
+import pytest
+
 import bench
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -66,3 +69,19 @@ def test_emit_prints_exactly_one_last_line(tmp_path, capsys, monkeypatch):
     with open(tmp_path / "gpurun_out" / "bench_full.json") as f:
         assert json.load(f)["config"]["name"] == "C3"
     assert json.loads(out)["full"] == os.path.join("gpurun_out", "bench_full.json")
+
+
+def test_dump_outputs_writes_float64_arrays_and_steps_are_validated(tmp_path):
+    args = bench.parse_args(["--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")])
+    assert args.steps == 3 and args.dump_outputs == str(tmp_path / "out")
+    rows = np.array([[7, 2, -1], [2 ** 40 + 1, 0, 5]], dtype=np.int64)
+    scores = np.array([[0.5, 0.25, 0.0], [1.0 / 3.0, -2.0, 1e-300]], dtype=np.float64)
+    counts = np.array([2, 3], dtype=np.int32)
+    bench.dump_outputs(args.dump_outputs, dict(zip(bench.OUTPUT_NAMES, (rows, scores, counts))))
+    for name, want in zip(bench.OUTPUT_NAMES, (rows, scores, counts)):
+        got = np.load(tmp_path / "out" / (name + ".npy"))
+        assert got.dtype == np.float64 and got.shape == want.shape
+        assert np.array_equal(got, want)
+    for bad in ("0", "-1"):
+        with pytest.raises(SystemExit):
+            bench.parse_args(["--steps", bad])
