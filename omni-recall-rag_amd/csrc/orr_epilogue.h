@@ -434,13 +434,55 @@ __device__ __forceinline__ int acc16_as_int_here(int token)
 
 typedef float f32x2e __attribute__((ext_vector_type(2)));
 
+// Four-bit count words: a word's low half (after >> 16 (g & 1)) split into (x, y) = its even and odd nibbles, one per byte;
+// nibble e is byte (e >> 1) of x (even e) or of y (odd e)
+__host__ __device__ constexpr uint32_t count_nibbles_even(uint32_t w) { return w & 0x0F0F0F0Fu; }
+__host__ __device__ constexpr uint32_t count_nibbles_odd(uint32_t w) { return (w >> 4) & 0x0F0F0F0Fu; }
+__host__ __device__ constexpr uint32_t count_nibble_operand(int e, uint32_t x, uint32_t y) { return (e & 1) ? y : x; }
+__host__ __device__ constexpr int count_nibble_byte(int e) { return e >> 1; }
+
+// Two-bit count words: the lane group's byte v (field e = bits 2e, 2e + 1) spread to field e -> byte e.  The shifted copies
+// are OR-ed: added (v * 0x41041) they overlap at bits 6-7, 12-13, 18-19 and the carries corrupt the neighbouring fields.
+__host__ __device__ constexpr uint32_t spread_count_fields2(uint32_t v)
+{
+    const uint32_t t = v | (v << 6);
+    return (t | (t << 12)) & 0x03030303u;
+}
+
+namespace count_word_checks {
+constexpr bool two_bit_spread_exact()
+{
+    for (uint32_t v = 0; v < 256u; ++v)
+        for (int e = 0; e < 4; ++e)
+            if (((spread_count_fields2(v) >> (8 * e)) & 0xFFu) != ((v >> (2 * e)) & 3u)) return false;
+    return true;
+}
+// every value of every nibble of both halves, on a background of zeros and of ones (what pass 1b reads: (w >> sh >> 4e) & 15)
+constexpr bool nibble_extraction_exact()
+{
+    for (int h = 0; h < 2; ++h)
+        for (int e = 0; e < 4; ++e)
+            for (uint32_t v = 0; v < 16u; ++v)
+                for (uint32_t bg : {0u, ~0u}) {
+                    const int at = 16 * h + 4 * e;
+                    const uint32_t w = (bg & ~(15u << at)) | (v << at);
+                    const uint32_t half = w >> (16 * h);
+                    const uint32_t op = count_nibble_operand(e, count_nibbles_even(half), count_nibbles_odd(half));
+                    if (((op >> (8 * count_nibble_byte(e))) & 0xFFu) != v) return false;
+                }
+    return true;
+}
+}  // namespace count_word_checks
+static_assert(count_word_checks::two_bit_spread_exact(), "two-bit count words: field e of a byte must land in byte e");
+static_assert(count_word_checks::nibble_extraction_exact(), "four-bit count words: nibble e must be byte (e >> 1) of x or y");
+
 // byte E of the pair (x, y) = (even nibbles, odd nibbles of a count word's low half, one per byte): nibble e of the word
 template <int E>
 __device__ __forceinline__ float count_of_nibble(uint32_t x, uint32_t y)
 {
-    const uint32_t v = (E & 1) ? y : x;
+    const uint32_t v = count_nibble_operand(E, x, y);
     float r;
-    if constexpr ((E >> 1) == 0) asm("v_cvt_f32_ubyte0 %0, %1" : "=v"(r) : "v"(v));
+    if constexpr (count_nibble_byte(E) == 0) asm("v_cvt_f32_ubyte0 %0, %1" : "=v"(r) : "v"(v));
     else asm("v_cvt_f32_ubyte1 %0, %1" : "=v"(r) : "v"(v));
     return r;
 }
@@ -473,7 +515,7 @@ __device__ __forceinline__ float ubyte_as_float(uint32_t v)
 // a is an integer dot (|a| <= 3072 * 127^2), rb <= 1e30 and qx <= 1: no product overflows; inf - inf only arises for pairs
 // that are to be dropped (row past the end and keep-everything query; no query and keep-everything row).
 // BITS = 2: two-bit count words (a batch whose queries all have at most three terms): half the words to load, the lane's four
-// counts of a tile are one byte of the word, spread to four bytes with one multiplication.
+// counts of a tile are one byte of the word, spread to four bytes without carries (spread_count_fields2).
 template <int QDEPTH, typename HOOK = EpiNoHook, int BITS = 4>
 __device__ __forceinline__ void fused_epilogue16(int acc_token, int qbase, int64_t colbase, int32_t B, int64_t n_rows,
                                                  const FusedEpilogue &epi, int lane, EpiParked *queue, int queue_stride, uint32_t idx_salt,
@@ -524,12 +566,12 @@ __device__ __forceinline__ void fused_epilogue16(int acc_token, int qbase, int64
                 // the count words of rows j0, j0 + 1: nibble e -> byte (e >> 1) of x (even e) or y (odd e); two-bit words: field e -> byte e of x
                 uint32_t x0, y0, x1, y1;
                 if constexpr (BITS == 2) {
-                    x0 = (__builtin_amdgcn_ubfe(L.w[b][j0][t], 8u * (uint32_t)g, 8u) * 0x41041u) & 0x03030303u;
-                    x1 = (__builtin_amdgcn_ubfe(L.w[b][j0 + 1][t], 8u * (uint32_t)g, 8u) * 0x41041u) & 0x03030303u;
+                    x0 = spread_count_fields2(__builtin_amdgcn_ubfe(L.w[b][j0][t], 8u * (uint32_t)g, 8u));
+                    x1 = spread_count_fields2(__builtin_amdgcn_ubfe(L.w[b][j0 + 1][t], 8u * (uint32_t)g, 8u));
                     y0 = y1 = 0u;
                 } else {
                     const uint32_t w0 = L.w[b][j0][t] >> sh, w1 = L.w[b][j0 + 1][t] >> sh;
-                    x0 = w0 & 0x0F0F0F0Fu; y0 = (w0 >> 4) & 0x0F0F0F0Fu; x1 = w1 & 0x0F0F0F0Fu; y1 = (w1 >> 4) & 0x0F0F0F0Fu;
+                    x0 = count_nibbles_even(w0); y0 = count_nibbles_odd(w0); x1 = count_nibbles_even(w1); y1 = count_nibbles_odd(w1);
                 }
                 static_for<4>([&](auto e_c) {
                     constexpr int e = decltype(e_c)::value;
