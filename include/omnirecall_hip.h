@@ -265,6 +265,27 @@ int orr_index_view(orr_index *parent, orr_index **view);
 int     orr_index_delete_rows(orr_index *idx, int64_t n, const int64_t *row_ids, int64_t *out_deleted);
 int64_t orr_index_live_rows(const orr_index *idx);
 
+/* ---- reindex in place ----------------------------------------------------------
+ * Replaces the vectors of sealed rows in place (reindex, DocumentIngestionService.cs:210-291): the reference
+ * re-embeds every chunk of a document and upserts the list again with the same chunk ids, contents and
+ * CreatedAtUtc (:277), so only the vectors change.  row_ids[n] are the ids of orr_index_append (host or device
+ * memory); emb is [n][dim] fp32 (host or device memory).  dim == the index dimension: each row gets its new
+ * vector; dim 0 with emb NULL: the rows lose their embedding (zero rows with norm 0, as orr_index_append stores a
+ * row without one); any other dim is ORR_EDIM, and an index created with dim 0 is ORR_ESTATE.  Afterwards the
+ * shard holds the same bytes a shard sealed from scratch with the new vectors would hold: embeddings, exact norms,
+ * and the rows of the int8 and bf16 shadows where those exist (shadows not built yet are built later from the new
+ * rows).  The token index, timestamps, row ids and candidate order stay as they are, nothing moves in HBM, so
+ * internal lanes and views (orr_index_view) see the new rows at once; views do not block the call.  Unknown and
+ * deleted ids are skipped (writing a deleted row would bring it back); every live row carrying a listed id is
+ * updated (duplicate ids of orr_index_append); an id listed twice is ORR_EINVAL before anything is written.
+ * *out_updated (may be NULL) = rows written.  Needs a sealed index (ORR_ESTATE) and the owning handle (ORR_EINVAL
+ * on a view).  Exclusive like delete: waits for the searches in flight.  The input goes through a device staging
+ * buffer of at most 256 MiB of rows per round: no second copy of the shard.  Cost: about 2 x 4 x dim bytes of
+ * HBM traffic per row plus the upload.  ORR_EDEVICE part way through leaves the listed rows in an unspecified mix
+ * of old and new: rebuild the shard. */
+int     orr_index_update_rows(orr_index *idx, int64_t n, const int64_t *row_ids, int32_t dim, const float *emb,
+                              int64_t *out_updated);
+
 /* ---- compaction ------------------------------------------------------------------
  * Rebuilds a sealed shard IN PLACE without its deleted rows -- the other half of "replace the chunk list"
  * (InMemoryIngestionStore.cs:17-25, 50-55), where the reference simply drops the old list: embeddings move up

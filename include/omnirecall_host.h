@@ -117,6 +117,11 @@ int64_t orrh_service_tombstoned_rows(orrh_service *svc);    /* rows dropped in p
 int64_t orrh_service_delta_merges(orrh_service *svc);       /* times the delta shards were merged into one (above) */
 int64_t orrh_service_compactions(orrh_service *svc);        /* shards compacted in place (orr_index_compact) instead of rebuilt, when more than a
                                                                quarter of a shard's rows had been dropped */
+/* A reindex (DocumentIngestionService.cs:210-291) that gives a document's chunks new vectors under the same chunk ids, chunk
+ * indices, contents and CreatedAtTicks, with the same count and with every new vector of the service's dimension (or null
+ * where the old one was null), overwrites those rows in place (orr_index_update_rows): no tombstones, no delta shard, no
+ * rebuild.  Any other change to the list takes the paths above.  Rows updated in place so far: */
+int64_t orrh_service_updated_rows(orrh_service *svc);
 /* SearchAsync(query, topK) with the query embedding supplied by the caller (the
  * IEmbeddingClient result; qdim 0 = empty vector) and a frozen clock.  *out_json is
  * malloc'd; release it with orrh_free.  A blank query is ORR_EINVAL "Query is required." */

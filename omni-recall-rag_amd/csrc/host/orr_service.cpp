@@ -105,7 +105,7 @@ struct orrh_service {
     int32_t dim = 0;
     uint64_t built_version = ~0ull;
     int64_t next_id = 0;
-    int64_t full_rebuilds = 0, delta_builds = 0, tombstoned_rows = 0, compactions = 0, delta_merges = 0;
+    int64_t full_rebuilds = 0, delta_builds = 0, tombstoned_rows = 0, compactions = 0, delta_merges = 0, updated_rows = 0;
 };
 
 namespace {
@@ -203,6 +203,44 @@ void assign_row_bases(orrh_service *svc)
     }
 }
 
+// Reindex (DocumentIngestionService.ReindexDocumentAsync, DocumentIngestionService.cs:210-291): the new chunk list of `doc`
+// carries, position by position, the chunk ids, chunk indices, contents and CreatedAtUtc (:277) of the rows live in `sh`
+// (positions `at`), and only the vectors differ.  Those are overwritten in place (orr_index_update_rows): no tombstones, no
+// delta shard.  Every row's new embedding must have svc->dim elements, or be empty where the old one was empty too, so that
+// the dimension a rebuild would pick (majority_dim) stays the same.  Returns 1 when done, 0 when the list does not qualify
+// (the caller takes the tombstone path), or an error.
+int reindex_in_place(orrh_service *svc, Shard &sh, const std::string &doc, const std::vector<size_t> &at, orrh_store *st)
+{
+    auto it = st->chunks_by_document.find(doc);
+    if (it == st->chunks_by_document.end() || svc->dim <= 0) return 0;
+    const std::vector<Chunk> &list = it->second;
+    if (list.empty() || list.size() != at.size()) return 0;
+    std::vector<int64_t> ids_with, ids_without;
+    std::vector<float> emb;
+    for (size_t i = 0; i < list.size(); ++i) {
+        const Chunk &o = sh.chunks[at[i]], &c = list[i];
+        if (c.id != o.id || c.chunk_index != o.chunk_index || c.content != o.content || c.created_ticks != o.created_ticks) return 0;
+        const bool usable = (int32_t)c.embedding.size() == svc->dim;
+        if (!usable && !(c.embedding.empty() && o.embedding.empty())) return 0;
+        if (usable) {
+            ids_with.push_back(sh.id_base + (int64_t)at[i]);
+            emb.insert(emb.end(), c.embedding.begin(), c.embedding.end());
+        } else {
+            ids_without.push_back(sh.id_base + (int64_t)at[i]);        // as build_shard stores a row without a usable vector
+        }
+    }
+    int64_t done = 0, done0 = 0;
+    int r = ORR_OK;
+    if (!ids_with.empty()) r = orr_index_update_rows(sh.index, (int64_t)ids_with.size(), ids_with.data(), svc->dim, emb.data(), &done);
+    if (r == ORR_OK && !ids_without.empty()) r = orr_index_update_rows(sh.index, (int64_t)ids_without.size(), ids_without.data(), 0, nullptr, &done0);
+    if (r == ORR_ESTATE || r == ORR_EDIM) return 0;
+    if (r != ORR_OK) return fail(r, orr_last_error());
+    for (size_t i = 0; i < list.size(); ++i) sh.chunks[at[i]].embedding = list[i].embedding;
+    sh.doc_stamps[doc] = st->chunk_stamp[doc];
+    svc->updated_rows += done + done0;
+    return 1;
+}
+
 // Bring the device shards up to date with the store (the :26 data source).  Chunk lists are
 // flattened in enumeration order, as GetRecentChunksAsync does (InMemoryIngestionStore.cs:59-60).
 int ensure_index(orrh_service *svc)
@@ -221,6 +259,19 @@ int ensure_index(orrh_service *svc)
         for (const auto &kv : sh.doc_stamps) {
             auto it = st->chunk_stamp.find(kv.first);
             if (it == st->chunk_stamp.end() || it->second != kv.second) stale.push_back(kv.first);
+        }
+        if (!stale.empty() && !changed) {               // lists that only changed their vectors: in place (reindex_in_place)
+            std::map<std::string, std::vector<size_t>> live_at;
+            for (size_t p = 0; p < sh.chunks.size(); ++p)
+                if ((sh.dead.empty() || !sh.dead[p]) && std::binary_search(stale.begin(), stale.end(), sh.chunks[p].document_id))
+                    live_at[sh.chunks[p].document_id].push_back(p);
+            std::vector<std::string> rest;
+            for (const auto &doc : stale) {
+                const int r = reindex_in_place(svc, sh, doc, live_at[doc], st);
+                if (r < 0) return r;
+                if (r == 0) rest.push_back(doc);
+            }
+            stale.swap(rest);
         }
         if (!stale.empty() && !changed) {
             if (sh.dead.empty()) sh.dead.assign(sh.chunks.size(), 0);
@@ -481,6 +532,13 @@ int64_t orrh_service_compactions(orrh_service *svc)
     if (!svc) return 0;
     std::lock_guard<std::mutex> l(svc->mu);
     return svc->compactions;
+}
+
+int64_t orrh_service_updated_rows(orrh_service *svc)
+{
+    if (!svc) return 0;
+    std::lock_guard<std::mutex> l(svc->mu);
+    return svc->updated_rows;
 }
 
 int64_t orrh_service_tombstoned_rows(orrh_service *svc)

@@ -1286,6 +1286,27 @@ int64_t orr_index_live_rows(const orr_index *idx)
     return idx ? idx->n_rows - (int64_t)(idx->parent ? idx->parent->dead.size() : idx->dead.size()) : 0;
 }
 
+// The live rows (not deleted) that carry the ids want[0..n): (position, index into want) for each, in the order of `want`;
+// a duplicate id of orr_index_append gives several.  Ids map to positions through idx->id_index, built at the first call.
+static int live_rows_of_ids(orr_index *idx, const std::vector<int64_t> &want, std::vector<std::pair<int64_t, int64_t>> &out)
+{
+    const size_t rows = (size_t)idx->n_rows;
+    if (idx->id_index.empty()) {                       // ids -> positions, once
+        std::vector<int64_t> ids(rows);
+        HIP_TRY(hipMemcpy(ids.data(), idx->d_row_ids, sizeof(int64_t) * rows, hipMemcpyDeviceToHost));
+        idx->id_index.resize(rows);
+        for (size_t p = 0; p < rows; ++p) idx->id_index[p] = {ids[p], (int64_t)p};
+        std::sort(idx->id_index.begin(), idx->id_index.end());
+    }
+    out.clear();
+    for (size_t i = 0; i < want.size(); ++i) {
+        auto it = std::lower_bound(idx->id_index.begin(), idx->id_index.end(), std::make_pair(want[i], (int64_t)-1));
+        for (; it != idx->id_index.end() && it->first == want[i]; ++it)
+            if (!std::binary_search(idx->dead.begin(), idx->dead.end(), it->second)) out.push_back({it->second, (int64_t)i});
+    }
+    return ORR_OK;
+}
+
 int orr_index_delete_rows(orr_index *idx, int64_t n, const int64_t *row_ids, int64_t *out_deleted)
 {
     if (out_deleted) *out_deleted = 0;
@@ -1297,21 +1318,12 @@ int orr_index_delete_rows(orr_index *idx, int64_t n, const int64_t *row_ids, int
     if (n == 0 || idx->n_rows == 0) return ORR_OK;
     HIP_TRY(hipSetDevice(idx->device));
     const size_t rows = (size_t)idx->n_rows;
-    if (idx->id_index.empty()) {                       // ids -> positions, once
-        std::vector<int64_t> ids(rows);
-        HIP_TRY(hipMemcpy(ids.data(), idx->d_row_ids, sizeof(int64_t) * rows, hipMemcpyDeviceToHost));
-        idx->id_index.resize(rows);
-        for (size_t p = 0; p < rows; ++p) idx->id_index[p] = {ids[p], (int64_t)p};
-        std::sort(idx->id_index.begin(), idx->id_index.end());
-    }
     std::vector<int64_t> want((size_t)n);
     HIP_TRY(hipMemcpy(want.data(), row_ids, sizeof(int64_t) * (size_t)n, hipMemcpyDefault));
+    std::vector<std::pair<int64_t, int64_t>> found;
+    ORR_TRY(live_rows_of_ids(idx, want, found));
     std::vector<int64_t> fresh;
-    for (int64_t id : want) {
-        auto it = std::lower_bound(idx->id_index.begin(), idx->id_index.end(), std::make_pair(id, (int64_t)-1));
-        for (; it != idx->id_index.end() && it->first == id; ++it)
-            if (!std::binary_search(idx->dead.begin(), idx->dead.end(), it->second)) fresh.push_back(it->second);
-    }
+    for (const auto &f : found) fresh.push_back(f.first);
     std::sort(fresh.begin(), fresh.end());
     fresh.erase(std::unique(fresh.begin(), fresh.end()), fresh.end());
     if (fresh.empty()) return ORR_OK;
@@ -1334,6 +1346,77 @@ int orr_index_delete_rows(orr_index *idx, int64_t n, const int64_t *row_ids, int
     idx->dead.swap(merged);
     { std::lock_guard<std::mutex> pl(idx->lanes_mu); idx->dead_count_pub = (int64_t)idx->dead.size(); }
     if (out_deleted) *out_deleted = (int64_t)fresh.size();
+    return ORR_OK;
+}
+
+int orr_index_update_rows(orr_index *idx, int64_t n, const int64_t *row_ids, int32_t dim, const float *emb, int64_t *out_updated)
+{
+    if (out_updated) *out_updated = 0;
+    if (!idx || n < 0 || (n > 0 && !row_ids)) return fail(ORR_EINVAL, "orr_index_update_rows: bad argument");
+    if (n > 0 && dim != 0 && !emb) return fail(ORR_EINVAL, "orr_index_update_rows: emb is NULL with dim %d", dim);
+    if (dim == 0 && emb) return fail(ORR_EINVAL, "orr_index_update_rows: dim 0 (rows without an embedding) takes emb = NULL");
+    AllLanes all(idx);                                 // no search in flight on any lane while the rows change
+    std::lock_guard<std::mutex> lock(idx->mu);
+    if (!idx->sealed) return fail(ORR_ESTATE, "orr_index_update_rows: the index is not sealed");
+    if (idx->is_view) return fail(ORR_EINVAL, "orr_index_update_rows: update the owning index, not a view");
+    if (idx->dim == 0) return fail(ORR_ESTATE, "orr_index_update_rows: the index was created with dim 0: it holds no embeddings");
+    if (dim != 0 && dim != idx->dim)
+        return fail(ORR_EDIM, "orr_index_update_rows: dim %d differs from the index dimension %d", dim, idx->dim);
+    if (n == 0 || idx->n_rows == 0) return ORR_OK;
+    HIP_TRY(hipSetDevice(idx->device));
+    std::vector<int64_t> want((size_t)n);
+    HIP_TRY(hipMemcpy(want.data(), row_ids, sizeof(int64_t) * (size_t)n, hipMemcpyDefault));
+    {
+        std::vector<int64_t> sorted(want);
+        std::sort(sorted.begin(), sorted.end());
+        const auto rep = std::adjacent_find(sorted.begin(), sorted.end());
+        if (rep != sorted.end()) return fail(ORR_EINVAL, "orr_index_update_rows: row id %lld is listed twice", (long long)*rep);
+    }
+    std::vector<std::pair<int64_t, int64_t>> found;    // (position, input row), ascending input row
+    ORR_TRY(live_rows_of_ids(idx, want, found));
+    if (found.empty()) return ORR_OK;
+    const int32_t D = idx->dim;
+    const int64_t n_t = (int64_t)found.size();
+    std::vector<int64_t> pos((size_t)n_t), src((size_t)n_t);
+    for (int64_t t = 0; t < n_t; ++t) { pos[(size_t)t] = found[(size_t)t].first; src[(size_t)t] = found[(size_t)t].second; }
+    // the input rows go through a bounded staging buffer (at most 256 MiB of rows per round, as compaction's bounce buffer):
+    // exact norms of the staged rows by the kernel the seal uses, then one wave per target writes the row, its norm and the
+    // shadows' rows in place
+    const int64_t chunk = std::max<int64_t>(1, ((int64_t)256 << 20) / ((int64_t)sizeof(float) * D));
+    const int64_t m_max = std::min<int64_t>(chunk, n);
+    hipStream_t s = idx->stream;
+    void *i8 = idx->i8_ready ? idx->emb_i8.p : nullptr;
+    void *bf = idx->shadow_ready ? idx->emb_shadow.p : nullptr;
+    DevBuf stage, norms, d_pos, d_src;
+    auto body = [&]() -> int {
+        ORR_TRY(stage.reserve(sizeof(float) * (size_t)m_max * D));
+        ORR_TRY(norms.reserve(sizeof(double) * (size_t)m_max));
+        ORR_TRY(d_pos.reserve(sizeof(int64_t) * (size_t)n_t));
+        ORR_TRY(d_src.reserve(sizeof(int64_t) * (size_t)n_t));
+        HIP_TRY(hipMemcpyAsync(d_pos.p, pos.data(), sizeof(int64_t) * (size_t)n_t, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_src.p, src.data(), sizeof(int64_t) * (size_t)n_t, hipMemcpyHostToDevice, s));
+        if (dim == 0) HIP_TRY(hipMemsetAsync(stage.p, 0, sizeof(float) * (size_t)m_max * D, s));      // zero rows, norm 0 (as append)
+        int64_t t0 = 0;
+        for (int64_t j0 = 0; j0 < n && t0 < n_t; j0 += chunk) {
+            const int64_t m = std::min<int64_t>(chunk, n - j0);
+            int64_t t1 = t0;
+            while (t1 < n_t && src[(size_t)t1] < j0 + m) ++t1;
+            if (t1 == t0) continue;                                   // no live row among these ids
+            if (dim != 0)
+                HIP_TRY(hipMemcpyAsync(stage.p, emb + (size_t)j0 * D, sizeof(float) * (size_t)m * D, hipMemcpyDefault, s));
+            HIP_TRY(orr::launch_dot_exact(stage.as<float>(), m, D, nullptr, 1, true, norms.as<double>(), m, s));
+            HIP_TRY(orr::launch_update_rows(stage.as<float>(), norms.as<double>(), d_pos.as<int64_t>() + t0, d_src.as<int64_t>() + t0, j0,
+                                            t1 - t0, D, idx->d_emb, idx->d_norm_b, i8, idx->i8_scale.as<float>(), idx->i8_rel_err.as<float>(),
+                                            idx->i8_rel_hat.as<float>(), idx->i8_rowf.as<float4>(), bf, s));
+            t0 = t1;
+        }
+        HIP_TRY(hipStreamSynchronize(s));
+        return ORR_OK;
+    };
+    const int r = body();
+    stage.release(); norms.release(); d_pos.release(); d_src.release();
+    if (r != ORR_OK) return r == ORR_ENOMEM ? r : fail(ORR_EDEVICE, "orr_index_update_rows: device update failed: %s", orr_last_error());
+    if (out_updated) *out_updated = n_t;
     return ORR_OK;
 }
 

@@ -281,6 +281,13 @@ hipError_t launch_screen_gemv_bf16(const void *q_hi, int32_t B, const void *e_sh
 size_t i8_tiled_bytes(int64_t n_rows, int32_t D);
 hipError_t launch_i8_shadow(const float *E, const double *norm_b, int64_t n_rows, int32_t D, void *tiled, float *scale,
                             float *rel_err, float *rel_hat, hipStream_t s);
+// orr_index_update_rows: targets t = 0..n_targets-1 get staged row src[t] - src_base of `rows` ([.][D] fp32, compact) and its
+// exact norm (norms[], launch_dot_exact self_norm over `rows`) at position pos[t] of E / norm_b, and, where the shadows exist
+// (non-null), the int8 image + scale / rel_err / rel_hat / rowf (D % 128 == 0) and the tiled bf16 image (D % 64 == 0) that
+// launch_i8_shadow + launch_i8_rowf and launch_bf16_tiled would write there.  Targets must be distinct positions.
+hipError_t launch_update_rows(const float *rows, const double *norms, const int64_t *pos, const int64_t *src, int64_t src_base,
+                              int64_t n_targets, int32_t D, float *E, double *norm_b, void *i8_tiled, float *i8_scale, float *i8_rel_err,
+                              float *i8_rel_hat, float4 *i8_rowf, void *bf16_tiled, hipStream_t s);
 // zero (optional): n_zero words the kernel clears as well (the pass's counters: saves the call a memset).
 hipError_t launch_i8_queries(const float *Q, int32_t B, int32_t D, void *q12, float *s1, double *err2, hipStream_t s,
                              double *err2_level1 = nullptr, uint32_t *zero = nullptr, int32_t n_zero = 0);

@@ -1209,6 +1209,82 @@ __global__ __launch_bounds__(256, 2) void screen_gemv_i8_kernel(I8Queries Q, int
     }
 }
 
+// Byte offset of element k of row rr of a 256-row tile in the tiled, swizzled int8 image: [D/64][256][64] per tile, 16-byte
+// chunks of a row permuted by ((rr >> 2) & 3).
+__device__ __forceinline__ int64_t i8_tiled_off(int k, int rr)
+{
+    return (int64_t)(k >> 6) * (256 * 64) + ((((k & 63) >> 4) ^ ((rr >> 2) & 3)) << 4) + (k & 15);
+}
+
+// The int8 image of ONE row (one whole wave; lane owns k = lane*4 .. +3 of every 256): writes the row's swizzled image at
+// dst (= row rr of its tile) and returns its scale, whether it holds a non-finite value, and sum (e - e^)^2 / sum e^2 over
+// the wave.  The shadow build (i8_shadow_kernel) and the in-place update (update_rows_kernel) both go through here.
+struct I8Row {
+    float se;
+    bool bad;
+    double d2, h2;
+};
+__device__ __forceinline__ I8Row i8_quantise_row(const float *__restrict__ src, int32_t D, int lane, int rr, int8_t *__restrict__ dst)
+{
+    float mx = 0.f;
+    bool bad = false;
+    for (int k = lane * 4; k < D; k += 256) {
+        const float4 v = *reinterpret_cast<const float4 *>(src + k);
+        mx = fmaxf(mx, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+        bad = bad || !(fabsf(v.x) <= 3.4028234663852886e38f) || !(fabsf(v.y) <= 3.4028234663852886e38f) ||
+              !(fabsf(v.z) <= 3.4028234663852886e38f) || !(fabsf(v.w) <= 3.4028234663852886e38f);
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d, 64));
+    bad = __any(bad);
+    const float se = (bad || mx == 0.f) ? 0.f : mx / 127.f;
+    const float inv = se > 0.f ? 1.f / se : 0.f;
+    double d2 = 0.0, h2 = 0.0;
+    for (int k = lane * 4; k < D; k += 256) {
+        const float4 v = *reinterpret_cast<const float4 *>(src + k);
+        const float x[4] = {v.x, v.y, v.z, v.w};
+        uint32_t packed = 0u;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            int q = se > 0.f ? __float2int_rn(x[e] * inv) : 0;
+            q = q > 127 ? 127 : (q < -127 ? -127 : q);
+            const double hat = (double)se * (double)q;
+            const double dl = (double)x[e] - hat;
+            d2 += dl * dl;
+            h2 += hat * hat;
+            packed |= ((uint32_t)(uint8_t)(int8_t)q) << (8 * e);
+        }
+        *reinterpret_cast<uint32_t *>(dst + i8_tiled_off(k, rr)) = packed;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) { d2 += __shfl_xor(d2, d, 64); h2 += __shfl_xor(h2, d, 64); }
+    I8Row r;
+    r.se = se; r.bad = bad; r.d2 = d2; r.h2 = h2;
+    return r;
+}
+
+// The two relative norms the bound needs, from a row's quantisation and its exact norm nb.
+__device__ __forceinline__ void i8_rel_norms(const I8Row &q, double nb, float &rel_err, float &rel_hat)
+{
+    if (!(nb > 0.0)) { rel_err = 0.f; rel_hat = 0.f; }                      // cosine is 0 for this row whatever the dot (:84)
+    else if (q.bad) { rel_err = __builtin_huge_valf(); rel_hat = 0.f; }      // never screened out
+    else {
+        rel_err = __double2float_ru(sqrt(q.d2 / nb) * 1.000001);
+        rel_hat = __double2float_ru(sqrt(q.h2 / nb) * 1.000001);
+    }
+}
+
+// rowf = {se, 0.7 (rel_err + 2^-22) rounded up, rel_hat, 0}: the row constants of the int8 GEMM's epilogue.
+__device__ __forceinline__ float4 i8_rowf_of(float scale, float rel_err, float rel_hat)
+{
+    float4 o;
+    o.x = scale;
+    o.y = __double2float_ru(0.7 * 1.000002 * ((double)rel_err * 1.0000003 + 2.4e-7) + 1e-9);
+    o.z = __double2float_ru((double)rel_hat * 1.000001);
+    o.w = 0.f;
+    return o;
+}
+
 // One wave per row: scale, int8 image (tiled, swizzled), and the two relative norms the bound needs.
 __global__ __launch_bounds__(256) void i8_shadow_kernel(const float *__restrict__ E, const double *__restrict__ norm_b, int64_t n_rows,
                                                         int64_t rows_padded, int32_t D, int8_t *__restrict__ out,
@@ -1222,51 +1298,13 @@ __global__ __launch_bounds__(256) void i8_shadow_kernel(const float *__restrict_
         int8_t *dst = out + (tile * KT) * (int64_t)(256 * 64) + rr * 64;
         if (row >= n_rows) {                                                // padding rows of the last tile
             for (int k = lane * 4; k < D; k += 256)
-                *reinterpret_cast<uint32_t *>(dst + (int64_t)(k >> 6) * (256 * 64) + ((((k & 63) >> 4) ^ ((rr >> 2) & 3)) << 4) + (k & 15)) = 0u;
+                *reinterpret_cast<uint32_t *>(dst + i8_tiled_off(k, rr)) = 0u;
             continue;
         }
-        const float *src = E + row * (int64_t)D;
-        float mx = 0.f;
-        bool bad = false;
-        for (int k = lane * 4; k < D; k += 256) {
-            const float4 v = *reinterpret_cast<const float4 *>(src + k);
-            mx = fmaxf(mx, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-            bad = bad || !(fabsf(v.x) <= 3.4028234663852886e38f) || !(fabsf(v.y) <= 3.4028234663852886e38f) ||
-                  !(fabsf(v.z) <= 3.4028234663852886e38f) || !(fabsf(v.w) <= 3.4028234663852886e38f);
-        }
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d, 64));
-        bad = __any(bad);
-        const float se = (bad || mx == 0.f) ? 0.f : mx / 127.f;
-        const float inv = se > 0.f ? 1.f / se : 0.f;
-        double d2 = 0.0, h2 = 0.0;
-        for (int k = lane * 4; k < D; k += 256) {
-            const float4 v = *reinterpret_cast<const float4 *>(src + k);
-            const float x[4] = {v.x, v.y, v.z, v.w};
-            uint32_t packed = 0u;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                int q = se > 0.f ? __float2int_rn(x[e] * inv) : 0;
-                q = q > 127 ? 127 : (q < -127 ? -127 : q);
-                const double hat = (double)se * (double)q;
-                const double dl = (double)x[e] - hat;
-                d2 += dl * dl;
-                h2 += hat * hat;
-                packed |= ((uint32_t)(uint8_t)(int8_t)q) << (8 * e);
-            }
-            *reinterpret_cast<uint32_t *>(dst + (int64_t)(k >> 6) * (256 * 64) + ((((k & 63) >> 4) ^ ((rr >> 2) & 3)) << 4) + (k & 15)) = packed;
-        }
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) { d2 += __shfl_xor(d2, d, 64); h2 += __shfl_xor(h2, d, 64); }
+        const I8Row q = i8_quantise_row(E + row * (int64_t)D, D, lane, rr, dst);
         if (lane == 0) {
-            const double nb = norm_b[row];
-            scale[row] = se;
-            if (!(nb > 0.0)) { rel_err[row] = 0.f; rel_hat[row] = 0.f; }     // cosine is 0 for this row whatever the dot (:84)
-            else if (bad) { rel_err[row] = __builtin_huge_valf(); rel_hat[row] = 0.f; }   // never screened out
-            else {
-                rel_err[row] = __double2float_ru(sqrt(d2 / nb) * 1.000001);
-                rel_hat[row] = __double2float_ru(sqrt(h2 / nb) * 1.000001);
-            }
+            scale[row] = q.se;
+            i8_rel_norms(q, norm_b[row], rel_err[row], rel_hat[row]);
         }
     }
 }
@@ -1367,18 +1405,12 @@ hipError_t launch_bf16_tiled(const float *X, int64_t n_rows, int32_t D, void *ou
     return hipGetLastError();
 }
 
-// rowf[r] = {se_r, 0.7 (rel_err + 2^-22) rounded up, rel_hat, 0}: the row constants of the int8 GEMM's epilogue.
+// rowf[r] = i8_rowf_of(scale[r], rel_err[r], rel_hat[r]) for every row.
 __global__ __launch_bounds__(256) void i8_rowf_kernel(const float *__restrict__ scale, const float *__restrict__ rel_err,
                                                       const float *__restrict__ rel_hat, int64_t n, float4 *__restrict__ out)
 {
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
-        float4 o;
-        o.x = scale[r];
-        o.y = __double2float_ru(0.7 * 1.000002 * ((double)rel_err[r] * 1.0000003 + 2.4e-7) + 1e-9);
-        o.z = __double2float_ru((double)rel_hat[r] * 1.000001);
-        o.w = 0.f;
-        out[r] = o;
-    }
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x)
+        out[r] = i8_rowf_of(scale[r], rel_err[r], rel_hat[r]);
 }
 
 hipError_t launch_i8_rowf(const float *scale, const float *rel_err, const float *rel_hat, int64_t n_rows, float4 *rowf, hipStream_t s)
@@ -1644,6 +1676,68 @@ hipError_t launch_i8_shadow(const float *E, const double *norm_b, int64_t n_rows
     const int64_t blocks = std::min<int64_t>((rows_padded + 3) / 4, 65536);
     hipLaunchKernelGGL(i8_shadow_kernel, dim3((unsigned)blocks), dim3(256), 0, s, E, norm_b, n_rows, rows_padded, D,
                        static_cast<int8_t *>(tiled), scale, rel_err, rel_hat);
+    return hipGetLastError();
+}
+
+// In-place update of sealed rows (orr_index_update_rows): one wave per target.  Target t takes staged row src[t] - src_base
+// of `rows` (compact [.][D] fp32) and its exact norm norms[src[t] - src_base] (launch_dot_exact, self_norm, over the staged
+// rows) to position pos[t], and leaves at that position what a seal and the shadow builds would have written there: the fp32
+// row, the norm, the int8 image with its scale / rel_err / rel_hat / rowf (i8 != nullptr) and the bf16 image (bf16 != nullptr).
+__global__ __launch_bounds__(256) void update_rows_kernel(const float *__restrict__ rows, const double *__restrict__ norms,
+                                                          const int64_t *__restrict__ pos, const int64_t *__restrict__ src,
+                                                          int64_t src_base, int64_t n_targets, int32_t D, float *__restrict__ E,
+                                                          double *__restrict__ norm_b, int8_t *__restrict__ i8, float *__restrict__ scale,
+                                                          float *__restrict__ rel_err, float *__restrict__ rel_hat,
+                                                          float4 *__restrict__ rowf, __bf16 *__restrict__ bf16)
+{
+    const int lane = threadIdx.x & 63;
+    for (int64_t t = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; t < n_targets; t += ((int64_t)gridDim.x * blockDim.x) >> 6) {
+        const int64_t j = src[t] - src_base, row = pos[t];
+        const float *x = rows + j * (int64_t)D;
+        float *dst = E + row * (int64_t)D;
+        if (D % 4 == 0) {
+            for (int k = lane * 4; k < D; k += 256) *reinterpret_cast<float4 *>(dst + k) = *reinterpret_cast<const float4 *>(x + k);
+        } else {                                                            // (rows of 3, 5, ... floats are not 16-byte aligned)
+            for (int k = lane; k < D; k += 64) dst[k] = x[k];
+        }
+        const double nb = norms[j];
+        if (lane == 0) norm_b[row] = nb;
+        const int64_t tile = row >> 8;
+        const int rr = (int)(row & 255);
+        if (i8) {                                                           // D % 128 == 0
+            const I8Row q = i8_quantise_row(x, D, lane, rr, i8 + (tile * (D / 64)) * (int64_t)(256 * 64) + rr * 64);
+            if (lane == 0) {
+                float re, rh;
+                i8_rel_norms(q, nb, re, rh);
+                scale[row] = q.se; rel_err[row] = re; rel_hat[row] = rh;
+                rowf[row] = i8_rowf_of(q.se, re, rh);
+            }
+        }
+        if (bf16) {                                                         // D % 64 == 0: the inverse of bf16_tiled_kernel's mapping
+            const int KT = D / kScBK;
+            for (int c8 = lane; c8 < D / 8; c8 += 64) {                     // 8 consecutive k: chunk c of K-tile kt
+                const int kt = c8 >> 2, c = c8 & 3;
+                const int64_t o = ((tile * KT + kt) << 10) | ((int64_t)rr << 2) | (int64_t)(c ^ ((rr >> 2) & 3));
+                const float4 v0 = *reinterpret_cast<const float4 *>(x + c8 * 8), v1 = *reinterpret_cast<const float4 *>(x + c8 * 8 + 4);
+                bf16x8 h;
+                h[0] = (__bf16)v0.x; h[1] = (__bf16)v0.y; h[2] = (__bf16)v0.z; h[3] = (__bf16)v0.w;
+                h[4] = (__bf16)v1.x; h[5] = (__bf16)v1.y; h[6] = (__bf16)v1.z; h[7] = (__bf16)v1.w;
+                *reinterpret_cast<bf16x8 *>(bf16 + o * 8) = h;
+            }
+        }
+    }
+}
+
+hipError_t launch_update_rows(const float *rows, const double *norms, const int64_t *pos, const int64_t *src, int64_t src_base,
+                              int64_t n_targets, int32_t D, float *E, double *norm_b, void *i8_tiled, float *i8_scale, float *i8_rel_err,
+                              float *i8_rel_hat, float4 *i8_rowf, void *bf16_tiled, hipStream_t s)
+{
+    if (n_targets <= 0) return hipSuccess;
+    if (D <= 0 || (i8_tiled && D % 128 != 0) || (bf16_tiled && D % 64 != 0)) return hipErrorInvalidValue;
+    if (i8_tiled && (!i8_scale || !i8_rel_err || !i8_rel_hat || !i8_rowf)) return hipErrorInvalidValue;
+    const int64_t blocks = std::min<int64_t>((n_targets + 3) / 4, 65536);
+    hipLaunchKernelGGL(update_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, s, rows, norms, pos, src, src_base, n_targets, D, E, norm_b,
+                       static_cast<int8_t *>(i8_tiled), i8_scale, i8_rel_err, i8_rel_hat, i8_rowf, static_cast<__bf16 *>(bf16_tiled));
     return hipGetLastError();
 }
 

@@ -130,6 +130,22 @@ class RecallIndex:
         N.check(N.hip.orr_index_delete_rows(self._h, int(ids.shape[0]), _ptr(ids), C.cast(C.byref(done), C.c_void_p)))
         return int(done.value)
 
+    def update_rows(self, row_ids, emb) -> int:
+        """orr_index_update_rows: the rows with these ids get new vectors in place (reindex; no reseal).  emb: [n, dim]
+        float32 (numpy or torch, host or device), or None: the rows lose their embedding.  Unknown and deleted ids are
+        skipped; returns how many rows were written."""
+        if not _is_torch(row_ids):
+            row_ids = np.ascontiguousarray(row_ids, dtype=np.int64).reshape(-1)
+        n = int(row_ids.shape[0])
+        if emb is not None and not _is_torch(emb):
+            emb = np.ascontiguousarray(emb, dtype=np.float32)
+        if emb is not None and (emb.ndim != 2 or int(emb.shape[0]) != n):
+            raise ValueError(f"update_rows: emb must be [{n}, dim], not {tuple(emb.shape)}")
+        dim = 0 if emb is None else int(emb.shape[1])
+        done = C.c_int64(0)
+        N.check(N.hip.orr_index_update_rows(self._h, n, _ptr(row_ids), dim, _ptr(emb), C.cast(C.byref(done), C.c_void_p)))
+        return int(done.value)
+
     @property
     def live_rows(self) -> int:
         return int(N.hip.orr_index_live_rows(self._h))

@@ -133,6 +133,10 @@ class RecallSearchService:
                 "compactions": int(N.host.orrh_service_compactions(self._h)),
                 "delta_merges": int(N.host.orrh_service_delta_merges(self._h))}
 
+    def UpdatedRows(self) -> int:
+        """Rows whose vectors a reindex replaced in place (same chunk ids, contents and CreatedAtTicks), so far."""
+        return int(N.host.orrh_service_updated_rows(self._h))
+
     def close(self):
         if self._h:
             N.host.orrh_service_destroy(self._h)
