@@ -1787,12 +1787,9 @@ struct BatchArgs {
     int64_t candidate_limit;
     int32_t topk = 10;             // the caller's k (two-stage floor); kprime is passed separately
     bool force_exact = false;      // skip the MFMA candidate pass (escalation after a failed certificate)
-    mutable bool used_mfma = false; // set by run_shard
     bool no_fuse = false;          // keep the batched pass unfused (retry after a candidate-buffer overflow)
     const double *norms_host = nullptr; // exact normA of every query, already computed by the caller (orr_cluster: once for all shards)
     orr_candidate *out_dev = nullptr;   // orr_search_shard with a device-resident `out`: the kernels write the records there
-    mutable bool used_fused = false;
-    mutable bool used_two_stage = false;   // the pass kept survivors in per-query buffers (idx->h_survivors holds their counts)
 };
 
 const orr_index *owner_of(const orr_index *idx) { return idx->parent ? idx->parent : idx; }
@@ -2160,35 +2157,338 @@ int run_large_k(orr_index *idx, const BatchArgs &a, int32_t kprime, int64_t n, c
 constexpr int kFinishFusedMaxB = 65535;
 constexpr int kRetryPass = 1;          // run_shard_once: a workspace was too small and has been enlarged; the same pass again
 
+// ---- One shard pass: a plan settled up front (plan_pass), then the stages that run it (run_shard_once).
+
+// Error of the approximate dot against the reference sum, relative to sum|q_k e_k| (<= |q||e| by Cauchy-Schwarz, which turns
+// it into a bound on the cosine).  The matrix cores' internal summation order and rounding mode are not documented, so every
+// addition (and every fp32 product) is charged one full unit in the last place, 2^-23, of a partial sum that never exceeds
+// sum|terms|:
+//   f32 MFMA    D products + D additions                      -> (2 D + 2) 2^-23
+//   split bf16  3 D additions of exact products, plus the dropped lo*lo and the second-order
+//               residuals of the split (u = 2^-8 per bf16 rounding) -> 3.1 u^2 + 3.06 D 2^-23
+//   plain bf16  (1 + u)^2 - 1 per product, D additions charged 2^-23 each -> 2^-7 (1 + 2^-9) + 1.02 D 2^-23
+// The int8 forms add their per-pair bound inside the kernels: the keys they leave are already lower bounds (kEpsI8).
+constexpr double kU23 = 1.1920928955078125e-07, kU16 = 1.52587890625e-05;
+constexpr double kEpsI8 = 1e-12;
+double cosine_bound(double eps_cos) { return 0.7 * 1.01 * eps_cos + 1e-12; }
+double eps_f32_mfma(int32_t D) { return cosine_bound((2.0 * (double)D + 2.0) * kU23); }
+double eps_split_bf16(int32_t D) { return cosine_bound(3.1 * kU16 + 3.06 * (double)D * kU23); }
+double eps_plain_bf16(int32_t D) { return cosine_bound(0.0078125 * (1.0 + 0.001953125) + 1.02 * (double)D * kU23); }
+
+// The form of one shard pass: which launches a batch gets (Timed names; DESIGN.md §10 has the table).
+enum class PassForm {
+    Empty,           // no participating row: trailer records only
+    Exact,           // dot_exact (or no vector side), row_consts, fuse_select, select_final
+    StreamMfma,      // gemv_mfma over all rows, then as Exact, then rescore_exact
+    SplitAll,        // gemm_dot_bf16x3 over all rows, then as Exact, then rescore_exact
+    SplitFused,      // gemm_dot_bf16x3 over a sampled prefix -> floor -> gemm_dot_bf16x3_fused over the rest, rescore_exact
+    TwoStageGemm,    // prefix -> floor -> screening GEMM over all rows into survivors' buffers -> exact tail
+    TwoStageStream,  // 1..8 queries: the streaming screen over the prefix -> floor, over all rows -> survivors -> exact tail
+    LargeK,          // k' beyond a selection list: run_large_k
+};
+
+// The screen of the two-stage forms over all rows, in the order of orr_search_stats.pass_mode: screen_i8_fused (K2j) in row
+// ranges, screen_gemv_i8 (K2i), screen_gemv_bf16 (K2g), screen_bf16_fused (K2c), gemm_dot_bf16x1_fused (fp32 rows converted).
+enum class Screen { None, I8Ranges, GemvI8, GemvBf16, Bf16Shadow, Bf16x1 };
+
+struct PassPlan {
+    PassForm form = PassForm::Exact;
+    Screen screen = Screen::None;
+    bool use_cos = false;
+    bool use_mfma = false;          // records carry no dot yet: filled in exactly on the device (an empty shard: the batch's choice)
+    bool q_on_device = false;       // the caller's query vectors are device memory
+    bool dev_norms = false;         // the queries' exact norms are computed on the device
+    bool prefix_i8 = false;         // the sampled prefix goes through the int8 screening GEMM: its keys are lower bounds
+    bool split_queries = false;     // the hi/lo bf16 split of the queries (launch_split_queries)
+    bool batched_score = false;     // per-row pieces once per batch
+    bool rowc_inline = false;       // the int8 stream forms the row constants in its epilogue (one or two uses per row)
+    int32_t fused_sample_seg = 0;   // > 0: fused epilogue behind a sampled prefix of that many segments
+    int64_t dotf_rows = 0;          // columns of the fp32 dots
+    int n_ranges = 1;               // row ranges of the int8 screening GEMM: [range_row[r], range_row[r + 1])
+    int64_t range_row[17] = {};
+    int32_t count_bits = 0;         // FusedEpilogue::count_bits
+    int prefix_floor_form = 0;      // fuse_select floor_only of the sampled prefix
+    double approx_eps = 0.0;        // bound of the approximate scores of the batched pass (and of the two-stage prefix)
+    double eps1 = 0.0;              // two-stage: bound of the screen over all rows (0: added inside the kernel)
+
+    bool two_stage() const {   // the pass keeps survivors in per-query buffers (idx->h_survivors holds their counts)
+        return form == PassForm::TwoStageGemm || form == PassForm::TwoStageStream;
+    }
+    bool stream() const { return form == PassForm::TwoStageStream; }
+    double plane_bytes_per_row(int32_t B) const { return (count_bits == 2 ? 8.0 : 16.0) * (double)((B + 31) / 32); }   // count words
+    bool fused() const { return fused_sample_seg > 0; }
+    int pass_mode() const { static constexpr int kMode[] = {0, 1, 1, 2, 2, 3}; return kMode[(int)screen]; }   // orr_search_stats
+};
+
+// Decides the form of one pass and what it derives, building the shadows it reads.
+int plan_pass(orr_index *idx, const BatchArgs &a, int32_t kprime, int64_t n, const std::vector<uint32_t> &qoff, PassPlan &p)
+{
+    const int32_t B = a.B, D = idx->dim;
+    const int32_t n_seg_all = (int32_t)((n + orr::kSelSegRows - 1) / orr::kSelSegRows);
+    const bool small_k = kprime <= orr::kSelWidth;
+    const bool floor_fits = !a.no_fuse && n_seg_all >= 48 && std::max<int32_t>(1, a.topk) <= orr::kSelWidth;
+    p = PassPlan{};
+    p.use_cos = a.dim > 0 && a.dim == D;
+    // 1..8 queries over a large shard with a shadow in place: the streaming form of the two-stage pass
+    // (stream over a sampled prefix -> floor, stream over all rows -> survivors, exact re-score)
+    bool stream = false, stream_i8 = false;
+    if (p.use_cos && !a.force_exact && idx->opt_two_stage == 1 && D % 64 == 0 && small_k && floor_fits && B <= orr::kMaxGemvScreenQ) {
+        ORR_TRY(ensure_i8_shadow(idx));
+        stream_i8 = idx->i8_ready;
+        if (!stream_i8) ORR_TRY(ensure_shadow(idx));
+        stream = stream_i8 || idx->shadow_ready;
+        // 5..8 queries on the int8 shadow: the screening GEMM with one live query tile is HBM-bound as well and
+        // reads the rows once, the stream would need two launches (1M x 3072: 8 queries 1.39 -> 0.97 ms)
+        if (stream_i8 && B > orr::kMaxI8ScreenQ) stream = stream_i8 = false;
+    }
+    // Batched candidate pass on the matrix cores (K2) + exact re-score (K6) from 5 queries up; below it the HBM-bound exact
+    // kernel is as fast and needs no second pass.
+    p.use_mfma = p.use_cos && !a.force_exact && (B >= 5 || stream) && D % 64 == 0 && small_k;
+    p.q_on_device = p.use_cos && is_device_pointer(a.q);
+    // Queries that already live on the device get their exact norms there (a handful of queries: the download and the
+    // host's pass cost less than the kernel's 3072-step chains).  The generic large-k path scores with host-side constants.
+    p.dev_norms = p.q_on_device && small_k && B >= 16 && !a.norms_host;
+    p.batched_score = (B >= 4 || stream) && small_k;
+    p.dotf_rows = n;
+    for (int r = 1; r <= 16; ++r) p.range_row[r] = n;
+    if (n == 0) { p.form = PassForm::Empty; return ORR_OK; }
+    if (!small_k) { p.form = PassForm::LargeK; return ORR_OK; }
+    if (!p.use_mfma) { p.form = PassForm::Exact; return ORR_OK; }
+    if (stream) {
+        // 1..8 queries: HBM-bound, so no GEMM tile: the streaming screen runs over the sample for the floor and then over
+        // all rows; the sample is scored by the stream itself, so its floor carries the stream's bound
+        p.form = PassForm::TwoStageStream;
+        p.screen = stream_i8 ? Screen::GemvI8 : Screen::GemvBf16;
+        p.fused_sample_seg = sample_segments(n_seg_all, n, a.topk, true, idx->sample_boost);
+        p.dotf_rows = (int64_t)p.fused_sample_seg * orr::kSelSegRows;
+        p.split_queries = !stream_i8;
+        p.rowc_inline = stream_i8;
+        p.approx_eps = stream_i8 ? kEpsI8 : eps_plain_bf16(D);
+        p.eps1 = stream_i8 ? 0.0 : eps_plain_bf16(D);
+        return ORR_OK;
+    }
+    // Where the two-stage pass applies it wins from the first MFMA batch on (1M x 3072 rows: 8 queries 2.19 ms against
+    // 2.35 ms streaming, 32 queries 2.28 against 3.07, 64 queries 2.4 against 6.3)
+    const bool two_stage = idx->opt_two_stage != 0 && floor_fits;
+    if (B <= 64 && !two_stage) {        // HBM-bound streaming form over all rows, 32 queries per launch
+        p.form = PassForm::StreamMfma;
+        p.approx_eps = eps_f32_mfma(D);
+        return ORR_OK;
+    }
+    // split bf16: queries split once; with enough rows the GEMM over everything behind a sampled prefix runs with the fused
+    // scoring epilogue (once the floor keys exist) and only the prefix's dots go through HBM
+    p.fused_sample_seg = ((idx->opt_fuse_epilogue || two_stage) && !a.no_fuse && n_seg_all >= 48)
+                             ? sample_segments(n_seg_all, n, a.topk, false, idx->sample_boost) : 0;
+    if (p.fused_sample_seg > 0) p.dotf_rows = (int64_t)p.fused_sample_seg * orr::kSelSegRows;
+    p.split_queries = true;
+    p.approx_eps = eps_split_bf16(D);
+    if (!two_stage) {
+        p.form = p.fused_sample_seg > 0 ? PassForm::SplitFused : PassForm::SplitAll;
+        return ORR_OK;
+    }
+    // ---- two-stage: floor from the k-th best score of the prefix; ONE screening product over ALL rows keeps every row
+    // that can still reach it; those are re-scored exactly; the best k' of them become the records.
+    p.form = PassForm::TwoStageGemm;
+    // Where the int8 shadow exists the prefix and the screen go through the int8 screening GEMM (integer dots out; the
+    // per-pair bound turns them into LOWER bounds of the scores), which reads a quarter of the bytes of the split pass and
+    // runs at twice its MFMA rate; else the screen runs on the bf16 shadow, else it converts the fp32 rows itself
+    if (idx->opt_two_stage == 1 && D % 128 == 0) {
+        ORR_TRY(ensure_i8_shadow(idx));
+        p.prefix_i8 = idx->i8_ready;
+    }
+    if (idx->opt_two_stage == 1 && !p.prefix_i8) ORR_TRY(ensure_shadow(idx));
+    p.screen = p.prefix_i8 ? Screen::I8Ranges : (idx->opt_two_stage == 1 && idx->shadow_ready) ? Screen::Bf16Shadow : Screen::Bf16x1;
+    if (p.prefix_i8) {
+        p.split_queries = false;
+        p.approx_eps = kEpsI8;
+    } else {
+        p.eps1 = eps_plain_bf16(D);
+    }
+    // the prefix's floor: 0 its rows ranked in full; 1 per-lane maxima, sorted; 2 wave maxima, nothing sorted (where 16 per
+    // segment are at least 8 k candidates per query)
+    static const char *prefix_env = getenv("ORR_PREFIX_FULL_RANKING");        // =1: form 0; =2: form 1 (A/B)
+    p.prefix_floor_form = (prefix_env && atoi(prefix_env) == 1) ? 0
+                          : ((int64_t)p.fused_sample_seg * 16 >= 8 * (int64_t)std::max<int32_t>(1, a.topk) && !(prefix_env && atoi(prefix_env) == 2)) ? 2 : 1;
+    // Large shards go through the int8 screening GEMM in FOUR ROW RANGES: only the first range's count words are formed
+    // in front of the GEMM; those of the later ranges are formed on the keyword stream while the earlier ranges are
+    // multiplied (the GEMM leaves half of the HBM bandwidth unused; in front of it the count words were 0.5 of the
+    // 1.6 ms a 10M-row, 256-query batch spends before its GEMM starts, 2.7 of 6.9 ms at 12.5M rows x 1024 queries).
+    const bool has_terms = qoff[(size_t)B] > qoff[0];
+    if (has_terms && p.prefix_i8 && n >= (int64_t)2000000) {
+        // four ranges, eight for more than 256 queries (the first range's count words sit in front of the GEMM: 4 planes
+        // x 4 B per row and 32 queries)
+        p.n_ranges = B > 256 ? 8 : 4;                     // (12.5M rows x 1024 queries: 43.0 / 41.1 / 41.0 ms per batch with 4 / 8 / 16)
+        // (boundaries on whole rounds of the persistent GEMM -- 256 workgroups x 256-row tiles: every workgroup of a
+        // launch then multiplies the same number of tiles; only the last range ends on a partial round)
+        constexpr int64_t kRound = 256 * 256;
+        for (int r = 1; r < p.n_ranges; ++r) p.range_row[r] = (n * r / p.n_ranges + kRound / 2) / kRound * kRound;
+    }
+    // two-bit count words where every query has at most three terms and the 16 x 16 x 64 form screens (its epilogue reads
+    // them): half the words written and read
+    uint32_t max_terms = 0;
+    for (int32_t b = 0; b < B; ++b) max_terms = std::max(max_terms, qoff[(size_t)b + 1] - qoff[(size_t)b]);
+    if (has_terms && max_terms <= 3 && p.prefix_i8 && orr::screen_i8_uses_tile16(B, n, D, (n + 63) / 64 * 64) && !getenv("ORR_COUNT_BITS4"))
+        p.count_bits = 2;
+    return ORR_OK;
+}
+
+// What the stages of one pass hand on to each other.
+struct PassIo {
+    const float *d_q = nullptr;         // the query vectors on the device
+    double *d_dot = nullptr;            // exact dots [B][n]
+    float *d_dotf = nullptr;            // approximate dots [B][dotf_rows]
+    orr::KwView kw{nullptr, 0, nullptr, nullptr, nullptr};
+    const double2 *d_rowc = nullptr;    // per-row selection constants, or null
+    orr_candidate *d_cand = nullptr;    // the records [B][kprime + 1]
+    bool direct_host = false;           // d_cand is pinned host memory
+};
+
+// The int8 image of the queries.  The stream's (gemm = false) has one error term and its launch clears the pass's counters;
+// the screening GEMM's has the second error term and is tiled like the rows.
+int launch_i8_query_image(orr_index *idx, const float *d_q, int32_t B, bool gemm, hipStream_t s)
+{
+    ORR_TRY(idx->ws_q8.reserve(2 * (size_t)B * idx->dim));
+    ORR_TRY(idx->ws_q8s1.reserve(sizeof(float) * (size_t)B));
+    if (!gemm) {
+        ORR_TRY(idx->ws_q8err.reserve(sizeof(double) * (size_t)B));
+        ORR_TRY(idx->ws_fcnt.reserve(sizeof(uint32_t) * 3 * (size_t)B));
+        HIP_TRY(orr::launch_i8_queries(d_q, B, idx->dim, idx->ws_q8.p, idx->ws_q8s1.as<float>(), idx->ws_q8err.as<double>(), s, nullptr,
+                                       idx->ws_fcnt.as<uint32_t>(), 3 * B));
+        return ORR_OK;
+    }
+    ORR_TRY(idx->ws_q8err.reserve(2 * sizeof(double) * (size_t)B));
+    ORR_TRY(idx->ws_qtiled.reserve(orr::i8_tiled_bytes(B, idx->dim)));
+    HIP_TRY(orr::launch_i8_queries(d_q, B, idx->dim, idx->ws_q8.p, idx->ws_q8s1.as<float>(), idx->ws_q8err.as<double>(), s,
+                                   idx->ws_q8err.as<double>() + B));
+    HIP_TRY(orr::launch_i8_tile_queries(idx->ws_q8.p, B, idx->dim, idx->ws_qtiled.p, s));
+    return ORR_OK;
+}
+
+// Stage 5: the cosine numerators -- exact fp64 dots (Exact, LargeK), fp32 dots of all rows (StreamMfma, SplitAll) or of the
+// sampled prefix (SplitFused, TwoStageGemm; the screening launch scores the rest).  The streaming form scores its prefix
+// in the stream itself: it only needs the split queries (bf16) or the int8 image (made in stage 3).
+int launch_numerators(orr_index *idx, const BatchArgs &a, const PassPlan &p, int64_t n, PassIo &io)
+{
+    if (!p.use_cos) return ORR_OK;
+    const int32_t B = a.B;
+    hipStream_t s = idx->stream;
+    auto split_queries = [&]() -> int {
+        ORR_TRY(idx->ws_qsplit.reserve(sizeof(float) * (size_t)B * idx->dim));
+        HIP_TRY(orr::launch_split_queries(io.d_q, B, idx->dim, idx->ws_qsplit.p, s));
+        return ORR_OK;
+    };
+    switch (p.form) {
+    case PassForm::Exact:
+    case PassForm::LargeK:
+        ORR_TRY(idx->ws_dot.reserve(sizeof(double) * (size_t)B * (size_t)n));
+        io.d_dot = idx->ws_dot.as<double>();
+        for (int32_t b0 = 0; b0 < B; b0 += orr::kMaxExactQ) {
+            const int32_t nq = std::min<int32_t>(orr::kMaxExactQ, B - b0);
+            Timed t(idx, "dot_exact", 4.0 * (double)n * idx->dim + 4.0 * nq * idx->dim + 8.0 * nq * (double)n);
+            HIP_TRY(orr::launch_dot_exact(idx->d_emb, n, idx->dim, io.d_q + (size_t)b0 * a.dim, nq, false,
+                                          io.d_dot + (size_t)b0 * n, n, s));
+        }
+        return ORR_OK;
+    case PassForm::TwoStageStream:
+        if (p.split_queries) ORR_TRY(split_queries());
+        return ORR_OK;
+    case PassForm::StreamMfma:
+        ORR_TRY(idx->ws_dotf.reserve(sizeof(float) * (size_t)B * (size_t)n));
+        io.d_dotf = idx->ws_dotf.as<float>();
+        for (int32_t b0 = 0; b0 < B; b0 += 32) {
+            const int32_t nq = std::min<int32_t>(32, B - b0);
+            Timed t(idx, "gemv_mfma", 4.0 * (double)n * idx->dim + 4.0 * (double)nq * idx->dim + 4.0 * (double)nq * (double)n);
+            HIP_TRY(orr::launch_gemv_mfma(io.d_q + (size_t)b0 * a.dim, nq, idx->d_emb, n, idx->dim, io.d_dotf + (size_t)b0 * n, n, s));
+        }
+        return ORR_OK;
+    default:                            // SplitAll, SplitFused, TwoStageGemm
+        break;
+    }
+    const int64_t dotf_rows = p.dotf_rows;
+    ORR_TRY(idx->ws_dotf.reserve(sizeof(float) * (size_t)B * (size_t)dotf_rows));
+    io.d_dotf = idx->ws_dotf.as<float>();
+    if (p.prefix_i8) {
+        ORR_TRY(launch_i8_query_image(idx, io.d_q, B, true, s));
+        const int64_t pre_rows = std::min<int64_t>(dotf_rows, n);
+        Timed t(idx, "screen_i8_prefix", 1.0 * (double)pre_rows * idx->dim + 1.0 * (double)B * idx->dim + 4.0 * (double)B * (double)pre_rows);
+        HIP_TRY(orr::launch_screen_i8_dots(idx->ws_qtiled.p, B, idx->emb_i8.p, pre_rows, idx->dim, io.d_dotf, dotf_rows, s));
+    } else {
+        ORR_TRY(split_queries());
+        Timed t(idx, "gemm_dot_bf16x3", 4.0 * (double)dotf_rows * idx->dim + 4.0 * (double)B * idx->dim + 4.0 * (double)B * (double)dotf_rows);
+        HIP_TRY(orr::launch_gemm_dot_bf16x3(idx->ws_qsplit.p, B, idx->d_emb, 0, dotf_rows, idx->dim, io.d_dotf, dotf_rows, nullptr, 3, s));
+    }
+    return ORR_OK;
+}
+
+// Stage 6: per-query constants (exact normA needs the vectors on the host, or comes from the device) and the per-row
+// selection constants, which do not depend on the keyword side: enqueued before the main stream waits for it.
+int launch_consts(orr_index *idx, const BatchArgs &a, const PassPlan &p, int64_t n, const std::vector<uint32_t> &qoff,
+                  bool download_pending, PassIo &io)
+{
+    const int32_t B = a.B;
+    hipStream_t s = idx->stream;
+    if (download_pending) HIP_TRY(hipEventSynchronize(idx->ev_q));
+    ORR_TRY(idx->pin_qc.reserve(sizeof(orr::QueryConst) * (size_t)B));
+    ORR_TRY(idx->ws_qc.reserve(sizeof(orr::QueryConst) * (size_t)B));
+    orr::QueryConst *qc = idx->pin_qc.as<orr::QueryConst>();
+    if (p.use_cos && !p.dev_norms) {
+        if (a.norms_host) memcpy(idx->h_norm_a.data(), a.norms_host, sizeof(double) * (size_t)B);
+        else exact_norms(idx->pin_q.as<float>(), B, a.dim, idx->h_norm_a.data());
+    }
+    for (int32_t b = 0; b < B; ++b) {
+        qc[b].use_cos = p.use_cos ? 1 : 0;
+        qc[b].norm_a = idx->h_norm_a[(size_t)b];
+        qc[b].n_terms = (int32_t)(qoff[b + 1] - qoff[b]);
+        qc[b].inv_n_terms = qc[b].n_terms > 0 ? 1.0 / (double)qc[b].n_terms : 0.0;
+        qc[b].inv_sqrt_na = 0.0;
+        if (p.batched_score && p.use_cos && !p.dev_norms) {
+            if (qc[b].norm_a <= 0.0) qc[b].use_cos = 0;                    // guard :84 -> cosine 0 for every row
+            else qc[b].inv_sqrt_na = 1.0 / std::sqrt(qc[b].norm_a);        // NaN stays NaN
+        }
+    }
+    if (p.dev_norms) {        // (the kernel that adds the norms reads the host's constants in place: no upload command)
+        HIP_TRY(hipStreamWaitEvent(s, idx->ev_q, 0));
+        HIP_TRY(orr::launch_patch_query_norms(idx->ws_qc.as<orr::QueryConst>(), idx->ws_norm_a.as<double>(), B, p.batched_score, s,
+                                              idx->pin_norm.as<double>(), qc));
+    } else {
+        HIP_TRY(hipMemcpyAsync(idx->ws_qc.p, qc, sizeof(orr::QueryConst) * (size_t)B, hipMemcpyHostToDevice, s));
+    }
+    if (p.batched_score && !p.rowc_inline) {
+        ORR_TRY(idx->ws_rowc.reserve(sizeof(double2) * (size_t)n));
+        Timed t(idx, "row_consts", 32.0 * (double)n);
+        HIP_TRY(orr::launch_row_consts(idx->d_norm_b, idx->d_created, a.now_ticks, n, idx->ws_rowc.as<double2>(), s));
+        io.d_rowc = idx->ws_rowc.as<double2>();
+    }
+    return ORR_OK;
+}
+
 // The tail of the two-stage pass: exact re-score of every buffered survivor (fp32 master, reference arithmetic), the best k' of
 // them as records with their exact dots.  dim % 256 == 0: finish_survivors (four lanes per survivor, or a wave per survivor for
 // the smallest batches; the workgroup that draws a query's last ticket -- or a second launch -- merges its lists and writes the
 // records, straight into pinned host memory when the record set is small); else four launches.  The survivors' counts go back
 // with the records (idx->pin_cnt).
-int two_stage_tail(orr_index *idx, const BatchArgs &a, int32_t kprime, int64_t n, const float *d_q, const orr::KwView &kw,
-                   const orr::FusedEpilogue &epi, uint32_t kCap, int32_t buf_lists, bool host_records, size_t rec_bytes,
-                   orr_candidate **d_cand_io, bool *direct_host_io, hipStream_t s)
+int two_stage_tail(orr_index *idx, const BatchArgs &a, int32_t kprime, int64_t n, PassIo &io, const orr::FusedEpilogue &epi,
+                   uint32_t kCap, int32_t buf_lists, bool host_records, size_t rec_bytes, hipStream_t s)
 {
     const int32_t B = a.B;
-    orr_candidate *d_cand = *d_cand_io;
     ORR_TRY(idx->ws_fdot.reserve(sizeof(double) * (size_t)B * kCap));
     ORR_TRY(idx->pin_cnt.reserve(sizeof(uint32_t) * (size_t)B));
     if (B <= kFinishFusedMaxB && idx->dim % 256 == 0) {
         // the tail in one launch; small record sets go straight into pinned host memory (they are final when written)
         if (host_records && !a.out_dev && rec_bytes <= (256u << 10)) {
             ORR_TRY(idx->pin_cand.reserve(rec_bytes));
-            d_cand = idx->pin_cand.as<orr_candidate>();
-            *direct_host_io = true;
+            io.d_cand = idx->pin_cand.as<orr_candidate>();
+            io.direct_host = true;
         }
         Timed t(idx, "finish_survivors", 0.0);
-        HIP_TRY(orr::launch_finish_survivors(idx->d_emb, idx->dim, d_q, B, idx->d_norm_b, idx->d_created, idx->d_row_ids, kw,
+        HIP_TRY(orr::launch_finish_survivors(idx->d_emb, idx->dim, io.d_q, B, idx->d_norm_b, idx->d_created, idx->d_row_ids, io.kw,
                                              idx->ws_qc.as<orr::QueryConst>(), a.now_ticks, epi.cnt, idx->ws_fcnt.as<uint32_t>() + 2 * B,
                                              kCap, epi.buf, idx->ws_fdot.as<double>(), idx->ws_sel.as<orr::SelEntry>(), kprime, n,
-                                             idx->row_base, idx->ws_tsL.as<double>(), d_cand, idx->pin_cnt.as<uint32_t>(), s));
+                                             idx->row_base, idx->ws_tsL.as<double>(), io.d_cand, idx->pin_cnt.as<uint32_t>(), s));
     } else {
         {
             Timed t(idx, "rescore_buffer_exact", 0.0);
-            HIP_TRY(orr::launch_rescore_buffer_exact(idx->d_emb, idx->dim, d_q, B, idx->d_norm_b, idx->d_created, kw,
+            HIP_TRY(orr::launch_rescore_buffer_exact(idx->d_emb, idx->dim, io.d_q, B, idx->d_norm_b, idx->d_created, io.kw,
                                                      idx->ws_qc.as<orr::QueryConst>(), a.now_ticks, epi.cnt, kCap, epi.buf,
                                                      idx->ws_fdot.as<double>(), s));
         }
@@ -2199,48 +2499,45 @@ int two_stage_tail(orr_index *idx, const BatchArgs &a, int32_t kprime, int64_t n
         {
             Timed t(idx, "select_final", (double)B * (double)buf_lists * orr::kSelWidth * sizeof(orr::SelEntry));
             HIP_TRY(orr::launch_select_final(idx->ws_sel.as<orr::SelEntry>(), buf_lists, B, kprime, n, idx->row_base,
-                                             nullptr, nullptr, 0, idx->d_norm_b, idx->d_created, idx->d_row_ids, kw,
-                                             0, 0.0, nullptr, epi.cnt, kCap, idx->ws_tsL.as<double>(), d_cand, s));
+                                             nullptr, nullptr, 0, idx->d_norm_b, idx->d_created, idx->d_row_ids, io.kw,
+                                             0, 0.0, nullptr, epi.cnt, kCap, idx->ws_tsL.as<double>(), io.d_cand, s));
         }
         {   // the records' exact dots come out of the buffer: no second K6 pass
             Timed t(idx, "records_dot_from_buffer", 0.0);
             HIP_TRY(orr::launch_records_dot_from_buffer(epi.buf, idx->ws_fdot.as<double>(), epi.cnt, kCap, B, kprime, idx->row_base,
-                                                        d_cand, s));
+                                                        io.d_cand, s));
         }
         // the survivors' counts go back with the records: per-query escalation and orr_index_search_stats
         HIP_TRY(hipMemcpyAsync(idx->pin_cnt.p, epi.cnt, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost, s));
     }
-    *d_cand_io = d_cand;
     return ORR_OK;
 }
 
-// The int8 screening GEMM (K2j) with the fused scoring epilogue over all participating rows, in n_ranges row ranges: the later
-// ranges' count words are formed on the keyword stream while the earlier ranges are multiplied (released when the main
-// stream gets here), every launch draws its output tiles from its own set of tickets.
-int screen_i8_in_ranges(orr_index *idx, const BatchArgs &a, int64_t n, const orr::KwView &kw, orr::FusedEpilogue epi, int n_ranges,
-                        const int64_t *range_row, double plane_bytes_per_row, hipStream_t s, bool tickets_cleared)
+// The int8 screening GEMM (K2j) with the fused scoring epilogue over all participating rows, in p.n_ranges row ranges: the
+// later ranges' count words are formed on the keyword stream while the earlier ranges are multiplied (released when the main
+// stream gets here), every launch draws its output tiles from its own set of tickets (cleared by fused_query_consts).
+int screen_i8_in_ranges(orr_index *idx, const BatchArgs &a, const PassPlan &p, int64_t n, const orr::KwView &kw,
+                        orr::FusedEpilogue epi, hipStream_t s)
 {
     const int32_t B = a.B;
+    const int64_t *range_row = p.range_row;
     // algorithmic bytes: the int8 rows once, per row its constants (rowc 16 B, i8_rowf 16 B) and, with query terms,
     // 16 B of count words per 32 queries; the query image once
-    if (n_ranges > 1) {
+    if (p.n_ranges > 1) {
         // the later ranges' count words: released when the main stream reaches the first range's GEMM
         hipStream_t k = idx->stream_kw;
         HIP_TRY(hipEventRecord(idx->ev_main_ready, s));
         HIP_TRY(hipStreamWaitEvent(k, idx->ev_main_ready, 0));
-        for (int r = 1; r < n_ranges; ++r) {
+        for (int r = 1; r < p.n_ranges; ++r) {
             {
-                Timed t(idx, "count_planes", plane_bytes_per_row * (double)(range_row[r + 1] - range_row[r]), k);
+                Timed t(idx, "count_planes", p.plane_bytes_per_row(B) * (double)(range_row[r + 1] - range_row[r]), k);
                 HIP_TRY(orr::launch_query_count_planes(kw, B, n, epi.plane_stride, idx->ws_fany.as<uint32_t>(), k, range_row[r],
                                                        range_row[r + 1], epi.count_bits == 2 ? 2 : 4));
             }
             HIP_TRY(hipEventRecord(idx->ev_range[r - 1], k));
         }
     }
-    // output-tile tickets of the 16 x 16 x 64 form: eight counters per launch, cleared once per pass
-    ORR_TRY(idx->ws_tickets.reserve(sizeof(uint32_t) * 8 * 16));
-    if (!tickets_cleared) HIP_TRY(hipMemsetAsync(idx->ws_tickets.p, 0, sizeof(uint32_t) * 8 * 16, s));
-    for (int r = 0; r < n_ranges; ++r) {
+    for (int r = 0; r < p.n_ranges; ++r) {
         if (r > 0) HIP_TRY(hipStreamWaitEvent(s, idx->ev_range[r - 1], 0));
         epi.tickets = idx->ws_tickets.as<uint32_t>() + 8 * r;
         const double rows_r = (double)(range_row[r + 1] - range_row[r]);
@@ -2251,18 +2548,285 @@ int screen_i8_in_ranges(orr_index *idx, const BatchArgs &a, int64_t n, const orr
     return ORR_OK;
 }
 
+// The two-stage forms after the prefix: the floor, the screen over all rows into the survivors' buffers, the exact tail.
+int screen_two_stage(orr_index *idx, const BatchArgs &a, const PassPlan &p, int32_t kprime, int64_t n, PassIo &io,
+                     orr::FusedEpilogue &epi, uint32_t kCap, int32_t buf_lists, int32_t lists_total, bool host_records, size_t rec_bytes)
+{
+    const int32_t B = a.B;
+    hipStream_t s = idx->stream;
+    const int32_t kth = std::max<int32_t>(1, a.topk);
+    unsigned long long *d_tau = idx->ws_tau.as<unsigned long long>();
+    ORR_TRY(idx->ws_tsL.reserve(sizeof(double) * (size_t)B));
+    ORR_TRY(idx->ws_tskey.reserve(sizeof(unsigned long long) * (size_t)B));
+    // the floor comes out of the sampling selection's own launch
+    orr::FloorOut floor;
+    floor.floor_key = idx->ws_tskey.as<unsigned long long>();
+    floor.L = idx->ws_tsL.as<double>();
+    floor.eps3 = p.approx_eps; floor.eps1 = p.eps1;
+    if (p.stream()) {
+        // the sample goes through the stream too: floor keys of 0 keep every sampled row, their
+        // approximate keys are sorted in lists of 64 and the k-th best one per query is the floor's base
+        const uint32_t cap_p = (uint32_t)p.dotf_rows;                 // a multiple of 4096
+        ORR_TRY(idx->ws_pbuf.reserve(sizeof(orr::SelEntry) * (size_t)B * cap_p));
+        if (idx->ws_zero.cap < sizeof(unsigned long long) * (size_t)B) {   // floor keys of 0, never written again
+            ORR_TRY(idx->ws_zero.reserve(sizeof(unsigned long long) * (size_t)std::max<int32_t>(B, 64)));
+            HIP_TRY(hipMemsetAsync(idx->ws_zero.p, 0, idx->ws_zero.cap, s));
+        }
+        const bool i8 = p.screen == Screen::GemvI8;
+        orr::FusedEpilogue pre = epi;
+        pre.tau = idx->ws_zero.as<unsigned long long>();
+        pre.buf = idx->ws_pbuf.as<orr::SelEntry>();
+        pre.cap = cap_p;
+        pre.cnt = idx->ws_fcnt.as<uint32_t>() + B;         // its own counters: one clearing for both launches
+        const int64_t pre_rows = std::min<int64_t>(p.dotf_rows, n);
+        const bool pre_lists = i8 && orr::screen_gemv_i8_prefix_makes_lists(idx->dim);   // sorted lists straight from the kernel
+        ORR_TRY(idx->ws_psel.reserve(sizeof(orr::SelEntry) * (size_t)B * cap_p));
+        if (pre_lists) pre.buf = idx->ws_psel.as<orr::SelEntry>();
+        {
+            Timed t(idx, "screen_gemv_prefix", (i8 ? 1.0 : 2.0) * (double)p.dotf_rows * idx->dim + 2.0 * (double)B * idx->dim);
+            if (i8)
+                HIP_TRY(orr::launch_screen_gemv_i8(idx->ws_q8.p, idx->ws_q8s1.as<float>(), idx->ws_q8err.as<double>(), B, idx->emb_i8.p,
+                                                   idx->i8_scale.as<float>(), idx->i8_rel_err.as<float>(), idx->i8_rel_hat.as<float>(),
+                                                   idx->d_norm_b, idx->d_created, a.now_ticks, pre_rows, idx->dim, pre, true, s));
+            else
+                HIP_TRY(orr::launch_screen_gemv_bf16(idx->ws_qsplit.p, B, idx->emb_shadow.p, pre_rows, idx->dim, pre, s));
+        }
+        {   // lists of 64 sorted in parallel (by the int8 stream itself where it can), then the k-th best key per query
+            Timed t(idx, "select_floor", 0.0);
+            const int32_t lists_all = (int32_t)(cap_p / orr::kSelWidth);
+            const int32_t lists_p = pre_lists ? (int32_t)((pre_rows + orr::kSelWidth - 1) / orr::kSelWidth) : lists_all;
+            if (!pre_lists)
+                HIP_TRY(orr::launch_buffer_to_lists(pre.buf, pre.cnt, cap_p, B, 0, lists_all, idx->ws_psel.as<orr::SelEntry>(), s));
+            HIP_TRY(orr::launch_select_final_sample(idx->ws_psel.as<orr::SelEntry>(), lists_all, lists_p, B, kth, d_tau, s, floor));
+        }
+    } else {
+        {
+            Timed t(idx, "select_floor", 0.0);
+            HIP_TRY(orr::launch_select_final_sample(idx->ws_sel.as<orr::SelEntry>(), lists_total, p.fused_sample_seg, B, kth, d_tau, s, floor,
+                                                    p.prefix_floor_form == 2 ? 1 : 0));
+        }
+        const bool gemm_i8 = p.screen == Screen::I8Ranges;
+        if (gemm_i8) {
+            epi.i8_rowf = idx->i8_rowf.as<float4>();
+            epi.i8_qs1 = idx->ws_q8s1.as<float>();
+        }
+        // (ws_fqf holds two arrays of B: qf, and behind it the NaN-safe copy the 16 x 16 x 64 form stages; the streaming
+        // kernels score in fp64 directly, no fp32 pre-filter constants)
+        HIP_TRY(orr::launch_fused_query_consts(idx->ws_qc.as<orr::QueryConst>(), idx->ws_tskey.as<unsigned long long>(), B,
+                                               idx->ws_fqf.as<float4>(), s, gemm_i8 ? idx->ws_q8s1.as<float>() : nullptr,
+                                               gemm_i8 ? idx->ws_q8err.as<double>() + B : nullptr,
+                                               gemm_i8 ? idx->ws_fqf.as<float4>() + B : nullptr,
+                                               idx->ws_fcnt.as<uint32_t>(), 3 * B, idx->ws_tickets.as<uint32_t>(), 8 * 16));
+        epi.qf16 = gemm_i8 ? idx->ws_fqf.as<float4>() + B : nullptr;
+    }
+    epi.tau = idx->ws_tskey.as<unsigned long long>();
+    if (p.screen == Screen::I8Ranges) {
+        ORR_TRY(screen_i8_in_ranges(idx, a, p, n, io.kw, epi, s));
+    } else if (p.screen == Screen::GemvI8) {
+        Timed t(idx, "screen_gemv_i8", 1.0 * (double)n * idx->dim + 28.0 * (double)n + 2.0 * (double)B * idx->dim);   // per row: scale, two relative norms (12 B), normB and created (16 B)
+        HIP_TRY(orr::launch_screen_gemv_i8(idx->ws_q8.p, idx->ws_q8s1.as<float>(), idx->ws_q8err.as<double>(), B, idx->emb_i8.p,
+                                           idx->i8_scale.as<float>(), idx->i8_rel_err.as<float>(), idx->i8_rel_hat.as<float>(),
+                                           idx->d_norm_b, idx->d_created, a.now_ticks, n, idx->dim, epi, false, s));
+    } else if (p.screen == Screen::GemvBf16) {
+        Timed t(idx, "screen_gemv_bf16", 2.0 * (double)n * idx->dim + 2.0 * (double)B * idx->dim);
+        HIP_TRY(orr::launch_screen_gemv_bf16(idx->ws_qsplit.p, B, idx->emb_shadow.p, n, idx->dim, epi, s));
+    } else if (p.screen == Screen::Bf16Shadow) {
+        ORR_TRY(idx->ws_qtiled.reserve(orr::bf16_tiled_bytes(B, idx->dim)));
+        HIP_TRY(orr::launch_bf16_tiled(io.d_q, B, idx->dim, idx->ws_qtiled.p, s));
+        Timed t(idx, "screen_bf16_fused", 2.0 * (double)n * idx->dim + 2.0 * (double)B * idx->dim);
+        HIP_TRY(orr::launch_screen_bf16(idx->ws_qtiled.p, B, idx->emb_shadow.p, 0, n, idx->dim, nullptr, 0, &epi, s));
+    } else {
+        Timed t(idx, "gemm_dot_bf16x1_fused", 4.0 * (double)n * idx->dim + 2.0 * (double)B * idx->dim);
+        HIP_TRY(orr::launch_gemm_dot_bf16x3(idx->ws_qsplit.p, B, idx->d_emb, 0, n, idx->dim, nullptr, 0, &epi, 1, s));
+    }
+    return two_stage_tail(idx, a, kprime, n, io, epi, kCap, buf_lists, host_records, rec_bytes, s);
+}
+
+// Stage 7 of the SplitFused and two-stage forms: prefix lists -> floor keys -> the screening launch with the scoring
+// epilogue -> survivors' buffers -> lists (SplitFused: the final merge reads prefix lists + buffer lists) or the exact tail.
+int select_fused(orr_index *idx, const BatchArgs &a, const PassPlan &p, int32_t kprime, int64_t n, PassIo &io, bool host_records,
+                 size_t rec_bytes)
+{
+    const int32_t B = a.B;
+    hipStream_t s = idx->stream;
+    uint32_t kCap = idx->survivor_cap;                              // survivors kept per query (a multiple of 64)
+    while (kCap > 8192 && (size_t)B * kCap * 40 > ((size_t)2 << 30)) kCap >>= 1;
+    idx->pass_cap = kCap;
+    const int32_t fss = p.fused_sample_seg;
+    const int32_t buf_lists = (int32_t)(kCap / orr::kSelWidth);
+    const int32_t lists_total = fss + buf_lists;
+    const int32_t finish_group = orr::finish_survivors_group(B, idx->dim);      // (finish_survivors' lists: one per group)
+    const int32_t lists_room = std::max<int32_t>(lists_total, finish_group ? (int32_t)(kCap / (uint32_t)finish_group) : 0);
+    ORR_TRY(idx->ws_sel.reserve(sizeof(orr::SelEntry) * (size_t)B * (size_t)lists_room * orr::kSelWidth));
+    ORR_TRY(idx->ws_tau.reserve(sizeof(unsigned long long) * (size_t)B));
+    ORR_TRY(idx->ws_fcnt.reserve(sizeof(uint32_t) * 3 * (size_t)B));      // [survivors][sampled prefix][workgroups done]
+    ORR_TRY(idx->ws_fbuf.reserve(sizeof(orr::SelEntry) * (size_t)B * kCap));
+    unsigned long long *d_tau = idx->ws_tau.as<unsigned long long>();
+    if (!p.stream()) {
+        Timed t(idx, "fuse_select", (double)B * (double)p.dotf_rows * 28.0);
+        orr::I8Prefix i8p;
+        if (p.prefix_i8) { i8p.rowf = idx->i8_rowf.as<float4>(); i8p.qs1 = idx->ws_q8s1.as<float>(); i8p.qerr2 = idx->ws_q8err.as<double>() + B; }
+        HIP_TRY(orr::launch_fuse_select(nullptr, io.d_dotf, p.dotf_rows, idx->d_norm_b, idx->d_created, io.d_rowc, io.kw,
+                                        idx->ws_qc.as<orr::QueryConst>(), a.now_ticks, std::min<int64_t>(p.dotf_rows, n), B, 0, fss,
+                                        nullptr, idx->ws_sel.as<orr::SelEntry>(), lists_total, s, i8p,
+                                        // two-stage: the prefix only yields the floor (the records come out of the survivors' buffers)
+                                        p.prefix_floor_form));
+    }
+    ORR_TRY(idx->ws_fqf.reserve(sizeof(float4) * 2 * (size_t)B));
+    orr::FusedEpilogue epi{};
+    epi.plane_stride = (n + 63) / 64 * 64;
+    if (io.kw.bitmaps && !p.stream()) {
+        ORR_TRY(idx->ws_fany.reserve(sizeof(uint32_t) * orr::kCountPlanes * (size_t)((B + 31) / 32) * (size_t)epi.plane_stride));
+        epi.count_bits = p.count_bits;
+        Timed t(idx, "count_planes", p.plane_bytes_per_row(B) * (double)(p.range_row[1] - p.range_row[0]));
+        HIP_TRY(orr::launch_query_count_planes(io.kw, B, n, epi.plane_stride, idx->ws_fany.as<uint32_t>(), s, 0, p.range_row[1],
+                                               epi.count_bits == 2 ? 2 : 4));
+        epi.count_planes = idx->ws_fany.as<uint32_t>();
+    }
+    epi.qf = idx->ws_fqf.as<float4>();
+    epi.rowc = io.d_rowc; epi.qc = idx->ws_qc.as<orr::QueryConst>(); epi.kw = io.kw;
+    epi.cnt = idx->ws_fcnt.as<uint32_t>(); epi.buf = idx->ws_fbuf.as<orr::SelEntry>(); epi.cap = kCap;
+    // (the counters are cleared by the query-constants launch in front of the screening launches; the int8 stream cleared
+    // them with the queries' images)
+    if (p.screen == Screen::GemvBf16) HIP_TRY(hipMemsetAsync(idx->ws_fcnt.p, 0, sizeof(uint32_t) * 3 * (size_t)B, s));
+    ORR_TRY(idx->ws_tickets.reserve(sizeof(uint32_t) * 8 * 16));
+    if (p.two_stage()) return screen_two_stage(idx, a, p, kprime, n, io, epi, kCap, buf_lists, lists_total, host_records, rec_bytes);
+
+    {
+        Timed t(idx, "select_floor", 0.0);
+        HIP_TRY(orr::launch_select_final_sample(idx->ws_sel.as<orr::SelEntry>(), lists_total, fss, B, kprime, d_tau, s));
+    }
+    HIP_TRY(orr::launch_fused_query_consts(idx->ws_qc.as<orr::QueryConst>(), d_tau, B, idx->ws_fqf.as<float4>(), s, nullptr, nullptr, nullptr,
+                                           idx->ws_fcnt.as<uint32_t>(), 3 * B));
+    epi.tau = d_tau;
+    {
+        Timed t(idx, "gemm_dot_bf16x3_fused", 4.0 * (double)(n - p.dotf_rows) * idx->dim + 4.0 * (double)B * idx->dim);
+        HIP_TRY(orr::launch_gemm_dot_bf16x3(idx->ws_qsplit.p, B, idx->d_emb, p.dotf_rows, n, idx->dim, nullptr, 0, &epi, 3, s));
+    }
+    {
+        Timed t(idx, "buffer_to_lists", 0.0);
+        HIP_TRY(orr::launch_buffer_to_lists(epi.buf, epi.cnt, kCap, B, fss, lists_total, idx->ws_sel.as<orr::SelEntry>(), s));
+    }
+    Timed t(idx, "select_final", (double)B * (double)lists_total * orr::kSelWidth * sizeof(orr::SelEntry));
+    HIP_TRY(orr::launch_select_final(idx->ws_sel.as<orr::SelEntry>(), lists_total, B, kprime, n, idx->row_base,
+                                     nullptr, nullptr, 0, idx->d_norm_b, idx->d_created, idx->d_row_ids, io.kw,
+                                     0, p.approx_eps, nullptr, epi.cnt, kCap, nullptr, io.d_cand, s));
+    return ORR_OK;
+}
+
+// Stage 7: selection for the form, then (batched pass) the records' dots again in the reference's own arithmetic (K6).  The
+// Exact, StreamMfma and SplitAll forms score and select over every row; large batches scan a prefix first, take its k'-th
+// best key per query as a floor, and let the rest of the corpus skip every 64-row batch that cannot beat it.
+int launch_selection(orr_index *idx, const BatchArgs &a, const PassPlan &p, int32_t kprime, int64_t n, PassIo &io, bool host_records,
+                     size_t rec_bytes)
+{
+    const int32_t B = a.B;
+    hipStream_t s = idx->stream;
+    if (p.form == PassForm::LargeK)
+        return run_large_k(idx, a, kprime, n, io.d_dot, io.kw, idx->pin_qc.as<orr::QueryConst>(), io.d_cand, s);
+    const int64_t n_seg = (n + orr::kSelSegRows - 1) / orr::kSelSegRows;
+    const int32_t n_seg32 = (int32_t)n_seg;
+    ORR_TRY(idx->ws_sel.reserve(sizeof(orr::SelEntry) * (size_t)B * (size_t)n_seg * orr::kSelWidth));
+    if (p.fused()) {
+        ORR_TRY(select_fused(idx, a, p, kprime, n, io, host_records, rec_bytes));
+    } else {
+        const orr::QueryConst *qc = idx->ws_qc.as<orr::QueryConst>();
+        unsigned long long *d_tau = nullptr;
+        const int32_t sample_seg = (B >= 8 && n_seg32 >= 48) ? std::min<int32_t>(64, std::max<int32_t>(16, n_seg32 / 16)) : 0;
+        if (sample_seg > 0) {
+            ORR_TRY(idx->ws_tau.reserve(sizeof(unsigned long long) * (size_t)B));
+            d_tau = idx->ws_tau.as<unsigned long long>();
+            {
+                Timed t(idx, "fuse_select", (double)B * (double)sample_seg * orr::kSelSegRows * 28.0);
+                HIP_TRY(orr::launch_fuse_select(io.d_dot, io.d_dotf, n, idx->d_norm_b, idx->d_created, io.d_rowc, io.kw, qc, a.now_ticks,
+                                                n, B, 0, sample_seg, nullptr, idx->ws_sel.as<orr::SelEntry>(), 0, s));
+            }
+            Timed t(idx, "select_floor", 0.0);
+            HIP_TRY(orr::launch_select_final_sample(idx->ws_sel.as<orr::SelEntry>(), n_seg32, sample_seg, B, kprime, d_tau, s));
+        }
+        {
+            Timed t(idx, "fuse_select", (double)B * (double)n * (8.0 * (p.use_cos ? 1 : 0) + 8.0 + 8.0));
+            HIP_TRY(orr::launch_fuse_select(io.d_dot, io.d_dotf, n, idx->d_norm_b, idx->d_created, io.d_rowc, io.kw, qc, a.now_ticks,
+                                            n, B, sample_seg, n_seg32 - sample_seg, d_tau, idx->ws_sel.as<orr::SelEntry>(), 0, s));
+        }
+        Timed t(idx, "select_final", (double)B * (double)n_seg * orr::kSelWidth * sizeof(orr::SelEntry));
+        HIP_TRY(orr::launch_select_final(idx->ws_sel.as<orr::SelEntry>(), n_seg32, B, kprime, n, idx->row_base,
+                                         io.d_dot, io.d_dotf, n, idx->d_norm_b, idx->d_created, idx->d_row_ids, io.kw,
+                                         p.use_mfma ? 0 : 1, p.approx_eps, nullptr, nullptr, 0u, nullptr, io.d_cand, s));
+    }
+    if (p.use_mfma && !p.two_stage()) {
+        Timed t(idx, "rescore_exact", (double)B * kprime * 4.0 * idx->dim);
+        HIP_TRY(orr::launch_rescore_exact(idx->d_emb, idx->dim, io.d_q, B, kprime, idx->row_base, io.d_cand, s));
+    }
+    return ORR_OK;
+}
+
+// Stage 9: wait for the pass; clear the keyword side's bitmaps and counters for the next search; statistics.  kRetryPass:
+// the keyword hit list was too short and has grown, this pass's records are discarded.
+int finish_pass(orr_index *idx, const BatchArgs &a, const PassPlan &p, const KwSide &kws, uint32_t n_terms_total)
+{
+    const int32_t B = a.B;
+    HIP_TRY(hipStreamSynchronize(idx->stream));
+    if (kws.bm_bytes) {        // every kernel that read the bitmaps is done: clear them for the next search
+        if (kws.bm_bytes >= ((size_t)16 << 20)) {   // (small ones stay on the keyword stream: a cross-stream wait costs a one-query call more)
+            HIP_TRY(hipMemsetAsync(idx->ws_bitmaps.p, 0, kws.bm_bytes, idx->stream_aux));
+            HIP_TRY(hipEventRecord(idx->ev_bm_clean, idx->stream_aux));
+            idx->bm_clean_pending = true;
+        } else {
+            HIP_TRY(hipMemsetAsync(idx->ws_bitmaps.p, 0, kws.bm_bytes, idx->stream_kw));
+        }
+        idx->bitmaps_clean = std::max(kws.bm_bytes, kws.bm_clean_before);
+    }
+    if (n_terms_total > 0 && idx->ws_counter.p) {   // ... and the keyword chain's counters (two memsets less in front of the next chain)
+        HIP_TRY(hipMemsetAsync(idx->ws_counter.p, 0, sizeof(unsigned long long), idx->stream_kw));
+        if (idx->ws_kwalias.p) HIP_TRY(hipMemsetAsync(idx->ws_kwalias.p, 0, idx->ws_kwalias.cap, idx->stream_kw));
+        idx->kw_counters_clean = true;
+        idx->kw_counters_of[0] = idx->ws_counter.p;
+        idx->kw_counters_of[1] = idx->ws_kwalias.p;
+    }
+    if (p.dev_norms) memcpy(idx->h_norm_a.data(), idx->pin_norm.p, sizeof(double) * (size_t)B);
+    if (n_terms_total > 0) {
+        idx->sstats.kw_hits_total += (int64_t)(*idx->pin_kwcnt.as<unsigned long long>() >> 32);
+        idx->sstats.kw_passes += 1;
+    }
+    if (p.two_stage()) {
+        idx->h_survivors.assign(idx->pin_cnt.as<uint32_t>(), idx->pin_cnt.as<uint32_t>() + B);
+        uint64_t sum = 0;
+        for (uint32_t cnt : idx->h_survivors) sum += cnt;
+        const uint64_t mean = sum / (uint64_t)B;
+        if (mean > 4096 && idx->sample_boost < 16) idx->sample_boost *= 2;
+        else if (mean < 512 && idx->sample_boost > 1) idx->sample_boost /= 2;
+    }
+    g_ht.mark(4);
+    collect_events(idx);
+    if (kws.overflow_possible) {
+        // (the counter as expand_hits left it in pinned memory: the device copy is zeroed again behind the pass)
+        const unsigned long long cnt = *idx->pin_kwcnt.as<unsigned long long>();
+        const uint32_t hits = (uint32_t)(cnt >> 32);
+        if (hits > kws.max_hits) {
+            // the distinct terms of this batch match more vocabulary tokens than the hit list holds (short terms against a
+            // large vocabulary): the bitmaps are incomplete, so this pass's records are discarded; the list grows to the
+            // measured count and the pass runs again (the index keeps the larger list)
+            if ((uint64_t)hits * sizeof(orr::KwHit) > ((uint64_t)8 << 30))
+                return fail(ORR_ENOMEM, "keyword terms matched %u vocabulary tokens: a hit list of that size is refused (8 GiB)", hits);
+            idx->kw_hits_cap = hits + hits / 4 + 1024u;
+            return kRetryPass;
+        }
+    }
+    return ORR_OK;
+}
+
 // Device side of one batch: exact dots, keyword bitmaps, fused scores, selection.
 // Records ([B][kprime+1]) land in pinned host memory (*recs_host) when host_records is set
 // and they are small, otherwise in idx->ws_cand (*recs_host = nullptr).  *q_host points at
 // the query vectors in host memory (valid until the next call).  Caller holds the lock.
 int run_shard_once(orr_index *idx, const BatchArgs &a, int32_t kprime, bool host_records, const float **q_host,
-                   const orr_candidate **recs_host)
+                   const orr_candidate **recs_host, PassPlan &p)
 {
     g_ht.start();
     ORR_TRY(bind_device(idx));
     const int64_t n = participating_rows(idx, a.candidate_limit);
     const int32_t B = a.B;
-    const bool use_cos = a.dim > 0 && a.dim == idx->dim;
     hipStream_t s = idx->stream;
     if (q_host) *q_host = nullptr;
     if (recs_host) *recs_host = nullptr;
@@ -2273,69 +2837,41 @@ int run_shard_once(orr_index *idx, const BatchArgs &a, int32_t kprime, bool host
         if (qoff[b + 1] < qoff[b]) return fail(ORR_EINVAL, "query_term_off is not monotone at query %d", b);
         if (qoff[b + 1] - qoff[b] > 65535) return fail(ORR_EINVAL, "query %d has more than 65535 terms", b);
     }
-    const uint32_t t_begin = qoff[0], t_end = qoff[B];
-    const uint32_t n_terms_total = t_end - t_begin;
+    const uint32_t n_terms_total = qoff[B] - qoff[0];
     if (n_terms_total > 0 && (!a.term_off || !a.terms_utf8)) return fail(ORR_EINVAL, "terms are referenced but term_off/terms_utf8 is NULL");
 
-    // ---- record destination
-    const size_t rec_count = (size_t)B * ((size_t)kprime + 1);
-    const size_t rec_bytes = sizeof(orr_candidate) * rec_count;
-    // Batched candidate pass on the matrix cores (K2) + exact re-score (K6) from this batch size
-    // up; below it the HBM-bound exact kernel is as fast and needs no second pass.
-    constexpr int mfma_min_batch = 5;
-    // 1..8 queries over a large shard with a shadow in place: the streaming form of the two-stage pass
-    // (stream over a sampled prefix -> floor, stream over all rows -> survivors, exact re-score)
-    bool ts_stream = false, ts_i8 = false;
-    if (use_cos && !a.force_exact && !a.no_fuse && idx->opt_two_stage == 1 && idx->dim % 64 == 0 && kprime <= orr::kSelWidth &&
-        (n + orr::kSelSegRows - 1) / orr::kSelSegRows >= 48 && std::max<int32_t>(1, a.topk) <= orr::kSelWidth &&
-        B <= orr::kMaxGemvScreenQ) {
-        ORR_TRY(ensure_i8_shadow(idx));
-        ts_i8 = idx->i8_ready;
-        if (!ts_i8) ORR_TRY(ensure_shadow(idx));
-        ts_stream = ts_i8 || idx->shadow_ready;
-        // 5..8 queries on the int8 shadow: the screening GEMM with one live query tile is HBM-bound as well and
-        // reads the rows once, the stream would need two launches (1M x 3072: 8 queries 1.39 -> 0.97 ms)
-        if (ts_i8 && B > orr::kMaxI8ScreenQ) { ts_i8 = false; ts_stream = false; }
-    }
-    const bool use_mfma = use_cos && !a.force_exact && (B >= mfma_min_batch || ts_stream) && idx->dim % 64 == 0 && kprime <= orr::kSelWidth;
-    const bool approx_pass = use_mfma;                   // records carry no dot yet: filled in exactly on the device
-    a.used_mfma = approx_pass;
-    a.used_fused = false;
-    a.used_two_stage = false;
+    ORR_TRY(plan_pass(idx, a, kprime, n, qoff, p));
     idx->h_survivors.clear();
-    bool direct_host = host_records && !approx_pass && rec_bytes <= (256u << 10);
-    orr_candidate *d_cand = nullptr;
-    if (direct_host) {
+
+    // ---- 1. record destination
+    const size_t rec_bytes = sizeof(orr_candidate) * (size_t)B * ((size_t)kprime + 1);
+    PassIo io;
+    io.direct_host = host_records && !p.use_mfma && rec_bytes <= (256u << 10);
+    if (io.direct_host) {
         ORR_TRY(idx->pin_cand.reserve(rec_bytes));
-        d_cand = idx->pin_cand.as<orr_candidate>();        // pinned host memory is device-writable
+        io.d_cand = idx->pin_cand.as<orr_candidate>();        // pinned host memory is device-writable
     } else if (a.out_dev) {
-        d_cand = a.out_dev;
+        io.d_cand = a.out_dev;
     } else {
         ORR_TRY(idx->ws_cand.reserve(rec_bytes));
-        d_cand = idx->ws_cand.as<orr_candidate>();
+        io.d_cand = idx->ws_cand.as<orr_candidate>();
     }
 
-    // ---- query vectors: the dot kernel reads them where they are (device) or from one upload
-    const float *d_q = nullptr;
+    // ---- 2. query vectors: the kernels read them where they are (device) or from one upload; device-resident ones get their
+    // exact norms on the device (beside the first cosine kernel) or are downloaded for the host's pass
     bool q_download_pending = false;
-    // Queries that already live on the device get their exact norms there (the kernel that computes the rows' norms):
-    // no download of the vectors, no host pass over them.  The generic large-k path scores with host-side constants.
-    bool dev_norms = false;
     idx->h_norm_a.assign((size_t)B, 0.0);
-    if (use_cos) {
+    if (p.use_cos) {
         const size_t qbytes = sizeof(float) * (size_t)B * a.dim;
-        constexpr int dev_norm_min = 16;
-        if (is_device_pointer(a.q) && kprime <= orr::kSelWidth && B >= dev_norm_min && !a.norms_host) {
-            // (a handful of queries: the download and the host's pass cost less than the kernel's 3072-step chains)
-            d_q = a.q;
-            dev_norms = true;
+        if (p.dev_norms) {
+            io.d_q = a.q;
             ORR_TRY(idx->ws_norm_a.reserve(sizeof(double) * (size_t)B));
             ORR_TRY(idx->pin_norm.reserve(sizeof(double) * (size_t)B));
-            HIP_TRY(orr::launch_dot_exact(d_q, B, a.dim, nullptr, 1, true, idx->ws_norm_a.as<double>(), B, idx->stream_aux));   // beside the first cosine kernel
+            HIP_TRY(orr::launch_dot_exact(io.d_q, B, a.dim, nullptr, 1, true, idx->ws_norm_a.as<double>(), B, idx->stream_aux));
             HIP_TRY(hipEventRecord(idx->ev_q, idx->stream_aux));
-        } else if (is_device_pointer(a.q)) {
+        } else if (p.q_on_device) {
             ORR_TRY(idx->pin_q.reserve(qbytes));
-            d_q = a.q;
+            io.d_q = a.q;
             HIP_TRY(hipMemcpyAsync(idx->pin_q.p, a.q, qbytes, hipMemcpyDeviceToHost, idx->stream_kw));
             HIP_TRY(hipEventRecord(idx->ev_q, idx->stream_kw));
             q_download_pending = true;
@@ -2344,539 +2880,73 @@ int run_shard_once(orr_index *idx, const BatchArgs &a, int32_t kprime, bool host
             memcpy(idx->pin_q.p, a.q, qbytes);
             ORR_TRY(idx->ws_q.reserve(qbytes));
             HIP_TRY(hipMemcpyAsync(idx->ws_q.p, idx->pin_q.p, qbytes, hipMemcpyHostToDevice, s));
-            d_q = idx->ws_q.as<float>();
+            io.d_q = idx->ws_q.as<float>();
         }
-        if (q_host && !dev_norms) *q_host = idx->pin_q.as<float>();
+        if (q_host && !p.dev_norms) *q_host = idx->pin_q.as<float>();
     }
 
-    // 1..4 queries on the int8 shadow: their int8 images are the first thing the main stream needs and depend on nothing
-    // else, so that launch goes out before the host prepares the keyword side; it also clears the pass's counters
-    bool counters_cleared = false;
-    if (n > 0 && ts_stream && ts_i8) {
-        ORR_TRY(idx->ws_q8.reserve(2 * (size_t)B * idx->dim));
-        ORR_TRY(idx->ws_q8s1.reserve(sizeof(float) * (size_t)B));
-        ORR_TRY(idx->ws_q8err.reserve(sizeof(double) * (size_t)B));
-        ORR_TRY(idx->ws_fcnt.reserve(sizeof(uint32_t) * 3 * (size_t)B));
-        HIP_TRY(orr::launch_i8_queries(d_q, B, idx->dim, idx->ws_q8.p, idx->ws_q8s1.as<float>(), idx->ws_q8err.as<double>(), s, nullptr,
-                                       idx->ws_fcnt.as<uint32_t>(), 3 * B));
-        counters_cleared = true;
-    }
-
-    if (n == 0) {   // nothing on this shard takes part: empty records + trailers
-        std::vector<orr_candidate> empty(rec_count);
+    if (p.form == PassForm::Empty) {   // nothing on this shard takes part: empty records + trailers
+        std::vector<orr_candidate> empty((size_t)B * ((size_t)kprime + 1));
         for (auto &c : empty) { memset(&c, 0, sizeof(c)); c.row_id = -1; c.order_key = -1; }
         for (int32_t b = 0; b < B; ++b) {
             orr_candidate &t = empty[(size_t)b * (kprime + 1) + kprime];
             t.approx_score = -std::numeric_limits<double>::infinity();
             t.order_key = 0; t.matches = 0; t.flags = ORR_CAND_TRAILER;
         }
-        if (direct_host) memcpy(d_cand, empty.data(), rec_bytes);
-        else HIP_TRY(hipMemcpyAsync(d_cand, empty.data(), rec_bytes, hipMemcpyHostToDevice, s));
+        if (io.direct_host) memcpy(io.d_cand, empty.data(), rec_bytes);
+        else HIP_TRY(hipMemcpyAsync(io.d_cand, empty.data(), rec_bytes, hipMemcpyHostToDevice, s));
         HIP_TRY(hipStreamSynchronize(s));
-        if (q_download_pending || dev_norms) HIP_TRY(hipEventSynchronize(idx->ev_q));    // nothing reads the caller's vectors after the call
-        if (recs_host && direct_host) *recs_host = d_cand;
+        if (q_download_pending || p.dev_norms) HIP_TRY(hipEventSynchronize(idx->ev_q));    // nothing reads the caller's vectors after the call
+        if (recs_host && io.direct_host) *recs_host = io.d_cand;
         return ORR_OK;
     }
 
-    // ---- K3 keyword side first, on its own stream
+    // ---- 3. the int8 image of 1..4 queries on the int8 shadow: the first thing the main stream needs, dependent on nothing
+    // else, so that launch goes out before the host prepares the keyword side
+    if (p.screen == Screen::GemvI8) ORR_TRY(launch_i8_query_image(idx, io.d_q, B, false, s));
+
+    // ---- 4. K3 keyword side, on its own stream
     KwSide kws;
     ORR_TRY(launch_keyword_side(idx, a, qoff, kws));
-    const orr::KwView kw = kws.view;
-    const size_t bm_bytes = kws.bm_bytes, bm_clean_before = kws.bm_clean_before;
-    const bool kw_overflow_possible = kws.overflow_possible;
-    const uint32_t kw_max_hits = kws.max_hits;
-
+    io.kw = kws.view;
     g_ht.mark(1);
-    // the hi/lo bf16 split of the queries, launched in front of the first kernel that reads it (the int8 forms never do)
-    bool queries_split = false;
-    auto need_split = [&]() -> int {
-        if (queries_split) return ORR_OK;
-        queries_split = true;
-        ORR_TRY(idx->ws_qsplit.reserve(sizeof(float) * (size_t)B * idx->dim));
-        HIP_TRY(orr::launch_split_queries(d_q, B, idx->dim, idx->ws_qsplit.p, s));
-        return ORR_OK;
-    };
-    // ---- cosine numerators
-    double *d_dot = nullptr;
-    float *d_dotf = nullptr;
-    double approx_eps = 0.0;
-    bool bf16_split = false;
-    int32_t fused_sample_seg = 0;      // > 0: fused epilogue behind a sampled prefix of that many segments
-    bool two_stage = false;            // plain-bf16 first stage over all rows + exact second stage
-    bool records_have_dots = false;    // two-stage: exact dots copied from the survivors' buffer
-    bool ts_gemv = false;              // two-stage with the streaming screen (1..8 queries)
-    bool prefix_i8 = false;            // the sampled prefix went through the int8 screening GEMM: its keys are lower bounds
-    int pass_mode = 0;                 // orr_search_stats.pass_mode of this pass
-    int64_t dotf_rows = n;             // columns of d_dotf
-    if (use_cos && use_mfma) {
-        if (!ts_stream && B <= 64) {
-            ORR_TRY(idx->ws_dotf.reserve(sizeof(float) * (size_t)B * (size_t)n));
-            d_dotf = idx->ws_dotf.as<float>();
-        }
-        // Where the two-stage pass applies it wins from the first MFMA batch on (1M x 3072 rows: 8 queries 2.19 ms
-        // against 2.35 ms streaming, 32 queries 2.28 against 3.07, 64 queries 2.4 against 6.3); ORR_TS_MIN_BATCH moves that
-        const bool ts_eligible = idx->opt_two_stage != 0 && !a.no_fuse && (n + orr::kSelSegRows - 1) / orr::kSelSegRows >= 48 &&
-                                 std::max<int32_t>(1, a.topk) <= orr::kSelWidth;
-        constexpr int ts_min_batch = 5;
-        if (ts_stream) {
-            // 1..8 queries: HBM-bound, so no GEMM tile: the streaming screen (K2i on the int8 shadow, else K2g on the
-            // bf16 one) runs over the sample for the floor and then over all rows
-            ts_gemv = true;
-            two_stage = true;
-            const int32_t n_seg_all = (int32_t)((n + orr::kSelSegRows - 1) / orr::kSelSegRows);
-            fused_sample_seg = sample_segments(n_seg_all, n, a.topk, true, idx->sample_boost);
-            dotf_rows = (int64_t)fused_sample_seg * orr::kSelSegRows;
-            if (ts_i8) {
-                // (quantised above, before the keyword side was prepared)
-            } else {
-                ORR_TRY(need_split());
-            }
-        } else if (B < ts_min_batch || (B <= 64 && !ts_eligible)) {   // HBM-bound streaming form over all rows, 32 queries per launch
-            for (int32_t b0 = 0; b0 < B; b0 += 32) {
-                const int32_t nq = std::min<int32_t>(32, B - b0);
-                Timed t(idx, "gemv_mfma", 4.0 * (double)n * idx->dim + 4.0 * (double)nq * idx->dim + 4.0 * (double)nq * (double)n);
-                HIP_TRY(orr::launch_gemv_mfma(d_q + (size_t)b0 * a.dim, nq, idx->d_emb, n, idx->dim, d_dotf + (size_t)b0 * n, n, s));
-            }
-        } else {
-            {   // split bf16: queries split once; with enough rows the GEMM over everything behind a
-                // sampled prefix runs with the fused scoring epilogue (launched further down, once the
-                // floor keys exist) and only the prefix's dots go through HBM
-                const int32_t n_seg_all = (int32_t)((n + orr::kSelSegRows - 1) / orr::kSelSegRows);
-                two_stage = idx->opt_two_stage != 0 && !a.no_fuse && n_seg_all >= 48 && std::max<int32_t>(1, a.topk) <= orr::kSelWidth;
-                fused_sample_seg = ((idx->opt_fuse_epilogue || two_stage) && !a.no_fuse && n_seg_all >= 48)
-                                       ? sample_segments(n_seg_all, n, a.topk, false, idx->sample_boost) : 0;
-                dotf_rows = fused_sample_seg > 0 ? (int64_t)fused_sample_seg * orr::kSelSegRows : n;
-                ORR_TRY(idx->ws_dotf.reserve(sizeof(float) * (size_t)B * (size_t)dotf_rows));
-                d_dotf = idx->ws_dotf.as<float>();
-                // Where the int8 shadow exists the sampled prefix goes through the int8 screening GEMM as well (integer
-                // dots out; fuse_select turns them into LOWER bounds of the scores with the per-pair bound), which reads
-                // a quarter of the bytes of the split pass and runs at twice its MFMA rate.
-                if (two_stage && fused_sample_seg > 0 && idx->opt_two_stage == 1 && idx->dim % 128 == 0) {
-                    ORR_TRY(ensure_i8_shadow(idx));
-                    prefix_i8 = idx->i8_ready;
-                }
-                if (prefix_i8) {
-                    ORR_TRY(idx->ws_q8.reserve(2 * (size_t)B * idx->dim));
-                    ORR_TRY(idx->ws_q8s1.reserve(sizeof(float) * (size_t)B));
-                    ORR_TRY(idx->ws_q8err.reserve(2 * sizeof(double) * (size_t)B));
-                    ORR_TRY(idx->ws_qtiled.reserve(orr::i8_tiled_bytes(B, idx->dim)));
-                    HIP_TRY(orr::launch_i8_queries(d_q, B, idx->dim, idx->ws_q8.p, idx->ws_q8s1.as<float>(), idx->ws_q8err.as<double>(), s,
-                                                   idx->ws_q8err.as<double>() + B));
-                    HIP_TRY(orr::launch_i8_tile_queries(idx->ws_q8.p, B, idx->dim, idx->ws_qtiled.p, s));
-                    const int64_t pre_rows = std::min<int64_t>(dotf_rows, n);
-                    Timed t(idx, "screen_i8_prefix", 1.0 * (double)pre_rows * idx->dim + 1.0 * (double)B * idx->dim + 4.0 * (double)B * (double)pre_rows);
-                    HIP_TRY(orr::launch_screen_i8_dots(idx->ws_qtiled.p, B, idx->emb_i8.p, pre_rows, idx->dim, d_dotf, dotf_rows, s));
-                } else {
-                    ORR_TRY(need_split());
-                    Timed t(idx, "gemm_dot_bf16x3", 4.0 * (double)dotf_rows * idx->dim + 4.0 * (double)B * idx->dim + 4.0 * (double)B * (double)dotf_rows);
-                    HIP_TRY(orr::launch_gemm_dot_bf16x3(idx->ws_qsplit.p, B, idx->d_emb, 0, dotf_rows, idx->dim, d_dotf, dotf_rows, nullptr, 3, s));
-                    bf16_split = true;
-                }
-            }
-        }
-        // Error of the approximate dot against the reference sum, relative to sum|q_k e_k| (<= |q||e| by
-        // Cauchy-Schwarz, which turns it into a bound on the cosine).  The matrix cores' internal
-        // summation order and rounding mode are not documented, so every addition (and every fp32
-        // product) is charged one full unit in the last place, 2^-23, of a partial sum that never
-        // exceeds sum|terms|:
-        //   f32 MFMA    D products + D additions                      -> (2 D + 2) 2^-23
-        //   split bf16  3 D additions of exact products, plus the dropped lo*lo and the second-order
-        //               residuals of the split (u = 2^-8 per bf16 rounding) -> 3.1 u^2 + 3.06 D 2^-23
-        const double u23 = 1.1920928955078125e-07, u16 = 1.52587890625e-05;
-        const double eps_cos = bf16_split ? 3.1 * u16 + 3.06 * (double)idx->dim * u23
-                                          : (2.0 * (double)idx->dim + 2.0) * u23;
-        approx_eps = 0.7 * 1.01 * eps_cos + 1e-12;
-        // streaming form: the prefix is scored by the plain-bf16 stream itself, so its floor carries that bound
-        if (ts_gemv) approx_eps = 0.7 * 1.01 * (0.0078125 * (1.0 + 0.001953125) + 1.02 * (double)idx->dim * u23) + 1e-12;
-        if (ts_i8 || prefix_i8) approx_eps = 1e-12;    // int8 forms: the sample's keys are already lower bounds
-    } else if (use_cos) {
-        ORR_TRY(idx->ws_dot.reserve(sizeof(double) * (size_t)B * (size_t)n));
-        d_dot = idx->ws_dot.as<double>();
-        for (int32_t b0 = 0; b0 < B; b0 += orr::kMaxExactQ) {
-            const int32_t nq = std::min<int32_t>(orr::kMaxExactQ, B - b0);
-            Timed t(idx, "dot_exact", 4.0 * (double)n * idx->dim + 4.0 * nq * idx->dim + 8.0 * nq * (double)n);
-            HIP_TRY(orr::launch_dot_exact(idx->d_emb, n, idx->dim, d_q + (size_t)b0 * a.dim, nq, false,
-                                          d_dot + (size_t)b0 * n, n, s));
-        }
-    }
 
+    // ---- 5. cosine numerators
+    ORR_TRY(launch_numerators(idx, a, p, n, io));
     g_ht.mark(0);
-    // ---- per-query constants (exact normA needs the vectors on the host)
-    const bool batched_score = (B >= 4 || ts_stream) && kprime <= orr::kSelWidth;     // per-row pieces once per batch
-    if (q_download_pending) HIP_TRY(hipEventSynchronize(idx->ev_q));
-    ORR_TRY(idx->pin_qc.reserve(sizeof(orr::QueryConst) * (size_t)B));
-    ORR_TRY(idx->ws_qc.reserve(sizeof(orr::QueryConst) * (size_t)B));
-    orr::QueryConst *qc = idx->pin_qc.as<orr::QueryConst>();
-    if (use_cos && !dev_norms) {
-        if (a.norms_host) memcpy(idx->h_norm_a.data(), a.norms_host, sizeof(double) * (size_t)B);
-        else exact_norms(idx->pin_q.as<float>(), B, a.dim, idx->h_norm_a.data());
-    }
-    for (int32_t b = 0; b < B; ++b) {
-        qc[b].use_cos = use_cos ? 1 : 0;
-        qc[b].norm_a = idx->h_norm_a[(size_t)b];
-        qc[b].n_terms = (int32_t)(qoff[b + 1] - qoff[b]);
-        qc[b].inv_n_terms = qc[b].n_terms > 0 ? 1.0 / (double)qc[b].n_terms : 0.0;
-        qc[b].inv_sqrt_na = 0.0;
-        if (batched_score && use_cos && !dev_norms) {
-            if (qc[b].norm_a <= 0.0) qc[b].use_cos = 0;                    // guard :84 -> cosine 0 for every row
-            else qc[b].inv_sqrt_na = 1.0 / std::sqrt(qc[b].norm_a);        // NaN stays NaN
-        }
-    }
-    if (dev_norms) {        // (the kernel that adds the norms reads the host's constants in place: no upload command)
-        HIP_TRY(hipStreamWaitEvent(s, idx->ev_q, 0));
-        HIP_TRY(orr::launch_patch_query_norms(idx->ws_qc.as<orr::QueryConst>(), idx->ws_norm_a.as<double>(), B, batched_score, s,
-                                              idx->pin_norm.as<double>(), qc));
-    } else {
-        HIP_TRY(hipMemcpyAsync(idx->ws_qc.p, qc, sizeof(orr::QueryConst) * (size_t)B, hipMemcpyHostToDevice, s));
-    }
-    // per-row selection constants do not depend on the keyword side: enqueued before the main stream waits for it
-    const double2 *d_rowc_early = nullptr;
-    const bool rowc_inline = ts_stream && ts_i8;        // the int8 stream forms them in its epilogue (one or two uses per row)
-    if (batched_score && kprime <= orr::kSelWidth && !rowc_inline) {
-        ORR_TRY(idx->ws_rowc.reserve(sizeof(double2) * (size_t)n));
-        Timed t(idx, "row_consts", 32.0 * (double)n);
-        HIP_TRY(orr::launch_row_consts(idx->d_norm_b, idx->d_created, a.now_ticks, n, idx->ws_rowc.as<double2>(), s));
-        d_rowc_early = idx->ws_rowc.as<double2>();
-    }
+
+    // ---- 6. query constants and row constants, then the keyword side joins the main stream
+    ORR_TRY(launch_consts(idx, a, p, n, qoff, q_download_pending, io));
     if (n_terms_total > 0) HIP_TRY(hipStreamWaitEvent(s, idx->ev_kw_done, 0));
     g_ht.mark(2);
 
-    // ---- K4/K5 fused score + selection
-    if (kprime <= orr::kSelWidth) {
-        const int64_t n_seg = (n + orr::kSelSegRows - 1) / orr::kSelSegRows;
-        ORR_TRY(idx->ws_sel.reserve(sizeof(orr::SelEntry) * (size_t)B * (size_t)n_seg * orr::kSelWidth));
-        const double2 *d_rowc = d_rowc_early;
-        const int32_t n_seg32 = (int32_t)n_seg;
-        unsigned long long *d_tau = nullptr;
-        if (fused_sample_seg > 0) {
-            // ---- fused batched pass: prefix lists -> floor keys -> GEMM with the scoring epilogue ->
-            // survivors' buffers -> lists; the final merge reads prefix lists + buffer lists
-            a.used_fused = true;
-            uint32_t kCap = idx->survivor_cap;                              // survivors kept per query (a multiple of 64)
-            while (kCap > 8192 && (size_t)B * kCap * 40 > ((size_t)2 << 30)) kCap >>= 1;
-            idx->pass_cap = kCap;
-            const int32_t buf_lists = (int32_t)(kCap / orr::kSelWidth);
-            const int32_t lists_total = fused_sample_seg + buf_lists;
-            const int32_t finish_group = orr::finish_survivors_group(B, idx->dim);      // (finish_survivors' lists: one per group)
-            const int32_t lists_room = std::max<int32_t>(lists_total, finish_group ? (int32_t)(kCap / (uint32_t)finish_group) : 0);
-            ORR_TRY(idx->ws_sel.reserve(sizeof(orr::SelEntry) * (size_t)B * (size_t)lists_room * orr::kSelWidth));
-            ORR_TRY(idx->ws_tau.reserve(sizeof(unsigned long long) * (size_t)B));
-            ORR_TRY(idx->ws_fcnt.reserve(sizeof(uint32_t) * 3 * (size_t)B));      // [survivors][sampled prefix][workgroups done]
-            ORR_TRY(idx->ws_fbuf.reserve(sizeof(orr::SelEntry) * (size_t)B * kCap));
-            d_tau = idx->ws_tau.as<unsigned long long>();
-            // 0: the prefix's rows are ranked in full; 1: per-lane maxima, sorted; 2: wave maxima, nothing sorted (where 16 per
-            // segment are at least 8 k candidates per query)
-            static const char *prefix_env = getenv("ORR_PREFIX_FULL_RANKING");        // =1: form 0; =2: form 1 (A/B)
-            const int prefix_floor_form = !(two_stage && d_rowc != nullptr) || (prefix_env && atoi(prefix_env) == 1) ? 0
-                                          : ((int64_t)fused_sample_seg * 16 >= 8 * (int64_t)std::max<int32_t>(1, a.topk) && !(prefix_env && atoi(prefix_env) == 2)) ? 2 : 1;
-            if (!ts_gemv) {
-                Timed t(idx, "fuse_select", (double)B * (double)dotf_rows * 28.0);
-                orr::I8Prefix i8p;
-                if (prefix_i8) { i8p.rowf = idx->i8_rowf.as<float4>(); i8p.qs1 = idx->ws_q8s1.as<float>(); i8p.qerr2 = idx->ws_q8err.as<double>() + B; }
-                HIP_TRY(orr::launch_fuse_select(nullptr, d_dotf, dotf_rows, idx->d_norm_b,
-                                                idx->d_created, d_rowc, kw, idx->ws_qc.as<orr::QueryConst>(), a.now_ticks,
-                                                std::min<int64_t>(dotf_rows, n), B, 0, fused_sample_seg, nullptr, idx->ws_sel.as<orr::SelEntry>(),
-                                                lists_total, s, i8p,
-                                                // two-stage: the prefix only yields the floor (the records come out of the survivors' buffers)
-                                                prefix_floor_form));
-            }
-            ORR_TRY(idx->ws_fqf.reserve(sizeof(float4) * 2 * (size_t)B));
-            orr::FusedEpilogue epi{};
-            epi.count_planes = nullptr;
-            epi.plane_stride = (n + 63) / 64 * 64;
-            // Large shards go through the int8 screening GEMM in FOUR ROW RANGES: only the first range's count words are formed
-            // in front of the GEMM; those of the later ranges are formed on the keyword stream while the earlier ranges are
-            // multiplied (the GEMM leaves half of the HBM bandwidth unused; in front of it the count words were 0.5 of the
-            // 1.6 ms a 10M-row, 256-query batch spends before its GEMM starts, 2.7 of 6.9 ms at 12.5M rows x 1024 queries).
-            int n_ranges = 1;
-            int64_t range_row[17];
-            range_row[0] = 0;
-            for (int r = 1; r <= 16; ++r) range_row[r] = n;
-            double plane_bytes_per_row = 4.0 * orr::kCountPlanes * (double)((B + 31) / 32);
-            if (kw.bitmaps && !ts_gemv) {
-                ORR_TRY(idx->ws_fany.reserve(sizeof(uint32_t) * orr::kCountPlanes * (size_t)((B + 31) / 32) * (size_t)epi.plane_stride));
-                if (prefix_i8 && two_stage && n >= (int64_t)2000000) {
-                    // four ranges, eight for more than 256 queries (the first range's count words sit in front of the GEMM: 4 planes
-                    // x 4 B per row and 32 queries)
-                    n_ranges = B > 256 ? 8 : 4;                     // (12.5M rows x 1024 queries: 43.0 / 41.1 / 41.0 ms per batch with 4 / 8 / 16)
-                    // (boundaries on whole rounds of the persistent GEMM -- 256 workgroups x 256-row tiles: every workgroup of a
-                    // launch then multiplies the same number of tiles; only the last range ends on a partial round)
-                    constexpr int64_t kRound = 256 * 256;
-                    for (int r = 1; r < n_ranges; ++r) range_row[r] = (n * r / n_ranges + kRound / 2) / kRound * kRound;
-                }
-                // two-bit count words where every query has at most three terms and the 16 x 16 x 64 form screens (its epilogue reads
-                // them): half the words written here and read there
-                uint32_t max_terms = 0;
-                for (int32_t b = 0; b < B; ++b) max_terms = std::max(max_terms, qoff[(size_t)b + 1] - qoff[(size_t)b]);
-                if (max_terms <= 3 && idx->opt_two_stage == 1 && two_stage && prefix_i8 && orr::screen_i8_uses_tile16(B, n, idx->dim, epi.plane_stride) &&
-                    !getenv("ORR_COUNT_BITS4"))
-                    epi.count_bits = 2;
-                plane_bytes_per_row = (epi.count_bits == 2 ? 8.0 : 16.0) * (double)((B + 31) / 32);
-                Timed t(idx, "count_planes", plane_bytes_per_row * (double)(range_row[1] - range_row[0]));
-                HIP_TRY(orr::launch_query_count_planes(kw, B, n, epi.plane_stride, idx->ws_fany.as<uint32_t>(), s, 0, range_row[1], epi.count_bits == 2 ? 2 : 4));
-                epi.count_planes = idx->ws_fany.as<uint32_t>();
-            }
-            epi.qf = idx->ws_fqf.as<float4>();
-            epi.rowc = d_rowc; epi.qc = idx->ws_qc.as<orr::QueryConst>(); epi.kw = kw;
-            epi.cnt = idx->ws_fcnt.as<uint32_t>(); epi.buf = idx->ws_fbuf.as<orr::SelEntry>(); epi.cap = kCap;
-            // (the counters are cleared by the query-constants launch in front of the screening launches; the streaming forms
-            // cleared them with the queries' images)
-            const bool clear_with_consts = !counters_cleared && !ts_gemv;
-            if (!counters_cleared && !clear_with_consts) HIP_TRY(hipMemsetAsync(idx->ws_fcnt.p, 0, sizeof(uint32_t) * 3 * (size_t)B, s));
-            ORR_TRY(idx->ws_tickets.reserve(sizeof(uint32_t) * 8 * 16));
-            if (two_stage) {
-                // ---- two-stage: floor from the k-th best split-pass score of the prefix; ONE plain-bf16
-                // product over ALL rows keeps every row that can still reach it; those are re-scored
-                // exactly; the best k' of them become the records
-                const int32_t kth = std::max<int32_t>(1, a.topk);
-                // plain bf16: (1 + u)^2 - 1 per product with u = 2^-8, D additions charged 2^-23 each
-                const bool i8_gemm_planned = idx->opt_two_stage == 1 && !ts_gemv && idx->dim % 128 == 0 &&
-                                             (idx->i8_ready || (!idx->i8_failed && !idx->is_view));
-                if (i8_gemm_planned) ORR_TRY(ensure_i8_shadow(idx));
-                const double eps1 = (ts_i8 || (i8_gemm_planned && idx->i8_ready)) ? 0.0     // int8 forms: the per-pair bound is added inside the kernel
-                                          : 0.7 * 1.01 * (0.0078125 * (1.0 + 0.001953125) + 1.02 * (double)idx->dim * 1.1920928955078125e-07) + 1e-12;
-                ORR_TRY(idx->ws_tsL.reserve(sizeof(double) * (size_t)B));
-                ORR_TRY(idx->ws_tskey.reserve(sizeof(unsigned long long) * (size_t)B));
-                // the floor comes out of the sampling selection's own launch
-                orr::FloorOut floor;
-                floor.floor_key = idx->ws_tskey.as<unsigned long long>();
-                floor.L = idx->ws_tsL.as<double>();
-                floor.eps3 = approx_eps; floor.eps1 = eps1;
-                if (ts_gemv) {
-                    // the sample goes through the stream too: floor keys of 0 keep every sampled row, their
-                    // approximate keys are sorted in lists of 64 and the k-th best one per query is the floor's base
-                    const uint32_t cap_p = (uint32_t)dotf_rows;                 // a multiple of 4096
-                    ORR_TRY(idx->ws_pbuf.reserve(sizeof(orr::SelEntry) * (size_t)B * cap_p));
-                    if (idx->ws_zero.cap < sizeof(unsigned long long) * (size_t)B) {   // floor keys of 0, never written again
-                        ORR_TRY(idx->ws_zero.reserve(sizeof(unsigned long long) * (size_t)std::max<int32_t>(B, 64)));
-                        HIP_TRY(hipMemsetAsync(idx->ws_zero.p, 0, idx->ws_zero.cap, s));
-                    }
-                    orr::FusedEpilogue pre = epi;
-                    pre.tau = idx->ws_zero.as<unsigned long long>();
-                    pre.buf = idx->ws_pbuf.as<orr::SelEntry>();
-                    pre.cap = cap_p;
-                    pre.cnt = idx->ws_fcnt.as<uint32_t>() + B;         // its own counters: one clearing for both launches
-                    const int64_t pre_rows = std::min<int64_t>(dotf_rows, n);
-                    const bool pre_lists = ts_i8 && orr::screen_gemv_i8_prefix_makes_lists(idx->dim);   // sorted lists straight from the kernel
-                    ORR_TRY(idx->ws_psel.reserve(sizeof(orr::SelEntry) * (size_t)B * cap_p));
-                    if (pre_lists) pre.buf = idx->ws_psel.as<orr::SelEntry>();
-                    if (!ts_i8) ORR_TRY(need_split());
-                    {
-                        Timed t(idx, "screen_gemv_prefix", (ts_i8 ? 1.0 : 2.0) * (double)dotf_rows * idx->dim + 2.0 * (double)B * idx->dim);
-                        if (ts_i8)
-                            HIP_TRY(orr::launch_screen_gemv_i8(idx->ws_q8.p, idx->ws_q8s1.as<float>(), idx->ws_q8err.as<double>(), B, idx->emb_i8.p,
-                                                               idx->i8_scale.as<float>(), idx->i8_rel_err.as<float>(), idx->i8_rel_hat.as<float>(),
-                                                               idx->d_norm_b, idx->d_created, a.now_ticks, pre_rows, idx->dim, pre, true, s));
-                        else
-                            HIP_TRY(orr::launch_screen_gemv_bf16(idx->ws_qsplit.p, B, idx->emb_shadow.p, pre_rows, idx->dim, pre, s));
-                    }
-                    {   // lists of 64 sorted in parallel (by the int8 stream itself where it can), then the k-th best key per query
-                        Timed t(idx, "select_floor", 0.0);
-                        const int32_t lists_all = (int32_t)(cap_p / orr::kSelWidth);
-                        const int32_t lists_p = pre_lists ? (int32_t)((pre_rows + orr::kSelWidth - 1) / orr::kSelWidth) : lists_all;
-                        if (!pre_lists)
-                            HIP_TRY(orr::launch_buffer_to_lists(pre.buf, pre.cnt, cap_p, B, 0, lists_all, idx->ws_psel.as<orr::SelEntry>(), s));
-                        HIP_TRY(orr::launch_select_final_sample(idx->ws_psel.as<orr::SelEntry>(), lists_all, lists_p, B, kth, d_tau, s, floor));
-                    }
-                } else {
-                    Timed t(idx, "select_floor", 0.0);
-                    HIP_TRY(orr::launch_select_final_sample(idx->ws_sel.as<orr::SelEntry>(), lists_total, fused_sample_seg, B, kth, d_tau, s, floor,
-                                                            prefix_floor_form == 2 ? 1 : 0));
-                }
-                // the screening GEMM runs on the int8 shadow where there is one (K2j), else on the bf16 shadow (K2c),
-                // else it converts the fp32 rows itself
-                bool gemm_i8 = false, tickets_cleared = false;
-                if (idx->opt_two_stage == 1 && !ts_gemv) {
-                    ORR_TRY(ensure_i8_shadow(idx));
-                    gemm_i8 = idx->i8_ready;
-                    if (!gemm_i8) ORR_TRY(ensure_shadow(idx));
-                }
-                if (gemm_i8) {
-                    if (!prefix_i8) {              // (the int8 prefix quantised and tiled the queries already)
-                        ORR_TRY(idx->ws_q8.reserve(2 * (size_t)B * idx->dim));
-                        ORR_TRY(idx->ws_q8s1.reserve(sizeof(float) * (size_t)B));
-                        ORR_TRY(idx->ws_q8err.reserve(2 * sizeof(double) * (size_t)B));
-                        HIP_TRY(orr::launch_i8_queries(d_q, B, idx->dim, idx->ws_q8.p, idx->ws_q8s1.as<float>(), idx->ws_q8err.as<double>(), s,
-                                                       idx->ws_q8err.as<double>() + B));
-                    }
-                    epi.i8_rowf = idx->i8_rowf.as<float4>();
-                    epi.i8_qs1 = idx->ws_q8s1.as<float>();
-                }
-                if (!ts_gemv) {                  // the streaming kernels score in fp64 directly, no fp32 pre-filter constants
-                    // (ws_fqf holds two arrays of B: qf, and behind it the NaN-safe copy the 16 x 16 x 64 form stages)
-                    HIP_TRY(orr::launch_fused_query_consts(idx->ws_qc.as<orr::QueryConst>(), idx->ws_tskey.as<unsigned long long>(), B,
-                                                           idx->ws_fqf.as<float4>(), s, gemm_i8 ? idx->ws_q8s1.as<float>() : nullptr,
-                                                           gemm_i8 ? idx->ws_q8err.as<double>() + B : nullptr,
-                                                           gemm_i8 ? idx->ws_fqf.as<float4>() + B : nullptr,
-                                                           clear_with_consts ? idx->ws_fcnt.as<uint32_t>() : nullptr, 3 * B,
-                                                           idx->ws_tickets.as<uint32_t>(), 8 * 16));
-                    tickets_cleared = true;
-                    epi.qf16 = gemm_i8 ? idx->ws_fqf.as<float4>() + B : nullptr;
-                }
-                epi.tau = idx->ws_tskey.as<unsigned long long>();
-                if (n_ranges > 1 && !gemm_i8) {         // (ranges were planned for the int8 GEMM: the other forms take one launch)
-                    Timed t(idx, "count_planes", plane_bytes_per_row * (double)(n - range_row[1]));
-                    HIP_TRY(orr::launch_query_count_planes(kw, B, n, epi.plane_stride, idx->ws_fany.as<uint32_t>(), s, range_row[1], n, epi.count_bits == 2 ? 2 : 4));
-                    n_ranges = 1;
-                }
-                if (gemm_i8) {
-                    if (!prefix_i8) {
-                        ORR_TRY(idx->ws_qtiled.reserve(orr::i8_tiled_bytes(B, idx->dim)));
-                        HIP_TRY(orr::launch_i8_tile_queries(idx->ws_q8.p, B, idx->dim, idx->ws_qtiled.p, s));
-                    }
-                    ORR_TRY(screen_i8_in_ranges(idx, a, n, kw, epi, n_ranges, range_row, plane_bytes_per_row, s, tickets_cleared));
-                } else if (ts_i8) {
-                    Timed t(idx, "screen_gemv_i8", 1.0 * (double)n * idx->dim + 28.0 * (double)n + 2.0 * (double)B * idx->dim);   // per row: scale, two relative norms (12 B), normB and created (16 B)
-                    HIP_TRY(orr::launch_screen_gemv_i8(idx->ws_q8.p, idx->ws_q8s1.as<float>(), idx->ws_q8err.as<double>(), B, idx->emb_i8.p,
-                                                       idx->i8_scale.as<float>(), idx->i8_rel_err.as<float>(), idx->i8_rel_hat.as<float>(),
-                                                       idx->d_norm_b, idx->d_created, a.now_ticks, n, idx->dim, epi, false, s));
-                } else if (ts_gemv) {
-                    ORR_TRY(need_split());
-                    Timed t(idx, "screen_gemv_bf16", 2.0 * (double)n * idx->dim + 2.0 * (double)B * idx->dim);
-                    HIP_TRY(orr::launch_screen_gemv_bf16(idx->ws_qsplit.p, B, idx->emb_shadow.p, n, idx->dim, epi, s));
-                } else if (idx->opt_two_stage == 1 && idx->shadow_ready) {
-                    ORR_TRY(idx->ws_qtiled.reserve(orr::bf16_tiled_bytes(B, idx->dim)));
-                    HIP_TRY(orr::launch_bf16_tiled(d_q, B, idx->dim, idx->ws_qtiled.p, s));
-                    Timed t(idx, "screen_bf16_fused", 2.0 * (double)n * idx->dim + 2.0 * (double)B * idx->dim);
-                    HIP_TRY(orr::launch_screen_bf16(idx->ws_qtiled.p, B, idx->emb_shadow.p, 0, n, idx->dim, nullptr, 0, &epi, s));
-                } else {
-                    ORR_TRY(need_split());
-                    Timed t(idx, "gemm_dot_bf16x1_fused", 4.0 * (double)n * idx->dim + 2.0 * (double)B * idx->dim);
-                    HIP_TRY(orr::launch_gemm_dot_bf16x3(idx->ws_qsplit.p, B, idx->d_emb, 0, n, idx->dim, nullptr, 0, &epi, 1, s));
-                }
-                ORR_TRY(two_stage_tail(idx, a, kprime, n, d_q, kw, epi, kCap, buf_lists, host_records, rec_bytes, &d_cand, &direct_host, s));
-                records_have_dots = true;
-                a.used_two_stage = true;
-                pass_mode = (gemm_i8 || ts_i8) ? 1 : (((ts_gemv && !ts_i8) || (idx->opt_two_stage == 1 && idx->shadow_ready)) ? 2 : 3);
-            } else {
-            {
-                Timed t(idx, "select_floor", 0.0);
-                HIP_TRY(orr::launch_select_final_sample(idx->ws_sel.as<orr::SelEntry>(), lists_total, fused_sample_seg, B, kprime, d_tau, s));
-            }
-            HIP_TRY(orr::launch_fused_query_consts(idx->ws_qc.as<orr::QueryConst>(), d_tau, B, idx->ws_fqf.as<float4>(), s, nullptr, nullptr, nullptr,
-                                                   clear_with_consts ? idx->ws_fcnt.as<uint32_t>() : nullptr, 3 * B));
-            epi.tau = d_tau;
-            {
-                ORR_TRY(need_split());
-                Timed t(idx, "gemm_dot_bf16x3_fused", 4.0 * (double)(n - dotf_rows) * idx->dim + 4.0 * (double)B * idx->dim);
-                HIP_TRY(orr::launch_gemm_dot_bf16x3(idx->ws_qsplit.p, B, idx->d_emb, dotf_rows, n, idx->dim, nullptr, 0, &epi, 3, s));
-            }
-            {
-                Timed t(idx, "buffer_to_lists", 0.0);
-                HIP_TRY(orr::launch_buffer_to_lists(epi.buf, epi.cnt, kCap, B, fused_sample_seg, lists_total,
-                                                    idx->ws_sel.as<orr::SelEntry>(), s));
-            }
-            {
-                Timed t(idx, "select_final", (double)B * (double)lists_total * orr::kSelWidth * sizeof(orr::SelEntry));
-                HIP_TRY(orr::launch_select_final(idx->ws_sel.as<orr::SelEntry>(), lists_total, B, kprime, n, idx->row_base,
-                                                 nullptr, nullptr, 0, idx->d_norm_b, idx->d_created, idx->d_row_ids, kw,
-                                                 0, approx_eps, nullptr, epi.cnt, kCap, nullptr, d_cand, s));
-            }
-            }
-        } else {
-        // Large batches: scan a prefix first, take its k'-th best key per query as a floor, and let
-        // the rest of the corpus skip every 64-row batch that cannot beat it.
-        const int32_t sample_seg = (B >= 8 && n_seg32 >= 48) ? std::min<int32_t>(64, std::max<int32_t>(16, n_seg32 / 16)) : 0;
-        if (sample_seg > 0) {
-            ORR_TRY(idx->ws_tau.reserve(sizeof(unsigned long long) * (size_t)B));
-            d_tau = idx->ws_tau.as<unsigned long long>();
-            {
-                Timed t(idx, "fuse_select", (double)B * (double)sample_seg * orr::kSelSegRows * 28.0);
-                HIP_TRY(orr::launch_fuse_select(d_dot, d_dotf, n, idx->d_norm_b, idx->d_created, d_rowc, kw,
-                                                idx->ws_qc.as<orr::QueryConst>(), a.now_ticks, n, B, 0, sample_seg, nullptr,
-                                                idx->ws_sel.as<orr::SelEntry>(), 0, s));
-            }
-            {
-                Timed t(idx, "select_floor", 0.0);
-                HIP_TRY(orr::launch_select_final_sample(idx->ws_sel.as<orr::SelEntry>(), n_seg32, sample_seg, B, kprime, d_tau, s));
-            }
-        }
-        {
-            Timed t(idx, "fuse_select", (double)B * (double)n * (8.0 * (use_cos ? 1 : 0) + 8.0 + 8.0));
-            HIP_TRY(orr::launch_fuse_select(d_dot, d_dotf, n, idx->d_norm_b, idx->d_created, d_rowc, kw,
-                                            idx->ws_qc.as<orr::QueryConst>(), a.now_ticks, n, B, sample_seg, n_seg32 - sample_seg,
-                                            d_tau, idx->ws_sel.as<orr::SelEntry>(), 0, s));
-        }
-        {
-            Timed t(idx, "select_final", (double)B * (double)n_seg * orr::kSelWidth * sizeof(orr::SelEntry));
-            HIP_TRY(orr::launch_select_final(idx->ws_sel.as<orr::SelEntry>(), (int32_t)n_seg, B, kprime, n, idx->row_base,
-                                             d_dot, d_dotf, n, idx->d_norm_b, idx->d_created, idx->d_row_ids, kw,
-                                             use_mfma ? 0 : 1, approx_eps, nullptr, nullptr, 0u, nullptr, d_cand, s));
-        }
-        }
-        if (approx_pass && !records_have_dots) {   // K6: the survivors' dots again, now in the reference's own arithmetic
-            Timed t(idx, "rescore_exact", (double)B * kprime * 4.0 * idx->dim);
-            HIP_TRY(orr::launch_rescore_exact(idx->d_emb, idx->dim, d_q, B, kprime, idx->row_base, d_cand, s));
-        }
-    } else {
-        ORR_TRY(run_large_k(idx, a, kprime, n, d_dot, kw, qc, d_cand, s));
-    }
-    if (!owner_of(idx)->dead.empty())      // records of deleted rows are dropped by the host finish
-        HIP_TRY(orr::launch_mark_dead_records(d_cand, B, kprime, owner_of(idx)->d_dead.as<int64_t>(),
+    // ---- 7. K4/K5 fused score + selection for the form
+    ORR_TRY(launch_selection(idx, a, p, kprime, n, io, host_records, rec_bytes));
+
+    // ---- 8. records of deleted rows are dropped by the host finish; large record sets go into pinned memory in one copy
+    if (!owner_of(idx)->dead.empty())
+        HIP_TRY(orr::launch_mark_dead_records(io.d_cand, B, kprime, owner_of(idx)->d_dead.as<int64_t>(),
                                               (int32_t)owner_of(idx)->dead.size(), idx->row_base, s));
-    if (host_records && !direct_host) {     // large record sets: one asynchronous copy into pinned memory behind the last kernel
+    if (host_records && !io.direct_host) {
         ORR_TRY(idx->pin_cand.reserve(rec_bytes));
-        HIP_TRY(hipMemcpyAsync(idx->pin_cand.p, d_cand, rec_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(idx->pin_cand.p, io.d_cand, rec_bytes, hipMemcpyDeviceToHost, s));
     }
     g_ht.mark(3);
-    idx->sstats.pass_mode = pass_mode;
-    HIP_TRY(hipStreamSynchronize(s));
-    if (bm_bytes) {            // every kernel that read the bitmaps is done: clear them for the next search
-        if (bm_bytes >= ((size_t)16 << 20)) {   // (small ones stay on the keyword stream: a cross-stream wait costs a one-query call more)
-            HIP_TRY(hipMemsetAsync(idx->ws_bitmaps.p, 0, bm_bytes, idx->stream_aux));
-            HIP_TRY(hipEventRecord(idx->ev_bm_clean, idx->stream_aux));
-            idx->bm_clean_pending = true;
-        } else {
-            HIP_TRY(hipMemsetAsync(idx->ws_bitmaps.p, 0, bm_bytes, idx->stream_kw));
-        }
-        idx->bitmaps_clean = std::max(bm_bytes, bm_clean_before);
-    }
-    if (n_terms_total > 0 && idx->ws_counter.p) {   // ... and the keyword chain's counters (two memsets less in front of the next chain)
-        HIP_TRY(hipMemsetAsync(idx->ws_counter.p, 0, sizeof(unsigned long long), idx->stream_kw));
-        if (idx->ws_kwalias.p) HIP_TRY(hipMemsetAsync(idx->ws_kwalias.p, 0, idx->ws_kwalias.cap, idx->stream_kw));
-        idx->kw_counters_clean = true;
-        idx->kw_counters_of[0] = idx->ws_counter.p;
-        idx->kw_counters_of[1] = idx->ws_kwalias.p;
-    }
-    if (dev_norms) memcpy(idx->h_norm_a.data(), idx->pin_norm.p, sizeof(double) * (size_t)B);
-    if (n_terms_total > 0) {
-        idx->sstats.kw_hits_total += (int64_t)(*idx->pin_kwcnt.as<unsigned long long>() >> 32);
-        idx->sstats.kw_passes += 1;
-    }
-    if (a.used_two_stage) {
-        idx->h_survivors.assign(idx->pin_cnt.as<uint32_t>(), idx->pin_cnt.as<uint32_t>() + B);
-        uint64_t sum = 0;
-        for (uint32_t cnt : idx->h_survivors) sum += cnt;
-        const uint64_t mean = sum / (uint64_t)B;
-        if (mean > 4096 && idx->sample_boost < 16) idx->sample_boost *= 2;
-        else if (mean < 512 && idx->sample_boost > 1) idx->sample_boost /= 2;
-    }
-    g_ht.mark(4);
-    collect_events(idx);
-    if (kw_overflow_possible) {
-        // (the counter as expand_hits left it in pinned memory: the device copy is zeroed again behind the pass)
-        const unsigned long long cnt = *idx->pin_kwcnt.as<unsigned long long>();
-        const uint32_t hits = (uint32_t)(cnt >> 32);
-        if (hits > kw_max_hits) {
-            // the distinct terms of this batch match more vocabulary tokens than the hit list holds (short terms against a
-            // large vocabulary): the bitmaps are incomplete, so this pass's records are discarded; the list grows to the
-            // measured count and the pass runs again (the index keeps the larger list)
-            if ((uint64_t)hits * sizeof(orr::KwHit) > ((uint64_t)8 << 30))
-                return fail(ORR_ENOMEM, "keyword terms matched %u vocabulary tokens: a hit list of that size is refused (8 GiB)", hits);
-            idx->kw_hits_cap = hits + hits / 4 + 1024u;
-            return kRetryPass;
-        }
-    }
-    if (recs_host && direct_host) *recs_host = d_cand;
+    idx->sstats.pass_mode = p.pass_mode();
+
+    // ---- 9. synchronise, clean up, statistics
+    const int r = finish_pass(idx, a, p, kws, n_terms_total);
+    if (r != ORR_OK) return r;
+    if (recs_host && io.direct_host) *recs_host = io.d_cand;
     else if (recs_host && host_records) *recs_host = idx->pin_cand.as<orr_candidate>();
     return ORR_OK;
 }
 
 int run_shard(orr_index *idx, const BatchArgs &a, int32_t kprime, bool host_records, const float **q_host,
-              const orr_candidate **recs_host)
+              const orr_candidate **recs_host, PassPlan &pass)
 {
-    for (int attempt = 0;; ++attempt) {
-        const int r = run_shard_once(idx, a, kprime, host_records, q_host, recs_host);
+    for (int attempt = 0;; ++attempt) {   // (the plan is made again: sample_boost may have changed)
+        const int r = run_shard_once(idx, a, kprime, host_records, q_host, recs_host, pass);
         if (r != kRetryPass) return r;
         idx->sstats.passes += 1;
         if (attempt >= 3) return fail(ORR_EDEVICE, "the keyword hit list kept overflowing");
@@ -3012,6 +3082,17 @@ int merge_impl(int32_t n_shards, int32_t B, int32_t kprime, const orr_candidate 
 // (queries x rows) are run over slices of the sub-batch, so the workspace stays bounded (kPassWorkspaceBytes).
 constexpr size_t kPassWorkspaceBytes = (size_t)4 << 30;
 
+// The survivors' buffers a repeat of the screening pass needs when the buffers overflowed: `queries` queries, the worst of
+// them kept `worst` survivors.  False where larger buffers are not the answer (too many survivors, or buffers of 2 GiB and
+// more); else *cap = pass_cap doubled until it holds worst with an eighth to spare.
+bool grown_survivor_cap(uint32_t pass_cap, uint32_t worst, int64_t n, size_t queries, uint32_t *cap)
+{
+    if (worst >= (1u << 19) || (int64_t)worst * 2 >= n || queries * (size_t)worst * 96 >= ((size_t)2 << 30)) return false;
+    *cap = pass_cap;
+    while (*cap < worst + worst / 8) *cap *= 2;
+    return true;
+}
+
 struct SubBatch {                  // storage of a compacted sub-batch (the vectors live in idx->ws_qsub when they are device-resident)
     std::vector<float> q_host;
     std::vector<uint8_t> pool;
@@ -3023,7 +3104,6 @@ int build_subset(orr_index *idx, const BatchArgs &orig, const std::vector<int32_
     out = orig;
     const int32_t nb = (int32_t)ids.size();
     out.B = nb;
-    out.used_mfma = out.used_fused = out.used_two_stage = false;
     if (orig.dim > 0) {
         const size_t row = (size_t)orig.dim;
         if (is_device_pointer(orig.q)) {
@@ -3082,7 +3162,8 @@ int search_ids(orr_index *idx, const BatchArgs &orig, const std::vector<int32_t>
 
     const float *q_host = nullptr;
     const orr_candidate *recs = nullptr;
-    ORR_TRY(run_shard(idx, cur, (int32_t)kprime, true, &q_host, &recs));
+    PassPlan pass;
+    ORR_TRY(run_shard(idx, cur, (int32_t)kprime, true, &q_host, &recs, pass));
     idx->sstats.passes += 1;
     if (depth > 0) idx->sstats.requeried += nb;
     std::vector<orr_candidate> copied;
@@ -3113,7 +3194,7 @@ int search_ids(orr_index *idx, const BatchArgs &orig, const std::vector<int32_t>
     // survivors of the screening pass (two-stage): statistics, and the buffer size the next pass needs
     uint32_t worst_unc_survivors = 0;
     bool unc_only_overflow = unc > 0;
-    if (cur.used_two_stage && (int32_t)idx->h_survivors.size() == nb) {
+    if (pass.two_stage() && (int32_t)idx->h_survivors.size() == nb) {
         for (int32_t i = 0; i < nb; ++i) {
             const uint32_t c = idx->h_survivors[(size_t)i];
             idx->sstats.survivors_total += c;
@@ -3135,12 +3216,10 @@ int search_ids(orr_index *idx, const BatchArgs &orig, const std::vector<int32_t>
     for (int32_t i = 0; i < nb; ++i) if (!cert[(size_t)i]) again.push_back(ids[(size_t)i]);
     BatchArgs next = orig;
     next.no_fuse = cur.no_fuse; next.force_exact = cur.force_exact;
-    if (unc_only_overflow && worst_unc_survivors < (1u << 19) && (int64_t)worst_unc_survivors * 2 < n &&
-        (size_t)again.size() * (size_t)worst_unc_survivors * 96 < ((size_t)2 << 30)) {
+    uint32_t cap = 0;
+    if (unc_only_overflow && grown_survivor_cap(idx->pass_cap, worst_unc_survivors, n, again.size(), &cap)) {
         // the screen kept more pairs than the buffers hold (rows clustered around the query): the same pass again for
         // these queries with buffers sized from the measured counts; the index keeps the larger size for later searches
-        uint32_t cap = idx->pass_cap;
-        while (cap < worst_unc_survivors + worst_unc_survivors / 8) cap *= 2;
         if (cap > idx->survivor_cap) idx->survivor_cap = cap;
         idx->sstats.buffer_growths += 1;
         if (!idx->is_view || idx->internal_lane) {      // the other lanes of the handle start from the measured size as well
@@ -3148,9 +3227,9 @@ int search_ids(orr_index *idx, const BatchArgs &orig, const std::vector<int32_t>
             std::lock_guard<std::mutex> ll(own->lanes_mu);
             own->survivor_cap_hint = std::max(own->survivor_cap_hint, cap);
         }
-    } else if (cur.used_fused && !cur.no_fuse) {
+    } else if (pass.fused() && !cur.no_fuse) {
         next.no_fuse = true;                                   // a tie at the cut or an overflow too large to buffer: unfused pass
-    } else if (cur.used_mfma) {
+    } else if (pass.use_mfma) {
         next.force_exact = true;                               // then the exact pass, same k'
         idx->sstats.exact_pass_queries += (int64_t)again.size();
     } else if (kprime >= n) {
@@ -3206,13 +3285,14 @@ static int shard_pass_into(orr_index *idx, BatchArgs a, int32_t kprime, int64_t 
     const size_t rec_q = sizeof(orr_candidate) * ((size_t)kprime + 1);
     unsigned char *dst = reinterpret_cast<unsigned char *>(out) + rec_q * first;
     a.out_dev = dev_out ? reinterpret_cast<orr_candidate *>(dst) : nullptr;   // records written where the caller wants them (the all-gather's send buffer)
-    ORR_TRY(run_shard(idx, a, kprime, false, nullptr, nullptr));
+    PassPlan pass;
+    ORR_TRY(run_shard(idx, a, kprime, false, nullptr, nullptr, pass));
     if (!dev_out) HIP_TRY(hipMemcpy(dst, idx->ws_cand.p, rec_q * (size_t)B, hipMemcpyDefault));
     idx->sstats.passes += 1;
     const int64_t n = participating_rows(idx, candidate_limit);
     std::vector<int32_t> active((size_t)B);             // the queries the last pass answered, in the batch's numbering
     std::iota(active.begin(), active.end(), 0);
-    bool two_stage = a.used_two_stage;
+    bool two_stage = pass.two_stage();
     for (int round = 0; round < 4 && two_stage && idx->h_survivors.size() == active.size(); ++round) {
         std::vector<int32_t> over;
         uint32_t worst = 0;
@@ -3224,9 +3304,8 @@ static int shard_pass_into(orr_index *idx, BatchArgs a, int32_t kprime, int64_t 
         }
         if (over.empty()) break;
         idx->sstats.overflowed_queries += (int64_t)over.size();
-        if (worst >= (1u << 19) || (int64_t)worst * 2 >= n || over.size() * (size_t)worst * 96 >= ((size_t)2 << 30)) break;   // the caller's escalation
-        uint32_t cap = idx->pass_cap;
-        while (cap < worst + worst / 8) cap *= 2;
+        uint32_t cap = 0;
+        if (!grown_survivor_cap(idx->pass_cap, worst, n, over.size(), &cap)) break;   // the caller's escalation
         if (cap > idx->survivor_cap) idx->survivor_cap = cap;
         idx->sstats.buffer_growths += 1;
         SubBatch sb;
@@ -3234,11 +3313,11 @@ static int shard_pass_into(orr_index *idx, BatchArgs a, int32_t kprime, int64_t 
         a.out_dev = nullptr;
         ORR_TRY(build_subset(idx, a, over, sb, sub));
         sub.no_fuse = a.no_fuse; sub.force_exact = a.force_exact;
-        ORR_TRY(run_shard(idx, sub, kprime, false, nullptr, nullptr));          // records in idx->ws_cand
+        ORR_TRY(run_shard(idx, sub, kprime, false, nullptr, nullptr, pass));    // records in idx->ws_cand
         idx->sstats.passes += 1; idx->sstats.requeried += (int64_t)over.size();
         for (size_t i = 0; i < over.size(); ++i)
             HIP_TRY(hipMemcpy(dst + rec_q * (size_t)over[i], static_cast<const unsigned char *>(idx->ws_cand.p) + rec_q * i, rec_q, hipMemcpyDefault));
-        two_stage = sub.used_two_stage;
+        two_stage = pass.two_stage();
         active.swap(over);
     }
     idx->sstats.survivor_capacity = idx->survivor_cap;
@@ -3607,15 +3686,16 @@ int cluster_search_ids(orr_cluster *c, const BatchArgs &orig, const std::vector<
         BatchArgs mine = cur;
         const float *qh = nullptr;
         const orr_candidate *recs = nullptr;
+        PassPlan pass;
         if (via_rccl) {
             mine.out_dev = c->xsend[(size_t)g].as<orr_candidate>();          // complete when run_shard returns (it synchronises its stream)
-            ORR_TRY(run_shard(sh, mine, (int32_t)kprime, false, &qh, &recs));
+            ORR_TRY(run_shard(sh, mine, (int32_t)kprime, false, &qh, &recs, pass));
         } else {
-            ORR_TRY(run_shard(sh, mine, (int32_t)kprime, true, &qh, &recs));
+            ORR_TRY(run_shard(sh, mine, (int32_t)kprime, true, &qh, &recs, pass));
             if (recs) memcpy(all.data() + (size_t)g * rec_per_shard, recs, sizeof(orr_candidate) * rec_per_shard);
             else HIP_TRY(hipMemcpy(all.data() + (size_t)g * rec_per_shard, sh->ws_cand.p, sizeof(orr_candidate) * rec_per_shard, hipMemcpyDeviceToHost));
         }
-        used_two_stage[(size_t)g] = mine.used_two_stage; used_fused[(size_t)g] = mine.used_fused; used_mfma[(size_t)g] = mine.used_mfma;
+        used_two_stage[(size_t)g] = pass.two_stage(); used_fused[(size_t)g] = pass.fused(); used_mfma[(size_t)g] = pass.use_mfma;
         return ORR_OK;
     }));
     if (via_rccl) {
@@ -3656,10 +3736,8 @@ int cluster_search_ids(orr_cluster *c, const BatchArgs &orig, const std::vector<
             if (cnt > sh->pass_cap) { c->sstats.overflowed_queries += 1; if (!cert[(size_t)i]) worst = std::max(worst, cnt); }
         }
         c->sstats.survivor_samples += nb;
-        if (worst > 0 && worst < (1u << 19) && (int64_t)worst * 2 < participating_rows(sh, orig.candidate_limit) &&
-            (size_t)unc * (size_t)worst * 96 < ((size_t)2 << 30)) {
-            uint32_t cap = sh->pass_cap;
-            while (cap < worst + worst / 8) cap *= 2;
+        uint32_t cap = 0;
+        if (worst > 0 && grown_survivor_cap(sh->pass_cap, worst, participating_rows(sh, orig.candidate_limit), (size_t)unc, &cap)) {
             if (cap > sh->survivor_cap) { sh->survivor_cap = cap; grow = true; }
             if (grow) {                                                     // (the repeat may run on another lane of this shard: the owner carries the size too)
                 orr_index *own = c->shards[(size_t)g];
