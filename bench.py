@@ -3,9 +3,14 @@
 
 One GPU (`python bench.py [--gpus 1]`), headline = BASELINE.json configs[2], "C3":
 10M chunks x 3072-d fp32 resident on one MI355X, 256 queries per step, top-k = 10, full hybrid
-score (cosine + keyword + recency fused 0.7/0.2/0.1), candidate_limit = whole corpus.  The same JSON
-line carries a second leg, configs[1] "C2" (1M chunks, one query per step), the parity block (HIP path
-against the oracle on a candidate_limit prefix of the headline corpus) and the CPU baseline.
+score (cosine + keyword + recency fused 0.7/0.2/0.1), candidate_limit = whole corpus.
+
+A plain run does what the headline figure needs and nothing else: it builds the corpus, runs the warm-up
+and the timed steps, writes --dump-outputs and prints the line.  `--full` adds the rest: the legs
+(configs[1] "C2": 1M chunks, one query per step, and the robustness legs on one GPU; C4, cluster and
+strong-scaling legs on several), two steps in flight, the per-kernel table, roofline.traffic measured by
+rocprofv3 child runs, the host probe, the parity block (HIP path against the oracle on a candidate_limit
+prefix of the headline corpus) and the CPU baseline.  The --no-* options trim a --full run.
 
 N > 1 GPUs (`--gpus N`; started plainly it spawns `python -m torch.distributed.run` as a CHILD before
 anything touches a GPU, started under torch.distributed.run it is one rank): 12.5M rows per GPU (the
@@ -19,7 +24,7 @@ A step is one pass of the hot path over one batch.  Inputs are resident in HBM b
 region; results land in host memory inside it.  Results are exact (the reference's arithmetic): the
 library screens the corpus through an int8 shadow with a rigorous per-pair bound and re-scores the
 survivors from the fp32 master in f32 x f32 -> f64.  The oracle is used here ONLY for
-the `cpu_baseline` / `parity` leg, never inside a timed GPU region.
+the `cpu_baseline` / `parity` leg of a --full run, never inside a timed GPU region.
 """
 from __future__ import annotations
 
@@ -58,6 +63,9 @@ def parse_args(argv=None):
     ap.add_argument("--dim", type=int, default=3072)
     ap.add_argument("--batch", type=int, default=0, help="queries per step of the whole job; 0 = 256 on one GPU (C3), 1024 on several (C5)")
     ap.add_argument("--topk", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline as well: legs, two steps in flight, the kernel table, "
+                         "roofline.traffic from rocprofv3, the host probe, parity and the CPU baseline (the --no-* options trim it)")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the oracle leg (cpu_baseline + parity)")
     ap.add_argument("--cpu-sample-rows", type=int, default=262144)
     ap.add_argument("--cpu-sample-queries", type=int, default=96)
@@ -95,6 +103,8 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:          # a plain run: the headline alone
+        args.no_legs = args.no_overlap_leg = args.no_cpu_baseline = args.no_pmc = True
     return args
 
 
@@ -178,7 +188,7 @@ def measure_traffic(args):
     if not os.path.exists(rocprof):
         return {"error": "rocprofv3 not found"}
     child = [sys.executable if os.path.basename(sys.executable).startswith("python") else "python3", os.path.abspath(__file__),
-             "--gpus", "1", "--no-legs", "--no-overlap-leg", "--no-cpu-baseline", "--no-pmc", "--steps", "3", "--warmup", "2",
+             "--gpus", "1", "--full", "--no-legs", "--no-overlap-leg", "--no-cpu-baseline", "--no-pmc", "--steps", "3", "--warmup", "2",
              "--dim", str(args.dim), "--topk", str(args.topk), "--rows-per-gpu", str(args.rows_per_gpu), "--batch", str(args.batch)]
     for o in args.set_option:
         child += ["--set-option", o]
@@ -266,6 +276,11 @@ class Leg:
         self.rows_per_gpu, self.n_total, self.batch, self.terms = rows_per_gpu, n_total, batch, terms
 
 
+def leg_steps(args):
+    """Steps run_leg issues through the handle: warm-up, timed, and in a --full run up to five untimed ones for the kernel table."""
+    return args.warmup + args.steps + (min(5, args.steps) if args.full else 0)
+
+
 def run_leg(leg, args, env, idx, front, gen, overlap=False, outputs=None):
     """Returns the leg's result dict on every rank (timings are the max over ranks).  `outputs` (a dict): receives what the
     last timed step returned."""
@@ -317,14 +332,15 @@ def run_leg(leg, args, env, idx, front, gen, overlap=False, outputs=None):
         outputs.update(zip(OUTPUT_NAMES, last))
     stats = idx.kernel_stats()
     sstats = idx.search_stats()
-    idx.set_profiling(1)
-    for s in range(args.warmup, args.warmup + min(5, args.steps)):
-        step(s)
-    torch.cuda.synchronize()
-    stats_all = idx.kernel_stats()
+    if args.full:
+        idx.set_profiling(1)
+        for s in range(args.warmup, args.warmup + min(5, args.steps)):
+            step(s)
+        torch.cuda.synchronize()
+        stats_all = idx.kernel_stats()
+        for name, v in stats_all.items():
+            stats.setdefault(name, v)
     idx.set_profiling(0)
-    for name, v in stats_all.items():
-        stats.setdefault(name, v)
 
     two = None
     if overlap and front is None:
@@ -383,7 +399,8 @@ def run_leg(leg, args, env, idx, front, gen, overlap=False, outputs=None):
         "roofline": roofline_of(stats, leg.rows_per_gpu, dim, B, args.steps),
         "search_stats": sstats,
         "kernels": {n: {"launches": v["launches"], "avg_ms": v["total_ms"] / max(1, v["launches"])} for n, v in stats.items()},
-        "kernels_source": "the kernel that streams every row: HIP events over the timed steps; the others: HIP events over 5 untimed steps after them",
+        "kernels_source": "the kernel that streams every row: HIP events over the timed steps"
+                          + ("; the others: HIP events over 5 untimed steps after them" if args.full else ""),
     }
     if two is not None:
         res["two_steps_in_flight"] = two
@@ -743,7 +760,7 @@ def main():
     rank = 0 if cluster_mode else int(os.environ.get("RANK", "0"))
     if not cluster_mode and world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
-    probe = host_probe() if rank == 0 else {}      # child processes only; before the first GPU call of this process
+    probe = host_probe() if rank == 0 and args.full else {}     # child processes only; before the first GPU call of this process
     if rank == 0 and world == 1 and not cluster_mode and not args.no_pmc and not args.dist_rehearsal:
         try:
             probe["pmc"] = measure_traffic(args)       # (children too: the profiler must not meet a process that already holds the GPU)
@@ -900,7 +917,7 @@ def run(args, probe, state, cluster_mode, world, rank):
         dump_head()
         head["rccl_ranks_seen"] = ranks_seen if args.backend == "nccl" else 0
         head["backend"] = args.backend + (" (RCCL over xGMI)" if args.backend == "nccl" else f" (rehearsal: {world} ranks, {n_visible} card(s))")
-        head["collectives_per_step"] = front.collectives / max(1, args.warmup + args.steps + min(5, args.steps))
+        head["collectives_per_step"] = front.collectives / max(1, leg_steps(args))
         head["escalated_queries"] = front.escalated_queries
         if rank == 0:                              # the headline is in hand from here on: a later failure still reports it
             state["out"] = assemble(args, probe, head, {}, setup_s, None, None, rows, n_total, B, world, t_start, leg_errors)
@@ -941,7 +958,7 @@ def run(args, probe, state, cluster_mode, world, rank):
             leg = Leg("strong", "fixed corpus (strong scaling): " + workload_label(rows_s, dim, 256, k, True, world), rows_s, rows_s * world, 256)
             r = run_leg(leg, args, env, idx_s, front_s, syn)
             r["scaling"] = "strong"
-            r["collectives_per_step"] = front_s.collectives / max(1, args.warmup + args.steps + min(5, args.steps))
+            r["collectives_per_step"] = front_s.collectives / max(1, leg_steps(args))
             legs_out[f"strong_{args.strong_rows // 1_000_000}M_rows_total_256_queries"] = r
             idx_s.close()
             del idx_s, front_s

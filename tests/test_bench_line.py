@@ -85,3 +85,15 @@ def test_dump_outputs_writes_float64_arrays_and_steps_are_validated(tmp_path):
     for bad in ("0", "-1"):
         with pytest.raises(SystemExit):
             bench.parse_args(["--steps", bad])
+
+
+def test_a_plain_run_is_the_headline_alone_and_full_keeps_the_rest():
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full
+    assert plain.no_legs and plain.no_overlap_leg and plain.no_cpu_baseline and plain.no_pmc
+    assert bench.leg_steps(plain) == 25                     # no untimed kernel-table steps
+    full = bench.parse_args(["--full", "--steps", "20", "--warmup", "5"])
+    assert not (full.no_legs or full.no_overlap_leg or full.no_cpu_baseline or full.no_pmc)
+    assert bench.leg_steps(full) == 30
+    trimmed = bench.parse_args(["--full", "--no-pmc"])      # the --no-* options still trim a --full run
+    assert trimmed.no_pmc and not (trimmed.no_legs or trimmed.no_overlap_leg or trimmed.no_cpu_baseline)

@@ -3,15 +3,15 @@
 # shape of the 100M-row configs (12.5M rows), each as the single JSON line bench.py prints.  Output: gpurun_out/sweep/.
 set -u
 cd "$(dirname "$0")/.." ; OUT=gpurun_out/sweep ; rm -rf $OUT ; mkdir -p $OUT
-( time timeout -k 10 500 python bench.py ) > $OUT/bench_default.json 2> $OUT/bench_default.err
+( time timeout -k 10 500 python bench.py --full ) > $OUT/bench_default.json 2> $OUT/bench_default.err
 for B in 1 4 8 32 64 128 256 1024; do
-  timeout -k 10 120 python bench.py --no-legs --no-cpu-baseline --rows-per-gpu 1000000 --batch $B > $OUT/bench_1m_b$B.json 2>/dev/null
+  timeout -k 10 120 python bench.py --full --no-legs --no-cpu-baseline --rows-per-gpu 1000000 --batch $B > $OUT/bench_1m_b$B.json 2>/dev/null
 done
 for B in 1 256 1024; do
-  timeout -k 10 300 python bench.py --no-legs --no-cpu-baseline --rows-per-gpu 12500000 --batch $B --steps 10 --warmup 3 > $OUT/bench_12p5m_b$B.json 2>/dev/null
+  timeout -k 10 300 python bench.py --full --no-legs --no-cpu-baseline --rows-per-gpu 12500000 --batch $B --steps 10 --warmup 3 > $OUT/bench_12p5m_b$B.json 2>/dev/null
 done
-timeout -k 10 300 python bench.py --no-legs --no-cpu-baseline --rows-per-gpu 12500000 --batch 256 --no-terms --steps 10 --warmup 4 > $OUT/bench_12p5m_b256_cosine_only.json 2>/dev/null
-timeout -k 10 120 python bench.py --no-legs --no-cpu-baseline --rows-per-gpu 1000000 --batch 1 --set-option two_stage=0 > $OUT/bench_1m_b1_exact_kernel.json 2>/dev/null
+timeout -k 10 300 python bench.py --full --no-legs --no-cpu-baseline --rows-per-gpu 12500000 --batch 256 --no-terms --steps 10 --warmup 4 > $OUT/bench_12p5m_b256_cosine_only.json 2>/dev/null
+timeout -k 10 120 python bench.py --full --no-legs --no-cpu-baseline --rows-per-gpu 1000000 --batch 1 --set-option two_stage=0 > $OUT/bench_1m_b1_exact_kernel.json 2>/dev/null
 python - <<EOF
 import json, glob, os
 for f in sorted(glob.glob("$OUT/*.json")):
