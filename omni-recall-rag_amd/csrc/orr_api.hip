@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "orr_kernels.h"
+#include "orr_lanes.h"
 #include "orr_token_index.h"
 
 namespace {
@@ -212,18 +213,9 @@ struct orr_index {
     PinnedBuf pin_meta, pin_q, pin_qc, pin_cand, pin_norm, pin_cnt, pin_kwcnt;
     hipEvent_t ev_q = nullptr;
 
-    // search lanes (owning index only): concurrent searches on ONE handle each take a lane -- the index itself, or one of up
-    // to max_lanes - 1 internal views (own streams and workspaces, shared corpus and shadows) created when first needed
-    std::mutex lanes_mu;
-    std::condition_variable lanes_cv;
-    std::vector<orr_index *> lanes;        // internal views (lane 0 is the index itself)
-    std::vector<char> lane_busy;           // [1 + lanes.size()]; a reserved slot whose view is still being made counts as busy
-    bool self_busy = false;
-    int lanes_reserved = 0;                // views being created right now
-    int max_lanes = 4;
+    // search lanes (owning index only; orr_lanes.h): concurrent searches on ONE handle each take a lane of this pool
+    LanePool lanes{this};
     bool internal_lane = false;            // this view belongs to its parent's lane pool (not handed to the caller)
-    int64_t dead_before_pub = 0, dead_count_pub = 0;   // (under lanes_mu) copies of dead_before / dead.size() a cluster reads without waiting for searches
-    uint32_t survivor_cap_hint = 0;        // (under lanes_mu) a lane measured that the survivors' buffers must be at least this large
     std::atomic<int> user_views{0};        // views handed to the caller (orr_index_view) that are still alive: they pin the shard's layout
 
     // profiling
@@ -237,99 +229,47 @@ static int make_view(orr_index *parent, orr_index **out, bool internal);
 
 namespace {
 
-// ---- search lanes ------------------------------------------------------------------------------------------------
+// ---- search lanes (orr_lanes.h) --------------------------------------------------------------------------------------
 // The request path is concurrent by nature (RecallSearchService is scoped, one instance per request, Program.cs:59; the store
 // behind it is lock-free, InMemoryIngestionStore.cs:8-9).  A search on an OWNING index takes a free lane: the index's own
 // workspaces, or those of an internal view (created on demand, at most max_lanes - 1 of them; corpus and shadows are shared,
 // nothing is copied).  Searches from different threads on one handle then run side by side; the caller never sees a view.
 // A view handle the caller made itself (orr_index_view) is its own single lane, as before.
-struct Lane {
-    orr_index *owner = nullptr;
-    orr_index *lane = nullptr;
-    int slot = -1;                                     // 0: the index itself; i >= 1: owner->lanes[i - 1]
-    Lane() = default;
-    Lane(const Lane &) = delete;
-    Lane &operator=(const Lane &) = delete;
-    Lane(Lane &&o) noexcept : owner(o.owner), lane(o.lane), slot(o.slot) { o.owner = nullptr; o.lane = nullptr; o.slot = -1; }
-    int acquire(orr_index *idx)
-    {
-        if (idx->is_view) { lane = idx; return ORR_OK; }
-        owner = idx;
-        std::unique_lock<std::mutex> lk(idx->lanes_mu);
-        for (;;) {
-            auto take = [&](orr_index *l, int sl) {
-                slot = sl; lane = l;
-                if (idx->survivor_cap_hint > l->survivor_cap) l->survivor_cap = idx->survivor_cap_hint;   // what another lane measured
-                return ORR_OK;
-            };
-            if (!idx->self_busy) { idx->self_busy = true; return take(idx, 0); }
-            for (size_t i = 0; i < idx->lanes.size(); ++i)
-                if (idx->lanes[i] && !idx->lane_busy[i]) { idx->lane_busy[i] = 1; return take(idx->lanes[i], (int)i + 1); }
-            if (idx->sealed && (int)idx->lanes.size() + 1 < idx->max_lanes) {
-                const size_t i = idx->lanes.size();
-                idx->lanes.push_back(nullptr);                     // the slot is reserved (and busy) while its view is made
-                idx->lane_busy.push_back(1);
-                lk.unlock();
-                orr_index *v = nullptr;
-                const int r = make_view(idx, &v, true);            // (waits for the search that holds the index's own lane)
-                lk.lock();
-                if (r == ORR_OK) {
-                    idx->lanes[i] = v; slot = (int)i + 1; lane = v;
-                    return ORR_OK;
-                }
-                // no room for another set of workspaces (or the index is being torn down): make do with the lanes there are
-                idx->lane_busy[i] = 0;
-                idx->max_lanes = 1;
-                for (orr_index *l : idx->lanes) if (l) ++idx->max_lanes;
-                continue;
-            }
-            idx->lanes_cv.wait(lk);
-        }
-    }
-    void release()
-    {
-        if (!owner) { lane = nullptr; return; }
-        {
-            std::lock_guard<std::mutex> lk(owner->lanes_mu);
-            if (slot == 0) owner->self_busy = false;
-            else if (slot > 0) owner->lane_busy[(size_t)slot - 1] = 0;
-        }
-        owner->lanes_cv.notify_all();
-        owner = nullptr; lane = nullptr; slot = -1;
-    }
-    ~Lane() { release(); }
-};
+LanePool *pool_of(orr_index *idx) { return idx && !idx->is_view ? &idx->lanes : nullptr; }
 
-// Everything that changes what the lanes share or reads their counters (deletes, options, statistics, save, destroy) waits until
-// no search is in flight on any lane and keeps new ones out meanwhile.
-struct AllLanes {
-    orr_index *owner = nullptr;
-    explicit AllLanes(orr_index *idx)
-    {
-        if (!idx || idx->is_view) return;
-        owner = idx;
-        std::unique_lock<std::mutex> lk(idx->lanes_mu);
-        idx->lanes_cv.wait(lk, [idx] {
-            if (idx->self_busy) return false;
-            for (size_t i = 0; i < idx->lanes.size(); ++i) if (idx->lane_busy[i]) return false;
-            return true;
-        });
-        idx->self_busy = true;
-        for (size_t i = 0; i < idx->lanes.size(); ++i) idx->lane_busy[i] = 1;
-    }
-    ~AllLanes()
-    {
-        if (!owner) return;
-        {
-            std::lock_guard<std::mutex> lk(owner->lanes_mu);
-            owner->self_busy = false;
-            for (size_t i = 0; i < owner->lanes.size(); ++i) owner->lane_busy[i] = 0;
-        }
-        owner->lanes_cv.notify_all();
-    }
-    AllLanes(const AllLanes &) = delete;
-    AllLanes &operator=(const AllLanes &) = delete;
-};
+// how the pool of `idx` makes another lane; none before the seal
+LanePool::Make lane_maker(orr_index *idx)
+{
+    if (!idx->sealed) return {};
+    return [idx](orr_index **v) { return make_view(idx, v, true); };   // (waits for the search that holds the index's own lane)
+}
+
+// a lane starts from the survivors' buffer size that another lane of its handle measured
+void adopt_survivor_hint(orr_index *owner, orr_index *lane)
+{
+    const uint32_t hint = owner->lanes.shared().survivor_cap_hint;
+    if (hint > lane->survivor_cap) lane->survivor_cap = hint;
+}
+
+void publish_survivor_hint(orr_index *owner, uint32_t cap)
+{
+    owner->lanes.update_shared([cap](LanePool::Shared &sh) { sh.survivor_cap_hint = std::max(sh.survivor_cap_hint, cap); });
+}
+
+Lane acquire_lane(orr_index *idx)
+{
+    if (idx->is_view) return Lane::of(idx);
+    Lane ln = idx->lanes.acquire(lane_maker(idx));
+    adopt_survivor_hint(idx, ln.lane);
+    return ln;
+}
+
+// fn(lane) for the index and every internal view of it; the caller holds Exclusive
+template <class F> void for_each_lane(orr_index *idx, F &&fn)
+{
+    if (idx->is_view) fn(idx);
+    else idx->lanes.for_each_lane(fn);
+}
 
 int stat_slot(orr_index *idx, const char *name)
 {
@@ -691,14 +631,13 @@ void orr_index_destroy(orr_index *idx)
     if (!idx) return;
     if (idx->is_view && !idx->internal_lane && idx->parent) const_cast<orr_index *>(idx->parent)->user_views.fetch_sub(1);
     if (!idx->is_view) {                               // the internal lanes go first (they borrow the corpus)
-        std::vector<orr_index *> lanes;
+        std::vector<orr_index *> views;
         {
-            AllLanes all(idx);
-            lanes.swap(idx->lanes);
-            idx->lane_busy.clear();
-            idx->max_lanes = 1;
+            LanePool::Exclusive all(&idx->lanes);
+            views = idx->lanes.drain();
+            idx->lanes.set_max_lanes(1);
         }
-        for (orr_index *l : lanes) if (l) orr_index_destroy(l);
+        for (orr_index *l : views) orr_index_destroy(l);
     }
     (void)hipSetDevice(idx->device);
     if (idx->stream) (void)hipStreamSynchronize(idx->stream);
@@ -750,10 +689,9 @@ void orr_index_destroy(orr_index *idx)
 int orr_index_set_row_base(orr_index *idx, int64_t row_base)
 {
     if (!idx || row_base < 0) return fail(ORR_EINVAL, "orr_index_set_row_base: bad argument");
-    AllLanes all(idx);
+    LanePool::Exclusive all(pool_of(idx));
     std::lock_guard<std::mutex> lock(idx->mu);
-    idx->row_base = row_base;
-    for (orr_index *l : idx->lanes) if (l) l->row_base = row_base;
+    for_each_lane(idx, [&](orr_index *x) { x->row_base = row_base; });
     return ORR_OK;
 }
 
@@ -987,7 +925,7 @@ int read_device_array(FILE *f, void *dptr, size_t bytes, std::vector<uint8_t> &b
 int orr_index_save(orr_index *idx, const char *path)
 {
     if (!idx || !path) return fail(ORR_EINVAL, "orr_index_save: null argument");
-    AllLanes all(idx);
+    LanePool::Exclusive all(pool_of(idx));
     std::lock_guard<std::mutex> lock(idx->mu);
     if (!idx->sealed) return fail(ORR_ESTATE, "orr_index_save: index is not sealed");
     if (idx->is_view) return fail(ORR_ESTATE, "orr_index_save: save the owning index, not a view");
@@ -1123,7 +1061,7 @@ int orr_index_load(const orr_config *cfg, const char *path, orr_index **out)
                     return fail(ORR_EINVAL, "shard file has a malformed deleted-row list");
             ORR_TRY(idx->d_dead.reserve(sizeof(int64_t) * idx->dead.size()));
             HIP_TRY(hipMemcpy(idx->d_dead.p, idx->dead.data(), sizeof(int64_t) * idx->dead.size(), hipMemcpyHostToDevice));
-            idx->dead_count_pub = (int64_t)idx->dead.size();
+            idx->lanes.update_shared([&](LanePool::Shared &sh) { sh.dead_count = (int64_t)idx->dead.size(); });
         }
         return ORR_OK;
     };
@@ -1311,7 +1249,7 @@ int orr_index_delete_rows(orr_index *idx, int64_t n, const int64_t *row_ids, int
 {
     if (out_deleted) *out_deleted = 0;
     if (!idx || n < 0 || (n > 0 && !row_ids)) return fail(ORR_EINVAL, "orr_index_delete_rows: bad argument");
-    AllLanes all(idx);                                 // no search in flight on any lane while the rows change
+    LanePool::Exclusive all(pool_of(idx));             // no search in flight on any lane while the rows change
     std::lock_guard<std::mutex> lock(idx->mu);
     if (!idx->sealed) return fail(ORR_ESTATE, "orr_index_delete_rows: the index is not sealed");
     if (idx->is_view) return fail(ORR_EINVAL, "orr_index_delete_rows: delete on the owning index, not on a view");
@@ -1344,7 +1282,7 @@ int orr_index_delete_rows(orr_index *idx, int64_t n, const int64_t *row_ids, int
     ORR_TRY(idx->d_dead.reserve(sizeof(int64_t) * merged.size()));
     HIP_TRY(hipMemcpy(idx->d_dead.p, merged.data(), sizeof(int64_t) * merged.size(), hipMemcpyHostToDevice));
     idx->dead.swap(merged);
-    { std::lock_guard<std::mutex> pl(idx->lanes_mu); idx->dead_count_pub = (int64_t)idx->dead.size(); }
+    idx->lanes.update_shared([&](LanePool::Shared &sh) { sh.dead_count = (int64_t)idx->dead.size(); });
     if (out_deleted) *out_deleted = (int64_t)fresh.size();
     return ORR_OK;
 }
@@ -1355,7 +1293,7 @@ int orr_index_update_rows(orr_index *idx, int64_t n, const int64_t *row_ids, int
     if (!idx || n < 0 || (n > 0 && !row_ids)) return fail(ORR_EINVAL, "orr_index_update_rows: bad argument");
     if (n > 0 && dim != 0 && !emb) return fail(ORR_EINVAL, "orr_index_update_rows: emb is NULL with dim %d", dim);
     if (dim == 0 && emb) return fail(ORR_EINVAL, "orr_index_update_rows: dim 0 (rows without an embedding) takes emb = NULL");
-    AllLanes all(idx);                                 // no search in flight on any lane while the rows change
+    LanePool::Exclusive all(pool_of(idx));             // no search in flight on any lane while the rows change
     std::lock_guard<std::mutex> lock(idx->mu);
     if (!idx->sealed) return fail(ORR_ESTATE, "orr_index_update_rows: the index is not sealed");
     if (idx->is_view) return fail(ORR_EINVAL, "orr_index_update_rows: update the owning index, not a view");
@@ -1425,8 +1363,7 @@ int orr_index_compact(orr_index *idx, int64_t *out_removed)
     if (out_removed) *out_removed = 0;
     if (!idx) return fail(ORR_EINVAL, "orr_index_compact: null index");
     if (idx->is_view) return fail(ORR_EINVAL, "orr_index_compact: compact the owning index, not a view");
-    std::vector<orr_index *> old_lanes;
-    AllLanes all(idx);                                 // no search in flight while rows move
+    LanePool::Exclusive all(pool_of(idx));             // no search in flight while rows move
     std::lock_guard<std::mutex> lock(idx->mu);
     if (!idx->sealed) return fail(ORR_ESTATE, "orr_index_compact: the index is not sealed");
     if (idx->user_views.load() > 0)
@@ -1533,52 +1470,57 @@ int orr_index_compact(orr_index *idx, int64_t *out_removed)
     idx->i8_ready = false; idx->i8_failed = false;
     idx->bitmaps_clean = 0; idx->bitmaps_clean_of = nullptr;
     idx->tok_bm.release(); idx->tok_bm_index.release(); idx->n_tok_bm = -1; idx->tok_bm_words = 0;
-    {
-        std::lock_guard<std::mutex> ll(idx->lanes_mu);
-        old_lanes.swap(idx->lanes);
-        idx->lane_busy.clear();
-        idx->dead_count_pub = 0;
-    }
-    for (orr_index *l : old_lanes) if (l) orr_index_destroy(l);
+    idx->lanes.update_shared([](LanePool::Shared &sh) { sh.dead_count = 0; });
+    for (orr_index *l : idx->lanes.drain()) orr_index_destroy(l);
     if (out_removed) *out_removed = n_dead;
     return ORR_OK;
+}
+
+// the sticky options (orr_index_set_option) a lane has in common with its index (kw_hits_cap: a lane that had grown its own
+// hit list starts from the index's size again and grows it again when a batch needs that)
+static void copy_options(const orr_index *from, orr_index *to)
+{
+    to->opt_fuse_epilogue = from->opt_fuse_epilogue; to->opt_two_stage = from->opt_two_stage;
+    to->opt_shard_pass = from->opt_shard_pass; to->opt_shard_topk = from->opt_shard_topk;
+    to->kw_hits_cap = from->kw_hits_cap; to->dead_before = from->dead_before;
+}
+
+// a lane borrows whatever shadows its index has now
+static void borrow_shadows(const orr_index *from, orr_index *to)
+{
+    to->emb_shadow.p = from->emb_shadow.p; to->shadow_ready = from->shadow_ready; to->shadow_failed = !from->shadow_ready;
+    to->emb_i8.p = from->emb_i8.p; to->i8_scale.p = from->i8_scale.p; to->i8_rel_err.p = from->i8_rel_err.p;
+    to->i8_rel_hat.p = from->i8_rel_hat.p; to->i8_rowf.p = from->i8_rowf.p;
+    to->i8_ready = from->i8_ready; to->i8_failed = !from->i8_ready;
 }
 
 int orr_index_set_option(orr_index *idx, const char *name, int64_t value)
 {
     if (!idx || !name) return fail(ORR_EINVAL, "orr_index_set_option: null argument");
-    AllLanes all(idx);                                 // options apply to every lane of the index
+    LanePool::Exclusive all(pool_of(idx));             // options apply to every lane of the index
     std::lock_guard<std::mutex> lock(idx->mu);
-    auto lanes = [&](auto &&fn) { fn(idx); for (orr_index *l : idx->lanes) if (l) fn(l); };
-    if (strcmp(name, "fuse_epilogue") == 0) { lanes([&](orr_index *x) { x->opt_fuse_epilogue = value != 0; }); return ORR_OK; }
-    if (strcmp(name, "dead_rows_before") == 0) {
-        if (value < 0) return fail(ORR_EINVAL, "orr_index_set_option: dead_rows_before must be >= 0");
-        lanes([&](orr_index *x) { x->dead_before = value; });
-        { std::lock_guard<std::mutex> pl(idx->lanes_mu); idx->dead_before_pub = value; }
-        return ORR_OK;
-    }
-    if (strcmp(name, "kw_hits_cap") == 0) {
-        if (value < 1 || value > (int64_t)0x7FFFFFFF) return fail(ORR_EINVAL, "orr_index_set_option: kw_hits_cap must be in 1 .. 2^31-1");
-        lanes([&](orr_index *x) { x->kw_hits_cap = (uint32_t)value; });
-        return ORR_OK;
-    }
     if (strcmp(name, "max_lanes") == 0) {
         if (value < 1 || value > 16) return fail(ORR_EINVAL, "orr_index_set_option: max_lanes must be in 1 .. 16");
         if (idx->is_view) return fail(ORR_EINVAL, "orr_index_set_option: max_lanes applies to the owning index");
-        idx->max_lanes = std::max<int>((int)value, 1 + (int)idx->lanes.size());      // (lanes that exist stay)
+        idx->lanes.set_max_lanes((int)value);
         return ORR_OK;
     }
-    if (strcmp(name, "shard_topk") == 0) {
+    if (strcmp(name, "fuse_epilogue") == 0) {
+        idx->opt_fuse_epilogue = value != 0;
+    } else if (strcmp(name, "dead_rows_before") == 0) {
+        if (value < 0) return fail(ORR_EINVAL, "orr_index_set_option: dead_rows_before must be >= 0");
+        idx->dead_before = value;
+        idx->lanes.update_shared([value](LanePool::Shared &sh) { sh.dead_before = value; });
+    } else if (strcmp(name, "kw_hits_cap") == 0) {
+        if (value < 1 || value > (int64_t)0x7FFFFFFF) return fail(ORR_EINVAL, "orr_index_set_option: kw_hits_cap must be in 1 .. 2^31-1");
+        idx->kw_hits_cap = (uint32_t)value;
+    } else if (strcmp(name, "shard_topk") == 0) {
         if (value < 0 || value > 1 << 30) return fail(ORR_EINVAL, "orr_index_set_option: shard_topk must be >= 0");
-        lanes([&](orr_index *x) { x->opt_shard_topk = (int)value; });
-        return ORR_OK;
-    }
-    if (strcmp(name, "shard_pass") == 0) {
+        idx->opt_shard_topk = (int)value;
+    } else if (strcmp(name, "shard_pass") == 0) {
         if (value < 0 || value > 2) return fail(ORR_EINVAL, "orr_index_set_option: shard_pass takes 0, 1 or 2");
-        lanes([&](orr_index *x) { x->opt_shard_pass = (int)value; });
-        return ORR_OK;
-    }
-    if (strcmp(name, "two_stage") == 0) {
+        idx->opt_shard_pass = (int)value;
+    } else if (strcmp(name, "two_stage") == 0) {
         if (value < 0 || value > 2) return fail(ORR_EINVAL, "orr_index_set_option: two_stage takes 0, 1 or 2");
         idx->opt_two_stage = (int)value;
         if (value == 1) {
@@ -1586,17 +1528,12 @@ int orr_index_set_option(orr_index *idx, const char *name, int64_t value)
             ORR_TRY(ensure_i8_shadow(idx));
             if (!idx->i8_ready) ORR_TRY(ensure_shadow(idx));
         }
-        for (orr_index *l : idx->lanes) {               // the lanes borrow whatever shadow exists now
-            if (!l) continue;
-            l->opt_two_stage = (int)value;
-            l->emb_shadow.p = idx->emb_shadow.p; l->shadow_ready = idx->shadow_ready; l->shadow_failed = !idx->shadow_ready;
-            l->emb_i8.p = idx->emb_i8.p; l->i8_scale.p = idx->i8_scale.p; l->i8_rel_err.p = idx->i8_rel_err.p;
-            l->i8_rel_hat.p = idx->i8_rel_hat.p; l->i8_rowf.p = idx->i8_rowf.p;
-            l->i8_ready = idx->i8_ready; l->i8_failed = !idx->i8_ready;
-        }
-        return ORR_OK;
+        for_each_lane(idx, [&](orr_index *x) { if (x != idx) borrow_shadows(idx, x); });
+    } else {
+        return fail(ORR_EINVAL, "orr_index_set_option: unknown option %s", name);
     }
-    return fail(ORR_EINVAL, "orr_index_set_option: unknown option %s", name);
+    for_each_lane(idx, [&](orr_index *x) { if (x != idx) copy_options(idx, x); });
+    return ORR_OK;
 }
 
 static int make_view(orr_index *parent, orr_index **out, bool internal);
@@ -1626,19 +1563,15 @@ static int make_view(orr_index *parent, orr_index **out, bool internal)
     v->n_tok_bm = parent->n_tok_bm; v->tok_bm_words = parent->tok_bm_words;
     v->tok_bm.p = parent->tok_bm.p; v->tok_bm_index.p = parent->tok_bm_index.p;                                        // borrowed
     v->vlong_start.p = parent->vlong_start.p; v->vlong_len.p = parent->vlong_len.p; v->vlong_id.p = parent->vlong_id.p;   // borrowed
-    v->parent = parent; v->dead_before = parent->dead_before;
+    v->parent = parent;
     v->device = parent->device; v->dim = parent->dim; v->row_base = parent->row_base;
     v->n_rows = parent->n_rows; v->cap_rows = parent->cap_rows;
     v->d_emb = parent->d_emb; v->d_created = parent->d_created; v->d_row_ids = parent->d_row_ids; v->d_norm_b = parent->d_norm_b;
     v->n_tokens = parent->n_tokens; v->d_vpool = parent->d_vpool; v->d_vstart = parent->d_vstart; v->d_vlen = parent->d_vlen;
     v->d_post_off = parent->d_post_off; v->d_post_rows = parent->d_post_rows; v->n_postings = parent->n_postings;
     v->sealed = true;
-    v->opt_fuse_epilogue = parent->opt_fuse_epilogue; v->opt_two_stage = parent->opt_two_stage;
-    v->emb_shadow.p = parent->emb_shadow.p; v->emb_shadow.cap = 0;           // borrowed, never freed here
-    v->shadow_ready = parent->shadow_ready; v->shadow_failed = !parent->shadow_ready;
-    v->emb_i8.p = parent->emb_i8.p; v->i8_scale.p = parent->i8_scale.p; v->i8_rel_err.p = parent->i8_rel_err.p;
-    v->i8_rel_hat.p = parent->i8_rel_hat.p; v->i8_rowf.p = parent->i8_rowf.p;   // borrowed as well
-    v->i8_ready = parent->i8_ready; v->i8_failed = !parent->i8_ready;
+    copy_options(parent, v);
+    borrow_shadows(parent, v);                         // (capacities stay 0: borrowed, never freed here)
     if (hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&v->stream_kw, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&v->stream_aux, hipStreamNonBlocking) != hipSuccess ||
@@ -1661,7 +1594,7 @@ static int make_view(orr_index *parent, orr_index **out, bool internal)
 int orr_index_screen_dots(orr_index *idx, int32_t B, int32_t dim, const float *q, float *out)
 {
     if (!idx || !q || !out || B <= 0) return fail(ORR_EINVAL, "orr_index_screen_dots: bad argument");
-    AllLanes all(idx);
+    LanePool::Exclusive all(pool_of(idx));
     std::lock_guard<std::mutex> lock(idx->mu);
     if (!idx->sealed) return fail(ORR_ESTATE, "orr_index_screen_dots: the index is not sealed");
     if (dim != idx->dim || dim <= 0 || dim % 64 != 0) return fail(ORR_EINVAL, "orr_index_screen_dots: dim must equal the index dimension and be a multiple of 64");
@@ -1690,7 +1623,7 @@ int orr_index_screen_i8_dots(orr_index *idx, int32_t B, int32_t dim, const float
                              int8_t *out_iq, int8_t *out_ie)
 {
     if (!idx || !q || B <= 0 || form < 0 || form > 2) return fail(ORR_EINVAL, "orr_index_screen_i8_dots: bad argument");
-    AllLanes all(idx);
+    LanePool::Exclusive all(pool_of(idx));
     std::lock_guard<std::mutex> lock(idx->mu);
     if (!idx->sealed) return fail(ORR_ESTATE, "orr_index_screen_i8_dots: the index is not sealed");
     if (dim != idx->dim || dim <= 0 || dim % 128 != 0) return fail(ORR_EINVAL, "orr_index_screen_i8_dots: dim must equal the index dimension and be a multiple of 128");
@@ -1738,30 +1671,27 @@ int orr_index_screen_i8_dots(orr_index *idx, int32_t B, int32_t dim, const float
 int orr_index_set_profiling(orr_index *idx, int32_t enabled)
 {
     if (!idx) return fail(ORR_EINVAL, "null index");
-    AllLanes all(idx);
+    LanePool::Exclusive all(pool_of(idx));
     std::lock_guard<std::mutex> lock(idx->mu);
     const int level = enabled == 2 ? 2 : (enabled != 0 ? 1 : 0);
-    idx->profiling = level;
-    idx->stats.clear();
-    for (orr_index *l : idx->lanes) if (l) { l->profiling = level; l->stats.clear(); }
+    for_each_lane(idx, [&](orr_index *x) { x->profiling = level; x->stats.clear(); });
     return ORR_OK;
 }
 
 int orr_index_kernel_stats(orr_index *idx, orr_kernel_stat *out, int32_t cap)
 {
     if (!idx) return fail(ORR_EINVAL, "null index");
-    AllLanes all(idx);
+    LanePool::Exclusive all(pool_of(idx));
     std::lock_guard<std::mutex> lock(idx->mu);
-    std::vector<KernelStat> sum = idx->stats;           // every lane's launches, by kernel name
-    for (orr_index *l : idx->lanes) {
-        if (!l) continue;
+    std::vector<KernelStat> sum;                        // every lane's launches, by kernel name
+    for_each_lane(idx, [&](orr_index *l) {
         for (const KernelStat &ks : l->stats) {
             size_t i = 0;
             while (i < sum.size() && sum[i].name != ks.name) ++i;
             if (i == sum.size()) { sum.push_back(ks); continue; }
             sum[i].launches += ks.launches; sum[i].total_ms += ks.total_ms; sum[i].algo_bytes += ks.algo_bytes;
         }
-    }
+    });
     const int32_t n = (int32_t)sum.size();
     for (int32_t i = 0; i < n && i < cap && out; ++i) {
         memset(&out[i], 0, sizeof(orr_kernel_stat));
@@ -3224,8 +3154,7 @@ int search_ids(orr_index *idx, const BatchArgs &orig, const std::vector<int32_t>
         idx->sstats.buffer_growths += 1;
         if (!idx->is_view || idx->internal_lane) {      // the other lanes of the handle start from the measured size as well
             orr_index *own = const_cast<orr_index *>(owner_of(idx));
-            std::lock_guard<std::mutex> ll(own->lanes_mu);
-            own->survivor_cap_hint = std::max(own->survivor_cap_hint, cap);
+            publish_survivor_hint(own, cap);
         }
     } else if (pass.fused() && !cur.no_fuse) {
         next.no_fuse = true;                                   // a tie at the cut or an overflow too large to buffer: unfused pass
@@ -3248,14 +3177,14 @@ extern "C" {
 int orr_index_search_stats(orr_index *idx, orr_search_stats *out, int32_t reset)
 {
     if (!idx) return fail(ORR_EINVAL, "orr_index_search_stats: null index");
-    AllLanes all(idx);
+    LanePool::Exclusive all(pool_of(idx));
     std::lock_guard<std::mutex> lock(idx->mu);
     idx->sstats.survivor_capacity = idx->survivor_cap;
     idx->sstats.vocab_tokens = idx->n_tokens;
     if (out) {
         *out = idx->sstats;
-        for (orr_index *l : idx->lanes) {               // the counters of every lane of this handle
-            if (!l) continue;
+        for_each_lane(idx, [&](orr_index *l) {         // the counters of every lane of this handle
+            if (l == idx) return;
             const orr_search_stats &t = l->sstats;
             out->searches += t.searches; out->queries += t.queries; out->passes += t.passes; out->requeried += t.requeried;
             out->overflowed_queries += t.overflowed_queries; out->buffer_growths += t.buffer_growths;
@@ -3264,12 +3193,11 @@ int orr_index_search_stats(orr_index *idx, orr_search_stats *out, int32_t reset)
             out->survivor_capacity = std::max<int64_t>(out->survivor_capacity, l->survivor_cap);
             out->kw_hits_total += t.kw_hits_total; out->kw_passes += t.kw_passes;
             if (out->pass_mode == 0) out->pass_mode = t.pass_mode;
-        }
+        });
     }
     if (reset) {
         auto clear = [](orr_index *x) { const int64_t cap = x->survivor_cap; x->sstats = orr_search_stats{}; x->sstats.survivor_capacity = cap; };
-        clear(idx);
-        for (orr_index *l : idx->lanes) if (l) clear(l);
+        for_each_lane(idx, clear);
     }
     return ORR_OK;
 }
@@ -3324,19 +3252,21 @@ static int shard_pass_into(orr_index *idx, BatchArgs a, int32_t kprime, int64_t 
     return ORR_OK;
 }
 
-int orr_search_shard_ex(orr_index *idx, int32_t B, int32_t dim, const float *q, const uint8_t *terms_utf8,
+// orr_search_shard_ex, or with `sticky` orr_search_shard: topk and pass are then the lane's options "shard_topk" and "shard_pass"
+// (every lane carries the options of its index, and they change under Exclusive only: the lane's holder reads them as they are)
+static int search_shard(orr_index *idx, int32_t B, int32_t dim, const float *q, const uint8_t *terms_utf8,
                         const uint32_t *term_off, const uint32_t *query_term_off, int64_t now_ticks, int32_t kprime,
-                        int64_t candidate_limit, int32_t topk, int32_t pass, orr_candidate *out)
+                        int64_t candidate_limit, int32_t topk, int32_t pass, bool sticky, orr_candidate *out)
 {
     BatchArgs a{B, dim, q, terms_utf8, term_off, query_term_off, now_ticks, candidate_limit, kprime};
     ORR_TRY(check_batch(idx, a, "orr_search_shard"));
     if (kprime < 1) return fail(ORR_EINVAL, "orr_search_shard: kprime must be >= 1");
     if (!out) return fail(ORR_EINVAL, "orr_search_shard: out is NULL");
     if (pass < 0 || pass > 2 || topk < 0) return fail(ORR_EINVAL, "orr_search_shard_ex: pass takes 0, 1 or 2 and topk must be >= 0");
-    Lane ln;                                           // concurrent calls on one handle run on different lanes
-    ORR_TRY(ln.acquire(idx));
+    Lane ln = acquire_lane(idx);                       // concurrent calls on one handle run on different lanes
     idx = ln.lane;
     std::lock_guard<std::mutex> lock(idx->mu);
+    if (sticky) { topk = idx->opt_shard_topk; pass = idx->opt_shard_pass; }
     // the caller's escalation after a merge that could not certify every query (orr_merge_candidates)
     a.no_fuse = pass >= 1;
     a.force_exact = pass >= 2;
@@ -3368,13 +3298,15 @@ int orr_search_shard(orr_index *idx, int32_t B, int32_t dim, const float *q, con
                      const uint32_t *term_off, const uint32_t *query_term_off, int64_t now_ticks, int32_t kprime,
                      int64_t candidate_limit, orr_candidate *out)
 {
-    if (!idx) return fail(ORR_EINVAL, "orr_search_shard: null index");
-    int32_t topk = 0, pass = 0;
-    {   // the sticky per-index forms of the two arguments ("shard_topk", "shard_pass"); orr_search_shard_ex takes them per call
-        std::lock_guard<std::mutex> lock(idx->mu);
-        topk = idx->opt_shard_topk; pass = idx->opt_shard_pass;
-    }
-    return orr_search_shard_ex(idx, B, dim, q, terms_utf8, term_off, query_term_off, now_ticks, kprime, candidate_limit, topk, pass, out);
+    // the sticky per-index forms of the two arguments ("shard_topk", "shard_pass"); orr_search_shard_ex takes them per call
+    return search_shard(idx, B, dim, q, terms_utf8, term_off, query_term_off, now_ticks, kprime, candidate_limit, 0, 0, true, out);
+}
+
+int orr_search_shard_ex(orr_index *idx, int32_t B, int32_t dim, const float *q, const uint8_t *terms_utf8,
+                        const uint32_t *term_off, const uint32_t *query_term_off, int64_t now_ticks, int32_t kprime,
+                        int64_t candidate_limit, int32_t topk, int32_t pass, orr_candidate *out)
+{
+    return search_shard(idx, B, dim, q, terms_utf8, term_off, query_term_off, now_ticks, kprime, candidate_limit, topk, pass, false, out);
 }
 
 int orr_merge_candidates(int32_t n_shards, int32_t B, int32_t kprime, const orr_candidate *all, int32_t index_dim,
@@ -3412,8 +3344,7 @@ int orr_search_batch(orr_index *idx, int32_t B, int32_t dim, const float *q, con
     BatchArgs a{B, dim, q, terms_utf8, term_off, query_term_off, now_ticks, candidate_limit, topk};
     ORR_TRY(check_batch(idx, a, "orr_search_batch"));
     if (!out_rows || !out_scores) return fail(ORR_EINVAL, "orr_search_batch: output buffers are required");
-    Lane ln;                                           // concurrent calls on one handle run on different lanes
-    ORR_TRY(ln.acquire(idx));
+    Lane ln = acquire_lane(idx);                       // concurrent calls on one handle run on different lanes
     idx = ln.lane;
     std::lock_guard<std::mutex> lock(idx->mu);
     const int32_t take = std::max<int32_t>(1, topk);
@@ -3665,7 +3596,7 @@ int cluster_search_ids(orr_cluster *c, const BatchArgs &orig, const std::vector<
     std::vector<uint8_t> used_two_stage((size_t)G, 0), used_fused((size_t)G, 0), used_mfma((size_t)G, 0);
     // every shard's half runs on a LANE of that shard (concurrent cluster searches take different lanes); the lanes stay held
     // until this pass has looked at what the screen kept on them
-    std::vector<Lane> lanes((size_t)G);
+    std::vector<Lane> lanes;
     std::vector<orr_index *> on((size_t)G, nullptr);
     // "exchange" = 1: the shards write their records into per-device send buffers and ONE RCCL all-gather brings every shard's
     // records to every device; the merge reads device 0's copy.  (One exchange at a time per cluster: the communicators are
@@ -3678,10 +3609,18 @@ int cluster_search_ids(orr_cluster *c, const BatchArgs &orig, const std::vector<
         via_rccl = rccl_prepare(c, rec_bytes_shard) == ORR_OK;
         if (!via_rccl) rccl_lock.unlock();
     }
+    {   // all lanes before any shard starts, here and in ascending shard order (acquire_in_order says why)
+        std::vector<LanePool *> pools;
+        std::vector<LanePool::Make> makes;
+        for (orr_index *sh : c->shards) { pools.push_back(&sh->lanes); makes.push_back(lane_maker(sh)); }
+        acquire_in_order(pools, makes, lanes);
+        for (int32_t g = 0; g < G; ++g) {
+            on[(size_t)g] = lanes[(size_t)g].lane;
+            adopt_survivor_hint(c->shards[(size_t)g], on[(size_t)g]);
+        }
+    }
     ORR_TRY(for_each_shard(G, [&](int32_t g) -> int {
-        ORR_TRY(lanes[(size_t)g].acquire(c->shards[(size_t)g]));
-        orr_index *sh = lanes[(size_t)g].lane;
-        on[(size_t)g] = sh;
+        orr_index *sh = on[(size_t)g];
         std::lock_guard<std::mutex> lock(sh->mu);
         BatchArgs mine = cur;
         const float *qh = nullptr;
@@ -3741,8 +3680,7 @@ int cluster_search_ids(orr_cluster *c, const BatchArgs &orig, const std::vector<
             if (cap > sh->survivor_cap) { sh->survivor_cap = cap; grow = true; }
             if (grow) {                                                     // (the repeat may run on another lane of this shard: the owner carries the size too)
                 orr_index *own = c->shards[(size_t)g];
-                std::lock_guard<std::mutex> ll(own->lanes_mu);
-                own->survivor_cap_hint = std::max(own->survivor_cap_hint, cap);
+                publish_survivor_hint(own, cap);
             }
         } else if (worst > 0) {
             only_overflow = false;                                          // too many survivors to buffer: a more exact pass instead
@@ -3929,14 +3867,9 @@ int orr_cluster_search_batch(orr_cluster *c, int32_t B, int32_t dim, const float
         // of it is idle while it changes)
         int64_t dead = 0;
         for (orr_index *sh : c->shards) {
-            int64_t have, mine;
-            {
-                std::lock_guard<std::mutex> sl(sh->lanes_mu);
-                have = sh->dead_before_pub;
-                mine = sh->dead_count_pub;
-            }
-            if (have != dead) ORR_TRY(orr_index_set_option(sh, "dead_rows_before", dead));
-            dead += mine;
+            const LanePool::Shared pub = sh->lanes.shared();
+            if (pub.dead_before != dead) ORR_TRY(orr_index_set_option(sh, "dead_rows_before", dead));
+            dead += pub.dead_count;
         }
     }
     const int32_t take = std::max<int32_t>(1, topk);
