@@ -31,6 +31,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "orr_escalation.h"
 #include "orr_kernels.h"
 #include "orr_lanes.h"
 #include "orr_token_index.h"
@@ -2151,7 +2152,7 @@ struct PassPlan {
 };
 
 // Decides the form of one pass and what it derives, building the shadows it reads.
-int plan_pass(orr_index *idx, const BatchArgs &a, int32_t kprime, int64_t n, const std::vector<uint32_t> &qoff, PassPlan &p)
+int plan_form(orr_index *idx, const BatchArgs &a, int32_t kprime, int64_t n, const std::vector<uint32_t> &qoff, PassPlan &p)
 {
     const int32_t B = a.B, D = idx->dim;
     const int32_t n_seg_all = (int32_t)((n + orr::kSelSegRows - 1) / orr::kSelSegRows);
@@ -2259,6 +2260,16 @@ int plan_pass(orr_index *idx, const BatchArgs &a, int32_t kprime, int64_t n, con
     for (int32_t b = 0; b < B; ++b) max_terms = std::max(max_terms, qoff[(size_t)b + 1] - qoff[(size_t)b]);
     if (has_terms && max_terms <= 3 && p.prefix_i8 && orr::screen_i8_uses_tile16(B, n, D, (n + 63) / 64 * 64) && !getenv("ORR_COUNT_BITS4"))
         p.count_bits = 2;
+    return ORR_OK;
+}
+
+// The plan of one pass: plan_form's, with what the escalation ladder takes for granted about it (orr_escalation.h).
+int plan_pass(orr_index *idx, const BatchArgs &a, int32_t kprime, int64_t n, const std::vector<uint32_t> &qoff, PassPlan &p)
+{
+    ORR_TRY(plan_form(idx, a, kprime, n, qoff, p));
+    assert(!p.fused() || !a.no_fuse);
+    assert(!p.use_mfma || !a.force_exact);
+    assert(!p.two_stage() || p.fused());
     return ORR_OK;
 }
 
@@ -3007,21 +3018,8 @@ int merge_impl(int32_t n_shards, int32_t B, int32_t kprime, const orr_candidate 
 // ---- one batch through the passes, escalating ONLY the queries that could not be certified ----------------------------
 // A query whose top-k could not be certified (a tie at the cut, a survivors' buffer that overflowed, k' too small for a
 // mass of equal scores) goes through the next more exact pass as part of a compacted sub-batch; the others keep their
-// results.  Order of escalation: larger survivors' buffers (when that was the only problem and they stay affordable) ->
-// unfused batched pass -> the reference-arithmetic pass over all rows -> k' x 4.  Passes whose workspace grows with
-// (queries x rows) are run over slices of the sub-batch, so the workspace stays bounded (kPassWorkspaceBytes).
-constexpr size_t kPassWorkspaceBytes = (size_t)4 << 30;
-
-// The survivors' buffers a repeat of the screening pass needs when the buffers overflowed: `queries` queries, the worst of
-// them kept `worst` survivors.  False where larger buffers are not the answer (too many survivors, or buffers of 2 GiB and
-// more); else *cap = pass_cap doubled until it holds worst with an eighth to spare.
-bool grown_survivor_cap(uint32_t pass_cap, uint32_t worst, int64_t n, size_t queries, uint32_t *cap)
-{
-    if (worst >= (1u << 19) || (int64_t)worst * 2 >= n || queries * (size_t)worst * 96 >= ((size_t)2 << 30)) return false;
-    *cap = pass_cap;
-    while (*cap < worst + worst / 8) *cap *= 2;
-    return true;
-}
+// results.  Which pass that is, and that the ladder ends, is orr_escalation.h's; escalate() below runs it for one index and
+// for the shards of a cluster.
 
 struct SubBatch {                  // storage of a compacted sub-batch (the vectors live in idx->ws_qsub when they are device-resident)
     std::vector<float> q_host;
@@ -3068,106 +3066,133 @@ int build_subset(orr_index *idx, const BatchArgs &orig, const std::vector<int32_
     return ORR_OK;
 }
 
-// ids: queries of `orig` to answer (ascending); whole = ids is the entire batch in order.  flags (no_fuse / force_exact) are
-// carried in `orig` for sub-batches.  Results are written to out_*[ids[i]].
-int search_ids(orr_index *idx, const BatchArgs &orig, const std::vector<int32_t> &ids, bool whole, int64_t kprime, int64_t n,
-               int64_t *out_rows, double *out_scores, int32_t *out_counts, int depth)
-{
-    const int32_t nb = (int32_t)ids.size();
-    const int32_t take = std::max<int32_t>(1, orig.topk);
-    const bool use_cos = orig.dim > 0 && orig.dim == idx->dim;
-    // passes that keep a number per (query,row): slices of the sub-batch
-    if ((orig.no_fuse || orig.force_exact) && nb > 1 && (size_t)nb * (size_t)std::max<int64_t>(n, 1) * 8 > kPassWorkspaceBytes) {
-        const int32_t per = (int32_t)std::max<size_t>(1, kPassWorkspaceBytes / ((size_t)std::max<int64_t>(n, 1) * 8));
-        for (int32_t i0 = 0; i0 < nb; i0 += per) {
-            std::vector<int32_t> part(ids.begin() + i0, ids.begin() + std::min<int32_t>(nb, i0 + per));
-            ORR_TRY(search_ids(idx, orig, part, false, kprime, n, out_rows, out_scores, out_counts, depth));
-        }
-        return ORR_OK;
-    }
-    SubBatch sb;
-    BatchArgs cur = orig;
-    if (!whole) ORR_TRY(build_subset(idx, orig, ids, sb, cur));
-    cur.no_fuse = orig.no_fuse; cur.force_exact = orig.force_exact;
+using escalation::ShardOutcome;
 
-    const float *q_host = nullptr;
+ShardOutcome outcome_of(const orr_index *lane, const PassPlan &pass, int64_t n)       // caller holds the lane
+{
+    ShardOutcome o;
+    o.two_stage = pass.two_stage(); o.fused = pass.fused(); o.use_mfma = pass.use_mfma;
+    o.pass_cap = lane->pass_cap; o.survivor_cap = lane->survivor_cap;
+    o.n = n;
+    o.pass_mode = lane->sstats.pass_mode;
+    o.survivors = lane->h_survivors;
+    return o;
+}
+
+// What one pass over a (sub-)batch hands to the host finish: the records of every shard, [G][B][k'+1], and what the shards kept.
+struct PassResult {
+    std::vector<ShardOutcome> shards;
     const orr_candidate *recs = nullptr;
-    PassPlan pass;
-    ORR_TRY(run_shard(idx, cur, (int32_t)kprime, true, &q_host, &recs, pass));
-    idx->sstats.passes += 1;
-    if (depth > 0) idx->sstats.requeried += nb;
-    std::vector<orr_candidate> copied;
-    if (!recs) {                                  // large record sets stay on the device until here
-        copied.resize((size_t)nb * ((size_t)kprime + 1));
-        HIP_TRY(hipMemcpy(copied.data(), idx->ws_cand.p, sizeof(orr_candidate) * copied.size(), hipMemcpyDeviceToHost));
-        recs = copied.data();
-    }
-    std::vector<uint8_t> cert((size_t)nb, 1);
-    int32_t unc = 0;
-    if (whole) {
-        ORR_TRY(merge_impl(1, nb, (int32_t)kprime, recs, cur.dim, use_cos, q_host, use_cos ? idx->h_norm_a.data() : nullptr,
-                           cur.query_term_off, cur.now_ticks, cur.topk, out_rows, out_scores, out_counts, &unc, cert.data()));
-    } else {
+    const float *q_host = nullptr;      // the query vectors in host memory, or null where norms are given and suffice
+    const double *norms = nullptr;      // exact norms of the queries (cosine only)
+    std::vector<orr_candidate> rec_store;
+    std::vector<double> norm_store;
+};
+
+// How escalate() reaches the GPU: one index on the lane its caller holds, or the shards of a cluster.
+struct Backend {
+    const char *name;                   // for messages
+    int32_t dim;
+    orr_index *subset_on;               // whose workspace holds a sub-batch of device-resident query vectors (build_subset)
+    int64_t n_total;                    // participating rows, all shards
+    int64_t slice_rows;                 // ... of the largest shard: what a per-(query,row) workspace is sized by
+    bool repeat_only_if_grown;          // escalation::decide
+    orr_search_stats *stats;
+    std::mutex *stats_mu;               // null: the caller's lock covers `stats`
+    std::function<int(const BatchArgs &, int32_t kprime, PassResult &)> run_pass;
+    std::function<void(const std::vector<ShardOutcome> &, const std::vector<uint32_t> &new_cap)> grow;   // GrowBuffers: Decision::new_cap
+};
+
+// One batch through the passes until every query is certified or nothing more exact exists.  Results go to out_*[b] of the
+// batch's numbering; a repeat overwrites what its pass could not certify.
+int escalate(const Backend &be, const BatchArgs &orig, int64_t kprime, int64_t *out_rows, double *out_scores, int32_t *out_counts)
+{
+    struct Rung {                       // queries of `orig` (ascending) and the pass they go through next
+        std::vector<int32_t> ids;
+        bool whole;                     // ids is the entire batch in order
+        bool no_fuse, force_exact;
+        int64_t kprime;
+        int repeats;
+    };
+    const int32_t take = std::max<int32_t>(1, orig.topk);
+    const bool use_cos = orig.dim > 0 && orig.dim == be.dim;
+    std::deque<Rung> todo(1, Rung{std::vector<int32_t>((size_t)orig.B), true, orig.no_fuse, orig.force_exact, kprime, 0});
+    std::iota(todo.front().ids.begin(), todo.front().ids.end(), 0);
+    while (!todo.empty()) {            // depth first: a slice's repeats run before the next slice
+        const Rung r = std::move(todo.front());
+        todo.pop_front();
+        const int32_t nb = (int32_t)r.ids.size();
+        if (const int32_t per = escalation::slice_width(nb, be.slice_rows, r.no_fuse || r.force_exact)) {
+            for (int32_t i0 = (nb - 1) / per * per; i0 >= 0; i0 -= per)
+                todo.push_front(Rung{std::vector<int32_t>(r.ids.begin() + i0, r.ids.begin() + std::min<int32_t>(nb, i0 + per)), false,
+                                     r.no_fuse, r.force_exact, r.kprime, r.repeats});
+            continue;
+        }
+        SubBatch sb;
+        BatchArgs cur = orig;
+        if (!r.whole) ORR_TRY(build_subset(be.subset_on, orig, r.ids, sb, cur));
+        cur.no_fuse = r.no_fuse; cur.force_exact = r.force_exact;
+        PassResult pr;
+        ORR_TRY(be.run_pass(cur, (int32_t)r.kprime, pr));
+        std::vector<uint8_t> cert((size_t)nb, 1);
         std::vector<int64_t> rows((size_t)nb * take);
         std::vector<double> scores((size_t)nb * take);
         std::vector<int32_t> counts((size_t)nb);
-        ORR_TRY(merge_impl(1, nb, (int32_t)kprime, recs, cur.dim, use_cos, q_host, use_cos ? idx->h_norm_a.data() : nullptr,
-                           cur.query_term_off, cur.now_ticks, cur.topk, rows.data(), scores.data(), counts.data(), &unc, cert.data()));
+        ORR_TRY(merge_impl((int32_t)pr.shards.size(), nb, (int32_t)r.kprime, pr.recs, cur.dim, use_cos, pr.q_host, pr.norms,
+                           cur.query_term_off, cur.now_ticks, cur.topk, rows.data(), scores.data(), counts.data(), nullptr, cert.data()));
         for (int32_t i = 0; i < nb; ++i) {
-            const size_t b = (size_t)ids[(size_t)i];
+            const size_t b = (size_t)r.ids[(size_t)i];
             memcpy(out_rows + b * take, rows.data() + (size_t)i * take, sizeof(int64_t) * take);
             memcpy(out_scores + b * take, scores.data() + (size_t)i * take, sizeof(double) * take);
             if (out_counts) out_counts[b] = counts[(size_t)i];
         }
-    }
-    g_ht.mark(5);
-    // survivors of the screening pass (two-stage): statistics, and the buffer size the next pass needs
-    uint32_t worst_unc_survivors = 0;
-    bool unc_only_overflow = unc > 0;
-    if (pass.two_stage() && (int32_t)idx->h_survivors.size() == nb) {
-        for (int32_t i = 0; i < nb; ++i) {
-            const uint32_t c = idx->h_survivors[(size_t)i];
-            idx->sstats.survivors_total += c;
-            idx->sstats.survivor_samples += 1;
-            if ((int64_t)c > idx->sstats.survivors_max) idx->sstats.survivors_max = c;
-            if (c > idx->pass_cap) idx->sstats.overflowed_queries += 1;
-            if (!cert[(size_t)i]) {
-                if (c > idx->pass_cap) worst_unc_survivors = std::max(worst_unc_survivors, c);
-                else unc_only_overflow = false;
-            }
+        g_ht.mark(5);
+        const escalation::Decision d = escalation::decide(pr.shards, cert, r.no_fuse, r.force_exact, r.kprime, be.n_total, be.repeat_only_if_grown);
+        {
+            std::unique_lock<std::mutex> lock = be.stats_mu ? std::unique_lock<std::mutex>(*be.stats_mu) : std::unique_lock<std::mutex>();
+            orr_search_stats &s = *be.stats;
+            s.passes += 1;
+            s.pass_mode = pr.shards[0].pass_mode;
+            if (r.repeats > 0) s.requeried += nb;
+            for (const ShardOutcome &o : pr.shards) escalation::account_survivors(s, o, (size_t)nb);
+            if (d.step == escalation::Step::GrowBuffers) s.buffer_growths += 1;
+            if (d.step == escalation::Step::Exact) s.exact_pass_queries += (int64_t)d.again.size();
         }
-    } else {
-        unc_only_overflow = false;
+        if (d.again.empty()) continue;
+        if (r.repeats >= escalation::kMaxRepeats) return fail(ORR_EDEVICE, "%s: escalation did not terminate", be.name);
+        Rung next{{}, false, r.no_fuse, r.force_exact, d.kprime, r.repeats + 1};
+        for (int32_t i : d.again) next.ids.push_back(r.ids[(size_t)i]);
+        if (d.step == escalation::Step::GrowBuffers) be.grow(pr.shards, d.new_cap);
+        if (d.step == escalation::Step::Unfused) next.no_fuse = true;
+        if (d.step == escalation::Step::Exact) next.force_exact = true;
+        todo.push_front(std::move(next));
     }
-    idx->sstats.survivor_capacity = idx->survivor_cap;
-    if (unc == 0) return ORR_OK;
+    return ORR_OK;
+}
 
-    std::vector<int32_t> again;
-    for (int32_t i = 0; i < nb; ++i) if (!cert[(size_t)i]) again.push_back(ids[(size_t)i]);
-    BatchArgs next = orig;
-    next.no_fuse = cur.no_fuse; next.force_exact = cur.force_exact;
-    uint32_t cap = 0;
-    if (unc_only_overflow && grown_survivor_cap(idx->pass_cap, worst_unc_survivors, n, again.size(), &cap)) {
-        // the screen kept more pairs than the buffers hold (rows clustered around the query): the same pass again for
-        // these queries with buffers sized from the measured counts; the index keeps the larger size for later searches
-        if (cap > idx->survivor_cap) idx->survivor_cap = cap;
-        idx->sstats.buffer_growths += 1;
-        if (!idx->is_view || idx->internal_lane) {      // the other lanes of the handle start from the measured size as well
-            orr_index *own = const_cast<orr_index *>(owner_of(idx));
-            publish_survivor_hint(own, cap);
+// escalate() on one index: the passes run on the lane the caller holds (under its lock).
+Backend index_backend(orr_index *idx, const char *name, int64_t n)
+{
+    Backend be{name, idx->dim, idx, n, n, false, &idx->sstats, nullptr, nullptr, nullptr};
+    be.run_pass = [idx, n](const BatchArgs &cur, int32_t kprime, PassResult &pr) -> int {
+        PassPlan pass;
+        ORR_TRY(run_shard(idx, cur, kprime, true, &pr.q_host, &pr.recs, pass));
+        if (!pr.recs) {                               // large record sets stay on the device until here
+            pr.rec_store.resize((size_t)cur.B * ((size_t)kprime + 1));
+            HIP_TRY(hipMemcpy(pr.rec_store.data(), idx->ws_cand.p, sizeof(orr_candidate) * pr.rec_store.size(), hipMemcpyDeviceToHost));
+            pr.recs = pr.rec_store.data();
         }
-    } else if (pass.fused() && !cur.no_fuse) {
-        next.no_fuse = true;                                   // a tie at the cut or an overflow too large to buffer: unfused pass
-    } else if (pass.use_mfma) {
-        next.force_exact = true;                               // then the exact pass, same k'
-        idx->sstats.exact_pass_queries += (int64_t)again.size();
-    } else if (kprime >= n) {
-        return ORR_OK;                                         // every participating row was a candidate: nothing more exact exists
-    } else {
-        kprime = std::min<int64_t>(n, kprime * 4);
-    }
-    if (depth > 40) return fail(ORR_EDEVICE, "orr_search_batch: escalation did not terminate");
-    return search_ids(idx, next, again, false, kprime, n, out_rows, out_scores, out_counts, depth + 1);
+        pr.norms = idx->h_norm_a.data();
+        pr.shards.assign(1, outcome_of(idx, pass, n));
+        return ORR_OK;
+    };
+    // the index keeps the larger size for later searches, and the other lanes of the handle start from it as well (a view the
+    // caller made tells its parent nothing)
+    be.grow = [idx](const std::vector<ShardOutcome> &, const std::vector<uint32_t> &new_cap) {
+        if (new_cap[0] > idx->survivor_cap) idx->survivor_cap = new_cap[0];
+        if (!idx->is_view || idx->internal_lane) publish_survivor_hint(const_cast<orr_index *>(owner_of(idx)), new_cap[0]);
+    };
+    return be;
 }
 
 }  // namespace
@@ -3185,14 +3210,8 @@ int orr_index_search_stats(orr_index *idx, orr_search_stats *out, int32_t reset)
         *out = idx->sstats;
         for_each_lane(idx, [&](orr_index *l) {         // the counters of every lane of this handle
             if (l == idx) return;
-            const orr_search_stats &t = l->sstats;
-            out->searches += t.searches; out->queries += t.queries; out->passes += t.passes; out->requeried += t.requeried;
-            out->overflowed_queries += t.overflowed_queries; out->buffer_growths += t.buffer_growths;
-            out->exact_pass_queries += t.exact_pass_queries; out->survivors_total += t.survivors_total;
-            out->survivor_samples += t.survivor_samples; out->survivors_max = std::max(out->survivors_max, t.survivors_max);
-            out->survivor_capacity = std::max<int64_t>(out->survivor_capacity, l->survivor_cap);
-            out->kw_hits_total += t.kw_hits_total; out->kw_passes += t.kw_passes;
-            if (out->pass_mode == 0) out->pass_mode = t.pass_mode;
+            l->sstats.survivor_capacity = l->survivor_cap;
+            escalation::add_search_stats(*out, l->sstats);
         });
     }
     if (reset) {
@@ -3220,35 +3239,27 @@ static int shard_pass_into(orr_index *idx, BatchArgs a, int32_t kprime, int64_t 
     const int64_t n = participating_rows(idx, candidate_limit);
     std::vector<int32_t> active((size_t)B);             // the queries the last pass answered, in the batch's numbering
     std::iota(active.begin(), active.end(), 0);
-    bool two_stage = pass.two_stage();
-    for (int round = 0; round < 4 && two_stage && idx->h_survivors.size() == active.size(); ++round) {
+    for (int round = 0; round < 4; ++round) {
+        const ShardOutcome kept = outcome_of(idx, pass, n);
+        if (!kept.kept(active.size())) break;
+        escalation::account_survivors(idx->sstats, kept, active.size());       // (statistics: only the queries this pass ran)
         std::vector<int32_t> over;
-        uint32_t worst = 0;
-        for (size_t i = 0; i < active.size(); ++i) {       // (statistics: only the queries this pass ran)
-            const uint32_t cnt = idx->h_survivors[i];
-            idx->sstats.survivors_total += cnt; idx->sstats.survivor_samples += 1;
-            if ((int64_t)cnt > idx->sstats.survivors_max) idx->sstats.survivors_max = cnt;
-            if (cnt > idx->pass_cap) { over.push_back(active[i]); worst = std::max(worst, cnt); }
-        }
-        if (over.empty()) break;
-        idx->sstats.overflowed_queries += (int64_t)over.size();
-        uint32_t cap = 0;
-        if (!grown_survivor_cap(idx->pass_cap, worst, n, over.size(), &cap)) break;   // the caller's escalation
+        uint32_t worst = 0, cap = 0;
+        for (size_t i = 0; i < active.size(); ++i)
+            if (kept.overflowed(i)) { over.push_back(active[i]); worst = std::max(worst, kept.survivors[i]); }
+        if (over.empty() || !escalation::grown_survivor_cap(kept.pass_cap, worst, n, over.size(), &cap)) break;   // the caller's escalation
         if (cap > idx->survivor_cap) idx->survivor_cap = cap;
         idx->sstats.buffer_growths += 1;
         SubBatch sb;
         BatchArgs sub;
         a.out_dev = nullptr;
         ORR_TRY(build_subset(idx, a, over, sb, sub));
-        sub.no_fuse = a.no_fuse; sub.force_exact = a.force_exact;
         ORR_TRY(run_shard(idx, sub, kprime, false, nullptr, nullptr, pass));    // records in idx->ws_cand
         idx->sstats.passes += 1; idx->sstats.requeried += (int64_t)over.size();
         for (size_t i = 0; i < over.size(); ++i)
             HIP_TRY(hipMemcpy(dst + rec_q * (size_t)over[i], static_cast<const unsigned char *>(idx->ws_cand.p) + rec_q * i, rec_q, hipMemcpyDefault));
-        two_stage = pass.two_stage();
         active.swap(over);
     }
-    idx->sstats.survivor_capacity = idx->survivor_cap;
     return ORR_OK;
 }
 
@@ -3277,21 +3288,17 @@ static int search_shard(orr_index *idx, int32_t B, int32_t dim, const float *q, 
     idx->sstats.searches += 1; idx->sstats.queries += B;
     // passes that keep one number per (query,row) -- the unfused and the exact one -- run over slices of the batch, so that
     // their workspace stays bounded whatever the batch (1024 queries x 12.5M rows x 8 B = 102 GB in one piece)
-    const int64_t n = std::max<int64_t>(1, participating_rows(idx, candidate_limit));
-    if (pass >= 1 && B > 1 && (size_t)B * (size_t)n * 8 > kPassWorkspaceBytes) {
-        const int32_t per = (int32_t)std::max<size_t>(1, kPassWorkspaceBytes / ((size_t)n * 8));
-        for (int32_t b0 = 0; b0 < B; b0 += per) {
-            std::vector<int32_t> part((size_t)std::min<int32_t>(per, B - b0));
-            std::iota(part.begin(), part.end(), b0);
-            SubBatch sb;
-            BatchArgs sub;
-            ORR_TRY(build_subset(idx, a, part, sb, sub));
-            sub.no_fuse = a.no_fuse; sub.force_exact = a.force_exact;
-            ORR_TRY(shard_pass_into(idx, sub, kprime, candidate_limit, out, (size_t)b0, dev_out));
-        }
-        return ORR_OK;
+    const int32_t per = escalation::slice_width(B, participating_rows(idx, candidate_limit), pass >= 1);
+    if (per == 0) return shard_pass_into(idx, a, kprime, candidate_limit, out, 0, dev_out);
+    for (int32_t b0 = 0; b0 < B; b0 += per) {
+        std::vector<int32_t> part((size_t)std::min<int32_t>(per, B - b0));
+        std::iota(part.begin(), part.end(), b0);
+        SubBatch sb;
+        BatchArgs sub;
+        ORR_TRY(build_subset(idx, a, part, sb, sub));
+        ORR_TRY(shard_pass_into(idx, sub, kprime, candidate_limit, out, (size_t)b0, dev_out));
     }
-    return shard_pass_into(idx, a, kprime, candidate_limit, out, 0, dev_out);
+    return ORR_OK;
 }
 
 int orr_search_shard(orr_index *idx, int32_t B, int32_t dim, const float *q, const uint8_t *terms_utf8,
@@ -3314,13 +3321,8 @@ int orr_merge_candidates(int32_t n_shards, int32_t B, int32_t kprime, const orr_
                          int32_t topk, int64_t *out_rows, double *out_scores, int32_t *out_counts,
                          int32_t *out_uncertified)
 {
-    if (n_shards < 1 || B < 1 || kprime < 1) return fail(ORR_EINVAL, "orr_merge_candidates: sizes must be positive");
-    if (!all || !query_term_off || !out_rows || !out_scores) return fail(ORR_EINVAL, "orr_merge_candidates: null argument");
-    if (dim < 0 || index_dim < 0) return fail(ORR_EINVAL, "orr_merge_candidates: negative dimension");
-    const bool use_cos = dim > 0 && dim == index_dim;
-    if (use_cos && !q_host) return fail(ORR_EINVAL, "orr_merge_candidates: q_host is required with dim %d", dim);
-    return merge_impl(n_shards, B, kprime, all, dim, use_cos, q_host, nullptr, query_term_off, now_ticks, topk, out_rows,
-                      out_scores, out_counts, out_uncertified);
+    return orr_merge_candidates_ex(n_shards, B, kprime, all, index_dim, dim, q_host, query_term_off, now_ticks, topk, out_rows,
+                                   out_scores, out_counts, out_uncertified, nullptr);
 }
 
 int orr_merge_candidates_ex(int32_t n_shards, int32_t B, int32_t kprime, const orr_candidate *all, int32_t index_dim,
@@ -3350,14 +3352,10 @@ int orr_search_batch(orr_index *idx, int32_t B, int32_t dim, const float *q, con
     const int32_t take = std::max<int32_t>(1, topk);
     const int64_t n = participating_rows(idx, candidate_limit);
 
-    // k': the asked k plus a margin, escalated until every query certifies.
-    int64_t kprime = std::min<int64_t>(std::max<int64_t>(1, n), std::max<int64_t>((int64_t)take + 22, 32));
-    if (kprime > orr::kSelWidth && take + 8 <= orr::kSelWidth) kprime = orr::kSelWidth;
     idx->sstats.searches += 1;
     idx->sstats.queries += B;
-    std::vector<int32_t> all((size_t)B);
-    std::iota(all.begin(), all.end(), 0);
-    const int r = search_ids(idx, a, all, true, kprime, n, out_rows, out_scores, out_counts, 0);
+    const int r = escalate(index_backend(idx, "orr_search_batch", n), a, escalation::initial_kprime(take, n, orr::kSelWidth),
+                           out_rows, out_scores, out_counts);
     g_ht.done();
     return r;
 }
@@ -3565,165 +3563,80 @@ int rccl_all_gather(orr_cluster *c, size_t bytes_per_shard, orr_candidate *out)
     return ORR_OK;
 }
 
-int cluster_search_ids(orr_cluster *c, const BatchArgs &orig, const std::vector<int32_t> &ids, bool whole, int64_t kprime, int64_t n_total,
-                       int64_t *out_rows, double *out_scores, int32_t *out_counts, int depth)
+// escalate() on a cluster: every pass runs on all shards at once, each shard's half on a lane of that shard that is taken and
+// given back inside the pass (concurrent cluster searches take different lanes).  The sub-batch is host memory (the cluster's
+// queries are host-resident by contract), built once for all shards.
+Backend cluster_backend(orr_cluster *c, int64_t candidate_limit)
 {
-    const int32_t nb = (int32_t)ids.size(), G = (int32_t)c->shards.size();
-    const int32_t take = std::max<int32_t>(1, orig.topk);
-    const bool use_cos = orig.dim > 0 && orig.dim == c->dim;
-    int64_t n_max = 1;
-    for (orr_index *sh : c->shards) n_max = std::max<int64_t>(n_max, participating_rows(sh, orig.candidate_limit));
-    if ((orig.no_fuse || orig.force_exact) && nb > 1 && (size_t)nb * (size_t)n_max * 8 > kPassWorkspaceBytes) {
-        const int32_t per = (int32_t)std::max<size_t>(1, kPassWorkspaceBytes / ((size_t)n_max * 8));
-        for (int32_t i0 = 0; i0 < nb; i0 += per) {
-            std::vector<int32_t> part(ids.begin() + i0, ids.begin() + std::min<int32_t>(nb, i0 + per));
-            ORR_TRY(cluster_search_ids(c, orig, part, false, kprime, n_total, out_rows, out_scores, out_counts, depth));
+    const int32_t G = (int32_t)c->shards.size();
+    Backend be{"orr_cluster_search_batch", c->dim, c->shards[0], 0, 1, true, &c->sstats, &c->stats_mu, nullptr, nullptr};
+    std::vector<int64_t> n_shard;
+    for (orr_index *sh : c->shards) {
+        n_shard.push_back(participating_rows(sh, candidate_limit));
+        be.n_total += n_shard.back();
+        be.slice_rows = std::max(be.slice_rows, n_shard.back());
+    }
+    be.run_pass = [c, G, n_shard](const BatchArgs &cur, int32_t kprime, PassResult &pr) -> int {
+        const bool use_cos = cur.dim > 0 && cur.dim == c->dim;
+        BatchArgs mine = cur;
+        if (use_cos) {
+            pr.norm_store.resize((size_t)cur.B);
+            exact_norms(cur.q, cur.B, cur.dim, pr.norm_store.data());
+            mine.norms_host = pr.norms = pr.norm_store.data();
         }
-        return ORR_OK;
-    }
-    // the sub-batch in host memory (the cluster's queries are host-resident by contract), built once for all shards
-    SubBatch sb;
-    BatchArgs cur = orig;
-    if (!whole) ORR_TRY(build_subset(c->shards[0], orig, ids, sb, cur));
-    std::vector<double> norms;
-    if (use_cos) {
-        norms.resize((size_t)nb);
-        exact_norms(cur.q, nb, cur.dim, norms.data());
-        cur.norms_host = norms.data();
-    }
-    const size_t rec_per_shard = (size_t)nb * ((size_t)kprime + 1);
-    std::vector<orr_candidate> all((size_t)G * rec_per_shard);
-    std::vector<uint8_t> used_two_stage((size_t)G, 0), used_fused((size_t)G, 0), used_mfma((size_t)G, 0);
-    // every shard's half runs on a LANE of that shard (concurrent cluster searches take different lanes); the lanes stay held
-    // until this pass has looked at what the screen kept on them
-    std::vector<Lane> lanes;
-    std::vector<orr_index *> on((size_t)G, nullptr);
-    // "exchange" = 1: the shards write their records into per-device send buffers and ONE RCCL all-gather brings every shard's
-    // records to every device; the merge reads device 0's copy.  (One exchange at a time per cluster: the communicators are
-    // not shared between concurrent collectives.)
-    std::unique_lock<std::mutex> rccl_lock(c->rccl_mu, std::defer_lock);
-    bool via_rccl = false;
-    const size_t rec_bytes_shard = sizeof(orr_candidate) * rec_per_shard;
-    if (c->exchange == 1) {
-        rccl_lock.lock();
-        via_rccl = rccl_prepare(c, rec_bytes_shard) == ORR_OK;
-        if (!via_rccl) rccl_lock.unlock();
-    }
-    {   // all lanes before any shard starts, here and in ascending shard order (acquire_in_order says why)
+        pr.q_host = cur.q;
+        const size_t rec_per_shard = (size_t)cur.B * ((size_t)kprime + 1);
+        pr.rec_store.resize((size_t)G * rec_per_shard);
+        pr.recs = pr.rec_store.data();
+        pr.shards.resize((size_t)G);
+        // "exchange" = 1: the shards write their records into per-device send buffers and ONE RCCL all-gather brings every shard's
+        // records to every device; the merge reads device 0's copy.  (One exchange at a time per cluster: the communicators are
+        // not shared between concurrent collectives.)
+        std::unique_lock<std::mutex> rccl_lock(c->rccl_mu, std::defer_lock);
+        bool via_rccl = false;
+        const size_t rec_bytes_shard = sizeof(orr_candidate) * rec_per_shard;
+        if (c->exchange == 1) {
+            rccl_lock.lock();
+            via_rccl = rccl_prepare(c, rec_bytes_shard) == ORR_OK;
+            if (!via_rccl) rccl_lock.unlock();
+        }
+        // all lanes before any shard starts, here and in ascending shard order (acquire_in_order says why)
+        std::vector<Lane> lanes;
         std::vector<LanePool *> pools;
         std::vector<LanePool::Make> makes;
         for (orr_index *sh : c->shards) { pools.push_back(&sh->lanes); makes.push_back(lane_maker(sh)); }
         acquire_in_order(pools, makes, lanes);
-        for (int32_t g = 0; g < G; ++g) {
-            on[(size_t)g] = lanes[(size_t)g].lane;
-            adopt_survivor_hint(c->shards[(size_t)g], on[(size_t)g]);
-        }
-    }
-    ORR_TRY(for_each_shard(G, [&](int32_t g) -> int {
-        orr_index *sh = on[(size_t)g];
-        std::lock_guard<std::mutex> lock(sh->mu);
-        BatchArgs mine = cur;
-        const float *qh = nullptr;
-        const orr_candidate *recs = nullptr;
-        PassPlan pass;
-        if (via_rccl) {
-            mine.out_dev = c->xsend[(size_t)g].as<orr_candidate>();          // complete when run_shard returns (it synchronises its stream)
-            ORR_TRY(run_shard(sh, mine, (int32_t)kprime, false, &qh, &recs, pass));
-        } else {
-            ORR_TRY(run_shard(sh, mine, (int32_t)kprime, true, &qh, &recs, pass));
-            if (recs) memcpy(all.data() + (size_t)g * rec_per_shard, recs, sizeof(orr_candidate) * rec_per_shard);
-            else HIP_TRY(hipMemcpy(all.data() + (size_t)g * rec_per_shard, sh->ws_cand.p, sizeof(orr_candidate) * rec_per_shard, hipMemcpyDeviceToHost));
-        }
-        used_two_stage[(size_t)g] = pass.two_stage(); used_fused[(size_t)g] = pass.fused(); used_mfma[(size_t)g] = pass.use_mfma;
-        return ORR_OK;
-    }));
-    if (via_rccl) {
-        ORR_TRY(rccl_all_gather(c, rec_bytes_shard, all.data()));
-        rccl_lock.unlock();
-    }
-    std::unique_lock<std::mutex> stats_lock(c->stats_mu);
-    c->sstats.passes += 1;
-    c->sstats.pass_mode = on[0]->sstats.pass_mode;
-    if (depth > 0) c->sstats.requeried += nb;
-    stats_lock.unlock();
-    std::vector<uint8_t> cert((size_t)nb, 1);
-    int32_t unc = 0;
-    std::vector<int64_t> rows((size_t)nb * take);
-    std::vector<double> scores((size_t)nb * take);
-    std::vector<int32_t> counts((size_t)nb);
-    ORR_TRY(merge_impl(G, nb, (int32_t)kprime, all.data(), cur.dim, use_cos, cur.q, use_cos ? norms.data() : nullptr, cur.query_term_off,
-                       cur.now_ticks, cur.topk, rows.data(), scores.data(), counts.data(), &unc, cert.data()));
-    for (int32_t i = 0; i < nb; ++i) {                                      // (a later pass overwrites what could not be certified)
-        const size_t b = (size_t)ids[(size_t)i];
-        memcpy(out_rows + b * take, rows.data() + (size_t)i * take, sizeof(int64_t) * take);
-        memcpy(out_scores + b * take, scores.data() + (size_t)i * take, sizeof(double) * take);
-        if (out_counts) out_counts[b] = counts[(size_t)i];
-    }
-    // survivors of the screening pass, per shard: statistics, and the buffer size a repeat needs
-    bool any_fused = false, any_mfma = false, grow = false, only_overflow = unc > 0;
-    stats_lock.lock();
-    for (int32_t g = 0; g < G; ++g) {
-        orr_index *sh = on[(size_t)g];
-        any_fused = any_fused || used_fused[(size_t)g];
-        any_mfma = any_mfma || used_mfma[(size_t)g];
-        if (!used_two_stage[(size_t)g] || (int32_t)sh->h_survivors.size() != nb) continue;
-        uint32_t worst = 0;
-        for (int32_t i = 0; i < nb; ++i) {
-            const uint32_t cnt = sh->h_survivors[(size_t)i];
-            c->sstats.survivors_total += cnt;
-            if ((int64_t)cnt > c->sstats.survivors_max) c->sstats.survivors_max = cnt;
-            if (cnt > sh->pass_cap) { c->sstats.overflowed_queries += 1; if (!cert[(size_t)i]) worst = std::max(worst, cnt); }
-        }
-        c->sstats.survivor_samples += nb;
-        uint32_t cap = 0;
-        if (worst > 0 && grown_survivor_cap(sh->pass_cap, worst, participating_rows(sh, orig.candidate_limit), (size_t)unc, &cap)) {
-            if (cap > sh->survivor_cap) { sh->survivor_cap = cap; grow = true; }
-            if (grow) {                                                     // (the repeat may run on another lane of this shard: the owner carries the size too)
-                orr_index *own = c->shards[(size_t)g];
-                publish_survivor_hint(own, cap);
+        for (int32_t g = 0; g < G; ++g) adopt_survivor_hint(c->shards[(size_t)g], lanes[(size_t)g].lane);
+        ORR_TRY(for_each_shard(G, [&](int32_t g) -> int {
+            orr_index *sh = lanes[(size_t)g].lane;
+            std::lock_guard<std::mutex> lock(sh->mu);
+            BatchArgs a = mine;
+            const float *qh = nullptr;
+            const orr_candidate *recs = nullptr;
+            orr_candidate *dst = pr.rec_store.data() + (size_t)g * rec_per_shard;
+            PassPlan pass;
+            if (via_rccl) {
+                a.out_dev = c->xsend[(size_t)g].as<orr_candidate>();             // complete when run_shard returns (it synchronises its stream)
+                ORR_TRY(run_shard(sh, a, kprime, false, &qh, &recs, pass));
+            } else {
+                ORR_TRY(run_shard(sh, a, kprime, true, &qh, &recs, pass));
+                if (recs) memcpy(dst, recs, rec_bytes_shard);
+                else HIP_TRY(hipMemcpy(dst, sh->ws_cand.p, rec_bytes_shard, hipMemcpyDeviceToHost));
             }
-        } else if (worst > 0) {
-            only_overflow = false;                                          // too many survivors to buffer: a more exact pass instead
-        }
-        c->sstats.survivor_capacity = std::max<int64_t>(c->sstats.survivor_capacity, sh->survivor_cap);
-    }
-    stats_lock.unlock();
-    if (unc == 0) return ORR_OK;
-    // queries uncertified for a reason other than an overflowing buffer need a more exact pass whatever the buffers do
-    if (grow) {
-        for (int32_t g = 0; g < G && only_overflow; ++g) {
-            orr_index *sh = on[(size_t)g];
-            if (!used_two_stage[(size_t)g] || (int32_t)sh->h_survivors.size() != nb) { only_overflow = false; break; }
-        }
-        if (only_overflow)
-            for (int32_t i = 0; i < nb && only_overflow; ++i) {
-                if (cert[(size_t)i]) continue;
-                bool over = false;
-                for (int32_t g = 0; g < G; ++g) over = over || on[(size_t)g]->h_survivors[(size_t)i] > on[(size_t)g]->pass_cap;
-                only_overflow = over;
-            }
-    }
-    // (a grown buffer size belongs to the lane that measured it; the shard's other lanes learn it when they overflow themselves)
-    lanes.clear();                                      // the repeat below takes lanes of its own
-    std::vector<int32_t> again;
-    for (int32_t i = 0; i < nb; ++i) if (!cert[(size_t)i]) again.push_back(ids[(size_t)i]);
-    BatchArgs next = orig;
-    if (grow && only_overflow) {
-        std::lock_guard<std::mutex> l(c->stats_mu);
-        c->sstats.buffer_growths += 1;                                       // the same pass again with buffers sized from the measured counts
-    } else if (any_fused && !orig.no_fuse) {
-        next.no_fuse = true;
-    } else if (any_mfma && !orig.force_exact) {
-        next.force_exact = true;
-        std::lock_guard<std::mutex> l(c->stats_mu);
-        c->sstats.exact_pass_queries += (int64_t)again.size();
-    } else if (kprime >= n_total) {
+            pr.shards[(size_t)g] = outcome_of(sh, pass, n_shard[(size_t)g]);
+            return ORR_OK;
+        }));
+        lanes.clear();
+        if (via_rccl) ORR_TRY(rccl_all_gather(c, rec_bytes_shard, pr.rec_store.data()));
         return ORR_OK;
-    } else {
-        kprime = std::min<int64_t>(n_total, kprime * 4);
-    }
-    if (depth >= 40) return fail(ORR_EDEVICE, "orr_cluster_search_batch: escalation did not terminate");
-    return cluster_search_ids(c, next, again, false, kprime, n_total, out_rows, out_scores, out_counts, depth + 1);
+    };
+    // a grown size reaches the shard's lanes through their owner: every lane adopts the owner's hint when a search takes it (the
+    // repeat may run on another lane than the one that measured the counts)
+    be.grow = [c](const std::vector<ShardOutcome> &ran, const std::vector<uint32_t> &new_cap) {
+        for (size_t g = 0; g < new_cap.size(); ++g)
+            if (new_cap[g] > ran[g].survivor_cap) publish_survivor_hint(c->shards[g], new_cap[g]);
+    };
+    return be;
 }
 
 }  // namespace
@@ -3873,20 +3786,15 @@ int orr_cluster_search_batch(orr_cluster *c, int32_t B, int32_t dim, const float
         }
     }
     const int32_t take = std::max<int32_t>(1, topk);
-    int64_t n_total = 0;
-    for (orr_index *sh : c->shards) n_total += participating_rows(sh, candidate_limit);
-    // k' per shard as orr_search_batch picks it for one shard: any shard may hold the whole top-k
-    int64_t kprime = std::min<int64_t>(std::max<int64_t>(1, n_total), std::max<int64_t>((int64_t)take + 22, 32));
-    if (kprime > orr::kSelWidth && take + 8 <= orr::kSelWidth) kprime = orr::kSelWidth;
+    const Backend be = cluster_backend(c, candidate_limit);
     {
         std::lock_guard<std::mutex> l(c->stats_mu);
         c->sstats.searches += 1;
         c->sstats.queries += B;
     }
     for (int64_t i = 0; i < (int64_t)B * take; ++i) { out_rows[i] = -1; out_scores[i] = 0.0; }
-    std::vector<int32_t> all((size_t)B);
-    std::iota(all.begin(), all.end(), 0);
-    return cluster_search_ids(c, a, all, true, kprime, n_total, out_rows, out_scores, out_counts, 0);
+    // k' per shard as orr_search_batch picks it for one shard: any shard may hold the whole top-k
+    return escalate(be, a, escalation::initial_kprime(take, be.n_total, orr::kSelWidth), out_rows, out_scores, out_counts);
 }
 
 int orr_cluster_search_stats(orr_cluster *c, orr_search_stats *out, int32_t reset)
