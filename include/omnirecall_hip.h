@@ -299,6 +299,36 @@ int     orr_index_update_rows(orr_index *idx, int64_t n, const int64_t *row_ids,
  * leaves the shard unusable: rebuild it. */
 int orr_index_compact(orr_index *idx, int64_t *out_removed);
 
+/* ---- rows into a sealed shard ------------------------------------------------------
+ * The missing half of UpsertChunksAsync (InMemoryIngestionStore.cs:17-25) on a SEALED shard: an upsert takes any CreatedAtUtc,
+ * and orr_index_append after the seal is ORR_ESTATE.  Arguments as orr_index_append (host or device pointers), except that
+ * row_ids is REQUIRED (ORR_EINVAL when NULL): the default id of append, row_base + position, is no longer unique once a shard
+ * was compacted.  Afterwards the shard is what a shard sealed from scratch from (the old rows in candidate order, then these
+ * rows in the order given) would be -- a stable CreatedAt-descending merge: at equal ticks every old row stays in front of
+ * every new one, new rows keep their relative order.  Embeddings bit for bit, exact norms (of the new rows: taken on the
+ * staging buffer by the kernel the seal uses), timestamps, row ids, and the token index as a map token -> ascending positions
+ * (tokens not seen before are appended to the vocabulary, so its ORDER, and with it the bytes of a shard file, may differ from
+ * a fresh seal's; searches do not).  Deleted rows stay deleted at their shifted positions.  orr_index_rows grows by n and rows
+ * behind an insertion point move down: a shard BEHIND this one in a global order moves down by n rows -- give it its new
+ * row_base (orr_index_set_row_base); orr_cluster_insert_rows does that for a cluster.  *out_inserted (may be NULL) = n.
+ *   dim   == the index dimension with emb = [n][dim], or 0 with emb = NULL for rows without an embedding (zero rows, norm 0);
+ *         any other dim is ORR_EDIM.  n == 0: ORR_OK, nothing is touched.  rows + n >= 2^32 - 1: ORR_EINVAL.
+ * Needs a sealed index (ORR_ESTATE) and the owning handle (ORR_EINVAL on a view); ORR_ESTATE while views made with
+ * orr_index_view are alive (they borrow the arrays that move).  Exclusive like compact: waits for the searches in flight;
+ * internal lanes are remade on demand.  A shadow (int8, bf16) that was built before the call is rebuilt from the moved rows
+ * before the call returns, one that was not stays unbuilt; token bitmaps are rebuilt at the next search that wants them.
+ * A shadow that cannot be rebuilt (no room for the grown shard, or a failure inside its build) is dropped and the call still
+ * returns ORR_OK: the rows are in, and the next search that wants the shadow builds it as on a new shard.
+ * Memory: with room reserved (orr_config.capacity_rows, or what the 1.5 x growth of append left) the embeddings move IN
+ * PLACE, from the last destination chunk to the first, through a bounce buffer of at most 256 MiB; the new rows come
+ * through a staging buffer of at most 256 MiB per round; rows in front of the first insertion point are not touched.
+ * WITHOUT room (a shard from orr_index_load has exactly its rows) the arrays are grown first, which takes a second copy of
+ * the embeddings for the duration of the copy, or ORR_ENOMEM.  Every allocation happens before the first row moves:
+ * ORR_ENOMEM leaves the shard exactly as it was and searchable.  ORR_EDEVICE part way leaves it unusable: rebuild it. */
+int orr_index_insert_rows(orr_index *idx, int64_t n, int32_t dim, const float *emb,
+                          const int64_t *created_ticks, const uint8_t *content_lower,
+                          const uint64_t *content_off, const int64_t *row_ids, int64_t *out_inserted);
+
 /* ---- tuning knobs ----------------------------------------------------------
  * Integer options of one index; unknown names are ORR_EINVAL.
  *   "dead_rows_before"  deleted rows in the shards in front of this one (default 0), see above.
@@ -397,6 +427,13 @@ int        orr_cluster_search_stats(orr_cluster *c, orr_search_stats *out, int32
 int        orr_cluster_set_option(orr_cluster *c, const char *name, int64_t value);
 /* orr_index_compact on every shard (concurrently), then the shards are placed in the global order again. */
 int        orr_cluster_compact(orr_cluster *c, int64_t *out_removed);
+
+/* orr_index_insert_rows into shard `shard`.  The rows must keep the order orr_cluster_seal checks (every row of shard i at
+ * least as new as every row of shard i + 1): ORR_EINVAL otherwise, BEFORE anything is written.  Then the shards are placed in
+ * the global order again (row_base, "dead_rows_before").  Exclusive against cluster searches. */
+int        orr_cluster_insert_rows(orr_cluster *c, int32_t shard, int64_t n, int32_t dim, const float *emb,
+                                   const int64_t *created_ticks, const uint8_t *content_lower,
+                                   const uint64_t *content_off, const int64_t *row_ids, int64_t *out_inserted);
 
 #ifdef __cplusplus
 }

@@ -122,6 +122,17 @@ int64_t orrh_service_compactions(orrh_service *svc);        /* shards compacted 
  * where the old one was null), overwrites those rows in place (orr_index_update_rows): no tombstones, no delta shard, no
  * rebuild.  Any other change to the list takes the paths above.  Rows updated in place so far: */
 int64_t orrh_service_updated_rows(orrh_service *svc);
+/* Integer options of a service; unknown names are ORR_EINVAL.
+ *   "insert_older"  0/1 (default 0).  UpsertChunksAsync (InMemoryIngestionStore.cs:17-25) takes any CreatedAtUtc; by default an
+ *                   upload whose chunks are not all strictly newer than everything indexed rebuilds the whole corpus.  With 1
+ *                   such chunks are inserted into the sealed shards in place (orr_index_insert_rows), each into the shard its
+ *                   ticks belong to, when that provably gives the order a rebuild would: every added document lies behind
+ *                   every indexed one in the store's enumeration order, or no added chunk has the CreatedAtUtc of a live
+ *                   indexed chunk; and the added chunks' majority dimension is the service's (or they have no vectors).
+ *                   Otherwise, and when an insert fails, what happens without the option happens.  Strictly newer uploads
+ *                   keep making delta shards.  full_rebuilds, delta_builds and the shard count do not change on this path. */
+int     orrh_service_set_option(orrh_service *svc, const char *name, int64_t value);
+int64_t orrh_service_inserted_rows(orrh_service *svc);      /* rows inserted into sealed shards in place so far */
 /* SearchAsync(query, topK) with the query embedding supplied by the caller (the
  * IEmbeddingClient result; qdim 0 = empty vector) and a frozen clock.  *out_json is
  * malloc'd; release it with orrh_free.  A blank query is ORR_EINVAL "Query is required." */

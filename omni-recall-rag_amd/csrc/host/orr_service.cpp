@@ -85,10 +85,16 @@ using orrh_detail::g_err;
 using orrh_detail::iso_utc;
 using orrh_detail::json_string;
 
+struct Extent {                      // chunks [first, first + count) of a shard carry the row ids id_base, id_base + 1, ...
+    int64_t id_base = 0;
+    size_t first = 0, count = 0;
+};
+
 struct Shard {                       // one sealed orr_index and the chunks behind its row ids
     orr_index *index = nullptr;
-    std::vector<Chunk> chunks;       // row id = id_base + position in this vector
-    int64_t id_base = 0;
+    std::vector<Chunk> chunks;       // as built (store enumeration order), then the chunks inserted later (orr_index_insert_rows)
+    std::vector<Extent> extents;     // row id <-> position in `chunks`: one extent from the build, one per insert (a grown shard's
+                                     // ids would otherwise run into the range of the shard made after it)
     int64_t min_created = 0, max_created = 0;
     std::map<std::string, uint64_t> doc_stamps;      // documents with live rows here -> version of their chunk list
     std::vector<char> dead;          // rows deleted in place (orr_index_delete_rows), by position in `chunks`
@@ -105,7 +111,8 @@ struct orrh_service {
     int32_t dim = 0;
     uint64_t built_version = ~0ull;
     int64_t next_id = 0;
-    int64_t full_rebuilds = 0, delta_builds = 0, tombstoned_rows = 0, compactions = 0, delta_merges = 0, updated_rows = 0;
+    int64_t full_rebuilds = 0, delta_builds = 0, tombstoned_rows = 0, compactions = 0, delta_merges = 0, updated_rows = 0, inserted_rows = 0;
+    bool insert_older = false;       // orrh_service_set_option("insert_older")
 };
 
 namespace {
@@ -127,6 +134,13 @@ void json_double(double v, std::string &out)
     out.append(buf, r.ptr);
 }
 
+int64_t id_of(const Shard &sh, size_t p)
+{
+    for (const Extent &e : sh.extents)
+        if (p >= e.first && p < e.first + e.count) return e.id_base + (int64_t)(p - e.first);
+    return -1;
+}
+
 void free_shards(orrh_service *svc)
 {
     for (auto &sh : svc->shards)
@@ -139,8 +153,9 @@ int build_shard(orrh_service *svc, std::vector<Chunk> &&chunks, int32_t dim, Sha
 {
     Shard sh;
     sh.chunks = std::move(chunks);
-    sh.id_base = svc->next_id;
+    const int64_t id_base = svc->next_id;
     svc->next_id += (int64_t)sh.chunks.size();
+    sh.extents.push_back({id_base, 0, sh.chunks.size()});
     orr_config cfg;
     memset(&cfg, 0, sizeof(cfg));
     cfg.struct_size = (int32_t)sizeof(cfg);
@@ -163,7 +178,7 @@ int build_shard(orrh_service *svc, std::vector<Chunk> &&chunks, int32_t dim, Sha
             const Chunk &c = sh.chunks[e];
             if (has) emb.insert(emb.end(), c.embedding.begin(), c.embedding.end());
             created.push_back(c.created_ticks);
-            ids.push_back(sh.id_base + (int64_t)e);
+            ids.push_back(id_base + (int64_t)e);
             sh.min_created = std::min(sh.min_created, c.created_ticks);
             sh.max_created = std::max(sh.max_created, c.created_ticks);
             pool += lower(c.content);                 // Content.ToLowerInvariant(), :110 hoisted to ingest
@@ -223,10 +238,10 @@ int reindex_in_place(orrh_service *svc, Shard &sh, const std::string &doc, const
         const bool usable = (int32_t)c.embedding.size() == svc->dim;
         if (!usable && !(c.embedding.empty() && o.embedding.empty())) return 0;
         if (usable) {
-            ids_with.push_back(sh.id_base + (int64_t)at[i]);
+            ids_with.push_back(id_of(sh, at[i]));
             emb.insert(emb.end(), c.embedding.begin(), c.embedding.end());
         } else {
-            ids_without.push_back(sh.id_base + (int64_t)at[i]);        // as build_shard stores a row without a usable vector
+            ids_without.push_back(id_of(sh, at[i]));        // as build_shard stores a row without a usable vector
         }
     }
     int64_t done = 0, done0 = 0;
@@ -238,6 +253,75 @@ int reindex_in_place(orrh_service *svc, Shard &sh, const std::string &doc, const
     for (size_t i = 0; i < list.size(); ++i) sh.chunks[at[i]].embedding = list[i].embedding;
     sh.doc_stamps[doc] = st->chunk_stamp[doc];
     svc->updated_rows += done + done0;
+    return 1;
+}
+
+// "insert_older": documents not yet indexed whose chunks are NOT all strictly newer than everything indexed go into the sealed
+// shards in place (orr_index_insert_rows) instead of forcing a rebuild of the whole corpus.  Each chunk goes into the shard
+// where it belongs -- the newest shard whose successor holds only strictly older rows, else the last -- which keeps the
+// shards' tick ranges in order (a shard's rows stay strictly newer than the next shard's).  An insert puts a new row BEHIND
+// every old row of the same ticks and keeps the new rows' order; a rebuild enumerates doc_order and sorts stably.  The two
+// agree when (a) every added document lies behind every indexed one in doc_order, or (b) no added chunk has the ticks of a
+// live indexed chunk (`added` is already in doc_order, so ties among the added chunks fall right by themselves).  Returns 1
+// when done, 0 when the upload does not qualify (nothing was touched), < 0 when an insert failed: the caller rebuilds.
+int insert_older_chunks(orrh_service *svc, const std::vector<Chunk> &added, const std::map<std::string, uint64_t> &added_stamps,
+                        const std::map<std::string, uint64_t> &indexed, orrh_store *st)
+{
+    const int32_t d = majority_dim(added);
+    if (!(d == svc->dim || d == 0)) return 0;
+    bool behind = true, seen_added = false;
+    for (const auto &doc : st->doc_order) {
+        if (added_stamps.count(doc)) seen_added = true;
+        else if (indexed.count(doc) && seen_added) { behind = false; break; }
+    }
+    if (!behind) {
+        std::vector<int64_t> ticks;
+        for (const auto &c : added) ticks.push_back(c.created_ticks);
+        std::sort(ticks.begin(), ticks.end());
+        for (const auto &sh : svc->shards)
+            for (size_t p = 0; p < sh.chunks.size(); ++p)
+                if ((sh.dead.empty() || !sh.dead[p]) && std::binary_search(ticks.begin(), ticks.end(), sh.chunks[p].created_ticks)) return 0;
+    }
+    const size_t S = svc->shards.size();
+    std::vector<std::vector<size_t>> into(S);
+    for (size_t a = 0; a < added.size(); ++a) {
+        size_t to = S - 1;
+        for (size_t i = 0; i + 1 < S; ++i)
+            if (svc->shards[i + 1].max_created < added[a].created_ticks) { to = i; break; }
+        into[to].push_back(a);
+    }
+    for (size_t i = 0; i < S; ++i) {
+        if (into[i].empty()) continue;
+        Shard &sh = svc->shards[i];
+        const size_t n = into[i].size();
+        std::vector<float> emb((size_t)svc->dim * n, 0.0f);          // a chunk without a usable vector: a zero row, as build_shard stores it
+        std::vector<int64_t> created(n), ids(n);
+        std::vector<uint64_t> off{0};
+        std::string pool;
+        for (size_t j = 0; j < n; ++j) {
+            const Chunk &c = added[into[i][j]];
+            if (svc->dim > 0 && (int32_t)c.embedding.size() == svc->dim) std::copy(c.embedding.begin(), c.embedding.end(), emb.begin() + j * (size_t)svc->dim);
+            created[j] = c.created_ticks;
+            ids[j] = svc->next_id + (int64_t)j;
+            pool += lower(c.content);
+            off.push_back(pool.size());
+        }
+        int64_t done = 0;
+        const int r = orr_index_insert_rows(sh.index, (int64_t)n, svc->dim, svc->dim > 0 ? emb.data() : nullptr, created.data(),
+                                            reinterpret_cast<const uint8_t *>(pool.data()), off.data(), ids.data(), &done);
+        if (r != ORR_OK) return fail(r, orr_last_error());
+        sh.extents.push_back({svc->next_id, sh.chunks.size(), n});
+        svc->next_id += (int64_t)n;
+        for (size_t j = 0; j < n; ++j) {
+            const Chunk &c = added[into[i][j]];
+            sh.min_created = sh.chunks.empty() ? c.created_ticks : std::min(sh.min_created, c.created_ticks);
+            sh.max_created = sh.chunks.empty() ? c.created_ticks : std::max(sh.max_created, c.created_ticks);
+            sh.doc_stamps[c.document_id] = added_stamps.at(c.document_id);
+            sh.chunks.push_back(c);
+        }
+        if (!sh.dead.empty()) sh.dead.resize(sh.chunks.size(), 0);
+        svc->inserted_rows += done;
+    }
     return 1;
 }
 
@@ -279,7 +363,7 @@ int ensure_index(orrh_service *svc)
             std::vector<size_t> marked;
             for (size_t p = 0; p < sh.chunks.size(); ++p)
                 if (!sh.dead[p] && std::binary_search(stale.begin(), stale.end(), sh.chunks[p].document_id)) {
-                    ids.push_back(sh.id_base + (int64_t)p);
+                    ids.push_back(id_of(sh, p));
                     marked.push_back(p);
                 }
             int64_t done = 0;
@@ -323,6 +407,7 @@ int ensure_index(orrh_service *svc)
         for (const auto &c : added) delta_ok = delta_ok && c.created_ticks > newest;      // strictly newer: ties keep enumeration order
         delta_ok = delta_ok && (d == svc->dim || d == 0);
     }
+    bool merge_declined = false;                       // strictly newer chunks, but eight shards and deltas too large to merge: rebuild
     if (delta_ok && svc->shards.size() >= 8) {
         // Eight shards already: the DELTA shards (all but the oldest) and the new chunks become ONE shard; the oldest -- the
         // large one of a corpus that grows by uploads -- stays on the device untouched.  The delta shards are strictly newer
@@ -360,8 +445,13 @@ int ensure_index(orrh_service *svc)
             return ORR_OK;
         }
         delta_ok = false;
+        merge_declined = true;
     }
-    if (delta_ok) {
+    bool inserted = false;
+    if (!delta_ok && svc->insert_older && !changed && !svc->shards.empty() && !added.empty() && !merge_declined)
+        inserted = insert_older_chunks(svc, added, added_stamps, indexed, st) == 1;      // (0 or a failure: what happens without the option)
+    if (inserted) {
+    } else if (delta_ok) {
         Shard sh;
         int r = build_shard(svc, std::move(added), svc->dim, &sh);
         if (r != ORR_OK) return r;
@@ -394,7 +484,8 @@ int ensure_index(orrh_service *svc)
 const Chunk *chunk_of(const orrh_service *svc, int64_t row_id)
 {
     for (const auto &sh : svc->shards)
-        if (row_id >= sh.id_base && row_id < sh.id_base + (int64_t)sh.chunks.size()) return &sh.chunks[(size_t)(row_id - sh.id_base)];
+        for (const Extent &e : sh.extents)
+            if (row_id >= e.id_base && row_id < e.id_base + (int64_t)e.count) return &sh.chunks[e.first + (size_t)(row_id - e.id_base)];
     return nullptr;
 }
 
@@ -539,6 +630,25 @@ int64_t orrh_service_updated_rows(orrh_service *svc)
     if (!svc) return 0;
     std::lock_guard<std::mutex> l(svc->mu);
     return svc->updated_rows;
+}
+
+int64_t orrh_service_inserted_rows(orrh_service *svc)
+{
+    if (!svc) return 0;
+    std::lock_guard<std::mutex> l(svc->mu);
+    return svc->inserted_rows;
+}
+
+int orrh_service_set_option(orrh_service *svc, const char *name, int64_t value)
+{
+    if (!svc || !name) return fail(ORR_EINVAL, "orrh_service_set_option: null argument");
+    std::lock_guard<std::mutex> l(svc->mu);
+    if (strcmp(name, "insert_older") == 0) {
+        if (value != 0 && value != 1) return fail(ORR_EINVAL, "orrh_service_set_option: insert_older takes 0 or 1");
+        svc->insert_older = value != 0;
+        return ORR_OK;
+    }
+    return fail(ORR_EINVAL, std::string("orrh_service_set_option: unknown option ") + name);
 }
 
 int64_t orrh_service_tombstoned_rows(orrh_service *svc)

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "orr_escalation.h"
+#include "orr_insert_plan.h"
 #include "orr_kernels.h"
 #include "orr_lanes.h"
 #include "orr_token_index.h"
@@ -1063,6 +1064,8 @@ int orr_index_load(const orr_config *cfg, const char *path, orr_index **out)
             ORR_TRY(idx->d_dead.reserve(sizeof(int64_t) * idx->dead.size()));
             HIP_TRY(hipMemcpy(idx->d_dead.p, idx->dead.data(), sizeof(int64_t) * idx->dead.size(), hipMemcpyHostToDevice));
             idx->lanes.update_shared([&](LanePool::Shared &sh) { sh.dead_count = (int64_t)idx->dead.size(); });
+            // the host mirror must stay a descending sequence (orr_index_insert_rows plans on it, a cluster compares its ends)
+            orr::repair_dead_ticks(idx->h_created, idx->dead);
         }
         return ORR_OK;
     };
@@ -1090,7 +1093,8 @@ static int ensure_shadow(orr_index *idx)
     if (idx->shadow_ready || idx->shadow_failed || !idx->sealed || idx->n_rows <= 0 || idx->dim <= 0 || idx->dim % 64 != 0) return ORR_OK;
     const size_t bytes = orr::bf16_tiled_bytes(idx->n_rows, idx->dim);
     size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < bytes + bytes / 8 + ((size_t)4 << 30)) {   // keep 4 GiB for workspaces
+    // (a buffer that already holds the bytes -- the rebuild behind orr_index_insert_rows -- needs no new room)
+    if (idx->emb_shadow.cap < bytes && (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < bytes + bytes / 8 + ((size_t)4 << 30))) {   // keep 4 GiB for workspaces
         idx->shadow_failed = true;
         return ORR_OK;
     }
@@ -1113,7 +1117,8 @@ static int ensure_i8_shadow(orr_index *idx)
     if (idx->is_view || idx->i8_ready || idx->i8_failed || !idx->sealed || idx->n_rows <= 0 || idx->dim <= 0 || idx->dim % 128 != 0) return ORR_OK;
     const size_t bytes = orr::i8_tiled_bytes(idx->n_rows, idx->dim) + 28 * (size_t)idx->n_rows;
     size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < bytes + bytes / 8 + ((size_t)8 << 30)) {   // keep 8 GiB for workspaces
+    if (idx->emb_i8.cap < orr::i8_tiled_bytes(idx->n_rows, idx->dim) &&
+        (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < bytes + bytes / 8 + ((size_t)8 << 30))) {   // keep 8 GiB for workspaces
         idx->i8_failed = true;
         return ORR_OK;
     }
@@ -1474,6 +1479,266 @@ int orr_index_compact(orr_index *idx, int64_t *out_removed)
     idx->lanes.update_shared([](LanePool::Shared &sh) { sh.dead_count = 0; });
     for (orr_index *l : idx->lanes.drain()) orr_index_destroy(l);
     if (out_removed) *out_removed = n_dead;
+    return ORR_OK;
+}
+
+namespace {
+
+// wall-clock phases of orr_index_insert_rows among the kernel statistics (orr_index_set_profiling(1)): they are host-timed,
+// each ends in a stream synchronise
+void add_phase_stat(orr_index *idx, const char *name, std::chrono::steady_clock::time_point t0, double bytes)
+{
+    if (idx->profiling != 1) return;
+    KernelStat &st = idx->stats[(size_t)stat_slot(idx, name)];
+    st.launches += 1;
+    st.total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    st.algo_bytes += bytes;
+}
+
+// room for `rows` rows of embeddings in a SEALED shard: 1.5 x like append, exactly `rows` when that does not fit.  The old
+// array is freed only after the copy, so this needs a second copy of the embeddings for a moment.  Only d_emb grows: after
+// the seal the per-row scalar arrays are never written behind n_rows, they are replaced whole (compaction, insertion) by
+// arrays of cap_rows entries.
+int grow_sealed_capacity(orr_index *idx, int64_t rows)
+{
+    if (rows <= idx->cap_rows) return ORR_OK;
+    int64_t nc = std::max<int64_t>(std::max<int64_t>(rows, idx->cap_rows + idx->cap_rows / 2), 1024);
+    if (idx->dim > 0) {
+        int r = dev_grow(&idx->d_emb, (size_t)idx->n_rows * idx->dim, (size_t)nc * idx->dim, idx->stream);
+        if (r == ORR_ENOMEM && nc > rows) {
+            (void)hipGetLastError();
+            nc = rows;
+            r = dev_grow(&idx->d_emb, (size_t)idx->n_rows * idx->dim, (size_t)nc * idx->dim, idx->stream);
+        }
+        ORR_TRY(r);
+    }
+    idx->cap_rows = nc;
+    return ORR_OK;
+}
+
+}  // namespace
+
+int orr_index_insert_rows(orr_index *idx, int64_t n, int32_t dim, const float *emb, const int64_t *created_ticks,
+                          const uint8_t *content_lower, const uint64_t *content_off, const int64_t *row_ids, int64_t *out_inserted)
+{
+    if (out_inserted) *out_inserted = 0;
+    if (!idx) return fail(ORR_EINVAL, "orr_index_insert_rows: null index");
+    if (n < 0) return fail(ORR_EINVAL, "orr_index_insert_rows: negative row count");
+    if (n > 0 && !row_ids)
+        return fail(ORR_EINVAL, "orr_index_insert_rows: row_ids are required (positions are not unique ids once a shard was compacted)");
+    if (n > 0 && (!created_ticks || !content_off)) return fail(ORR_EINVAL, "orr_index_insert_rows: created_ticks and content_off are required");
+    if (n > 0 && dim != 0 && !emb) return fail(ORR_EINVAL, "orr_index_insert_rows: emb is NULL with dim %d", dim);
+    if (dim == 0 && emb) return fail(ORR_EINVAL, "orr_index_insert_rows: dim 0 (rows without an embedding) takes emb = NULL");
+    if (idx->is_view) return fail(ORR_EINVAL, "orr_index_insert_rows: insert into the owning index, not into a view");
+    LanePool::Exclusive all(pool_of(idx));             // no search in flight while rows move
+    std::lock_guard<std::mutex> lock(idx->mu);
+    if (!idx->sealed) return fail(ORR_ESTATE, "orr_index_insert_rows: the index is not sealed (orr_index_append takes rows before the seal)");
+    if (idx->user_views.load() > 0)
+        return fail(ORR_ESTATE, "orr_index_insert_rows: %d view(s) of this index are alive (orr_index_view): destroy them first", idx->user_views.load());
+    if (dim != 0 && dim != idx->dim)
+        return fail(ORR_EDIM, "orr_index_insert_rows: dim %d differs from the index dimension %d", dim, idx->dim);
+    if (idx->n_rows + n >= (int64_t)0xFFFFFFFFll) return fail(ORR_EINVAL, "orr_index_insert_rows: more than 2^32-1 rows in one shard");
+    if (n == 0) return ORR_OK;
+    ORR_TRY(bind_device(idx));
+    hipStream_t s = idx->stream;
+    const int32_t D = idx->dim;
+    const int64_t n_old = idx->n_rows, total = n_old + n;
+    auto t_phase = std::chrono::steady_clock::now();
+
+    // ---- the new rows' scalars and text come to the host; the merge plan (orr_insert_plan.h)
+    std::vector<int64_t> new_ticks((size_t)n), new_ids((size_t)n);
+    std::vector<uint64_t> off((size_t)n + 1);
+    HIP_TRY(hipMemcpy(new_ticks.data(), created_ticks, sizeof(int64_t) * (size_t)n, hipMemcpyDefault));
+    HIP_TRY(hipMemcpy(new_ids.data(), row_ids, sizeof(int64_t) * (size_t)n, hipMemcpyDefault));
+    HIP_TRY(hipMemcpy(off.data(), content_off, sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyDefault));
+    std::vector<uint32_t> new_len((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        if (off[(size_t)i + 1] < off[(size_t)i]) return fail(ORR_EINVAL, "orr_index_insert_rows: content_off is not monotone at row %lld", (long long)i);
+        if (off[(size_t)i + 1] - off[(size_t)i] >= (1ull << 31)) return fail(ORR_EINVAL, "orr_index_insert_rows: content of row %lld exceeds 2 GiB", (long long)i);
+        new_len[(size_t)i] = (uint32_t)(off[(size_t)i + 1] - off[(size_t)i]);
+    }
+    const uint64_t text_bytes = off[(size_t)n] - off[0];
+    if (text_bytes > 0 && !content_lower) return fail(ORR_EINVAL, "orr_index_insert_rows: content_lower is NULL");
+    std::vector<uint8_t> text((size_t)text_bytes + 16, 0x20);
+    if (text_bytes) HIP_TRY(hipMemcpy(text.data(), content_lower + off[0], (size_t)text_bytes, hipMemcpyDefault));
+    const orr::InsertPlan pl = orr::make_insert_plan(idx->h_created.data(), n_old, new_ticks.data(), n);
+    const int64_t first = pl.first_moved, n_moved = total - first;     // rows in front of `first` stay where they are
+
+    // ---- token index: the new rows' own index (in merged rank order), merged on the host into the shard's (one pass over the
+    // old postings, as compaction's renumbering; the old text left HBM at the seal and is not needed)
+    std::vector<int64_t> r_ticks((size_t)n), r_ids((size_t)n);
+    orr::TokenIndexHost ti_old, ti_new;
+    {
+        std::vector<uint64_t> r_start((size_t)n);
+        std::vector<uint32_t> r_len((size_t)n);
+        for (int64_t k = 0; k < n; ++k) {
+            const size_t j = (size_t)pl.order[(size_t)k];
+            r_ticks[(size_t)k] = new_ticks[j]; r_ids[(size_t)k] = new_ids[j];
+            r_start[(size_t)k] = off[j] - off[0]; r_len[(size_t)k] = new_len[j];
+        }
+        orr::TokenIndexHost ti_add;
+        const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+        orr::build_token_index(text.data(), r_start.data(), r_len.data(), n, (int)std::min(hw, 32u), ti_add);
+        const size_t V = (size_t)idx->n_tokens;
+        ti_old.vstart.resize(V); ti_old.vlen.resize(V); ti_old.post_off.assign(V + 1, 0); ti_old.post_rows.resize((size_t)idx->n_postings);
+        if (V) {
+            HIP_TRY(hipMemcpy(ti_old.vstart.data(), idx->d_vstart, sizeof(uint64_t) * V, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(ti_old.vlen.data(), idx->d_vlen, sizeof(uint32_t) * V, hipMemcpyDeviceToHost));
+            ti_old.vpool.resize((size_t)orr::vocab_pool_bytes(ti_old));
+            HIP_TRY(hipMemcpy(ti_old.vpool.data(), idx->d_vpool, ti_old.vpool.size(), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(ti_old.post_off.data(), idx->d_post_off, sizeof(uint64_t) * (V + 1), hipMemcpyDeviceToHost));
+        }
+        if (idx->n_postings) HIP_TRY(hipMemcpy(ti_old.post_rows.data(), idx->d_post_rows, sizeof(uint32_t) * ti_old.post_rows.size(), hipMemcpyDeviceToHost));
+        orr::merge_token_index(ti_old, ti_add, pl, ti_new);
+        ti_old = orr::TokenIndexHost();
+    }
+    add_phase_stat(idx, "insert_token_index_host", t_phase, 4.0 * (double)ti_new.post_rows.size());
+    std::vector<int64_t> src((size_t)n_moved);
+    orr::plan_sources(pl, first, total, src.data());
+    const std::vector<int64_t> new_dead = orr::remap_dead(pl, idx->dead);
+
+    // ---- every allocation comes before the first row moves: ORR_ENOMEM leaves the shard as it was
+    const int64_t chunk = D > 0 ? std::max<int64_t>(1, ((int64_t)256 << 20) / ((int64_t)sizeof(float) * D)) : total;
+    const bool old_rows_move = first < n_old;
+    ORR_TRY(grow_sealed_capacity(idx, total));
+    struct Fresh {
+        int64_t *created = nullptr, *ids = nullptr, *norms = nullptr, *src = nullptr, *add_ticks = nullptr, *add_ids = nullptr, *add_norms = nullptr;
+        uint8_t *vpool = nullptr; uint64_t *vstart = nullptr, *post_off = nullptr; uint32_t *vlen = nullptr, *post_rows = nullptr;
+        DevBuf stage, bounce;
+        ~Fresh()
+        {
+            for (void *p : {(void *)created, (void *)ids, (void *)norms, (void *)src, (void *)add_ticks, (void *)add_ids, (void *)add_norms,
+                            (void *)vpool, (void *)vstart, (void *)post_off, (void *)vlen, (void *)post_rows})
+                if (p) (void)hipFree(p);
+            stage.release(); bounce.release();
+        }
+    } fr;
+    const size_t cap = (size_t)std::max<int64_t>(idx->cap_rows, 1);
+    ORR_TRY(dev_alloc(&fr.created, cap));
+    ORR_TRY(dev_alloc(&fr.ids, cap));
+    ORR_TRY(dev_alloc(&fr.norms, cap));
+    ORR_TRY(dev_alloc(&fr.src, (size_t)n_moved));
+    ORR_TRY(dev_alloc(&fr.add_ticks, (size_t)n));
+    ORR_TRY(dev_alloc(&fr.add_ids, (size_t)n));
+    ORR_TRY(dev_alloc(&fr.add_norms, (size_t)n));
+    ORR_TRY(dev_alloc(&fr.vpool, ti_new.vpool.size() + orr::kScanPoolSlack));
+    ORR_TRY(dev_alloc(&fr.vstart, ti_new.vstart.size()));
+    ORR_TRY(dev_alloc(&fr.vlen, ti_new.vlen.size()));
+    ORR_TRY(dev_alloc(&fr.post_off, ti_new.post_off.size()));
+    ORR_TRY(dev_alloc(&fr.post_rows, ti_new.post_rows.size()));
+    if (D > 0) {
+        ORR_TRY(fr.stage.reserve(sizeof(float) * (size_t)std::min<int64_t>(chunk, n) * D));
+        if (old_rows_move) ORR_TRY(fr.bounce.reserve(sizeof(float) * (size_t)std::min<int64_t>(chunk, n_moved) * D));
+    }
+    if (!new_dead.empty()) ORR_TRY(idx->d_dead.reserve(sizeof(int64_t) * new_dead.size()));
+
+    auto body = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(fr.src, src.data(), sizeof(int64_t) * (size_t)n_moved, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(fr.add_ticks, r_ticks.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(fr.add_ids, r_ids.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(fr.add_norms, 0, sizeof(double) * (size_t)n, s));
+        // ---- embeddings: IN PLACE.  Rows only move towards higher positions, so the destination chunks go from the LAST to the
+        // first: a chunk's destination never reaches rows an earlier chunk (in position) still has to read.  A chunk none of whose
+        // old sources lies inside it is written directly; the others pass through the bounce buffer, as in compaction.  The new
+        // rows of a chunk come through the staging buffer, where their exact norms are taken by the kernel the seal uses.
+        t_phase = std::chrono::steady_clock::now();
+        if (D > 0) {
+            if (dim == 0) HIP_TRY(hipMemsetAsync(fr.stage.p, 0, sizeof(float) * (size_t)std::min<int64_t>(chunk, n) * D, s));   // zero rows, norm 0 (as append)
+            for (int64_t d1 = total; d1 > first;) {
+                const int64_t d0 = std::max<int64_t>(first, d1 - chunk), m = d1 - d0;
+                const int64_t k0 = (int64_t)(std::lower_bound(pl.new_pos.begin(), pl.new_pos.end(), d0) - pl.new_pos.begin());
+                const int64_t k1 = (int64_t)(std::lower_bound(pl.new_pos.begin(), pl.new_pos.end(), d1) - pl.new_pos.begin());
+                if (k1 > k0 && dim != 0) {
+                    for (int64_t k = k0; k < k1;) {                                 // runs of consecutive input rows go in one copy
+                        int64_t e = k + 1;
+                        while (e < k1 && pl.order[(size_t)e] == pl.order[(size_t)e - 1] + 1) ++e;
+                        HIP_TRY(hipMemcpyAsync(fr.stage.as<float>() + (size_t)(k - k0) * D, emb + (size_t)pl.order[(size_t)k] * D,
+                                               sizeof(float) * (size_t)(e - k) * D, hipMemcpyDefault, s));
+                        k = e;
+                    }
+                    HIP_TRY(orr::launch_dot_exact(fr.stage.as<float>(), k1 - k0, D, nullptr, 1, true, reinterpret_cast<double *>(fr.add_norms) + k0, k1 - k0, s));
+                }
+                const int64_t p_hi = d1 - k1;                                       // old positions [d0 - k0, p_hi) land in this chunk
+                const bool direct = p_hi <= d0 - k0 || p_hi <= d0;
+                float *dst = idx->d_emb + (size_t)d0 * D;
+                {
+                    Timed t(idx, direct ? "merge_rows_f32_direct" : "merge_rows_f32_bounce", 8.0 * (double)m * D);
+                    HIP_TRY(orr::launch_merge_rows_f32(idx->d_emb, fr.stage.as<float>(), fr.src + (d0 - first), k0, direct ? dst : fr.bounce.as<float>(), m, D, s));
+                }
+                if (!direct) HIP_TRY(hipMemcpyAsync(dst, fr.bounce.p, sizeof(float) * (size_t)m * D, hipMemcpyDeviceToDevice, s));
+                d1 = d0;
+            }
+            HIP_TRY(hipStreamSynchronize(s));
+            collect_events(idx);
+            add_phase_stat(idx, "insert_move_rows", t_phase, 8.0 * (double)n_moved * D);
+        }
+        // ---- per-row scalars: merged into new arrays through the same source list (the norms as bit patterns; a deleted row's
+        // overwritten norm and timestamp travel with it)
+        t_phase = std::chrono::steady_clock::now();
+        if (first > 0) {
+            HIP_TRY(hipMemcpyAsync(fr.created, idx->d_created, sizeof(int64_t) * (size_t)first, hipMemcpyDeviceToDevice, s));
+            HIP_TRY(hipMemcpyAsync(fr.ids, idx->d_row_ids, sizeof(int64_t) * (size_t)first, hipMemcpyDeviceToDevice, s));
+            HIP_TRY(hipMemcpyAsync(fr.norms, idx->d_norm_b, sizeof(double) * (size_t)first, hipMemcpyDeviceToDevice, s));
+        }
+        HIP_TRY(orr::launch_merge_i64(idx->d_created, fr.add_ticks, fr.src, fr.created + first, n_moved, s));
+        HIP_TRY(orr::launch_merge_i64(idx->d_row_ids, fr.add_ids, fr.src, fr.ids + first, n_moved, s));
+        HIP_TRY(orr::launch_merge_i64(reinterpret_cast<const int64_t *>(idx->d_norm_b), fr.add_norms, fr.src, fr.norms + first, n_moved, s));
+        // ---- token index
+        HIP_TRY(hipMemsetAsync(fr.vpool, 0x20, ti_new.vpool.size() + orr::kScanPoolSlack, s));
+        if (!ti_new.vpool.empty()) HIP_TRY(hipMemcpyAsync(fr.vpool, ti_new.vpool.data(), ti_new.vpool.size(), hipMemcpyHostToDevice, s));
+        if (!ti_new.vstart.empty()) {
+            HIP_TRY(hipMemcpyAsync(fr.vstart, ti_new.vstart.data(), sizeof(uint64_t) * ti_new.vstart.size(), hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(fr.vlen, ti_new.vlen.data(), sizeof(uint32_t) * ti_new.vlen.size(), hipMemcpyHostToDevice, s));
+        }
+        HIP_TRY(hipMemcpyAsync(fr.post_off, ti_new.post_off.data(), sizeof(uint64_t) * ti_new.post_off.size(), hipMemcpyHostToDevice, s));
+        if (!ti_new.post_rows.empty())
+            HIP_TRY(hipMemcpyAsync(fr.post_rows, ti_new.post_rows.data(), sizeof(uint32_t) * ti_new.post_rows.size(), hipMemcpyHostToDevice, s));
+        if (!new_dead.empty()) HIP_TRY(hipMemcpyAsync(idx->d_dead.p, new_dead.data(), sizeof(int64_t) * new_dead.size(), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        add_phase_stat(idx, "insert_scalars_and_upload", t_phase, 48.0 * (double)n_moved + 4.0 * (double)ti_new.post_rows.size());
+        return ORR_OK;
+    };
+    const int r = body();
+    if (r != ORR_OK)                                   // (rows may have moved: the shard is unusable, the caller rebuilds it)
+        return fail(ORR_EDEVICE, "orr_index_insert_rows: failed part way, rebuild the shard: %s", std::string(orr_last_error()).c_str());
+    std::swap(idx->d_created, fr.created);
+    std::swap(idx->d_row_ids, fr.ids);
+    { int64_t *old_norms = reinterpret_cast<int64_t *>(idx->d_norm_b); idx->d_norm_b = reinterpret_cast<double *>(fr.norms); fr.norms = old_norms; }
+    std::swap(idx->d_vpool, fr.vpool); std::swap(idx->d_vstart, fr.vstart); std::swap(idx->d_vlen, fr.vlen);
+    std::swap(idx->d_post_off, fr.post_off); std::swap(idx->d_post_rows, fr.post_rows);          // (fr frees the old arrays)
+    idx->n_tokens = (int64_t)ti_new.vstart.size();
+    idx->n_postings = ti_new.post_rows.size();
+    // ---- host mirrors and what hangs on positions
+    {
+        std::vector<int64_t> hc = orr::merge_rows(pl, idx->h_created.data(), new_ticks.data());
+        std::vector<uint32_t> hl = orr::merge_rows(pl, idx->h_clen.data(), new_len.data());
+        idx->h_created.swap(hc);
+        idx->h_clen.swap(hl);
+        idx->h_cprefix.assign((size_t)total + 1, 0);
+        for (int64_t p = 0; p < total; ++p) idx->h_cprefix[(size_t)p + 1] = idx->h_cprefix[(size_t)p] + idx->h_clen[(size_t)p];
+    }
+    idx->n_rows = total;
+    idx->dead = new_dead;                              // (their number is unchanged: the lanes' shared dead_count stays)
+    idx->id_index.clear();
+    idx->n_vlong = -1; idx->n_vmid = 0;
+    idx->bitmaps_clean = 0; idx->bitmaps_clean_of = nullptr;
+    idx->tok_bm.release(); idx->tok_bm_index.release(); idx->n_tok_bm = -1; idx->tok_bm_words = 0;
+    for (orr_index *l : idx->lanes.drain()) orr_index_destroy(l);      // they borrow arrays that were replaced; remade on demand
+    // ---- a shadow that was ready is rebuilt now, from the moved rows, by the routine set_option("two_stage") uses: the next
+    // search does not pay for it.  One that did not exist stays unbuilt.
+    t_phase = std::chrono::steady_clock::now();
+    const bool had_i8 = idx->i8_ready, had_bf16 = idx->shadow_ready;
+    idx->i8_ready = false; idx->i8_failed = false; idx->shadow_ready = false; idx->shadow_failed = false;
+    auto drop_i8 = [idx] { idx->emb_i8.release(); idx->i8_scale.release(); idx->i8_rel_err.release(); idx->i8_rel_hat.release(); idx->i8_rowf.release(); };
+    // buffers too small for the grown shard go BEFORE the rebuild asks how much memory is free; buffers that still fit are used again
+    if (!had_i8 || idx->emb_i8.cap < orr::i8_tiled_bytes(total, D) || idx->i8_rowf.cap < sizeof(float4) * (size_t)total) drop_i8();
+    if (!had_bf16 || idx->emb_shadow.cap < orr::bf16_tiled_bytes(total, D)) idx->emb_shadow.release();
+    if (out_inserted) *out_inserted = n;
+    // The rows are in and the shard is whole whatever happens to a shadow: one that cannot be rebuilt now (no room, or a HIP error
+    // in its build) is dropped, nothing stays marked as failed, and the next search that wants it tries again as on a new shard.
+    if (had_i8 && (ensure_i8_shadow(idx) != ORR_OK || !idx->i8_ready)) { (void)hipGetLastError(); drop_i8(); idx->i8_ready = false; idx->i8_failed = false; }
+    if (had_bf16 && (ensure_shadow(idx) != ORR_OK || !idx->shadow_ready)) { (void)hipGetLastError(); idx->emb_shadow.release(); idx->shadow_ready = false; idx->shadow_failed = false; }
+    if (had_i8 || had_bf16) add_phase_stat(idx, "insert_shadow_rebuild", t_phase, 0.0);
     return ORR_OK;
 }
 
@@ -3762,6 +4027,40 @@ int orr_cluster_compact(orr_cluster *c, int64_t *out_removed)
     ORR_TRY(place_shards(c));                          // the shards behind a compacted one move up in the global order
     if (out_removed) for (int64_t r : removed) *out_removed += r;
     return ORR_OK;
+}
+
+int orr_cluster_insert_rows(orr_cluster *c, int32_t shard, int64_t n, int32_t dim, const float *emb, const int64_t *created_ticks,
+                            const uint8_t *content_lower, const uint64_t *content_off, const int64_t *row_ids, int64_t *out_inserted)
+{
+    if (out_inserted) *out_inserted = 0;
+    if (!c) return fail(ORR_EINVAL, "orr_cluster_insert_rows: null cluster");
+    if (shard < 0 || shard >= (int32_t)c->shards.size()) return fail(ORR_EINVAL, "orr_cluster_insert_rows: no shard %d", shard);
+    if (n < 0) return fail(ORR_EINVAL, "orr_cluster_insert_rows: negative row count");
+    if (n > 0 && !created_ticks) return fail(ORR_EINVAL, "orr_cluster_insert_rows: created_ticks are required");
+    std::unique_lock<std::shared_mutex> lock(c->mu);   // no search in flight on the cluster
+    if (!c->sealed) return fail(ORR_ESTATE, "orr_cluster_insert_rows: the cluster is not sealed");
+    if (n > 0) {
+        // the order orr_cluster_seal checks, BEFORE anything is written: the new rows against the nearest non-empty neighbours
+        orr_index *sh = c->shards[(size_t)shard];
+        ORR_TRY(bind_device(sh));
+        std::vector<int64_t> ticks((size_t)n);
+        HIP_TRY(hipMemcpy(ticks.data(), created_ticks, sizeof(int64_t) * (size_t)n, hipMemcpyDefault));
+        const auto mm = std::minmax_element(ticks.begin(), ticks.end());
+        for (int32_t g = shard - 1; g >= 0; --g)
+            if (!c->shards[(size_t)g]->h_created.empty()) {
+                if (*mm.second > c->shards[(size_t)g]->h_created.back())
+                    return fail(ORR_EINVAL, "orr_cluster_insert_rows: a row is newer than a row of shard %d in front of shard %d", g, shard);
+                break;
+            }
+        for (int32_t g = shard + 1; g < (int32_t)c->shards.size(); ++g)
+            if (!c->shards[(size_t)g]->h_created.empty()) {
+                if (*mm.first < c->shards[(size_t)g]->h_created.front())
+                    return fail(ORR_EINVAL, "orr_cluster_insert_rows: a row is older than a row of shard %d behind shard %d", g, shard);
+                break;
+            }
+    }
+    ORR_TRY(orr_index_insert_rows(c->shards[(size_t)shard], n, dim, emb, created_ticks, content_lower, content_off, row_ids, out_inserted));
+    return place_shards(c);                            // the shards behind it move down in the global order
 }
 
 int orr_cluster_search_batch(orr_cluster *c, int32_t B, int32_t dim, const float *q_host, const uint8_t *terms_utf8,

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/omnirecall_hip.h"
+#include "orr_layout.h"
 
 #include <atomic>
 
@@ -79,9 +80,7 @@ hipError_t launch_dot_exact(const float *E, int64_t n_rows, int32_t D, const flo
 // Pool layout: row r occupies [cstart[r], cstart[r]+clen[r]), cstart 16-byte aligned,
 // followed by 1..16 space bytes; the pool is over-allocated by kScanPoolSlack bytes.
 // Terms must not contain whitespace bytes.
-constexpr size_t kScanPoolSlack = 2048;
-constexpr uint64_t kRowAlign = 16;
-inline uint64_t padded_row_bytes(uint64_t len) { return (len / kRowAlign + 1) * kRowAlign; }
+// (kScanPoolSlack, kRowAlign, padded_row_bytes: orr_layout.h)
 hipError_t launch_keyword_scan(const uint8_t *pool, const uint64_t *cstart, const uint32_t *clen, int64_t n_rows,
                                const uint8_t *term_pool, const ScanTerm *terms, int32_t n_terms,
                                const uint32_t *q_term_off, int32_t B, uint16_t *matches,
@@ -371,6 +370,13 @@ hipError_t launch_records_from_sorted(const unsigned long long *keys, const uint
 hipError_t launch_gather_rows_f32(const float *src, float *dst, const int64_t *perm, int64_t n, int32_t D,
                                   hipStream_t s);
 hipError_t launch_gather_i64(const int64_t *src, int64_t *dst, const int64_t *perm, int64_t n, hipStream_t s);
+// orr_index_insert_rows, the two-source merge: dst row r (r = 0..n-1) <- E row src_idx[r] when src_idx[r] >= 0, else row
+// ~src_idx[r] - stage_base of `stage` ([.][D] fp32, the new rows of this round).  16-byte vectors when D % 4 == 0.  dst may
+// point into E when no source row of the launch lies inside [dst, dst + n rows).
+hipError_t launch_merge_rows_f32(const float *E, const float *stage, const int64_t *src_idx, int64_t stage_base, float *dst,
+                                 int64_t n, int32_t D, hipStream_t s);
+// ... and one 8-byte value per row: dst[r] = src_idx[r] >= 0 ? old[src_idx[r]] : add[~src_idx[r]] (dst a separate array).
+hipError_t launch_merge_i64(const int64_t *old, const int64_t *add, const int64_t *src_idx, int64_t *dst, int64_t n, hipStream_t s);
 // Content rows: dst row r <- src row perm[r] (perm == nullptr: identity).
 hipError_t launch_gather_content(const uint8_t *src_pool, const uint64_t *src_start, const uint32_t *src_len,
                                  uint8_t *dst_pool, const uint64_t *dst_start, const int64_t *perm, int64_t n,

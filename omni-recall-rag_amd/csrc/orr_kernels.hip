@@ -1262,6 +1262,46 @@ __global__ __launch_bounds__(256) void gather_u32_kernel(const uint32_t *__restr
         dst[r] = src[perm[r]];
 }
 
+// ---- orr_index_insert_rows: the two-source row merge.  Destination row r takes E row src_idx[r] when that is >= 0, else row
+// ~src_idx[r] - stage_base of the staging buffer (the new rows of this round).  One wave per row; whole rows move as 16-byte
+// vectors when D % 4 == 0 (four in flight per lane), element by element otherwise.  E and dst may be the SAME array (rows
+// moving up inside the shard): the caller guarantees that no source row of a launch lies inside its destination range.
+__global__ __launch_bounds__(256) void merge_rows_f32_kernel(const float *E, const float *stage, const int64_t *__restrict__ src_idx,
+                                                             int64_t stage_base, float *dst, int64_t n, int32_t D)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t wave_id = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t r = wave_id; r < n; r += n_waves) {
+        const int64_t si = src_idx[r];
+        const float *s = si >= 0 ? E + si * (int64_t)D : stage + (~si - stage_base) * (int64_t)D;
+        float *d = dst + r * (int64_t)D;
+        if ((D & 3) == 0) {
+            const float4 *s4 = reinterpret_cast<const float4 *>(s);
+            float4 *d4 = reinterpret_cast<float4 *>(d);
+            const int32_t n4 = D >> 2;
+            int32_t i = lane;
+            for (; i + 192 < n4; i += 256) {
+                const float4 a = s4[i], b = s4[i + 64], c = s4[i + 128], e = s4[i + 192];
+                d4[i] = a; d4[i + 64] = b; d4[i + 128] = c; d4[i + 192] = e;
+            }
+            for (; i < n4; i += 64) d4[i] = s4[i];
+        } else {
+            for (int32_t i = lane; i < D; i += 64) d[i] = s[i];
+        }
+    }
+}
+
+// the same choice for one 8-byte value per row (timestamps, ids, norms as bit patterns); add[] is indexed by ~src_idx[r]
+__global__ __launch_bounds__(256) void merge_i64_kernel(const int64_t *__restrict__ old, const int64_t *__restrict__ add,
+                                                        const int64_t *__restrict__ src_idx, int64_t *__restrict__ dst, int64_t n)
+{
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t si = src_idx[r];
+        dst[r] = si >= 0 ? old[si] : add[~si];
+    }
+}
+
 // ---- deleted rows (orr_index_delete_rows).  A deleted row keeps its position; its norm and timestamp are
 // overwritten so that it scores at most 0.2 (keyword part only) and its records are flagged for the host
 // finish, which drops them.
@@ -1314,6 +1354,24 @@ hipError_t launch_gather_i64(const int64_t *src, int64_t *dst, const int64_t *pe
 {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(gather_i64_kernel, dim3(capped_blocks(n, 256)), dim3(256), 0, s, src, dst, perm, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_rows_f32(const float *E, const float *stage, const int64_t *src_idx, int64_t stage_base, float *dst,
+                                 int64_t n, int32_t D, hipStream_t s)
+{
+    if (n <= 0 || D <= 0) return hipSuccess;
+    // one wave per row up to 2^20 workgroups (a chunk of 256 MiB has fewer rows than that for D >= 64): a capped grid would
+    // give some waves one row more than others, a tenth of the launch's time at 12 KB rows
+    const unsigned blocks = (unsigned)std::min<int64_t>((n + 3) / 4, (int64_t)1 << 20);
+    hipLaunchKernelGGL(merge_rows_f32_kernel, dim3(blocks), dim3(256), 0, s, E, stage, src_idx, stage_base, dst, n, D);
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_i64(const int64_t *old, const int64_t *add, const int64_t *src_idx, int64_t *dst, int64_t n, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(merge_i64_kernel, dim3(capped_blocks(n, 256)), dim3(256), 0, s, old, add, src_idx, dst, n);
     return hipGetLastError();
 }
 

@@ -12,6 +12,8 @@
 // (char.IsWhiteSpace), on the UTF-8 bytes of the already lowercased content.
 #include "orr_token_index.h"
 
+#include "orr_layout.h"
+
 #include <algorithm>
 #include <cstring>
 #include <string_view>
@@ -140,7 +142,7 @@ void build_token_index(const uint8_t *pool, const uint64_t *cstart, const uint32
     for (size_t v = 0; v < V; ++v) {
         out.vstart[v] = cur;
         out.vlen[v] = (uint32_t)vocab[v].size();
-        cur += (vocab[v].size() / 16 + 1) * 16;
+        cur += padded_row_bytes(vocab[v].size());
     }
     out.vpool.assign(cur, 0x20);
     for (size_t v = 0; v < V; ++v) memcpy(out.vpool.data() + out.vstart[v], vocab[v].data(), vocab[v].size());

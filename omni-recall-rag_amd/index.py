@@ -146,6 +146,33 @@ class RecallIndex:
         N.check(N.hip.orr_index_update_rows(self._h, n, _ptr(row_ids), dim, _ptr(emb), C.cast(C.byref(done), C.c_void_p)))
         return int(done.value)
 
+    @staticmethod
+    def _row_args(emb, created_ticks, content_lower, content_off, row_ids):
+        if content_off is None:
+            content_lower, content_off = pack_contents(content_lower)
+        n = int(content_off.shape[0]) - 1
+        if not _is_torch(created_ticks):
+            created_ticks = np.ascontiguousarray(created_ticks, dtype=np.int64)
+        if emb is not None and not _is_torch(emb):
+            emb = np.ascontiguousarray(emb, dtype=np.float32)
+        if row_ids is None:
+            raise ValueError("insert_rows: row_ids are required")
+        if not _is_torch(row_ids):
+            row_ids = np.ascontiguousarray(row_ids, dtype=np.int64).reshape(-1)
+        if int(created_ticks.shape[0]) != n or int(row_ids.shape[0]) != n or (emb is not None and (emb.ndim != 2 or int(emb.shape[0]) != n)):
+            raise ValueError(f"insert_rows: {n} rows of content need [{n}] ticks, [{n}] row ids and [{n}, dim] vectors")
+        dim = 0 if emb is None else int(emb.shape[1])
+        return n, dim, emb, created_ticks, content_lower, content_off, row_ids
+
+    def insert_rows(self, emb, created_ticks, content_lower, content_off=None, row_ids=None) -> int:
+        """orr_index_insert_rows: rows into the SEALED shard in place, arguments as append() except that row_ids are
+        required.  The shard afterwards is what a seal of (the old rows, then these) would make.  Returns the rows inserted."""
+        n, dim, emb, created_ticks, content_lower, content_off, row_ids = self._row_args(emb, created_ticks, content_lower, content_off, row_ids)
+        done = C.c_int64(0)
+        N.check(N.hip.orr_index_insert_rows(self._h, n, dim, _ptr(emb), _ptr(created_ticks), _ptr(content_lower), _ptr(content_off),
+                                            _ptr(row_ids), C.cast(C.byref(done), C.c_void_p)))
+        return int(done.value)
+
     @property
     def live_rows(self) -> int:
         return int(N.hip.orr_index_live_rows(self._h))
@@ -348,6 +375,15 @@ class RecallCluster:
         """orr_cluster_compact: every shard without its deleted rows, placed in the global order again."""
         done = C.c_int64(0)
         N.check(N.hip.orr_cluster_compact(self._h, C.cast(C.byref(done), C.c_void_p)))
+        return int(done.value)
+
+    def insert_rows(self, shard: int, emb, created_ticks, content_lower, content_off=None, row_ids=None) -> int:
+        """orr_cluster_insert_rows: rows into sealed shard `shard` in place (they must keep the shards' order: no newer than
+        the shard in front, no older than the shard behind); the shards are then placed in the global order again."""
+        n, dim, emb, created_ticks, content_lower, content_off, row_ids = RecallIndex._row_args(emb, created_ticks, content_lower, content_off, row_ids)
+        done = C.c_int64(0)
+        N.check(N.hip.orr_cluster_insert_rows(self._h, int(shard), n, dim, _ptr(emb), _ptr(created_ticks), _ptr(content_lower),
+                                              _ptr(content_off), _ptr(row_ids), C.cast(C.byref(done), C.c_void_p)))
         return int(done.value)
 
     def search_stats(self, reset: bool = False) -> dict:

@@ -137,6 +137,15 @@ class RecallSearchService:
         """Rows whose vectors a reindex replaced in place (same chunk ids, contents and CreatedAtTicks), so far."""
         return int(N.host.orrh_service_updated_rows(self._h))
 
+    def SetOption(self, name: str, value: int) -> None:
+        """orrh_service_set_option.  "insert_older" = 1: uploads that are not strictly newer than everything indexed are
+        inserted into the sealed shards in place where that gives the order of a rebuild, instead of rebuilding."""
+        _check(N.host.orrh_service_set_option(self._h, name.encode(), int(value)))
+
+    def InsertedRows(self) -> int:
+        """Rows inserted into sealed shards in place ("insert_older"), so far."""
+        return int(N.host.orrh_service_inserted_rows(self._h))
+
     def close(self):
         if self._h:
             N.host.orrh_service_destroy(self._h)
