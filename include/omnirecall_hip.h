@@ -119,7 +119,8 @@ typedef struct orr_search_stats {
     int64_t pass_mode;           /* what the LAST device pass ran: 0 no two-stage pass (exact kernel, unfused batched pass,
                                     large-k sort); 1 two-stage on the int8 shadow; 2 two-stage on the bf16 shadow; 3 two-stage
                                     WITHOUT a shadow (fp32 rows converted inside the kernel: "two_stage" = 2, or the shadow
-                                    did not fit in device memory and "two_stage" = 1 fell back)                          */
+                                    did not fit in device memory and "two_stage" = 1 fell back); 4 scoped pass
+                                    (orr_search_batch_scoped: no screen, the listed rows re-scored exactly)              */
     int64_t reserved[1];         /* orr_cluster_search_stats: record exchanges done by RCCL all-gather ("exchange" = 1)      */
 } orr_search_stats;
 
@@ -328,6 +329,52 @@ int orr_index_compact(orr_index *idx, int64_t *out_removed);
 int orr_index_insert_rows(orr_index *idx, int64_t n, int32_t dim, const float *emb,
                           const int64_t *created_ticks, const uint8_t *content_lower,
                           const uint64_t *content_off, const int64_t *row_ids, int64_t *out_inserted);
+
+/* ---- scoped search: rank only the rows a caller lists ---------------------------------------
+ * "Search inside these documents" (IIngestionStore.GetChunksByDocumentIdAsync, IIngestionStore.cs:11, and the per-document
+ * endpoints), or inside whatever a host's own metadata filter selected.  Query b's scope S_b is a multiset of row ids (the ids
+ * of orr_index_append): scope_ids[scope_off[b] .. scope_off[b+1]); scope_off == NULL: all B queries share the whole list.
+ * scope_ids is host or device memory, scope_off[B+1] host memory.
+ *   result      what orr_search_batch would return on a shard sealed from scratch from only the LIVE rows whose id is in S_b, in
+ *               their present candidate order, arguments otherwise the same: rows, order and fp64 scores bit for bit.
+ *   ids         unknown ids and ids of deleted rows are skipped; an id listed twice counts once; an id carried by several
+ *               rows (duplicate ids at append) brings every live one of them, as in orr_index_update_rows.
+ *   candidate_limit  counts scoped live rows only: the first max(1, candidate_limit) of them in candidate order take part
+ *               (GetRecentChunksAsync(maxCount) over a store that holds only those chunks).
+ *   empty       an empty scope, or one without a live row, gives out_counts[b] = 0.
+ * topk, dim 0 / another dimension, rows without an embedding, NaN order and ties: as orr_search_batch.
+ * A scoped search is a search: it takes a lane, runs beside other searches, works on views, counts in orr_search_stats
+ * (pass_mode 4).  It never builds a shadow and never runs a pass over all rows: the listed ids are resolved on the device
+ * through a table of the shard's (id, position) pairs sorted by id -- 12 bytes per row, built at the first scoped search
+ * (ORR_ENOMEM when it does not fit), shared by the lanes and views, dropped by orr_index_insert_rows and orr_index_compact,
+ * never saved -- and the exact re-score of the two-stage pass reads the listed rows only: about 4 x dim bytes of HBM per
+ * (query, scoped row) pair.  Large scopes shared by many queries are therefore the wrong tool.
+ * "Never builds a shadow" is about the search itself: a concurrent search that makes another lane of the handle goes through
+ * orr_index_view's preparation, which builds the shadow of a two-stage-sized shard with "two_stage" = 1 as for any search.
+ * One query may bring at most 4,194,240 scoped rows (after the candidate_limit clip) to a search: ORR_EINVAL beyond that.
+ * Argument errors (ORR_EINVAL before any device call): a null index, n_scope_ids < 0, scope_ids NULL with n_scope_ids > 0,
+ * offsets that do not start at 0, decrease, or do not end at n_scope_ids. */
+int orr_search_batch_scoped(orr_index *idx, int32_t B, int32_t dim, const float *q,
+                            const uint8_t *terms_utf8, const uint32_t *term_off, const uint32_t *query_term_off,
+                            int64_t now_ticks, int32_t topk, int64_t candidate_limit,
+                            int64_t n_scope_ids, const int64_t *scope_ids, const uint64_t *scope_off,
+                            int64_t *out_rows, double *out_scores, int32_t *out_counts);
+
+/* Row-sharded form, with the record contract of orr_search_shard: [B][kprime+1] records (host or device), every record with
+ * ORR_CAND_DOT_EXACT, the trailer's order_key = the scoped rows that took part on this shard and approx_score = -inf when all
+ * of them are records: orr_merge_candidates(_ex) is used unchanged.  topk as orr_search_shard_ex (0: unknown).
+ * candidate_limit is GLOBAL over scoped live rows: the shard lets its first max(0, candidate_limit - scope_before[b]) take
+ * part, scope_before[b] (host memory; NULL: zeros) being query b's scoped live rows on the shards in front of this one
+ * (orr_index_scope_count).  row_base only enters order_key. */
+int orr_search_shard_scoped(orr_index *idx, int32_t B, int32_t dim, const float *q,
+                            const uint8_t *terms_utf8, const uint32_t *term_off, const uint32_t *query_term_off,
+                            int64_t now_ticks, int32_t kprime, int64_t candidate_limit, int32_t topk,
+                            int64_t n_scope_ids, const int64_t *scope_ids, const uint64_t *scope_off,
+                            const int64_t *scope_before, orr_candidate *out);
+
+/* out_live[B] (host memory): the live rows query b's scope resolves to on this shard. */
+int orr_index_scope_count(orr_index *idx, int32_t B, int64_t n_scope_ids, const int64_t *scope_ids,
+                          const uint64_t *scope_off, int64_t *out_live);
 
 /* ---- tuning knobs ----------------------------------------------------------
  * Integer options of one index; unknown names are ORR_EINVAL.

@@ -138,6 +138,14 @@ int64_t orrh_service_inserted_rows(orrh_service *svc);      /* rows inserted int
  * malloc'd; release it with orrh_free.  A blank query is ORR_EINVAL "Query is required." */
 int  orrh_service_search_json(orrh_service *svc, const char *query_utf8, const float *qvec, int32_t qdim,
                               int32_t topk, int64_t now_ticks, char **out_json, int64_t *out_len);
+/* The same over the chunks of the given documents only -- "search inside these documents": GetChunksByDocumentIdAsync
+ * (IIngestionStore.cs:11) feeding RecallSearchService.cs:26-37, so candidate_limit counts those chunks alone.  The response body
+ * is the same.  The documents' chunks are mapped to the row ids the service assigned; one shard answers through
+ * orr_search_batch_scoped, several through orr_index_scope_count + orr_search_shard_scoped per shard and the merge loop of the
+ * unscoped search.  Unknown document ids are skipped; n_documents 0 gives "citations":[]; a blank query is ORR_EINVAL. */
+int  orrh_service_search_documents_json(orrh_service *svc, const char *query_utf8, const float *qvec, int32_t qdim,
+                                        int32_t topk, int64_t now_ticks, const char *const *document_ids, int32_t n_documents,
+                                        char **out_json, int64_t *out_len);
 void orrh_free(void *p);
 
 /* ---- request micro-batcher -----------------------------------------

@@ -80,6 +80,12 @@ hip.orr_search_batch.restype = C.c_int
 hip.orr_search_batch.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp]
 hip.orr_search_shard.restype = C.c_int
 hip.orr_search_shard.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _vp]
+hip.orr_search_batch_scoped.restype = C.c_int
+hip.orr_search_batch_scoped.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp]
+hip.orr_search_shard_scoped.restype = C.c_int
+hip.orr_search_shard_scoped.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _i64, _vp, _vp, _vp, _vp]
+hip.orr_index_scope_count.restype = C.c_int
+hip.orr_index_scope_count.argtypes = [_vp, _i32, _i64, _vp, _vp, _vp]
 hip.orr_search_shard_ex.restype = C.c_int
 hip.orr_search_shard_ex.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, _vp]
 hip.orr_merge_candidates_ex.restype = C.c_int
@@ -188,6 +194,8 @@ host.orrh_service_destroy.restype = None
 host.orrh_service_destroy.argtypes = [_vp]
 host.orrh_service_search_json.restype = C.c_int
 host.orrh_service_search_json.argtypes = [_vp, C.c_char_p, _vp, _i32, _i32, _i64, C.POINTER(_vp), C.POINTER(_i64)]
+host.orrh_service_search_documents_json.restype = C.c_int
+host.orrh_service_search_documents_json.argtypes = [_vp, C.c_char_p, _vp, _i32, _i32, _i64, C.POINTER(C.c_char_p), _i32, C.POINTER(_vp), C.POINTER(_i64)]
 host.orrh_free.restype = None
 host.orrh_free.argtypes = [_vp]
 host.orrh_batcher_create.restype = _vp
@@ -212,7 +220,7 @@ host.orrh_batcher_stats.argtypes = [_vp, _vp, _vp, _vp]
 EXPORTED_HIP_SYMBOLS = [
     "orr_abi_version", "orr_device_count", "orr_last_error", "orr_index_create", "orr_index_destroy",
     "orr_index_append", "orr_index_seal", "orr_index_rows", "orr_index_dim", "orr_search_batch",
-    "orr_search_shard", "orr_search_shard_ex", "orr_merge_candidates", "orr_merge_candidates_ex", "orr_index_set_profiling", "orr_index_kernel_stats",
+    "orr_search_shard", "orr_search_shard_ex", "orr_search_batch_scoped", "orr_search_shard_scoped", "orr_index_scope_count", "orr_merge_candidates", "orr_merge_candidates_ex", "orr_index_set_profiling", "orr_index_kernel_stats",
     "orr_index_save", "orr_index_load", "orr_index_set_row_base", "orr_index_set_option", "orr_index_screen_dots", "orr_index_screen_i8_dots", "orr_index_view",
     "orr_index_delete_rows", "orr_index_update_rows", "orr_index_insert_rows", "orr_cluster_insert_rows", "orr_index_live_rows", "orr_index_compact", "orr_cluster_compact", "orr_index_search_stats",
     "orr_cluster_create", "orr_cluster_destroy", "orr_cluster_shards", "orr_cluster_shard", "orr_cluster_seal", "orr_cluster_rows",
@@ -222,7 +230,7 @@ EXPORTED_HOST_SYMBOLS = ["orrh_is_blank", "orrh_lower_invariant", "orrh_query_te
                          "orrh_round4", "orrh_has_sufficient_evidence", "orrh_format_score_f4", "orrh_last_error", "orrh_store_create", "orrh_store_destroy",
                          "orrh_store_upsert_document", "orrh_store_upsert_chunks", "orrh_store_delete_document",
                          "orrh_store_chunk_count", "orrh_store_import_cosmos_json", "orrh_store_export_cosmos_json", "orrh_service_create", "orrh_service_destroy",
-                         "orrh_service_search_json", "orrh_service_stats", "orrh_service_tombstoned_rows", "orrh_service_compactions", "orrh_service_delta_merges", "orrh_service_updated_rows", "orrh_service_inserted_rows", "orrh_service_set_option", "orrh_free", "orrh_batcher_create", "orrh_batcher_destroy",
+                         "orrh_service_search_json", "orrh_service_search_documents_json", "orrh_service_stats", "orrh_service_tombstoned_rows", "orrh_service_compactions", "orrh_service_delta_merges", "orrh_service_updated_rows", "orrh_service_inserted_rows", "orrh_service_set_option", "orrh_free", "orrh_batcher_create", "orrh_batcher_destroy",
                          "orrh_batcher_search", "orrh_batcher_search_at", "orrh_batcher_stats"]
 
 

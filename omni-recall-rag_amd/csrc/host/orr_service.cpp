@@ -10,6 +10,7 @@
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -489,24 +490,18 @@ const Chunk *chunk_of(const orrh_service *svc, int64_t row_id)
     return nullptr;
 }
 
-// RecallSearchService.cs:26-37 over one or several shards.
-int search_shards(orrh_service *svc, int32_t qdim, const float *qvec, const uint8_t *terms, const uint32_t *term_off,
-                  const uint32_t *qoff, int64_t now_ticks, int32_t topk, int64_t *rows, double *scores, int32_t *count)
+// The loop every multi-shard caller runs: each shard's k' records (`shard_records(i, k', out)`), the host merge, and k' x 4 for
+// as long as some query could not be certified and k' is below the `total` rows that take part.
+template <class ShardRecords>
+int merge_shards(orrh_service *svc, int64_t total, ShardRecords shard_records, int32_t qdim, const float *qvec, const uint32_t *qoff,
+                 int64_t now_ticks, int32_t topk, int64_t *rows, double *scores, int32_t *count)
 {
-    if (svc->shards.size() == 1) {
-        int r = orr_search_batch(svc->shards[0].index, 1, qdim, qdim > 0 ? qvec : nullptr, terms, term_off, qoff, now_ticks, topk,
-                                 svc->candidate_limit, rows, scores, count);
-        return r == ORR_OK ? ORR_OK : fail(r, orr_last_error());
-    }
     const int32_t n_sh = (int32_t)svc->shards.size();
-    int64_t total = 0;
-    for (const auto &sh : svc->shards) total += (int64_t)sh.chunks.size();
     int64_t kprime = std::min<int64_t>(std::max<int64_t>(total, 1), std::max<int64_t>(std::max(1, topk) + 22, 32));
     for (;;) {
         std::vector<orr_candidate> recs((size_t)n_sh * ((size_t)kprime + 1));
         for (int32_t i = 0; i < n_sh; ++i) {
-            int r = orr_search_shard(svc->shards[i].index, 1, qdim, qdim > 0 ? qvec : nullptr, terms, term_off, qoff, now_ticks,
-                                     (int32_t)kprime, svc->candidate_limit, recs.data() + (size_t)i * (kprime + 1));
+            int r = shard_records(i, (int32_t)kprime, recs.data() + (size_t)i * (kprime + 1));
             if (r != ORR_OK) return fail(r, orr_last_error());
         }
         int32_t unc = 0;
@@ -516,6 +511,127 @@ int search_shards(orrh_service *svc, int32_t qdim, const float *qvec, const uint
         if (unc == 0 || kprime >= total) return ORR_OK;
         kprime = std::min<int64_t>(total, kprime * 4);
     }
+}
+
+// RecallSearchService.cs:26-37 over one or several shards.
+int search_shards(orrh_service *svc, int32_t qdim, const float *qvec, const uint8_t *terms, const uint32_t *term_off,
+                  const uint32_t *qoff, int64_t now_ticks, int32_t topk, int64_t *rows, double *scores, int32_t *count)
+{
+    const float *q = qdim > 0 ? qvec : nullptr;
+    if (svc->shards.size() == 1) {
+        int r = orr_search_batch(svc->shards[0].index, 1, qdim, q, terms, term_off, qoff, now_ticks, topk,
+                                 svc->candidate_limit, rows, scores, count);
+        return r == ORR_OK ? ORR_OK : fail(r, orr_last_error());
+    }
+    int64_t total = 0;
+    for (const auto &sh : svc->shards) total += (int64_t)sh.chunks.size();
+    return merge_shards(svc, total, [&](int32_t i, int32_t kprime, orr_candidate *out) {
+        return orr_search_shard(svc->shards[i].index, 1, qdim, q, terms, term_off, qoff, now_ticks, kprime, svc->candidate_limit, out);
+    }, qdim, qvec, qoff, now_ticks, topk, rows, scores, count);
+}
+
+// The same over the chunks of the given documents only (GetChunksByDocumentIdAsync, IIngestionStore.cs:11, feeding :26-37): the
+// documents' chunks were mapped to the row ids the extents assigned (rows deleted in place are skipped by the library, rows that
+// were compacted away are unknown to it), and every shard ranks just those rows.  candidate_limit counts scoped rows in the
+// global order: each shard is told how many scoped live rows lie in front of it.
+int search_shards_scoped(orrh_service *svc, const std::vector<int64_t> &ids, int32_t qdim, const float *qvec, const uint8_t *terms,
+                         const uint32_t *term_off, const uint32_t *qoff, int64_t now_ticks, int32_t topk, int64_t *rows, double *scores,
+                         int32_t *count)
+{
+    const int64_t n_ids = (int64_t)ids.size();
+    const int64_t *idp = n_ids ? ids.data() : nullptr;
+    const float *q = qdim > 0 ? qvec : nullptr;
+    if (svc->shards.size() == 1) {
+        int r = orr_search_batch_scoped(svc->shards[0].index, 1, qdim, q, terms, term_off, qoff, now_ticks, topk,
+                                        svc->candidate_limit, n_ids, idp, nullptr, rows, scores, count);
+        return r == ORR_OK ? ORR_OK : fail(r, orr_last_error());
+    }
+    std::vector<int64_t> before(svc->shards.size(), 0);
+    int64_t total = 0;
+    for (size_t i = 0; i < svc->shards.size(); ++i) {
+        int64_t live = 0;
+        int r = orr_index_scope_count(svc->shards[i].index, 1, n_ids, idp, nullptr, &live);
+        if (r != ORR_OK) return fail(r, orr_last_error());
+        before[i] = total;
+        total += live;
+    }
+    return merge_shards(svc, total, [&](int32_t i, int32_t kprime, orr_candidate *out) {
+        return orr_search_shard_scoped(svc->shards[i].index, 1, qdim, q, terms, term_off, qoff, now_ticks, kprime, svc->candidate_limit, 0,
+                                       n_ids, idp, nullptr, &before[(size_t)i], out);
+    }, qdim, qvec, qoff, now_ticks, topk, rows, scores, count);
+}
+
+// SearchAsync (RecallSearchService.cs:20-57) as JSON; documents != nullptr: over the chunks of those documents only.
+int search_json(orrh_service *svc, const char *fn, const char *query_utf8, const float *qvec, int32_t qdim, int32_t topk, int64_t now_ticks,
+                const std::set<std::string> *documents, char **out_json, int64_t *out_len)
+{
+    if (!svc || !out_json) return fail(ORR_EINVAL, std::string(fn) + ": null argument");
+    *out_json = nullptr;
+    const std::string query = query_utf8 ? query_utf8 : "";
+    if (orrh_is_blank(reinterpret_cast<const uint8_t *>(query.data()), (int64_t)query.size()))
+        return fail(ORR_EINVAL, "Query is required.");                                       // :22-23
+    std::lock_guard<std::mutex> l(svc->mu);
+    int r = ensure_index(svc);                                                                // the :26 data source
+    if (r != ORR_OK) return r;
+
+    // queryTerms (:95-108), once per query
+    std::vector<uint8_t> terms(4 * query.size() + 16);
+    std::vector<uint32_t> term_off(query.size() + 2);
+    const int32_t T = orrh_query_terms(reinterpret_cast<const uint8_t *>(query.data()), (int64_t)query.size(), terms.data(),
+                                       (int64_t)terms.size(), term_off.data(), (int32_t)term_off.size());
+    if (T < 0) return fail(ORR_EINVAL, "query tokenisation failed");
+    const uint32_t qoff[2] = {0, (uint32_t)T};
+
+    const int32_t k = std::max(1, topk);                                                      // :36
+    std::vector<int64_t> rows((size_t)k, -1);
+    std::vector<double> scores((size_t)k, 0.0);
+    int32_t count = 0;
+    if (documents) {
+        std::vector<int64_t> ids;                      // unknown documents have no chunk: skipped
+        for (const Shard &sh : svc->shards)
+            for (size_t p = 0; p < sh.chunks.size(); ++p)
+                if (documents->count(sh.chunks[p].document_id) && !(p < sh.dead.size() && sh.dead[p])) ids.push_back(id_of(sh, p));
+        r = search_shards_scoped(svc, ids, qdim, qvec, terms.data(), term_off.data(), qoff, now_ticks, topk, rows.data(), scores.data(),
+                                 &count);
+    } else {
+        r = search_shards(svc, qdim, qvec, terms.data(), term_off.data(), qoff, now_ticks, topk, rows.data(), scores.data(),
+                          &count);                                                            // replaces :26-37
+    }
+    if (r != ORR_OK) return r;
+
+    std::string js = "{\"query\":";
+    json_string(query, js);
+    js += ",\"citations\":[";
+    {
+        std::lock_guard<std::mutex> sl(svc->store->mu);
+        for (int32_t i = 0; i < count; ++i) {
+            const Chunk *cp = chunk_of(svc, rows[i]);
+            if (!cp) return fail(ORR_ECOMM, "search returned an unknown row id");
+            const Chunk &c = *cp;
+            auto d = svc->store->documents.find(c.document_id);                               // :39,44
+            const std::string file = d == svc->store->documents.end() ? "unknown" : d->second.file_name;   // :47
+            std::string snip(4 * c.content.size() + 16, '\0');
+            int64_t m = orrh_build_snippet(reinterpret_cast<const uint8_t *>(c.content.data()), (int64_t)c.content.size(), 180,
+                                           reinterpret_cast<uint8_t *>(&snip[0]), (int64_t)snip.size());   // :50
+            snip.resize(m < 0 ? 0 : (size_t)m);
+            if (i) js.push_back(',');
+            js += "{\"documentId\":"; json_string(c.document_id, js);
+            js += ",\"fileName\":"; json_string(file, js);
+            js += ",\"chunkId\":"; json_string(c.id, js);
+            js += ",\"chunkIndex\":" + std::to_string(c.chunk_index);
+            js += ",\"snippet\":"; json_string(snip, js);
+            js += ",\"score\":"; json_double(orrh_round4(scores[i]), js);                     // :51
+            js += ",\"createdAtUtc\":"; json_string(iso_utc(c.created_ticks), js);
+            js.push_back('}');
+        }
+    }
+    js += "]}";
+    char *buf = static_cast<char *>(malloc(js.size() + 1));
+    if (!buf) return fail(ORR_ENOMEM, "out of memory");
+    memcpy(buf, js.data(), js.size() + 1);
+    *out_json = buf;
+    if (out_len) *out_len = (int64_t)js.size();
+    return ORR_OK;
 }
 
 }  // namespace
@@ -663,64 +779,19 @@ void orrh_free(void *p) { free(p); }
 int orrh_service_search_json(orrh_service *svc, const char *query_utf8, const float *qvec, int32_t qdim, int32_t topk,
                              int64_t now_ticks, char **out_json, int64_t *out_len)
 {
-    if (!svc || !out_json) return fail(ORR_EINVAL, "orrh_service_search_json: null argument");
-    *out_json = nullptr;
-    const std::string query = query_utf8 ? query_utf8 : "";
-    if (orrh_is_blank(reinterpret_cast<const uint8_t *>(query.data()), (int64_t)query.size()))
-        return fail(ORR_EINVAL, "Query is required.");                                       // :22-23
-    std::lock_guard<std::mutex> l(svc->mu);
-    int r = ensure_index(svc);                                                                // the :26 data source
-    if (r != ORR_OK) return r;
+    return search_json(svc, "orrh_service_search_json", query_utf8, qvec, qdim, topk, now_ticks, nullptr, out_json, out_len);
+}
 
-    // queryTerms (:95-108), once per query
-    std::vector<uint8_t> terms(4 * query.size() + 16);
-    std::vector<uint32_t> term_off(query.size() + 2);
-    const int32_t T = orrh_query_terms(reinterpret_cast<const uint8_t *>(query.data()), (int64_t)query.size(), terms.data(),
-                                       (int64_t)terms.size(), term_off.data(), (int32_t)term_off.size());
-    if (T < 0) return fail(ORR_EINVAL, "query tokenisation failed");
-    const uint32_t qoff[2] = {0, (uint32_t)T};
-
-    const int32_t k = std::max(1, topk);                                                      // :36
-    std::vector<int64_t> rows((size_t)k, -1);
-    std::vector<double> scores((size_t)k, 0.0);
-    int32_t count = 0;
-    r = search_shards(svc, qdim, qvec, terms.data(), term_off.data(), qoff, now_ticks, topk, rows.data(), scores.data(),
-                      &count);                                                                // replaces :26-37
-    if (r != ORR_OK) return r;
-
-    std::string js = "{\"query\":";
-    json_string(query, js);
-    js += ",\"citations\":[";
-    {
-        std::lock_guard<std::mutex> sl(svc->store->mu);
-        for (int32_t i = 0; i < count; ++i) {
-            const Chunk *cp = chunk_of(svc, rows[i]);
-            if (!cp) return fail(ORR_ECOMM, "search returned an unknown row id");
-            const Chunk &c = *cp;
-            auto d = svc->store->documents.find(c.document_id);                               // :39,44
-            const std::string file = d == svc->store->documents.end() ? "unknown" : d->second.file_name;   // :47
-            std::string snip(4 * c.content.size() + 16, '\0');
-            int64_t m = orrh_build_snippet(reinterpret_cast<const uint8_t *>(c.content.data()), (int64_t)c.content.size(), 180,
-                                           reinterpret_cast<uint8_t *>(&snip[0]), (int64_t)snip.size());   // :50
-            snip.resize(m < 0 ? 0 : (size_t)m);
-            if (i) js.push_back(',');
-            js += "{\"documentId\":"; json_string(c.document_id, js);
-            js += ",\"fileName\":"; json_string(file, js);
-            js += ",\"chunkId\":"; json_string(c.id, js);
-            js += ",\"chunkIndex\":" + std::to_string(c.chunk_index);
-            js += ",\"snippet\":"; json_string(snip, js);
-            js += ",\"score\":"; json_double(orrh_round4(scores[i]), js);                     // :51
-            js += ",\"createdAtUtc\":"; json_string(iso_utc(c.created_ticks), js);
-            js.push_back('}');
-        }
-    }
-    js += "]}";
-    char *buf = static_cast<char *>(malloc(js.size() + 1));
-    if (!buf) return fail(ORR_ENOMEM, "out of memory");
-    memcpy(buf, js.data(), js.size() + 1);
-    *out_json = buf;
-    if (out_len) *out_len = (int64_t)js.size();
-    return ORR_OK;
+int orrh_service_search_documents_json(orrh_service *svc, const char *query_utf8, const float *qvec, int32_t qdim, int32_t topk,
+                                       int64_t now_ticks, const char *const *document_ids, int32_t n_documents, char **out_json,
+                                       int64_t *out_len)
+{
+    if (n_documents < 0 || (n_documents > 0 && !document_ids))
+        return fail(ORR_EINVAL, "orrh_service_search_documents_json: document_ids is NULL or their number negative");
+    std::set<std::string> documents;
+    for (int32_t i = 0; i < n_documents; ++i)
+        if (document_ids[i]) documents.insert(document_ids[i]);
+    return search_json(svc, "orrh_service_search_documents_json", query_utf8, qvec, qdim, topk, now_ticks, &documents, out_json, out_len);
 }
 
 }  // extern "C"

@@ -35,6 +35,7 @@
 #include "orr_insert_plan.h"
 #include "orr_kernels.h"
 #include "orr_lanes.h"
+#include "orr_scope_plan.h"
 #include "orr_token_index.h"
 
 namespace {
@@ -205,6 +206,15 @@ struct orr_index {
     int64_t dead_before = 0;           // deleted rows in the shards in front of this one ("dead_rows_before")
     const orr_index *parent = nullptr; // views: the deleted set lives in the owning index
     std::vector<std::pair<int64_t, int64_t>> id_index;   // (row id, position) ascending, built at the first delete
+
+    // scoped search (orr_search_batch_scoped): the shard's (row id, position) pairs sorted by id, on the OWNING index -- built at
+    // the first scoped search (ensure_scope_table), shared by its lanes and views, dropped when positions move (compact, insert)
+    std::mutex scope_mu;
+    std::atomic<bool> scope_ready{false};
+    int64_t *scope_tab_ids = nullptr;  // [n_rows] ascending
+    uint32_t *scope_tab_pos = nullptr; // [n_rows] positions, ascending within equal ids
+    DevBuf ws_scope_ids, ws_scope_meta, ws_scope_bm, ws_scope_chunks, ws_scope_sel;   // a lane's: listed ids, offsets + limits, bitmaps, chunk counts, a pass's queries
+    PinnedBuf pin_scope, pin_scope_pass;
 
     // search workspace
     DevBuf ws_q, ws_dot, ws_dotf, ws_sel, ws_cand, ws_qc, ws_rowc, ws_tau, ws_qsplit, ws_fcnt, ws_fbuf, ws_fqf, ws_fany, ws_tsL, ws_tskey, ws_qtiled, ws_fdot, ws_pbuf, ws_psel, ws_q8, ws_q8s1, ws_q8err, ws_zero, ws_norm_a;
@@ -667,6 +677,8 @@ void orr_index_destroy(orr_index *idx)
         if (idx->d_vlen) (void)hipFree(idx->d_vlen);
         if (idx->d_post_off) (void)hipFree(idx->d_post_off);
         if (idx->d_post_rows) (void)hipFree(idx->d_post_rows);
+        if (idx->scope_tab_ids) (void)hipFree(idx->scope_tab_ids);
+        if (idx->scope_tab_pos) (void)hipFree(idx->scope_tab_pos);
     } else {
         idx->emb_shadow.p = nullptr; idx->emb_shadow.cap = 0;
         for (DevBuf *b : {&idx->emb_i8, &idx->i8_scale, &idx->i8_rel_err, &idx->i8_rel_hat, &idx->i8_rowf, &idx->tok_bm, &idx->tok_bm_index}) { b->p = nullptr; b->cap = 0; }
@@ -675,6 +687,8 @@ void orr_index_destroy(orr_index *idx)
     idx->d_dead.release();
     if (!idx->is_view) { idx->vlong_start.release(); idx->vlong_len.release(); idx->vlong_id.release(); }
     idx->ws_norm_a.release();
+    for (DevBuf *b : {&idx->ws_scope_ids, &idx->ws_scope_meta, &idx->ws_scope_bm, &idx->ws_scope_chunks, &idx->ws_scope_sel}) b->release();
+    idx->pin_scope.release(); idx->pin_scope_pass.release();
     DevBuf *bufs[] = {&idx->ws_q, &idx->ws_dot, &idx->ws_dotf, &idx->ws_rowc, &idx->ws_tau, &idx->ws_qsplit, &idx->ws_fcnt,
                       &idx->ws_fbuf, &idx->ws_fqf, &idx->ws_fany, &idx->ws_tsL, &idx->ws_tskey, &idx->ws_qtiled, &idx->ws_fdot, &idx->ws_pbuf, &idx->ws_psel, &idx->ws_q8, &idx->ws_q8s1, &idx->ws_q8err, &idx->ws_zero, &idx->ws_sel, &idx->ws_cand, &idx->ws_qc, &idx->ws_keys_a, &idx->ws_keys_b,
                       &idx->ws_vals_a, &idx->ws_vals_b, &idx->ws_sort_tmp, &idx->ws_raw, &idx->ws_src_start, &idx->ws_qsub,
@@ -1230,6 +1244,16 @@ int64_t orr_index_live_rows(const orr_index *idx)
     return idx ? idx->n_rows - (int64_t)(idx->parent ? idx->parent->dead.size() : idx->dead.size()) : 0;
 }
 
+// The id table of scoped searches goes when positions move (the caller holds Exclusive: no search reads it).
+static void drop_scope_table(orr_index *idx)
+{
+    std::lock_guard<std::mutex> g(idx->scope_mu);
+    if (idx->scope_tab_ids) (void)hipFree(idx->scope_tab_ids);
+    if (idx->scope_tab_pos) (void)hipFree(idx->scope_tab_pos);
+    idx->scope_tab_ids = nullptr; idx->scope_tab_pos = nullptr;
+    idx->scope_ready.store(false, std::memory_order_release);
+}
+
 // The live rows (not deleted) that carry the ids want[0..n): (position, index into want) for each, in the order of `want`;
 // a duplicate id of orr_index_append gives several.  Ids map to positions through idx->id_index, built at the first call.
 static int live_rows_of_ids(orr_index *idx, const std::vector<int64_t> &want, std::vector<std::pair<int64_t, int64_t>> &out)
@@ -1470,6 +1494,7 @@ int orr_index_compact(orr_index *idx, int64_t *out_removed)
     idx->dead.clear();
     idx->d_dead.release();
     idx->id_index.clear();
+    drop_scope_table(idx);
     // derived copies are rebuilt at the next search that wants them; the lanes' borrowed pointers die with the lanes
     idx->emb_shadow.release(); idx->shadow_ready = false; idx->shadow_failed = false;
     idx->emb_i8.release(); idx->i8_scale.release(); idx->i8_rel_err.release(); idx->i8_rel_hat.release(); idx->i8_rowf.release();
@@ -1720,6 +1745,7 @@ int orr_index_insert_rows(orr_index *idx, int64_t n, int32_t dim, const float *e
     idx->n_rows = total;
     idx->dead = new_dead;                              // (their number is unchanged: the lanes' shared dead_count stays)
     idx->id_index.clear();
+    drop_scope_table(idx);
     idx->n_vlong = -1; idx->n_vmid = 0;
     idx->bitmaps_clean = 0; idx->bitmaps_clean_of = nullptr;
     idx->tok_bm.release(); idx->tok_bm_index.release(); idx->n_tok_bm = -1; idx->tok_bm_words = 0;
@@ -3460,6 +3486,479 @@ Backend index_backend(orr_index *idx, const char *name, int64_t n)
     return be;
 }
 
+// ---- scoped search: rank only the rows a caller lists (orr_search_batch_scoped, orr_search_shard_scoped) -------------------
+// Query b's scope is a list of row ids.  The ids are resolved on the device (a table of the shard's (id, position) pairs sorted
+// by id, a binary search per listed id) into one bitmap over the shard's rows per query -- repeats fall together, the bits are
+// in candidate order, deleted rows are left out, candidate_limit is a prefix popcount -- and the bitmaps are compacted into the
+// survivors' buffers of the two-stage pass, whose exact tail (two_stage_tail) then runs as behind a screen.  No screen, no
+// shadow, no pass over all rows; the forms, the ladder and the slicing are orr_scope_plan.h's.
+
+struct ScopeArgs {
+    int64_t n_ids;
+    const int64_t *ids;            // host or device
+    const uint64_t *off;           // host [B + 1], or null: every query owns the whole list
+    const int64_t *before;         // host [B] scoped live rows in the shards in front (orr_search_shard_scoped), or null
+};
+
+int check_scope(const orr_index *idx, int32_t B, const ScopeArgs &sc, const char *fn)
+{
+    if (sc.n_ids < 0) return fail(ORR_EINVAL, "%s: n_scope_ids is negative", fn);
+    if (sc.n_ids > 0 && !sc.ids) return fail(ORR_EINVAL, "%s: scope_ids is NULL with %lld ids", fn, (long long)sc.n_ids);
+    if (B > 0 && !scope::offsets_valid(sc.off, B, sc.n_ids))
+        return fail(ORR_EINVAL, "%s: scope_off must start at 0, never decrease and end at n_scope_ids", fn);
+    if (!idx) return fail(ORR_EINVAL, "%s: null index", fn);
+    return ORR_OK;
+}
+
+// The id table, once per sealed shard (12 bytes per row); the caller holds a lane of the handle.  ORR_ENOMEM without room.
+int ensure_scope_table(orr_index *lane)
+{
+    orr_index *own = const_cast<orr_index *>(owner_of(lane));
+    if (own->scope_ready.load(std::memory_order_acquire)) return ORR_OK;
+    std::lock_guard<std::mutex> g(own->scope_mu);
+    if (own->scope_ready.load(std::memory_order_acquire)) return ORR_OK;
+    const int64_t n = own->n_rows;
+    if (n > 0) {
+        const auto t0 = std::chrono::steady_clock::now();
+        DevBuf iota, tmp;
+        size_t tmp_bytes = 0;
+        HIP_TRY(orr::scope_sort_id_table(nullptr, tmp_bytes, own->d_row_ids, nullptr, nullptr, nullptr, n, lane->stream));
+        int64_t *ids = nullptr;
+        uint32_t *pos = nullptr;
+        int r = dev_alloc(&ids, (size_t)n);
+        if (r == ORR_OK) r = dev_alloc(&pos, (size_t)n);
+        if (r == ORR_OK) r = iota.reserve(sizeof(uint32_t) * (size_t)n);
+        if (r == ORR_OK) r = tmp.reserve(tmp_bytes);
+        if (r == ORR_OK) {
+            size_t tb = tmp.cap;
+            hipError_t e = orr::scope_sort_id_table(tmp.p, tb, own->d_row_ids, ids, iota.as<uint32_t>(), pos, n, lane->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(lane->stream);
+            if (e != hipSuccess) r = fail(ORR_EDEVICE, "scope id table: %s", hipGetErrorString(e));
+        }
+        iota.release(); tmp.release();
+        if (r != ORR_OK) {
+            (void)hipGetLastError();
+            if (ids) (void)hipFree(ids);
+            if (pos) (void)hipFree(pos);
+            return r;
+        }
+        own->scope_tab_ids = ids;
+        own->scope_tab_pos = pos;
+        add_phase_stat(lane, "scope_id_table", t0, 12.0 * (double)n);
+    }
+    own->scope_ready.store(true, std::memory_order_release);
+    return ORR_OK;
+}
+
+// The scope bitmaps of queries [b0, b0 + nq) of a call, on the lane's workspaces, and what they resolve to.
+struct ScopeSlice {
+    int32_t b0 = 0, nq = 0, n_bitmaps = 0;
+    int64_t words = 0;
+    const uint32_t *live = nullptr;    // pinned host [nq]: live rows of each query's scope on this shard
+    const uint32_t *took = nullptr;    // ... of which the first limit take part
+    const int64_t *d_limit = nullptr;  // device [nq]
+};
+
+// limit[b]: scoped live rows query b of the CALL lets take part.  Ends in a stream synchronise: live / took are final.
+int build_scope_slice(orr_index *idx, const ScopeArgs &sc, const std::vector<int64_t> &limit, int32_t b0, int32_t nq, ScopeSlice &sl)
+{
+    hipStream_t s = idx->stream;
+    const orr_index *own = owner_of(idx);
+    const bool shared = sc.off == nullptr;
+    const uint64_t id0 = shared ? 0 : sc.off[b0], id1 = shared ? (uint64_t)sc.n_ids : sc.off[b0 + nq];
+    const int64_t n_ids = (int64_t)(id1 - id0);
+    sl.b0 = b0; sl.nq = nq; sl.n_bitmaps = shared ? 1 : nq;
+    sl.words = (int64_t)(scope::bitmap_bytes(idx->n_rows) / 4);
+    const int32_t n_chunks = orr::scope_chunks(sl.words);
+    // one pinned block: [offsets u64 x (nq + 1)][limits i64 x nq][live u32 x nq][took u32 x nq]; the first two go up
+    const size_t o_lim = sizeof(uint64_t) * ((size_t)nq + 1), o_live = o_lim + sizeof(int64_t) * (size_t)nq, o_took = o_live + sizeof(uint32_t) * (size_t)nq;
+    ORR_TRY(idx->pin_scope.reserve(o_took + sizeof(uint32_t) * (size_t)nq));
+    ORR_TRY(idx->ws_scope_meta.reserve(o_live));
+    ORR_TRY(idx->ws_scope_ids.reserve(sizeof(int64_t) * (size_t)std::max<int64_t>(n_ids, 1)));
+    ORR_TRY(idx->ws_scope_bm.reserve(sizeof(uint32_t) * (size_t)sl.n_bitmaps * (size_t)sl.words));
+    ORR_TRY(idx->ws_scope_chunks.reserve(sizeof(uint32_t) * (size_t)sl.n_bitmaps * (size_t)n_chunks));
+    uint8_t *hp = idx->pin_scope.as<uint8_t>();
+    uint64_t *h_off = reinterpret_cast<uint64_t *>(hp);
+    int64_t *h_lim = reinterpret_cast<int64_t *>(hp + o_lim);
+    for (int32_t i = 0; i <= nq; ++i) h_off[i] = shared ? 0 : sc.off[b0 + i] - id0;
+    for (int32_t i = 0; i < nq; ++i) h_lim[i] = limit[(size_t)(b0 + i)];
+    uint32_t *h_live = reinterpret_cast<uint32_t *>(hp + o_live), *h_took = reinterpret_cast<uint32_t *>(hp + o_took);
+    uint8_t *dm = idx->ws_scope_meta.as<uint8_t>();
+    HIP_TRY(hipMemcpyAsync(dm, hp, o_live, hipMemcpyHostToDevice, s));
+    if (n_ids > 0) HIP_TRY(hipMemcpyAsync(idx->ws_scope_ids.p, sc.ids + id0, sizeof(int64_t) * (size_t)n_ids, hipMemcpyDefault, s));   // the list is copied, nothing else
+    HIP_TRY(hipMemsetAsync(idx->ws_scope_bm.p, 0, sizeof(uint32_t) * (size_t)sl.n_bitmaps * (size_t)sl.words, s));
+    sl.d_limit = reinterpret_cast<const int64_t *>(dm + o_lim);
+    {
+        Timed t(idx, "scope_lookup", 8.0 * (double)n_ids);
+        HIP_TRY(orr::launch_scope_lookup(own->scope_tab_ids, own->scope_tab_pos, idx->n_rows, idx->ws_scope_ids.as<int64_t>(), n_ids,
+                                         shared ? nullptr : reinterpret_cast<const uint64_t *>(dm), nq, own->d_dead.as<int64_t>(),
+                                         (int32_t)own->dead.size(), idx->ws_scope_bm.as<uint32_t>(), sl.words, s));
+    }
+    {
+        Timed t(idx, "scope_counts", 4.0 * (double)sl.n_bitmaps * (double)sl.words);
+        HIP_TRY(orr::launch_scope_counts(idx->ws_scope_bm.as<uint32_t>(), sl.words, sl.n_bitmaps, nq, sl.d_limit, idx->ws_scope_chunks.as<uint32_t>(),
+                                         h_live, h_took, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    collect_events(idx);
+    sl.live = h_live; sl.took = h_took;
+    return ORR_OK;
+}
+
+// One scoped pass over the queries of `a` (a compacted sub-batch; query i of it is query qsel[i] of the slice): the slice's
+// bitmaps -> survivors' buffers -> the exact tail (Selection) or every pair a record (AllRecords, kprime >= every count).  The
+// records land in host memory (*recs_host).  kRetryPass as run_shard_once.  Caller holds the lane and its lock.
+int run_scoped_pass(orr_index *idx, const BatchArgs &a, const std::vector<uint32_t> &qsel, const ScopeSlice &sl, scope::Form form,
+                    int32_t kprime, const float **q_host, const orr_candidate **recs_host)
+{
+    ORR_TRY(bind_device(idx));
+    const int32_t B = a.B, D = idx->dim;
+    hipStream_t s = idx->stream;
+    *q_host = nullptr; *recs_host = nullptr;
+    std::vector<uint32_t> qoff((size_t)B + 1);
+    memcpy(qoff.data(), a.query_term_off, sizeof(uint32_t) * ((size_t)B + 1));
+    for (int32_t b = 0; b < B; ++b) {
+        if (qoff[b + 1] < qoff[b]) return fail(ORR_EINVAL, "query_term_off is not monotone at query %d", b);
+        if (qoff[b + 1] - qoff[b] > 65535) return fail(ORR_EINVAL, "query %d has more than 65535 terms", b);
+    }
+    const uint32_t n_terms_total = qoff[B] - qoff[0];
+    if (n_terms_total > 0 && (!a.term_off || !a.terms_utf8)) return fail(ORR_EINVAL, "terms are referenced but term_off/terms_utf8 is NULL");
+
+    PassPlan p;                        // what launch_consts and finish_pass read of a plan: no screen, no batched score
+    p.form = PassForm::Exact;
+    p.use_cos = a.dim > 0 && a.dim == D;
+    p.q_on_device = p.use_cos && is_device_pointer(a.q);
+    idx->h_survivors.clear();
+
+    // ---- records: small sets straight into pinned host memory, large ones through one copy
+    const size_t rec_bytes = sizeof(orr_candidate) * (size_t)B * ((size_t)kprime + 1);
+    PassIo io;
+    io.direct_host = rec_bytes <= (256u << 10);
+    ORR_TRY(idx->pin_cand.reserve(rec_bytes));
+    if (io.direct_host) {
+        io.d_cand = idx->pin_cand.as<orr_candidate>();
+    } else {
+        ORR_TRY(idx->ws_cand.reserve(rec_bytes));
+        io.d_cand = idx->ws_cand.as<orr_candidate>();
+    }
+
+    // ---- query vectors, as run_shard_once (exact norms on the host)
+    bool q_download_pending = false;
+    idx->h_norm_a.assign((size_t)B, 0.0);
+    if (p.use_cos) {
+        const size_t qbytes = sizeof(float) * (size_t)B * a.dim;
+        ORR_TRY(idx->pin_q.reserve(qbytes));
+        if (p.q_on_device) {
+            io.d_q = a.q;
+            HIP_TRY(hipMemcpyAsync(idx->pin_q.p, a.q, qbytes, hipMemcpyDeviceToHost, idx->stream_kw));
+            HIP_TRY(hipEventRecord(idx->ev_q, idx->stream_kw));
+            q_download_pending = true;
+        } else {
+            memcpy(idx->pin_q.p, a.q, qbytes);
+            ORR_TRY(idx->ws_q.reserve(qbytes));
+            HIP_TRY(hipMemcpyAsync(idx->ws_q.p, idx->pin_q.p, qbytes, hipMemcpyHostToDevice, s));
+            io.d_q = idx->ws_q.as<float>();
+        }
+        *q_host = idx->pin_q.as<float>();
+    }
+
+    // ---- the survivors' buffers, filled from the bitmaps: [counts | unused | tickets] as the tail expects them, no floor
+    uint32_t worst = 0;
+    for (uint32_t q : qsel) worst = std::max(worst, sl.took[q]);
+    const uint32_t cap = scope::slice_cap(worst);
+    const int32_t buf_lists = (int32_t)(cap / orr::kSelWidth);
+    const size_t o_sel = sizeof(uint32_t) * 3 * (size_t)B, o_L = (o_sel + sizeof(uint32_t) * (size_t)B + 7) / 8 * 8;
+    ORR_TRY(idx->pin_scope_pass.reserve(o_L + sizeof(double) * (size_t)B));
+    uint8_t *hp = idx->pin_scope_pass.as<uint8_t>();
+    uint32_t *h_cnt = reinterpret_cast<uint32_t *>(hp), *h_sel = reinterpret_cast<uint32_t *>(hp + o_sel);
+    double *h_L = reinterpret_cast<double *>(hp + o_L);
+    for (int32_t b = 0; b < B; ++b) {
+        h_cnt[b] = sl.took[qsel[(size_t)b]]; h_cnt[B + b] = 0; h_cnt[2 * B + b] = 0;
+        h_sel[b] = qsel[(size_t)b];
+        h_L[b] = -std::numeric_limits<double>::infinity();
+    }
+    ORR_TRY(idx->ws_fcnt.reserve(o_sel));
+    ORR_TRY(idx->ws_scope_sel.reserve(sizeof(uint32_t) * (size_t)B));
+    ORR_TRY(idx->ws_tsL.reserve(sizeof(double) * (size_t)B));
+    ORR_TRY(idx->ws_fbuf.reserve(sizeof(orr::SelEntry) * (size_t)B * cap));
+    ORR_TRY(idx->ws_fdot.reserve(sizeof(double) * (size_t)B * cap));
+    ORR_TRY(idx->pin_cnt.reserve(sizeof(uint32_t) * (size_t)B));
+    HIP_TRY(hipMemcpyAsync(idx->ws_fcnt.p, h_cnt, o_sel, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(idx->ws_scope_sel.p, h_sel, sizeof(uint32_t) * (size_t)B, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(idx->ws_tsL.p, h_L, sizeof(double) * (size_t)B, hipMemcpyHostToDevice, s));
+    orr::FusedEpilogue epi{};
+    epi.cnt = idx->ws_fcnt.as<uint32_t>(); epi.buf = idx->ws_fbuf.as<orr::SelEntry>(); epi.cap = cap;
+    {
+        Timed t(idx, "scope_compact", 16.0 * (double)B * (double)worst);
+        HIP_TRY(orr::launch_scope_compact(idx->ws_scope_bm.as<uint32_t>(), sl.words, sl.n_bitmaps, idx->ws_scope_chunks.as<uint32_t>(),
+                                          idx->ws_scope_sel.as<uint32_t>(), B, sl.d_limit, epi.buf, cap, s));
+    }
+
+    // ---- keyword side (its own stream), query constants, then the two join
+    KwSide kws;
+    ORR_TRY(launch_keyword_side(idx, a, qoff, kws));
+    io.kw = kws.view;
+    ORR_TRY(launch_consts(idx, a, p, 0, qoff, q_download_pending, io));
+    if (n_terms_total > 0) HIP_TRY(hipStreamWaitEvent(s, idx->ev_kw_done, 0));
+
+    // ---- the re-score in the reference arithmetic and the records
+    const bool tail_kernels = p.use_cos && D % 64 == 0;        // rescore_buffer_exact / finish_survivors apply
+    const double pair_bytes = (double)B * (double)worst * 4.0 * (p.use_cos ? D : 0);
+    auto rescore = [&]() -> int {
+        if (tail_kernels) {
+            Timed t(idx, "rescore_buffer_exact", pair_bytes);
+            HIP_TRY(orr::launch_rescore_buffer_exact(idx->d_emb, D, io.d_q, B, idx->d_norm_b, idx->d_created, io.kw, idx->ws_qc.as<orr::QueryConst>(),
+                                                     a.now_ticks, epi.cnt, cap, epi.buf, idx->ws_fdot.as<double>(), s));
+        } else {
+            Timed t(idx, "scope_rescore", pair_bytes);
+            HIP_TRY(orr::launch_scope_rescore_generic(idx->d_emb, D, io.d_q, B, idx->d_norm_b, idx->d_created, io.kw, idx->ws_qc.as<orr::QueryConst>(),
+                                                      a.now_ticks, epi.cnt, cap, epi.buf, idx->ws_fdot.as<double>(), s));
+        }
+        return ORR_OK;
+    };
+    if (form == scope::Form::AllRecords) {
+        ORR_TRY(rescore());
+        Timed t(idx, "scope_records", (double)rec_bytes);
+        HIP_TRY(orr::launch_scope_records(epi.buf, idx->ws_fdot.as<double>(), epi.cnt, cap, B, kprime, idx->row_base, idx->d_norm_b, idx->d_created,
+                                          idx->d_row_ids, io.kw, io.d_cand, s));
+    } else {
+        const int32_t group = orr::finish_survivors_group(B, D);
+        const int32_t lists_room = std::max<int32_t>(buf_lists, group ? (int32_t)(cap / (uint32_t)group) : 0);
+        ORR_TRY(idx->ws_sel.reserve(sizeof(orr::SelEntry) * (size_t)B * (size_t)lists_room * orr::kSelWidth));
+        if (tail_kernels) {
+            ORR_TRY(two_stage_tail(idx, a, kprime, idx->n_rows, io, epi, cap, buf_lists, io.direct_host, rec_bytes, s));
+        } else {
+            ORR_TRY(rescore());
+            {
+                Timed t(idx, "buffer_to_lists", 0.0);
+                HIP_TRY(orr::launch_buffer_to_lists(epi.buf, epi.cnt, cap, B, 0, buf_lists, idx->ws_sel.as<orr::SelEntry>(), s));
+            }
+            {
+                Timed t(idx, "select_final", (double)B * (double)buf_lists * orr::kSelWidth * sizeof(orr::SelEntry));
+                HIP_TRY(orr::launch_select_final(idx->ws_sel.as<orr::SelEntry>(), buf_lists, B, kprime, idx->n_rows, idx->row_base, nullptr, nullptr, 0,
+                                                 idx->d_norm_b, idx->d_created, idx->d_row_ids, io.kw, 0, 0.0, nullptr, epi.cnt, cap,
+                                                 idx->ws_tsL.as<double>(), io.d_cand, s));
+            }
+            Timed t(idx, "records_dot_from_buffer", 0.0);
+            HIP_TRY(orr::launch_records_dot_from_buffer(epi.buf, idx->ws_fdot.as<double>(), epi.cnt, cap, B, kprime, idx->row_base, io.d_cand, s));
+        }
+        HIP_TRY(orr::launch_scope_trailers(io.d_cand, B, kprime, epi.cnt, s));
+    }
+    if (!io.direct_host) HIP_TRY(hipMemcpyAsync(idx->pin_cand.p, io.d_cand, rec_bytes, hipMemcpyDeviceToHost, s));
+    idx->sstats.pass_mode = 4;
+    const int r = finish_pass(idx, a, p, kws, n_terms_total);
+    if (r != ORR_OK) return r;
+    *recs_host = idx->pin_cand.as<orr_candidate>();
+    return ORR_OK;
+}
+
+int run_scoped(orr_index *idx, const BatchArgs &a, const std::vector<uint32_t> &qsel, const ScopeSlice &sl, scope::Form form, int32_t kprime,
+               const float **q_host, const orr_candidate **recs_host)
+{
+    for (int attempt = 0;; ++attempt) {
+        const int r = run_scoped_pass(idx, a, qsel, sl, form, kprime, q_host, recs_host);
+        idx->sstats.passes += 1;
+        if (r != kRetryPass) return r;
+        if (attempt >= 3) return fail(ORR_EDEVICE, "the keyword hit list kept overflowing");
+    }
+}
+
+// the queries `ids` (of the call's numbering) as a batch: the call's own arguments when that is all of them in order
+int scoped_sub_batch(orr_index *idx, const BatchArgs &orig, const std::vector<int32_t> &ids, SubBatch &sb, BatchArgs &cur)
+{
+    bool whole = (int32_t)ids.size() == orig.B;
+    for (size_t i = 0; i < ids.size() && whole; ++i) whole = ids[i] == (int32_t)i;
+    if (whole) { cur = orig; return ORR_OK; }
+    return build_subset(idx, orig, ids, sb, cur);
+}
+
+constexpr size_t kScopeAllRecordsBytes = escalation::kPassWorkspaceBytes / 4;      // (its records also cross to the host in one piece)
+
+// bytes per pair of a Selection pass on this lane: the smallest group the tail's one-launch form may sort (a sub-batch of one
+// query), where that form runs at all
+size_t scoped_selection_pair_bytes(const orr_index *idx, const BatchArgs &a)
+{
+    const bool fused_tail = a.dim > 0 && a.dim == idx->dim && idx->dim % 256 == 0;
+    return scope::pair_bytes_selection(fused_tail ? orr::finish_survivors_group(1, idx->dim) : 0);
+}
+
+// a query whose scope brings more rows than a pass takes (scope::kMaxScopeRows) is refused before any pass runs
+int check_scope_sizes(const ScopeSlice &sl, const char *fn)
+{
+    for (int32_t i = 0; i < sl.nq; ++i)
+        if (sl.took[i] > scope::kMaxScopeRows)
+            return fail(ORR_EINVAL, "%s: the scope of query %d resolves to %u rows; at most %u scoped rows per query take part in one search "
+                        "(lower candidate_limit, or search unscoped)", fn, sl.b0 + i, sl.took[i], scope::kMaxScopeRows);
+    return ORR_OK;
+}
+
+// orr_search_batch_scoped on the lane the caller holds.
+int scoped_batch(orr_index *idx, const BatchArgs &orig, const ScopeArgs &sc, int64_t *out_rows, double *out_scores, int32_t *out_counts)
+{
+    const int32_t B = orig.B, take = std::max<int32_t>(1, orig.topk);
+    const bool use_cos = orig.dim > 0 && orig.dim == idx->dim;
+    for (size_t i = 0; i < (size_t)B * take; ++i) { out_rows[i] = -1; out_scores[i] = 0.0; }
+    if (out_counts) for (int32_t b = 0; b < B; ++b) out_counts[b] = 0;
+    if (idx->n_rows <= 0 || sc.n_ids == 0) return ORR_OK;
+    ORR_TRY(bind_device(idx));
+    ORR_TRY(ensure_scope_table(idx));
+    const std::vector<int64_t> limit((size_t)B, std::max<int64_t>(1, orig.candidate_limit));     // Take(Math.Max(1, maxCount)), over the scoped rows
+    const int32_t per = scope::bitmap_slice(B, idx->n_rows, escalation::kPassWorkspaceBytes / 4);
+    for (int32_t b0 = 0; b0 < B; b0 += per) {
+        ScopeSlice sl;
+        ORR_TRY(build_scope_slice(idx, sc, limit, b0, std::min<int32_t>(per, B - b0), sl));
+        ORR_TRY(check_scope_sizes(sl, "orr_search_batch_scoped"));
+        struct Todo { std::vector<uint32_t> q; scope::Rung rung; int repeats; };     // queries of the slice and the pass they take next
+        Todo first{{}, {}, 0};
+        uint32_t max_scope = 0;
+        for (int32_t i = 0; i < sl.nq; ++i)
+            if (sl.took[i] > 0) { first.q.push_back((uint32_t)i); max_scope = std::max(max_scope, sl.took[i]); }
+        if (first.q.empty()) continue;
+        first.rung = scope::first_rung(take, max_scope, orr::kSelWidth);
+        std::deque<Todo> todo(1, std::move(first));
+        while (!todo.empty()) {
+            const Todo r = std::move(todo.front());
+            todo.pop_front();
+            const bool all = r.rung.form == scope::Form::AllRecords;
+            std::vector<uint32_t> counts(r.q.size());
+            for (size_t i = 0; i < r.q.size(); ++i) counts[i] = sl.took[r.q[i]];
+            Todo next{{}, {}, r.repeats + 1};
+            uint32_t next_scope = 0;
+            for (const auto &part : scope::slice_by_pairs(counts, all ? scope::kPairBytesAllRecords : scoped_selection_pair_bytes(idx, orig),
+                                                          all ? kScopeAllRecordsBytes : escalation::kPassWorkspaceBytes)) {
+                const std::vector<uint32_t> qsel(r.q.begin() + part.first, r.q.begin() + part.second);
+                const int32_t nb = (int32_t)qsel.size();
+                std::vector<int32_t> ids((size_t)nb);
+                uint32_t worst = 1;
+                for (int32_t i = 0; i < nb; ++i) { ids[(size_t)i] = b0 + (int32_t)qsel[(size_t)i]; worst = std::max(worst, sl.took[qsel[(size_t)i]]); }
+                const int32_t kprime = all ? (int32_t)worst : (int32_t)r.rung.kprime;
+                SubBatch sb;
+                BatchArgs cur;
+                ORR_TRY(scoped_sub_batch(idx, orig, ids, sb, cur));
+                const float *q_host = nullptr;
+                const orr_candidate *recs = nullptr;
+                ORR_TRY(run_scoped(idx, cur, qsel, sl, r.rung.form, kprime, &q_host, &recs));
+                std::vector<uint8_t> cert((size_t)nb, 1);
+                std::vector<int64_t> rows((size_t)nb * take);
+                std::vector<double> scores((size_t)nb * take);
+                std::vector<int32_t> cnts((size_t)nb);
+                ORR_TRY(merge_impl(1, nb, kprime, recs, cur.dim, use_cos, q_host, idx->h_norm_a.data(), cur.query_term_off, cur.now_ticks, cur.topk,
+                                   rows.data(), scores.data(), cnts.data(), nullptr, cert.data()));
+                for (int32_t i = 0; i < nb; ++i) {
+                    const size_t b = (size_t)ids[(size_t)i];
+                    memcpy(out_rows + b * take, rows.data() + (size_t)i * take, sizeof(int64_t) * take);
+                    memcpy(out_scores + b * take, scores.data() + (size_t)i * take, sizeof(double) * take);
+                    if (out_counts) out_counts[b] = cnts[(size_t)i];
+                    if (!cert[(size_t)i]) { next.q.push_back(qsel[(size_t)i]); next_scope = std::max(next_scope, sl.took[qsel[(size_t)i]]); }
+                }
+                if (r.repeats > 0) idx->sstats.requeried += nb;
+            }
+            if (next.q.empty()) continue;
+            next.rung = scope::next_rung(r.rung, next_scope, orr::kSelWidth);
+            if (next.rung.form == scope::Form::Done || next.repeats > scope::kMaxRungs)
+                return fail(ORR_EDEVICE, "orr_search_batch_scoped: a pass over every scoped row left a query uncertified");
+            todo.push_front(std::move(next));
+        }
+    }
+    return ORR_OK;
+}
+
+// The best kprime records of each query out of its K >= kprime AllRecords records, ranked by the exact key on the host, with the
+// trailer orr_search_shard leaves: the cut-off is the worst kept record's exact score (bound 0).
+void reduce_all_records(const orr_candidate *recs, int32_t nb, int32_t K, int32_t kprime, bool use_cos, const double *norms,
+                        const uint32_t *query_term_off, int64_t now_ticks, orr_candidate *out)
+{
+    std::vector<std::pair<Ranked, int32_t>> ranked;
+    for (int32_t b = 0; b < nb; ++b) {
+        const orr_candidate *in = recs + (size_t)b * ((size_t)K + 1);
+        orr_candidate *o = out + (size_t)b * ((size_t)kprime + 1);
+        const int32_t n = in[K].matches;
+        ranked.clear();
+        for (int32_t i = 0; i < n; ++i) {
+            Ranked r;
+            r.score = exact_score(in[i], use_cos, use_cos ? norms[b] : 0.0, (int32_t)(query_term_off[b + 1] - query_term_off[b]), now_ticks);
+            r.order_key = in[i].order_key;
+            r.row_id = in[i].row_id;
+            ranked.push_back({r, i});
+        }
+        std::sort(ranked.begin(), ranked.end(), [](const std::pair<Ranked, int32_t> &x, const std::pair<Ranked, int32_t> &y) {
+            const int c = compare_double(x.first.score, y.first.score);
+            return c != 0 ? c > 0 : x.first.order_key < y.first.order_key;
+        });
+        const int32_t kept = std::min<int32_t>(n, kprime);
+        for (int32_t i = 0; i < kprime; ++i) {
+            if (i < kept) {
+                o[i] = in[ranked[(size_t)i].second];
+                o[i].approx_score = ranked[(size_t)i].first.score;
+            } else {
+                memset(&o[i], 0, sizeof(o[i]));
+                o[i].row_id = -1; o[i].order_key = -1;
+            }
+        }
+        orr_candidate t = in[K];
+        t.matches = kept;
+        t.approx_score = n <= kprime ? -std::numeric_limits<double>::infinity() : ranked[(size_t)kept - 1].first.score;
+        o[kprime] = t;
+    }
+}
+
+// orr_search_shard_scoped on the lane the caller holds: one pass at the caller's k', no ladder (the caller's merge certifies).
+int scoped_shard(orr_index *idx, const BatchArgs &orig, const ScopeArgs &sc, int32_t kprime, orr_candidate *out)
+{
+    const int32_t B = orig.B;
+    const bool use_cos = orig.dim > 0 && orig.dim == idx->dim;
+    const size_t rec_q = (size_t)kprime + 1;
+    std::vector<int64_t> limit((size_t)B);
+    for (int32_t b = 0; b < B; ++b)
+        limit[(size_t)b] = std::max<int64_t>(0, std::max<int64_t>(1, orig.candidate_limit) - (sc.before ? std::max<int64_t>(0, sc.before[b]) : 0));
+    ORR_TRY(bind_device(idx));
+    if (idx->n_rows <= 0 || sc.n_ids == 0) {           // nothing on this shard takes part: empty records + trailers
+        std::vector<orr_candidate> empty((size_t)B * rec_q);
+        for (auto &c : empty) { memset(&c, 0, sizeof(c)); c.row_id = -1; c.order_key = -1; }
+        for (int32_t b = 0; b < B; ++b) {
+            orr_candidate &t = empty[(size_t)b * rec_q + (size_t)kprime];
+            t.approx_score = -std::numeric_limits<double>::infinity();
+            t.order_key = 0; t.flags = ORR_CAND_TRAILER;
+        }
+        HIP_TRY(hipMemcpy(out, empty.data(), sizeof(orr_candidate) * empty.size(), hipMemcpyDefault));
+        return ORR_OK;
+    }
+    ORR_TRY(ensure_scope_table(idx));
+    const bool all = kprime > orr::kSelWidth;
+    const int32_t per = scope::bitmap_slice(B, idx->n_rows, escalation::kPassWorkspaceBytes / 4);
+    std::vector<orr_candidate> reduced;
+    for (int32_t b0 = 0; b0 < B; b0 += per) {
+        ScopeSlice sl;
+        ORR_TRY(build_scope_slice(idx, sc, limit, b0, std::min<int32_t>(per, B - b0), sl));
+        ORR_TRY(check_scope_sizes(sl, "orr_search_shard_scoped"));
+        const std::vector<uint32_t> counts(sl.took, sl.took + sl.nq);
+        for (const auto &part : scope::slice_by_pairs(counts, all ? scope::kPairBytesAllRecords : scoped_selection_pair_bytes(idx, orig),
+                                                      all ? kScopeAllRecordsBytes : escalation::kPassWorkspaceBytes)) {
+            const int32_t nb = part.second - part.first;
+            std::vector<uint32_t> qsel((size_t)nb);
+            std::vector<int32_t> ids((size_t)nb);
+            uint32_t worst = (uint32_t)kprime;         // (AllRecords: at least k' records per query, so that the reduction has its slots)
+            for (int32_t i = 0; i < nb; ++i) {
+                qsel[(size_t)i] = (uint32_t)(part.first + i); ids[(size_t)i] = b0 + part.first + i;
+                worst = std::max(worst, sl.took[part.first + i]);
+            }
+            SubBatch sb;
+            BatchArgs cur;
+            ORR_TRY(scoped_sub_batch(idx, orig, ids, sb, cur));
+            const float *q_host = nullptr;
+            const orr_candidate *recs = nullptr;
+            ORR_TRY(run_scoped(idx, cur, qsel, sl, all ? scope::Form::AllRecords : scope::Form::Selection, all ? (int32_t)worst : kprime, &q_host, &recs));
+            if (all) {
+                reduced.resize((size_t)nb * rec_q);
+                reduce_all_records(recs, nb, (int32_t)worst, kprime, use_cos, idx->h_norm_a.data(), cur.query_term_off, cur.now_ticks, reduced.data());
+                recs = reduced.data();
+            }
+            HIP_TRY(hipMemcpy(out + (size_t)ids[0] * rec_q, recs, sizeof(orr_candidate) * (size_t)nb * rec_q, hipMemcpyDefault));
+        }
+    }
+    return ORR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3623,6 +4122,70 @@ int orr_search_batch(orr_index *idx, int32_t B, int32_t dim, const float *q, con
                            out_rows, out_scores, out_counts);
     g_ht.done();
     return r;
+}
+
+int orr_search_batch_scoped(orr_index *idx, int32_t B, int32_t dim, const float *q, const uint8_t *terms_utf8,
+                            const uint32_t *term_off, const uint32_t *query_term_off, int64_t now_ticks, int32_t topk,
+                            int64_t candidate_limit, int64_t n_scope_ids, const int64_t *scope_ids, const uint64_t *scope_off,
+                            int64_t *out_rows, double *out_scores, int32_t *out_counts)
+{
+    BatchArgs a{B, dim, q, terms_utf8, term_off, query_term_off, now_ticks, candidate_limit, topk};
+    const ScopeArgs sc{n_scope_ids, scope_ids, scope_off, nullptr};
+    ORR_TRY(check_scope(idx, B, sc, "orr_search_batch_scoped"));
+    ORR_TRY(check_batch(idx, a, "orr_search_batch_scoped"));
+    if (!out_rows || !out_scores) return fail(ORR_EINVAL, "orr_search_batch_scoped: output buffers are required");
+    Lane ln = acquire_lane(idx);                       // a search like any other: its own lane, concurrent with the others
+    idx = ln.lane;
+    std::lock_guard<std::mutex> lock(idx->mu);
+    idx->sstats.searches += 1;
+    idx->sstats.queries += B;
+    return scoped_batch(idx, a, sc, out_rows, out_scores, out_counts);
+}
+
+int orr_search_shard_scoped(orr_index *idx, int32_t B, int32_t dim, const float *q, const uint8_t *terms_utf8,
+                            const uint32_t *term_off, const uint32_t *query_term_off, int64_t now_ticks, int32_t kprime,
+                            int64_t candidate_limit, int32_t topk, int64_t n_scope_ids, const int64_t *scope_ids,
+                            const uint64_t *scope_off, const int64_t *scope_before, orr_candidate *out)
+{
+    BatchArgs a{B, dim, q, terms_utf8, term_off, query_term_off, now_ticks, candidate_limit, kprime};
+    const ScopeArgs sc{n_scope_ids, scope_ids, scope_off, scope_before};
+    ORR_TRY(check_scope(idx, B, sc, "orr_search_shard_scoped"));
+    ORR_TRY(check_batch(idx, a, "orr_search_shard_scoped"));
+    if (kprime < 1) return fail(ORR_EINVAL, "orr_search_shard_scoped: kprime must be >= 1");
+    if (topk < 0) return fail(ORR_EINVAL, "orr_search_shard_scoped: topk must be >= 0");
+    if (!out) return fail(ORR_EINVAL, "orr_search_shard_scoped: out is NULL");
+    if (topk > 0) a.topk = std::min<int32_t>(kprime, topk);
+    Lane ln = acquire_lane(idx);
+    idx = ln.lane;
+    std::lock_guard<std::mutex> lock(idx->mu);
+    idx->sstats.searches += 1;
+    idx->sstats.queries += B;
+    return scoped_shard(idx, a, sc, kprime, out);
+}
+
+int orr_index_scope_count(orr_index *idx, int32_t B, int64_t n_scope_ids, const int64_t *scope_ids, const uint64_t *scope_off,
+                          int64_t *out_live)
+{
+    const ScopeArgs sc{n_scope_ids, scope_ids, scope_off, nullptr};
+    ORR_TRY(check_scope(idx, B, sc, "orr_index_scope_count"));
+    if (B <= 0) return fail(ORR_EINVAL, "orr_index_scope_count: batch size must be positive");
+    if (!out_live) return fail(ORR_EINVAL, "orr_index_scope_count: out_live is NULL");
+    if (!idx->sealed) return fail(ORR_ESTATE, "orr_index_scope_count: index is not sealed");
+    Lane ln = acquire_lane(idx);
+    idx = ln.lane;
+    std::lock_guard<std::mutex> lock(idx->mu);
+    for (int32_t b = 0; b < B; ++b) out_live[b] = 0;
+    if (idx->n_rows <= 0 || n_scope_ids == 0) return ORR_OK;
+    ORR_TRY(bind_device(idx));
+    ORR_TRY(ensure_scope_table(idx));
+    const std::vector<int64_t> limit((size_t)B, std::numeric_limits<int64_t>::max());
+    const int32_t per = scope::bitmap_slice(B, idx->n_rows, escalation::kPassWorkspaceBytes / 4);
+    for (int32_t b0 = 0; b0 < B; b0 += per) {
+        ScopeSlice sl;
+        ORR_TRY(build_scope_slice(idx, sc, limit, b0, std::min<int32_t>(per, B - b0), sl));
+        for (int32_t i = 0; i < sl.nq; ++i) out_live[b0 + i] = (int64_t)sl.live[i];
+    }
+    return ORR_OK;
 }
 
 }  // extern "C"

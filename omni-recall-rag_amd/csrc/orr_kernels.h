@@ -7,6 +7,7 @@
 
 #include "../../include/omnirecall_hip.h"
 #include "orr_layout.h"
+#include "orr_scope_plan.h"
 
 #include <atomic>
 
@@ -387,5 +388,40 @@ hipError_t launch_iota_i64(int64_t *dst, int64_t n, int64_t base, hipStream_t s)
 hipError_t launch_tombstone_rows(const int64_t *pos, int32_t n, double *norm_b, int64_t *created, hipStream_t s);
 hipError_t launch_mark_dead_records(orr_candidate *recs, int32_t B, int32_t kprime, const int64_t *dead, int32_t n_dead,
                                     int64_t row_base, hipStream_t s);
+
+
+// ---- scoped search (orr_search_batch_scoped; the rules are orr_scope_plan.h's) ----------------------------------------------
+// The id table of a sealed shard: ids_out ascending with pos_out the rows' positions (ascending within equal ids), through a
+// stable radix sort of (ids_in, 0 .. n-1); pos_in is scratch of n words.  temp == nullptr: only temp_bytes is set.
+hipError_t scope_sort_id_table(void *temp, size_t &temp_bytes, const int64_t *ids_in, int64_t *ids_out, uint32_t *pos_in,
+                               uint32_t *pos_out, int64_t n, hipStream_t s);
+// Listed ids -> bits: bit p of bitmaps[b * words ..) for every live row p (not in dead[], ascending) that carries an id of
+// query b's list ids[scope_off[b] .. scope_off[b + 1]) (scope_off == nullptr: one bitmap for the whole list).  The bitmaps
+// must be zero on entry; words % 4 == 0, words * 32 >= n_rows.
+hipError_t launch_scope_lookup(const int64_t *table_ids, const uint32_t *table_pos, int64_t n_rows, const int64_t *ids, int64_t n_ids,
+                               const uint64_t *scope_off, int32_t n_q, const int64_t *dead, int32_t n_dead, uint32_t *bitmaps,
+                               int64_t words, hipStream_t s);
+constexpr int kScopeChunkWords = 1024;     // words of a bitmap one workgroup counts / compacts (32,768 rows)
+inline int32_t scope_chunks(int64_t words) { return (int32_t)((words + kScopeChunkWords - 1) / kScopeChunkWords); }
+// chunk_cnt[n_bitmaps][scope_chunks(words)] = set bits per chunk; live[q] = set bits of query q's bitmap, took[q] =
+// min(live[q], max(0, limit[q])) (live / took may be pinned host memory).  n_bitmaps is n_q, or 1: all queries share it.
+hipError_t launch_scope_counts(const uint32_t *bitmaps, int64_t words, int32_t n_bitmaps, int32_t n_q, const int64_t *limit,
+                               uint32_t *chunk_cnt, uint32_t *live, uint32_t *took, hipStream_t s);
+// buf[i][0 .. took[qsel[i]]) = the first limit[qsel[i]] set bits of query qsel[i]'s bitmap as entries in candidate order
+// (key 1, pos = the row); cap entries per query, nothing is written beyond them.
+hipError_t launch_scope_compact(const uint32_t *bitmaps, int64_t words, int32_t n_bitmaps, const uint32_t *chunk_cnt, const uint32_t *qsel,
+                                int32_t n_sel, const int64_t *limit, SelEntry *buf, uint32_t cap, hipStream_t s);
+// launch_rescore_buffer_exact for any D and for queries without a cosine part (qc.use_cos == 0: Q is not read); also leaves
+// the pair's keyword matches in the entry's pad.
+hipError_t launch_scope_rescore_generic(const float *E, int32_t D, const float *Q, int32_t B, const double *norm_b, const int64_t *created,
+                                        KwView kw, const QueryConst *qc, int64_t now_ticks, const uint32_t *cnt, uint32_t cap, SelEntry *buf,
+                                        double *buf_dot, hipStream_t s);
+// Every buffered pair of a query as a record (exact dot from buf_dot, ORR_CAND_DOT_EXACT), kprime >= every count; trailer:
+// approx_score -inf, order_key = the query's count.
+hipError_t launch_scope_records(const SelEntry *buf, const double *buf_dot, const uint32_t *cnt, uint32_t cap, int32_t B, int32_t kprime,
+                                int64_t row_base, const double *norm_b, const int64_t *created, const int64_t *row_ids, KwView kw,
+                                orr_candidate *recs, hipStream_t s);
+// The trailers the two-stage tail wrote, made a scoped pass's: order_key = cnt[b], no floor (ORR_CAND_TWO_STAGE cleared).
+hipError_t launch_scope_trailers(orr_candidate *recs, int32_t B, int32_t kprime, const uint32_t *cnt, hipStream_t s);
 
 }  // namespace orr

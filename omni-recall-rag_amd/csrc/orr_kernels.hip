@@ -1416,4 +1416,304 @@ hipError_t launch_mark_dead_records(orr_candidate *recs, int32_t B, int32_t kpri
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Scoped search (orr_search_batch_scoped): the rows a caller lists by id become the entries of the survivors' buffers
+// the exact tail of the two-stage pass consumes.  No kernel here reads an embedding of a row outside a scope.
+//   id table     the shard's (row id, position) pairs sorted by id: ids[] ascending, pos[] ascending within equal ids
+//   bitmaps      one bit per row of the shard and scope: removes repeats, keeps candidate order, and makes candidate_limit a
+//                prefix popcount (scope::clip_word, shared with the host's selftest)
+//   chunks       kScopeChunkWords words of a bitmap: the unit of the popcounts and of the compaction's workgroups
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void iota_u32_kernel(uint32_t *__restrict__ dst, int64_t n)
+{
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) dst[r] = (uint32_t)r;
+}
+
+hipError_t scope_sort_id_table(void *temp, size_t &temp_bytes, const int64_t *ids_in, int64_t *ids_out, uint32_t *pos_in,
+                               uint32_t *pos_out, int64_t n, hipStream_t s)
+{
+    if (temp) {
+        hipLaunchKernelGGL(iota_u32_kernel, dim3(capped_blocks(n, 256)), dim3(256), 0, s, pos_in, n);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    // (a stable radix sort: equal ids keep their positions ascending)
+    return hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, ids_in, ids_out, pos_in, pos_out, (int)n, 0, 64, s);
+}
+
+// One thread per listed id: the run of equal ids in the table, every live position of it a bit in the bitmap of the query that
+// owns the id (scope_off[n_q + 1] relative to ids[0]; null: one bitmap for all).  Unknown ids find no run.
+__global__ __launch_bounds__(256) void scope_lookup_kernel(const int64_t *__restrict__ table_ids, const uint32_t *__restrict__ table_pos,
+                                                           int64_t n_rows, const int64_t *__restrict__ ids, int64_t n_ids,
+                                                           const uint64_t *__restrict__ scope_off, int32_t n_q,
+                                                           const int64_t *__restrict__ dead, int32_t n_dead,
+                                                           uint32_t *__restrict__ bitmaps, int64_t words)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_ids) return;
+    int64_t bm = 0;
+    if (scope_off) {                                   // the query b with scope_off[b] <= i < scope_off[b + 1]
+        int32_t lo = 0, hi = n_q;
+        while (hi - lo > 1) {
+            const int32_t mid = (lo + hi) >> 1;
+            if (scope_off[mid] <= (uint64_t)i) lo = mid; else hi = mid;
+        }
+        bm = lo;
+    }
+    const int64_t want = ids[i];
+    int64_t lo = 0, hi = n_rows;                       // first table entry with id >= want
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (table_ids[mid] < want) lo = mid + 1; else hi = mid;
+    }
+    for (; lo < n_rows && table_ids[lo] == want; ++lo) {
+        const uint32_t p = table_pos[lo];
+        int32_t dl = 0, dh = n_dead;                   // deleted rows take no part (dead[] ascending)
+        while (dl < dh) {
+            const int32_t mid = (dl + dh) >> 1;
+            if (dead[mid] < (int64_t)p) dl = mid + 1; else dh = mid;
+        }
+        if (dl < n_dead && dead[dl] == (int64_t)p) continue;
+        atomicOr(bitmaps + bm * words + (p >> 5), 1u << (p & 31u));
+    }
+}
+
+hipError_t launch_scope_lookup(const int64_t *table_ids, const uint32_t *table_pos, int64_t n_rows, const int64_t *ids, int64_t n_ids,
+                               const uint64_t *scope_off, int32_t n_q, const int64_t *dead, int32_t n_dead, uint32_t *bitmaps,
+                               int64_t words, hipStream_t s)
+{
+    if (n_ids <= 0 || n_rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(scope_lookup_kernel, dim3((unsigned)((n_ids + 255) / 256)), dim3(256), 0, s, table_ids, table_pos, n_rows, ids, n_ids,
+                       scope_off, n_q, dead, n_dead, bitmaps, words);
+    return hipGetLastError();
+}
+
+__device__ __forceinline__ uint32_t block_sum_u32(uint32_t v, uint32_t *sh4)   // 256 threads; every thread gets the sum
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off, 64);
+    __syncthreads();                                   // (sh4 may still be read from a previous call)
+    if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return sh4[0] + sh4[1] + sh4[2] + sh4[3];
+}
+
+// chunk_cnt[bm][chunk] = set bits of that chunk
+__global__ __launch_bounds__(256) void scope_chunk_counts_kernel(const uint32_t *__restrict__ bitmaps, int64_t words, int32_t n_chunks,
+                                                                 uint32_t *__restrict__ chunk_cnt)
+{
+    __shared__ uint32_t sh4[4];
+    const int64_t bm = blockIdx.x, w0 = (int64_t)blockIdx.y * kScopeChunkWords + (int64_t)threadIdx.x * 4;
+    uint32_t c = 0;
+    if (w0 < words) {                                  // (words is a multiple of 4: whole uint4s)
+        const uint4 v = *reinterpret_cast<const uint4 *>(bitmaps + bm * words + w0);
+        c = __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w);
+    }
+    c = block_sum_u32(c, sh4);
+    if (threadIdx.x == 0) chunk_cnt[bm * n_chunks + blockIdx.y] = c;
+}
+
+// Per query: live[q] = rows its scope resolves to, took[q] = min(live, limit[q]) (either may be pinned host memory)
+__global__ __launch_bounds__(256) void scope_totals_kernel(const uint32_t *__restrict__ chunk_cnt, int32_t n_chunks, int32_t shared_scope,
+                                                           const int64_t *__restrict__ limit, uint32_t *__restrict__ live,
+                                                           uint32_t *__restrict__ took)
+{
+    __shared__ uint32_t sh4[4];
+    const int q = blockIdx.x;
+    const uint32_t *mine = chunk_cnt + (int64_t)(shared_scope ? 0 : q) * n_chunks;
+    uint32_t c = 0;
+    for (int i = threadIdx.x; i < n_chunks; i += 256) c += mine[i];
+    c = block_sum_u32(c, sh4);
+    if (threadIdx.x == 0) {
+        live[q] = c;
+        const int64_t lim = limit[q] < 0 ? 0 : limit[q];
+        took[q] = (int64_t)c < lim ? c : (uint32_t)lim;
+    }
+}
+
+hipError_t launch_scope_counts(const uint32_t *bitmaps, int64_t words, int32_t n_bitmaps, int32_t n_q, const int64_t *limit,
+                               uint32_t *chunk_cnt, uint32_t *live, uint32_t *took, hipStream_t s)
+{
+    if (n_q <= 0 || n_bitmaps <= 0) return hipSuccess;
+    if (words % 4 != 0 || (n_bitmaps != 1 && n_bitmaps != n_q)) return hipErrorInvalidValue;
+    const int32_t n_chunks = scope_chunks(words);
+    if (n_chunks > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(scope_chunk_counts_kernel, dim3((unsigned)n_bitmaps, (unsigned)n_chunks), dim3(256), 0, s, bitmaps, words, n_chunks, chunk_cnt);
+    hipLaunchKernelGGL(scope_totals_kernel, dim3((unsigned)n_q), dim3(256), 0, s, chunk_cnt, n_chunks, n_bitmaps == 1 && n_q > 1 ? 1 : 0, limit,
+                       live, took);
+    return hipGetLastError();
+}
+
+// Workgroup (i, chunk): query qsel[i] of the slice's bitmaps; the chunk's set bits, clipped to the query's first limit rows,
+// become entries buf[i][rank] in candidate order (key 1: a placeholder the re-score overwrites; 0 would be an empty slot).
+__global__ __launch_bounds__(256) void scope_compact_kernel(const uint32_t *__restrict__ bitmaps, int64_t words, int32_t n_chunks,
+                                                            const uint32_t *__restrict__ chunk_cnt, int32_t shared_scope,
+                                                            const uint32_t *__restrict__ qsel, const int64_t *__restrict__ limit,
+                                                            SelEntry *__restrict__ buf, uint32_t cap)
+{
+    __shared__ uint32_t sh4[4];
+    __shared__ uint32_t wave_base[4];
+    const int i = blockIdx.x, chunk = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t q = qsel[i];
+    const int64_t bm = shared_scope ? 0 : (int64_t)q;
+    const uint32_t *cc = chunk_cnt + bm * n_chunks;
+    if (cc[chunk] == 0u) return;                                   // (uniform: most chunks of a small scope)
+    const int64_t lim = limit[q] < 0 ? 0 : limit[q];
+    uint32_t before = 0;                                           // set bits in front of this chunk
+    for (int c = tid; c < chunk; c += 256) before += cc[c];
+    before = block_sum_u32(before, sh4);
+    if ((int64_t)before >= lim) return;
+    const int64_t w0 = (int64_t)chunk * kScopeChunkWords + (int64_t)tid * 4;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    if (w0 < words) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(bitmaps + bm * words + w0);
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    }
+    const uint32_t mine = __popc(w[0]) + __popc(w[1]) + __popc(w[2]) + __popc(w[3]);
+    uint32_t incl = mine;                                          // inclusive scan over the wave, then over the four waves
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t o = (uint32_t)__shfl_up((int)incl, off, 64);
+        if (lane >= off) incl += o;
+    }
+    if (lane == 63) wave_base[wave] = incl;
+    __syncthreads();
+    uint32_t rank = before + incl - mine;
+    for (int k = 0; k < wave; ++k) rank += wave_base[k];
+    SelEntry *out = buf + (int64_t)i * cap;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        uint32_t bits = scope::clip_word(w[k], (uint64_t)rank, (uint64_t)lim);
+        rank += __popc(w[k]);
+        uint32_t r = rank - __popc(w[k]);
+        while (bits) {
+            const uint32_t bit = (uint32_t)__ffs((int)bits) - 1u;
+            bits &= bits - 1u;
+            if (r < cap) {
+                SelEntry e;
+                e.key = 1ull; e.pos = (uint32_t)((w0 + k) * 32 + bit); e.pad = 0u;
+                out[r] = e;
+            }
+            ++r;
+        }
+    }
+}
+
+hipError_t launch_scope_compact(const uint32_t *bitmaps, int64_t words, int32_t n_bitmaps, const uint32_t *chunk_cnt, const uint32_t *qsel,
+                                int32_t n_sel, const int64_t *limit, SelEntry *buf, uint32_t cap, hipStream_t s)
+{
+    if (n_sel <= 0) return hipSuccess;
+    if (words % 4 != 0 || cap == 0) return hipErrorInvalidValue;
+    const int32_t n_chunks = scope_chunks(words);
+    if (n_chunks > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(scope_compact_kernel, dim3((unsigned)n_sel, (unsigned)n_chunks), dim3(256), 0, s, bitmaps, words, n_chunks, chunk_cnt,
+                       n_bitmaps == 1 ? 1 : 0, qsel, limit, buf, cap);
+    return hipGetLastError();
+}
+
+// The re-score of the buffered pairs where the tail's own kernels do not apply (a dimension that is no multiple of 64, or no
+// cosine at all: dim 0, a query of another dimension): one thread per pair, the reference's sum in index order.
+__global__ __launch_bounds__(256) void scope_rescore_generic_kernel(const float *__restrict__ E, int32_t D, const float *__restrict__ Q,
+                                                                    const double *__restrict__ norm_b, const int64_t *__restrict__ created,
+                                                                    KwView kw, const QueryConst *__restrict__ qcs, int64_t now_ticks,
+                                                                    const uint32_t *__restrict__ cnt, uint32_t cap, SelEntry *__restrict__ buf,
+                                                                    double *__restrict__ buf_dot)
+{
+    const int b = blockIdx.x;
+    const uint32_t n = cnt[b] < cap ? cnt[b] : cap;
+    const QueryConst qc = qcs[b];
+    for (uint32_t i = blockIdx.y * 256u + threadIdx.x; i < n; i += gridDim.y * 256u) {
+        SelEntry *mine = buf + (int64_t)b * cap + i;
+        const int64_t row = (int64_t)mine->pos;
+        double acc = 0.0;
+        if (qc.use_cos) {
+            const float *e = E + row * (int64_t)D, *q = Q + (int64_t)b * D;
+            for (int c = 0; c < D; ++c) {
+                const float p = q[c] * e[c];
+                acc += (double)p;
+            }
+        }
+        const uint32_t m = (qc.n_terms > 0 && kw.bitmaps) ? kw_matches(kw, b, (uint32_t)row) : 0u;
+        mine->key = score_key(fused_score(acc, norm_b[row], created[row], m, qc, now_ticks));
+        mine->pad = m;
+        buf_dot[(int64_t)b * cap + i] = acc;
+    }
+}
+
+hipError_t launch_scope_rescore_generic(const float *E, int32_t D, const float *Q, int32_t B, const double *norm_b, const int64_t *created,
+                                        KwView kw, const QueryConst *qc, int64_t now_ticks, const uint32_t *cnt, uint32_t cap, SelEntry *buf,
+                                        double *buf_dot, hipStream_t s)
+{
+    if (B <= 0 || cap == 0) return hipSuccess;
+    const unsigned gy = (unsigned)std::min<uint32_t>((cap + 255u) / 256u, 1024u);
+    hipLaunchKernelGGL(scope_rescore_generic_kernel, dim3((unsigned)B, gy), dim3(256), 0, s, E, D, Q, norm_b, created, kw, qc, now_ticks, cnt, cap,
+                       buf, buf_dot);
+    return hipGetLastError();
+}
+
+// AllRecords: every buffered pair a record with its exact dot (buf_dot, written by the re-score), in candidate order; empty
+// records behind them; the trailer says that nothing was cut (approx_score -inf) and how many scoped rows took part.
+__global__ __launch_bounds__(256) void scope_records_kernel(const SelEntry *__restrict__ buf, const double *__restrict__ buf_dot,
+                                                            const uint32_t *__restrict__ cnt, uint32_t cap, int32_t kprime, int64_t row_base,
+                                                            const double *__restrict__ norm_b, const int64_t *__restrict__ created,
+                                                            const int64_t *__restrict__ row_ids, KwView kw, orr_candidate *__restrict__ recs)
+{
+    const int b = blockIdx.x;
+    const uint32_t n = cnt[b] < cap ? cnt[b] : cap;
+    orr_candidate *o = recs + (int64_t)b * ((int64_t)kprime + 1);
+    for (int64_t i = (int64_t)blockIdx.y * 256 + threadIdx.x; i <= (int64_t)kprime; i += (int64_t)gridDim.y * 256) {
+        orr_candidate c;
+        if (i == (int64_t)kprime) {
+            const uint32_t valid = n < (uint32_t)kprime ? n : (uint32_t)kprime;
+            c.approx_score = -__builtin_huge_val(); c.dot = 0.0; c.norm_b = 0.0; c.created_ticks = 0;
+            c.row_id = -1; c.order_key = (int64_t)n; c.matches = (int32_t)valid; c.flags = ORR_CAND_TRAILER;
+        } else if (i < (int64_t)n) {
+            const SelEntry e = buf[(int64_t)b * cap + i];
+            c.approx_score = key_score(e.key);
+            c.dot = buf_dot[(int64_t)b * cap + i];
+            c.norm_b = norm_b[e.pos];
+            c.created_ticks = created[e.pos];
+            c.row_id = row_ids[e.pos];
+            c.order_key = row_base + (int64_t)e.pos;
+            c.matches = kw.bitmaps ? (int32_t)kw_matches(kw, b, e.pos) : 0;
+            c.flags = ORR_CAND_DOT_EXACT;
+        } else {
+            c.approx_score = 0.0; c.dot = 0.0; c.norm_b = 0.0; c.created_ticks = 0;
+            c.row_id = -1; c.order_key = -1; c.matches = 0; c.flags = 0;
+        }
+        o[i] = c;
+    }
+}
+
+hipError_t launch_scope_records(const SelEntry *buf, const double *buf_dot, const uint32_t *cnt, uint32_t cap, int32_t B, int32_t kprime,
+                                int64_t row_base, const double *norm_b, const int64_t *created, const int64_t *row_ids, KwView kw,
+                                orr_candidate *recs, hipStream_t s)
+{
+    if (B <= 0) return hipSuccess;
+    if (kprime < 1) return hipErrorInvalidValue;
+    const unsigned gy = (unsigned)std::min<int64_t>(((int64_t)kprime + 1 + 255) / 256, 1024);
+    hipLaunchKernelGGL(scope_records_kernel, dim3((unsigned)B, gy), dim3(256), 0, s, buf, buf_dot, cnt, cap, kprime, row_base, norm_b, created,
+                       row_ids, kw, recs);
+    return hipGetLastError();
+}
+
+// Selection: the tail's trailers say "two-stage, floor L, n rows took part"; a scoped pass has no floor and its rows are the
+// query's scoped ones -- order_key = the scoped rows that took part, no ORR_CAND_TWO_STAGE, norm_b 0.
+__global__ void scope_trailers_kernel(orr_candidate *recs, int32_t B, int32_t kprime, const uint32_t *__restrict__ cnt)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    orr_candidate *t = recs + (int64_t)b * ((int64_t)kprime + 1) + kprime;
+    t->order_key = (int64_t)cnt[b];
+    t->norm_b = 0.0;
+    t->flags &= ~ORR_CAND_TWO_STAGE;
+}
+
+hipError_t launch_scope_trailers(orr_candidate *recs, int32_t B, int32_t kprime, const uint32_t *cnt, hipStream_t s)
+{
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(scope_trailers_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, recs, B, kprime, cnt);
+    return hipGetLastError();
+}
+
 }  // namespace orr

@@ -240,6 +240,74 @@ class RecallIndex:
                                               int(kprime), int(candidate_limit), max(0, int(topk or 0)), int(shard_pass or 0), _ptr(out)))
         return out
 
+    @staticmethod
+    def _scope_args(scope_ids, n_queries: int):
+        """A scope for the ABI: one flat list of row ids (numpy / torch, host or device) shared by every query, or a sequence
+        of n_queries lists, one per query.  Returns (n_ids, ids, offsets or None)."""
+        shared = _is_torch(scope_ids) or isinstance(scope_ids, np.ndarray) or \
+            (len(scope_ids) == 0 or not hasattr(scope_ids[0], "__len__"))
+        if shared:
+            ids = scope_ids if _is_torch(scope_ids) else np.ascontiguousarray(scope_ids, dtype=np.int64).reshape(-1)
+            if _is_torch(ids):
+                ids = ids.reshape(-1)
+            return int(ids.shape[0]), ids, None
+        if len(scope_ids) != n_queries:
+            raise ValueError(f"scope_ids: {len(scope_ids)} lists for {n_queries} queries")
+        parts = [p if _is_torch(p) else np.ascontiguousarray(p, dtype=np.int64).reshape(-1) for p in scope_ids]
+        off = np.zeros(n_queries + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([int(p.shape[0]) for p in parts], dtype=np.uint64)
+        if parts and all(_is_torch(p) for p in parts):
+            import torch
+            ids = torch.cat([p.reshape(-1) for p in parts]).contiguous()
+        else:
+            parts = [p.cpu().numpy() if _is_torch(p) else p for p in parts]
+            ids = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0, np.int64), dtype=np.int64)
+        return int(ids.shape[0]), ids, off
+
+    def search_scoped(self, qvecs, queries_terms, now_ticks: int, topk: int, scope_ids, candidate_limit: int = 300, scope_off=None):
+        """orr_search_batch_scoped: every query ranks only the live rows whose id its scope lists.  scope_ids: one flat list
+        (numpy or torch, host or device) shared by all queries, a sequence of per-query lists, or -- with scope_off [B+1] given --
+        the flat list the offsets cut.  Returns (rows [B,k] int64, scores [B,k] float64, counts [B] int32)."""
+        B = len(queries_terms)
+        dim, q, _keep = self._query_args(qvecs, B)
+        pool, toff, qoff = pack_terms(queries_terms)
+        if scope_off is None:
+            n_ids, ids, off = self._scope_args(scope_ids, B)
+        else:
+            ids = scope_ids if _is_torch(scope_ids) else np.ascontiguousarray(scope_ids, dtype=np.int64).reshape(-1)
+            n_ids, off = int(ids.shape[0]), np.ascontiguousarray(scope_off, dtype=np.uint64)
+        k = max(1, int(topk))
+        rows = np.full((B, k), -1, dtype=np.int64)
+        scores = np.zeros((B, k), dtype=np.float64)
+        counts = np.zeros(B, dtype=np.int32)
+        N.check(N.hip.orr_search_batch_scoped(self._h, B, dim, _ptr(q), _ptr(pool), _ptr(toff), _ptr(qoff), now_ticks, int(topk),
+                                              int(candidate_limit), n_ids, _ptr(ids) if n_ids else None, _ptr(off),
+                                              _ptr(rows), _ptr(scores), _ptr(counts)))
+        return rows, scores, counts
+
+    def search_shard_scoped(self, qvecs, queries_terms, now_ticks: int, kprime: int, candidate_limit: int, scope_ids,
+                            scope_before=None, topk: int = 0, out=None):
+        """orr_search_shard_scoped: this shard's [B, kprime+1] records of a scoped search (for merge_candidates).  scope_before
+        [B]: each query's scoped live rows on the shards in front (scope_count there), or None."""
+        B = len(queries_terms)
+        dim, q, _keep = self._query_args(qvecs, B)
+        pool, toff, qoff = pack_terms(queries_terms)
+        n_ids, ids, off = self._scope_args(scope_ids, B)
+        before = None if scope_before is None else np.ascontiguousarray(scope_before, dtype=np.int64).reshape(B)
+        if out is None:
+            out = np.zeros((B, kprime + 1), dtype=CAND_DTYPE)
+        N.check(N.hip.orr_search_shard_scoped(self._h, B, dim, _ptr(q), _ptr(pool), _ptr(toff), _ptr(qoff), now_ticks, int(kprime),
+                                              int(candidate_limit), max(0, int(topk)), n_ids, _ptr(ids) if n_ids else None, _ptr(off),
+                                              _ptr(before), _ptr(out)))
+        return out
+
+    def scope_count(self, scope_ids, n_queries: int = 1) -> np.ndarray:
+        """orr_index_scope_count: [n_queries] int64, the live rows each query's scope resolves to on this shard."""
+        n_ids, ids, off = self._scope_args(scope_ids, n_queries)
+        live = np.zeros(n_queries, dtype=np.int64)
+        N.check(N.hip.orr_index_scope_count(self._h, int(n_queries), n_ids, _ptr(ids) if n_ids else None, _ptr(off), _ptr(live)))
+        return live
+
     def view(self) -> "RecallIndex":
         """orr_index_view: a second search lane over this sealed shard (own streams and workspaces, shared
         corpus).  Searches on the index and on its views may run concurrently from different threads."""

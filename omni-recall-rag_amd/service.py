@@ -124,6 +124,22 @@ class RecallSearchService:
         finally:
             N.host.orrh_free(out)
 
+    def SearchInDocuments(self, query: str, topK: int, document_ids: Sequence[str], now_ticks: Optional[int] = None) -> dict:
+        """SearchAsync over the chunks of the given documents only (orrh_service_search_documents_json): the same response
+        body; unknown document ids are skipped, no documents give no citations."""
+        vec = np.ascontiguousarray(self.embedding_client.Embed(query), dtype=np.float32) \
+            if query is not None and query.strip() else np.zeros(0, np.float32)
+        out, ln = C.c_void_p(), C.c_int64()
+        now = now_ticks if now_ticks is not None else self.now_ticks
+        docs = [str(d).encode() for d in document_ids]
+        arr = (C.c_char_p * max(1, len(docs)))(*docs)
+        _check(N.host.orrh_service_search_documents_json(self._h, (query or "").encode(), vec.ctypes.data if vec.size else None,
+                                                         int(vec.size), topK, now, arr, len(docs), C.byref(out), C.byref(ln)))
+        try:
+            return json.loads(C.string_at(out, ln.value).decode("utf-8"))
+        finally:
+            N.host.orrh_free(out)
+
     def Stats(self) -> dict:
         n, full, delta = C.c_int32(0), C.c_int64(0), C.c_int64(0)
         N.host.orrh_service_stats(self._h, C.cast(C.byref(n), C.c_void_p), C.cast(C.byref(full), C.c_void_p),
