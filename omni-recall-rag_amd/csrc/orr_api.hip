@@ -2575,6 +2575,105 @@ struct PassIo {
     bool direct_host = false;           // d_cand is pinned host memory
 };
 
+// The front end of a pass, unscoped (run_shard_once) or scoped (run_scoped_pass): the term offsets, the plan, where the
+// records go, the query vectors where the kernels and the host finish read them.
+struct PassFront {
+    std::vector<uint32_t> qoff;         // query_term_off [B + 1], validated
+    uint32_t n_terms_total = 0;
+    size_t rec_bytes = 0;               // the records [B][kprime + 1]
+    bool q_download_pending = false;    // device-resident vectors are on their way to the host (ev_q)
+    PassIo io;
+};
+
+// Builds the front end: validates the term offsets, has the caller settle the plan (`plan(qoff, p)`, which reads them), places
+// the records and stages the query vectors.  What differs between the callers: whether small record sets may go straight into
+// pinned host memory (where the records carry their dots), whether BatchArgs::out_dev applies, whether the plan may leave the
+// queries' exact norms to the device.  *q_host (if asked for): the vectors in host memory, valid until the next call.
+template <class Plan>
+int open_pass(orr_index *idx, const BatchArgs &a, int32_t kprime, Plan &&plan, bool pinned_records, bool out_dev, bool dev_norms,
+              const float **q_host, PassPlan &p, PassFront &f)
+{
+    const int32_t B = a.B;
+    hipStream_t s = idx->stream;
+    if (q_host) *q_host = nullptr;
+    f.qoff.resize((size_t)B + 1);
+    memcpy(f.qoff.data(), a.query_term_off, sizeof(uint32_t) * ((size_t)B + 1));
+    for (int32_t b = 0; b < B; ++b) {
+        if (f.qoff[b + 1] < f.qoff[b]) return fail(ORR_EINVAL, "query_term_off is not monotone at query %d", b);
+        if (f.qoff[b + 1] - f.qoff[b] > 65535) return fail(ORR_EINVAL, "query %d has more than 65535 terms", b);
+    }
+    f.n_terms_total = f.qoff[B] - f.qoff[0];
+    if (f.n_terms_total > 0 && (!a.term_off || !a.terms_utf8)) return fail(ORR_EINVAL, "terms are referenced but term_off/terms_utf8 is NULL");
+
+    ORR_TRY(plan(f.qoff, p));
+    if (!dev_norms) p.dev_norms = false;
+    idx->h_survivors.clear();
+
+    // ---- record destination
+    PassIo &io = f.io;
+    f.rec_bytes = sizeof(orr_candidate) * (size_t)B * ((size_t)kprime + 1);
+    io.direct_host = pinned_records && !p.use_mfma && f.rec_bytes <= (256u << 10);
+    if (io.direct_host) {
+        ORR_TRY(idx->pin_cand.reserve(f.rec_bytes));
+        io.d_cand = idx->pin_cand.as<orr_candidate>();        // pinned host memory is device-writable
+    } else if (out_dev && a.out_dev) {
+        io.d_cand = a.out_dev;
+    } else {
+        ORR_TRY(idx->ws_cand.reserve(f.rec_bytes));
+        io.d_cand = idx->ws_cand.as<orr_candidate>();
+    }
+
+    // ---- query vectors: the kernels read them where they are (device) or from one upload; device-resident ones get their
+    // exact norms on the device (beside the first cosine kernel) or are downloaded for the host's pass
+    idx->h_norm_a.assign((size_t)B, 0.0);
+    if (!p.use_cos) return ORR_OK;
+    const size_t qbytes = sizeof(float) * (size_t)B * a.dim;
+    if (p.dev_norms) {
+        io.d_q = a.q;
+        ORR_TRY(idx->ws_norm_a.reserve(sizeof(double) * (size_t)B));
+        ORR_TRY(idx->pin_norm.reserve(sizeof(double) * (size_t)B));
+        HIP_TRY(orr::launch_dot_exact(io.d_q, B, a.dim, nullptr, 1, true, idx->ws_norm_a.as<double>(), B, idx->stream_aux));
+        HIP_TRY(hipEventRecord(idx->ev_q, idx->stream_aux));
+        return ORR_OK;
+    }
+    ORR_TRY(idx->pin_q.reserve(qbytes));
+    if (p.q_on_device) {
+        io.d_q = a.q;
+        HIP_TRY(hipMemcpyAsync(idx->pin_q.p, a.q, qbytes, hipMemcpyDeviceToHost, idx->stream_kw));
+        HIP_TRY(hipEventRecord(idx->ev_q, idx->stream_kw));
+        f.q_download_pending = true;
+    } else {
+        memcpy(idx->pin_q.p, a.q, qbytes);
+        ORR_TRY(idx->ws_q.reserve(qbytes));
+        HIP_TRY(hipMemcpyAsync(idx->ws_q.p, idx->pin_q.p, qbytes, hipMemcpyHostToDevice, s));
+        io.d_q = idx->ws_q.as<float>();
+    }
+    if (q_host) *q_host = idx->pin_q.as<float>();
+    return ORR_OK;
+}
+
+// Records of a (sub-)batch no row takes part in: empty slots and, per query, the trailer of a pass that cut nothing.
+std::vector<orr_candidate> empty_records(int32_t B, int32_t kprime)
+{
+    std::vector<orr_candidate> empty((size_t)B * ((size_t)kprime + 1));
+    for (auto &c : empty) { memset(&c, 0, sizeof(c)); c.row_id = -1; c.order_key = -1; }
+    for (int32_t b = 0; b < B; ++b) {
+        orr_candidate &t = empty[(size_t)b * ((size_t)kprime + 1) + (size_t)kprime];
+        t.approx_score = -std::numeric_limits<double>::infinity();
+        t.order_key = 0; t.flags = ORR_CAND_TRAILER;
+    }
+    return empty;
+}
+
+// Large record sets (and those of a batched pass, whose dots are filled in last) reach pinned host memory in one copy.
+int records_to_host(orr_index *idx, const PassFront &f, hipStream_t s)
+{
+    if (f.io.direct_host) return ORR_OK;
+    ORR_TRY(idx->pin_cand.reserve(f.rec_bytes));
+    HIP_TRY(hipMemcpyAsync(idx->pin_cand.p, f.io.d_cand, f.rec_bytes, hipMemcpyDeviceToHost, s));
+    return ORR_OK;
+}
+
 // The int8 image of the queries.  The stream's (gemm = false) has one error term and its launch clears the pass's counters;
 // the screening GEMM's has the second error term and is tiled like the rows.
 int launch_i8_query_image(orr_index *idx, const float *d_q, int32_t B, bool gemm, hipStream_t s)
@@ -2694,18 +2793,36 @@ int launch_consts(orr_index *idx, const BatchArgs &a, const PassPlan &p, int64_t
     return ORR_OK;
 }
 
-// The tail of the two-stage pass: exact re-score of every buffered survivor (fp32 master, reference arithmetic), the best k' of
-// them as records with their exact dots.  dim % 256 == 0: finish_survivors (four lanes per survivor, or a wave per survivor for
-// the smallest batches; the workgroup that draws a query's last ticket -- or a second launch -- merges its lists and writes the
-// records, straight into pinned host memory when the record set is small); else four launches.  The survivors' counts go back
-// with the records (idx->pin_cnt).
+// The kernel that re-scores buffered survivors in the reference arithmetic, and with it whether anybody reads their counts.
+enum class Rescore {
+    BufferExact,    // rescore_buffer_exact (a cosine part, dim % 64 == 0), inside finish_survivors where dim % 256 == 0; the
+                    // survivors' counts go back with the records (idx->pin_cnt)
+    ScopeGeneric,   // scope_rescore: any dimension, queries without a cosine part (a scoped pass); the host knows the counts
+};
+
+// Exact re-score of every buffered survivor into idx->ws_fdot, as its own launch.
+int rescore_survivors(orr_index *idx, const BatchArgs &a, const PassIo &io, const orr::FusedEpilogue &epi, uint32_t kCap, Rescore how,
+                      double bytes, hipStream_t s)
+{
+    Timed t(idx, how == Rescore::BufferExact ? "rescore_buffer_exact" : "scope_rescore", bytes);
+    HIP_TRY((how == Rescore::BufferExact ? orr::launch_rescore_buffer_exact : orr::launch_scope_rescore_generic)(
+        idx->d_emb, idx->dim, io.d_q, a.B, idx->d_norm_b, idx->d_created, io.kw, idx->ws_qc.as<orr::QueryConst>(), a.now_ticks, epi.cnt, kCap,
+        epi.buf, idx->ws_fdot.as<double>(), s));
+    return ORR_OK;
+}
+
+// The tail of the two-stage pass and of a scoped Selection pass: exact re-score of every buffered survivor (fp32 master,
+// reference arithmetic), the best k' of them as records with their exact dots.  BufferExact and dim % 256 == 0:
+// finish_survivors (four lanes per survivor, or a wave per survivor for the smallest batches; the workgroup that draws a
+// query's last ticket -- or a second launch -- merges its lists and writes the records, straight into pinned host memory when
+// the record set is small); else four launches, the first of them `how` (Timed bytes: rescore_bytes).
 int two_stage_tail(orr_index *idx, const BatchArgs &a, int32_t kprime, int64_t n, PassIo &io, const orr::FusedEpilogue &epi,
-                   uint32_t kCap, int32_t buf_lists, bool host_records, size_t rec_bytes, hipStream_t s)
+                   uint32_t kCap, int32_t buf_lists, bool host_records, size_t rec_bytes, Rescore how, double rescore_bytes, hipStream_t s)
 {
     const int32_t B = a.B;
     ORR_TRY(idx->ws_fdot.reserve(sizeof(double) * (size_t)B * kCap));
     ORR_TRY(idx->pin_cnt.reserve(sizeof(uint32_t) * (size_t)B));
-    if (B <= kFinishFusedMaxB && idx->dim % 256 == 0) {
+    if (how == Rescore::BufferExact && B <= kFinishFusedMaxB && idx->dim % 256 == 0) {
         // the tail in one launch; small record sets go straight into pinned host memory (they are final when written)
         if (host_records && !a.out_dev && rec_bytes <= (256u << 10)) {
             ORR_TRY(idx->pin_cand.reserve(rec_bytes));
@@ -2718,12 +2835,7 @@ int two_stage_tail(orr_index *idx, const BatchArgs &a, int32_t kprime, int64_t n
                                              kCap, epi.buf, idx->ws_fdot.as<double>(), idx->ws_sel.as<orr::SelEntry>(), kprime, n,
                                              idx->row_base, idx->ws_tsL.as<double>(), io.d_cand, idx->pin_cnt.as<uint32_t>(), s));
     } else {
-        {
-            Timed t(idx, "rescore_buffer_exact", 0.0);
-            HIP_TRY(orr::launch_rescore_buffer_exact(idx->d_emb, idx->dim, io.d_q, B, idx->d_norm_b, idx->d_created, io.kw,
-                                                     idx->ws_qc.as<orr::QueryConst>(), a.now_ticks, epi.cnt, kCap, epi.buf,
-                                                     idx->ws_fdot.as<double>(), s));
-        }
+        ORR_TRY(rescore_survivors(idx, a, io, epi, kCap, how, rescore_bytes, s));
         {
             Timed t(idx, "buffer_to_lists", 0.0);
             HIP_TRY(orr::launch_buffer_to_lists(epi.buf, epi.cnt, kCap, B, 0, buf_lists, idx->ws_sel.as<orr::SelEntry>(), s));
@@ -2740,7 +2852,8 @@ int two_stage_tail(orr_index *idx, const BatchArgs &a, int32_t kprime, int64_t n
                                                         io.d_cand, s));
         }
         // the survivors' counts go back with the records: per-query escalation and orr_index_search_stats
-        HIP_TRY(hipMemcpyAsync(idx->pin_cnt.p, epi.cnt, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost, s));
+        if (how == Rescore::BufferExact)
+            HIP_TRY(hipMemcpyAsync(idx->pin_cnt.p, epi.cnt, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost, s));
     }
     return ORR_OK;
 }
@@ -2871,7 +2984,7 @@ int screen_two_stage(orr_index *idx, const BatchArgs &a, const PassPlan &p, int3
         Timed t(idx, "gemm_dot_bf16x1_fused", 4.0 * (double)n * idx->dim + 2.0 * (double)B * idx->dim);
         HIP_TRY(orr::launch_gemm_dot_bf16x3(idx->ws_qsplit.p, B, idx->d_emb, 0, n, idx->dim, nullptr, 0, &epi, 1, s));
     }
-    return two_stage_tail(idx, a, kprime, n, io, epi, kCap, buf_lists, host_records, rec_bytes, s);
+    return two_stage_tail(idx, a, kprime, n, io, epi, kCap, buf_lists, host_records, rec_bytes, Rescore::BufferExact, 0.0, s);
 }
 
 // Stage 7 of the SplitFused and two-stage forms: prefix lists -> floor keys -> the screening launch with the scoring
@@ -3060,75 +3173,20 @@ int run_shard_once(orr_index *idx, const BatchArgs &a, int32_t kprime, bool host
     const int64_t n = participating_rows(idx, a.candidate_limit);
     const int32_t B = a.B;
     hipStream_t s = idx->stream;
-    if (q_host) *q_host = nullptr;
     if (recs_host) *recs_host = nullptr;
 
-    std::vector<uint32_t> qoff((size_t)B + 1);
-    memcpy(qoff.data(), a.query_term_off, sizeof(uint32_t) * ((size_t)B + 1));
-    for (int32_t b = 0; b < B; ++b) {
-        if (qoff[b + 1] < qoff[b]) return fail(ORR_EINVAL, "query_term_off is not monotone at query %d", b);
-        if (qoff[b + 1] - qoff[b] > 65535) return fail(ORR_EINVAL, "query %d has more than 65535 terms", b);
-    }
-    const uint32_t n_terms_total = qoff[B] - qoff[0];
-    if (n_terms_total > 0 && (!a.term_off || !a.terms_utf8)) return fail(ORR_EINVAL, "terms are referenced but term_off/terms_utf8 is NULL");
-
-    ORR_TRY(plan_pass(idx, a, kprime, n, qoff, p));
-    idx->h_survivors.clear();
-
-    // ---- 1. record destination
-    const size_t rec_bytes = sizeof(orr_candidate) * (size_t)B * ((size_t)kprime + 1);
-    PassIo io;
-    io.direct_host = host_records && !p.use_mfma && rec_bytes <= (256u << 10);
-    if (io.direct_host) {
-        ORR_TRY(idx->pin_cand.reserve(rec_bytes));
-        io.d_cand = idx->pin_cand.as<orr_candidate>();        // pinned host memory is device-writable
-    } else if (a.out_dev) {
-        io.d_cand = a.out_dev;
-    } else {
-        ORR_TRY(idx->ws_cand.reserve(rec_bytes));
-        io.d_cand = idx->ws_cand.as<orr_candidate>();
-    }
-
-    // ---- 2. query vectors: the kernels read them where they are (device) or from one upload; device-resident ones get their
-    // exact norms on the device (beside the first cosine kernel) or are downloaded for the host's pass
-    bool q_download_pending = false;
-    idx->h_norm_a.assign((size_t)B, 0.0);
-    if (p.use_cos) {
-        const size_t qbytes = sizeof(float) * (size_t)B * a.dim;
-        if (p.dev_norms) {
-            io.d_q = a.q;
-            ORR_TRY(idx->ws_norm_a.reserve(sizeof(double) * (size_t)B));
-            ORR_TRY(idx->pin_norm.reserve(sizeof(double) * (size_t)B));
-            HIP_TRY(orr::launch_dot_exact(io.d_q, B, a.dim, nullptr, 1, true, idx->ws_norm_a.as<double>(), B, idx->stream_aux));
-            HIP_TRY(hipEventRecord(idx->ev_q, idx->stream_aux));
-        } else if (p.q_on_device) {
-            ORR_TRY(idx->pin_q.reserve(qbytes));
-            io.d_q = a.q;
-            HIP_TRY(hipMemcpyAsync(idx->pin_q.p, a.q, qbytes, hipMemcpyDeviceToHost, idx->stream_kw));
-            HIP_TRY(hipEventRecord(idx->ev_q, idx->stream_kw));
-            q_download_pending = true;
-        } else {
-            ORR_TRY(idx->pin_q.reserve(qbytes));
-            memcpy(idx->pin_q.p, a.q, qbytes);
-            ORR_TRY(idx->ws_q.reserve(qbytes));
-            HIP_TRY(hipMemcpyAsync(idx->ws_q.p, idx->pin_q.p, qbytes, hipMemcpyHostToDevice, s));
-            io.d_q = idx->ws_q.as<float>();
-        }
-        if (q_host && !p.dev_norms) *q_host = idx->pin_q.as<float>();
-    }
+    // ---- 1, 2. term offsets, the plan, record destination, query vectors
+    PassFront f;
+    ORR_TRY(open_pass(idx, a, kprime, [&](const std::vector<uint32_t> &qoff, PassPlan &plan) { return plan_pass(idx, a, kprime, n, qoff, plan); },
+                      host_records, true, true, q_host, p, f));
+    PassIo &io = f.io;
 
     if (p.form == PassForm::Empty) {   // nothing on this shard takes part: empty records + trailers
-        std::vector<orr_candidate> empty((size_t)B * ((size_t)kprime + 1));
-        for (auto &c : empty) { memset(&c, 0, sizeof(c)); c.row_id = -1; c.order_key = -1; }
-        for (int32_t b = 0; b < B; ++b) {
-            orr_candidate &t = empty[(size_t)b * (kprime + 1) + kprime];
-            t.approx_score = -std::numeric_limits<double>::infinity();
-            t.order_key = 0; t.matches = 0; t.flags = ORR_CAND_TRAILER;
-        }
-        if (io.direct_host) memcpy(io.d_cand, empty.data(), rec_bytes);
-        else HIP_TRY(hipMemcpyAsync(io.d_cand, empty.data(), rec_bytes, hipMemcpyHostToDevice, s));
+        const std::vector<orr_candidate> empty = empty_records(B, kprime);
+        if (io.direct_host) memcpy(io.d_cand, empty.data(), f.rec_bytes);
+        else HIP_TRY(hipMemcpyAsync(io.d_cand, empty.data(), f.rec_bytes, hipMemcpyHostToDevice, s));
         HIP_TRY(hipStreamSynchronize(s));
-        if (q_download_pending || p.dev_norms) HIP_TRY(hipEventSynchronize(idx->ev_q));    // nothing reads the caller's vectors after the call
+        if (f.q_download_pending || p.dev_norms) HIP_TRY(hipEventSynchronize(idx->ev_q));    // nothing reads the caller's vectors after the call
         if (recs_host && io.direct_host) *recs_host = io.d_cand;
         return ORR_OK;
     }
@@ -3139,7 +3197,7 @@ int run_shard_once(orr_index *idx, const BatchArgs &a, int32_t kprime, bool host
 
     // ---- 4. K3 keyword side, on its own stream
     KwSide kws;
-    ORR_TRY(launch_keyword_side(idx, a, qoff, kws));
+    ORR_TRY(launch_keyword_side(idx, a, f.qoff, kws));
     io.kw = kws.view;
     g_ht.mark(1);
 
@@ -3148,41 +3206,55 @@ int run_shard_once(orr_index *idx, const BatchArgs &a, int32_t kprime, bool host
     g_ht.mark(0);
 
     // ---- 6. query constants and row constants, then the keyword side joins the main stream
-    ORR_TRY(launch_consts(idx, a, p, n, qoff, q_download_pending, io));
-    if (n_terms_total > 0) HIP_TRY(hipStreamWaitEvent(s, idx->ev_kw_done, 0));
+    ORR_TRY(launch_consts(idx, a, p, n, f.qoff, f.q_download_pending, io));
+    if (f.n_terms_total > 0) HIP_TRY(hipStreamWaitEvent(s, idx->ev_kw_done, 0));
     g_ht.mark(2);
 
     // ---- 7. K4/K5 fused score + selection for the form
-    ORR_TRY(launch_selection(idx, a, p, kprime, n, io, host_records, rec_bytes));
+    ORR_TRY(launch_selection(idx, a, p, kprime, n, io, host_records, f.rec_bytes));
 
     // ---- 8. records of deleted rows are dropped by the host finish; large record sets go into pinned memory in one copy
     if (!owner_of(idx)->dead.empty())
         HIP_TRY(orr::launch_mark_dead_records(io.d_cand, B, kprime, owner_of(idx)->d_dead.as<int64_t>(),
                                               (int32_t)owner_of(idx)->dead.size(), idx->row_base, s));
-    if (host_records && !io.direct_host) {
-        ORR_TRY(idx->pin_cand.reserve(rec_bytes));
-        HIP_TRY(hipMemcpyAsync(idx->pin_cand.p, io.d_cand, rec_bytes, hipMemcpyDeviceToHost, s));
-    }
+    if (host_records) ORR_TRY(records_to_host(idx, f, s));
     g_ht.mark(3);
     idx->sstats.pass_mode = p.pass_mode();
 
     // ---- 9. synchronise, clean up, statistics
-    const int r = finish_pass(idx, a, p, kws, n_terms_total);
+    const int r = finish_pass(idx, a, p, kws, f.n_terms_total);
     if (r != ORR_OK) return r;
     if (recs_host && io.direct_host) *recs_host = io.d_cand;
     else if (recs_host && host_records) *recs_host = idx->pin_cand.as<orr_candidate>();
     return ORR_OK;
 }
 
-int run_shard(orr_index *idx, const BatchArgs &a, int32_t kprime, bool host_records, const float **q_host,
-              const orr_candidate **recs_host, PassPlan &pass)
+// A pass until the keyword hit list held every hit.  sstats.passes counts the attempts that were thrown away; the one that
+// stood is the caller's to count.
+template <class Pass>
+int retry_pass(orr_index *idx, Pass &&once)
 {
-    for (int attempt = 0;; ++attempt) {   // (the plan is made again: sample_boost may have changed)
-        const int r = run_shard_once(idx, a, kprime, host_records, q_host, recs_host, pass);
+    for (int attempt = 0;; ++attempt) {
+        const int r = once();
         if (r != kRetryPass) return r;
         idx->sstats.passes += 1;
         if (attempt >= 3) return fail(ORR_EDEVICE, "the keyword hit list kept overflowing");
     }
+}
+
+int run_shard(orr_index *idx, const BatchArgs &a, int32_t kprime, bool host_records, const float **q_host,
+              const orr_candidate **recs_host, PassPlan &pass)
+{
+    // (the plan is made again: sample_boost may have changed)
+    return retry_pass(idx, [&] { return run_shard_once(idx, a, kprime, host_records, q_host, recs_host, pass); });
+}
+
+// The ranking order of the host finish.
+bool ranks_before(const Ranked &x, const Ranked &y)
+{
+    const int c = compare_double(x.score, y.score);
+    if (c != 0) return c > 0;                 // OrderByDescending(score)       :34
+    return x.order_key < y.order_key;         // ThenByDescending(created), stable == candidate order  :35
 }
 
 // Host finish for one query over records from any number of shards.
@@ -3224,11 +3296,7 @@ int32_t finish_query(const orr_candidate *const *shard_recs, int32_t n_shards, i
             if (!(tr.approx_score != tr.approx_score) && tr.approx_score > cutoff) cutoff = tr.approx_score;
         }
     }
-    std::sort(ranked.begin(), ranked.end(), [](const Ranked &x, const Ranked &y) {
-        const int c = compare_double(x.score, y.score);
-        if (c != 0) return c > 0;                 // OrderByDescending(score)       :34
-        return x.order_key < y.order_key;         // ThenByDescending(created), stable == candidate order  :35
-    });
+    std::sort(ranked.begin(), ranked.end(), ranks_before);
     const int32_t take = std::max<int32_t>(1, topk);                                 // :36
     const int32_t n_out = (int32_t)std::min<size_t>((size_t)take, ranked.size());
     for (int32_t i = 0; i < n_out; ++i) {
@@ -3305,6 +3373,27 @@ int merge_impl(int32_t n_shards, int32_t B, int32_t kprime, const orr_candidate 
     return ORR_OK;
 }
 
+// Host finish of one pass over the sub-batch `cur` = queries `ids` of the call: the results go to out_*[ids[i]] of the call's
+// numbering, cert[i] tells whether query i of the sub-batch was certified.
+int merge_into(int32_t n_shards, int32_t kprime, const orr_candidate *recs, const BatchArgs &cur, bool use_cos, const float *q_host,
+               const double *norms, const std::vector<int32_t> &ids, int64_t *out_rows, double *out_scores, int32_t *out_counts,
+               std::vector<uint8_t> &cert)
+{
+    const int32_t nb = (int32_t)ids.size(), take = std::max<int32_t>(1, cur.topk);
+    cert.assign((size_t)nb, 1);
+    std::vector<int64_t> rows((size_t)nb * take);
+    std::vector<double> scores((size_t)nb * take);
+    std::vector<int32_t> counts((size_t)nb);
+    ORR_TRY(merge_impl(n_shards, nb, kprime, recs, cur.dim, use_cos, q_host, norms, cur.query_term_off, cur.now_ticks, cur.topk, rows.data(),
+                       scores.data(), counts.data(), nullptr, cert.data()));
+    for (int32_t i = 0; i < nb; ++i) {
+        const size_t b = (size_t)ids[(size_t)i];
+        memcpy(out_rows + b * take, rows.data() + (size_t)i * take, sizeof(int64_t) * take);
+        memcpy(out_scores + b * take, scores.data() + (size_t)i * take, sizeof(double) * take);
+        if (out_counts) out_counts[b] = counts[(size_t)i];
+    }
+    return ORR_OK;
+}
 
 // ---- one batch through the passes, escalating ONLY the queries that could not be certified ----------------------------
 // A query whose top-k could not be certified (a tie at the cut, a survivors' buffer that overflowed, k' too small for a
@@ -3318,10 +3407,14 @@ struct SubBatch {                  // storage of a compacted sub-batch (the vect
     std::vector<uint32_t> term_off, qoff;
 };
 
+// The queries `ids` of `orig` as a batch of their own: `orig` itself where that is all of them in order.
 int build_subset(orr_index *idx, const BatchArgs &orig, const std::vector<int32_t> &ids, SubBatch &sb, BatchArgs &out)
 {
     out = orig;
     const int32_t nb = (int32_t)ids.size();
+    bool whole = nb == orig.B;
+    for (int32_t i = 0; i < nb && whole; ++i) whole = ids[(size_t)i] == i;
+    if (whole) return ORR_OK;
     out.B = nb;
     if (orig.dim > 0) {
         const size_t row = (size_t)orig.dim;
@@ -3400,14 +3493,12 @@ int escalate(const Backend &be, const BatchArgs &orig, int64_t kprime, int64_t *
 {
     struct Rung {                       // queries of `orig` (ascending) and the pass they go through next
         std::vector<int32_t> ids;
-        bool whole;                     // ids is the entire batch in order
         bool no_fuse, force_exact;
         int64_t kprime;
         int repeats;
     };
-    const int32_t take = std::max<int32_t>(1, orig.topk);
     const bool use_cos = orig.dim > 0 && orig.dim == be.dim;
-    std::deque<Rung> todo(1, Rung{std::vector<int32_t>((size_t)orig.B), true, orig.no_fuse, orig.force_exact, kprime, 0});
+    std::deque<Rung> todo(1, Rung{std::vector<int32_t>((size_t)orig.B), orig.no_fuse, orig.force_exact, kprime, 0});
     std::iota(todo.front().ids.begin(), todo.front().ids.end(), 0);
     while (!todo.empty()) {            // depth first: a slice's repeats run before the next slice
         const Rung r = std::move(todo.front());
@@ -3415,28 +3506,19 @@ int escalate(const Backend &be, const BatchArgs &orig, int64_t kprime, int64_t *
         const int32_t nb = (int32_t)r.ids.size();
         if (const int32_t per = escalation::slice_width(nb, be.slice_rows, r.no_fuse || r.force_exact)) {
             for (int32_t i0 = (nb - 1) / per * per; i0 >= 0; i0 -= per)
-                todo.push_front(Rung{std::vector<int32_t>(r.ids.begin() + i0, r.ids.begin() + std::min<int32_t>(nb, i0 + per)), false,
+                todo.push_front(Rung{std::vector<int32_t>(r.ids.begin() + i0, r.ids.begin() + std::min<int32_t>(nb, i0 + per)),
                                      r.no_fuse, r.force_exact, r.kprime, r.repeats});
             continue;
         }
         SubBatch sb;
-        BatchArgs cur = orig;
-        if (!r.whole) ORR_TRY(build_subset(be.subset_on, orig, r.ids, sb, cur));
+        BatchArgs cur;
+        ORR_TRY(build_subset(be.subset_on, orig, r.ids, sb, cur));
         cur.no_fuse = r.no_fuse; cur.force_exact = r.force_exact;
         PassResult pr;
         ORR_TRY(be.run_pass(cur, (int32_t)r.kprime, pr));
-        std::vector<uint8_t> cert((size_t)nb, 1);
-        std::vector<int64_t> rows((size_t)nb * take);
-        std::vector<double> scores((size_t)nb * take);
-        std::vector<int32_t> counts((size_t)nb);
-        ORR_TRY(merge_impl((int32_t)pr.shards.size(), nb, (int32_t)r.kprime, pr.recs, cur.dim, use_cos, pr.q_host, pr.norms,
-                           cur.query_term_off, cur.now_ticks, cur.topk, rows.data(), scores.data(), counts.data(), nullptr, cert.data()));
-        for (int32_t i = 0; i < nb; ++i) {
-            const size_t b = (size_t)r.ids[(size_t)i];
-            memcpy(out_rows + b * take, rows.data() + (size_t)i * take, sizeof(int64_t) * take);
-            memcpy(out_scores + b * take, scores.data() + (size_t)i * take, sizeof(double) * take);
-            if (out_counts) out_counts[b] = counts[(size_t)i];
-        }
+        std::vector<uint8_t> cert;
+        ORR_TRY(merge_into((int32_t)pr.shards.size(), (int32_t)r.kprime, pr.recs, cur, use_cos, pr.q_host, pr.norms, r.ids, out_rows, out_scores,
+                           out_counts, cert));
         g_ht.mark(5);
         const escalation::Decision d = escalation::decide(pr.shards, cert, r.no_fuse, r.force_exact, r.kprime, be.n_total, be.repeat_only_if_grown);
         {
@@ -3451,7 +3533,7 @@ int escalate(const Backend &be, const BatchArgs &orig, int64_t kprime, int64_t *
         }
         if (d.again.empty()) continue;
         if (r.repeats >= escalation::kMaxRepeats) return fail(ORR_EDEVICE, "%s: escalation did not terminate", be.name);
-        Rung next{{}, false, r.no_fuse, r.force_exact, d.kprime, r.repeats + 1};
+        Rung next{{}, r.no_fuse, r.force_exact, d.kprime, r.repeats + 1};
         for (int32_t i : d.again) next.ids.push_back(r.ids[(size_t)i]);
         if (d.step == escalation::Step::GrowBuffers) be.grow(pr.shards, d.new_cap);
         if (d.step == escalation::Step::Unfused) next.no_fuse = true;
@@ -3607,60 +3689,25 @@ int build_scope_slice(orr_index *idx, const ScopeArgs &sc, const std::vector<int
 
 // One scoped pass over the queries of `a` (a compacted sub-batch; query i of it is query qsel[i] of the slice): the slice's
 // bitmaps -> survivors' buffers -> the exact tail (Selection) or every pair a record (AllRecords, kprime >= every count).  The
-// records land in host memory (*recs_host).  kRetryPass as run_shard_once.  Caller holds the lane and its lock.
+// records land in host memory (*recs_host).  kRetryPass as run_shard_once, whose front end and stages it runs in the same
+// order without a screen.  Caller holds the lane and its lock.
 int run_scoped_pass(orr_index *idx, const BatchArgs &a, const std::vector<uint32_t> &qsel, const ScopeSlice &sl, scope::Form form,
                     int32_t kprime, const float **q_host, const orr_candidate **recs_host)
 {
     ORR_TRY(bind_device(idx));
     const int32_t B = a.B, D = idx->dim;
     hipStream_t s = idx->stream;
-    *q_host = nullptr; *recs_host = nullptr;
-    std::vector<uint32_t> qoff((size_t)B + 1);
-    memcpy(qoff.data(), a.query_term_off, sizeof(uint32_t) * ((size_t)B + 1));
-    for (int32_t b = 0; b < B; ++b) {
-        if (qoff[b + 1] < qoff[b]) return fail(ORR_EINVAL, "query_term_off is not monotone at query %d", b);
-        if (qoff[b + 1] - qoff[b] > 65535) return fail(ORR_EINVAL, "query %d has more than 65535 terms", b);
-    }
-    const uint32_t n_terms_total = qoff[B] - qoff[0];
-    if (n_terms_total > 0 && (!a.term_off || !a.terms_utf8)) return fail(ORR_EINVAL, "terms are referenced but term_off/terms_utf8 is NULL");
-
-    PassPlan p;                        // what launch_consts and finish_pass read of a plan: no screen, no batched score
-    p.form = PassForm::Exact;
-    p.use_cos = a.dim > 0 && a.dim == D;
-    p.q_on_device = p.use_cos && is_device_pointer(a.q);
-    idx->h_survivors.clear();
-
-    // ---- records: small sets straight into pinned host memory, large ones through one copy
-    const size_t rec_bytes = sizeof(orr_candidate) * (size_t)B * ((size_t)kprime + 1);
-    PassIo io;
-    io.direct_host = rec_bytes <= (256u << 10);
-    ORR_TRY(idx->pin_cand.reserve(rec_bytes));
-    if (io.direct_host) {
-        io.d_cand = idx->pin_cand.as<orr_candidate>();
-    } else {
-        ORR_TRY(idx->ws_cand.reserve(rec_bytes));
-        io.d_cand = idx->ws_cand.as<orr_candidate>();
-    }
-
-    // ---- query vectors, as run_shard_once (exact norms on the host)
-    bool q_download_pending = false;
-    idx->h_norm_a.assign((size_t)B, 0.0);
-    if (p.use_cos) {
-        const size_t qbytes = sizeof(float) * (size_t)B * a.dim;
-        ORR_TRY(idx->pin_q.reserve(qbytes));
-        if (p.q_on_device) {
-            io.d_q = a.q;
-            HIP_TRY(hipMemcpyAsync(idx->pin_q.p, a.q, qbytes, hipMemcpyDeviceToHost, idx->stream_kw));
-            HIP_TRY(hipEventRecord(idx->ev_q, idx->stream_kw));
-            q_download_pending = true;
-        } else {
-            memcpy(idx->pin_q.p, a.q, qbytes);
-            ORR_TRY(idx->ws_q.reserve(qbytes));
-            HIP_TRY(hipMemcpyAsync(idx->ws_q.p, idx->pin_q.p, qbytes, hipMemcpyHostToDevice, s));
-            io.d_q = idx->ws_q.as<float>();
-        }
-        *q_host = idx->pin_q.as<float>();
-    }
+    *recs_host = nullptr;
+    PassPlan p;
+    PassFront f;
+    auto plan = [&](const std::vector<uint32_t> &, PassPlan &pl) {   // what launch_consts and finish_pass read of a plan: no screen, no batched score
+        pl.form = PassForm::Exact;
+        pl.use_cos = a.dim > 0 && a.dim == D;
+        pl.q_on_device = pl.use_cos && is_device_pointer(a.q);
+        return ORR_OK;
+    };
+    ORR_TRY(open_pass(idx, a, kprime, plan, true, false, false, q_host, p, f));
+    PassIo &io = f.io;
 
     // ---- the survivors' buffers, filled from the bitmaps: [counts | unused | tickets] as the tail expects them, no floor
     uint32_t worst = 0;
@@ -3681,8 +3728,6 @@ int run_scoped_pass(orr_index *idx, const BatchArgs &a, const std::vector<uint32
     ORR_TRY(idx->ws_scope_sel.reserve(sizeof(uint32_t) * (size_t)B));
     ORR_TRY(idx->ws_tsL.reserve(sizeof(double) * (size_t)B));
     ORR_TRY(idx->ws_fbuf.reserve(sizeof(orr::SelEntry) * (size_t)B * cap));
-    ORR_TRY(idx->ws_fdot.reserve(sizeof(double) * (size_t)B * cap));
-    ORR_TRY(idx->pin_cnt.reserve(sizeof(uint32_t) * (size_t)B));
     HIP_TRY(hipMemcpyAsync(idx->ws_fcnt.p, h_cnt, o_sel, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(idx->ws_scope_sel.p, h_sel, sizeof(uint32_t) * (size_t)B, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(idx->ws_tsL.p, h_L, sizeof(double) * (size_t)B, hipMemcpyHostToDevice, s));
@@ -3696,99 +3741,86 @@ int run_scoped_pass(orr_index *idx, const BatchArgs &a, const std::vector<uint32
 
     // ---- keyword side (its own stream), query constants, then the two join
     KwSide kws;
-    ORR_TRY(launch_keyword_side(idx, a, qoff, kws));
+    ORR_TRY(launch_keyword_side(idx, a, f.qoff, kws));
     io.kw = kws.view;
-    ORR_TRY(launch_consts(idx, a, p, 0, qoff, q_download_pending, io));
-    if (n_terms_total > 0) HIP_TRY(hipStreamWaitEvent(s, idx->ev_kw_done, 0));
+    ORR_TRY(launch_consts(idx, a, p, 0, f.qoff, f.q_download_pending, io));
+    if (f.n_terms_total > 0) HIP_TRY(hipStreamWaitEvent(s, idx->ev_kw_done, 0));
 
     // ---- the re-score in the reference arithmetic and the records
-    const bool tail_kernels = p.use_cos && D % 64 == 0;        // rescore_buffer_exact / finish_survivors apply
+    const Rescore how = p.use_cos && D % 64 == 0 ? Rescore::BufferExact : Rescore::ScopeGeneric;
     const double pair_bytes = (double)B * (double)worst * 4.0 * (p.use_cos ? D : 0);
-    auto rescore = [&]() -> int {
-        if (tail_kernels) {
-            Timed t(idx, "rescore_buffer_exact", pair_bytes);
-            HIP_TRY(orr::launch_rescore_buffer_exact(idx->d_emb, D, io.d_q, B, idx->d_norm_b, idx->d_created, io.kw, idx->ws_qc.as<orr::QueryConst>(),
-                                                     a.now_ticks, epi.cnt, cap, epi.buf, idx->ws_fdot.as<double>(), s));
-        } else {
-            Timed t(idx, "scope_rescore", pair_bytes);
-            HIP_TRY(orr::launch_scope_rescore_generic(idx->d_emb, D, io.d_q, B, idx->d_norm_b, idx->d_created, io.kw, idx->ws_qc.as<orr::QueryConst>(),
-                                                      a.now_ticks, epi.cnt, cap, epi.buf, idx->ws_fdot.as<double>(), s));
-        }
-        return ORR_OK;
-    };
     if (form == scope::Form::AllRecords) {
-        ORR_TRY(rescore());
-        Timed t(idx, "scope_records", (double)rec_bytes);
+        ORR_TRY(idx->ws_fdot.reserve(sizeof(double) * (size_t)B * cap));
+        ORR_TRY(rescore_survivors(idx, a, io, epi, cap, how, pair_bytes, s));
+        Timed t(idx, "scope_records", (double)f.rec_bytes);
         HIP_TRY(orr::launch_scope_records(epi.buf, idx->ws_fdot.as<double>(), epi.cnt, cap, B, kprime, idx->row_base, idx->d_norm_b, idx->d_created,
                                           idx->d_row_ids, io.kw, io.d_cand, s));
     } else {
         const int32_t group = orr::finish_survivors_group(B, D);
         const int32_t lists_room = std::max<int32_t>(buf_lists, group ? (int32_t)(cap / (uint32_t)group) : 0);
         ORR_TRY(idx->ws_sel.reserve(sizeof(orr::SelEntry) * (size_t)B * (size_t)lists_room * orr::kSelWidth));
-        if (tail_kernels) {
-            ORR_TRY(two_stage_tail(idx, a, kprime, idx->n_rows, io, epi, cap, buf_lists, io.direct_host, rec_bytes, s));
-        } else {
-            ORR_TRY(rescore());
-            {
-                Timed t(idx, "buffer_to_lists", 0.0);
-                HIP_TRY(orr::launch_buffer_to_lists(epi.buf, epi.cnt, cap, B, 0, buf_lists, idx->ws_sel.as<orr::SelEntry>(), s));
-            }
-            {
-                Timed t(idx, "select_final", (double)B * (double)buf_lists * orr::kSelWidth * sizeof(orr::SelEntry));
-                HIP_TRY(orr::launch_select_final(idx->ws_sel.as<orr::SelEntry>(), buf_lists, B, kprime, idx->n_rows, idx->row_base, nullptr, nullptr, 0,
-                                                 idx->d_norm_b, idx->d_created, idx->d_row_ids, io.kw, 0, 0.0, nullptr, epi.cnt, cap,
-                                                 idx->ws_tsL.as<double>(), io.d_cand, s));
-            }
-            Timed t(idx, "records_dot_from_buffer", 0.0);
-            HIP_TRY(orr::launch_records_dot_from_buffer(epi.buf, idx->ws_fdot.as<double>(), epi.cnt, cap, B, kprime, idx->row_base, io.d_cand, s));
-        }
+        // (the four-launch tail behind rescore_buffer_exact reports no bytes, as behind a screen)
+        ORR_TRY(two_stage_tail(idx, a, kprime, idx->n_rows, io, epi, cap, buf_lists, true, f.rec_bytes, how,
+                               how == Rescore::BufferExact ? 0.0 : pair_bytes, s));
         HIP_TRY(orr::launch_scope_trailers(io.d_cand, B, kprime, epi.cnt, s));
     }
-    if (!io.direct_host) HIP_TRY(hipMemcpyAsync(idx->pin_cand.p, io.d_cand, rec_bytes, hipMemcpyDeviceToHost, s));
+    ORR_TRY(records_to_host(idx, f, s));
     idx->sstats.pass_mode = 4;
-    const int r = finish_pass(idx, a, p, kws, n_terms_total);
+    const int r = finish_pass(idx, a, p, kws, f.n_terms_total);
     if (r != ORR_OK) return r;
     *recs_host = idx->pin_cand.as<orr_candidate>();
     return ORR_OK;
 }
 
-int run_scoped(orr_index *idx, const BatchArgs &a, const std::vector<uint32_t> &qsel, const ScopeSlice &sl, scope::Form form, int32_t kprime,
-               const float **q_host, const orr_candidate **recs_host)
-{
-    for (int attempt = 0;; ++attempt) {
-        const int r = run_scoped_pass(idx, a, qsel, sl, form, kprime, q_host, recs_host);
-        idx->sstats.passes += 1;
-        if (r != kRetryPass) return r;
-        if (attempt >= 3) return fail(ORR_EDEVICE, "the keyword hit list kept overflowing");
-    }
-}
+// The slices of a scoped call: queries [b0, b0 + nq) whose bitmaps are built together.  A query whose scope brings more rows
+// than a pass takes (scope::kMaxScopeRows) is refused before any pass runs.
+int32_t scope_slice_width(const orr_index *idx, int32_t B) { return scope::bitmap_slice(B, idx->n_rows, escalation::kPassWorkspaceBytes / 4); }
 
-// the queries `ids` (of the call's numbering) as a batch: the call's own arguments when that is all of them in order
-int scoped_sub_batch(orr_index *idx, const BatchArgs &orig, const std::vector<int32_t> &ids, SubBatch &sb, BatchArgs &cur)
+int open_scope_slice(orr_index *idx, const ScopeArgs &sc, const std::vector<int64_t> &limit, int32_t b0, int32_t per, const char *fn, ScopeSlice &sl)
 {
-    bool whole = (int32_t)ids.size() == orig.B;
-    for (size_t i = 0; i < ids.size() && whole; ++i) whole = ids[i] == (int32_t)i;
-    if (whole) { cur = orig; return ORR_OK; }
-    return build_subset(idx, orig, ids, sb, cur);
-}
-
-constexpr size_t kScopeAllRecordsBytes = escalation::kPassWorkspaceBytes / 4;      // (its records also cross to the host in one piece)
-
-// bytes per pair of a Selection pass on this lane: the smallest group the tail's one-launch form may sort (a sub-batch of one
-// query), where that form runs at all
-size_t scoped_selection_pair_bytes(const orr_index *idx, const BatchArgs &a)
-{
-    const bool fused_tail = a.dim > 0 && a.dim == idx->dim && idx->dim % 256 == 0;
-    return scope::pair_bytes_selection(fused_tail ? orr::finish_survivors_group(1, idx->dim) : 0);
-}
-
-// a query whose scope brings more rows than a pass takes (scope::kMaxScopeRows) is refused before any pass runs
-int check_scope_sizes(const ScopeSlice &sl, const char *fn)
-{
+    ORR_TRY(build_scope_slice(idx, sc, limit, b0, std::min<int32_t>(per, (int32_t)limit.size() - b0), sl));
     for (int32_t i = 0; i < sl.nq; ++i)
         if (sl.took[i] > scope::kMaxScopeRows)
             return fail(ORR_EINVAL, "%s: the scope of query %d resolves to %u rows; at most %u scoped rows per query take part in one search "
                         "(lower candidate_limit, or search unscoped)", fn, sl.b0 + i, sl.took[i], scope::kMaxScopeRows);
+    return ORR_OK;
+}
+
+// One part of a slice after its scoped pass: what the host finish needs of it.
+struct ScopedPart {
+    std::vector<uint32_t> qsel;         // its queries in the slice's numbering
+    std::vector<int32_t> ids;           // ... in the call's
+    int32_t kprime = 0;                 // records per query of the pass
+    SubBatch sb;
+    BatchArgs cur;                      // the part as a batch
+    const float *q_host = nullptr;
+    const orr_candidate *recs = nullptr;   // [ids.size()][kprime + 1], host memory, valid until the lane's next pass
+};
+
+// The queries `q` of a slice through one scoped pass of the form, in parts whose pairs stay within the workspace; done(part)
+// after each.  Selection: kprime records per query.  AllRecords: as many as the part's largest scope holds, at least kprime.
+template <class Done>
+int for_each_scoped_part(orr_index *idx, const BatchArgs &orig, const ScopeSlice &sl, const std::vector<uint32_t> &q, scope::Form form,
+                         int32_t kprime, Done &&done)
+{
+    const bool all = form == scope::Form::AllRecords;
+    std::vector<uint32_t> counts(q.size());
+    for (size_t i = 0; i < q.size(); ++i) counts[i] = sl.took[q[i]];
+    // bytes per pair of a Selection pass on this lane: the smallest group the tail's one-launch form may sort (a sub-batch of one
+    // query), where that form runs at all; the records of AllRecords also cross to the host in one piece
+    const bool fused_tail = orig.dim > 0 && orig.dim == idx->dim && idx->dim % 256 == 0;
+    const size_t pair_bytes = all ? scope::kPairBytesAllRecords : scope::pair_bytes_selection(fused_tail ? orr::finish_survivors_group(1, idx->dim) : 0);
+    for (const auto &part : scope::slice_by_pairs(counts, pair_bytes, escalation::kPassWorkspaceBytes / (all ? 4 : 1))) {
+        ScopedPart pt;
+        pt.qsel.assign(q.begin() + part.first, q.begin() + part.second);
+        uint32_t worst = (uint32_t)kprime;
+        for (uint32_t i : pt.qsel) { pt.ids.push_back(sl.b0 + (int32_t)i); worst = std::max(worst, sl.took[i]); }
+        pt.kprime = all ? (int32_t)worst : kprime;
+        ORR_TRY(build_subset(idx, orig, pt.ids, pt.sb, pt.cur));
+        ORR_TRY(retry_pass(idx, [&] { return run_scoped_pass(idx, pt.cur, pt.qsel, sl, form, pt.kprime, &pt.q_host, &pt.recs); }));
+        idx->sstats.passes += 1;
+        ORR_TRY(done(pt));
+    }
     return ORR_OK;
 }
 
@@ -3803,11 +3835,10 @@ int scoped_batch(orr_index *idx, const BatchArgs &orig, const ScopeArgs &sc, int
     ORR_TRY(bind_device(idx));
     ORR_TRY(ensure_scope_table(idx));
     const std::vector<int64_t> limit((size_t)B, std::max<int64_t>(1, orig.candidate_limit));     // Take(Math.Max(1, maxCount)), over the scoped rows
-    const int32_t per = scope::bitmap_slice(B, idx->n_rows, escalation::kPassWorkspaceBytes / 4);
+    const int32_t per = scope_slice_width(idx, B);
     for (int32_t b0 = 0; b0 < B; b0 += per) {
         ScopeSlice sl;
-        ORR_TRY(build_scope_slice(idx, sc, limit, b0, std::min<int32_t>(per, B - b0), sl));
-        ORR_TRY(check_scope_sizes(sl, "orr_search_batch_scoped"));
+        ORR_TRY(open_scope_slice(idx, sc, limit, b0, per, "orr_search_batch_scoped", sl));
         struct Todo { std::vector<uint32_t> q; scope::Rung rung; int repeats; };     // queries of the slice and the pass they take next
         Todo first{{}, {}, 0};
         uint32_t max_scope = 0;
@@ -3820,39 +3851,16 @@ int scoped_batch(orr_index *idx, const BatchArgs &orig, const ScopeArgs &sc, int
             const Todo r = std::move(todo.front());
             todo.pop_front();
             const bool all = r.rung.form == scope::Form::AllRecords;
-            std::vector<uint32_t> counts(r.q.size());
-            for (size_t i = 0; i < r.q.size(); ++i) counts[i] = sl.took[r.q[i]];
             Todo next{{}, {}, r.repeats + 1};
             uint32_t next_scope = 0;
-            for (const auto &part : scope::slice_by_pairs(counts, all ? scope::kPairBytesAllRecords : scoped_selection_pair_bytes(idx, orig),
-                                                          all ? kScopeAllRecordsBytes : escalation::kPassWorkspaceBytes)) {
-                const std::vector<uint32_t> qsel(r.q.begin() + part.first, r.q.begin() + part.second);
-                const int32_t nb = (int32_t)qsel.size();
-                std::vector<int32_t> ids((size_t)nb);
-                uint32_t worst = 1;
-                for (int32_t i = 0; i < nb; ++i) { ids[(size_t)i] = b0 + (int32_t)qsel[(size_t)i]; worst = std::max(worst, sl.took[qsel[(size_t)i]]); }
-                const int32_t kprime = all ? (int32_t)worst : (int32_t)r.rung.kprime;
-                SubBatch sb;
-                BatchArgs cur;
-                ORR_TRY(scoped_sub_batch(idx, orig, ids, sb, cur));
-                const float *q_host = nullptr;
-                const orr_candidate *recs = nullptr;
-                ORR_TRY(run_scoped(idx, cur, qsel, sl, r.rung.form, kprime, &q_host, &recs));
-                std::vector<uint8_t> cert((size_t)nb, 1);
-                std::vector<int64_t> rows((size_t)nb * take);
-                std::vector<double> scores((size_t)nb * take);
-                std::vector<int32_t> cnts((size_t)nb);
-                ORR_TRY(merge_impl(1, nb, kprime, recs, cur.dim, use_cos, q_host, idx->h_norm_a.data(), cur.query_term_off, cur.now_ticks, cur.topk,
-                                   rows.data(), scores.data(), cnts.data(), nullptr, cert.data()));
-                for (int32_t i = 0; i < nb; ++i) {
-                    const size_t b = (size_t)ids[(size_t)i];
-                    memcpy(out_rows + b * take, rows.data() + (size_t)i * take, sizeof(int64_t) * take);
-                    memcpy(out_scores + b * take, scores.data() + (size_t)i * take, sizeof(double) * take);
-                    if (out_counts) out_counts[b] = cnts[(size_t)i];
-                    if (!cert[(size_t)i]) { next.q.push_back(qsel[(size_t)i]); next_scope = std::max(next_scope, sl.took[qsel[(size_t)i]]); }
-                }
-                if (r.repeats > 0) idx->sstats.requeried += nb;
-            }
+            ORR_TRY(for_each_scoped_part(idx, orig, sl, r.q, r.rung.form, all ? 1 : (int32_t)r.rung.kprime, [&](const ScopedPart &pt) -> int {
+                std::vector<uint8_t> cert;
+                ORR_TRY(merge_into(1, pt.kprime, pt.recs, pt.cur, use_cos, pt.q_host, idx->h_norm_a.data(), pt.ids, out_rows, out_scores, out_counts, cert));
+                for (size_t i = 0; i < cert.size(); ++i)
+                    if (!cert[i]) { next.q.push_back(pt.qsel[i]); next_scope = std::max(next_scope, sl.took[pt.qsel[i]]); }
+                if (r.repeats > 0) idx->sstats.requeried += (int64_t)pt.ids.size();
+                return ORR_OK;
+            }));
             if (next.q.empty()) continue;
             next.rung = scope::next_rung(r.rung, next_scope, orr::kSelWidth);
             if (next.rung.form == scope::Form::Done || next.repeats > scope::kMaxRungs)
@@ -3881,10 +3889,7 @@ void reduce_all_records(const orr_candidate *recs, int32_t nb, int32_t K, int32_
             r.row_id = in[i].row_id;
             ranked.push_back({r, i});
         }
-        std::sort(ranked.begin(), ranked.end(), [](const std::pair<Ranked, int32_t> &x, const std::pair<Ranked, int32_t> &y) {
-            const int c = compare_double(x.first.score, y.first.score);
-            return c != 0 ? c > 0 : x.first.order_key < y.first.order_key;
-        });
+        std::sort(ranked.begin(), ranked.end(), [](const std::pair<Ranked, int32_t> &x, const std::pair<Ranked, int32_t> &y) { return ranks_before(x.first, y.first); });
         const int32_t kept = std::min<int32_t>(n, kprime);
         for (int32_t i = 0; i < kprime; ++i) {
             if (i < kept) {
@@ -3913,48 +3918,27 @@ int scoped_shard(orr_index *idx, const BatchArgs &orig, const ScopeArgs &sc, int
         limit[(size_t)b] = std::max<int64_t>(0, std::max<int64_t>(1, orig.candidate_limit) - (sc.before ? std::max<int64_t>(0, sc.before[b]) : 0));
     ORR_TRY(bind_device(idx));
     if (idx->n_rows <= 0 || sc.n_ids == 0) {           // nothing on this shard takes part: empty records + trailers
-        std::vector<orr_candidate> empty((size_t)B * rec_q);
-        for (auto &c : empty) { memset(&c, 0, sizeof(c)); c.row_id = -1; c.order_key = -1; }
-        for (int32_t b = 0; b < B; ++b) {
-            orr_candidate &t = empty[(size_t)b * rec_q + (size_t)kprime];
-            t.approx_score = -std::numeric_limits<double>::infinity();
-            t.order_key = 0; t.flags = ORR_CAND_TRAILER;
-        }
-        HIP_TRY(hipMemcpy(out, empty.data(), sizeof(orr_candidate) * empty.size(), hipMemcpyDefault));
+        HIP_TRY(hipMemcpy(out, empty_records(B, kprime).data(), sizeof(orr_candidate) * (size_t)B * rec_q, hipMemcpyDefault));
         return ORR_OK;
     }
     ORR_TRY(ensure_scope_table(idx));
-    const bool all = kprime > orr::kSelWidth;
-    const int32_t per = scope::bitmap_slice(B, idx->n_rows, escalation::kPassWorkspaceBytes / 4);
+    const bool all = kprime > orr::kSelWidth;          // (AllRecords: at least k' records per query, so that the reduction has its slots)
+    const int32_t per = scope_slice_width(idx, B);
     std::vector<orr_candidate> reduced;
     for (int32_t b0 = 0; b0 < B; b0 += per) {
         ScopeSlice sl;
-        ORR_TRY(build_scope_slice(idx, sc, limit, b0, std::min<int32_t>(per, B - b0), sl));
-        ORR_TRY(check_scope_sizes(sl, "orr_search_shard_scoped"));
-        const std::vector<uint32_t> counts(sl.took, sl.took + sl.nq);
-        for (const auto &part : scope::slice_by_pairs(counts, all ? scope::kPairBytesAllRecords : scoped_selection_pair_bytes(idx, orig),
-                                                      all ? kScopeAllRecordsBytes : escalation::kPassWorkspaceBytes)) {
-            const int32_t nb = part.second - part.first;
-            std::vector<uint32_t> qsel((size_t)nb);
-            std::vector<int32_t> ids((size_t)nb);
-            uint32_t worst = (uint32_t)kprime;         // (AllRecords: at least k' records per query, so that the reduction has its slots)
-            for (int32_t i = 0; i < nb; ++i) {
-                qsel[(size_t)i] = (uint32_t)(part.first + i); ids[(size_t)i] = b0 + part.first + i;
-                worst = std::max(worst, sl.took[part.first + i]);
-            }
-            SubBatch sb;
-            BatchArgs cur;
-            ORR_TRY(scoped_sub_batch(idx, orig, ids, sb, cur));
-            const float *q_host = nullptr;
-            const orr_candidate *recs = nullptr;
-            ORR_TRY(run_scoped(idx, cur, qsel, sl, all ? scope::Form::AllRecords : scope::Form::Selection, all ? (int32_t)worst : kprime, &q_host, &recs));
+        ORR_TRY(open_scope_slice(idx, sc, limit, b0, per, "orr_search_shard_scoped", sl));
+        std::vector<uint32_t> q((size_t)sl.nq);
+        std::iota(q.begin(), q.end(), 0u);
+        ORR_TRY(for_each_scoped_part(idx, orig, sl, q, all ? scope::Form::AllRecords : scope::Form::Selection, kprime, [&](const ScopedPart &pt) -> int {
+            const size_t nb = pt.ids.size();
             if (all) {
-                reduced.resize((size_t)nb * rec_q);
-                reduce_all_records(recs, nb, (int32_t)worst, kprime, use_cos, idx->h_norm_a.data(), cur.query_term_off, cur.now_ticks, reduced.data());
-                recs = reduced.data();
+                reduced.resize(nb * rec_q);
+                reduce_all_records(pt.recs, (int32_t)nb, pt.kprime, kprime, use_cos, idx->h_norm_a.data(), pt.cur.query_term_off, pt.cur.now_ticks, reduced.data());
             }
-            HIP_TRY(hipMemcpy(out + (size_t)ids[0] * rec_q, recs, sizeof(orr_candidate) * (size_t)nb * rec_q, hipMemcpyDefault));
-        }
+            HIP_TRY(hipMemcpy(out + (size_t)pt.ids[0] * rec_q, all ? reduced.data() : pt.recs, sizeof(orr_candidate) * nb * rec_q, hipMemcpyDefault));
+            return ORR_OK;
+        }));
     }
     return ORR_OK;
 }
@@ -4179,7 +4163,7 @@ int orr_index_scope_count(orr_index *idx, int32_t B, int64_t n_scope_ids, const 
     ORR_TRY(bind_device(idx));
     ORR_TRY(ensure_scope_table(idx));
     const std::vector<int64_t> limit((size_t)B, std::numeric_limits<int64_t>::max());
-    const int32_t per = scope::bitmap_slice(B, idx->n_rows, escalation::kPassWorkspaceBytes / 4);
+    const int32_t per = scope_slice_width(idx, B);
     for (int32_t b0 = 0; b0 < B; b0 += per) {
         ScopeSlice sl;
         ORR_TRY(build_scope_slice(idx, sc, limit, b0, std::min<int32_t>(per, B - b0), sl));

@@ -469,3 +469,49 @@ def test_three_shards_scope_count_shard_records_and_the_unchanged_merge():
             assert _same(scores[b, :counts[b]], want_scores), (b, topk, limit)
     for p in parts:
         p.close()
+
+
+_TIE_CORPORA = {}
+
+
+def _tie_corpus(dim):
+    """600 rows of which 200 (positions 150 .. 349) are one row repeated: embedding, created and content.  Returns the corpus
+    with its model, the two scopes of the ladder test and their oracles, computed once per dimension."""
+    if dim not in _TIE_CORPORA:
+        rng = np.random.default_rng(80 + dim)
+        n = 600
+        c = random_corpus(rng, n, dim)
+        same = np.arange(150, 350)
+        vec = rng.standard_normal(dim).astype(np.float32)
+        for r in same:
+            c["emb"][r] = vec.copy()
+            c["created"][r] = NOW - 30 * DAY
+            c["contents"][r] = "alpha kubernetes helm chart"
+        # 100 ordinary rows with pairwise distinct `created` (and none of the 200): no two of them tie without a vector either
+        ordinary = np.setdiff1d(np.arange(n), same)
+        ordinary = ordinary[c["created"][ordinary] != NOW - 30 * DAY]
+        _, first = np.unique(c["created"][ordinary], return_index=True)
+        plain = np.sort(ordinary[first])[:100].astype(np.int64)
+        assert len(plain) == 100
+        model = Model(c["emb"], c["created"], c["contents"])
+        scopes = [same.astype(np.int64), plain]
+        _TIE_CORPORA[dim] = (c, model, scopes, [model.sub(s) for s in scopes], rng.standard_normal((2, dim)).astype(np.float32))
+    return _TIE_CORPORA[dim]
+
+
+@pytest.mark.parametrize("with_vectors", [True, False])
+@pytest.mark.parametrize("dim", [3, 64, 256])                                # generic re-score, four-launch tail, one-launch tail
+def test_a_scope_of_identical_rows_climbs_the_ladder_to_all_records(dim, with_vectors):
+    c, model, scopes, subs, q = _tie_corpus(dim)
+    idx = build_index(c)
+    idx.reset_search_stats()
+    _check_batch(idx, model, subs, list(q) if with_vectors else None, ["the kubernetes helm", "alpha"], 10, len(c["created"]), scopes,
+                 what="ties")                                                # (the ties in candidate order: the oracle's order)
+    st = idx.search_stats()
+    # Two queries of at most 200 scoped rows are one part of one slice.  Both start at k' = 32 (Selection).  Query 1's 100 rows
+    # score differently, so it is certified at once.  Query 0's 200 rows score alike: its 10th score equals the cut-off, it is
+    # not certified, and its next rung 4 x 32 = 128 > 64 is AllRecords, which certifies by construction: two passes, the second
+    # with one query; no rung of the unscoped ladder (no grown buffer, no exact pass over all rows).
+    assert st["pass_mode"] == 4 and st["passes"] == 2 and st["requeried"] == 1, st
+    assert st["exact_pass_queries"] == 0 and st["buffer_growths"] == 0, st
+    idx.close()
