@@ -120,7 +120,9 @@ typedef struct orr_search_stats {
                                     large-k sort); 1 two-stage on the int8 shadow; 2 two-stage on the bf16 shadow; 3 two-stage
                                     WITHOUT a shadow (fp32 rows converted inside the kernel: "two_stage" = 2, or the shadow
                                     did not fit in device memory and "two_stage" = 1 fell back); 4 scoped pass
-                                    (orr_search_batch_scoped: no screen, the listed rows re-scored exactly)              */
+                                    (orr_search_batch_scoped: no screen, the listed rows re-scored exactly; also the list path
+                                    of orr_search_batch_masked); 5 two-stage screen under a scope mask
+                                    (orr_search_batch_masked)                                                            */
     int64_t reserved[1];         /* orr_cluster_search_stats: record exchanges done by RCCL all-gather ("exchange" = 1)      */
 } orr_search_stats;
 
@@ -372,6 +374,31 @@ int orr_search_shard_scoped(orr_index *idx, int32_t B, int32_t dim, const float 
                             int64_t n_scope_ids, const int64_t *scope_ids, const uint64_t *scope_off,
                             const int64_t *scope_before, orr_candidate *out);
 
+/* ---- masked search: one scope shared by every query of the batch, screened once per batch ----
+ * A tenant's rows, a collection, a time window: a LARGE scope that the whole batch shares.  scope_ids[0 .. n_scope_ids) (host
+ * or device memory) is that scope.  The result is exactly what orr_search_batch_scoped defines for scope_off == NULL -- what
+ * orr_search_batch would return on a shard sealed from scratch from only the live rows whose id is listed, in their present
+ * candidate order: rows, order and fp64 scores bit for bit -- and ids (unknown, deleted, listed twice, carried by several
+ * rows), candidate_limit (counts scoped live rows), an empty scope (counts of 0), topk, dim 0 or another dimension, NaN order,
+ * ties and the argument errors are as documented there.
+ * What differs is the cost.  The scoped call re-scores every listed row once per query; this call streams the shard's shadow
+ * ONCE per batch through the two-stage screen with the scope as a mask on the rows (pass_mode 5), re-scores an in-scope
+ * sample of about sqrt(topk x scoped rows) rows per query for the floor, and re-scores the survivors exactly.  Unlike the
+ * scoped call it therefore MAY build a shadow ("two_stage") and MAY run a pass over all rows of the shard in front of the
+ * scope's last row.  Where the screen does not apply (what a two-stage pass needs: a cosine part, dim % 64 == 0,
+ * max(1, topk) <= 64, at least 196,608 rows in front of the scope's last row, "two_stage" != 0; and a scope larger than the
+ * sample) or does not pay ("mask_screen"), and for queries the screen cannot certify, the call runs the scoped pass over the
+ * scope in parts of at most "mask_part_rows" rows (pass_mode 4).  There is NO limit on the size of the scope: this call never
+ * answers ORR_EINVAL for a scope that is too large.
+ * A masked search is a search: it takes a lane, runs beside other searches, works on views, counts in orr_search_stats
+ * (survivors_* count what is left behind the mask; exact_pass_queries is never raised), and uses the id table of the scoped
+ * search (12 bytes per row, built at the first scoped or masked search). */
+int orr_search_batch_masked(orr_index *idx, int32_t B, int32_t dim, const float *q,
+                            const uint8_t *terms_utf8, const uint32_t *term_off, const uint32_t *query_term_off,
+                            int64_t now_ticks, int32_t topk, int64_t candidate_limit,
+                            int64_t n_scope_ids, const int64_t *scope_ids,
+                            int64_t *out_rows, double *out_scores, int32_t *out_counts);
+
 /* out_live[B] (host memory): the live rows query b's scope resolves to on this shard. */
 int orr_index_scope_count(orr_index *idx, int32_t B, int64_t n_scope_ids, const int64_t *scope_ids,
                           const uint64_t *scope_off, int64_t *out_live);
@@ -384,6 +411,12 @@ int orr_index_scope_count(orr_index *idx, int32_t B, int64_t n_scope_ids, const 
  *   "kw_hits_cap"    entries of the keyword chain's hit list, one per (distinct query term, vocabulary token containing it)
  *                    (default 16M = 384 MB at most).  A batch that needs more grows the list to the measured count and
  *                    repeats its pass; the option exists to pre-size it (or, in tests, to force that path).
+ *   "mask_screen"    0/1/2 (default 0): how orr_search_batch_masked picks its pass -- 0 by the cost rule (the masked screen
+ *                    when max(4 x queries, 128) x scoped rows >= rows in front of the scope's last row, else the list path), 1 the
+ *                    masked screen whenever the pass is eligible, 2 never (the list path in parts).  The results are the
+ *                    same; the option exists for measurements and tests.
+ *   "mask_part_rows" 1..4,194,240 (default 4,194,240): the most scoped rows one part of orr_search_batch_masked's list
+ *                    path takes.  Smaller values exist so that tests reach the multi-part path on a small shard.
  *   "shard_pass"     0/1/2 (default 0): which pass orr_search_shard runs -- 0 the library's choice, 1 the unfused
  *                    batched pass, 2 the reference-arithmetic pass over every row.  The caller of
  *                    orr_merge_candidates sets 2 for the repeat of a batch some query of which could not be certified.

@@ -36,6 +36,7 @@
 #include "orr_kernels.h"
 #include "orr_lanes.h"
 #include "orr_scope_plan.h"
+#include "orr_mask_plan.h"
 #include "orr_token_index.h"
 
 namespace {
@@ -215,6 +216,12 @@ struct orr_index {
     uint32_t *scope_tab_pos = nullptr; // [n_rows] positions, ascending within equal ids
     DevBuf ws_scope_ids, ws_scope_meta, ws_scope_bm, ws_scope_chunks, ws_scope_sel;   // a lane's: listed ids, offsets + limits, bitmaps, chunk counts, a pass's queries
     PinnedBuf pin_scope, pin_scope_pass;
+    // masked search (orr_search_batch_masked), a lane's: the call's shared scope bitmap and its chunk counts (the list path in
+    // parts rewrites ws_scope_bm per part), the sample's counts and the zeros that select the one bitmap, n_clip and the sample's sizes
+    DevBuf ws_mask_bm, ws_mask_chunks, ws_mask_cnt, ws_mask_meta;
+    PinnedBuf pin_mask;
+    int opt_mask_screen = 0;           // "mask_screen": 0 by the cost rule, 1 whenever eligible, 2 never (orr_mask_plan.h)
+    int64_t opt_mask_part_rows = mask::kDefaultPartRows;   // "mask_part_rows": scoped rows per part of the list path
 
     // search workspace
     DevBuf ws_q, ws_dot, ws_dotf, ws_sel, ws_cand, ws_qc, ws_rowc, ws_tau, ws_qsplit, ws_fcnt, ws_fbuf, ws_fqf, ws_fany, ws_tsL, ws_tskey, ws_qtiled, ws_fdot, ws_pbuf, ws_psel, ws_q8, ws_q8s1, ws_q8err, ws_zero, ws_norm_a;
@@ -689,6 +696,8 @@ void orr_index_destroy(orr_index *idx)
     idx->ws_norm_a.release();
     for (DevBuf *b : {&idx->ws_scope_ids, &idx->ws_scope_meta, &idx->ws_scope_bm, &idx->ws_scope_chunks, &idx->ws_scope_sel}) b->release();
     idx->pin_scope.release(); idx->pin_scope_pass.release();
+    for (DevBuf *b : {&idx->ws_mask_bm, &idx->ws_mask_chunks, &idx->ws_mask_cnt, &idx->ws_mask_meta}) b->release();
+    idx->pin_mask.release();
     DevBuf *bufs[] = {&idx->ws_q, &idx->ws_dot, &idx->ws_dotf, &idx->ws_rowc, &idx->ws_tau, &idx->ws_qsplit, &idx->ws_fcnt,
                       &idx->ws_fbuf, &idx->ws_fqf, &idx->ws_fany, &idx->ws_tsL, &idx->ws_tskey, &idx->ws_qtiled, &idx->ws_fdot, &idx->ws_pbuf, &idx->ws_psel, &idx->ws_q8, &idx->ws_q8s1, &idx->ws_q8err, &idx->ws_zero, &idx->ws_sel, &idx->ws_cand, &idx->ws_qc, &idx->ws_keys_a, &idx->ws_keys_b,
                       &idx->ws_vals_a, &idx->ws_vals_b, &idx->ws_sort_tmp, &idx->ws_raw, &idx->ws_src_start, &idx->ws_qsub,
@@ -1775,6 +1784,7 @@ static void copy_options(const orr_index *from, orr_index *to)
     to->opt_fuse_epilogue = from->opt_fuse_epilogue; to->opt_two_stage = from->opt_two_stage;
     to->opt_shard_pass = from->opt_shard_pass; to->opt_shard_topk = from->opt_shard_topk;
     to->kw_hits_cap = from->kw_hits_cap; to->dead_before = from->dead_before;
+    to->opt_mask_screen = from->opt_mask_screen; to->opt_mask_part_rows = from->opt_mask_part_rows;
 }
 
 // a lane borrows whatever shadows its index has now
@@ -1812,6 +1822,13 @@ int orr_index_set_option(orr_index *idx, const char *name, int64_t value)
     } else if (strcmp(name, "shard_pass") == 0) {
         if (value < 0 || value > 2) return fail(ORR_EINVAL, "orr_index_set_option: shard_pass takes 0, 1 or 2");
         idx->opt_shard_pass = (int)value;
+    } else if (strcmp(name, "mask_screen") == 0) {
+        if (value < 0 || value > 2) return fail(ORR_EINVAL, "orr_index_set_option: mask_screen takes 0, 1 or 2");
+        idx->opt_mask_screen = (int)value;
+    } else if (strcmp(name, "mask_part_rows") == 0) {
+        if (!mask::part_rows_valid(value))
+            return fail(ORR_EINVAL, "orr_index_set_option: mask_part_rows must be in 1 .. %u", scope::kMaxScopeRows);
+        idx->opt_mask_part_rows = value;
     } else if (strcmp(name, "two_stage") == 0) {
         if (value < 0 || value > 2) return fail(ORR_EINVAL, "orr_index_set_option: two_stage takes 0, 1 or 2");
         idx->opt_two_stage = (int)value;
@@ -2432,6 +2449,7 @@ struct PassPlan {
     int prefix_floor_form = 0;      // fuse_select floor_only of the sampled prefix
     double approx_eps = 0.0;        // bound of the approximate scores of the batched pass (and of the two-stage prefix)
     double eps1 = 0.0;              // two-stage: bound of the screen over all rows (0: added inside the kernel)
+    bool masked = false;            // the screen runs under a scope mask (run_masked_pass): no prefix, the floor from an in-scope sample
 
     bool two_stage() const {   // the pass keeps survivors in per-query buffers (idx->h_survivors holds their counts)
         return form == PassForm::TwoStageGemm || form == PassForm::TwoStageStream;
@@ -2439,7 +2457,7 @@ struct PassPlan {
     bool stream() const { return form == PassForm::TwoStageStream; }
     double plane_bytes_per_row(int32_t B) const { return (count_bits == 2 ? 8.0 : 16.0) * (double)((B + 31) / 32); }   // count words
     bool fused() const { return fused_sample_seg > 0; }
-    int pass_mode() const { static constexpr int kMode[] = {0, 1, 1, 2, 2, 3}; return kMode[(int)screen]; }   // orr_search_stats
+    int pass_mode() const { static constexpr int kMode[] = {0, 1, 1, 2, 2, 3}; return masked ? 5 : kMode[(int)screen]; }   // orr_search_stats
 };
 
 // Decides the form of one pass and what it derives, building the shadows it reads.
@@ -2564,6 +2582,16 @@ int plan_pass(orr_index *idx, const BatchArgs &a, int32_t kprime, int64_t n, con
     return ORR_OK;
 }
 
+// The shared scope of a masked search as its pass sees it (orr_search_batch_masked; the rules are orr_mask_plan.h's).
+struct MaskScope {
+    const uint32_t *bm = nullptr;       // device: the scope's bitmap over the shard's rows, deleted rows left out
+    const uint32_t *chunks = nullptr;   // device: its chunk counts (launch_scope_counts)
+    int64_t words = 0;
+    int64_t live = 0, took = 0;         // live rows of the scope; the first `took` of them take part
+    int64_t n_clip = 0;                 // one past the last of those: the pass runs over rows [0, n_clip)
+    int64_t sample = 0;                 // rows of the in-scope sample the floor comes from (mask::sample_rows)
+};
+
 // What the stages of one pass hand on to each other.
 struct PassIo {
     const float *d_q = nullptr;         // the query vectors on the device
@@ -2573,6 +2601,7 @@ struct PassIo {
     const double2 *d_rowc = nullptr;    // per-row selection constants, or null
     orr_candidate *d_cand = nullptr;    // the records [B][kprime + 1]
     bool direct_host = false;           // d_cand is pinned host memory
+    const MaskScope *mask = nullptr;    // a masked pass: the scope (else null)
 };
 
 // The front end of a pass, unscoped (run_shard_once) or scoped (run_scoped_pass): the term offsets, the plan, where the
@@ -2708,6 +2737,10 @@ int launch_numerators(orr_index *idx, const BatchArgs &a, const PassPlan &p, int
         HIP_TRY(orr::launch_split_queries(io.d_q, B, idx->dim, idx->ws_qsplit.p, s));
         return ORR_OK;
     };
+    if (p.masked) {                     // no prefix under a mask (the floor comes from an in-scope sample): only the images the screen reads
+        if (p.prefix_i8) return launch_i8_query_image(idx, io.d_q, B, true, s);
+        return p.split_queries ? split_queries() : ORR_OK;
+    }
     switch (p.form) {
     case PassForm::Exact:
     case PassForm::LargeK:
@@ -2786,8 +2819,11 @@ int launch_consts(orr_index *idx, const BatchArgs &a, const PassPlan &p, int64_t
     }
     if (p.batched_score && !p.rowc_inline) {
         ORR_TRY(idx->ws_rowc.reserve(sizeof(double2) * (size_t)n));
-        Timed t(idx, "row_consts", 32.0 * (double)n);
-        HIP_TRY(orr::launch_row_consts(idx->d_norm_b, idx->d_created, a.now_ticks, n, idx->ws_rowc.as<double2>(), s));
+        Timed t(idx, io.mask ? "row_consts_masked" : "row_consts", 32.0 * (double)n);
+        if (io.mask)      // rows outside the scope get constants below every floor
+            HIP_TRY(orr::launch_row_consts_masked(idx->d_norm_b, idx->d_created, a.now_ticks, n, io.mask->bm, idx->ws_rowc.as<double2>(), s));
+        else
+            HIP_TRY(orr::launch_row_consts(idx->d_norm_b, idx->d_created, a.now_ticks, n, idx->ws_rowc.as<double2>(), s));
         io.d_rowc = idx->ws_rowc.as<double2>();
     }
     return ORR_OK;
@@ -2893,6 +2929,50 @@ int screen_i8_in_ranges(orr_index *idx, const BatchArgs &a, const PassPlan &p, i
     return ORR_OK;
 }
 
+// The floor of a masked pass: the first mask.sample in-scope rows become buffer entries, the exact re-score gives them exact
+// keys, and their kth best per query is the floor's base -- a lower bound of the final kth best whatever the scope looks like.
+// The keys are exact scores of the device's arithmetic: the floor carries the certificate's own bound, no screen's.
+int masked_floor(orr_index *idx, const BatchArgs &a, const PassIo &io, int32_t kth, orr::FloorOut floor)
+{
+    const int32_t B = a.B;
+    hipStream_t s = idx->stream;
+    const MaskScope &m = *io.mask;
+    const uint32_t cap = (uint32_t)m.sample;                                   // whole lists of 64, fewer than took
+    const int32_t lists = (int32_t)(cap / orr::kSelWidth);
+    // [limit i64][query -> bitmap 0, u32 x B][counts u32 x B]
+    const size_t o_sel = sizeof(int64_t), o_cnt = o_sel + sizeof(uint32_t) * (size_t)B, bytes = o_cnt + sizeof(uint32_t) * (size_t)B;
+    ORR_TRY(idx->pin_mask.reserve(sizeof(int64_t) + bytes));                   // (its first word: n_clip, masked_batch's)
+    ORR_TRY(idx->ws_mask_cnt.reserve(bytes));
+    uint8_t *hp = idx->pin_mask.as<uint8_t>() + sizeof(int64_t);
+    *reinterpret_cast<int64_t *>(hp) = m.sample;
+    for (int32_t b = 0; b < B; ++b) {
+        reinterpret_cast<uint32_t *>(hp + o_sel)[b] = 0u;
+        reinterpret_cast<uint32_t *>(hp + o_cnt)[b] = cap;
+    }
+    HIP_TRY(hipMemcpyAsync(idx->ws_mask_cnt.p, hp, bytes, hipMemcpyHostToDevice, s));
+    uint8_t *dp = idx->ws_mask_cnt.as<uint8_t>();
+    const uint32_t *d_cnt = reinterpret_cast<const uint32_t *>(dp + o_cnt);
+    ORR_TRY(idx->ws_pbuf.reserve(sizeof(orr::SelEntry) * (size_t)B * cap));
+    ORR_TRY(idx->ws_psel.reserve(sizeof(orr::SelEntry) * (size_t)B * cap));
+    ORR_TRY(idx->ws_dot.reserve(sizeof(double) * (size_t)B * cap));
+    orr::SelEntry *buf = idx->ws_pbuf.as<orr::SelEntry>();
+    {
+        Timed t(idx, "mask_sample_compact", 16.0 * (double)B * (double)cap);
+        HIP_TRY(orr::launch_scope_compact(m.bm, m.words, 1, m.chunks, reinterpret_cast<const uint32_t *>(dp + o_sel), B,
+                                          reinterpret_cast<const int64_t *>(dp), buf, cap, s));
+    }
+    {
+        Timed t(idx, "mask_sample_rescore", (double)B * (double)cap * 4.0 * idx->dim);
+        HIP_TRY(orr::launch_rescore_buffer_exact(idx->d_emb, idx->dim, io.d_q, B, idx->d_norm_b, idx->d_created, io.kw,
+                                                 idx->ws_qc.as<orr::QueryConst>(), a.now_ticks, d_cnt, cap, buf, idx->ws_dot.as<double>(), s));
+    }
+    Timed t(idx, "mask_sample_floor", 0.0);
+    HIP_TRY(orr::launch_buffer_to_lists(buf, d_cnt, cap, B, 0, lists, idx->ws_psel.as<orr::SelEntry>(), s));
+    floor.eps3 = kCertifyEps;
+    HIP_TRY(orr::launch_select_final_sample(idx->ws_psel.as<orr::SelEntry>(), lists, lists, B, kth, idx->ws_tau.as<unsigned long long>(), s, floor));
+    return ORR_OK;
+}
+
 // The two-stage forms after the prefix: the floor, the screen over all rows into the survivors' buffers, the exact tail.
 int screen_two_stage(orr_index *idx, const BatchArgs &a, const PassPlan &p, int32_t kprime, int64_t n, PassIo &io,
                      orr::FusedEpilogue &epi, uint32_t kCap, int32_t buf_lists, int32_t lists_total, bool host_records, size_t rec_bytes)
@@ -2908,7 +2988,10 @@ int screen_two_stage(orr_index *idx, const BatchArgs &a, const PassPlan &p, int3
     floor.floor_key = idx->ws_tskey.as<unsigned long long>();
     floor.L = idx->ws_tsL.as<double>();
     floor.eps3 = p.approx_eps; floor.eps1 = p.eps1;
-    if (p.stream()) {
+    if (io.mask) ORR_TRY(masked_floor(idx, a, io, kth, floor));
+    if (io.mask && p.stream()) {
+        // (the stream scores in fp64 against the floor keys directly: nothing more in front of it)
+    } else if (p.stream()) {
         // the sample goes through the stream too: floor keys of 0 keep every sampled row, their
         // approximate keys are sorted in lists of 64 and the k-th best one per query is the floor's base
         const uint32_t cap_p = (uint32_t)p.dotf_rows;                 // a multiple of 4096
@@ -2945,7 +3028,7 @@ int screen_two_stage(orr_index *idx, const BatchArgs &a, const PassPlan &p, int3
             HIP_TRY(orr::launch_select_final_sample(idx->ws_psel.as<orr::SelEntry>(), lists_all, lists_p, B, kth, d_tau, s, floor));
         }
     } else {
-        {
+        if (!io.mask) {
             Timed t(idx, "select_floor", 0.0);
             HIP_TRY(orr::launch_select_final_sample(idx->ws_sel.as<orr::SelEntry>(), lists_total, p.fused_sample_seg, B, kth, d_tau, s, floor,
                                                     p.prefix_floor_form == 2 ? 1 : 0));
@@ -2971,7 +3054,7 @@ int screen_two_stage(orr_index *idx, const BatchArgs &a, const PassPlan &p, int3
         Timed t(idx, "screen_gemv_i8", 1.0 * (double)n * idx->dim + 28.0 * (double)n + 2.0 * (double)B * idx->dim);   // per row: scale, two relative norms (12 B), normB and created (16 B)
         HIP_TRY(orr::launch_screen_gemv_i8(idx->ws_q8.p, idx->ws_q8s1.as<float>(), idx->ws_q8err.as<double>(), B, idx->emb_i8.p,
                                            idx->i8_scale.as<float>(), idx->i8_rel_err.as<float>(), idx->i8_rel_hat.as<float>(),
-                                           idx->d_norm_b, idx->d_created, a.now_ticks, n, idx->dim, epi, false, s));
+                                           io.mask ? nullptr : idx->d_norm_b, idx->d_created, a.now_ticks, n, idx->dim, epi, false, s));   // (masked: the constants come from epi.rowc)
     } else if (p.screen == Screen::GemvBf16) {
         Timed t(idx, "screen_gemv_bf16", 2.0 * (double)n * idx->dim + 2.0 * (double)B * idx->dim);
         HIP_TRY(orr::launch_screen_gemv_bf16(idx->ws_qsplit.p, B, idx->emb_shadow.p, n, idx->dim, epi, s));
@@ -2984,7 +3067,13 @@ int screen_two_stage(orr_index *idx, const BatchArgs &a, const PassPlan &p, int3
         Timed t(idx, "gemm_dot_bf16x1_fused", 4.0 * (double)n * idx->dim + 2.0 * (double)B * idx->dim);
         HIP_TRY(orr::launch_gemm_dot_bf16x3(idx->ws_qsplit.p, B, idx->d_emb, 0, n, idx->dim, nullptr, 0, &epi, 1, s));
     }
-    return two_stage_tail(idx, a, kprime, n, io, epi, kCap, buf_lists, host_records, rec_bytes, Rescore::BufferExact, 0.0, s);
+    if (io.mask) {      // the one exact application of the mask: what the screen buffered from outside the scope goes
+        Timed t(idx, "mask_survivors", 16.0 * (double)B * (double)kCap);
+        HIP_TRY(orr::launch_mask_survivors(io.mask->bm, io.mask->n_clip, epi.cnt, kCap, epi.buf, B, s));
+    }
+    ORR_TRY(two_stage_tail(idx, a, kprime, n, io, epi, kCap, buf_lists, host_records, rec_bytes, Rescore::BufferExact, 0.0, s));
+    if (io.mask) HIP_TRY(orr::launch_mask_trailers(io.d_cand, B, kprime, io.mask->took, s));
+    return ORR_OK;
 }
 
 // Stage 7 of the SplitFused and two-stage forms: prefix lists -> floor keys -> the screening launch with the scoring
@@ -3007,7 +3096,7 @@ int select_fused(orr_index *idx, const BatchArgs &a, const PassPlan &p, int32_t 
     ORR_TRY(idx->ws_fcnt.reserve(sizeof(uint32_t) * 3 * (size_t)B));      // [survivors][sampled prefix][workgroups done]
     ORR_TRY(idx->ws_fbuf.reserve(sizeof(orr::SelEntry) * (size_t)B * kCap));
     unsigned long long *d_tau = idx->ws_tau.as<unsigned long long>();
-    if (!p.stream()) {
+    if (!p.stream() && !io.mask) {
         Timed t(idx, "fuse_select", (double)B * (double)p.dotf_rows * 28.0);
         orr::I8Prefix i8p;
         if (p.prefix_i8) { i8p.rowf = idx->i8_rowf.as<float4>(); i8p.qs1 = idx->ws_q8s1.as<float>(); i8p.qerr2 = idx->ws_q8err.as<double>() + B; }
@@ -3138,7 +3227,7 @@ int finish_pass(orr_index *idx, const BatchArgs &a, const PassPlan &p, const KwS
         idx->h_survivors.assign(idx->pin_cnt.as<uint32_t>(), idx->pin_cnt.as<uint32_t>() + B);
         uint64_t sum = 0;
         for (uint32_t cnt : idx->h_survivors) sum += cnt;
-        const uint64_t mean = sum / (uint64_t)B;
+        const uint64_t mean = p.masked ? 1024 : sum / (uint64_t)B;     // (a masked pass has no sampled prefix to steer)
         if (mean > 4096 && idx->sample_boost < 16) idx->sample_boost *= 2;
         else if (mean < 512 && idx->sample_boost > 1) idx->sample_boost /= 2;
     }
@@ -3871,6 +3960,242 @@ int scoped_batch(orr_index *idx, const BatchArgs &orig, const ScopeArgs &sc, int
     return ORR_OK;
 }
 
+// ---- masked search: one scope shared by every query of the batch, screened once per batch (orr_search_batch_masked) ---------
+// The scope resolves to ONE bitmap as a shared scoped list does; then, instead of re-scoring every listed row per query, the
+// two-stage screen of the unscoped pass runs over rows [0, n_clip) with the mask in its row constants, a filter behind it makes
+// the mask exact, and the exact tail ranks what is left.  Large scopes that the cost rule leaves to the list path, ineligible
+// passes and the end of the ladder run the scoped pass over the bitmap in parts.  The rules are orr_mask_plan.h's.
+
+constexpr int kNotMaskable = 2;        // run_masked_pass: plan_form found no two-stage form for the batch (k' beyond a list, no shadow): the list path
+
+// One masked pass over the queries of `a`: run_shard_once's front end and stages over rows [0, ms.n_clip), no prefix (the floor
+// comes from an in-scope sample, masked_floor), the survivors filtered by the mask in front of the tail.  Records in host
+// memory (*recs_host).  kRetryPass as run_shard_once; kNotMaskable before anything ran.  Caller holds the lane and its lock.
+int run_masked_pass(orr_index *idx, const BatchArgs &a, int32_t kprime, const MaskScope &ms, const float **q_host,
+                    const orr_candidate **recs_host, PassPlan &p)
+{
+    ORR_TRY(bind_device(idx));
+    const int64_t n = ms.n_clip;
+    const int32_t B = a.B;
+    hipStream_t s = idx->stream;
+    *recs_host = nullptr;
+    PassFront f;
+    auto plan = [&](const std::vector<uint32_t> &qoff, PassPlan &pl) -> int {
+        ORR_TRY(plan_pass(idx, a, kprime, n, qoff, pl));
+        if (!pl.two_stage()) return kNotMaskable;
+        pl.masked = true;
+        pl.rowc_inline = false;        // the mask lives in the materialised row constants: the int8 stream reads them too
+        return ORR_OK;
+    };
+    ORR_TRY(open_pass(idx, a, kprime, plan, true, false, false, q_host, p, f));
+    PassIo &io = f.io;
+    io.mask = &ms;
+    if (p.screen == Screen::GemvI8) ORR_TRY(launch_i8_query_image(idx, io.d_q, B, false, s));
+    KwSide kws;
+    ORR_TRY(launch_keyword_side(idx, a, f.qoff, kws));
+    io.kw = kws.view;
+    ORR_TRY(launch_numerators(idx, a, p, n, io));
+    ORR_TRY(launch_consts(idx, a, p, n, f.qoff, f.q_download_pending, io));
+    if (f.n_terms_total > 0) HIP_TRY(hipStreamWaitEvent(s, idx->ev_kw_done, 0));
+    ORR_TRY(launch_selection(idx, a, p, kprime, n, io, true, f.rec_bytes));
+    // (no record of a deleted row: the mask never held one)
+    ORR_TRY(records_to_host(idx, f, s));
+    idx->sstats.pass_mode = p.pass_mode();
+    const int r = finish_pass(idx, a, p, kws, f.n_terms_total);
+    if (r != ORR_OK) return r;
+    *recs_host = io.direct_host ? io.d_cand : idx->pin_cand.as<orr_candidate>();
+    return ORR_OK;
+}
+
+// The list path in parts for the queries `ids` of the call (ascending): the scope's first ms.took rows cut by rank into parts
+// of at most mask_part_rows, each part a scoped pass over every query (for_each_scoped_part), the parts' records merged per
+// query as shards in global order are; an uncertified query climbs scope::next_rung over all parts.  `sl` is the call's slice
+// (b0 = 0, every query of the call, one shared bitmap in ws_scope_bm, which a part overwrites when there are several).
+int masked_list_path(orr_index *idx, const BatchArgs &orig, const ScopeSlice &sl, const MaskScope &ms, const std::vector<int32_t> &ids,
+                     bool requery, int64_t *out_rows, double *out_scores, int32_t *out_counts)
+{
+    const int32_t take = std::max<int32_t>(1, orig.topk);
+    const bool use_cos = orig.dim > 0 && orig.dim == idx->dim;
+    const int64_t part_rows = idx->opt_mask_part_rows;
+    const int64_t P = mask::part_count(ms.took, part_rows);
+    if (P > (1 << 16)) return fail(ORR_EINVAL, "orr_search_batch_masked: mask_part_rows %lld cuts the scope into %lld parts", (long long)part_rows, (long long)P);
+    const int64_t max_part = std::min<int64_t>(ms.took, part_rows);
+    hipStream_t s = idx->stream;
+    uint32_t *h_live = const_cast<uint32_t *>(sl.live), *h_took = const_cast<uint32_t *>(sl.took);       // pin_scope: a part's counts land there
+    struct Todo { std::vector<int32_t> ids; scope::Rung rung; int repeats; };
+    std::deque<Todo> todo(1, Todo{ids, scope::first_rung(take, max_part, orr::kSelWidth), requery ? 1 : 0});
+    while (!todo.empty()) {
+        const Todo r = std::move(todo.front());
+        todo.pop_front();
+        const bool all = r.rung.form == scope::Form::AllRecords;
+        const int64_t K = all ? std::max<int64_t>(1, max_part) : r.rung.kprime;       // records per query and part
+        const int32_t n_ids = (int32_t)r.ids.size();
+        const int32_t group = mask::merge_group(n_ids, P, K, mask::kMergeBudgetBytes);
+        const size_t rec_q = (size_t)K + 1;
+        Todo next{{}, {}, r.repeats + 1};
+        for (int32_t g0 = 0; g0 < n_ids; g0 += group) {
+            const std::vector<int32_t> gids(r.ids.begin() + g0, r.ids.begin() + std::min<int32_t>(n_ids, g0 + group));
+            const size_t nb = gids.size();
+            const std::vector<uint32_t> q(gids.begin(), gids.end());                  // the slice's numbering is the call's
+            std::vector<orr_candidate> store((size_t)P * nb * rec_q);
+            std::vector<double> norms(nb, 0.0);
+            for (int64_t j = 0; j < P; ++j) {
+                if (P > 1) {       // this part's bitmap and counts; candidate_limit is already in the clip to ms.took
+                    const auto range = mask::part_range(j, ms.took, part_rows);
+                    Timed t(idx, "mask_part", 8.0 * (double)ms.words);
+                    HIP_TRY(orr::launch_mask_part(ms.bm, ms.words, ms.chunks, (uint64_t)range.first, (uint64_t)range.second,
+                                                  idx->ws_scope_bm.as<uint32_t>(), s));
+                    HIP_TRY(orr::launch_scope_counts(idx->ws_scope_bm.as<uint32_t>(), sl.words, 1, sl.nq, sl.d_limit,
+                                                     idx->ws_scope_chunks.as<uint32_t>(), h_live, h_took, s));
+                }
+                HIP_TRY(hipStreamSynchronize(s));
+                collect_events(idx);
+                ORR_TRY(for_each_scoped_part(idx, orig, sl, q, r.rung.form, all ? 1 : (int32_t)K, [&](const ScopedPart &pt) -> int {
+                    for (size_t i = 0; i < pt.ids.size(); ++i) {
+                        const size_t at = (size_t)(std::lower_bound(gids.begin(), gids.end(), pt.ids[i]) - gids.begin());
+                        orr_candidate *dst = store.data() + ((size_t)j * nb + at) * rec_q;
+                        const orr_candidate *src = pt.recs + i * ((size_t)pt.kprime + 1);
+                        const size_t have = std::min<size_t>((size_t)pt.kprime, (size_t)K);
+                        memcpy(dst, src, sizeof(orr_candidate) * have);
+                        for (size_t e = have; e < (size_t)K; ++e) { memset(&dst[e], 0, sizeof(dst[e])); dst[e].row_id = -1; dst[e].order_key = -1; }
+                        dst[K] = src[pt.kprime];
+                        norms[at] = idx->h_norm_a[i];
+                    }
+                    if (r.repeats > 0 && j == 0) idx->sstats.requeried += (int64_t)pt.ids.size();
+                    return ORR_OK;
+                }));
+            }
+            SubBatch sb;
+            BatchArgs cur;
+            ORR_TRY(build_subset(idx, orig, gids, sb, cur));
+            std::vector<uint8_t> cert;
+            ORR_TRY(merge_into((int32_t)P, (int32_t)K, store.data(), cur, use_cos, nullptr, norms.data(), gids, out_rows, out_scores, out_counts, cert));
+            for (size_t i = 0; i < cert.size(); ++i)
+                if (!cert[i]) next.ids.push_back(gids[i]);
+        }
+        if (next.ids.empty()) continue;
+        next.rung = scope::next_rung(r.rung, max_part, orr::kSelWidth);
+        if (next.rung.form == scope::Form::Done || next.repeats > scope::kMaxRungs + 1)
+            return fail(ORR_EDEVICE, "orr_search_batch_masked: a pass over every scoped row left a query uncertified");
+        todo.push_front(std::move(next));
+    }
+    return ORR_OK;
+}
+
+// The queries `ids` of the call through the masked screen and its ladder (mask::next_step).  The ladder is a query's: of the
+// queries a pass leaves uncertified, those whose overflowing buffer can be grown repeat together, the others take the next rung.
+int masked_screen_ladder(orr_index *idx, const BatchArgs &orig, const ScopeSlice &sl, const MaskScope &ms, std::vector<int32_t> first_ids,
+                         int64_t *out_rows, double *out_scores, int32_t *out_counts)
+{
+    const int32_t take = std::max<int32_t>(1, orig.topk);
+    const bool use_cos = orig.dim > 0 && orig.dim == idx->dim;
+    struct Todo { std::vector<int32_t> ids; int64_t kprime; bool grown; int repeats; };
+    std::deque<Todo> todo(1, Todo{std::move(first_ids), escalation::initial_kprime(take, ms.took, orr::kSelWidth), false, 0});
+    while (!todo.empty()) {
+        const Todo r = std::move(todo.front());
+        todo.pop_front();
+        const size_t nb = r.ids.size();
+        SubBatch sb;
+        BatchArgs cur;
+        ORR_TRY(build_subset(idx, orig, r.ids, sb, cur));
+        PassPlan pass;
+        const float *q_host = nullptr;
+        const orr_candidate *recs = nullptr;
+        const int rc = retry_pass(idx, [&] { return run_masked_pass(idx, cur, (int32_t)r.kprime, ms, &q_host, &recs, pass); });
+        if (rc == kNotMaskable) {
+            ORR_TRY(masked_list_path(idx, orig, sl, ms, r.ids, r.repeats > 0, out_rows, out_scores, out_counts));
+            continue;
+        }
+        if (rc != ORR_OK) return rc;
+        std::vector<uint8_t> cert;
+        ORR_TRY(merge_into(1, (int32_t)r.kprime, recs, cur, use_cos, q_host, idx->h_norm_a.data(), r.ids, out_rows, out_scores, out_counts, cert));
+        const ShardOutcome o = outcome_of(idx, pass, ms.n_clip);
+        idx->sstats.passes += 1;
+        if (r.repeats > 0) idx->sstats.requeried += (int64_t)nb;
+        escalation::account_survivors(idx->sstats, o, nb);
+        size_t n_again = 0;
+        for (size_t i = 0; i < nb; ++i) n_again += cert[i] ? 0 : 1;
+        if (n_again == 0) continue;
+        // uncertified queries: those that overflowed a buffer larger ones can hold, and the rest
+        std::vector<int32_t> grow, rest;
+        uint32_t worst = 0, cap_i = 0;
+        for (size_t i = 0; i < nb; ++i) {
+            if (cert[i]) continue;
+            if (!r.grown && o.kept(nb) && o.overflowed(i) && escalation::grown_survivor_cap(o.pass_cap, o.survivors[i], ms.n_clip, n_again, &cap_i)) {
+                grow.push_back(r.ids[i]);
+                worst = std::max(worst, o.survivors[i]);
+            } else {
+                rest.push_back(r.ids[i]);
+            }
+        }
+        if (r.repeats >= mask::kMaxScreenRepeats) { rest.insert(rest.end(), grow.begin(), grow.end()); std::sort(rest.begin(), rest.end()); grow.clear(); }
+        if (!rest.empty()) {
+            const mask::Next nx = mask::next_step(false, r.grown, o.pass_cap, 0, ms.n_clip, rest.size(), r.kprime, orr::kSelWidth);
+            if (nx.step == mask::Step::WiderK && r.repeats < mask::kMaxScreenRepeats) todo.push_back(Todo{rest, nx.kprime, r.grown, r.repeats + 1});
+            else ORR_TRY(masked_list_path(idx, orig, sl, ms, rest, true, out_rows, out_scores, out_counts));
+        }
+        if (!grow.empty()) {
+            const mask::Next nx = mask::next_step(true, r.grown, o.pass_cap, worst, ms.n_clip, grow.size(), r.kprime, orr::kSelWidth);
+            if (nx.step != mask::Step::GrowBuffers) {
+                ORR_TRY(masked_list_path(idx, orig, sl, ms, grow, true, out_rows, out_scores, out_counts));
+                continue;
+            }
+            idx->sstats.buffer_growths += 1;       // the index keeps the larger size, as for the unscoped search
+            if (nx.new_cap > idx->survivor_cap) idx->survivor_cap = nx.new_cap;
+            if (!idx->is_view || idx->internal_lane) publish_survivor_hint(const_cast<orr_index *>(owner_of(idx)), nx.new_cap);
+            todo.push_back(Todo{grow, nx.kprime, true, r.repeats + 1});
+        }
+    }
+    return ORR_OK;
+}
+
+// orr_search_batch_masked on the lane the caller holds.
+int masked_batch(orr_index *idx, const BatchArgs &orig, const ScopeArgs &sc, int64_t *out_rows, double *out_scores, int32_t *out_counts)
+{
+    const int32_t B = orig.B, take = std::max<int32_t>(1, orig.topk);
+    const bool use_cos = orig.dim > 0 && orig.dim == idx->dim;
+    for (size_t i = 0; i < (size_t)B * take; ++i) { out_rows[i] = -1; out_scores[i] = 0.0; }
+    if (out_counts) for (int32_t b = 0; b < B; ++b) out_counts[b] = 0;
+    if (idx->n_rows <= 0 || sc.n_ids == 0) return ORR_OK;
+    ORR_TRY(bind_device(idx));
+    ORR_TRY(ensure_scope_table(idx));
+    hipStream_t s = idx->stream;
+    // ---- resolve: one shared bitmap; live and took are the same for every query
+    const std::vector<int64_t> limit((size_t)B, std::max<int64_t>(1, orig.candidate_limit));
+    ScopeSlice sl;
+    ORR_TRY(build_scope_slice(idx, sc, limit, 0, B, sl));
+    MaskScope ms;
+    ms.words = sl.words; ms.live = sl.live[0]; ms.took = sl.took[0];
+    if (ms.took == 0) return ORR_OK;
+    // ---- the scope's bitmap is kept beside the slice's (which the list path rewrites per part); clip
+    const size_t bm_bytes = sizeof(uint32_t) * (size_t)ms.words, ch_bytes = sizeof(uint32_t) * (size_t)orr::scope_chunks(ms.words);
+    ORR_TRY(idx->ws_mask_bm.reserve(bm_bytes));
+    ORR_TRY(idx->ws_mask_chunks.reserve(ch_bytes));
+    ORR_TRY(idx->pin_mask.reserve(sizeof(int64_t)));
+    HIP_TRY(hipMemcpyAsync(idx->ws_mask_bm.p, idx->ws_scope_bm.p, bm_bytes, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(idx->ws_mask_chunks.p, idx->ws_scope_chunks.p, ch_bytes, hipMemcpyDeviceToDevice, s));
+    ms.bm = idx->ws_mask_bm.as<uint32_t>(); ms.chunks = idx->ws_mask_chunks.as<uint32_t>();
+    {
+        Timed t(idx, "mask_clip", 4.0 * (double)orr::kScopeChunkWords + (double)ch_bytes);
+        HIP_TRY(orr::launch_mask_clip(ms.bm, ms.words, ms.chunks, (uint32_t)ms.took, idx->pin_mask.as<int64_t>(), s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    collect_events(idx);
+    ms.n_clip = std::min<int64_t>(*idx->pin_mask.as<int64_t>(), idx->n_rows);
+    ms.sample = mask::sample_rows(orig.topk, ms.took);
+    // ---- the screen or the list path
+    const bool eligible = mask::eligible(use_cos, idx->dim, orig.topk, orr::kSelWidth, ms.n_clip, idx->opt_two_stage, ms.took);
+    std::vector<int32_t> ids((size_t)B);
+    std::iota(ids.begin(), ids.end(), 0);
+    if (mask::choose(idx->opt_mask_screen, eligible, B, ms.took, ms.n_clip) == mask::Path::List)
+        return masked_list_path(idx, orig, sl, ms, ids, false, out_rows, out_scores, out_counts);
+    const int32_t per = mask::screen_slice(B, ms.sample);
+    for (int32_t b0 = 0; b0 < B; b0 += per)
+        ORR_TRY(masked_screen_ladder(idx, orig, sl, ms, std::vector<int32_t>(ids.begin() + b0, ids.begin() + std::min<int32_t>(B, b0 + per)),
+                                     out_rows, out_scores, out_counts));
+    return ORR_OK;
+}
+
 // The best kprime records of each query out of its K >= kprime AllRecords records, ranked by the exact key on the host, with the
 // trailer orr_search_shard leaves: the cut-off is the worst kept record's exact score (bound 0).
 void reduce_all_records(const orr_candidate *recs, int32_t nb, int32_t K, int32_t kprime, bool use_cos, const double *norms,
@@ -4124,6 +4449,24 @@ int orr_search_batch_scoped(orr_index *idx, int32_t B, int32_t dim, const float 
     idx->sstats.searches += 1;
     idx->sstats.queries += B;
     return scoped_batch(idx, a, sc, out_rows, out_scores, out_counts);
+}
+
+int orr_search_batch_masked(orr_index *idx, int32_t B, int32_t dim, const float *q, const uint8_t *terms_utf8,
+                            const uint32_t *term_off, const uint32_t *query_term_off, int64_t now_ticks, int32_t topk,
+                            int64_t candidate_limit, int64_t n_scope_ids, const int64_t *scope_ids,
+                            int64_t *out_rows, double *out_scores, int32_t *out_counts)
+{
+    BatchArgs a{B, dim, q, terms_utf8, term_off, query_term_off, now_ticks, candidate_limit, topk};
+    const ScopeArgs sc{n_scope_ids, scope_ids, nullptr, nullptr};
+    ORR_TRY(check_scope(idx, B, sc, "orr_search_batch_masked"));
+    ORR_TRY(check_batch(idx, a, "orr_search_batch_masked"));
+    if (!out_rows || !out_scores) return fail(ORR_EINVAL, "orr_search_batch_masked: output buffers are required");
+    Lane ln = acquire_lane(idx);                       // a search like any other: its own lane, concurrent with the others
+    idx = ln.lane;
+    std::lock_guard<std::mutex> lock(idx->mu);
+    idx->sstats.searches += 1;
+    idx->sstats.queries += B;
+    return masked_batch(idx, a, sc, out_rows, out_scores, out_counts);
 }
 
 int orr_search_shard_scoped(orr_index *idx, int32_t B, int32_t dim, const float *q, const uint8_t *terms_utf8,

@@ -8,6 +8,7 @@
 #include "../../include/omnirecall_hip.h"
 #include "orr_layout.h"
 #include "orr_scope_plan.h"
+#include "orr_mask_plan.h"
 
 #include <atomic>
 
@@ -423,5 +424,21 @@ hipError_t launch_scope_records(const SelEntry *buf, const double *buf_dot, cons
                                 orr_candidate *recs, hipStream_t s);
 // The trailers the two-stage tail wrote, made a scoped pass's: order_key = cnt[b], no floor (ORR_CAND_TWO_STAGE cleared).
 hipError_t launch_scope_trailers(orr_candidate *recs, int32_t B, int32_t kprime, const uint32_t *cnt, hipStream_t s);
+
+// ---- masked search (orr_search_batch_masked; the rules are orr_mask_plan.h's) ----------------------------------------------
+// *n_clip (may be pinned host memory) = one past the position of the took-th set bit of the bitmap (1 <= took <= its set
+// bits; chunk_cnt as launch_scope_counts left it).
+hipError_t launch_mask_clip(const uint32_t *bitmap, int64_t words, const uint32_t *chunk_cnt, uint32_t took, int64_t *n_clip, hipStream_t s);
+// launch_row_consts for the rows whose bit is set; {0, mask::kMaskedRecency} for the others.  The bitmap covers n_rows.
+hipError_t launch_row_consts_masked(const double *norm_b, const int64_t *created, int64_t now_ticks, int64_t n_rows, const uint32_t *bitmap,
+                                    double2 *out, hipStream_t s);
+// Per query: buf[b][0 .. min(cnt[b], cap)) compacted in place to the entries mask::survivor_in_scope keeps; cnt[b] = their
+// number, or unchanged where cnt[b] > cap (the overflow signal stays).
+hipError_t launch_mask_survivors(const uint32_t *bitmap, int64_t n_clip, uint32_t *cnt, uint32_t cap, SelEntry *buf, int32_t B, hipStream_t s);
+// out (words, all written) = the set bits of bitmap with rank in [first, last) among its set bits.
+hipError_t launch_mask_part(const uint32_t *bitmap, int64_t words, const uint32_t *chunk_cnt, uint64_t first, uint64_t last, uint32_t *out,
+                            hipStream_t s);
+// The two-stage tail's trailers behind a masked screen: order_key = took, floor and flags kept.
+hipError_t launch_mask_trailers(orr_candidate *recs, int32_t B, int32_t kprime, int64_t took, hipStream_t s);
 
 }  // namespace orr

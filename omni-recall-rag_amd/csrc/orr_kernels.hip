@@ -1716,4 +1716,202 @@ hipError_t launch_scope_trailers(orr_candidate *recs, int32_t B, int32_t kprime,
     return hipGetLastError();
 }
 
+// ---- masked search (orr_search_batch_masked; the rules are orr_mask_plan.h's) -----------------------------------------------
+
+// One workgroup: n_clip = one past the position of the took-th set bit (1 <= took <= set bits) of a bitmap whose chunk counts
+// exist.  Thread t sums a contiguous run of chunks, thread 0 walks the 256 sums and then that run; the chunk found is scanned
+// the same way, four words per thread; scope::clip_word leaves the took-th bit as the highest of the last word.
+__global__ __launch_bounds__(256) void mask_clip_kernel(const uint32_t *__restrict__ bitmap, int64_t words, int32_t n_chunks,
+                                                        const uint32_t *__restrict__ chunk_cnt, uint32_t took, int64_t *__restrict__ n_clip)
+{
+    __shared__ uint32_t part[256];
+    __shared__ int32_t s_at;
+    __shared__ uint32_t s_before;
+    const int tid = threadIdx.x;
+    const int32_t per = (n_chunks + 255) / 256;
+    const int32_t c0 = min(n_chunks, tid * per), c1 = min(n_chunks, c0 + per);
+    uint32_t sum = 0;
+    for (int32_t c = c0; c < c1; ++c) sum += chunk_cnt[c];
+    part[tid] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t before = 0;
+        int t = 0;
+        while (t < 255 && before + part[t] < took) before += part[t++];
+        int32_t c = min(n_chunks - 1, t * per);
+        const int32_t c_end = min(n_chunks, c + per) - 1;
+        while (c < c_end && before + chunk_cnt[c] < took) before += chunk_cnt[c++];
+        s_at = c; s_before = before;
+    }
+    __syncthreads();
+    const int32_t chunk = s_at;
+    const int64_t w0 = (int64_t)chunk * kScopeChunkWords + (int64_t)tid * 4;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    if (w0 < words) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(bitmap + w0);
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    }
+    uint32_t before = s_before;
+    __syncthreads();                                   // (part and s_at are written again)
+    part[tid] = __popc(w[0]) + __popc(w[1]) + __popc(w[2]) + __popc(w[3]);
+    __syncthreads();
+    if (tid == 0) {
+        int t = 0;
+        while (t < 255 && before + part[t] < took) before += part[t++];
+        s_at = t; s_before = before;
+    }
+    __syncthreads();
+    if (tid != s_at) return;
+    before = s_before;
+    int64_t clip = words * 32;                         // (took beyond the set bits: every row)
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t c = __popc(w[k]);
+        if (c != 0u && before + c >= took) {
+            const uint32_t kept = scope::clip_word(w[k], (uint64_t)before, (uint64_t)took);
+            clip = (w0 + k) * 32 + (32 - __clz((int)kept));
+            break;
+        }
+        before += c;
+    }
+    *n_clip = clip;
+}
+
+hipError_t launch_mask_clip(const uint32_t *bitmap, int64_t words, const uint32_t *chunk_cnt, uint32_t took, int64_t *n_clip, hipStream_t s)
+{
+    if (words <= 0 || words % 4 != 0 || took == 0u) return hipErrorInvalidValue;
+    const int32_t n_chunks = scope_chunks(words);
+    hipLaunchKernelGGL(mask_clip_kernel, dim3(1), dim3(256), 0, s, bitmap, words, n_chunks, chunk_cnt, took, n_clip);
+    return hipGetLastError();
+}
+
+// launch_row_consts under a scope mask: a row whose bit is clear gets {0, mask::kMaskedRecency} -- no cosine part (x = 0 is the
+// "normB <= 0" case of every screen) and a recency term below every floor a query can have.  The sentinel is finite:
+// fused_epilogue16 turns non-finite row constants into "keep everything" and v_max3_f32 drops NaNs (orr_mask_plan.h has the
+// bound); what reaches a buffer in spite of it is removed by mask_survivors.
+__global__ __launch_bounds__(256) void row_consts_masked_kernel(const double *__restrict__ norm_b, const int64_t *__restrict__ created,
+                                                                int64_t now_ticks, int64_t n_rows, const uint32_t *__restrict__ bitmap,
+                                                                double2 *__restrict__ out)
+{
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rows; r += (int64_t)gridDim.x * blockDim.x) {
+        double2 o;
+        o.x = 0.0; o.y = mask::kMaskedRecency;
+        if ((bitmap[r >> 5] >> (r & 31)) & 1u) o = row_consts_of(norm_b[r], created[r], now_ticks);
+        out[r] = o;
+    }
+}
+
+hipError_t launch_row_consts_masked(const double *norm_b, const int64_t *created, int64_t now_ticks, int64_t n_rows, const uint32_t *bitmap,
+                                    double2 *out, hipStream_t s)
+{
+    if (n_rows <= 0) return hipSuccess;
+    const int64_t blocks = std::min<int64_t>((n_rows + 255) / 256, 2048);
+    hipLaunchKernelGGL(row_consts_masked_kernel, dim3((unsigned)blocks), dim3(256), 0, s, norm_b, created, now_ticks, n_rows, bitmap, out);
+    return hipGetLastError();
+}
+
+// Behind the screen, one workgroup per query: buf[b][0 .. min(cnt, cap)) compacted in place, in order, to the entries
+// mask::survivor_in_scope keeps.  Tiles of 256 entries: a tile is read before anything of it is written, and what a tile
+// writes lies in front of the next tile.  cnt[b] becomes the kept count, except where the buffer had overflowed: that count
+// stays (cnt > cap is the overflow signal of the tail's trailer, and the size the grown buffers are derived from).
+__global__ __launch_bounds__(256) void mask_survivors_kernel(const uint32_t *__restrict__ bitmap, int64_t n_clip, uint32_t *__restrict__ cnt,
+                                                             uint32_t cap, SelEntry *__restrict__ buf)
+{
+    __shared__ uint32_t wave_kept[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t c = cnt[b], n = c < cap ? c : cap;
+    SelEntry *mine = buf + (int64_t)b * cap;
+    uint32_t out = 0;
+    for (uint32_t base = 0; base < n; base += 256u) {
+        const uint32_t i = base + (uint32_t)tid;
+        SelEntry e;
+        e.key = 0ull; e.pos = 0u; e.pad = 0u;
+        bool keep = false;
+        if (i < n) {
+            e = mine[i];
+            keep = mask::survivor_in_scope(bitmap, e.pos, (uint64_t)n_clip);
+        }
+        const unsigned long long kept = __ballot(keep);
+        const uint32_t rank = (uint32_t)__popcll(kept & ((1ull << lane) - 1ull));
+        __syncthreads();                               // the tile is in registers; the last round's wave_kept has been read
+        if (lane == 0) wave_kept[wave] = (uint32_t)__popcll(kept);
+        __syncthreads();
+        uint32_t at = out + rank;
+        for (int k = 0; k < wave; ++k) at += wave_kept[k];
+        if (keep) mine[at] = e;
+        out += wave_kept[0] + wave_kept[1] + wave_kept[2] + wave_kept[3];
+    }
+    if (tid == 0) cnt[b] = c > cap ? c : out;
+}
+
+hipError_t launch_mask_survivors(const uint32_t *bitmap, int64_t n_clip, uint32_t *cnt, uint32_t cap, SelEntry *buf, int32_t B, hipStream_t s)
+{
+    if (B <= 0) return hipSuccess;
+    if (cap == 0u || n_clip < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mask_survivors_kernel, dim3((unsigned)B), dim3(256), 0, s, bitmap, n_clip, cnt, cap, buf);
+    return hipGetLastError();
+}
+
+// One part of the list path: out = the set bits of `bitmap` whose rank lies in [first, last) (mask::part_word), every word of
+// out written.  Workgroup per chunk, ranks as scope_compact_kernel forms them.
+__global__ __launch_bounds__(256) void mask_part_kernel(const uint32_t *__restrict__ bitmap, int64_t words, const uint32_t *__restrict__ chunk_cnt,
+                                                        uint64_t first, uint64_t last, uint32_t *__restrict__ out)
+{
+    __shared__ uint32_t sh4[4];
+    __shared__ uint32_t wave_base[4];
+    const int chunk = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t before = 0;
+    for (int c = tid; c < chunk; c += 256) before += chunk_cnt[c];
+    before = block_sum_u32(before, sh4);
+    const int64_t w0 = (int64_t)chunk * kScopeChunkWords + (int64_t)tid * 4;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    if (w0 < words) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(bitmap + w0);
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    }
+    const uint32_t own = __popc(w[0]) + __popc(w[1]) + __popc(w[2]) + __popc(w[3]);
+    uint32_t incl = own;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t o = (uint32_t)__shfl_up((int)incl, off, 64);
+        if (lane >= off) incl += o;
+    }
+    if (lane == 63) wave_base[wave] = incl;
+    __syncthreads();
+    uint64_t rank = (uint64_t)before + incl - own;
+    for (int k = 0; k < wave; ++k) rank += wave_base[k];
+    if (w0 >= words) return;
+    uint32_t o[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        o[k] = mask::part_word(w[k], rank, first, last);
+        rank += __popc(w[k]);
+    }
+    *reinterpret_cast<uint4 *>(out + w0) = make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+hipError_t launch_mask_part(const uint32_t *bitmap, int64_t words, const uint32_t *chunk_cnt, uint64_t first, uint64_t last, uint32_t *out,
+                            hipStream_t s)
+{
+    if (words <= 0 || words % 4 != 0 || last < first) return hipErrorInvalidValue;
+    const int32_t n_chunks = scope_chunks(words);
+    hipLaunchKernelGGL(mask_part_kernel, dim3((unsigned)n_chunks), dim3(256), 0, s, bitmap, words, chunk_cnt, first, last, out);
+    return hipGetLastError();
+}
+
+// The trailers the two-stage tail wrote behind a masked screen: the floor stays (ORR_CAND_TWO_STAGE, L in norm_b); the rows
+// that took part are the scope's first `took`.
+__global__ void mask_trailers_kernel(orr_candidate *recs, int32_t B, int32_t kprime, int64_t took)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    recs[(int64_t)b * ((int64_t)kprime + 1) + kprime].order_key = took;
+}
+
+hipError_t launch_mask_trailers(orr_candidate *recs, int32_t B, int32_t kprime, int64_t took, hipStream_t s)
+{
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(mask_trailers_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, recs, B, kprime, took);
+    return hipGetLastError();
+}
+
 }  // namespace orr

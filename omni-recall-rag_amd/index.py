@@ -285,6 +285,25 @@ class RecallIndex:
                                               _ptr(rows), _ptr(scores), _ptr(counts)))
         return rows, scores, counts
 
+    def search_masked(self, qvecs, queries_terms, now_ticks: int, topk: int, scope_ids, candidate_limit: int = 300):
+        """orr_search_batch_masked: every query ranks only the live rows whose id the ONE shared scope lists (a flat list,
+        numpy or torch, host or device) -- the results of search_scoped with a shared list, through a masked two-stage screen
+        that reads the shard once per batch; no limit on the size of the scope.  Returns (rows [B,k] int64, scores [B,k]
+        float64, counts [B] int32)."""
+        B = len(queries_terms)
+        dim, q, _keep = self._query_args(qvecs, B)
+        pool, toff, qoff = pack_terms(queries_terms)
+        ids = scope_ids if _is_torch(scope_ids) else np.ascontiguousarray(scope_ids, dtype=np.int64).reshape(-1)
+        n_ids = int(ids.shape[0])
+        k = max(1, int(topk))
+        rows = np.full((B, k), -1, dtype=np.int64)
+        scores = np.zeros((B, k), dtype=np.float64)
+        counts = np.zeros(B, dtype=np.int32)
+        N.check(N.hip.orr_search_batch_masked(self._h, B, dim, _ptr(q), _ptr(pool), _ptr(toff), _ptr(qoff), now_ticks, int(topk),
+                                              int(candidate_limit), n_ids, _ptr(ids) if n_ids else None,
+                                              _ptr(rows), _ptr(scores), _ptr(counts)))
+        return rows, scores, counts
+
     def search_shard_scoped(self, qvecs, queries_terms, now_ticks: int, kprime: int, candidate_limit: int, scope_ids,
                             scope_before=None, topk: int = 0, out=None):
         """orr_search_shard_scoped: this shard's [B, kprime+1] records of a scoped search (for merge_candidates).  scope_before
