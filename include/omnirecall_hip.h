@@ -454,6 +454,30 @@ int orr_index_screen_dots(orr_index *idx, int32_t B, int32_t dim, const float *q
 int orr_index_screen_i8_dots(orr_index *idx, int32_t B, int32_t dim, const float *q, int32_t form, int32_t nt_rows,
                              int32_t *out_dots, int8_t *out_iq, int8_t *out_ie);
 
+/* Diagnostics for the claims the screens' exactness rests on besides the GEMM's integers: every constant and every approximate
+ * dot that a certificate charges can be compared with a high-precision restatement (tests/test_gpu_screen_bounds.py).
+ * Out of scope: the kernels that exist in fused form only (the bf16 stream K2g and the one-product bf16x1 form), and running a
+ * fused epilogue with a floor of zero.
+ *
+ * orr_index_screen_i8_consts: what the int8 shadow holds per row -- out_scale / out_rel_err / out_rel_hat [rows] and
+ * out_rowf [rows][4] -- and, for the B given queries (B may be 0), what the searches' quantisation makes of them: out_s1 [B],
+ * out_err2 [B] (both int8 levels), out_err2_level1 [B] (the first level only: the screening GEMM's) and out_iq2 [B][dim], the
+ * second-level image (orr_index_screen_i8_dots returns the first).  Any output may be NULL.  dim % 128 == 0. */
+int orr_index_screen_i8_consts(orr_index *idx, int32_t B, int32_t dim, const float *q, float *out_scale, float *out_rel_err,
+                               float *out_rel_hat, float *out_rowf, float *out_s1, double *out_err2, double *out_err2_level1,
+                               int8_t *out_iq2);
+
+/* The RAW int32 accumulators of the streaming int8 screen (K2i), out_dots[B][2][orr_index_rows]: [b][0] = I1 (first query
+ * level), [b][1] = I2 (second level), for B = 1..4 queries, from the same K loop, prefetch, cross-lane reduction and grid as a
+ * search's launch; only the scoring tail is replaced by two stores.  unit16 = 0: the 128-row-unit form of the pass over all
+ * rows; 1: the 16-row-unit form of the sampled prefix, which needs dim % 1024 == 0 (ORR_EINVAL otherwise). */
+int orr_index_screen_i8_stream_dots(orr_index *idx, int32_t B, int32_t dim, const float *q, int32_t unit16, int32_t *out_dots);
+
+/* out[B][orr_index_rows] = the fp32 dots of one of the batched pass's kernels over the fp32 rows.  kernel 0: the streaming f32
+ * MFMA form (K2s), the queries sent in groups of 32 as the pass sends them (up to 16 queries and 17..32 run different kernels);
+ * kernel 1: the queries split into bf16 hi/lo halves, then the unfused three-product split-bf16 GEMM.  dim % 64 == 0. */
+int orr_index_pass_dots(orr_index *idx, int32_t kernel, int32_t B, int32_t dim, const float *q, float *out);
+
 /* ---- measurement ---------------------------------------------------------*/
 /* enabled: 0 off; 1 an event pair around every kernel; 2 only around the one launch per search that streams every row
  * (each pair costs a few microseconds of stream time, which a one-query search notices).  Also resets the counters. */

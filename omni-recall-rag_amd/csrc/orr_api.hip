@@ -1977,6 +1977,108 @@ int orr_index_screen_i8_dots(orr_index *idx, int32_t B, int32_t dim, const float
     return ORR_OK;
 }
 
+int orr_index_screen_i8_consts(orr_index *idx, int32_t B, int32_t dim, const float *q, float *out_scale, float *out_rel_err,
+                               float *out_rel_hat, float *out_rowf, float *out_s1, double *out_err2, double *out_err2_level1,
+                               int8_t *out_iq2)
+{
+    if (!idx || B < 0 || (B > 0 && !q)) return fail(ORR_EINVAL, "orr_index_screen_i8_consts: bad argument");
+    LanePool::Exclusive all(pool_of(idx));
+    std::lock_guard<std::mutex> lock(idx->mu);
+    if (!idx->sealed) return fail(ORR_ESTATE, "orr_index_screen_i8_consts: the index is not sealed");
+    if (dim != idx->dim || dim <= 0 || dim % 128 != 0) return fail(ORR_EINVAL, "orr_index_screen_i8_consts: dim must equal the index dimension and be a multiple of 128");
+    if (idx->n_rows <= 0) return ORR_OK;
+    HIP_TRY(hipSetDevice(idx->device));
+    ORR_TRY(ensure_i8_shadow(idx));
+    if (!idx->i8_ready) return fail(ORR_ENOMEM, "orr_index_screen_i8_consts: the int8 shadow does not fit in device memory");
+    hipStream_t s = idx->stream;
+    const size_t n = (size_t)idx->n_rows;
+    if (out_scale) HIP_TRY(hipMemcpyAsync(out_scale, idx->i8_scale.p, sizeof(float) * n, hipMemcpyDefault, s));
+    if (out_rel_err) HIP_TRY(hipMemcpyAsync(out_rel_err, idx->i8_rel_err.p, sizeof(float) * n, hipMemcpyDefault, s));
+    if (out_rel_hat) HIP_TRY(hipMemcpyAsync(out_rel_hat, idx->i8_rel_hat.p, sizeof(float) * n, hipMemcpyDefault, s));
+    if (out_rowf) HIP_TRY(hipMemcpyAsync(out_rowf, idx->i8_rowf.p, sizeof(float4) * n, hipMemcpyDefault, s));
+    if (B > 0) {
+        ORR_TRY(idx->ws_q.reserve(sizeof(float) * (size_t)B * dim));
+        ORR_TRY(idx->ws_q8.reserve(2 * (size_t)B * dim));
+        ORR_TRY(idx->ws_q8s1.reserve(sizeof(float) * (size_t)B));
+        ORR_TRY(idx->ws_q8err.reserve(2 * sizeof(double) * (size_t)B));
+        HIP_TRY(hipMemcpyAsync(idx->ws_q.p, q, sizeof(float) * (size_t)B * dim, hipMemcpyDefault, s));
+        // the quantisation the searches use: both int8 levels and both error terms
+        HIP_TRY(orr::launch_i8_queries(idx->ws_q.as<float>(), B, dim, idx->ws_q8.p, idx->ws_q8s1.as<float>(), idx->ws_q8err.as<double>(), s,
+                                       idx->ws_q8err.as<double>() + B));
+        if (out_s1) HIP_TRY(hipMemcpyAsync(out_s1, idx->ws_q8s1.p, sizeof(float) * (size_t)B, hipMemcpyDefault, s));
+        if (out_err2) HIP_TRY(hipMemcpyAsync(out_err2, idx->ws_q8err.p, sizeof(double) * (size_t)B, hipMemcpyDefault, s));
+        if (out_err2_level1) HIP_TRY(hipMemcpyAsync(out_err2_level1, idx->ws_q8err.as<double>() + B, sizeof(double) * (size_t)B, hipMemcpyDefault, s));
+        if (out_iq2) HIP_TRY(hipMemcpyAsync(out_iq2, static_cast<const int8_t *>(idx->ws_q8.p) + (size_t)B * dim, (size_t)B * dim, hipMemcpyDefault, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    return ORR_OK;
+}
+
+int orr_index_screen_i8_stream_dots(orr_index *idx, int32_t B, int32_t dim, const float *q, int32_t unit16, int32_t *out_dots)
+{
+    if (!idx || !q || !out_dots || B <= 0 || B > orr::kMaxI8ScreenQ) return fail(ORR_EINVAL, "orr_index_screen_i8_stream_dots: bad argument (1..4 queries)");
+    LanePool::Exclusive all(pool_of(idx));
+    std::lock_guard<std::mutex> lock(idx->mu);
+    if (!idx->sealed) return fail(ORR_ESTATE, "orr_index_screen_i8_stream_dots: the index is not sealed");
+    if (dim != idx->dim || dim <= 0 || dim % 128 != 0) return fail(ORR_EINVAL, "orr_index_screen_i8_stream_dots: dim must equal the index dimension and be a multiple of 128");
+    if (unit16 && dim % 1024 != 0) return fail(ORR_EINVAL, "orr_index_screen_i8_stream_dots: the 16-row-unit form needs dim % 1024 == 0");
+    if (idx->n_rows <= 0) return ORR_OK;
+    HIP_TRY(hipSetDevice(idx->device));
+    ORR_TRY(ensure_i8_shadow(idx));
+    if (!idx->i8_ready) return fail(ORR_ENOMEM, "orr_index_screen_i8_stream_dots: the int8 shadow does not fit in device memory");
+    hipStream_t s = idx->stream;
+    const size_t n = (size_t)idx->n_rows, bytes = sizeof(int32_t) * 2 * (size_t)B * n;
+    ORR_TRY(idx->ws_q.reserve(sizeof(float) * (size_t)B * dim));
+    ORR_TRY(idx->ws_q8.reserve(2 * (size_t)B * dim));
+    ORR_TRY(idx->ws_q8s1.reserve(sizeof(float) * (size_t)B));
+    ORR_TRY(idx->ws_q8err.reserve(2 * sizeof(double) * (size_t)B));
+    ORR_TRY(idx->ws_dotf.reserve(bytes));
+    HIP_TRY(hipMemcpyAsync(idx->ws_q.p, q, sizeof(float) * (size_t)B * dim, hipMemcpyDefault, s));
+    HIP_TRY(orr::launch_i8_queries(idx->ws_q.as<float>(), B, dim, idx->ws_q8.p, idx->ws_q8s1.as<float>(), idx->ws_q8err.as<double>(), s,
+                                   idx->ws_q8err.as<double>() + B));
+    HIP_TRY(hipMemsetAsync(idx->ws_dotf.p, 0xAB, bytes, s));                 // (an element the kernel never writes shows up as 0xABABABAB)
+    {
+        Timed t(idx, unit16 ? "screen_gemv_i8_dots_u16" : "screen_gemv_i8_dots_u128", 1.0 * (double)n * dim + 2.0 * (double)B * dim + 8.0 * (double)B * (double)n);
+        HIP_TRY(orr::launch_screen_gemv_i8_dots(idx->ws_q8.p, B, idx->emb_i8.p, idx->n_rows, dim, idx->ws_dotf.as<int32_t>(), unit16 != 0, s));
+    }
+    HIP_TRY(hipMemcpyAsync(out_dots, idx->ws_dotf.p, bytes, hipMemcpyDefault, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    collect_events(idx);
+    return ORR_OK;
+}
+
+int orr_index_pass_dots(orr_index *idx, int32_t kernel, int32_t B, int32_t dim, const float *q, float *out)
+{
+    if (!idx || !q || !out || B <= 0 || kernel < 0 || kernel > 1) return fail(ORR_EINVAL, "orr_index_pass_dots: bad argument");
+    LanePool::Exclusive all(pool_of(idx));
+    std::lock_guard<std::mutex> lock(idx->mu);
+    if (!idx->sealed) return fail(ORR_ESTATE, "orr_index_pass_dots: the index is not sealed");
+    if (dim != idx->dim || dim <= 0 || dim % 64 != 0) return fail(ORR_EINVAL, "orr_index_pass_dots: dim must equal the index dimension and be a multiple of 64");
+    if (idx->n_rows <= 0) return ORR_OK;
+    HIP_TRY(hipSetDevice(idx->device));
+    hipStream_t s = idx->stream;
+    const int64_t n = idx->n_rows;
+    ORR_TRY(idx->ws_q.reserve(sizeof(float) * (size_t)B * dim));
+    ORR_TRY(idx->ws_dotf.reserve(sizeof(float) * (size_t)B * (size_t)n));
+    HIP_TRY(hipMemcpyAsync(idx->ws_q.p, q, sizeof(float) * (size_t)B * dim, hipMemcpyDefault, s));
+    if (kernel == 0) {
+        for (int32_t b0 = 0; b0 < B; b0 += 32) {                               // groups of 32, as the pass sends them (launch_numerators)
+            const int32_t nq = std::min<int32_t>(32, B - b0);
+            Timed t(idx, "gemv_mfma", 4.0 * (double)n * dim + 4.0 * (double)nq * dim + 4.0 * (double)nq * (double)n);
+            HIP_TRY(orr::launch_gemv_mfma(idx->ws_q.as<float>() + (size_t)b0 * dim, nq, idx->d_emb, n, dim, idx->ws_dotf.as<float>() + (size_t)b0 * n, n, s));
+        }
+    } else {
+        ORR_TRY(idx->ws_qsplit.reserve(sizeof(float) * (size_t)B * dim));
+        HIP_TRY(orr::launch_split_queries(idx->ws_q.as<float>(), B, dim, idx->ws_qsplit.p, s));
+        Timed t(idx, "gemm_dot_bf16x3", 4.0 * (double)n * dim + 4.0 * (double)B * dim + 4.0 * (double)B * (double)n);
+        HIP_TRY(orr::launch_gemm_dot_bf16x3(idx->ws_qsplit.p, B, idx->d_emb, 0, n, dim, idx->ws_dotf.as<float>(), n, nullptr, 3, s));
+    }
+    HIP_TRY(hipMemcpyAsync(out, idx->ws_dotf.p, sizeof(float) * (size_t)B * (size_t)n, hipMemcpyDefault, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    collect_events(idx);
+    return ORR_OK;
+}
+
 int orr_index_set_profiling(orr_index *idx, int32_t enabled)
 {
     if (!idx) return fail(ORR_EINVAL, "null index");
@@ -2407,6 +2509,11 @@ constexpr int kRetryPass = 1;          // run_shard_once: a workspace was too sm
 //               residuals of the split (u = 2^-8 per bf16 rounding) -> 3.1 u^2 + 3.06 D 2^-23
 //   plain bf16  (1 + u)^2 - 1 per product, D additions charged 2^-23 each -> 2^-7 (1 + 2^-9) + 1.02 D 2^-23
 // The int8 forms add their per-pair bound inside the kernels: the keys they leave are already lower bounds (kEpsI8).
+// All three charge the reference's fp32 products a RELATIVE error, which holds while those products are normal numbers.  The
+// int8 forms hand rows with 0 < normB < 2^-96 and queries with 0 < max|q| < 2^-48 to the exact pass (orr_screen.hip,
+// kI8MinNormB).  These three have no per-row never-drop value: a host-resident batch that holds such a query takes the exact
+// pass (plan_form, has_tiny_query; without it the bf16 shadow and the in-kernel bf16 conversion lose a winner whose products
+// are subnormal, tests/test_gpu_screen_bounds.py); rows that small, and such queries in device memory, stay out of contract.
 constexpr double kU23 = 1.1920928955078125e-07, kU16 = 1.52587890625e-05;
 constexpr double kEpsI8 = 1e-12;
 double cosine_bound(double eps_cos) { return 0.7 * 1.01 * eps_cos + 1e-12; }
@@ -2460,6 +2567,18 @@ struct PassPlan {
     int pass_mode() const { static constexpr int kMode[] = {0, 1, 1, 2, 2, 3}; return masked ? 5 : kMode[(int)screen]; }   // orr_search_stats
 };
 
+// Whether a host-resident batch holds a query whose largest coordinate is positive and below 2^-48: its products with the rows
+// are subnormal in fp32, where the relative product error that cosine_bound charges does not hold (see the eps table above).
+static bool has_tiny_query(const float *q, int32_t B, int32_t D)
+{
+    for (int32_t b = 0; b < B; ++b) {
+        float mx = 0.f;
+        for (int32_t k = 0; k < D; ++k) mx = std::max(mx, std::fabs(q[(size_t)b * D + k]));
+        if (mx > 0.f && mx < 0x1p-48f) return true;
+    }
+    return false;
+}
+
 // Decides the form of one pass and what it derives, building the shadows it reads.
 int plan_form(orr_index *idx, const BatchArgs &a, int32_t kprime, int64_t n, const std::vector<uint32_t> &qoff, PassPlan &p)
 {
@@ -2469,10 +2588,14 @@ int plan_form(orr_index *idx, const BatchArgs &a, int32_t kprime, int64_t n, con
     const bool floor_fits = !a.no_fuse && n_seg_all >= 48 && std::max<int32_t>(1, a.topk) <= orr::kSelWidth;
     p = PassPlan{};
     p.use_cos = a.dim > 0 && a.dim == D;
+    p.q_on_device = p.use_cos && is_device_pointer(a.q);
+    // the forms without the int8 shadow's per-pair bound have no way to keep such a query's pairs: the exact pass takes the batch
+    const bool force_exact = a.force_exact || (p.use_cos && (idx->opt_two_stage != 1 || D % 128 != 0) && !p.q_on_device &&
+                                               has_tiny_query(a.q, B, D));
     // 1..8 queries over a large shard with a shadow in place: the streaming form of the two-stage pass
     // (stream over a sampled prefix -> floor, stream over all rows -> survivors, exact re-score)
     bool stream = false, stream_i8 = false;
-    if (p.use_cos && !a.force_exact && idx->opt_two_stage == 1 && D % 64 == 0 && small_k && floor_fits && B <= orr::kMaxGemvScreenQ) {
+    if (p.use_cos && !force_exact && idx->opt_two_stage == 1 && D % 64 == 0 && small_k && floor_fits && B <= orr::kMaxGemvScreenQ) {
         ORR_TRY(ensure_i8_shadow(idx));
         stream_i8 = idx->i8_ready;
         if (!stream_i8) ORR_TRY(ensure_shadow(idx));
@@ -2483,8 +2606,7 @@ int plan_form(orr_index *idx, const BatchArgs &a, int32_t kprime, int64_t n, con
     }
     // Batched candidate pass on the matrix cores (K2) + exact re-score (K6) from 5 queries up; below it the HBM-bound exact
     // kernel is as fast and needs no second pass.
-    p.use_mfma = p.use_cos && !a.force_exact && (B >= 5 || stream) && D % 64 == 0 && small_k;
-    p.q_on_device = p.use_cos && is_device_pointer(a.q);
+    p.use_mfma = p.use_cos && !force_exact && (B >= 5 || stream) && D % 64 == 0 && small_k;
     // Queries that already live on the device get their exact norms there (a handful of queries: the download and the
     // host's pass cost less than the kernel's 3072-step chains).  The generic large-k path scores with host-side constants.
     p.dev_norms = p.q_on_device && small_k && B >= 16 && !a.norms_host;

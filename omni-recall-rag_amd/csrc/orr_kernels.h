@@ -300,6 +300,10 @@ hipError_t launch_screen_gemv_i8(const void *q12, const float *s1, const double 
                                  const float *scale, const float *rel_err, const float *rel_hat, const double *norm_b,
                                  const int64_t *created, int64_t now_ticks, int64_t n_rows, int32_t D,
                                  const FusedEpilogue &epi, bool lower_bound, hipStream_t s);
+// Diagnostic: the raw accumulators of the same kernel, S[b][0][r] = I1 and S[b][1][r] = I2 for 1..kMaxI8ScreenQ queries, in the
+// 16-row-unit form of the sampled prefix (fine; D % 1024 == 0) or the 128-row-unit form of the pass over all rows.
+hipError_t launch_screen_gemv_i8_dots(const void *q12, int32_t B, const void *tiled, int64_t n_rows, int32_t D, int32_t *S, bool fine,
+                                      hipStream_t s);
 // K2j: the screening GEMM on the int8 shadow (v_mfma_i32_32x32x32_i8: twice the bf16 rate, half its bytes).
 // Queries: ONE int8 level (q1 of launch_i8_queries, err2_l1), tiled like the rows; epi must carry i8_rowf / i8_qs1.
 hipError_t launch_i8_rowf(const float *scale, const float *rel_err, const float *rel_hat, int64_t n_rows, float4 *rowf, hipStream_t s);

@@ -1094,13 +1094,16 @@ struct I8Queries {
 // 34 -> 12 us, and that launch is on the critical path of a one-query search).
 // LISTS (with JR = 1 and floor keys of 0: the sampled prefix): a workgroup's 64 rows per query leave as one sorted list
 // buf[b][64 l .. 64 l + 63], l = unit / 4, what buffer_to_lists would make of them -- no counters, no second launch.
-template <int NQ, bool LOWER, int JR, bool LISTS = false>
+// DOTS (diagnostic, orr_index_screen_i8_stream_dots): no scoring tail -- the two raw int32 accumulators of every pair go to
+// the int32 array [NQ][2][n_rows] that epi.buf then points to; nothing else of R, Q.s1, Q.err2 or epi is read.
+template <int NQ, bool LOWER, int JR, bool LISTS = false, bool DOTS = false>
 __global__ __launch_bounds__(256, 2) void screen_gemv_i8_kernel(I8Queries Q, int32_t D, I8Rows R, int64_t n_units, int64_t n_rows,
                                                                 FusedEpilogue epi)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lq[];     // [2][NQ][D] int8
     __shared__ SelEntry own[LISTS ? NQ : 1][kSelWidth];
     static_assert(!LISTS || JR == 1, "LISTS: one 16-row group per wave");
+    static_assert(!DOTS || !LISTS, "DOTS: stores only");
     constexpr int KS = 8 / JR;                     // k-tiles per stage
     constexpr int UPT = 16 / JR;                   // units per 256-row tile
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1151,6 +1154,11 @@ __global__ __launch_bounds__(256, 2) void screen_gemv_i8_kernel(I8Queries Q, int
                 a2[b][j] += __shfl_xor(a2[b][j], 1, 64); a2[b][j] += __shfl_xor(a2[b][j], 2, 64);
             }
         const int sl = lane & 3;
+// this lane's pair of accumulators of query b: lane sl of a quad holds the sums of 16-row group jj * 4 + sl
+#define ORR_PICK_I12(i1, i2, b) \
+        int i1 = a1[b][jj * 4], i2 = a2[b][jj * 4]; \
+        _Pragma("unroll") for (int t = 1; t < 4; ++t) \
+            if (jj * 4 + t < JR && sl == t) { i1 = a1[b][jj * 4 + t < JR ? jj * 4 + t : 0]; i2 = a2[b][jj * 4 + t < JR ? jj * 4 + t : 0]; }
 #pragma unroll
         for (int jj = 0; jj < (JR + 3) / 4; ++jj) {
             if (jj * 4 + sl >= JR) continue;
@@ -1162,14 +1170,21 @@ __global__ __launch_bounds__(256, 2) void screen_gemv_i8_kernel(I8Queries Q, int
                 }
                 continue;
             }
+            if (DOTS) {
+                int32_t *S = reinterpret_cast<int32_t *>(epi.buf);
+#pragma unroll
+                for (int b = 0; b < NQ; ++b) {
+                    ORR_PICK_I12(i1, i2, b)
+                    S[(int64_t)(2 * b) * n_rows + row] = i1;
+                    S[(int64_t)(2 * b + 1) * n_rows + row] = i2;
+                }
+                continue;
+            }
             const double2 rc = R.norm_b ? row_consts_of(R.norm_b[row], R.created[row], R.now_ticks) : epi.rowc[row];
             const double se = (double)R.scale[row], re = (double)R.rel_err[row], rh = (double)R.rel_hat[row];
 #pragma unroll
             for (int b = 0; b < NQ; ++b) {
-                int i1 = a1[b][jj * 4], i2 = a2[b][jj * 4];
-#pragma unroll
-                for (int t = 1; t < 4; ++t)
-                    if (jj * 4 + t < JR && sl == t) { i1 = a1[b][jj * 4 + t < JR ? jj * 4 + t : 0]; i2 = a2[b][jj * 4 + t < JR ? jj * 4 + t : 0]; }
+                ORR_PICK_I12(i1, i2, b)
                 const QueryConst qc = epi.qc[b];
                 const double dot = se * (double)Q.s1[b] * ((double)i1 + (double)i2 * (1.0 / 254.0));
                 // |cos error| <= (|q|/sqrt(normA)) re + (|q - q^|/sqrt(normA)) rh ; the first factor is 1 up to 2^-23
@@ -1194,6 +1209,7 @@ __global__ __launch_bounds__(256, 2) void screen_gemv_i8_kernel(I8Queries Q, int
                 }
             }
         }
+#undef ORR_PICK_I12
         if (LISTS) {                               // (n_units is a multiple of 4: a workgroup's waves leave the loop together)
             __syncthreads();
             if (wave < NQ) {
@@ -1263,11 +1279,21 @@ __device__ __forceinline__ I8Row i8_quantise_row(const float *__restrict__ src, 
     return r;
 }
 
+// Below these the screen's bound no longer covers the reference's own arithmetic, and a row or a query is handed to the exact
+// pass instead.  The bound charges the reference's fp32 products fl32(q_k e_k) a RELATIVE rounding error (the 1.2e-7 of
+// screen_gemv_i8_kernel, the 2.4e-7 of i8_rowf_of), which holds only while the products are normal numbers: a subnormal
+// product is off by up to 2^-150 absolutely, whatever its size (rows of equal magnitude 3e-21 against themselves: the
+// reference's cosine is off by up to 580 times the bound).  With normB >= 2^-96 and max|q| >= 2^-48 the cosine's denominator is
+// sqrt(normA) sqrt(normB) >= 2^-96 (1 - 2^-23); the D products' underflow errors sum to at most D 2^-150, on the cosine
+// D 2^-54 = 1.7e-13 at D = 3072: inside the bound's + 1e-9.
+constexpr double kI8MinNormB = 0x1p-96;     // rows: 0 < normB below this -> rel_err = +inf (never screened out)
+constexpr float kI8MinQueryMax = 0x1p-48f;  // queries: 0 < max|q| below this -> err2 = +inf (every pair passes)
+
 // The two relative norms the bound needs, from a row's quantisation and its exact norm nb.
 __device__ __forceinline__ void i8_rel_norms(const I8Row &q, double nb, float &rel_err, float &rel_hat)
 {
     if (!(nb > 0.0)) { rel_err = 0.f; rel_hat = 0.f; }                      // cosine is 0 for this row whatever the dot (:84)
-    else if (q.bad) { rel_err = __builtin_huge_valf(); rel_hat = 0.f; }      // never screened out
+    else if (q.bad || nb < kI8MinNormB) { rel_err = __builtin_huge_valf(); rel_hat = 0.f; }      // never screened out
     else {
         rel_err = __double2float_ru(sqrt(q.d2 / nb) * 1.000001);
         rel_hat = __double2float_ru(sqrt(q.h2 / nb) * 1.000001);
@@ -1325,8 +1351,8 @@ __global__ __launch_bounds__(256) void i8_queries_kernel(const float *__restrict
     for (int k = tid; k < D; k += 256) { const float v = q[k]; mx = fmaxf(mx, fabsf(v)); bad = bad || !(fabsf(v) <= 3.4028234663852886e38f); }
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d, 64));
-    if (lane == 0) red_f[wave] = (__any(bad) ? __builtin_huge_valf() : mx);
-    bad = __any(bad);
+    bad = __any(bad);                                                          // (by the whole wave: inside the branch below only lane 0 would vote)
+    if (lane == 0) red_f[wave] = (bad ? __builtin_huge_valf() : mx);
     __syncthreads();
     mx = fmaxf(fmaxf(red_f[0], red_f[1]), fmaxf(red_f[2], red_f[3]));
     const bool usable = mx > 0.f && mx <= 3.4028234663852886e38f;
@@ -1353,8 +1379,9 @@ __global__ __launch_bounds__(256) void i8_queries_kernel(const float *__restrict
         s1_out[b] = s1;
         const double tot = red_d[0] + red_d[1] + red_d[2] + red_d[3];
         const double tot1 = red_d1[0] + red_d1[1] + red_d1[2] + red_d1[3];
-        err2_out[b] = (mx <= 3.4028234663852886e38f) ? tot * 1.000001 : __builtin_huge_val();
-        if (err2_l1_out) err2_l1_out[b] = (mx <= 3.4028234663852886e38f) ? tot1 * 1.000001 : __builtin_huge_val();
+        const bool bounded = mx <= 3.4028234663852886e38f && !(mx > 0.f && mx < kI8MinQueryMax);   // (see kI8MinQueryMax)
+        err2_out[b] = bounded ? tot * 1.000001 : __builtin_huge_val();
+        if (err2_l1_out) err2_l1_out[b] = bounded ? tot1 * 1.000001 : __builtin_huge_val();
     }
 }
 
@@ -1755,6 +1782,14 @@ hipError_t launch_i8_queries(const float *Q, int32_t B, int32_t D, void *q12, fl
 // int32 accumulators per query and row).  lower_bound = true: keys are score - bound (prefix floor).
 bool screen_gemv_i8_prefix_makes_lists(int32_t D) { return D % 1024 == 0; }
 
+// Units of work and workgroups of one launch of the streaming int8 screen: 16-row units (fine) or 128-row units.
+static void screen_gemv_i8_grid(int64_t n_rows, bool fine, int64_t &n_units, int64_t &blocks)
+{
+    const int64_t tiles = (n_rows + kScBN - 1) / kScBN;
+    n_units = tiles * (fine ? 16 : 2);
+    blocks = std::min<int64_t>((n_units + 3) / 4, 512);
+}
+
 hipError_t launch_screen_gemv_i8(const void *q12, const float *s1, const double *err2, int32_t B, const void *tiled,
                                  const float *scale, const float *rel_err, const float *rel_hat, const double *norm_b,
                                  const int64_t *created, int64_t now_ticks, int64_t n_rows, int32_t D,
@@ -1765,9 +1800,8 @@ hipError_t launch_screen_gemv_i8(const void *q12, const float *s1, const double 
     // the sampled prefix (lower_bound) is a few thousand rows on the critical path of the call: 16-row units spread it over
     // hundreds of waves; the pass over all rows streams 128-row units
     const bool fine = lower_bound && screen_gemv_i8_prefix_makes_lists(D);    // sorted lists of 64 into epi.buf (floor keys must be 0)
-    const int64_t tiles = (n_rows + kScBN - 1) / kScBN;
-    const int64_t n_units = tiles * (fine ? 16 : 2);
-    const int64_t blocks = std::min<int64_t>((n_units + 3) / 4, 512);
+    int64_t n_units, blocks;
+    screen_gemv_i8_grid(n_rows, fine, n_units, blocks);
     const int8_t *q1 = static_cast<const int8_t *>(q12), *q2 = q1 + (size_t)B * D;
     I8Rows Rd{static_cast<const int8_t *>(tiled), scale, rel_err, rel_hat, norm_b, created, now_ticks};
     for (int32_t b0 = 0; b0 < B; b0 += kMaxI8ScreenQ) {
@@ -1792,6 +1826,36 @@ hipError_t launch_screen_gemv_i8(const void *q12, const float *s1, const double 
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// Diagnostic (orr_index_screen_i8_stream_dots): S[b][0][r] = I1, S[b][1][r] = I2, the RAW int32 accumulators of the streaming
+// int8 screen for 1..kMaxI8ScreenQ queries over rows [0, n_rows), from the same K loop, clamped prefetch, cross-lane
+// reduction and grid as launch_screen_gemv_i8 (only the scoring tail is replaced by two stores).  fine: the 16-row-unit form
+// of the sampled prefix (D % 1024 == 0), else the 128-row-unit form of the pass over all rows.
+hipError_t launch_screen_gemv_i8_dots(const void *q12, int32_t B, const void *tiled, int64_t n_rows, int32_t D, int32_t *S, bool fine,
+                                      hipStream_t s)
+{
+    if (B <= 0 || n_rows <= 0) return hipSuccess;
+    if (B > kMaxI8ScreenQ || D <= 0 || D % 128 != 0 || !S || (fine && !screen_gemv_i8_prefix_makes_lists(D))) return hipErrorInvalidValue;
+    int64_t n_units, blocks;
+    screen_gemv_i8_grid(n_rows, fine, n_units, blocks);
+    const size_t lds = 2 * (size_t)B * (size_t)D;
+    if (lds > 65536) return hipErrorInvalidValue;
+    const int8_t *q1 = static_cast<const int8_t *>(q12), *q2 = q1 + (size_t)B * D;
+    I8Rows Rd{static_cast<const int8_t *>(tiled), nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+    I8Queries Qd{q1, q2, nullptr, nullptr};
+    FusedEpilogue e2{};
+    e2.buf = reinterpret_cast<SelEntry *>(S);
+#define ORR_I8D(NQ) do { if (fine) hipLaunchKernelGGL((screen_gemv_i8_kernel<NQ, true, 1, false, true>), dim3((unsigned)blocks), dim3(256), lds, s, Qd, D, Rd, n_units, n_rows, e2); \
+                         else hipLaunchKernelGGL((screen_gemv_i8_kernel<NQ, false, 8, false, true>), dim3((unsigned)blocks), dim3(256), lds, s, Qd, D, Rd, n_units, n_rows, e2); } while (0)
+    switch (B) {
+    case 1: ORR_I8D(1); break;
+    case 2: ORR_I8D(2); break;
+    case 3: ORR_I8D(3); break;
+    default: ORR_I8D(4); break;
+    }
+#undef ORR_I8D
+    return hipGetLastError();
 }
 
 // The screening pass for B <= kMaxGemvScreenQ queries: q_hi is the linear [B][D] bf16 image (hi halves of

@@ -361,6 +361,42 @@ class RecallIndex:
         N.check(N.hip.orr_index_screen_i8_dots(self._h, B, dim, _ptr(q), int(form), 1 if nt_rows else 0, _ptr(dots), _ptr(iq), _ptr(ie)))
         return dots, iq, ie
 
+    def screen_i8_consts(self, qvecs=None) -> dict:
+        """orr_index_screen_i8_consts: the int8 shadow's row constants (scale, rel_err, rel_hat [rows]; rowf [rows, 4]) and, with
+        queries, their quantisation's (s1 [B] fp32; err2, err2_level1 [B] fp64; iq2 [B, dim], the second int8 level)."""
+        n = self.rows
+        out = {"scale": np.empty(n, np.float32), "rel_err": np.empty(n, np.float32), "rel_hat": np.empty(n, np.float32),
+               "rowf": np.empty((n, 4), np.float32)}
+        B, dim, q = 0, self.dim, None
+        if qvecs is not None:
+            q = np.ascontiguousarray(qvecs, dtype=np.float32)
+            q = q.reshape(1, -1) if q.ndim == 1 else q
+            B, dim = int(q.shape[0]), int(q.shape[1])
+            out.update(s1=np.empty(B, np.float32), err2=np.empty(B, np.float64), err2_level1=np.empty(B, np.float64),
+                       iq2=np.empty((B, dim), np.int8))
+        N.check(N.hip.orr_index_screen_i8_consts(self._h, B, dim, _ptr(q), _ptr(out["scale"]), _ptr(out["rel_err"]), _ptr(out["rel_hat"]),
+                                                 _ptr(out["rowf"]), _ptr(out.get("s1")), _ptr(out.get("err2")),
+                                                 _ptr(out.get("err2_level1")), _ptr(out.get("iq2"))))
+        return out
+
+    def screen_i8_stream_dots(self, qvecs, unit16: bool = False) -> np.ndarray:
+        """orr_index_screen_i8_stream_dots: raw int32 accumulators [B, 2, rows] (I1, I2) of the streaming int8 screen for 1..4
+        queries, in its 128-row-unit form or (unit16, dim % 1024 == 0) its 16-row-unit form."""
+        q = np.ascontiguousarray(qvecs, dtype=np.float32)
+        q = q.reshape(1, -1) if q.ndim == 1 else q
+        out = np.empty((q.shape[0], 2, self.rows), dtype=np.int32)
+        N.check(N.hip.orr_index_screen_i8_stream_dots(self._h, int(q.shape[0]), int(q.shape[1]), _ptr(q), 1 if unit16 else 0, _ptr(out)))
+        return out
+
+    def pass_dots(self, qvecs, kernel: int) -> np.ndarray:
+        """orr_index_pass_dots: fp32 dots [B, rows] of the batched pass's streaming f32 MFMA form (kernel 0) or of the unfused
+        split-bf16 GEMM with three products (kernel 1)."""
+        q = np.ascontiguousarray(qvecs, dtype=np.float32)
+        q = q.reshape(1, -1) if q.ndim == 1 else q
+        out = np.empty((q.shape[0], self.rows), dtype=np.float32)
+        N.check(N.hip.orr_index_pass_dots(self._h, int(kernel), int(q.shape[0]), int(q.shape[1]), _ptr(q), _ptr(out)))
+        return out
+
     def set_profiling(self, on) -> None:
         """False/0 off, True/1 every kernel, 2 only the launch that streams every row (orr_index_set_profiling)."""
         N.check(N.hip.orr_index_set_profiling(self._h, int(on)))

@@ -421,6 +421,10 @@ def test_insert_into_a_two_stage_shard_equals_a_fresh_shard(dim):
         d2, iq2, ie2 = fresh.screen_i8_dots(qs[:8], 0, images=True)
         assert np.array_equal(ie1, ie2), "int8 row images differ at rows %s" % np.nonzero((ie1 != ie2).any(1))[0][:10]
         assert np.array_equal(d1, d2)
+        c1, c2 = idx.screen_i8_consts(), fresh.screen_i8_consts()             # the bound's row constants, bit for bit
+        for name in ("scale", "rel_err", "rel_hat", "rowf"):
+            differ = np.nonzero((c1[name].view(np.uint32) != c2[name].view(np.uint32)).reshape(n + m, -1).any(1))[0]
+            assert differ.size == 0, f"{name} differs from a fresh shard's at rows {differ[:10]}"
     else:
         assert np.array_equal(idx.screen_dots(qs[:8]), fresh.screen_dots(qs[:8]), equal_nan=True)
     for B in (1, 8, 200):

@@ -227,6 +227,11 @@ def test_update_two_stage_shard_equals_a_fresh_shard(dim, tmp_path):
             assert np.array_equal(ie1, ie2), f"form {form}: int8 images differ at rows {np.nonzero((ie1 != ie2).any(1))[0][:10]}"
             assert np.array_equal(d1, d2), f"form {form}: accumulators differ"
         assert np.array_equal(ie1[upd], _quantise_rows(new[upd]))
+        # the row constants of the bound (the saved file does not hold them): what update_rows_kernel wrote against the shadow build
+        c1, c2 = idx.screen_i8_consts(), fresh.screen_i8_consts()
+        for name in ("scale", "rel_err", "rel_hat", "rowf"):
+            differ = np.nonzero((c1[name].view(np.uint32) != c2[name].view(np.uint32)).reshape(n, -1).any(1))[0]
+            assert differ.size == 0, f"{name} differs from a fresh shard's at rows {differ[:10]}"
     s1, s2 = idx.screen_dots(qs[:8]), fresh.screen_dots(qs[:8])
     assert np.array_equal(s1, s2, equal_nan=True)
 
