@@ -122,7 +122,8 @@ typedef struct orr_search_stats {
                                     did not fit in device memory and "two_stage" = 1 fell back); 4 scoped pass
                                     (orr_search_batch_scoped: no screen, the listed rows re-scored exactly; also the list path
                                     of orr_search_batch_masked); 5 two-stage screen under a scope mask
-                                    (orr_search_batch_masked)                                                            */
+                                    (orr_search_batch_masked); 6 two-stage screen under the masks of several groups at
+                                    once (orr_search_batch_masked_groups; 4 or 5 where a group's own path ran last)        */
     int64_t reserved[1];         /* orr_cluster_search_stats: record exchanges done by RCCL all-gather ("exchange" = 1)      */
 } orr_search_stats;
 
@@ -398,6 +399,36 @@ int orr_search_batch_masked(orr_index *idx, int32_t B, int32_t dim, const float 
                             int64_t now_ticks, int32_t topk, int64_t candidate_limit,
                             int64_t n_scope_ids, const int64_t *scope_ids,
                             int64_t *out_rows, double *out_scores, int32_t *out_counts);
+
+/* ---- grouped masked search: several large scopes share one screening pass ----
+ * Requests that arrive together belong to different tenants, collections or time windows: G scopes, each shared by the queries
+ * that name it.  Group g's ids are scope_ids[group_off[g] .. group_off[g + 1]) (scope_ids host or device memory; group_off
+ * host memory, n_groups + 1 entries); query b searches inside group query_group[b] (host memory, B entries).
+ * Query b's result is exactly what orr_search_batch_masked returns for that query with group query_group[b]'s ids as the
+ * scope -- what orr_search_batch would return on a shard sealed from only the live rows of that group: rows, order and fp64
+ * scores bit for bit.  candidate_limit counts each group's own scoped live rows; ids (unknown, deleted, listed twice, carried
+ * by several rows), an empty group (counts of 0), topk, dim, NaN order and ties are as documented for the masked call.  Groups
+ * may overlap, may be equal, may be empty, and may be named by no query.
+ * What differs is the cost.  A masked call per group streams the shard's shadow once per GROUP; this call streams it once per
+ * BATCH: the groups large enough to screen (more rows than their in-scope sample) run through ONE two-stage pass whose row
+ * constants admit every such group's rows, whose floor comes per query from a sample of its own group, and whose survivors are
+ * filtered per query against its own group's bitmap and clip (pass_mode 6).  Smaller groups, groups of a batch in which the
+ * grouped pass is not eligible or does not pay ("mask_screen": 0 by the summed cost rule -- the sum over the screening groups
+ * of max(max(4 x queries of the group, 128) x scoped rows, 524,288) >= rows in front of the last group's last row --, 1
+ * whenever eligible, 2 never), and queries the grouped pass cannot certify run as a masked call of their group (pass_mode 5
+ * or 4).  One used group (named by a query, with a live row) IS the masked call.  A buffer growth of the grouped pass is the
+ * call's own: it counts in buffer_growths and leaves survivor_capacity alone.
+ * ORR_EINVAL before any device call, with the outputs untouched: the masked call's argument errors, n_groups outside 1 .. 64
+ * (a stated cap: the group bitmaps take n_groups x rows / 8 bytes), group_off or query_group NULL, offsets that do not start at
+ * 0, decrease, or do not end at n_scope_ids, a query_group[b] outside [0, n_groups).
+ * The call is a search: it takes a lane, runs beside other searches, works on views and counts in orr_search_stats. */
+int orr_search_batch_masked_groups(orr_index *idx, int32_t B, int32_t dim, const float *q,
+                                   const uint8_t *terms_utf8, const uint32_t *term_off, const uint32_t *query_term_off,
+                                   int64_t now_ticks, int32_t topk, int64_t candidate_limit,
+                                   int32_t n_groups, int64_t n_scope_ids, const int64_t *scope_ids,
+                                   const uint64_t *group_off /* host [n_groups + 1] */,
+                                   const int32_t *query_group /* host [B] */,
+                                   int64_t *out_rows, double *out_scores, int32_t *out_counts);
 
 /* out_live[B] (host memory): the live rows query b's scope resolves to on this shard. */
 int orr_index_scope_count(orr_index *idx, int32_t B, int64_t n_scope_ids, const int64_t *scope_ids,

@@ -37,6 +37,7 @@
 #include "orr_lanes.h"
 #include "orr_scope_plan.h"
 #include "orr_mask_plan.h"
+#include "orr_group_plan.h"
 #include "orr_token_index.h"
 
 namespace {
@@ -220,6 +221,10 @@ struct orr_index {
     // parts rewrites ws_scope_bm per part), the sample's counts and the zeros that select the one bitmap, n_clip and the sample's sizes
     DevBuf ws_mask_bm, ws_mask_chunks, ws_mask_cnt, ws_mask_meta;
     PinnedBuf pin_mask;
+    // grouped masked search (orr_search_batch_masked_groups), a lane's: the call's G bitmaps and their chunk counts (a group's
+    // own masked call rewrites ws_scope_bm and ws_mask_bm), the groups' clips and samples; pinned: the clips as mask_clip leaves them
+    DevBuf ws_group_bm, ws_group_chunks, ws_group_meta;
+    PinnedBuf pin_group;
     int opt_mask_screen = 0;           // "mask_screen": 0 by the cost rule, 1 whenever eligible, 2 never (orr_mask_plan.h)
     int64_t opt_mask_part_rows = mask::kDefaultPartRows;   // "mask_part_rows": scoped rows per part of the list path
 
@@ -698,6 +703,8 @@ void orr_index_destroy(orr_index *idx)
     idx->pin_scope.release(); idx->pin_scope_pass.release();
     for (DevBuf *b : {&idx->ws_mask_bm, &idx->ws_mask_chunks, &idx->ws_mask_cnt, &idx->ws_mask_meta}) b->release();
     idx->pin_mask.release();
+    for (DevBuf *b : {&idx->ws_group_bm, &idx->ws_group_chunks, &idx->ws_group_meta}) b->release();
+    idx->pin_group.release();
     DevBuf *bufs[] = {&idx->ws_q, &idx->ws_dot, &idx->ws_dotf, &idx->ws_rowc, &idx->ws_tau, &idx->ws_qsplit, &idx->ws_fcnt,
                       &idx->ws_fbuf, &idx->ws_fqf, &idx->ws_fany, &idx->ws_tsL, &idx->ws_tskey, &idx->ws_qtiled, &idx->ws_fdot, &idx->ws_pbuf, &idx->ws_psel, &idx->ws_q8, &idx->ws_q8s1, &idx->ws_q8err, &idx->ws_zero, &idx->ws_sel, &idx->ws_cand, &idx->ws_qc, &idx->ws_keys_a, &idx->ws_keys_b,
                       &idx->ws_vals_a, &idx->ws_vals_b, &idx->ws_sort_tmp, &idx->ws_raw, &idx->ws_src_start, &idx->ws_qsub,
@@ -2557,6 +2564,7 @@ struct PassPlan {
     double approx_eps = 0.0;        // bound of the approximate scores of the batched pass (and of the two-stage prefix)
     double eps1 = 0.0;              // two-stage: bound of the screen over all rows (0: added inside the kernel)
     bool masked = false;            // the screen runs under a scope mask (run_masked_pass): no prefix, the floor from an in-scope sample
+    bool grouped = false;           // ... under the masks of several groups at once (a masked pass with a GroupScopes)
 
     bool two_stage() const {   // the pass keeps survivors in per-query buffers (idx->h_survivors holds their counts)
         return form == PassForm::TwoStageGemm || form == PassForm::TwoStageStream;
@@ -2564,7 +2572,7 @@ struct PassPlan {
     bool stream() const { return form == PassForm::TwoStageStream; }
     double plane_bytes_per_row(int32_t B) const { return (count_bits == 2 ? 8.0 : 16.0) * (double)((B + 31) / 32); }   // count words
     bool fused() const { return fused_sample_seg > 0; }
-    int pass_mode() const { static constexpr int kMode[] = {0, 1, 1, 2, 2, 3}; return masked ? 5 : kMode[(int)screen]; }   // orr_search_stats
+    int pass_mode() const { static constexpr int kMode[] = {0, 1, 1, 2, 2, 3}; return grouped ? 6 : masked ? 5 : kMode[(int)screen]; }   // orr_search_stats
 };
 
 // Whether a host-resident batch holds a query whose largest coordinate is positive and below 2^-48: its products with the rows
@@ -2714,6 +2722,26 @@ struct MaskScope {
     int64_t sample = 0;                 // rows of the in-scope sample the floor comes from (mask::sample_rows)
 };
 
+// The scopes of a grouped masked pass (orr_search_batch_masked_groups; the rules are orr_group_plan.h's): G bitmaps, each shared by
+// the queries that name it.  The pass carries a MaskScope beside it (n_clip: the largest clip of a screen group, sample: the
+// largest sample) for what the stages ask of a scope as a whole.
+struct GroupScopes {
+    int32_t n_groups = 0;
+    const uint32_t *bm = nullptr;       // device [n_groups][words]: the groups' bitmaps, deleted rows left out
+    const uint32_t *chunks = nullptr;   // device [n_groups][scope_chunks(words)]
+    int64_t words = 0;
+    std::vector<int64_t> took, n_clip, sample;   // per group: the rows that take part, one past the last of them, m_g
+    const int64_t *d_clip = nullptr;    // device [n_groups]: n_clip of a screen group, 0 for the others
+    const int64_t *d_sample = nullptr;  // device [n_groups]: m_g
+    bool floor_heads = false;           // every query's sample fills 8 k lists (group::floor_from_heads)
+    std::vector<int32_t> qgroup;        // the group of each query of the PASS (a sub-batch of the call)
+    uint32_t cap = 0;                   // > 0: entries per query of the survivors' buffers of this pass (the call's own growth)
+    // device, written by the floor stage of the pass: the group and the rows that took part per query
+    const uint32_t *d_qgroup = nullptr;
+    const int64_t *d_took = nullptr;
+    uint32_t *h_screened = nullptr;     // pinned, a query per entry: under profiling the counts the screen left IN FRONT of the filter
+};
+
 // What the stages of one pass hand on to each other.
 struct PassIo {
     const float *d_q = nullptr;         // the query vectors on the device
@@ -2724,6 +2752,7 @@ struct PassIo {
     orr_candidate *d_cand = nullptr;    // the records [B][kprime + 1]
     bool direct_host = false;           // d_cand is pinned host memory
     const MaskScope *mask = nullptr;    // a masked pass: the scope (else null)
+    GroupScopes *groups = nullptr;      // ... of several groups: their scopes (else null)
 };
 
 // The front end of a pass, unscoped (run_shard_once) or scoped (run_scoped_pass): the term offsets, the plan, where the
@@ -2941,8 +2970,11 @@ int launch_consts(orr_index *idx, const BatchArgs &a, const PassPlan &p, int64_t
     }
     if (p.batched_score && !p.rowc_inline) {
         ORR_TRY(idx->ws_rowc.reserve(sizeof(double2) * (size_t)n));
-        Timed t(idx, io.mask ? "row_consts_masked" : "row_consts", 32.0 * (double)n);
-        if (io.mask)      // rows outside the scope get constants below every floor
+        Timed t(idx, io.groups ? "row_consts_grouped" : io.mask ? "row_consts_masked" : "row_consts", 32.0 * (double)n);
+        if (io.groups)    // rows outside every screen group's clipped scope get constants below every floor
+            HIP_TRY(orr::launch_row_consts_grouped(idx->d_norm_b, idx->d_created, a.now_ticks, n, io.groups->bm, io.groups->words,
+                                                   io.groups->n_groups, io.groups->d_clip, idx->ws_rowc.as<double2>(), s));
+        else if (io.mask) // rows outside the scope get constants below every floor
             HIP_TRY(orr::launch_row_consts_masked(idx->d_norm_b, idx->d_created, a.now_ticks, n, io.mask->bm, idx->ws_rowc.as<double2>(), s));
         else
             HIP_TRY(orr::launch_row_consts(idx->d_norm_b, idx->d_created, a.now_ticks, n, idx->ws_rowc.as<double2>(), s));
@@ -3059,29 +3091,37 @@ int masked_floor(orr_index *idx, const BatchArgs &a, const PassIo &io, int32_t k
     const int32_t B = a.B;
     hipStream_t s = idx->stream;
     const MaskScope &m = *io.mask;
+    GroupScopes *gs = io.groups;
     const uint32_t cap = (uint32_t)m.sample;                                   // whole lists of 64, fewer than took
     const int32_t lists = (int32_t)(cap / orr::kSelWidth);
-    // [limit i64][query -> bitmap 0, u32 x B][counts u32 x B]
-    const size_t o_sel = sizeof(int64_t), o_cnt = o_sel + sizeof(uint32_t) * (size_t)B, bytes = o_cnt + sizeof(uint32_t) * (size_t)B;
+    // [limit i64][query -> bitmap 0, u32 x B][counts u32 x B]; grouped: [rows that took part, i64 x B][query -> its group's
+    // bitmap][counts: its group's sample <= cap], the limits per bitmap are the call's (GroupScopes::d_sample)
+    const size_t o_sel = sizeof(int64_t) * (gs ? (size_t)B : 1), o_cnt = o_sel + sizeof(uint32_t) * (size_t)B, bytes = o_cnt + sizeof(uint32_t) * (size_t)B;
     ORR_TRY(idx->pin_mask.reserve(sizeof(int64_t) + bytes));                   // (its first word: n_clip, masked_batch's)
     ORR_TRY(idx->ws_mask_cnt.reserve(bytes));
     uint8_t *hp = idx->pin_mask.as<uint8_t>() + sizeof(int64_t);
-    *reinterpret_cast<int64_t *>(hp) = m.sample;
+    if (!gs) *reinterpret_cast<int64_t *>(hp) = m.sample;
     for (int32_t b = 0; b < B; ++b) {
-        reinterpret_cast<uint32_t *>(hp + o_sel)[b] = 0u;
-        reinterpret_cast<uint32_t *>(hp + o_cnt)[b] = cap;
+        const int32_t g = gs ? gs->qgroup[(size_t)b] : 0;
+        if (gs) reinterpret_cast<int64_t *>(hp)[b] = gs->took[(size_t)g];
+        reinterpret_cast<uint32_t *>(hp + o_sel)[b] = (uint32_t)g;
+        reinterpret_cast<uint32_t *>(hp + o_cnt)[b] = gs ? (uint32_t)gs->sample[(size_t)g] : cap;
     }
     HIP_TRY(hipMemcpyAsync(idx->ws_mask_cnt.p, hp, bytes, hipMemcpyHostToDevice, s));
     uint8_t *dp = idx->ws_mask_cnt.as<uint8_t>();
     const uint32_t *d_cnt = reinterpret_cast<const uint32_t *>(dp + o_cnt);
+    if (gs) { gs->d_took = reinterpret_cast<const int64_t *>(dp); gs->d_qgroup = reinterpret_cast<const uint32_t *>(dp + o_sel); }
     ORR_TRY(idx->ws_pbuf.reserve(sizeof(orr::SelEntry) * (size_t)B * cap));
     ORR_TRY(idx->ws_psel.reserve(sizeof(orr::SelEntry) * (size_t)B * cap));
     ORR_TRY(idx->ws_dot.reserve(sizeof(double) * (size_t)B * cap));
     orr::SelEntry *buf = idx->ws_pbuf.as<orr::SelEntry>();
     {
         Timed t(idx, "mask_sample_compact", 16.0 * (double)B * (double)cap);
-        HIP_TRY(orr::launch_scope_compact(m.bm, m.words, 1, m.chunks, reinterpret_cast<const uint32_t *>(dp + o_sel), B,
-                                          reinterpret_cast<const int64_t *>(dp), buf, cap, s));
+        if (gs)
+            HIP_TRY(orr::launch_scope_compact(gs->bm, gs->words, gs->n_groups, gs->chunks, gs->d_qgroup, B, gs->d_sample, buf, cap, s));
+        else
+            HIP_TRY(orr::launch_scope_compact(m.bm, m.words, 1, m.chunks, reinterpret_cast<const uint32_t *>(dp + o_sel), B,
+                                              reinterpret_cast<const int64_t *>(dp), buf, cap, s));
     }
     {
         Timed t(idx, "mask_sample_rescore", (double)B * (double)cap * 4.0 * idx->dim);
@@ -3091,7 +3131,9 @@ int masked_floor(orr_index *idx, const BatchArgs &a, const PassIo &io, int32_t k
     Timed t(idx, "mask_sample_floor", 0.0);
     HIP_TRY(orr::launch_buffer_to_lists(buf, d_cnt, cap, B, 0, lists, idx->ws_psel.as<orr::SelEntry>(), s));
     floor.eps3 = kCertifyEps;
-    HIP_TRY(orr::launch_select_final_sample(idx->ws_psel.as<orr::SelEntry>(), lists, lists, B, kth, idx->ws_tau.as<unsigned long long>(), s, floor));
+    // (grouped: the lists behind a query's own sample are empty, so the heads alone serve only where every sample fills 8 k lists)
+    HIP_TRY(orr::launch_select_final_sample(idx->ws_psel.as<orr::SelEntry>(), lists, lists, B, kth, idx->ws_tau.as<unsigned long long>(), s, floor,
+                                            0, gs && !gs->floor_heads ? 1 : 0));
     return ORR_OK;
 }
 
@@ -3189,12 +3231,19 @@ int screen_two_stage(orr_index *idx, const BatchArgs &a, const PassPlan &p, int3
         Timed t(idx, "gemm_dot_bf16x1_fused", 4.0 * (double)n * idx->dim + 2.0 * (double)B * idx->dim);
         HIP_TRY(orr::launch_gemm_dot_bf16x3(idx->ws_qsplit.p, B, idx->d_emb, 0, n, idx->dim, nullptr, 0, &epi, 1, s));
     }
-    if (io.mask) {      // the one exact application of the mask: what the screen buffered from outside the scope goes
+    if (io.groups) {    // ... of the query's own group: a row of another group that beat the query's floor goes here
+        if (idx->profiling == 1 && io.groups->h_screened)      // (kernel statistics: what the screen buffered, other groups' rows included)
+            HIP_TRY(hipMemcpyAsync(io.groups->h_screened, epi.cnt, sizeof(uint32_t) * (size_t)B, hipMemcpyDeviceToHost, s));
+        Timed t(idx, "mask_survivors_grouped", 16.0 * (double)B * (double)kCap);
+        HIP_TRY(orr::launch_mask_survivors_grouped(io.groups->bm, io.groups->words, io.groups->n_groups, io.groups->d_clip, io.groups->d_qgroup,
+                                                   epi.cnt, kCap, epi.buf, B, s));
+    } else if (io.mask) {      // the one exact application of the mask: what the screen buffered from outside the scope goes
         Timed t(idx, "mask_survivors", 16.0 * (double)B * (double)kCap);
         HIP_TRY(orr::launch_mask_survivors(io.mask->bm, io.mask->n_clip, epi.cnt, kCap, epi.buf, B, s));
     }
     ORR_TRY(two_stage_tail(idx, a, kprime, n, io, epi, kCap, buf_lists, host_records, rec_bytes, Rescore::BufferExact, 0.0, s));
-    if (io.mask) HIP_TRY(orr::launch_mask_trailers(io.d_cand, B, kprime, io.mask->took, s));
+    if (io.groups) HIP_TRY(orr::launch_mask_trailers_grouped(io.d_cand, B, kprime, io.groups->d_took, s));
+    else if (io.mask) HIP_TRY(orr::launch_mask_trailers(io.d_cand, B, kprime, io.mask->took, s));
     return ORR_OK;
 }
 
@@ -3206,6 +3255,7 @@ int select_fused(orr_index *idx, const BatchArgs &a, const PassPlan &p, int32_t 
     const int32_t B = a.B;
     hipStream_t s = idx->stream;
     uint32_t kCap = idx->survivor_cap;                              // survivors kept per query (a multiple of 64)
+    if (io.groups && io.groups->cap) kCap = io.groups->cap;         // (a grouped call's own growth: the lane does not keep it)
     while (kCap > 8192 && (size_t)B * kCap * 40 > ((size_t)2 << 30)) kCap >>= 1;
     idx->pass_cap = kCap;
     const int32_t fss = p.fused_sample_seg;
@@ -4093,8 +4143,10 @@ constexpr int kNotMaskable = 2;        // run_masked_pass: plan_form found no tw
 // One masked pass over the queries of `a`: run_shard_once's front end and stages over rows [0, ms.n_clip), no prefix (the floor
 // comes from an in-scope sample, masked_floor), the survivors filtered by the mask in front of the tail.  Records in host
 // memory (*recs_host).  kRetryPass as run_shard_once; kNotMaskable before anything ran.  Caller holds the lane and its lock.
+// With `groups` the pass is a grouped one (orr_search_batch_masked_groups): ms carries the largest clip and the largest sample, the
+// row constants, the sample, the filter and the trailers take each query's own group from `groups`.
 int run_masked_pass(orr_index *idx, const BatchArgs &a, int32_t kprime, const MaskScope &ms, const float **q_host,
-                    const orr_candidate **recs_host, PassPlan &p)
+                    const orr_candidate **recs_host, PassPlan &p, GroupScopes *groups = nullptr)
 {
     ORR_TRY(bind_device(idx));
     const int64_t n = ms.n_clip;
@@ -4106,12 +4158,14 @@ int run_masked_pass(orr_index *idx, const BatchArgs &a, int32_t kprime, const Ma
         ORR_TRY(plan_pass(idx, a, kprime, n, qoff, pl));
         if (!pl.two_stage()) return kNotMaskable;
         pl.masked = true;
+        pl.grouped = groups != nullptr;
         pl.rowc_inline = false;        // the mask lives in the materialised row constants: the int8 stream reads them too
         return ORR_OK;
     };
     ORR_TRY(open_pass(idx, a, kprime, plan, true, false, false, q_host, p, f));
     PassIo &io = f.io;
     io.mask = &ms;
+    io.groups = groups;
     if (p.screen == Screen::GemvI8) ORR_TRY(launch_i8_query_image(idx, io.d_q, B, false, s));
     KwSide kws;
     ORR_TRY(launch_keyword_side(idx, a, f.qoff, kws));
@@ -4125,6 +4179,12 @@ int run_masked_pass(orr_index *idx, const BatchArgs &a, int32_t kprime, const Ma
     idx->sstats.pass_mode = p.pass_mode();
     const int r = finish_pass(idx, a, p, kws, f.n_terms_total);
     if (r != ORR_OK) return r;
+    if (groups && groups->h_screened && idx->profiling == 1) {
+        // "grouped_screen_pairs": 16 bytes per pair the screen buffered in front of the filter (what mask_survivors_grouped read)
+        double pairs = 0.0;
+        for (int32_t b = 0; b < B; ++b) pairs += (double)std::min<uint32_t>(groups->h_screened[b], idx->pass_cap);
+        add_phase_stat(idx, "grouped_screen_pairs", std::chrono::steady_clock::now(), 16.0 * pairs);
+    }
     *recs_host = io.direct_host ? io.d_cand : idx->pin_cand.as<orr_candidate>();
     return ORR_OK;
 }
@@ -4315,6 +4375,229 @@ int masked_batch(orr_index *idx, const BatchArgs &orig, const ScopeArgs &sc, int
     for (int32_t b0 = 0; b0 < B; b0 += per)
         ORR_TRY(masked_screen_ladder(idx, orig, sl, ms, std::vector<int32_t>(ids.begin() + b0, ids.begin() + std::min<int32_t>(B, b0 + per)),
                                      out_rows, out_scores, out_counts));
+    return ORR_OK;
+}
+
+// ---- grouped masked search: G scopes, each shared by the queries that name it, screened together (orr_search_batch_masked_groups)
+// Each group alone is a masked search; what the groups share is the one stream over the shard's shadow.  The rules -- which
+// groups screen together, their samples, the cost rule, the ladder -- are orr_group_plan.h's.
+
+struct GroupArgs {
+    int32_t n_groups;
+    int64_t n_ids;
+    const int64_t *ids;            // host or device
+    const uint64_t *off;           // host [n_groups + 1]
+    const int32_t *query_group;    // host [B]
+};
+
+// The queries `ids` of the call (ascending, all of group g) as a masked call of their own, the results scattered back.
+int masked_sub_batch(orr_index *idx, const BatchArgs &orig, const GroupArgs &ga, int32_t g, const std::vector<int32_t> &ids,
+                     int64_t *out_rows, double *out_scores, int32_t *out_counts)
+{
+    if (ids.empty()) return ORR_OK;
+    const int32_t take = std::max<int32_t>(1, orig.topk);
+    const ScopeArgs sc{(int64_t)(ga.off[g + 1] - ga.off[g]), ga.ids ? ga.ids + ga.off[g] : nullptr, nullptr, nullptr};
+    SubBatch sb;
+    BatchArgs cur;
+    ORR_TRY(build_subset(idx, orig, ids, sb, cur));
+    if (cur.B == orig.B) return masked_batch(idx, cur, sc, out_rows, out_scores, out_counts);       // every query of the call
+    const size_t nb = ids.size();
+    std::vector<int64_t> rows(nb * (size_t)take);
+    std::vector<double> scores(nb * (size_t)take);
+    std::vector<int32_t> counts(nb);
+    ORR_TRY(masked_batch(idx, cur, sc, rows.data(), scores.data(), counts.data()));
+    for (size_t i = 0; i < nb; ++i) {
+        const size_t b = (size_t)ids[i];
+        memcpy(out_rows + b * take, rows.data() + i * take, sizeof(int64_t) * take);
+        memcpy(out_scores + b * take, scores.data() + i * take, sizeof(double) * take);
+        if (out_counts) out_counts[b] = counts[i];
+    }
+    return ORR_OK;
+}
+
+// `ids` (ascending) split by group, each part a masked call of its own.  The call resolves its group again instead of taking
+// the bitmap the grouped resolve holds: masked_screen_ladder ends in masked_list_path, which reads ONE shared bitmap with its
+// pinned counts and device limits from the lane's scoped slice (ws_scope_bm, pin_scope, ws_scope_meta) and rewrites it per
+// part -- the grouped resolve left G bitmaps and G pseudo-queries there, and a slice rebuilt by hand from them would be a
+// second copy of build_scope_slice's layout.  One scope_lookup of the group's ids (14-55 us measured) on a path that runs only
+// for queries the grouped pass could not certify buys that the ladder is the masked call's, unchanged and already tested.
+int masked_sub_batches(orr_index *idx, const BatchArgs &orig, const GroupArgs &ga, const std::vector<int32_t> &ids, bool requery,
+                       int64_t *out_rows, double *out_scores, int32_t *out_counts)
+{
+    std::vector<std::vector<int32_t>> by_group((size_t)ga.n_groups);
+    for (int32_t b : ids) by_group[(size_t)ga.query_group[b]].push_back(b);
+    for (int32_t g = 0; g < ga.n_groups; ++g) {
+        if (by_group[(size_t)g].empty()) continue;
+        if (requery) idx->sstats.requeried += (int64_t)by_group[(size_t)g].size();
+        ORR_TRY(masked_sub_batch(idx, orig, ga, g, by_group[(size_t)g], out_rows, out_scores, out_counts));
+    }
+    return ORR_OK;
+}
+
+// The queries `first_ids` of the call (all of screen groups) through the grouped pass and its ladder (group::next_step): the
+// queries whose only problem was an overflowing buffer repeat together once, with buffers of the call's own; every other
+// uncertified query enters its group's masked call.
+int grouped_screen_ladder(orr_index *idx, const BatchArgs &orig, const GroupArgs &ga, GroupScopes &gs, const MaskScope &ms,
+                          std::vector<int32_t> first_ids, int64_t *out_rows, double *out_scores, int32_t *out_counts)
+{
+    const int32_t take = std::max<int32_t>(1, orig.topk);
+    const bool use_cos = orig.dim > 0 && orig.dim == idx->dim;
+    const int32_t kprime = (int32_t)escalation::initial_kprime(take, ms.took, orr::kSelWidth);
+    std::vector<int32_t> ids = std::move(first_ids);
+    bool grown = false;
+    gs.cap = 0;
+    for (int pass_no = 0; !ids.empty(); ++pass_no) {
+        const size_t nb = ids.size();
+        SubBatch sb;
+        BatchArgs cur;
+        ORR_TRY(build_subset(idx, orig, ids, sb, cur));
+        gs.qgroup.resize(nb);
+        for (size_t i = 0; i < nb; ++i) gs.qgroup[i] = ga.query_group[ids[i]];
+        PassPlan pass;
+        const float *q_host = nullptr;
+        const orr_candidate *recs = nullptr;
+        const int rc = retry_pass(idx, [&] { return run_masked_pass(idx, cur, kprime, ms, &q_host, &recs, pass, &gs); });
+        if (rc == kNotMaskable) return masked_sub_batches(idx, orig, ga, ids, pass_no > 0, out_rows, out_scores, out_counts);
+        if (rc != ORR_OK) return rc;
+        std::vector<uint8_t> cert;
+        ORR_TRY(merge_into(1, kprime, recs, cur, use_cos, q_host, idx->h_norm_a.data(), ids, out_rows, out_scores, out_counts, cert));
+        const ShardOutcome o = outcome_of(idx, pass, ms.n_clip);       // (survivor_cap: the lane's, which the call's own growth leaves alone)
+        idx->sstats.passes += 1;
+        if (pass_no > 0) idx->sstats.requeried += (int64_t)nb;
+        escalation::account_survivors(idx->sstats, o, nb);
+        size_t n_again = 0;
+        for (size_t i = 0; i < nb; ++i) n_again += cert[i] ? 0 : 1;
+        if (n_again == 0) break;
+        std::vector<int32_t> grow, rest;
+        uint32_t worst = 0, cap_i = 0;
+        for (size_t i = 0; i < nb; ++i) {
+            if (cert[i]) continue;
+            if (!grown && pass_no + 1 < group::kMaxGroupedPasses && o.kept(nb) && o.overflowed(i) &&
+                escalation::grown_survivor_cap(o.pass_cap, o.survivors[i], ms.n_clip, n_again, &cap_i)) {
+                grow.push_back(ids[i]);
+                worst = std::max(worst, o.survivors[i]);
+            } else {
+                rest.push_back(ids[i]);
+            }
+        }
+        group::Next nx;
+        if (!grow.empty()) nx = group::next_step(true, grown, o.pass_cap, worst, ms.n_clip, grow.size());
+        if (nx.step != group::Step::GrowBuffers) { rest.insert(rest.end(), grow.begin(), grow.end()); std::sort(rest.begin(), rest.end()); grow.clear(); }
+        ORR_TRY(masked_sub_batches(idx, orig, ga, rest, true, out_rows, out_scores, out_counts));
+        if (grow.empty()) break;
+        idx->sstats.buffer_growths += 1;       // the call's own: neither the lane nor the handle keeps the size
+        gs.cap = nx.new_cap;
+        grown = true;
+        ids = std::move(grow);
+    }
+    gs.cap = 0;
+    return ORR_OK;
+}
+
+// orr_search_batch_masked_groups on the lane the caller holds.
+int grouped_batch(orr_index *idx, const BatchArgs &call, const GroupArgs &ga, int64_t *out_rows, double *out_scores, int32_t *out_counts)
+{
+    const int32_t B = call.B, take = std::max<int32_t>(1, call.topk), G = ga.n_groups;
+    const bool use_cos = call.dim > 0 && call.dim == idx->dim;
+    for (size_t i = 0; i < (size_t)B * take; ++i) { out_rows[i] = -1; out_scores[i] = 0.0; }
+    if (out_counts) for (int32_t b = 0; b < B; ++b) out_counts[b] = 0;
+    if (idx->n_rows <= 0 || ga.n_ids == 0) return ORR_OK;
+    ORR_TRY(bind_device(idx));
+    std::vector<std::vector<int32_t>> members((size_t)G);
+    for (int32_t b = 0; b < B; ++b) members[(size_t)ga.query_group[b]].push_back(b);
+    // ---- the groups that can be used at all; one of them: the masked call itself, nothing new runs
+    int32_t named = 0, only = -1;
+    for (int32_t g = 0; g < G; ++g)
+        if (!members[(size_t)g].empty() && ga.off[g + 1] > ga.off[g]) { named += 1; only = g; }
+    if (named == 0) return ORR_OK;
+    if (named == 1 && (int32_t)members[(size_t)only].size() == B)        // (whole: the vectors stay where they are)
+        return masked_sub_batch(idx, call, ga, only, members[(size_t)only], out_rows, out_scores, out_counts);
+    // (sub-batches are gathered on the host, and gathered again by the passes they take: device-resident vectors come down once)
+    BatchArgs orig = call;
+    std::vector<float> q_down;
+    if (call.dim > 0 && is_device_pointer(call.q)) {
+        q_down.resize((size_t)B * (size_t)call.dim);
+        HIP_TRY(hipMemcpy(q_down.data(), call.q, sizeof(float) * q_down.size(), hipMemcpyDeviceToHost));
+        orig.q = q_down.data();
+    }
+    if (named == 1) return masked_sub_batch(idx, orig, ga, only, members[(size_t)only], out_rows, out_scores, out_counts);
+    ORR_TRY(ensure_scope_table(idx));
+    hipStream_t s = idx->stream;
+    // ---- resolve: the groups as G pseudo-queries of a scoped slice -> G bitmaps, live and took per group
+    const std::vector<int64_t> limit((size_t)G, std::max<int64_t>(1, call.candidate_limit));
+    const ScopeArgs sc{ga.n_ids, ga.ids, ga.off, nullptr};
+    ScopeSlice sl;
+    ORR_TRY(build_scope_slice(idx, sc, limit, 0, G, sl));
+    std::vector<group::GroupIn> gin((size_t)G);
+    for (int32_t g = 0; g < G; ++g) { gin[(size_t)g].took = sl.took[g]; gin[(size_t)g].queries = (int32_t)members[(size_t)g].size(); }
+    int32_t n_used = 0;
+    for (int32_t g = 0; g < G; ++g)
+        if (group::used(gin[(size_t)g])) { n_used += 1; only = g; }
+    if (n_used == 0) return ORR_OK;
+    if (n_used == 1) return masked_sub_batch(idx, orig, ga, only, members[(size_t)only], out_rows, out_scores, out_counts);
+    // ---- the bitmaps are kept beside the slice's (which a group's own masked call rewrites); clip per used group
+    GroupScopes gs;
+    gs.n_groups = G; gs.words = sl.words;
+    const int32_t n_chunks = orr::scope_chunks(sl.words);
+    const size_t bm_bytes = sizeof(uint32_t) * (size_t)G * (size_t)sl.words, ch_bytes = sizeof(uint32_t) * (size_t)G * (size_t)n_chunks;
+    ORR_TRY(idx->ws_group_bm.reserve(bm_bytes));
+    ORR_TRY(idx->ws_group_chunks.reserve(ch_bytes));
+    ORR_TRY(idx->pin_group.reserve(sizeof(int64_t) * 2 * (size_t)G + sizeof(uint32_t) * (size_t)B));      // [clip x G][sample x G][screened x B]
+    ORR_TRY(idx->ws_group_meta.reserve(sizeof(int64_t) * 2 * (size_t)G));
+    HIP_TRY(hipMemcpyAsync(idx->ws_group_bm.p, idx->ws_scope_bm.p, bm_bytes, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(idx->ws_group_chunks.p, idx->ws_scope_chunks.p, ch_bytes, hipMemcpyDeviceToDevice, s));
+    gs.bm = idx->ws_group_bm.as<uint32_t>(); gs.chunks = idx->ws_group_chunks.as<uint32_t>();
+    int64_t *h_meta = idx->pin_group.as<int64_t>();            // [clip x G][sample x G]
+    for (int32_t g = 0; g < 2 * G; ++g) h_meta[g] = 0;
+    for (int32_t g = 0; g < G; ++g) {
+        if (!group::used(gin[(size_t)g])) continue;
+        Timed t(idx, "mask_clip", 4.0 * (double)orr::kScopeChunkWords + 4.0 * (double)n_chunks);
+        HIP_TRY(orr::launch_mask_clip(gs.bm + (size_t)g * (size_t)sl.words, sl.words, gs.chunks + (size_t)g * (size_t)n_chunks,
+                                      (uint32_t)gin[(size_t)g].took, h_meta + g, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    collect_events(idx);
+    for (int32_t g = 0; g < G; ++g) gin[(size_t)g].n_clip = std::min<int64_t>(h_meta[g], idx->n_rows);
+    // ---- the plan: samples, screen and list groups, the grouped pass or a masked call per group
+    const uint32_t cap = group::pass_cap(idx->survivor_cap, B);
+    const group::Plan plan = group::plan(gin, call.topk, cap, idx->opt_mask_screen, use_cos, idx->dim, orr::kSelWidth, idx->opt_two_stage);
+    std::vector<int32_t> screened;
+    for (int32_t g = 0; g < G; ++g) {
+        const group::Role role = plan.role[(size_t)g];
+        if (role == group::Role::Unused) continue;
+        if (plan.grouped && role == group::Role::Screen) screened.insert(screened.end(), members[(size_t)g].begin(), members[(size_t)g].end());
+    }
+    // ---- list groups, and every used group where the grouped pass does not run: a masked call of their own (first: pass_mode
+    // tells what ran last)
+    for (int32_t g = 0; g < G; ++g) {
+        const group::Role role = plan.role[(size_t)g];
+        if (role == group::Role::Unused || (plan.grouped && role == group::Role::Screen)) continue;
+        ORR_TRY(masked_sub_batch(idx, orig, ga, g, members[(size_t)g], out_rows, out_scores, out_counts));
+    }
+    // ---- the grouped pass over the screen groups' queries, in slices
+    if (!screened.empty()) {
+        std::sort(screened.begin(), screened.end());
+        gs.took.resize((size_t)G); gs.n_clip.resize((size_t)G); gs.sample = plan.sample;
+        for (int32_t g = 0; g < G; ++g) {
+            gs.took[(size_t)g] = gin[(size_t)g].took;
+            gs.n_clip[(size_t)g] = gin[(size_t)g].n_clip;
+            h_meta[g] = group::screen_clip(plan.role[(size_t)g] == group::Role::Screen, gin[(size_t)g].n_clip);
+            h_meta[G + g] = plan.sample[(size_t)g];
+        }
+        HIP_TRY(hipMemcpyAsync(idx->ws_group_meta.p, h_meta, sizeof(int64_t) * 2 * (size_t)G, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));                      // (pin_group is the next grouped call's on this lane)
+        gs.d_clip = idx->ws_group_meta.as<int64_t>(); gs.d_sample = gs.d_clip + G;
+        gs.floor_heads = group::floor_from_heads(plan.min_sample, call.topk, orr::kSelWidth);
+        gs.h_screened = reinterpret_cast<uint32_t *>(h_meta + 2 * G);
+        MaskScope ms;                                          // the scopes as a whole: what the stages ask of one
+        ms.words = sl.words; ms.took = plan.min_took; ms.live = plan.min_took;
+        ms.n_clip = plan.n_clip; ms.sample = plan.max_sample;
+        const int32_t per = group::screen_slice((int32_t)screened.size(), plan.max_sample);
+        for (size_t b0 = 0; b0 < screened.size(); b0 += (size_t)per)
+            ORR_TRY(grouped_screen_ladder(idx, orig, ga, gs, ms,
+                                          std::vector<int32_t>(screened.begin() + b0, screened.begin() + std::min(screened.size(), b0 + (size_t)per)),
+                                          out_rows, out_scores, out_counts));
+    }
     return ORR_OK;
 }
 
@@ -4589,6 +4872,34 @@ int orr_search_batch_masked(orr_index *idx, int32_t B, int32_t dim, const float 
     idx->sstats.searches += 1;
     idx->sstats.queries += B;
     return masked_batch(idx, a, sc, out_rows, out_scores, out_counts);
+}
+
+int orr_search_batch_masked_groups(orr_index *idx, int32_t B, int32_t dim, const float *q, const uint8_t *terms_utf8,
+                                   const uint32_t *term_off, const uint32_t *query_term_off, int64_t now_ticks, int32_t topk,
+                                   int64_t candidate_limit, int32_t n_groups, int64_t n_scope_ids, const int64_t *scope_ids,
+                                   const uint64_t *group_off, const int32_t *query_group,
+                                   int64_t *out_rows, double *out_scores, int32_t *out_counts)
+{
+    static const char *fn = "orr_search_batch_masked_groups";
+    BatchArgs a{B, dim, q, terms_utf8, term_off, query_term_off, now_ticks, candidate_limit, topk};
+    const ScopeArgs sc{n_scope_ids, scope_ids, nullptr, nullptr};
+    ORR_TRY(check_scope(idx, B, sc, fn));
+    ORR_TRY(check_batch(idx, a, fn));
+    if (!out_rows || !out_scores) return fail(ORR_EINVAL, "%s: output buffers are required", fn);
+    if (!group::groups_valid(n_groups)) return fail(ORR_EINVAL, "%s: n_groups must be in 1 .. %d", fn, group::kMaxGroups);
+    if (!group_off) return fail(ORR_EINVAL, "%s: group_off is NULL", fn);
+    if (!query_group) return fail(ORR_EINVAL, "%s: query_group is NULL", fn);
+    if (!scope::offsets_valid(group_off, n_groups, n_scope_ids))
+        return fail(ORR_EINVAL, "%s: group_off must start at 0, never decrease and end at n_scope_ids", fn);
+    if (!group::assignment_valid(query_group, B, n_groups))
+        return fail(ORR_EINVAL, "%s: query_group must name a group in 0 .. %d for every query", fn, n_groups - 1);
+    const GroupArgs ga{n_groups, n_scope_ids, scope_ids, group_off, query_group};
+    Lane ln = acquire_lane(idx);                       // a search like any other: its own lane, concurrent with the others
+    idx = ln.lane;
+    std::lock_guard<std::mutex> lock(idx->mu);
+    idx->sstats.searches += 1;
+    idx->sstats.queries += B;
+    return grouped_batch(idx, a, ga, out_rows, out_scores, out_counts);
 }
 
 int orr_search_shard_scoped(orr_index *idx, int32_t B, int32_t dim, const float *q, const uint8_t *terms_utf8,

@@ -355,7 +355,8 @@ struct FloorOut {
 };
 hipError_t launch_select_final_sample(const SelEntry *sel, int32_t n_seg_total, int32_t sample_seg, int32_t B,
                                       int32_t kprime, unsigned long long *tau_out, hipStream_t s, FloorOut floor = FloorOut(),
-                                      int32_t wave_maxima = 0);    // 1: the lists hold 16 unsorted wave maxima each (fuse_select floor_only = 2)
+                                      int32_t wave_maxima = 0,     // 1: the lists hold 16 unsorted wave maxima each (fuse_select floor_only = 2)
+                                      int32_t merge_all = 0);      // 1: never from the lists' heads alone (some query's lists may be empty: a grouped pass)
 
 // Generic path for large k: keys[r] = score key of (query b,row r), vals[r] = r.
 hipError_t launch_score_keys(const double *dot, const double *norm_b, const int64_t *created,
@@ -444,5 +445,17 @@ hipError_t launch_mask_part(const uint32_t *bitmap, int64_t words, const uint32_
                             hipStream_t s);
 // The two-stage tail's trailers behind a masked screen: order_key = took, floor and flags kept.
 hipError_t launch_mask_trailers(orr_candidate *recs, int32_t B, int32_t kprime, int64_t took, hipStream_t s);
+
+// ---- grouped masked search (orr_search_batch_masked_groups; the rules are orr_group_plan.h's) -------------------------------
+// bitmaps[n_groups][words] as launch_scope_lookup leaves them; clip[n_groups] (device): the rows [0, clip[g]) of group g take
+// part, 0 for a group that takes no part in the pass.
+// launch_row_consts for the rows some group holds in front of its own clip; {0, mask::kMaskedRecency} for the others.
+hipError_t launch_row_consts_grouped(const double *norm_b, const int64_t *created, int64_t now_ticks, int64_t n_rows, const uint32_t *bitmaps,
+                                     int64_t words, int32_t n_groups, const int64_t *clip, double2 *out, hipStream_t s);
+// launch_mask_survivors with the bitmap and the clip of query b's own group, qgroup[b] (device, < n_groups).
+hipError_t launch_mask_survivors_grouped(const uint32_t *bitmaps, int64_t words, int32_t n_groups, const int64_t *clip, const uint32_t *qgroup,
+                                         uint32_t *cnt, uint32_t cap, SelEntry *buf, int32_t B, hipStream_t s);
+// launch_mask_trailers with took[b] (device) per query.
+hipError_t launch_mask_trailers_grouped(orr_candidate *recs, int32_t B, int32_t kprime, const int64_t *took, hipStream_t s);
 
 }  // namespace orr

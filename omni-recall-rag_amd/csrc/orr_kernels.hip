@@ -1117,7 +1117,8 @@ __global__ __launch_bounds__(64) void select_floor_heads_kernel(const SelEntry *
 }
 
 hipError_t launch_select_final_sample(const SelEntry *sel, int32_t n_seg_total, int32_t sample_seg, int32_t B,
-                                      int32_t kprime, unsigned long long *tau_out, hipStream_t s, FloorOut floor, int32_t wave_maxima)
+                                      int32_t kprime, unsigned long long *tau_out, hipStream_t s, FloorOut floor, int32_t wave_maxima,
+                                      int32_t merge_all)
 {
     if (B <= 0 || sample_seg <= 0) return hipSuccess;
     if (kprime < 1 || kprime > kSelWidth) return hipErrorInvalidValue;
@@ -1127,7 +1128,7 @@ hipError_t launch_select_final_sample(const SelEntry *sel, int32_t n_seg_total, 
         return hipGetLastError();
     }
     static const bool full = getenv("ORR_FLOOR_FULL") != nullptr;      // (A/B)
-    if (floor.floor_key && sample_seg >= 8 * kprime && !full) {        // (a two-stage pass's floor: any k distinct rows' k-th key serves)
+    if (floor.floor_key && sample_seg >= 8 * kprime && !full && !merge_all) {        // (a two-stage pass's floor: any k distinct rows' k-th key serves)
         hipLaunchKernelGGL(select_floor_heads_kernel, dim3((unsigned)B), dim3(64), 0, s, sel, sample_seg, n_seg_total, kprime, tau_out, floor, 1);
         return hipGetLastError();
     }
@@ -1911,6 +1912,99 @@ hipError_t launch_mask_trailers(orr_candidate *recs, int32_t B, int32_t kprime, 
 {
     if (B <= 0) return hipSuccess;
     hipLaunchKernelGGL(mask_trailers_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, recs, B, kprime, took);
+    return hipGetLastError();
+}
+
+// ---- grouped masked search (orr_search_batch_masked_groups; the rules are orr_group_plan.h's) ------------------------------
+
+// launch_row_consts under G scope masks at once: a row keeps its real constants when some group holds it in front of that
+// group's own clip (mask::survivor_in_scope per group: the 32 rows of a word read the same G words), else it gets the masked
+// row's constants as row_consts_masked_kernel gives them.  A group with clip 0 takes no part.
+__global__ __launch_bounds__(256) void row_consts_grouped_kernel(const double *__restrict__ norm_b, const int64_t *__restrict__ created,
+                                                                 int64_t now_ticks, int64_t n_rows, const uint32_t *__restrict__ bitmaps,
+                                                                 int64_t words, int32_t n_groups, const int64_t *__restrict__ clip,
+                                                                 double2 *__restrict__ out)
+{
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rows; r += (int64_t)gridDim.x * blockDim.x) {
+        bool held = false;
+        for (int32_t g = 0; g < n_groups && !held; ++g)
+            held = mask::survivor_in_scope(bitmaps + (int64_t)g * words, (uint32_t)r, (uint64_t)clip[g]);
+        double2 o;
+        o.x = 0.0; o.y = mask::kMaskedRecency;
+        if (held) o = row_consts_of(norm_b[r], created[r], now_ticks);
+        out[r] = o;
+    }
+}
+
+hipError_t launch_row_consts_grouped(const double *norm_b, const int64_t *created, int64_t now_ticks, int64_t n_rows, const uint32_t *bitmaps,
+                                     int64_t words, int32_t n_groups, const int64_t *clip, double2 *out, hipStream_t s)
+{
+    if (n_rows <= 0) return hipSuccess;
+    if (n_groups <= 0 || words <= 0 || n_rows > words * 32) return hipErrorInvalidValue;      // (every row has its bit in every bitmap)
+    const int64_t blocks = std::min<int64_t>((n_rows + 255) / 256, 2048);
+    hipLaunchKernelGGL(row_consts_grouped_kernel, dim3((unsigned)blocks), dim3(256), 0, s, norm_b, created, now_ticks, n_rows, bitmaps, words,
+                       n_groups, clip, out);
+    return hipGetLastError();
+}
+
+// mask_survivors_kernel against the bitmap and the clip of the query's own group: a row of another group that beat this
+// query's floor was buffered by the screen and goes here.  Tiles, order and the overflow signal as there.
+__global__ __launch_bounds__(256) void mask_survivors_grouped_kernel(const uint32_t *__restrict__ bitmaps, int64_t words, int32_t n_groups,
+                                                                     const int64_t *__restrict__ clip, const uint32_t *__restrict__ qgroup,
+                                                                     uint32_t *__restrict__ cnt, uint32_t cap, SelEntry *__restrict__ buf)
+{
+    __shared__ uint32_t wave_kept[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t g = qgroup[b];
+    const bool known = g < (uint32_t)n_groups;                     // (a query without a group keeps nothing)
+    const uint32_t *bitmap = bitmaps + (int64_t)(known ? g : 0u) * words;
+    const uint64_t n_clip = known && clip[g] > 0 ? (uint64_t)clip[g] : 0ull;
+    const uint32_t c = cnt[b], n = c < cap ? c : cap;
+    SelEntry *mine = buf + (int64_t)b * cap;
+    uint32_t out = 0;
+    for (uint32_t base = 0; base < n; base += 256u) {
+        const uint32_t i = base + (uint32_t)tid;
+        SelEntry e;
+        e.key = 0ull; e.pos = 0u; e.pad = 0u;
+        bool keep = false;
+        if (i < n) {
+            e = mine[i];
+            keep = mask::survivor_in_scope(bitmap, e.pos, n_clip);
+        }
+        const unsigned long long kept = __ballot(keep);
+        const uint32_t rank = (uint32_t)__popcll(kept & ((1ull << lane) - 1ull));
+        __syncthreads();                               // the tile is in registers; the last round's wave_kept has been read
+        if (lane == 0) wave_kept[wave] = (uint32_t)__popcll(kept);
+        __syncthreads();
+        uint32_t at = out + rank;
+        for (int k = 0; k < wave; ++k) at += wave_kept[k];
+        if (keep) mine[at] = e;
+        out += wave_kept[0] + wave_kept[1] + wave_kept[2] + wave_kept[3];
+    }
+    if (tid == 0) cnt[b] = c > cap ? c : out;
+}
+
+hipError_t launch_mask_survivors_grouped(const uint32_t *bitmaps, int64_t words, int32_t n_groups, const int64_t *clip, const uint32_t *qgroup,
+                                         uint32_t *cnt, uint32_t cap, SelEntry *buf, int32_t B, hipStream_t s)
+{
+    if (B <= 0) return hipSuccess;
+    if (cap == 0u || n_groups <= 0 || words <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mask_survivors_grouped_kernel, dim3((unsigned)B), dim3(256), 0, s, bitmaps, words, n_groups, clip, qgroup, cnt, cap, buf);
+    return hipGetLastError();
+}
+
+// mask_trailers_kernel with the rows that took part per query: the first took[b] of its group's scope.
+__global__ void mask_trailers_grouped_kernel(orr_candidate *recs, int32_t B, int32_t kprime, const int64_t *__restrict__ took)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    recs[(int64_t)b * ((int64_t)kprime + 1) + kprime].order_key = took[b];
+}
+
+hipError_t launch_mask_trailers_grouped(orr_candidate *recs, int32_t B, int32_t kprime, const int64_t *took, hipStream_t s)
+{
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(mask_trailers_grouped_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, recs, B, kprime, took);
     return hipGetLastError();
 }
 

@@ -304,6 +304,35 @@ class RecallIndex:
                                               _ptr(rows), _ptr(scores), _ptr(counts)))
         return rows, scores, counts
 
+    def search_masked_groups(self, qvecs, queries_terms, now_ticks: int, topk: int, group_scopes, query_group,
+                             candidate_limit: int = 300, group_off=None):
+        """orr_search_batch_masked_groups: query b ranks only the live rows whose id group query_group[b] lists -- for every
+        query the result of search_masked with its group's ids as the scope, while the groups' large scopes share ONE
+        screening pass over the shard.  group_scopes: a sequence of G id arrays, or -- with group_off [G+1] given -- the flat
+        array (numpy or torch, host or device) the offsets cut.  At most 64 groups.  Returns (rows [B,k] int64, scores [B,k]
+        float64, counts [B] int32)."""
+        B = len(queries_terms)
+        dim, q, _keep = self._query_args(qvecs, B)
+        pool, toff, qoff = pack_terms(queries_terms)
+        if group_off is None:
+            n_ids, ids, off = self._scope_args([g for g in group_scopes], len(group_scopes))
+            if off is None:                          # (a sequence without a list in it: no groups at all)
+                raise ValueError("group_scopes: a sequence of id arrays, or a flat array with group_off")
+        else:
+            ids = group_scopes if _is_torch(group_scopes) else np.ascontiguousarray(group_scopes, dtype=np.int64).reshape(-1)
+            n_ids, off = int(ids.shape[0]), np.ascontiguousarray(group_off, dtype=np.uint64)
+        qg = np.ascontiguousarray(query_group, dtype=np.int32).reshape(-1)
+        if qg.shape[0] != B:
+            raise ValueError(f"query_group: {qg.shape[0]} entries for {B} queries")
+        k = max(1, int(topk))
+        rows = np.full((B, k), -1, dtype=np.int64)
+        scores = np.zeros((B, k), dtype=np.float64)
+        counts = np.zeros(B, dtype=np.int32)
+        N.check(N.hip.orr_search_batch_masked_groups(self._h, B, dim, _ptr(q), _ptr(pool), _ptr(toff), _ptr(qoff), now_ticks, int(topk),
+                                                     int(candidate_limit), int(off.shape[0]) - 1, n_ids, _ptr(ids) if n_ids else None,
+                                                     _ptr(off), _ptr(qg), _ptr(rows), _ptr(scores), _ptr(counts)))
+        return rows, scores, counts
+
     def search_shard_scoped(self, qvecs, queries_terms, now_ticks: int, kprime: int, candidate_limit: int, scope_ids,
                             scope_before=None, topk: int = 0, out=None):
         """orr_search_shard_scoped: this shard's [B, kprime+1] records of a scoped search (for merge_candidates).  scope_before
@@ -413,10 +442,18 @@ class RecallIndex:
         N.check(N.hip.orr_index_search_stats(self._h, None, 1))
 
     def kernel_stats(self) -> dict:
-        arr = (N.OrrKernelStat * 32)()
-        n = N.hip.orr_index_kernel_stats(self._h, C.cast(arr, C.c_void_p), 32)
+        """orr_index_kernel_stats: every timed name since profiling was switched on (kernels, and host phases such as
+        "scope_id_table" or "grouped_screen_pairs").  The call reports how many names there are; the array grows to hold them
+        all (a grouped search with a list group beside it uses more than 32)."""
+        cap = 64
+        while True:
+            arr = (N.OrrKernelStat * cap)()
+            n = N.hip.orr_index_kernel_stats(self._h, C.cast(arr, C.c_void_p), cap)
+            if n <= cap:
+                break
+            cap = n
         return {arr[i].name.decode(): {"launches": int(arr[i].launches), "total_ms": float(arr[i].total_ms),
-                                       "algo_bytes": float(arr[i].algo_bytes)} for i in range(min(n, 32))}
+                                       "algo_bytes": float(arr[i].algo_bytes)} for i in range(max(n, 0))}
 
 
 class _BorrowedIndex(RecallIndex):
