@@ -400,6 +400,37 @@ int orr_search_batch_masked(orr_index *idx, int32_t B, int32_t dim, const float 
                             int64_t n_scope_ids, const int64_t *scope_ids,
                             int64_t *out_rows, double *out_scores, int32_t *out_counts);
 
+/* Row-sharded form of the masked search, with the record contract of orr_search_shard / orr_search_shard_scoped: [B][kprime+1]
+ * records (host or device `out`), the last record of each query its trailer; orr_merge_candidates(_ex) is used unchanged.
+ *   scope            ONE list shared by the batch (host or device memory), resolved as orr_search_batch_masked resolves it (id
+ *                    table, one bitmap, deleted rows left out; unknown ids, ids listed twice and ids carried by several rows as
+ *                    documented there).
+ *   candidate_limit  GLOBAL over scoped live rows: the shard lets its first took = min(live, max(0, max(1, candidate_limit) -
+ *                    scope_before)) scoped live rows take part, scope_before being the scope's live rows on the shards in front
+ *                    of this one (orr_index_scope_count there; ONE number, the scope is shared).  row_base only enters
+ *                    order_key.
+ *   kprime           ONE pass at the caller's kprime, no ladder inside: the caller's merge certifies.  Only the queries whose
+ *                    survivors' buffers overflowed repeat once inside the call with buffers sized from the measured counts;
+ *                    after that the trailer carries ORR_CAND_OVERFLOW.
+ *   pass             0: the library's choice -- the masked screen where it is eligible and pays for this shard's took rows in
+ *                    front of this shard's clip ("mask_screen"), else the list path; 1: the list path in parts
+ *                    ("mask_part_rows"), never the screen.  A kprime above a selection list (64), or a batch no two-stage form
+ *                    exists for, takes the list path whatever `pass` says (beyond a list: every scoped row scored, reduced to
+ *                    kprime records on the host).
+ *   topk             as orr_search_shard_ex (0: unknown): the floor comes from the min(kprime, topk)-th best of the shard's
+ *                    in-scope sample -- valid across shards, the global k-th best is at least every shard's.
+ *   trailer          order_key = took, matches = the valid records.  Behind the screen ORR_CAND_TWO_STAGE with the floor L in
+ *                    norm_b (every scoped row not offered scores below L); behind the list path no floor, and every record has
+ *                    ORR_CAND_DOT_EXACT.  took == 0 (an empty shard, an empty list, a limit used up in front): empty records
+ *                    and a trailer that cut nothing.
+ * It is a search: it takes a lane, runs beside other searches, works on views and counts in orr_search_stats (pass_mode 5 or 4).
+ * ORR_EINVAL before any device call: the masked call's argument errors, kprime < 1, topk < 0, pass outside {0, 1},
+ * scope_before < 0, out NULL. */
+int orr_search_shard_masked(orr_index *idx, int32_t B, int32_t dim, const float *q,
+                            const uint8_t *terms_utf8, const uint32_t *term_off, const uint32_t *query_term_off,
+                            int64_t now_ticks, int32_t kprime, int64_t candidate_limit, int32_t topk, int32_t pass,
+                            int64_t n_scope_ids, const int64_t *scope_ids, int64_t scope_before, orr_candidate *out);
+
 /* ---- grouped masked search: several large scopes share one screening pass ----
  * Requests that arrive together belong to different tenants, collections or time windows: G scopes, each shared by the queries
  * that name it.  Group g's ids are scope_ids[group_off[g] .. group_off[g + 1]) (scope_ids host or device memory; group_off
@@ -549,6 +580,33 @@ int        orr_cluster_search_batch(orr_cluster *c, int32_t B, int32_t dim, cons
                                     const uint32_t *query_term_off, int64_t now_ticks, int32_t topk,
                                     int64_t candidate_limit, int64_t *out_rows, double *out_scores,
                                     int32_t *out_counts);
+/* Search inside a scope over all shards: exactly what orr_search_batch_scoped / orr_search_batch_masked return on ONE index
+ * that holds all the cluster's rows in the global candidate order -- rows, order and fp64 scores bit for bit; candidate_limit
+ * counts scoped live rows over the whole cluster; an id carried by rows on different shards brings every live one of them.
+ * q_host AND scope_ids (and scope_off) are HOST memory, every shard's device reads them: a device pointer is ORR_EINVAL.  A null
+ * cluster or a bad scope argument (as documented for the single-index calls) is ORR_EINVAL with the outputs untouched, an
+ * unsealed cluster ORR_ESTATE.
+ * A call holds one search lane per shard from start to end.  Every shard counts the scope's live rows (orr_index_scope_count),
+ * the host splits the limit (scope_before = the live rows on the shards in front), every shard answers at once with k' records
+ * per query (orr_search_shard_scoped / orr_search_shard_masked, topk handed down), the host merges as orr_merge_candidates_ex
+ * does, and only the queries it cannot certify repeat: k' x 4 while a selection list holds it, then (masked) the list path
+ * (pass = 1), then k' x 4 up to the largest number of scoped rows any shard lets take part, where every scoped row is a record;
+ * ORR_EDEVICE if a query is uncertified even there.  One merge gathers at most 1 GiB of records (wider rungs run in slices of
+ * the queries).
+ * orr_cluster_search_stats counts searches, queries, passes (one per repeat, whatever the number of shards) and requeried; the
+ * shards' own orr_index_search_stats keep counting their passes.  The "exchange" option does NOT apply: the records of these
+ * two calls always come back through pinned host memory. */
+int        orr_cluster_search_batch_scoped(orr_cluster *c, int32_t B, int32_t dim, const float *q_host,
+                                           const uint8_t *terms_utf8, const uint32_t *term_off,
+                                           const uint32_t *query_term_off, int64_t now_ticks, int32_t topk,
+                                           int64_t candidate_limit, int64_t n_scope_ids, const int64_t *scope_ids,
+                                           const uint64_t *scope_off, int64_t *out_rows, double *out_scores,
+                                           int32_t *out_counts);
+int        orr_cluster_search_batch_masked(orr_cluster *c, int32_t B, int32_t dim, const float *q_host,
+                                           const uint8_t *terms_utf8, const uint32_t *term_off,
+                                           const uint32_t *query_term_off, int64_t now_ticks, int32_t topk,
+                                           int64_t candidate_limit, int64_t n_scope_ids, const int64_t *scope_ids,
+                                           int64_t *out_rows, double *out_scores, int32_t *out_counts);
 int        orr_cluster_search_stats(orr_cluster *c, orr_search_stats *out, int32_t reset);
 /* Integer options of a cluster; unknown names are ORR_EINVAL.
  *   "exchange"   0 (default): the per-shard [B][k'+1] candidate records come back through pinned host memory (every record is

@@ -88,6 +88,8 @@ hip.orr_search_batch_masked_groups.restype = C.c_int
 hip.orr_search_batch_masked_groups.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]
 hip.orr_search_shard_scoped.restype = C.c_int
 hip.orr_search_shard_scoped.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _i64, _vp, _vp, _vp, _vp]
+hip.orr_search_shard_masked.restype = C.c_int
+hip.orr_search_shard_masked.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, _i64, _vp, _i64, _vp]
 hip.orr_index_scope_count.restype = C.c_int
 hip.orr_index_scope_count.argtypes = [_vp, _i32, _i64, _vp, _vp, _vp]
 hip.orr_search_shard_ex.restype = C.c_int
@@ -148,6 +150,10 @@ hip.orr_cluster_rows.restype = _i64
 hip.orr_cluster_rows.argtypes = [_vp]
 hip.orr_cluster_search_batch.restype = C.c_int
 hip.orr_cluster_search_batch.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp]
+hip.orr_cluster_search_batch_scoped.restype = C.c_int
+hip.orr_cluster_search_batch_scoped.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp]
+hip.orr_cluster_search_batch_masked.restype = C.c_int
+hip.orr_cluster_search_batch_masked.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp]
 hip.orr_cluster_set_option.restype = C.c_int
 hip.orr_cluster_set_option.argtypes = [_vp, C.c_char_p, _i64]
 hip.orr_cluster_search_stats.restype = C.c_int
@@ -230,11 +236,11 @@ host.orrh_batcher_stats.argtypes = [_vp, _vp, _vp, _vp]
 EXPORTED_HIP_SYMBOLS = [
     "orr_abi_version", "orr_device_count", "orr_last_error", "orr_index_create", "orr_index_destroy",
     "orr_index_append", "orr_index_seal", "orr_index_rows", "orr_index_dim", "orr_search_batch",
-    "orr_search_shard", "orr_search_shard_ex", "orr_search_batch_scoped", "orr_search_batch_masked", "orr_search_batch_masked_groups", "orr_search_shard_scoped", "orr_index_scope_count", "orr_merge_candidates", "orr_merge_candidates_ex", "orr_index_set_profiling", "orr_index_kernel_stats",
+    "orr_search_shard", "orr_search_shard_ex", "orr_search_batch_scoped", "orr_search_batch_masked", "orr_search_batch_masked_groups", "orr_search_shard_scoped", "orr_search_shard_masked", "orr_index_scope_count", "orr_merge_candidates", "orr_merge_candidates_ex", "orr_index_set_profiling", "orr_index_kernel_stats",
     "orr_index_save", "orr_index_load", "orr_index_set_row_base", "orr_index_set_option", "orr_index_screen_dots", "orr_index_screen_i8_dots", "orr_index_screen_i8_consts", "orr_index_screen_i8_stream_dots", "orr_index_pass_dots", "orr_index_view",
     "orr_index_delete_rows", "orr_index_update_rows", "orr_index_insert_rows", "orr_cluster_insert_rows", "orr_index_live_rows", "orr_index_compact", "orr_cluster_compact", "orr_index_search_stats",
     "orr_cluster_create", "orr_cluster_destroy", "orr_cluster_shards", "orr_cluster_shard", "orr_cluster_seal", "orr_cluster_rows",
-    "orr_cluster_search_batch", "orr_cluster_search_stats", "orr_cluster_set_option",
+    "orr_cluster_search_batch", "orr_cluster_search_batch_scoped", "orr_cluster_search_batch_masked", "orr_cluster_search_stats", "orr_cluster_set_option",
 ]
 EXPORTED_HOST_SYMBOLS = ["orrh_is_blank", "orrh_lower_invariant", "orrh_query_terms", "orrh_build_snippet",
                          "orrh_round4", "orrh_has_sufficient_evidence", "orrh_format_score_f4", "orrh_last_error", "orrh_store_create", "orrh_store_destroy",

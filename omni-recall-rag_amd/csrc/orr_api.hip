@@ -38,6 +38,7 @@
 #include "orr_scope_plan.h"
 #include "orr_mask_plan.h"
 #include "orr_group_plan.h"
+#include "orr_cluster_scope_plan.h"
 #include "orr_token_index.h"
 
 namespace {
@@ -3843,12 +3844,18 @@ struct ScopeArgs {
     const int64_t *before;         // host [B] scoped live rows in the shards in front (orr_search_shard_scoped), or null
 };
 
-int check_scope(const orr_index *idx, int32_t B, const ScopeArgs &sc, const char *fn)
+int check_scope_args(int32_t B, const ScopeArgs &sc, const char *fn)
 {
     if (sc.n_ids < 0) return fail(ORR_EINVAL, "%s: n_scope_ids is negative", fn);
     if (sc.n_ids > 0 && !sc.ids) return fail(ORR_EINVAL, "%s: scope_ids is NULL with %lld ids", fn, (long long)sc.n_ids);
     if (B > 0 && !scope::offsets_valid(sc.off, B, sc.n_ids))
         return fail(ORR_EINVAL, "%s: scope_off must start at 0, never decrease and end at n_scope_ids", fn);
+    return ORR_OK;
+}
+
+int check_scope(const orr_index *idx, int32_t B, const ScopeArgs &sc, const char *fn)
+{
+    ORR_TRY(check_scope_args(B, sc, fn));
     if (!idx) return fail(ORR_EINVAL, "%s: null index", fn);
     return ORR_OK;
 }
@@ -4189,6 +4196,52 @@ int run_masked_pass(orr_index *idx, const BatchArgs &a, int32_t kprime, const Ma
     return ORR_OK;
 }
 
+// One rung of the list path for the queries `gids` of the call (ascending): the scope's first ms.took rows cut by rank into P
+// parts of at most mask_part_rows, each part a scoped pass of `form` over every query (for_each_scoped_part); the parts' records
+// in store [P][gids.size()][K + 1] as shards' records are laid out, the queries' exact norms in norms.  K: k' of a Selection
+// pass, the largest part of an AllRecords one.  `sl` is the call's slice (b0 = 0, every query of the call, one shared bitmap
+// in ws_scope_bm, which a part overwrites when there are several).
+int list_part_records(orr_index *idx, const BatchArgs &orig, const ScopeSlice &sl, const MaskScope &ms, const std::vector<int32_t> &gids,
+                      scope::Form form, int64_t K, bool requery, std::vector<orr_candidate> &store, std::vector<double> &norms)
+{
+    const bool all = form == scope::Form::AllRecords;
+    const int64_t part_rows = idx->opt_mask_part_rows;
+    const int64_t P = mask::part_count(ms.took, part_rows);
+    hipStream_t s = idx->stream;
+    uint32_t *h_live = const_cast<uint32_t *>(sl.live), *h_took = const_cast<uint32_t *>(sl.took);       // pin_scope: a part's counts land there
+    const size_t nb = gids.size(), rec_q = (size_t)K + 1;
+    const std::vector<uint32_t> q(gids.begin(), gids.end());                  // the slice's numbering is the call's
+    store.assign((size_t)P * nb * rec_q, orr_candidate{});
+    norms.assign(nb, 0.0);
+    for (int64_t j = 0; j < P; ++j) {
+        if (P > 1) {       // this part's bitmap and counts; candidate_limit is already in the clip to ms.took
+            const auto range = mask::part_range(j, ms.took, part_rows);
+            Timed t(idx, "mask_part", 8.0 * (double)ms.words);
+            HIP_TRY(orr::launch_mask_part(ms.bm, ms.words, ms.chunks, (uint64_t)range.first, (uint64_t)range.second,
+                                          idx->ws_scope_bm.as<uint32_t>(), s));
+            HIP_TRY(orr::launch_scope_counts(idx->ws_scope_bm.as<uint32_t>(), sl.words, 1, sl.nq, sl.d_limit,
+                                             idx->ws_scope_chunks.as<uint32_t>(), h_live, h_took, s));
+        }
+        HIP_TRY(hipStreamSynchronize(s));
+        collect_events(idx);
+        ORR_TRY(for_each_scoped_part(idx, orig, sl, q, form, all ? 1 : (int32_t)K, [&](const ScopedPart &pt) -> int {
+            for (size_t i = 0; i < pt.ids.size(); ++i) {
+                const size_t at = (size_t)(std::lower_bound(gids.begin(), gids.end(), pt.ids[i]) - gids.begin());
+                orr_candidate *dst = store.data() + ((size_t)j * nb + at) * rec_q;
+                const orr_candidate *src = pt.recs + i * ((size_t)pt.kprime + 1);
+                const size_t have = std::min<size_t>((size_t)pt.kprime, (size_t)K);
+                memcpy(dst, src, sizeof(orr_candidate) * have);
+                for (size_t e = have; e < (size_t)K; ++e) { memset(&dst[e], 0, sizeof(dst[e])); dst[e].row_id = -1; dst[e].order_key = -1; }
+                dst[K] = src[pt.kprime];
+                norms[at] = idx->h_norm_a[i];
+            }
+            if (requery && j == 0) idx->sstats.requeried += (int64_t)pt.ids.size();
+            return ORR_OK;
+        }));
+    }
+    return ORR_OK;
+}
+
 // The list path in parts for the queries `ids` of the call (ascending): the scope's first ms.took rows cut by rank into parts
 // of at most mask_part_rows, each part a scoped pass over every query (for_each_scoped_part), the parts' records merged per
 // query as shards in global order are; an uncertified query climbs scope::next_rung over all parts.  `sl` is the call's slice
@@ -4202,8 +4255,6 @@ int masked_list_path(orr_index *idx, const BatchArgs &orig, const ScopeSlice &sl
     const int64_t P = mask::part_count(ms.took, part_rows);
     if (P > (1 << 16)) return fail(ORR_EINVAL, "orr_search_batch_masked: mask_part_rows %lld cuts the scope into %lld parts", (long long)part_rows, (long long)P);
     const int64_t max_part = std::min<int64_t>(ms.took, part_rows);
-    hipStream_t s = idx->stream;
-    uint32_t *h_live = const_cast<uint32_t *>(sl.live), *h_took = const_cast<uint32_t *>(sl.took);       // pin_scope: a part's counts land there
     struct Todo { std::vector<int32_t> ids; scope::Rung rung; int repeats; };
     std::deque<Todo> todo(1, Todo{ids, scope::first_rung(take, max_part, orr::kSelWidth), requery ? 1 : 0});
     while (!todo.empty()) {
@@ -4213,40 +4264,12 @@ int masked_list_path(orr_index *idx, const BatchArgs &orig, const ScopeSlice &sl
         const int64_t K = all ? std::max<int64_t>(1, max_part) : r.rung.kprime;       // records per query and part
         const int32_t n_ids = (int32_t)r.ids.size();
         const int32_t group = mask::merge_group(n_ids, P, K, mask::kMergeBudgetBytes);
-        const size_t rec_q = (size_t)K + 1;
         Todo next{{}, {}, r.repeats + 1};
         for (int32_t g0 = 0; g0 < n_ids; g0 += group) {
             const std::vector<int32_t> gids(r.ids.begin() + g0, r.ids.begin() + std::min<int32_t>(n_ids, g0 + group));
-            const size_t nb = gids.size();
-            const std::vector<uint32_t> q(gids.begin(), gids.end());                  // the slice's numbering is the call's
-            std::vector<orr_candidate> store((size_t)P * nb * rec_q);
-            std::vector<double> norms(nb, 0.0);
-            for (int64_t j = 0; j < P; ++j) {
-                if (P > 1) {       // this part's bitmap and counts; candidate_limit is already in the clip to ms.took
-                    const auto range = mask::part_range(j, ms.took, part_rows);
-                    Timed t(idx, "mask_part", 8.0 * (double)ms.words);
-                    HIP_TRY(orr::launch_mask_part(ms.bm, ms.words, ms.chunks, (uint64_t)range.first, (uint64_t)range.second,
-                                                  idx->ws_scope_bm.as<uint32_t>(), s));
-                    HIP_TRY(orr::launch_scope_counts(idx->ws_scope_bm.as<uint32_t>(), sl.words, 1, sl.nq, sl.d_limit,
-                                                     idx->ws_scope_chunks.as<uint32_t>(), h_live, h_took, s));
-                }
-                HIP_TRY(hipStreamSynchronize(s));
-                collect_events(idx);
-                ORR_TRY(for_each_scoped_part(idx, orig, sl, q, r.rung.form, all ? 1 : (int32_t)K, [&](const ScopedPart &pt) -> int {
-                    for (size_t i = 0; i < pt.ids.size(); ++i) {
-                        const size_t at = (size_t)(std::lower_bound(gids.begin(), gids.end(), pt.ids[i]) - gids.begin());
-                        orr_candidate *dst = store.data() + ((size_t)j * nb + at) * rec_q;
-                        const orr_candidate *src = pt.recs + i * ((size_t)pt.kprime + 1);
-                        const size_t have = std::min<size_t>((size_t)pt.kprime, (size_t)K);
-                        memcpy(dst, src, sizeof(orr_candidate) * have);
-                        for (size_t e = have; e < (size_t)K; ++e) { memset(&dst[e], 0, sizeof(dst[e])); dst[e].row_id = -1; dst[e].order_key = -1; }
-                        dst[K] = src[pt.kprime];
-                        norms[at] = idx->h_norm_a[i];
-                    }
-                    if (r.repeats > 0 && j == 0) idx->sstats.requeried += (int64_t)pt.ids.size();
-                    return ORR_OK;
-                }));
-            }
+            std::vector<orr_candidate> store;
+            std::vector<double> norms;
+            ORR_TRY(list_part_records(idx, orig, sl, ms, gids, r.rung.form, K, r.repeats > 0, store, norms));
             SubBatch sb;
             BatchArgs cur;
             ORR_TRY(build_subset(idx, orig, gids, sb, cur));
@@ -4331,25 +4354,18 @@ int masked_screen_ladder(orr_index *idx, const BatchArgs &orig, const ScopeSlice
     return ORR_OK;
 }
 
-// orr_search_batch_masked on the lane the caller holds.
-int masked_batch(orr_index *idx, const BatchArgs &orig, const ScopeArgs &sc, int64_t *out_rows, double *out_scores, int32_t *out_counts)
+// The ONE scope of a masked call on the lane the caller holds (the id table exists): resolved to a shared bitmap whose first
+// `limit` live rows take part, kept beside the slice's (which the list path rewrites per part), clipped, the sample sized for
+// the caller's k.  ms.took == 0: nothing takes part, and nothing but words / live / took is set.
+int resolve_mask_scope(orr_index *idx, int32_t B, int32_t topk, const ScopeArgs &sc, int64_t limit_rows, ScopeSlice &sl, MaskScope &ms)
 {
-    const int32_t B = orig.B, take = std::max<int32_t>(1, orig.topk);
-    const bool use_cos = orig.dim > 0 && orig.dim == idx->dim;
-    for (size_t i = 0; i < (size_t)B * take; ++i) { out_rows[i] = -1; out_scores[i] = 0.0; }
-    if (out_counts) for (int32_t b = 0; b < B; ++b) out_counts[b] = 0;
-    if (idx->n_rows <= 0 || sc.n_ids == 0) return ORR_OK;
-    ORR_TRY(bind_device(idx));
-    ORR_TRY(ensure_scope_table(idx));
     hipStream_t s = idx->stream;
     // ---- resolve: one shared bitmap; live and took are the same for every query
-    const std::vector<int64_t> limit((size_t)B, std::max<int64_t>(1, orig.candidate_limit));
-    ScopeSlice sl;
+    const std::vector<int64_t> limit((size_t)B, limit_rows);
     ORR_TRY(build_scope_slice(idx, sc, limit, 0, B, sl));
-    MaskScope ms;
     ms.words = sl.words; ms.live = sl.live[0]; ms.took = sl.took[0];
     if (ms.took == 0) return ORR_OK;
-    // ---- the scope's bitmap is kept beside the slice's (which the list path rewrites per part); clip
+    // ---- the scope's bitmap is kept beside the slice's; clip
     const size_t bm_bytes = sizeof(uint32_t) * (size_t)ms.words, ch_bytes = sizeof(uint32_t) * (size_t)orr::scope_chunks(ms.words);
     ORR_TRY(idx->ws_mask_bm.reserve(bm_bytes));
     ORR_TRY(idx->ws_mask_chunks.reserve(ch_bytes));
@@ -4364,7 +4380,24 @@ int masked_batch(orr_index *idx, const BatchArgs &orig, const ScopeArgs &sc, int
     HIP_TRY(hipStreamSynchronize(s));
     collect_events(idx);
     ms.n_clip = std::min<int64_t>(*idx->pin_mask.as<int64_t>(), idx->n_rows);
-    ms.sample = mask::sample_rows(orig.topk, ms.took);
+    ms.sample = mask::sample_rows(topk, ms.took);
+    return ORR_OK;
+}
+
+// orr_search_batch_masked on the lane the caller holds.
+int masked_batch(orr_index *idx, const BatchArgs &orig, const ScopeArgs &sc, int64_t *out_rows, double *out_scores, int32_t *out_counts)
+{
+    const int32_t B = orig.B, take = std::max<int32_t>(1, orig.topk);
+    const bool use_cos = orig.dim > 0 && orig.dim == idx->dim;
+    for (size_t i = 0; i < (size_t)B * take; ++i) { out_rows[i] = -1; out_scores[i] = 0.0; }
+    if (out_counts) for (int32_t b = 0; b < B; ++b) out_counts[b] = 0;
+    if (idx->n_rows <= 0 || sc.n_ids == 0) return ORR_OK;
+    ORR_TRY(bind_device(idx));
+    ORR_TRY(ensure_scope_table(idx));
+    ScopeSlice sl;
+    MaskScope ms;
+    ORR_TRY(resolve_mask_scope(idx, B, orig.topk, sc, std::max<int64_t>(1, orig.candidate_limit), sl, ms));
+    if (ms.took == 0) return ORR_OK;
     // ---- the screen or the list path
     const bool eligible = mask::eligible(use_cos, idx->dim, orig.topk, orr::kSelWidth, ms.n_clip, idx->opt_two_stage, ms.took);
     std::vector<int32_t> ids((size_t)B);
@@ -4601,40 +4634,63 @@ int grouped_batch(orr_index *idx, const BatchArgs &call, const GroupArgs &ga, in
     return ORR_OK;
 }
 
-// The best kprime records of each query out of its K >= kprime AllRecords records, ranked by the exact key on the host, with the
-// trailer orr_search_shard leaves: the cut-off is the worst kept record's exact score (bound 0).
-void reduce_all_records(const orr_candidate *recs, int32_t nb, int32_t K, int32_t kprime, bool use_cos, const double *norms,
-                        const uint32_t *query_term_off, int64_t now_ticks, orr_candidate *out)
+// The best kprime records of each query out of the exact-dot records of P parts ([P][nb][K + 1], as shards' records are laid out:
+// one AllRecords pass, or the parts of the list path), ranked by the exact key on the host, with the trailer orr_search_shard
+// leaves.  What the reduction drops scores no better than the worst kept record (bound 0); what a part's own selection cut
+// keeps that part's cut-off, bound and overflow flag; order_key adds up to the rows that took part.
+void reduce_part_records(const orr_candidate *recs, int32_t P, int32_t nb, int64_t K, int32_t kprime, bool use_cos, const double *norms,
+                         const std::vector<int32_t> &n_terms, int64_t now_ticks, orr_candidate *out)
 {
-    std::vector<std::pair<Ranked, int32_t>> ranked;
+    std::vector<std::pair<Ranked, const orr_candidate *>> ranked;
     for (int32_t b = 0; b < nb; ++b) {
-        const orr_candidate *in = recs + (size_t)b * ((size_t)K + 1);
         orr_candidate *o = out + (size_t)b * ((size_t)kprime + 1);
-        const int32_t n = in[K].matches;
+        orr_candidate t = recs[(size_t)b * ((size_t)K + 1) + (size_t)K];       // part 0's trailer
+        // the cut-offs as finish_query reads them: the largest that is a number; NaN (everything left out is NaN too) only alone
+        double cut = -std::numeric_limits<double>::infinity();
+        bool nan_cut = false;
+        auto add_cut = [&](double c) { if (c != c) nan_cut = true; else if (c > cut) cut = c; };
+        add_cut(t.approx_score);
         ranked.clear();
-        for (int32_t i = 0; i < n; ++i) {
-            Ranked r;
-            r.score = exact_score(in[i], use_cos, use_cos ? norms[b] : 0.0, (int32_t)(query_term_off[b + 1] - query_term_off[b]), now_ticks);
-            r.order_key = in[i].order_key;
-            r.row_id = in[i].row_id;
-            ranked.push_back({r, i});
+        for (int32_t j = 0; j < P; ++j) {
+            const orr_candidate *in = recs + ((size_t)j * (size_t)nb + (size_t)b) * ((size_t)K + 1);
+            const orr_candidate &tj = in[K];
+            for (int32_t i = 0; i < tj.matches; ++i) {
+                if (in[i].row_id < 0 && in[i].order_key < 0) continue;
+                Ranked r;
+                r.score = exact_score(in[i], use_cos, use_cos ? norms[b] : 0.0, n_terms[(size_t)b], now_ticks);
+                r.order_key = in[i].order_key;
+                r.row_id = in[i].row_id;
+                ranked.push_back({r, &in[i]});
+            }
+            if (j == 0) continue;
+            t.order_key += tj.order_key;
+            t.flags |= tj.flags & ORR_CAND_OVERFLOW;
+            t.dot = std::max(t.dot, tj.dot);
+            add_cut(tj.approx_score);
         }
-        std::sort(ranked.begin(), ranked.end(), [](const std::pair<Ranked, int32_t> &x, const std::pair<Ranked, int32_t> &y) { return ranks_before(x.first, y.first); });
-        const int32_t kept = std::min<int32_t>(n, kprime);
+        std::sort(ranked.begin(), ranked.end(), [](const std::pair<Ranked, const orr_candidate *> &x, const std::pair<Ranked, const orr_candidate *> &y) { return ranks_before(x.first, y.first); });
+        const int32_t n = (int32_t)ranked.size(), kept = std::min<int32_t>(n, kprime);
         for (int32_t i = 0; i < kprime; ++i) {
             if (i < kept) {
-                o[i] = in[ranked[(size_t)i].second];
+                o[i] = *ranked[(size_t)i].second;
                 o[i].approx_score = ranked[(size_t)i].first.score;
             } else {
                 memset(&o[i], 0, sizeof(o[i]));
                 o[i].row_id = -1; o[i].order_key = -1;
             }
         }
-        orr_candidate t = in[K];
         t.matches = kept;
-        t.approx_score = n <= kprime ? -std::numeric_limits<double>::infinity() : ranked[(size_t)kept - 1].first.score;
+        if (n > kprime) add_cut(ranked[(size_t)kept - 1].first.score);
+        t.approx_score = cut == -std::numeric_limits<double>::infinity() && nan_cut ? std::numeric_limits<double>::quiet_NaN() : cut;
         o[kprime] = t;
     }
+}
+
+std::vector<int32_t> term_counts(const uint32_t *query_term_off, int32_t nb)
+{
+    std::vector<int32_t> n((size_t)nb);
+    for (int32_t b = 0; b < nb; ++b) n[(size_t)b] = (int32_t)(query_term_off[b + 1] - query_term_off[b]);
+    return n;
 }
 
 // orr_search_shard_scoped on the lane the caller holds: one pass at the caller's k', no ladder (the caller's merge certifies).
@@ -4664,12 +4720,136 @@ int scoped_shard(orr_index *idx, const BatchArgs &orig, const ScopeArgs &sc, int
             const size_t nb = pt.ids.size();
             if (all) {
                 reduced.resize(nb * rec_q);
-                reduce_all_records(pt.recs, (int32_t)nb, pt.kprime, kprime, use_cos, idx->h_norm_a.data(), pt.cur.query_term_off, pt.cur.now_ticks, reduced.data());
+                reduce_part_records(pt.recs, 1, (int32_t)nb, pt.kprime, kprime, use_cos, idx->h_norm_a.data(), term_counts(pt.cur.query_term_off, (int32_t)nb),
+                                    pt.cur.now_ticks, reduced.data());
             }
             HIP_TRY(hipMemcpy(out + (size_t)pt.ids[0] * rec_q, all ? reduced.data() : pt.recs, sizeof(orr_candidate) * nb * rec_q, hipMemcpyDefault));
             return ORR_OK;
         }));
     }
+    return ORR_OK;
+}
+
+// orr_index_scope_count on the lane the caller holds: out_live[b] = the live rows query b's scope resolves to on this shard.
+int scope_count_on_lane(orr_index *idx, int32_t B, const ScopeArgs &sc, int64_t *out_live)
+{
+    for (int32_t b = 0; b < B; ++b) out_live[b] = 0;
+    if (idx->n_rows <= 0 || sc.n_ids == 0) return ORR_OK;
+    ORR_TRY(bind_device(idx));
+    ORR_TRY(ensure_scope_table(idx));
+    const std::vector<int64_t> limit((size_t)B, std::numeric_limits<int64_t>::max());
+    const int32_t per = scope_slice_width(idx, B);
+    for (int32_t b0 = 0; b0 < B; b0 += per) {
+        ScopeSlice sl;
+        ORR_TRY(build_scope_slice(idx, sc, limit, b0, std::min<int32_t>(per, B - b0), sl));
+        for (int32_t i = 0; i < sl.nq; ++i) out_live[b0 + i] = (int64_t)sl.live[i];
+    }
+    return ORR_OK;
+}
+
+// ---- orr_search_shard_masked: the record form of the masked search, one pass at the caller's k' ----------------------------
+
+// The list path of the shard form for the queries `ids` of the call (ascending): one rung of the list path in parts
+// (list_part_records) at k' -- beyond a selection list the all-records form -- and the parts' records reduced to k' per query.
+// One part within a list is what the scoped pass wrote, trailer included.
+int masked_shard_list(orr_index *idx, const BatchArgs &orig, const ScopeSlice &sl, const MaskScope &ms, const std::vector<int32_t> &ids,
+                      int32_t kprime, orr_candidate *out)
+{
+    const bool use_cos = orig.dim > 0 && orig.dim == idx->dim;
+    const bool all = kprime > orr::kSelWidth;
+    const int64_t part_rows = idx->opt_mask_part_rows;
+    const int64_t P = mask::part_count(ms.took, part_rows);
+    if (P > (1 << 16)) return fail(ORR_EINVAL, "orr_search_shard_masked: mask_part_rows %lld cuts the scope into %lld parts", (long long)part_rows, (long long)P);
+    const int64_t K = all ? std::max<int64_t>({(int64_t)1, std::min<int64_t>(ms.took, part_rows)}) : (int64_t)kprime;   // records per query and part
+    const size_t rec_q = (size_t)kprime + 1;
+    const int32_t n_ids = (int32_t)ids.size();
+    const int32_t group = mask::merge_group(n_ids, P, K, mask::kMergeBudgetBytes);
+    std::vector<orr_candidate> store, reduced;
+    std::vector<double> norms;
+    for (int32_t g0 = 0; g0 < n_ids; g0 += group) {
+        const std::vector<int32_t> gids(ids.begin() + g0, ids.begin() + std::min<int32_t>(n_ids, g0 + group));
+        const int32_t nb = (int32_t)gids.size();
+        ORR_TRY(list_part_records(idx, orig, sl, ms, gids, all ? scope::Form::AllRecords : scope::Form::Selection, K, false, store, norms));
+        const orr_candidate *recs = store.data();
+        if (all || P > 1) {
+            std::vector<int32_t> n_terms((size_t)nb);
+            for (int32_t i = 0; i < nb; ++i) n_terms[(size_t)i] = (int32_t)(orig.query_term_off[gids[(size_t)i] + 1] - orig.query_term_off[gids[(size_t)i]]);
+            reduced.resize((size_t)nb * rec_q);
+            reduce_part_records(store.data(), (int32_t)P, nb, K, kprime, use_cos, norms.data(), n_terms, orig.now_ticks, reduced.data());
+            recs = reduced.data();
+        }
+        for (int32_t i = 0; i < nb; ++i)
+            HIP_TRY(hipMemcpy(out + (size_t)gids[(size_t)i] * rec_q, recs + (size_t)i * rec_q, sizeof(orr_candidate) * rec_q, hipMemcpyDefault));
+    }
+    return ORR_OK;
+}
+
+// The queries `ids` of the call (ascending) through ONE masked screen at k'; the queries whose survivors' buffers overflowed
+// repeat once, inside the call, with buffers sized from the measured counts (shard_pass_into's growth).  A pass plan_form finds
+// no two-stage form for goes down the list path.
+int masked_shard_screen(orr_index *idx, const BatchArgs &orig, const ScopeSlice &sl, const MaskScope &ms, const std::vector<int32_t> &ids,
+                        int32_t kprime, orr_candidate *out)
+{
+    const size_t rec_q = (size_t)kprime + 1;
+    std::vector<int32_t> active = ids;
+    for (int round = 0; round < 2; ++round) {
+        const size_t nb = active.size();
+        SubBatch sb;
+        BatchArgs cur;
+        ORR_TRY(build_subset(idx, orig, active, sb, cur));
+        PassPlan pass;
+        const float *q_host = nullptr;
+        const orr_candidate *recs = nullptr;
+        const int rc = retry_pass(idx, [&] { return run_masked_pass(idx, cur, kprime, ms, &q_host, &recs, pass); });
+        if (rc == kNotMaskable) return masked_shard_list(idx, orig, sl, ms, active, kprime, out);
+        if (rc != ORR_OK) return rc;
+        for (size_t i = 0; i < nb; ++i)
+            HIP_TRY(hipMemcpy(out + (size_t)active[i] * rec_q, recs + i * rec_q, sizeof(orr_candidate) * rec_q, hipMemcpyDefault));
+        const ShardOutcome o = outcome_of(idx, pass, ms.n_clip);
+        idx->sstats.passes += 1;
+        if (round > 0) idx->sstats.requeried += (int64_t)nb;
+        escalation::account_survivors(idx->sstats, o, nb);
+        if (round > 0 || !o.kept(nb)) break;
+        std::vector<int32_t> over;
+        uint32_t worst = 0, cap = 0;
+        for (size_t i = 0; i < nb; ++i)
+            if (o.overflowed(i)) { over.push_back(active[i]); worst = std::max(worst, o.survivors[i]); }
+        if (over.empty() || !escalation::grown_survivor_cap(o.pass_cap, worst, ms.n_clip, over.size(), &cap)) break;     // the caller's escalation
+        idx->sstats.buffer_growths += 1;                       // the index keeps the larger size, as for the unscoped search
+        if (cap > idx->survivor_cap) idx->survivor_cap = cap;
+        if (!idx->is_view || idx->internal_lane) publish_survivor_hint(const_cast<orr_index *>(owner_of(idx)), cap);
+        active.swap(over);
+    }
+    return ORR_OK;
+}
+
+// orr_search_shard_masked on the lane the caller holds: one pass at the caller's k', no ladder (the caller's merge certifies).
+// orig.topk: the k the floor's sample serves.
+int masked_shard(orr_index *idx, const BatchArgs &orig, const ScopeArgs &sc, int64_t scope_before, int32_t kprime, int32_t pass, orr_candidate *out)
+{
+    const int32_t B = orig.B;
+    const bool use_cos = orig.dim > 0 && orig.dim == idx->dim;
+    const size_t rec_q = (size_t)kprime + 1;
+    const int64_t limit = cscope::shard_limit(orig.candidate_limit, scope_before);
+    ORR_TRY(bind_device(idx));
+    auto nothing = [&]() -> int {                      // nothing on this shard takes part: empty records + trailers
+        HIP_TRY(hipMemcpy(out, empty_records(B, kprime).data(), sizeof(orr_candidate) * (size_t)B * rec_q, hipMemcpyDefault));
+        return ORR_OK;
+    };
+    if (idx->n_rows <= 0 || sc.n_ids == 0 || limit == 0) return nothing();
+    ORR_TRY(ensure_scope_table(idx));
+    ScopeSlice sl;
+    MaskScope ms;
+    ORR_TRY(resolve_mask_scope(idx, B, orig.topk, sc, limit, sl, ms));
+    if (ms.took == 0) return nothing();
+    std::vector<int32_t> ids((size_t)B);
+    std::iota(ids.begin(), ids.end(), 0);
+    const bool eligible = mask::eligible(use_cos, idx->dim, orig.topk, orr::kSelWidth, ms.n_clip, idx->opt_two_stage, ms.took);
+    if (pass != 0 || kprime > orr::kSelWidth || mask::choose(idx->opt_mask_screen, eligible, B, ms.took, ms.n_clip) == mask::Path::List)
+        return masked_shard_list(idx, orig, sl, ms, ids, kprime, out);
+    const int32_t per = mask::screen_slice(B, ms.sample);
+    for (int32_t b0 = 0; b0 < B; b0 += per)
+        ORR_TRY(masked_shard_screen(idx, orig, sl, ms, std::vector<int32_t>(ids.begin() + b0, ids.begin() + std::min<int32_t>(B, b0 + per)), kprime, out));
     return ORR_OK;
 }
 
@@ -4934,18 +5114,30 @@ int orr_index_scope_count(orr_index *idx, int32_t B, int64_t n_scope_ids, const 
     Lane ln = acquire_lane(idx);
     idx = ln.lane;
     std::lock_guard<std::mutex> lock(idx->mu);
-    for (int32_t b = 0; b < B; ++b) out_live[b] = 0;
-    if (idx->n_rows <= 0 || n_scope_ids == 0) return ORR_OK;
-    ORR_TRY(bind_device(idx));
-    ORR_TRY(ensure_scope_table(idx));
-    const std::vector<int64_t> limit((size_t)B, std::numeric_limits<int64_t>::max());
-    const int32_t per = scope_slice_width(idx, B);
-    for (int32_t b0 = 0; b0 < B; b0 += per) {
-        ScopeSlice sl;
-        ORR_TRY(build_scope_slice(idx, sc, limit, b0, std::min<int32_t>(per, B - b0), sl));
-        for (int32_t i = 0; i < sl.nq; ++i) out_live[b0 + i] = (int64_t)sl.live[i];
-    }
-    return ORR_OK;
+    return scope_count_on_lane(idx, B, sc, out_live);
+}
+
+int orr_search_shard_masked(orr_index *idx, int32_t B, int32_t dim, const float *q, const uint8_t *terms_utf8,
+                            const uint32_t *term_off, const uint32_t *query_term_off, int64_t now_ticks, int32_t kprime,
+                            int64_t candidate_limit, int32_t topk, int32_t pass, int64_t n_scope_ids, const int64_t *scope_ids,
+                            int64_t scope_before, orr_candidate *out)
+{
+    BatchArgs a{B, dim, q, terms_utf8, term_off, query_term_off, now_ticks, candidate_limit, kprime};
+    const ScopeArgs sc{n_scope_ids, scope_ids, nullptr, nullptr};
+    if (kprime < 1) return fail(ORR_EINVAL, "orr_search_shard_masked: kprime must be >= 1");
+    if (topk < 0) return fail(ORR_EINVAL, "orr_search_shard_masked: topk must be >= 0");
+    if (pass < 0 || pass > 1) return fail(ORR_EINVAL, "orr_search_shard_masked: pass takes 0 (the library's choice) or 1 (the list path)");
+    if (scope_before < 0) return fail(ORR_EINVAL, "orr_search_shard_masked: scope_before is negative");
+    if (!out) return fail(ORR_EINVAL, "orr_search_shard_masked: out is NULL");
+    ORR_TRY(check_scope(idx, B, sc, "orr_search_shard_masked"));
+    ORR_TRY(check_batch(idx, a, "orr_search_shard_masked"));
+    if (topk > 0) a.topk = std::min<int32_t>(kprime, topk);
+    Lane ln = acquire_lane(idx);                       // a search like any other: its own lane, concurrent with the others
+    idx = ln.lane;
+    std::lock_guard<std::mutex> lock(idx->mu);
+    idx->sstats.searches += 1;
+    idx->sstats.queries += B;
+    return masked_shard(idx, a, sc, scope_before, kprime, pass, out);
 }
 
 }  // extern "C"
@@ -5227,6 +5419,166 @@ Backend cluster_backend(orr_cluster *c, int64_t candidate_limit)
     return be;
 }
 
+// ---- scoped and masked search over the shards (orr_cluster_search_batch_scoped, orr_cluster_search_batch_masked) ----------
+// The call holds one lane per shard from its first step to its last.  Count: every shard resolves the scope and reports its
+// live rows; the host splits the global candidate_limit (cscope::split_limit).  Pass: every shard runs its shard form
+// (scoped_shard / masked_shard, which resolve the scope again on the lane: nothing of the count is kept on the device) at k'
+// into its slice of one record array in host memory.  Merge: merge_into, as orr_merge_candidates_ex.  Ladder: the uncertified
+// queries repeat as a compacted sub-batch on the next rung (cscope::next_rung).  The rules are orr_cluster_scope_plan.h's.
+struct ClusterScope {
+    bool masked;                   // one list shared by the batch through the masked shard form; else per-query lists (off) or a shared one
+    int64_t n_ids;
+    const int64_t *ids;            // host
+    const uint64_t *off;           // host [B + 1] or null
+};
+
+int cluster_scope_search(orr_cluster *c, const char *fn, const BatchArgs &orig, const ClusterScope &cs, int64_t *out_rows, double *out_scores,
+                         int32_t *out_counts)
+{
+    const int32_t G = (int32_t)c->shards.size(), B = orig.B, take = std::max<int32_t>(1, orig.topk);
+    const bool use_cos = orig.dim > 0 && orig.dim == c->dim;
+    for (size_t i = 0; i < (size_t)B * take; ++i) { out_rows[i] = -1; out_scores[i] = 0.0; }
+    if (out_counts) for (int32_t b = 0; b < B; ++b) out_counts[b] = 0;
+    {
+        std::lock_guard<std::mutex> l(c->stats_mu);
+        c->sstats.searches += 1;
+        c->sstats.queries += B;
+    }
+    if (cs.n_ids == 0) return ORR_OK;
+    // all lanes before any shard starts, in ascending shard order (acquire_in_order says why), kept for the call
+    std::vector<Lane> lanes;
+    std::vector<LanePool *> pools;
+    std::vector<LanePool::Make> makes;
+    for (orr_index *sh : c->shards) { pools.push_back(&sh->lanes); makes.push_back(lane_maker(sh)); }
+    acquire_in_order(pools, makes, lanes);
+    for (int32_t g = 0; g < G; ++g) adopt_survivor_hint(c->shards[(size_t)g], lanes[(size_t)g].lane);
+    std::vector<double> norms;
+    if (use_cos) {
+        norms.resize((size_t)B);
+        exact_norms(orig.q, B, orig.dim, norms.data());
+    }
+
+    // ---- count: live[g][b] (masked: one number per shard), then the split
+    const bool shared = cs.off == nullptr;
+    const int32_t nq = shared ? 1 : B;
+    std::vector<int64_t> live((size_t)G * (size_t)nq, 0);
+    const ScopeArgs whole{cs.n_ids, cs.ids, cs.off, nullptr};
+    ORR_TRY(for_each_shard(G, [&](int32_t g) -> int {
+        orr_index *sh = lanes[(size_t)g].lane;
+        std::lock_guard<std::mutex> lock(sh->mu);
+        return scope_count_on_lane(sh, nq, whole, live.data() + (size_t)g * (size_t)nq);
+    }));
+    std::vector<cscope::Split> split((size_t)nq);          // per query (a shared list: one for all)
+    for (int32_t b = 0; b < nq; ++b) {
+        std::vector<int64_t> col((size_t)G);
+        for (int32_t g = 0; g < G; ++g) col[(size_t)g] = live[(size_t)g * (size_t)nq + (size_t)b];
+        split[(size_t)b] = cscope::split_limit(col, orig.candidate_limit);
+    }
+    auto split_of = [&](int32_t b) -> const cscope::Split & { return split[shared ? 0 : (size_t)b]; };
+
+    // ---- the ladder
+    struct Todo { std::vector<int32_t> ids; cscope::Rung rung; int repeats; };
+    Todo first{{}, {}, 0};
+    int64_t total = 0;
+    for (int32_t b = 0; b < B; ++b)
+        if (split_of(b).total > 0) { first.ids.push_back(b); total = std::max(total, split_of(b).total); }
+    if (first.ids.empty()) return ORR_OK;
+    first.rung = cscope::first_rung(cs.masked, take, total, orr::kSelWidth);
+    std::deque<Todo> todo(1, std::move(first));
+    while (!todo.empty()) {
+        const Todo r = std::move(todo.front());
+        todo.pop_front();
+        const int32_t n_ids = (int32_t)r.ids.size(), kprime = (int32_t)std::min<int64_t>(r.rung.kprime, std::numeric_limits<int32_t>::max() - 1);
+        const size_t rec_q = (size_t)kprime + 1;
+        const int32_t per = cscope::merge_slice(n_ids, G, kprime, mask::kMergeBudgetBytes);
+        Todo next{{}, {}, r.repeats + 1};
+        int64_t largest = 0;
+        bool screened = false;
+        for (int32_t i0 = 0; i0 < n_ids; i0 += per) {
+            const std::vector<int32_t> ids(r.ids.begin() + i0, r.ids.begin() + std::min<int32_t>(n_ids, i0 + per));
+            const int32_t nb = (int32_t)ids.size();
+            SubBatch sb;
+            BatchArgs cur;
+            ORR_TRY(build_subset(lanes[0].lane, orig, ids, sb, cur));                  // (host-resident vectors: nothing of the lane is used)
+            std::vector<double> sub_norms((size_t)nb, 0.0);
+            if (use_cos) for (int32_t i = 0; i < nb; ++i) sub_norms[(size_t)i] = norms[(size_t)ids[(size_t)i]];
+            // the scopes of the sub-batch: a shared list as it is, per-query lists gathered in the sub-batch's order
+            std::vector<int64_t> sub_ids;
+            std::vector<uint64_t> sub_off;
+            ScopeArgs sc{cs.n_ids, cs.ids, cs.off, nullptr};
+            if (!shared && cur.B != orig.B) {
+                sub_off.assign(1, 0);
+                for (int32_t b : ids) {
+                    sub_ids.insert(sub_ids.end(), cs.ids + cs.off[b], cs.ids + cs.off[b + 1]);
+                    sub_off.push_back((uint64_t)sub_ids.size());
+                }
+                if (sub_ids.empty()) sub_ids.push_back(-1);                            // (every list empty: an id no row carries)
+                sc = ScopeArgs{(int64_t)sub_off.back(), sub_ids.data(), sub_off.data(), nullptr};
+            }
+            std::vector<int64_t> before((size_t)G * (size_t)nb);
+            for (int32_t g = 0; g < G; ++g)
+                for (int32_t i = 0; i < nb; ++i) before[(size_t)g * (size_t)nb + (size_t)i] = split_of(ids[(size_t)i]).before[(size_t)g];
+            std::vector<orr_candidate> recs((size_t)G * (size_t)nb * rec_q);
+            ORR_TRY(for_each_shard(G, [&](int32_t g) -> int {
+                orr_index *sh = lanes[(size_t)g].lane;
+                std::lock_guard<std::mutex> lock(sh->mu);
+                BatchArgs a = cur;
+                a.topk = std::min<int32_t>(kprime, take);                              // the floor's k: the global k-th best is at least every shard's
+                if (use_cos) a.norms_host = sub_norms.data();
+                orr_candidate *dst = recs.data() + (size_t)g * (size_t)nb * rec_q;
+                sh->sstats.searches += 1; sh->sstats.queries += nb;
+                if (cs.masked) return masked_shard(sh, a, sc, before[(size_t)g * (size_t)nb], kprime, r.rung.pass, dst);
+                ScopeArgs mine = sc;
+                mine.before = before.data() + (size_t)g * (size_t)nb;
+                return scoped_shard(sh, a, mine, kprime, dst);
+            }));
+            std::vector<uint8_t> cert;
+            ORR_TRY(merge_into(G, kprime, recs.data(), cur, use_cos, cur.q, use_cos ? sub_norms.data() : nullptr, ids, out_rows, out_scores, out_counts, cert));
+            for (int32_t i = 0; i < nb; ++i) {
+                if (cert[(size_t)i]) continue;
+                next.ids.push_back(ids[(size_t)i]);
+                largest = std::max(largest, split_of(ids[(size_t)i]).largest);
+                for (int32_t g = 0; g < G; ++g)
+                    screened = screened || (recs[((size_t)g * (size_t)nb + (size_t)i) * rec_q + (size_t)kprime].flags & ORR_CAND_TWO_STAGE) != 0;
+            }
+            std::lock_guard<std::mutex> l(c->stats_mu);
+            c->sstats.passes += 1;
+            c->sstats.pass_mode = cs.masked && r.rung.pass == 0 ? 5 : 4;
+            if (r.repeats > 0) c->sstats.requeried += nb;
+        }
+        if (next.ids.empty()) continue;
+        next.rung = cscope::next_rung(r.rung, cs.masked, screened, largest, orr::kSelWidth);
+        if (next.rung.done || next.repeats >= cscope::kMaxRungs)
+            return fail(ORR_EDEVICE, "%s: a pass with every scoped row a record left a query uncertified", fn);
+        todo.push_front(std::move(next));
+    }
+    return ORR_OK;
+}
+
+// The checks the two calls share; the cluster's shared lock is the caller's.
+int check_cluster_scope(orr_cluster *c, const char *fn, const BatchArgs &a, const ClusterScope &cs, const int64_t *out_rows, const double *out_scores)
+{
+    ORR_TRY(check_scope_args(a.B, ScopeArgs{cs.n_ids, cs.ids, cs.off, nullptr}, fn));       // (the scope before the handle, as the index calls check)
+    if (!c) return fail(ORR_EINVAL, "%s: null cluster", fn);
+    if (a.B <= 0) return fail(ORR_EINVAL, "%s: batch size must be positive", fn);
+    if (a.dim < 0) return fail(ORR_EINVAL, "%s: negative query dimension", fn);
+    if (a.dim > 0 && !a.q) return fail(ORR_EINVAL, "%s: q is NULL with dim %d", fn, a.dim);
+    if (!a.query_term_off) return fail(ORR_EINVAL, "%s: query_term_off is required", fn);
+    if (!out_rows || !out_scores) return fail(ORR_EINVAL, "%s: output buffers are required", fn);
+    if (a.dim > 0 && is_device_pointer(a.q)) return fail(ORR_EINVAL, "%s: the query vectors must be in host memory (every shard's device reads them)", fn);
+    if (cs.n_ids > 0 && is_device_pointer(cs.ids)) return fail(ORR_EINVAL, "%s: scope_ids must be in host memory (every shard's device reads them)", fn);
+    return ORR_OK;
+}
+
+int cluster_scope_call(orr_cluster *c, const char *fn, const BatchArgs &a, const ClusterScope &cs, int64_t *out_rows, double *out_scores,
+                       int32_t *out_counts)
+{
+    ORR_TRY(check_cluster_scope(c, fn, a, cs, out_rows, out_scores));
+    std::shared_lock<std::shared_mutex> lock(c->mu);   // searches run side by side; seal and destroy are exclusive
+    if (!c->sealed) return fail(ORR_ESTATE, "%s: the cluster is not sealed", fn);
+    return cluster_scope_search(c, fn, a, cs, out_rows, out_scores, out_counts);
+}
+
 }  // namespace
 
 extern "C" {
@@ -5417,6 +5769,24 @@ int orr_cluster_search_batch(orr_cluster *c, int32_t B, int32_t dim, const float
     for (int64_t i = 0; i < (int64_t)B * take; ++i) { out_rows[i] = -1; out_scores[i] = 0.0; }
     // k' per shard as orr_search_batch picks it for one shard: any shard may hold the whole top-k
     return escalate(be, a, escalation::initial_kprime(take, be.n_total, orr::kSelWidth), out_rows, out_scores, out_counts);
+}
+
+int orr_cluster_search_batch_scoped(orr_cluster *c, int32_t B, int32_t dim, const float *q_host, const uint8_t *terms_utf8,
+                                    const uint32_t *term_off, const uint32_t *query_term_off, int64_t now_ticks, int32_t topk,
+                                    int64_t candidate_limit, int64_t n_scope_ids, const int64_t *scope_ids, const uint64_t *scope_off,
+                                    int64_t *out_rows, double *out_scores, int32_t *out_counts)
+{
+    const BatchArgs a{B, dim, q_host, terms_utf8, term_off, query_term_off, now_ticks, candidate_limit, topk};
+    return cluster_scope_call(c, "orr_cluster_search_batch_scoped", a, ClusterScope{false, n_scope_ids, scope_ids, scope_off}, out_rows, out_scores, out_counts);
+}
+
+int orr_cluster_search_batch_masked(orr_cluster *c, int32_t B, int32_t dim, const float *q_host, const uint8_t *terms_utf8,
+                                    const uint32_t *term_off, const uint32_t *query_term_off, int64_t now_ticks, int32_t topk,
+                                    int64_t candidate_limit, int64_t n_scope_ids, const int64_t *scope_ids,
+                                    int64_t *out_rows, double *out_scores, int32_t *out_counts)
+{
+    const BatchArgs a{B, dim, q_host, terms_utf8, term_off, query_term_off, now_ticks, candidate_limit, topk};
+    return cluster_scope_call(c, "orr_cluster_search_batch_masked", a, ClusterScope{true, n_scope_ids, scope_ids, nullptr}, out_rows, out_scores, out_counts);
 }
 
 int orr_cluster_search_stats(orr_cluster *c, orr_search_stats *out, int32_t reset)

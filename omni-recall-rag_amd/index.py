@@ -349,6 +349,23 @@ class RecallIndex:
                                               _ptr(before), _ptr(out)))
         return out
 
+    def search_shard_masked(self, qvecs, queries_terms, now_ticks: int, kprime: int, candidate_limit: int, scope_ids,
+                            scope_before: int = 0, topk: int = 0, shard_pass: int = 0, out=None):
+        """orr_search_shard_masked: this shard's [B, kprime+1] records of a masked search (for merge_candidates).  scope_ids:
+        ONE flat list shared by the batch (numpy or torch, host or device); scope_before: the scope's live rows on the shards
+        in front (scope_count there); shard_pass: 0 the library's choice (the masked screen where it pays), 1 the list path."""
+        B = len(queries_terms)
+        dim, q, _keep = self._query_args(qvecs, B)
+        pool, toff, qoff = pack_terms(queries_terms)
+        ids = scope_ids if _is_torch(scope_ids) else np.ascontiguousarray(scope_ids, dtype=np.int64).reshape(-1)
+        n_ids = int(ids.shape[0])
+        if out is None:
+            out = np.zeros((B, kprime + 1), dtype=CAND_DTYPE)
+        N.check(N.hip.orr_search_shard_masked(self._h, B, dim, _ptr(q), _ptr(pool), _ptr(toff), _ptr(qoff), now_ticks, int(kprime),
+                                              int(candidate_limit), max(0, int(topk)), int(shard_pass), n_ids, _ptr(ids) if n_ids else None,
+                                              int(scope_before), _ptr(out)))
+        return out
+
     def scope_count(self, scope_ids, n_queries: int = 1) -> np.ndarray:
         """orr_index_scope_count: [n_queries] int64, the live rows each query's scope resolves to on this shard."""
         n_ids, ids, off = self._scope_args(scope_ids, n_queries)
@@ -525,6 +542,51 @@ class RecallCluster:
         counts = np.zeros(B, dtype=np.int32)
         N.check(N.hip.orr_cluster_search_batch(self._h, B, dim, _ptr(q), _ptr(pool), _ptr(toff), _ptr(qoff), now_ticks, int(topk),
                                                int(candidate_limit), _ptr(rows), _ptr(scores), _ptr(counts)))
+        return rows, scores, counts
+
+    def _host_query_args(self, qvecs, B: int):
+        if qvecs is None:
+            return 0, None
+        q = np.ascontiguousarray(qvecs, dtype=np.float32).reshape(B, -1)
+        dim = int(q.shape[1])
+        return dim, (q if dim > 0 else None)
+
+    def search_scoped(self, qvecs, queries_terms, now_ticks: int, topk: int, scope_ids, candidate_limit: int = 300, scope_off=None):
+        """orr_cluster_search_batch_scoped: RecallIndex.search_scoped over all shards, as one index holding all the rows would
+        answer.  qvecs and the scope in host memory (numpy): one flat list shared by all queries, a sequence of per-query lists,
+        or -- with scope_off [B+1] given -- the flat list the offsets cut."""
+        B = len(queries_terms)
+        dim, q = self._host_query_args(qvecs, B)
+        pool, toff, qoff = pack_terms(queries_terms)
+        if scope_off is None:
+            n_ids, ids, off = RecallIndex._scope_args(scope_ids, B)
+        else:
+            ids = np.ascontiguousarray(scope_ids, dtype=np.int64).reshape(-1)
+            n_ids, off = int(ids.shape[0]), np.ascontiguousarray(scope_off, dtype=np.uint64)
+        k = max(1, int(topk))
+        rows = np.full((B, k), -1, dtype=np.int64)
+        scores = np.zeros((B, k), dtype=np.float64)
+        counts = np.zeros(B, dtype=np.int32)
+        N.check(N.hip.orr_cluster_search_batch_scoped(self._h, B, dim, _ptr(q), _ptr(pool), _ptr(toff), _ptr(qoff), now_ticks, int(topk),
+                                                      int(candidate_limit), n_ids, _ptr(ids) if n_ids else None, _ptr(off),
+                                                      _ptr(rows), _ptr(scores), _ptr(counts)))
+        return rows, scores, counts
+
+    def search_masked(self, qvecs, queries_terms, now_ticks: int, topk: int, scope_ids, candidate_limit: int = 300):
+        """orr_cluster_search_batch_masked: RecallIndex.search_masked over all shards -- ONE scope shared by the batch (a flat
+        numpy list in host memory), every shard's masked screen at once.  qvecs in host memory (numpy) or None."""
+        B = len(queries_terms)
+        dim, q = self._host_query_args(qvecs, B)
+        pool, toff, qoff = pack_terms(queries_terms)
+        ids = np.ascontiguousarray(scope_ids, dtype=np.int64).reshape(-1)
+        n_ids = int(ids.shape[0])
+        k = max(1, int(topk))
+        rows = np.full((B, k), -1, dtype=np.int64)
+        scores = np.zeros((B, k), dtype=np.float64)
+        counts = np.zeros(B, dtype=np.int32)
+        N.check(N.hip.orr_cluster_search_batch_masked(self._h, B, dim, _ptr(q), _ptr(pool), _ptr(toff), _ptr(qoff), now_ticks, int(topk),
+                                                      int(candidate_limit), n_ids, _ptr(ids) if n_ids else None,
+                                                      _ptr(rows), _ptr(scores), _ptr(counts)))
         return rows, scores, counts
 
     def set_option(self, name: str, value: int) -> None:
