@@ -465,6 +465,81 @@ int orr_search_batch_masked_groups(orr_index *idx, int32_t B, int32_t dim, const
 int orr_index_scope_count(orr_index *idx, int32_t B, int64_t n_scope_ids, const int64_t *scope_ids,
                           const uint64_t *scope_off, int64_t *out_live);
 
+/* ---- scope handles: resolve a scope once, keep it through maintenance --------
+ * The scoped, masked and grouped calls above take their scope as a list of row ids and resolve it on every call.  An orr_scope
+ * is that resolve kept: a set of ROWS of one sealed shard, resident on its device as the bitmap the masked call builds, with
+ * its counts.  It is fixed when the rows are added and follows those rows wherever maintenance moves them:
+ *   orr_index_delete_rows      the deleted rows leave every scope
+ *   orr_index_compact          positions close up; every scope is carried along (it holds no deleted row, so nothing leaves)
+ *   orr_index_insert_rows      old rows move; every scope is carried along.  Rows inserted later belong to NO scope -- a time
+ *                              window whose interval covers them included -- until orr_scope_add_ids names them; that call
+ *                              looks up only the ids it is given and ORs them in
+ *   orr_index_update_rows, orr_index_set_row_base   touch no scope
+ * Unlike a view, a scope does not block compaction or insertion.  Scopes are not saved by orr_index_save.  A scope costs one
+ * bit per row of the shard plus its chunk counts (1.25 MB at 10M rows); ORR_ENOMEM when that does not fit.
+ *   orr_scope_create        resolves ids exactly as orr_search_batch_masked resolves its list: unknown ids and deleted rows are
+ *                           passed over, an id listed twice counts once, an id carried by several rows brings all of them.
+ *                           n_ids == 0 gives an empty scope.  ids may be host or device memory.
+ *   orr_scope_create_ticks  the live rows with ticks_from <= CreatedAtUtc.Ticks < ticks_to.  Half-open, so adjacent windows
+ *                           tile; ticks_from >= ticks_to gives an empty scope, not an error; INT64_MIN and INT64_MAX are the
+ *                           open ends.  Rows are in CreatedAt-descending order, so this costs two binary searches on the host
+ *                           and one fill, however large the window.
+ *   orr_scope_add_ids       adds the live rows that carry the ids; *out_added (may be NULL) = rows that were not in it before
+ *   orr_scope_combine       dst = dst AND src, dst OR src, or dst AND NOT src, in place; src is unchanged (src == dst is allowed)
+ *   orr_scope_rows          live rows in it now; -1 on an orphaned handle (or NULL)
+ *   orr_scope_row_ids       the ids of its live rows in candidate order into out_ids (host memory, room for cap ids); *out_n =
+ *                           their number.  Nothing is written beyond cap; ORR_EINVAL, after *out_n is set, when cap is too small
+ *   orr_scope_destroy       frees it (NULL is allowed)
+ * idx may be the owning index or any view of it.  A scope belongs to the shard it was made on: using it with another shard, or
+ * combining scopes of two shards, is ORR_EINVAL.  orr_index_destroy of the owning index frees the device memory of the scopes
+ * that are still alive and orphans them: every later call on one is ORR_ESTATE, orr_scope_rows is -1, and orr_scope_destroy
+ * still has to be called to free the host part.  orr_scope_destroy and orr_index_destroy may be called from different threads
+ * at the same time (the library serialises the two); a search, add_ids or combine on a scope must have returned before its
+ * index is destroyed, as for every other call on that index.
+ * If a delete, a compaction or an insertion has changed the rows but a device error then keeps the library from bringing a
+ * scope's counts up to date, the call returns that error, the shard itself is whole, and that scope is orphaned (ORR_ESTATE
+ * from then on) rather than searched with stale counts: make it again.
+ * Threads: searches hold a scope shared, so any number may search one scope at once; add_ids, combine (on dst) and destroy hold
+ * it exclusively and wait for them.  create, add_ids, combine and row_ids take a lane like a search.
+ * ORR_EINVAL before any device call, with the outputs untouched, and before the index handle is looked at: a NULL scope or out
+ * pointer, negative counts, ids NULL with n_ids > 0, op outside 0 .. 2. */
+typedef struct orr_scope orr_scope;      /* opaque: a set of rows of one sealed shard, resident on its device */
+#define ORR_SCOPE_AND    0
+#define ORR_SCOPE_OR     1
+#define ORR_SCOPE_ANDNOT 2
+int     orr_scope_create(orr_index *idx, int64_t n_ids, const int64_t *ids /* host or device */, orr_scope **out);
+int     orr_scope_create_ticks(orr_index *idx, int64_t ticks_from, int64_t ticks_to, orr_scope **out);
+int     orr_scope_add_ids(orr_scope *s, int64_t n_ids, const int64_t *ids /* host or device */, int64_t *out_added);
+int     orr_scope_combine(orr_scope *dst, int32_t op, const orr_scope *src);
+int64_t orr_scope_rows(const orr_scope *s);
+int     orr_scope_row_ids(orr_scope *s, int64_t cap, int64_t *out_ids /* host */, int64_t *out_n);
+void    orr_scope_destroy(orr_scope *s);
+
+/* orr_search_batch_masked with the scope taken from a handle: what orr_search_batch would return on a shard sealed from scratch
+ * from only the scope's live rows, in their present candidate order -- rows, order and fp64 scores bit for bit.
+ * candidate_limit counts the scope's live rows; an empty scope gives counts of 0; topk, dim 0 or another dimension, NaN order
+ * and ties follow orr_search_batch.  Nothing is resolved: no id crosses to the device, no lookup and no count runs, and when
+ * candidate_limit reaches every row of the scope not even the clip is computed.  The paths behind the resolve, "mask_screen",
+ * "mask_part_rows" and the statistics (pass_mode 5 or 4) are the masked call's.
+ * ORR_EINVAL: the masked call's argument errors, a NULL scope (before the index handle is looked at), a scope of another shard.
+ * ORR_ESTATE: an orphaned scope. */
+int orr_search_batch_in_scope(orr_index *idx, int32_t B, int32_t dim, const float *q,
+                              const uint8_t *terms_utf8, const uint32_t *term_off, const uint32_t *query_term_off,
+                              int64_t now_ticks, int32_t topk, int64_t candidate_limit, const orr_scope *scope,
+                              int64_t *out_rows, double *out_scores, int32_t *out_counts);
+
+/* orr_search_batch_masked_groups with the groups taken from handles: query b searches inside scopes[query_scope[b]], and its
+ * result is what orr_search_batch_in_scope returns for it with that scope.  n_scopes is 1 .. 64; scopes may repeat, overlap, be
+ * empty or be named by no query.  The scopes large enough to screen share one pass over the shard's shadow (pass_mode 6); the
+ * others, and queries that pass cannot certify, run as the in-scope call of their handle.  One used scope IS the in-scope call.
+ * ORR_EINVAL before any device call and before the index handle is looked at: n_scopes outside 1 .. 64, scopes or an entry of
+ * it NULL, query_scope NULL or an entry outside [0, n_scopes); then: a scope of another shard.  ORR_ESTATE: an orphaned scope. */
+int orr_search_batch_in_scopes(orr_index *idx, int32_t B, int32_t dim, const float *q,
+                               const uint8_t *terms_utf8, const uint32_t *term_off, const uint32_t *query_term_off,
+                               int64_t now_ticks, int32_t topk, int64_t candidate_limit,
+                               int32_t n_scopes, const orr_scope *const *scopes, const int32_t *query_scope /* host [B] */,
+                               int64_t *out_rows, double *out_scores, int32_t *out_counts);
+
 /* ---- tuning knobs ----------------------------------------------------------
  * Integer options of one index; unknown names are ORR_EINVAL.
  *   "dead_rows_before"  deleted rows in the shards in front of this one (default 0), see above.

@@ -38,6 +38,7 @@
 #include "orr_scope_plan.h"
 #include "orr_mask_plan.h"
 #include "orr_group_plan.h"
+#include "orr_scope_set_plan.h"
 #include "orr_cluster_scope_plan.h"
 #include "orr_token_index.h"
 
@@ -226,6 +227,9 @@ struct orr_index {
     // own masked call rewrites ws_scope_bm and ws_mask_bm), the groups' clips and samples; pinned: the clips as mask_clip leaves them
     DevBuf ws_group_bm, ws_group_chunks, ws_group_meta;
     PinnedBuf pin_group;
+    // scope handles (orr_scope) of this shard, on the OWNING index, under scope_mu: deletes clear their rows, compaction and
+    // insertion carry them along, orr_index_destroy orphans them
+    std::vector<orr_scope *> scopes;
     int opt_mask_screen = 0;           // "mask_screen": 0 by the cost rule, 1 whenever eligible, 2 never (orr_mask_plan.h)
     int64_t opt_mask_part_rows = mask::kDefaultPartRows;   // "mask_part_rows": scoped rows per part of the list path
 
@@ -249,6 +253,23 @@ struct orr_index {
     std::vector<PendingEvent> pending;
     std::vector<hipEvent_t> event_pool;
 };
+
+// A scope handle: a set of rows of one sealed shard as the bitmap scope_lookup writes (words % 4 == 0, deleted rows left out,
+// bits at or above n_rows clear), with what a masked search asks of a resolved scope.  Every operation keeps all of it current
+// (refresh_scope).  Searches hold mu shared; whatever writes the bitmap holds it exclusively.
+struct orr_scope {
+    std::atomic<orr_index *> owner{nullptr};   // the owning index; nullptr once that was destroyed (the handle is orphaned)
+    mutable std::shared_mutex mu;
+    int64_t n_rows = 0, words = 0;             // the shard's rows the bitmap covers, its words (scope::bitmap_bytes / 4)
+    uint32_t *bm = nullptr;                    // device [words]
+    uint32_t *chunks = nullptr;                // device [scope_chunks(words)], as launch_scope_counts leaves them
+    std::atomic<int64_t> live{0};              // set bits
+    int64_t n_clip_all = 0;                    // one past the last set bit
+};
+
+// orr_scope_destroy and the orphaning in orr_index_destroy exclude each other, whatever threads release the two handles: a
+// scope's destroy either finishes before its index lets go of it or finds itself orphaned.  Taken before scope_mu and a scope's mu.
+static std::mutex g_scope_life_mu;
 
 static int make_view(orr_index *parent, orr_index **out, bool internal);
 
@@ -692,6 +713,18 @@ void orr_index_destroy(orr_index *idx)
         if (idx->d_post_rows) (void)hipFree(idx->d_post_rows);
         if (idx->scope_tab_ids) (void)hipFree(idx->scope_tab_ids);
         if (idx->scope_tab_pos) (void)hipFree(idx->scope_tab_pos);
+        // scope handles that are still alive lose their device memory and their shard: every later call on one is ORR_ESTATE
+        std::lock_guard<std::mutex> life(g_scope_life_mu);
+        std::lock_guard<std::mutex> g(idx->scope_mu);
+        for (orr_scope *sc : idx->scopes) {
+            std::unique_lock<std::shared_mutex> w(sc->mu);
+            if (sc->bm) (void)hipFree(sc->bm);
+            if (sc->chunks) (void)hipFree(sc->chunks);
+            sc->bm = nullptr; sc->chunks = nullptr;
+            sc->live.store(-1);
+            sc->owner.store(nullptr);
+        }
+        idx->scopes.clear();
     } else {
         idx->emb_shadow.p = nullptr; idx->emb_shadow.cap = 0;
         for (DevBuf *b : {&idx->emb_i8, &idx->i8_scale, &idx->i8_rel_err, &idx->i8_rel_hat, &idx->i8_rowf, &idx->tok_bm, &idx->tok_bm_index}) { b->p = nullptr; b->cap = 0; }
@@ -1262,9 +1295,14 @@ int64_t orr_index_live_rows(const orr_index *idx)
 }
 
 // The id table of scoped searches goes when positions move (the caller holds Exclusive: no search reads it).
-static void drop_scope_table(orr_index *idx)
+// `held` is the caller's lock on the index's scope_mu (ScopeRemap takes it for the whole move): ensure_scope_table builds the
+// table under that mutex.
+static void drop_scope_table(orr_index *idx, const std::unique_lock<std::mutex> &held)
 {
-    std::lock_guard<std::mutex> g(idx->scope_mu);
+    if (!held.owns_lock() || held.mutex() != &idx->scope_mu) {
+        fprintf(stderr, "omnirecall: drop_scope_table without the index's scope_mu held\n");
+        abort();
+    }
     if (idx->scope_tab_ids) (void)hipFree(idx->scope_tab_ids);
     if (idx->scope_tab_pos) (void)hipFree(idx->scope_tab_pos);
     idx->scope_tab_ids = nullptr; idx->scope_tab_pos = nullptr;
@@ -1291,6 +1329,155 @@ static int live_rows_of_ids(orr_index *idx, const std::vector<int64_t> &want, st
     }
     return ORR_OK;
 }
+
+// ---- scope handles through maintenance (orr_scope; the rules are orr_scope_set_plan.h's) -------------------------------------
+
+static void free_scope_arrays(uint32_t *bm, uint32_t *chunks)
+{
+    if (bm) (void)hipFree(bm);
+    if (chunks) (void)hipFree(chunks);
+}
+
+// The bitmap and the chunk counts of a scope over `rows` rows (neither is initialised).
+static int alloc_scope_arrays(int64_t rows, uint32_t **bm, uint32_t **chunks, int64_t *words)
+{
+    *words = (int64_t)(scope::bitmap_bytes(rows) / 4);
+    *bm = nullptr; *chunks = nullptr;
+    int r = dev_alloc(bm, (size_t)*words);
+    if (r == ORR_OK) r = dev_alloc(chunks, (size_t)orr::scope_chunks(*words));
+    if (r != ORR_OK) { (void)hipGetLastError(); free_scope_arrays(*bm, *chunks); *bm = nullptr; *chunks = nullptr; }
+    return r;
+}
+
+// What a scope keeps beside its bitmap, brought up to date after the bitmap changed: the chunk counts, live, n_clip_all (as
+// mask_clip with took = live: the live-th set bit is the last one).  On the lane the caller holds; ends synchronised.
+static int refresh_scope(orr_index *lane, orr_scope *sc)
+{
+    hipStream_t s = lane->stream;
+    ORR_TRY(lane->pin_scope.reserve(16));              // [limit i64][live u32][took u32]
+    ORR_TRY(lane->ws_scope_meta.reserve(8));
+    ORR_TRY(lane->pin_mask.reserve(sizeof(int64_t)));
+    uint8_t *hp = lane->pin_scope.as<uint8_t>();
+    *reinterpret_cast<int64_t *>(hp) = std::numeric_limits<int64_t>::max();
+    uint32_t *h_live = reinterpret_cast<uint32_t *>(hp + 8);
+    HIP_TRY(hipMemcpyAsync(lane->ws_scope_meta.p, hp, 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(orr::launch_scope_counts(sc->bm, sc->words, 1, 1, lane->ws_scope_meta.as<int64_t>(), sc->chunks, h_live, h_live + 1, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const int64_t live = (int64_t)*h_live;
+    int64_t clip = 0;
+    if (live > 0) {
+        HIP_TRY(orr::launch_mask_clip(sc->bm, sc->words, sc->chunks, (uint32_t)live, lane->pin_mask.as<int64_t>(), s));
+        HIP_TRY(hipStreamSynchronize(s));
+        clip = std::min<int64_t>(*lane->pin_mask.as<int64_t>(), sc->n_rows);
+    }
+    collect_events(lane);
+    sc->n_clip_all = clip;
+    sc->live.store(live);
+    return ORR_OK;
+}
+
+// A scope loses its device memory and its shard: every later call on it is ORR_ESTATE (the caller holds sc->mu exclusively and
+// takes it out of the index's list).
+static void orphan_scope(orr_scope *sc)
+{
+    free_scope_arrays(sc->bm, sc->chunks);
+    sc->bm = nullptr; sc->chunks = nullptr;
+    sc->live.store(-1);
+    sc->owner.store(nullptr);
+}
+
+// Every scope of idx->scopes through change(scope) and refresh_scope.  A scope whose bitmap changed but whose counts could not
+// be brought up to date (a device error) must not be searched with stale counts: it is orphaned, and the first error returned.
+// The caller holds scope_mu.
+static int change_scopes(orr_index *idx, const std::function<int(size_t, orr_scope *)> &change)
+{
+    int r = ORR_OK;
+    std::vector<orr_scope *> kept;
+    for (size_t i = 0; i < idx->scopes.size(); ++i) {
+        orr_scope *sc = idx->scopes[i];
+        std::unique_lock<std::shared_mutex> w(sc->mu);
+        int ri = change(i, sc);
+        if (ri == ORR_OK) ri = refresh_scope(idx, sc);
+        if (ri == ORR_OK) { kept.push_back(sc); continue; }
+        (void)hipStreamSynchronize(idx->stream);
+        (void)hipGetLastError();
+        orphan_scope(sc);
+        if (r == ORR_OK) r = ri;
+    }
+    idx->scopes.swap(kept);
+    return r;
+}
+
+// orr_index_delete_rows: the newly deleted positions (device, n of them) leave every scope of the shard.
+static int scopes_drop_positions(orr_index *idx, const int64_t *d_pos, int64_t n)
+{
+    std::lock_guard<std::mutex> g(idx->scope_mu);
+    return change_scopes(idx, [&](size_t, orr_scope *sc) -> int {
+        Timed t(idx, "scope_clear_positions", 12.0 * (double)n);
+        HIP_TRY(orr::launch_scope_clear_positions(sc->bm, sc->words, d_pos, n, idx->stream));
+        return ORR_OK;
+    });
+}
+
+// Carries every scope of a shard through a move of its rows (orr_index_compact, orr_index_insert_rows) in three steps: alloc
+// (the new bitmaps, before the first row moves: ORR_ENOMEM leaves every scope as it was), run (ONE scope_remap launch for all
+// scopes, while the source list is still there), commit (the scopes take their new arrays; the counts are refreshed; a scope whose refresh fails is orphaned).  The
+// caller holds LanePool::Exclusive; the struct holds the shard's scope_mu from alloc on, so no scope comes or goes meanwhile.
+struct ScopeRemap {
+    orr_index *idx = nullptr;
+    std::unique_lock<std::mutex> reg;
+    int64_t new_rows = 0, new_words = 0;
+    std::vector<uint32_t *> bm, chunks;                // the new arrays, one pair per scope of idx->scopes
+    DevBuf ptrs;                                       // device: [old bitmaps x G][new bitmaps x G]
+    bool committed = false;
+    ~ScopeRemap()
+    {
+        if (!committed) for (size_t i = 0; i < bm.size(); ++i) free_scope_arrays(bm[i], chunks[i]);
+        ptrs.release();
+    }
+    int alloc(orr_index *index, int64_t rows)
+    {
+        idx = index; new_rows = rows;
+        reg = std::unique_lock<std::mutex>(idx->scope_mu);
+        const size_t G = idx->scopes.size();
+        if (G == 0) return ORR_OK;
+        for (size_t i = 0; i < G; ++i) {
+            uint32_t *b = nullptr, *c = nullptr;
+            ORR_TRY(alloc_scope_arrays(rows, &b, &c, &new_words));
+            bm.push_back(b); chunks.push_back(c);
+        }
+        return ptrs.reserve(sizeof(void *) * 2 * G);
+    }
+    // destination row d < first keeps its bit, row first + r takes that of old position src[r] (device), none when negative
+    int run(const int64_t *src, int64_t first)
+    {
+        const size_t G = bm.size();
+        if (G == 0) return ORR_OK;
+        hipStream_t s = idx->stream;
+        std::vector<const void *> h(2 * G);
+        for (size_t i = 0; i < G; ++i) { h[i] = idx->scopes[i]->bm; h[G + i] = bm[i]; }
+        HIP_TRY(hipMemcpy(ptrs.p, h.data(), sizeof(void *) * 2 * G, hipMemcpyHostToDevice));
+        {
+            Timed t(idx, "scope_remap", 8.0 * (double)(new_rows - first) + 8.0 * (double)G * (double)new_words);
+            HIP_TRY(orr::launch_scope_remap(src, first, new_rows, new_words, ptrs.as<const uint32_t *>(), idx->scopes[0]->words,
+                                            reinterpret_cast<uint32_t *const *>(ptrs.as<uint32_t *>() + G), (int32_t)G, s));
+        }
+        HIP_TRY(hipStreamSynchronize(s));
+        collect_events(idx);
+        return ORR_OK;
+    }
+    int commit()
+    {
+        committed = true;
+        if (bm.empty()) return ORR_OK;
+        return change_scopes(idx, [&](size_t i, orr_scope *sc) -> int {
+            free_scope_arrays(sc->bm, sc->chunks);
+            sc->bm = bm[i]; sc->chunks = chunks[i];
+            sc->n_rows = new_rows; sc->words = new_words;
+            return ORR_OK;
+        });
+    }
+};
 
 int orr_index_delete_rows(orr_index *idx, int64_t n, const int64_t *row_ids, int64_t *out_deleted)
 {
@@ -1324,6 +1511,7 @@ int orr_index_delete_rows(orr_index *idx, int64_t n, const int64_t *row_ids, int
         orr::launch_tombstone_rows(tmp.as<int64_t>(), (int32_t)fresh.size(), idx->d_norm_b, idx->d_created, idx->stream) != hipSuccess ||
         hipStreamSynchronize(idx->stream) != hipSuccess)
         r = fail(ORR_EDEVICE, "orr_index_delete_rows: device update failed");
+    if (r == ORR_OK) r = scopes_drop_positions(idx, tmp.as<int64_t>(), (int64_t)fresh.size());
     tmp.release();
     ORR_TRY(r);
     ORR_TRY(idx->d_dead.reserve(sizeof(int64_t) * merged.size()));
@@ -1431,6 +1619,8 @@ int orr_index_compact(orr_index *idx, int64_t *out_removed)
         }
         shift[(size_t)n] = (uint32_t)d;
     }
+    ScopeRemap scopes;                                 // (deleted rows are already absent from every scope: the remap only closes gaps)
+    ORR_TRY(scopes.alloc(idx, n_new));
     DevBuf d_live;
     ORR_TRY(d_live.reserve(sizeof(int64_t) * (size_t)std::max<int64_t>(n_new, 1)));
     int r = ORR_OK;
@@ -1492,7 +1682,7 @@ int orr_index_compact(orr_index *idx, int64_t *out_removed)
             if (w) HIP_TRY(hipMemcpy(idx->d_post_rows, rows.data(), sizeof(uint32_t) * w, hipMemcpyHostToDevice));
             idx->n_postings = w;
         }
-        return ORR_OK;
+        return scopes.run(d_live.as<int64_t>(), 0);    // (while d_live is there)
     };
     r = body();
     d_live.release();
@@ -1511,7 +1701,7 @@ int orr_index_compact(orr_index *idx, int64_t *out_removed)
     idx->dead.clear();
     idx->d_dead.release();
     idx->id_index.clear();
-    drop_scope_table(idx);
+    drop_scope_table(idx, scopes.reg);
     // derived copies are rebuilt at the next search that wants them; the lanes' borrowed pointers die with the lanes
     idx->emb_shadow.release(); idx->shadow_ready = false; idx->shadow_failed = false;
     idx->emb_i8.release(); idx->i8_scale.release(); idx->i8_rel_err.release(); idx->i8_rel_hat.release(); idx->i8_rowf.release();
@@ -1521,7 +1711,7 @@ int orr_index_compact(orr_index *idx, int64_t *out_removed)
     idx->lanes.update_shared([](LanePool::Shared &sh) { sh.dead_count = 0; });
     for (orr_index *l : idx->lanes.drain()) orr_index_destroy(l);
     if (out_removed) *out_removed = n_dead;
-    return ORR_OK;
+    return scopes.commit();
 }
 
 namespace {
@@ -1673,6 +1863,8 @@ int orr_index_insert_rows(orr_index *idx, int64_t n, int32_t dim, const float *e
         if (old_rows_move) ORR_TRY(fr.bounce.reserve(sizeof(float) * (size_t)std::min<int64_t>(chunk, n_moved) * D));
     }
     if (!new_dead.empty()) ORR_TRY(idx->d_dead.reserve(sizeof(int64_t) * new_dead.size()));
+    ScopeRemap scopes;                                 // the grown bitmaps of every scope handle
+    ORR_TRY(scopes.alloc(idx, total));
 
     auto body = [&]() -> int {
         HIP_TRY(hipMemcpyAsync(fr.src, src.data(), sizeof(int64_t) * (size_t)n_moved, hipMemcpyHostToDevice, s));
@@ -1738,7 +1930,7 @@ int orr_index_insert_rows(orr_index *idx, int64_t n, int32_t dim, const float *e
         if (!new_dead.empty()) HIP_TRY(hipMemcpyAsync(idx->d_dead.p, new_dead.data(), sizeof(int64_t) * new_dead.size(), hipMemcpyHostToDevice, s));
         HIP_TRY(hipStreamSynchronize(s));
         add_phase_stat(idx, "insert_scalars_and_upload", t_phase, 48.0 * (double)n_moved + 4.0 * (double)ti_new.post_rows.size());
-        return ORR_OK;
+        return scopes.run(fr.src, first);              // a new row is in no scope; fr.src goes with fr
     };
     const int r = body();
     if (r != ORR_OK)                                   // (rows may have moved: the shard is unusable, the caller rebuilds it)
@@ -1760,9 +1952,10 @@ int orr_index_insert_rows(orr_index *idx, int64_t n, int32_t dim, const float *e
         for (int64_t p = 0; p < total; ++p) idx->h_cprefix[(size_t)p + 1] = idx->h_cprefix[(size_t)p] + idx->h_clen[(size_t)p];
     }
     idx->n_rows = total;
+    const int scopes_r = scopes.commit();              // (reported at the end: the rows are in whatever it says)
     idx->dead = new_dead;                              // (their number is unchanged: the lanes' shared dead_count stays)
     idx->id_index.clear();
-    drop_scope_table(idx);
+    drop_scope_table(idx, scopes.reg);
     idx->n_vlong = -1; idx->n_vmid = 0;
     idx->bitmaps_clean = 0; idx->bitmaps_clean_of = nullptr;
     idx->tok_bm.release(); idx->tok_bm_index.release(); idx->n_tok_bm = -1; idx->tok_bm_words = 0;
@@ -1782,7 +1975,7 @@ int orr_index_insert_rows(orr_index *idx, int64_t n, int32_t dim, const float *e
     if (had_i8 && (ensure_i8_shadow(idx) != ORR_OK || !idx->i8_ready)) { (void)hipGetLastError(); drop_i8(); idx->i8_ready = false; idx->i8_failed = false; }
     if (had_bf16 && (ensure_shadow(idx) != ORR_OK || !idx->shadow_ready)) { (void)hipGetLastError(); idx->emb_shadow.release(); idx->shadow_ready = false; idx->shadow_failed = false; }
     if (had_i8 || had_bf16) add_phase_stat(idx, "insert_shadow_rebuild", t_phase, 0.0);
-    return ORR_OK;
+    return scopes_r;
 }
 
 // the sticky options (orr_index_set_option) a lane has in common with its index (kw_hits_cap: a lane that had grown its own
@@ -3907,6 +4100,8 @@ struct ScopeSlice {
     const uint32_t *live = nullptr;    // pinned host [nq]: live rows of each query's scope on this shard
     const uint32_t *took = nullptr;    // ... of which the first limit take part
     const int64_t *d_limit = nullptr;  // device [nq]
+    const uint32_t *bm = nullptr;      // device [n_bitmaps][words]: the lane's ws_scope_bm, or a scope handle's own (read-only)
+    const uint32_t *chunks = nullptr;  // device [n_bitmaps][scope_chunks(words)], likewise
 };
 
 // limit[b]: scoped live rows query b of the CALL lets take part.  Ends in a stream synchronise: live / took are final.
@@ -3952,6 +4147,35 @@ int build_scope_slice(orr_index *idx, const ScopeArgs &sc, const std::vector<int
     HIP_TRY(hipStreamSynchronize(s));
     collect_events(idx);
     sl.live = h_live; sl.took = h_took;
+    sl.bm = idx->ws_scope_bm.as<uint32_t>(); sl.chunks = idx->ws_scope_chunks.as<uint32_t>();
+    return ORR_OK;
+}
+
+// The slice of a call whose B queries share the scope of a handle: nothing is resolved, the numbers are the handle's and the
+// bitmap is the handle's own (a search never writes it: the list path writes its parts into the lane's workspace).  The caller
+// holds the scope shared.  No synchronise: the limits go up in stream order.
+int slice_of_handle(orr_index *idx, const orr_scope *h, int32_t B, int64_t limit_rows, ScopeSlice &sl)
+{
+    sl.b0 = 0; sl.nq = B; sl.n_bitmaps = 1; sl.words = h->words;
+    const size_t o_lim = sizeof(uint64_t) * ((size_t)B + 1), o_live = o_lim + sizeof(int64_t) * (size_t)B, o_took = o_live + sizeof(uint32_t) * (size_t)B;
+    ORR_TRY(idx->pin_scope.reserve(o_took + sizeof(uint32_t) * (size_t)B));      // build_scope_slice's block
+    ORR_TRY(idx->ws_scope_meta.reserve(o_live));
+    uint8_t *hp = idx->pin_scope.as<uint8_t>();
+    uint64_t *h_off = reinterpret_cast<uint64_t *>(hp);
+    int64_t *h_lim = reinterpret_cast<int64_t *>(hp + o_lim);
+    uint32_t *h_live = reinterpret_cast<uint32_t *>(hp + o_live), *h_took = reinterpret_cast<uint32_t *>(hp + o_took);
+    const int64_t live = h->live.load();
+    for (int32_t i = 0; i <= B; ++i) h_off[i] = 0;
+    for (int32_t i = 0; i < B; ++i) {
+        h_lim[i] = limit_rows;
+        h_live[i] = (uint32_t)live;
+        h_took[i] = (uint32_t)std::min<int64_t>(live, std::max<int64_t>(0, limit_rows));
+    }
+    uint8_t *dm = idx->ws_scope_meta.as<uint8_t>();
+    HIP_TRY(hipMemcpyAsync(dm, hp, o_live, hipMemcpyHostToDevice, idx->stream));
+    sl.d_limit = reinterpret_cast<const int64_t *>(dm + o_lim);
+    sl.live = h_live; sl.took = h_took;
+    sl.bm = h->bm; sl.chunks = h->chunks;
     return ORR_OK;
 }
 
@@ -4003,8 +4227,7 @@ int run_scoped_pass(orr_index *idx, const BatchArgs &a, const std::vector<uint32
     epi.cnt = idx->ws_fcnt.as<uint32_t>(); epi.buf = idx->ws_fbuf.as<orr::SelEntry>(); epi.cap = cap;
     {
         Timed t(idx, "scope_compact", 16.0 * (double)B * (double)worst);
-        HIP_TRY(orr::launch_scope_compact(idx->ws_scope_bm.as<uint32_t>(), sl.words, sl.n_bitmaps, idx->ws_scope_chunks.as<uint32_t>(),
-                                          idx->ws_scope_sel.as<uint32_t>(), B, sl.d_limit, epi.buf, cap, s));
+        HIP_TRY(orr::launch_scope_compact(sl.bm, sl.words, sl.n_bitmaps, sl.chunks, idx->ws_scope_sel.as<uint32_t>(), B, sl.d_limit, epi.buf, cap, s));
     }
 
     // ---- keyword side (its own stream), query constants, then the two join
@@ -4145,6 +4368,14 @@ int scoped_batch(orr_index *idx, const BatchArgs &orig, const ScopeArgs &sc, int
 // the mask exact, and the exact tail ranks what is left.  Large scopes that the cost rule leaves to the list path, ineligible
 // passes and the end of the ladder run the scoped pass over the bitmap in parts.  The rules are orr_mask_plan.h's.
 
+// Where the ONE scope of a masked call comes from: a list of ids, resolved by the call, or a scope handle (the caller holds it
+// shared and has checked that it belongs to this shard).
+struct ScopeSource {
+    const ScopeArgs *list = nullptr;
+    const orr_scope *handle = nullptr;
+    bool empty() const { return handle ? handle->live.load() <= 0 : list->n_ids == 0; }
+};
+
 constexpr int kNotMaskable = 2;        // run_masked_pass: plan_form found no two-stage form for the batch (k' beyond a list, no shadow): the list path
 
 // One masked pass over the queries of `a`: run_shard_once's front end and stages over rows [0, ms.n_clip), no prefix (the floor
@@ -4201,9 +4432,10 @@ int run_masked_pass(orr_index *idx, const BatchArgs &a, int32_t kprime, const Ma
 // in store [P][gids.size()][K + 1] as shards' records are laid out, the queries' exact norms in norms.  K: k' of a Selection
 // pass, the largest part of an AllRecords one.  `sl` is the call's slice (b0 = 0, every query of the call, one shared bitmap
 // in ws_scope_bm, which a part overwrites when there are several).
-int list_part_records(orr_index *idx, const BatchArgs &orig, const ScopeSlice &sl, const MaskScope &ms, const std::vector<int32_t> &gids,
+int list_part_records(orr_index *idx, const BatchArgs &orig, const ScopeSlice &call_sl, const MaskScope &ms, const std::vector<int32_t> &gids,
                       scope::Form form, int64_t K, bool requery, std::vector<orr_candidate> &store, std::vector<double> &norms)
 {
+    ScopeSlice sl = call_sl;
     const bool all = form == scope::Form::AllRecords;
     const int64_t part_rows = idx->opt_mask_part_rows;
     const int64_t P = mask::part_count(ms.took, part_rows);
@@ -4213,6 +4445,11 @@ int list_part_records(orr_index *idx, const BatchArgs &orig, const ScopeSlice &s
     const std::vector<uint32_t> q(gids.begin(), gids.end());                  // the slice's numbering is the call's
     store.assign((size_t)P * nb * rec_q, orr_candidate{});
     norms.assign(nb, 0.0);
+    if (P > 1) {           // the parts are written into the lane's own workspace, whoever owns the scope's bitmap
+        ORR_TRY(idx->ws_scope_bm.reserve(sizeof(uint32_t) * (size_t)sl.words));
+        ORR_TRY(idx->ws_scope_chunks.reserve(sizeof(uint32_t) * (size_t)orr::scope_chunks(sl.words)));
+        sl.bm = idx->ws_scope_bm.as<uint32_t>(); sl.chunks = idx->ws_scope_chunks.as<uint32_t>();
+    }
     for (int64_t j = 0; j < P; ++j) {
         if (P > 1) {       // this part's bitmap and counts; candidate_limit is already in the clip to ms.took
             const auto range = mask::part_range(j, ms.took, part_rows);
@@ -4357,12 +4594,35 @@ int masked_screen_ladder(orr_index *idx, const BatchArgs &orig, const ScopeSlice
 // The ONE scope of a masked call on the lane the caller holds (the id table exists): resolved to a shared bitmap whose first
 // `limit` live rows take part, kept beside the slice's (which the list path rewrites per part), clipped, the sample sized for
 // the caller's k.  ms.took == 0: nothing takes part, and nothing but words / live / took is set.
-int resolve_mask_scope(orr_index *idx, int32_t B, int32_t topk, const ScopeArgs &sc, int64_t limit_rows, ScopeSlice &sl, MaskScope &ms)
+// The source is a list of ids, resolved now, or a scope handle, which holds all of it already: then no id goes up, no lookup and
+// no count runs, the bitmap is read where it lies, and a call whose limit reaches every row of the scope takes the handle's
+// n_clip_all without a launch or a synchronise.
+int resolve_mask_scope(orr_index *idx, int32_t B, int32_t topk, const ScopeSource &src, int64_t limit_rows, ScopeSlice &sl, MaskScope &ms)
 {
     hipStream_t s = idx->stream;
+    if (src.handle) {
+        const orr_scope *h = src.handle;
+        ORR_TRY(slice_of_handle(idx, h, B, limit_rows, sl));
+        ms.words = sl.words; ms.live = sl.live[0]; ms.took = sl.took[0];
+        if (ms.took == 0) return ORR_OK;
+        ms.bm = h->bm; ms.chunks = h->chunks;
+        ms.n_clip = h->n_clip_all;
+        if (ms.took < ms.live) {
+            ORR_TRY(idx->pin_mask.reserve(sizeof(int64_t)));
+            {
+                Timed t(idx, "mask_clip", 4.0 * (double)orr::kScopeChunkWords + 4.0 * (double)orr::scope_chunks(ms.words));
+                HIP_TRY(orr::launch_mask_clip(ms.bm, ms.words, ms.chunks, (uint32_t)ms.took, idx->pin_mask.as<int64_t>(), s));
+            }
+            HIP_TRY(hipStreamSynchronize(s));
+            collect_events(idx);
+            ms.n_clip = std::min<int64_t>(*idx->pin_mask.as<int64_t>(), idx->n_rows);
+        }
+        ms.sample = mask::sample_rows(topk, ms.took);
+        return ORR_OK;
+    }
     // ---- resolve: one shared bitmap; live and took are the same for every query
     const std::vector<int64_t> limit((size_t)B, limit_rows);
-    ORR_TRY(build_scope_slice(idx, sc, limit, 0, B, sl));
+    ORR_TRY(build_scope_slice(idx, *src.list, limit, 0, B, sl));
     ms.words = sl.words; ms.live = sl.live[0]; ms.took = sl.took[0];
     if (ms.took == 0) return ORR_OK;
     // ---- the scope's bitmap is kept beside the slice's; clip
@@ -4385,18 +4645,18 @@ int resolve_mask_scope(orr_index *idx, int32_t B, int32_t topk, const ScopeArgs 
 }
 
 // orr_search_batch_masked on the lane the caller holds.
-int masked_batch(orr_index *idx, const BatchArgs &orig, const ScopeArgs &sc, int64_t *out_rows, double *out_scores, int32_t *out_counts)
+int masked_batch(orr_index *idx, const BatchArgs &orig, const ScopeSource &src, int64_t *out_rows, double *out_scores, int32_t *out_counts)
 {
     const int32_t B = orig.B, take = std::max<int32_t>(1, orig.topk);
     const bool use_cos = orig.dim > 0 && orig.dim == idx->dim;
     for (size_t i = 0; i < (size_t)B * take; ++i) { out_rows[i] = -1; out_scores[i] = 0.0; }
     if (out_counts) for (int32_t b = 0; b < B; ++b) out_counts[b] = 0;
-    if (idx->n_rows <= 0 || sc.n_ids == 0) return ORR_OK;
+    if (idx->n_rows <= 0 || src.empty()) return ORR_OK;
     ORR_TRY(bind_device(idx));
-    ORR_TRY(ensure_scope_table(idx));
+    if (src.list) ORR_TRY(ensure_scope_table(idx));
     ScopeSlice sl;
     MaskScope ms;
-    ORR_TRY(resolve_mask_scope(idx, B, orig.topk, sc, std::max<int64_t>(1, orig.candidate_limit), sl, ms));
+    ORR_TRY(resolve_mask_scope(idx, B, orig.topk, src, std::max<int64_t>(1, orig.candidate_limit), sl, ms));
     if (ms.took == 0) return ORR_OK;
     // ---- the screen or the list path
     const bool eligible = mask::eligible(use_cos, idx->dim, orig.topk, orr::kSelWidth, ms.n_clip, idx->opt_two_stage, ms.took);
@@ -4421,6 +4681,8 @@ struct GroupArgs {
     const int64_t *ids;            // host or device
     const uint64_t *off;           // host [n_groups + 1]
     const int32_t *query_group;    // host [B]
+    const orr_scope *const *scopes = nullptr;   // [n_groups] instead of the lists (orr_search_batch_in_scopes): held shared by the caller
+    bool listed(int32_t g) const { return scopes ? scopes[g]->live.load() > 0 : off[g + 1] > off[g]; }
 };
 
 // The queries `ids` of the call (ascending, all of group g) as a masked call of their own, the results scattered back.
@@ -4429,16 +4691,18 @@ int masked_sub_batch(orr_index *idx, const BatchArgs &orig, const GroupArgs &ga,
 {
     if (ids.empty()) return ORR_OK;
     const int32_t take = std::max<int32_t>(1, orig.topk);
-    const ScopeArgs sc{(int64_t)(ga.off[g + 1] - ga.off[g]), ga.ids ? ga.ids + ga.off[g] : nullptr, nullptr, nullptr};
+    ScopeArgs sc{0, nullptr, nullptr, nullptr};
+    if (!ga.scopes) sc = ScopeArgs{(int64_t)(ga.off[g + 1] - ga.off[g]), ga.ids ? ga.ids + ga.off[g] : nullptr, nullptr, nullptr};
+    const ScopeSource src{ga.scopes ? nullptr : &sc, ga.scopes ? ga.scopes[g] : nullptr};
     SubBatch sb;
     BatchArgs cur;
     ORR_TRY(build_subset(idx, orig, ids, sb, cur));
-    if (cur.B == orig.B) return masked_batch(idx, cur, sc, out_rows, out_scores, out_counts);       // every query of the call
+    if (cur.B == orig.B) return masked_batch(idx, cur, src, out_rows, out_scores, out_counts);      // every query of the call
     const size_t nb = ids.size();
     std::vector<int64_t> rows(nb * (size_t)take);
     std::vector<double> scores(nb * (size_t)take);
     std::vector<int32_t> counts(nb);
-    ORR_TRY(masked_batch(idx, cur, sc, rows.data(), scores.data(), counts.data()));
+    ORR_TRY(masked_batch(idx, cur, src, rows.data(), scores.data(), counts.data()));
     for (size_t i = 0; i < nb; ++i) {
         const size_t b = (size_t)ids[i];
         memcpy(out_rows + b * take, rows.data() + i * take, sizeof(int64_t) * take);
@@ -4534,14 +4798,14 @@ int grouped_batch(orr_index *idx, const BatchArgs &call, const GroupArgs &ga, in
     const bool use_cos = call.dim > 0 && call.dim == idx->dim;
     for (size_t i = 0; i < (size_t)B * take; ++i) { out_rows[i] = -1; out_scores[i] = 0.0; }
     if (out_counts) for (int32_t b = 0; b < B; ++b) out_counts[b] = 0;
-    if (idx->n_rows <= 0 || ga.n_ids == 0) return ORR_OK;
+    if (idx->n_rows <= 0 || (!ga.scopes && ga.n_ids == 0)) return ORR_OK;
     ORR_TRY(bind_device(idx));
     std::vector<std::vector<int32_t>> members((size_t)G);
     for (int32_t b = 0; b < B; ++b) members[(size_t)ga.query_group[b]].push_back(b);
     // ---- the groups that can be used at all; one of them: the masked call itself, nothing new runs
     int32_t named = 0, only = -1;
     for (int32_t g = 0; g < G; ++g)
-        if (!members[(size_t)g].empty() && ga.off[g + 1] > ga.off[g]) { named += 1; only = g; }
+        if (!members[(size_t)g].empty() && ga.listed(g)) { named += 1; only = g; }
     if (named == 0) return ORR_OK;
     if (named == 1 && (int32_t)members[(size_t)only].size() == B)        // (whole: the vectors stay where they are)
         return masked_sub_batch(idx, call, ga, only, members[(size_t)only], out_rows, out_scores, out_counts);
@@ -4554,15 +4818,21 @@ int grouped_batch(orr_index *idx, const BatchArgs &call, const GroupArgs &ga, in
         orig.q = q_down.data();
     }
     if (named == 1) return masked_sub_batch(idx, orig, ga, only, members[(size_t)only], out_rows, out_scores, out_counts);
-    ORR_TRY(ensure_scope_table(idx));
     hipStream_t s = idx->stream;
-    // ---- resolve: the groups as G pseudo-queries of a scoped slice -> G bitmaps, live and took per group
+    // ---- resolve: the groups as G pseudo-queries of a scoped slice -> G bitmaps, live and took per group; handles bring theirs
     const std::vector<int64_t> limit((size_t)G, std::max<int64_t>(1, call.candidate_limit));
     const ScopeArgs sc{ga.n_ids, ga.ids, ga.off, nullptr};
     ScopeSlice sl;
-    ORR_TRY(build_scope_slice(idx, sc, limit, 0, G, sl));
     std::vector<group::GroupIn> gin((size_t)G);
-    for (int32_t g = 0; g < G; ++g) { gin[(size_t)g].took = sl.took[g]; gin[(size_t)g].queries = (int32_t)members[(size_t)g].size(); }
+    if (ga.scopes) {
+        sl.words = ga.scopes[0]->words;
+        for (int32_t g = 0; g < G; ++g) gin[(size_t)g].took = std::min<int64_t>(ga.scopes[g]->live.load(), limit[(size_t)g]);
+    } else {
+        ORR_TRY(ensure_scope_table(idx));
+        ORR_TRY(build_scope_slice(idx, sc, limit, 0, G, sl));
+        for (int32_t g = 0; g < G; ++g) gin[(size_t)g].took = sl.took[g];
+    }
+    for (int32_t g = 0; g < G; ++g) gin[(size_t)g].queries = (int32_t)members[(size_t)g].size();
     int32_t n_used = 0;
     for (int32_t g = 0; g < G; ++g)
         if (group::used(gin[(size_t)g])) { n_used += 1; only = g; }
@@ -4577,20 +4847,38 @@ int grouped_batch(orr_index *idx, const BatchArgs &call, const GroupArgs &ga, in
     ORR_TRY(idx->ws_group_chunks.reserve(ch_bytes));
     ORR_TRY(idx->pin_group.reserve(sizeof(int64_t) * 2 * (size_t)G + sizeof(uint32_t) * (size_t)B));      // [clip x G][sample x G][screened x B]
     ORR_TRY(idx->ws_group_meta.reserve(sizeof(int64_t) * 2 * (size_t)G));
-    HIP_TRY(hipMemcpyAsync(idx->ws_group_bm.p, idx->ws_scope_bm.p, bm_bytes, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(idx->ws_group_chunks.p, idx->ws_scope_chunks.p, ch_bytes, hipMemcpyDeviceToDevice, s));
+    if (ga.scopes) {       // the used handles' arrays, gathered: the grouped stages want them contiguous (an unused group's are never read)
+        for (int32_t g = 0; g < G; ++g) {
+            if (!group::used(gin[(size_t)g])) continue;
+            HIP_TRY(hipMemcpyAsync(idx->ws_group_bm.as<uint32_t>() + (size_t)g * (size_t)sl.words, ga.scopes[g]->bm, sizeof(uint32_t) * (size_t)sl.words,
+                                   hipMemcpyDeviceToDevice, s));
+            HIP_TRY(hipMemcpyAsync(idx->ws_group_chunks.as<uint32_t>() + (size_t)g * (size_t)n_chunks, ga.scopes[g]->chunks,
+                                   sizeof(uint32_t) * (size_t)n_chunks, hipMemcpyDeviceToDevice, s));
+        }
+    } else {
+        HIP_TRY(hipMemcpyAsync(idx->ws_group_bm.p, idx->ws_scope_bm.p, bm_bytes, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(idx->ws_group_chunks.p, idx->ws_scope_chunks.p, ch_bytes, hipMemcpyDeviceToDevice, s));
+    }
     gs.bm = idx->ws_group_bm.as<uint32_t>(); gs.chunks = idx->ws_group_chunks.as<uint32_t>();
     int64_t *h_meta = idx->pin_group.as<int64_t>();            // [clip x G][sample x G]
     for (int32_t g = 0; g < 2 * G; ++g) h_meta[g] = 0;
+    bool clipped = false;
     for (int32_t g = 0; g < G; ++g) {
         if (!group::used(gin[(size_t)g])) continue;
+        if (ga.scopes && gin[(size_t)g].took == ga.scopes[g]->live.load()) continue;      // every row of the handle: its n_clip_all, below
         Timed t(idx, "mask_clip", 4.0 * (double)orr::kScopeChunkWords + 4.0 * (double)n_chunks);
         HIP_TRY(orr::launch_mask_clip(gs.bm + (size_t)g * (size_t)sl.words, sl.words, gs.chunks + (size_t)g * (size_t)n_chunks,
                                       (uint32_t)gin[(size_t)g].took, h_meta + g, s));
+        clipped = true;
     }
-    HIP_TRY(hipStreamSynchronize(s));
-    collect_events(idx);
-    for (int32_t g = 0; g < G; ++g) gin[(size_t)g].n_clip = std::min<int64_t>(h_meta[g], idx->n_rows);
+    if (clipped || !ga.scopes) {
+        HIP_TRY(hipStreamSynchronize(s));
+        collect_events(idx);
+    }
+    for (int32_t g = 0; g < G; ++g) {
+        if (ga.scopes && group::used(gin[(size_t)g]) && gin[(size_t)g].took == ga.scopes[g]->live.load()) h_meta[g] = ga.scopes[g]->n_clip_all;
+        gin[(size_t)g].n_clip = std::min<int64_t>(h_meta[g], idx->n_rows);
+    }
     // ---- the plan: samples, screen and list groups, the grouped pass or a masked call per group
     const uint32_t cap = group::pass_cap(idx->survivor_cap, B);
     const group::Plan plan = group::plan(gin, call.topk, cap, idx->opt_mask_screen, use_cos, idx->dim, orr::kSelWidth, idx->opt_two_stage);
@@ -4840,7 +5128,7 @@ int masked_shard(orr_index *idx, const BatchArgs &orig, const ScopeArgs &sc, int
     ORR_TRY(ensure_scope_table(idx));
     ScopeSlice sl;
     MaskScope ms;
-    ORR_TRY(resolve_mask_scope(idx, B, orig.topk, sc, limit, sl, ms));
+    ORR_TRY(resolve_mask_scope(idx, B, orig.topk, ScopeSource{&sc, nullptr}, limit, sl, ms));
     if (ms.took == 0) return nothing();
     std::vector<int32_t> ids((size_t)B);
     std::iota(ids.begin(), ids.end(), 0);
@@ -5051,7 +5339,7 @@ int orr_search_batch_masked(orr_index *idx, int32_t B, int32_t dim, const float 
     std::lock_guard<std::mutex> lock(idx->mu);
     idx->sstats.searches += 1;
     idx->sstats.queries += B;
-    return masked_batch(idx, a, sc, out_rows, out_scores, out_counts);
+    return masked_batch(idx, a, ScopeSource{&sc, nullptr}, out_rows, out_scores, out_counts);
 }
 
 int orr_search_batch_masked_groups(orr_index *idx, int32_t B, int32_t dim, const float *q, const uint8_t *terms_utf8,
@@ -5077,6 +5365,269 @@ int orr_search_batch_masked_groups(orr_index *idx, int32_t B, int32_t dim, const
     Lane ln = acquire_lane(idx);                       // a search like any other: its own lane, concurrent with the others
     idx = ln.lane;
     std::lock_guard<std::mutex> lock(idx->mu);
+    idx->sstats.searches += 1;
+    idx->sstats.queries += B;
+    return grouped_batch(idx, a, ga, out_rows, out_scores, out_counts);
+}
+
+// ---- scope handles (orr_scope): the resolve of a masked search, kept ---------------------------------------------------------
+
+// The shard of a scope, or the reason it cannot be used: ORR_ESTATE orphaned; with idx: ORR_EINVAL another shard.
+static int scope_owner(const orr_scope *sc, const orr_index *idx, const char *fn, orr_index **own)
+{
+    *own = sc->owner.load();
+    if (!*own) return fail(ORR_ESTATE, "%s: the scope is orphaned: its index was destroyed", fn);
+    if (idx && owner_of(idx) != *own) return fail(ORR_EINVAL, "%s: the scope belongs to another shard", fn);
+    return ORR_OK;
+}
+
+// ids (host or device) -> their live rows' bits OR-ed into the scope's bitmap, on the lane the caller holds
+static int scope_or_ids(orr_index *lane, orr_scope *sc, int64_t n_ids, const int64_t *ids)
+{
+    if (n_ids <= 0 || lane->n_rows <= 0) return ORR_OK;
+    ORR_TRY(ensure_scope_table(lane));
+    const orr_index *own = owner_of(lane);
+    ORR_TRY(lane->ws_scope_ids.reserve(sizeof(int64_t) * (size_t)n_ids));
+    HIP_TRY(hipMemcpyAsync(lane->ws_scope_ids.p, ids, sizeof(int64_t) * (size_t)n_ids, hipMemcpyDefault, lane->stream));
+    Timed t(lane, "scope_handle_lookup", 8.0 * (double)n_ids);
+    HIP_TRY(orr::launch_scope_lookup(own->scope_tab_ids, own->scope_tab_pos, lane->n_rows, lane->ws_scope_ids.as<int64_t>(), n_ids, nullptr, 1,
+                                     own->d_dead.as<int64_t>(), (int32_t)own->dead.size(), sc->bm, sc->words, lane->stream));
+    return ORR_OK;
+}
+
+// A new scope over the lane's shard filled by fill(scope), counted, and registered with the owning index.
+static int make_scope(orr_index *idx, const char *fn, orr_scope **out, const std::function<int(orr_index *, orr_scope *)> &fill)
+{
+    Lane ln = acquire_lane(idx);                       // the lookup runs like a search: its own lane, beside the others
+    orr_index *lane = ln.lane;
+    std::lock_guard<std::mutex> lock(lane->mu);
+    if (!lane->sealed) return fail(ORR_ESTATE, "%s: the index is not sealed", fn);
+    ORR_TRY(bind_device(lane));
+    orr_scope *sc = new (std::nothrow) orr_scope();
+    if (!sc) return fail(ORR_ENOMEM, "out of host memory");
+    sc->n_rows = lane->n_rows;
+    int r = alloc_scope_arrays(sc->n_rows, &sc->bm, &sc->chunks, &sc->words);
+    if (r == ORR_OK) r = fill(lane, sc);
+    if (r == ORR_OK) r = refresh_scope(lane, sc);
+    if (r != ORR_OK) {
+        (void)hipStreamSynchronize(lane->stream);
+        free_scope_arrays(sc->bm, sc->chunks);
+        delete sc;
+        return r;
+    }
+    orr_index *own = const_cast<orr_index *>(owner_of(lane));
+    sc->owner.store(own);
+    { std::lock_guard<std::mutex> g(own->scope_mu); own->scopes.push_back(sc); }
+    *out = sc;
+    return ORR_OK;
+}
+
+int orr_scope_create(orr_index *idx, int64_t n_ids, const int64_t *ids, orr_scope **out)
+{
+    if (!out) return fail(ORR_EINVAL, "orr_scope_create: out is NULL");
+    if (n_ids < 0) return fail(ORR_EINVAL, "orr_scope_create: n_ids is negative");
+    if (n_ids > 0 && !ids) return fail(ORR_EINVAL, "orr_scope_create: ids is NULL with %lld ids", (long long)n_ids);
+    if (!idx) return fail(ORR_EINVAL, "orr_scope_create: null index");
+    return make_scope(idx, "orr_scope_create", out, [&](orr_index *lane, orr_scope *sc) -> int {
+        HIP_TRY(hipMemsetAsync(sc->bm, 0, sizeof(uint32_t) * (size_t)sc->words, lane->stream));
+        return scope_or_ids(lane, sc, n_ids, ids);
+    });
+}
+
+int orr_scope_create_ticks(orr_index *idx, int64_t ticks_from, int64_t ticks_to, orr_scope **out)
+{
+    if (!out) return fail(ORR_EINVAL, "orr_scope_create_ticks: out is NULL");
+    if (!idx) return fail(ORR_EINVAL, "orr_scope_create_ticks: null index");
+    return make_scope(idx, "orr_scope_create_ticks", out, [&](orr_index *lane, orr_scope *sc) -> int {
+        const orr_index *own = owner_of(lane);         // the host mirror of the timestamps and the deleted set live there
+        const auto range = scope_set::ticks_range(own->h_created.data(), std::min<int64_t>((int64_t)own->h_created.size(), lane->n_rows), ticks_from, ticks_to);
+        {
+            Timed t(lane, "scope_fill_range", 4.0 * (double)sc->words);
+            HIP_TRY(orr::launch_scope_fill_range(sc->bm, sc->words, range.first, range.second, lane->stream));
+        }
+        Timed t(lane, "scope_clear_positions", 12.0 * (double)own->dead.size());
+        HIP_TRY(orr::launch_scope_clear_positions(sc->bm, sc->words, own->d_dead.as<int64_t>(), (int64_t)own->dead.size(), lane->stream));
+        return ORR_OK;
+    });
+}
+
+int orr_scope_add_ids(orr_scope *s, int64_t n_ids, const int64_t *ids, int64_t *out_added)
+{
+    if (n_ids < 0) return fail(ORR_EINVAL, "orr_scope_add_ids: n_ids is negative");
+    if (n_ids > 0 && !ids) return fail(ORR_EINVAL, "orr_scope_add_ids: ids is NULL with %lld ids", (long long)n_ids);
+    if (!s) return fail(ORR_EINVAL, "orr_scope_add_ids: null scope");
+    orr_index *own = nullptr;
+    ORR_TRY(scope_owner(s, nullptr, "orr_scope_add_ids", &own));
+    Lane ln = acquire_lane(own);
+    orr_index *lane = ln.lane;
+    std::lock_guard<std::mutex> lock(lane->mu);
+    std::unique_lock<std::shared_mutex> w(s->mu);
+    ORR_TRY(scope_owner(s, nullptr, "orr_scope_add_ids", &own));
+    ORR_TRY(bind_device(lane));
+    const int64_t before = s->live.load();
+    int r = scope_or_ids(lane, s, n_ids, ids);
+    if (r == ORR_OK) r = refresh_scope(lane, s);
+    if (r != ORR_OK) { (void)hipStreamSynchronize(lane->stream); return r; }
+    if (out_added) *out_added = s->live.load() - before;
+    return ORR_OK;
+}
+
+int orr_scope_combine(orr_scope *dst, int32_t op, const orr_scope *src)
+{
+    if (!scope_set::op_valid(op)) return fail(ORR_EINVAL, "orr_scope_combine: op must be ORR_SCOPE_AND (0), ORR_SCOPE_OR (1) or ORR_SCOPE_ANDNOT (2)");
+    if (!dst || !src) return fail(ORR_EINVAL, "orr_scope_combine: null scope");
+    orr_index *own = nullptr, *own_src = nullptr;
+    ORR_TRY(scope_owner(dst, nullptr, "orr_scope_combine", &own));
+    ORR_TRY(scope_owner(src, nullptr, "orr_scope_combine", &own_src));
+    if (own != own_src) return fail(ORR_EINVAL, "orr_scope_combine: the scopes belong to different shards");
+    Lane ln = acquire_lane(own);
+    orr_index *lane = ln.lane;
+    std::lock_guard<std::mutex> lock(lane->mu);
+    // dst exclusively, src shared, the lower address first (two combines with the roles swapped must not wait for each other)
+    std::unique_lock<std::shared_mutex> w(dst->mu, std::defer_lock);
+    std::shared_lock<std::shared_mutex> rd(src->mu, std::defer_lock);
+    if (src == dst) w.lock();
+    else if ((const void *)dst < (const void *)src) { w.lock(); rd.lock(); }
+    else { rd.lock(); w.lock(); }
+    ORR_TRY(scope_owner(dst, nullptr, "orr_scope_combine", &own));
+    ORR_TRY(scope_owner(src, nullptr, "orr_scope_combine", &own_src));
+    if (dst->words != src->words) return fail(ORR_ESTATE, "orr_scope_combine: the scopes cover different row counts");
+    ORR_TRY(bind_device(lane));
+    {
+        Timed t(lane, "scope_combine", 12.0 * (double)dst->words);
+        HIP_TRY(orr::launch_scope_combine(dst->bm, src->bm, dst->words, op, lane->stream));
+    }
+    const int r = refresh_scope(lane, dst);
+    if (r != ORR_OK) (void)hipStreamSynchronize(lane->stream);
+    return r;
+}
+
+int64_t orr_scope_rows(const orr_scope *s)
+{
+    if (!s || !s->owner.load()) return -1;
+    return s->live.load();
+}
+
+int orr_scope_row_ids(orr_scope *s, int64_t cap, int64_t *out_ids, int64_t *out_n)
+{
+    if (cap < 0) return fail(ORR_EINVAL, "orr_scope_row_ids: cap is negative");
+    if (!out_n) return fail(ORR_EINVAL, "orr_scope_row_ids: out_n is NULL");
+    if (cap > 0 && !out_ids) return fail(ORR_EINVAL, "orr_scope_row_ids: out_ids is NULL with room for %lld ids", (long long)cap);
+    if (!s) return fail(ORR_EINVAL, "orr_scope_row_ids: null scope");
+    orr_index *own = nullptr;
+    ORR_TRY(scope_owner(s, nullptr, "orr_scope_row_ids", &own));
+    Lane ln = acquire_lane(own);
+    orr_index *lane = ln.lane;
+    std::lock_guard<std::mutex> lock(lane->mu);
+    std::shared_lock<std::shared_mutex> rd(s->mu);
+    ORR_TRY(scope_owner(s, nullptr, "orr_scope_row_ids", &own));
+    const int64_t live = s->live.load();
+    *out_n = live;
+    if (live > cap) return fail(ORR_EINVAL, "orr_scope_row_ids: the scope holds %lld rows, out_ids has room for %lld", (long long)live, (long long)cap);
+    if (live == 0) return ORR_OK;
+    ORR_TRY(bind_device(lane));
+    hipStream_t st = lane->stream;
+    // the bitmap compacted into entries in candidate order (the scoped pass's kernel, one pseudo-query), then their ids gathered
+    const uint32_t ecap = scope::slice_cap((uint32_t)live);
+    DevBuf entries, d_ids;
+    auto body = [&]() -> int {
+        ORR_TRY(entries.reserve(sizeof(orr::SelEntry) * (size_t)ecap));
+        ORR_TRY(d_ids.reserve(sizeof(int64_t) * (size_t)live));
+        ORR_TRY(lane->pin_scope.reserve(16));
+        ORR_TRY(lane->ws_scope_meta.reserve(8));
+        ORR_TRY(lane->ws_scope_sel.reserve(sizeof(uint32_t)));
+        *lane->pin_scope.as<int64_t>() = live;
+        HIP_TRY(hipMemcpyAsync(lane->ws_scope_meta.p, lane->pin_scope.p, 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(lane->ws_scope_sel.p, 0, sizeof(uint32_t), st));
+        HIP_TRY(orr::launch_scope_compact(s->bm, s->words, 1, s->chunks, lane->ws_scope_sel.as<uint32_t>(), 1, lane->ws_scope_meta.as<int64_t>(),
+                                          entries.as<orr::SelEntry>(), ecap, st));
+        HIP_TRY(orr::launch_scope_entry_ids(entries.as<orr::SelEntry>(), live, lane->d_row_ids, lane->n_rows, d_ids.as<int64_t>(), st));
+        HIP_TRY(hipMemcpyAsync(out_ids, d_ids.p, sizeof(int64_t) * (size_t)live, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return ORR_OK;
+    };
+    const int r = body();
+    if (r != ORR_OK) (void)hipStreamSynchronize(st);
+    entries.release(); d_ids.release();
+    return r;
+}
+
+void orr_scope_destroy(orr_scope *s)
+{
+    if (!s) return;
+    std::lock_guard<std::mutex> life(g_scope_life_mu); // (the owning index is not destroyed meanwhile)
+    orr_index *own = s->owner.load();
+    if (own) {                                         // (the shard's maintenance holds scope_mu while it walks its scopes)
+        std::lock_guard<std::mutex> g(own->scope_mu);
+        own->scopes.erase(std::remove(own->scopes.begin(), own->scopes.end(), s), own->scopes.end());
+    }
+    {
+        std::unique_lock<std::shared_mutex> w(s->mu);  // waits for the searches that hold it
+        if (s->owner.load()) {
+            (void)hipSetDevice(own->device);
+            free_scope_arrays(s->bm, s->chunks);
+        }
+        s->bm = nullptr; s->chunks = nullptr;
+    }
+    delete s;
+}
+
+int orr_search_batch_in_scope(orr_index *idx, int32_t B, int32_t dim, const float *q, const uint8_t *terms_utf8,
+                              const uint32_t *term_off, const uint32_t *query_term_off, int64_t now_ticks, int32_t topk,
+                              int64_t candidate_limit, const orr_scope *scope, int64_t *out_rows, double *out_scores, int32_t *out_counts)
+{
+    static const char *fn = "orr_search_batch_in_scope";
+    BatchArgs a{B, dim, q, terms_utf8, term_off, query_term_off, now_ticks, candidate_limit, topk};
+    if (!scope) return fail(ORR_EINVAL, "%s: null scope", fn);
+    ORR_TRY(check_batch(idx, a, fn));
+    if (!out_rows || !out_scores) return fail(ORR_EINVAL, "%s: output buffers are required", fn);
+    orr_index *own = nullptr;
+    ORR_TRY(scope_owner(scope, idx, fn, &own));
+    Lane ln = acquire_lane(idx);                       // a search like any other: its own lane, concurrent with the others
+    idx = ln.lane;
+    std::lock_guard<std::mutex> lock(idx->mu);
+    std::shared_lock<std::shared_mutex> rd(scope->mu);
+    ORR_TRY(scope_owner(scope, idx, fn, &own));
+    if (scope->n_rows != idx->n_rows) return fail(ORR_ESTATE, "%s: the scope covers %lld rows, the handle %lld", fn, (long long)scope->n_rows, (long long)idx->n_rows);
+    idx->sstats.searches += 1;
+    idx->sstats.queries += B;
+    return masked_batch(idx, a, ScopeSource{nullptr, scope}, out_rows, out_scores, out_counts);
+}
+
+int orr_search_batch_in_scopes(orr_index *idx, int32_t B, int32_t dim, const float *q, const uint8_t *terms_utf8,
+                               const uint32_t *term_off, const uint32_t *query_term_off, int64_t now_ticks, int32_t topk,
+                               int64_t candidate_limit, int32_t n_scopes, const orr_scope *const *scopes, const int32_t *query_scope,
+                               int64_t *out_rows, double *out_scores, int32_t *out_counts)
+{
+    static const char *fn = "orr_search_batch_in_scopes";
+    BatchArgs a{B, dim, q, terms_utf8, term_off, query_term_off, now_ticks, candidate_limit, topk};
+    if (!scope_set::scopes_valid(n_scopes)) return fail(ORR_EINVAL, "%s: n_scopes must be in 1 .. %d", fn, scope_set::kMaxScopes);
+    if (!scopes) return fail(ORR_EINVAL, "%s: scopes is NULL", fn);
+    if (!query_scope) return fail(ORR_EINVAL, "%s: query_scope is NULL", fn);
+    if (B > 0 && !group::assignment_valid(query_scope, B, n_scopes))
+        return fail(ORR_EINVAL, "%s: query_scope must name a scope in 0 .. %d for every query", fn, n_scopes - 1);
+    for (int32_t g = 0; g < n_scopes; ++g)
+        if (!scopes[g]) return fail(ORR_EINVAL, "%s: scopes[%d] is a null scope", fn, g);
+    ORR_TRY(check_batch(idx, a, fn));
+    if (!out_rows || !out_scores) return fail(ORR_EINVAL, "%s: output buffers are required", fn);
+    orr_index *own = nullptr;
+    for (int32_t g = 0; g < n_scopes; ++g) ORR_TRY(scope_owner(scopes[g], idx, fn, &own));
+    Lane ln = acquire_lane(idx);
+    idx = ln.lane;
+    std::lock_guard<std::mutex> lock(idx->mu);
+    // every distinct scope shared, in address order
+    std::vector<const orr_scope *> distinct(scopes, scopes + n_scopes);
+    std::sort(distinct.begin(), distinct.end(), std::less<const orr_scope *>());
+    distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+    std::vector<std::shared_lock<std::shared_mutex>> held;
+    held.reserve(distinct.size());
+    for (const orr_scope *sc : distinct) held.emplace_back(sc->mu);
+    for (const orr_scope *sc : distinct) {
+        ORR_TRY(scope_owner(sc, idx, fn, &own));
+        if (sc->n_rows != idx->n_rows) return fail(ORR_ESTATE, "%s: a scope covers %lld rows, the handle %lld", fn, (long long)sc->n_rows, (long long)idx->n_rows);
+    }
+    GroupArgs ga{n_scopes, 0, nullptr, nullptr, query_scope};
+    ga.scopes = scopes;
     idx->sstats.searches += 1;
     idx->sstats.queries += B;
     return grouped_batch(idx, a, ga, out_rows, out_scores, out_counts);

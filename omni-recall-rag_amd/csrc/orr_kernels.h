@@ -9,6 +9,7 @@
 #include "orr_layout.h"
 #include "orr_scope_plan.h"
 #include "orr_mask_plan.h"
+#include "orr_scope_set_plan.h"
 
 #include <atomic>
 
@@ -457,5 +458,20 @@ hipError_t launch_mask_survivors_grouped(const uint32_t *bitmaps, int64_t words,
                                          uint32_t *cnt, uint32_t cap, SelEntry *buf, int32_t B, hipStream_t s);
 // launch_mask_trailers with took[b] (device) per query.
 hipError_t launch_mask_trailers_grouped(orr_candidate *recs, int32_t B, int32_t kprime, const int64_t *took, hipStream_t s);
+
+// ---- scope handles (orr_scope; the rules are orr_scope_set_plan.h's) ---------------------------------------------------------
+// bitmap (words, all written) = the bits [p0, p1); 0 <= p0, p1 <= words * 32.
+hipError_t launch_scope_fill_range(uint32_t *bitmap, int64_t words, int64_t p0, int64_t p1, hipStream_t s);
+// The bit of each of pos[0 .. n) (device) cleared.
+hipError_t launch_scope_clear_positions(uint32_t *bitmap, int64_t words, const int64_t *pos, int64_t n, hipStream_t s);
+// dst = dst AND / OR / ANDNOT src (scope_set::Op), in place; both of `words` words.
+hipError_t launch_scope_combine(uint32_t *dst, const uint32_t *src, int64_t words, int32_t op, hipStream_t s);
+// new_bm[g] (new_words words, all written) = old_bm[g] carried through a move of rows, for n_scopes bitmaps at once (the pointer
+// arrays are device memory): destination row d < first keeps its bit, row first + r < n_new takes the bit of old position
+// src[r] (device, n_new - first entries), none when src[r] < 0.  new_bm[g] must not alias old_bm[g].
+hipError_t launch_scope_remap(const int64_t *src, int64_t first, int64_t n_new, int64_t new_words, const uint32_t *const *old_bm,
+                              int64_t old_words, uint32_t *const *new_bm, int32_t n_scopes, hipStream_t s);
+// out[i] = row_ids[buf[i].pos] for the n entries launch_scope_compact left.
+hipError_t launch_scope_entry_ids(const SelEntry *buf, int64_t n, const int64_t *row_ids, int64_t n_rows, int64_t *out, hipStream_t s);
 
 }  // namespace orr

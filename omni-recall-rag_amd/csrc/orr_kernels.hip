@@ -2008,4 +2008,105 @@ hipError_t launch_mask_trailers_grouped(orr_candidate *recs, int32_t B, int32_t 
     return hipGetLastError();
 }
 
+// ---- scope handles (orr_scope; the rules are orr_scope_set_plan.h's) ---------------------------------------------------------
+// All of these stream a bitmap of a bit per row once: nothing next to a search.  They must be exact, not fast.
+
+// bits [p0, p1) set, every other bit of the `words` words clear: four words per thread, every word written
+__global__ __launch_bounds__(256) void scope_fill_range_kernel(uint32_t *__restrict__ bitmap, int64_t words, int64_t p0, int64_t p1)
+{
+    const int64_t w0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (w0 >= words) return;                           // (words is a multiple of 4: whole uint4s)
+    *reinterpret_cast<uint4 *>(bitmap + w0) = make_uint4(scope_set::range_word(w0, p0, p1), scope_set::range_word(w0 + 1, p0, p1),
+                                                         scope_set::range_word(w0 + 2, p0, p1), scope_set::range_word(w0 + 3, p0, p1));
+}
+
+hipError_t launch_scope_fill_range(uint32_t *bitmap, int64_t words, int64_t p0, int64_t p1, hipStream_t s)
+{
+    if (words <= 0 || words % 4 != 0 || p0 < 0 || p1 > words * 32) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(scope_fill_range_kernel, dim3((unsigned)((words / 4 + 255) / 256)), dim3(256), 0, s, bitmap, words, p0, p1);
+    return hipGetLastError();
+}
+
+// the bit of every listed position cleared (positions outside the bitmap are passed over)
+__global__ __launch_bounds__(256) void scope_clear_positions_kernel(uint32_t *__restrict__ bitmap, int64_t words, const int64_t *__restrict__ pos,
+                                                                    int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t p = pos[i];
+    if (p < 0 || p >= words * 32) return;
+    atomicAnd(bitmap + (p >> 5), ~(1u << (uint32_t)(p & 31)));
+}
+
+hipError_t launch_scope_clear_positions(uint32_t *bitmap, int64_t words, const int64_t *pos, int64_t n, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    if (words <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(scope_clear_positions_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, bitmap, words, pos, n);
+    return hipGetLastError();
+}
+
+// dst = dst op src over 16-byte vectors, in place (scope_set::combine_word)
+__global__ __launch_bounds__(256) void scope_combine_kernel(uint32_t *__restrict__ dst, const uint32_t *__restrict__ src, int64_t words, int32_t op)
+{
+    const int64_t w0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (w0 >= words) return;
+    const uint4 a = *reinterpret_cast<const uint4 *>(dst + w0), b = *reinterpret_cast<const uint4 *>(src + w0);
+    *reinterpret_cast<uint4 *>(dst + w0) = make_uint4(scope_set::combine_word(a.x, b.x, op), scope_set::combine_word(a.y, b.y, op),
+                                                      scope_set::combine_word(a.z, b.z, op), scope_set::combine_word(a.w, b.w, op));
+}
+
+hipError_t launch_scope_combine(uint32_t *dst, const uint32_t *src, int64_t words, int32_t op, hipStream_t s)
+{
+    if (words <= 0 || words % 4 != 0 || !scope_set::op_valid(op)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(scope_combine_kernel, dim3((unsigned)((words / 4 + 255) / 256)), dim3(256), 0, s, dst, src, words, op);
+    return hipGetLastError();
+}
+
+// Carries n_scopes bitmaps through a move of rows (compaction, insertion).  One lane per destination row: its source position
+// (scope_set::remap_source) is read ONCE, then for every scope the lane fetches its source bit and a ballot forms the wave's 64
+// destination bits, which lane 0 stores as one 8-byte word pair.  Every word of the new bitmaps is written; rows at or above
+// n_new and the padding words come out zero because remap_source gives them no source.  The sources of a wave are monotone and
+// almost consecutive (rows keep their order), so its source bits lie in two or three words that come from cache.
+__global__ __launch_bounds__(256) void scope_remap_kernel(const int64_t *__restrict__ src, int64_t first, int64_t n_new, int64_t new_words,
+                                                          const uint32_t *const *__restrict__ old_bm, int64_t old_words,
+                                                          uint32_t *const *__restrict__ new_bm, int32_t n_scopes)
+{
+    const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t d0 = d & ~(int64_t)63;               // the wave's first row: 64 rows = two whole words
+    if (d0 >= new_words * 32) return;                  // (wave-uniform; new_words is a multiple of 4)
+    const int64_t sp = scope_set::remap_source(d, first, n_new, src);
+    for (int32_t g = 0; g < n_scopes; ++g) {
+        const unsigned long long bits = __ballot(scope_set::bit_at(old_bm[g], old_words, sp) != 0u);
+        if ((threadIdx.x & 63) == 0) *reinterpret_cast<uint2 *>(new_bm[g] + (d0 >> 5)) = make_uint2((uint32_t)bits, (uint32_t)(bits >> 32));
+    }
+}
+
+hipError_t launch_scope_remap(const int64_t *src, int64_t first, int64_t n_new, int64_t new_words, const uint32_t *const *old_bm,
+                              int64_t old_words, uint32_t *const *new_bm, int32_t n_scopes, hipStream_t s)
+{
+    if (n_scopes <= 0) return hipSuccess;
+    if (new_words <= 0 || new_words % 4 != 0 || old_words <= 0 || first < 0 || n_new < first || n_new > new_words * 32) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(scope_remap_kernel, dim3((unsigned)((new_words * 32 + 255) / 256)), dim3(256), 0, s, src, first, n_new, new_words, old_bm,
+                       old_words, new_bm, n_scopes);
+    return hipGetLastError();
+}
+
+// out[i] = row_ids[buf[i].pos]: the ids of compacted scope entries, in candidate order
+__global__ __launch_bounds__(256) void scope_entry_ids_kernel(const SelEntry *__restrict__ buf, int64_t n, const int64_t *__restrict__ row_ids,
+                                                              int64_t n_rows, int64_t *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t p = buf[i].pos;
+    out[i] = (int64_t)p < n_rows ? row_ids[p] : -1;
+}
+
+hipError_t launch_scope_entry_ids(const SelEntry *buf, int64_t n, const int64_t *row_ids, int64_t n_rows, int64_t *out, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(scope_entry_ids_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, buf, n, row_ids, n_rows, out);
+    return hipGetLastError();
+}
+
 }  // namespace orr

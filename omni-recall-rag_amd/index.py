@@ -76,6 +76,64 @@ def pack_contents(contents: Sequence[bytes]) -> Tuple[np.ndarray, np.ndarray]:
     return pool, off
 
 
+class RecallScope:
+    """A scope handle (orr_scope): a set of ROWS of one sealed shard, resolved once and resident on its device.  It follows
+    its rows through delete_rows, compact and insert_rows of the shard; rows inserted later are in no scope until add_ids
+    names them.  Made by RecallIndex.scope / scope_ticks; close it before or after its index (after: only the host part is
+    left to free)."""
+
+    def __init__(self, handle, index: "RecallIndex"):
+        self._h = handle
+        self._index = index                  # keeps the index object alive
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            N.hip.orr_scope_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def rows(self) -> int:
+        """orr_scope_rows: live rows in the scope now; -1 once its index was destroyed."""
+        return int(N.hip.orr_scope_rows(self._h))
+
+    def row_ids(self) -> np.ndarray:
+        """orr_scope_row_ids: the ids of the scope's live rows, in candidate order."""
+        n = C.c_int64(0)
+        out = np.zeros(max(self.rows, 0), dtype=np.int64)
+        N.check(N.hip.orr_scope_row_ids(self._h, int(out.shape[0]), _ptr(out) if out.shape[0] else None, C.cast(C.byref(n), C.c_void_p)))
+        return out[:int(n.value)]
+
+    def add_ids(self, row_ids) -> int:
+        """orr_scope_add_ids: the live rows that carry these ids join the scope.  Returns how many were not in it before."""
+        ids = row_ids if _is_torch(row_ids) else np.ascontiguousarray(row_ids, dtype=np.int64).reshape(-1)
+        n_ids = int(ids.shape[0])
+        added = C.c_int64(0)
+        N.check(N.hip.orr_scope_add_ids(self._h, n_ids, _ptr(ids) if n_ids else None, C.cast(C.byref(added), C.c_void_p)))
+        return int(added.value)
+
+    def _combine(self, op: int, other: "RecallScope") -> "RecallScope":
+        N.check(N.hip.orr_scope_combine(self._h, op, other._h))
+        return self
+
+    def and_(self, other: "RecallScope") -> "RecallScope":
+        """self = self AND other, in place."""
+        return self._combine(N.ORR_SCOPE_AND, other)
+
+    def or_(self, other: "RecallScope") -> "RecallScope":
+        """self = self OR other, in place."""
+        return self._combine(N.ORR_SCOPE_OR, other)
+
+    def andnot(self, other: "RecallScope") -> "RecallScope":
+        """self = self AND NOT other, in place."""
+        return self._combine(N.ORR_SCOPE_ANDNOT, other)
+
+
 class RecallIndex:
     """One corpus shard resident on one GPU (orr_index)."""
 
@@ -331,6 +389,54 @@ class RecallIndex:
         N.check(N.hip.orr_search_batch_masked_groups(self._h, B, dim, _ptr(q), _ptr(pool), _ptr(toff), _ptr(qoff), now_ticks, int(topk),
                                                      int(candidate_limit), int(off.shape[0]) - 1, n_ids, _ptr(ids) if n_ids else None,
                                                      _ptr(off), _ptr(qg), _ptr(rows), _ptr(scores), _ptr(counts)))
+        return rows, scores, counts
+
+    def scope(self, row_ids) -> RecallScope:
+        """orr_scope_create: the live rows that carry these ids (numpy or torch, host or device), resolved once."""
+        ids = row_ids if _is_torch(row_ids) else np.ascontiguousarray(row_ids, dtype=np.int64).reshape(-1)
+        n_ids = int(ids.shape[0])
+        h = C.c_void_p()
+        N.check(N.hip.orr_scope_create(self._h, n_ids, _ptr(ids) if n_ids else None, C.byref(h)))
+        return RecallScope(h, self)
+
+    def scope_ticks(self, ticks_from: int, ticks_to: int) -> RecallScope:
+        """orr_scope_create_ticks: the live rows with ticks_from <= CreatedAtUtc.Ticks < ticks_to."""
+        h = C.c_void_p()
+        N.check(N.hip.orr_scope_create_ticks(self._h, int(ticks_from), int(ticks_to), C.byref(h)))
+        return RecallScope(h, self)
+
+    def search_in_scope(self, qvecs, queries_terms, now_ticks: int, topk: int, scope: RecallScope, candidate_limit: int = 300):
+        """orr_search_batch_in_scope: search_masked with the scope taken from a handle -- nothing is resolved per call.
+        Returns (rows [B,k] int64, scores [B,k] float64, counts [B] int32)."""
+        B = len(queries_terms)
+        dim, q, _keep = self._query_args(qvecs, B)
+        pool, toff, qoff = pack_terms(queries_terms)
+        k = max(1, int(topk))
+        rows = np.full((B, k), -1, dtype=np.int64)
+        scores = np.zeros((B, k), dtype=np.float64)
+        counts = np.zeros(B, dtype=np.int32)
+        N.check(N.hip.orr_search_batch_in_scope(self._h, B, dim, _ptr(q), _ptr(pool), _ptr(toff), _ptr(qoff), now_ticks, int(topk),
+                                                int(candidate_limit), scope._h, _ptr(rows), _ptr(scores), _ptr(counts)))
+        return rows, scores, counts
+
+    def search_in_scopes(self, qvecs, queries_terms, now_ticks: int, topk: int, scopes: Sequence[RecallScope], query_scope,
+                         candidate_limit: int = 300):
+        """orr_search_batch_in_scopes: query b searches inside scopes[query_scope[b]]; the large scopes share ONE screening
+        pass over the shard.  At most 64 scopes.  Returns (rows [B,k] int64, scores [B,k] float64, counts [B] int32)."""
+        B = len(queries_terms)
+        dim, q, _keep = self._query_args(qvecs, B)
+        pool, toff, qoff = pack_terms(queries_terms)
+        qs = np.ascontiguousarray(query_scope, dtype=np.int32).reshape(-1)
+        if qs.shape[0] != B:
+            raise ValueError(f"query_scope: {qs.shape[0]} entries for {B} queries")
+        handles = (C.c_void_p * max(1, len(scopes)))(*[sc._h for sc in scopes])
+        k = max(1, int(topk))
+        rows = np.full((B, k), -1, dtype=np.int64)
+        scores = np.zeros((B, k), dtype=np.float64)
+        counts = np.zeros(B, dtype=np.int32)
+        N.check(N.hip.orr_search_batch_in_scopes(self._h, B, dim, _ptr(q), _ptr(pool), _ptr(toff), _ptr(qoff), now_ticks, int(topk),
+                                                 int(candidate_limit), len(scopes), C.cast(handles, C.c_void_p), _ptr(qs),
+                                                 _ptr(rows), _ptr(scores), _ptr(counts)))
         return rows, scores, counts
 
     def search_shard_scoped(self, qvecs, queries_terms, now_ticks: int, kprime: int, candidate_limit: int, scope_ids,
