@@ -473,7 +473,9 @@ int orr_index_scope_count(orr_index *idx, int32_t B, int64_t n_scope_ids, const 
  *   orr_index_compact          positions close up; every scope is carried along (it holds no deleted row, so nothing leaves)
  *   orr_index_insert_rows      old rows move; every scope is carried along.  Rows inserted later belong to NO scope -- a time
  *                              window whose interval covers them included -- until orr_scope_add_ids names them; that call
- *                              looks up only the ids it is given and ORs them in
+ *                              looks up only the ids it is given and ORs them in.  A term scope is no exception: rows
+ *                              inserted later are not in it even when their text contains its terms (it is not evaluated
+ *                              again); an orr_scope_create_terms made afterwards holds them
  *   orr_index_update_rows, orr_index_set_row_base   touch no scope
  * Unlike a view, a scope does not block compaction or insertion.  Scopes are not saved by orr_index_save.  A scope costs one
  * bit per row of the shard plus its chunk counts (1.25 MB at 10M rows); ORR_ENOMEM when that does not fit.
@@ -484,6 +486,18 @@ int orr_index_scope_count(orr_index *idx, int32_t B, int64_t n_scope_ids, const 
  *                           tile; ticks_from >= ticks_to gives an empty scope, not an error; INT64_MIN and INT64_MAX are the
  *                           open ends.  Rows are in CreatedAt-descending order, so this costs two binary searches on the host
  *                           and one fill, however large the window.
+ *   orr_scope_create_terms  the live rows whose lowercased content contains EVERY term (ORR_TERMS_ALL) or AT LEAST ONE term
+ *                           (ORR_TERMS_ANY) as a substring: the rows for which the keyword side of a search with these terms
+ *                           would count n of n matches, or at least one (contentLower.Contains(term, Ordinal)).  The terms are
+ *                           HOST memory in the form of orr_search_batch's: term t is terms_utf8[term_off[t] .. term_off[t+1]),
+ *                           already lowercased, without whitespace; stop words are the caller's choice, a scope takes the
+ *                           terms it is given.  A row without content is never in; a term that matches nothing empties ALL
+ *                           and adds nothing to ANY; a term listed twice counts once.  n_terms == 0 gives an empty scope in
+ *                           both modes, as n_ids == 0 does -- the scope of ALL live rows is
+ *                           orr_scope_create_ticks(INT64_MIN, INT64_MAX), which is also the left side of "contains none of":
+ *                           all rows ANDNOT the ANY scope.  At most 256 terms (a row bitmap of workspace per distinct term:
+ *                           320 MB at 10M rows).  The keyword chain of a search runs once for the call, on the device; no
+ *                           search statistic moves.
  *   orr_scope_add_ids       adds the live rows that carry the ids; *out_added (may be NULL) = rows that were not in it before
  *   orr_scope_combine       dst = dst AND src, dst OR src, or dst AND NOT src, in place; src is unchanged (src == dst is allowed)
  *   orr_scope_rows          live rows in it now; -1 on an orphaned handle (or NULL)
@@ -502,13 +516,19 @@ int orr_index_scope_count(orr_index *idx, int32_t B, int64_t n_scope_ids, const 
  * Threads: searches hold a scope shared, so any number may search one scope at once; add_ids, combine (on dst) and destroy hold
  * it exclusively and wait for them.  create, add_ids, combine and row_ids take a lane like a search.
  * ORR_EINVAL before any device call, with the outputs untouched, and before the index handle is looked at: a NULL scope or out
- * pointer, negative counts, ids NULL with n_ids > 0, op outside 0 .. 2. */
+ * pointer, negative counts, ids NULL with n_ids > 0, op outside 0 .. 2; for orr_scope_create_terms, in this order: out NULL,
+ * n_terms outside 0 .. 256, terms_utf8 or term_off NULL with n_terms > 0, mode outside 0 .. 1, an empty term or offsets that
+ * decrease -- then a NULL index, then ORR_ESTATE for an index that is not sealed. */
 typedef struct orr_scope orr_scope;      /* opaque: a set of rows of one sealed shard, resident on its device */
 #define ORR_SCOPE_AND    0
 #define ORR_SCOPE_OR     1
 #define ORR_SCOPE_ANDNOT 2
+#define ORR_TERMS_ALL 0
+#define ORR_TERMS_ANY 1
 int     orr_scope_create(orr_index *idx, int64_t n_ids, const int64_t *ids /* host or device */, orr_scope **out);
 int     orr_scope_create_ticks(orr_index *idx, int64_t ticks_from, int64_t ticks_to, orr_scope **out);
+int     orr_scope_create_terms(orr_index *idx, int32_t n_terms, const uint8_t *terms_utf8 /* host */, const uint32_t *term_off /* host [n_terms+1] */,
+                               int32_t mode, orr_scope **out);
 int     orr_scope_add_ids(orr_scope *s, int64_t n_ids, const int64_t *ids /* host or device */, int64_t *out_added);
 int     orr_scope_combine(orr_scope *dst, int32_t op, const orr_scope *src);
 int64_t orr_scope_rows(const orr_scope *s);

@@ -39,6 +39,7 @@
 #include "orr_mask_plan.h"
 #include "orr_group_plan.h"
 #include "orr_scope_set_plan.h"
+#include "orr_scope_terms_plan.h"
 #include "orr_cluster_scope_plan.h"
 #include "orr_token_index.h"
 
@@ -219,6 +220,8 @@ struct orr_index {
     uint32_t *scope_tab_pos = nullptr; // [n_rows] positions, ascending within equal ids
     DevBuf ws_scope_ids, ws_scope_meta, ws_scope_bm, ws_scope_chunks, ws_scope_sel;   // a lane's: listed ids, offsets + limits, bitmaps, chunk counts, a pass's queries
     PinnedBuf pin_scope, pin_scope_pass;
+    DevBuf ws_scope_terms;                     // a lane's: where each distinct term's bitmap starts (orr_scope_create_terms)
+    PinnedBuf pin_scope_terms;                 // ... and the host's copy of it
     // masked search (orr_search_batch_masked), a lane's: the call's shared scope bitmap and its chunk counts (the list path in
     // parts rewrites ws_scope_bm per part), the sample's counts and the zeros that select the one bitmap, n_clip and the sample's sizes
     DevBuf ws_mask_bm, ws_mask_chunks, ws_mask_cnt, ws_mask_meta;
@@ -735,6 +738,7 @@ void orr_index_destroy(orr_index *idx)
     idx->ws_norm_a.release();
     for (DevBuf *b : {&idx->ws_scope_ids, &idx->ws_scope_meta, &idx->ws_scope_bm, &idx->ws_scope_chunks, &idx->ws_scope_sel}) b->release();
     idx->pin_scope.release(); idx->pin_scope_pass.release();
+    idx->ws_scope_terms.release(); idx->pin_scope_terms.release();
     for (DevBuf *b : {&idx->ws_mask_bm, &idx->ws_mask_chunks, &idx->ws_mask_cnt, &idx->ws_mask_meta}) b->release();
     idx->pin_mask.release();
     for (DevBuf *b : {&idx->ws_group_bm, &idx->ws_group_chunks, &idx->ws_group_meta}) b->release();
@@ -3561,12 +3565,12 @@ int launch_selection(orr_index *idx, const BatchArgs &a, const PassPlan &p, int3
     return ORR_OK;
 }
 
-// Stage 9: wait for the pass; clear the keyword side's bitmaps and counters for the next search; statistics.  kRetryPass:
-// the keyword hit list was too short and has grown, this pass's records are discarded.
-int finish_pass(orr_index *idx, const BatchArgs &a, const PassPlan &p, const KwSide &kws, uint32_t n_terms_total)
+// What the keyword chain leaves behind, put right for the next chain on this lane: the term bitmaps it used cleared, its
+// counters zeroed.  Every kernel that read the bitmaps must be DONE (the host has waited for it): the large clear runs on the
+// auxiliary stream, behind nothing.  finish_pass and orr_scope_create_terms both end with this.  (A chain whose caller skipped
+// it clears everything itself, in front of its kernels: launch_keyword_side withdraws these vouchers on entry.)
+int clean_keyword_side(orr_index *idx, const KwSide &kws, uint32_t n_terms_total)
 {
-    const int32_t B = a.B;
-    HIP_TRY(hipStreamSynchronize(idx->stream));
     if (kws.bm_bytes) {        // every kernel that read the bitmaps is done: clear them for the next search
         if (kws.bm_bytes >= ((size_t)16 << 20)) {   // (small ones stay on the keyword stream: a cross-stream wait costs a one-query call more)
             HIP_TRY(hipMemsetAsync(idx->ws_bitmaps.p, 0, kws.bm_bytes, idx->stream_aux));
@@ -3584,6 +3588,16 @@ int finish_pass(orr_index *idx, const BatchArgs &a, const PassPlan &p, const KwS
         idx->kw_counters_of[0] = idx->ws_counter.p;
         idx->kw_counters_of[1] = idx->ws_kwalias.p;
     }
+    return ORR_OK;
+}
+
+// Stage 9: wait for the pass; clear the keyword side's bitmaps and counters for the next search; statistics.  kRetryPass:
+// the keyword hit list was too short and has grown, this pass's records are discarded.
+int finish_pass(orr_index *idx, const BatchArgs &a, const PassPlan &p, const KwSide &kws, uint32_t n_terms_total)
+{
+    const int32_t B = a.B;
+    HIP_TRY(hipStreamSynchronize(idx->stream));
+    ORR_TRY(clean_keyword_side(idx, kws, n_terms_total));
     if (p.dev_norms) memcpy(idx->h_norm_a.data(), idx->pin_norm.p, sizeof(double) * (size_t)B);
     if (n_terms_total > 0) {
         idx->sstats.kw_hits_total += (int64_t)(*idx->pin_kwcnt.as<unsigned long long>() >> 32);
@@ -5448,6 +5462,103 @@ int orr_scope_create_ticks(orr_index *idx, int64_t ticks_from, int64_t ticks_to,
         Timed t(lane, "scope_clear_positions", 12.0 * (double)own->dead.size());
         HIP_TRY(orr::launch_scope_clear_positions(sc->bm, sc->words, own->d_dead.as<int64_t>(), (int64_t)own->dead.size(), lane->stream));
         return ORR_OK;
+    });
+}
+
+// The fill of a term scope (orr_scope_terms_plan.h), on the lane the caller holds:
+//   1. the keyword chain of a search for ONE query that owns every term (launch_keyword_side, as it is): a row bitmap per
+//      DISTINCT term, its own or -- where the term's only hit is a token with a stored bitmap -- an alias into the token store;
+//   2. scope_terms_combine behind it on the keyword stream: the bitmaps folded into the scope's, every word written;
+//   3. the hit list checked as finish_pass checks it: too short, and the bitmaps are incomplete -- the list grows by the
+//      search's rule and the chain runs again, a scope is never made of a truncated list;
+//   4. the lane left as a search leaves it (clean_keyword_side), whether the chain stands or runs again;
+//   5. the deleted rows cleared on the scope's own stream, behind an event: posting lists keep deleted positions until compaction.
+// The search statistics do not move (this is no search); the kernel statistics record the launches.
+static int scope_fill_terms_run(orr_index *lane, orr_scope *sc, int32_t n_terms, const uint8_t *terms_utf8, const uint32_t *term_off, int32_t mode)
+{
+    if (n_terms == 0 || lane->n_rows <= 0) {           // nothing to fold: the empty scope
+        HIP_TRY(hipMemsetAsync(sc->bm, 0, sizeof(uint32_t) * (size_t)sc->words, lane->stream));
+        return ORR_OK;
+    }
+    const orr_index *own = owner_of(lane);
+    const uint32_t query_term_off[2] = {0u, (uint32_t)n_terms};
+    BatchArgs a{1, 0, nullptr, terms_utf8, term_off, query_term_off, 0, 0};
+    const std::vector<uint32_t> qoff(query_term_off, query_term_off + 2);
+    hipStream_t k = lane->stream_kw;
+    for (int attempt = 0;; ++attempt) {
+        KwSide kws;
+        ORR_TRY(launch_keyword_side(lane, a, qoff, kws));
+        const int64_t words = kws.view.words_per_term;
+        if (words != sc->words || kws.bm_bytes == 0 || kws.bm_bytes % (sizeof(uint32_t) * (size_t)words) != 0)
+            return fail(ORR_ESTATE, "orr_scope_create_terms: the keyword side's bitmaps have %lld words, the scope's %lld", (long long)words, (long long)sc->words);
+        const int32_t n_distinct = (int32_t)(kws.bm_bytes / (sizeof(uint32_t) * (size_t)words));
+        // 16-byte vectors: words % 4 == 0 and each base is t * words, or the token store (tok_bm_words == words) seen from the bitmaps
+        if (words % 4 != 0 || (reinterpret_cast<uintptr_t>(kws.view.bitmaps) & 15u) || (reinterpret_cast<uintptr_t>(lane->tok_bm.p) & 15u))
+            return fail(ORR_ESTATE, "orr_scope_create_terms: a term bitmap is not 16-byte aligned");
+        ORR_TRY(lane->ws_scope_terms.reserve(sizeof(int64_t) * (size_t)scope_terms::kMaxTerms));
+        int64_t *h_base = nullptr;                     // the host's copy of the bases: only the statistics read it
+        if (lane->profiling == 1) {
+            ORR_TRY(lane->pin_scope_terms.reserve(sizeof(int64_t) * (size_t)scope_terms::kMaxTerms));
+            h_base = lane->pin_scope_terms.as<int64_t>();
+        }
+        {
+            Timed t(lane, "scope_terms_bases", 24.0 * (double)n_distinct, k);
+            HIP_TRY(orr::launch_scope_terms_bases(kws.view.term_word_off, n_distinct, words, lane->ws_scope_terms.as<int64_t>(), h_base, k));
+        }
+        {
+            Timed t(lane, "scope_terms_combine", 4.0 * (double)words * ((double)n_distinct + 1.0), k);
+            HIP_TRY(orr::launch_scope_terms_combine(kws.view.bitmaps, lane->ws_scope_terms.as<int64_t>(), n_distinct, mode, words, lane->n_rows, sc->bm, k));
+        }
+        HIP_TRY(hipEventRecord(lane->ev_kw_done, k));
+        HIP_TRY(hipStreamSynchronize(k));              // the bitmaps are read: they may be cleared; the hit count is in pinned memory
+        bool truncated = false;
+        if (kws.overflow_possible) {
+            const uint32_t hits = (uint32_t)(*lane->pin_kwcnt.as<unsigned long long>() >> 32);
+            if (hits > kws.max_hits) {
+                if ((uint64_t)hits * sizeof(orr::KwHit) > ((uint64_t)8 << 30))
+                    return fail(ORR_ENOMEM, "orr_scope_create_terms: the terms matched %u vocabulary tokens: a hit list of that size is refused (8 GiB)", hits);
+                lane->kw_hits_cap = hits + hits / 4 + 1024u;
+                truncated = true;
+            }
+        }
+        ORR_TRY(clean_keyword_side(lane, kws, (uint32_t)n_terms));
+        if (truncated) {
+            if (attempt >= 3) return fail(ORR_EDEVICE, "orr_scope_create_terms: the keyword hit list kept overflowing");
+            continue;
+        }
+        if (h_base) {                  // what the fold read from STORED token bitmaps (aliased terms: nothing was expanded for them)
+            int64_t aliased = 0;
+            for (int32_t t = 0; t < n_distinct; ++t) aliased += h_base[t] != (int64_t)t * words;
+            lane->stats[(size_t)stat_slot(lane, "scope_terms_aliased")].algo_bytes += 4.0 * (double)words * (double)aliased;
+        }
+        break;
+    }
+    HIP_TRY(hipStreamWaitEvent(lane->stream, lane->ev_kw_done, 0));
+    Timed t(lane, "scope_clear_positions", 12.0 * (double)own->dead.size());
+    HIP_TRY(orr::launch_scope_clear_positions(sc->bm, sc->words, own->d_dead.as<int64_t>(), (int64_t)own->dead.size(), lane->stream));
+    return ORR_OK;
+}
+
+// ... and whatever it launched on the keyword stream is done before a failed fill's caller frees the scope's bitmap
+static int scope_fill_terms(orr_index *lane, orr_scope *sc, int32_t n_terms, const uint8_t *terms_utf8, const uint32_t *term_off, int32_t mode)
+{
+    const int r = scope_fill_terms_run(lane, sc, n_terms, terms_utf8, term_off, mode);
+    if (r != ORR_OK) (void)hipStreamSynchronize(lane->stream_kw);
+    return r;
+}
+
+int orr_scope_create_terms(orr_index *idx, int32_t n_terms, const uint8_t *terms_utf8, const uint32_t *term_off, int32_t mode, orr_scope **out)
+{
+    if (!out) return fail(ORR_EINVAL, "orr_scope_create_terms: out is NULL");
+    if (!scope_terms::terms_valid(n_terms)) return fail(ORR_EINVAL, "orr_scope_create_terms: n_terms must be in 0 .. %d", scope_terms::kMaxTerms);
+    if (n_terms > 0 && (!terms_utf8 || !term_off)) return fail(ORR_EINVAL, "orr_scope_create_terms: terms_utf8 or term_off is NULL with %d terms", n_terms);
+    if (!scope_terms::mode_valid(mode)) return fail(ORR_EINVAL, "orr_scope_create_terms: mode must be ORR_TERMS_ALL (0) or ORR_TERMS_ANY (1)");
+    const int32_t bad = scope_terms::first_bad_term(term_off, n_terms);
+    if (bad >= 0 && term_off[bad + 1] == term_off[bad]) return fail(ORR_EINVAL, "orr_scope_create_terms: term %d is empty", bad);
+    if (bad >= 0) return fail(ORR_EINVAL, "orr_scope_create_terms: term_off is not monotone at term %d", bad);
+    if (!idx) return fail(ORR_EINVAL, "orr_scope_create_terms: null index");
+    return make_scope(idx, "orr_scope_create_terms", out, [&](orr_index *lane, orr_scope *sc) -> int {
+        return scope_fill_terms(lane, sc, n_terms, terms_utf8, term_off, mode);
     });
 }
 

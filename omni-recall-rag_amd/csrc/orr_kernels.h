@@ -10,6 +10,7 @@
 #include "orr_scope_plan.h"
 #include "orr_mask_plan.h"
 #include "orr_scope_set_plan.h"
+#include "orr_scope_terms_plan.h"
 
 #include <atomic>
 
@@ -473,5 +474,17 @@ hipError_t launch_scope_remap(const int64_t *src, int64_t first, int64_t n_new, 
                               int64_t old_words, uint32_t *const *new_bm, int32_t n_scopes, hipStream_t s);
 // out[i] = row_ids[buf[i].pos] for the n entries launch_scope_compact left.
 hipError_t launch_scope_entry_ids(const SelEntry *buf, int64_t n, const int64_t *row_ids, int64_t n_rows, int64_t *out, hipStream_t s);
+
+// ---- term scopes (orr_scope_create_terms; the rules are orr_scope_terms_plan.h's) -------------------------------------------
+// term_base[t] (device, and its copy term_base_host in pinned memory when given) = where distinct term t's row bitmap starts, in
+// words from the keyword chain's bitmaps: term_word_off[t] where the alias stage ran (KwView::term_word_off, device; a stored
+// token bitmap for an aliased term), t * words where it did not (term_word_off NULL).  1 <= n <= scope_terms::kMaxTerms.
+hipError_t launch_scope_terms_bases(const int64_t *term_word_off, int32_t n, int64_t words, int64_t *term_base, int64_t *term_base_host,
+                                    hipStream_t s);
+// dst (words, all written) = the words of the n distinct terms' bitmaps (bitmaps + term_base[t], read-only: a base may point into
+// the stored token bitmaps) folded with AND (scope_terms::All) or OR (Any), the bits at or above n_rows clear.  words % 4 == 0,
+// bitmaps and dst 16-byte aligned and every base a multiple of 4 words: one 16-byte load per term and lane.
+hipError_t launch_scope_terms_combine(const uint32_t *bitmaps, const int64_t *term_base /* device, [n] words from bitmaps */,
+                                      int32_t n, int32_t mode, int64_t words, int64_t n_rows, uint32_t *dst, hipStream_t s);
 
 }  // namespace orr

@@ -2109,4 +2109,58 @@ hipError_t launch_scope_entry_ids(const SelEntry *buf, int64_t n, const int64_t 
     return hipGetLastError();
 }
 
+// ---- term scopes (orr_scope_create_terms; the rules are orr_scope_terms_plan.h's) -------------------------------------------
+
+// where each distinct term's bitmap starts (n <= 256 values: one workgroup)
+__global__ __launch_bounds__(256) void scope_terms_bases_kernel(const int64_t *__restrict__ term_word_off, int32_t n, int64_t words,
+                                                                int64_t *__restrict__ term_base, int64_t *__restrict__ term_base_host)
+{
+    const int32_t t = threadIdx.x;
+    if (t >= n) return;
+    const int64_t base = term_word_off ? term_word_off[t] : (int64_t)t * words;
+    term_base[t] = base;
+    if (term_base_host) term_base_host[t] = base;
+}
+
+hipError_t launch_scope_terms_bases(const int64_t *term_word_off, int32_t n, int64_t words, int64_t *term_base, int64_t *term_base_host,
+                                    hipStream_t s)
+{
+    if (n < 1 || n > scope_terms::kMaxTerms || words <= 0 || !term_base) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(scope_terms_bases_kernel, dim3(1), dim3(256), 0, s, term_word_off, n, words, term_base, term_base_host);
+    return hipGetLastError();
+}
+
+// One lane per 16-byte vector of dst, grid-stride: the lane loads the same vector of each term's bitmap (consecutive lanes,
+// consecutive vectors: every load of a wave is one contiguous 1 KiB), folds them (scope_terms::fold_word), masks the tail
+// (scope_terms::tail_mask) and stores once.  The bases are the same for every lane: they come through the scalar cache.
+__global__ __launch_bounds__(256) void scope_terms_combine_kernel(const uint32_t *__restrict__ bitmaps, const int64_t *__restrict__ term_base,
+                                                                  int32_t n, int32_t mode, int64_t words, int64_t n_rows, uint32_t *__restrict__ dst)
+{
+    const int64_t n_vec = words / 4, stride = (int64_t)gridDim.x * 256;
+    const uint32_t id = scope_terms::fold_identity(mode);
+    for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < n_vec; v += stride) {
+        const int64_t w0 = v * 4;
+        uint4 acc = make_uint4(id, id, id, id);
+        for (int32_t t = 0; t < n; ++t) {
+            const uint4 x = *reinterpret_cast<const uint4 *>(bitmaps + term_base[t] + w0);
+            acc.x = scope_terms::fold_word(acc.x, x.x, mode); acc.y = scope_terms::fold_word(acc.y, x.y, mode);
+            acc.z = scope_terms::fold_word(acc.z, x.z, mode); acc.w = scope_terms::fold_word(acc.w, x.w, mode);
+        }
+        *reinterpret_cast<uint4 *>(dst + w0) = make_uint4(acc.x & scope_terms::tail_mask(w0, n_rows), acc.y & scope_terms::tail_mask(w0 + 1, n_rows),
+                                                          acc.z & scope_terms::tail_mask(w0 + 2, n_rows), acc.w & scope_terms::tail_mask(w0 + 3, n_rows));
+    }
+}
+
+hipError_t launch_scope_terms_combine(const uint32_t *bitmaps, const int64_t *term_base, int32_t n, int32_t mode, int64_t words, int64_t n_rows,
+                                      uint32_t *dst, hipStream_t s)
+{
+    if (n < 1 || !scope_terms::terms_valid(n) || !scope_terms::mode_valid(mode) || words <= 0 || words % 4 != 0 || n_rows < 0 || n_rows > words * 32 ||
+        !bitmaps || !term_base || !dst)
+        return hipErrorInvalidValue;
+    if ((reinterpret_cast<uintptr_t>(bitmaps) | reinterpret_cast<uintptr_t>(dst)) & 15u) return hipErrorInvalidValue;   // 16-byte vectors
+    const int64_t blocks = std::min<int64_t>((words / 4 + 255) / 256, 2048);
+    hipLaunchKernelGGL(scope_terms_combine_kernel, dim3((unsigned)blocks), dim3(256), 0, s, bitmaps, term_base, n, mode, words, n_rows, dst);
+    return hipGetLastError();
+}
+
 }  // namespace orr

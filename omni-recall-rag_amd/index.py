@@ -79,7 +79,7 @@ def pack_contents(contents: Sequence[bytes]) -> Tuple[np.ndarray, np.ndarray]:
 class RecallScope:
     """A scope handle (orr_scope): a set of ROWS of one sealed shard, resolved once and resident on its device.  It follows
     its rows through delete_rows, compact and insert_rows of the shard; rows inserted later are in no scope until add_ids
-    names them.  Made by RecallIndex.scope / scope_ticks; close it before or after its index (after: only the host part is
+    names them.  Made by RecallIndex.scope / scope_ticks / scope_terms; close it before or after its index (after: only the host part is
     left to free)."""
 
     def __init__(self, handle, index: "RecallIndex"):
@@ -403,6 +403,18 @@ class RecallIndex:
         """orr_scope_create_ticks: the live rows with ticks_from <= CreatedAtUtc.Ticks < ticks_to."""
         h = C.c_void_p()
         N.check(N.hip.orr_scope_create_ticks(self._h, int(ticks_from), int(ticks_to), C.byref(h)))
+        return RecallScope(h, self)
+
+    def scope_terms(self, terms: Sequence[bytes], mode: str = "all") -> RecallScope:
+        """orr_scope_create_terms: the live rows whose lowercased content contains every term (mode "all") or at least one
+        (mode "any") as a substring.  terms: lowercased bytes without whitespace; no terms give an empty scope."""
+        modes = {"all": N.ORR_TERMS_ALL, "any": N.ORR_TERMS_ANY}
+        if mode not in modes:
+            raise ValueError('mode: "all" or "any"')
+        pool, toff, _ = pack_terms([list(terms)])
+        n_terms = int(toff.shape[0]) - 1
+        h = C.c_void_p()
+        N.check(N.hip.orr_scope_create_terms(self._h, n_terms, _ptr(pool), _ptr(toff), modes[mode], C.byref(h)))
         return RecallScope(h, self)
 
     def search_in_scope(self, qvecs, queries_terms, now_ticks: int, topk: int, scope: RecallScope, candidate_limit: int = 300):
