@@ -560,6 +560,19 @@ int orr_search_batch_in_scopes(orr_index *idx, int32_t B, int32_t dim, const flo
                                int32_t n_scopes, const orr_scope *const *scopes, const int32_t *query_scope /* host [B] */,
                                int64_t *out_rows, double *out_scores, int32_t *out_counts);
 
+/* orr_search_shard_masked with the scope taken from a handle: the record form of orr_search_batch_in_scope, the shard half of
+ * orr_cluster_search_batch_in_scope.  The contract is orr_search_shard_masked's, unchanged: [B][kprime+1] records and the
+ * trailer, `pass` 0 / 1, topk, candidate_limit GLOBAL with scope_before the scope's live rows on the shards in front (read
+ * there with orr_scope_rows: no count runs), the one in-call repeat of overflowed queries, pass_mode 5 or 4.  Nothing is
+ * resolved: no id crosses to the device, no lookup and no count runs, and a limit that reaches every row of the scope on this
+ * shard computes no clip either.
+ * ORR_EINVAL before any device call, in this order: kprime < 1, topk < 0, pass outside {0, 1}, scope_before < 0, out NULL, a
+ * NULL scope, then a NULL index and the batch's argument errors; then a scope of another shard.  ORR_ESTATE: an orphaned scope. */
+int orr_search_shard_in_scope(orr_index *idx, int32_t B, int32_t dim, const float *q,
+                              const uint8_t *terms_utf8, const uint32_t *term_off, const uint32_t *query_term_off,
+                              int64_t now_ticks, int32_t kprime, int64_t candidate_limit, int32_t topk, int32_t pass,
+                              const orr_scope *scope, int64_t scope_before, orr_candidate *out);
+
 /* ---- tuning knobs ----------------------------------------------------------
  * Integer options of one index; unknown names are ORR_EINVAL.
  *   "dead_rows_before"  deleted rows in the shards in front of this one (default 0), see above.
@@ -722,6 +735,68 @@ int        orr_cluster_compact(orr_cluster *c, int64_t *out_removed);
 int        orr_cluster_insert_rows(orr_cluster *c, int32_t shard, int64_t n, int32_t dim, const float *emb,
                                    const int64_t *created_ticks, const uint8_t *content_lower,
                                    const uint64_t *content_off, const int64_t *row_ids, int64_t *out_inserted);
+
+/* ---- cluster scope handles: keep a resolved scope on every shard -------------
+ * An orr_cluster_scope is a set of rows of one sealed cluster, held as ONE orr_scope PER SHARD; each part is made on its shard
+ * by the single-shard call of the same name, at once on all shards, and every per-shard rule above holds unchanged: how unknown
+ * ids, ids listed twice and ids carried by several rows resolve; half-open tick windows with INT64_MIN / INT64_MAX as the open
+ * ends; ORR_TERMS_ALL / ORR_TERMS_ANY, at most 256 terms, no empty term; deleted rows are never in a scope; rows inserted later
+ * are in no scope.  An id carried by rows on two shards sets a bit on both.  If the creation fails on any shard the parts
+ * already made are destroyed, *out is untouched and that error is returned.
+ *   maintenance  nothing new: the parts are registered with their shards, so orr_index_delete_rows on orr_cluster_shard(i),
+ *                orr_cluster_compact and orr_cluster_insert_rows carry them.  The cluster scope caches no count: rows and the
+ *                search read every part's count when they are called.
+ *   add_ids      orr_scope_add_ids on every shard; *out_added (may be NULL) is the sum over the shards
+ *   combine      orr_scope_combine on every shard; scopes of two different clusters are ORR_EINVAL; src == dst is allowed
+ *   rows         the sum over the shards; -1 on an orphaned handle (or NULL)
+ *   row_ids      the ids of the live rows in the GLOBAL candidate order (shard 0's, then shard 1's, ...): every shard writes at
+ *                the offset of the live counts of the shards in front of it.  *out_n = their number; nothing is written beyond
+ *                cap; when cap is too small: ORR_EINVAL after *out_n is set, nothing written at all
+ *   shard        part i, borrowed as orr_cluster_shard's result is (never destroy it; NULL out of range): for orr_scope_rows
+ *                and orr_search_shard_in_scope
+ *   destroy      frees it and its parts (NULL is allowed)
+ * add_ids and combine hold every part exclusively for the whole call -- taken in ascending shard order, within a shard by the
+ * single shard's rule (dst and src in address order) -- so a search sees the edit on all shards or on none.  If an edit fails
+ * on some shard (a device error), some shards may hold it and others not: the call returns that error and the cluster scope is
+ * orphaned, never left half-applied and searchable; make it again.
+ * orr_cluster_destroy orphans the cluster scopes that are still alive: every later call on one is ORR_ESTATE, rows is -1, and
+ * orr_cluster_scope_destroy still has to be called to free the host part.  The two destroys may be called from different
+ * threads in either order (the library serialises them); every other call on a cluster scope must have returned before its
+ * cluster is destroyed.  orr_index_destroy of a cluster's shard is not a supported call.
+ * create, add_ids, combine, row_ids and the search run beside cluster searches (each takes one lane per shard, in shard order)
+ * and are excluded by orr_cluster_compact, orr_cluster_insert_rows and orr_cluster_seal.
+ * Argument errors come before any device call and before a handle is looked at, with the outputs untouched, in this order: out
+ * pointer NULL (row_ids: cap negative, out_n NULL, out_ids NULL with cap > 0), negative counts, ids NULL with n_ids > 0, op
+ * outside 0 .. 2; for create_terms: out NULL, n_terms outside 0 .. 256, terms_utf8 or term_off NULL with n_terms > 0, mode
+ * outside 0 .. 1, an empty term or offsets that decrease; then a NULL scope, then a NULL cluster; then ids in device memory
+ * (ORR_EINVAL: every shard's device reads them), ORR_ESTATE for an unsealed cluster or an orphaned scope. */
+typedef struct orr_cluster_scope orr_cluster_scope;   /* opaque: one orr_scope per shard of one sealed cluster */
+int     orr_cluster_scope_create(orr_cluster *c, int64_t n_ids, const int64_t *ids /* HOST */, orr_cluster_scope **out);
+int     orr_cluster_scope_create_ticks(orr_cluster *c, int64_t ticks_from, int64_t ticks_to, orr_cluster_scope **out);
+int     orr_cluster_scope_create_terms(orr_cluster *c, int32_t n_terms, const uint8_t *terms_utf8 /* host */, const uint32_t *term_off /* host [n_terms+1] */,
+                                       int32_t mode, orr_cluster_scope **out);
+int     orr_cluster_scope_add_ids(orr_cluster_scope *s, int64_t n_ids, const int64_t *ids /* HOST */, int64_t *out_added);
+int     orr_cluster_scope_combine(orr_cluster_scope *dst, int32_t op, const orr_cluster_scope *src);
+int64_t orr_cluster_scope_rows(const orr_cluster_scope *s);
+int     orr_cluster_scope_row_ids(orr_cluster_scope *s, int64_t cap, int64_t *out_ids /* HOST */, int64_t *out_n);
+const orr_scope *orr_cluster_scope_shard(const orr_cluster_scope *s, int32_t i);
+void    orr_cluster_scope_destroy(orr_cluster_scope *s);
+
+/* orr_cluster_search_batch_masked with the scope taken from a handle: what orr_search_batch_in_scope returns on ONE index that
+ * holds all the cluster's rows with the same set of rows as its scope -- rows, order and fp64 scores bit for bit.
+ * candidate_limit counts the scope's live rows over the whole cluster; an empty scope gives counts of 0 with the outputs filled
+ * as the masked call fills them.  No id list goes to any shard and NO count step runs: behind the lanes every part is taken
+ * shared in ascending shard order, the live counts are read from the handles, the limit is split on those numbers, and every
+ * shard answers through orr_search_shard_in_scope's pass.  The merge, the ladder, the slices and the statistics are the masked
+ * cluster call's; the "exchange" option does not apply.
+ * Errors, in this order, with the outputs untouched: ORR_EINVAL for B <= 0, dim < 0, q_host NULL with dim > 0, query_term_off
+ * NULL, out_rows or out_scores NULL, a NULL scope, a NULL cluster, q_host in device memory; ORR_ESTATE for an unsealed cluster
+ * or an orphaned scope; ORR_EINVAL for a scope of another cluster. */
+int orr_cluster_search_batch_in_scope(orr_cluster *c, int32_t B, int32_t dim, const float *q_host,
+                                      const uint8_t *terms_utf8, const uint32_t *term_off, const uint32_t *query_term_off,
+                                      int64_t now_ticks, int32_t topk, int64_t candidate_limit,
+                                      const orr_cluster_scope *scope,
+                                      int64_t *out_rows, double *out_scores, int32_t *out_counts);
 
 #ifdef __cplusplus
 }

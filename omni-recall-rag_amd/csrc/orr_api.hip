@@ -40,6 +40,7 @@
 #include "orr_group_plan.h"
 #include "orr_scope_set_plan.h"
 #include "orr_scope_terms_plan.h"
+#include "orr_cluster_handle_plan.h"
 #include "orr_cluster_scope_plan.h"
 #include "orr_token_index.h"
 
@@ -5126,8 +5127,9 @@ int masked_shard_screen(orr_index *idx, const BatchArgs &orig, const ScopeSlice 
 }
 
 // orr_search_shard_masked on the lane the caller holds: one pass at the caller's k', no ladder (the caller's merge certifies).
-// orig.topk: the k the floor's sample serves.
-int masked_shard(orr_index *idx, const BatchArgs &orig, const ScopeArgs &sc, int64_t scope_before, int32_t kprime, int32_t pass, orr_candidate *out)
+// orig.topk: the k the floor's sample serves.  The scope is a list, resolved here, or a handle the caller holds shared
+// (orr_search_shard_in_scope): then nothing is resolved, as in masked_batch.
+int masked_shard(orr_index *idx, const BatchArgs &orig, const ScopeSource &src, int64_t scope_before, int32_t kprime, int32_t pass, orr_candidate *out)
 {
     const int32_t B = orig.B;
     const bool use_cos = orig.dim > 0 && orig.dim == idx->dim;
@@ -5138,11 +5140,11 @@ int masked_shard(orr_index *idx, const BatchArgs &orig, const ScopeArgs &sc, int
         HIP_TRY(hipMemcpy(out, empty_records(B, kprime).data(), sizeof(orr_candidate) * (size_t)B * rec_q, hipMemcpyDefault));
         return ORR_OK;
     };
-    if (idx->n_rows <= 0 || sc.n_ids == 0 || limit == 0) return nothing();
-    ORR_TRY(ensure_scope_table(idx));
+    if (idx->n_rows <= 0 || src.empty() || limit == 0) return nothing();
+    if (src.list) ORR_TRY(ensure_scope_table(idx));
     ScopeSlice sl;
     MaskScope ms;
-    ORR_TRY(resolve_mask_scope(idx, B, orig.topk, ScopeSource{&sc, nullptr}, limit, sl, ms));
+    ORR_TRY(resolve_mask_scope(idx, B, orig.topk, src, limit, sl, ms));
     if (ms.took == 0) return nothing();
     std::vector<int32_t> ids((size_t)B);
     std::iota(ids.begin(), ids.end(), 0);
@@ -5562,18 +5564,9 @@ int orr_scope_create_terms(orr_index *idx, int32_t n_terms, const uint8_t *terms
     });
 }
 
-int orr_scope_add_ids(orr_scope *s, int64_t n_ids, const int64_t *ids, int64_t *out_added)
+// orr_scope_add_ids behind its locks: the caller holds the lane, its lock and the scope exclusively
+static int scope_add_ids_held(orr_index *lane, orr_scope *s, int64_t n_ids, const int64_t *ids, int64_t *out_added)
 {
-    if (n_ids < 0) return fail(ORR_EINVAL, "orr_scope_add_ids: n_ids is negative");
-    if (n_ids > 0 && !ids) return fail(ORR_EINVAL, "orr_scope_add_ids: ids is NULL with %lld ids", (long long)n_ids);
-    if (!s) return fail(ORR_EINVAL, "orr_scope_add_ids: null scope");
-    orr_index *own = nullptr;
-    ORR_TRY(scope_owner(s, nullptr, "orr_scope_add_ids", &own));
-    Lane ln = acquire_lane(own);
-    orr_index *lane = ln.lane;
-    std::lock_guard<std::mutex> lock(lane->mu);
-    std::unique_lock<std::shared_mutex> w(s->mu);
-    ORR_TRY(scope_owner(s, nullptr, "orr_scope_add_ids", &own));
     ORR_TRY(bind_device(lane));
     const int64_t before = s->live.load();
     int r = scope_or_ids(lane, s, n_ids, ids);
@@ -5583,25 +5576,9 @@ int orr_scope_add_ids(orr_scope *s, int64_t n_ids, const int64_t *ids, int64_t *
     return ORR_OK;
 }
 
-int orr_scope_combine(orr_scope *dst, int32_t op, const orr_scope *src)
+// orr_scope_combine behind its locks: the caller holds the lane, its lock, dst exclusively and src shared
+static int scope_combine_held(orr_index *lane, orr_scope *dst, int32_t op, const orr_scope *src)
 {
-    if (!scope_set::op_valid(op)) return fail(ORR_EINVAL, "orr_scope_combine: op must be ORR_SCOPE_AND (0), ORR_SCOPE_OR (1) or ORR_SCOPE_ANDNOT (2)");
-    if (!dst || !src) return fail(ORR_EINVAL, "orr_scope_combine: null scope");
-    orr_index *own = nullptr, *own_src = nullptr;
-    ORR_TRY(scope_owner(dst, nullptr, "orr_scope_combine", &own));
-    ORR_TRY(scope_owner(src, nullptr, "orr_scope_combine", &own_src));
-    if (own != own_src) return fail(ORR_EINVAL, "orr_scope_combine: the scopes belong to different shards");
-    Lane ln = acquire_lane(own);
-    orr_index *lane = ln.lane;
-    std::lock_guard<std::mutex> lock(lane->mu);
-    // dst exclusively, src shared, the lower address first (two combines with the roles swapped must not wait for each other)
-    std::unique_lock<std::shared_mutex> w(dst->mu, std::defer_lock);
-    std::shared_lock<std::shared_mutex> rd(src->mu, std::defer_lock);
-    if (src == dst) w.lock();
-    else if ((const void *)dst < (const void *)src) { w.lock(); rd.lock(); }
-    else { rd.lock(); w.lock(); }
-    ORR_TRY(scope_owner(dst, nullptr, "orr_scope_combine", &own));
-    ORR_TRY(scope_owner(src, nullptr, "orr_scope_combine", &own_src));
     if (dst->words != src->words) return fail(ORR_ESTATE, "orr_scope_combine: the scopes cover different row counts");
     ORR_TRY(bind_device(lane));
     {
@@ -5613,29 +5590,9 @@ int orr_scope_combine(orr_scope *dst, int32_t op, const orr_scope *src)
     return r;
 }
 
-int64_t orr_scope_rows(const orr_scope *s)
+// orr_scope_row_ids behind its locks: the ids of the scope's `live` rows (> 0) in candidate order into out_ids (host memory)
+static int scope_row_ids_held(orr_index *lane, const orr_scope *s, int64_t live, int64_t *out_ids)
 {
-    if (!s || !s->owner.load()) return -1;
-    return s->live.load();
-}
-
-int orr_scope_row_ids(orr_scope *s, int64_t cap, int64_t *out_ids, int64_t *out_n)
-{
-    if (cap < 0) return fail(ORR_EINVAL, "orr_scope_row_ids: cap is negative");
-    if (!out_n) return fail(ORR_EINVAL, "orr_scope_row_ids: out_n is NULL");
-    if (cap > 0 && !out_ids) return fail(ORR_EINVAL, "orr_scope_row_ids: out_ids is NULL with room for %lld ids", (long long)cap);
-    if (!s) return fail(ORR_EINVAL, "orr_scope_row_ids: null scope");
-    orr_index *own = nullptr;
-    ORR_TRY(scope_owner(s, nullptr, "orr_scope_row_ids", &own));
-    Lane ln = acquire_lane(own);
-    orr_index *lane = ln.lane;
-    std::lock_guard<std::mutex> lock(lane->mu);
-    std::shared_lock<std::shared_mutex> rd(s->mu);
-    ORR_TRY(scope_owner(s, nullptr, "orr_scope_row_ids", &own));
-    const int64_t live = s->live.load();
-    *out_n = live;
-    if (live > cap) return fail(ORR_EINVAL, "orr_scope_row_ids: the scope holds %lld rows, out_ids has room for %lld", (long long)live, (long long)cap);
-    if (live == 0) return ORR_OK;
     ORR_TRY(bind_device(lane));
     hipStream_t st = lane->stream;
     // the bitmap compacted into entries in candidate order (the scoped pass's kernel, one pseudo-query), then their ids gathered
@@ -5661,6 +5618,69 @@ int orr_scope_row_ids(orr_scope *s, int64_t cap, int64_t *out_ids, int64_t *out_
     if (r != ORR_OK) (void)hipStreamSynchronize(st);
     entries.release(); d_ids.release();
     return r;
+}
+
+int orr_scope_add_ids(orr_scope *s, int64_t n_ids, const int64_t *ids, int64_t *out_added)
+{
+    if (n_ids < 0) return fail(ORR_EINVAL, "orr_scope_add_ids: n_ids is negative");
+    if (n_ids > 0 && !ids) return fail(ORR_EINVAL, "orr_scope_add_ids: ids is NULL with %lld ids", (long long)n_ids);
+    if (!s) return fail(ORR_EINVAL, "orr_scope_add_ids: null scope");
+    orr_index *own = nullptr;
+    ORR_TRY(scope_owner(s, nullptr, "orr_scope_add_ids", &own));
+    Lane ln = acquire_lane(own);
+    orr_index *lane = ln.lane;
+    std::lock_guard<std::mutex> lock(lane->mu);
+    std::unique_lock<std::shared_mutex> w(s->mu);
+    ORR_TRY(scope_owner(s, nullptr, "orr_scope_add_ids", &own));
+    return scope_add_ids_held(lane, s, n_ids, ids, out_added);
+}
+
+int orr_scope_combine(orr_scope *dst, int32_t op, const orr_scope *src)
+{
+    if (!scope_set::op_valid(op)) return fail(ORR_EINVAL, "orr_scope_combine: op must be ORR_SCOPE_AND (0), ORR_SCOPE_OR (1) or ORR_SCOPE_ANDNOT (2)");
+    if (!dst || !src) return fail(ORR_EINVAL, "orr_scope_combine: null scope");
+    orr_index *own = nullptr, *own_src = nullptr;
+    ORR_TRY(scope_owner(dst, nullptr, "orr_scope_combine", &own));
+    ORR_TRY(scope_owner(src, nullptr, "orr_scope_combine", &own_src));
+    if (own != own_src) return fail(ORR_EINVAL, "orr_scope_combine: the scopes belong to different shards");
+    Lane ln = acquire_lane(own);
+    orr_index *lane = ln.lane;
+    std::lock_guard<std::mutex> lock(lane->mu);
+    // dst exclusively, src shared, the lower address first (two combines with the roles swapped must not wait for each other)
+    std::unique_lock<std::shared_mutex> w(dst->mu, std::defer_lock);
+    std::shared_lock<std::shared_mutex> rd(src->mu, std::defer_lock);
+    if (src == dst) w.lock();
+    else if ((const void *)dst < (const void *)src) { w.lock(); rd.lock(); }
+    else { rd.lock(); w.lock(); }
+    ORR_TRY(scope_owner(dst, nullptr, "orr_scope_combine", &own));
+    ORR_TRY(scope_owner(src, nullptr, "orr_scope_combine", &own_src));
+    return scope_combine_held(lane, dst, op, src);
+}
+
+int64_t orr_scope_rows(const orr_scope *s)
+{
+    if (!s || !s->owner.load()) return -1;
+    return s->live.load();
+}
+
+int orr_scope_row_ids(orr_scope *s, int64_t cap, int64_t *out_ids, int64_t *out_n)
+{
+    if (cap < 0) return fail(ORR_EINVAL, "orr_scope_row_ids: cap is negative");
+    if (!out_n) return fail(ORR_EINVAL, "orr_scope_row_ids: out_n is NULL");
+    if (cap > 0 && !out_ids) return fail(ORR_EINVAL, "orr_scope_row_ids: out_ids is NULL with room for %lld ids", (long long)cap);
+    if (!s) return fail(ORR_EINVAL, "orr_scope_row_ids: null scope");
+    orr_index *own = nullptr;
+    ORR_TRY(scope_owner(s, nullptr, "orr_scope_row_ids", &own));
+    Lane ln = acquire_lane(own);
+    orr_index *lane = ln.lane;
+    std::lock_guard<std::mutex> lock(lane->mu);
+    std::shared_lock<std::shared_mutex> rd(s->mu);
+    ORR_TRY(scope_owner(s, nullptr, "orr_scope_row_ids", &own));
+    const int64_t live = s->live.load();
+    *out_n = live;
+    if (live > cap) return fail(ORR_EINVAL, "orr_scope_row_ids: the scope holds %lld rows, out_ids has room for %lld", (long long)live, (long long)cap);
+    if (live == 0) return ORR_OK;
+    return scope_row_ids_held(lane, s, live, out_ids);
 }
 
 void orr_scope_destroy(orr_scope *s)
@@ -5799,7 +5819,35 @@ int orr_search_shard_masked(orr_index *idx, int32_t B, int32_t dim, const float 
     std::lock_guard<std::mutex> lock(idx->mu);
     idx->sstats.searches += 1;
     idx->sstats.queries += B;
-    return masked_shard(idx, a, sc, scope_before, kprime, pass, out);
+    return masked_shard(idx, a, ScopeSource{&sc, nullptr}, scope_before, kprime, pass, out);
+}
+
+int orr_search_shard_in_scope(orr_index *idx, int32_t B, int32_t dim, const float *q, const uint8_t *terms_utf8,
+                              const uint32_t *term_off, const uint32_t *query_term_off, int64_t now_ticks, int32_t kprime,
+                              int64_t candidate_limit, int32_t topk, int32_t pass, const orr_scope *scope, int64_t scope_before,
+                              orr_candidate *out)
+{
+    static const char *fn = "orr_search_shard_in_scope";
+    BatchArgs a{B, dim, q, terms_utf8, term_off, query_term_off, now_ticks, candidate_limit, kprime};
+    if (kprime < 1) return fail(ORR_EINVAL, "%s: kprime must be >= 1", fn);
+    if (topk < 0) return fail(ORR_EINVAL, "%s: topk must be >= 0", fn);
+    if (pass < 0 || pass > 1) return fail(ORR_EINVAL, "%s: pass takes 0 (the library's choice) or 1 (the list path)", fn);
+    if (scope_before < 0) return fail(ORR_EINVAL, "%s: scope_before is negative", fn);
+    if (!out) return fail(ORR_EINVAL, "%s: out is NULL", fn);
+    if (!scope) return fail(ORR_EINVAL, "%s: null scope", fn);
+    ORR_TRY(check_batch(idx, a, fn));
+    if (topk > 0) a.topk = std::min<int32_t>(kprime, topk);
+    orr_index *own = nullptr;
+    ORR_TRY(scope_owner(scope, idx, fn, &own));
+    Lane ln = acquire_lane(idx);                       // a search like any other: its own lane, concurrent with the others
+    idx = ln.lane;
+    std::lock_guard<std::mutex> lock(idx->mu);
+    std::shared_lock<std::shared_mutex> rd(scope->mu);
+    ORR_TRY(scope_owner(scope, idx, fn, &own));
+    if (scope->n_rows != idx->n_rows) return fail(ORR_ESTATE, "%s: the scope covers %lld rows, the handle %lld", fn, (long long)scope->n_rows, (long long)idx->n_rows);
+    idx->sstats.searches += 1;
+    idx->sstats.queries += B;
+    return masked_shard(idx, a, ScopeSource{nullptr, scope}, scope_before, kprime, pass, out);
 }
 
 }  // extern "C"
@@ -5862,6 +5910,14 @@ struct orr_cluster {
     std::vector<DevBuf> xsend, xrecv;  // [G] grow-only
     PinnedBuf xhost;
     int64_t rccl_exchanges = 0;        // all-gathers done (orr_cluster_search_stats reports them in reserved[0])
+    std::vector<orr_cluster_scope *> cscopes;   // cluster scope handles that are alive, under g_scope_life_mu: orr_cluster_destroy orphans them
+};
+
+// A cluster scope handle: one orr_scope per shard of one sealed cluster, each made on its shard and registered there, so the
+// shards' maintenance carries them.  No count is kept here: rows and the search read every part's live when they are called.
+struct orr_cluster_scope {
+    std::atomic<orr_cluster *> owner{nullptr};   // nullptr: orphaned (the cluster was destroyed, or an edit ended on some shards only)
+    std::vector<orr_scope *> parts;              // [shards]
 };
 
 namespace {
@@ -6087,12 +6143,23 @@ Backend cluster_backend(orr_cluster *c, int64_t candidate_limit)
 // (scoped_shard / masked_shard, which resolve the scope again on the lane: nothing of the count is kept on the device) at k'
 // into its slice of one record array in host memory.  Merge: merge_into, as orr_merge_candidates_ex.  Ladder: the uncertified
 // queries repeat as a compacted sub-batch on the next rung (cscope::next_rung).  The rules are orr_cluster_scope_plan.h's.
+// With a handle (orr_cluster_search_batch_in_scope) there is no count step: the counts are the handles' own, read behind the
+// lanes and the shared holds, and the shard form takes each shard's part as it lies (orr_cluster_handle_plan.h).
 struct ClusterScope {
     bool masked;                   // one list shared by the batch through the masked shard form; else per-query lists (off) or a shared one
     int64_t n_ids;
     const int64_t *ids;            // host
     const uint64_t *off;           // host [B + 1] or null
+    const orr_cluster_scope *handle = nullptr;   // masked, instead of the list (orr_cluster_search_batch_in_scope)
 };
+
+// The cluster of a cluster scope, or ORR_ESTATE: orphaned.
+int cluster_scope_owner(const orr_cluster_scope *s, const char *fn, orr_cluster **c)
+{
+    *c = s->owner.load();
+    if (!*c) return fail(ORR_ESTATE, "%s: the cluster scope is orphaned: its cluster was destroyed, or an edit of it failed on some shards", fn);
+    return ORR_OK;
+}
 
 int cluster_scope_search(orr_cluster *c, const char *fn, const BatchArgs &orig, const ClusterScope &cs, int64_t *out_rows, double *out_scores,
                          int32_t *out_counts)
@@ -6106,7 +6173,7 @@ int cluster_scope_search(orr_cluster *c, const char *fn, const BatchArgs &orig, 
         c->sstats.searches += 1;
         c->sstats.queries += B;
     }
-    if (cs.n_ids == 0) return ORR_OK;
+    if (!cs.handle && cs.n_ids == 0) return ORR_OK;
     // all lanes before any shard starts, in ascending shard order (acquire_in_order says why), kept for the call
     std::vector<Lane> lanes;
     std::vector<LanePool *> pools;
@@ -6125,16 +6192,33 @@ int cluster_scope_search(orr_cluster *c, const char *fn, const BatchArgs &orig, 
     const int32_t nq = shared ? 1 : B;
     std::vector<int64_t> live((size_t)G * (size_t)nq, 0);
     const ScopeArgs whole{cs.n_ids, cs.ids, cs.off, nullptr};
-    ORR_TRY(for_each_shard(G, [&](int32_t g) -> int {
-        orr_index *sh = lanes[(size_t)g].lane;
-        std::lock_guard<std::mutex> lock(sh->mu);
-        return scope_count_on_lane(sh, nq, whole, live.data() + (size_t)g * (size_t)nq);
-    }));
     std::vector<cscope::Split> split((size_t)nq);          // per query (a shared list: one for all)
-    for (int32_t b = 0; b < nq; ++b) {
-        std::vector<int64_t> col((size_t)G);
-        for (int32_t g = 0; g < G; ++g) col[(size_t)g] = live[(size_t)g * (size_t)nq + (size_t)b];
-        split[(size_t)b] = cscope::split_limit(col, orig.candidate_limit);
+    // a handle: no count step.  Behind the lanes (no delete, compaction or insertion runs on a shard whose lane is held) every
+    // shard's scope is taken shared in ascending shard order, and the counts are the handles' own.
+    std::vector<std::shared_lock<std::shared_mutex>> held;
+    if (cs.handle) {
+        held.reserve((size_t)G);
+        for (int32_t g = 0; g < G; ++g) held.emplace_back(cs.handle->parts[(size_t)g]->mu);
+        for (int32_t g = 0; g < G; ++g) {
+            const orr_scope *part = cs.handle->parts[(size_t)g];
+            orr_index *own = nullptr;
+            ORR_TRY(scope_owner(part, c->shards[(size_t)g], fn, &own));
+            if (part->n_rows != lanes[(size_t)g].lane->n_rows)
+                return fail(ORR_ESTATE, "%s: the scope covers %lld rows of shard %d, the shard holds %lld", fn, (long long)part->n_rows, g, (long long)lanes[(size_t)g].lane->n_rows);
+            live[(size_t)g] = part->live.load();
+        }
+        if (!chandle::handle_split(live, orig.candidate_limit, split[0])) return fail(ORR_ESTATE, "%s: a shard's scope is orphaned", fn);
+    } else {
+        ORR_TRY(for_each_shard(G, [&](int32_t g) -> int {
+            orr_index *sh = lanes[(size_t)g].lane;
+            std::lock_guard<std::mutex> lock(sh->mu);
+            return scope_count_on_lane(sh, nq, whole, live.data() + (size_t)g * (size_t)nq);
+        }));
+        for (int32_t b = 0; b < nq; ++b) {
+            std::vector<int64_t> col((size_t)G);
+            for (int32_t g = 0; g < G; ++g) col[(size_t)g] = live[(size_t)g * (size_t)nq + (size_t)b];
+            split[(size_t)b] = cscope::split_limit(col, orig.candidate_limit);
+        }
     }
     auto split_of = [&](int32_t b) -> const cscope::Split & { return split[shared ? 0 : (size_t)b]; };
 
@@ -6189,7 +6273,8 @@ int cluster_scope_search(orr_cluster *c, const char *fn, const BatchArgs &orig, 
                 if (use_cos) a.norms_host = sub_norms.data();
                 orr_candidate *dst = recs.data() + (size_t)g * (size_t)nb * rec_q;
                 sh->sstats.searches += 1; sh->sstats.queries += nb;
-                if (cs.masked) return masked_shard(sh, a, sc, before[(size_t)g * (size_t)nb], kprime, r.rung.pass, dst);
+                if (cs.handle) return masked_shard(sh, a, ScopeSource{nullptr, cs.handle->parts[(size_t)g]}, before[(size_t)g * (size_t)nb], kprime, r.rung.pass, dst);
+                if (cs.masked) return masked_shard(sh, a, ScopeSource{&sc, nullptr}, before[(size_t)g * (size_t)nb], kprime, r.rung.pass, dst);
                 ScopeArgs mine = sc;
                 mine.before = before.data() + (size_t)g * (size_t)nb;
                 return scoped_shard(sh, a, mine, kprime, dst);
@@ -6278,6 +6363,11 @@ void orr_cluster_destroy(orr_cluster *c)
         }
     }
     c->xhost.release();
+    {   // cluster scopes that are still alive are orphaned before their shards go (each shard then orphans its part)
+        std::lock_guard<std::mutex> life(g_scope_life_mu);
+        for (orr_cluster_scope *s : c->cscopes) s->owner.store(nullptr);
+        c->cscopes.clear();
+    }
     for (orr_index *sh : c->shards) orr_index_destroy(sh);
     delete c;
 }
@@ -6458,6 +6548,274 @@ int orr_cluster_search_stats(orr_cluster *c, orr_search_stats *out, int32_t rese
     if (out) { *out = c->sstats; out->reserved[0] = c->rccl_exchanges; }
     if (reset) c->sstats = orr_search_stats{};
     return ORR_OK;
+}
+
+}  // extern "C"
+
+// ---- cluster scope handles (orr_cluster_scope): one orr_scope per shard, the rules are orr_cluster_handle_plan.h's ------------
+
+namespace {
+
+// One lane per shard, in ascending shard order (acquire_in_order says why), for a call that works on every shard.
+void acquire_cluster_lanes(orr_cluster *c, std::vector<Lane> &lanes)
+{
+    std::vector<LanePool *> pools;
+    std::vector<LanePool::Make> makes;
+    for (orr_index *sh : c->shards) { pools.push_back(&sh->lanes); makes.push_back(lane_maker(sh)); }
+    acquire_in_order(pools, makes, lanes);
+}
+
+// Every part belongs to its shard of `c` still (none was orphaned on its own); the caller holds the parts.
+int cluster_scope_parts_alive(const orr_cluster *c, const orr_cluster_scope *s, const char *fn)
+{
+    for (size_t g = 0; g < s->parts.size(); ++g) {
+        orr_index *own = nullptr;
+        ORR_TRY(scope_owner(s->parts[g], c->shards[g], fn, &own));
+    }
+    return ORR_OK;
+}
+
+// The cluster scope can no longer be used (ORR_ESTATE from now on); its parts stay with their shards until it is destroyed.
+void orphan_cluster_scope(orr_cluster_scope *s)
+{
+    std::lock_guard<std::mutex> life(g_scope_life_mu);
+    orr_cluster *c = s->owner.load();
+    if (!c) return;
+    c->cscopes.erase(std::remove(c->cscopes.begin(), c->cscopes.end(), s), c->cscopes.end());
+    s->owner.store(nullptr);
+}
+
+// A new cluster scope: make(shard, &part) on every shard at once.  A failure on any shard destroys the parts already made.
+int make_cluster_scope(orr_cluster *c, const char *fn, orr_cluster_scope **out, const std::function<int(orr_index *, orr_scope **)> &make)
+{
+    std::shared_lock<std::shared_mutex> lock(c->mu);   // like a search: beside the others; seal, compact, insert are exclusive
+    if (!c->sealed) return fail(ORR_ESTATE, "%s: the cluster is not sealed", fn);
+    const int32_t G = (int32_t)c->shards.size();
+    orr_cluster_scope *s = new (std::nothrow) orr_cluster_scope();
+    if (!s) return fail(ORR_ENOMEM, "out of host memory");
+    s->parts.assign((size_t)G, nullptr);
+    const int r = for_each_shard(G, [&](int32_t g) -> int { return make(c->shards[(size_t)g], &s->parts[(size_t)g]); });
+    if (r != ORR_OK) {
+        const std::string keep = g_last_error;
+        for (orr_scope *part : s->parts) orr_scope_destroy(part);
+        delete s;
+        g_last_error = keep;
+        return r;
+    }
+    s->owner.store(c);
+    { std::lock_guard<std::mutex> life(g_scope_life_mu); c->cscopes.push_back(s); }
+    *out = s;
+    return ORR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int orr_cluster_scope_create(orr_cluster *c, int64_t n_ids, const int64_t *ids, orr_cluster_scope **out)
+{
+    static const char *fn = "orr_cluster_scope_create";
+    if (!out) return fail(ORR_EINVAL, "%s: out is NULL", fn);
+    if (n_ids < 0) return fail(ORR_EINVAL, "%s: n_ids is negative", fn);
+    if (n_ids > 0 && !ids) return fail(ORR_EINVAL, "%s: ids is NULL with %lld ids", fn, (long long)n_ids);
+    if (!c) return fail(ORR_EINVAL, "%s: null cluster", fn);
+    if (n_ids > 0 && is_device_pointer(ids)) return fail(ORR_EINVAL, "%s: ids must be in host memory (every shard's device reads them)", fn);
+    return make_cluster_scope(c, fn, out, [&](orr_index *sh, orr_scope **part) { return orr_scope_create(sh, n_ids, ids, part); });
+}
+
+int orr_cluster_scope_create_ticks(orr_cluster *c, int64_t ticks_from, int64_t ticks_to, orr_cluster_scope **out)
+{
+    static const char *fn = "orr_cluster_scope_create_ticks";
+    if (!out) return fail(ORR_EINVAL, "%s: out is NULL", fn);
+    if (!c) return fail(ORR_EINVAL, "%s: null cluster", fn);
+    return make_cluster_scope(c, fn, out, [&](orr_index *sh, orr_scope **part) { return orr_scope_create_ticks(sh, ticks_from, ticks_to, part); });
+}
+
+int orr_cluster_scope_create_terms(orr_cluster *c, int32_t n_terms, const uint8_t *terms_utf8, const uint32_t *term_off, int32_t mode,
+                                   orr_cluster_scope **out)
+{
+    static const char *fn = "orr_cluster_scope_create_terms";
+    if (!out) return fail(ORR_EINVAL, "%s: out is NULL", fn);
+    if (!scope_terms::terms_valid(n_terms)) return fail(ORR_EINVAL, "%s: n_terms must be in 0 .. %d", fn, scope_terms::kMaxTerms);
+    if (n_terms > 0 && (!terms_utf8 || !term_off)) return fail(ORR_EINVAL, "%s: terms_utf8 or term_off is NULL with %d terms", fn, n_terms);
+    if (!scope_terms::mode_valid(mode)) return fail(ORR_EINVAL, "%s: mode must be ORR_TERMS_ALL (0) or ORR_TERMS_ANY (1)", fn);
+    const int32_t bad = scope_terms::first_bad_term(term_off, n_terms);
+    if (bad >= 0 && term_off[bad + 1] == term_off[bad]) return fail(ORR_EINVAL, "%s: term %d is empty", fn, bad);
+    if (bad >= 0) return fail(ORR_EINVAL, "%s: term_off is not monotone at term %d", fn, bad);
+    if (!c) return fail(ORR_EINVAL, "%s: null cluster", fn);
+    return make_cluster_scope(c, fn, out, [&](orr_index *sh, orr_scope **part) { return orr_scope_create_terms(sh, n_terms, terms_utf8, term_off, mode, part); });
+}
+
+int orr_cluster_scope_add_ids(orr_cluster_scope *s, int64_t n_ids, const int64_t *ids, int64_t *out_added)
+{
+    static const char *fn = "orr_cluster_scope_add_ids";
+    if (n_ids < 0) return fail(ORR_EINVAL, "%s: n_ids is negative", fn);
+    if (n_ids > 0 && !ids) return fail(ORR_EINVAL, "%s: ids is NULL with %lld ids", fn, (long long)n_ids);
+    if (!s) return fail(ORR_EINVAL, "%s: null scope", fn);
+    if (n_ids > 0 && is_device_pointer(ids)) return fail(ORR_EINVAL, "%s: ids must be in host memory (every shard's device reads them)", fn);
+    orr_cluster *c = nullptr;
+    ORR_TRY(cluster_scope_owner(s, fn, &c));
+    std::shared_lock<std::shared_mutex> lock(c->mu);
+    const int32_t G = (int32_t)c->shards.size();
+    std::vector<Lane> lanes;
+    acquire_cluster_lanes(c, lanes);
+    std::vector<std::unique_lock<std::shared_mutex>> held;     // every part exclusively, in ascending shard order
+    held.reserve((size_t)G);
+    for (int32_t g = 0; g < G; ++g) held.emplace_back(s->parts[(size_t)g]->mu);
+    ORR_TRY(cluster_scope_owner(s, fn, &c));
+    ORR_TRY(cluster_scope_parts_alive(c, s, fn));
+    std::vector<int64_t> added((size_t)G, 0);
+    const int r = for_each_shard(G, [&](int32_t g) -> int {
+        orr_index *lane = lanes[(size_t)g].lane;
+        std::lock_guard<std::mutex> l(lane->mu);
+        return scope_add_ids_held(lane, s->parts[(size_t)g], n_ids, ids, &added[(size_t)g]);
+    });
+    if (r != ORR_OK) {             // some shards may hold the edit and others not: never searched like that
+        const std::string keep = g_last_error;
+        orphan_cluster_scope(s);
+        g_last_error = keep;
+        return r;
+    }
+    if (out_added) { *out_added = 0; for (int64_t a : added) *out_added += a; }
+    return ORR_OK;
+}
+
+int orr_cluster_scope_combine(orr_cluster_scope *dst, int32_t op, const orr_cluster_scope *src)
+{
+    static const char *fn = "orr_cluster_scope_combine";
+    if (!scope_set::op_valid(op)) return fail(ORR_EINVAL, "%s: op must be ORR_SCOPE_AND (0), ORR_SCOPE_OR (1) or ORR_SCOPE_ANDNOT (2)", fn);
+    if (!dst || !src) return fail(ORR_EINVAL, "%s: null scope", fn);
+    auto pair = [&](orr_cluster **c) -> int {
+        *c = dst->owner.load();
+        switch (chandle::pair_valid(*c, src->owner.load(), dst->parts.size(), src->parts.size())) {
+        case chandle::Pair::Orphaned: return fail(ORR_ESTATE, "%s: a cluster scope is orphaned: its cluster was destroyed, or an edit of it failed on some shards", fn);
+        case chandle::Pair::OtherCluster: return fail(ORR_EINVAL, "%s: the scopes belong to different clusters", fn);
+        case chandle::Pair::Shards: return fail(ORR_ESTATE, "%s: the scopes cover different numbers of shards", fn);
+        case chandle::Pair::Ok: break;
+        }
+        return ORR_OK;
+    };
+    orr_cluster *c = nullptr;
+    ORR_TRY(pair(&c));
+    std::shared_lock<std::shared_mutex> lock(c->mu);
+    const int32_t G = (int32_t)c->shards.size();
+    std::vector<Lane> lanes;
+    acquire_cluster_lanes(c, lanes);
+    // ascending shard; within a shard dst exclusively, src shared, the lower address first (chandle::holds)
+    std::vector<uintptr_t> a_dst, a_src;
+    for (int32_t g = 0; g < G; ++g) {
+        a_dst.push_back(reinterpret_cast<uintptr_t>(dst->parts[(size_t)g]));
+        a_src.push_back(reinterpret_cast<uintptr_t>(src->parts[(size_t)g]));
+    }
+    std::vector<std::unique_lock<std::shared_mutex>> held_w;
+    std::vector<std::shared_lock<std::shared_mutex>> held_r;
+    held_w.reserve((size_t)G); held_r.reserve((size_t)G);
+    for (const chandle::Hold &h : chandle::holds(a_dst, a_src, true)) {
+        if (h.exclusive) held_w.emplace_back(dst->parts[(size_t)h.shard]->mu);
+        else held_r.emplace_back(src->parts[(size_t)h.shard]->mu);
+    }
+    ORR_TRY(pair(&c));
+    ORR_TRY(cluster_scope_parts_alive(c, dst, fn));
+    ORR_TRY(cluster_scope_parts_alive(c, src, fn));
+    const int r = for_each_shard(G, [&](int32_t g) -> int {
+        orr_index *lane = lanes[(size_t)g].lane;
+        std::lock_guard<std::mutex> l(lane->mu);
+        return scope_combine_held(lane, dst->parts[(size_t)g], op, src->parts[(size_t)g]);
+    });
+    if (r != ORR_OK) {             // some shards may hold the edit and others not: never searched like that
+        const std::string keep = g_last_error;
+        held_w.clear(); held_r.clear();
+        orphan_cluster_scope(dst);
+        g_last_error = keep;
+    }
+    return r;
+}
+
+int64_t orr_cluster_scope_rows(const orr_cluster_scope *s)
+{
+    if (!s || !s->owner.load()) return -1;
+    int64_t n = 0;
+    for (const orr_scope *part : s->parts) {
+        const int64_t live = orr_scope_rows(part);
+        if (live < 0) return -1;
+        n += live;
+    }
+    return n;
+}
+
+int orr_cluster_scope_row_ids(orr_cluster_scope *s, int64_t cap, int64_t *out_ids, int64_t *out_n)
+{
+    static const char *fn = "orr_cluster_scope_row_ids";
+    if (cap < 0) return fail(ORR_EINVAL, "%s: cap is negative", fn);
+    if (!out_n) return fail(ORR_EINVAL, "%s: out_n is NULL", fn);
+    if (cap > 0 && !out_ids) return fail(ORR_EINVAL, "%s: out_ids is NULL with room for %lld ids", fn, (long long)cap);
+    if (!s) return fail(ORR_EINVAL, "%s: null scope", fn);
+    orr_cluster *c = nullptr;
+    ORR_TRY(cluster_scope_owner(s, fn, &c));
+    std::shared_lock<std::shared_mutex> lock(c->mu);
+    const int32_t G = (int32_t)c->shards.size();
+    std::vector<Lane> lanes;
+    acquire_cluster_lanes(c, lanes);
+    std::vector<std::shared_lock<std::shared_mutex>> held;
+    held.reserve((size_t)G);
+    for (int32_t g = 0; g < G; ++g) held.emplace_back(s->parts[(size_t)g]->mu);
+    ORR_TRY(cluster_scope_owner(s, fn, &c));
+    ORR_TRY(cluster_scope_parts_alive(c, s, fn));
+    std::vector<int64_t> live((size_t)G);
+    for (int32_t g = 0; g < G; ++g) live[(size_t)g] = s->parts[(size_t)g]->live.load();
+    const chandle::RowIdPlan plan = chandle::row_id_plan(live, cap);
+    *out_n = plan.total;
+    if (!plan.fits) return fail(ORR_EINVAL, "%s: the scope holds %lld rows, out_ids has room for %lld", fn, (long long)plan.total, (long long)cap);
+    return for_each_shard(G, [&](int32_t g) -> int {
+        if (live[(size_t)g] <= 0) return ORR_OK;
+        orr_index *lane = lanes[(size_t)g].lane;
+        std::lock_guard<std::mutex> l(lane->mu);
+        return scope_row_ids_held(lane, s->parts[(size_t)g], live[(size_t)g], out_ids + plan.offset[(size_t)g]);
+    });
+}
+
+const orr_scope *orr_cluster_scope_shard(const orr_cluster_scope *s, int32_t i)
+{
+    if (!s || i < 0 || i >= (int32_t)s->parts.size()) { (void)fail(ORR_EINVAL, "orr_cluster_scope_shard: no shard %d", i); return nullptr; }
+    return s->parts[(size_t)i];
+}
+
+void orr_cluster_scope_destroy(orr_cluster_scope *s)
+{
+    if (!s) return;
+    {   // (the cluster is not destroyed meanwhile; afterwards it no longer knows this scope)
+        std::lock_guard<std::mutex> life(g_scope_life_mu);
+        orr_cluster *c = s->owner.load();
+        if (c) c->cscopes.erase(std::remove(c->cscopes.begin(), c->cscopes.end(), s), c->cscopes.end());
+        s->owner.store(nullptr);
+    }
+    for (orr_scope *part : s->parts) orr_scope_destroy(part);      // each against its own shard's destroy, as a single scope
+    delete s;
+}
+
+int orr_cluster_search_batch_in_scope(orr_cluster *c, int32_t B, int32_t dim, const float *q_host, const uint8_t *terms_utf8,
+                                      const uint32_t *term_off, const uint32_t *query_term_off, int64_t now_ticks, int32_t topk,
+                                      int64_t candidate_limit, const orr_cluster_scope *scope, int64_t *out_rows, double *out_scores,
+                                      int32_t *out_counts)
+{
+    static const char *fn = "orr_cluster_search_batch_in_scope";
+    const BatchArgs a{B, dim, q_host, terms_utf8, term_off, query_term_off, now_ticks, candidate_limit, topk};
+    if (B <= 0) return fail(ORR_EINVAL, "%s: batch size must be positive", fn);
+    if (dim < 0) return fail(ORR_EINVAL, "%s: negative query dimension", fn);
+    if (dim > 0 && !q_host) return fail(ORR_EINVAL, "%s: q is NULL with dim %d", fn, dim);
+    if (!query_term_off) return fail(ORR_EINVAL, "%s: query_term_off is required", fn);
+    if (!out_rows || !out_scores) return fail(ORR_EINVAL, "%s: output buffers are required", fn);
+    if (!scope) return fail(ORR_EINVAL, "%s: null scope", fn);
+    if (!c) return fail(ORR_EINVAL, "%s: null cluster", fn);
+    if (dim > 0 && is_device_pointer(q_host)) return fail(ORR_EINVAL, "%s: the query vectors must be in host memory (every shard's device reads them)", fn);
+    std::shared_lock<std::shared_mutex> lock(c->mu);   // searches run side by side; seal and destroy are exclusive
+    if (!c->sealed) return fail(ORR_ESTATE, "%s: the cluster is not sealed", fn);
+    orr_cluster *own = nullptr;
+    ORR_TRY(cluster_scope_owner(scope, fn, &own));
+    if (own != c || scope->parts.size() != c->shards.size()) return fail(ORR_EINVAL, "%s: the scope belongs to another cluster", fn);
+    ClusterScope cs{true, 0, nullptr, nullptr};
+    cs.handle = scope;
+    return cluster_scope_search(c, fn, a, cs, out_rows, out_scores, out_counts);
 }
 
 }  // extern "C"

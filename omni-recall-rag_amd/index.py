@@ -134,6 +134,86 @@ class RecallScope:
         return self._combine(N.ORR_SCOPE_ANDNOT, other)
 
 
+class _BorrowedScope(RecallScope):
+    """A shard's part of a RecallClusterScope: usable like a RecallScope (rows, row_ids, RecallIndex.search_shard_in_scope),
+    never destroyed through this object; it ends with its cluster scope."""
+
+    def close(self) -> None:
+        self._h = None
+
+
+class RecallClusterScope:
+    """A cluster scope handle (orr_cluster_scope): a set of ROWS of one sealed cluster, held as one scope per shard.  Every
+    rule of RecallScope holds per shard; it follows its rows through delete_rows on a shard, RecallCluster.compact and
+    insert_rows.  Made by RecallCluster.scope / scope_ticks / scope_terms; close it before or after its cluster (after: only
+    the host part is left to free)."""
+
+    def __init__(self, handle, cluster: "RecallCluster"):
+        self._h = handle
+        self._cluster = cluster              # keeps the cluster object alive
+        self._parts = []
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            for part in self._parts:
+                part.close()
+            self._parts = []
+            N.hip.orr_cluster_scope_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def rows(self) -> int:
+        """orr_cluster_scope_rows: live rows in the scope now, over all shards; -1 once it is orphaned."""
+        return int(N.hip.orr_cluster_scope_rows(self._h))
+
+    def row_ids(self) -> np.ndarray:
+        """orr_cluster_scope_row_ids: the ids of the scope's live rows in the global candidate order."""
+        n = C.c_int64(0)
+        out = np.zeros(max(self.rows, 0), dtype=np.int64)
+        N.check(N.hip.orr_cluster_scope_row_ids(self._h, int(out.shape[0]), _ptr(out) if out.shape[0] else None, C.cast(C.byref(n), C.c_void_p)))
+        return out[:int(n.value)]
+
+    def add_ids(self, row_ids) -> int:
+        """orr_cluster_scope_add_ids: the live rows that carry these ids (numpy, host memory) join the scope on every shard.
+        Returns how many were not in it before."""
+        ids = np.ascontiguousarray(row_ids, dtype=np.int64).reshape(-1)
+        n_ids = int(ids.shape[0])
+        added = C.c_int64(0)
+        N.check(N.hip.orr_cluster_scope_add_ids(self._h, n_ids, _ptr(ids) if n_ids else None, C.cast(C.byref(added), C.c_void_p)))
+        return int(added.value)
+
+    def _combine(self, op: int, other: "RecallClusterScope") -> "RecallClusterScope":
+        N.check(N.hip.orr_cluster_scope_combine(self._h, op, other._h))
+        return self
+
+    def and_(self, other: "RecallClusterScope") -> "RecallClusterScope":
+        """self = self AND other, in place, on every shard."""
+        return self._combine(N.ORR_SCOPE_AND, other)
+
+    def or_(self, other: "RecallClusterScope") -> "RecallClusterScope":
+        """self = self OR other, in place, on every shard."""
+        return self._combine(N.ORR_SCOPE_OR, other)
+
+    def andnot(self, other: "RecallClusterScope") -> "RecallClusterScope":
+        """self = self AND NOT other, in place, on every shard."""
+        return self._combine(N.ORR_SCOPE_ANDNOT, other)
+
+    def shard(self, i: int) -> RecallScope:
+        """orr_cluster_scope_shard: shard i's part, borrowed."""
+        p = N.hip.orr_cluster_scope_shard(self._h, int(i))
+        if not p:
+            N.check(N.ORR_EINVAL)
+        part = _BorrowedScope(C.c_void_p(p), self)
+        self._parts.append(part)
+        return part
+
+
 class RecallIndex:
     """One corpus shard resident on one GPU (orr_index)."""
 
@@ -484,6 +564,20 @@ class RecallIndex:
                                               int(scope_before), _ptr(out)))
         return out
 
+    def search_shard_in_scope(self, qvecs, queries_terms, now_ticks: int, kprime: int, candidate_limit: int, scope: RecallScope,
+                              scope_before: int = 0, topk: int = 0, shard_pass: int = 0, out=None):
+        """orr_search_shard_in_scope: search_shard_masked with the scope taken from a handle of this shard (a RecallScope, or
+        RecallClusterScope.shard(i)); scope_before: the scope's live rows on the shards in front (their handles' rows)."""
+        B = len(queries_terms)
+        dim, q, _keep = self._query_args(qvecs, B)
+        pool, toff, qoff = pack_terms(queries_terms)
+        if out is None:
+            out = np.zeros((B, kprime + 1), dtype=CAND_DTYPE)
+        N.check(N.hip.orr_search_shard_in_scope(self._h, B, dim, _ptr(q), _ptr(pool), _ptr(toff), _ptr(qoff), now_ticks, int(kprime),
+                                                int(candidate_limit), max(0, int(topk)), int(shard_pass), scope._h,
+                                                int(scope_before), _ptr(out)))
+        return out
+
     def scope_count(self, scope_ids, n_queries: int = 1) -> np.ndarray:
         """orr_index_scope_count: [n_queries] int64, the live rows each query's scope resolves to on this shard."""
         n_ids, ids, off = self._scope_args(scope_ids, n_queries)
@@ -705,6 +799,47 @@ class RecallCluster:
         N.check(N.hip.orr_cluster_search_batch_masked(self._h, B, dim, _ptr(q), _ptr(pool), _ptr(toff), _ptr(qoff), now_ticks, int(topk),
                                                       int(candidate_limit), n_ids, _ptr(ids) if n_ids else None,
                                                       _ptr(rows), _ptr(scores), _ptr(counts)))
+        return rows, scores, counts
+
+    def scope(self, row_ids) -> RecallClusterScope:
+        """orr_cluster_scope_create: the live rows that carry these ids (numpy, host memory), resolved once on every shard."""
+        ids = np.ascontiguousarray(row_ids, dtype=np.int64).reshape(-1)
+        n_ids = int(ids.shape[0])
+        h = C.c_void_p()
+        N.check(N.hip.orr_cluster_scope_create(self._h, n_ids, _ptr(ids) if n_ids else None, C.byref(h)))
+        return RecallClusterScope(h, self)
+
+    def scope_ticks(self, ticks_from: int, ticks_to: int) -> RecallClusterScope:
+        """orr_cluster_scope_create_ticks: the live rows with ticks_from <= CreatedAtUtc.Ticks < ticks_to, on every shard."""
+        h = C.c_void_p()
+        N.check(N.hip.orr_cluster_scope_create_ticks(self._h, int(ticks_from), int(ticks_to), C.byref(h)))
+        return RecallClusterScope(h, self)
+
+    def scope_terms(self, terms: Sequence[bytes], mode: str = "all") -> RecallClusterScope:
+        """orr_cluster_scope_create_terms: the live rows whose lowercased content contains every term (mode "all") or at
+        least one (mode "any"), on every shard.  terms: lowercased bytes without whitespace; no terms give an empty scope."""
+        modes = {"all": N.ORR_TERMS_ALL, "any": N.ORR_TERMS_ANY}
+        if mode not in modes:
+            raise ValueError('mode: "all" or "any"')
+        pool, toff, _ = pack_terms([list(terms)])
+        n_terms = int(toff.shape[0]) - 1
+        h = C.c_void_p()
+        N.check(N.hip.orr_cluster_scope_create_terms(self._h, n_terms, _ptr(pool), _ptr(toff), modes[mode], C.byref(h)))
+        return RecallClusterScope(h, self)
+
+    def search_in_scope(self, qvecs, queries_terms, now_ticks: int, topk: int, scope: RecallClusterScope, candidate_limit: int = 300):
+        """orr_cluster_search_batch_in_scope: search_masked with the scope taken from a handle -- no id list goes to the
+        shards, nothing is counted or resolved per call.  qvecs in host memory (numpy) or None.
+        Returns (rows [B,k] int64, scores [B,k] float64, counts [B] int32)."""
+        B = len(queries_terms)
+        dim, q = self._host_query_args(qvecs, B)
+        pool, toff, qoff = pack_terms(queries_terms)
+        k = max(1, int(topk))
+        rows = np.full((B, k), -1, dtype=np.int64)
+        scores = np.zeros((B, k), dtype=np.float64)
+        counts = np.zeros(B, dtype=np.int32)
+        N.check(N.hip.orr_cluster_search_batch_in_scope(self._h, B, dim, _ptr(q), _ptr(pool), _ptr(toff), _ptr(qoff), now_ticks, int(topk),
+                                                        int(candidate_limit), scope._h, _ptr(rows), _ptr(scores), _ptr(counts)))
         return rows, scores, counts
 
     def set_option(self, name: str, value: int) -> None:
