@@ -573,6 +573,29 @@ int orr_search_shard_in_scope(orr_index *idx, int32_t B, int32_t dim, const floa
                               int64_t now_ticks, int32_t kprime, int64_t candidate_limit, int32_t topk, int32_t pass,
                               const orr_scope *scope, int64_t scope_before, orr_candidate *out);
 
+/* orr_search_batch_in_scopes in record form: the shard half of orr_cluster_search_batch_in_scopes, with the contract of
+ * orr_search_shard_in_scope.  Query b's [kprime+1] records and trailer are those of a search inside scopes[query_scope[b]];
+ * orr_merge_candidates(_ex) takes them unchanged.  candidate_limit is GLOBAL and scope_before[g] is scope g's live rows on the
+ * shards in front (their handles' orr_scope_rows): min(live_g, max(0, max(1, candidate_limit) - scope_before[g])) rows of scope
+ * g take part here.  ONE pass at the caller's kprime, no ladder inside but the one in-call repeat of queries whose survivors'
+ * buffers overflowed (with buffers of the call's own: "survivor_capacity" does not change); `pass` 0 / 1 and topk as in the
+ * masked shard form.  The scopes large enough to screen share one pass over the shard's shadow (pass_mode 6; the front of that
+ * pass gathers the handles' bitmaps and clips them in one launch); a small scope, and every scope where the shared pass is not
+ * eligible or does not pay, answers through orr_search_shard_in_scope's pass for its queries.  A query's trailer carries in
+ * order_key the rows of its OWN scope that took part here, and behind the screen ORR_CAND_TWO_STAGE with the floor in norm_b;
+ * a query whose scope lets no row take part here gets an empty record list.  With one used scope the records are
+ * orr_search_shard_in_scope's, record for record.  n_scopes is 1 .. 64; scopes may repeat, overlap, be empty or be named by
+ * no query.
+ * ORR_EINVAL before any device call and before a handle is looked at, in this order: n_scopes outside 1 .. 64; scopes or an entry
+ * of it NULL; query_scope NULL or an entry outside [0, n_scopes); scope_before NULL or a negative entry; kprime < 1, topk < 0,
+ * pass outside {0, 1}, out NULL; then a NULL index and the batch's argument errors; then a scope of another shard.
+ * ORR_ESTATE: an orphaned scope. */
+int orr_search_shard_in_scopes(orr_index *idx, int32_t B, int32_t dim, const float *q,
+                               const uint8_t *terms_utf8, const uint32_t *term_off, const uint32_t *query_term_off,
+                               int64_t now_ticks, int32_t kprime, int64_t candidate_limit, int32_t topk, int32_t pass,
+                               int32_t n_scopes, const orr_scope *const *scopes, const int32_t *query_scope /* host [B] */,
+                               const int64_t *scope_before /* host [n_scopes] */, orr_candidate *out);
+
 /* ---- tuning knobs ----------------------------------------------------------
  * Integer options of one index; unknown names are ORR_EINVAL.
  *   "dead_rows_before"  deleted rows in the shards in front of this one (default 0), see above.
@@ -797,6 +820,26 @@ int orr_cluster_search_batch_in_scope(orr_cluster *c, int32_t B, int32_t dim, co
                                       int64_t now_ticks, int32_t topk, int64_t candidate_limit,
                                       const orr_cluster_scope *scope,
                                       int64_t *out_rows, double *out_scores, int32_t *out_counts);
+
+/* Several cluster scopes in one batch: query b searches inside scopes[query_scope[b]], and its rows, order and fp64 scores are
+ * bit for bit what orr_cluster_search_batch_in_scope returns for it with that scope.  candidate_limit counts each scope's own
+ * live rows over the whole cluster.  n_scopes is 1 .. 64; scopes may repeat (a handle listed twice is one group and is held
+ * once), overlap, be empty or be named by no query; the results never depend on which path ran.
+ * Behind the lanes the parts of all distinct scopes are taken shared in one total order (ascending shard, within a shard
+ * ascending part address), the live counts are read from the handles (no count step), the limit is split per scope, and every
+ * shard runs orr_search_shard_in_scopes ONCE for the whole batch: the shards stream their shadows once per batch, not once per
+ * scope.  A query the merge cannot certify repeats through the in-scope cluster ladder of its own scope, together with that
+ * scope's other uncertified queries.  One used scope IS orr_cluster_search_batch_in_scope.  orr_cluster_search_stats reports
+ * pass_mode 6 when a shard ran the shared pass; passes and requeried count as in the in-scope call.
+ * Errors, in this order, with the outputs untouched: ORR_EINVAL for n_scopes outside 1 .. 64; scopes or an entry of it NULL;
+ * query_scope NULL or an entry outside [0, n_scopes); B <= 0, dim < 0, q_host NULL with dim > 0, query_term_off NULL, out_rows
+ * or out_scores NULL; a NULL cluster; q_host in device memory.  ORR_ESTATE for an unsealed cluster or an orphaned scope;
+ * ORR_EINVAL for a scope of another cluster. */
+int orr_cluster_search_batch_in_scopes(orr_cluster *c, int32_t B, int32_t dim, const float *q_host,
+                                       const uint8_t *terms_utf8, const uint32_t *term_off, const uint32_t *query_term_off,
+                                       int64_t now_ticks, int32_t topk, int64_t candidate_limit,
+                                       int32_t n_scopes, const orr_cluster_scope *const *scopes, const int32_t *query_scope /* host [B] */,
+                                       int64_t *out_rows, double *out_scores, int32_t *out_counts);
 
 #ifdef __cplusplus
 }

@@ -41,6 +41,7 @@
 #include "orr_scope_set_plan.h"
 #include "orr_scope_terms_plan.h"
 #include "orr_cluster_handle_plan.h"
+#include "orr_cluster_group_plan.h"
 #include "orr_cluster_scope_plan.h"
 #include "orr_token_index.h"
 
@@ -3875,6 +3876,7 @@ struct SubBatch {                  // storage of a compacted sub-batch (the vect
     std::vector<float> q_host;
     std::vector<uint8_t> pool;
     std::vector<uint32_t> term_off, qoff;
+    std::vector<double> norms;
 };
 
 // The queries `ids` of `orig` as a batch of their own: `orig` itself where that is all of them in order.
@@ -3886,6 +3888,11 @@ int build_subset(orr_index *idx, const BatchArgs &orig, const std::vector<int32_
     for (int32_t i = 0; i < nb && whole; ++i) whole = ids[(size_t)i] == i;
     if (whole) return ORR_OK;
     out.B = nb;
+    if (orig.norms_host) {                             // (per query of the batch, as the vectors are)
+        sb.norms.resize((size_t)nb);
+        for (int32_t i = 0; i < nb; ++i) sb.norms[(size_t)i] = orig.norms_host[ids[(size_t)i]];
+        out.norms_host = sb.norms.data();
+    }
     if (orig.dim > 0) {
         const size_t row = (size_t)orig.dim;
         if (is_device_pointer(orig.q)) {
@@ -4806,11 +4813,137 @@ int grouped_screen_ladder(orr_index *idx, const BatchArgs &orig, const GroupArgs
     return ORR_OK;
 }
 
+// The front of a grouped call on the lane the caller holds: resolve (G bitmaps; the handles bring theirs), gather, clip, plan.
+// took: with handles, the rows of each group that take part on this shard (the caller's rule: the index call's
+// group::took_of, the shard form's cscope::shard_took); ignored for lists, whose slice counts them under the call's limit.
+struct GroupFront {
+    ScopeSlice sl;
+    std::vector<group::GroupIn> gin;
+    int32_t n_used = 0, only = -1;      // n_used <= 1: nothing below is set -- no group, or the masked call of group `only`
+    group::Plan plan;
+    GroupScopes gs;
+    MaskScope ms;                       // the scopes as a whole: what the stages ask of one (set with `screened`)
+    std::vector<int32_t> screened;      // ascending: the queries of the grouped pass (empty: it does not run)
+};
+
+int grouped_front(orr_index *idx, const BatchArgs &call, const GroupArgs &ga, const std::vector<std::vector<int32_t>> &members,
+                  const int64_t *took, GroupFront &f)
+{
+    const int32_t B = call.B, G = ga.n_groups;
+    const bool use_cos = call.dim > 0 && call.dim == idx->dim;
+    hipStream_t s = idx->stream;
+    // ---- resolve: the groups as G pseudo-queries of a scoped slice -> G bitmaps, live and took per group; handles bring theirs
+    const std::vector<int64_t> limit((size_t)G, std::max<int64_t>(1, call.candidate_limit));
+    const ScopeArgs sc{ga.n_ids, ga.ids, ga.off, nullptr};
+    ScopeSlice &sl = f.sl;
+    std::vector<group::GroupIn> &gin = f.gin;
+    gin.assign((size_t)G, group::GroupIn{});
+    if (ga.scopes) {
+        sl.words = ga.scopes[0]->words;
+        for (int32_t g = 0; g < G; ++g) gin[(size_t)g].took = took[g];
+    } else {
+        ORR_TRY(ensure_scope_table(idx));
+        ORR_TRY(build_scope_slice(idx, sc, limit, 0, G, sl));
+        for (int32_t g = 0; g < G; ++g) gin[(size_t)g].took = sl.took[g];
+    }
+    for (int32_t g = 0; g < G; ++g) gin[(size_t)g].queries = (int32_t)members[(size_t)g].size();
+    f.n_used = 0; f.only = -1;
+    for (int32_t g = 0; g < G; ++g)
+        if (group::used(gin[(size_t)g])) { f.n_used += 1; f.only = g; }
+    if (f.n_used <= 1) return ORR_OK;
+    // ---- the bitmaps are kept beside the slice's (which a group's own masked call rewrites); clip per used group
+    GroupScopes &gs = f.gs;
+    gs.n_groups = G; gs.words = sl.words;
+    const int32_t n_chunks = orr::scope_chunks(sl.words);
+    const size_t bm_bytes = sizeof(uint32_t) * (size_t)G * (size_t)sl.words, ch_bytes = sizeof(uint32_t) * (size_t)G * (size_t)n_chunks;
+    ORR_TRY(idx->ws_group_bm.reserve(bm_bytes));
+    ORR_TRY(idx->ws_group_chunks.reserve(ch_bytes));
+    ORR_TRY(idx->pin_group.reserve(sizeof(int64_t) * 2 * (size_t)G + sizeof(uint32_t) * (size_t)B));      // [clip x G][sample x G][screened x B]
+    ORR_TRY(idx->ws_group_meta.reserve(sizeof(int64_t) * 2 * (size_t)G));
+    gs.bm = idx->ws_group_bm.as<uint32_t>(); gs.chunks = idx->ws_group_chunks.as<uint32_t>();
+    int64_t *h_meta = idx->pin_group.as<int64_t>();            // [clip x G][sample x G]
+    for (int32_t g = 0; g < 2 * G; ++g) h_meta[g] = 0;
+    bool clipped = false;
+    if (ga.scopes) {
+        // the used handles' arrays, gathered (the grouped stages want them contiguous; an unused group's are never read), and the
+        // clip of every handle not all of whose rows take part: one launch
+        orr::GroupGatherTable tab{};
+        int32_t n_entries = 0;
+        for (int32_t g = 0; g < G; ++g) {
+            if (!group::used(gin[(size_t)g])) continue;
+            if (ga.scopes[g]->words != sl.words) return fail(ORR_ESTATE, "grouped search: the scopes cover different numbers of rows");
+            const bool clip = gin[(size_t)g].took < ga.scopes[g]->live.load();
+            tab.bm[n_entries] = ga.scopes[g]->bm; tab.chunks[n_entries] = ga.scopes[g]->chunks;
+            tab.clip_took[n_entries] = clip ? (uint32_t)gin[(size_t)g].took : 0u;
+            tab.slot[n_entries] = g;
+            n_entries += 1;
+            clipped = clipped || clip;
+        }
+        {
+            Timed t(idx, "group_gather_clip", 2.0 * 4.0 * ((double)sl.words + (double)n_chunks) * (double)n_entries);
+            HIP_TRY(orr::launch_group_gather_clip(tab, n_entries, G, sl.words, idx->ws_group_bm.as<uint32_t>(), idx->ws_group_chunks.as<uint32_t>(),
+                                                  h_meta, s));
+        }
+    } else {
+        HIP_TRY(hipMemcpyAsync(idx->ws_group_bm.p, idx->ws_scope_bm.p, bm_bytes, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(idx->ws_group_chunks.p, idx->ws_scope_chunks.p, ch_bytes, hipMemcpyDeviceToDevice, s));
+        for (int32_t g = 0; g < G; ++g) {
+            if (!group::used(gin[(size_t)g])) continue;
+            Timed t(idx, "mask_clip", 4.0 * (double)orr::kScopeChunkWords + 4.0 * (double)n_chunks);
+            HIP_TRY(orr::launch_mask_clip(gs.bm + (size_t)g * (size_t)sl.words, sl.words, gs.chunks + (size_t)g * (size_t)n_chunks,
+                                          (uint32_t)gin[(size_t)g].took, h_meta + g, s));
+            clipped = true;
+        }
+    }
+    if (clipped || !ga.scopes) {
+        HIP_TRY(hipStreamSynchronize(s));
+        collect_events(idx);
+    }
+    for (int32_t g = 0; g < G; ++g) {
+        if (ga.scopes && group::used(gin[(size_t)g]) && gin[(size_t)g].took == ga.scopes[g]->live.load()) h_meta[g] = ga.scopes[g]->n_clip_all;
+        gin[(size_t)g].n_clip = std::min<int64_t>(h_meta[g], idx->n_rows);
+    }
+    // ---- the plan: samples, screen and list groups, the grouped pass or a masked call per group
+    const uint32_t cap = group::pass_cap(idx->survivor_cap, B);
+    f.plan = group::plan(gin, call.topk, cap, idx->opt_mask_screen, use_cos, idx->dim, orr::kSelWidth, idx->opt_two_stage);
+    const group::Plan &plan = f.plan;
+    f.screened.clear();
+    for (int32_t g = 0; g < G; ++g)
+        if (plan.grouped && plan.role[(size_t)g] == group::Role::Screen) f.screened.insert(f.screened.end(), members[(size_t)g].begin(), members[(size_t)g].end());
+    return ORR_OK;
+}
+
+// What the grouped pass over f.screened reads, on the device (after the groups' own calls: they use the lane).
+int grouped_front_upload(orr_index *idx, const BatchArgs &call, GroupFront &f)
+{
+    const int32_t G = f.gs.n_groups;
+    const group::Plan &plan = f.plan;
+    GroupScopes &gs = f.gs;
+    hipStream_t s = idx->stream;
+    int64_t *h_meta = idx->pin_group.as<int64_t>();
+    std::sort(f.screened.begin(), f.screened.end());
+    gs.took.resize((size_t)G); gs.n_clip.resize((size_t)G); gs.sample = plan.sample;
+    for (int32_t g = 0; g < G; ++g) {
+        gs.took[(size_t)g] = f.gin[(size_t)g].took;
+        gs.n_clip[(size_t)g] = f.gin[(size_t)g].n_clip;
+        h_meta[g] = group::screen_clip(plan.role[(size_t)g] == group::Role::Screen, f.gin[(size_t)g].n_clip);
+        h_meta[G + g] = plan.sample[(size_t)g];
+    }
+    HIP_TRY(hipMemcpyAsync(idx->ws_group_meta.p, h_meta, sizeof(int64_t) * 2 * (size_t)G, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));                      // (pin_group is the next grouped call's on this lane)
+    gs.d_clip = idx->ws_group_meta.as<int64_t>(); gs.d_sample = gs.d_clip + G;
+    gs.floor_heads = group::floor_from_heads(plan.min_sample, call.topk, orr::kSelWidth);
+    gs.h_screened = reinterpret_cast<uint32_t *>(h_meta + 2 * G);
+    f.ms = MaskScope{};
+    f.ms.words = f.sl.words; f.ms.took = plan.min_took; f.ms.live = plan.min_took;
+    f.ms.n_clip = plan.n_clip; f.ms.sample = plan.max_sample;
+    return ORR_OK;
+}
+
 // orr_search_batch_masked_groups on the lane the caller holds.
 int grouped_batch(orr_index *idx, const BatchArgs &call, const GroupArgs &ga, int64_t *out_rows, double *out_scores, int32_t *out_counts)
 {
     const int32_t B = call.B, take = std::max<int32_t>(1, call.topk), G = ga.n_groups;
-    const bool use_cos = call.dim > 0 && call.dim == idx->dim;
     for (size_t i = 0; i < (size_t)B * take; ++i) { out_rows[i] = -1; out_scores[i] = 0.0; }
     if (out_counts) for (int32_t b = 0; b < B; ++b) out_counts[b] = 0;
     if (idx->n_rows <= 0 || (!ga.scopes && ga.n_ids == 0)) return ORR_OK;
@@ -4833,76 +4966,14 @@ int grouped_batch(orr_index *idx, const BatchArgs &call, const GroupArgs &ga, in
         orig.q = q_down.data();
     }
     if (named == 1) return masked_sub_batch(idx, orig, ga, only, members[(size_t)only], out_rows, out_scores, out_counts);
-    hipStream_t s = idx->stream;
-    // ---- resolve: the groups as G pseudo-queries of a scoped slice -> G bitmaps, live and took per group; handles bring theirs
-    const std::vector<int64_t> limit((size_t)G, std::max<int64_t>(1, call.candidate_limit));
-    const ScopeArgs sc{ga.n_ids, ga.ids, ga.off, nullptr};
-    ScopeSlice sl;
-    std::vector<group::GroupIn> gin((size_t)G);
-    if (ga.scopes) {
-        sl.words = ga.scopes[0]->words;
-        for (int32_t g = 0; g < G; ++g) gin[(size_t)g].took = std::min<int64_t>(ga.scopes[g]->live.load(), limit[(size_t)g]);
-    } else {
-        ORR_TRY(ensure_scope_table(idx));
-        ORR_TRY(build_scope_slice(idx, sc, limit, 0, G, sl));
-        for (int32_t g = 0; g < G; ++g) gin[(size_t)g].took = sl.took[g];
-    }
-    for (int32_t g = 0; g < G; ++g) gin[(size_t)g].queries = (int32_t)members[(size_t)g].size();
-    int32_t n_used = 0;
-    for (int32_t g = 0; g < G; ++g)
-        if (group::used(gin[(size_t)g])) { n_used += 1; only = g; }
-    if (n_used == 0) return ORR_OK;
-    if (n_used == 1) return masked_sub_batch(idx, orig, ga, only, members[(size_t)only], out_rows, out_scores, out_counts);
-    // ---- the bitmaps are kept beside the slice's (which a group's own masked call rewrites); clip per used group
-    GroupScopes gs;
-    gs.n_groups = G; gs.words = sl.words;
-    const int32_t n_chunks = orr::scope_chunks(sl.words);
-    const size_t bm_bytes = sizeof(uint32_t) * (size_t)G * (size_t)sl.words, ch_bytes = sizeof(uint32_t) * (size_t)G * (size_t)n_chunks;
-    ORR_TRY(idx->ws_group_bm.reserve(bm_bytes));
-    ORR_TRY(idx->ws_group_chunks.reserve(ch_bytes));
-    ORR_TRY(idx->pin_group.reserve(sizeof(int64_t) * 2 * (size_t)G + sizeof(uint32_t) * (size_t)B));      // [clip x G][sample x G][screened x B]
-    ORR_TRY(idx->ws_group_meta.reserve(sizeof(int64_t) * 2 * (size_t)G));
-    if (ga.scopes) {       // the used handles' arrays, gathered: the grouped stages want them contiguous (an unused group's are never read)
-        for (int32_t g = 0; g < G; ++g) {
-            if (!group::used(gin[(size_t)g])) continue;
-            HIP_TRY(hipMemcpyAsync(idx->ws_group_bm.as<uint32_t>() + (size_t)g * (size_t)sl.words, ga.scopes[g]->bm, sizeof(uint32_t) * (size_t)sl.words,
-                                   hipMemcpyDeviceToDevice, s));
-            HIP_TRY(hipMemcpyAsync(idx->ws_group_chunks.as<uint32_t>() + (size_t)g * (size_t)n_chunks, ga.scopes[g]->chunks,
-                                   sizeof(uint32_t) * (size_t)n_chunks, hipMemcpyDeviceToDevice, s));
-        }
-    } else {
-        HIP_TRY(hipMemcpyAsync(idx->ws_group_bm.p, idx->ws_scope_bm.p, bm_bytes, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(idx->ws_group_chunks.p, idx->ws_scope_chunks.p, ch_bytes, hipMemcpyDeviceToDevice, s));
-    }
-    gs.bm = idx->ws_group_bm.as<uint32_t>(); gs.chunks = idx->ws_group_chunks.as<uint32_t>();
-    int64_t *h_meta = idx->pin_group.as<int64_t>();            // [clip x G][sample x G]
-    for (int32_t g = 0; g < 2 * G; ++g) h_meta[g] = 0;
-    bool clipped = false;
-    for (int32_t g = 0; g < G; ++g) {
-        if (!group::used(gin[(size_t)g])) continue;
-        if (ga.scopes && gin[(size_t)g].took == ga.scopes[g]->live.load()) continue;      // every row of the handle: its n_clip_all, below
-        Timed t(idx, "mask_clip", 4.0 * (double)orr::kScopeChunkWords + 4.0 * (double)n_chunks);
-        HIP_TRY(orr::launch_mask_clip(gs.bm + (size_t)g * (size_t)sl.words, sl.words, gs.chunks + (size_t)g * (size_t)n_chunks,
-                                      (uint32_t)gin[(size_t)g].took, h_meta + g, s));
-        clipped = true;
-    }
-    if (clipped || !ga.scopes) {
-        HIP_TRY(hipStreamSynchronize(s));
-        collect_events(idx);
-    }
-    for (int32_t g = 0; g < G; ++g) {
-        if (ga.scopes && group::used(gin[(size_t)g]) && gin[(size_t)g].took == ga.scopes[g]->live.load()) h_meta[g] = ga.scopes[g]->n_clip_all;
-        gin[(size_t)g].n_clip = std::min<int64_t>(h_meta[g], idx->n_rows);
-    }
-    // ---- the plan: samples, screen and list groups, the grouped pass or a masked call per group
-    const uint32_t cap = group::pass_cap(idx->survivor_cap, B);
-    const group::Plan plan = group::plan(gin, call.topk, cap, idx->opt_mask_screen, use_cos, idx->dim, orr::kSelWidth, idx->opt_two_stage);
-    std::vector<int32_t> screened;
-    for (int32_t g = 0; g < G; ++g) {
-        const group::Role role = plan.role[(size_t)g];
-        if (role == group::Role::Unused) continue;
-        if (plan.grouped && role == group::Role::Screen) screened.insert(screened.end(), members[(size_t)g].begin(), members[(size_t)g].end());
-    }
+    std::vector<int64_t> took;
+    if (ga.scopes)
+        for (int32_t g = 0; g < G; ++g) took.push_back(group::took_of(ga.scopes[g]->live.load(), call.candidate_limit));
+    GroupFront f;
+    ORR_TRY(grouped_front(idx, call, ga, members, took.data(), f));
+    if (f.n_used == 0) return ORR_OK;
+    if (f.n_used == 1) return masked_sub_batch(idx, orig, ga, f.only, members[(size_t)f.only], out_rows, out_scores, out_counts);
+    const group::Plan &plan = f.plan;
     // ---- list groups, and every used group where the grouped pass does not run: a masked call of their own (first: pass_mode
     // tells what ran last)
     for (int32_t g = 0; g < G; ++g) {
@@ -4911,26 +4982,12 @@ int grouped_batch(orr_index *idx, const BatchArgs &call, const GroupArgs &ga, in
         ORR_TRY(masked_sub_batch(idx, orig, ga, g, members[(size_t)g], out_rows, out_scores, out_counts));
     }
     // ---- the grouped pass over the screen groups' queries, in slices
-    if (!screened.empty()) {
-        std::sort(screened.begin(), screened.end());
-        gs.took.resize((size_t)G); gs.n_clip.resize((size_t)G); gs.sample = plan.sample;
-        for (int32_t g = 0; g < G; ++g) {
-            gs.took[(size_t)g] = gin[(size_t)g].took;
-            gs.n_clip[(size_t)g] = gin[(size_t)g].n_clip;
-            h_meta[g] = group::screen_clip(plan.role[(size_t)g] == group::Role::Screen, gin[(size_t)g].n_clip);
-            h_meta[G + g] = plan.sample[(size_t)g];
-        }
-        HIP_TRY(hipMemcpyAsync(idx->ws_group_meta.p, h_meta, sizeof(int64_t) * 2 * (size_t)G, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s));                      // (pin_group is the next grouped call's on this lane)
-        gs.d_clip = idx->ws_group_meta.as<int64_t>(); gs.d_sample = gs.d_clip + G;
-        gs.floor_heads = group::floor_from_heads(plan.min_sample, call.topk, orr::kSelWidth);
-        gs.h_screened = reinterpret_cast<uint32_t *>(h_meta + 2 * G);
-        MaskScope ms;                                          // the scopes as a whole: what the stages ask of one
-        ms.words = sl.words; ms.took = plan.min_took; ms.live = plan.min_took;
-        ms.n_clip = plan.n_clip; ms.sample = plan.max_sample;
+    if (!f.screened.empty()) {
+        ORR_TRY(grouped_front_upload(idx, call, f));
+        const std::vector<int32_t> &screened = f.screened;
         const int32_t per = group::screen_slice((int32_t)screened.size(), plan.max_sample);
         for (size_t b0 = 0; b0 < screened.size(); b0 += (size_t)per)
-            ORR_TRY(grouped_screen_ladder(idx, orig, ga, gs, ms,
+            ORR_TRY(grouped_screen_ladder(idx, orig, ga, f.gs, f.ms,
                                           std::vector<int32_t>(screened.begin() + b0, screened.begin() + std::min(screened.size(), b0 + (size_t)per)),
                                           out_rows, out_scores, out_counts));
     }
@@ -5154,6 +5211,142 @@ int masked_shard(orr_index *idx, const BatchArgs &orig, const ScopeSource &src, 
     const int32_t per = mask::screen_slice(B, ms.sample);
     for (int32_t b0 = 0; b0 < B; b0 += per)
         ORR_TRY(masked_shard_screen(idx, orig, sl, ms, std::vector<int32_t>(ids.begin() + b0, ids.begin() + std::min<int32_t>(B, b0 + per)), kprime, out));
+    return ORR_OK;
+}
+
+// ---- orr_search_shard_in_scopes: the record form of the grouped search over handles, one pass at the caller's k' ------------
+
+// The queries `ids` of the call (ascending, all of group g) through the masked shard form of their group, the records
+// scattered into out.
+int grouped_shard_own(orr_index *idx, const BatchArgs &orig, const GroupArgs &ga, int32_t g, const std::vector<int32_t> &ids,
+                      int64_t scope_before, int32_t kprime, int32_t pass, orr_candidate *out)
+{
+    if (ids.empty()) return ORR_OK;
+    const size_t rec_q = (size_t)kprime + 1;
+    const ScopeSource src{nullptr, ga.scopes[g]};
+    SubBatch sb;
+    BatchArgs cur;
+    ORR_TRY(build_subset(idx, orig, ids, sb, cur));
+    if (cur.B == orig.B) return masked_shard(idx, cur, src, scope_before, kprime, pass, out);       // every query of the call
+    std::vector<orr_candidate> recs(ids.size() * rec_q);
+    ORR_TRY(masked_shard(idx, cur, src, scope_before, kprime, pass, recs.data()));
+    for (size_t i = 0; i < ids.size(); ++i)
+        HIP_TRY(hipMemcpy(out + (size_t)ids[i] * rec_q, recs.data() + i * rec_q, sizeof(orr_candidate) * rec_q, hipMemcpyDefault));
+    return ORR_OK;
+}
+
+// `ids` (ascending) split by group, each part through its group's own masked shard form.
+int grouped_shard_owns(orr_index *idx, const BatchArgs &orig, const GroupArgs &ga, const std::vector<int32_t> &ids, const int64_t *scope_before,
+                       int32_t kprime, int32_t pass, orr_candidate *out)
+{
+    std::vector<std::vector<int32_t>> by_group((size_t)ga.n_groups);
+    for (int32_t b : ids) by_group[(size_t)ga.query_group[b]].push_back(b);
+    for (int32_t g = 0; g < ga.n_groups; ++g)
+        ORR_TRY(grouped_shard_own(idx, orig, ga, g, by_group[(size_t)g], scope_before[g], kprime, pass, out));
+    return ORR_OK;
+}
+
+// The queries `ids` of the call (ascending, all of screen groups) through ONE grouped screen at k'; the queries whose survivors'
+// buffers overflowed repeat once, inside the call, with buffers of the call's own (group::next_step).  A pass plan_form finds
+// no two-stage form for goes through the groups' own shard forms.
+int grouped_shard_screen(orr_index *idx, const BatchArgs &orig, const GroupArgs &ga, GroupScopes &gs, const MaskScope &ms,
+                         const std::vector<int32_t> &ids, const int64_t *scope_before, int32_t kprime, orr_candidate *out, bool *ran)
+{
+    const size_t rec_q = (size_t)kprime + 1;
+    std::vector<int32_t> active = ids;
+    gs.cap = 0;
+    for (int round = 0; round < group::kMaxGroupedPasses; ++round) {
+        const size_t nb = active.size();
+        SubBatch sb;
+        BatchArgs cur;
+        ORR_TRY(build_subset(idx, orig, active, sb, cur));
+        gs.qgroup.resize(nb);
+        for (size_t i = 0; i < nb; ++i) gs.qgroup[i] = ga.query_group[active[i]];
+        PassPlan pass;
+        const float *q_host = nullptr;
+        const orr_candidate *recs = nullptr;
+        const int rc = retry_pass(idx, [&] { return run_masked_pass(idx, cur, kprime, ms, &q_host, &recs, pass, &gs); });
+        if (rc == kNotMaskable) { gs.cap = 0; return grouped_shard_owns(idx, orig, ga, active, scope_before, kprime, 0, out); }
+        if (rc != ORR_OK) { gs.cap = 0; return rc; }
+        *ran = true;
+        for (size_t i = 0; i < nb; ++i)
+            HIP_TRY(hipMemcpy(out + (size_t)active[i] * rec_q, recs + i * rec_q, sizeof(orr_candidate) * rec_q, hipMemcpyDefault));
+        const ShardOutcome o = outcome_of(idx, pass, ms.n_clip);       // (survivor_cap: the lane's, which the call's own growth leaves alone)
+        idx->sstats.passes += 1;
+        if (round > 0) idx->sstats.requeried += (int64_t)nb;
+        escalation::account_survivors(idx->sstats, o, nb);
+        if (round + 1 >= group::kMaxGroupedPasses || !o.kept(nb)) break;
+        std::vector<int32_t> over;
+        uint32_t worst = 0;
+        for (size_t i = 0; i < nb; ++i)
+            if (o.overflowed(i)) { over.push_back(active[i]); worst = std::max(worst, o.survivors[i]); }
+        if (over.empty()) break;
+        const group::Next nx = group::next_step(true, false, o.pass_cap, worst, ms.n_clip, over.size());
+        if (nx.step != group::Step::GrowBuffers) break;                // the caller's escalation
+        idx->sstats.buffer_growths += 1;       // the call's own: neither the lane nor the handle keeps the size
+        gs.cap = nx.new_cap;
+        active.swap(over);
+    }
+    gs.cap = 0;
+    return ORR_OK;
+}
+
+// orr_search_shard_in_scopes on the lane the caller holds, the scopes held shared by the caller: one pass at the caller's k', no
+// ladder (the caller's merge certifies).  orig.topk: the k the floors' samples serve.  *ran_grouped: a grouped screen ran.
+int grouped_shard(orr_index *idx, const BatchArgs &call, const GroupArgs &ga, const int64_t *scope_before, int32_t kprime, int32_t pass,
+                  orr_candidate *out, bool *ran_grouped)
+{
+    const int32_t B = call.B, G = ga.n_groups;
+    const size_t rec_q = (size_t)kprime + 1;
+    bool ran_here = false;
+    bool *ran = ran_grouped ? ran_grouped : &ran_here;
+    *ran = false;
+    ORR_TRY(bind_device(idx));
+    std::vector<std::vector<int32_t>> members((size_t)G);
+    for (int32_t b = 0; b < B; ++b) members[(size_t)ga.query_group[b]].push_back(b);
+    std::vector<int64_t> took((size_t)G, 0);
+    int32_t n_used = 0, only = -1;
+    for (int32_t g = 0; g < G; ++g) {
+        took[(size_t)g] = idx->n_rows <= 0 ? 0 : cscope::shard_took(ga.scopes[g]->live.load(), call.candidate_limit, scope_before[g]);
+        if (!members[(size_t)g].empty() && took[(size_t)g] > 0) { n_used += 1; only = g; }
+    }
+    // one used group that every query names: the in-scope shard form itself, nothing new runs
+    if (n_used == 1 && (int32_t)members[(size_t)only].size() == B) return masked_shard(idx, call, ScopeSource{nullptr, ga.scopes[only]}, scope_before[only], kprime, pass, out);
+    // a query whose scope takes no row here: an empty record and trailer (the others are written over below)
+    HIP_TRY(hipMemcpy(out, empty_records(B, kprime).data(), sizeof(orr_candidate) * (size_t)B * rec_q, hipMemcpyDefault));
+    if (n_used == 0) return ORR_OK;
+    // (sub-batches are gathered on the host, and gathered again by the passes they take: device-resident vectors come down once)
+    BatchArgs orig = call;
+    std::vector<float> q_down;
+    if (call.dim > 0 && is_device_pointer(call.q)) {
+        q_down.resize((size_t)B * (size_t)call.dim);
+        HIP_TRY(hipMemcpy(q_down.data(), call.q, sizeof(float) * q_down.size(), hipMemcpyDeviceToHost));
+        orig.q = q_down.data();
+    }
+    auto own = [&](int32_t g) { return grouped_shard_own(idx, orig, ga, g, members[(size_t)g], scope_before[g], kprime, pass, out); };
+    if (n_used == 1) return own(only);
+    if (pass != 0 || kprime > orr::kSelWidth) {         // the list path: per group
+        for (int32_t g = 0; g < G; ++g)
+            if (!members[(size_t)g].empty() && took[(size_t)g] > 0) ORR_TRY(own(g));
+        return ORR_OK;
+    }
+    GroupFront f;
+    ORR_TRY(grouped_front(idx, orig, ga, members, took.data(), f));
+    const group::Plan &plan = f.plan;
+    for (int32_t g = 0; g < G; ++g) {
+        const group::Role role = plan.role[(size_t)g];
+        if (role == group::Role::Unused || (plan.grouped && role == group::Role::Screen)) continue;
+        ORR_TRY(own(g));
+    }
+    if (!f.screened.empty()) {
+        ORR_TRY(grouped_front_upload(idx, orig, f));
+        const std::vector<int32_t> &screened = f.screened;
+        const int32_t per = group::screen_slice((int32_t)screened.size(), plan.max_sample);
+        for (size_t b0 = 0; b0 < screened.size(); b0 += (size_t)per)
+            ORR_TRY(grouped_shard_screen(idx, orig, ga, f.gs, f.ms,
+                                         std::vector<int32_t>(screened.begin() + b0, screened.begin() + std::min(screened.size(), b0 + (size_t)per)),
+                                         scope_before, kprime, out, ran));
+    }
     return ORR_OK;
 }
 
@@ -5850,6 +6043,52 @@ int orr_search_shard_in_scope(orr_index *idx, int32_t B, int32_t dim, const floa
     return masked_shard(idx, a, ScopeSource{nullptr, scope}, scope_before, kprime, pass, out);
 }
 
+int orr_search_shard_in_scopes(orr_index *idx, int32_t B, int32_t dim, const float *q, const uint8_t *terms_utf8,
+                               const uint32_t *term_off, const uint32_t *query_term_off, int64_t now_ticks, int32_t kprime,
+                               int64_t candidate_limit, int32_t topk, int32_t pass, int32_t n_scopes, const orr_scope *const *scopes,
+                               const int32_t *query_scope, const int64_t *scope_before, orr_candidate *out)
+{
+    static const char *fn = "orr_search_shard_in_scopes";
+    BatchArgs a{B, dim, q, terms_utf8, term_off, query_term_off, now_ticks, candidate_limit, kprime};
+    if (!scope_set::scopes_valid(n_scopes)) return fail(ORR_EINVAL, "%s: n_scopes must be in 1 .. %d", fn, scope_set::kMaxScopes);
+    if (!scopes) return fail(ORR_EINVAL, "%s: scopes is NULL", fn);
+    for (int32_t g = 0; g < n_scopes; ++g)
+        if (!scopes[g]) return fail(ORR_EINVAL, "%s: scopes[%d] is a null scope", fn, g);
+    if (!query_scope) return fail(ORR_EINVAL, "%s: query_scope is NULL", fn);
+    if (B > 0 && !group::assignment_valid(query_scope, B, n_scopes))
+        return fail(ORR_EINVAL, "%s: query_scope must name a scope in 0 .. %d for every query", fn, n_scopes - 1);
+    if (!scope_before) return fail(ORR_EINVAL, "%s: scope_before is NULL", fn);
+    for (int32_t g = 0; g < n_scopes; ++g)
+        if (scope_before[g] < 0) return fail(ORR_EINVAL, "%s: scope_before[%d] is negative", fn, g);
+    if (kprime < 1) return fail(ORR_EINVAL, "%s: kprime must be >= 1", fn);
+    if (topk < 0) return fail(ORR_EINVAL, "%s: topk must be >= 0", fn);
+    if (pass < 0 || pass > 1) return fail(ORR_EINVAL, "%s: pass takes 0 (the library's choice) or 1 (the list path)", fn);
+    if (!out) return fail(ORR_EINVAL, "%s: out is NULL", fn);
+    ORR_TRY(check_batch(idx, a, fn));
+    if (topk > 0) a.topk = std::min<int32_t>(kprime, topk);
+    orr_index *own = nullptr;
+    for (int32_t g = 0; g < n_scopes; ++g) ORR_TRY(scope_owner(scopes[g], idx, fn, &own));
+    Lane ln = acquire_lane(idx);
+    idx = ln.lane;
+    std::lock_guard<std::mutex> lock(idx->mu);
+    // every distinct scope shared, in address order
+    std::vector<const orr_scope *> distinct(scopes, scopes + n_scopes);
+    std::sort(distinct.begin(), distinct.end(), std::less<const orr_scope *>());
+    distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+    std::vector<std::shared_lock<std::shared_mutex>> held;
+    held.reserve(distinct.size());
+    for (const orr_scope *sc : distinct) held.emplace_back(sc->mu);
+    for (const orr_scope *sc : distinct) {
+        ORR_TRY(scope_owner(sc, idx, fn, &own));
+        if (sc->n_rows != idx->n_rows) return fail(ORR_ESTATE, "%s: a scope covers %lld rows, the handle %lld", fn, (long long)sc->n_rows, (long long)idx->n_rows);
+    }
+    GroupArgs ga{n_scopes, 0, nullptr, nullptr, query_scope};
+    ga.scopes = scopes;
+    idx->sstats.searches += 1;
+    idx->sstats.queries += B;
+    return grouped_shard(idx, a, ga, scope_before, kprime, pass, out, nullptr);
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -6161,26 +6400,48 @@ int cluster_scope_owner(const orr_cluster_scope *s, const char *fn, orr_cluster 
     return ORR_OK;
 }
 
-int cluster_scope_search(orr_cluster *c, const char *fn, const BatchArgs &orig, const ClusterScope &cs, int64_t *out_rows, double *out_scores,
-                         int32_t *out_counts)
+// What every cluster scope call does first: the outputs empty, the call counted.
+void cluster_scope_begin(orr_cluster *c, const BatchArgs &orig, int64_t *out_rows, double *out_scores, int32_t *out_counts)
 {
-    const int32_t G = (int32_t)c->shards.size(), B = orig.B, take = std::max<int32_t>(1, orig.topk);
-    const bool use_cos = orig.dim > 0 && orig.dim == c->dim;
+    const int32_t B = orig.B, take = std::max<int32_t>(1, orig.topk);
     for (size_t i = 0; i < (size_t)B * take; ++i) { out_rows[i] = -1; out_scores[i] = 0.0; }
     if (out_counts) for (int32_t b = 0; b < B; ++b) out_counts[b] = 0;
-    {
-        std::lock_guard<std::mutex> l(c->stats_mu);
-        c->sstats.searches += 1;
-        c->sstats.queries += B;
-    }
-    if (!cs.handle && cs.n_ids == 0) return ORR_OK;
-    // all lanes before any shard starts, in ascending shard order (acquire_in_order says why), kept for the call
-    std::vector<Lane> lanes;
+    std::lock_guard<std::mutex> l(c->stats_mu);
+    c->sstats.searches += 1;
+    c->sstats.queries += B;
+}
+
+// All lanes before any shard starts, in ascending shard order (acquire_in_order says why), kept for the call.
+void cluster_scope_lanes(orr_cluster *c, std::vector<Lane> &lanes)
+{
     std::vector<LanePool *> pools;
     std::vector<LanePool::Make> makes;
     for (orr_index *sh : c->shards) { pools.push_back(&sh->lanes); makes.push_back(lane_maker(sh)); }
     acquire_in_order(pools, makes, lanes);
-    for (int32_t g = 0; g < G; ++g) adopt_survivor_hint(c->shards[(size_t)g], lanes[(size_t)g].lane);
+    for (size_t g = 0; g < c->shards.size(); ++g) adopt_survivor_hint(c->shards[g], lanes[g].lane);
+}
+
+int cluster_scope_on_lanes(orr_cluster *c, const char *fn, const BatchArgs &orig, const ClusterScope &cs, std::vector<Lane> &lanes,
+                           bool handle_held, bool requery, int64_t *out_rows, double *out_scores, int32_t *out_counts);
+
+int cluster_scope_search(orr_cluster *c, const char *fn, const BatchArgs &orig, const ClusterScope &cs, int64_t *out_rows, double *out_scores,
+                         int32_t *out_counts)
+{
+    cluster_scope_begin(c, orig, out_rows, out_scores, out_counts);
+    if (!cs.handle && cs.n_ids == 0) return ORR_OK;
+    std::vector<Lane> lanes;
+    cluster_scope_lanes(c, lanes);
+    return cluster_scope_on_lanes(c, fn, orig, cs, lanes, false, false, out_rows, out_scores, out_counts);
+}
+
+// The search on the lanes the caller took.  handle_held: the caller holds the handle's parts shared already (a grouped call,
+// which holds several); requery: the queries come from a pass that left them uncertified, and count as requeried from the
+// first rung on.  The outputs are the caller's, emptied.
+int cluster_scope_on_lanes(orr_cluster *c, const char *fn, const BatchArgs &orig, const ClusterScope &cs, std::vector<Lane> &lanes,
+                           bool handle_held, bool requery, int64_t *out_rows, double *out_scores, int32_t *out_counts)
+{
+    const int32_t G = (int32_t)c->shards.size(), B = orig.B, take = std::max<int32_t>(1, orig.topk);
+    const bool use_cos = orig.dim > 0 && orig.dim == c->dim;
     std::vector<double> norms;
     if (use_cos) {
         norms.resize((size_t)B);
@@ -6198,7 +6459,7 @@ int cluster_scope_search(orr_cluster *c, const char *fn, const BatchArgs &orig, 
     std::vector<std::shared_lock<std::shared_mutex>> held;
     if (cs.handle) {
         held.reserve((size_t)G);
-        for (int32_t g = 0; g < G; ++g) held.emplace_back(cs.handle->parts[(size_t)g]->mu);
+        for (int32_t g = 0; g < G && !handle_held; ++g) held.emplace_back(cs.handle->parts[(size_t)g]->mu);
         for (int32_t g = 0; g < G; ++g) {
             const orr_scope *part = cs.handle->parts[(size_t)g];
             orr_index *own = nullptr;
@@ -6291,13 +6552,152 @@ int cluster_scope_search(orr_cluster *c, const char *fn, const BatchArgs &orig, 
             std::lock_guard<std::mutex> l(c->stats_mu);
             c->sstats.passes += 1;
             c->sstats.pass_mode = cs.masked && r.rung.pass == 0 ? 5 : 4;
-            if (r.repeats > 0) c->sstats.requeried += nb;
+            if (r.repeats > 0 || requery) c->sstats.requeried += nb;
         }
         if (next.ids.empty()) continue;
         next.rung = cscope::next_rung(r.rung, cs.masked, screened, largest, orr::kSelWidth);
         if (next.rung.done || next.repeats >= cscope::kMaxRungs)
             return fail(ORR_EDEVICE, "%s: a pass with every scoped row a record left a query uncertified", fn);
         todo.push_front(std::move(next));
+    }
+    return ORR_OK;
+}
+
+// ---- grouped search over the shards (orr_cluster_search_batch_in_scopes; the rules are orr_cluster_group_plan.h's) -----------
+// The queries `ids` of the call (ascending, all of one handle) through the in-scope cluster ladder of that handle, on the lanes
+// and holds the caller took, the results scattered back.
+int cluster_scope_sub(orr_cluster *c, const char *fn, const BatchArgs &orig, const orr_cluster_scope *handle, const std::vector<int32_t> &ids,
+                      std::vector<Lane> &lanes, bool requery, int64_t *out_rows, double *out_scores, int32_t *out_counts)
+{
+    if (ids.empty()) return ORR_OK;
+    const int32_t take = std::max<int32_t>(1, orig.topk);
+    ClusterScope cs{true, 0, nullptr, nullptr};
+    cs.handle = handle;
+    SubBatch sb;
+    BatchArgs cur;
+    ORR_TRY(build_subset(lanes[0].lane, orig, ids, sb, cur));          // (host-resident vectors: nothing of the lane is used)
+    if (cur.B == orig.B) return cluster_scope_on_lanes(c, fn, cur, cs, lanes, true, requery, out_rows, out_scores, out_counts);
+    const size_t nb = ids.size();
+    std::vector<int64_t> rows(nb * (size_t)take, -1);
+    std::vector<double> scores(nb * (size_t)take, 0.0);
+    std::vector<int32_t> counts(nb, 0);
+    ORR_TRY(cluster_scope_on_lanes(c, fn, cur, cs, lanes, true, requery, rows.data(), scores.data(), counts.data()));
+    for (size_t i = 0; i < nb; ++i) {
+        const size_t b = (size_t)ids[i];
+        memcpy(out_rows + b * take, rows.data() + i * take, sizeof(int64_t) * take);
+        memcpy(out_scores + b * take, scores.data() + i * take, sizeof(double) * take);
+        if (out_counts) out_counts[b] = counts[i];
+    }
+    return ORR_OK;
+}
+
+int cluster_grouped_search(orr_cluster *c, const char *fn, const BatchArgs &orig, int32_t n_scopes, const orr_cluster_scope *const *scopes,
+                           const int32_t *query_scope, int64_t *out_rows, double *out_scores, int32_t *out_counts)
+{
+    const int32_t G = (int32_t)c->shards.size(), B = orig.B, take = std::max<int32_t>(1, orig.topk);
+    const bool use_cos = orig.dim > 0 && orig.dim == c->dim;
+    cluster_scope_begin(c, orig, out_rows, out_scores, out_counts);
+    std::vector<Lane> lanes;
+    cluster_scope_lanes(c, lanes);
+    // ---- the groups: the distinct handles; their parts shared, in one total order, behind the lanes
+    std::vector<uintptr_t> addr((size_t)n_scopes);
+    for (int32_t i = 0; i < n_scopes; ++i) addr[(size_t)i] = reinterpret_cast<uintptr_t>(scopes[i]);
+    const cgroup::Distinct dis = cgroup::distinct(addr);
+    const int32_t D = (int32_t)dis.first.size();
+    std::vector<const orr_cluster_scope *> handle((size_t)D);
+    std::vector<std::vector<uintptr_t>> parts((size_t)D, std::vector<uintptr_t>((size_t)G));
+    for (int32_t d = 0; d < D; ++d) {
+        handle[(size_t)d] = scopes[dis.first[(size_t)d]];
+        for (int32_t g = 0; g < G; ++g) parts[(size_t)d][(size_t)g] = reinterpret_cast<uintptr_t>(handle[(size_t)d]->parts[(size_t)g]);
+    }
+    std::vector<std::shared_lock<std::shared_mutex>> held;
+    const std::vector<cgroup::Hold> order = cgroup::holds(parts);
+    held.reserve(order.size());
+    for (const cgroup::Hold &h : order) held.emplace_back(handle[(size_t)h.group]->parts[(size_t)h.shard]->mu);
+    std::vector<std::vector<int64_t>> live((size_t)D, std::vector<int64_t>((size_t)G, 0));
+    for (int32_t d = 0; d < D; ++d)
+        for (int32_t g = 0; g < G; ++g) {
+            const orr_scope *part = handle[(size_t)d]->parts[(size_t)g];
+            orr_index *own = nullptr;
+            ORR_TRY(scope_owner(part, c->shards[(size_t)g], fn, &own));
+            if (part->n_rows != lanes[(size_t)g].lane->n_rows)
+                return fail(ORR_ESTATE, "%s: a scope covers %lld rows of shard %d, the shard holds %lld", fn, (long long)part->n_rows, g, (long long)lanes[(size_t)g].lane->n_rows);
+            live[(size_t)d][(size_t)g] = part->live.load();
+        }
+    std::vector<cscope::Split> split;
+    if (!cgroup::splits(live, orig.candidate_limit, split)) return fail(ORR_ESTATE, "%s: a shard's scope is orphaned", fn);
+    std::vector<int32_t> qgroup((size_t)B);
+    for (int32_t b = 0; b < B; ++b) qgroup[(size_t)b] = dis.group_of[(size_t)query_scope[b]];
+    const cgroup::First first = cgroup::first(split, qgroup);
+    if (first.n_used == 0) return ORR_OK;
+    // one used group: the in-scope cluster call itself, nothing new runs
+    if (first.n_used == 1) return cluster_scope_sub(c, fn, orig, handle[(size_t)first.only], first.ids, lanes, false, out_rows, out_scores, out_counts);
+
+    // ---- the first rung: every shard runs its grouped shard form once
+    std::vector<double> norms;
+    if (use_cos) {
+        norms.resize((size_t)B);
+        exact_norms(orig.q, B, orig.dim, norms.data());
+    }
+    const cscope::Rung rung = cscope::first_rung(true, take, first.total, orr::kSelWidth);
+    const int32_t n_ids = (int32_t)first.ids.size(), kprime = (int32_t)std::min<int64_t>(rung.kprime, std::numeric_limits<int32_t>::max() - 1);
+    const size_t rec_q = (size_t)kprime + 1;
+    const int32_t per = cscope::merge_slice(n_ids, G, kprime, mask::kMergeBudgetBytes);
+    std::vector<std::vector<int32_t>> again((size_t)D);
+    bool any_grouped = false;
+    for (int32_t i0 = 0; i0 < n_ids; i0 += per) {
+        const std::vector<int32_t> ids(first.ids.begin() + i0, first.ids.begin() + std::min<int32_t>(n_ids, i0 + per));
+        const int32_t nb = (int32_t)ids.size();
+        SubBatch sb;
+        BatchArgs cur;
+        ORR_TRY(build_subset(lanes[0].lane, orig, ids, sb, cur));                      // (host-resident vectors: nothing of the lane is used)
+        std::vector<double> sub_norms((size_t)nb, 0.0);
+        std::vector<int32_t> sub_group((size_t)nb);
+        for (int32_t i = 0; i < nb; ++i) {
+            if (use_cos) sub_norms[(size_t)i] = norms[(size_t)ids[(size_t)i]];
+            sub_group[(size_t)i] = qgroup[(size_t)ids[(size_t)i]];
+        }
+        std::vector<orr_candidate> recs((size_t)G * (size_t)nb * rec_q);
+        std::vector<uint8_t> ran((size_t)G, 0);
+        ORR_TRY(for_each_shard(G, [&](int32_t g) -> int {
+            orr_index *sh = lanes[(size_t)g].lane;
+            std::lock_guard<std::mutex> lock(sh->mu);
+            BatchArgs a = cur;
+            a.topk = std::min<int32_t>(kprime, take);                                  // the floor's k: the global k-th best is at least every shard's
+            if (use_cos) a.norms_host = sub_norms.data();
+            std::vector<const orr_scope *> mine((size_t)D);
+            std::vector<int64_t> before((size_t)D);
+            for (int32_t d = 0; d < D; ++d) { mine[(size_t)d] = handle[(size_t)d]->parts[(size_t)g]; before[(size_t)d] = split[(size_t)d].before[(size_t)g]; }
+            GroupArgs ga{D, 0, nullptr, nullptr, sub_group.data()};
+            ga.scopes = mine.data();
+            sh->sstats.searches += 1; sh->sstats.queries += nb;
+            bool grouped = false;
+            const int rc = grouped_shard(sh, a, ga, before.data(), kprime, rung.pass, recs.data() + (size_t)g * (size_t)nb * rec_q, &grouped);
+            ran[(size_t)g] = grouped ? 1 : 0;
+            return rc;
+        }));
+        std::vector<uint8_t> cert;
+        ORR_TRY(merge_into(G, kprime, recs.data(), cur, use_cos, cur.q, use_cos ? sub_norms.data() : nullptr, ids, out_rows, out_scores, out_counts, cert));
+        cgroup::route(ids, cert, qgroup, again);
+        bool grouped = false;
+        for (int32_t g = 0; g < G; ++g) grouped = grouped || ran[(size_t)g] != 0;
+        any_grouped = any_grouped || grouped;
+        std::lock_guard<std::mutex> l(c->stats_mu);
+        c->sstats.passes += 1;
+        c->sstats.pass_mode = grouped ? 6 : rung.pass == 0 ? 5 : 4;
+    }
+    // ---- every uncertified query: its own group's ladder, with the group's others
+    for (int32_t d = 0; d < D; ++d) {
+        if (again[(size_t)d].empty()) continue;
+        for (int32_t b : again[(size_t)d]) {           // (the ladder's merge writes every slot of a query it certifies; start from empty)
+            for (int32_t t = 0; t < take; ++t) { out_rows[(size_t)b * take + t] = -1; out_scores[(size_t)b * take + t] = 0.0; }
+            if (out_counts) out_counts[b] = 0;
+        }
+        ORR_TRY(cluster_scope_sub(c, fn, orig, handle[(size_t)d], again[(size_t)d], lanes, true, out_rows, out_scores, out_counts));
+    }
+    if (any_grouped) {                                 // (pass_mode tells that a grouped pass ran, whatever a group's own ladder ran after it)
+        std::lock_guard<std::mutex> l(c->stats_mu);
+        c->sstats.pass_mode = 6;
     }
     return ORR_OK;
 }
@@ -6816,6 +7216,37 @@ int orr_cluster_search_batch_in_scope(orr_cluster *c, int32_t B, int32_t dim, co
     ClusterScope cs{true, 0, nullptr, nullptr};
     cs.handle = scope;
     return cluster_scope_search(c, fn, a, cs, out_rows, out_scores, out_counts);
+}
+
+int orr_cluster_search_batch_in_scopes(orr_cluster *c, int32_t B, int32_t dim, const float *q_host, const uint8_t *terms_utf8,
+                                       const uint32_t *term_off, const uint32_t *query_term_off, int64_t now_ticks, int32_t topk,
+                                       int64_t candidate_limit, int32_t n_scopes, const orr_cluster_scope *const *scopes,
+                                       const int32_t *query_scope, int64_t *out_rows, double *out_scores, int32_t *out_counts)
+{
+    static const char *fn = "orr_cluster_search_batch_in_scopes";
+    const BatchArgs a{B, dim, q_host, terms_utf8, term_off, query_term_off, now_ticks, candidate_limit, topk};
+    if (!scope_set::scopes_valid(n_scopes)) return fail(ORR_EINVAL, "%s: n_scopes must be in 1 .. %d", fn, scope_set::kMaxScopes);
+    if (!scopes) return fail(ORR_EINVAL, "%s: scopes is NULL", fn);
+    for (int32_t g = 0; g < n_scopes; ++g)
+        if (!scopes[g]) return fail(ORR_EINVAL, "%s: scopes[%d] is a null scope", fn, g);
+    if (!query_scope) return fail(ORR_EINVAL, "%s: query_scope is NULL", fn);
+    if (B > 0 && !group::assignment_valid(query_scope, B, n_scopes))
+        return fail(ORR_EINVAL, "%s: query_scope must name a scope in 0 .. %d for every query", fn, n_scopes - 1);
+    if (B <= 0) return fail(ORR_EINVAL, "%s: batch size must be positive", fn);
+    if (dim < 0) return fail(ORR_EINVAL, "%s: negative query dimension", fn);
+    if (dim > 0 && !q_host) return fail(ORR_EINVAL, "%s: q is NULL with dim %d", fn, dim);
+    if (!query_term_off) return fail(ORR_EINVAL, "%s: query_term_off is required", fn);
+    if (!out_rows || !out_scores) return fail(ORR_EINVAL, "%s: output buffers are required", fn);
+    if (!c) return fail(ORR_EINVAL, "%s: null cluster", fn);
+    if (dim > 0 && is_device_pointer(q_host)) return fail(ORR_EINVAL, "%s: the query vectors must be in host memory (every shard's device reads them)", fn);
+    std::shared_lock<std::shared_mutex> lock(c->mu);   // searches run side by side; seal and destroy are exclusive
+    if (!c->sealed) return fail(ORR_ESTATE, "%s: the cluster is not sealed", fn);
+    for (int32_t g = 0; g < n_scopes; ++g) {
+        orr_cluster *own = nullptr;
+        ORR_TRY(cluster_scope_owner(scopes[g], fn, &own));
+        if (own != c || scopes[g]->parts.size() != c->shards.size()) return fail(ORR_EINVAL, "%s: scopes[%d] belongs to another cluster", fn, g);
+    }
+    return cluster_grouped_search(c, fn, a, n_scopes, scopes, query_scope, out_rows, out_scores, out_counts);
 }
 
 }  // extern "C"

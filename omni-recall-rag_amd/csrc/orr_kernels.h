@@ -436,6 +436,21 @@ hipError_t launch_scope_trailers(orr_candidate *recs, int32_t B, int32_t kprime,
 // *n_clip (may be pinned host memory) = one past the position of the took-th set bit of the bitmap (1 <= took <= its set
 // bits; chunk_cnt as launch_scope_counts left it).
 hipError_t launch_mask_clip(const uint32_t *bitmap, int64_t words, const uint32_t *chunk_cnt, uint32_t took, int64_t *n_clip, hipStream_t s);
+// The front of a grouped pass over scope handles in one launch.  Entry e of the table (e < n_entries <= kMaxGatherGroups): the
+// bitmap (`words` words, words % 4 == 0, 16-byte aligned) and chunk counts of a handle are copied to dst_bm[slot[e]][words] and
+// dst_chunks[slot[e]][scope_chunks(words)] (slot[e] < n_slots; distinct entries name distinct slots), and where clip_took[e] > 0
+// n_clip[slot[e]] (may be pinned host memory) = what launch_mask_clip gives for that bitmap and took, read from the source.
+// The table travels by value.  hipErrorInvalidValue before the launch for a bad shape, a null or a misaligned base.
+constexpr int32_t kMaxGatherGroups = 64;
+constexpr int64_t kGatherMaxBlocksX = 256;
+struct GroupGatherTable {
+    const uint32_t *bm[kMaxGatherGroups];
+    const uint32_t *chunks[kMaxGatherGroups];
+    uint32_t clip_took[kMaxGatherGroups];
+    int32_t slot[kMaxGatherGroups];
+};
+hipError_t launch_group_gather_clip(const GroupGatherTable &tab, int32_t n_entries, int32_t n_slots, int64_t words, uint32_t *dst_bm,
+                                    uint32_t *dst_chunks, int64_t *n_clip, hipStream_t s);
 // launch_row_consts for the rows whose bit is set; {0, mask::kMaskedRecency} for the others.  The bitmap covers n_rows.
 hipError_t launch_row_consts_masked(const double *norm_b, const int64_t *created, int64_t now_ticks, int64_t n_rows, const uint32_t *bitmap,
                                     double2 *out, hipStream_t s);

@@ -1719,11 +1719,12 @@ hipError_t launch_scope_trailers(orr_candidate *recs, int32_t B, int32_t kprime,
 
 // ---- masked search (orr_search_batch_masked; the rules are orr_mask_plan.h's) -----------------------------------------------
 
-// One workgroup: n_clip = one past the position of the took-th set bit (1 <= took <= set bits) of a bitmap whose chunk counts
-// exist.  Thread t sums a contiguous run of chunks, thread 0 walks the 256 sums and then that run; the chunk found is scanned
-// the same way, four words per thread; scope::clip_word leaves the took-th bit as the highest of the last word.
-__global__ __launch_bounds__(256) void mask_clip_kernel(const uint32_t *__restrict__ bitmap, int64_t words, int32_t n_chunks,
-                                                        const uint32_t *__restrict__ chunk_cnt, uint32_t took, int64_t *__restrict__ n_clip)
+// One workgroup of 256: *n_clip = one past the position of the took-th set bit (1 <= took <= set bits) of a bitmap whose chunk
+// counts exist.  Thread t sums a contiguous run of chunks, thread 0 walks the 256 sums and then that run; the chunk found is
+// scanned the same way, four words per thread; scope::clip_word leaves the took-th bit as the highest of the last word.
+// Every thread of the workgroup calls it (it synchronises); the rule of mask_clip_kernel and of group_gather_clip_kernel.
+__device__ __forceinline__ void mask_clip_rule(const uint32_t *__restrict__ bitmap, int64_t words, int32_t n_chunks,
+                                               const uint32_t *__restrict__ chunk_cnt, uint32_t took, int64_t *__restrict__ n_clip)
 {
     __shared__ uint32_t part[256];
     __shared__ int32_t s_at;
@@ -1777,11 +1778,57 @@ __global__ __launch_bounds__(256) void mask_clip_kernel(const uint32_t *__restri
     *n_clip = clip;
 }
 
+__global__ __launch_bounds__(256) void mask_clip_kernel(const uint32_t *__restrict__ bitmap, int64_t words, int32_t n_chunks,
+                                                        const uint32_t *__restrict__ chunk_cnt, uint32_t took, int64_t *__restrict__ n_clip)
+{
+    mask_clip_rule(bitmap, words, n_chunks, chunk_cnt, took, n_clip);
+}
+
 hipError_t launch_mask_clip(const uint32_t *bitmap, int64_t words, const uint32_t *chunk_cnt, uint32_t took, int64_t *n_clip, hipStream_t s)
 {
     if (words <= 0 || words % 4 != 0 || took == 0u) return hipErrorInvalidValue;
     const int32_t n_chunks = scope_chunks(words);
     hipLaunchKernelGGL(mask_clip_kernel, dim3(1), dim3(256), 0, s, bitmap, words, n_chunks, chunk_cnt, took, n_clip);
+    return hipGetLastError();
+}
+
+// The front of a grouped pass over scope handles in ONE launch: blockIdx.y = an entry of the table (a used group), the
+// workgroups of a row copy the group's bitmap (16 bytes per lane, contiguous per wave, grid-stride) and chunk counts from the
+// handle's own arrays into slot `slot` of the call's contiguous arrays; workgroup x == 0 of an entry whose took lies below the
+// handle's live rows (clip_took > 0) also computes the group's clip -- from the SOURCE arrays, which nobody writes during the
+// call, so no workgroup waits for another -- into n_clip[slot].  No atomics; the LDS is mask_clip_rule's.
+__global__ __launch_bounds__(256) void group_gather_clip_kernel(const GroupGatherTable tab, int64_t words, int32_t n_chunks,
+                                                                uint32_t *__restrict__ dst_bm, uint32_t *__restrict__ dst_chunks,
+                                                                int64_t *__restrict__ n_clip)
+{
+    const int e = blockIdx.y;
+    const uint32_t *__restrict__ src_bm = tab.bm[e];
+    const uint32_t *__restrict__ src_ch = tab.chunks[e];
+    const int64_t slot = tab.slot[e];
+    const uint4 *__restrict__ in = reinterpret_cast<const uint4 *>(src_bm);
+    uint4 *__restrict__ out = reinterpret_cast<uint4 *>(dst_bm + slot * words);
+    const int64_t vecs = words >> 2, stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < vecs; v += stride) out[v] = in[v];
+    uint32_t *__restrict__ out_ch = dst_chunks + slot * (int64_t)n_chunks;      // (n_chunks need not be a multiple of 4: words of 4 bytes)
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n_chunks; c += stride) out_ch[c] = src_ch[c];
+    if (blockIdx.x != 0 || tab.clip_took[e] == 0u) return;
+    mask_clip_rule(src_bm, words, n_chunks, src_ch, tab.clip_took[e], n_clip + slot);
+}
+
+hipError_t launch_group_gather_clip(const GroupGatherTable &tab, int32_t n_entries, int32_t n_slots, int64_t words, uint32_t *dst_bm,
+                                    uint32_t *dst_chunks, int64_t *n_clip, hipStream_t s)
+{
+    if (n_entries <= 0) return hipSuccess;
+    if (n_entries > kMaxGatherGroups || n_slots < 1 || n_slots > kMaxGatherGroups || words <= 0 || words % 4 != 0 || !dst_bm || !dst_chunks || !n_clip)
+        return hipErrorInvalidValue;
+    if (reinterpret_cast<uintptr_t>(dst_bm) % 16 != 0) return hipErrorInvalidValue;
+    for (int32_t e = 0; e < n_entries; ++e) {
+        if (!tab.bm[e] || !tab.chunks[e] || reinterpret_cast<uintptr_t>(tab.bm[e]) % 16 != 0) return hipErrorInvalidValue;
+        if (tab.slot[e] < 0 || tab.slot[e] >= n_slots) return hipErrorInvalidValue;
+    }
+    const int32_t n_chunks = scope_chunks(words);
+    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(((words >> 2) + 255) / 256, kGatherMaxBlocksX));
+    hipLaunchKernelGGL(group_gather_clip_kernel, dim3(gx, (unsigned)n_entries), dim3(256), 0, s, tab, words, n_chunks, dst_bm, dst_chunks, n_clip);
     return hipGetLastError();
 }
 

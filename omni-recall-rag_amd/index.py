@@ -578,6 +578,28 @@ class RecallIndex:
                                                 int(scope_before), _ptr(out)))
         return out
 
+    def search_shard_in_scopes(self, qvecs, queries_terms, now_ticks: int, kprime: int, candidate_limit: int,
+                               scopes: Sequence[RecallScope], query_scope, scope_before, topk: int = 0, shard_pass: int = 0, out=None):
+        """orr_search_shard_in_scopes: this shard's [B, kprime+1] records of a grouped search, query b inside
+        scopes[query_scope[b]] (handles of this shard: RecallScope, or RecallClusterScope.shard(i)); scope_before [len(scopes)]:
+        each scope's live rows on the shards in front (their handles' rows)."""
+        B = len(queries_terms)
+        dim, q, _keep = self._query_args(qvecs, B)
+        pool, toff, qoff = pack_terms(queries_terms)
+        qs = np.ascontiguousarray(query_scope, dtype=np.int32).reshape(-1)
+        if qs.shape[0] != B:
+            raise ValueError(f"query_scope: {qs.shape[0]} entries for {B} queries")
+        before = np.ascontiguousarray(scope_before, dtype=np.int64).reshape(-1)
+        if before.shape[0] != len(scopes):
+            raise ValueError(f"scope_before: {before.shape[0]} entries for {len(scopes)} scopes")
+        handles = (C.c_void_p * max(1, len(scopes)))(*[sc._h for sc in scopes])
+        if out is None:
+            out = np.zeros((B, kprime + 1), dtype=CAND_DTYPE)
+        N.check(N.hip.orr_search_shard_in_scopes(self._h, B, dim, _ptr(q), _ptr(pool), _ptr(toff), _ptr(qoff), now_ticks, int(kprime),
+                                                 int(candidate_limit), max(0, int(topk)), int(shard_pass), len(scopes),
+                                                 C.cast(handles, C.c_void_p), _ptr(qs), _ptr(before), _ptr(out)))
+        return out
+
     def scope_count(self, scope_ids, n_queries: int = 1) -> np.ndarray:
         """orr_index_scope_count: [n_queries] int64, the live rows each query's scope resolves to on this shard."""
         n_ids, ids, off = self._scope_args(scope_ids, n_queries)
@@ -840,6 +862,27 @@ class RecallCluster:
         counts = np.zeros(B, dtype=np.int32)
         N.check(N.hip.orr_cluster_search_batch_in_scope(self._h, B, dim, _ptr(q), _ptr(pool), _ptr(toff), _ptr(qoff), now_ticks, int(topk),
                                                         int(candidate_limit), scope._h, _ptr(rows), _ptr(scores), _ptr(counts)))
+        return rows, scores, counts
+
+    def search_in_scopes(self, qvecs, queries_terms, now_ticks: int, topk: int, scopes: Sequence[RecallClusterScope], query_scope,
+                         candidate_limit: int = 300):
+        """orr_cluster_search_batch_in_scopes: query b searches inside scopes[query_scope[b]], each result what search_in_scope
+        returns with that scope; every shard streams its shadow once per batch.  At most 64 scopes.  qvecs in host memory
+        (numpy) or None.  Returns (rows [B,k] int64, scores [B,k] float64, counts [B] int32)."""
+        B = len(queries_terms)
+        dim, q = self._host_query_args(qvecs, B)
+        pool, toff, qoff = pack_terms(queries_terms)
+        qs = np.ascontiguousarray(query_scope, dtype=np.int32).reshape(-1)
+        if qs.shape[0] != B:
+            raise ValueError(f"query_scope: {qs.shape[0]} entries for {B} queries")
+        handles = (C.c_void_p * max(1, len(scopes)))(*[sc._h for sc in scopes])
+        k = max(1, int(topk))
+        rows = np.full((B, k), -1, dtype=np.int64)
+        scores = np.zeros((B, k), dtype=np.float64)
+        counts = np.zeros(B, dtype=np.int32)
+        N.check(N.hip.orr_cluster_search_batch_in_scopes(self._h, B, dim, _ptr(q), _ptr(pool), _ptr(toff), _ptr(qoff), now_ticks,
+                                                         int(topk), int(candidate_limit), len(scopes), C.cast(handles, C.c_void_p),
+                                                         _ptr(qs), _ptr(rows), _ptr(scores), _ptr(counts)))
         return rows, scores, counts
 
     def set_option(self, name: str, value: int) -> None:
