@@ -475,7 +475,10 @@ int orr_index_scope_count(orr_index *idx, int32_t B, int64_t n_scope_ids, const 
  *                              window whose interval covers them included -- until orr_scope_add_ids names them; that call
  *                              looks up only the ids it is given and ORs them in.  A term scope is no exception: rows
  *                              inserted later are not in it even when their text contains its terms (it is not evaluated
- *                              again); an orr_scope_create_terms made afterwards holds them
+ *                              again); an orr_scope_create_terms made afterwards holds them.  Nor is a cosine scope:
+ *                              rows inserted later are not in it however close they lie to its probes, and
+ *                              orr_index_update_rows does not evaluate it again either -- a row it held stays in it with its
+ *                              new vector; an orr_scope_create_near made afterwards sees the rows as they are then
  *   orr_index_update_rows, orr_index_set_row_base   touch no scope
  * Unlike a view, a scope does not block compaction or insertion.  Scopes are not saved by orr_index_save.  A scope costs one
  * bit per row of the shard plus its chunk counts (1.25 MB at 10M rows); ORR_ENOMEM when that does not fit.
@@ -498,6 +501,23 @@ int orr_index_scope_count(orr_index *idx, int32_t B, int64_t n_scope_ids, const 
  *                           all rows ANDNOT the ANY scope.  At most 256 terms (a row bitmap of workspace per distinct term:
  *                           320 MB at 10M rows).  The keyword chain of a search runs once for the call, on the device; no
  *                           search statistic moves.
+ *   orr_scope_create_near   the live rows r with CosineSimilarity(probe_p, e_r) >= min_cosine for EVERY probe (ORR_NEAR_ALL) or
+ *                           for AT LEAST ONE (ORR_NEAR_ANY): the reference's function (RecallSearchService.cs:69-88) bit for
+ *                           bit, compared as C# compares doubles.  probes is [n_probes][dim] floats in host or device memory.
+ *                           The reference's guards stand: a row without an embedding has cosine 0, so has a probe or a row
+ *                           with norm <= 0; dim 0 (probes may be NULL) or a dim other than the index's gives cosine 0 for
+ *                           every row -- the scope is then every live row when 0 >= min_cosine and empty otherwise, and no row
+ *                           is read; a NaN cosine is never >= anything.  min_cosine may be -infinity or +infinity.  A probe
+ *                           listed twice counts once; n_probes == 0 gives the empty scope in both modes.  AT MOST 8 PROBES per
+ *                           call (one walk of the rows carries 8): fold more with orr_scope_combine (AND for ALL, OR for ANY).
+ *                           A set without a size limit, not a ranking: "everything but the rows close to X" is all rows
+ *                           (orr_scope_create_ticks(INT64_MIN, INT64_MAX)) ANDNOT this scope.  The rows are walked once, in
+ *                           the exact arithmetic of the search's exact pass; a pair whose cosine lies within 2^-40 of
+ *                           min_cosine (or is not finite) is decided on the host by the expression the host finish of a search
+ *                           uses.  Those pairs go through a list of "near_band_cap" entries of 16 bytes (orr_index_set_option,
+ *                           default 65,536, 1 .. 2^31): a walk that needs more -- thousands of copies of the probe with
+ *                           min_cosine at their own cosine -- grows the list to what it needed and runs once more.  No search
+ *                           statistic moves.
  *   orr_scope_add_ids       adds the live rows that carry the ids; *out_added (may be NULL) = rows that were not in it before
  *   orr_scope_combine       dst = dst AND src, dst OR src, or dst AND NOT src, in place; src is unchanged (src == dst is allowed)
  *   orr_scope_rows          live rows in it now; -1 on an orphaned handle (or NULL)
@@ -518,17 +538,23 @@ int orr_index_scope_count(orr_index *idx, int32_t B, int64_t n_scope_ids, const 
  * ORR_EINVAL before any device call, with the outputs untouched, and before the index handle is looked at: a NULL scope or out
  * pointer, negative counts, ids NULL with n_ids > 0, op outside 0 .. 2; for orr_scope_create_terms, in this order: out NULL,
  * n_terms outside 0 .. 256, terms_utf8 or term_off NULL with n_terms > 0, mode outside 0 .. 1, an empty term or offsets that
- * decrease -- then a NULL index, then ORR_ESTATE for an index that is not sealed. */
+ * decrease; for orr_scope_create_near, in this order: out NULL, n_probes outside 0 .. 8, dim negative, probes NULL with
+ * n_probes > 0 and dim > 0, mode outside 0 .. 1, min_cosine NaN -- then a NULL index, then ORR_ESTATE for an index that is not
+ * sealed. */
 typedef struct orr_scope orr_scope;      /* opaque: a set of rows of one sealed shard, resident on its device */
 #define ORR_SCOPE_AND    0
 #define ORR_SCOPE_OR     1
 #define ORR_SCOPE_ANDNOT 2
 #define ORR_TERMS_ALL 0
 #define ORR_TERMS_ANY 1
+#define ORR_NEAR_ALL 0
+#define ORR_NEAR_ANY 1
 int     orr_scope_create(orr_index *idx, int64_t n_ids, const int64_t *ids /* host or device */, orr_scope **out);
 int     orr_scope_create_ticks(orr_index *idx, int64_t ticks_from, int64_t ticks_to, orr_scope **out);
 int     orr_scope_create_terms(orr_index *idx, int32_t n_terms, const uint8_t *terms_utf8 /* host */, const uint32_t *term_off /* host [n_terms+1] */,
                                int32_t mode, orr_scope **out);
+int     orr_scope_create_near(orr_index *idx, int32_t n_probes, int32_t dim, const float *probes /* host or device, [n_probes][dim] */,
+                              double min_cosine, int32_t mode, orr_scope **out);
 int     orr_scope_add_ids(orr_scope *s, int64_t n_ids, const int64_t *ids /* host or device */, int64_t *out_added);
 int     orr_scope_combine(orr_scope *dst, int32_t op, const orr_scope *src);
 int64_t orr_scope_rows(const orr_scope *s);
@@ -791,13 +817,15 @@ int        orr_cluster_insert_rows(orr_cluster *c, int32_t shard, int64_t n, int
  * Argument errors come before any device call and before a handle is looked at, with the outputs untouched, in this order: out
  * pointer NULL (row_ids: cap negative, out_n NULL, out_ids NULL with cap > 0), negative counts, ids NULL with n_ids > 0, op
  * outside 0 .. 2; for create_terms: out NULL, n_terms outside 0 .. 256, terms_utf8 or term_off NULL with n_terms > 0, mode
- * outside 0 .. 1, an empty term or offsets that decrease; then a NULL scope, then a NULL cluster; then ids in device memory
- * (ORR_EINVAL: every shard's device reads them), ORR_ESTATE for an unsealed cluster or an orphaned scope. */
+ * outside 0 .. 1, an empty term or offsets that decrease; for create_near: orr_scope_create_near's, in its order; then a NULL
+ * scope, then a NULL cluster; then ids or probes in device memory (ORR_EINVAL: every shard's device reads them), ORR_ESTATE for an unsealed cluster or an orphaned scope. */
 typedef struct orr_cluster_scope orr_cluster_scope;   /* opaque: one orr_scope per shard of one sealed cluster */
 int     orr_cluster_scope_create(orr_cluster *c, int64_t n_ids, const int64_t *ids /* HOST */, orr_cluster_scope **out);
 int     orr_cluster_scope_create_ticks(orr_cluster *c, int64_t ticks_from, int64_t ticks_to, orr_cluster_scope **out);
 int     orr_cluster_scope_create_terms(orr_cluster *c, int32_t n_terms, const uint8_t *terms_utf8 /* host */, const uint32_t *term_off /* host [n_terms+1] */,
                                        int32_t mode, orr_cluster_scope **out);
+int     orr_cluster_scope_create_near(orr_cluster *c, int32_t n_probes, int32_t dim, const float *probes /* HOST */,
+                                      double min_cosine, int32_t mode, orr_cluster_scope **out);
 int     orr_cluster_scope_add_ids(orr_cluster_scope *s, int64_t n_ids, const int64_t *ids /* HOST */, int64_t *out_added);
 int     orr_cluster_scope_combine(orr_cluster_scope *dst, int32_t op, const orr_cluster_scope *src);
 int64_t orr_cluster_scope_rows(const orr_cluster_scope *s);

@@ -25,6 +25,7 @@ ORR_OK, ORR_EINVAL, ORR_ENOMEM, ORR_EDEVICE, ORR_ECOMM, ORR_EDIM, ORR_ESTATE = 0
 ORR_CAND_TRAILER, ORR_CAND_DOT_EXACT, ORR_CAND_DEAD = 1, 2, 16
 ORR_SCOPE_AND, ORR_SCOPE_OR, ORR_SCOPE_ANDNOT = 0, 1, 2
 ORR_TERMS_ALL, ORR_TERMS_ANY = 0, 1
+ORR_NEAR_ALL, ORR_NEAR_ANY = 0, 1
 
 
 class OrrConfig(C.Structure):
@@ -100,6 +101,8 @@ hip.orr_scope_create_ticks.restype = C.c_int
 hip.orr_scope_create_ticks.argtypes = [_vp, _i64, _i64, C.POINTER(_vp)]
 hip.orr_scope_create_terms.restype = C.c_int
 hip.orr_scope_create_terms.argtypes = [_vp, _i32, _vp, _vp, _i32, C.POINTER(_vp)]
+hip.orr_scope_create_near.restype = C.c_int
+hip.orr_scope_create_near.argtypes = [_vp, _i32, _i32, _vp, C.c_double, _i32, C.POINTER(_vp)]
 hip.orr_scope_add_ids.restype = C.c_int
 hip.orr_scope_add_ids.argtypes = [_vp, _i64, _vp, _vp]
 hip.orr_scope_combine.restype = C.c_int
@@ -190,6 +193,8 @@ hip.orr_cluster_scope_create_ticks.restype = C.c_int
 hip.orr_cluster_scope_create_ticks.argtypes = [_vp, _i64, _i64, C.POINTER(_vp)]
 hip.orr_cluster_scope_create_terms.restype = C.c_int
 hip.orr_cluster_scope_create_terms.argtypes = [_vp, _i32, _vp, _vp, _i32, C.POINTER(_vp)]
+hip.orr_cluster_scope_create_near.restype = C.c_int
+hip.orr_cluster_scope_create_near.argtypes = [_vp, _i32, _i32, _vp, C.c_double, _i32, C.POINTER(_vp)]
 hip.orr_cluster_scope_add_ids.restype = C.c_int
 hip.orr_cluster_scope_add_ids.argtypes = [_vp, _i64, _vp, _vp]
 hip.orr_cluster_scope_combine.restype = C.c_int
@@ -289,9 +294,9 @@ EXPORTED_HIP_SYMBOLS = [
     "orr_index_delete_rows", "orr_index_update_rows", "orr_index_insert_rows", "orr_cluster_insert_rows", "orr_index_live_rows", "orr_index_compact", "orr_cluster_compact", "orr_index_search_stats",
     "orr_cluster_create", "orr_cluster_destroy", "orr_cluster_shards", "orr_cluster_shard", "orr_cluster_seal", "orr_cluster_rows",
     "orr_cluster_search_batch", "orr_cluster_search_batch_scoped", "orr_cluster_search_batch_masked", "orr_cluster_search_stats", "orr_cluster_set_option",
-    "orr_scope_create", "orr_scope_create_ticks", "orr_scope_create_terms", "orr_scope_add_ids", "orr_scope_combine", "orr_scope_rows", "orr_scope_row_ids", "orr_scope_destroy",
+    "orr_scope_create", "orr_scope_create_ticks", "orr_scope_create_terms", "orr_scope_create_near", "orr_scope_add_ids", "orr_scope_combine", "orr_scope_rows", "orr_scope_row_ids", "orr_scope_destroy",
     "orr_search_batch_in_scope", "orr_search_batch_in_scopes", "orr_search_shard_in_scope", "orr_search_shard_in_scopes",
-    "orr_cluster_scope_create", "orr_cluster_scope_create_ticks", "orr_cluster_scope_create_terms", "orr_cluster_scope_add_ids", "orr_cluster_scope_combine",
+    "orr_cluster_scope_create", "orr_cluster_scope_create_ticks", "orr_cluster_scope_create_terms", "orr_cluster_scope_create_near", "orr_cluster_scope_add_ids", "orr_cluster_scope_combine",
     "orr_cluster_scope_rows", "orr_cluster_scope_row_ids", "orr_cluster_scope_shard", "orr_cluster_scope_destroy", "orr_cluster_search_batch_in_scope",
     "orr_cluster_search_batch_in_scopes",
 ]

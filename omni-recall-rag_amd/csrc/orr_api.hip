@@ -40,6 +40,7 @@
 #include "orr_group_plan.h"
 #include "orr_scope_set_plan.h"
 #include "orr_scope_terms_plan.h"
+#include "orr_scope_near_plan.h"
 #include "orr_cluster_handle_plan.h"
 #include "orr_cluster_group_plan.h"
 #include "orr_cluster_scope_plan.h"
@@ -224,6 +225,10 @@ struct orr_index {
     PinnedBuf pin_scope, pin_scope_pass;
     DevBuf ws_scope_terms;                     // a lane's: where each distinct term's bitmap starts (orr_scope_create_terms)
     PinnedBuf pin_scope_terms;                 // ... and the host's copy of it
+    // cosine scopes (orr_scope_create_near), a lane's: the probes and their exact norms, the band list with its counter, the
+    // listed rows' norms (then the positions the host decided out)
+    DevBuf ws_near_q, ws_near_norm, ws_near_band, ws_near_cnt, ws_near_rows;
+    int64_t near_band_cap = scope_near::kDefaultBandCap;   // "near_band_cap": entries of the band list; grows to the measured count when a walk exceeds it
     // masked search (orr_search_batch_masked), a lane's: the call's shared scope bitmap and its chunk counts (the list path in
     // parts rewrites ws_scope_bm per part), the sample's counts and the zeros that select the one bitmap, n_clip and the sample's sizes
     DevBuf ws_mask_bm, ws_mask_chunks, ws_mask_cnt, ws_mask_meta;
@@ -573,12 +578,8 @@ struct Ranked {
 double exact_score(const orr_candidate &c, bool use_cos, double norm_a, int32_t n_terms, int64_t now_ticks)
 {
     double cosv = 0.0;
-    if (use_cos) {
-        if (norm_a <= 0.0 || c.norm_b <= 0.0)
-            cosv = 0.0;
-        else
-            cosv = c.dot / (std::sqrt(norm_a) * std::sqrt(c.norm_b));
-    }
+    if (use_cos)
+        cosv = scope_near::cosine_of(c.dot, norm_a, c.norm_b);   // :84-87, the one expression the cosine scope's band decides with too
     double kw = n_terms > 0 ? (double)c.matches / (double)n_terms : 0.0;
     double total_days = (double)(now_ticks - c.created_ticks) / 864000000000.0;
     double age_days = total_days > 0.0 ? total_days : 0.0;
@@ -741,6 +742,7 @@ void orr_index_destroy(orr_index *idx)
     for (DevBuf *b : {&idx->ws_scope_ids, &idx->ws_scope_meta, &idx->ws_scope_bm, &idx->ws_scope_chunks, &idx->ws_scope_sel}) b->release();
     idx->pin_scope.release(); idx->pin_scope_pass.release();
     idx->ws_scope_terms.release(); idx->pin_scope_terms.release();
+    for (DevBuf *b : {&idx->ws_near_q, &idx->ws_near_norm, &idx->ws_near_band, &idx->ws_near_cnt, &idx->ws_near_rows}) b->release();
     for (DevBuf *b : {&idx->ws_mask_bm, &idx->ws_mask_chunks, &idx->ws_mask_cnt, &idx->ws_mask_meta}) b->release();
     idx->pin_mask.release();
     for (DevBuf *b : {&idx->ws_group_bm, &idx->ws_group_chunks, &idx->ws_group_meta}) b->release();
@@ -1992,6 +1994,7 @@ static void copy_options(const orr_index *from, orr_index *to)
     to->opt_shard_pass = from->opt_shard_pass; to->opt_shard_topk = from->opt_shard_topk;
     to->kw_hits_cap = from->kw_hits_cap; to->dead_before = from->dead_before;
     to->opt_mask_screen = from->opt_mask_screen; to->opt_mask_part_rows = from->opt_mask_part_rows;
+    to->near_band_cap = from->near_band_cap;
 }
 
 // a lane borrows whatever shadows its index has now
@@ -2036,6 +2039,9 @@ int orr_index_set_option(orr_index *idx, const char *name, int64_t value)
         if (!mask::part_rows_valid(value))
             return fail(ORR_EINVAL, "orr_index_set_option: mask_part_rows must be in 1 .. %u", scope::kMaxScopeRows);
         idx->opt_mask_part_rows = value;
+    } else if (strcmp(name, "near_band_cap") == 0) {
+        if (!scope_near::band_cap_valid(value)) return fail(ORR_EINVAL, "orr_index_set_option: near_band_cap must be in 1 .. 2^31");
+        idx->near_band_cap = value;
     } else if (strcmp(name, "two_stage") == 0) {
         if (value < 0 || value > 2) return fail(ORR_EINVAL, "orr_index_set_option: two_stage takes 0, 1 or 2");
         idx->opt_two_stage = (int)value;
@@ -5813,6 +5819,124 @@ static int scope_row_ids_held(orr_index *lane, const orr_scope *s, int64_t live,
     return r;
 }
 
+// The fill of a cosine scope (orr_scope_near_plan.h), on the lane the caller holds:
+//   1. no probes: the empty scope.  A foreign dim: every cosine is 0 -- all rows or none (scope_fill_range), no row is walked;
+//   2. the probes brought to the device (they may live there already) and their exact norms taken as the queries' are
+//      (launch_dot_exact, self_norm);
+//   3. scope_near: launch_dot_exact's walk, a bit per row, every word written; pairs the device may not decide go to the band
+//      list.  A list that was too short grows from the measured count and the walk runs again: never a truncated list;
+//   4. the band: the listed rows' norms gathered, the list read back, every pair decided by scope_near::cosine_of on the HOST --
+//      exact_score's expression -- and the pending rows that fold to false cleared (they were written set);
+//   5. the deleted rows cleared.
+// The search statistics do not move (this is no search); the kernel statistics record the launches.
+static int scope_fill_near(orr_index *lane, orr_scope *sc, int32_t n_probes, int32_t dim, const float *probes, double min_cosine, int32_t mode)
+{
+    const orr_index *own = owner_of(lane);
+    hipStream_t s = lane->stream;
+    const int64_t n = lane->n_rows;
+    if (n_probes == 0 || n <= 0) {                     // nothing to compare with: the empty scope
+        HIP_TRY(hipMemsetAsync(sc->bm, 0, sizeof(uint32_t) * (size_t)sc->words, s));
+        return ORR_OK;
+    }
+    if (scope_near::foreign_dim(dim, lane->dim)) {
+        Timed t(lane, "scope_fill_range", 4.0 * (double)sc->words);
+        HIP_TRY(orr::launch_scope_fill_range(sc->bm, sc->words, 0, scope_near::all_rows_at_zero(min_cosine) ? n : 0, s));
+    } else {
+        ORR_TRY(lane->ws_near_q.reserve(sizeof(float) * (size_t)n_probes * (size_t)dim));
+        ORR_TRY(lane->ws_near_norm.reserve(sizeof(double) * (size_t)scope_near::kMaxProbes));
+        ORR_TRY(lane->ws_near_cnt.reserve(sizeof(unsigned long long)));
+        HIP_TRY(hipMemcpyAsync(lane->ws_near_q.p, probes, sizeof(float) * (size_t)n_probes * (size_t)dim, hipMemcpyDefault, s));
+        {
+            Timed t(lane, "scope_near_probe_norms", (4.0 * dim + 8.0) * n_probes);
+            HIP_TRY(orr::launch_dot_exact(lane->ws_near_q.as<float>(), n_probes, dim, nullptr, 1, true, lane->ws_near_norm.as<double>(), n_probes, s));
+        }
+        unsigned long long count = 0;
+        for (int attempt = 0;; ++attempt) {
+            const int64_t cap = lane->near_band_cap;
+            ORR_TRY(lane->ws_near_band.reserve(sizeof(scope_near::BandEntry) * (size_t)cap));
+            HIP_TRY(hipMemsetAsync(lane->ws_near_cnt.p, 0, sizeof(unsigned long long), s));
+            {
+                Timed t(lane, "scope_near", 4.0 * (double)n * dim + 8.0 * (double)n + 4.0 * (double)sc->words);
+                HIP_TRY(orr::launch_scope_near(lane->d_emb, n, dim, lane->ws_near_q.as<float>(), n_probes, lane->ws_near_norm.as<double>(), lane->d_norm_b,
+                                               min_cosine, mode, lane->ws_near_band.as<scope_near::BandEntry>(),
+                                               lane->ws_near_cnt.as<unsigned long long>(), cap, sc->bm, sc->words, s));
+            }
+            HIP_TRY(hipMemcpyAsync(&count, lane->ws_near_cnt.p, sizeof(count), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            if (count <= (unsigned long long)cap) break;
+            if (count > (unsigned long long)scope_near::kMaxBandCap || attempt >= 3)
+                return fail(ORR_EDEVICE, "orr_scope_create_near: the band list kept overflowing (%llu pairs)", count);
+            lane->near_band_cap = scope_near::grown_cap((int64_t)count);
+        }
+        if (count > 0) {
+            const size_t m = (size_t)count;
+            ORR_TRY(lane->ws_near_rows.reserve(sizeof(double) * m));
+            {
+                Timed t(lane, "scope_near_band_norms", 32.0 * (double)m);
+                HIP_TRY(orr::launch_scope_near_band_norms(lane->ws_near_band.as<scope_near::BandEntry>(), (int64_t)m, lane->d_norm_b, n, lane->ws_near_rows.as<double>(), s));
+            }
+            std::vector<scope_near::BandEntry> band(m);
+            std::vector<double> norm_b(m);
+            double norm_a[scope_near::kMaxProbes] = {};
+            HIP_TRY(hipMemcpyAsync(band.data(), lane->ws_near_band.p, sizeof(scope_near::BandEntry) * m, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(norm_b.data(), lane->ws_near_rows.p, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(norm_a, lane->ws_near_norm.p, sizeof(double) * (size_t)n_probes, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            std::vector<size_t> order(m);
+            for (size_t i = 0; i < m; ++i) order[i] = i;
+            std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return band[a].pos < band[b].pos; });
+            std::vector<int64_t> out_rows;             // the pending rows the host decides OUT: their bits were written set
+            for (size_t i = 0; i < m;) {
+                double c[scope_near::kMaxProbes];
+                int32_t k = 0;
+                const uint32_t pos = band[order[i]].pos;
+                for (; i < m && band[order[i]].pos == pos; ++i) {
+                    const scope_near::BandEntry &e = band[order[i]];
+                    if ((int64_t)pos >= n || e.probe >= (uint32_t)n_probes || k >= scope_near::kMaxProbes)
+                        return fail(ORR_EDEVICE, "orr_scope_create_near: a malformed band entry (row %u, probe %u)", e.pos, e.probe);
+                    c[k++] = scope_near::cosine_of(e.dot, norm_a[e.probe], norm_b[order[i]]);
+                }
+                if (!scope_near::pending_row_in(c, k, min_cosine, mode)) out_rows.push_back((int64_t)pos);
+            }
+            if (!out_rows.empty()) {                   // (ws_near_rows holds 8 bytes per band entry: enough for a position per row)
+                HIP_TRY(hipMemcpyAsync(lane->ws_near_rows.p, out_rows.data(), sizeof(int64_t) * out_rows.size(), hipMemcpyHostToDevice, s));
+                {
+                    Timed t(lane, "scope_near_fixup", 12.0 * (double)out_rows.size());
+                    HIP_TRY(orr::launch_scope_clear_positions(sc->bm, sc->words, lane->ws_near_rows.as<int64_t>(), (int64_t)out_rows.size(), s));
+                }
+                HIP_TRY(hipStreamSynchronize(s));      // out_rows is read until here
+            }
+            if (lane->profiling == 1) lane->stats[(size_t)stat_slot(lane, "scope_near_band_pairs")].algo_bytes += 16.0 * (double)m;
+        }
+    }
+    Timed t(lane, "scope_clear_positions", 12.0 * (double)own->dead.size());
+    HIP_TRY(orr::launch_scope_clear_positions(sc->bm, sc->words, own->d_dead.as<int64_t>(), (int64_t)own->dead.size(), s));
+    return ORR_OK;
+}
+
+// the argument errors of orr_scope_create_near and its cluster form, in their order (scope_near::first_invalid)
+static int near_arguments(const char *fn, bool out_null, int32_t n_probes, int32_t dim, const float *probes, int32_t mode, double min_cosine)
+{
+    switch (scope_near::first_invalid(out_null, n_probes, dim, probes == nullptr, mode, min_cosine)) {
+    case 0: return ORR_OK;
+    case 1: return fail(ORR_EINVAL, "%s: out is NULL", fn);
+    case 2: return fail(ORR_EINVAL, "%s: n_probes must be in 0 .. %d (fold more with orr_scope_combine)", fn, scope_near::kMaxProbes);
+    case 3: return fail(ORR_EINVAL, "%s: dim is negative", fn);
+    case 4: return fail(ORR_EINVAL, "%s: probes is NULL with %d probes of dim %d", fn, n_probes, dim);
+    case 5: return fail(ORR_EINVAL, "%s: mode must be ORR_NEAR_ALL (0) or ORR_NEAR_ANY (1)", fn);
+    default: return fail(ORR_EINVAL, "%s: min_cosine is NaN", fn);
+    }
+}
+
+int orr_scope_create_near(orr_index *idx, int32_t n_probes, int32_t dim, const float *probes, double min_cosine, int32_t mode, orr_scope **out)
+{
+    ORR_TRY(near_arguments("orr_scope_create_near", out == nullptr, n_probes, dim, probes, mode, min_cosine));
+    if (!idx) return fail(ORR_EINVAL, "orr_scope_create_near: null index");
+    return make_scope(idx, "orr_scope_create_near", out, [&](orr_index *lane, orr_scope *sc) -> int {
+        return scope_fill_near(lane, sc, n_probes, dim, probes, min_cosine, mode);
+    });
+}
+
 int orr_scope_add_ids(orr_scope *s, int64_t n_ids, const int64_t *ids, int64_t *out_added)
 {
     if (n_ids < 0) return fail(ORR_EINVAL, "orr_scope_add_ids: n_ids is negative");
@@ -7044,6 +7168,16 @@ int orr_cluster_scope_create_terms(orr_cluster *c, int32_t n_terms, const uint8_
     if (bad >= 0) return fail(ORR_EINVAL, "%s: term_off is not monotone at term %d", fn, bad);
     if (!c) return fail(ORR_EINVAL, "%s: null cluster", fn);
     return make_cluster_scope(c, fn, out, [&](orr_index *sh, orr_scope **part) { return orr_scope_create_terms(sh, n_terms, terms_utf8, term_off, mode, part); });
+}
+
+int orr_cluster_scope_create_near(orr_cluster *c, int32_t n_probes, int32_t dim, const float *probes, double min_cosine, int32_t mode,
+                                  orr_cluster_scope **out)
+{
+    static const char *fn = "orr_cluster_scope_create_near";
+    ORR_TRY(near_arguments(fn, out == nullptr, n_probes, dim, probes, mode, min_cosine));
+    if (!c) return fail(ORR_EINVAL, "%s: null cluster", fn);
+    if (n_probes > 0 && dim > 0 && is_device_pointer(probes)) return fail(ORR_EINVAL, "%s: probes must be in host memory (every shard's device reads them)", fn);
+    return make_cluster_scope(c, fn, out, [&](orr_index *sh, orr_scope **part) { return orr_scope_create_near(sh, n_probes, dim, probes, min_cosine, mode, part); });
 }
 
 int orr_cluster_scope_add_ids(orr_cluster_scope *s, int64_t n_ids, const int64_t *ids, int64_t *out_added)

@@ -11,6 +11,7 @@
 #include "orr_mask_plan.h"
 #include "orr_scope_set_plan.h"
 #include "orr_scope_terms_plan.h"
+#include "orr_scope_near_plan.h"
 
 #include <atomic>
 
@@ -501,5 +502,16 @@ hipError_t launch_scope_terms_bases(const int64_t *term_word_off, int32_t n, int
 // bitmaps and dst 16-byte aligned and every base a multiple of 4 words: one 16-byte load per term and lane.
 hipError_t launch_scope_terms_combine(const uint32_t *bitmaps, const int64_t *term_base /* device, [n] words from bitmaps */,
                                       int32_t n, int32_t mode, int64_t words, int64_t n_rows, uint32_t *dst, hipStream_t s);
+
+// ---- cosine scopes (orr_scope_create_near; the rules are orr_scope_near_plan.h's) -------------------------------------------
+// bm (words, all written) = bit r set iff row r < n_rows is In or Pending by scope_near::row_state over the device's cosines of
+// the nq probes Q [nq][D] with row r of E (exact dots by launch_dot_exact's walk, norm_a [nq] and norm_b [n_rows] the exact
+// norms).  Every band pair of a pending row bumps *band_cnt (zeroed by the caller) and, below band_cap, is stored in band.
+// 1 <= nq <= kMaxExactQ, D > 0, words % 4 == 0, n_rows <= 32 * words, band 16-byte and bm 8-byte aligned.
+hipError_t launch_scope_near(const float *E, int64_t n_rows, int32_t D, const float *Q, int32_t nq, const double *norm_a, const double *norm_b,
+                             double min_cosine, int32_t mode, scope_near::BandEntry *band, unsigned long long *band_cnt, int64_t band_cap,
+                             uint32_t *bm, int64_t words, hipStream_t s);
+// out[i] = norm_b[band[i].pos] for the n entries a walk listed.
+hipError_t launch_scope_near_band_norms(const scope_near::BandEntry *band, int64_t n, const double *norm_b, int64_t n_rows, double *out, hipStream_t s);
 
 }  // namespace orr

@@ -73,16 +73,16 @@ hipError_t launch_row_consts(const double *norm_b, const int64_t *created, int64
 // Tile: [64 rows][64 floats] = 16 KiB per wave, 16-byte chunks XOR-swizzled by
 // (row & 15) so that the 16-lane groups of ds_read_b128 hit 16 distinct slots.
 // ---------------------------------------------------------------------------
-template <int NQ, bool SELF, bool PREFETCH, bool NT>
-__global__ __launch_bounds__(256) void dot_exact_tiled(const float *__restrict__ E, int64_t n_rows, int32_t D,
-                                                       const float *__restrict__ Q, double *__restrict__ out,
-                                                       int64_t out_stride)
+// The walk: each wave of the workgroup takes groups of 64 consecutive rows (group g = rows [64 g, 64 g + 64), grid-stride over
+// n_groups) and calls end(row0, lane, acc) once per group with acc[q] of lane l = the exact dot of row row0 + l with Q[q]
+// (SELF: with itself), 0 for a row at or above n_rows.  dot_exact_tiled and scope_near_tiled are this walk with two endings.
+template <int NQ, bool SELF, bool PREFETCH, bool NT, class END>
+__device__ __forceinline__ void exact_walk_tiled(const float *E, int64_t n_rows, int64_t n_groups, int32_t D, const float *Q, END end)
 {
     __shared__ __attribute__((aligned(16))) float tile_all[4][64 * 64];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     float *tile = tile_all[wave];
-    const int64_t n_groups = (n_rows + 63) >> 6;
     const int ld_row = lane >> 4;     // 0..3: row within a 4-row load
     const int ld_ch = lane & 15;      // 16-byte chunk within the 256-byte row piece
 
@@ -152,11 +152,21 @@ __global__ __launch_bounds__(256) void dot_exact_tiled(const float *__restrict__
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
+        end(row0, lane, acc);
+    }
+}
+
+template <int NQ, bool SELF, bool PREFETCH, bool NT>
+__global__ __launch_bounds__(256) void dot_exact_tiled(const float *__restrict__ E, int64_t n_rows, int32_t D,
+                                                       const float *__restrict__ Q, double *__restrict__ out,
+                                                       int64_t out_stride)
+{
+    exact_walk_tiled<NQ, SELF, PREFETCH, NT>(E, n_rows, (n_rows + 63) >> 6, D, Q, [&](int64_t row0, int lane, const double (&acc)[NQ]) {
         if (row0 + lane < n_rows) {
 #pragma unroll
             for (int q = 0; q < NQ; ++q) out[(int64_t)q * out_stride + row0 + lane] = acc[q];
         }
-    }
+    });
 }
 
 // Any D (tests use 2, 3, ...): one thread per row, plain loads.  Correctness path
@@ -2207,6 +2217,144 @@ hipError_t launch_scope_terms_combine(const uint32_t *bitmaps, const int64_t *te
     if ((reinterpret_cast<uintptr_t>(bitmaps) | reinterpret_cast<uintptr_t>(dst)) & 15u) return hipErrorInvalidValue;   // 16-byte vectors
     const int64_t blocks = std::min<int64_t>((words / 4 + 255) / 256, 2048);
     hipLaunchKernelGGL(scope_terms_combine_kernel, dim3((unsigned)blocks), dim3(256), 0, s, bitmaps, term_base, n, mode, words, n_rows, dst);
+    return hipGetLastError();
+}
+
+// ---- cosine scopes (orr_scope_create_near; the rules are orr_scope_near_plan.h's) -------------------------------------------
+static_assert(scope_near::kMaxProbes == kMaxExactQ, "a cosine scope's probes are one walk of the exact dot");
+
+struct NearOut {                       // what the ending of a cosine scope's walk needs
+    const double *norm_a;              // [nq] the probes' exact norms
+    const double *norm_b;              // [n_rows] the rows' exact norms
+    double t;                          // min_cosine
+    int32_t mode;
+    scope_near::BandEntry *band;       // [band_cap]
+    unsigned long long *band_cnt;      // the pairs the walk wanted to list
+    int64_t band_cap;
+    uint32_t *bm;                      // the scope's bitmap
+    int64_t n_rows;
+};
+
+// The ending of the walk for the wave's 64 rows [row0, row0 + 64), every lane of the wave taking part: lane l has the exact dots
+// acc[0 .. nq) of row row0 + l (zeros at or above n_rows, where the norm counts as 0 as well: cosine 0).  Per pair
+// scope_near::cosine_of, per row scope_near::row_state; a pending row (a pair in the band that can still change the fold) lists
+// its band pairs for the host and keeps its bit SET until the host has decided (the host clears the losers).  One ballot forms
+// the two words, the tail mask clears what is no row, and lane 0 stores the pair: vector stores only.
+__device__ __forceinline__ void scope_near_store(const double *acc, int32_t nq, int64_t row0, int lane, const NearOut &o)
+{
+    const int64_t row = row0 + lane;
+    const bool is_row = row < o.n_rows;
+    const double nb = is_row ? o.norm_b[row] : 0.0;
+    double c[scope_near::kMaxProbes];
+#pragma unroll
+    for (int q = 0; q < scope_near::kMaxProbes; ++q) {
+        c[q] = 0.0;
+        if (q < nq) c[q] = scope_near::cosine_of(acc[q], o.norm_a[q], nb);
+    }
+    const int32_t state = scope_near::row_state(c, nq, o.t, o.mode);
+    if (state == scope_near::Pending && is_row) {
+#pragma unroll
+        for (int q = 0; q < scope_near::kMaxProbes; ++q) {
+            if (q < nq && scope_near::in_band(c[q], o.t)) {
+                const unsigned long long at = atomicAdd(o.band_cnt, 1ull);
+                if (at < (unsigned long long)o.band_cap) {
+                    const double d = acc[q];
+                    *reinterpret_cast<uint4 *>(o.band + at) = make_uint4((uint32_t)row, (uint32_t)q, (uint32_t)__double2loint(d), (uint32_t)__double2hiint(d));
+                }
+            }
+        }
+    }
+    const unsigned long long bits = __ballot(state != scope_near::Out);
+    if (lane == 0) {
+        const int64_t w = row0 >> 5;
+        *reinterpret_cast<uint2 *>(o.bm + w) = make_uint2((uint32_t)bits & scope_near::tail_mask(w, o.n_rows),
+                                                          (uint32_t)(bits >> 32) & scope_near::tail_mask(w + 1, o.n_rows));
+    }
+}
+
+// dot_exact_tiled's walk with scope_near_store for its ending: a bit per row where that kernel writes 8 * NQ bytes.  The groups
+// run to the end of the BITMAP (words / 2 of them: words % 4 == 0), so every word is written; the walk loads nothing for rows
+// at or above n_rows.
+template <int NQ>
+__global__ __launch_bounds__(256) void scope_near_tiled(const float *__restrict__ E, int32_t D, const float *__restrict__ Q, int64_t words, NearOut o)
+{
+    exact_walk_tiled<NQ, false, true, true>(E, o.n_rows, words >> 1, D, Q, [&](int64_t row0, int lane, const double (&acc)[NQ]) {
+        scope_near_store(acc, NQ, row0, lane, o);
+    });
+}
+
+// Any D, after dot_exact_generic: one thread per row, plain loads, 64 consecutive rows per wave; the same ending.
+__global__ __launch_bounds__(256) void scope_near_generic(const float *__restrict__ E, int32_t D, const float *__restrict__ Q, int32_t nq, int64_t words, NearOut o)
+{
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t row0 = row & ~(int64_t)63;
+    if (row0 >= words * 32) return;                    // (wave-uniform: words * 32 is a multiple of 64)
+    double acc[scope_near::kMaxProbes];
+#pragma unroll
+    for (int q = 0; q < scope_near::kMaxProbes; ++q) {
+        acc[q] = 0.0;
+        if (q < nq && row < o.n_rows) {
+            const float *e = E + row * (int64_t)D, *x = Q + (int64_t)q * D;
+            double a = 0.0;
+            for (int i = 0; i < D; ++i) {
+                float p = x[i] * e[i];
+                a += (double)p;
+            }
+            acc[q] = a;
+        }
+    }
+    scope_near_store(acc, nq, row0, threadIdx.x & 63, o);
+}
+
+hipError_t launch_scope_near(const float *E, int64_t n_rows, int32_t D, const float *Q, int32_t nq, const double *norm_a, const double *norm_b,
+                             double min_cosine, int32_t mode, scope_near::BandEntry *band, unsigned long long *band_cnt, int64_t band_cap,
+                             uint32_t *bm, int64_t words, hipStream_t s)
+{
+    if (nq < 1 || nq > scope_near::kMaxProbes || D <= 0 || n_rows < 0 || words <= 0 || words % 4 != 0 || n_rows > words * 32 ||
+        !scope_near::mode_valid(mode) || min_cosine != min_cosine || !scope_near::band_cap_valid(band_cap) ||
+        !E || !Q || !norm_a || !norm_b || !band || !band_cnt || !bm)
+        return hipErrorInvalidValue;
+    if ((reinterpret_cast<uintptr_t>(band) & 15u) || (reinterpret_cast<uintptr_t>(bm) & 7u)) return hipErrorInvalidValue;   // 16- and 8-byte stores
+    const NearOut o{norm_a, norm_b, min_cosine, mode, band, band_cnt, band_cap, bm, n_rows};
+    const bool tiled = (D % 64 == 0) && ((reinterpret_cast<uintptr_t>(E) & 15) == 0);
+    if (!tiled) {
+        hipLaunchKernelGGL(scope_near_generic, dim3((unsigned)((words * 32 + 255) / 256)), dim3(256), 0, s, E, D, Q, nq, words, o);
+        return hipGetLastError();
+    }
+    const int64_t n_groups = words / 2;
+    int64_t blocks = (n_groups + 3) / 4;
+    if (blocks > 256 * 16) blocks = 256 * 16;          // launch_dot_exact's grid
+    dim3 grid((unsigned)blocks), block(256);
+#define ORR_LAUNCH_NEAR(NQ_) hipLaunchKernelGGL((scope_near_tiled<NQ_>), grid, block, 0, s, E, D, Q, words, o)
+    switch (nq) {
+    case 1: ORR_LAUNCH_NEAR(1); break;
+    case 2: ORR_LAUNCH_NEAR(2); break;
+    case 3: ORR_LAUNCH_NEAR(3); break;
+    case 4: ORR_LAUNCH_NEAR(4); break;
+    case 5: ORR_LAUNCH_NEAR(5); break;
+    case 6: ORR_LAUNCH_NEAR(6); break;
+    case 7: ORR_LAUNCH_NEAR(7); break;
+    default: ORR_LAUNCH_NEAR(8); break;
+    }
+#undef ORR_LAUNCH_NEAR
+    return hipGetLastError();
+}
+
+// out[i] = norm_b[band[i].pos]: the one thing the host's decision of a band pair needs beside the entry and the probe's norm
+__global__ __launch_bounds__(256) void scope_near_band_norms_kernel(const scope_near::BandEntry *__restrict__ band, int64_t n,
+                                                                    const double *__restrict__ norm_b, int64_t n_rows, double *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t p = band[i].pos;
+    out[i] = (int64_t)p < n_rows ? norm_b[p] : 0.0;
+}
+
+hipError_t launch_scope_near_band_norms(const scope_near::BandEntry *band, int64_t n, const double *norm_b, int64_t n_rows, double *out, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    if (!band || !norm_b || !out || n_rows < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(scope_near_band_norms_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, band, n, norm_b, n_rows, out);
     return hipGetLastError();
 }
 

@@ -76,10 +76,30 @@ def pack_contents(contents: Sequence[bytes]) -> Tuple[np.ndarray, np.ndarray]:
     return pool, off
 
 
+def _near_args(probes, mode: str, device_ok: bool):
+    """(n_probes, dim, array kept alive, mode) of a cosine scope's probes: [n, dim] float32, numpy or (device_ok) a torch tensor;
+    None or an empty list is no probes."""
+    modes = {"all": N.ORR_NEAR_ALL, "any": N.ORR_NEAR_ANY}
+    if mode not in modes:
+        raise ValueError('mode: "all" or "any"')
+    if probes is None:
+        return 0, 0, None, modes[mode]
+    if _is_torch(probes) and device_ok:
+        import torch
+        p = probes.to(torch.float32).contiguous()
+    else:
+        p = np.ascontiguousarray(probes, dtype=np.float32)
+    if p.ndim == 1:
+        p = p.reshape(1, -1) if p.shape[0] else p.reshape(0, 0)
+    if p.ndim != 2:
+        raise ValueError("probes: [n_probes, dim]")
+    return int(p.shape[0]), int(p.shape[1]), p, modes[mode]
+
+
 class RecallScope:
     """A scope handle (orr_scope): a set of ROWS of one sealed shard, resolved once and resident on its device.  It follows
     its rows through delete_rows, compact and insert_rows of the shard; rows inserted later are in no scope until add_ids
-    names them.  Made by RecallIndex.scope / scope_ticks / scope_terms; close it before or after its index (after: only the host part is
+    names them.  Made by RecallIndex.scope / scope_ticks / scope_terms / scope_near; close it before or after its index (after: only the host part is
     left to free)."""
 
     def __init__(self, handle, index: "RecallIndex"):
@@ -497,6 +517,15 @@ class RecallIndex:
         N.check(N.hip.orr_scope_create_terms(self._h, n_terms, _ptr(pool), _ptr(toff), modes[mode], C.byref(h)))
         return RecallScope(h, self)
 
+    def scope_near(self, probes, min_cosine: float, mode: str = "all") -> RecallScope:
+        """orr_scope_create_near: the live rows whose reference cosine to every probe (mode "all") or to at least one
+        (mode "any") is >= min_cosine.  probes: [n_probes, dim] float32, numpy or a torch tensor on the device, at most 8;
+        no probes give an empty scope; a dim other than the index's gives cosine 0 for every row."""
+        n, dim, p, m = _near_args(probes, mode, True)
+        h = C.c_void_p()
+        N.check(N.hip.orr_scope_create_near(self._h, n, dim, _ptr(p) if n and dim else None, float(min_cosine), m, C.byref(h)))
+        return RecallScope(h, self)
+
     def search_in_scope(self, qvecs, queries_terms, now_ticks: int, topk: int, scope: RecallScope, candidate_limit: int = 300):
         """orr_search_batch_in_scope: search_masked with the scope taken from a handle -- nothing is resolved per call.
         Returns (rows [B,k] int64, scores [B,k] float64, counts [B] int32)."""
@@ -847,6 +876,14 @@ class RecallCluster:
         n_terms = int(toff.shape[0]) - 1
         h = C.c_void_p()
         N.check(N.hip.orr_cluster_scope_create_terms(self._h, n_terms, _ptr(pool), _ptr(toff), modes[mode], C.byref(h)))
+        return RecallClusterScope(h, self)
+
+    def scope_near(self, probes, min_cosine: float, mode: str = "all") -> RecallClusterScope:
+        """orr_cluster_scope_create_near: the live rows whose reference cosine to every probe (mode "all") or to at least
+        one (mode "any") is >= min_cosine, on every shard.  probes: [n_probes, dim] float32 in host memory, at most 8."""
+        n, dim, p, m = _near_args(probes, mode, False)
+        h = C.c_void_p()
+        N.check(N.hip.orr_cluster_scope_create_near(self._h, n, dim, _ptr(p) if n and dim else None, float(min_cosine), m, C.byref(h)))
         return RecallClusterScope(h, self)
 
     def search_in_scope(self, qvecs, queries_terms, now_ticks: int, topk: int, scope: RecallClusterScope, candidate_limit: int = 300):
