@@ -697,6 +697,28 @@ int orr_index_screen_i8_stream_dots(orr_index *idx, int32_t B, int32_t dim, cons
  * kernel 1: the queries split into bf16 hi/lo halves, then the unfused three-product split-bf16 GEMM.  dim % 64 == 0. */
 int orr_index_pass_dots(orr_index *idx, int32_t kernel, int32_t B, int32_t dim, const float *q, float *out);
 
+/* Diagnostic: the keyword chain of a search, seen directly (tests/test_gpu_keyword_chain.py).  Runs the chain exactly as a
+ * search for ONE query that owns all n_terms terms runs it -- vocabulary match, alias stage, posting expansion, the repeat with
+ * a grown hit list when the list was too short, and the cleanup that leaves the lane as a search leaves it -- and returns what
+ * the scoring kernels would read:
+ *   out_bitmaps [n_terms][words]  uint32, host memory: bit r & 31 of word r >> 5 is set iff row r (candidate order) contains
+ *                                 the term.  words = ((orr_index_rows + 31) / 32 + 3) / 4 * 4, the chain's own words_per_term;
+ *                                 pass it as out_words_per_term (ORR_EINVAL when it differs).  A term whose bitmap is a stored
+ *                                 token bitmap is returned from there: the caller cannot tell from the bits where they came
+ *                                 from.  The bits are RAW: the positions of deleted rows are NOT cleared (posting lists keep
+ *                                 them until compaction; a search drops such rows behind the scoring).
+ *   out_alias [n_terms]           uint8, may be NULL: 1 where the term's only hit was a token with a stored bitmap.
+ *   out_info [4]                  int64: [0] words, [1] the (term, token) hits of the final, untruncated run, [2] how many
+ *                                 times the chain ran, [3] the short-token form that ran: 0 all-pairs, 1 lookup (both are
+ *                                 the kernel statistic "vocab_match").
+ * terms_utf8 / term_off as in orr_search_batch: term t is bytes [term_off[t], term_off[t + 1]).  1 .. 4096 terms, none empty,
+ * all DISTINCT (ORR_EINVAL otherwise); a result of more than 2^30 bytes is refused (ORR_EINVAL).
+ * form: -1 as a search would choose, 0 the all-pairs form, 1 the lookup form.  mid: -1 default, 0 sends the tokens of 17..32
+ * bytes through the wave-per-token scan.  Both hold for this call only and go ahead of ORR_VOCAB_LOOKUP / ORR_VOCAB_MID.
+ * The search statistics do not move; the kernel statistics record the launches.  ORR_ESTATE when the index is not sealed. */
+int orr_index_keyword_bitmaps(orr_index *idx, int32_t n_terms, const uint8_t *terms_utf8, const uint32_t *term_off, int32_t form,
+                              int32_t mid, int64_t out_words_per_term, uint32_t *out_bitmaps, uint8_t *out_alias, int64_t *out_info);
+
 /* ---- measurement ---------------------------------------------------------*/
 /* enabled: 0 off; 1 an event pair around every kernel; 2 only around the one launch per search that streams every row
  * (each pair costs a few microseconds of stream time, which a one-query search notices).  Also resets the counters. */

@@ -159,6 +159,8 @@ hip.orr_index_screen_i8_stream_dots.restype = C.c_int
 hip.orr_index_screen_i8_stream_dots.argtypes = [_vp, _i32, _i32, _vp, _i32, _vp]
 hip.orr_index_pass_dots.restype = C.c_int
 hip.orr_index_pass_dots.argtypes = [_vp, _i32, _i32, _i32, _vp, _vp]
+hip.orr_index_keyword_bitmaps.restype = C.c_int
+hip.orr_index_keyword_bitmaps.argtypes = [_vp, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp]
 hip.orr_index_set_profiling.restype = C.c_int
 hip.orr_index_set_profiling.argtypes = [_vp, _i32]
 hip.orr_index_kernel_stats.restype = C.c_int
@@ -290,7 +292,7 @@ EXPORTED_HIP_SYMBOLS = [
     "orr_abi_version", "orr_device_count", "orr_last_error", "orr_index_create", "orr_index_destroy",
     "orr_index_append", "orr_index_seal", "orr_index_rows", "orr_index_dim", "orr_search_batch",
     "orr_search_shard", "orr_search_shard_ex", "orr_search_batch_scoped", "orr_search_batch_masked", "orr_search_batch_masked_groups", "orr_search_shard_scoped", "orr_search_shard_masked", "orr_index_scope_count", "orr_merge_candidates", "orr_merge_candidates_ex", "orr_index_set_profiling", "orr_index_kernel_stats",
-    "orr_index_save", "orr_index_load", "orr_index_set_row_base", "orr_index_set_option", "orr_index_screen_dots", "orr_index_screen_i8_dots", "orr_index_screen_i8_consts", "orr_index_screen_i8_stream_dots", "orr_index_pass_dots", "orr_index_view",
+    "orr_index_save", "orr_index_load", "orr_index_set_row_base", "orr_index_set_option", "orr_index_screen_dots", "orr_index_screen_i8_dots", "orr_index_screen_i8_consts", "orr_index_screen_i8_stream_dots", "orr_index_pass_dots", "orr_index_keyword_bitmaps", "orr_index_view",
     "orr_index_delete_rows", "orr_index_update_rows", "orr_index_insert_rows", "orr_cluster_insert_rows", "orr_index_live_rows", "orr_index_compact", "orr_cluster_compact", "orr_index_search_stats",
     "orr_cluster_create", "orr_cluster_destroy", "orr_cluster_shards", "orr_cluster_shard", "orr_cluster_seal", "orr_cluster_rows",
     "orr_cluster_search_batch", "orr_cluster_search_batch_scoped", "orr_cluster_search_batch_masked", "orr_cluster_search_stats", "orr_cluster_set_option",

@@ -194,6 +194,9 @@ struct orr_index {
     std::vector<double> h_norm_a;      // exact query norms of the batch in flight (run_shard -> host finish)
     std::vector<uint32_t> h_survivors; // two-stage pass: (query,row) pairs the screen kept, per query of the batch in flight (else empty)
     uint32_t kw_hits_cap = 16u << 20;  // (term, token) matches the hit list of the keyword chain holds; grows to the measured count when a batch exceeds it
+    // orr_index_keyword_bitmaps, for the one chain it runs on this lane: the short-token form (-1 as a search chooses, 0 all-pairs,
+    // 1 lookup) and the 17..32-byte kernel (-1 default, 0 off) ahead of the environment switches; and the form the last chain ran
+    int kw_force_form = -1, kw_force_mid = -1, kw_form_ran = -1;
     uint32_t survivor_cap = 8192;      // entries per query of the survivors' buffers; grows when a query overflows it (clustered corpora)
     uint32_t pass_cap = 8192;          // what the pass in flight uses: survivor_cap, halved until a batch's buffers stay below 2 GiB
     orr_search_stats sstats{};         // orr_index_search_stats
@@ -2440,6 +2443,7 @@ struct KwSide {
     size_t bm_bytes = 0, bm_clean_before = 0;     // the batch's own bitmaps: bytes used, bytes known to be zero on entry
     bool overflow_possible = false;               // the hit list may have been too short (checked behind the pass)
     uint32_t max_hits = 0;
+    const uint8_t *alias = nullptr;               // per distinct term: its bitmap is a stored token bitmap (device; null without a token store)
 };
 
 int launch_keyword_side(orr_index *idx, const BatchArgs &a, const std::vector<uint32_t> &qoff, KwSide &out)
@@ -2487,7 +2491,9 @@ int launch_keyword_side(orr_index *idx, const BatchArgs &a, const std::vector<ui
         // (the lookup pays from tens of millions of (token, term) pairs on: below, sorting the terms on the host -- 0.15 ms for the
         // 3,000 terms of 1024 queries -- costs more than comparing them all on the GPU)
         const bool vocab_lookup = [&] { static const int e = [] { const char *v = getenv("ORR_VOCAB_LOOKUP"); return v ? atoi(v) : -1; }();
+                                        if (idx->kw_force_form >= 0) return idx->kw_force_form != 0;      // orr_index_keyword_bitmaps
                                         return e >= 0 ? e != 0 : (TT >= 64 && (int64_t)TT * idx->n_tokens >= ((int64_t)1 << 25)); }();
+        idx->kw_form_ran = vocab_lookup ? 1 : 0;
         const size_t meta_bytes = vocab_lookup ? off_bloom + orr::kVocabBloomBits / 8 : off_pool + pool_bytes + 16;
         ORR_TRY(idx->pin_meta.reserve(meta_bytes));
         ORR_TRY(idx->ws_meta.reserve(meta_bytes));
@@ -2609,7 +2615,7 @@ int launch_keyword_side(orr_index *idx, const BatchArgs &a, const std::vector<ui
             // tokens of 17..32 bytes (the front of the list of longer tokens): one lane per token as well (ORR_VOCAB_MID=0: through
             // the wave-per-token scan like the longer ones, A/B)
             static const bool mid_off = [] { const char *e = getenv("ORR_VOCAB_MID"); return e && atoi(e) == 0; }();
-            const int64_t n_mid = mid_off ? 0 : std::min<int64_t>(idx->n_vmid, VL);
+            const int64_t n_mid = (idx->kw_force_mid >= 0 ? idx->kw_force_mid == 0 : mid_off) ? 0 : std::min<int64_t>(idx->n_vmid, VL);
             if (n_mid > 0) {
                 Timed t(idx, "vocab_match_mid", 0.0, k);
                 HIP_TRY(orr::launch_vocab_match_mid(idx->d_vpool, idx->vlong_start.as<uint64_t>(), idx->vlong_len.as<uint32_t>(),
@@ -2646,6 +2652,7 @@ int launch_keyword_side(orr_index *idx, const BatchArgs &a, const std::vector<ui
                                              reinterpret_cast<uint32_t *>(wa + o_tok), reinterpret_cast<int64_t *>(wa + o_off), wa + o_alias, k));
                 out.view.term_word_off = reinterpret_cast<const int64_t *>(wa + o_off);
                 skip = wa + o_alias;
+                out.alias = skip;
             }
             // the bitmaps are first written here: the clearing behind the last search (on the auxiliary stream) must be done,
             // and what lies beyond the cleared part is cleared now
@@ -5761,6 +5768,107 @@ int orr_scope_create_terms(orr_index *idx, int32_t n_terms, const uint8_t *terms
     return make_scope(idx, "orr_scope_create_terms", out, [&](orr_index *lane, orr_scope *sc) -> int {
         return scope_fill_terms(lane, sc, n_terms, terms_utf8, term_off, mode);
     });
+}
+
+// Diagnostic (tests/test_gpu_keyword_chain.py): the keyword chain of a search for ONE query that owns every term, as
+// scope_fill_terms_run runs it -- launch_keyword_side as it is, the repeat with a grown hit list, clean_keyword_side -- with the
+// per-term bitmaps, the alias flags and the hit count copied out instead of folded.
+constexpr int32_t kKwDiagMaxTerms = 4096;
+constexpr uint64_t kKwDiagMaxBytes = (uint64_t)1 << 30;
+
+static int keyword_bitmaps_run(orr_index *lane, int32_t n_terms, const uint8_t *terms_utf8, const uint32_t *term_off, int64_t words,
+                               uint32_t *out_bitmaps, uint8_t *out_alias, int64_t *out_info)
+{
+    const uint32_t query_term_off[2] = {0u, (uint32_t)n_terms};
+    BatchArgs a{1, 0, nullptr, terms_utf8, term_off, query_term_off, 0, 0};
+    const std::vector<uint32_t> qoff(query_term_off, query_term_off + 2);
+    hipStream_t k = lane->stream_kw;
+    std::vector<int64_t> h_off((size_t)n_terms);
+    std::vector<uint8_t> h_alias((size_t)n_terms, 0);
+    for (int attempt = 0;; ++attempt) {
+        KwSide kws;
+        ORR_TRY(launch_keyword_side(lane, a, qoff, kws));
+        if (kws.view.words_per_term != words || kws.bm_bytes != sizeof(uint32_t) * (size_t)n_terms * (size_t)words)
+            return fail(ORR_ESTATE, "orr_index_keyword_bitmaps: the keyword side made %zu bytes of bitmaps of %lld words for %d terms",
+                        kws.bm_bytes, (long long)kws.view.words_per_term, n_terms);
+        const bool has_store = kws.view.term_word_off != nullptr && kws.alias != nullptr;
+        if (has_store) {
+            HIP_TRY(hipMemcpyAsync(h_off.data(), kws.view.term_word_off, sizeof(int64_t) * (size_t)n_terms, hipMemcpyDeviceToHost, k));
+            HIP_TRY(hipMemcpyAsync(h_alias.data(), kws.alias, (size_t)n_terms, hipMemcpyDeviceToHost, k));
+        }
+        HIP_TRY(hipStreamSynchronize(k));              // the chain is done; the hit count is in pinned memory
+        const uint32_t hits = (uint32_t)(*lane->pin_kwcnt.as<unsigned long long>() >> 32);
+        bool truncated = false;
+        if (kws.overflow_possible && hits > kws.max_hits) {
+            if ((uint64_t)hits * sizeof(orr::KwHit) > ((uint64_t)8 << 30))
+                return fail(ORR_ENOMEM, "orr_index_keyword_bitmaps: the terms matched %u vocabulary tokens: a hit list of that size is refused (8 GiB)", hits);
+            lane->kw_hits_cap = hits + hits / 4 + 1024u;
+            truncated = true;
+        }
+        if (!truncated) {      // raw bits, an aliased term's from the token store (term_word_off counts words from the batch's bitmaps)
+            HIP_TRY(hipMemcpyAsync(out_bitmaps, kws.view.bitmaps, kws.bm_bytes, hipMemcpyDeviceToHost, k));
+            for (int32_t t = 0; has_store && t < n_terms; ++t)
+                if (h_off[(size_t)t] != (int64_t)t * words)
+                    HIP_TRY(hipMemcpyAsync(out_bitmaps + (size_t)t * (size_t)words, kws.view.bitmaps + h_off[(size_t)t], sizeof(uint32_t) * (size_t)words,
+                                           hipMemcpyDeviceToHost, k));
+            HIP_TRY(hipStreamSynchronize(k));
+        }
+        ORR_TRY(clean_keyword_side(lane, kws, (uint32_t)n_terms));
+        if (truncated) {
+            if (attempt >= 3) return fail(ORR_EDEVICE, "orr_index_keyword_bitmaps: the keyword hit list kept overflowing");
+            continue;
+        }
+        if (out_alias) memcpy(out_alias, h_alias.data(), (size_t)n_terms);
+        out_info[1] = (int64_t)hits;
+        out_info[2] = attempt + 1;
+        out_info[3] = lane->kw_form_ran;
+        break;
+    }
+    return ORR_OK;
+}
+
+int orr_index_keyword_bitmaps(orr_index *idx, int32_t n_terms, const uint8_t *terms_utf8, const uint32_t *term_off, int32_t form, int32_t mid,
+                              int64_t out_words_per_term, uint32_t *out_bitmaps, uint8_t *out_alias, int64_t *out_info)
+{
+    static const char *fn = "orr_index_keyword_bitmaps";
+    if (!out_bitmaps || !out_info) return fail(ORR_EINVAL, "%s: out_bitmaps or out_info is NULL", fn);
+    if (n_terms < 1 || n_terms > kKwDiagMaxTerms) return fail(ORR_EINVAL, "%s: n_terms must be in 1 .. %d", fn, kKwDiagMaxTerms);
+    if (!terms_utf8 || !term_off) return fail(ORR_EINVAL, "%s: terms_utf8 or term_off is NULL", fn);
+    if (form < -1 || form > 1) return fail(ORR_EINVAL, "%s: form must be -1 (as a search chooses), 0 (all-pairs) or 1 (lookup)", fn);
+    if (mid < -1 || mid > 0) return fail(ORR_EINVAL, "%s: mid must be -1 (default) or 0 (tokens of 17..32 bytes through the wave scan)", fn);
+    const int32_t bad = scope_terms::first_bad_term(term_off, n_terms);
+    if (bad >= 0 && term_off[bad + 1] == term_off[bad]) return fail(ORR_EINVAL, "%s: term %d is empty", fn, bad);
+    if (bad >= 0) return fail(ORR_EINVAL, "%s: term_off is not monotone at term %d", fn, bad);
+    {
+        std::vector<std::string_view> sorted((size_t)n_terms);
+        for (int32_t t = 0; t < n_terms; ++t)
+            sorted[(size_t)t] = std::string_view(reinterpret_cast<const char *>(terms_utf8) + term_off[t], term_off[t + 1] - term_off[t]);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(ORR_EINVAL, "%s: the terms are not distinct", fn);
+    }
+    if (!idx) return fail(ORR_EINVAL, "%s: null index", fn);
+    Lane ln = acquire_lane(idx);                       // the chain runs like a search's: its own lane, beside the others
+    orr_index *lane = ln.lane;
+    std::lock_guard<std::mutex> lock(lane->mu);
+    if (!lane->sealed) return fail(ORR_ESTATE, "%s: the index is not sealed", fn);
+    const int64_t words = ((lane->n_rows + 31) / 32 + 3) / 4 * 4;           // launch_keyword_side's words_per_term
+    if (out_words_per_term != words) return fail(ORR_EINVAL, "%s: a term bitmap of this shard has %lld words, not %lld", fn, (long long)words, (long long)out_words_per_term);
+    if ((uint64_t)n_terms * (uint64_t)words * sizeof(uint32_t) > kKwDiagMaxBytes)
+        return fail(ORR_EINVAL, "%s: %d bitmaps of %lld words are more than the %llu bytes a call returns", fn, n_terms, (long long)words, (unsigned long long)kKwDiagMaxBytes);
+    out_info[0] = words; out_info[1] = 0; out_info[2] = 0; out_info[3] = -1;
+    if (out_alias) memset(out_alias, 0, (size_t)n_terms);
+    if (lane->n_rows <= 0) return ORR_OK;
+    ORR_TRY(bind_device(lane));
+    struct Overrides {                                 // per-call state of the lane: launch_keyword_side reads it ahead of the environment
+        orr_index *l;
+        ~Overrides() { l->kw_force_form = l->kw_force_mid = -1; }
+    } overrides{lane};
+    lane->kw_force_form = form;
+    lane->kw_force_mid = mid;
+    const int r = keyword_bitmaps_run(lane, n_terms, terms_utf8, term_off, words, out_bitmaps, out_alias, out_info);
+    if (r != ORR_OK) (void)hipStreamSynchronize(lane->stream_kw);
+    collect_events(lane);
+    return r;
 }
 
 // orr_scope_add_ids behind its locks: the caller holds the lane, its lock and the scope exclusively

@@ -706,6 +706,21 @@ class RecallIndex:
         N.check(N.hip.orr_index_pass_dots(self._h, int(kernel), int(q.shape[0]), int(q.shape[1]), _ptr(q), _ptr(out)))
         return out
 
+    def keyword_bitmaps(self, terms: Sequence[bytes], form: int = -1, mid: int = -1) -> dict:
+        """orr_index_keyword_bitmaps: the keyword chain of a search for one query that owns every term (distinct, none empty, at
+        most 4096), seen directly.  form: -1 as a search chooses, 0 all-pairs, 1 lookup; mid: -1 default, 0 tokens of 17..32
+        bytes through the wave scan.  Returns bitmaps [n_terms, words] uint32 (raw: deleted positions are not cleared), alias
+        [n_terms] uint8, hits, runs (how often the chain ran) and form (the short-token form that ran: 0 all-pairs, 1 lookup)."""
+        pool, toff, _ = pack_terms([list(terms)])
+        n_terms = int(toff.shape[0]) - 1
+        words = ((self.rows + 31) // 32 + 3) // 4 * 4
+        bitmaps = np.zeros((max(n_terms, 0), words), dtype=np.uint32)
+        alias = np.zeros(max(n_terms, 0), dtype=np.uint8)
+        info = np.zeros(4, dtype=np.int64)
+        N.check(N.hip.orr_index_keyword_bitmaps(self._h, n_terms, _ptr(pool), _ptr(toff), int(form), int(mid), words,
+                                                bitmaps.ctypes.data, alias.ctypes.data, _ptr(info)))
+        return {"bitmaps": bitmaps, "alias": alias, "words": int(info[0]), "hits": int(info[1]), "runs": int(info[2]), "form": int(info[3])}
+
     def set_profiling(self, on) -> None:
         """False/0 off, True/1 every kernel, 2 only the launch that streams every row (orr_index_set_profiling)."""
         N.check(N.hip.orr_index_set_profiling(self._h, int(on)))

@@ -8,8 +8,9 @@ run of equal keys), verifies the candidates and reports a (token, term) pair onc
 occurs.  This file restates exactly that with Python integers and checks it against `term in token` on random and
 engineered vocabularies (repeated letters, terms that occur several times in a token, terms that are prefixes or
 suffixes of one another, one-letter terms, 16-byte tokens and terms).
-(The device code itself is compared with the oracle in tests/test_gpu_parity.py, with the lookup forced in
-profiles/r03_switch_matrix.txt.)
+(The device code itself -- the kernel, its LDS stage, the rebasing of the staged hits and the path past the stage -- is run in
+tests/test_gpu_keyword_chain.py: its bitmaps, hit count and alias flags against Python references, in the forced lookup form
+and where the default selection takes it.)
 """
 import itertools
 import random
