@@ -52,7 +52,8 @@ typedef enum orr_status {
     ORR_EDEVICE = -3,   /* HIP runtime / kernel failure, or no gfx950 device                   */
     ORR_ECOMM   = -4,   /* shard exchange inconsistent (merge input malformed)                 */
     ORR_EDIM    = -5,   /* appended embedding dimension differs from the index dimension       */
-    ORR_ESTATE  = -6    /* call not valid in this state (append after seal, search before)     */
+    ORR_ESTATE  = -6,   /* call not valid in this state (append after seal, search before)     */
+    ORR_ELIMIT  = -7    /* the request is larger than a sticky limit allows (orr_search_range_cosine) */
 } orr_status;
 
 typedef struct orr_index orr_index;      /* opaque: one corpus shard resident on one GPU */
@@ -586,6 +587,56 @@ int orr_search_batch_in_scopes(orr_index *idx, int32_t B, int32_t dim, const flo
                                int32_t n_scopes, const orr_scope *const *scopes, const int32_t *query_scope /* host [B] */,
                                int64_t *out_rows, double *out_scores, int32_t *out_counts);
 
+/* ---- cosine range search -----------------------------------------------------
+ * For each of B query vectors: EVERY row whose cosine to it is at least min_cosine[b], with that cosine -- the range question
+ * beside top-k (near-duplicates at ingest, "more like this chunk, with scores", evidence checks above a similarity).  A search
+ * ranks at most topk rows by the fused score; orr_scope_create_near makes a set without cosines for one threshold.
+ *   a hit           row r is a hit of query b when it is live, it is in `within` (NULL: every live row) and
+ *                   CosineSimilarity(q_b, e_r) >= min_cosine[b]: the reference's function (RecallSearchService.cs:69-88) bit for
+ *                   bit, compared as C# compares doubles.  The guards are orr_scope_create_near's: a row without an embedding
+ *                   has cosine 0, so has a query with norm <= 0, so has every pair when dim is 0 (q may be NULL) or differs
+ *                   from the index's -- no row is walked for such a query: its hits are all the allowed rows in candidate order
+ *                   when 0 >= min_cosine[b], and none otherwise.  A NaN cosine is never a hit.
+ *   out_total [B]   the exact number of hits of each query
+ *   out_n [B]       min(out_total[b], max_hits)
+ *   out_hits        [B][max_hits]: out_hits[b][0 .. out_n[b]) are the best hits, cosine descending (as double.CompareTo orders)
+ *                   and then candidate position ascending; cosine is the reference's double, order_key = row_base + position as
+ *                   in orr_candidate.  The entries behind out_n[b] are not written.  max_hits == 0 asks for totals only
+ *                   (out_hits may be NULL).
+ *   B               1 .. 64; B == 0 returns ORR_OK and writes nothing.  q is [B][dim] floats in host or device memory.
+ *   min_cosine      host [B], one threshold per query; -infinity and +infinity are allowed, NaN is ORR_EINVAL.
+ * The call is for SELECTIVE thresholds.  Where dim % 128 == 0 and the int8 shadow fits (it is built at the first call, on a
+ * shard of any size) the rows are screened through the shadow, four queries per stream, with a rigorous per-pair bound; the
+ * surviving pairs are re-scored in the reference's arithmetic on the device and every pair that is not certainly below the
+ * threshold is decided on the host by the host finish's own expression.  Other queries (another dim % 128, non-finite or tiny
+ * coordinates: 0 < max|q| < 2^-48) take the exact form: the exact-dot walk of all rows, eight queries per walk.  Both give the
+ * same answer.  When the pairs of ONE query that would have to be re-scored exceed "range_pair_cap" the call returns ORR_ELIMIT:
+ * out_n is all 0, no hit is written, and out_total[b] holds for EVERY query the number of pairs that were kept for it -- an
+ * upper bound of its hits, so the caller sees which query to tighten.  An unselective set is what orr_scope_create_near makes.
+ * Options (orr_index_set_option): "range_pair_cap" 1 .. 2^31 (default 1,048,576); "range_buffer" 1 .. 4,194,240 (default
+ * 8192), the entries per query the survivors' buffers and hit lists start with -- a call that needs more grows them to what it
+ * measured and runs that launch group again, and the lane keeps the grown size: a list is never truncated; "range_form" 0 the
+ * library's choice (today: the screen wherever it applies), 1 the screen wherever it applies, 2 the exact form only (for tests
+ * and measurements: the answers are the same).
+ * The call takes a search lane as orr_search_batch_in_scope does: re-entrant on one handle, views work, the scope is held shared
+ * for the call.  The search statistics do not move; the kernel statistics record every launch under its own name
+ * (screen_gemv_i8_range, range_rescore_exact, range_collect, range_dot_exact, range_collect_dense, ...) and, as byte counts
+ * without launches, range_screen_pairs (16 bytes per pair the screen kept) and range_host_pairs (32 bytes per pair the host
+ * decided).
+ * Errors, in this order, before the handle is looked at and with the outputs untouched: ORR_EINVAL for B outside 0 .. 64, dim
+ * negative, max_hits negative; then, for B > 0: q NULL with dim > 0, min_cosine NULL, out_hits NULL with max_hits > 0, out_n
+ * NULL, out_total NULL, a NaN threshold; then a NULL index.  Then ORR_EINVAL for a scope of another shard, ORR_ESTATE for an
+ * orphaned scope or an index that is not sealed. */
+typedef struct orr_range_hit {
+    int64_t row_id;         /* caller's id of the row                                           */
+    int64_t order_key;      /* global candidate position (row_base + position in the shard)     */
+    double  cosine;         /* CosineSimilarity(q_b, e_r), the reference's value                */
+} orr_range_hit;            /* 24 bytes */
+int orr_search_range_cosine(orr_index *idx, int32_t B, int32_t dim, const float *q /* host or device, [B][dim] */,
+                            const double *min_cosine /* host [B] */, const orr_scope *within /* or NULL: every live row */,
+                            int32_t max_hits, orr_range_hit *out_hits /* host [B][max_hits] */,
+                            int32_t *out_n /* host [B] */, int64_t *out_total /* host [B] */);
+
 /* orr_search_shard_masked with the scope taken from a handle: the record form of orr_search_batch_in_scope, the shard half of
  * orr_cluster_search_batch_in_scope.  The contract is orr_search_shard_masked's, unchanged: [B][kprime+1] records and the
  * trailer, `pass` 0 / 1, topk, candidate_limit GLOBAL with scope_before the scope's live rows on the shards in front (read
@@ -636,6 +687,7 @@ int orr_search_shard_in_scopes(orr_index *idx, int32_t B, int32_t dim, const flo
  *                    same; the option exists for measurements and tests.
  *   "mask_part_rows" 1..4,194,240 (default 4,194,240): the most scoped rows one part of orr_search_batch_masked's list
  *                    path takes.  Smaller values exist so that tests reach the multi-part path on a small shard.
+ *   "range_pair_cap", "range_buffer", "range_form"   see orr_search_range_cosine.
  *   "shard_pass"     0/1/2 (default 0): which pass orr_search_shard runs -- 0 the library's choice, 1 the unfused
  *                    batched pass, 2 the reference-arithmetic pass over every row.  The caller of
  *                    orr_merge_candidates sets 2 for the repeat of a batch some query of which could not be certified.
@@ -890,6 +942,18 @@ int orr_cluster_search_batch_in_scopes(orr_cluster *c, int32_t B, int32_t dim, c
                                        int64_t now_ticks, int32_t topk, int64_t candidate_limit,
                                        int32_t n_scopes, const orr_cluster_scope *const *scopes, const int32_t *query_scope /* host [B] */,
                                        int64_t *out_rows, double *out_scores, int32_t *out_counts);
+
+/* orr_search_range_cosine over a cluster: the answers of that call on ONE index holding all the cluster's rows -- ids, order,
+ * cosine bits and totals.  Every shard runs the call at once on a lane of its own (taken in ascending shard order, the parts of
+ * `within` held shared); the host merges the shards' lists by (cosine descending, order_key ascending), sums the totals and
+ * cuts at max_hits.  ORR_ELIMIT from any shard is the call's status, with the shards' counts summed in out_total.  The options
+ * are the shards' (orr_cluster_shard + orr_index_set_option).
+ * Errors: orr_search_range_cosine's argument errors in its order, then a NULL cluster, then q_host in device memory
+ * (ORR_EINVAL: every shard's device reads it); ORR_ESTATE for an unsealed cluster or an orphaned scope; ORR_EINVAL for a scope
+ * of another cluster. */
+int orr_cluster_search_range_cosine(orr_cluster *c, int32_t B, int32_t dim, const float *q_host, const double *min_cosine /* host [B] */,
+                                    const orr_cluster_scope *within /* or NULL */, int32_t max_hits, orr_range_hit *out_hits,
+                                    int32_t *out_n, int64_t *out_total);
 
 #ifdef __cplusplus
 }

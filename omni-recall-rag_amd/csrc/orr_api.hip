@@ -232,6 +232,14 @@ struct orr_index {
     // listed rows' norms (then the positions the host decided out)
     DevBuf ws_near_q, ws_near_norm, ws_near_band, ws_near_cnt, ws_near_rows;
     int64_t near_band_cap = scope_near::kDefaultBandCap;   // "near_band_cap": entries of the band list; grows to the measured count when a walk exceeds it
+    // cosine range search (orr_search_range_cosine), a lane's: the allowed rows of a call without a scope; the queries as given
+    // and in their walked order; their exact norms; per walked query norm, threshold and QueryConst; the survivors' and the
+    // lists' counters; the survivors' buffers with their exact dots; the lists; the exact form's dense dots
+    DevBuf ws_range_allowed, ws_range_q, ws_range_qp, ws_range_norm, ws_range_consts, ws_range_cnt, ws_range_buf, ws_range_bdot, ws_range_list, ws_range_dots;
+    int opt_range_form = range::Auto;                      // "range_form": 0 the screen where it applies, 1 the same, 2 the exact form only
+    int64_t opt_range_pair_cap = range::kDefaultPairCap;   // "range_pair_cap": kept pairs of one query beyond which the call is ORR_ELIMIT
+    int64_t range_buffer = range::kDefaultBuffer;          // "range_buffer": entries per query of the survivors' buffers and the lists; grows to the measured count
+    int64_t range_list_cap = 0;                            // ... and what the exact form's lists have grown to beyond it
     // masked search (orr_search_batch_masked), a lane's: the call's shared scope bitmap and its chunk counts (the list path in
     // parts rewrites ws_scope_bm per part), the sample's counts and the zeros that select the one bitmap, n_clip and the sample's sizes
     DevBuf ws_mask_bm, ws_mask_chunks, ws_mask_cnt, ws_mask_meta;
@@ -746,6 +754,8 @@ void orr_index_destroy(orr_index *idx)
     idx->pin_scope.release(); idx->pin_scope_pass.release();
     idx->ws_scope_terms.release(); idx->pin_scope_terms.release();
     for (DevBuf *b : {&idx->ws_near_q, &idx->ws_near_norm, &idx->ws_near_band, &idx->ws_near_cnt, &idx->ws_near_rows}) b->release();
+    for (DevBuf *b : {&idx->ws_range_allowed, &idx->ws_range_q, &idx->ws_range_qp, &idx->ws_range_norm, &idx->ws_range_consts, &idx->ws_range_cnt,
+                      &idx->ws_range_buf, &idx->ws_range_bdot, &idx->ws_range_list, &idx->ws_range_dots}) b->release();
     for (DevBuf *b : {&idx->ws_mask_bm, &idx->ws_mask_chunks, &idx->ws_mask_cnt, &idx->ws_mask_meta}) b->release();
     idx->pin_mask.release();
     for (DevBuf *b : {&idx->ws_group_bm, &idx->ws_group_chunks, &idx->ws_group_meta}) b->release();
@@ -1998,6 +2008,8 @@ static void copy_options(const orr_index *from, orr_index *to)
     to->kw_hits_cap = from->kw_hits_cap; to->dead_before = from->dead_before;
     to->opt_mask_screen = from->opt_mask_screen; to->opt_mask_part_rows = from->opt_mask_part_rows;
     to->near_band_cap = from->near_band_cap;
+    to->opt_range_form = from->opt_range_form; to->opt_range_pair_cap = from->opt_range_pair_cap;
+    to->range_buffer = from->range_buffer; to->range_list_cap = from->range_list_cap;
 }
 
 // a lane borrows whatever shadows its index has now
@@ -2045,6 +2057,16 @@ int orr_index_set_option(orr_index *idx, const char *name, int64_t value)
     } else if (strcmp(name, "near_band_cap") == 0) {
         if (!scope_near::band_cap_valid(value)) return fail(ORR_EINVAL, "orr_index_set_option: near_band_cap must be in 1 .. 2^31");
         idx->near_band_cap = value;
+    } else if (strcmp(name, "range_pair_cap") == 0) {
+        if (!range::pair_cap_valid(value)) return fail(ORR_EINVAL, "orr_index_set_option: range_pair_cap must be in 1 .. 2^31");
+        idx->opt_range_pair_cap = value;
+    } else if (strcmp(name, "range_buffer") == 0) {
+        if (!range::buffer_valid(value)) return fail(ORR_EINVAL, "orr_index_set_option: range_buffer must be in 1 .. %lld", (long long)range::kMaxBuffer);
+        idx->range_buffer = value;
+        idx->range_list_cap = 0;
+    } else if (strcmp(name, "range_form") == 0) {
+        if (!range::form_valid(value)) return fail(ORR_EINVAL, "orr_index_set_option: range_form takes 0, 1 or 2");
+        idx->opt_range_form = (int)value;
     } else if (strcmp(name, "two_stage") == 0) {
         if (value < 0 || value > 2) return fail(ORR_EINVAL, "orr_index_set_option: two_stage takes 0, 1 or 2");
         idx->opt_two_stage = (int)value;
@@ -6189,6 +6211,398 @@ int orr_search_batch_in_scopes(orr_index *idx, int32_t B, int32_t dim, const flo
     return grouped_batch(idx, a, ga, out_rows, out_scores, out_counts);
 }
 
+// ---- cosine range search (orr_search_range_cosine; the rules are orr_range_plan.h's) ----------------------------------------
+
+struct RangeArgs {
+    int32_t B, dim;
+    const float *q;
+    const double *min_cosine;
+    int32_t max_hits;
+};
+
+// One shard's answer: per query its best max_hits hits in order and the exact number of hits -- or, with `limit`, no hits
+// and in `total` the pairs each query's screen kept (an upper bound of its hits).
+struct RangeOut {
+    std::vector<std::vector<range::Hit>> hits;
+    std::vector<int64_t> total;
+    bool limit = false;
+};
+
+// The host's decision of one query's list: cosine_of and >= on every pair it received, the order, the cut.
+static void range_finish_query(const std::vector<range::ListEntry> &list, double norm_a, double t, int32_t max_hits, int64_t row_base,
+                               std::vector<range::Hit> &hits, int64_t &total)
+{
+    struct Scored { double c; uint32_t pos; int64_t row_id; };
+    std::vector<Scored> kept;
+    for (const range::ListEntry &e : list) {
+        const double c = scope_near::cosine_of(e.dot, norm_a, e.norm_b);
+        if (scope_near::verdict(c, t)) kept.push_back(Scored{c, e.pos, e.row_id});
+    }
+    total = (int64_t)kept.size();
+    const size_t take = (size_t)std::min<int64_t>(total, max_hits);
+    auto first = [](const Scored &a, const Scored &b) { return range::before(a.c, (int64_t)a.pos, b.c, (int64_t)b.pos); };
+    std::partial_sort(kept.begin(), kept.begin() + (ptrdiff_t)take, kept.end(), first);
+    hits.clear();
+    hits.reserve(take);
+    for (size_t i = 0; i < take; ++i) hits.push_back(range::Hit{kept[i].row_id, row_base + (int64_t)kept[i].pos, kept[i].c});
+}
+
+// The call on the lane the caller holds (with the scope, if any, held shared):
+//   1. the allowed rows: the scope's bitmap, or all rows with the deleted ones cleared;
+//   2. the queries brought to the device (they may live there already), their exact norms taken as a search takes them, and --
+//      where the screen applies -- their int8 images with the quantisation error;
+//   3. every query gets its form: AT ZERO (a foreign dim, a norm <= 0: every cosine is 0, no row is walked), the SCREEN (the int8
+//      shadow, dim % 128 == 0, a finite quantisation error, "range_form" not 2) or the EXACT form; the walked queries are put
+//      in that order (a batch that is in it already is used where it lies);
+//   4. the screen, kScreenQ queries per launch: K2i with the RANGE ending -> survivors' buffers -> launch_rescore_buffer_exact
+//      -> range_collect -> one list per query;
+//   5. the exact form, kMaxExactQ queries per walk: launch_dot_exact over all rows -> range_collect_dense -> the same lists;
+//   6. the host decides every listed pair (range_finish_query).
+// A buffer that was too short grows (range::grown_cap) and its launches run again; a query whose kept pairs exceed
+// "range_pair_cap" turns the call into counting: o.limit.  The search statistics do not move.
+static int range_run(orr_index *lane, const RangeArgs &a, const orr_scope *within, RangeOut &o)
+{
+    const orr_index *own = owner_of(lane);
+    hipStream_t s = lane->stream;
+    const int32_t B = a.B, D = lane->dim;
+    const int64_t n = lane->n_rows;
+    o.hits.assign((size_t)B, {});
+    o.total.assign((size_t)B, 0);
+    o.limit = false;
+    const int64_t allowed_rows = within ? within->live.load() : n - (int64_t)own->dead.size();
+    if (n <= 0 || allowed_rows <= 0) return ORR_OK;
+    const bool profiled = lane->profiling == 1;
+
+    const int64_t words = ((n + 31) / 32 + 3) / 4 * 4;
+    const uint32_t *allowed = nullptr;
+    if (within) {
+        if (within->words != words) return fail(ORR_ESTATE, "orr_search_range_cosine: the scope's bitmap has %lld words, the shard's %lld", (long long)within->words, (long long)words);
+        allowed = within->bm;
+    } else {
+        ORR_TRY(lane->ws_range_allowed.reserve(sizeof(uint32_t) * (size_t)words));
+        {
+            Timed t(lane, "scope_fill_range", 4.0 * (double)words);
+            HIP_TRY(orr::launch_scope_fill_range(lane->ws_range_allowed.as<uint32_t>(), words, 0, n, s));
+        }
+        Timed t(lane, "scope_clear_positions", 12.0 * (double)own->dead.size());
+        HIP_TRY(orr::launch_scope_clear_positions(lane->ws_range_allowed.as<uint32_t>(), words, own->d_dead.as<int64_t>(), (int64_t)own->dead.size(), s));
+        allowed = lane->ws_range_allowed.as<uint32_t>();
+    }
+
+    // -- the queries, their norms, their forms
+    const bool foreign = scope_near::foreign_dim(a.dim, D);
+    std::vector<double> norm_a((size_t)B, 0.0), err2((size_t)B, std::numeric_limits<double>::infinity());
+    bool screen_ok = false;
+    if (!foreign) {
+        ORR_TRY(lane->ws_range_q.reserve(sizeof(float) * (size_t)B * (size_t)D));
+        ORR_TRY(lane->ws_range_norm.reserve(sizeof(double) * (size_t)range::kMaxQueries));
+        HIP_TRY(hipMemcpyAsync(lane->ws_range_q.p, a.q, sizeof(float) * (size_t)B * (size_t)D, hipMemcpyDefault, s));
+        {
+            Timed t(lane, "range_query_norms", (4.0 * D + 8.0) * B);
+            HIP_TRY(orr::launch_dot_exact(lane->ws_range_q.as<float>(), B, D, nullptr, 1, true, lane->ws_range_norm.as<double>(), B, s));
+        }
+        HIP_TRY(hipMemcpyAsync(norm_a.data(), lane->ws_range_norm.p, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, s));
+        if (lane->opt_range_form != range::Exact && D % 128 == 0 && 2 * (size_t)range::kScreenQ * (size_t)D <= 65536) {
+            ORR_TRY(ensure_i8_shadow(lane));           // directly: the screen runs on a shard of any size
+            if (lane->is_view && !lane->i8_ready && lane->parent) {
+                // a lane made before its index had the shadow borrows it now -- when the index's own lane is idle; else the
+                // exact form answers this call (the shadow is only dropped with every lane idle: insert, compact)
+                orr_index *p = const_cast<orr_index *>(lane->parent);
+                if (p->mu.try_lock()) {
+                    if (p->i8_ready) borrow_shadows(p, lane);
+                    p->mu.unlock();
+                }
+            }
+            screen_ok = lane->i8_ready;
+        }
+        if (screen_ok) {
+            ORR_TRY(lane->ws_q8.reserve(2 * (size_t)B * (size_t)D));
+            ORR_TRY(lane->ws_q8s1.reserve(sizeof(float) * (size_t)B));
+            ORR_TRY(lane->ws_q8err.reserve(2 * sizeof(double) * (size_t)B));
+            {
+                Timed t(lane, "range_i8_queries", 6.0 * (double)B * D);
+                HIP_TRY(orr::launch_i8_queries(lane->ws_range_q.as<float>(), B, D, lane->ws_q8.p, lane->ws_q8s1.as<float>(), lane->ws_q8err.as<double>(), s, nullptr));
+            }
+            HIP_TRY(hipMemcpyAsync(err2.data(), lane->ws_q8err.p, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, s));
+        }
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    std::vector<int32_t> perm;                         // the walked queries: the screen's first, then the exact form's
+    int32_t ns = 0;
+    std::vector<int32_t> zero;
+    for (int32_t b = 0; b < B; ++b) {
+        if (foreign || range::at_zero(a.dim, D, norm_a[(size_t)b])) zero.push_back(b);
+        else if (screen_ok && std::isfinite(err2[(size_t)b])) perm.push_back(b);
+    }
+    ns = (int32_t)perm.size();
+    for (int32_t b = 0; b < B; ++b)
+        if (!foreign && !range::at_zero(a.dim, D, norm_a[(size_t)b]) && !(screen_ok && std::isfinite(err2[(size_t)b]))) perm.push_back(b);
+    const int32_t nw = (int32_t)perm.size();
+
+    // -- at zero: every allowed row, in candidate order, with cosine 0 -- or none
+    bool zero_listed = false;
+    std::vector<range::Hit> zero_hits;
+    for (int32_t b : zero) {
+        if (!scope_near::all_rows_at_zero(a.min_cosine[b])) continue;
+        o.total[(size_t)b] = allowed_rows;
+        if (a.max_hits == 0) continue;
+        if (!zero_listed) {
+            zero_listed = true;
+            const size_t take = (size_t)std::min<int64_t>(allowed_rows, a.max_hits);
+            std::vector<uint32_t> bm((size_t)words);
+            HIP_TRY(hipMemcpyAsync(bm.data(), allowed, sizeof(uint32_t) * (size_t)words, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            std::vector<orr::SelEntry> ent;
+            ent.reserve(take);
+            for (int64_t r = 0; r < n && ent.size() < take; ++r)
+                if ((bm[(size_t)(r >> 5)] >> (uint32_t)(r & 31)) & 1u) { orr::SelEntry e; e.key = 0; e.pos = (uint32_t)r; e.pad = 0; ent.push_back(e); }
+            std::vector<int64_t> ids(ent.size());
+            if (!ent.empty()) {
+                ORR_TRY(lane->ws_range_buf.reserve(sizeof(orr::SelEntry) * ent.size()));
+                ORR_TRY(lane->ws_range_bdot.reserve(sizeof(int64_t) * ent.size()));
+                HIP_TRY(hipMemcpyAsync(lane->ws_range_buf.p, ent.data(), sizeof(orr::SelEntry) * ent.size(), hipMemcpyHostToDevice, s));
+                HIP_TRY(orr::launch_scope_entry_ids(lane->ws_range_buf.as<orr::SelEntry>(), (int64_t)ent.size(), lane->d_row_ids, n, lane->ws_range_bdot.as<int64_t>(), s));
+                HIP_TRY(hipMemcpyAsync(ids.data(), lane->ws_range_bdot.p, sizeof(int64_t) * ent.size(), hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+            }
+            for (size_t i = 0; i < ent.size(); ++i) zero_hits.push_back(range::Hit{ids[i], lane->row_base + (int64_t)ent[i].pos, 0.0});
+        }
+        o.hits[(size_t)b] = zero_hits;
+    }
+    if (nw == 0) return ORR_OK;
+
+    // -- the walked queries in their order, with what the kernels read per query
+    bool in_place = true;
+    for (int32_t p = 0; p < nw; ++p) in_place = in_place && perm[(size_t)p] == p;
+    const float *Qp = lane->ws_range_q.as<float>();
+    const int8_t *q1 = static_cast<const int8_t *>(lane->ws_q8.p), *q2 = ns > 0 ? q1 + (size_t)B * (size_t)D : nullptr;
+    if (!in_place) {
+        ORR_TRY(lane->ws_range_qp.reserve(sizeof(float) * (size_t)nw * (size_t)D));
+        for (int32_t p = 0; p < nw; ++p)
+            HIP_TRY(hipMemcpyAsync(lane->ws_range_qp.as<float>() + (size_t)p * D, lane->ws_range_q.as<float>() + (size_t)perm[(size_t)p] * D,
+                                   sizeof(float) * (size_t)D, hipMemcpyDeviceToDevice, s));
+        Qp = lane->ws_range_qp.as<float>();
+        if (ns > 0) {
+            Timed t(lane, "range_i8_queries", 6.0 * (double)ns * D);
+            HIP_TRY(orr::launch_i8_queries(Qp, ns, D, lane->ws_q8.p, lane->ws_q8s1.as<float>(), lane->ws_q8err.as<double>(), s, nullptr));
+        }
+        if (ns > 0) q2 = q1 + (size_t)ns * (size_t)D;
+    }
+    std::vector<double> h_na((size_t)nw), h_t((size_t)nw);
+    std::vector<orr::QueryConst> h_qc((size_t)nw);
+    for (int32_t p = 0; p < nw; ++p) {
+        const int32_t b = perm[(size_t)p];
+        h_na[(size_t)p] = norm_a[(size_t)b];
+        h_t[(size_t)p] = a.min_cosine[b];
+        orr::QueryConst qc{};
+        qc.norm_a = norm_a[(size_t)b];
+        qc.inv_sqrt_na = 1.0 / std::sqrt(norm_a[(size_t)b]);
+        qc.use_cos = 1;
+        h_qc[(size_t)p] = qc;
+    }
+    ORR_TRY(lane->ws_range_consts.reserve((2 * sizeof(double) + sizeof(orr::QueryConst)) * (size_t)range::kMaxQueries));
+    double *d_na = lane->ws_range_consts.as<double>(), *d_t = d_na + range::kMaxQueries;
+    orr::QueryConst *d_qc = reinterpret_cast<orr::QueryConst *>(d_t + range::kMaxQueries);
+    HIP_TRY(hipMemcpyAsync(d_na, h_na.data(), sizeof(double) * (size_t)nw, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_t, h_t.data(), sizeof(double) * (size_t)nw, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_qc, h_qc.data(), sizeof(orr::QueryConst) * (size_t)nw, hipMemcpyHostToDevice, s));
+    ORR_TRY(lane->ws_range_cnt.reserve(sizeof(uint32_t) * 2 * (size_t)range::kMaxQueries));
+    uint32_t *d_cnt = lane->ws_range_cnt.as<uint32_t>(), *d_lcnt = d_cnt + range::kMaxQueries;
+
+    const int64_t pair_cap = lane->opt_range_pair_cap;
+    double screen_pairs = 0.0, host_pairs = 0.0;
+    std::vector<range::ListEntry> list;
+    // the lists of walked queries [p0, p0 + nq) (lcap entries each, counts h_lcnt) read back and decided
+    auto finish = [&](int32_t p0, int32_t nq, uint32_t lcap, const uint32_t *h_lcnt) -> int {
+        for (int32_t i = 0; i < nq; ++i) {
+            const int32_t b = perm[(size_t)(p0 + i)];
+            list.resize(h_lcnt[i]);
+            if (!list.empty()) {
+                HIP_TRY(hipMemcpyAsync(list.data(), lane->ws_range_list.as<range::ListEntry>() + (size_t)i * lcap, sizeof(range::ListEntry) * list.size(), hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+            }
+            host_pairs += (double)list.size();
+            range_finish_query(list, norm_a[(size_t)b], a.min_cosine[b], a.max_hits, lane->row_base, o.hits[(size_t)b], o.total[(size_t)b]);
+        }
+        return ORR_OK;
+    };
+
+    // -- the exact form over the walked queries [p0, p0 + cnt_q), kMaxExactQ per walk
+    auto exact_form = [&](int32_t p0, int32_t cnt_q) -> int {
+        for (int32_t e0 = p0; e0 < p0 + cnt_q; e0 += orr::kMaxExactQ) {
+            const int32_t nq = std::min<int32_t>(orr::kMaxExactQ, p0 + cnt_q - e0);
+            ORR_TRY(lane->ws_range_dots.reserve(sizeof(double) * (size_t)nq * (size_t)n));
+            {
+                Timed t(lane, "range_dot_exact", 4.0 * (double)n * D + 8.0 * (double)nq * (double)n);
+                HIP_TRY(orr::launch_dot_exact(lane->d_emb, n, D, Qp + (size_t)e0 * D, nq, false, lane->ws_range_dots.as<double>(), n, s));
+            }
+            uint32_t h_lcnt[orr::kMaxExactQ] = {};
+            int64_t lcap = 0;
+            for (int attempt = 0;; ++attempt) {
+                // (a call that only counts any more stores nothing: lists of one entry)
+                lcap = o.limit ? 1 : range::buffer_cap(std::max(lane->range_buffer, lane->range_list_cap), range::kMaxPairCap);
+                ORR_TRY(lane->ws_range_list.reserve(sizeof(range::ListEntry) * (size_t)nq * (size_t)lcap));
+                HIP_TRY(hipMemsetAsync(d_lcnt, 0, sizeof(uint32_t) * (size_t)nq, s));
+                {
+                    Timed t(lane, "range_collect_dense", 8.0 * (double)nq * (double)n + 16.0 * (double)n);
+                    HIP_TRY(orr::launch_range_collect_dense(lane->ws_range_dots.as<double>(), n, nq, d_na + e0, lane->d_norm_b, lane->d_row_ids, n, allowed, d_t + e0,
+                                                            lane->ws_range_list.as<range::ListEntry>(), d_lcnt, (uint32_t)lcap, s));
+                }
+                HIP_TRY(hipMemcpyAsync(h_lcnt, d_lcnt, sizeof(uint32_t) * (size_t)nq, hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+                const uint32_t mx = *std::max_element(h_lcnt, h_lcnt + nq);
+                if ((int64_t)mx > pair_cap) o.limit = true;
+                if (o.limit || (int64_t)mx <= lcap) break;
+                if (attempt >= 3) return fail(ORR_EDEVICE, "orr_search_range_cosine: a hit list kept overflowing (%u pairs)", mx);
+                lane->range_list_cap = range::grown_cap((int64_t)mx, range::kMaxPairCap);     // the dots stand: only the ending runs again
+                if (profiled) lane->stats[(size_t)stat_slot(lane, "range_buffer_growths")].algo_bytes += 1.0;
+            }
+            if (o.limit) { for (int32_t i = 0; i < nq; ++i) o.total[(size_t)perm[(size_t)(e0 + i)]] = (int64_t)h_lcnt[i]; continue; }
+            ORR_TRY(finish(e0, nq, (uint32_t)lcap, h_lcnt));
+        }
+        return ORR_OK;
+    };
+
+    // -- the screen over the walked queries [0, ns): as many launch groups at a time as their buffers allow
+    for (int32_t b0 = 0; b0 < ns;) {
+        const int64_t cap = range::buffer_cap(lane->range_buffer);
+        const int64_t per_query = cap * (int64_t)(sizeof(orr::SelEntry) + sizeof(double) + sizeof(range::ListEntry));
+        const int32_t fit = (int32_t)std::max<int64_t>(range::kScreenQ, (((int64_t)2 << 30) / per_query) / range::kScreenQ * range::kScreenQ);
+        const int32_t nq = std::min<int32_t>(ns - b0, fit);
+        if (!o.limit) {
+            ORR_TRY(lane->ws_range_buf.reserve(sizeof(orr::SelEntry) * (size_t)nq * (size_t)cap));
+            ORR_TRY(lane->ws_range_bdot.reserve(sizeof(double) * (size_t)nq * (size_t)cap));
+            ORR_TRY(lane->ws_range_list.reserve(sizeof(range::ListEntry) * (size_t)nq * (size_t)cap));
+        } else {
+            ORR_TRY(lane->ws_range_buf.reserve(sizeof(orr::SelEntry) * (size_t)nq));
+        }
+        const uint32_t scap = o.limit ? 1u : (uint32_t)cap;            // (a call that only counts any more stores nothing: buffers of one entry)
+        HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(uint32_t) * 2 * (size_t)range::kMaxQueries, s));
+        for (int32_t g0 = 0; g0 < nq; g0 += range::kScreenQ) {
+            const int32_t gq = std::min<int32_t>(range::kScreenQ, nq - g0), p = b0 + g0;
+            Timed t(lane, "screen_gemv_i8_range", 1.0 * (double)n * D + 20.0 * (double)n + 2.0 * (double)gq * D);   // per row: scale, two relative norms, normB
+            HIP_TRY(orr::launch_screen_gemv_i8_range(q1 + (size_t)p * D, q2 + (size_t)p * D, lane->ws_q8s1.as<float>() + p, lane->ws_q8err.as<double>() + p, gq,
+                                                     lane->emb_i8.p, lane->i8_scale.as<float>(), lane->i8_rel_err.as<float>(), lane->i8_rel_hat.as<float>(),
+                                                     lane->d_norm_b, n, D, d_qc + p, d_t + p, allowed, d_cnt + g0,
+                                                     lane->ws_range_buf.as<orr::SelEntry>() + (size_t)g0 * scap, scap, s));
+        }
+        uint32_t h_cnt[range::kMaxQueries] = {}, h_lcnt[range::kMaxQueries] = {};
+        HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, sizeof(uint32_t) * (size_t)nq, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        const uint32_t mx = *std::max_element(h_cnt, h_cnt + nq);
+        if ((int64_t)mx > pair_cap) o.limit = true;
+        if (o.limit) {
+            for (int32_t i = 0; i < nq; ++i) o.total[(size_t)perm[(size_t)(b0 + i)]] = (int64_t)h_cnt[i];
+            b0 += nq;
+            continue;
+        }
+        if ((int64_t)mx > cap) {
+            if (cap >= range::kMaxBuffer) {            // more survivors than a buffer of the exact re-score holds: the exact form
+                ORR_TRY(exact_form(b0, nq));
+                b0 += nq;
+                continue;
+            }
+            lane->range_buffer = range::grown_cap((int64_t)mx, range::kMaxBuffer);
+            if (profiled) lane->stats[(size_t)stat_slot(lane, "range_buffer_growths")].algo_bytes += 1.0;
+            continue;                                  // the launch groups run again with the grown size
+        }
+        for (int32_t i = 0; i < nq; ++i) screen_pairs += (double)h_cnt[i];
+        {
+            Timed t(lane, "range_rescore_exact", (4.0 * D + 40.0) * (double)mx * nq);
+            HIP_TRY(orr::launch_rescore_buffer_exact(lane->d_emb, D, Qp + (size_t)b0 * D, nq, lane->d_norm_b, lane->d_created, orr::KwView{}, d_qc + b0, 0, d_cnt,
+                                                     (uint32_t)cap, lane->ws_range_buf.as<orr::SelEntry>(), lane->ws_range_bdot.as<double>(), s));
+        }
+        {
+            Timed t(lane, "range_collect", 64.0 * (double)mx * nq);
+            HIP_TRY(orr::launch_range_collect(lane->ws_range_buf.as<orr::SelEntry>(), lane->ws_range_bdot.as<double>(), d_cnt, (uint32_t)cap, nq, d_na + b0, lane->d_norm_b,
+                                              lane->d_row_ids, n, d_t + b0, lane->ws_range_list.as<range::ListEntry>(), d_lcnt, (uint32_t)cap, s));
+        }
+        HIP_TRY(hipMemcpyAsync(h_lcnt, d_lcnt, sizeof(uint32_t) * (size_t)nq, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        ORR_TRY(finish(b0, nq, (uint32_t)cap, h_lcnt));
+        b0 += nq;
+    }
+    ORR_TRY(exact_form(ns, nw - ns));
+    if (o.limit)                                       // the queries answered before the limit was met: their hits are an upper bound too
+        for (int32_t b = 0; b < B; ++b) o.hits[(size_t)b].clear();
+    if (profiled) {
+        lane->stats[(size_t)stat_slot(lane, "range_screen_pairs")].algo_bytes += 16.0 * screen_pairs;
+        lane->stats[(size_t)stat_slot(lane, "range_host_pairs")].algo_bytes += 32.0 * host_pairs;
+    }
+    return ORR_OK;
+}
+
+// ... and whatever it left on the stream is done before the caller's buffers go away
+static int range_on_lane(orr_index *lane, const RangeArgs &a, const orr_scope *within, RangeOut &o)
+{
+    int r = bind_device(lane);
+    if (r == ORR_OK) r = range_run(lane, a, within, o);
+    if (r != ORR_OK) (void)hipStreamSynchronize(lane->stream);
+    collect_events(lane);
+    return r;
+}
+
+// the argument errors of orr_search_range_cosine and its cluster form, in their order (range::first_invalid)
+static int range_arguments(const char *fn, const RangeArgs &a, const void *out_hits, const void *out_n, const void *out_total)
+{
+    int32_t bad = 0;
+    switch (range::first_invalid(a.B, a.dim, a.q == nullptr, a.min_cosine, a.max_hits, out_hits == nullptr, out_n == nullptr, out_total == nullptr, &bad)) {
+    case 0: return ORR_OK;
+    case 1: return fail(ORR_EINVAL, "%s: the batch size must be in 0 .. %d", fn, range::kMaxQueries);
+    case 2: return fail(ORR_EINVAL, "%s: dim is negative", fn);
+    case 3: return fail(ORR_EINVAL, "%s: max_hits is negative", fn);
+    case 4: return fail(ORR_EINVAL, "%s: q is NULL with dim %d", fn, a.dim);
+    case 5: return fail(ORR_EINVAL, "%s: min_cosine is NULL", fn);
+    case 6: return fail(ORR_EINVAL, "%s: out_hits is NULL with max_hits %d", fn, a.max_hits);
+    case 7: return fail(ORR_EINVAL, "%s: out_n is NULL", fn);
+    case 8: return fail(ORR_EINVAL, "%s: out_total is NULL", fn);
+    default: return fail(ORR_EINVAL, "%s: min_cosine[%d] is NaN", fn, bad);
+    }
+}
+
+// The outputs of a call from its (merged) answer.  With the limit met: no hits, and the upper bounds in out_total.
+static int range_write(const char *fn, const RangeArgs &a, const RangeOut &o, orr_range_hit *out_hits, int32_t *out_n, int64_t *out_total)
+{
+    for (int32_t b = 0; b < a.B; ++b) {
+        out_total[b] = o.total[(size_t)b];
+        out_n[b] = o.limit ? 0 : (int32_t)o.hits[(size_t)b].size();
+        for (size_t i = 0; !o.limit && i < o.hits[(size_t)b].size(); ++i) {
+            const range::Hit &h = o.hits[(size_t)b][i];
+            out_hits[(size_t)b * (size_t)a.max_hits + i] = orr_range_hit{h.row_id, h.order_key, h.cosine};
+        }
+    }
+    if (!o.limit) return ORR_OK;
+    int32_t worst = 0;
+    for (int32_t b = 1; b < a.B; ++b) if (o.total[(size_t)b] > o.total[(size_t)worst]) worst = b;
+    return fail(ORR_ELIMIT, "%s: query %d keeps %lld pairs for the exact re-score, more than range_pair_cap: tighten its min_cosine (out_total holds every query's count), "
+                            "or make a set with orr_scope_create_near", fn, worst, (long long)o.total[(size_t)worst]);
+}
+
+int orr_search_range_cosine(orr_index *idx, int32_t B, int32_t dim, const float *q, const double *min_cosine, const orr_scope *within,
+                            int32_t max_hits, orr_range_hit *out_hits, int32_t *out_n, int64_t *out_total)
+{
+    static const char *fn = "orr_search_range_cosine";
+    const RangeArgs a{B, dim, q, min_cosine, max_hits};
+    ORR_TRY(range_arguments(fn, a, out_hits, out_n, out_total));
+    if (!idx) return fail(ORR_EINVAL, "%s: null index", fn);
+    if (B == 0) return ORR_OK;
+    orr_index *own = nullptr;
+    if (within) ORR_TRY(scope_owner(within, idx, fn, &own));
+    Lane ln = acquire_lane(idx);                       // like a search: its own lane, concurrent with the others
+    orr_index *lane = ln.lane;
+    std::lock_guard<std::mutex> lock(lane->mu);
+    std::shared_lock<std::shared_mutex> rd;
+    if (within) rd = std::shared_lock<std::shared_mutex>(within->mu);
+    if (!lane->sealed) return fail(ORR_ESTATE, "%s: the index is not sealed", fn);
+    if (within) {
+        ORR_TRY(scope_owner(within, idx, fn, &own));
+        if (within->n_rows != lane->n_rows) return fail(ORR_ESTATE, "%s: the scope covers %lld rows, the handle %lld", fn, (long long)within->n_rows, (long long)lane->n_rows);
+    }
+    RangeOut o;
+    ORR_TRY(range_on_lane(lane, a, within, o));
+    return range_write(fn, a, o, out_hits, out_n, out_total);
+}
+
 int orr_search_shard_scoped(orr_index *idx, int32_t B, int32_t dim, const float *q, const uint8_t *terms_utf8,
                             const uint32_t *term_off, const uint32_t *query_term_off, int64_t now_ticks, int32_t kprime,
                             int64_t candidate_limit, int32_t topk, int64_t n_scope_ids, const int64_t *scope_ids,
@@ -7489,6 +7903,60 @@ int orr_cluster_search_batch_in_scopes(orr_cluster *c, int32_t B, int32_t dim, c
         if (own != c || scopes[g]->parts.size() != c->shards.size()) return fail(ORR_EINVAL, "%s: scopes[%d] belongs to another cluster", fn, g);
     }
     return cluster_grouped_search(c, fn, a, n_scopes, scopes, query_scope, out_rows, out_scores, out_counts);
+}
+
+// Every shard runs the single call at once, each on a lane of its own; the host merges the shards' lists by (cosine descending,
+// order_key ascending), sums the totals and cuts at max_hits.  The limit met on any shard is the call's: the upper bounds summed.
+int orr_cluster_search_range_cosine(orr_cluster *c, int32_t B, int32_t dim, const float *q_host, const double *min_cosine,
+                                    const orr_cluster_scope *within, int32_t max_hits, orr_range_hit *out_hits, int32_t *out_n, int64_t *out_total)
+{
+    static const char *fn = "orr_cluster_search_range_cosine";
+    const RangeArgs a{B, dim, q_host, min_cosine, max_hits};
+    ORR_TRY(range_arguments(fn, a, out_hits, out_n, out_total));
+    if (!c) return fail(ORR_EINVAL, "%s: null cluster", fn);
+    if (B == 0) return ORR_OK;
+    if (dim > 0 && is_device_pointer(q_host)) return fail(ORR_EINVAL, "%s: the query vectors must be in host memory (every shard's device reads them)", fn);
+    std::shared_lock<std::shared_mutex> lock(c->mu);   // like a search: beside the others; seal and destroy are exclusive
+    if (!c->sealed) return fail(ORR_ESTATE, "%s: the cluster is not sealed", fn);
+    auto scope_of_this_cluster = [&]() -> int {
+        orr_cluster *own = nullptr;
+        ORR_TRY(cluster_scope_owner(within, fn, &own));
+        if (own != c || within->parts.size() != c->shards.size()) return fail(ORR_EINVAL, "%s: the scope belongs to another cluster", fn);
+        return ORR_OK;
+    };
+    if (within) ORR_TRY(scope_of_this_cluster());
+    const int32_t G = (int32_t)c->shards.size();
+    std::vector<Lane> lanes;
+    acquire_cluster_lanes(c, lanes);
+    std::vector<std::shared_lock<std::shared_mutex>> held;     // every part shared, in ascending shard order
+    if (within) {
+        held.reserve((size_t)G);
+        for (int32_t g = 0; g < G; ++g) held.emplace_back(within->parts[(size_t)g]->mu);
+        ORR_TRY(scope_of_this_cluster());
+        ORR_TRY(cluster_scope_parts_alive(c, within, fn));
+    }
+    std::vector<RangeOut> outs((size_t)G);
+    ORR_TRY(for_each_shard(G, [&](int32_t g) -> int {
+        orr_index *lane = lanes[(size_t)g].lane;
+        std::lock_guard<std::mutex> l(lane->mu);
+        const orr_scope *part = within ? within->parts[(size_t)g] : nullptr;
+        if (part && part->n_rows != lane->n_rows)
+            return fail(ORR_ESTATE, "%s: the scope covers %lld rows of shard %d, the shard holds %lld", fn, (long long)part->n_rows, g, (long long)lane->n_rows);
+        return range_on_lane(lane, a, part, outs[(size_t)g]);
+    }));
+    RangeOut o;
+    o.hits.assign((size_t)B, {});
+    o.total.assign((size_t)B, 0);
+    for (const RangeOut &part : outs) o.limit = o.limit || part.limit;
+    for (int32_t b = 0; b < B; ++b) {
+        std::vector<const std::vector<range::Hit> *> lists;
+        for (const RangeOut &part : outs) {
+            o.total[(size_t)b] += part.total[(size_t)b];
+            lists.push_back(&part.hits[(size_t)b]);
+        }
+        if (!o.limit) o.hits[(size_t)b] = range::merge_lists(lists, max_hits);
+    }
+    return range_write(fn, a, o, out_hits, out_n, out_total);
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 #include "orr_scope_set_plan.h"
 #include "orr_scope_terms_plan.h"
 #include "orr_scope_near_plan.h"
+#include "orr_range_plan.h"
 
 #include <atomic>
 
@@ -513,5 +514,22 @@ hipError_t launch_scope_near(const float *E, int64_t n_rows, int32_t D, const fl
                              uint32_t *bm, int64_t words, hipStream_t s);
 // out[i] = norm_b[band[i].pos] for the n entries a walk listed.
 hipError_t launch_scope_near_band_norms(const scope_near::BandEntry *band, int64_t n, const double *norm_b, int64_t n_rows, double *out, hipStream_t s);
+
+// ---- cosine range search (orr_search_range_cosine; the rules are orr_range_plan.h's) ----------------------------------------
+// The screen: one launch of K2i's 128-row-unit form with the RANGE ending for nq = 1..kMaxI8ScreenQ queries (orr_screen.hip).
+hipError_t launch_screen_gemv_i8_range(const void *q1, const void *q2, const float *s1, const double *err2, int32_t nq, const void *tiled,
+                                       const float *scale, const float *rel_err, const float *rel_hat, const double *norm_b, int64_t n_rows,
+                                       int32_t D, const QueryConst *qc, const double *min_cosine, const uint32_t *allowed, uint32_t *cnt,
+                                       SelEntry *buf, uint32_t cap, hipStream_t s);
+// Behind launch_rescore_buffer_exact: every survivor buf[b][i], i < min(cnt[b], cap), of the nq queries with its exact dot
+// buf_dot[b][i]: the device's cosine (scope_near::cosine_of), range::device_keeps, and the kept pairs appended to list[b][..]
+// (list_cap entries per query, list_cnt [nq] zeroed by the caller counts every kept pair).
+hipError_t launch_range_collect(const SelEntry *buf, const double *buf_dot, const uint32_t *cnt, uint32_t cap, int32_t nq, const double *norm_a,
+                                const double *norm_b, const int64_t *row_ids, int64_t n_rows, const double *min_cosine,
+                                range::ListEntry *list, uint32_t *list_cnt, uint32_t list_cap, hipStream_t s);
+// The exact form: the same for EVERY allowed row from dense exact dots dots[q][r] (launch_dot_exact, stride dot_stride).
+hipError_t launch_range_collect_dense(const double *dots, int64_t dot_stride, int32_t nq, const double *norm_a, const double *norm_b,
+                                      const int64_t *row_ids, int64_t n_rows, const uint32_t *allowed, const double *min_cosine,
+                                      range::ListEntry *list, uint32_t *list_cnt, uint32_t list_cap, hipStream_t s);
 
 }  // namespace orr

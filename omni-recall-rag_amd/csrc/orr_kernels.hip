@@ -2358,4 +2358,83 @@ hipError_t launch_scope_near_band_norms(const scope_near::BandEntry *band, int64
     return hipGetLastError();
 }
 
+// ---- cosine range search (orr_search_range_cosine; the rules are orr_range_plan.h's) ----------------------------------------
+static_assert(range::kScreenQ == kMaxI8ScreenQ, "a launch group of the range screen is one launch of K2i");
+
+// One kept pair into its query's list: the slot from the list's counter (which counts every kept pair, stored or not), the
+// entry as two 16-byte vector stores.
+__device__ __forceinline__ void range_list_append(range::ListEntry *__restrict__ list, uint32_t *__restrict__ list_cnt, uint32_t list_cap,
+                                                  int64_t row_id, double dot, double nb, uint32_t pos)
+{
+    const uint32_t slot = atomicAdd(list_cnt, 1u);
+    if (slot >= list_cap) return;
+    uint4 *o = reinterpret_cast<uint4 *>(list + slot);
+    o[0] = make_uint4((uint32_t)row_id, (uint32_t)((unsigned long long)row_id >> 32), (uint32_t)__double2loint(dot), (uint32_t)__double2hiint(dot));
+    o[1] = make_uint4((uint32_t)__double2loint(nb), (uint32_t)__double2hiint(nb), pos, 0u);
+}
+
+// blockIdx.y = the query; the survivors of its buffer, grid-stride
+__global__ __launch_bounds__(256) void range_collect(const SelEntry *__restrict__ buf, const double *__restrict__ buf_dot, const uint32_t *__restrict__ cnt,
+                                                     uint32_t cap, const double *__restrict__ norm_a, const double *__restrict__ norm_b,
+                                                     const int64_t *__restrict__ row_ids, int64_t n_rows, const double *__restrict__ min_cosine,
+                                                     range::ListEntry *__restrict__ list, uint32_t *__restrict__ list_cnt, uint32_t list_cap)
+{
+    const int b = blockIdx.y;
+    const uint32_t n = cnt[b] < cap ? cnt[b] : cap;
+    const double na = norm_a[b], t = min_cosine[b];
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        const uint32_t pos = buf[(int64_t)b * cap + i].pos;
+        if ((int64_t)pos >= n_rows) continue;
+        const double dot = buf_dot[(int64_t)b * cap + i], nb = norm_b[pos];
+        if (range::device_keeps(scope_near::cosine_of(dot, na, nb), t))
+            range_list_append(list + (int64_t)b * list_cap, list_cnt + b, list_cap, row_ids[pos], dot, nb, pos);
+    }
+}
+
+hipError_t launch_range_collect(const SelEntry *buf, const double *buf_dot, const uint32_t *cnt, uint32_t cap, int32_t nq, const double *norm_a,
+                                const double *norm_b, const int64_t *row_ids, int64_t n_rows, const double *min_cosine,
+                                range::ListEntry *list, uint32_t *list_cnt, uint32_t list_cap, hipStream_t s)
+{
+    if (nq <= 0) return hipSuccess;
+    if (!buf || !buf_dot || !cnt || cap == 0 || !norm_a || !norm_b || !row_ids || n_rows < 0 || !min_cosine || !list || !list_cnt || list_cap == 0)
+        return hipErrorInvalidValue;
+    if (reinterpret_cast<uintptr_t>(list) & 15u) return hipErrorInvalidValue;                  // 16-byte stores
+    const unsigned blocks = (unsigned)std::min<uint32_t>((cap + 255u) / 256u, 1024u);
+    hipLaunchKernelGGL(range_collect, dim3(blocks, (unsigned)nq), dim3(256), 0, s, buf, buf_dot, cnt, cap, norm_a, norm_b, row_ids, n_rows, min_cosine,
+                       list, list_cnt, list_cap);
+    return hipGetLastError();
+}
+
+// One lane per row, grid-stride: the row's word of the allowed bitmap, its norm and id once, then the nq dense dots (consecutive
+// lanes, consecutive rows of dots[q]: contiguous loads).
+__global__ __launch_bounds__(256) void range_collect_dense(const double *__restrict__ dots, int64_t dot_stride, int32_t nq, const double *__restrict__ norm_a,
+                                                           const double *__restrict__ norm_b, const int64_t *__restrict__ row_ids, int64_t n_rows,
+                                                           const uint32_t *__restrict__ allowed, const double *__restrict__ min_cosine,
+                                                           range::ListEntry *__restrict__ list, uint32_t *__restrict__ list_cnt, uint32_t list_cap)
+{
+    for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < n_rows; row += (int64_t)gridDim.x * 256) {
+        if (!((allowed[row >> 5] >> (uint32_t)(row & 31)) & 1u)) continue;
+        const double nb = norm_b[row];
+        for (int32_t q = 0; q < nq; ++q) {
+            const double dot = dots[(int64_t)q * dot_stride + row];
+            if (range::device_keeps(scope_near::cosine_of(dot, norm_a[q], nb), min_cosine[q]))
+                range_list_append(list + (int64_t)q * list_cap, list_cnt + q, list_cap, row_ids[row], dot, nb, (uint32_t)row);
+        }
+    }
+}
+
+hipError_t launch_range_collect_dense(const double *dots, int64_t dot_stride, int32_t nq, const double *norm_a, const double *norm_b,
+                                      const int64_t *row_ids, int64_t n_rows, const uint32_t *allowed, const double *min_cosine,
+                                      range::ListEntry *list, uint32_t *list_cnt, uint32_t list_cap, hipStream_t s)
+{
+    if (nq <= 0 || n_rows <= 0) return hipSuccess;
+    if (nq > kMaxExactQ || !dots || dot_stride < n_rows || !norm_a || !norm_b || !row_ids || !allowed || !min_cosine || !list || !list_cnt || list_cap == 0)
+        return hipErrorInvalidValue;
+    if (reinterpret_cast<uintptr_t>(list) & 15u) return hipErrorInvalidValue;                  // 16-byte stores
+    const int64_t blocks = std::min<int64_t>((n_rows + 255) / 256, 2048);
+    hipLaunchKernelGGL(range_collect_dense, dim3((unsigned)blocks), dim3(256), 0, s, dots, dot_stride, nq, norm_a, norm_b, row_ids, n_rows, allowed,
+                       min_cosine, list, list_cnt, list_cap);
+    return hipGetLastError();
+}
+
 }  // namespace orr

@@ -1096,7 +1096,12 @@ struct I8Queries {
 // buf[b][64 l .. 64 l + 63], l = unit / 4, what buffer_to_lists would make of them -- no counters, no second launch.
 // DOTS (diagnostic, orr_index_screen_i8_stream_dots): no scoring tail -- the two raw int32 accumulators of every pair go to
 // the int32 array [NQ][2][n_rows] that epi.buf then points to; nothing else of R, Q.s1, Q.err2 or epi is read.
-template <int NQ, bool LOWER, int JR, bool LISTS = false, bool DOTS = false>
+// RANGE (orr_search_range_cosine; the rules are orr_range_plan.h's): the ending of a cosine range search -- no score, no row
+// constants, no keyword words, no recency.  A row whose bit in the `allowed` bitmap (epi.count_planes: one word per 32 rows,
+// the scope's bitmap or all rows without the deleted ones) is clear is passed over; for the others cos^ = dot^ / (sqrt(normA)
+// sqrt(normB)) with the reference's guards, and the pair is appended to epi.buf through epi.cnt / epi.cap, as the scoring
+// tail appends, unless cos^ + range::cos_bound stays below the query's threshold (epi.tau[b]: the BITS of min_cosine[b]).
+template <int NQ, bool LOWER, int JR, bool LISTS = false, bool DOTS = false, bool RANGE = false>
 __global__ __launch_bounds__(256, 2) void screen_gemv_i8_kernel(I8Queries Q, int32_t D, I8Rows R, int64_t n_units, int64_t n_rows,
                                                                 FusedEpilogue epi)
 {
@@ -1104,6 +1109,7 @@ __global__ __launch_bounds__(256, 2) void screen_gemv_i8_kernel(I8Queries Q, int
     __shared__ SelEntry own[LISTS ? NQ : 1][kSelWidth];
     static_assert(!LISTS || JR == 1, "LISTS: one 16-row group per wave");
     static_assert(!DOTS || !LISTS, "DOTS: stores only");
+    static_assert(!RANGE || (!DOTS && !LISTS && !LOWER), "RANGE: an ending of its own, an upper bound");
     constexpr int KS = 8 / JR;                     // k-tiles per stage
     constexpr int UPT = 16 / JR;                   // units per 256-row tile
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1177,6 +1183,28 @@ __global__ __launch_bounds__(256, 2) void screen_gemv_i8_kernel(I8Queries Q, int
                     ORR_PICK_I12(i1, i2, b)
                     S[(int64_t)(2 * b) * n_rows + row] = i1;
                     S[(int64_t)(2 * b + 1) * n_rows + row] = i2;
+                }
+                continue;
+            }
+            if (RANGE) {
+                if (!((epi.count_planes[row >> 5] >> (uint32_t)(row & 31)) & 1u)) continue;
+                const double nb = R.norm_b[row];
+                const double isb = nb > 0.0 ? 1.0 / sqrt(nb) : 0.0;          // (:84-85: a norm <= 0 gives cosine 0)
+                const double se = (double)R.scale[row], re = (double)R.rel_err[row], rh = (double)R.rel_hat[row];
+#pragma unroll
+                for (int b = 0; b < NQ; ++b) {
+                    ORR_PICK_I12(i1, i2, b)
+                    const double isa = epi.qc[b].inv_sqrt_na;
+                    const double dot = se * (double)Q.s1[b] * ((double)i1 + (double)i2 * (1.0 / 254.0));
+                    if (range::screen_keeps(dot * isa * isb, range::cos_bound(re, rh, sqrt(Q.err2[b]) * isa),
+                                            __longlong_as_double((long long)epi.tau[b]))) {
+                        const uint32_t slot = atomicAdd(&epi.cnt[b], 1u);
+                        if (slot < epi.cap) {
+                            SelEntry en;
+                            en.key = 0ull; en.pos = (uint32_t)row; en.pad = 0;
+                            epi.buf[(int64_t)b * epi.cap + slot] = en;
+                        }
+                    }
                 }
                 continue;
             }
@@ -1855,6 +1883,42 @@ hipError_t launch_screen_gemv_i8_dots(const void *q12, int32_t B, const void *ti
     default: ORR_I8D(4); break;
     }
 #undef ORR_I8D
+    return hipGetLastError();
+}
+
+// The screen of a cosine range search (orr_search_range_cosine): ONE launch of the 128-row-unit form for nq = 1..kMaxI8ScreenQ
+// queries with the RANGE ending -- K loop, staging, reduction and grid are launch_screen_gemv_i8's.  q1 / q2: the queries' two
+// int8 levels [nq][D] (launch_i8_queries; the levels of a larger batch are taken apart by the caller), s1 / err2 / qc /
+// min_cosine [nq]; allowed: one word per 32 rows, at least ceil(n_rows / 32) of them; cnt [nq] zeroed by the caller,
+// buf [nq][cap].  Only qc[b].inv_sqrt_na is read.
+hipError_t launch_screen_gemv_i8_range(const void *q1, const void *q2, const float *s1, const double *err2, int32_t nq, const void *tiled,
+                                       const float *scale, const float *rel_err, const float *rel_hat, const double *norm_b, int64_t n_rows,
+                                       int32_t D, const QueryConst *qc, const double *min_cosine, const uint32_t *allowed, uint32_t *cnt,
+                                       SelEntry *buf, uint32_t cap, hipStream_t s)
+{
+    if (nq <= 0 || n_rows <= 0) return hipSuccess;
+    if (nq > kMaxI8ScreenQ || D <= 0 || D % 128 != 0 || cap == 0) return hipErrorInvalidValue;
+    if (!q1 || !q2 || !s1 || !err2 || !tiled || !scale || !rel_err || !rel_hat || !norm_b || !qc || !min_cosine || !allowed || !cnt || !buf)
+        return hipErrorInvalidValue;
+    int64_t n_units, blocks;
+    screen_gemv_i8_grid(n_rows, false, n_units, blocks);
+    const size_t lds = 2 * (size_t)nq * (size_t)D;
+    if (lds > 65536) return hipErrorInvalidValue;
+    I8Rows Rd{static_cast<const int8_t *>(tiled), scale, rel_err, rel_hat, norm_b, nullptr, 0};
+    I8Queries Qd{static_cast<const int8_t *>(q1), static_cast<const int8_t *>(q2), s1, err2};
+    FusedEpilogue e2{};
+    e2.qc = qc;
+    e2.tau = reinterpret_cast<const unsigned long long *>(min_cosine);
+    e2.count_planes = allowed;
+    e2.cnt = cnt; e2.buf = buf; e2.cap = cap;
+#define ORR_I8R(NQ) hipLaunchKernelGGL((screen_gemv_i8_kernel<NQ, false, 8, false, false, true>), dim3((unsigned)blocks), dim3(256), lds, s, Qd, D, Rd, n_units, n_rows, e2)
+    switch (nq) {
+    case 1: ORR_I8R(1); break;
+    case 2: ORR_I8R(2); break;
+    case 3: ORR_I8R(3); break;
+    default: ORR_I8R(4); break;
+    }
+#undef ORR_I8R
     return hipGetLastError();
 }
 

@@ -96,6 +96,48 @@ def _near_args(probes, mode: str, device_ok: bool):
     return int(p.shape[0]), int(p.shape[1]), p, modes[mode]
 
 
+RANGE_HIT_DTYPE = np.dtype([("row_id", "<i8"), ("order_key", "<i8"), ("cosine", "<f8")])
+assert RANGE_HIT_DTYPE.itemsize == 24
+
+
+def _range_cosine(call, handle, qvecs, min_cosine, max_hits: int, within, device_ok: bool):
+    """orr_search_range_cosine / orr_cluster_search_range_cosine through `call`.  Returns (row_ids, order_keys, cosines, totals):
+    three lists of per-query arrays, best hit first, and totals [B] int64, the exact number of hits of each query.  Over the
+    pair limit the OrrError (code ORR_ELIMIT) carries `totals`: every query's upper bound."""
+    t = np.ascontiguousarray(min_cosine, dtype=np.float64).reshape(-1)
+    B = int(t.shape[0])
+    if qvecs is None:
+        dim, q = 0, None
+    else:
+        if _is_torch(qvecs) and device_ok:
+            import torch
+            q = qvecs.to(torch.float32).contiguous()
+        else:
+            q = np.ascontiguousarray(qvecs, dtype=np.float32)
+        if q.ndim == 1 and B == 1:
+            q = q.reshape(1, -1)
+        if q.ndim != 2 or int(q.shape[0]) != B:
+            raise ValueError(f"qvecs: [{B}, dim] for {B} thresholds")
+        dim = int(q.shape[1])
+    k = int(max_hits)
+    hits = np.zeros((B, max(k, 0)), dtype=RANGE_HIT_DTYPE)
+    n = np.zeros(max(B, 1), dtype=np.int32)
+    totals = np.zeros(max(B, 1), dtype=np.int64)
+    status = call(handle, B, dim, _ptr(q) if dim else None, _ptr(t) if B else None, within._h if within is not None else None, k,
+                  _ptr(hits) if k > 0 and B else None, _ptr(n), _ptr(totals))
+    totals = totals[:B]
+    if status != N.ORR_OK:
+        try:
+            N.check(status)
+        except N.OrrError as e:
+            e.totals = totals
+            raise
+    rows = [hits[b, :n[b]]["row_id"].copy() for b in range(B)]
+    keys = [hits[b, :n[b]]["order_key"].copy() for b in range(B)]
+    cos = [hits[b, :n[b]]["cosine"].copy() for b in range(B)]
+    return rows, keys, cos, totals
+
+
 class RecallScope:
     """A scope handle (orr_scope): a set of ROWS of one sealed shard, resolved once and resident on its device.  It follows
     its rows through delete_rows, compact and insert_rows of the shard; rows inserted later are in no scope until add_ids
@@ -526,6 +568,14 @@ class RecallIndex:
         N.check(N.hip.orr_scope_create_near(self._h, n, dim, _ptr(p) if n and dim else None, float(min_cosine), m, C.byref(h)))
         return RecallScope(h, self)
 
+    def range_cosine(self, qvecs, min_cosine, max_hits: int, within: Optional[RecallScope] = None):
+        """orr_search_range_cosine: for each query EVERY live row (of `within`, when given) whose reference cosine to it is >=
+        its own min_cosine[b], with that cosine.  qvecs: [B, dim] float32, numpy or a torch tensor on the device, at most 64;
+        min_cosine: B thresholds.  Returns (row_ids, order_keys, cosines, totals): per-query arrays of the best max_hits hits,
+        cosine descending then candidate position, and totals [B], the exact number of hits.  OrrError with code ORR_ELIMIT
+        (its `totals`: every query's upper bound) when a query is too unselective for "range_pair_cap"."""
+        return _range_cosine(N.hip.orr_search_range_cosine, self._h, qvecs, min_cosine, max_hits, within, True)
+
     def search_in_scope(self, qvecs, queries_terms, now_ticks: int, topk: int, scope: RecallScope, candidate_limit: int = 300):
         """orr_search_batch_in_scope: search_masked with the scope taken from a handle -- nothing is resolved per call.
         Returns (rows [B,k] int64, scores [B,k] float64, counts [B] int32)."""
@@ -900,6 +950,11 @@ class RecallCluster:
         h = C.c_void_p()
         N.check(N.hip.orr_cluster_scope_create_near(self._h, n, dim, _ptr(p) if n and dim else None, float(min_cosine), m, C.byref(h)))
         return RecallClusterScope(h, self)
+
+    def range_cosine(self, qvecs, min_cosine, max_hits: int, within: Optional[RecallClusterScope] = None):
+        """orr_cluster_search_range_cosine: RecallIndex.range_cosine over every shard, merged -- the answers of one index
+        holding all the rows.  qvecs in host memory (numpy)."""
+        return _range_cosine(N.hip.orr_cluster_search_range_cosine, self._h, qvecs, min_cosine, max_hits, within, False)
 
     def search_in_scope(self, qvecs, queries_terms, now_ticks: int, topk: int, scope: RecallClusterScope, candidate_limit: int = 300):
         """orr_cluster_search_batch_in_scope: search_masked with the scope taken from a handle -- no id list goes to the
