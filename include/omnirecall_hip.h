@@ -637,6 +637,25 @@ int orr_search_range_cosine(orr_index *idx, int32_t B, int32_t dim, const float 
                             int32_t max_hits, orr_range_hit *out_hits /* host [B][max_hits] */,
                             int32_t *out_n /* host [B] */, int64_t *out_total /* host [B] */);
 
+/* orr_search_range_cosine for a BULK of queries: the same contract word for word, except that B is 0 .. 1024 -- the hits, their
+ * order, the cosine bits, order_key and out_total, the guards, ORR_ELIMIT with its upper bounds, lanes, views and scopes, and the
+ * argument errors in their order with the first rule reading 0 .. 1024.  For any batch the answer is exactly what
+ * orr_search_range_cosine returns on the same queries in slices of 64 (an upload's hundreds of overlapping chunks against the
+ * shard: the near-duplicate question at ingest in one call).
+ * What differs is the screen.  Where dim % 128 == 0 and dim >= 512, the int8 shadow is in place and at least 65 queries of the
+ * call are screened at all, they go through ONE pass of the int8 screening GEMM per launch group (kernel statistics:
+ * screen_tile16_range, in front of it range_i8_tile_queries) with the bound for the query's first int8 level, instead of one
+ * stream over the shard per four queries; a launch group is as many queries as their survivors' buffers fit in 2 GiB.  Every
+ * other query goes where orr_search_range_cosine sends it: the stream in groups of four, or the exact form; with B <= 64 the
+ * call launches what orr_search_range_cosine launches.  Option "range_gemm" (orr_index_set_option, sticky, this call only):
+ * 0 the rule above (default), 1 the GEMM wherever its shape applies, from one query up, 2 never (for tests and measurements:
+ * the answers are the same).  "range_form" 2 still sends everything to the exact form; "range_pair_cap" and "range_buffer" work
+ * as they do there. */
+int orr_search_range_cosine_bulk(orr_index *idx, int32_t B, int32_t dim, const float *q /* host or device, [B][dim] */,
+                                 const double *min_cosine /* host [B] */, const orr_scope *within /* or NULL: every live row */,
+                                 int32_t max_hits, orr_range_hit *out_hits /* host [B][max_hits] */,
+                                 int32_t *out_n /* host [B] */, int64_t *out_total /* host [B] */);
+
 /* orr_search_shard_masked with the scope taken from a handle: the record form of orr_search_batch_in_scope, the shard half of
  * orr_cluster_search_batch_in_scope.  The contract is orr_search_shard_masked's, unchanged: [B][kprime+1] records and the
  * trailer, `pass` 0 / 1, topk, candidate_limit GLOBAL with scope_before the scope's live rows on the shards in front (read
@@ -687,7 +706,7 @@ int orr_search_shard_in_scopes(orr_index *idx, int32_t B, int32_t dim, const flo
  *                    same; the option exists for measurements and tests.
  *   "mask_part_rows" 1..4,194,240 (default 4,194,240): the most scoped rows one part of orr_search_batch_masked's list
  *                    path takes.  Smaller values exist so that tests reach the multi-part path on a small shard.
- *   "range_pair_cap", "range_buffer", "range_form"   see orr_search_range_cosine.
+ *   "range_pair_cap", "range_buffer", "range_form"   see orr_search_range_cosine; "range_gemm": orr_search_range_cosine_bulk.
  *   "shard_pass"     0/1/2 (default 0): which pass orr_search_shard runs -- 0 the library's choice, 1 the unfused
  *                    batched pass, 2 the reference-arithmetic pass over every row.  The caller of
  *                    orr_merge_candidates sets 2 for the repeat of a batch some query of which could not be certified.
@@ -952,6 +971,13 @@ int orr_cluster_search_batch_in_scopes(orr_cluster *c, int32_t B, int32_t dim, c
  * (ORR_EINVAL: every shard's device reads it); ORR_ESTATE for an unsealed cluster or an orphaned scope; ORR_EINVAL for a scope
  * of another cluster. */
 int orr_cluster_search_range_cosine(orr_cluster *c, int32_t B, int32_t dim, const float *q_host, const double *min_cosine /* host [B] */,
+                                    const orr_cluster_scope *within /* or NULL */, int32_t max_hits, orr_range_hit *out_hits,
+                                    int32_t *out_n, int64_t *out_total);
+
+/* orr_search_range_cosine_bulk over a cluster: orr_cluster_search_range_cosine with B 0 .. 1024, every shard running the bulk
+ * call at once on its own lane; the lists are merged and the totals summed as there, and any shard's ORR_ELIMIT is the call's.
+ * "range_gemm" is each shard index's own option. */
+int orr_cluster_search_range_cosine_bulk(orr_cluster *c, int32_t B, int32_t dim, const float *q_host, const double *min_cosine /* host [B] */,
                                     const orr_cluster_scope *within /* or NULL */, int32_t max_hits, orr_range_hit *out_hits,
                                     int32_t *out_n, int64_t *out_total);
 

@@ -120,6 +120,8 @@ hip.orr_search_batch_in_scopes.restype = C.c_int
 hip.orr_search_batch_in_scopes.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp]
 hip.orr_search_range_cosine.restype = C.c_int
 hip.orr_search_range_cosine.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp]
+hip.orr_search_range_cosine_bulk.restype = C.c_int
+hip.orr_search_range_cosine_bulk.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp]
 hip.orr_search_shard_in_scope.restype = C.c_int
 hip.orr_search_shard_in_scope.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, _vp, _i64, _vp]
 hip.orr_search_shard_in_scopes.restype = C.c_int
@@ -218,6 +220,8 @@ hip.orr_cluster_search_batch_in_scopes.restype = C.c_int
 hip.orr_cluster_search_batch_in_scopes.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp]
 hip.orr_cluster_search_range_cosine.restype = C.c_int
 hip.orr_cluster_search_range_cosine.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp]
+hip.orr_cluster_search_range_cosine_bulk.restype = C.c_int
+hip.orr_cluster_search_range_cosine_bulk.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp]
 
 host.orrh_is_blank.restype = _i32
 host.orrh_is_blank.argtypes = [C.c_char_p, _i64]
@@ -302,10 +306,10 @@ EXPORTED_HIP_SYMBOLS = [
     "orr_cluster_create", "orr_cluster_destroy", "orr_cluster_shards", "orr_cluster_shard", "orr_cluster_seal", "orr_cluster_rows",
     "orr_cluster_search_batch", "orr_cluster_search_batch_scoped", "orr_cluster_search_batch_masked", "orr_cluster_search_stats", "orr_cluster_set_option",
     "orr_scope_create", "orr_scope_create_ticks", "orr_scope_create_terms", "orr_scope_create_near", "orr_scope_add_ids", "orr_scope_combine", "orr_scope_rows", "orr_scope_row_ids", "orr_scope_destroy",
-    "orr_search_batch_in_scope", "orr_search_batch_in_scopes", "orr_search_shard_in_scope", "orr_search_shard_in_scopes", "orr_search_range_cosine",
+    "orr_search_batch_in_scope", "orr_search_batch_in_scopes", "orr_search_shard_in_scope", "orr_search_shard_in_scopes", "orr_search_range_cosine", "orr_search_range_cosine_bulk",
     "orr_cluster_scope_create", "orr_cluster_scope_create_ticks", "orr_cluster_scope_create_terms", "orr_cluster_scope_create_near", "orr_cluster_scope_add_ids", "orr_cluster_scope_combine",
     "orr_cluster_scope_rows", "orr_cluster_scope_row_ids", "orr_cluster_scope_shard", "orr_cluster_scope_destroy", "orr_cluster_search_batch_in_scope",
-    "orr_cluster_search_batch_in_scopes", "orr_cluster_search_range_cosine",
+    "orr_cluster_search_batch_in_scopes", "orr_cluster_search_range_cosine", "orr_cluster_search_range_cosine_bulk",
 ]
 EXPORTED_HOST_SYMBOLS = ["orrh_is_blank", "orrh_lower_invariant", "orrh_query_terms", "orrh_build_snippet",
                          "orrh_round4", "orrh_has_sufficient_evidence", "orrh_format_score_f4", "orrh_last_error", "orrh_store_create", "orrh_store_destroy",

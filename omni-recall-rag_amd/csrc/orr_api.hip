@@ -41,6 +41,7 @@
 #include "orr_scope_set_plan.h"
 #include "orr_scope_terms_plan.h"
 #include "orr_scope_near_plan.h"
+#include "orr_range_bulk_plan.h"
 #include "orr_cluster_handle_plan.h"
 #include "orr_cluster_group_plan.h"
 #include "orr_cluster_scope_plan.h"
@@ -235,7 +236,8 @@ struct orr_index {
     // cosine range search (orr_search_range_cosine), a lane's: the allowed rows of a call without a scope; the queries as given
     // and in their walked order; their exact norms; per walked query norm, threshold and QueryConst; the survivors' and the
     // lists' counters; the survivors' buffers with their exact dots; the lists; the exact form's dense dots
-    DevBuf ws_range_allowed, ws_range_q, ws_range_qp, ws_range_norm, ws_range_consts, ws_range_cnt, ws_range_buf, ws_range_bdot, ws_range_list, ws_range_dots;
+    DevBuf ws_range_allowed, ws_range_q, ws_range_qp, ws_range_norm, ws_range_consts, ws_range_cnt, ws_range_buf, ws_range_bdot, ws_range_list, ws_range_dots, ws_range_args;
+    int opt_range_gemm = range_bulk::Auto;                 // "range_gemm" (orr_search_range_cosine_bulk): 0 the GEMM screen from 65 walked queries up, 1 wherever it applies, 2 never
     int opt_range_form = range::Auto;                      // "range_form": 0 the screen where it applies, 1 the same, 2 the exact form only
     int64_t opt_range_pair_cap = range::kDefaultPairCap;   // "range_pair_cap": kept pairs of one query beyond which the call is ORR_ELIMIT
     int64_t range_buffer = range::kDefaultBuffer;          // "range_buffer": entries per query of the survivors' buffers and the lists; grows to the measured count
@@ -755,7 +757,7 @@ void orr_index_destroy(orr_index *idx)
     idx->ws_scope_terms.release(); idx->pin_scope_terms.release();
     for (DevBuf *b : {&idx->ws_near_q, &idx->ws_near_norm, &idx->ws_near_band, &idx->ws_near_cnt, &idx->ws_near_rows}) b->release();
     for (DevBuf *b : {&idx->ws_range_allowed, &idx->ws_range_q, &idx->ws_range_qp, &idx->ws_range_norm, &idx->ws_range_consts, &idx->ws_range_cnt,
-                      &idx->ws_range_buf, &idx->ws_range_bdot, &idx->ws_range_list, &idx->ws_range_dots}) b->release();
+                      &idx->ws_range_buf, &idx->ws_range_bdot, &idx->ws_range_list, &idx->ws_range_dots, &idx->ws_range_args}) b->release();
     for (DevBuf *b : {&idx->ws_mask_bm, &idx->ws_mask_chunks, &idx->ws_mask_cnt, &idx->ws_mask_meta}) b->release();
     idx->pin_mask.release();
     for (DevBuf *b : {&idx->ws_group_bm, &idx->ws_group_chunks, &idx->ws_group_meta}) b->release();
@@ -2008,7 +2010,7 @@ static void copy_options(const orr_index *from, orr_index *to)
     to->kw_hits_cap = from->kw_hits_cap; to->dead_before = from->dead_before;
     to->opt_mask_screen = from->opt_mask_screen; to->opt_mask_part_rows = from->opt_mask_part_rows;
     to->near_band_cap = from->near_band_cap;
-    to->opt_range_form = from->opt_range_form; to->opt_range_pair_cap = from->opt_range_pair_cap;
+    to->opt_range_form = from->opt_range_form; to->opt_range_gemm = from->opt_range_gemm; to->opt_range_pair_cap = from->opt_range_pair_cap;
     to->range_buffer = from->range_buffer; to->range_list_cap = from->range_list_cap;
 }
 
@@ -2064,6 +2066,9 @@ int orr_index_set_option(orr_index *idx, const char *name, int64_t value)
         if (!range::buffer_valid(value)) return fail(ORR_EINVAL, "orr_index_set_option: range_buffer must be in 1 .. %lld", (long long)range::kMaxBuffer);
         idx->range_buffer = value;
         idx->range_list_cap = 0;
+    } else if (strcmp(name, "range_gemm") == 0) {
+        if (!range_bulk::gemm_valid(value)) return fail(ORR_EINVAL, "orr_index_set_option: range_gemm takes 0, 1 or 2");
+        idx->opt_range_gemm = (int)value;
     } else if (strcmp(name, "range_form") == 0) {
         if (!range::form_valid(value)) return fail(ORR_EINVAL, "orr_index_set_option: range_form takes 0, 1 or 2");
         idx->opt_range_form = (int)value;
@@ -6218,6 +6223,8 @@ struct RangeArgs {
     const float *q;
     const double *min_cosine;
     int32_t max_hits;
+    bool bulk = false;                                 // orr_search_range_cosine_bulk: up to range_bulk::kMaxQueries queries, the GEMM screen where its rules send them
+    const char *fn = "orr_search_range_cosine";
 };
 
 // One shard's answer: per query its best max_hits hits in order and the exact number of hits -- or, with `limit`, no hits
@@ -6254,8 +6261,9 @@ static void range_finish_query(const std::vector<range::ListEntry> &list, double
 //   3. every query gets its form: AT ZERO (a foreign dim, a norm <= 0: every cosine is 0, no row is walked), the SCREEN (the int8
 //      shadow, dim % 128 == 0, a finite quantisation error, "range_form" not 2) or the EXACT form; the walked queries are put
 //      in that order (a batch that is in it already is used where it lies);
-//   4. the screen, kScreenQ queries per launch: K2i with the RANGE ending -> survivors' buffers -> launch_rescore_buffer_exact
-//      -> range_collect -> one list per query;
+//   4. the screen -- the stream, kScreenQ queries per launch: K2i with the RANGE ending; or, for a bulk call whose walked SCREEN
+//      queries range_bulk::gemm_takes, the int8 screening GEMM with the RANGE ending, one launch per group
+//      (orr_range_bulk_plan.h) -- -> survivors' buffers -> launch_rescore_buffer_exact -> range_collect -> one list per query;
 //   5. the exact form, kMaxExactQ queries per walk: launch_dot_exact over all rows -> range_collect_dense -> the same lists;
 //   6. the host decides every listed pair (range_finish_query).
 // A buffer that was too short grows (range::grown_cap) and its launches run again; a query whose kept pairs exceed
@@ -6276,7 +6284,7 @@ static int range_run(orr_index *lane, const RangeArgs &a, const orr_scope *withi
     const int64_t words = ((n + 31) / 32 + 3) / 4 * 4;
     const uint32_t *allowed = nullptr;
     if (within) {
-        if (within->words != words) return fail(ORR_ESTATE, "orr_search_range_cosine: the scope's bitmap has %lld words, the shard's %lld", (long long)within->words, (long long)words);
+        if (within->words != words) return fail(ORR_ESTATE, "%s: the scope's bitmap has %lld words, the shard's %lld", a.fn, (long long)within->words, (long long)words);
         allowed = within->bm;
     } else {
         ORR_TRY(lane->ws_range_allowed.reserve(sizeof(uint32_t) * (size_t)words));
@@ -6295,14 +6303,14 @@ static int range_run(orr_index *lane, const RangeArgs &a, const orr_scope *withi
     bool screen_ok = false;
     if (!foreign) {
         ORR_TRY(lane->ws_range_q.reserve(sizeof(float) * (size_t)B * (size_t)D));
-        ORR_TRY(lane->ws_range_norm.reserve(sizeof(double) * (size_t)range::kMaxQueries));
+        ORR_TRY(lane->ws_range_norm.reserve(sizeof(double) * (size_t)B));
         HIP_TRY(hipMemcpyAsync(lane->ws_range_q.p, a.q, sizeof(float) * (size_t)B * (size_t)D, hipMemcpyDefault, s));
         {
             Timed t(lane, "range_query_norms", (4.0 * D + 8.0) * B);
             HIP_TRY(orr::launch_dot_exact(lane->ws_range_q.as<float>(), B, D, nullptr, 1, true, lane->ws_range_norm.as<double>(), B, s));
         }
         HIP_TRY(hipMemcpyAsync(norm_a.data(), lane->ws_range_norm.p, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, s));
-        if (lane->opt_range_form != range::Exact && D % 128 == 0 && 2 * (size_t)range::kScreenQ * (size_t)D <= 65536) {
+        if (lane->opt_range_form != range::Exact && range_bulk::stream_shape(D)) {
             ORR_TRY(ensure_i8_shadow(lane));           // directly: the screen runs on a shard of any size
             if (lane->is_view && !lane->i8_ready && lane->parent) {
                 // a lane made before its index had the shadow borrows it now -- when the index's own lane is idle; else the
@@ -6321,7 +6329,8 @@ static int range_run(orr_index *lane, const RangeArgs &a, const orr_scope *withi
             ORR_TRY(lane->ws_q8err.reserve(2 * sizeof(double) * (size_t)B));
             {
                 Timed t(lane, "range_i8_queries", 6.0 * (double)B * D);
-                HIP_TRY(orr::launch_i8_queries(lane->ws_range_q.as<float>(), B, D, lane->ws_q8.p, lane->ws_q8s1.as<float>(), lane->ws_q8err.as<double>(), s, nullptr));
+                HIP_TRY(orr::launch_i8_queries(lane->ws_range_q.as<float>(), B, D, lane->ws_q8.p, lane->ws_q8s1.as<float>(), lane->ws_q8err.as<double>(), s,
+                                               lane->ws_q8err.as<double>() + B));
             }
             HIP_TRY(hipMemcpyAsync(err2.data(), lane->ws_q8err.p, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, s));
         }
@@ -6384,7 +6393,7 @@ static int range_run(orr_index *lane, const RangeArgs &a, const orr_scope *withi
         Qp = lane->ws_range_qp.as<float>();
         if (ns > 0) {
             Timed t(lane, "range_i8_queries", 6.0 * (double)ns * D);
-            HIP_TRY(orr::launch_i8_queries(Qp, ns, D, lane->ws_q8.p, lane->ws_q8s1.as<float>(), lane->ws_q8err.as<double>(), s, nullptr));
+            HIP_TRY(orr::launch_i8_queries(Qp, ns, D, lane->ws_q8.p, lane->ws_q8s1.as<float>(), lane->ws_q8err.as<double>(), s, lane->ws_q8err.as<double>() + B));
         }
         if (ns > 0) q2 = q1 + (size_t)ns * (size_t)D;
     }
@@ -6400,14 +6409,24 @@ static int range_run(orr_index *lane, const RangeArgs &a, const orr_scope *withi
         qc.use_cos = 1;
         h_qc[(size_t)p] = qc;
     }
-    ORR_TRY(lane->ws_range_consts.reserve((2 * sizeof(double) + sizeof(orr::QueryConst)) * (size_t)range::kMaxQueries));
-    double *d_na = lane->ws_range_consts.as<double>(), *d_t = d_na + range::kMaxQueries;
-    orr::QueryConst *d_qc = reinterpret_cast<orr::QueryConst *>(d_t + range::kMaxQueries);
+    ORR_TRY(lane->ws_range_consts.reserve((2 * sizeof(double) + sizeof(orr::QueryConst)) * (size_t)nw));
+    double *d_na = lane->ws_range_consts.as<double>(), *d_t = d_na + nw;
+    orr::QueryConst *d_qc = reinterpret_cast<orr::QueryConst *>(d_t + nw);
     HIP_TRY(hipMemcpyAsync(d_na, h_na.data(), sizeof(double) * (size_t)nw, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_t, h_t.data(), sizeof(double) * (size_t)nw, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_qc, h_qc.data(), sizeof(orr::QueryConst) * (size_t)nw, hipMemcpyHostToDevice, s));
-    ORR_TRY(lane->ws_range_cnt.reserve(sizeof(uint32_t) * 2 * (size_t)range::kMaxQueries));
-    uint32_t *d_cnt = lane->ws_range_cnt.as<uint32_t>(), *d_lcnt = d_cnt + range::kMaxQueries;
+    ORR_TRY(lane->ws_range_cnt.reserve(sizeof(uint32_t) * 2 * (size_t)nw));
+    uint32_t *d_cnt = lane->ws_range_cnt.as<uint32_t>(), *d_lcnt = d_cnt + nw;
+    // the screen of the walked SCREEN queries (orr_range_bulk_plan.h): the GEMM reads the tiled image of their first int8 level
+    const bool gemm = range_bulk::gemm_takes(D, ns, lane->opt_range_gemm, a.bulk);
+    if (gemm) {
+        ORR_TRY(lane->ws_qtiled.reserve(orr::i8_tiled_bytes(ns, D)));
+        ORR_TRY(lane->ws_tickets.reserve(sizeof(uint32_t) * 8 * 16));
+        ORR_TRY(lane->ws_range_args.reserve(orr::kRangeTile16ArgsBytes));
+        Timed t(lane, "range_i8_tile_queries", 2.0 * (double)ns * D);
+        HIP_TRY(orr::launch_i8_tile_queries(q1, ns, D, lane->ws_qtiled.p, s));
+    }
+    const double *d_err1 = lane->ws_q8err.as<double>() + B;
 
     const int64_t pair_cap = lane->opt_range_pair_cap;
     double screen_pairs = 0.0, host_pairs = 0.0;
@@ -6453,7 +6472,7 @@ static int range_run(orr_index *lane, const RangeArgs &a, const orr_scope *withi
                 const uint32_t mx = *std::max_element(h_lcnt, h_lcnt + nq);
                 if ((int64_t)mx > pair_cap) o.limit = true;
                 if (o.limit || (int64_t)mx <= lcap) break;
-                if (attempt >= 3) return fail(ORR_EDEVICE, "orr_search_range_cosine: a hit list kept overflowing (%u pairs)", mx);
+                if (attempt >= 3) return fail(ORR_EDEVICE, "%s: a hit list kept overflowing (%u pairs)", a.fn, mx);
                 lane->range_list_cap = range::grown_cap((int64_t)mx, range::kMaxPairCap);     // the dots stand: only the ending runs again
                 if (profiled) lane->stats[(size_t)stat_slot(lane, "range_buffer_growths")].algo_bytes += 1.0;
             }
@@ -6464,11 +6483,11 @@ static int range_run(orr_index *lane, const RangeArgs &a, const orr_scope *withi
     };
 
     // -- the screen over the walked queries [0, ns): as many launch groups at a time as their buffers allow
+    std::vector<uint32_t> h_cnt_v, h_lcnt_v;
     for (int32_t b0 = 0; b0 < ns;) {
         const int64_t cap = range::buffer_cap(lane->range_buffer);
-        const int64_t per_query = cap * (int64_t)(sizeof(orr::SelEntry) + sizeof(double) + sizeof(range::ListEntry));
-        const int32_t fit = (int32_t)std::max<int64_t>(range::kScreenQ, (((int64_t)2 << 30) / per_query) / range::kScreenQ * range::kScreenQ);
-        const int32_t nq = std::min<int32_t>(ns - b0, fit);
+        static_assert(range_bulk::kPairBytes == (int64_t)(sizeof(orr::SelEntry) + sizeof(double) + sizeof(range::ListEntry)), "what one kept pair takes");
+        const int32_t nq = std::min<int32_t>(ns - b0, range_bulk::group_queries(cap, gemm ? 1 : range::kScreenQ));
         if (!o.limit) {
             ORR_TRY(lane->ws_range_buf.reserve(sizeof(orr::SelEntry) * (size_t)nq * (size_t)cap));
             ORR_TRY(lane->ws_range_bdot.reserve(sizeof(double) * (size_t)nq * (size_t)cap));
@@ -6477,8 +6496,21 @@ static int range_run(orr_index *lane, const RangeArgs &a, const orr_scope *withi
             ORR_TRY(lane->ws_range_buf.reserve(sizeof(orr::SelEntry) * (size_t)nq));
         }
         const uint32_t scap = o.limit ? 1u : (uint32_t)cap;            // (a call that only counts any more stores nothing: buffers of one entry)
-        HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(uint32_t) * 2 * (size_t)range::kMaxQueries, s));
-        for (int32_t g0 = 0; g0 < nq; g0 += range::kScreenQ) {
+        HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(uint32_t) * 2 * (size_t)nw, s));
+        if (gemm) {
+            // one launch for the group; queries [b0, b0 + nq) of the tiled image start at a query tile only for b0 == 0, so a
+            // later group gets an image of its own
+            if (b0 > 0) {
+                Timed t(lane, "range_i8_tile_queries", 2.0 * (double)nq * D);
+                HIP_TRY(orr::launch_i8_tile_queries(q1 + (size_t)b0 * D, nq, D, lane->ws_qtiled.p, s));
+            }
+            HIP_TRY(hipMemsetAsync(lane->ws_tickets.p, 0, sizeof(uint32_t) * 8, s));
+            Timed t(lane, "screen_tile16_range", 1.0 * (double)n * D + 24.0 * (double)n + (double)orr::i8_tiled_bytes(nq, D));   // per row: scale, two relative norms, normB, its share of the bitmap
+            HIP_TRY(orr::launch_screen_tile16_range(lane->ws_qtiled.p, lane->ws_q8s1.as<float>() + b0, d_err1 + b0, nq, lane->emb_i8.p, lane->i8_scale.as<float>(),
+                                                    lane->i8_rel_err.as<float>(), lane->i8_rel_hat.as<float>(), lane->d_norm_b, n, D, d_qc + b0, d_t + b0, allowed,
+                                                    d_cnt, lane->ws_range_buf.as<orr::SelEntry>(), scap, lane->ws_tickets.as<uint32_t>(), lane->ws_range_args.p, s));
+        }
+        for (int32_t g0 = 0; !gemm && g0 < nq; g0 += range::kScreenQ) {
             const int32_t gq = std::min<int32_t>(range::kScreenQ, nq - g0), p = b0 + g0;
             Timed t(lane, "screen_gemv_i8_range", 1.0 * (double)n * D + 20.0 * (double)n + 2.0 * (double)gq * D);   // per row: scale, two relative norms, normB
             HIP_TRY(orr::launch_screen_gemv_i8_range(q1 + (size_t)p * D, q2 + (size_t)p * D, lane->ws_q8s1.as<float>() + p, lane->ws_q8err.as<double>() + p, gq,
@@ -6486,7 +6518,9 @@ static int range_run(orr_index *lane, const RangeArgs &a, const orr_scope *withi
                                                      lane->d_norm_b, n, D, d_qc + p, d_t + p, allowed, d_cnt + g0,
                                                      lane->ws_range_buf.as<orr::SelEntry>() + (size_t)g0 * scap, scap, s));
         }
-        uint32_t h_cnt[range::kMaxQueries] = {}, h_lcnt[range::kMaxQueries] = {};
+        h_cnt_v.assign((size_t)nq, 0u);
+        h_lcnt_v.assign((size_t)nq, 0u);
+        uint32_t *const h_cnt = h_cnt_v.data(), *const h_lcnt = h_lcnt_v.data();
         HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, sizeof(uint32_t) * (size_t)nq, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         const uint32_t mx = *std::max_element(h_cnt, h_cnt + nq);
@@ -6546,9 +6580,11 @@ static int range_on_lane(orr_index *lane, const RangeArgs &a, const orr_scope *w
 static int range_arguments(const char *fn, const RangeArgs &a, const void *out_hits, const void *out_n, const void *out_total)
 {
     int32_t bad = 0;
-    switch (range::first_invalid(a.B, a.dim, a.q == nullptr, a.min_cosine, a.max_hits, out_hits == nullptr, out_n == nullptr, out_total == nullptr, &bad)) {
+    const int32_t rule = a.bulk ? range_bulk::first_invalid(a.B, a.dim, a.q == nullptr, a.min_cosine, a.max_hits, out_hits == nullptr, out_n == nullptr, out_total == nullptr, &bad)
+                                : range::first_invalid(a.B, a.dim, a.q == nullptr, a.min_cosine, a.max_hits, out_hits == nullptr, out_n == nullptr, out_total == nullptr, &bad);
+    switch (rule) {
     case 0: return ORR_OK;
-    case 1: return fail(ORR_EINVAL, "%s: the batch size must be in 0 .. %d", fn, range::kMaxQueries);
+    case 1: return fail(ORR_EINVAL, "%s: the batch size must be in 0 .. %d", fn, a.bulk ? range_bulk::kMaxQueries : range::kMaxQueries);
     case 2: return fail(ORR_EINVAL, "%s: dim is negative", fn);
     case 3: return fail(ORR_EINVAL, "%s: max_hits is negative", fn);
     case 4: return fail(ORR_EINVAL, "%s: q is NULL with dim %d", fn, a.dim);
@@ -6578,14 +6614,13 @@ static int range_write(const char *fn, const RangeArgs &a, const RangeOut &o, or
                             "or make a set with orr_scope_create_near", fn, worst, (long long)o.total[(size_t)worst]);
 }
 
-int orr_search_range_cosine(orr_index *idx, int32_t B, int32_t dim, const float *q, const double *min_cosine, const orr_scope *within,
-                            int32_t max_hits, orr_range_hit *out_hits, int32_t *out_n, int64_t *out_total)
+// orr_search_range_cosine and orr_search_range_cosine_bulk: one body, a.bulk apart
+static int range_search(orr_index *idx, const RangeArgs &a, const orr_scope *within, orr_range_hit *out_hits, int32_t *out_n, int64_t *out_total)
 {
-    static const char *fn = "orr_search_range_cosine";
-    const RangeArgs a{B, dim, q, min_cosine, max_hits};
+    const char *fn = a.fn;
     ORR_TRY(range_arguments(fn, a, out_hits, out_n, out_total));
     if (!idx) return fail(ORR_EINVAL, "%s: null index", fn);
-    if (B == 0) return ORR_OK;
+    if (a.B == 0) return ORR_OK;
     orr_index *own = nullptr;
     if (within) ORR_TRY(scope_owner(within, idx, fn, &own));
     Lane ln = acquire_lane(idx);                       // like a search: its own lane, concurrent with the others
@@ -6601,6 +6636,18 @@ int orr_search_range_cosine(orr_index *idx, int32_t B, int32_t dim, const float 
     RangeOut o;
     ORR_TRY(range_on_lane(lane, a, within, o));
     return range_write(fn, a, o, out_hits, out_n, out_total);
+}
+
+int orr_search_range_cosine(orr_index *idx, int32_t B, int32_t dim, const float *q, const double *min_cosine, const orr_scope *within,
+                            int32_t max_hits, orr_range_hit *out_hits, int32_t *out_n, int64_t *out_total)
+{
+    return range_search(idx, RangeArgs{B, dim, q, min_cosine, max_hits, false, "orr_search_range_cosine"}, within, out_hits, out_n, out_total);
+}
+
+int orr_search_range_cosine_bulk(orr_index *idx, int32_t B, int32_t dim, const float *q, const double *min_cosine, const orr_scope *within,
+                                 int32_t max_hits, orr_range_hit *out_hits, int32_t *out_n, int64_t *out_total)
+{
+    return range_search(idx, RangeArgs{B, dim, q, min_cosine, max_hits, true, "orr_search_range_cosine_bulk"}, within, out_hits, out_n, out_total);
 }
 
 int orr_search_shard_scoped(orr_index *idx, int32_t B, int32_t dim, const float *q, const uint8_t *terms_utf8,
@@ -7907,11 +7954,25 @@ int orr_cluster_search_batch_in_scopes(orr_cluster *c, int32_t B, int32_t dim, c
 
 // Every shard runs the single call at once, each on a lane of its own; the host merges the shards' lists by (cosine descending,
 // order_key ascending), sums the totals and cuts at max_hits.  The limit met on any shard is the call's: the upper bounds summed.
+static int cluster_range_search(orr_cluster *c, const RangeArgs &a, const orr_cluster_scope *within, orr_range_hit *out_hits, int32_t *out_n, int64_t *out_total);
 int orr_cluster_search_range_cosine(orr_cluster *c, int32_t B, int32_t dim, const float *q_host, const double *min_cosine,
                                     const orr_cluster_scope *within, int32_t max_hits, orr_range_hit *out_hits, int32_t *out_n, int64_t *out_total)
 {
-    static const char *fn = "orr_cluster_search_range_cosine";
-    const RangeArgs a{B, dim, q_host, min_cosine, max_hits};
+    return cluster_range_search(c, RangeArgs{B, dim, q_host, min_cosine, max_hits, false, "orr_cluster_search_range_cosine"}, within, out_hits, out_n, out_total);
+}
+
+int orr_cluster_search_range_cosine_bulk(orr_cluster *c, int32_t B, int32_t dim, const float *q_host, const double *min_cosine,
+                                         const orr_cluster_scope *within, int32_t max_hits, orr_range_hit *out_hits, int32_t *out_n, int64_t *out_total)
+{
+    return cluster_range_search(c, RangeArgs{B, dim, q_host, min_cosine, max_hits, true, "orr_cluster_search_range_cosine_bulk"}, within, out_hits, out_n, out_total);
+}
+
+// (the body of the two calls above; C++ linkage inside the extern "C" block is fine for a static function)
+static int cluster_range_search(orr_cluster *c, const RangeArgs &a, const orr_cluster_scope *within, orr_range_hit *out_hits, int32_t *out_n, int64_t *out_total)
+{
+    const char *fn = a.fn;
+    const int32_t B = a.B, dim = a.dim, max_hits = a.max_hits;
+    const float *q_host = a.q;
     ORR_TRY(range_arguments(fn, a, out_hits, out_n, out_total));
     if (!c) return fail(ORR_EINVAL, "%s: null cluster", fn);
     if (B == 0) return ORR_OK;

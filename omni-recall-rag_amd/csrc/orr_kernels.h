@@ -521,6 +521,13 @@ hipError_t launch_screen_gemv_i8_range(const void *q1, const void *q2, const flo
                                        const float *scale, const float *rel_err, const float *rel_hat, const double *norm_b, int64_t n_rows,
                                        int32_t D, const QueryConst *qc, const double *min_cosine, const uint32_t *allowed, uint32_t *cnt,
                                        SelEntry *buf, uint32_t cap, hipStream_t s);
+// The same screen for any number of queries through the int8 screening GEMM's 16 x 16 x 64 form (orr_search_range_cosine_bulk);
+// the ONE-level query error bounds it.  args_ws: kRangeTile16ArgsBytes of device memory for the launch.  See orr_screen.hip.
+constexpr size_t kRangeTile16ArgsBytes = 128;
+hipError_t launch_screen_tile16_range(const void *q_tiled, const float *s1, const double *err2_level1, int32_t nq, const void *e_tiled,
+                                      const float *scale, const float *rel_err, const float *rel_hat, const double *norm_b, int64_t n_rows,
+                                      int32_t D, const QueryConst *qc, const double *min_cosine, const uint32_t *allowed, uint32_t *cnt,
+                                      SelEntry *buf, uint32_t cap, uint32_t *tickets, void *args_ws, hipStream_t s);
 // Behind launch_rescore_buffer_exact: every survivor buf[b][i], i < min(cnt[b], cap), of the nq queries with its exact dot
 // buf_dot[b][i]: the device's cosine (scope_near::cosine_of), range::device_keeps, and the kept pairs appended to list[b][..]
 // (list_cap entries per query, list_cnt [nq] zeroed by the caller counts every kept pair).

@@ -346,8 +346,37 @@ __global__ __launch_bounds__(512, 1) void screen_bf16_kernel(const __bf16 *__res
 // (64 registers), the rings are 3 query + 6 row stages, the epilogue keeps 16 KiB.
 // ---------------------------------------------------------------------------
 constexpr int kS4NA = 3, kS4NB = 6;
+struct RangeTileQuery { double s1, isa, qe1, t; };
+// What screen_tile16_kernel<..., RANGE> takes in FusedEpilogue's place (a type of its own: FusedEpilogue, an argument of every
+// screening kernel, stays as it is): the tickets, which the kernel's shared text reads, and ONE pointer to the ending's
+// arguments in device memory.  As kernel arguments they would live in scalar registers from the kernel's first instruction,
+// across the K loop, to the ending -- 23 more spilled than the DOTS form spills; behind a pointer they are read where the ending
+// begins, from the scalar cache.  The allowed rows' bitmap is count_planes, where the stream's RANGE ending has it; norm_b, scale,
+// rel_err, rel_hat are the raw per-row arrays that ending reads (not i8_rowf, which carries the score's 0.7); err2_level1 is the
+// queries' ONE-level quantisation error.
+struct RangeTile16Args {
+    const QueryConst *qc;              // [B]: only inv_sqrt_na is read
+    const unsigned long long *tau;     // [B]: the BITS of min_cosine
+    const uint32_t *count_planes;      // the allowed rows: one word per 32 rows
+    const float *i8_qs1;               // [B]
+    const double *err2_level1;         // [B]
+    const double *norm_b;              // per row
+    const float *scale, *rel_err, *rel_hat;
+    uint32_t *cnt;                     // [B]
+    SelEntry *buf;                     // [B][cap]
+    uint32_t cap;
+};
+static_assert(sizeof(RangeTile16Args) <= kRangeTile16ArgsBytes, "the caller's block holds the arguments");
+struct RangeEpilogue16 {
+    const RangeTile16Args *args;       // device memory, written by launch_screen_tile16_range in front of the launch
+    uint32_t *tickets;                 // as FusedEpilogue::tickets
+    static constexpr unsigned long long *stamps = nullptr;     // (the stamps are the fused launches')
+};
+__global__ void range_tile16_args_kernel(RangeTile16Args a, RangeTile16Args *out) { if (threadIdx.x == 0 && blockIdx.x == 0) *out = a; }
+    // a query of screen_tile16_kernel<..., RANGE>, staged in LDS: s1, 1 / sqrt(normA), |q - q^1| / sqrt(normA), min_cosine
 constexpr int kS4Queue = 6;
 constexpr int kS16Queue = 5;                            // the 16 x 16 x 64 form parks five: the sixth plane's first word is its ticket mailbox
+static_assert(256 * 32 <= kS16Queue * 8 * 256, "the RANGE ending's staged queries end in front of the ticket mailbox");
 constexpr int kS4EpiBytes = kS4Queue * 8 * 256 + 4096;
 constexpr int kS4Lds = (kS4NA + kS4NB) * kScImage + kS4EpiBytes;
 static_assert(kS4Lds <= 160 * 1024, "the rings and the epilogue's region must fit a CU's LDS");
@@ -635,16 +664,26 @@ __global__ __launch_bounds__(256, 1) void screen_tile4_kernel(const __bf16 *__re
 // ---------------------------------------------------------------------------
 // DOTS (diagnostic, orr_index_screen_i8_dots): no scoring epilogue -- the raw int32 accumulators go to S[query][row].
 // BITS2: the count words hold two bits per (query,row) (FusedEpilogue::count_bits == 2).
-template <bool NT, bool DOTS = false, bool BITS2 = false>
+// RANGE (orr_search_range_cosine_bulk; the rules are orr_range_bulk_plan.h's): the ending of a cosine range search, the one of
+// screen_gemv_i8_kernel<..., RANGE> on this accumulator layout -- no score, no count words, no parking queue.  Per output tile the
+// 256 threads stage their query's {s1, 1 / sqrt(normA), |q - q^1| / sqrt(normA), min_cosine} in the LDS of the parking queue
+// (RangeTileQuery, 8 KiB in front of the ticket mailbox); a lane loads its eight rows' bit of the `allowed` bitmap
+// (count_planes), normB, scale and the two relative norms once; then every pair of an allowed row < n_rows and a
+// query < B is tested in binary64 as the stream tests it, with the ONE-level query error (the GEMM multiplies the first level
+// only), and appended through cnt / buf / cap (RangeTile16Args) unless cos^ + range::cos_bound stays below the threshold.
+template <bool NT, bool DOTS = false, bool BITS2 = false, bool RANGE = false>
 __global__ __launch_bounds__(256, 1) void screen_tile16_kernel(const __bf16 *__restrict__ Qh, int32_t B,
                                                               const __bf16 *__restrict__ Eh, int64_t row_first, int64_t n_rows,
                                                               int32_t D, float *__restrict__ S, int64_t s_stride,
-                                                              int32_t n_ntiles, int32_t n_mtiles, int32_t flags, FusedEpilogue epi)
+                                                              int32_t n_ntiles, int32_t n_mtiles, int32_t flags,
+                                                              typename std::conditional<RANGE, RangeEpilogue16, FusedEpilogue>::type epi)
 {
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
     unsigned char *const lds_a = lds, *const lds_b = lds + kS4NA * kScImage, *const lds_epi = lds + (kS4NA + kS4NB) * kScImage;
     constexpr bool FUSED = true, I8 = true;
     constexpr int LIVE = 8;
+    static_assert(!RANGE || (!DOTS && !BITS2), "RANGE: an ending of its own");
+    constexpr bool PLAIN = DOTS || RANGE;                                   // no scoring epilogue: nothing of it is requested from the K loop
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = LIVE == 8 ? wave >> 1 : 0, wc = LIVE == 8 ? wave & 1 : wave;
@@ -765,12 +804,12 @@ __global__ __launch_bounds__(256, 1) void screen_tile16_kernel(const __bf16 *__r
     // when that whole ring has (10,000 cycles per tile by the stamps).  Hence also: the last kS4NA / kS4NB iterations
     // request nothing (their counted waits shrink with what is left in flight), and the ring is refilled for the next
     // output tile only when the epilogue's inputs are in registers -- it fills while the epilogue computes.
-    FusedEpilogue ep = epi;
+    auto ep = epi;
     EpiTileLoads16 pre;
     float4 qf_mine = make_float4(0.f, 0.f, 0.f, 0.f);
     auto epilogue_requests = [&]() __attribute__((always_inline)) {
         if (dyn && tid == 0) ticket = atomicAdd(&epi.tickets[n_mtiles == 1 ? 0 : xcd], 1u);      // (the oldest of what goes out here)
-        if constexpr (FUSED && !DOTS) {
+        if constexpr (FUSED && !PLAIN) {
             // laundered once per output tile: otherwise everything derived from these is hoisted out of the persistent loop
             asm volatile("" : "+s"(ep.rowc), "+s"(ep.qc), "+s"(ep.tau), "+s"(ep.qf), "+s"(ep.count_planes), "+s"(ep.plane_stride),
                               "+s"(ep.i8_rowf), "+s"(ep.i8_qs1), "+s"(ep.cnt), "+s"(ep.buf));
@@ -878,7 +917,7 @@ __global__ __launch_bounds__(256, 1) void screen_tile16_kernel(const __bf16 *__r
         constexpr int r = decltype(r_c)::value;
         if constexpr (r < RING) {
             constexpr int ring_left = r <= RING - 2 ? KP * (RING - 2 - r) : 63;
-            constexpr int allowed = r > kHookR && !DOTS ? ring_left + kEpiLoads : ring_left;
+            constexpr int allowed = r > kHookR && !PLAIN ? ring_left + kEpiLoads : ring_left;
             using WaitTail = std::integral_constant<int, (allowed > 63 ? 63 : allowed)>;
             using Hook = std::integral_constant<bool, r == kHookR>;
             tile_iter(std::false_type{}, std::false_type{}, WaitTail{}, Hook{});
@@ -914,6 +953,69 @@ __global__ __launch_bounds__(256, 1) void screen_tile16_kernel(const __bf16 *__r
             if (tid == 0) *mailbox = dyn_checked(ticket_id(ticket));
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         }
+        if (has_next) { if (row_loader) refill(std::true_type{}); else refill(std::false_type{}); }
+    } else if constexpr (RANGE) {
+        // this thread's query of the output tile, staged for every lane that tests it (queries >= B: zeros, never read -- the
+        // tiled query image pads them with zeros, whose cos^ of 0 would pass any threshold <= the bound)
+        RangeTileQuery *const rq = reinterpret_cast<RangeTileQuery *>(lds_epi);
+        const RangeTile16Args *ap = epi.args;
+        asm volatile("" : "+s"(ap));                                       // (read HERE, per output tile: not held in registers across the K loop)
+        const RangeTile16Args ra = *ap;
+        {
+            const int q = b0 + tid;
+            RangeTileQuery mine;
+            mine.s1 = 0.0; mine.isa = 0.0; mine.qe1 = 0.0; mine.t = 0.0;
+            if (q < B) {
+                mine.isa = ra.qc[q].inv_sqrt_na;
+                mine.s1 = (double)ra.i8_qs1[q];
+                mine.qe1 = sqrt(ra.err2_level1[q]) * mine.isa;
+                mine.t = __longlong_as_double((long long)ra.tau[q]);
+            }
+            rq[tid] = mine;
+        }
+        // this lane's eight rows 16 j + c: clamped, never branched around; a row past n_rows or without its bit tests nothing
+        const int c = tile16_c_of(lane_t), g = tile16_g_of(lane_t);
+        uint32_t aw[8];
+        double nb[8];
+        float rse[8], rre[8], rrh[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int64_t row = n0 + wc * 128 + 16 * j + c, at = row < n_rows ? row : n_rows - 1;
+            aw[j] = ra.count_planes[at >> 5];
+            nb[j] = ra.norm_b[at];
+            rse[j] = ra.scale[at]; rre[j] = ra.rel_err[at]; rrh[j] = ra.rel_hat[at];
+        }
+        if (dyn && tid == 0) *mailbox = dyn_checked(ticket_id(ticket));
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // the staged queries (and the mailbox) visible to every wave
+        const RangeTileQuery *const rql = rq + wr * 128 + 4 * g;
+        static_for<8>([&](auto j_c) {
+            constexpr int j = decltype(j_c)::value;
+            const int64_t row = n0 + wc * 128 + 16 * j + c;
+            if (row < n_rows && ((aw[j] >> (uint32_t)(row & 31)) & 1u)) {
+                const double isb = nb[j] > 0.0 ? 1.0 / sqrt(nb[j]) : 0.0;  // (:84-85: a norm <= 0 gives cosine 0)
+                const double se = (double)rse[j], re = (double)rre[j], rh = (double)rrh[j];
+                static_for<8>([&](auto i_c) {
+                    static_for<4>([&](auto e_c) {
+                        constexpr int i = decltype(i_c)::value, e = decltype(e_c)::value;
+                        const int qi = b0 + wr * 128 + 16 * i + 4 * g + e;
+                        const int v = acc16_as_int_here<4 * (8 * i + j) + e>(acc_token);
+                        if (qi < B) {
+                            const RangeTileQuery k = rql[16 * i + e];
+                            const double dot = se * k.s1 * (double)v;
+                            if (range::screen_keeps(dot * k.isa * isb, range::cos_bound(re, rh, k.qe1), k.t)) {
+                                const uint32_t slot = atomicAdd(&ra.cnt[qi], 1u);
+                                if (slot < ra.cap) {
+                                    SelEntry en;
+                                    en.key = 0ull; en.pos = (uint32_t)row; en.pad = 0;
+                                    ra.buf[(int64_t)qi * ra.cap + slot] = en;
+                                }
+                            }
+                        }
+                    });
+                });
+            }
+        });
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                   // (the appends: the counted waits of the next tile's K loop count requests only)
         if (has_next) { if (row_loader) refill(std::true_type{}); else refill(std::false_type{}); }
     } else {
         uint32_t salt = 0;
@@ -1687,6 +1789,51 @@ hipError_t launch_screen_i8_dots_raw(const void *q_tiled, int32_t B, const void 
     }
 #undef ORR_LAUNCH_I8R16
 #undef ORR_LAUNCH_I8R4
+    return hipGetLastError();
+}
+
+// The screen of a bulk cosine range search (orr_search_range_cosine_bulk): ONE launch of the 16 x 16 x 64 form of the int8
+// screening GEMM with the RANGE ending over rows [0, n_rows) for nq = 1 .. any number of queries -- K loop, rings, requests, grid
+// (screen_grid: ORR_SCREEN_GRID applies) and ticket walk are the fused launches'; rows non-temporal for a single query tile.
+// q_tiled: the tiled image of the queries' FIRST int8 level (launch_i8_tile_queries); s1 / err2_level1 / qc / min_cosine [nq]
+// (only qc[b].inv_sqrt_na is read); allowed: one word per 32 rows; cnt [nq] zeroed by the caller, buf [nq][cap]; tickets: 8 words
+// zeroed by the caller for this launch, or null for static assignment; args_ws: kRangeTile16ArgsBytes of device memory the launch
+// may use until it has run (the ending's arguments, written by a one-thread launch in front).  D % 128 == 0 and D / 64 > 6
+// (range_bulk::gemm_shape).
+hipError_t launch_screen_tile16_range(const void *q_tiled, const float *s1, const double *err2_level1, int32_t nq, const void *e_tiled,
+                                      const float *scale, const float *rel_err, const float *rel_hat, const double *norm_b, int64_t n_rows,
+                                      int32_t D, const QueryConst *qc, const double *min_cosine, const uint32_t *allowed, uint32_t *cnt,
+                                      SelEntry *buf, uint32_t cap, uint32_t *tickets, void *args_ws, hipStream_t s)
+{
+    if (nq <= 0 || n_rows <= 0) return hipSuccess;
+    if (D <= 0 || D % 128 != 0 || D / 64 <= kS4NB || cap == 0 || n_rows >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+    if (!q_tiled || !s1 || !err2_level1 || !e_tiled || !scale || !rel_err || !rel_hat || !norm_b || !qc || !min_cosine || !allowed || !cnt || !buf || !args_ws)
+        return hipErrorInvalidValue;
+    const int64_t n_ntiles = (n_rows + kScBN - 1) / kScBN;
+    const int32_t n_mtiles = (nq + kScBM - 1) / kScBM;
+    const int64_t blocks = ((n_ntiles + 7) / 8) * 8 * n_mtiles;
+    if (blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
+    RangeTile16Args ra{};
+    ra.qc = qc;
+    ra.tau = reinterpret_cast<const unsigned long long *>(min_cosine);
+    ra.count_planes = allowed;
+    ra.i8_qs1 = s1; ra.err2_level1 = err2_level1;
+    ra.norm_b = norm_b; ra.scale = scale; ra.rel_err = rel_err; ra.rel_hat = rel_hat;
+    ra.cnt = cnt; ra.buf = buf; ra.cap = cap;
+    hipLaunchKernelGGL(range_tile16_args_kernel, dim3(1), dim3(64), 0, s, ra, static_cast<RangeTile16Args *>(args_ws));
+    RangeEpilogue16 e2{};
+    e2.args = static_cast<const RangeTile16Args *>(args_ws);
+    e2.tickets = tickets;
+    if (const char *t = getenv("ORR_SCREEN_TICKETS")) { if (atoi(t) == 0) e2.tickets = nullptr; }
+#define ORR_LAUNCH_I8RG(NT) do { \
+        const hipError_t attr = ensure_max_dynamic_lds<screen_tile16_kernel<NT, false, false, true>>(kS4Lds); \
+        if (attr != hipSuccess) return attr; \
+        hipLaunchKernelGGL((screen_tile16_kernel<NT, false, false, true>), dim3((unsigned)screen_grid(blocks, D / 64)), dim3(256), kS4Lds, s, \
+                           static_cast<const __bf16 *>(q_tiled), nq, static_cast<const __bf16 *>(e_tiled), (int64_t)0, n_rows, D, \
+                           static_cast<float *>(nullptr), (int64_t)0, (int32_t)n_ntiles, n_mtiles, 1, e2); } while (0)
+    if (n_mtiles == 1) ORR_LAUNCH_I8RG(true);
+    else ORR_LAUNCH_I8RG(false);
+#undef ORR_LAUNCH_I8RG
     return hipGetLastError();
 }
 

@@ -576,6 +576,12 @@ class RecallIndex:
         (its `totals`: every query's upper bound) when a query is too unselective for "range_pair_cap"."""
         return _range_cosine(N.hip.orr_search_range_cosine, self._h, qvecs, min_cosine, max_hits, within, True)
 
+    def range_cosine_bulk(self, qvecs, min_cosine, max_hits: int, within: Optional[RecallScope] = None):
+        """orr_search_range_cosine_bulk: range_cosine for up to 1024 queries in one call -- the same answers as range_cosine on
+        slices of 64; from 65 screened queries up (dim % 128 == 0, dim >= 512) the int8 screening GEMM screens them in one
+        pass over the shard per launch group.  Takes and returns what range_cosine does."""
+        return _range_cosine(N.hip.orr_search_range_cosine_bulk, self._h, qvecs, min_cosine, max_hits, within, True)
+
     def search_in_scope(self, qvecs, queries_terms, now_ticks: int, topk: int, scope: RecallScope, candidate_limit: int = 300):
         """orr_search_batch_in_scope: search_masked with the scope taken from a handle -- nothing is resolved per call.
         Returns (rows [B,k] int64, scores [B,k] float64, counts [B] int32)."""
@@ -955,6 +961,10 @@ class RecallCluster:
         """orr_cluster_search_range_cosine: RecallIndex.range_cosine over every shard, merged -- the answers of one index
         holding all the rows.  qvecs in host memory (numpy)."""
         return _range_cosine(N.hip.orr_cluster_search_range_cosine, self._h, qvecs, min_cosine, max_hits, within, False)
+
+    def range_cosine_bulk(self, qvecs, min_cosine, max_hits: int, within: Optional[RecallClusterScope] = None):
+        """orr_cluster_search_range_cosine_bulk: RecallIndex.range_cosine_bulk over every shard, merged as range_cosine merges."""
+        return _range_cosine(N.hip.orr_cluster_search_range_cosine_bulk, self._h, qvecs, min_cosine, max_hits, within, False)
 
     def search_in_scope(self, qvecs, queries_terms, now_ticks: int, topk: int, scope: RecallClusterScope, candidate_limit: int = 300):
         """orr_cluster_search_batch_in_scope: search_masked with the scope taken from a handle -- no id list goes to the
