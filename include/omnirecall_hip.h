@@ -656,6 +656,47 @@ int orr_search_range_cosine_bulk(orr_index *idx, int32_t B, int32_t dim, const f
                                  int32_t max_hits, orr_range_hit *out_hits /* host [B][max_hits] */,
                                  int32_t *out_n /* host [B] */, int64_t *out_total /* host [B] */);
 
+/* ---- diverse search: the results compared WITH EACH OTHER ------------------------------------------------------------------
+ * Every search above compares a query with rows.  This one also compares the best rows of a query with each other and returns
+ * topk of them that are not near-copies of one another: a near-duplicate collapse of the ranked list, or maximal marginal
+ * relevance (MMR).  The cluster form, pools beyond 56 and a per-document cap are not offered.
+ *
+ * 1. The pool.  within == NULL: exactly what orr_search_batch returns for topk = pool; with a scope: exactly what
+ *    orr_search_batch_in_scope returns for topk = pool -- rows, unrounded fused scores, order, and all their rules
+ *    (candidate_limit, a foreign dim, ties, NaN order, deleted rows, lanes, views, a scope of another shard).
+ *    max(1, topk) <= pool <= 56 (ORR_DIVERSE_MAX_POOL: the largest take the search serves from one selection list).
+ *    DIVERSIFICATION NEVER LOOKS OUTSIDE THE POOL: when the pool runs out, out_counts[b] stays below topk.
+ * 2. The cosines.  c_ij = CosineSimilarity(e_i, e_j) of RecallSearchService.cs:69-88 with the two STORED rows as a and b, bit for
+ *    bit: evaluated on the host from three sums that are exact on the device.  A row without an embedding, or an index of
+ *    dim 0, has cosine 0 with everything; the query's own dim plays no part.
+ * 3. The greedy pass over the pool in rank order, on the host.
+ *    ORR_DIVERSE_COLLAPSE, param = max_cosine: ranks 0, 1, ...; a member is kept unless c >= max_cosine (C#'s >=: a NaN cosine
+ *      drops nothing) for some member already kept; stops at take = max(1, topk) kept.  max_cosine = +inf reads no cosine and
+ *      gives the plain search's first `take` rows bit for bit.
+ *    ORR_DIVERSE_MMR, param = lambda in [0, 1]: rank 0 is kept first; each next pick is the remaining member with the greatest
+ *      (lambda * score) - ((1.0 - lambda) * m), binary64, left to right, no contraction; m is the maximum of its cosines to the
+ *      kept members (the fold starts at -inf with `if (c > m) m = c`, so NaN is skipped; still -inf: m = 0).  Values are
+ *      compared as double.CompareTo orders them, a tie goes to the lower pool rank.  With 1.0 - lambda == 0.0 the penalty is
+ *      exactly 0: lambda = 1 is the plain search bit for bit and reads no cosine.
+ * out_rows / out_scores [B][max(1,topk)]: the picks in pick order with their FUSED scores (not MMR values); out_counts [B];
+ * out_pool_rank [B][max(1,topk)] (may be NULL): each pick's rank in the undiversified order.  Unused slots: -1 / 0.0 / -1.
+ * ORR_EINVAL before the handle is looked at, the outputs untouched, in this order: out_rows, out_scores or out_counts NULL; pool
+ * outside 1 .. 56; max(1, topk) > pool; a mode other than the two; param NaN; lambda outside [0, 1].  Then a NULL index, and,
+ * unless B == 0 (which writes nothing), the errors of the underlying search.
+ * Kernel statistics: the pool's search as always, then ONE pair_dots launch for (up to 1024 queries of) the batch; a query whose
+ * pool has fewer than 2 members, an index of dim 0, max_cosine = +inf and lambda == 1 take none.  The search statistics move as
+ * for one search of B queries. */
+#define ORR_DIVERSE_COLLAPSE 0
+#define ORR_DIVERSE_MMR      1
+#define ORR_DIVERSE_MAX_POOL 56
+int orr_search_batch_diverse(orr_index *idx, int32_t B, int32_t dim, const float *q,
+                             const uint8_t *terms_utf8, const uint32_t *term_off, const uint32_t *query_term_off,
+                             int64_t now_ticks, int32_t topk, int64_t candidate_limit,
+                             const orr_scope *within /* or NULL: every live row */,
+                             int32_t pool, int32_t mode, double param,
+                             int64_t *out_rows, double *out_scores, int32_t *out_counts,
+                             int32_t *out_pool_rank /* [B][max(1,topk)], may be NULL */);
+
 /* orr_search_shard_masked with the scope taken from a handle: the record form of orr_search_batch_in_scope, the shard half of
  * orr_cluster_search_batch_in_scope.  The contract is orr_search_shard_masked's, unchanged: [B][kprime+1] records and the
  * trailer, `pass` 0 / 1, topk, candidate_limit GLOBAL with scope_before the scope's live rows on the shards in front (read
@@ -767,6 +808,17 @@ int orr_index_screen_i8_stream_dots(orr_index *idx, int32_t B, int32_t dim, cons
  * MFMA form (K2s), the queries sent in groups of 32 as the pass sends them (up to 16 queries and 17..32 run different kernels);
  * kernel 1: the queries split into bf16 hi/lo halves, then the unfused three-product split-bf16 GEMM.  dim % 64 == 0. */
 int orr_index_pass_dots(orr_index *idx, int32_t kernel, int32_t B, int32_t dim, const float *q, float *out);
+
+/* Diagnostic: the pair matrices orr_search_batch_diverse forms its cosines from (tests/test_gpu_diverse.py).  List l is the
+ * positions[list_off[l] .. list_off[l + 1]) (candidate order: order_key - row_base); out[l][i][j] = out[l][j][i] is the exact dot
+ * of its rows i and j -- products rounded to binary32, summed in binary64 in index order, RecallSearchService.cs:77-82 -- and the
+ * diagonal a row's exact self-dot.  A position may repeat.  Elements at or beyond a list's own length are left as they were.
+ * ORR_EINVAL from the host, before any launch: out NULL, n_lists < 0, stride outside 1 .. 56, list_off or positions NULL, a
+ * NULL index, list_off not starting at 0 or decreasing, a list longer than stride, a position outside [0, orr_index_rows).
+ * An index of dim 0: zeros.  Kernel statistic: pair_dots, one launch per 1024 lists. */
+int orr_index_pair_dots(orr_index *idx, int32_t n_lists, const uint32_t *list_off /* host [n_lists+1] */,
+                        const int64_t *positions /* host */, int32_t stride /* >= the longest list, <= 56 */,
+                        double *out /* host [n_lists][stride][stride] */);
 
 /* Diagnostic: the keyword chain of a search, seen directly (tests/test_gpu_keyword_chain.py).  Runs the chain exactly as a
  * search for ONE query that owns all n_terms terms runs it -- vocabulary match, alias stage, posting expansion, the repeat with

@@ -122,6 +122,8 @@ hip.orr_search_range_cosine.restype = C.c_int
 hip.orr_search_range_cosine.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp]
 hip.orr_search_range_cosine_bulk.restype = C.c_int
 hip.orr_search_range_cosine_bulk.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp]
+hip.orr_search_batch_diverse.restype = C.c_int
+hip.orr_search_batch_diverse.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _vp, _i32, _i32, C.c_double, _vp, _vp, _vp, _vp]
 hip.orr_search_shard_in_scope.restype = C.c_int
 hip.orr_search_shard_in_scope.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, _vp, _i64, _vp]
 hip.orr_search_shard_in_scopes.restype = C.c_int
@@ -164,6 +166,8 @@ hip.orr_index_screen_i8_stream_dots.restype = C.c_int
 hip.orr_index_screen_i8_stream_dots.argtypes = [_vp, _i32, _i32, _vp, _i32, _vp]
 hip.orr_index_pass_dots.restype = C.c_int
 hip.orr_index_pass_dots.argtypes = [_vp, _i32, _i32, _i32, _vp, _vp]
+hip.orr_index_pair_dots.restype = C.c_int
+hip.orr_index_pair_dots.argtypes = [_vp, _i32, _vp, _vp, _i32, _vp]
 hip.orr_index_keyword_bitmaps.restype = C.c_int
 hip.orr_index_keyword_bitmaps.argtypes = [_vp, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp]
 hip.orr_index_set_profiling.restype = C.c_int
@@ -307,6 +311,7 @@ EXPORTED_HIP_SYMBOLS = [
     "orr_cluster_search_batch", "orr_cluster_search_batch_scoped", "orr_cluster_search_batch_masked", "orr_cluster_search_stats", "orr_cluster_set_option",
     "orr_scope_create", "orr_scope_create_ticks", "orr_scope_create_terms", "orr_scope_create_near", "orr_scope_add_ids", "orr_scope_combine", "orr_scope_rows", "orr_scope_row_ids", "orr_scope_destroy",
     "orr_search_batch_in_scope", "orr_search_batch_in_scopes", "orr_search_shard_in_scope", "orr_search_shard_in_scopes", "orr_search_range_cosine", "orr_search_range_cosine_bulk",
+    "orr_search_batch_diverse", "orr_index_pair_dots",
     "orr_cluster_scope_create", "orr_cluster_scope_create_ticks", "orr_cluster_scope_create_terms", "orr_cluster_scope_create_near", "orr_cluster_scope_add_ids", "orr_cluster_scope_combine",
     "orr_cluster_scope_rows", "orr_cluster_scope_row_ids", "orr_cluster_scope_shard", "orr_cluster_scope_destroy", "orr_cluster_search_batch_in_scope",
     "orr_cluster_search_batch_in_scopes", "orr_cluster_search_range_cosine", "orr_cluster_search_range_cosine_bulk",

@@ -237,6 +237,10 @@ struct orr_index {
     // and in their walked order; their exact norms; per walked query norm, threshold and QueryConst; the survivors' and the
     // lists' counters; the survivors' buffers with their exact dots; the lists; the exact form's dense dots
     DevBuf ws_range_allowed, ws_range_q, ws_range_qp, ws_range_norm, ws_range_consts, ws_range_cnt, ws_range_buf, ws_range_bdot, ws_range_list, ws_range_dots, ws_range_args;
+    // diverse search (orr_search_batch_diverse, orr_index_pair_dots), a lane's: the lists' positions and lengths, the pair matrices;
+    // pinned: the staging of the first two and the matrices as they come back
+    DevBuf ws_diverse_pos, ws_diverse_cnt, ws_diverse_out;
+    PinnedBuf pin_diverse;
     int opt_range_gemm = range_bulk::Auto;                 // "range_gemm" (orr_search_range_cosine_bulk): 0 the GEMM screen from 65 walked queries up, 1 wherever it applies, 2 never
     int opt_range_form = range::Auto;                      // "range_form": 0 the screen where it applies, 1 the same, 2 the exact form only
     int64_t opt_range_pair_cap = range::kDefaultPairCap;   // "range_pair_cap": kept pairs of one query beyond which the call is ORR_ELIMIT
@@ -759,6 +763,8 @@ void orr_index_destroy(orr_index *idx)
     for (DevBuf *b : {&idx->ws_range_allowed, &idx->ws_range_q, &idx->ws_range_qp, &idx->ws_range_norm, &idx->ws_range_consts, &idx->ws_range_cnt,
                       &idx->ws_range_buf, &idx->ws_range_bdot, &idx->ws_range_list, &idx->ws_range_dots, &idx->ws_range_args}) b->release();
     for (DevBuf *b : {&idx->ws_mask_bm, &idx->ws_mask_chunks, &idx->ws_mask_cnt, &idx->ws_mask_meta}) b->release();
+    for (DevBuf *b : {&idx->ws_diverse_pos, &idx->ws_diverse_cnt, &idx->ws_diverse_out}) b->release();
+    idx->pin_diverse.release();
     idx->pin_mask.release();
     for (DevBuf *b : {&idx->ws_group_bm, &idx->ws_group_chunks, &idx->ws_group_meta}) b->release();
     idx->pin_group.release();
@@ -2374,6 +2380,7 @@ struct BatchArgs {
     bool no_fuse = false;          // keep the batched pass unfused (retry after a candidate-buffer overflow)
     const double *norms_host = nullptr; // exact normA of every query, already computed by the caller (orr_cluster: once for all shards)
     orr_candidate *out_dev = nullptr;   // orr_search_shard with a device-resident `out`: the kernels write the records there
+    int64_t *out_keys = nullptr;        // orr_search_batch_diverse: [B][max(1, topk)] of the CALL's numbering, each result's order_key beside out_rows
 };
 
 const orr_index *owner_of(const orr_index *idx) { return idx->parent ? idx->parent : idx; }
@@ -3773,7 +3780,7 @@ bool ranks_before(const Ranked &x, const Ranked &y)
 // candidate sets were provably unable to reach the top-k.
 int32_t finish_query(const orr_candidate *const *shard_recs, int32_t n_shards, int32_t kprime, bool use_cos,
                      double norm_a, int32_t n_terms, int64_t now_ticks, int32_t topk, int64_t *out_rows,
-                     double *out_scores, bool *certified, int *err)
+                     double *out_scores, bool *certified, int *err, int64_t *out_keys = nullptr)
 {
     std::vector<Ranked> ranked;
     double cutoff = -std::numeric_limits<double>::infinity();
@@ -3813,6 +3820,7 @@ int32_t finish_query(const orr_candidate *const *shard_recs, int32_t n_shards, i
     for (int32_t i = 0; i < n_out; ++i) {
         out_rows[i] = ranked[i].row_id;
         out_scores[i] = ranked[i].score;
+        if (out_keys) out_keys[i] = ranked[i].order_key;
     }
     const bool lower_bounded = need_score != -std::numeric_limits<double>::infinity();
     if (overflow) {
@@ -3834,7 +3842,7 @@ int32_t finish_query(const orr_candidate *const *shard_recs, int32_t n_shards, i
 int merge_impl(int32_t n_shards, int32_t B, int32_t kprime, const orr_candidate *all, int32_t dim, bool use_cos,
                const float *q_host, const double *norms, const uint32_t *query_term_off, int64_t now_ticks, int32_t topk,
                int64_t *out_rows, double *out_scores, int32_t *out_counts, int32_t *out_uncertified,
-               uint8_t *out_certified = nullptr)
+               uint8_t *out_certified = nullptr, int64_t *out_keys = nullptr)
 {
     const int32_t take = std::max<int32_t>(1, topk);
     int32_t unc = 0;
@@ -3856,7 +3864,8 @@ int merge_impl(int32_t n_shards, int32_t B, int32_t kprime, const orr_candidate 
             int err = ORR_OK;
             for (int32_t i = 0; i < take; ++i) { out_rows[(size_t)b * take + i] = -1; out_scores[(size_t)b * take + i] = 0.0; }
             const int32_t cnt = finish_query(recs.data(), n_shards, kprime, use_cos, norm_a, n_terms, now_ticks, topk,
-                                             out_rows + (size_t)b * take, out_scores + (size_t)b * take, &cert, &err);
+                                             out_rows + (size_t)b * take, out_scores + (size_t)b * take, &cert, &err,
+                                             out_keys ? out_keys + (size_t)b * take : nullptr);
             if (err != ORR_OK) { *err_out = err; return; }
             if (out_counts) out_counts[b] = cnt;
             if (out_certified) out_certified[b] = cert ? 1 : 0;
@@ -3895,10 +3904,12 @@ int merge_into(int32_t n_shards, int32_t kprime, const orr_candidate *recs, cons
     std::vector<int64_t> rows((size_t)nb * take);
     std::vector<double> scores((size_t)nb * take);
     std::vector<int32_t> counts((size_t)nb);
+    std::vector<int64_t> keys(cur.out_keys ? (size_t)nb * take : 0);
     ORR_TRY(merge_impl(n_shards, nb, kprime, recs, cur.dim, use_cos, q_host, norms, cur.query_term_off, cur.now_ticks, cur.topk, rows.data(),
-                       scores.data(), counts.data(), nullptr, cert.data()));
+                       scores.data(), counts.data(), nullptr, cert.data(), cur.out_keys ? keys.data() : nullptr));
     for (int32_t i = 0; i < nb; ++i) {
         const size_t b = (size_t)ids[(size_t)i];
+        if (cur.out_keys) memcpy(cur.out_keys + b * take, keys.data() + (size_t)i * take, sizeof(int64_t) * take);
         memcpy(out_rows + b * take, rows.data() + (size_t)i * take, sizeof(int64_t) * take);
         memcpy(out_scores + b * take, scores.data() + (size_t)i * take, sizeof(double) * take);
         if (out_counts) out_counts[b] = counts[(size_t)i];
@@ -6648,6 +6659,201 @@ int orr_search_range_cosine_bulk(orr_index *idx, int32_t B, int32_t dim, const f
                                  int32_t max_hits, orr_range_hit *out_hits, int32_t *out_n, int64_t *out_total)
 {
     return range_search(idx, RangeArgs{B, dim, q, min_cosine, max_hits, true, "orr_search_range_cosine_bulk"}, within, out_hits, out_n, out_total);
+}
+
+// ---- diverse search (orr_search_batch_diverse, orr_index_pair_dots; the rules are orr_diverse_plan.h's) ----------------------
+static_assert(diverse::kSelWidth == orr::kSelWidth, "diverse::kMaxPool is the ladder's largest take from one selection list");
+static_assert(diverse::kMaxPool == ORR_DIVERSE_MAX_POOL && diverse::Collapse == ORR_DIVERSE_COLLAPSE && diverse::Mmr == ORR_DIVERSE_MMR, "the header's constants");
+
+// The exact pair matrices of n_lists lists on the lane the caller holds: list l is cnt[l] <= stride positions pos[l * stride + i],
+// every one of them checked against the shard's rows by the caller.  mats [n_lists][stride][stride]: the elements with i and j
+// below cnt[l] are the kernel's, the others are whatever the workspace held.  Positions and lengths go up and the matrices come
+// back through pinned memory, kListsPerLaunch lists a launch.
+static int pair_dots_on_lane(orr_index *lane, int32_t n_lists, int32_t stride, const uint32_t *pos, const uint32_t *cnt, double *mats)
+{
+    constexpr int32_t kListsPerLaunch = 1024;
+    if (n_lists <= 0) return ORR_OK;
+    ORR_TRY(bind_device(lane));
+    hipStream_t s = lane->stream;
+    const int32_t D = lane->dim;
+    const size_t per_pos = (size_t)stride, per_mat = (size_t)stride * (size_t)stride;
+    const size_t group = (size_t)std::min<int32_t>(n_lists, kListsPerLaunch);
+    const size_t pos_bytes = sizeof(uint32_t) * group * per_pos, cnt_bytes = sizeof(uint32_t) * group, mat_bytes = sizeof(double) * group * per_mat;
+    const size_t pin_mat_at = (pos_bytes + cnt_bytes + 15) / 16 * 16;
+    ORR_TRY(lane->ws_diverse_pos.reserve(pos_bytes));
+    ORR_TRY(lane->ws_diverse_cnt.reserve(cnt_bytes));
+    ORR_TRY(lane->ws_diverse_out.reserve(mat_bytes));
+    ORR_TRY(lane->pin_diverse.reserve(pin_mat_at + mat_bytes));
+    uint8_t *pin = lane->pin_diverse.as<uint8_t>();
+    for (int32_t l0 = 0; l0 < n_lists; l0 += kListsPerLaunch) {
+        const size_t nl = (size_t)std::min<int32_t>(kListsPerLaunch, n_lists - l0);
+        double rows_read = 0.0, pairs = 0.0;
+        for (size_t l = 0; l < nl; ++l) { rows_read += (double)cnt[(size_t)l0 + l]; pairs += (double)diverse::pair_count((int32_t)cnt[(size_t)l0 + l]); }
+        memcpy(pin, pos + (size_t)l0 * per_pos, sizeof(uint32_t) * nl * per_pos);
+        memcpy(pin + pos_bytes, cnt + l0, sizeof(uint32_t) * nl);
+        HIP_TRY(hipMemcpyAsync(lane->ws_diverse_pos.p, pin, sizeof(uint32_t) * nl * per_pos, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(lane->ws_diverse_cnt.p, pin + pos_bytes, sizeof(uint32_t) * nl, hipMemcpyHostToDevice, s));
+        {
+            Timed t(lane, "pair_dots", 4.0 * rows_read * (double)D + 16.0 * pairs);
+            HIP_TRY(orr::launch_pair_dots(lane->d_emb, lane->n_rows, D, lane->ws_diverse_pos.as<uint32_t>(), lane->ws_diverse_cnt.as<uint32_t>(),
+                                          (int32_t)nl, stride, lane->ws_diverse_out.as<double>(), s));
+        }
+        HIP_TRY(hipMemcpyAsync(pin + pin_mat_at, lane->ws_diverse_out.p, sizeof(double) * nl * per_mat, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        collect_events(lane);
+        memcpy(mats + (size_t)l0 * per_mat, pin + pin_mat_at, sizeof(double) * nl * per_mat);
+    }
+    return ORR_OK;
+}
+
+struct DiverseArgs {
+    int32_t pool, mode;
+    double param;
+};
+
+// orr_search_batch_diverse on the lane the caller holds (with the scope, if any, held shared):
+//   1. the pool: the plain search (the masked search inside `within`) for topk = pool, unchanged, which also hands back every
+//      result's order_key (BatchArgs::out_keys); position = order_key - row_base;
+//   2. the queries whose greedy pass reads a cosine (diverse::needs_dots) send their pools to ONE launch_pair_dots per 1024 of
+//      them; the matrices come back to the host;
+//   3. the host forms c_ij = scope_near::cosine_of(dot_ij, dot_ii, dot_jj) -- the diagonal supplies both norms -- runs
+//      diverse::select_collapse / select_mmr and writes the outputs.  A query that reads no cosine takes no launch.
+static int diverse_run(orr_index *lane, const char *fn, const BatchArgs &a, const orr_scope *within, const DiverseArgs &d, int64_t *out_rows,
+                       double *out_scores, int32_t *out_counts, int32_t *out_pool_rank)
+{
+    const int32_t B = a.B, pool = d.pool, take = diverse::take_of(a.topk);
+    std::vector<int64_t> p_rows((size_t)B * pool, -1), p_keys((size_t)B * pool, -1);
+    std::vector<double> p_scores((size_t)B * pool, 0.0);
+    std::vector<int32_t> p_cnt((size_t)B, 0);
+    BatchArgs pa = a;
+    pa.topk = pool;
+    pa.out_keys = p_keys.data();
+    if (within) {
+        ORR_TRY(masked_batch(lane, pa, ScopeSource{nullptr, within}, p_rows.data(), p_scores.data(), p_cnt.data()));
+    } else {
+        const int64_t n = participating_rows(lane, a.candidate_limit);
+        ORR_TRY(escalate(index_backend(lane, fn, n), pa, escalation::initial_kprime(pool, n, orr::kSelWidth), p_rows.data(), p_scores.data(), p_cnt.data()));
+    }
+    // ---- the pools that are compared
+    std::vector<int32_t> slot_of((size_t)B, -1);
+    int32_t n_lists = 0, stride = 1;
+    for (int32_t b = 0; b < B; ++b) {
+        if (!diverse::needs_dots(d.mode, d.param, p_cnt[(size_t)b], lane->dim)) continue;
+        slot_of[(size_t)b] = n_lists++;
+        stride = std::max(stride, p_cnt[(size_t)b]);
+    }
+    std::vector<double> mats;
+    if (n_lists > 0) {
+        std::vector<uint32_t> pos((size_t)n_lists * stride, 0u), cnt((size_t)n_lists, 0u);
+        for (int32_t b = 0; b < B; ++b) {
+            const int32_t l = slot_of[(size_t)b];
+            if (l < 0) continue;
+            cnt[(size_t)l] = (uint32_t)p_cnt[(size_t)b];
+            for (int32_t i = 0; i < p_cnt[(size_t)b]; ++i) {
+                const int64_t p = p_keys[(size_t)b * pool + i] - lane->row_base;
+                if (p < 0 || p >= lane->n_rows) return fail(ORR_EDEVICE, "%s: a result's order_key lies outside the shard", fn);
+                pos[(size_t)l * stride + i] = (uint32_t)p;
+            }
+        }
+        mats.resize((size_t)n_lists * stride * stride);
+        ORR_TRY(pair_dots_on_lane(lane, n_lists, stride, pos.data(), cnt.data(), mats.data()));
+    }
+    // ---- the greedy pass and the outputs
+    std::vector<int32_t> picks((size_t)take);
+    for (int32_t b = 0; b < B; ++b) {
+        const int32_t n = p_cnt[(size_t)b];
+        const double *m = slot_of[(size_t)b] >= 0 ? mats.data() + (size_t)slot_of[(size_t)b] * stride * stride : nullptr;
+        auto cosine = [m, stride](int32_t i, int32_t j) -> double {
+            if (!m) return 0.0;
+            return scope_near::cosine_of(m[diverse::mat_index(stride, i, j)], m[diverse::mat_index(stride, i, i)], m[diverse::mat_index(stride, j, j)]);
+        };
+        const int32_t kept = d.mode == diverse::Collapse ? diverse::select_collapse(n, take, d.param, cosine, picks.data())
+                                                         : diverse::select_mmr(n, take, d.param, p_scores.data() + (size_t)b * pool, cosine, picks.data());
+        for (int32_t i = 0; i < take; ++i) {
+            const size_t o = (size_t)b * take + i;
+            const bool have = i < kept;
+            out_rows[o] = have ? p_rows[(size_t)b * pool + picks[(size_t)i]] : -1;
+            out_scores[o] = have ? p_scores[(size_t)b * pool + picks[(size_t)i]] : 0.0;
+            if (out_pool_rank) out_pool_rank[o] = have ? picks[(size_t)i] : -1;
+        }
+        out_counts[b] = kept;
+    }
+    return ORR_OK;
+}
+
+int orr_search_batch_diverse(orr_index *idx, int32_t B, int32_t dim, const float *q, const uint8_t *terms_utf8, const uint32_t *term_off,
+                             const uint32_t *query_term_off, int64_t now_ticks, int32_t topk, int64_t candidate_limit, const orr_scope *within,
+                             int32_t pool, int32_t mode, double param, int64_t *out_rows, double *out_scores, int32_t *out_counts,
+                             int32_t *out_pool_rank)
+{
+    static const char *fn = "orr_search_batch_diverse";
+    switch (diverse::first_invalid(!out_rows || !out_scores || !out_counts, topk, pool, mode, param)) {
+    case 0: break;
+    case 1: return fail(ORR_EINVAL, "%s: out_rows, out_scores and out_counts are required", fn);
+    case 2: return fail(ORR_EINVAL, "%s: pool must be in 1 .. %d", fn, diverse::kMaxPool);
+    case 3: return fail(ORR_EINVAL, "%s: topk %d exceeds the pool of %d", fn, topk, pool);
+    case 4: return fail(ORR_EINVAL, "%s: mode must be ORR_DIVERSE_COLLAPSE (0) or ORR_DIVERSE_MMR (1)", fn);
+    case 5: return fail(ORR_EINVAL, "%s: param is NaN", fn);
+    default: return fail(ORR_EINVAL, "%s: lambda must be in [0, 1]", fn);
+    }
+    if (!idx) return fail(ORR_EINVAL, "%s: null index", fn);
+    if (B == 0) return ORR_OK;
+    BatchArgs a{B, dim, q, terms_utf8, term_off, query_term_off, now_ticks, candidate_limit, topk};
+    ORR_TRY(check_batch(idx, a, fn));
+    orr_index *own = nullptr;
+    if (within) ORR_TRY(scope_owner(within, idx, fn, &own));
+    Lane ln = acquire_lane(idx);                       // a search like any other: its own lane, concurrent with the others
+    idx = ln.lane;
+    std::lock_guard<std::mutex> lock(idx->mu);
+    std::shared_lock<std::shared_mutex> rd;
+    if (within) {
+        rd = std::shared_lock<std::shared_mutex>(within->mu);
+        ORR_TRY(scope_owner(within, idx, fn, &own));
+        if (within->n_rows != idx->n_rows) return fail(ORR_ESTATE, "%s: the scope covers %lld rows, the handle %lld", fn, (long long)within->n_rows, (long long)idx->n_rows);
+    }
+    idx->sstats.searches += 1;
+    idx->sstats.queries += B;
+    const int r = diverse_run(idx, fn, a, within, DiverseArgs{pool, mode, param}, out_rows, out_scores, out_counts, out_pool_rank);
+    g_ht.done();
+    return r;
+}
+
+int orr_index_pair_dots(orr_index *idx, int32_t n_lists, const uint32_t *list_off, const int64_t *positions, int32_t stride, double *out)
+{
+    static const char *fn = "orr_index_pair_dots";
+    switch (diverse::first_invalid_pairs(!out, n_lists, !list_off, !positions, stride)) {
+    case 0: break;
+    case 1: return fail(ORR_EINVAL, "%s: out is NULL", fn);
+    case 2: return fail(ORR_EINVAL, "%s: n_lists is negative", fn);
+    case 3: return fail(ORR_EINVAL, "%s: stride must be in 1 .. %d", fn, diverse::kMaxPool);
+    case 4: return fail(ORR_EINVAL, "%s: list_off is NULL", fn);
+    default: return fail(ORR_EINVAL, "%s: positions is NULL", fn);
+    }
+    if (!idx) return fail(ORR_EINVAL, "%s: null index", fn);
+    if (list_off[0] != 0) return fail(ORR_EINVAL, "%s: list_off must start at 0", fn);
+    for (int32_t l = 0; l < n_lists; ++l) {
+        if (list_off[l + 1] < list_off[l]) return fail(ORR_EINVAL, "%s: list_off decreases at list %d", fn, l);
+        if (list_off[l + 1] - list_off[l] > (uint32_t)stride) return fail(ORR_EINVAL, "%s: list %d holds %u positions, stride is %d", fn, l, list_off[l + 1] - list_off[l], stride);
+    }
+    Lane ln = acquire_lane(idx);
+    orr_index *lane = ln.lane;
+    std::lock_guard<std::mutex> lock(lane->mu);
+    if (!lane->sealed) return fail(ORR_ESTATE, "%s: the index is not sealed", fn);
+    for (uint32_t e = 0; e < list_off[n_lists]; ++e)                          // before any launch: the kernel is never handed a row it cannot read
+        if (positions[e] < 0 || positions[e] >= lane->n_rows)
+            return fail(ORR_EINVAL, "%s: positions[%u] = %lld is outside 0 .. %lld", fn, e, (long long)positions[e], (long long)lane->n_rows - 1);
+    if (n_lists == 0) return ORR_OK;
+    std::vector<uint32_t> pos((size_t)n_lists * stride, 0u), cnt((size_t)n_lists, 0u);
+    for (int32_t l = 0; l < n_lists; ++l) {
+        cnt[(size_t)l] = list_off[l + 1] - list_off[l];
+        for (uint32_t i = 0; i < cnt[(size_t)l]; ++i) pos[(size_t)l * stride + i] = (uint32_t)positions[list_off[l] + i];
+    }
+    std::vector<double> mats((size_t)n_lists * stride * stride, 0.0);
+    if (lane->dim > 0) ORR_TRY(pair_dots_on_lane(lane, n_lists, stride, pos.data(), cnt.data(), mats.data()));
+    for (int32_t l = 0; l < n_lists; ++l)                                     // (what lies at or beyond a list's length stays as the caller left it)
+        for (uint32_t i = 0; i < cnt[(size_t)l]; ++i)
+            memcpy(out + ((size_t)l * stride + i) * stride, mats.data() + ((size_t)l * stride + i) * stride, sizeof(double) * cnt[(size_t)l]);
+    return ORR_OK;
 }
 
 int orr_search_shard_scoped(orr_index *idx, int32_t B, int32_t dim, const float *q, const uint8_t *terms_utf8,

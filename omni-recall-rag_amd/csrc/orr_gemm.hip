@@ -1506,4 +1506,115 @@ hipError_t launch_rescore_exact(const float *E, int32_t D, const float *Q, int32
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// K7  pairwise exact dots of short lists of rows (orr_search_batch_diverse, orr_index_pair_dots; rules: orr_diverse_plan.h).
+// One workgroup of diverse::kPairThreads threads owns one list of cnt <= diverse::kMaxPool rows.  It stages a slab of
+// kPairSlab columns of the list's rows in LDS (row stride kPairSlab + 4 floats: row r starts at bank 4 r mod 64, so the
+// 16-byte reads of 16 different rows at one column fall on 64 different banks) and walks the slab once per owned pair
+// (diverse::owned_pair / pair_of: at most kPairsPerThread pairs a thread, i <= j), carrying one binary64 sum per pair in
+// registers across the slabs: each sum is the reference's loop (RecallSearchService.cs:77-82) literally -- the product
+// rounded to binary32, added in binary64, in index order.  Any D > 0: the staging loads are 16 bytes wide where D % 4 == 0
+// and E is 16-byte aligned (VEC), single floats otherwise; the last slab is walked to its own width.  A slot of the tile
+// beyond cnt, a column beyond the slab's width and a position at or above n_rows are never read from E.
+// ---------------------------------------------------------------------------
+constexpr int kPairSlab = 256;                    // columns of one slab
+constexpr int kPairLds = kPairSlab + 4;           // floats of one row of the tile
+static_assert(diverse::kMaxPool * kPairLds * 4 <= 64 * 1024, "the tile is static LDS");
+static_assert(diverse::kPairThreads * diverse::kPairsPerThread >= diverse::kMaxPairs, "every pair of the longest list has an owner");
+
+template <bool VEC>
+__global__ __launch_bounds__(diverse::kPairThreads) void pair_dots_kernel(const float *__restrict__ E, int64_t n_rows, int32_t D,
+                                                                          const uint32_t *__restrict__ pos, const uint32_t *__restrict__ cnt,
+                                                                          int32_t stride, double *__restrict__ out)
+{
+    constexpr int NP = diverse::kPairsPerThread;
+    __shared__ __attribute__((aligned(16))) float tile[diverse::kMaxPool * kPairLds];
+    __shared__ int64_t row_of[diverse::kMaxPool];
+    const int t = threadIdx.x;
+    const int64_t l = blockIdx.x;
+    const int32_t n = min((int32_t)cnt[l], min(stride, diverse::kMaxPool));
+    if (n <= 0) return;                                                     // (the whole workgroup)
+    if (t < n) {
+        const int64_t p = (int64_t)pos[l * stride + t];
+        row_of[t] = p < n_rows ? p : -1;                                    // (never: the host checks every position)
+    }
+    const int32_t np = diverse::pair_count(n);
+    int32_t pi[NP], pj[NP];                                                 // the owned pairs' rows as offsets into the tile
+    bool live[NP];
+    double acc[NP];
+#pragma unroll
+    for (int s = 0; s < NP; ++s) {
+        const int32_t p = diverse::owned_pair(t, s);
+        int32_t i = 0, j = 0;
+        live[s] = p < np;
+        if (live[s]) diverse::pair_of(p, n, &i, &j);
+        pi[s] = i * kPairLds;
+        pj[s] = j * kPairLds;
+        acc[s] = 0.0;
+    }
+    __syncthreads();
+    for (int32_t c0 = 0; c0 < D; c0 += kPairSlab) {
+        const int32_t w = min(kPairSlab, D - c0);                           // columns of this slab
+        if (c0 > 0) __syncthreads();                                        // the slab before is walked
+        if constexpr (VEC) {
+            const int32_t w4 = w >> 2;                                      // (D % 4 == 0: so is w)
+            for (int32_t e = t; e < n * w4; e += diverse::kPairThreads) {
+                const int32_t r = e / w4, k = (e - r * w4) << 2;
+                const int64_t row = row_of[r];
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (row >= 0) v = *reinterpret_cast<const float4 *>(E + row * (int64_t)D + c0 + k);
+                *reinterpret_cast<float4 *>(&tile[r * kPairLds + k]) = v;
+            }
+        } else {
+            for (int32_t e = t; e < n * w; e += diverse::kPairThreads) {
+                const int32_t r = e / w, k = e - r * w;
+                const int64_t row = row_of[r];
+                tile[r * kPairLds + k] = row >= 0 ? E[row * (int64_t)D + c0 + k] : 0.f;
+            }
+        }
+        __syncthreads();
+        int32_t k = 0;
+        for (; k + 4 <= w; k += 4) {
+#pragma unroll
+            for (int s = 0; s < NP; ++s) {
+                const float4 a = *reinterpret_cast<const float4 *>(&tile[pi[s] + k]);
+                const float4 b = *reinterpret_cast<const float4 *>(&tile[pj[s] + k]);
+                float p;
+                p = a.x * b.x; acc[s] += (double)p;
+                p = a.y * b.y; acc[s] += (double)p;
+                p = a.z * b.z; acc[s] += (double)p;
+                p = a.w * b.w; acc[s] += (double)p;
+            }
+        }
+        for (; k < w; ++k) {                                                // the last slab's tail columns (D % 4 != 0)
+#pragma unroll
+            for (int s = 0; s < NP; ++s) {
+                const float p = tile[pi[s] + k] * tile[pj[s] + k];
+                acc[s] += (double)p;
+            }
+        }
+    }
+    double *o = out + l * (int64_t)stride * stride;
+#pragma unroll
+    for (int s = 0; s < NP; ++s) {
+        if (!live[s]) continue;
+        const int32_t i = pi[s] / kPairLds, j = pj[s] / kPairLds;
+        o[diverse::mat_index(stride, i, j)] = acc[s];
+        o[diverse::mat_index(stride, j, i)] = acc[s];
+    }
+}
+
+hipError_t launch_pair_dots(const float *E, int64_t n_rows, int32_t D, const uint32_t *pos, const uint32_t *cnt, int32_t n_lists,
+                            int32_t stride, double *out, hipStream_t s)
+{
+    if (n_lists <= 0) return hipSuccess;
+    if (D <= 0 || stride < 1 || stride > diverse::kMaxPool) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)n_lists), block((unsigned)diverse::kPairThreads);
+    if (D % 4 == 0 && (reinterpret_cast<uintptr_t>(E) & 15) == 0)
+        hipLaunchKernelGGL(pair_dots_kernel<true>, grid, block, 0, s, E, n_rows, D, pos, cnt, stride, out);
+    else
+        hipLaunchKernelGGL(pair_dots_kernel<false>, grid, block, 0, s, E, n_rows, D, pos, cnt, stride, out);
+    return hipGetLastError();
+}
+
 }  // namespace orr

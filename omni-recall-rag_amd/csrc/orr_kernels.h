@@ -13,6 +13,7 @@
 #include "orr_scope_terms_plan.h"
 #include "orr_scope_near_plan.h"
 #include "orr_range_plan.h"
+#include "orr_diverse_plan.h"
 
 #include <atomic>
 
@@ -538,5 +539,14 @@ hipError_t launch_range_collect(const SelEntry *buf, const double *buf_dot, cons
 hipError_t launch_range_collect_dense(const double *dots, int64_t dot_stride, int32_t nq, const double *norm_a, const double *norm_b,
                                       const int64_t *row_ids, int64_t n_rows, const uint32_t *allowed, const double *min_cosine,
                                       range::ListEntry *list, uint32_t *list_cnt, uint32_t list_cap, hipStream_t s);
+
+// ---- diverse search (orr_search_batch_diverse, orr_index_pair_dots; the rules are orr_diverse_plan.h's) ----------------------
+// out[l][i][j] = out[l][j][i] = the exact dot (products rounded to binary32, summed in binary64 in index order) of rows
+// pos[l][i] and pos[l][j] of E for i, j < cnt[l]; the diagonal is a row's self-dot.  Elements at or beyond cnt[l] are neither
+// read nor written.  D > 0, 0 <= cnt[l] <= stride <= diverse::kMaxPool, every listed position below n_rows (the caller's duty:
+// a position at or above n_rows is treated as a zero row, never read).  One workgroup per list: any number of lists.
+hipError_t launch_pair_dots(const float *E, int64_t n_rows, int32_t D, const uint32_t *pos /* [n_lists][stride] */,
+                            const uint32_t *cnt /* [n_lists] */, int32_t n_lists, int32_t stride, double *out /* [n_lists][stride][stride] */,
+                            hipStream_t s);
 
 }  // namespace orr

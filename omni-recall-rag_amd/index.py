@@ -582,6 +582,30 @@ class RecallIndex:
         pass over the shard per launch group.  Takes and returns what range_cosine does."""
         return _range_cosine(N.hip.orr_search_range_cosine_bulk, self._h, qvecs, min_cosine, max_hits, within, True)
 
+    def search_diverse(self, qvecs, queries_terms, now_ticks: int, topk: int, pool: int, mode: str = "collapse", param: float = 0.95,
+                       within: Optional[RecallScope] = None, candidate_limit: int = 300):
+        """orr_search_batch_diverse: the plain search's best `pool` rows of every query (inside `within`, when given), compared
+        with each other by the reference's cosine of the stored rows, and a greedy pass over them in rank order that keeps up
+        to topk: mode "collapse" drops a row whose cosine to a kept one is >= param (max_cosine), mode "mmr" picks by
+        param * score - (1 - param) * (greatest cosine to a kept row) (param = lambda in [0, 1]).  pool is at most 56; nothing
+        outside the pool is looked at, so counts may stay below topk.
+        Returns (rows [B,k] int64, fused scores [B,k] float64, counts [B] int32, pool_rank [B,k] int32) in pick order."""
+        modes = {"collapse": 0, "mmr": 1}
+        if mode not in modes:
+            raise ValueError("mode must be 'collapse' or 'mmr'")
+        B = len(queries_terms)
+        dim, q, _keep = self._query_args(qvecs, B)
+        tpool, toff, qoff = pack_terms(queries_terms)
+        k = max(1, int(topk))
+        rows = np.full((B, k), -1, dtype=np.int64)
+        scores = np.zeros((B, k), dtype=np.float64)
+        counts = np.zeros(B, dtype=np.int32)
+        ranks = np.full((B, k), -1, dtype=np.int32)
+        N.check(N.hip.orr_search_batch_diverse(self._h, B, dim, _ptr(q), _ptr(tpool), _ptr(toff), _ptr(qoff), now_ticks, int(topk),
+                                               int(candidate_limit), within._h if within is not None else None, int(pool), modes[mode],
+                                               float(param), _ptr(rows), _ptr(scores), _ptr(counts), _ptr(ranks)))
+        return rows, scores, counts, ranks
+
     def search_in_scope(self, qvecs, queries_terms, now_ticks: int, topk: int, scope: RecallScope, candidate_limit: int = 300):
         """orr_search_batch_in_scope: search_masked with the scope taken from a handle -- nothing is resolved per call.
         Returns (rows [B,k] int64, scores [B,k] float64, counts [B] int32)."""
@@ -760,6 +784,20 @@ class RecallIndex:
         q = q.reshape(1, -1) if q.ndim == 1 else q
         out = np.empty((q.shape[0], self.rows), dtype=np.float32)
         N.check(N.hip.orr_index_pass_dots(self._h, int(kernel), int(q.shape[0]), int(q.shape[1]), _ptr(q), _ptr(out)))
+        return out
+
+    def pair_dots(self, lists) -> np.ndarray:
+        """orr_index_pair_dots: for every list of up to 56 row positions (candidate order: order_key - row_base) the matrix of the
+        exact dots of its rows with each other (the diagonal: a row's exact norm).  Returns [n_lists, stride, stride] float64,
+        stride the longest list's length; what lies beyond a list's own length is NaN."""
+        lists = [np.ascontiguousarray(l, dtype=np.int64).reshape(-1) for l in lists]
+        stride = max([1] + [len(l) for l in lists])
+        off = np.zeros(len(lists) + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(l) for l in lists])
+        pos = np.concatenate(lists) if lists else np.zeros(0, np.int64)
+        pos = np.ascontiguousarray(pos if len(pos) else np.zeros(1, np.int64), dtype=np.int64)
+        out = np.full((len(lists), stride, stride), np.nan, dtype=np.float64)
+        N.check(N.hip.orr_index_pair_dots(self._h, len(lists), _ptr(off), _ptr(pos), stride, _ptr(out)))
         return out
 
     def keyword_bitmaps(self, terms: Sequence[bytes], form: int = -1, mid: int = -1) -> dict:
