@@ -787,8 +787,11 @@ int orr_index_screen_i8_dots(orr_index *idx, int32_t B, int32_t dim, const float
 
 /* Diagnostics for the claims the screens' exactness rests on besides the GEMM's integers: every constant and every approximate
  * dot that a certificate charges can be compared with a high-precision restatement (tests/test_gpu_screen_bounds.py).
- * Out of scope: the kernels that exist in fused form only (the bf16 stream K2g and the one-product bf16x1 form), and running a
- * fused epilogue with a floor of zero.
+ * Out of scope of THESE entry points: the kernels that exist in fused form only (the bf16 stream K2g and the one-product bf16x1
+ * form), and running a fused epilogue with a floor of zero.  Those, the floor a search screens against and what its fused
+ * epilogue keeps are seen through orr_index_capture_screen below, inside a search itself (tests/test_gpu_screen_survivors.py).
+ * Still out of scope: a pass in several row ranges (2M+ rows with query terms) is captured as the whole it is, the ranges'
+ * launches are not told apart; the cluster forms capture per shard handle only.
  *
  * orr_index_screen_i8_consts: what the int8 shadow holds per row -- out_scale / out_rel_err / out_rel_hat [rows] and
  * out_rowf [rows][4] -- and, for the B given queries (B may be 0), what the searches' quantisation makes of them: out_s1 [B],
@@ -808,6 +811,48 @@ int orr_index_screen_i8_stream_dots(orr_index *idx, int32_t B, int32_t dim, cons
  * MFMA form (K2s), the queries sent in groups of 32 as the pass sends them (up to 16 queries and 17..32 run different kernels);
  * kernel 1: the queries split into bf16 hi/lo halves, then the unfused three-product split-bf16 GEMM.  dim % 64 == 0. */
 int orr_index_pass_dots(orr_index *idx, int32_t kernel, int32_t B, int32_t dim, const float *q, float *out);
+
+/* Diagnostic: the two-stage screen of a search, seen directly (tests/test_gpu_screen_survivors.py): the floor each query was
+ * screened against and the survivors' buffers as the screen (and, in a masked or grouped search, the scope filter behind it) left
+ * them, in front of the exact tail.
+ *
+ * orr_index_capture_screen(idx, 1) arms the handle: the FIRST pass through the two-stage screen of the next search on it --
+ * plain, shard, masked, grouped or scoped, whatever the entry point -- synchronises its stream at that point and copies the
+ * fields below to host memory the handle owns; the tail then runs as always.  One capture per arming: later passes of the same
+ * call (the repeats of overflowed queries) and later searches record nothing until the handle is armed again, which also drops
+ * the capture it holds.  enabled = 0 disarms and keeps what was captured.  The capture changes neither which kernels run nor
+ * their arguments nor the records returned; unarmed, a pass pays one branch on the host.  Searching one handle from several
+ * threads while it is armed is the caller's error: which of them is captured is not defined.  A view handle of the caller's
+ * (orr_index_view) is armed and read on its own.  ORR_EINVAL: a NULL index; ORR_ESTATE: the index is not sealed.
+ *
+ * orr_index_captured_screen reports and fetches.  With all five arrays NULL it fills *info only: sizes first.  With all five
+ * given, B and cap must equal info->B and info->cap of the capture held:
+ *   out_floor_key [B]       the floor keys (key > floor_key <=> score >= F; 0: no floor, everything is kept)
+ *   out_L [B]               L, the lower bound of the query's exact kth best score that the floor stands for (-inf: none)
+ *   out_cnt [B]             pairs the screen counted per query; more than cap: the buffer overflowed and holds the first cap
+ *   out_key / out_pos [B][cap]   the buffers' entries (slots at or beyond min(cnt, cap) are left as they are): the screen's key
+ *                           of the pair -- all ones where it was kept without one -- and the row's position (candidate order)
+ * ORR_EINVAL, in this order, before the handle is looked at and with nothing written: info NULL; some but not all of the arrays
+ * NULL; arrays given with B <= 0 or cap == 0; a NULL index.  Then ORR_ESTATE: the index is not sealed, or nothing was captured
+ * since the handle was armed; ORR_EINVAL: B or cap differ from the capture's (nothing written, info neither). */
+typedef struct orr_screen_capture {
+    int32_t B;              /* queries of the captured pass */
+    int32_t kth;            /* the floor's rank: max(1, topK) */
+    uint32_t cap;           /* entries per query of the survivors' buffers in that pass */
+    int32_t screen;         /* the screen that ran: 1 screen_i8_fused, 2 screen_gemv_i8, 3 screen_gemv_bf16, 4 screen_bf16_fused,
+                               5 gemm_dot_bf16x1_fused */
+    int32_t tile_form;      /* screen 1: 0 eight-wave, 1 four-wave 32 x 32 x 32, 2 four-wave 16 x 16 x 64 tile; else -1 */
+    int32_t scope;          /* 0 no scope mask, 1 one shared scope, 2 groups of scopes */
+    int32_t floor_form;     /* the prefix's floor: 0 full ranking, 1 per-lane maxima, 2 wave maxima; -1: a stream's or a masked sample's own ranking */
+    int32_t reserved;
+    int64_t n;              /* participating rows: positions [0, n) were screened */
+    int64_t prefix_rows;    /* rows [0, prefix_rows) gave the floor; with a scope: the first prefix_rows in-scope rows (grouped: at most) */
+    double eps3;            /* bound of the keys the floor was selected from, as the floor's launch got it */
+    double eps1;            /* bound of the screen's keys (0: the int8 forms add their per-pair bound inside the kernel) */
+} orr_screen_capture;
+int orr_index_capture_screen(orr_index *idx, int32_t enabled);
+int orr_index_captured_screen(orr_index *idx, orr_screen_capture *info, int32_t B, uint32_t cap, uint64_t *out_floor_key, double *out_L,
+                              uint32_t *out_cnt, uint64_t *out_key, uint32_t *out_pos);
 
 /* Diagnostic: the pair matrices orr_search_batch_diverse forms its cosines from (tests/test_gpu_diverse.py).  List l is the
  * positions[list_off[l] .. list_off[l + 1]) (candidate order: order_key - row_base); out[l][i][j] = out[l][j][i] is the exact dot

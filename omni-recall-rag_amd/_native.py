@@ -51,6 +51,12 @@ class OrrSearchStats(C.Structure):
                                          "survivor_capacity", "vocab_tokens", "kw_hits_total", "kw_passes", "pass_mode")] + [("reserved", C.c_int64 * 1)]
 
 
+class OrrScreenCapture(C.Structure):
+    _fields_ = [("B", C.c_int32), ("kth", C.c_int32), ("cap", C.c_uint32), ("screen", C.c_int32), ("tile_form", C.c_int32),
+                ("scope", C.c_int32), ("floor_form", C.c_int32), ("reserved", C.c_int32), ("n", C.c_int64), ("prefix_rows", C.c_int64),
+                ("eps3", C.c_double), ("eps1", C.c_double)]
+
+
 def _load(path: str) -> C.CDLL:
     if not os.path.exists(path):
         raise ImportError(f"{path} is missing: build it first (python -c 'import __graft_entry__ as g; g.build()'). "
@@ -166,6 +172,10 @@ hip.orr_index_screen_i8_stream_dots.restype = C.c_int
 hip.orr_index_screen_i8_stream_dots.argtypes = [_vp, _i32, _i32, _vp, _i32, _vp]
 hip.orr_index_pass_dots.restype = C.c_int
 hip.orr_index_pass_dots.argtypes = [_vp, _i32, _i32, _i32, _vp, _vp]
+hip.orr_index_capture_screen.restype = C.c_int
+hip.orr_index_capture_screen.argtypes = [_vp, _i32]
+hip.orr_index_captured_screen.restype = C.c_int
+hip.orr_index_captured_screen.argtypes = [_vp, C.POINTER(OrrScreenCapture), _i32, C.c_uint32, _vp, _vp, _vp, _vp, _vp]
 hip.orr_index_pair_dots.restype = C.c_int
 hip.orr_index_pair_dots.argtypes = [_vp, _i32, _vp, _vp, _i32, _vp]
 hip.orr_index_keyword_bitmaps.restype = C.c_int
@@ -305,7 +315,7 @@ EXPORTED_HIP_SYMBOLS = [
     "orr_abi_version", "orr_device_count", "orr_last_error", "orr_index_create", "orr_index_destroy",
     "orr_index_append", "orr_index_seal", "orr_index_rows", "orr_index_dim", "orr_search_batch",
     "orr_search_shard", "orr_search_shard_ex", "orr_search_batch_scoped", "orr_search_batch_masked", "orr_search_batch_masked_groups", "orr_search_shard_scoped", "orr_search_shard_masked", "orr_index_scope_count", "orr_merge_candidates", "orr_merge_candidates_ex", "orr_index_set_profiling", "orr_index_kernel_stats",
-    "orr_index_save", "orr_index_load", "orr_index_set_row_base", "orr_index_set_option", "orr_index_screen_dots", "orr_index_screen_i8_dots", "orr_index_screen_i8_consts", "orr_index_screen_i8_stream_dots", "orr_index_pass_dots", "orr_index_keyword_bitmaps", "orr_index_view",
+    "orr_index_save", "orr_index_load", "orr_index_set_row_base", "orr_index_set_option", "orr_index_screen_dots", "orr_index_screen_i8_dots", "orr_index_screen_i8_consts", "orr_index_screen_i8_stream_dots", "orr_index_pass_dots", "orr_index_capture_screen", "orr_index_captured_screen", "orr_index_keyword_bitmaps", "orr_index_view",
     "orr_index_delete_rows", "orr_index_update_rows", "orr_index_insert_rows", "orr_cluster_insert_rows", "orr_index_live_rows", "orr_index_compact", "orr_cluster_compact", "orr_index_search_stats",
     "orr_cluster_create", "orr_cluster_destroy", "orr_cluster_shards", "orr_cluster_shard", "orr_cluster_seal", "orr_cluster_rows",
     "orr_cluster_search_batch", "orr_cluster_search_batch_scoped", "orr_cluster_search_batch_masked", "orr_cluster_search_stats", "orr_cluster_set_option",

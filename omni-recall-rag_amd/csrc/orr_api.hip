@@ -141,6 +141,17 @@ struct PendingEvent {
     hipEvent_t start, stop;
 };
 
+// orr_index_capture_screen: what the first two-stage pass after the arming left in front of its exact tail, on the handle.
+struct ScreenCapture {
+    std::atomic<int> armed{0};
+    bool have = false;
+    orr_screen_capture info{};
+    std::vector<unsigned long long> floor_key;
+    std::vector<double> L;
+    std::vector<uint32_t> cnt;
+    std::vector<orr::SelEntry> buf;
+};
+
 }  // namespace
 
 struct orr_index {
@@ -273,6 +284,9 @@ struct orr_index {
     LanePool lanes{this};
     bool internal_lane = false;            // this view belongs to its parent's lane pool (not handed to the caller)
     std::atomic<int> user_views{0};        // views handed to the caller (orr_index_view) that are still alive: they pin the shard's layout
+
+    // orr_index_capture_screen, on the handle the caller holds (a lane of the pool records into its owner's)
+    ScreenCapture capture;
 
     // profiling
     int profiling = 0;                     // 0 off, 1 every kernel, 2 only the pass over all rows (the kernel a roofline is quoted on)
@@ -2328,6 +2342,51 @@ int orr_index_pass_dots(orr_index *idx, int32_t kernel, int32_t B, int32_t dim, 
     return ORR_OK;
 }
 
+int orr_index_capture_screen(orr_index *idx, int32_t enabled)
+{
+    if (!idx) return fail(ORR_EINVAL, "orr_index_capture_screen: null index");
+    LanePool::Exclusive all(pool_of(idx));             // no search in flight on any lane while the switch moves
+    std::lock_guard<std::mutex> lock(idx->mu);
+    if (!idx->sealed) return fail(ORR_ESTATE, "orr_index_capture_screen: the index is not sealed");
+    ScreenCapture &c = idx->capture;
+    if (enabled) {
+        c.have = false;
+        c.floor_key.clear(); c.L.clear(); c.cnt.clear(); c.buf.clear();
+    }
+    c.armed.store(enabled ? 1 : 0, std::memory_order_relaxed);
+    return ORR_OK;
+}
+
+int orr_index_captured_screen(orr_index *idx, orr_screen_capture *info, int32_t B, uint32_t cap, uint64_t *out_floor_key, double *out_L,
+                              uint32_t *out_cnt, uint64_t *out_key, uint32_t *out_pos)
+{
+    if (!info) return fail(ORR_EINVAL, "orr_index_captured_screen: info is NULL");
+    const int given = (out_floor_key != nullptr) + (out_L != nullptr) + (out_cnt != nullptr) + (out_key != nullptr) + (out_pos != nullptr);
+    if (given != 0 && given != 5) return fail(ORR_EINVAL, "orr_index_captured_screen: give all five arrays or none");
+    if (given && (B <= 0 || cap == 0)) return fail(ORR_EINVAL, "orr_index_captured_screen: arrays given with B <= 0 or cap == 0");
+    if (!idx) return fail(ORR_EINVAL, "orr_index_captured_screen: null index");
+    LanePool::Exclusive all(pool_of(idx));
+    std::lock_guard<std::mutex> lock(idx->mu);
+    if (!idx->sealed) return fail(ORR_ESTATE, "orr_index_captured_screen: the index is not sealed");
+    const ScreenCapture &c = idx->capture;
+    if (!c.have) return fail(ORR_ESTATE, "orr_index_captured_screen: nothing was captured since the handle was armed");
+    if (given && (B != c.info.B || cap != c.info.cap)) return fail(ORR_EINVAL, "orr_index_captured_screen: B or cap differ from the capture's");
+    *info = c.info;
+    if (!given) return ORR_OK;
+    const size_t nb = (size_t)c.info.B, kc = (size_t)c.info.cap;
+    for (size_t b = 0; b < nb; ++b) {
+        out_floor_key[b] = c.floor_key[b];
+        out_L[b] = c.L[b];
+        out_cnt[b] = c.cnt[b];
+        const size_t filled = std::min<size_t>(c.cnt[b], kc);
+        for (size_t i = 0; i < filled; ++i) {
+            out_key[b * kc + i] = c.buf[b * kc + i].key;
+            out_pos[b * kc + i] = c.buf[b * kc + i].pos;
+        }
+    }
+    return ORR_OK;
+}
+
 int orr_index_set_profiling(orr_index *idx, int32_t enabled)
 {
     if (!idx) return fail(ORR_EINVAL, "null index");
@@ -2923,7 +2982,7 @@ int plan_form(orr_index *idx, const BatchArgs &a, int32_t kprime, int64_t n, con
     }
     // the prefix's floor: 0 its rows ranked in full; 1 per-lane maxima, sorted; 2 wave maxima, nothing sorted (where 16 per
     // segment are at least 8 k candidates per query)
-    static const char *prefix_env = getenv("ORR_PREFIX_FULL_RANKING");        // =1: form 0; =2: form 1 (A/B)
+    const char *prefix_env = getenv("ORR_PREFIX_FULL_RANKING");               // =1: form 0; =2: form 1 (A/B and the floor's tests: read at every plan)
     p.prefix_floor_form = (prefix_env && atoi(prefix_env) == 1) ? 0
                           : ((int64_t)p.fused_sample_seg * 16 >= 8 * (int64_t)std::max<int32_t>(1, a.topk) && !(prefix_env && atoi(prefix_env) == 2)) ? 2 : 1;
     // Large shards go through the int8 screening GEMM in FOUR ROW RANGES: only the first range's count words are formed
@@ -3333,7 +3392,40 @@ int screen_i8_in_ranges(orr_index *idx, const BatchArgs &a, const PassPlan &p, i
 // The floor of a masked pass: the first mask.sample in-scope rows become buffer entries, the exact re-score gives them exact
 // keys, and their kth best per query is the floor's base -- a lower bound of the final kth best whatever the scope looks like.
 // The keys are exact scores of the device's arithmetic: the floor carries the certificate's own bound, no screen's.
-int masked_floor(orr_index *idx, const BatchArgs &a, const PassIo &io, int32_t kth, orr::FloorOut floor)
+// orr_index_capture_screen: the handle whose capture a pass on this lane records into (an internal lane: its owner's).
+orr_index *capture_handle(orr_index *lane) { return lane->internal_lane && lane->parent ? const_cast<orr_index *>(lane->parent) : lane; }
+
+// The capture point of screen_two_stage: behind the screen and the scope filter, in front of the exact tail.  Waits for the
+// stream, copies the floor, the counters and the buffers of all B queries to the handle and disarms it; launches nothing.
+int capture_screen(orr_index *idx, const BatchArgs &a, const PassPlan &p, int64_t n, const PassIo &io, const orr::FloorOut &floor,
+                   const orr::FusedEpilogue &epi, uint32_t kCap, int32_t kth, hipStream_t s)
+{
+    ScreenCapture &c = capture_handle(idx)->capture;
+    const size_t B = (size_t)a.B;
+    c.armed.store(0, std::memory_order_relaxed);            // one capture per arming, whether or not this one succeeds
+    c.have = false;
+    c.floor_key.resize(B); c.L.resize(B); c.cnt.resize(B); c.buf.resize(B * (size_t)kCap);
+    HIP_TRY(hipMemcpyAsync(c.floor_key.data(), floor.floor_key, sizeof(unsigned long long) * B, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(c.L.data(), floor.L, sizeof(double) * B, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(c.cnt.data(), epi.cnt, sizeof(uint32_t) * B, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(c.buf.data(), epi.buf, sizeof(orr::SelEntry) * B * (size_t)kCap, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    orr_screen_capture &o = c.info;
+    o = orr_screen_capture{};
+    o.B = a.B; o.kth = kth; o.cap = kCap;
+    o.screen = (int32_t)p.screen;
+    o.tile_form = p.screen == Screen::I8Ranges ? orr::screen_i8_form(a.B, p.range_row[1], idx->dim, epi) : -1;
+    o.scope = io.groups ? 2 : io.mask ? 1 : 0;
+    o.floor_form = io.mask || p.stream() ? -1 : p.prefix_floor_form;
+    o.n = n;
+    o.prefix_rows = io.mask ? io.mask->sample : std::min<int64_t>(p.dotf_rows, n);
+    o.eps3 = floor.eps3; o.eps1 = floor.eps1;
+    c.have = true;
+    return ORR_OK;
+}
+
+// (floor.eps3 becomes the bound the sample's exact keys carry: what the floor's launch gets, and what a capture reports)
+int masked_floor(orr_index *idx, const BatchArgs &a, const PassIo &io, int32_t kth, orr::FloorOut &floor)
 {
     const int32_t B = a.B;
     hipStream_t s = idx->stream;
@@ -3488,6 +3580,7 @@ int screen_two_stage(orr_index *idx, const BatchArgs &a, const PassPlan &p, int3
         Timed t(idx, "mask_survivors", 16.0 * (double)B * (double)kCap);
         HIP_TRY(orr::launch_mask_survivors(io.mask->bm, io.mask->n_clip, epi.cnt, kCap, epi.buf, B, s));
     }
+    if (capture_handle(idx)->capture.armed.load(std::memory_order_relaxed)) ORR_TRY(capture_screen(idx, a, p, n, io, floor, epi, kCap, kth, s));
     ORR_TRY(two_stage_tail(idx, a, kprime, n, io, epi, kCap, buf_lists, host_records, rec_bytes, Rescore::BufferExact, 0.0, s));
     if (io.groups) HIP_TRY(orr::launch_mask_trailers_grouped(io.d_cand, B, kprime, io.groups->d_took, s));
     else if (io.mask) HIP_TRY(orr::launch_mask_trailers(io.d_cand, B, kprime, io.mask->took, s));

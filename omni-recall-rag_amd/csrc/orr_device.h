@@ -56,12 +56,15 @@ __device__ __forceinline__ double key_score(unsigned long long k)
 __device__ __forceinline__ void two_stage_floor_of(unsigned long long tau_k, double eps3, double eps1, unsigned long long *floor_key,
                                                    double *L_out)
 {
-    if (tau_k <= 1ull) {                    // fewer than k rows in the prefix, or a NaN: keep everything (-> overflow -> retry)
+    const double sk = key_score(tau_k);
+    // fewer than k rows in the prefix, or a NaN: keep everything (-> overflow -> retry).  Likewise a k-th key that is no finite
+    // score -- the all-ones key a stream gives a pair whose dot is not finite (a NaN query: every row of its prefix): L came
+    // out NaN beside a floor key of 0 (tests/test_gpu_screen_survivors.py).
+    if (tau_k <= 1ull || !(fabs(sk) <= 1.7976931348623157e308)) {
         *floor_key = 0ull;
         *L_out = -__builtin_huge_val();
         return;
     }
-    const double sk = key_score(tau_k);
     const double L = sk - eps3;
     const double F = L - eps1 - 1e-9 * (1.0 + fabs(sk));
     const unsigned long long fk = score_key(F);

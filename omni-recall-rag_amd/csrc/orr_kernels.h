@@ -266,6 +266,9 @@ hipError_t launch_query_count_planes(KwView kw, int32_t B, int64_t n_rows, int64
                                      int64_t row_first = 0, int64_t row_end = -1, int32_t bits = 4);
 // whether launch_screen_i8 runs its 16 x 16 x 64 form for this shape (the only form that reads two-bit count words)
 bool screen_i8_uses_tile16(int32_t B, int64_t n_rows, int32_t D, int64_t plane_stride);
+// which form of the tile launch_screen_i8 runs for this shape and epilogue: 0 eight-wave, 1 four-wave 32 x 32 x 32, 2 four-wave
+// 16 x 16 x 64 (orr_index_screen_i8_dots numbers them the same way)
+int32_t screen_i8_form(int32_t B, int64_t n_rows, int32_t D, const FusedEpilogue &epi);
 // qf16 (optional, [B]): the same constants made safe for a NaN-dropping test (fused_epilogue16) -- finite qx / qz, a query with
 // anything non-finite turned into "every pair passes" (qx = qz = 0, floor -inf) -- with .w = the largest finite query bound
 // term of the batch in EVERY entry.

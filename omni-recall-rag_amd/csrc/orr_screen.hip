@@ -1679,7 +1679,7 @@ hipError_t launch_screen_i8(const void *q_tiled, int32_t B, const void *e_tiled,
         // 129+ queries: the tile on 16 x 16 x 64 MFMAs, unless the shard is so large that its epilogue's 32-bit word offsets
         // inside a pair of count planes would not do (then the 32 x 32 x 32 form).  Measured on one box, eight-wave form long
         // gone: 1M x 3072 rows x 256 queries 0.89 -> 0.85 ms, x 1024: 3.23 -> 2.92 ms; C3 (4 launches) 2.23 -> 2.13 ms each.
-        const bool tile16 = screen_i8_uses_tile16(B, n_rows, D, epi.plane_stride) && epi.qf16 != nullptr;
+        const bool tile16 = screen_i8_form(B, n_rows, D, epi) == 2;
         if (epi.count_bits == 2 && !tile16) return hipErrorInvalidValue;   // (only the 16 x 16 x 64 form reads two-bit count words)
         if (tile16 && B > 256) ORR_LAUNCH_I8W16(false);
         else if (tile16 && B > 128) ORR_LAUNCH_I8W16(true);
@@ -1702,6 +1702,12 @@ hipError_t launch_screen_i8(const void *q_tiled, int32_t B, const void *e_tiled,
         }
     }
     return hipGetLastError();
+}
+
+int32_t screen_i8_form(int32_t B, int64_t n_rows, int32_t D, const FusedEpilogue &epi)
+{
+    if (!(B > 64 && D / 64 >= kS4NB)) return 0;
+    return screen_i8_uses_tile16(B, n_rows, D, epi.plane_stride) && epi.qf16 != nullptr ? 2 : 1;
 }
 
 bool screen_i8_uses_tile16(int32_t B, int64_t n_rows, int32_t D, int64_t plane_stride)

@@ -786,6 +786,25 @@ class RecallIndex:
         N.check(N.hip.orr_index_pass_dots(self._h, int(kernel), int(q.shape[0]), int(q.shape[1]), _ptr(q), _ptr(out)))
         return out
 
+    def capture_screen(self, enabled: bool = True) -> None:
+        """orr_index_capture_screen: arm the handle -- the first pass through the two-stage screen of the next search records its
+        floor and its survivors' buffers (one capture per arming) -- or disarm it."""
+        N.check(N.hip.orr_index_capture_screen(self._h, 1 if enabled else 0))
+
+    def captured_screen(self) -> dict:
+        """orr_index_captured_screen: the capture the handle holds.  The plan scalars (B, kth, cap, screen, tile_form, scope,
+        floor_form, n, prefix_rows, eps3, eps1), floor_key [B] uint64, L [B] float64, cnt [B] uint32 and the buffers key [B, cap]
+        uint64 / pos [B, cap] uint32, of which a query's first min(cnt, cap) slots are filled (the rest: key 0, pos 2^32 - 1)."""
+        info = N.OrrScreenCapture()
+        N.check(N.hip.orr_index_captured_screen(self._h, C.byref(info), 0, 0, None, None, None, None, None))
+        B, cap = int(info.B), int(info.cap)
+        out = {"floor_key": np.zeros(B, np.uint64), "L": np.zeros(B, np.float64), "cnt": np.zeros(B, np.uint32),
+               "key": np.zeros((B, cap), np.uint64), "pos": np.full((B, cap), 0xFFFFFFFF, np.uint32)}
+        N.check(N.hip.orr_index_captured_screen(self._h, C.byref(info), B, cap, _ptr(out["floor_key"]), _ptr(out["L"]), _ptr(out["cnt"]),
+                                                _ptr(out["key"]), _ptr(out["pos"])))
+        out.update({name: getattr(info, name) for name, _ in N.OrrScreenCapture._fields_ if name != "reserved"})
+        return out
+
     def pair_dots(self, lists) -> np.ndarray:
         """orr_index_pair_dots: for every list of up to 56 row positions (candidate order: order_key - row_base) the matrix of the
         exact dots of its rows with each other (the diagonal: a row's exact norm).  Returns [n_lists, stride, stride] float64,

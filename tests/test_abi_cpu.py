@@ -61,7 +61,38 @@ def test_argument_errors_map_to_einval():
     assert P.native.hip.orr_index_rows(None) == 0
 
 
-QUERIES = ["azure", "what is the kubernetes", "  Azure\tAZURE azure  Cosmos ", "the of and", "a b c　d",
+def test_screen_capture_argument_errors_come_before_the_handle_with_nothing_written():
+    """orr_index_capture_screen / orr_index_captured_screen: every argument error that needs no handle is ORR_EINVAL on a NULL
+    one, in the header's order, each case holding exactly one error more than the one behind it, and writes nothing.  (What a
+    live handle answers -- not sealed, nothing captured, sizes that differ from the capture's -- needs a device:
+    tests/test_gpu_screen_survivors.py.)"""
+    P = pkg()
+    N, E = P.native, P.native.ORR_EINVAL
+    fn, err = N.hip.orr_index_captured_screen, N.hip.orr_last_error
+    assert N.hip.orr_index_capture_screen(None, 1) == E and b"null index" in err()
+    assert N.hip.orr_index_capture_screen(None, 0) == E
+    info = N.OrrScreenCapture()
+    assert C.sizeof(N.OrrScreenCapture) == 64
+    B, cap = 3, 64
+    arrays = [np.full(B, 7, np.uint64), np.full(B, 7.0), np.full(B, 7, np.uint32), np.full(B * cap, 7, np.uint64), np.full(B * cap, 7, np.uint32)]
+    ptrs = [a.ctypes.data for a in arrays]
+    assert fn(None, None, B, cap, *ptrs) == E and b"info is NULL" in err()
+    for missing in range(5):                                              # some but not all of the arrays
+        some = list(ptrs)
+        some[missing] = None
+        assert fn(None, C.byref(info), B, cap, *some) == E and b"all five arrays or none" in err(), missing
+    assert fn(None, C.byref(info), B, cap, ptrs[0], None, None, None, None) == E and b"all five arrays or none" in err()
+    for bad_b, bad_cap in ((0, cap), (-1, cap), (B, 0)):                  # arrays given, sizes that can belong to no capture
+        assert fn(None, C.byref(info), bad_b, bad_cap, *ptrs) == E and b"B <= 0 or cap == 0" in err()
+    assert fn(None, C.byref(info), B, cap, *ptrs) == E and b"null index" in err()
+    assert fn(None, C.byref(info), 0, 0, None, None, None, None, None) == E and b"null index" in err()
+    assert bytes(info) == bytes(C.sizeof(info)) and all((a == 7).all() for a in arrays)
+    assert callable(P.RecallIndex.capture_screen) and callable(P.RecallIndex.captured_screen)
+    header = open(os.path.join(ROOT, "include", "omnirecall_hip.h")).read()
+    assert "Searching one handle from several" in header and "orr_index_capture_screen" in open(os.path.join(ROOT, "DESIGN.md")).read()
+
+
+QUERIES = ["azure","what is the kubernetes", "  Azure\tAZURE azure  Cosmos ", "the of and", "a b c　d",
            "x\x1cy", "ÄRGER ärger", "İstanbul i̇stanbul", "What backend did we choose?", "   ", "",
            "ǅ Ǆ ǆ ΑΒΓ Σίσυφος ЖЁ", "tab sep line"]
 
