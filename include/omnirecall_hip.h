@@ -659,7 +659,8 @@ int orr_search_range_cosine_bulk(orr_index *idx, int32_t B, int32_t dim, const f
 /* ---- diverse search: the results compared WITH EACH OTHER ------------------------------------------------------------------
  * Every search above compares a query with rows.  This one also compares the best rows of a query with each other and returns
  * topk of them that are not near-copies of one another: a near-duplicate collapse of the ranked list, or maximal marginal
- * relevance (MMR).  The cluster form, pools beyond 56 and a per-document cap are not offered.
+ * relevance (MMR).  The cluster form and pools beyond 56 are not offered; a per-document cap is
+ * orr_search_batch_per_key below.
  *
  * 1. The pool.  within == NULL: exactly what orr_search_batch returns for topk = pool; with a scope: exactly what
  *    orr_search_batch_in_scope returns for topk = pool -- rows, unrounded fused scores, order, and all their rules
@@ -696,6 +697,68 @@ int orr_search_batch_diverse(orr_index *idx, int32_t B, int32_t dim, const float
                              int32_t pool, int32_t mode, double param,
                              int64_t *out_rows, double *out_scores, int32_t *out_counts,
                              int32_t *out_pool_rank /* [B][max(1,topk)], may be NULL */);
+
+/* ---- row keys and the per-key search: at most m rows per document, exact beyond the pool ------------------------------------
+ * Every search above ranks chunks; a corpus cut by a sliding-window chunker lets one relevant document own the first ten places.
+ * An orr_keys is a handle like orr_scope: one int64_t key per row of one sealed shard, resident on its device (8 bytes per row);
+ * ORR_KEY_NONE means "no key".  A key is whatever the host groups by, typically a document number.
+ *
+ *   orr_keys_create  every row starts at ORR_KEY_NONE, then what orr_keys_set does.
+ *   orr_keys_set     the ids are resolved through the id table exactly as orr_scope_create resolves them (host or device memory,
+ *                    keys in the same memory as row_ids); keys[i] is stored at every live row of row_ids[i]; ids that name no
+ *                    live row are passed over; *out_set (may be NULL) = the entries that named a live row.  For an id listed
+ *                    twice with different keys the row gets one of them: it is UNSPECIFIED which.  n == 0 is legal.
+ *   orr_keys_get     host ids -> host keys; an unknown or dead id reads ORR_KEY_NONE.
+ *   orr_keys_rows    the live rows whose key is not ORR_KEY_NONE (one counting launch); -1 on an orphaned handle or NULL.
+ *   orr_keys_destroy NULL is allowed.
+ * Maintenance: orr_index_delete_rows and orr_index_update_rows need nothing; orr_index_compact and orr_index_insert_rows carry
+ * every registered orr_keys through the move with ONE keys_remap launch per call, from the sources scope_remap reads; a new row
+ * reads ORR_KEY_NONE until the host sets it.  Insertion allocates the grown columns in its allocation phase: ORR_ENOMEM leaves
+ * shard, scopes and keys as they were.  Lifetime and threads are orr_scope's: registered with the owning index, usable through
+ * any view, held shared by searches and exclusively by set and destroy; create, set, get and rows take a lane;
+ * orr_index_destroy frees the device part and orphans the handle (ORR_ESTATE from then on, rows -1, destroy still frees the
+ * host part).  Not saved in the shard file, like scopes.
+ *
+ * orr_scope_create_keys: "search inside these documents" without listing a chunk id -- the live rows whose key equals one of
+ * keys[0 .. n_keys) (host; duplicates count once; listing ORR_KEY_NONE selects the rows without a key), an ordinary orr_scope
+ * from then on.  n_keys 0 .. 65,536; 0 gives the empty scope.  One keys_member launch.  ORR_EINVAL in this order: out NULL,
+ * n_keys outside its range, keys NULL with n_keys > 0, a NULL keys handle, a NULL index; then keys of another shard
+ * (ORR_EINVAL) or orphaned (ORR_ESTATE).
+ *
+ * orr_search_batch_per_key.  Let R be the complete ranking of the call's candidates: what orr_search_batch (within == NULL) or
+ * orr_search_batch_in_scope would return with topk = all rows -- rows, unrounded fused scores bit for bit, order, the NaN
+ * order, candidate_limit counting live rows (of the scope).  Walk R from the top: a row is kept when its key is ORR_KEY_NONE or
+ * fewer than max_per_key kept rows carry its key; stop at take = max(1, topk) kept.  out_rows / out_scores / out_keys
+ * [B][take] in walk order, out_counts [B]; unused slots -1 / 0.0 / ORR_KEY_NONE.  THE CALL LOOKS OUTSIDE THE POOL:
+ * out_counts[b] < take only when the candidates ran out.  max_per_key 1 .. INT32_MAX (at max_per_key >= take the result is the
+ * plain search's first take rows bit for bit); max(1, topk) <= pool <= 56 as in the diverse search.
+ * The rounds (csrc/orr_per_key_plan.h): round 1 is the plain (in-scope) search for topk = pool; a query whose walk has not
+ * kept take rows goes on, in slices of at most 64 queries, to rounds over the FROZEN candidate set of round 1 without the rows
+ * of closed keys (keys_exclude: 64 exclusion bitmaps in one pass over the rows) and without the rows already seen
+ * (keys_clear_seen), with no further limit, the slice's scopes sharing ONE grouped search; one keys_gather per round reads the
+ * rows' keys.  out_rounds [B] (may be NULL) = the rounds run, <= take.  The search statistics move as for the searches run.
+ * ORR_EINVAL before the handle is looked at, the outputs untouched, in this order: out_rows, out_scores, out_keys or out_counts
+ * NULL; pool outside 1 .. 56; max(1, topk) > pool; max_per_key < 1; keys NULL; then a NULL index, and, unless B == 0 (which
+ * writes nothing), the errors of the underlying search.  Then ORR_EINVAL for a scope or keys of another shard, ORR_ESTATE for an
+ * orphaned scope or keys.
+ * Out of scope: the cluster forms and sharded.py, the record (shard) form, the service mirror and the micro-batcher, saving
+ * keys in the shard file, pools above 56, and combining with the diverse search. */
+#define ORR_KEY_NONE INT64_MIN
+typedef struct orr_keys orr_keys;
+int     orr_keys_create(orr_index *idx, int64_t n, const int64_t *row_ids /* host or device */,
+                        const int64_t *keys /* same memory as row_ids */, orr_keys **out);
+int     orr_keys_set(orr_keys *k, int64_t n, const int64_t *row_ids, const int64_t *keys, int64_t *out_set /* may be NULL */);
+int     orr_keys_get(orr_keys *k, int64_t n, const int64_t *row_ids /* host */, int64_t *out_keys /* host */);
+int64_t orr_keys_rows(const orr_keys *k);
+void    orr_keys_destroy(orr_keys *k);
+int     orr_scope_create_keys(orr_index *idx, const orr_keys *k, int32_t n_keys, const int64_t *keys /* host */, orr_scope **out);
+int orr_search_batch_per_key(orr_index *idx, int32_t B, int32_t dim, const float *q,
+                             const uint8_t *terms_utf8, const uint32_t *term_off, const uint32_t *query_term_off,
+                             int64_t now_ticks, int32_t topk, int64_t candidate_limit,
+                             const orr_scope *within /* or NULL: every live row */,
+                             const orr_keys *keys, int32_t max_per_key, int32_t pool,
+                             int64_t *out_rows, double *out_scores, int64_t *out_keys, int32_t *out_counts,
+                             int32_t *out_rounds /* [B], may be NULL */);
 
 /* orr_search_shard_masked with the scope taken from a handle: the record form of orr_search_batch_in_scope, the shard half of
  * orr_cluster_search_batch_in_scope.  The contract is orr_search_shard_masked's, unchanged: [B][kprime+1] records and the

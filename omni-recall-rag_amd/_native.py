@@ -27,6 +27,7 @@ ORR_CAND_TRAILER, ORR_CAND_DOT_EXACT, ORR_CAND_DEAD = 1, 2, 16
 ORR_SCOPE_AND, ORR_SCOPE_OR, ORR_SCOPE_ANDNOT = 0, 1, 2
 ORR_TERMS_ALL, ORR_TERMS_ANY = 0, 1
 ORR_NEAR_ALL, ORR_NEAR_ANY = 0, 1
+ORR_KEY_NONE = -(1 << 63)
 
 
 class OrrConfig(C.Structure):
@@ -130,6 +131,20 @@ hip.orr_search_range_cosine_bulk.restype = C.c_int
 hip.orr_search_range_cosine_bulk.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp]
 hip.orr_search_batch_diverse.restype = C.c_int
 hip.orr_search_batch_diverse.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _vp, _i32, _i32, C.c_double, _vp, _vp, _vp, _vp]
+hip.orr_keys_create.restype = C.c_int
+hip.orr_keys_create.argtypes = [_vp, _i64, _vp, _vp, C.POINTER(_vp)]
+hip.orr_keys_set.restype = C.c_int
+hip.orr_keys_set.argtypes = [_vp, _i64, _vp, _vp, _vp]
+hip.orr_keys_get.restype = C.c_int
+hip.orr_keys_get.argtypes = [_vp, _i64, _vp, _vp]
+hip.orr_keys_rows.restype = _i64
+hip.orr_keys_rows.argtypes = [_vp]
+hip.orr_keys_destroy.restype = None
+hip.orr_keys_destroy.argtypes = [_vp]
+hip.orr_scope_create_keys.restype = C.c_int
+hip.orr_scope_create_keys.argtypes = [_vp, _vp, _i32, _vp, C.POINTER(_vp)]
+hip.orr_search_batch_per_key.restype = C.c_int
+hip.orr_search_batch_per_key.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]
 hip.orr_search_shard_in_scope.restype = C.c_int
 hip.orr_search_shard_in_scope.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, _vp, _i64, _vp]
 hip.orr_search_shard_in_scopes.restype = C.c_int
@@ -322,6 +337,7 @@ EXPORTED_HIP_SYMBOLS = [
     "orr_scope_create", "orr_scope_create_ticks", "orr_scope_create_terms", "orr_scope_create_near", "orr_scope_add_ids", "orr_scope_combine", "orr_scope_rows", "orr_scope_row_ids", "orr_scope_destroy",
     "orr_search_batch_in_scope", "orr_search_batch_in_scopes", "orr_search_shard_in_scope", "orr_search_shard_in_scopes", "orr_search_range_cosine", "orr_search_range_cosine_bulk",
     "orr_search_batch_diverse", "orr_index_pair_dots",
+    "orr_keys_create", "orr_keys_set", "orr_keys_get", "orr_keys_rows", "orr_keys_destroy", "orr_scope_create_keys", "orr_search_batch_per_key",
     "orr_cluster_scope_create", "orr_cluster_scope_create_ticks", "orr_cluster_scope_create_terms", "orr_cluster_scope_create_near", "orr_cluster_scope_add_ids", "orr_cluster_scope_combine",
     "orr_cluster_scope_rows", "orr_cluster_scope_row_ids", "orr_cluster_scope_shard", "orr_cluster_scope_destroy", "orr_cluster_search_batch_in_scope",
     "orr_cluster_search_batch_in_scopes", "orr_cluster_search_range_cosine", "orr_cluster_search_range_cosine_bulk",

@@ -268,7 +268,10 @@ struct orr_index {
     // scope handles (orr_scope) of this shard, on the OWNING index, under scope_mu: deletes clear their rows, compaction and
     // insertion carry them along, orr_index_destroy orphans them
     std::vector<orr_scope *> scopes;
-    int opt_mask_screen = 0;           // "mask_screen": 0 by the cost rule, 1 whenever eligible, 2 never (orr_mask_plan.h)
+    // row keys (orr_keys) of this shard, registered like the scopes, under scope_mu: compaction and insertion carry them along
+    // (KeysRemap), orr_index_destroy orphans them
+    std::vector<orr_keys *> key_cols;
+    int opt_mask_screen = 0;          // "mask_screen": 0 by the cost rule, 1 whenever eligible, 2 never (orr_mask_plan.h)
     int64_t opt_mask_part_rows = mask::kDefaultPartRows;   // "mask_part_rows": scoped rows per part of the list path
 
     // search workspace
@@ -306,6 +309,15 @@ struct orr_scope {
     uint32_t *chunks = nullptr;                // device [scope_chunks(words)], as launch_scope_counts leaves them
     std::atomic<int64_t> live{0};              // set bits
     int64_t n_clip_all = 0;                    // one past the last set bit
+};
+
+// Row keys: one int64 per row of one sealed shard (ORR_KEY_NONE: no key), resident on its device.  Lifetime and threads are a
+// scope's: searches hold mu shared, orr_keys_set and orr_keys_destroy hold it exclusively, maintenance swaps the column under it.
+struct orr_keys {
+    std::atomic<orr_index *> owner{nullptr};   // the owning index; nullptr once that was destroyed (the handle is orphaned)
+    mutable std::shared_mutex mu;
+    int64_t n_rows = 0;                        // the shard's rows the column covers
+    int64_t *d_key = nullptr;                  // device [max(n_rows, 1)]
 };
 
 // orr_scope_destroy and the orphaning in orr_index_destroy exclude each other, whatever threads release the two handles: a
@@ -762,6 +774,13 @@ void orr_index_destroy(orr_index *idx)
             sc->owner.store(nullptr);
         }
         idx->scopes.clear();
+        for (orr_keys *k : idx->key_cols) {            // row keys likewise
+            std::unique_lock<std::shared_mutex> w(k->mu);
+            if (k->d_key) (void)hipFree(k->d_key);
+            k->d_key = nullptr;
+            k->owner.store(nullptr);
+        }
+        idx->key_cols.clear();
     } else {
         idx->emb_shadow.p = nullptr; idx->emb_shadow.cap = 0;
         for (DevBuf *b : {&idx->emb_i8, &idx->i8_scale, &idx->i8_rel_err, &idx->i8_rel_hat, &idx->i8_rowf, &idx->tok_bm, &idx->tok_bm_index}) { b->p = nullptr; b->cap = 0; }
@@ -1522,6 +1541,63 @@ struct ScopeRemap {
     }
 };
 
+// Carries every registered orr_keys of a shard through the same move, in the same three steps: alloc (the new columns, in the
+// allocation phase: ORR_ENOMEM leaves every column as it was), run (ONE keys_remap launch for all columns, from the sources
+// scope_remap reads), commit (the handles take their new columns).  A new row reads ORR_KEY_NONE until the host sets it.  The
+// caller holds LanePool::Exclusive and -- through its ScopeRemap, whose alloc comes first -- the shard's scope_mu.
+struct KeysRemap {
+    orr_index *idx = nullptr;
+    int64_t new_rows = 0;
+    std::vector<int64_t *> cols;                       // the new columns, one per handle of idx->key_cols
+    DevBuf ptrs;                                       // device: [old columns x G][new columns x G]
+    bool committed = false;
+    ~KeysRemap()
+    {
+        if (!committed) for (int64_t *c : cols) if (c) (void)hipFree(c);
+        ptrs.release();
+    }
+    int alloc(orr_index *index, int64_t rows)
+    {
+        idx = index; new_rows = rows;
+        const size_t G = idx->key_cols.size();
+        if (G == 0) return ORR_OK;
+        for (size_t i = 0; i < G; ++i) {
+            int64_t *c = nullptr;
+            ORR_TRY(dev_alloc(&c, (size_t)std::max<int64_t>(rows, 1)));
+            cols.push_back(c);
+        }
+        return ptrs.reserve(sizeof(void *) * 2 * G);
+    }
+    int run(const int64_t *src, int64_t first)
+    {
+        const size_t G = cols.size();
+        if (G == 0) return ORR_OK;
+        hipStream_t s = idx->stream;
+        std::vector<const void *> h(2 * G);
+        for (size_t i = 0; i < G; ++i) { h[i] = idx->key_cols[i]->d_key; h[G + i] = cols[i]; }
+        HIP_TRY(hipMemcpy(ptrs.p, h.data(), sizeof(void *) * 2 * G, hipMemcpyHostToDevice));
+        {
+            Timed t(idx, "keys_remap", 8.0 * (double)(new_rows - first) + 16.0 * (double)G * (double)new_rows);
+            HIP_TRY(orr::launch_keys_remap(src, first, new_rows, ptrs.as<const int64_t *>(), reinterpret_cast<int64_t *const *>(ptrs.as<int64_t *>() + G),
+                                           (int32_t)G, s));
+        }
+        HIP_TRY(hipStreamSynchronize(s));
+        collect_events(idx);
+        return ORR_OK;
+    }
+    void commit()
+    {
+        committed = true;
+        for (size_t i = 0; i < cols.size(); ++i) {
+            orr_keys *k = idx->key_cols[i];
+            std::unique_lock<std::shared_mutex> w(k->mu);
+            if (k->d_key) (void)hipFree(k->d_key);
+            k->d_key = cols[i];
+            k->n_rows = new_rows;
+        }
+    }
+};
+
 int orr_index_delete_rows(orr_index *idx, int64_t n, const int64_t *row_ids, int64_t *out_deleted)
 {
     if (out_deleted) *out_deleted = 0;
@@ -1664,6 +1740,8 @@ int orr_index_compact(orr_index *idx, int64_t *out_removed)
     }
     ScopeRemap scopes;                                 // (deleted rows are already absent from every scope: the remap only closes gaps)
     ORR_TRY(scopes.alloc(idx, n_new));
+    KeysRemap key_cols;                                // (under the scope_mu `scopes` holds)
+    ORR_TRY(key_cols.alloc(idx, n_new));
     DevBuf d_live;
     ORR_TRY(d_live.reserve(sizeof(int64_t) * (size_t)std::max<int64_t>(n_new, 1)));
     int r = ORR_OK;
@@ -1725,6 +1803,7 @@ int orr_index_compact(orr_index *idx, int64_t *out_removed)
             if (w) HIP_TRY(hipMemcpy(idx->d_post_rows, rows.data(), sizeof(uint32_t) * w, hipMemcpyHostToDevice));
             idx->n_postings = w;
         }
+        ORR_TRY(key_cols.run(d_live.as<int64_t>(), 0));
         return scopes.run(d_live.as<int64_t>(), 0);    // (while d_live is there)
     };
     r = body();
@@ -1754,6 +1833,7 @@ int orr_index_compact(orr_index *idx, int64_t *out_removed)
     idx->lanes.update_shared([](LanePool::Shared &sh) { sh.dead_count = 0; });
     for (orr_index *l : idx->lanes.drain()) orr_index_destroy(l);
     if (out_removed) *out_removed = n_dead;
+    key_cols.commit();
     return scopes.commit();
 }
 
@@ -1908,6 +1988,8 @@ int orr_index_insert_rows(orr_index *idx, int64_t n, int32_t dim, const float *e
     if (!new_dead.empty()) ORR_TRY(idx->d_dead.reserve(sizeof(int64_t) * new_dead.size()));
     ScopeRemap scopes;                                 // the grown bitmaps of every scope handle
     ORR_TRY(scopes.alloc(idx, total));
+    KeysRemap key_cols;                                // the grown columns of every orr_keys (under the scope_mu `scopes` holds)
+    ORR_TRY(key_cols.alloc(idx, total));
 
     auto body = [&]() -> int {
         HIP_TRY(hipMemcpyAsync(fr.src, src.data(), sizeof(int64_t) * (size_t)n_moved, hipMemcpyHostToDevice, s));
@@ -1973,6 +2055,7 @@ int orr_index_insert_rows(orr_index *idx, int64_t n, int32_t dim, const float *e
         if (!new_dead.empty()) HIP_TRY(hipMemcpyAsync(idx->d_dead.p, new_dead.data(), sizeof(int64_t) * new_dead.size(), hipMemcpyHostToDevice, s));
         HIP_TRY(hipStreamSynchronize(s));
         add_phase_stat(idx, "insert_scalars_and_upload", t_phase, 48.0 * (double)n_moved + 4.0 * (double)ti_new.post_rows.size());
+        ORR_TRY(key_cols.run(fr.src, first));          // a new row has no key
         return scopes.run(fr.src, first);              // a new row is in no scope; fr.src goes with fr
     };
     const int r = body();
@@ -1996,6 +2079,7 @@ int orr_index_insert_rows(orr_index *idx, int64_t n, int32_t dim, const float *e
     }
     idx->n_rows = total;
     const int scopes_r = scopes.commit();              // (reported at the end: the rows are in whatever it says)
+    key_cols.commit();
     idx->dead = new_dead;                              // (their number is unchanged: the lanes' shared dead_count stays)
     idx->id_index.clear();
     drop_scope_table(idx, scopes.reg);
@@ -4868,9 +4952,12 @@ int masked_sub_batch(orr_index *idx, const BatchArgs &orig, const GroupArgs &ga,
     std::vector<int64_t> rows(nb * (size_t)take);
     std::vector<double> scores(nb * (size_t)take);
     std::vector<int32_t> counts(nb);
+    std::vector<int64_t> keys(orig.out_keys ? nb * (size_t)take : 0);      // (out_keys is in the numbering of the call that receives it)
+    if (orig.out_keys) cur.out_keys = keys.data();
     ORR_TRY(masked_batch(idx, cur, src, rows.data(), scores.data(), counts.data()));
     for (size_t i = 0; i < nb; ++i) {
         const size_t b = (size_t)ids[i];
+        if (orig.out_keys) memcpy(orig.out_keys + b * take, keys.data() + i * take, sizeof(int64_t) * take);
         memcpy(out_rows + b * take, rows.data() + i * take, sizeof(int64_t) * take);
         memcpy(out_scores + b * take, scores.data() + i * take, sizeof(double) * take);
         if (out_counts) out_counts[b] = counts[i];
@@ -6947,6 +7034,556 @@ int orr_index_pair_dots(orr_index *idx, int32_t n_lists, const uint32_t *list_of
         for (uint32_t i = 0; i < cnt[(size_t)l]; ++i)
             memcpy(out + ((size_t)l * stride + i) * stride, mats.data() + ((size_t)l * stride + i) * stride, sizeof(double) * cnt[(size_t)l]);
     return ORR_OK;
+}
+
+// ---- row keys and the per-key search (orr_keys, orr_search_batch_per_key; the rules are orr_per_key_plan.h's) -----------------
+
+static_assert(per_key::kSelWidth == orr::kSelWidth, "orr_per_key_plan.h restates the selection width");
+static_assert(per_key::kMaxSlots <= orr::kMaxGatherGroups, "a slice's temporary scopes go through one grouped call");
+
+// The shard of a key column, or the reason it cannot be used: ORR_ESTATE orphaned; with idx: ORR_EINVAL another shard.
+static int keys_owner(const orr_keys *k, const orr_index *idx, const char *fn, orr_index **own)
+{
+    *own = k->owner.load();
+    if (!*own) return fail(ORR_ESTATE, "%s: the keys are orphaned: their index was destroyed", fn);
+    if (idx && owner_of(idx) != *own) return fail(ORR_EINVAL, "%s: the keys belong to another shard", fn);
+    return ORR_OK;
+}
+
+// orr_keys_set behind its locks (the lane, its lock, the column exclusively): ids and keys (host or device, the same memory)
+// come to the device, keys_scatter stores behind scope_lookup's search.
+static int keys_set_held(orr_index *lane, orr_keys *k, int64_t n, const int64_t *row_ids, const int64_t *keys, int64_t *out_set)
+{
+    if (out_set) *out_set = 0;
+    if (n <= 0 || lane->n_rows <= 0) return ORR_OK;
+    ORR_TRY(bind_device(lane));
+    ORR_TRY(ensure_scope_table(lane));
+    const orr_index *own = owner_of(lane);
+    hipStream_t s = lane->stream;
+    DevBuf in;                                         // [ids x n][keys x n][counter]
+    auto body = [&]() -> int {
+        ORR_TRY(in.reserve(sizeof(int64_t) * (2 * (size_t)n + 1)));
+        int64_t *d_ids = in.as<int64_t>(), *d_keys = d_ids + n;
+        unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(d_keys + n);
+        HIP_TRY(hipMemcpyAsync(d_ids, row_ids, sizeof(int64_t) * (size_t)n, hipMemcpyDefault, s));
+        HIP_TRY(hipMemcpyAsync(d_keys, keys, sizeof(int64_t) * (size_t)n, hipMemcpyDefault, s));
+        HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), s));
+        {
+            Timed t(lane, "keys_scatter", 24.0 * (double)n);
+            HIP_TRY(orr::launch_keys_scatter(own->scope_tab_ids, own->scope_tab_pos, lane->n_rows, d_ids, d_keys, n, own->d_dead.as<int64_t>(),
+                                             (int32_t)own->dead.size(), k->d_key, d_cnt, s));
+        }
+        unsigned long long cnt = 0;
+        HIP_TRY(hipMemcpyAsync(&cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        collect_events(lane);
+        if (out_set) *out_set = (int64_t)cnt;
+        return ORR_OK;
+    };
+    const int r = body();
+    if (r != ORR_OK) (void)hipStreamSynchronize(s);
+    in.release();
+    return r;
+}
+
+int orr_keys_create(orr_index *idx, int64_t n, const int64_t *row_ids, const int64_t *keys, orr_keys **out)
+{
+    static const char *fn = "orr_keys_create";
+    if (!out) return fail(ORR_EINVAL, "%s: out is NULL", fn);
+    if (n < 0) return fail(ORR_EINVAL, "%s: n is negative", fn);
+    if (n > 0 && (!row_ids || !keys)) return fail(ORR_EINVAL, "%s: row_ids or keys is NULL with %lld entries", fn, (long long)n);
+    if (!idx) return fail(ORR_EINVAL, "%s: null index", fn);
+    Lane ln = acquire_lane(idx);
+    orr_index *lane = ln.lane;
+    std::lock_guard<std::mutex> lock(lane->mu);
+    if (!lane->sealed) return fail(ORR_ESTATE, "%s: the index is not sealed", fn);
+    ORR_TRY(bind_device(lane));
+    orr_keys *k = new (std::nothrow) orr_keys();
+    if (!k) return fail(ORR_ENOMEM, "out of host memory");
+    k->n_rows = lane->n_rows;
+    int r = dev_alloc(&k->d_key, (size_t)std::max<int64_t>(k->n_rows, 1));
+    if (r == ORR_OK) {
+        Timed t(lane, "keys_fill_none", 8.0 * (double)k->n_rows);
+        if (orr::launch_keys_fill_none(k->d_key, k->n_rows, lane->stream) != hipSuccess) r = fail(ORR_EDEVICE, "%s: the fill failed", fn);
+    }
+    if (r == ORR_OK) r = keys_set_held(lane, k, n, row_ids, keys, nullptr);
+    if (r == ORR_OK && hipStreamSynchronize(lane->stream) != hipSuccess) r = fail(ORR_EDEVICE, "%s: device failure", fn);
+    if (r != ORR_OK) {
+        (void)hipStreamSynchronize(lane->stream);
+        (void)hipGetLastError();
+        if (k->d_key) (void)hipFree(k->d_key);
+        delete k;
+        return r;
+    }
+    orr_index *own = const_cast<orr_index *>(owner_of(lane));
+    k->owner.store(own);
+    { std::lock_guard<std::mutex> g(own->scope_mu); own->key_cols.push_back(k); }
+    *out = k;
+    return ORR_OK;
+}
+
+int orr_keys_set(orr_keys *k, int64_t n, const int64_t *row_ids, const int64_t *keys, int64_t *out_set)
+{
+    static const char *fn = "orr_keys_set";
+    if (n < 0) return fail(ORR_EINVAL, "%s: n is negative", fn);
+    if (n > 0 && (!row_ids || !keys)) return fail(ORR_EINVAL, "%s: row_ids or keys is NULL with %lld entries", fn, (long long)n);
+    if (!k) return fail(ORR_EINVAL, "%s: null keys", fn);
+    orr_index *own = nullptr;
+    ORR_TRY(keys_owner(k, nullptr, fn, &own));
+    Lane ln = acquire_lane(own);
+    orr_index *lane = ln.lane;
+    std::lock_guard<std::mutex> lock(lane->mu);
+    std::unique_lock<std::shared_mutex> w(k->mu);
+    ORR_TRY(keys_owner(k, nullptr, fn, &own));
+    return keys_set_held(lane, k, n, row_ids, keys, out_set);
+}
+
+int orr_keys_get(orr_keys *k, int64_t n, const int64_t *row_ids, int64_t *out_keys)
+{
+    static const char *fn = "orr_keys_get";
+    if (n < 0) return fail(ORR_EINVAL, "%s: n is negative", fn);
+    if (n > 0 && (!row_ids || !out_keys)) return fail(ORR_EINVAL, "%s: row_ids or out_keys is NULL with %lld entries", fn, (long long)n);
+    if (!k) return fail(ORR_EINVAL, "%s: null keys", fn);
+    orr_index *own = nullptr;
+    ORR_TRY(keys_owner(k, nullptr, fn, &own));
+    Lane ln = acquire_lane(own);
+    orr_index *lane = ln.lane;
+    std::lock_guard<std::mutex> lock(lane->mu);
+    std::shared_lock<std::shared_mutex> rd(k->mu);
+    ORR_TRY(keys_owner(k, nullptr, fn, &own));
+    if (n == 0) return ORR_OK;
+    if (lane->n_rows <= 0) { for (int64_t i = 0; i < n; ++i) out_keys[i] = ORR_KEY_NONE; return ORR_OK; }
+    ORR_TRY(bind_device(lane));
+    ORR_TRY(ensure_scope_table(lane));
+    hipStream_t s = lane->stream;
+    DevBuf io;                                         // [ids x n][keys x n]
+    auto body = [&]() -> int {
+        ORR_TRY(io.reserve(sizeof(int64_t) * 2 * (size_t)n));
+        int64_t *d_ids = io.as<int64_t>(), *d_out = d_ids + n;
+        HIP_TRY(hipMemcpyAsync(d_ids, row_ids, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, s));
+        {
+            Timed t(lane, "keys_gather", 24.0 * (double)n);
+            HIP_TRY(orr::launch_keys_gather(k->d_key, lane->n_rows, d_ids, n, own->scope_tab_ids, own->scope_tab_pos, own->d_dead.as<int64_t>(),
+                                            (int32_t)own->dead.size(), d_out, s));
+        }
+        HIP_TRY(hipMemcpyAsync(out_keys, d_out, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        collect_events(lane);
+        return ORR_OK;
+    };
+    const int r = body();
+    if (r != ORR_OK) (void)hipStreamSynchronize(s);
+    io.release();
+    return r;
+}
+
+int64_t orr_keys_rows(const orr_keys *k)
+{
+    if (!k) return -1;
+    orr_index *own = k->owner.load();
+    if (!own) return -1;
+    Lane ln = acquire_lane(own);
+    orr_index *lane = ln.lane;
+    std::lock_guard<std::mutex> lock(lane->mu);
+    std::shared_lock<std::shared_mutex> rd(k->mu);
+    if (!k->owner.load()) return -1;
+    if (lane->n_rows <= 0) return 0;
+    if (bind_device(lane) != ORR_OK) return -1;
+    hipStream_t s = lane->stream;
+    DevBuf cnt;
+    unsigned long long h = 0;
+    bool ok = cnt.reserve(sizeof(unsigned long long)) == ORR_OK && hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long), s) == hipSuccess;
+    if (ok) {
+        Timed t(lane, "keys_count", 8.0 * (double)lane->n_rows);
+        ok = orr::launch_keys_count(k->d_key, lane->n_rows, own->d_dead.as<int64_t>(), (int32_t)own->dead.size(), cnt.as<unsigned long long>(), s) == hipSuccess;
+    }
+    ok = ok && hipMemcpyAsync(&h, cnt.p, sizeof(h), hipMemcpyDeviceToHost, s) == hipSuccess;
+    ok = hipStreamSynchronize(s) == hipSuccess && ok;
+    collect_events(lane);
+    cnt.release();
+    return ok ? (int64_t)h : -1;
+}
+
+void orr_keys_destroy(orr_keys *k)
+{
+    if (!k) return;
+    std::lock_guard<std::mutex> life(g_scope_life_mu); // (the owning index is not destroyed meanwhile)
+    orr_index *own = k->owner.load();
+    if (own) {                                         // (the shard's maintenance holds scope_mu while it walks its columns)
+        std::lock_guard<std::mutex> g(own->scope_mu);
+        own->key_cols.erase(std::remove(own->key_cols.begin(), own->key_cols.end(), k), own->key_cols.end());
+    }
+    {
+        std::unique_lock<std::shared_mutex> w(k->mu);  // waits for the searches that hold it
+        if (k->owner.load()) {
+            (void)hipSetDevice(own->device);
+            if (k->d_key) (void)hipFree(k->d_key);
+        }
+        k->d_key = nullptr;
+    }
+    delete k;
+}
+
+int orr_scope_create_keys(orr_index *idx, const orr_keys *k, int32_t n_keys, const int64_t *keys, orr_scope **out)
+{
+    static const char *fn = "orr_scope_create_keys";
+    switch (per_key::first_invalid_scope_keys(!out, n_keys, !keys, !k)) {
+    case 0: break;
+    case 1: return fail(ORR_EINVAL, "%s: out is NULL", fn);
+    case 2: return fail(ORR_EINVAL, "%s: n_keys must be in 0 .. %d", fn, per_key::kMaxScopeKeys);
+    case 3: return fail(ORR_EINVAL, "%s: keys is NULL with %d keys", fn, n_keys);
+    default: return fail(ORR_EINVAL, "%s: null keys handle", fn);
+    }
+    if (!idx) return fail(ORR_EINVAL, "%s: null index", fn);
+    orr_index *own = nullptr;
+    ORR_TRY(keys_owner(k, idx, fn, &own));
+    const std::vector<int64_t> table = per_key::member_table(keys, n_keys);
+    return make_scope(idx, fn, out, [&](orr_index *lane, orr_scope *sc) -> int {
+        std::shared_lock<std::shared_mutex> rd(k->mu);
+        ORR_TRY(keys_owner(k, lane, fn, &own));
+        if (k->n_rows != lane->n_rows) return fail(ORR_ESTATE, "%s: the keys cover %lld rows, the handle %lld", fn, (long long)k->n_rows, (long long)lane->n_rows);
+        const orr_index *o = owner_of(lane);
+        hipStream_t s = lane->stream;
+        if (table.empty() || lane->n_rows <= 0) {      // the empty scope
+            HIP_TRY(hipMemsetAsync(sc->bm, 0, sizeof(uint32_t) * (size_t)sc->words, s));
+            return ORR_OK;
+        }
+        DevBuf tab;
+        auto body = [&]() -> int {
+            ORR_TRY(tab.reserve(sizeof(int64_t) * table.size()));
+            HIP_TRY(hipMemcpyAsync(tab.p, table.data(), sizeof(int64_t) * table.size(), hipMemcpyHostToDevice, s));
+            {
+                Timed t(lane, "keys_member", 8.0 * (double)lane->n_rows + 4.0 * (double)sc->words);
+                HIP_TRY(orr::launch_keys_member(k->d_key, lane->n_rows, tab.as<int64_t>(), (int32_t)table.size(), sc->bm, sc->words, s));
+            }
+            {
+                Timed t(lane, "scope_clear_positions", 12.0 * (double)o->dead.size());
+                HIP_TRY(orr::launch_scope_clear_positions(sc->bm, sc->words, o->d_dead.as<int64_t>(), (int64_t)o->dead.size(), s));
+            }
+            HIP_TRY(hipStreamSynchronize(s));          // (the table goes with this frame)
+            return ORR_OK;
+        };
+        const int r = body();
+        if (r != ORR_OK) (void)hipStreamSynchronize(s);
+        tab.release();
+        return r;
+    });
+}
+
+namespace {
+
+// What a per-key call owns from its second round on: the frozen candidate set, the slice's exclusion bitmaps with their chunk
+// counts, the union table, the seen pairs, the gather's staging.
+struct PerKeyWork {
+    DevBuf c_bm, ex_bm, ex_chunks, tab, seen, limits, gio;
+    PinnedBuf pin;                                     // [live u32 x 64][took u32 x 64][clip i64 x 64]
+    int64_t words = 0;
+    bool frozen = false;
+    std::vector<float> q_down;                         // device-resident queries come down once for the sub-batches
+    ~PerKeyWork()
+    {
+        for (DevBuf *b : {&c_bm, &ex_bm, &ex_chunks, &tab, &seen, &limits, &gio}) b->release();
+        pin.release();
+    }
+};
+
+// out[i] = the key of position pos[i] (ORR_KEY_NONE for a negative one): ONE keys_gather launch, ends synchronised
+int per_key_gather(orr_index *lane, const orr_keys *keys, DevBuf &io, const std::vector<int64_t> &pos, std::vector<int64_t> &out)
+{
+    const size_t n = pos.size();
+    out.assign(n, ORR_KEY_NONE);
+    if (n == 0) return ORR_OK;
+    hipStream_t s = lane->stream;
+    ORR_TRY(io.reserve(sizeof(int64_t) * 2 * n));
+    int64_t *d_pos = io.as<int64_t>(), *d_out = d_pos + n;
+    HIP_TRY(hipMemcpyAsync(d_pos, pos.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, s));
+    {
+        Timed t(lane, "keys_gather", 24.0 * (double)n);
+        HIP_TRY(orr::launch_keys_gather(keys->d_key, lane->n_rows, d_pos, (int64_t)n, nullptr, nullptr, nullptr, 0, d_out, s));
+    }
+    HIP_TRY(hipMemcpyAsync(out.data(), d_out, sizeof(int64_t) * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    collect_events(lane);
+    return ORR_OK;
+}
+
+// The frozen candidate set C of a call as a bitmap, built once when a second round is first needed: the rows that took part in
+// round 1 -- `within`'s bits (or the live rows) below the clip position of the call's candidate_limit.
+int per_key_freeze(orr_index *lane, const BatchArgs &a, const orr_scope *within, PerKeyWork &w)
+{
+    if (w.frozen) return ORR_OK;
+    const orr_index *own = owner_of(lane);
+    hipStream_t s = lane->stream;
+    w.words = (int64_t)(scope::bitmap_bytes(lane->n_rows) / 4);
+    ORR_TRY(w.c_bm.reserve(sizeof(uint32_t) * (size_t)w.words));
+    int64_t n_clip = 0;
+    if (!within) {
+        n_clip = participating_rows(lane, a.candidate_limit);
+    } else {
+        const int64_t live = within->live.load(), took = std::min<int64_t>(live, std::max<int64_t>(1, a.candidate_limit));
+        n_clip = within->n_clip_all;
+        if (took < live && took > 0) {
+            ORR_TRY(lane->pin_mask.reserve(sizeof(int64_t)));
+            {
+                Timed t(lane, "mask_clip", 4.0 * (double)orr::kScopeChunkWords + 4.0 * (double)orr::scope_chunks(w.words));
+                HIP_TRY(orr::launch_mask_clip(within->bm, within->words, within->chunks, (uint32_t)took, lane->pin_mask.as<int64_t>(), s));
+            }
+            HIP_TRY(hipStreamSynchronize(s));
+            collect_events(lane);
+            n_clip = *lane->pin_mask.as<int64_t>();
+        }
+    }
+    n_clip = std::max<int64_t>(0, std::min<int64_t>(n_clip, lane->n_rows));
+    {
+        Timed t(lane, "scope_fill_range", 4.0 * (double)w.words);
+        HIP_TRY(orr::launch_scope_fill_range(w.c_bm.as<uint32_t>(), w.words, 0, n_clip, s));
+    }
+    if (within) {
+        Timed t(lane, "scope_combine", 12.0 * (double)w.words);
+        HIP_TRY(orr::launch_scope_combine(w.c_bm.as<uint32_t>(), within->bm, w.words, ORR_SCOPE_AND, s));
+    } else {
+        Timed t(lane, "scope_clear_positions", 12.0 * (double)own->dead.size());
+        HIP_TRY(orr::launch_scope_clear_positions(w.c_bm.as<uint32_t>(), w.words, own->d_dead.as<int64_t>(), (int64_t)own->dead.size(), s));
+    }
+    w.frozen = true;
+    return ORR_OK;
+}
+
+// One round beyond the first for the unfinished queries `ids` (ascending, at most per_key::kMaxSlots) of the call `a` (vectors in
+// host memory): ONE keys_exclude launch into the call's temporary scope bitmaps, at most one keys_clear_seen behind it, the
+// counts the grouped stages ask of a scope, ONE search through grouped_batch (masked_batch for a slice of one query) over
+// temporary scopes that are never registered with the index, and the round's rows with their positions: [ids.size()][pool].
+int per_key_round(orr_index *lane, const BatchArgs &a, const orr_keys *keys, int32_t pool, const std::vector<int32_t> &ids,
+                  const std::vector<per_key::State> &st, PerKeyWork &w, std::vector<int64_t> &r_rows, std::vector<double> &r_scores,
+                  std::vector<int64_t> &r_pos, std::vector<int32_t> &r_cnt)
+{
+    const int32_t S = (int32_t)ids.size();
+    hipStream_t s = lane->stream;
+    const int64_t words = w.words;
+    const int32_t n_chunks = orr::scope_chunks(words);
+    // ---- the union table of the slots' closed keys, the seen pairs
+    std::vector<const std::set<int64_t> *> closed((size_t)S);
+    for (int32_t i = 0; i < S; ++i) closed[(size_t)i] = &st[(size_t)ids[(size_t)i]].closed;
+    std::vector<int64_t> tk;
+    std::vector<uint64_t> tm;
+    per_key::build_table(closed, tk, tm);
+    const size_t n_tab = tk.size();
+    std::vector<int64_t> seen_pos;
+    std::vector<int32_t> seen_slot;
+    for (int32_t i = 0; i < S; ++i)
+        for (int64_t p : st[(size_t)ids[(size_t)i]].seen) { seen_pos.push_back(p); seen_slot.push_back(i); }
+    const size_t n_seen = seen_pos.size();
+    ORR_TRY(w.ex_bm.reserve(sizeof(uint32_t) * (size_t)S * (size_t)words));
+    ORR_TRY(w.ex_chunks.reserve(sizeof(uint32_t) * (size_t)S * (size_t)n_chunks));
+    ORR_TRY(w.tab.reserve(16 * std::max<size_t>(n_tab, 1)));
+    ORR_TRY(w.seen.reserve(12 * std::max<size_t>(n_seen, 1)));
+    ORR_TRY(w.limits.reserve(sizeof(int64_t) * per_key::kMaxSlots + 2 * sizeof(uint32_t) * per_key::kMaxSlots));      // [limit][live][took]
+    ORR_TRY(w.pin.reserve((4 + 4 + 8) * (size_t)per_key::kMaxSlots));
+    int64_t *d_tk = w.tab.as<int64_t>();
+    uint64_t *d_tm = reinterpret_cast<uint64_t *>(d_tk + n_tab);
+    int64_t *d_seen_pos = w.seen.as<int64_t>();
+    int32_t *d_seen_slot = reinterpret_cast<int32_t *>(d_seen_pos + n_seen);
+    if (n_tab) {
+        HIP_TRY(hipMemcpyAsync(d_tk, tk.data(), sizeof(int64_t) * n_tab, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_tm, tm.data(), sizeof(uint64_t) * n_tab, hipMemcpyHostToDevice, s));
+    }
+    if (n_seen) {
+        HIP_TRY(hipMemcpyAsync(d_seen_pos, seen_pos.data(), sizeof(int64_t) * n_seen, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_seen_slot, seen_slot.data(), sizeof(int32_t) * n_seen, hipMemcpyHostToDevice, s));
+    }
+    const std::vector<int64_t> no_limit((size_t)per_key::kMaxSlots, std::numeric_limits<int64_t>::max());
+    HIP_TRY(hipMemcpyAsync(w.limits.p, no_limit.data(), sizeof(int64_t) * no_limit.size(), hipMemcpyHostToDevice, s));
+    uint32_t *ex = w.ex_bm.as<uint32_t>(), *exc = w.ex_chunks.as<uint32_t>();
+    {
+        Timed t(lane, "keys_exclude", 8.0 * (double)lane->n_rows + 4.0 * (double)words * (double)(S + 1));
+        HIP_TRY(orr::launch_keys_exclude(keys->d_key, lane->n_rows, w.c_bm.as<uint32_t>(), words, d_tk, d_tm, (int32_t)n_tab, S, ex, s));
+    }
+    if (n_seen) {
+        Timed t(lane, "keys_clear_seen", 16.0 * (double)n_seen);
+        HIP_TRY(orr::launch_keys_clear_seen(ex, words, S, d_seen_slot, d_seen_pos, (int64_t)n_seen, s));
+    }
+    // ---- what a scope keeps beside its bitmap (refresh_scope's two steps, each ONE launch for the S bitmaps; one synchronise)
+    uint32_t *h_live = w.pin.as<uint32_t>();
+    int64_t *h_clip = reinterpret_cast<int64_t *>(h_live + 2 * per_key::kMaxSlots);
+    uint32_t *d_live = reinterpret_cast<uint32_t *>(w.limits.as<int64_t>() + per_key::kMaxSlots), *d_took = d_live + per_key::kMaxSlots;
+    {
+        Timed t(lane, "scope_counts", 4.0 * (double)S * (double)words);
+        HIP_TRY(orr::launch_scope_counts(ex, words, S, S, w.limits.as<int64_t>(), exc, d_live, d_took, s));
+    }
+    {
+        Timed t(lane, "mask_clip_slots", (4.0 * (double)orr::kScopeChunkWords + 4.0 * (double)n_chunks) * (double)S);
+        HIP_TRY(orr::launch_mask_clip_slots(ex, words, exc, d_live, S, h_clip, s));
+    }
+    HIP_TRY(hipMemcpyAsync(h_live, d_live, sizeof(uint32_t) * (size_t)S, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    collect_events(lane);
+    std::unique_ptr<orr_scope[]> tmp(new orr_scope[(size_t)S]);
+    std::vector<const orr_scope *> ptrs((size_t)S);
+    for (int32_t i = 0; i < S; ++i) {
+        orr_scope &sc = tmp[(size_t)i];
+        sc.owner.store(const_cast<orr_index *>(owner_of(lane)));
+        sc.n_rows = lane->n_rows; sc.words = words;
+        sc.bm = ex + (size_t)i * (size_t)words; sc.chunks = exc + (size_t)i * (size_t)n_chunks;
+        sc.live.store((int64_t)h_live[i]);
+        sc.n_clip_all = std::min<int64_t>(h_clip[i], lane->n_rows);
+        ptrs[(size_t)i] = &sc;
+    }
+    // ---- the search: C minus the exclusions, with no further limit
+    SubBatch sb;
+    BatchArgs cur;
+    ORR_TRY(build_subset(lane, a, ids, sb, cur));
+    cur.topk = pool;
+    cur.candidate_limit = std::max<int64_t>(1, lane->n_rows);
+    r_rows.assign((size_t)S * pool, -1); r_scores.assign((size_t)S * pool, 0.0); r_pos.assign((size_t)S * pool, -1); r_cnt.assign((size_t)S, 0);
+    cur.out_keys = r_pos.data();
+    lane->sstats.searches += 1;
+    lane->sstats.queries += S;
+    if (S == 1) {
+        ORR_TRY(masked_batch(lane, cur, ScopeSource{nullptr, ptrs[0]}, r_rows.data(), r_scores.data(), r_cnt.data()));
+    } else {
+        std::vector<int32_t> qg((size_t)S);
+        std::iota(qg.begin(), qg.end(), 0);
+        GroupArgs ga{S, 0, nullptr, nullptr, qg.data()};
+        ga.scopes = ptrs.data();
+        ORR_TRY(grouped_batch(lane, cur, ga, r_rows.data(), r_scores.data(), r_cnt.data()));
+    }
+    return ORR_OK;
+}
+
+// orr_search_batch_per_key on the lane the caller holds (the scope, if any, and the keys held shared).
+int per_key_run(orr_index *lane, const char *fn, const BatchArgs &a, const orr_scope *within, const orr_keys *keys, int32_t max_per_key,
+                int32_t pool, int64_t *out_rows, double *out_scores, int64_t *out_row_keys, int32_t *out_counts, int32_t *out_rounds)
+{
+    const int32_t B = a.B, take = per_key::take_of(a.topk);
+    for (size_t i = 0; i < (size_t)B * take; ++i) { out_rows[i] = -1; out_scores[i] = 0.0; out_row_keys[i] = ORR_KEY_NONE; }
+    for (int32_t b = 0; b < B; ++b) { out_counts[b] = 0; if (out_rounds) out_rounds[b] = 0; }
+    // ---- round 1: the pool, exactly the call the diverse search makes for its own
+    std::vector<int64_t> r_rows((size_t)B * pool, -1), r_pos((size_t)B * pool, -1);
+    std::vector<double> r_scores((size_t)B * pool, 0.0);
+    std::vector<int32_t> r_cnt((size_t)B, 0);
+    {
+        BatchArgs pa = a;
+        pa.topk = pool;
+        pa.out_keys = r_pos.data();
+        if (within) {
+            ORR_TRY(masked_batch(lane, pa, ScopeSource{nullptr, within}, r_rows.data(), r_scores.data(), r_cnt.data()));
+        } else {
+            const int64_t n = participating_rows(lane, a.candidate_limit);
+            ORR_TRY(escalate(index_backend(lane, fn, n), pa, escalation::initial_kprime(pool, n, orr::kSelWidth), r_rows.data(), r_scores.data(), r_cnt.data()));
+        }
+    }
+    ORR_TRY(bind_device(lane));
+    PerKeyWork w;
+    std::vector<per_key::State> st((size_t)B);
+    std::vector<int32_t> ids((size_t)B);               // the queries of the round in flight: [i] of r_* is query ids[i]
+    std::iota(ids.begin(), ids.end(), 0);
+    std::vector<int64_t> kept_rows, kept_keys;         // [B][take], filled as the walks keep rows
+    std::vector<double> kept_scores;
+    BatchArgs host_a = a;
+    for (int32_t round = 1; !ids.empty(); ++round) {
+        if (round > take) return fail(ORR_EDEVICE, "%s: a round kept no row", fn);      // (every round keeps at least one)
+        // ---- the round's keys: ONE keys_gather
+        const size_t nq = ids.size();
+        std::vector<int64_t> pos(nq * (size_t)pool, -1), rk;
+        for (size_t i = 0; i < nq; ++i)
+            for (int32_t j = 0; j < r_cnt[i]; ++j) {
+                const int64_t p = r_pos[i * pool + j] - lane->row_base;
+                if (p < 0 || p >= lane->n_rows) return fail(ORR_EDEVICE, "%s: a result's order_key lies outside the shard", fn);
+                pos[i * pool + j] = p;
+            }
+        ORR_TRY(per_key_gather(lane, keys, w.gio, pos, rk));
+        // ---- the walk
+        std::vector<int32_t> unfinished;
+        std::vector<int32_t> number((size_t)pool);
+        std::iota(number.begin(), number.end(), 0);
+        for (size_t i = 0; i < nq; ++i) {
+            const int32_t b = ids[i];
+            per_key::State &s = st[(size_t)b];
+            const size_t had = s.kept.size();
+            per_key::walk_round(s, r_cnt[i], rk.data() + i * pool, pos.data() + i * pool, number.data(), take, max_per_key, pool);
+            for (size_t t = had; t < s.kept.size(); ++t) {
+                const size_t o = (size_t)b * take + t, from = i * pool + (size_t)s.kept[t];
+                out_rows[o] = r_rows[from]; out_scores[o] = r_scores[from]; out_row_keys[o] = rk[from];
+            }
+            out_counts[b] = (int32_t)s.kept.size();
+            if (out_rounds) out_rounds[b] = s.rounds;
+            if (!s.finished) {
+                if (s.kept.size() == had) return fail(ORR_EDEVICE, "%s: a round kept no row", fn);
+                unfinished.push_back(b);
+            }
+        }
+        if (unfinished.empty()) break;
+        // ---- the next round, in slices of at most 64 queries
+        if (!w.frozen) {
+            ORR_TRY(per_key_freeze(lane, a, within, w));
+            if (a.dim > 0 && is_device_pointer(a.q)) {
+                w.q_down.resize((size_t)B * (size_t)a.dim);
+                HIP_TRY(hipMemcpy(w.q_down.data(), a.q, sizeof(float) * w.q_down.size(), hipMemcpyDeviceToHost));
+                host_a.q = w.q_down.data();
+            }
+        }
+        const size_t nu = unfinished.size();
+        std::vector<int64_t> n_rows(nu * (size_t)pool, -1), n_pos(nu * (size_t)pool, -1);
+        std::vector<double> n_scores(nu * (size_t)pool, 0.0);
+        std::vector<int32_t> n_cnt(nu, 0);
+        for (size_t b0 = 0; b0 < nu; b0 += (size_t)per_key::kMaxSlots) {
+            const size_t S = std::min<size_t>((size_t)per_key::kMaxSlots, nu - b0);
+            const std::vector<int32_t> slice(unfinished.begin() + b0, unfinished.begin() + b0 + S);
+            std::vector<int64_t> s_rows, s_pos;
+            std::vector<double> s_scores;
+            std::vector<int32_t> s_cnt;
+            ORR_TRY(per_key_round(lane, host_a, keys, pool, slice, st, w, s_rows, s_scores, s_pos, s_cnt));
+            memcpy(n_rows.data() + b0 * pool, s_rows.data(), sizeof(int64_t) * S * pool);
+            memcpy(n_pos.data() + b0 * pool, s_pos.data(), sizeof(int64_t) * S * pool);
+            memcpy(n_scores.data() + b0 * pool, s_scores.data(), sizeof(double) * S * pool);
+            memcpy(n_cnt.data() + b0, s_cnt.data(), sizeof(int32_t) * S);
+        }
+        ids.swap(unfinished);
+        r_rows.swap(n_rows); r_pos.swap(n_pos); r_scores.swap(n_scores); r_cnt.swap(n_cnt);
+    }
+    return ORR_OK;
+}
+
+}  // namespace
+
+int orr_search_batch_per_key(orr_index *idx, int32_t B, int32_t dim, const float *q, const uint8_t *terms_utf8, const uint32_t *term_off,
+                             const uint32_t *query_term_off, int64_t now_ticks, int32_t topk, int64_t candidate_limit, const orr_scope *within,
+                             const orr_keys *keys, int32_t max_per_key, int32_t pool, int64_t *out_rows, double *out_scores, int64_t *out_keys,
+                             int32_t *out_counts, int32_t *out_rounds)
+{
+    static const char *fn = "orr_search_batch_per_key";
+    switch (per_key::first_invalid(!out_rows || !out_scores || !out_keys || !out_counts, topk, pool, max_per_key, !keys)) {
+    case 0: break;
+    case 1: return fail(ORR_EINVAL, "%s: out_rows, out_scores, out_keys and out_counts are required", fn);
+    case 2: return fail(ORR_EINVAL, "%s: pool must be in 1 .. %d", fn, per_key::kMaxPool);
+    case 3: return fail(ORR_EINVAL, "%s: topk %d exceeds the pool of %d", fn, topk, pool);
+    case 4: return fail(ORR_EINVAL, "%s: max_per_key must be at least 1", fn);
+    default: return fail(ORR_EINVAL, "%s: null keys", fn);
+    }
+    if (!idx) return fail(ORR_EINVAL, "%s: null index", fn);
+    if (B == 0) return ORR_OK;
+    BatchArgs a{B, dim, q, terms_utf8, term_off, query_term_off, now_ticks, candidate_limit, topk};
+    ORR_TRY(check_batch(idx, a, fn));
+    orr_index *own = nullptr;
+    if (within) ORR_TRY(scope_owner(within, idx, fn, &own));
+    ORR_TRY(keys_owner(keys, idx, fn, &own));
+    Lane ln = acquire_lane(idx);                       // a search like any other: its own lane, concurrent with the others
+    idx = ln.lane;
+    std::lock_guard<std::mutex> lock(idx->mu);
+    std::shared_lock<std::shared_mutex> rd;
+    if (within) {
+        rd = std::shared_lock<std::shared_mutex>(within->mu);
+        ORR_TRY(scope_owner(within, idx, fn, &own));
+        if (within->n_rows != idx->n_rows) return fail(ORR_ESTATE, "%s: the scope covers %lld rows, the handle %lld", fn, (long long)within->n_rows, (long long)idx->n_rows);
+    }
+    std::shared_lock<std::shared_mutex> rk(keys->mu);
+    ORR_TRY(keys_owner(keys, idx, fn, &own));
+    if (keys->n_rows != idx->n_rows) return fail(ORR_ESTATE, "%s: the keys cover %lld rows, the handle %lld", fn, (long long)keys->n_rows, (long long)idx->n_rows);
+    idx->sstats.searches += 1;
+    idx->sstats.queries += B;
+    const int r = per_key_run(idx, fn, a, within, keys, max_per_key, pool, out_rows, out_scores, out_keys, out_counts, out_rounds);
+    g_ht.done();
+    return r;
 }
 
 int orr_search_shard_scoped(orr_index *idx, int32_t B, int32_t dim, const float *q, const uint8_t *terms_utf8,

@@ -14,6 +14,7 @@
 #include "orr_scope_near_plan.h"
 #include "orr_range_plan.h"
 #include "orr_diverse_plan.h"
+#include "orr_per_key_plan.h"
 
 #include <atomic>
 
@@ -442,6 +443,11 @@ hipError_t launch_scope_trailers(orr_candidate *recs, int32_t B, int32_t kprime,
 // *n_clip (may be pinned host memory) = one past the position of the took-th set bit of the bitmap (1 <= took <= its set
 // bits; chunk_cnt as launch_scope_counts left it).
 hipError_t launch_mask_clip(const uint32_t *bitmap, int64_t words, const uint32_t *chunk_cnt, uint32_t took, int64_t *n_clip, hipStream_t s);
+// launch_mask_clip with took = the set bits, for n_slots bitmaps [n_slots][words] with chunk counts [n_slots][scope_chunks(words)] in
+// one launch: n_clip[s] (may be pinned host memory) = one past the last set bit of bitmap s, 0 for an empty one.  live [n_slots]: the
+// bitmaps' set bits, DEVICE memory (launch_scope_counts wrote them on the same stream).
+hipError_t launch_mask_clip_slots(const uint32_t *bitmaps, int64_t words, const uint32_t *chunk_cnt, const uint32_t *live, int32_t n_slots,
+                                  int64_t *n_clip, hipStream_t s);
 // The front of a grouped pass over scope handles in one launch.  Entry e of the table (e < n_entries <= kMaxGatherGroups): the
 // bitmap (`words` words, words % 4 == 0, 16-byte aligned) and chunk counts of a handle are copied to dst_bm[slot[e]][words] and
 // dst_chunks[slot[e]][scope_chunks(words)] (slot[e] < n_slots; distinct entries name distinct slots), and where clip_took[e] > 0
@@ -495,6 +501,36 @@ hipError_t launch_scope_remap(const int64_t *src, int64_t first, int64_t n_new, 
                               int64_t old_words, uint32_t *const *new_bm, int32_t n_scopes, hipStream_t s);
 // out[i] = row_ids[buf[i].pos] for the n entries launch_scope_compact left.
 hipError_t launch_scope_entry_ids(const SelEntry *buf, int64_t n, const int64_t *row_ids, int64_t n_rows, int64_t *out, hipStream_t s);
+
+// ---- row keys and the per-key search (orr_keys, orr_search_batch_per_key; the rules are orr_per_key_plan.h's) -----------------
+// out[s][words] for s < n_slots (all words written) = base AND NOT the rows whose key slot s has closed: key [n_rows] the key
+// column, tab_keys / tab_masks [n_tab] the sorted union table (per_key::build_table; LDS up to per_key::kLdsTable entries, global
+// memory beyond).  base: words % 4 == 0, 16-byte aligned, bits at or above n_rows clear; out 16-byte aligned.  No atomics.
+hipError_t launch_keys_exclude(const int64_t *key, int64_t n_rows, const uint32_t *base, int64_t words, const int64_t *tab_keys,
+                               const uint64_t *tab_masks, int32_t n_tab, int32_t n_slots, uint32_t *out, hipStream_t s);
+// The bit of position pos[i] cleared in bitmap slot[i] of bitmaps[.][words], for n (slot, position) pairs (device).
+hipError_t launch_keys_clear_seen(uint32_t *bitmaps, int64_t words, int32_t n_slots, const int32_t *slot, const int64_t *pos, int64_t n,
+                                  hipStream_t s);
+// bm (words, all written) = bit r set iff row r < n_rows carries a key of tab_keys [n_tab] (ascending, distinct; ORR_KEY_NONE may
+// be listed and then selects the rows without a key).  words % 4 == 0.
+hipError_t launch_keys_member(const int64_t *key, int64_t n_rows, const int64_t *tab_keys, int32_t n_tab, uint32_t *bm, int64_t words,
+                              hipStream_t s);
+// out[i] = key[pos[i]] (ORR_KEY_NONE for a position outside the shard).  With the id table (table_ids non-null) pos[i] is a
+// row id: the key of the first live row that carries it, ORR_KEY_NONE when there is none.
+hipError_t launch_keys_gather(const int64_t *key, int64_t n_rows, const int64_t *pos, int64_t n, const int64_t *table_ids,
+                              const uint32_t *table_pos, const int64_t *dead, int32_t n_dead, int64_t *out, hipStream_t s);
+// key[p] = keys[i] for every live row p that carries id ids[i] (scope_lookup's search); *n_set (device, zeroed by the caller)
+// counts the entries that named a live row.
+hipError_t launch_keys_scatter(const int64_t *table_ids, const uint32_t *table_pos, int64_t n_rows, const int64_t *ids, const int64_t *keys,
+                               int64_t n, const int64_t *dead, int32_t n_dead, int64_t *key, unsigned long long *n_set, hipStream_t s);
+// new_key[g][d] for d < n_new = old_key[g][d] for d < first, old_key[g][src[d - first]] beyond, ORR_KEY_NONE when that source is
+// negative (a new row): n_cols columns in one launch (the pointer arrays are device memory).  No column aliases its source.
+hipError_t launch_keys_remap(const int64_t *src, int64_t first, int64_t n_new, const int64_t *const *old_key, int64_t *const *new_key,
+                             int32_t n_cols, hipStream_t s);
+// key[0 .. n) = ORR_KEY_NONE
+hipError_t launch_keys_fill_none(int64_t *key, int64_t n, hipStream_t s);
+// *out (device, zeroed by the caller) += the rows r < n_rows with a key that are not in dead[] (ascending).
+hipError_t launch_keys_count(const int64_t *key, int64_t n_rows, const int64_t *dead, int32_t n_dead, unsigned long long *out, hipStream_t s);
 
 // ---- term scopes (orr_scope_create_terms; the rules are orr_scope_terms_plan.h's) -------------------------------------------
 // term_base[t] (device, and its copy term_base_host in pinned memory when given) = where distinct term t's row bitmap starts, in

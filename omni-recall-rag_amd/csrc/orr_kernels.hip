@@ -1788,17 +1788,39 @@ __device__ __forceinline__ void mask_clip_rule(const uint32_t *__restrict__ bitm
     *n_clip = clip;
 }
 
+// Workgroup s clips bitmap s of [gridDim.x][words] (chunk counts [gridDim.x][n_chunks]) into n_clip[s]: one workgroup and `took` for
+// launch_mask_clip; for launch_mask_clip_slots took_of[s] (device memory) is the slot's took, and a slot without a set bit gives 0.
 __global__ __launch_bounds__(256) void mask_clip_kernel(const uint32_t *__restrict__ bitmap, int64_t words, int32_t n_chunks,
-                                                        const uint32_t *__restrict__ chunk_cnt, uint32_t took, int64_t *__restrict__ n_clip)
+                                                        const uint32_t *__restrict__ chunk_cnt, uint32_t took,
+                                                        const uint32_t *__restrict__ took_of, int64_t *__restrict__ n_clip)
 {
-    mask_clip_rule(bitmap, words, n_chunks, chunk_cnt, took, n_clip);
+    const int64_t sl = blockIdx.x;
+    if (took_of) {
+        took = took_of[sl];                            // (workgroup-uniform)
+        if (took == 0u) {
+            if (threadIdx.x == 0) n_clip[sl] = 0;
+            return;
+        }
+    }
+    mask_clip_rule(bitmap + sl * words, words, n_chunks, chunk_cnt + sl * n_chunks, took, n_clip + sl);
 }
 
 hipError_t launch_mask_clip(const uint32_t *bitmap, int64_t words, const uint32_t *chunk_cnt, uint32_t took, int64_t *n_clip, hipStream_t s)
 {
     if (words <= 0 || words % 4 != 0 || took == 0u) return hipErrorInvalidValue;
     const int32_t n_chunks = scope_chunks(words);
-    hipLaunchKernelGGL(mask_clip_kernel, dim3(1), dim3(256), 0, s, bitmap, words, n_chunks, chunk_cnt, took, n_clip);
+    hipLaunchKernelGGL(mask_clip_kernel, dim3(1), dim3(256), 0, s, bitmap, words, n_chunks, chunk_cnt, took, (const uint32_t *)nullptr, n_clip);
+    return hipGetLastError();
+}
+
+// launch_mask_clip for n_slots contiguous bitmaps in ONE launch, took = the slot's set bits (live, device memory): n_clip[s] = one
+// past the last set bit of bitmap s, 0 for an empty one (what refresh_scope keeps as a scope's n_clip_all).
+hipError_t launch_mask_clip_slots(const uint32_t *bitmaps, int64_t words, const uint32_t *chunk_cnt, const uint32_t *live, int32_t n_slots,
+                                  int64_t *n_clip, hipStream_t s)
+{
+    if (n_slots <= 0) return hipSuccess;
+    if (words <= 0 || words % 4 != 0 || !bitmaps || !chunk_cnt || !live || !n_clip) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mask_clip_kernel, dim3((unsigned)n_slots), dim3(256), 0, s, bitmaps, words, scope_chunks(words), chunk_cnt, 0u, live, n_clip);
     return hipGetLastError();
 }
 
@@ -2163,6 +2185,296 @@ hipError_t launch_scope_entry_ids(const SelEntry *buf, int64_t n, const int64_t 
 {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(scope_entry_ids_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, buf, n, row_ids, n_rows, out);
+    return hipGetLastError();
+}
+
+// ---- row keys and the per-key search (orr_keys, orr_search_batch_per_key; the rules are orr_per_key_plan.h's) -----------------
+
+// the wave's OR of a 64-bit value, in every lane (a butterfly over the two halves)
+__device__ __forceinline__ uint64_t wave_or_u64(uint64_t v)
+{
+    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        lo |= (uint32_t)__shfl_xor((int)lo, off, 64);
+        hi |= (uint32_t)__shfl_xor((int)hi, off, 64);
+    }
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// A workgroup owns per_key::kBlockRows rows = kBlockWords words of every slot.  Each lane loads its eight keys (coalesced 8-byte
+// loads) and searches the union table once per key (LDS: the table is staged first; otherwise it is read from global memory and
+// stays in L2).  A workgroup none of whose rows is closed -- the common case: closed keys are a few thousand rows of millions --
+// copies its base words into every slot as 16-byte vectors.  Any other workgroup builds the slots' words in an LDS tile: the
+// tile starts as the base, then a wave with a closed row forms, for every slot in the OR of its lanes' masks, the slot's 64
+// bits with one ballot (per_key::exclude_bits); the tile leaves as 16-byte vectors too.  Either way a slot receives
+// 256 contiguous bytes per workgroup instead of 8 bytes per wave.  Every word of the n_slots bitmaps is written.  No atomics.
+template <bool LDS>
+__global__ __launch_bounds__(256) void keys_exclude_kernel(const int64_t *__restrict__ key, int64_t n_rows, const uint32_t *__restrict__ base,
+                                                           int64_t words, const int64_t *__restrict__ tab_keys,
+                                                           const uint64_t *__restrict__ tab_masks, int32_t n_tab, int32_t n_slots,
+                                                           uint32_t *__restrict__ out)
+{
+    __shared__ int64_t sh_keys[LDS ? per_key::kLdsTable : 1];
+    __shared__ uint64_t sh_masks[LDS ? per_key::kLdsTable : 1];
+    __shared__ __attribute__((aligned(16))) uint32_t tile[per_key::kMaxSlots][per_key::kBlockWords];
+    const int tid = threadIdx.x;
+    if (LDS) {
+        for (int i = tid; i < n_tab; i += 256) { sh_keys[i] = tab_keys[i]; sh_masks[i] = tab_masks[i]; }
+        __syncthreads();
+    }
+    const int64_t *tk = LDS ? sh_keys : tab_keys;
+    const uint64_t *tm = LDS ? sh_masks : tab_masks;
+    const int64_t w0 = (int64_t)blockIdx.x * per_key::kBlockWords;
+    if (w0 >= words) return;                           // (workgroup-uniform)
+    const int wc = (int)(words - w0 < per_key::kBlockWords ? words - w0 : per_key::kBlockWords);      // a multiple of 4
+    const int64_t row0 = w0 * 32;
+    uint64_t m[8];
+    int any = 0;
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+        const int64_t r = row0 + it * 256 + tid;
+        const int64_t k = r < n_rows ? key[r] : per_key::kNone;
+        m[it] = per_key::table_mask(tk, tm, n_tab, k);
+        any |= m[it] != 0ull;
+    }
+    const int hit = __syncthreads_or(any);
+    const int vec = wc >> 2;                           // 16-byte vectors per slot
+    const uint4 *base4 = reinterpret_cast<const uint4 *>(base + w0);
+    if (!hit) {
+        for (int i = tid; i < n_slots * vec; i += 256) {
+            const int s = i / vec, j = i - s * vec;
+            reinterpret_cast<uint4 *>(out + (int64_t)s * words + w0)[j] = base4[j];
+        }
+        return;
+    }
+    for (int i = tid; i < n_slots * per_key::kBlockWords; i += 256) {
+        const int s = i >> 6, j = i & 63;
+        tile[s][j] = j < wc ? base[w0 + j] : 0u;
+    }
+    __syncthreads();
+    const int wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+        uint64_t o = wave_or_u64(m[it]);               // the same in every lane of the wave
+        const int wi = it * 8 + wave * 2;              // the wave's 64 rows: words wi, wi + 1 of the workgroup's
+        if (o == 0ull || wi >= wc) continue;
+        const uint64_t b = (uint64_t)base[w0 + wi] | ((uint64_t)base[w0 + wi + 1] << 32);
+        while (o) {
+            const int s = __ffsll((long long)o) - 1;
+            o &= o - 1ull;
+            const uint64_t closed = __ballot(per_key::slot_closed(m[it], s));
+            if (lane == 0 && s < n_slots) {
+                const uint64_t v = per_key::exclude_bits(b, closed);
+                tile[s][wi] = (uint32_t)v;
+                tile[s][wi + 1] = (uint32_t)(v >> 32);
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < n_slots * vec; i += 256) {
+        const int s = i / vec, j = i - s * vec;
+        reinterpret_cast<uint4 *>(out + (int64_t)s * words + w0)[j] = *reinterpret_cast<const uint4 *>(&tile[s][j * 4]);
+    }
+}
+
+hipError_t launch_keys_exclude(const int64_t *key, int64_t n_rows, const uint32_t *base, int64_t words, const int64_t *tab_keys,
+                               const uint64_t *tab_masks, int32_t n_tab, int32_t n_slots, uint32_t *out, hipStream_t s)
+{
+    if (n_slots <= 0) return hipSuccess;
+    if (words <= 0 || words % 4 != 0 || n_rows < 0 || n_rows > words * 32 || n_slots > per_key::kMaxSlots || n_tab < 0 || !key || !base || !out ||
+        (n_tab > 0 && (!tab_keys || !tab_masks)))
+        return hipErrorInvalidValue;
+    if (reinterpret_cast<uintptr_t>(base) % 16 != 0 || reinterpret_cast<uintptr_t>(out) % 16 != 0) return hipErrorInvalidValue;
+    const unsigned blocks = (unsigned)((words + per_key::kBlockWords - 1) / per_key::kBlockWords);
+    if (per_key::table_in_lds(n_tab))
+        hipLaunchKernelGGL(keys_exclude_kernel<true>, dim3(blocks), dim3(256), 0, s, key, n_rows, base, words, tab_keys, tab_masks, n_tab, n_slots, out);
+    else
+        hipLaunchKernelGGL(keys_exclude_kernel<false>, dim3(blocks), dim3(256), 0, s, key, n_rows, base, words, tab_keys, tab_masks, n_tab, n_slots, out);
+    return hipGetLastError();
+}
+
+// scope_clear_positions with a slot: pair i clears bit pos[i] of bitmap slot[i] (pairs outside the bitmaps are passed over)
+__global__ __launch_bounds__(256) void keys_clear_seen_kernel(uint32_t *__restrict__ bitmaps, int64_t words, int32_t n_slots,
+                                                              const int32_t *__restrict__ slot, const int64_t *__restrict__ pos, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t p = pos[i];
+    const int32_t sl = slot[i];
+    if (p < 0 || p >= words * 32 || sl < 0 || sl >= n_slots) return;
+    atomicAnd(bitmaps + (int64_t)sl * words + (p >> 5), ~(1u << (uint32_t)(p & 31)));
+}
+
+hipError_t launch_keys_clear_seen(uint32_t *bitmaps, int64_t words, int32_t n_slots, const int32_t *slot, const int64_t *pos, int64_t n,
+                                  hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    if (words <= 0 || n_slots <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(keys_clear_seen_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, bitmaps, words, n_slots, slot, pos, n);
+    return hipGetLastError();
+}
+
+// One lane per row, the table search of keys_exclude with one slot and no base (per_key::table_find: ORR_KEY_NONE is a key like
+// any other here); a ballot forms the wave's 64 bits, lane 0 stores them.  Every word is written; rows at or above n_rows are clear.
+template <bool LDS>
+__global__ __launch_bounds__(256) void keys_member_kernel(const int64_t *__restrict__ key, int64_t n_rows, const int64_t *__restrict__ tab_keys,
+                                                          int32_t n_tab, uint32_t *__restrict__ bm, int64_t words)
+{
+    __shared__ int64_t sh_keys[LDS ? per_key::kLdsTable : 1];
+    const int tid = threadIdx.x;
+    if (LDS) {
+        for (int i = tid; i < n_tab; i += 256) sh_keys[i] = tab_keys[i];
+        __syncthreads();
+    }
+    const int64_t *tk = LDS ? sh_keys : tab_keys;
+    const int64_t r = (int64_t)blockIdx.x * 256 + tid;
+    const int64_t r0 = r & ~(int64_t)63;
+    if (r0 >= words * 32) return;                      // (wave-uniform; words is a multiple of 4)
+    const bool in = r < n_rows && per_key::table_find(tk, n_tab, key[r]) >= 0;
+    const unsigned long long bits = __ballot(in);
+    if ((tid & 63) == 0) *reinterpret_cast<uint2 *>(bm + (r0 >> 5)) = make_uint2((uint32_t)bits, (uint32_t)(bits >> 32));
+}
+
+hipError_t launch_keys_member(const int64_t *key, int64_t n_rows, const int64_t *tab_keys, int32_t n_tab, uint32_t *bm, int64_t words,
+                              hipStream_t s)
+{
+    if (words <= 0 || words % 4 != 0 || n_rows < 0 || n_rows > words * 32 || n_tab < 0 || !key || !bm || (n_tab > 0 && !tab_keys))
+        return hipErrorInvalidValue;
+    const unsigned blocks = (unsigned)((words * 32 + 255) / 256);
+    if (per_key::table_in_lds(n_tab))
+        hipLaunchKernelGGL(keys_member_kernel<true>, dim3(blocks), dim3(256), 0, s, key, n_rows, tab_keys, n_tab, bm, words);
+    else
+        hipLaunchKernelGGL(keys_member_kernel<false>, dim3(blocks), dim3(256), 0, s, key, n_rows, tab_keys, n_tab, bm, words);
+    return hipGetLastError();
+}
+
+// whether position p is in dead[0 .. n_dead) (ascending)
+__device__ __forceinline__ bool keys_row_dead(const int64_t *__restrict__ dead, int32_t n_dead, int64_t p)
+{
+    int32_t dl = 0, dh = n_dead;
+    while (dl < dh) {
+        const int32_t mid = (dl + dh) >> 1;
+        if (dead[mid] < p) dl = mid + 1; else dh = mid;
+    }
+    return dl < n_dead && dead[dl] == p;
+}
+
+__global__ __launch_bounds__(256) void keys_gather_kernel(const int64_t *__restrict__ key, int64_t n_rows, const int64_t *__restrict__ pos, int64_t n,
+                                                          const int64_t *__restrict__ table_ids, const uint32_t *__restrict__ table_pos,
+                                                          const int64_t *__restrict__ dead, int32_t n_dead, int64_t *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    int64_t p = pos[i];
+    if (table_ids) {                                   // pos[i] is a row id: its first live row (scope_lookup's search)
+        const int64_t want = p;
+        int64_t lo = 0, hi = n_rows;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (table_ids[mid] < want) lo = mid + 1; else hi = mid;
+        }
+        p = -1;
+        for (; lo < n_rows && table_ids[lo] == want; ++lo)
+            if (!keys_row_dead(dead, n_dead, (int64_t)table_pos[lo])) { p = (int64_t)table_pos[lo]; break; }
+    }
+    out[i] = (p >= 0 && p < n_rows) ? key[p] : per_key::kNone;
+}
+
+hipError_t launch_keys_gather(const int64_t *key, int64_t n_rows, const int64_t *pos, int64_t n, const int64_t *table_ids,
+                              const uint32_t *table_pos, const int64_t *dead, int32_t n_dead, int64_t *out, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    if (!key || !pos || !out || n_rows < 0 || (table_ids && !table_pos) || (n_dead > 0 && !dead)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(keys_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, key, n_rows, pos, n, table_ids, table_pos, dead,
+                       n_dead, out);
+    return hipGetLastError();
+}
+
+// One thread per entry: the run of equal ids in the table, every live position of it takes the entry's key.
+__global__ __launch_bounds__(256) void keys_scatter_kernel(const int64_t *__restrict__ table_ids, const uint32_t *__restrict__ table_pos,
+                                                           int64_t n_rows, const int64_t *__restrict__ ids, const int64_t *__restrict__ keys,
+                                                           int64_t n, const int64_t *__restrict__ dead, int32_t n_dead,
+                                                           int64_t *__restrict__ key, unsigned long long *__restrict__ n_set)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t want = ids[i];
+    int64_t lo = 0, hi = n_rows;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (table_ids[mid] < want) lo = mid + 1; else hi = mid;
+    }
+    bool named = false;
+    for (; lo < n_rows && table_ids[lo] == want; ++lo) {
+        const int64_t p = (int64_t)table_pos[lo];
+        if (p >= n_rows || keys_row_dead(dead, n_dead, p)) continue;
+        key[p] = keys[i];
+        named = true;
+    }
+    if (named) atomicAdd(n_set, 1ull);
+}
+
+hipError_t launch_keys_scatter(const int64_t *table_ids, const uint32_t *table_pos, int64_t n_rows, const int64_t *ids, const int64_t *keys,
+                               int64_t n, const int64_t *dead, int32_t n_dead, int64_t *key, unsigned long long *n_set, hipStream_t s)
+{
+    if (n <= 0 || n_rows <= 0) return hipSuccess;
+    if (!table_ids || !table_pos || !ids || !keys || !key || !n_set || (n_dead > 0 && !dead)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(keys_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, table_ids, table_pos, n_rows, ids, keys, n, dead,
+                       n_dead, key, n_set);
+    return hipGetLastError();
+}
+
+// One lane per destination row, its source read ONCE (scope_set::remap_source, as scope_remap), then every column's key.
+__global__ __launch_bounds__(256) void keys_remap_kernel(const int64_t *__restrict__ src, int64_t first, int64_t n_new,
+                                                         const int64_t *const *__restrict__ old_key, int64_t *const *__restrict__ new_key,
+                                                         int32_t n_cols)
+{
+    const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (d >= n_new) return;
+    const int64_t sp = scope_set::remap_source(d, first, n_new, src);
+    for (int32_t g = 0; g < n_cols; ++g) new_key[g][d] = sp >= 0 ? old_key[g][sp] : per_key::kNone;
+}
+
+hipError_t launch_keys_remap(const int64_t *src, int64_t first, int64_t n_new, const int64_t *const *old_key, int64_t *const *new_key,
+                             int32_t n_cols, hipStream_t s)
+{
+    if (n_cols <= 0 || n_new <= 0) return hipSuccess;
+    if (first < 0 || n_new < first || !old_key || !new_key || (n_new > first && !src)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(keys_remap_kernel, dim3((unsigned)((n_new + 255) / 256)), dim3(256), 0, s, src, first, n_new, old_key, new_key, n_cols);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void keys_fill_none_kernel(int64_t *__restrict__ key, int64_t n)
+{
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) key[r] = per_key::kNone;
+}
+
+hipError_t launch_keys_fill_none(int64_t *key, int64_t n, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(keys_fill_none_kernel, dim3(capped_blocks(n, 256)), dim3(256), 0, s, key, n);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void keys_count_kernel(const int64_t *__restrict__ key, int64_t n_rows, const int64_t *__restrict__ dead,
+                                                         int32_t n_dead, unsigned long long *__restrict__ out)
+{
+    unsigned long long c = 0;                          // one ballot per 64 rows, counted by lane 0 of the wave
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t r0 = (int64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63); r0 < n_rows; r0 += stride) {
+        const int64_t r = r0 + (threadIdx.x & 63);
+        const bool has = r < n_rows && key[r] != per_key::kNone && !keys_row_dead(dead, n_dead, r);
+        c += (unsigned long long)__popcll(__ballot(has));
+    }
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, c);
+}
+
+hipError_t launch_keys_count(const int64_t *key, int64_t n_rows, const int64_t *dead, int32_t n_dead, unsigned long long *out, hipStream_t s)
+{
+    if (n_rows <= 0) return hipSuccess;
+    if (!key || !out || (n_dead > 0 && !dead)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(keys_count_kernel, dim3(capped_blocks(n_rows, 256)), dim3(256), 0, s, key, n_rows, dead, n_dead, out);
     return hipGetLastError();
 }
 

@@ -196,6 +196,68 @@ class RecallScope:
         return self._combine(N.ORR_SCOPE_ANDNOT, other)
 
 
+class RecallKeys:
+    """Row keys (orr_keys): one int64 key per row of one sealed shard, resident on its device; KEY_NONE means "no key".  A key
+    is whatever the host groups by, typically a document number.  The column follows its rows through compact and insert_rows
+    of the shard; rows inserted later read KEY_NONE until `set` names them.  Made by RecallIndex.keys; close it before or
+    after its index (after: only the host part is left to free)."""
+
+    KEY_NONE = N.ORR_KEY_NONE
+
+    def __init__(self, handle, index: "RecallIndex"):
+        self._h = handle
+        self._index = index                  # keeps the index object alive
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            N.hip.orr_keys_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _pairs(row_ids, keys):
+        if _is_torch(row_ids) != _is_torch(keys):
+            raise ValueError("row_ids and keys live in the same memory: both numpy or both torch")
+        if _is_torch(row_ids):                           # (the library reads raw int64: no other dtype, layout or mixed placement)
+            import torch
+            if row_ids.device != keys.device:
+                raise ValueError("row_ids and keys live in the same memory: both on the host or both on one device")
+            row_ids = row_ids.to(torch.int64).reshape(-1).contiguous()
+            keys = keys.to(torch.int64).reshape(-1).contiguous()
+        else:
+            row_ids = np.ascontiguousarray(row_ids, dtype=np.int64).reshape(-1)
+            keys = np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)
+        if int(row_ids.shape[0]) != int(keys.shape[0]):
+            raise ValueError("one key per row id")
+        return row_ids, keys, int(row_ids.shape[0])
+
+    def set(self, row_ids, keys) -> int:
+        """orr_keys_set: keys[i] is stored at the live rows that carry row_ids[i] (numpy or torch, both in the same memory).
+        Returns how many entries named a live row.  An id listed twice with different keys gets one of them."""
+        ids, ks, n = self._pairs(row_ids, keys)
+        done = C.c_int64(0)
+        N.check(N.hip.orr_keys_set(self._h, n, _ptr(ids) if n else None, _ptr(ks) if n else None, C.cast(C.byref(done), C.c_void_p)))
+        return int(done.value)
+
+    def get(self, row_ids) -> np.ndarray:
+        """orr_keys_get: the keys of these row ids (host); an unknown or deleted id reads KEY_NONE."""
+        ids = np.ascontiguousarray(row_ids, dtype=np.int64).reshape(-1)
+        out = np.full(ids.shape[0], N.ORR_KEY_NONE, dtype=np.int64)
+        n = int(ids.shape[0])
+        N.check(N.hip.orr_keys_get(self._h, n, _ptr(ids) if n else None, _ptr(out) if n else None))
+        return out
+
+    @property
+    def rows(self) -> int:
+        """orr_keys_rows: live rows whose key is not KEY_NONE; -1 once the index was destroyed."""
+        return int(N.hip.orr_keys_rows(self._h))
+
+
 class _BorrowedScope(RecallScope):
     """A shard's part of a RecallClusterScope: usable like a RecallScope (rows, row_ids, RecallIndex.search_shard_in_scope),
     never destroyed through this object; it ends with its cluster scope."""
@@ -605,6 +667,43 @@ class RecallIndex:
                                                int(candidate_limit), within._h if within is not None else None, int(pool), modes[mode],
                                                float(param), _ptr(rows), _ptr(scores), _ptr(counts), _ptr(ranks)))
         return rows, scores, counts, ranks
+
+    def keys(self, row_ids, keys) -> RecallKeys:
+        """orr_keys_create: a key column over this shard, every row at KEY_NONE, then RecallKeys.set(row_ids, keys)."""
+        ids, ks, n = RecallKeys._pairs(row_ids, keys)
+        h = C.c_void_p()
+        N.check(N.hip.orr_keys_create(self._h, n, _ptr(ids) if n else None, _ptr(ks) if n else None, C.byref(h)))
+        return RecallKeys(h, self)
+
+    def scope_keys(self, keys_handle: RecallKeys, keys) -> RecallScope:
+        """orr_scope_create_keys: the live rows whose key is one of `keys` (host int64, at most 65,536; duplicates count once;
+        KEY_NONE selects the rows without a key; no keys give an empty scope): "search inside these documents"."""
+        ks = np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)
+        n = int(ks.shape[0])
+        h = C.c_void_p()
+        N.check(N.hip.orr_scope_create_keys(self._h, keys_handle._h, n, _ptr(ks) if n else None, C.byref(h)))
+        return RecallScope(h, self)
+
+    def search_per_key(self, qvecs, queries_terms, now_ticks: int, topk: int, keys: RecallKeys, max_per_key: int = 1, pool: int = 24,
+                       within: Optional[RecallScope] = None, candidate_limit: int = 300):
+        """orr_search_batch_per_key: the plain search's ranking of every query (inside `within`, when given) walked from the
+        top, keeping at most max_per_key rows of each key and every row without one, until topk are kept.  Exact beyond the
+        pool: counts stay below topk only when the candidates ran out.  max(1, topk) <= pool <= 56.
+        Returns (rows [B,k] int64, fused scores [B,k] float64, keys [B,k] int64, counts [B] int32, rounds [B] int32)."""
+        B = len(queries_terms)
+        dim, q, _keep = self._query_args(qvecs, B)
+        tpool, toff, qoff = pack_terms(queries_terms)
+        k = max(1, int(topk))
+        rows = np.full((B, k), -1, dtype=np.int64)
+        scores = np.zeros((B, k), dtype=np.float64)
+        rkeys = np.full((B, k), N.ORR_KEY_NONE, dtype=np.int64)
+        counts = np.zeros(B, dtype=np.int32)
+        rounds = np.zeros(B, dtype=np.int32)
+        N.check(N.hip.orr_search_batch_per_key(self._h, B, dim, _ptr(q), _ptr(tpool), _ptr(toff), _ptr(qoff), now_ticks, int(topk),
+                                               int(candidate_limit), within._h if within is not None else None, keys._h,
+                                               int(max_per_key), int(pool), _ptr(rows), _ptr(scores), _ptr(rkeys), _ptr(counts),
+                                               _ptr(rounds)))
+        return rows, scores, rkeys, counts, rounds
 
     def search_in_scope(self, qvecs, queries_terms, now_ticks: int, topk: int, scope: RecallScope, candidate_limit: int = 300):
         """orr_search_batch_in_scope: search_masked with the scope taken from a handle -- nothing is resolved per call.
