@@ -1,5 +1,6 @@
 // orr_range_bulk_plan_selftest -- the rules of orr_range_bulk_plan.h on the CPU (no HIP, no GPU): which screen a walked query
-// gets for every combination of shape, shadow, quantisation error, walked count and the two options; the launch groups against
+// gets for every combination of shape, shadow, quantisation error, walked count and the two options; the walk plan the driver
+// runs (walk_of) for every batch of up to six queries and across the GEMM's threshold; the launch groups against
 // the 2 GiB rule; the argument rules with the batch limit of 1024; the screen's bound for the ONE-level query against a float64
 // restatement of the quantisation (Gaussian vectors at three scales, one-hot vectors, equal-magnitude vectors: never below the
 // true |cos - cos^|); and the ending's lane map, a bijection onto the wave's 128 x 128 tile.
@@ -33,24 +34,109 @@ static void test_paths()
                     for (int32_t gemm : {0, 1, 2})
                         for (int32_t form : {0, 1, 2}) {
                             const Path p = path_of(dim, shadow, finite, walked, gemm, form);
-                            // restated from the issue's words, not from the header's helpers
-                            const bool screen_today = form != 2 && dim % 128 == 0 && shadow && finite;
+                            // which screen: restated from the issue's words, not from the header's helpers
                             const bool shape = dim % 128 == 0 && dim >= 448;
                             const bool enough = gemm == 1 ? walked >= 1 : walked >= 65;
-                            const Path want = !screen_today ? ExactForm : (shape && gemm != 2 && enough) ? GemmScreen : Stream;
+                            const bool takes = shape && gemm != 2 && enough;
+                            CHECK(gemm_takes(dim, walked, gemm, true) == takes && !gemm_takes(dim, walked, gemm, false));
+                            const Path want = !stream_applies(dim, shadow, finite, form) ? ExactForm : takes ? GemmScreen : Stream;
                             CHECK(p == want);
-                            CHECK(stream_applies(dim, shadow, finite, form) == screen_today);
-                            CHECK(gemm_takes(dim, walked, gemm, true) == (shape && gemm != 2 && enough) && !gemm_takes(dim, walked, gemm, false));
                             // the old entry point never takes the GEMM, and is otherwise the same
                             CHECK(path_of(dim, shadow, finite, walked, gemm, form, false) == (want == GemmScreen ? Stream : want));
                             n_gemm += p == GemmScreen; n_stream += p == Stream; n_exact += p == ExactForm;
                         }
     CHECK(n_gemm > 0 && n_stream > 0 && n_exact > 0);
+    // the SCREEN form: every one of its four conditions on its own (the rule at work is checked through the walk plan below)
+    CHECK(stream_applies(128, true, true, 0) && stream_applies(512, true, true, 1) && stream_applies(8192, true, true, 0));
+    CHECK(!stream_applies(128, true, true, 2) && !stream_applies(128, false, true, 0) && !stream_applies(128, true, false, 0));
+    CHECK(!stream_applies(70, true, true, 0) && !stream_applies(192, true, true, 0) && !stream_applies(8320, true, true, 0) && !stream_applies(0, true, true, 0));
     CHECK(!gemm_shape(448) && gemm_shape(512) && gemm_shape(3072) && !gemm_shape(384) && !gemm_shape(70) && !gemm_shape(128) && !gemm_shape(480) && !gemm_shape(0));
     CHECK(stream_shape(128) && stream_shape(8192) && !stream_shape(8320) && !stream_shape(70));
     CHECK(kGemmMinWalked == 65 && kMaxQueries == 1024 && kQueryTile == 256);
     CHECK(gemm_valid(0) && gemm_valid(1) && gemm_valid(2) && !gemm_valid(3) && !gemm_valid(-1));
     CHECK(query_tiles(1) == 1 && query_tiles(256) == 1 && query_tiles(257) == 2 && query_tiles(1024) == 4);
+}
+
+// ---- the walk plan (walk_of), the rule the driver runs: every query in one place, the places path_of's, the order, the layout
+static long long g_walks = 0, g_walks_permuted = 0, g_walks_gemm = 0;
+
+static void check_walk(int32_t B, int32_t dim, int32_t index_dim, const std::vector<double> &norm, const std::vector<double> &err, bool shadow, int32_t form,
+                       int32_t gemm, bool bulk)
+{
+    using namespace range_bulk;
+    const Walk w = walk_of(B, dim, index_dim, norm.data(), err.data(), shadow, form, gemm, bulk);
+    const int32_t nw = (int32_t)w.perm.size();
+    bool ok = w.n_screen >= 0 && w.n_screen <= nw && (int32_t)w.zero.size() + nw == B;
+    // every query is in exactly one of zero and perm: AT ZERO there, walked here
+    std::vector<int> seen((size_t)B, 0);
+    for (int32_t b : w.zero) {
+        ok = ok && b >= 0 && b < B;
+        if (b >= 0 && b < B) { ++seen[(size_t)b]; ok = ok && range::at_zero(dim, index_dim, norm[(size_t)b]); }
+    }
+    for (int32_t b : w.perm) {
+        ok = ok && b >= 0 && b < B;
+        if (b >= 0 && b < B) { ++seen[(size_t)b]; ok = ok && !range::at_zero(dim, index_dim, norm[(size_t)b]); }
+    }
+    for (int v : seen) ok = ok && v == 1;
+    CHECK(ok);
+    if (!ok) return;
+    // a walked query's place is its path's: the SCREEN queries in front, all through the one screen, the EXACT ones behind
+    CHECK(w.gemm == gemm_takes(index_dim, w.n_screen, gemm, bulk));
+    bool placed = true, ascending = true, identity = true;
+    for (int32_t p = 0; p < nw; ++p) {
+        const int32_t b = w.perm[(size_t)p];
+        const Path path = path_of(index_dim, shadow, std::isfinite(err[(size_t)b]), w.n_screen, gemm, form, bulk);
+        placed = placed && path == (p >= w.n_screen ? ExactForm : w.gemm ? GemmScreen : Stream);
+        if (p > 0 && p != w.n_screen) ascending = ascending && w.perm[(size_t)(p - 1)] < b;
+        identity = identity && b == p;
+    }
+    for (size_t i = 1; i < w.zero.size(); ++i) ascending = ascending && w.zero[i - 1] < w.zero[i];
+    CHECK(placed);
+    CHECK(ascending);
+    CHECK(w.in_place == identity);
+    ++g_walks; g_walks_permuted += !w.in_place; g_walks_gemm += w.gemm;
+}
+
+static void test_walk()
+{
+    // every batch of 0 .. 6 queries, each with a norm > 0 or <= 0 and a finite or an infinite error, asked with the index's dim
+    // and with a foreign one, under every setting of the shadow, the two options and the entry point
+    for (int32_t index_dim : {70, 128, 512})
+        for (int32_t dim : {index_dim, index_dim + 58, 0})
+            for (int32_t B = 0; B <= 6; ++B)
+                for (int32_t states = 0; states < (1 << (2 * B)); ++states) {
+                    std::vector<double> norm((size_t)B), err((size_t)B);
+                    for (int32_t b = 0; b < B; ++b) {
+                        norm[(size_t)b] = ((states >> (2 * b)) & 1) ? 1.5 + b : (b & 1) ? -1.0 : 0.0;
+                        err[(size_t)b] = ((states >> (2 * b + 1)) & 1) ? 1e-6 * (b + 1) : kInf;
+                    }
+                    for (bool shadow : {false, true})
+                        for (int32_t form : {0, 1, 2})
+                            for (int32_t gemm : {0, 1, 2})
+                                for (bool bulk : {false, true}) check_walk(B, dim, index_dim, norm, err, shadow, form, gemm, bulk);
+                }
+    CHECK(g_walks > 1000000 && g_walks_permuted > 0 && g_walks_gemm > 0);
+    // across kGemmMinWalked: 64 SCREEN queries stream, 65 and 1024 go through the GEMM -- of a bulk call only; one query the
+    // shadow cannot bound among 65 leaves 64 for the stream and, unless it is the last, a permuted batch
+    using range_bulk::walk_of;
+    for (int32_t B : {64, 65, 1024}) {
+        const std::vector<double> norm((size_t)B, 2.0), err((size_t)B, 1e-6);
+        for (bool bulk : {false, true}) {
+            check_walk(B, 512, 512, norm, err, true, 0, 0, bulk);
+            const range_bulk::Walk w = walk_of(B, 512, 512, norm.data(), err.data(), true, 0, 0, bulk);
+            CHECK(w.n_screen == B && w.in_place && w.zero.empty() && w.gemm == (bulk && B >= 65));
+        }
+        check_walk(B, 128, 128, norm, err, true, 0, 0, true);
+        CHECK(!walk_of(B, 128, 128, norm.data(), err.data(), true, 0, 0, true).gemm);     // no GEMM shape
+    }
+    for (int32_t at : {0, 64}) {
+        const std::vector<double> norm(65, 2.0);
+        std::vector<double> err(65, 1e-6);
+        err[(size_t)at] = kNaN;                        // not finite either
+        check_walk(65, 512, 512, norm, err, true, 0, 0, true);
+        const range_bulk::Walk w = walk_of(65, 512, 512, norm.data(), err.data(), true, 0, 0, true);
+        CHECK(w.n_screen == 64 && !w.gemm && w.perm[64] == at && w.in_place == (at == 64));
+    }
 }
 
 static void test_groups()
@@ -65,7 +151,7 @@ static void test_groups()
             CHECK(q == unit || (int64_t)q * cap * kPairBytes <= kGroupBytes);
             // ... and is the largest that does, short of the call's limit
             CHECK(q == kMaxQueries || (int64_t)(q + unit) * cap * kPairBytes > kGroupBytes);
-            // the stream's groups are range_run's: max(4, (2 GiB / per_query) / 4 * 4), beyond 1024 no call asks
+            // the stream's groups are the cosine range search's own: max(4, (2 GiB / per_query) / 4 * 4), beyond 1024 no call asks
             if (unit == range::kScreenQ) {
                 const int64_t old_fit = std::max<int64_t>(range::kScreenQ, (((int64_t)2 << 30) / (cap * 56)) / range::kScreenQ * range::kScreenQ);
                 CHECK(q == std::min<int64_t>(old_fit, kMaxQueries));
@@ -281,6 +367,7 @@ static void test_lane_map()
 int main()
 {
     test_paths();
+    test_walk();
     test_groups();
     test_arguments();
     test_bound();

@@ -6445,315 +6445,419 @@ static void range_finish_query(const std::vector<range::ListEntry> &list, double
     for (size_t i = 0; i < take; ++i) hits.push_back(range::Hit{kept[i].row_id, row_base + (int64_t)kept[i].pos, kept[i].c});
 }
 
-// The call on the lane the caller holds (with the scope, if any, held shared):
-//   1. the allowed rows: the scope's bitmap, or all rows with the deleted ones cleared;
-//   2. the queries brought to the device (they may live there already), their exact norms taken as a search takes them, and --
-//      where the screen applies -- their int8 images with the quantisation error;
-//   3. every query gets its form: AT ZERO (a foreign dim, a norm <= 0: every cosine is 0, no row is walked), the SCREEN (the int8
-//      shadow, dim % 128 == 0, a finite quantisation error, "range_form" not 2) or the EXACT form; the walked queries are put
-//      in that order (a batch that is in it already is used where it lies);
-//   4. the screen -- the stream, kScreenQ queries per launch: K2i with the RANGE ending; or, for a bulk call whose walked SCREEN
-//      queries range_bulk::gemm_takes, the int8 screening GEMM with the RANGE ending, one launch per group
-//      (orr_range_bulk_plan.h) -- -> survivors' buffers -> launch_rescore_buffer_exact -> range_collect -> one list per query;
-//   5. the exact form, kMaxExactQ queries per walk: launch_dot_exact over all rows -> range_collect_dense -> the same lists;
-//   6. the host decides every listed pair (range_finish_query).
-// A buffer that was too short grows (range::grown_cap) and its launches run again; a query whose kept pairs exceed
-// "range_pair_cap" turns the call into counting: o.limit.  The search statistics do not move.
-static int range_run(orr_index *lane, const RangeArgs &a, const orr_scope *within, RangeOut &o)
+// What one call carries from stage to stage (range_run lists the stages): the lane and the call, the allowed rows, the queries'
+// norms, the walk plan (range_bulk::walk_of), what the kernels read per walked query, and the pair counters.
+struct RangeWork {
+    orr_index *const lane;
+    const RangeArgs &a;
+    RangeOut &o;
+    const hipStream_t s;
+    const int32_t B, D;
+    const int64_t n, words, allowed_rows;
+    const uint32_t *allowed = nullptr;                 // the scope's bitmap, or ws_range_allowed
+    std::vector<double> norm_a, err2;                  // per query: the exact norm; the two-level quantisation error (+inf: none was taken)
+    bool shadow = false;                               // the int8 shadow is in place, and the screen may read it
+    range_bulk::Walk walk;
+    int32_t ns = 0, nw = 0;                            // walk.n_screen; the walked queries, walk.perm.size()
+    // per walked query, in walk.perm's order
+    const float *Qp = nullptr;
+    const int8_t *q1 = nullptr, *q2 = nullptr;         // the SCREEN queries' two int8 levels
+    const double *d_err1 = nullptr;                    // ... and their one-level error (the GEMM's)
+    double *d_na = nullptr, *d_t = nullptr;
+    orr::QueryConst *d_qc = nullptr;
+    uint32_t *d_cnt = nullptr, *d_lcnt = nullptr;
+    // A query's kept pairs exceeded "range_pair_cap": from here on the call only counts -- nothing is stored, re-scored or read
+    // back, and o.total receives the counters.  It becomes o.limit.
+    bool counting = false;
+    double screen_pairs = 0.0, host_pairs = 0.0;
+    std::vector<uint32_t> h_cnt, h_lcnt;               // a launch group's counters on the host
+    std::vector<range::ListEntry> list;
+
+    RangeWork(orr_index *l, const RangeArgs &args, const orr_scope *within, RangeOut &out)
+        : lane(l), a(args), o(out), s(l->stream), B(args.B), D(l->dim), n(l->n_rows), words(((l->n_rows + 31) / 32 + 3) / 4 * 4),
+          allowed_rows(within ? within->live.load() : l->n_rows - (int64_t)owner_of(l)->dead.size()) {}
+
+    // entries per query: the sticky size as the screen uses it (its launch groups are sized by it) ...
+    int64_t buffer_cap() const { return range::buffer_cap(lane->range_buffer); }
+    // ... what the survivors' buffers hold, and what the exact form's lists hold: one entry each in a call that only counts
+    int64_t buffer_entries() const { return counting ? 1 : buffer_cap(); }
+    int64_t list_entries() const { return counting ? 1 : range::buffer_cap(std::max(lane->range_buffer, lane->range_list_cap), range::kMaxPairCap); }
+};
+
+static void range_stat(orr_index *lane, const char *name, double v)
 {
-    const orr_index *own = owner_of(lane);
-    hipStream_t s = lane->stream;
-    const int32_t B = a.B, D = lane->dim;
-    const int64_t n = lane->n_rows;
-    o.hits.assign((size_t)B, {});
-    o.total.assign((size_t)B, 0);
-    o.limit = false;
-    const int64_t allowed_rows = within ? within->live.load() : n - (int64_t)own->dead.size();
-    if (n <= 0 || allowed_rows <= 0) return ORR_OK;
-    const bool profiled = lane->profiling == 1;
+    if (lane->profiling == 1) lane->stats[(size_t)stat_slot(lane, name)].algo_bytes += v;
+}
 
-    const int64_t words = ((n + 31) / 32 + 3) / 4 * 4;
-    const uint32_t *allowed = nullptr;
+// 1. the allowed rows: the scope's bitmap, or all rows with the deleted ones cleared
+static int range_allowed_rows(RangeWork &w, const orr_scope *within)
+{
+    orr_index *lane = w.lane;
     if (within) {
-        if (within->words != words) return fail(ORR_ESTATE, "%s: the scope's bitmap has %lld words, the shard's %lld", a.fn, (long long)within->words, (long long)words);
-        allowed = within->bm;
-    } else {
-        ORR_TRY(lane->ws_range_allowed.reserve(sizeof(uint32_t) * (size_t)words));
-        {
-            Timed t(lane, "scope_fill_range", 4.0 * (double)words);
-            HIP_TRY(orr::launch_scope_fill_range(lane->ws_range_allowed.as<uint32_t>(), words, 0, n, s));
-        }
-        Timed t(lane, "scope_clear_positions", 12.0 * (double)own->dead.size());
-        HIP_TRY(orr::launch_scope_clear_positions(lane->ws_range_allowed.as<uint32_t>(), words, own->d_dead.as<int64_t>(), (int64_t)own->dead.size(), s));
-        allowed = lane->ws_range_allowed.as<uint32_t>();
+        if (within->words != w.words)
+            return fail(ORR_ESTATE, "%s: the scope's bitmap has %lld words, the shard's %lld", w.a.fn, (long long)within->words, (long long)w.words);
+        w.allowed = within->bm;
+        return ORR_OK;
     }
+    const orr_index *own = owner_of(lane);
+    ORR_TRY(lane->ws_range_allowed.reserve(sizeof(uint32_t) * (size_t)w.words));
+    {
+        Timed t(lane, "scope_fill_range", 4.0 * (double)w.words);
+        HIP_TRY(orr::launch_scope_fill_range(lane->ws_range_allowed.as<uint32_t>(), w.words, 0, w.n, w.s));
+    }
+    Timed t(lane, "scope_clear_positions", 12.0 * (double)own->dead.size());
+    HIP_TRY(orr::launch_scope_clear_positions(lane->ws_range_allowed.as<uint32_t>(), w.words, own->d_dead.as<int64_t>(), (int64_t)own->dead.size(), w.s));
+    w.allowed = lane->ws_range_allowed.as<uint32_t>();
+    return ORR_OK;
+}
 
-    // -- the queries, their norms, their forms
-    const bool foreign = scope_near::foreign_dim(a.dim, D);
-    std::vector<double> norm_a((size_t)B, 0.0), err2((size_t)B, std::numeric_limits<double>::infinity());
-    bool screen_ok = false;
-    if (!foreign) {
-        ORR_TRY(lane->ws_range_q.reserve(sizeof(float) * (size_t)B * (size_t)D));
-        ORR_TRY(lane->ws_range_norm.reserve(sizeof(double) * (size_t)B));
-        HIP_TRY(hipMemcpyAsync(lane->ws_range_q.p, a.q, sizeof(float) * (size_t)B * (size_t)D, hipMemcpyDefault, s));
+// 2. the queries brought to the device (they may live there already), their exact norms taken as a search takes them, and -- where
+// the screen's shape holds and the int8 shadow is in place -- their int8 images with the quantisation errors.  A foreign dim
+// reads no query: every one is AT ZERO.
+static int range_queries(RangeWork &w)
+{
+    orr_index *lane = w.lane;
+    const int32_t B = w.B, D = w.D;
+    hipStream_t s = w.s;
+    w.norm_a.assign((size_t)B, 0.0);
+    w.err2.assign((size_t)B, std::numeric_limits<double>::infinity());
+    if (scope_near::foreign_dim(w.a.dim, D)) return ORR_OK;
+    ORR_TRY(lane->ws_range_q.reserve(sizeof(float) * (size_t)B * (size_t)D));
+    ORR_TRY(lane->ws_range_norm.reserve(sizeof(double) * (size_t)B));
+    HIP_TRY(hipMemcpyAsync(lane->ws_range_q.p, w.a.q, sizeof(float) * (size_t)B * (size_t)D, hipMemcpyDefault, s));
+    {
+        Timed t(lane, "range_query_norms", (4.0 * D + 8.0) * B);
+        HIP_TRY(orr::launch_dot_exact(lane->ws_range_q.as<float>(), B, D, nullptr, 1, true, lane->ws_range_norm.as<double>(), B, s));
+    }
+    HIP_TRY(hipMemcpyAsync(w.norm_a.data(), lane->ws_range_norm.p, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, s));
+    if (lane->opt_range_form != range::Exact && range_bulk::stream_shape(D)) {
+        ORR_TRY(ensure_i8_shadow(lane));               // directly: the screen runs on a shard of any size
+        if (lane->is_view && !lane->i8_ready && lane->parent) {
+            // a lane made before its index had the shadow borrows it now -- when the index's own lane is idle; else the
+            // exact form answers this call (the shadow is only dropped with every lane idle: insert, compact)
+            orr_index *p = const_cast<orr_index *>(lane->parent);
+            if (p->mu.try_lock()) {
+                if (p->i8_ready) borrow_shadows(p, lane);
+                p->mu.unlock();
+            }
+        }
+        w.shadow = lane->i8_ready;
+    }
+    if (w.shadow) {
+        ORR_TRY(lane->ws_q8.reserve(2 * (size_t)B * (size_t)D));
+        ORR_TRY(lane->ws_q8s1.reserve(sizeof(float) * (size_t)B));
+        ORR_TRY(lane->ws_q8err.reserve(2 * sizeof(double) * (size_t)B));
         {
-            Timed t(lane, "range_query_norms", (4.0 * D + 8.0) * B);
-            HIP_TRY(orr::launch_dot_exact(lane->ws_range_q.as<float>(), B, D, nullptr, 1, true, lane->ws_range_norm.as<double>(), B, s));
+            Timed t(lane, "range_i8_queries", 6.0 * (double)B * D);
+            HIP_TRY(orr::launch_i8_queries(lane->ws_range_q.as<float>(), B, D, lane->ws_q8.p, lane->ws_q8s1.as<float>(), lane->ws_q8err.as<double>(), s,
+                                           lane->ws_q8err.as<double>() + B));
         }
-        HIP_TRY(hipMemcpyAsync(norm_a.data(), lane->ws_range_norm.p, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, s));
-        if (lane->opt_range_form != range::Exact && range_bulk::stream_shape(D)) {
-            ORR_TRY(ensure_i8_shadow(lane));           // directly: the screen runs on a shard of any size
-            if (lane->is_view && !lane->i8_ready && lane->parent) {
-                // a lane made before its index had the shadow borrows it now -- when the index's own lane is idle; else the
-                // exact form answers this call (the shadow is only dropped with every lane idle: insert, compact)
-                orr_index *p = const_cast<orr_index *>(lane->parent);
-                if (p->mu.try_lock()) {
-                    if (p->i8_ready) borrow_shadows(p, lane);
-                    p->mu.unlock();
-                }
-            }
-            screen_ok = lane->i8_ready;
-        }
-        if (screen_ok) {
-            ORR_TRY(lane->ws_q8.reserve(2 * (size_t)B * (size_t)D));
-            ORR_TRY(lane->ws_q8s1.reserve(sizeof(float) * (size_t)B));
-            ORR_TRY(lane->ws_q8err.reserve(2 * sizeof(double) * (size_t)B));
-            {
-                Timed t(lane, "range_i8_queries", 6.0 * (double)B * D);
-                HIP_TRY(orr::launch_i8_queries(lane->ws_range_q.as<float>(), B, D, lane->ws_q8.p, lane->ws_q8s1.as<float>(), lane->ws_q8err.as<double>(), s,
-                                               lane->ws_q8err.as<double>() + B));
-            }
-            HIP_TRY(hipMemcpyAsync(err2.data(), lane->ws_q8err.p, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, s));
-        }
+        HIP_TRY(hipMemcpyAsync(w.err2.data(), lane->ws_q8err.p, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    return ORR_OK;
+}
+
+// 3a. the queries AT ZERO: every allowed row, in candidate order, with cosine 0 -- or none.  The rows are listed once.
+static int range_answers_at_zero(RangeWork &w)
+{
+    orr_index *lane = w.lane;
+    hipStream_t s = w.s;
+    bool any = false;
+    for (int32_t b : w.walk.zero) {
+        if (!scope_near::all_rows_at_zero(w.a.min_cosine[b])) continue;
+        w.o.total[(size_t)b] = w.allowed_rows;
+        any = true;
+    }
+    if (!any || w.a.max_hits == 0) return ORR_OK;
+    const size_t take = (size_t)std::min<int64_t>(w.allowed_rows, w.a.max_hits);
+    std::vector<uint32_t> bm((size_t)w.words);
+    HIP_TRY(hipMemcpyAsync(bm.data(), w.allowed, sizeof(uint32_t) * (size_t)w.words, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    std::vector<orr::SelEntry> ent;
+    ent.reserve(take);
+    for (int64_t r = 0; r < w.n && ent.size() < take; ++r)
+        if ((bm[(size_t)(r >> 5)] >> (uint32_t)(r & 31)) & 1u) { orr::SelEntry e; e.key = 0; e.pos = (uint32_t)r; e.pad = 0; ent.push_back(e); }
+    std::vector<int64_t> ids(ent.size());
+    if (!ent.empty()) {
+        ORR_TRY(lane->ws_range_buf.reserve(sizeof(orr::SelEntry) * ent.size()));
+        ORR_TRY(lane->ws_range_bdot.reserve(sizeof(int64_t) * ent.size()));
+        HIP_TRY(hipMemcpyAsync(lane->ws_range_buf.p, ent.data(), sizeof(orr::SelEntry) * ent.size(), hipMemcpyHostToDevice, s));
+        HIP_TRY(orr::launch_scope_entry_ids(lane->ws_range_buf.as<orr::SelEntry>(), (int64_t)ent.size(), lane->d_row_ids, w.n, lane->ws_range_bdot.as<int64_t>(), s));
+        HIP_TRY(hipMemcpyAsync(ids.data(), lane->ws_range_bdot.p, sizeof(int64_t) * ent.size(), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
     }
-    std::vector<int32_t> perm;                         // the walked queries: the screen's first, then the exact form's
-    int32_t ns = 0;
-    std::vector<int32_t> zero;
-    for (int32_t b = 0; b < B; ++b) {
-        if (foreign || range::at_zero(a.dim, D, norm_a[(size_t)b])) zero.push_back(b);
-        else if (screen_ok && std::isfinite(err2[(size_t)b])) perm.push_back(b);
-    }
-    ns = (int32_t)perm.size();
-    for (int32_t b = 0; b < B; ++b)
-        if (!foreign && !range::at_zero(a.dim, D, norm_a[(size_t)b]) && !(screen_ok && std::isfinite(err2[(size_t)b]))) perm.push_back(b);
-    const int32_t nw = (int32_t)perm.size();
-
-    // -- at zero: every allowed row, in candidate order, with cosine 0 -- or none
-    bool zero_listed = false;
     std::vector<range::Hit> zero_hits;
-    for (int32_t b : zero) {
-        if (!scope_near::all_rows_at_zero(a.min_cosine[b])) continue;
-        o.total[(size_t)b] = allowed_rows;
-        if (a.max_hits == 0) continue;
-        if (!zero_listed) {
-            zero_listed = true;
-            const size_t take = (size_t)std::min<int64_t>(allowed_rows, a.max_hits);
-            std::vector<uint32_t> bm((size_t)words);
-            HIP_TRY(hipMemcpyAsync(bm.data(), allowed, sizeof(uint32_t) * (size_t)words, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            std::vector<orr::SelEntry> ent;
-            ent.reserve(take);
-            for (int64_t r = 0; r < n && ent.size() < take; ++r)
-                if ((bm[(size_t)(r >> 5)] >> (uint32_t)(r & 31)) & 1u) { orr::SelEntry e; e.key = 0; e.pos = (uint32_t)r; e.pad = 0; ent.push_back(e); }
-            std::vector<int64_t> ids(ent.size());
-            if (!ent.empty()) {
-                ORR_TRY(lane->ws_range_buf.reserve(sizeof(orr::SelEntry) * ent.size()));
-                ORR_TRY(lane->ws_range_bdot.reserve(sizeof(int64_t) * ent.size()));
-                HIP_TRY(hipMemcpyAsync(lane->ws_range_buf.p, ent.data(), sizeof(orr::SelEntry) * ent.size(), hipMemcpyHostToDevice, s));
-                HIP_TRY(orr::launch_scope_entry_ids(lane->ws_range_buf.as<orr::SelEntry>(), (int64_t)ent.size(), lane->d_row_ids, n, lane->ws_range_bdot.as<int64_t>(), s));
-                HIP_TRY(hipMemcpyAsync(ids.data(), lane->ws_range_bdot.p, sizeof(int64_t) * ent.size(), hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipStreamSynchronize(s));
-            }
-            for (size_t i = 0; i < ent.size(); ++i) zero_hits.push_back(range::Hit{ids[i], lane->row_base + (int64_t)ent[i].pos, 0.0});
-        }
-        o.hits[(size_t)b] = zero_hits;
-    }
-    if (nw == 0) return ORR_OK;
+    for (size_t i = 0; i < ent.size(); ++i) zero_hits.push_back(range::Hit{ids[i], lane->row_base + (int64_t)ent[i].pos, 0.0});
+    for (int32_t b : w.walk.zero)
+        if (scope_near::all_rows_at_zero(w.a.min_cosine[b])) w.o.hits[(size_t)b] = zero_hits;
+    return ORR_OK;
+}
 
-    // -- the walked queries in their order, with what the kernels read per query
-    bool in_place = true;
-    for (int32_t p = 0; p < nw; ++p) in_place = in_place && perm[(size_t)p] == p;
-    const float *Qp = lane->ws_range_q.as<float>();
-    const int8_t *q1 = static_cast<const int8_t *>(lane->ws_q8.p), *q2 = ns > 0 ? q1 + (size_t)B * (size_t)D : nullptr;
-    if (!in_place) {
+// 3b. the walked queries in walk.perm's order, with what the kernels read per query.  TWO LAYOUTS: a batch that is in that order
+// already (walk.in_place) is used where it lies -- Qp is the batch and the int8 image is range_queries' of all B queries; any
+// other batch is copied into the order, and its ns SCREEN queries, now in front, are imaged again.  launch_i8_queries puts the
+// second level behind the first of the batch it was given: behind B queries in the one layout, behind ns in the other.  The
+// one-level errors stay behind the B two-level ones either way.
+static int range_stage_walked(RangeWork &w)
+{
+    orr_index *lane = w.lane;
+    const int32_t B = w.B, D = w.D, ns = w.ns, nw = w.nw;
+    const std::vector<int32_t> &perm = w.walk.perm;
+    hipStream_t s = w.s;
+    w.Qp = lane->ws_range_q.as<float>();
+    if (!w.walk.in_place) {
         ORR_TRY(lane->ws_range_qp.reserve(sizeof(float) * (size_t)nw * (size_t)D));
         for (int32_t p = 0; p < nw; ++p)
             HIP_TRY(hipMemcpyAsync(lane->ws_range_qp.as<float>() + (size_t)p * D, lane->ws_range_q.as<float>() + (size_t)perm[(size_t)p] * D,
                                    sizeof(float) * (size_t)D, hipMemcpyDeviceToDevice, s));
-        Qp = lane->ws_range_qp.as<float>();
+        w.Qp = lane->ws_range_qp.as<float>();
         if (ns > 0) {
             Timed t(lane, "range_i8_queries", 6.0 * (double)ns * D);
-            HIP_TRY(orr::launch_i8_queries(Qp, ns, D, lane->ws_q8.p, lane->ws_q8s1.as<float>(), lane->ws_q8err.as<double>(), s, lane->ws_q8err.as<double>() + B));
+            HIP_TRY(orr::launch_i8_queries(w.Qp, ns, D, lane->ws_q8.p, lane->ws_q8s1.as<float>(), lane->ws_q8err.as<double>(), s, lane->ws_q8err.as<double>() + B));
         }
-        if (ns > 0) q2 = q1 + (size_t)ns * (size_t)D;
+    }
+    if (ns > 0) {
+        w.q1 = static_cast<const int8_t *>(lane->ws_q8.p);
+        w.q2 = w.q1 + (size_t)(w.walk.in_place ? B : ns) * (size_t)D;
+        w.d_err1 = lane->ws_q8err.as<double>() + B;
     }
     std::vector<double> h_na((size_t)nw), h_t((size_t)nw);
     std::vector<orr::QueryConst> h_qc((size_t)nw);
     for (int32_t p = 0; p < nw; ++p) {
         const int32_t b = perm[(size_t)p];
-        h_na[(size_t)p] = norm_a[(size_t)b];
-        h_t[(size_t)p] = a.min_cosine[b];
+        h_na[(size_t)p] = w.norm_a[(size_t)b];
+        h_t[(size_t)p] = w.a.min_cosine[b];
         orr::QueryConst qc{};
-        qc.norm_a = norm_a[(size_t)b];
-        qc.inv_sqrt_na = 1.0 / std::sqrt(norm_a[(size_t)b]);
+        qc.norm_a = w.norm_a[(size_t)b];
+        qc.inv_sqrt_na = 1.0 / std::sqrt(w.norm_a[(size_t)b]);
         qc.use_cos = 1;
         h_qc[(size_t)p] = qc;
     }
     ORR_TRY(lane->ws_range_consts.reserve((2 * sizeof(double) + sizeof(orr::QueryConst)) * (size_t)nw));
-    double *d_na = lane->ws_range_consts.as<double>(), *d_t = d_na + nw;
-    orr::QueryConst *d_qc = reinterpret_cast<orr::QueryConst *>(d_t + nw);
-    HIP_TRY(hipMemcpyAsync(d_na, h_na.data(), sizeof(double) * (size_t)nw, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_t, h_t.data(), sizeof(double) * (size_t)nw, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_qc, h_qc.data(), sizeof(orr::QueryConst) * (size_t)nw, hipMemcpyHostToDevice, s));
+    w.d_na = lane->ws_range_consts.as<double>();
+    w.d_t = w.d_na + nw;
+    w.d_qc = reinterpret_cast<orr::QueryConst *>(w.d_t + nw);
+    HIP_TRY(hipMemcpyAsync(w.d_na, h_na.data(), sizeof(double) * (size_t)nw, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(w.d_t, h_t.data(), sizeof(double) * (size_t)nw, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(w.d_qc, h_qc.data(), sizeof(orr::QueryConst) * (size_t)nw, hipMemcpyHostToDevice, s));
     ORR_TRY(lane->ws_range_cnt.reserve(sizeof(uint32_t) * 2 * (size_t)nw));
-    uint32_t *d_cnt = lane->ws_range_cnt.as<uint32_t>(), *d_lcnt = d_cnt + nw;
-    // the screen of the walked SCREEN queries (orr_range_bulk_plan.h): the GEMM reads the tiled image of their first int8 level
-    const bool gemm = range_bulk::gemm_takes(D, ns, lane->opt_range_gemm, a.bulk);
-    if (gemm) {
+    w.d_cnt = lane->ws_range_cnt.as<uint32_t>();
+    w.d_lcnt = w.d_cnt + nw;
+    // the GEMM reads the tiled image of the SCREEN queries' first int8 level
+    if (w.walk.gemm) {
         ORR_TRY(lane->ws_qtiled.reserve(orr::i8_tiled_bytes(ns, D)));
         ORR_TRY(lane->ws_tickets.reserve(sizeof(uint32_t) * 8 * 16));
         ORR_TRY(lane->ws_range_args.reserve(orr::kRangeTile16ArgsBytes));
         Timed t(lane, "range_i8_tile_queries", 2.0 * (double)ns * D);
-        HIP_TRY(orr::launch_i8_tile_queries(q1, ns, D, lane->ws_qtiled.p, s));
+        HIP_TRY(orr::launch_i8_tile_queries(w.q1, ns, D, lane->ws_qtiled.p, s));
     }
-    const double *d_err1 = lane->ws_q8err.as<double>() + B;
+    return ORR_OK;
+}
 
-    const int64_t pair_cap = lane->opt_range_pair_cap;
-    double screen_pairs = 0.0, host_pairs = 0.0;
-    std::vector<range::ListEntry> list;
-    // the lists of walked queries [p0, p0 + nq) (lcap entries each, counts h_lcnt) read back and decided
-    auto finish = [&](int32_t p0, int32_t nq, uint32_t lcap, const uint32_t *h_lcnt) -> int {
-        for (int32_t i = 0; i < nq; ++i) {
-            const int32_t b = perm[(size_t)(p0 + i)];
-            list.resize(h_lcnt[i]);
-            if (!list.empty()) {
-                HIP_TRY(hipMemcpyAsync(list.data(), lane->ws_range_list.as<range::ListEntry>() + (size_t)i * lcap, sizeof(range::ListEntry) * list.size(), hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipStreamSynchronize(s));
-            }
-            host_pairs += (double)list.size();
-            range_finish_query(list, norm_a[(size_t)b], a.min_cosine[b], a.max_hits, lane->row_base, o.hits[(size_t)b], o.total[(size_t)b]);
-        }
-        return ORR_OK;
-    };
+// THE GROWTH RULE, the screen's buffers' and the exact form's lists' alike.  `count`: what nq queries wanted of `cap` entries each.
+enum class RangeFit {
+    Fits,                                              // go on: everything was stored
+    CountOnly,                                         // a query exceeded "range_pair_cap": the call only counts from now on
+    Again,                                             // too short: `sticky` has grown from the measured count (the lane keeps it), run again
+    Full,                                              // too short, and the caller allows no growth
+};
+static RangeFit range_fit(RangeWork &w, const uint32_t *count, int32_t nq, int64_t cap, bool may_grow, int64_t &sticky, int64_t max_cap, uint32_t &worst)
+{
+    worst = *std::max_element(count, count + nq);
+    if ((int64_t)worst > w.lane->opt_range_pair_cap) w.counting = true;
+    if (w.counting) return RangeFit::CountOnly;
+    if ((int64_t)worst <= cap) return RangeFit::Fits;
+    if (!may_grow) return RangeFit::Full;
+    sticky = range::grown_cap((int64_t)worst, max_cap);
+    range_stat(w.lane, "range_buffer_growths", 1.0);
+    return RangeFit::Again;
+}
 
-    // -- the exact form over the walked queries [p0, p0 + cnt_q), kMaxExactQ per walk
-    auto exact_form = [&](int32_t p0, int32_t cnt_q) -> int {
-        for (int32_t e0 = p0; e0 < p0 + cnt_q; e0 += orr::kMaxExactQ) {
-            const int32_t nq = std::min<int32_t>(orr::kMaxExactQ, p0 + cnt_q - e0);
-            ORR_TRY(lane->ws_range_dots.reserve(sizeof(double) * (size_t)nq * (size_t)n));
-            {
-                Timed t(lane, "range_dot_exact", 4.0 * (double)n * D + 8.0 * (double)nq * (double)n);
-                HIP_TRY(orr::launch_dot_exact(lane->d_emb, n, D, Qp + (size_t)e0 * D, nq, false, lane->ws_range_dots.as<double>(), n, s));
-            }
-            uint32_t h_lcnt[orr::kMaxExactQ] = {};
-            int64_t lcap = 0;
-            for (int attempt = 0;; ++attempt) {
-                // (a call that only counts any more stores nothing: lists of one entry)
-                lcap = o.limit ? 1 : range::buffer_cap(std::max(lane->range_buffer, lane->range_list_cap), range::kMaxPairCap);
-                ORR_TRY(lane->ws_range_list.reserve(sizeof(range::ListEntry) * (size_t)nq * (size_t)lcap));
-                HIP_TRY(hipMemsetAsync(d_lcnt, 0, sizeof(uint32_t) * (size_t)nq, s));
-                {
-                    Timed t(lane, "range_collect_dense", 8.0 * (double)nq * (double)n + 16.0 * (double)n);
-                    HIP_TRY(orr::launch_range_collect_dense(lane->ws_range_dots.as<double>(), n, nq, d_na + e0, lane->d_norm_b, lane->d_row_ids, n, allowed, d_t + e0,
-                                                            lane->ws_range_list.as<range::ListEntry>(), d_lcnt, (uint32_t)lcap, s));
-                }
-                HIP_TRY(hipMemcpyAsync(h_lcnt, d_lcnt, sizeof(uint32_t) * (size_t)nq, hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipStreamSynchronize(s));
-                const uint32_t mx = *std::max_element(h_lcnt, h_lcnt + nq);
-                if ((int64_t)mx > pair_cap) o.limit = true;
-                if (o.limit || (int64_t)mx <= lcap) break;
-                if (attempt >= 3) return fail(ORR_EDEVICE, "%s: a hit list kept overflowing (%u pairs)", a.fn, mx);
-                lane->range_list_cap = range::grown_cap((int64_t)mx, range::kMaxPairCap);     // the dots stand: only the ending runs again
-                if (profiled) lane->stats[(size_t)stat_slot(lane, "range_buffer_growths")].algo_bytes += 1.0;
-            }
-            if (o.limit) { for (int32_t i = 0; i < nq; ++i) o.total[(size_t)perm[(size_t)(e0 + i)]] = (int64_t)h_lcnt[i]; continue; }
-            ORR_TRY(finish(e0, nq, (uint32_t)lcap, h_lcnt));
-        }
-        return ORR_OK;
-    };
+// ... and what a call that only counts leaves of the walked queries [p0, p0 + nq): the counters, upper bounds of their hits
+static void range_totals_are_counts(RangeWork &w, int32_t p0, int32_t nq, const uint32_t *count)
+{
+    for (int32_t i = 0; i < nq; ++i) w.o.total[(size_t)w.walk.perm[(size_t)(p0 + i)]] = (int64_t)count[i];
+}
 
-    // -- the screen over the walked queries [0, ns): as many launch groups at a time as their buffers allow
-    std::vector<uint32_t> h_cnt_v, h_lcnt_v;
-    for (int32_t b0 = 0; b0 < ns;) {
-        const int64_t cap = range::buffer_cap(lane->range_buffer);
-        static_assert(range_bulk::kPairBytes == (int64_t)(sizeof(orr::SelEntry) + sizeof(double) + sizeof(range::ListEntry)), "what one kept pair takes");
-        const int32_t nq = std::min<int32_t>(ns - b0, range_bulk::group_queries(cap, gemm ? 1 : range::kScreenQ));
-        if (!o.limit) {
-            ORR_TRY(lane->ws_range_buf.reserve(sizeof(orr::SelEntry) * (size_t)nq * (size_t)cap));
-            ORR_TRY(lane->ws_range_bdot.reserve(sizeof(double) * (size_t)nq * (size_t)cap));
-            ORR_TRY(lane->ws_range_list.reserve(sizeof(range::ListEntry) * (size_t)nq * (size_t)cap));
-        } else {
-            ORR_TRY(lane->ws_range_buf.reserve(sizeof(orr::SelEntry) * (size_t)nq));
+// 6. the lists of the walked queries [p0, p0 + nq) (lcap entries each, counts h_lcnt) read back, and every listed pair decided by
+// the host (range_finish_query)
+static int range_read_back(RangeWork &w, int32_t p0, int32_t nq, uint32_t lcap, const uint32_t *h_lcnt)
+{
+    orr_index *lane = w.lane;
+    for (int32_t i = 0; i < nq; ++i) {
+        const int32_t b = w.walk.perm[(size_t)(p0 + i)];
+        w.list.resize(h_lcnt[i]);
+        if (!w.list.empty()) {
+            HIP_TRY(hipMemcpyAsync(w.list.data(), lane->ws_range_list.as<range::ListEntry>() + (size_t)i * lcap, sizeof(range::ListEntry) * w.list.size(), hipMemcpyDeviceToHost, w.s));
+            HIP_TRY(hipStreamSynchronize(w.s));
         }
-        const uint32_t scap = o.limit ? 1u : (uint32_t)cap;            // (a call that only counts any more stores nothing: buffers of one entry)
-        HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(uint32_t) * 2 * (size_t)nw, s));
-        if (gemm) {
-            // one launch for the group; queries [b0, b0 + nq) of the tiled image start at a query tile only for b0 == 0, so a
-            // later group gets an image of its own
-            if (b0 > 0) {
-                Timed t(lane, "range_i8_tile_queries", 2.0 * (double)nq * D);
-                HIP_TRY(orr::launch_i8_tile_queries(q1 + (size_t)b0 * D, nq, D, lane->ws_qtiled.p, s));
-            }
-            HIP_TRY(hipMemsetAsync(lane->ws_tickets.p, 0, sizeof(uint32_t) * 8, s));
-            Timed t(lane, "screen_tile16_range", 1.0 * (double)n * D + 24.0 * (double)n + (double)orr::i8_tiled_bytes(nq, D));   // per row: scale, two relative norms, normB, its share of the bitmap
-            HIP_TRY(orr::launch_screen_tile16_range(lane->ws_qtiled.p, lane->ws_q8s1.as<float>() + b0, d_err1 + b0, nq, lane->emb_i8.p, lane->i8_scale.as<float>(),
-                                                    lane->i8_rel_err.as<float>(), lane->i8_rel_hat.as<float>(), lane->d_norm_b, n, D, d_qc + b0, d_t + b0, allowed,
-                                                    d_cnt, lane->ws_range_buf.as<orr::SelEntry>(), scap, lane->ws_tickets.as<uint32_t>(), lane->ws_range_args.p, s));
-        }
-        for (int32_t g0 = 0; !gemm && g0 < nq; g0 += range::kScreenQ) {
-            const int32_t gq = std::min<int32_t>(range::kScreenQ, nq - g0), p = b0 + g0;
-            Timed t(lane, "screen_gemv_i8_range", 1.0 * (double)n * D + 20.0 * (double)n + 2.0 * (double)gq * D);   // per row: scale, two relative norms, normB
-            HIP_TRY(orr::launch_screen_gemv_i8_range(q1 + (size_t)p * D, q2 + (size_t)p * D, lane->ws_q8s1.as<float>() + p, lane->ws_q8err.as<double>() + p, gq,
-                                                     lane->emb_i8.p, lane->i8_scale.as<float>(), lane->i8_rel_err.as<float>(), lane->i8_rel_hat.as<float>(),
-                                                     lane->d_norm_b, n, D, d_qc + p, d_t + p, allowed, d_cnt + g0,
-                                                     lane->ws_range_buf.as<orr::SelEntry>() + (size_t)g0 * scap, scap, s));
-        }
-        h_cnt_v.assign((size_t)nq, 0u);
-        h_lcnt_v.assign((size_t)nq, 0u);
-        uint32_t *const h_cnt = h_cnt_v.data(), *const h_lcnt = h_lcnt_v.data();
-        HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, sizeof(uint32_t) * (size_t)nq, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        const uint32_t mx = *std::max_element(h_cnt, h_cnt + nq);
-        if ((int64_t)mx > pair_cap) o.limit = true;
-        if (o.limit) {
-            for (int32_t i = 0; i < nq; ++i) o.total[(size_t)perm[(size_t)(b0 + i)]] = (int64_t)h_cnt[i];
-            b0 += nq;
-            continue;
-        }
-        if ((int64_t)mx > cap) {
-            if (cap >= range::kMaxBuffer) {            // more survivors than a buffer of the exact re-score holds: the exact form
-                ORR_TRY(exact_form(b0, nq));
-                b0 += nq;
-                continue;
-            }
-            lane->range_buffer = range::grown_cap((int64_t)mx, range::kMaxBuffer);
-            if (profiled) lane->stats[(size_t)stat_slot(lane, "range_buffer_growths")].algo_bytes += 1.0;
-            continue;                                  // the launch groups run again with the grown size
-        }
-        for (int32_t i = 0; i < nq; ++i) screen_pairs += (double)h_cnt[i];
-        {
-            Timed t(lane, "range_rescore_exact", (4.0 * D + 40.0) * (double)mx * nq);
-            HIP_TRY(orr::launch_rescore_buffer_exact(lane->d_emb, D, Qp + (size_t)b0 * D, nq, lane->d_norm_b, lane->d_created, orr::KwView{}, d_qc + b0, 0, d_cnt,
-                                                     (uint32_t)cap, lane->ws_range_buf.as<orr::SelEntry>(), lane->ws_range_bdot.as<double>(), s));
-        }
-        {
-            Timed t(lane, "range_collect", 64.0 * (double)mx * nq);
-            HIP_TRY(orr::launch_range_collect(lane->ws_range_buf.as<orr::SelEntry>(), lane->ws_range_bdot.as<double>(), d_cnt, (uint32_t)cap, nq, d_na + b0, lane->d_norm_b,
-                                              lane->d_row_ids, n, d_t + b0, lane->ws_range_list.as<range::ListEntry>(), d_lcnt, (uint32_t)cap, s));
-        }
-        HIP_TRY(hipMemcpyAsync(h_lcnt, d_lcnt, sizeof(uint32_t) * (size_t)nq, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        ORR_TRY(finish(b0, nq, (uint32_t)cap, h_lcnt));
-        b0 += nq;
+        w.host_pairs += (double)w.list.size();
+        range_finish_query(w.list, w.norm_a[(size_t)b], w.a.min_cosine[b], w.a.max_hits, lane->row_base, w.o.hits[(size_t)b], w.o.total[(size_t)b]);
     }
-    ORR_TRY(exact_form(ns, nw - ns));
+    return ORR_OK;
+}
+
+// 5. one walk of the exact form, the walked queries [e0, e0 + nq), nq <= kMaxExactQ: launch_dot_exact over all rows ->
+// range_collect_dense -> one list per query.  A list that was too short grows, and only the ending runs again: the dots stand.
+static int range_exact_walk(RangeWork &w, int32_t e0, int32_t nq)
+{
+    orr_index *lane = w.lane;
+    const int64_t n = w.n;
+    hipStream_t s = w.s;
+    ORR_TRY(lane->ws_range_dots.reserve(sizeof(double) * (size_t)nq * (size_t)n));
+    {
+        Timed t(lane, "range_dot_exact", 4.0 * (double)n * w.D + 8.0 * (double)nq * (double)n);
+        HIP_TRY(orr::launch_dot_exact(lane->d_emb, n, w.D, w.Qp + (size_t)e0 * w.D, nq, false, lane->ws_range_dots.as<double>(), n, s));
+    }
+    uint32_t h_lcnt[orr::kMaxExactQ] = {}, mx = 0;
+    int64_t lcap = 0;
+    RangeFit fit = RangeFit::Again;
+    for (int attempt = 0; fit == RangeFit::Again; ++attempt) {
+        lcap = w.list_entries();
+        ORR_TRY(lane->ws_range_list.reserve(sizeof(range::ListEntry) * (size_t)nq * (size_t)lcap));
+        HIP_TRY(hipMemsetAsync(w.d_lcnt, 0, sizeof(uint32_t) * (size_t)nq, s));
+        {
+            Timed t(lane, "range_collect_dense", 8.0 * (double)nq * (double)n + 16.0 * (double)n);
+            HIP_TRY(orr::launch_range_collect_dense(lane->ws_range_dots.as<double>(), n, nq, w.d_na + e0, lane->d_norm_b, lane->d_row_ids, n, w.allowed, w.d_t + e0,
+                                                    lane->ws_range_list.as<range::ListEntry>(), w.d_lcnt, (uint32_t)lcap, s));
+        }
+        HIP_TRY(hipMemcpyAsync(h_lcnt, w.d_lcnt, sizeof(uint32_t) * (size_t)nq, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        fit = range_fit(w, h_lcnt, nq, lcap, attempt < 3, lane->range_list_cap, range::kMaxPairCap, mx);
+        if (fit == RangeFit::Full) return fail(ORR_EDEVICE, "%s: a hit list kept overflowing (%u pairs)", w.a.fn, mx);
+    }
+    if (fit == RangeFit::CountOnly) { range_totals_are_counts(w, e0, nq, h_lcnt); return ORR_OK; }
+    return range_read_back(w, e0, nq, (uint32_t)lcap, h_lcnt);
+}
+
+// ... over the walked queries [p0, p0 + cnt_q), kMaxExactQ per walk
+static int range_exact_form(RangeWork &w, int32_t p0, int32_t cnt_q)
+{
+    for (int32_t e0 = p0; e0 < p0 + cnt_q; e0 += orr::kMaxExactQ) ORR_TRY(range_exact_walk(w, e0, std::min<int32_t>(orr::kMaxExactQ, p0 + cnt_q - e0)));
+    return ORR_OK;
+}
+
+// 4a. one launch group of the screen, the walked SCREEN queries [b0, b0 + nq) at `cap` entries each: the GEMM in ONE launch, or
+// the stream, kScreenQ queries per launch -> the survivors' buffers, their counters in w.h_cnt
+static int range_screen_group(RangeWork &w, int32_t b0, int32_t nq, int64_t cap)
+{
+    orr_index *lane = w.lane;
+    const int32_t D = w.D;
+    const int64_t n = w.n;
+    hipStream_t s = w.s;
+    static_assert(range_bulk::kPairBytes == (int64_t)(sizeof(orr::SelEntry) + sizeof(double) + sizeof(range::ListEntry)), "what one kept pair takes");
+    const uint32_t scap = (uint32_t)w.buffer_entries();
+    ORR_TRY(lane->ws_range_buf.reserve(sizeof(orr::SelEntry) * (size_t)nq * (size_t)scap));
+    if (!w.counting) {                                 // (what the re-score and the collecting write)
+        ORR_TRY(lane->ws_range_bdot.reserve(sizeof(double) * (size_t)nq * (size_t)cap));
+        ORR_TRY(lane->ws_range_list.reserve(sizeof(range::ListEntry) * (size_t)nq * (size_t)cap));
+    }
+    HIP_TRY(hipMemsetAsync(w.d_cnt, 0, sizeof(uint32_t) * 2 * (size_t)w.nw, s));
+    if (w.walk.gemm) {
+        // one launch for the group; queries [b0, b0 + nq) of the tiled image start at a query tile only for b0 == 0, so a
+        // later group gets an image of its own
+        if (b0 > 0) {
+            Timed t(lane, "range_i8_tile_queries", 2.0 * (double)nq * D);
+            HIP_TRY(orr::launch_i8_tile_queries(w.q1 + (size_t)b0 * D, nq, D, lane->ws_qtiled.p, s));
+        }
+        HIP_TRY(hipMemsetAsync(lane->ws_tickets.p, 0, sizeof(uint32_t) * 8, s));
+        Timed t(lane, "screen_tile16_range", 1.0 * (double)n * D + 24.0 * (double)n + (double)orr::i8_tiled_bytes(nq, D));   // per row: scale, two relative norms, normB, its share of the bitmap
+        HIP_TRY(orr::launch_screen_tile16_range(lane->ws_qtiled.p, lane->ws_q8s1.as<float>() + b0, w.d_err1 + b0, nq, lane->emb_i8.p, lane->i8_scale.as<float>(),
+                                                lane->i8_rel_err.as<float>(), lane->i8_rel_hat.as<float>(), lane->d_norm_b, n, D, w.d_qc + b0, w.d_t + b0, w.allowed,
+                                                w.d_cnt, lane->ws_range_buf.as<orr::SelEntry>(), scap, lane->ws_tickets.as<uint32_t>(), lane->ws_range_args.p, s));
+    }
+    for (int32_t g0 = 0; !w.walk.gemm && g0 < nq; g0 += range::kScreenQ) {
+        const int32_t gq = std::min<int32_t>(range::kScreenQ, nq - g0), p = b0 + g0;
+        Timed t(lane, "screen_gemv_i8_range", 1.0 * (double)n * D + 20.0 * (double)n + 2.0 * (double)gq * D);   // per row: scale, two relative norms, normB
+        HIP_TRY(orr::launch_screen_gemv_i8_range(w.q1 + (size_t)p * D, w.q2 + (size_t)p * D, lane->ws_q8s1.as<float>() + p, lane->ws_q8err.as<double>() + p, gq,
+                                                 lane->emb_i8.p, lane->i8_scale.as<float>(), lane->i8_rel_err.as<float>(), lane->i8_rel_hat.as<float>(),
+                                                 lane->d_norm_b, n, D, w.d_qc + p, w.d_t + p, w.allowed, w.d_cnt + g0,
+                                                 lane->ws_range_buf.as<orr::SelEntry>() + (size_t)g0 * scap, scap, s));
+    }
+    w.h_cnt.assign((size_t)nq, 0u);
+    HIP_TRY(hipMemcpyAsync(w.h_cnt.data(), w.d_cnt, sizeof(uint32_t) * (size_t)nq, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return ORR_OK;
+}
+
+// 4b. ... whose survivors, at most mx per query, fit: launch_rescore_buffer_exact -> range_collect -> one list per query -> the host
+static int range_rescore_collect(RangeWork &w, int32_t b0, int32_t nq, int64_t cap, uint32_t mx)
+{
+    orr_index *lane = w.lane;
+    hipStream_t s = w.s;
+    for (int32_t i = 0; i < nq; ++i) w.screen_pairs += (double)w.h_cnt[(size_t)i];
+    {
+        Timed t(lane, "range_rescore_exact", (4.0 * w.D + 40.0) * (double)mx * nq);
+        HIP_TRY(orr::launch_rescore_buffer_exact(lane->d_emb, w.D, w.Qp + (size_t)b0 * w.D, nq, lane->d_norm_b, lane->d_created, orr::KwView{}, w.d_qc + b0, 0, w.d_cnt,
+                                                 (uint32_t)cap, lane->ws_range_buf.as<orr::SelEntry>(), lane->ws_range_bdot.as<double>(), s));
+    }
+    {
+        Timed t(lane, "range_collect", 64.0 * (double)mx * nq);
+        HIP_TRY(orr::launch_range_collect(lane->ws_range_buf.as<orr::SelEntry>(), lane->ws_range_bdot.as<double>(), w.d_cnt, (uint32_t)cap, nq, w.d_na + b0, lane->d_norm_b,
+                                          lane->d_row_ids, w.n, w.d_t + b0, lane->ws_range_list.as<range::ListEntry>(), w.d_lcnt, (uint32_t)cap, s));
+    }
+    w.h_lcnt.assign((size_t)nq, 0u);
+    HIP_TRY(hipMemcpyAsync(w.h_lcnt.data(), w.d_lcnt, sizeof(uint32_t) * (size_t)nq, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return range_read_back(w, b0, nq, (uint32_t)cap, w.h_lcnt.data());
+}
+
+// 4. the screen over the walked queries [0, ns): as many queries per launch group as their buffers allow
+// (range_bulk::group_queries); a group whose buffers were too short runs again with the grown size
+static int range_screen(RangeWork &w)
+{
+    for (int32_t b0 = 0, nq = 0; b0 < w.ns; b0 += nq) {
+        int64_t cap = 0;
+        uint32_t mx = 0;
+        RangeFit fit = RangeFit::Again;
+        while (fit == RangeFit::Again) {
+            cap = w.buffer_cap();
+            nq = std::min<int32_t>(w.ns - b0, range_bulk::group_queries(cap, w.walk.gemm ? 1 : range::kScreenQ));
+            ORR_TRY(range_screen_group(w, b0, nq, cap));
+            fit = range_fit(w, w.h_cnt.data(), nq, cap, cap < range::kMaxBuffer, w.lane->range_buffer, range::kMaxBuffer, mx);
+        }
+        if (fit == RangeFit::CountOnly) range_totals_are_counts(w, b0, nq, w.h_cnt.data());
+        else if (fit == RangeFit::Full) ORR_TRY(range_exact_form(w, b0, nq));      // more survivors than a buffer of the exact re-score holds
+        else ORR_TRY(range_rescore_collect(w, b0, nq, cap, mx));
+    }
+    return ORR_OK;
+}
+
+// The call on the lane the caller holds (with the scope, if any, held shared), stage by stage:
+//   1. range_allowed_rows;
+//   2. range_queries;
+//   3. every query gets its form -- range_bulk::walk_of: AT ZERO (a foreign dim, a norm <= 0: every cosine is 0, no row is
+//      walked), the SCREEN (stream_applies) or the EXACT form, and which screen (gemm_takes) -- and the walked queries their
+//      order: range_answers_at_zero, range_stage_walked;
+//   4. range_screen: range_screen_group -- the stream, K2i with the RANGE ending, or the int8 screening GEMM with the RANGE
+//      ending, one launch per group -- -> range_rescore_collect; beyond range::kMaxBuffer survivors the exact form;
+//   5. range_exact_form, kMaxExactQ queries per range_exact_walk;
+//   6. range_read_back: the host decides every listed pair (range_finish_query).
+// A buffer or list that was too short grows and its launches run again; a query whose kept pairs exceed "range_pair_cap" turns
+// the call into counting (range_fit, RangeWork::counting): o.limit.  The search statistics do not move.
+static int range_run(orr_index *lane, const RangeArgs &a, const orr_scope *within, RangeOut &o)
+{
+    RangeWork w(lane, a, within, o);
+    o.hits.assign((size_t)w.B, {});
+    o.total.assign((size_t)w.B, 0);
+    o.limit = false;
+    if (w.n <= 0 || w.allowed_rows <= 0) return ORR_OK;
+    ORR_TRY(range_allowed_rows(w, within));
+    ORR_TRY(range_queries(w));
+    w.walk = range_bulk::walk_of(w.B, a.dim, w.D, w.norm_a.data(), w.err2.data(), w.shadow, lane->opt_range_form, lane->opt_range_gemm, a.bulk);
+    w.ns = w.walk.n_screen;
+    w.nw = (int32_t)w.walk.perm.size();
+    ORR_TRY(range_answers_at_zero(w));
+    if (w.nw == 0) return ORR_OK;
+    ORR_TRY(range_stage_walked(w));
+    ORR_TRY(range_screen(w));
+    ORR_TRY(range_exact_form(w, w.ns, w.nw - w.ns));
+    o.limit = w.counting;
     if (o.limit)                                       // the queries answered before the limit was met: their hits are an upper bound too
-        for (int32_t b = 0; b < B; ++b) o.hits[(size_t)b].clear();
-    if (profiled) {
-        lane->stats[(size_t)stat_slot(lane, "range_screen_pairs")].algo_bytes += 16.0 * screen_pairs;
-        lane->stats[(size_t)stat_slot(lane, "range_host_pairs")].algo_bytes += 32.0 * host_pairs;
-    }
+        for (int32_t b = 0; b < w.B; ++b) o.hits[(size_t)b].clear();
+    range_stat(lane, "range_screen_pairs", 16.0 * w.screen_pairs);
+    range_stat(lane, "range_host_pairs", 32.0 * w.host_pairs);
     return ORR_OK;
 }
 
@@ -8890,20 +8994,6 @@ int orr_cluster_search_batch_in_scopes(orr_cluster *c, int32_t B, int32_t dim, c
 
 // Every shard runs the single call at once, each on a lane of its own; the host merges the shards' lists by (cosine descending,
 // order_key ascending), sums the totals and cuts at max_hits.  The limit met on any shard is the call's: the upper bounds summed.
-static int cluster_range_search(orr_cluster *c, const RangeArgs &a, const orr_cluster_scope *within, orr_range_hit *out_hits, int32_t *out_n, int64_t *out_total);
-int orr_cluster_search_range_cosine(orr_cluster *c, int32_t B, int32_t dim, const float *q_host, const double *min_cosine,
-                                    const orr_cluster_scope *within, int32_t max_hits, orr_range_hit *out_hits, int32_t *out_n, int64_t *out_total)
-{
-    return cluster_range_search(c, RangeArgs{B, dim, q_host, min_cosine, max_hits, false, "orr_cluster_search_range_cosine"}, within, out_hits, out_n, out_total);
-}
-
-int orr_cluster_search_range_cosine_bulk(orr_cluster *c, int32_t B, int32_t dim, const float *q_host, const double *min_cosine,
-                                         const orr_cluster_scope *within, int32_t max_hits, orr_range_hit *out_hits, int32_t *out_n, int64_t *out_total)
-{
-    return cluster_range_search(c, RangeArgs{B, dim, q_host, min_cosine, max_hits, true, "orr_cluster_search_range_cosine_bulk"}, within, out_hits, out_n, out_total);
-}
-
-// (the body of the two calls above; C++ linkage inside the extern "C" block is fine for a static function)
 static int cluster_range_search(orr_cluster *c, const RangeArgs &a, const orr_cluster_scope *within, orr_range_hit *out_hits, int32_t *out_n, int64_t *out_total)
 {
     const char *fn = a.fn;
@@ -8954,6 +9044,18 @@ static int cluster_range_search(orr_cluster *c, const RangeArgs &a, const orr_cl
         if (!o.limit) o.hits[(size_t)b] = range::merge_lists(lists, max_hits);
     }
     return range_write(fn, a, o, out_hits, out_n, out_total);
+}
+
+int orr_cluster_search_range_cosine(orr_cluster *c, int32_t B, int32_t dim, const float *q_host, const double *min_cosine,
+                                    const orr_cluster_scope *within, int32_t max_hits, orr_range_hit *out_hits, int32_t *out_n, int64_t *out_total)
+{
+    return cluster_range_search(c, RangeArgs{B, dim, q_host, min_cosine, max_hits, false, "orr_cluster_search_range_cosine"}, within, out_hits, out_n, out_total);
+}
+
+int orr_cluster_search_range_cosine_bulk(orr_cluster *c, int32_t B, int32_t dim, const float *q_host, const double *min_cosine,
+                                         const orr_cluster_scope *within, int32_t max_hits, orr_range_hit *out_hits, int32_t *out_n, int64_t *out_total)
+{
+    return cluster_range_search(c, RangeArgs{B, dim, q_host, min_cosine, max_hits, true, "orr_cluster_search_range_cosine_bulk"}, within, out_hits, out_n, out_total);
 }
 
 }  // extern "C"

@@ -13,9 +13,13 @@
 //                 are what the old call costs, and the old call's launches are a tested property); 1 -- from one query up;
 //                 2 -- never.  Else the stream, four per launch.  The one-level error is finite exactly when the two-level one
 //                 is (i8_queries_kernel: both are +inf for a query it cannot bound), so one test serves both screens.
+//   the walk      walk_of: the rule the driver runs (range_run, orr_api.hip).  From the queries' exact norms and quantisation
+//                 errors: the queries AT ZERO (range::at_zero), the walked ones in their order -- the SCREEN form's, then the
+//                 EXACT form's, each ascending --, whether the GEMM screens the former (gemm_takes), and whether the batch is in
+//                 that order already and is walked where it lies.
 //   launch groups group_queries: as many queries per launch as their survivors' buffers, re-scored dots and lists fit in 2 GiB
-//                 (range_run's rule), in whole queries for the GEMM and in whole launches of four for the stream.  A launch
-//                 of more than kQueryTile = 256 queries walks several query tiles.
+//                 (what range_screen_group reserves), in whole queries for the GEMM and in whole launches of four for the
+//                 stream.  A launch of more than kQueryTile = 256 queries walks several query tiles.
 //   bound         The GEMM multiplies the FIRST query level only: q^ = s1 a, dot^ = se_r s1 I.  range::cos_bound's derivation
 //                 holds for any q^ -- it uses |q - q^| and |e^| only -- so the bound is cos_bound(re, rh, qe1) with
 //                 qe1 = sqrt(err2_level1) / sqrt(normA), err2_level1 = 1.000001 |q - s1 a|^2 as i8_queries_kernel sums it in
@@ -33,6 +37,10 @@
 #pragma once
 
 #include "orr_range_plan.h"
+
+#include <cmath>
+#include <cstdint>
+#include <vector>
 
 namespace range_bulk {
 
@@ -59,7 +67,7 @@ inline int32_t first_invalid(int32_t B, int32_t dim, bool q_null, const double *
     return 0;
 }
 
-// the shapes: where the streaming screen runs today (range_run), and the four-wave forms' condition
+// the shapes: where the streaming screen runs (range_queries takes the int8 images there), and the four-wave forms' condition
 inline bool stream_shape(int32_t dim) { return dim > 0 && dim % 128 == 0 && 2 * (int64_t)range::kScreenQ * dim <= 65536; }
 inline bool gemm_shape(int32_t dim) { return dim > 0 && dim % 128 == 0 && dim / 64 > 6; }
 
@@ -82,6 +90,34 @@ inline Path path_of(int32_t dim, bool shadow, bool finite_err, int32_t n_screen,
 {
     if (!stream_applies(dim, shadow, finite_err, range_form)) return ExactForm;
     return gemm_takes(dim, n_screen, range_gemm, bulk) ? GemmScreen : Stream;
+}
+
+// The walk of one call, both entry points': every query's form and the order the walked ones are put in.
+struct Walk {
+    std::vector<int32_t> zero;                        // the queries AT ZERO (range::at_zero: no row is walked), ascending
+    std::vector<int32_t> perm;                        // the walked queries: the SCREEN form's first, then the EXACT form's, each ascending
+    int32_t n_screen = 0;                             // how many of perm have the SCREEN form
+    bool gemm = false;                                // the GEMM screens them (gemm_takes); else the stream
+    bool in_place = true;                             // perm[p] == p throughout: the batch is walked where it lies
+};
+
+// norm_a[b]: query b's exact norm; err2[b]: its two-level quantisation error (+inf where none was taken); shadow: the int8 shadow
+// is in place.  Made of range::at_zero, stream_applies and gemm_takes and of nothing else.
+inline Walk walk_of(int32_t B, int32_t dim, int32_t index_dim, const double *norm_a, const double *err2, bool shadow, int32_t range_form,
+                    int32_t range_gemm, bool bulk)
+{
+    Walk w;
+    std::vector<int32_t> exact;
+    for (int32_t b = 0; b < B; ++b) {
+        if (range::at_zero(dim, index_dim, norm_a[b])) w.zero.push_back(b);
+        else if (stream_applies(index_dim, shadow, std::isfinite(err2[b]), range_form)) w.perm.push_back(b);
+        else exact.push_back(b);
+    }
+    w.n_screen = (int32_t)w.perm.size();
+    w.perm.insert(w.perm.end(), exact.begin(), exact.end());
+    w.gemm = gemm_takes(index_dim, w.n_screen, range_gemm, bulk);
+    for (size_t p = 0; p < w.perm.size(); ++p) w.in_place = w.in_place && w.perm[p] == (int32_t)p;
+    return w;
 }
 
 // Queries of one launch group at `cap` entries per query: what fits kGroupBytes, in whole units (1: the GEMM; range::kScreenQ:

@@ -73,15 +73,26 @@ def test_the_kernel_the_driver_and_the_selftest_share_the_rules():
         assert piece in ending, piece
     for absent in ("i8_rowf", "kw_matches", "rowc", "created", "epilogue_requests", "fused_epilogue16"):
         assert absent not in ending, absent
-    # the driver: one range_run, its screen stage a choice; nothing sized by 64 any more
-    assert api.count("static int range_run(") == 1
-    run = api.split("static int range_run(")[1].split("\nstatic int range_on_lane(")[0]
-    for piece in ("range_bulk::gemm_takes(D, ns, lane->opt_range_gemm, a.bulk)", "range_bulk::group_queries(cap, gemm ? 1 : range::kScreenQ)",
+    # the driver: one range_run, the list of its stages; which form a query gets and which screen is the header's walk plan,
+    # called once; nothing sized by 64 any more
+    assert api.count("static int range_run(") == 1 and api.count("// ---- cosine range search") == 1
+    section = api.split("// ---- cosine range search")[1].split("\nstatic int range_on_lane(")[0]
+    run = section.split("static int range_run(")[1]
+    assert section.count("range_bulk::walk_of(") == 1 and "range_bulk::walk_of(w.B, a.dim, w.D, " in run
+    walk = header.split("inline Walk walk_of(")[1].split("\n}\n")[0]
+    for piece in ("range::at_zero(dim, index_dim, ", "stream_applies(index_dim, shadow, ", "gemm_takes(index_dim, w.n_screen, range_gemm, bulk)"):
+        assert piece in walk, piece
+    assert re.search(r"\bwalk_of\(", selftest)
+    for name in ("stream_applies(", "gemm_takes(", "range::at_zero(", "isfinite("):    # the classification exists once, in the header
+        assert name not in section, name
+    for piece in ("range_bulk::group_queries(cap, w.walk.gemm ? 1 : range::kScreenQ)",
                   "orr::launch_screen_tile16_range(", "orr::launch_screen_gemv_i8_range(", "\"screen_tile16_range\"", "range::grown_cap("):
-        assert piece in run, piece
-    assert "range::kMaxQueries" not in run and "kMaxQueries]" not in run
+        assert piece in section, piece
+    assert section.count("range::grown_cap(") == 1                             # the growth rule exists once
+    assert "[&]" not in section                                                # stages are functions, not closures over the call
+    assert "range::kMaxQueries" not in section and "kMaxQueries]" not in section
     for name in ("plan_pass", "run_shard_once", "sstats"):
-        assert name not in run, name
+        assert name not in section, name
     launcher = screen.split("hipError_t launch_screen_tile16_range(")[1].split("\n}\n")[0]
     assert "screen_grid(blocks, D / 64)" in launcher and "ensure_max_dynamic_lds<screen_tile16_kernel<NT, false, false, true>>" in launcher
     makefile = open(os.path.join(CSRC, "Makefile")).read()

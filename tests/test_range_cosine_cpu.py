@@ -46,12 +46,16 @@ def test_the_kernels_the_driver_and_the_selftest_share_the_inlines():
     finish = api.split("static void range_finish_query(")[1].split("\n}\n")[0]
     assert "scope_near::cosine_of(e.dot, norm_a, e.norm_b)" in finish and "scope_near::verdict(c, t)" in finish and "range::before(" in finish
     assert "sqrt" not in finish
-    for name in ("first_invalid", "at_zero", "grown_cap", "buffer_cap", "merge_lists", "pair_cap_valid", "buffer_valid", "form_valid"):
+    for name in ("first_invalid", "grown_cap", "buffer_cap", "merge_lists", "pair_cap_valid", "buffer_valid", "form_valid"):
         assert f"range::{name}(" in api, name
+    # ... and which queries are AT ZERO through the walk plan it calls (orr_range_bulk_plan.h, both entry points')
+    walk = open(os.path.join(CSRC, "orr_range_bulk_plan.h")).read().split("inline Walk walk_of(")[1].split("\n}\n")[0]
+    assert "range::at_zero(" in walk and "range_bulk::walk_of(" in api
     # beside the search passes, not through them
-    run = api.split("static int range_run(")[1].split("\nstatic int range_on_lane(")[0]
+    assert api.count("static int range_run(") == 1 and api.count("// ---- cosine range search") == 1
+    section = api.split("// ---- cosine range search")[1].split("\nstatic int range_on_lane(")[0]
     for name in ("plan_pass", "run_shard_once", "sstats"):
-        assert name not in run, name
+        assert name not in section, name
     makefile = open(os.path.join(CSRC, "Makefile")).read()
     assert "host/orr_range_plan_selftest" in makefile.split("all:")[0]                    # in SELFTEST: build() makes it
     assert "orr_range_plan.h" in makefile.split("%.o: %.hip")[1].split("\n")[0]
