@@ -34,6 +34,7 @@
 #include "orr_escalation.h"
 #include "orr_insert_plan.h"
 #include "orr_kernels.h"
+#include "orr_keyword_plan.h"
 #include "orr_lanes.h"
 #include "orr_scope_plan.h"
 #include "orr_mask_plan.h"
@@ -152,6 +153,39 @@ struct ScreenCapture {
     std::vector<orr::SelEntry> buf;
 };
 
+// What the last keyword chain on a lane left clean, so that the next one clears only what nobody has vouched for.  The chain
+// withdraws everything on entry (launch_keyword_side) and its caller grants it again behind the clean (clean_keyword_side);
+// each voucher names the buffer it is about, which may have moved since.  A chain whose caller never cleaned finds nothing
+// granted and clears everything itself: slow, not wrong.
+struct KwVouchers {
+    size_t bitmaps = 0;                // leading bytes of ws_bitmaps known to be zero
+    const void *bitmaps_of = nullptr;
+    bool counters = false;             // the hit counter and the per-term hit counts are zero
+    const void *counters_of[2] = {nullptr, nullptr};   // ws_counter, ws_kwalias
+    bool clear_in_flight = false;      // the bitmaps' clearing is on the auxiliary stream: ev_bm_clean is recorded behind it.  No
+                                       // voucher but a debt -- the next chain to write the bitmaps waits for it -- so it outlives withdraw
+    KwVouchers withdraw()
+    {
+        const KwVouchers held = *this;
+        *this = KwVouchers{};
+        clear_in_flight = held.clear_in_flight;
+        return held;
+    }
+    void withdraw_bitmaps() { bitmaps = 0; bitmaps_of = nullptr; }      // compaction, insertion: the rows moved
+    void grant_bitmaps(const void *buf, size_t bytes, bool on_aux_stream)
+    {
+        bitmaps = bytes;
+        bitmaps_of = buf;
+        if (on_aux_stream) clear_in_flight = true;
+    }
+    void grant_counters(const void *counter, const void *alias_counts)
+    {
+        counters = true;
+        counters_of[0] = counter;
+        counters_of[1] = alias_counts;
+    }
+};
+
 }  // namespace
 
 struct orr_index {
@@ -163,9 +197,7 @@ struct orr_index {
     hipStream_t stream_aux = nullptr;  // what must not sit in front of the keyword chain: the clearing of the term bitmaps behind a
                                        // search (0.1 ms at 10M rows x 256 queries) and the norms of device-resident queries
     hipEvent_t ev_bm_clean = nullptr;  // ... recorded behind that clearing; the next search's posting expansion waits for it
-    bool bm_clean_pending = false;
-    bool kw_counters_clean = false;    // the hit counter and the per-term hit counts were zeroed behind the last search
-    const void *kw_counters_of[2] = {nullptr, nullptr};
+    KwVouchers kw_clean;               // what the last keyword chain on this lane left clean
     hipEvent_t ev_inputs = nullptr, ev_kw_done = nullptr, ev_main_ready = nullptr, ev_range[15] = {};     // (one per row range but the first: 16 ranges at most)
     std::mutex mu;
 
@@ -278,8 +310,6 @@ struct orr_index {
     DevBuf ws_q, ws_dot, ws_dotf, ws_sel, ws_cand, ws_qc, ws_rowc, ws_tau, ws_qsplit, ws_fcnt, ws_fbuf, ws_fqf, ws_fany, ws_tsL, ws_tskey, ws_qtiled, ws_fdot, ws_pbuf, ws_psel, ws_q8, ws_q8s1, ws_q8err, ws_zero, ws_norm_a;
     DevBuf ws_keys_a, ws_keys_b, ws_vals_a, ws_vals_b, ws_sort_tmp, ws_raw, ws_src_start, ws_qsub;
     DevBuf ws_vmatch, ws_bitmaps, ws_hits, ws_counter, ws_meta, ws_tickets, ws_kwalias;
-    size_t bitmaps_clean = 0;          // leading bytes of ws_bitmaps known to be zero (cleared again behind every search)
-    const void *bitmaps_clean_of = nullptr;
     PinnedBuf pin_meta, pin_q, pin_qc, pin_cand, pin_norm, pin_cnt, pin_kwcnt;
     hipEvent_t ev_q = nullptr;
 
@@ -1302,7 +1332,7 @@ static int ensure_token_bitmaps(orr_index *idx)
     if (const char *e = getenv("ORR_TOKEN_BITMAPS")) { if (atoi(e) == 0) return ORR_OK; }      // diagnostic: A/B against per-batch expansion
     const int64_t n = idx->n_rows, V = idx->n_tokens;
     if (n < 48 * (int64_t)orr::kSelSegRows || V <= 0 || idx->n_postings == 0) return ORR_OK;   // small shards expand in microseconds
-    const int64_t words = ((n + 31) / 32 + 3) / 4 * 4;
+    const int64_t words = keyword::words_per_term(n);
     std::vector<uint64_t> off((size_t)V + 1);
     HIP_TRY(hipMemcpy(off.data(), idx->d_post_off, sizeof(uint64_t) * ((size_t)V + 1), hipMemcpyDeviceToHost));
     std::vector<uint32_t> toks;
@@ -1828,7 +1858,7 @@ int orr_index_compact(orr_index *idx, int64_t *out_removed)
     idx->emb_shadow.release(); idx->shadow_ready = false; idx->shadow_failed = false;
     idx->emb_i8.release(); idx->i8_scale.release(); idx->i8_rel_err.release(); idx->i8_rel_hat.release(); idx->i8_rowf.release();
     idx->i8_ready = false; idx->i8_failed = false;
-    idx->bitmaps_clean = 0; idx->bitmaps_clean_of = nullptr;
+    idx->kw_clean.withdraw_bitmaps();
     idx->tok_bm.release(); idx->tok_bm_index.release(); idx->n_tok_bm = -1; idx->tok_bm_words = 0;
     idx->lanes.update_shared([](LanePool::Shared &sh) { sh.dead_count = 0; });
     for (orr_index *l : idx->lanes.drain()) orr_index_destroy(l);
@@ -2084,7 +2114,7 @@ int orr_index_insert_rows(orr_index *idx, int64_t n, int32_t dim, const float *e
     idx->id_index.clear();
     drop_scope_table(idx, scopes.reg);
     idx->n_vlong = -1; idx->n_vmid = 0;
-    idx->bitmaps_clean = 0; idx->bitmaps_clean_of = nullptr;
+    idx->kw_clean.withdraw_bitmaps();
     idx->tok_bm.release(); idx->tok_bm_index.release(); idx->n_tok_bm = -1; idx->tok_bm_words = 0;
     for (orr_index *l : idx->lanes.drain()) orr_index_destroy(l);      // they borrow arrays that were replaced; remade on demand
     // ---- a shadow that was ready is rebuilt now, from the moved rows, by the routine set_option("two_stage") uses: the next
@@ -2623,233 +2653,203 @@ struct KwSide {
     const uint8_t *alias = nullptr;               // per distinct term: its bitmap is a stored token bitmap (device; null without a token store)
 };
 
+// ORR_VOCAB_LOOKUP=0|1 forces the short tokens' form, ORR_VOCAB_MID=0 sends the tokens of 17..32 bytes through the wave-per-token
+// scan like the longer ones (A/B): read once, at the first chain; a call's own overrides (orr_index_keyword_bitmaps) go first
+struct KwEnv {
+    int lookup;        // -1 unset
+    bool mid_off;
+};
+static int env_switch(const char *v) { return v ? atoi(v) : -1; }
+static const KwEnv &kw_env()
+{
+    static const KwEnv e{env_switch(getenv("ORR_VOCAB_LOOKUP")), env_switch(getenv("ORR_VOCAB_MID")) == 0};
+    return e;
+}
+
+// One chain's working set: what the plan decided (orr_keyword_plan.h) and what a stage hands to the ones behind it.
+struct KwWork {
+    hipStream_t k = nullptr;
+    uint32_t n_terms_total = 0, TT = 0;
+    bool lookup = false;                          // the short tokens' form
+    keyword::MetaLayout lay{};
+    int64_t V = 0, VL = 0, n_mid = 0, words = 0;  // tokens, the long ones, of those one lane per token; words of a bitmap
+    keyword::HitList hits{0, false};
+    KwVouchers held;                              // what the last chain on this lane left clean
+    size_t bm_bytes = 0, bm_clean = 0;            // the batch's own bitmaps: bytes used, leading bytes that are zero already
+    bool counters_clean = false;
+    uint8_t *dm = nullptr;                        // the image on the device
+    const int64_t *term_word_off = nullptr;       // the alias stage's, where the shard stores token bitmaps
+    const uint8_t *skip = nullptr;
+};
+
+// 1. the distinct terms, the short tokens' form, the image in pinned memory
+static int kw_plan_and_fill(orr_index *idx, const BatchArgs &a, const std::vector<uint32_t> &qoff, KwWork &w)
+{
+    keyword::Distinct d;
+    const int64_t bad = keyword::distinct_terms(a.terms_utf8, a.term_off, qoff.data(), a.B, d);
+    if (bad >= 0) return fail(ORR_EINVAL, "term_off is not monotone at term %u", (uint32_t)bad);
+    w.TT = (uint32_t)d.terms.size();
+    w.lookup = keyword::short_form(w.TT, idx->n_tokens, idx->kw_force_form, kw_env().lookup);
+    idx->kw_form_ran = w.lookup ? 1 : 0;
+    w.lay = keyword::layout_of(w.TT, w.n_terms_total, a.B, d.pool_bytes, w.lookup);
+    ORR_TRY(idx->pin_meta.reserve(w.lay.meta_bytes));
+    ORR_TRY(idx->ws_meta.reserve(w.lay.meta_bytes));
+    keyword::fill_meta(idx->pin_meta.as<uint8_t>(), w.lay, d, w.lookup);
+    return ORR_OK;
+}
+
+// 2. the workspaces.  The term bitmaps must start out zero.  Every search clears what it used again when it is done (behind its
+// last kernel, while the host finishes the batch), so the next one only clears what lies beyond: the memset (270 MB at 1024
+// queries x 1M rows) leaves the critical path of the keyword chain.  The vouchers are withdrawn here -- until this chain's
+// caller has cleaned up after it -- and compared behind the reserve: the buffer may have moved.
+static int kw_reserve(orr_index *idx, KwWork &w)
+{
+    w.V = idx->n_tokens;
+    w.words = keyword::words_per_term(idx->n_rows);
+    w.hits = keyword::hit_list(w.V, w.TT, idx->kw_hits_cap);
+    ORR_TRY(ensure_vlong(idx));
+    ORR_TRY(ensure_token_bitmaps(idx));
+    w.VL = idx->n_vlong;
+    w.n_mid = keyword::mid_tokens(idx->n_vmid, w.VL, idx->kw_force_mid, kw_env().mid_off);
+    w.bm_bytes = sizeof(uint32_t) * (size_t)w.TT * (size_t)w.words;
+    ORR_TRY(idx->ws_vmatch.reserve(sizeof(uint16_t) * (size_t)w.TT * (size_t)std::max<int64_t>(w.VL, 1)));
+    ORR_TRY(idx->ws_bitmaps.reserve(w.bm_bytes));
+    w.held = idx->kw_clean.withdraw();
+    w.bm_clean = w.held.bitmaps_of == idx->ws_bitmaps.p ? w.held.bitmaps : 0;
+    ORR_TRY(idx->ws_hits.reserve(sizeof(orr::KwHit) * (size_t)w.hits.max_hits));
+    ORR_TRY(idx->ws_counter.reserve(sizeof(unsigned long long)));
+    ORR_TRY(idx->pin_kwcnt.reserve(sizeof(unsigned long long)));
+    // (the chain's counters were zeroed behind the last search on this stream, unless this is the first one or they moved)
+    w.counters_clean = w.held.counters && w.held.counters_of[0] == idx->ws_counter.p;
+    return ORR_OK;
+}
+
+// 3. the image goes up in one copy; the hit counter starts at zero, on the device and in pinned memory
+static int kw_upload(orr_index *idx, KwWork &w)
+{
+    *idx->pin_kwcnt.as<unsigned long long>() = 0ull;
+    w.dm = idx->ws_meta.as<uint8_t>();
+    HIP_TRY(hipMemcpyAsync(w.dm, idx->pin_meta.as<uint8_t>(), w.lay.meta_bytes, hipMemcpyHostToDevice, w.k));
+    if (!w.counters_clean) HIP_TRY(hipMemsetAsync(idx->ws_counter.p, 0, sizeof(unsigned long long), w.k));
+    return ORR_OK;
+}
+
+// 4. tokens of at most 16 bytes: one lane per token against every distinct term, hits reserved in place; where tokens x terms
+// is large the terms are looked up (sorted by first dword) instead of compared one by one
+static int kw_match_short(orr_index *idx, const KwWork &w)
+{
+    const orr::MatchTerm *terms = reinterpret_cast<const orr::MatchTerm *>(w.dm + w.lay.match);
+    Timed t(idx, "vocab_match", 0.0, w.k);
+    if (w.lookup) {
+        const uint32_t *lk = reinterpret_cast<const uint32_t *>(w.dm + w.lay.lk);
+        HIP_TRY(orr::launch_vocab_match_lookup(idx->d_vpool, idx->d_vstart, idx->d_vlen, w.V, terms, lk, lk + keyword::kLkHead,
+                                               lk + keyword::kLkHead + w.TT, reinterpret_cast<const uint32_t *>(w.dm + w.lay.bloom), idx->d_post_off,
+                                               idx->ws_counter.as<unsigned long long>(), idx->ws_hits.as<orr::KwHit>(), w.hits.max_hits, w.k));
+    } else {
+        HIP_TRY(orr::launch_vocab_match_short(idx->d_vpool, idx->d_vstart, idx->d_vlen, w.V, terms, (int32_t)w.TT, idx->d_post_off,
+                                              idx->ws_counter.as<unsigned long long>(), idx->ws_hits.as<orr::KwHit>(), w.hits.max_hits, w.k));
+    }
+    return ORR_OK;
+}
+
+// 5. the longer tokens: those of 17..32 bytes (the front of their list) one lane per token as well; for the rest every distinct
+// term is its own 1-term "query" of the wave-per-token scan
+static int kw_match_long(orr_index *idx, const KwWork &w)
+{
+    const int32_t TT = (int32_t)w.TT;
+    const int64_t n_mid = w.n_mid, VS = w.VL - n_mid;
+    if (n_mid > 0) {
+        Timed t(idx, "vocab_match_mid", 0.0, w.k);
+        HIP_TRY(orr::launch_vocab_match_mid(idx->d_vpool, idx->vlong_start.as<uint64_t>(), idx->vlong_len.as<uint32_t>(),
+                                            idx->vlong_id.as<uint32_t>(), n_mid, reinterpret_cast<const orr::MatchTerm8 *>(w.dm + w.lay.match8),
+                                            TT, idx->d_post_off, idx->ws_counter.as<unsigned long long>(),
+                                            idx->ws_hits.as<orr::KwHit>(), w.hits.max_hits, w.k));
+    }
+    if (VS <= 0) return ORR_OK;
+    {
+        Timed t(idx, "vocab_scan", 0.0, w.k);
+        HIP_TRY(orr::launch_vocab_scan(idx->d_vpool, idx->vlong_start.as<uint64_t>() + n_mid, idx->vlong_len.as<uint32_t>() + n_mid, VS,
+                                       w.dm + w.lay.pool, reinterpret_cast<const orr::ScanTerm *>(w.dm + w.lay.terms), TT,
+                                       reinterpret_cast<const uint32_t *>(w.dm + w.lay.iota), idx->ws_vmatch.as<uint16_t>(), w.k));
+    }
+    Timed t(idx, "vocab_hits", 0.0, w.k);
+    HIP_TRY(orr::launch_vocab_hits(idx->ws_vmatch.as<uint16_t>(), VS, TT, idx->vlong_id.as<uint32_t>() + n_mid, idx->d_post_off,
+                                   idx->ws_counter.as<unsigned long long>(), idx->ws_hits.as<orr::KwHit>(), w.hits.max_hits, w.k));
+    return ORR_OK;
+}
+
+// 6. terms whose only hit is a token with a stored bitmap use that bitmap as it is (no expansion, nothing copied)
+static int kw_alias(orr_index *idx, KwWork &w)
+{
+    if (!(idx->n_tok_bm > 0 && idx->tok_bm_words == w.words)) return ORR_OK;
+    const size_t TT = w.TT;
+    const size_t o_tok = sizeof(uint32_t) * TT, o_off = (2 * o_tok + 7) / 8 * 8, o_alias = o_off + sizeof(int64_t) * TT;
+    ORR_TRY(idx->ws_kwalias.reserve(o_alias + TT + 16));
+    uint8_t *wa = idx->ws_kwalias.as<uint8_t>();
+    if (!(w.counters_clean && w.held.counters_of[1] == idx->ws_kwalias.p))
+        HIP_TRY(hipMemsetAsync(wa, 0, o_tok, w.k));              // the hit counts
+    const int64_t delta = (int64_t)(idx->tok_bm.as<uint32_t>() - idx->ws_bitmaps.as<uint32_t>());   // words from the batch's bitmaps to the token store
+    Timed t(idx, "kw_alias", 0.0, w.k);
+    HIP_TRY(orr::launch_kw_alias(idx->ws_hits.as<orr::KwHit>(), idx->ws_counter.as<unsigned long long>(), w.hits.max_hits, (int32_t)TT,
+                                 idx->tok_bm_index.as<int32_t>(), delta, w.words, reinterpret_cast<uint32_t *>(wa),
+                                 reinterpret_cast<uint32_t *>(wa + o_tok), reinterpret_cast<int64_t *>(wa + o_off), wa + o_alias, w.k));
+    w.term_word_off = reinterpret_cast<const int64_t *>(wa + o_off);
+    w.skip = wa + o_alias;
+    return ORR_OK;
+}
+
+// 7. the bitmaps are first written behind this: the clearing behind the last search (on the auxiliary stream) must be done,
+// and what lies beyond the cleared part is cleared now.  (A corpus without tokens: nothing is expanded, the bitmaps are read
+// all the same.)
+static int kw_settle_bitmaps(orr_index *idx, const KwWork &w)
+{
+    if (idx->kw_clean.clear_in_flight) {
+        HIP_TRY(hipStreamWaitEvent(w.k, idx->ev_bm_clean, 0));
+        idx->kw_clean.clear_in_flight = false;
+    }
+    if (w.bm_clean < w.bm_bytes)
+        HIP_TRY(hipMemsetAsync(static_cast<uint8_t *>(idx->ws_bitmaps.p) + w.bm_clean, 0, w.bm_bytes - w.bm_clean, w.k));
+    return ORR_OK;
+}
+
+// 8. the hits' posting lists OR-ed into the bitmaps; the hit count goes to pinned memory (statistics, and the check of the list)
+static int kw_expand(orr_index *idx, const KwWork &w)
+{
+    Timed t(idx, "expand_hits", 0.0, w.k);
+    HIP_TRY(orr::launch_expand_hits(idx->ws_hits.as<orr::KwHit>(), idx->ws_counter.as<unsigned long long>(), w.hits.max_hits,
+                                    idx->d_post_rows, idx->ws_bitmaps.as<uint32_t>(), w.words, w.k,
+                                    idx->pin_kwcnt.as<unsigned long long>(), w.skip));
+    return ORR_OK;
+}
+
 int launch_keyword_side(orr_index *idx, const BatchArgs &a, const std::vector<uint32_t> &qoff, KwSide &out)
 {
-    const int32_t B = a.B;
-    const uint32_t t_begin = qoff[0], n_terms_total = qoff[(size_t)B] - qoff[0];
-    if (n_terms_total == 0) return ORR_OK;
-    {
-
-        // distinct terms of the batch: open addressing on an FNV-1a hash of the bytes (a batch of 1024 queries has
-        // ~3000 terms; the node-based map this replaces cost as much as the GPU side of a small batch)
-        std::vector<std::string_view> dterms;
-        dterms.reserve(n_terms_total);
-        uint32_t table_size = 16;
-        while (table_size < 2 * n_terms_total + 2) table_size <<= 1;
-        std::vector<uint32_t> table(table_size, 0xFFFFFFFFu);
-        std::vector<uint32_t> qmeta((size_t)n_terms_total + (size_t)B + 1);   // [term -> distinct idx][query offsets]
-        for (uint32_t t = 0; t < n_terms_total; ++t) {
-            const uint32_t o = a.term_off[t_begin + t], e = a.term_off[t_begin + t + 1];
-            if (e < o) return fail(ORR_EINVAL, "term_off is not monotone at term %u", t_begin + t);
-            std::string_view sv(reinterpret_cast<const char *>(a.terms_utf8) + o, e - o);
-            uint64_t h = 1469598103934665603ull;
-            for (unsigned char ch : sv) h = (h ^ ch) * 1099511628211ull;
-            uint32_t slot = (uint32_t)(h ^ (h >> 32)) & (table_size - 1);
-            while (table[slot] != 0xFFFFFFFFu && dterms[table[slot]] != sv) slot = (slot + 1) & (table_size - 1);
-            if (table[slot] == 0xFFFFFFFFu) {
-                table[slot] = (uint32_t)dterms.size();
-                dterms.push_back(sv);
-            }
-            qmeta[t] = table[slot];
-        }
-        for (int32_t b = 0; b <= B; ++b) qmeta[n_terms_total + b] = qoff[b] - t_begin;
-        const uint32_t TT = (uint32_t)dterms.size();
-        size_t pool_bytes = 0;
-        for (auto &d : dterms) pool_bytes += d.size();
-        // one pinned block, one upload: [ScanTerm x TT][qmeta][iota 0..64][term bytes]
-        const size_t off_terms = 0;
-        const size_t off_qmeta = off_terms + sizeof(orr::ScanTerm) * TT;
-        const size_t off_iota = off_qmeta + sizeof(uint32_t) * qmeta.size();
-        const size_t off_match = off_iota + sizeof(uint32_t) * 65;
-        const size_t off_match8 = off_match + sizeof(orr::MatchTerm) * TT;
-        const size_t off_lk = off_match8 + sizeof(orr::MatchTerm8) * TT;       // [8 u32 class boundaries][TT keys][TT term numbers]
-        const size_t off_pool = off_lk + sizeof(uint32_t) * (8 + 2 * (size_t)TT);
-        const size_t off_bloom = (off_pool + pool_bytes + 16 + 15) / 16 * 16;   // (last: only uploaded when the lookup form runs)
-        // (the lookup pays from tens of millions of (token, term) pairs on: below, sorting the terms on the host -- 0.15 ms for the
-        // 3,000 terms of 1024 queries -- costs more than comparing them all on the GPU)
-        const bool vocab_lookup = [&] { static const int e = [] { const char *v = getenv("ORR_VOCAB_LOOKUP"); return v ? atoi(v) : -1; }();
-                                        if (idx->kw_force_form >= 0) return idx->kw_force_form != 0;      // orr_index_keyword_bitmaps
-                                        return e >= 0 ? e != 0 : (TT >= 64 && (int64_t)TT * idx->n_tokens >= ((int64_t)1 << 25)); }();
-        idx->kw_form_ran = vocab_lookup ? 1 : 0;
-        const size_t meta_bytes = vocab_lookup ? off_bloom + orr::kVocabBloomBits / 8 : off_pool + pool_bytes + 16;
-        ORR_TRY(idx->pin_meta.reserve(meta_bytes));
-        ORR_TRY(idx->ws_meta.reserve(meta_bytes));
-        uint8_t *hm = idx->pin_meta.as<uint8_t>();
-        orr::ScanTerm *st = reinterpret_cast<orr::ScanTerm *>(hm + off_terms);
-        uint32_t cursor = 0;
-        for (uint32_t t = 0; t < TT; ++t) {
-            st[t].off = cursor;
-            st[t].len = (uint32_t)dterms[t].size();
-            uint32_t pre = 0, msk = 0;
-            for (uint32_t k = 0; k < 4 && k < st[t].len; ++k) {
-                pre |= (uint32_t)(uint8_t)dterms[t][k] << (8 * k);
-                msk |= 0xFFu << (8 * k);
-            }
-            st[t].prefix = pre;
-            st[t].mask = msk;
-            orr::MatchTerm &mt = reinterpret_cast<orr::MatchTerm *>(hm + off_match)[t];
-            memset(&mt, 0, sizeof(mt));
-            mt.len = st[t].len;
-            for (uint32_t k = 0; k < 16 && k < st[t].len; ++k) {
-                mt.w[k >> 2] |= (uint32_t)(uint8_t)dterms[t][k] << (8 * (k & 3));
-                mt.m[k >> 2] |= 0xFFu << (8 * (k & 3));
-            }
-            orr::MatchTerm8 &m8 = reinterpret_cast<orr::MatchTerm8 *>(hm + off_match8)[t];
-            memset(&m8, 0, sizeof(m8));
-            m8.len = st[t].len;
-            for (uint32_t k = 0; k < 32 && k < st[t].len; ++k) {
-                m8.w[k >> 2] |= (uint32_t)(uint8_t)dterms[t][k] << (8 * (k & 3));
-                m8.m[k >> 2] |= 0xFFu << (8 * (k & 3));
-            }
-            memcpy(hm + off_pool + cursor, dterms[t].data(), dterms[t].size());
-            cursor += st[t].len;
-        }
-        if (vocab_lookup) {   // the terms of at most 16 bytes sorted by (class = min(bytes, 4), length-masked first dword): vocab_match_lookup
-            uint32_t *lk = reinterpret_cast<uint32_t *>(hm + off_lk), *keys = lk + 8, *tix = keys + TT;
-            const orr::MatchTerm *mts = reinterpret_cast<const orr::MatchTerm *>(hm + off_match);
-            std::vector<std::pair<uint64_t, uint32_t>> order;
-            order.reserve(TT);
-            for (uint32_t t = 0; t < TT; ++t)
-                if (st[t].len >= 1 && st[t].len <= 16)
-                    order.emplace_back(((uint64_t)(std::min<uint32_t>(st[t].len, 4u) - 1u) << 32) | mts[t].w[0], t);
-            std::sort(order.begin(), order.end());
-            for (int c = 0; c <= 4; ++c) lk[c] = 0;
-            for (size_t i = 0; i < order.size(); ++i) {
-                keys[i] = (uint32_t)order[i].first;
-                tix[i] = order[i].second;
-                lk[(order[i].first >> 32) + 1] = (uint32_t)i + 1;
-            }
-            for (int c = 1; c <= 4; ++c) lk[c] = std::max(lk[c], lk[c - 1]);     // empty classes inherit the boundary in front of them
-            lk[5] = lk[6] = lk[7] = 0;
-            uint32_t *bloom = reinterpret_cast<uint32_t *>(hm + off_bloom);
-            memset(bloom, 0, orr::kVocabBloomBits / 8);
-            for (const auto &o : order) {
-                const uint32_t hb = orr::vocab_bloom_hash((uint32_t)o.first, (uint32_t)(o.first >> 32));
-                bloom[hb >> 5] |= 1u << (hb & 31u);
-            }
-        }
-        memcpy(hm + off_qmeta, qmeta.data(), sizeof(uint32_t) * qmeta.size());
-        uint32_t *iota = reinterpret_cast<uint32_t *>(hm + off_iota);
-        for (uint32_t i = 0; i < 65; ++i) iota[i] = i;
-
-        const int64_t V = idx->n_tokens;
-        const int64_t words = ((idx->n_rows + 31) / 32 + 3) / 4 * 4;       // 16-byte aligned bitmaps
-        const uint64_t want_hits = (uint64_t)std::max<int64_t>(V, 1) * TT;
-        const uint32_t max_hits = (uint32_t)std::min<uint64_t>(want_hits, idx->kw_hits_cap);
-        ORR_TRY(ensure_vlong(idx));
-        ORR_TRY(ensure_token_bitmaps(idx));
-        const int64_t VL = idx->n_vlong;
-        ORR_TRY(idx->ws_vmatch.reserve(sizeof(uint16_t) * (size_t)TT * (size_t)std::max<int64_t>(VL, 1)));
-        ORR_TRY(idx->ws_bitmaps.reserve(sizeof(uint32_t) * (size_t)TT * (size_t)words));
-        // The term bitmaps must start out zero.  Every search clears what it used again when it is done (on this side
-        // stream, behind its last kernel, while the host finishes the batch), so the next one only clears what lies
-        // beyond: the memset (270 MB at 1024 queries x 1M rows) leaves the critical path of the keyword chain.
-        out.bm_bytes = sizeof(uint32_t) * (size_t)TT * (size_t)words;
-        size_t bm_clean = idx->bitmaps_clean_of == idx->ws_bitmaps.p ? idx->bitmaps_clean : 0;
-        idx->bitmaps_clean = 0;                        // until this search has cleaned up after itself
-        idx->bitmaps_clean_of = idx->ws_bitmaps.p;
-        out.bm_clean_before = bm_clean;
-        ORR_TRY(idx->ws_hits.reserve(sizeof(orr::KwHit) * (size_t)max_hits));
-        ORR_TRY(idx->ws_counter.reserve(sizeof(unsigned long long)));
-        ORR_TRY(idx->pin_kwcnt.reserve(sizeof(unsigned long long)));
-        *idx->pin_kwcnt.as<unsigned long long>() = 0ull;
-        hipStream_t k = idx->stream_kw;
-        uint8_t *dm = idx->ws_meta.as<uint8_t>();
-        HIP_TRY(hipMemcpyAsync(dm, hm, meta_bytes, hipMemcpyHostToDevice, k));
-        // (the chain's counters were zeroed behind the last search on this stream, unless this is the first one or they moved)
-        const bool counters_clean = idx->kw_counters_clean && idx->kw_counters_of[0] == idx->ws_counter.p;
-        idx->kw_counters_clean = false;
-        if (!counters_clean) HIP_TRY(hipMemsetAsync(idx->ws_counter.p, 0, sizeof(unsigned long long), k));
-        bool bitmaps_settled = false;
-        auto settle_bitmaps = [&]() -> int {
-            if (bitmaps_settled) return ORR_OK;
-            bitmaps_settled = true;
-            if (idx->bm_clean_pending) {
-                HIP_TRY(hipStreamWaitEvent(k, idx->ev_bm_clean, 0));
-                idx->bm_clean_pending = false;
-            }
-            if (bm_clean < out.bm_bytes)
-                HIP_TRY(hipMemsetAsync(static_cast<uint8_t *>(idx->ws_bitmaps.p) + bm_clean, 0, out.bm_bytes - bm_clean, k));
-            return ORR_OK;
-        };
-        if (V > 0) {
-            const orr::ScanTerm *d_terms = reinterpret_cast<const orr::ScanTerm *>(dm + off_terms);
-            {   // tokens of at most 16 bytes: one lane per token against every distinct term, hits reserved in place; where tokens x terms
-                // is large the terms are looked up (sorted by first dword) instead of compared one by one (ORR_VOCAB_LOOKUP=0|1 forces either)
-                Timed t(idx, "vocab_match", 0.0, k);
-                if (vocab_lookup) {
-                    const uint32_t *lk = reinterpret_cast<const uint32_t *>(dm + off_lk);
-                    HIP_TRY(orr::launch_vocab_match_lookup(idx->d_vpool, idx->d_vstart, idx->d_vlen, V,
-                                                           reinterpret_cast<const orr::MatchTerm *>(dm + off_match), lk, lk + 8, lk + 8 + TT,
-                                                           reinterpret_cast<const uint32_t *>(dm + off_bloom), idx->d_post_off,
-                                                           idx->ws_counter.as<unsigned long long>(), idx->ws_hits.as<orr::KwHit>(), max_hits, k));
-                } else {
-                    HIP_TRY(orr::launch_vocab_match_short(idx->d_vpool, idx->d_vstart, idx->d_vlen, V,
-                                                          reinterpret_cast<const orr::MatchTerm *>(dm + off_match), (int32_t)TT, idx->d_post_off,
-                                                          idx->ws_counter.as<unsigned long long>(), idx->ws_hits.as<orr::KwHit>(), max_hits, k));
-                }
-            }
-            // tokens of 17..32 bytes (the front of the list of longer tokens): one lane per token as well (ORR_VOCAB_MID=0: through
-            // the wave-per-token scan like the longer ones, A/B)
-            static const bool mid_off = [] { const char *e = getenv("ORR_VOCAB_MID"); return e && atoi(e) == 0; }();
-            const int64_t n_mid = (idx->kw_force_mid >= 0 ? idx->kw_force_mid == 0 : mid_off) ? 0 : std::min<int64_t>(idx->n_vmid, VL);
-            if (n_mid > 0) {
-                Timed t(idx, "vocab_match_mid", 0.0, k);
-                HIP_TRY(orr::launch_vocab_match_mid(idx->d_vpool, idx->vlong_start.as<uint64_t>(), idx->vlong_len.as<uint32_t>(),
-                                                    idx->vlong_id.as<uint32_t>(), n_mid, reinterpret_cast<const orr::MatchTerm8 *>(dm + off_match8),
-                                                    (int32_t)TT, idx->d_post_off, idx->ws_counter.as<unsigned long long>(),
-                                                    idx->ws_hits.as<orr::KwHit>(), max_hits, k));
-            }
-            if (VL - n_mid > 0) {   // the rest: every distinct term is its own 1-term "query" of the wave-per-token scan
-                const int64_t VS = VL - n_mid;
-                {
-                    Timed t(idx, "vocab_scan", 0.0, k);
-                    HIP_TRY(orr::launch_vocab_scan(idx->d_vpool, idx->vlong_start.as<uint64_t>() + n_mid, idx->vlong_len.as<uint32_t>() + n_mid, VS,
-                                                   dm + off_pool, d_terms, (int32_t)TT, reinterpret_cast<const uint32_t *>(dm + off_iota),
-                                                   idx->ws_vmatch.as<uint16_t>(), k));
-                }
-                {
-                    Timed t(idx, "vocab_hits", 0.0, k);
-                    HIP_TRY(orr::launch_vocab_hits(idx->ws_vmatch.as<uint16_t>(), VS, (int32_t)TT, idx->vlong_id.as<uint32_t>() + n_mid, idx->d_post_off,
-                                                   idx->ws_counter.as<unsigned long long>(), idx->ws_hits.as<orr::KwHit>(), max_hits, k));
-                }
-            }
-            // terms whose only hit is a token with a stored bitmap use that bitmap as it is (no expansion, nothing copied)
-            const uint8_t *skip = nullptr;
-            if (idx->n_tok_bm > 0 && idx->tok_bm_words == words) {
-                const size_t o_tok = sizeof(uint32_t) * (size_t)TT, o_off = (2 * o_tok + 7) / 8 * 8, o_alias = o_off + sizeof(int64_t) * (size_t)TT;
-                ORR_TRY(idx->ws_kwalias.reserve(o_alias + (size_t)TT + 16));
-                uint8_t *wa = idx->ws_kwalias.as<uint8_t>();
-                if (!(counters_clean && idx->kw_counters_of[1] == idx->ws_kwalias.p))
-                    HIP_TRY(hipMemsetAsync(wa, 0, o_tok, k));              // the hit counts
-                const int64_t delta = (int64_t)(idx->tok_bm.as<uint32_t>() - idx->ws_bitmaps.as<uint32_t>());   // words from the batch's bitmaps to the token store
-                Timed t(idx, "kw_alias", 0.0, k);
-                HIP_TRY(orr::launch_kw_alias(idx->ws_hits.as<orr::KwHit>(), idx->ws_counter.as<unsigned long long>(), max_hits, (int32_t)TT,
-                                             idx->tok_bm_index.as<int32_t>(), delta, words, reinterpret_cast<uint32_t *>(wa),
-                                             reinterpret_cast<uint32_t *>(wa + o_tok), reinterpret_cast<int64_t *>(wa + o_off), wa + o_alias, k));
-                out.view.term_word_off = reinterpret_cast<const int64_t *>(wa + o_off);
-                skip = wa + o_alias;
-                out.alias = skip;
-            }
-            // the bitmaps are first written here: the clearing behind the last search (on the auxiliary stream) must be done,
-            // and what lies beyond the cleared part is cleared now
-            ORR_TRY(settle_bitmaps());
-            {
-                Timed t(idx, "expand_hits", 0.0, k);
-                HIP_TRY(orr::launch_expand_hits(idx->ws_hits.as<orr::KwHit>(), idx->ws_counter.as<unsigned long long>(), max_hits,
-                                                idx->d_post_rows, idx->ws_bitmaps.as<uint32_t>(), words, k,
-                                                idx->pin_kwcnt.as<unsigned long long>(), skip));     // hits of this pass: statistics
-            }
-        }
-        ORR_TRY(settle_bitmaps());                     // (a corpus without tokens: nothing expanded, the bitmaps are read all the same)
-        HIP_TRY(hipEventRecord(idx->ev_kw_done, k));
-        out.view.bitmaps = idx->ws_bitmaps.as<uint32_t>();
-        out.view.words_per_term = words;
-        out.view.q_term_idx = reinterpret_cast<const uint32_t *>(dm + off_qmeta);
-        out.view.q_term_off = out.view.q_term_idx + n_terms_total;
-        out.overflow_possible = want_hits > (uint64_t)max_hits;
-        out.max_hits = max_hits;
+    KwWork w;
+    w.k = idx->stream_kw;
+    w.n_terms_total = qoff[(size_t)a.B] - qoff[0];
+    if (w.n_terms_total == 0) return ORR_OK;
+    ORR_TRY(kw_plan_and_fill(idx, a, qoff, w));
+    ORR_TRY(kw_reserve(idx, w));
+    out.bm_bytes = w.bm_bytes;
+    out.bm_clean_before = w.bm_clean;
+    ORR_TRY(kw_upload(idx, w));
+    if (w.V > 0) {
+        ORR_TRY(kw_match_short(idx, w));
+        ORR_TRY(kw_match_long(idx, w));
+        ORR_TRY(kw_alias(idx, w));
     }
+    ORR_TRY(kw_settle_bitmaps(idx, w));
+    if (w.V > 0) ORR_TRY(kw_expand(idx, w));
+    // 9. the main stream joins behind this event
+    HIP_TRY(hipEventRecord(idx->ev_kw_done, w.k));
+    out.view.bitmaps = idx->ws_bitmaps.as<uint32_t>();
+    out.view.words_per_term = w.words;
+    out.view.q_term_idx = reinterpret_cast<const uint32_t *>(w.dm + w.lay.qmeta);
+    out.view.q_term_off = out.view.q_term_idx + w.n_terms_total;
+    out.view.term_word_off = w.term_word_off;
+    out.alias = w.skip;
+    out.overflow_possible = w.hits.overflow_possible;
+    out.max_hits = w.hits.max_hits;
     return ORR_OK;
 }
 
@@ -3798,23 +3798,43 @@ int launch_selection(orr_index *idx, const BatchArgs &a, const PassPlan &p, int3
 int clean_keyword_side(orr_index *idx, const KwSide &kws, uint32_t n_terms_total)
 {
     if (kws.bm_bytes) {        // every kernel that read the bitmaps is done: clear them for the next search
-        if (kws.bm_bytes >= ((size_t)16 << 20)) {   // (small ones stay on the keyword stream: a cross-stream wait costs a one-query call more)
+        const bool on_aux = kws.bm_bytes >= ((size_t)16 << 20);   // (small ones stay on the keyword stream: a cross-stream wait costs a one-query call more)
+        if (on_aux) {
             HIP_TRY(hipMemsetAsync(idx->ws_bitmaps.p, 0, kws.bm_bytes, idx->stream_aux));
             HIP_TRY(hipEventRecord(idx->ev_bm_clean, idx->stream_aux));
-            idx->bm_clean_pending = true;
         } else {
             HIP_TRY(hipMemsetAsync(idx->ws_bitmaps.p, 0, kws.bm_bytes, idx->stream_kw));
         }
-        idx->bitmaps_clean = std::max(kws.bm_bytes, kws.bm_clean_before);
+        idx->kw_clean.grant_bitmaps(idx->ws_bitmaps.p, std::max(kws.bm_bytes, kws.bm_clean_before), on_aux);
     }
     if (n_terms_total > 0 && idx->ws_counter.p) {   // ... and the keyword chain's counters (two memsets less in front of the next chain)
         HIP_TRY(hipMemsetAsync(idx->ws_counter.p, 0, sizeof(unsigned long long), idx->stream_kw));
         if (idx->ws_kwalias.p) HIP_TRY(hipMemsetAsync(idx->ws_kwalias.p, 0, idx->ws_kwalias.cap, idx->stream_kw));
-        idx->kw_counters_clean = true;
-        idx->kw_counters_of[0] = idx->ws_counter.p;
-        idx->kw_counters_of[1] = idx->ws_kwalias.p;
+        idx->kw_clean.grant_counters(idx->ws_counter.p, idx->ws_kwalias.p);
     }
     return ORR_OK;
+}
+
+// The one rule for a hit list that may have been too short (keyword::after_run), behind the caller's synchronise: the count as
+// expand_hits left it in pinned memory (the device copy is zeroed again behind the chain).  More hits than the list holds -- short
+// terms against a large vocabulary -- and the bitmaps are incomplete: what was made of them is discarded, the lane keeps a list
+// grown to the measured count and the chain runs again (kRetryPass); the callers' loops end after kMaxRuns runs.  fn: the entry point's
+// name in front of the message, null for a search.
+int check_hit_list(orr_index *idx, const KwSide &kws, const char *fn)
+{
+    if (!kws.overflow_possible) return ORR_OK;
+    const uint32_t hits = (uint32_t)(*idx->pin_kwcnt.as<unsigned long long>() >> 32);
+    const keyword::AfterRun r = keyword::after_run(hits, kws.max_hits);
+    if (r.kind == keyword::AfterRun::Stands) return ORR_OK;
+    if (r.kind == keyword::AfterRun::Refused)
+        return fn ? fail(ORR_ENOMEM, "%s: the terms matched %u vocabulary tokens: a hit list of that size is refused (8 GiB)", fn, hits)
+                  : fail(ORR_ENOMEM, "keyword terms matched %u vocabulary tokens: a hit list of that size is refused (8 GiB)", hits);
+    idx->kw_hits_cap = r.new_cap;
+    return kRetryPass;
+}
+int hit_list_kept_overflowing(const char *fn)
+{
+    return fn ? fail(ORR_EDEVICE, "%s: the keyword hit list kept overflowing", fn) : fail(ORR_EDEVICE, "the keyword hit list kept overflowing");
 }
 
 // Stage 9: wait for the pass; clear the keyword side's bitmaps and counters for the next search; statistics.  kRetryPass:
@@ -3839,21 +3859,7 @@ int finish_pass(orr_index *idx, const BatchArgs &a, const PassPlan &p, const KwS
     }
     g_ht.mark(4);
     collect_events(idx);
-    if (kws.overflow_possible) {
-        // (the counter as expand_hits left it in pinned memory: the device copy is zeroed again behind the pass)
-        const unsigned long long cnt = *idx->pin_kwcnt.as<unsigned long long>();
-        const uint32_t hits = (uint32_t)(cnt >> 32);
-        if (hits > kws.max_hits) {
-            // the distinct terms of this batch match more vocabulary tokens than the hit list holds (short terms against a
-            // large vocabulary): the bitmaps are incomplete, so this pass's records are discarded; the list grows to the
-            // measured count and the pass runs again (the index keeps the larger list)
-            if ((uint64_t)hits * sizeof(orr::KwHit) > ((uint64_t)8 << 30))
-                return fail(ORR_ENOMEM, "keyword terms matched %u vocabulary tokens: a hit list of that size is refused (8 GiB)", hits);
-            idx->kw_hits_cap = hits + hits / 4 + 1024u;
-            return kRetryPass;
-        }
-    }
-    return ORR_OK;
+    return check_hit_list(idx, kws, nullptr);
 }
 
 // Device side of one batch: exact dots, keyword bitmaps, fused scores, selection.
@@ -3933,7 +3939,7 @@ int retry_pass(orr_index *idx, Pass &&once)
         const int r = once();
         if (r != kRetryPass) return r;
         idx->sstats.passes += 1;
-        if (attempt >= 3) return fail(ORR_EDEVICE, "the keyword hit list kept overflowing");
+        if (attempt + 1 >= keyword::kMaxRuns) return hit_list_kept_overflowing(nullptr);
     }
 }
 
@@ -5895,8 +5901,8 @@ int orr_scope_create_ticks(orr_index *idx, int64_t ticks_from, int64_t ticks_to,
 //   1. the keyword chain of a search for ONE query that owns every term (launch_keyword_side, as it is): a row bitmap per
 //      DISTINCT term, its own or -- where the term's only hit is a token with a stored bitmap -- an alias into the token store;
 //   2. scope_terms_combine behind it on the keyword stream: the bitmaps folded into the scope's, every word written;
-//   3. the hit list checked as finish_pass checks it: too short, and the bitmaps are incomplete -- the list grows by the
-//      search's rule and the chain runs again, a scope is never made of a truncated list;
+//   3. the hit list checked as finish_pass checks it (check_hit_list): too short, and the bitmaps are incomplete -- the list
+//      grows and the chain runs again, a scope is never made of a truncated list;
 //   4. the lane left as a search leaves it (clean_keyword_side), whether the chain stands or runs again;
 //   5. the deleted rows cleared on the scope's own stream, behind an event: posting lists keep deleted positions until compaction.
 // The search statistics do not move (this is no search); the kernel statistics record the launches.
@@ -5937,19 +5943,11 @@ static int scope_fill_terms_run(orr_index *lane, orr_scope *sc, int32_t n_terms,
         }
         HIP_TRY(hipEventRecord(lane->ev_kw_done, k));
         HIP_TRY(hipStreamSynchronize(k));              // the bitmaps are read: they may be cleared; the hit count is in pinned memory
-        bool truncated = false;
-        if (kws.overflow_possible) {
-            const uint32_t hits = (uint32_t)(*lane->pin_kwcnt.as<unsigned long long>() >> 32);
-            if (hits > kws.max_hits) {
-                if ((uint64_t)hits * sizeof(orr::KwHit) > ((uint64_t)8 << 30))
-                    return fail(ORR_ENOMEM, "orr_scope_create_terms: the terms matched %u vocabulary tokens: a hit list of that size is refused (8 GiB)", hits);
-                lane->kw_hits_cap = hits + hits / 4 + 1024u;
-                truncated = true;
-            }
-        }
+        const int verdict = check_hit_list(lane, kws, "orr_scope_create_terms");
+        if (verdict != ORR_OK && verdict != kRetryPass) return verdict;
         ORR_TRY(clean_keyword_side(lane, kws, (uint32_t)n_terms));
-        if (truncated) {
-            if (attempt >= 3) return fail(ORR_EDEVICE, "orr_scope_create_terms: the keyword hit list kept overflowing");
+        if (verdict == kRetryPass) {
+            if (attempt + 1 >= keyword::kMaxRuns) return hit_list_kept_overflowing("orr_scope_create_terms");
             continue;
         }
         if (h_base) {                  // what the fold read from STORED token bitmaps (aliased terms: nothing was expanded for them)
@@ -6016,14 +6014,9 @@ static int keyword_bitmaps_run(orr_index *lane, int32_t n_terms, const uint8_t *
         }
         HIP_TRY(hipStreamSynchronize(k));              // the chain is done; the hit count is in pinned memory
         const uint32_t hits = (uint32_t)(*lane->pin_kwcnt.as<unsigned long long>() >> 32);
-        bool truncated = false;
-        if (kws.overflow_possible && hits > kws.max_hits) {
-            if ((uint64_t)hits * sizeof(orr::KwHit) > ((uint64_t)8 << 30))
-                return fail(ORR_ENOMEM, "orr_index_keyword_bitmaps: the terms matched %u vocabulary tokens: a hit list of that size is refused (8 GiB)", hits);
-            lane->kw_hits_cap = hits + hits / 4 + 1024u;
-            truncated = true;
-        }
-        if (!truncated) {      // raw bits, an aliased term's from the token store (term_word_off counts words from the batch's bitmaps)
+        const int verdict = check_hit_list(lane, kws, "orr_index_keyword_bitmaps");
+        if (verdict != ORR_OK && verdict != kRetryPass) return verdict;
+        if (verdict == ORR_OK) {      // raw bits, an aliased term's from the token store (term_word_off counts words from the batch's bitmaps)
             HIP_TRY(hipMemcpyAsync(out_bitmaps, kws.view.bitmaps, kws.bm_bytes, hipMemcpyDeviceToHost, k));
             for (int32_t t = 0; has_store && t < n_terms; ++t)
                 if (h_off[(size_t)t] != (int64_t)t * words)
@@ -6032,8 +6025,8 @@ static int keyword_bitmaps_run(orr_index *lane, int32_t n_terms, const uint8_t *
             HIP_TRY(hipStreamSynchronize(k));
         }
         ORR_TRY(clean_keyword_side(lane, kws, (uint32_t)n_terms));
-        if (truncated) {
-            if (attempt >= 3) return fail(ORR_EDEVICE, "orr_index_keyword_bitmaps: the keyword hit list kept overflowing");
+        if (verdict == kRetryPass) {
+            if (attempt + 1 >= keyword::kMaxRuns) return hit_list_kept_overflowing("orr_index_keyword_bitmaps");
             continue;
         }
         if (out_alias) memcpy(out_alias, h_alias.data(), (size_t)n_terms);
@@ -6069,7 +6062,7 @@ int orr_index_keyword_bitmaps(orr_index *idx, int32_t n_terms, const uint8_t *te
     orr_index *lane = ln.lane;
     std::lock_guard<std::mutex> lock(lane->mu);
     if (!lane->sealed) return fail(ORR_ESTATE, "%s: the index is not sealed", fn);
-    const int64_t words = ((lane->n_rows + 31) / 32 + 3) / 4 * 4;           // launch_keyword_side's words_per_term
+    const int64_t words = keyword::words_per_term(lane->n_rows);
     if (out_words_per_term != words) return fail(ORR_EINVAL, "%s: a term bitmap of this shard has %lld words, not %lld", fn, (long long)words, (long long)out_words_per_term);
     if ((uint64_t)n_terms * (uint64_t)words * sizeof(uint32_t) > kKwDiagMaxBytes)
         return fail(ORR_EINVAL, "%s: %d bitmaps of %lld words are more than the %llu bytes a call returns", fn, n_terms, (long long)words, (unsigned long long)kKwDiagMaxBytes);
@@ -6190,7 +6183,7 @@ static int scope_fill_near(orr_index *lane, orr_scope *sc, int32_t n_probes, int
             HIP_TRY(hipMemcpyAsync(&count, lane->ws_near_cnt.p, sizeof(count), hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
             if (count <= (unsigned long long)cap) break;
-            if (count > (unsigned long long)scope_near::kMaxBandCap || attempt >= 3)
+            if (count > (unsigned long long)scope_near::kMaxBandCap || attempt + 1 >= scope_near::kMaxWalks)
                 return fail(ORR_EDEVICE, "orr_scope_create_near: the band list kept overflowing (%llu pairs)", count);
             lane->near_band_cap = scope_near::grown_cap((int64_t)count);
         }
@@ -6474,7 +6467,7 @@ struct RangeWork {
     std::vector<range::ListEntry> list;
 
     RangeWork(orr_index *l, const RangeArgs &args, const orr_scope *within, RangeOut &out)
-        : lane(l), a(args), o(out), s(l->stream), B(args.B), D(l->dim), n(l->n_rows), words(((l->n_rows + 31) / 32 + 3) / 4 * 4),
+        : lane(l), a(args), o(out), s(l->stream), B(args.B), D(l->dim), n(l->n_rows), words(keyword::words_per_term(l->n_rows)),
           allowed_rows(within ? within->live.load() : l->n_rows - (int64_t)owner_of(l)->dead.size()) {}
 
     // entries per query: the sticky size as the screen uses it (its launch groups are sized by it) ...

@@ -15,6 +15,7 @@
 #include "orr_range_plan.h"
 #include "orr_diverse_plan.h"
 #include "orr_per_key_plan.h"
+#include "orr_keyword_plan.h"
 
 #include <atomic>
 
@@ -67,13 +68,7 @@ struct SelEntry {
     uint32_t pad;
 };
 
-// Per-term metadata for the keyword scan (built on the host per batch).
-struct ScanTerm {
-    uint32_t off;      // byte offset of the term in the term pool
-    uint32_t len;      // bytes
-    uint32_t prefix;   // first min(4,len) bytes, little-endian packed
-    uint32_t mask;     // byte mask of those bytes
-};
+// (ScanTerm, the per-term metadata of the keyword scan: orr_keyword_plan.h)
 
 // K0 / K1e: out[q][r] = sum_i (double)fl32(Q[q][i] * E[r][i]) in index order (exact
 // reference arithmetic, RecallSearchService.cs:77-82).  self_norm: Q is ignored and
@@ -125,23 +120,14 @@ struct KwHit {
     uint32_t term;
     uint32_t token;         // vocabulary token of the hit (launch_kw_alias: a term whose ONLY hit is a token with a stored bitmap needs no expansion)
 };
+static_assert(sizeof(KwHit) == keyword::kHitBytes, "keyword::after_run sizes the hit list");
 constexpr uint32_t kPostChunk = 1024;
 
 // token_ids != nullptr: the scanned rows were the vocabulary tokens token_ids[0..n_tokens) (the long ones)
 hipError_t launch_vocab_hits(const uint16_t *vmatch, int64_t n_tokens, int32_t n_terms, const uint32_t *token_ids,
                              const uint64_t *post_off, unsigned long long *counter, KwHit *hits, uint32_t max_hits, hipStream_t s);
 
-// A query term for the lane-per-token matcher: its first 16 bytes as dwords with byte masks.
-struct MatchTerm {
-    uint32_t w[4], m[4];
-    uint32_t len;       // bytes; terms longer than 16 bytes cannot occur in the tokens this kernel covers
-    uint32_t pad[3];
-};
-struct MatchTerm8 {                   // the same with eight dwords: terms of up to 32 bytes against tokens of 17..32 bytes
-    uint32_t w[8], m[8];
-    uint32_t len;
-    uint32_t pad[3];
-};
+// (MatchTerm, MatchTerm8 -- a query term for the lane-per-token matchers -- kVocabBloomBits and vocab_bloom_hash: orr_keyword_plan.h)
 constexpr int kMatchGroup = 32;       // terms per workgroup (grid.y)
 // Every token of at most 16 bytes against every term, hits reserved as by launch_vocab_hits.
 hipError_t launch_vocab_match_short(const uint8_t *vpool, const uint64_t *vstart, const uint32_t *vlen, int64_t n_tokens,
@@ -150,16 +136,6 @@ hipError_t launch_vocab_match_short(const uint8_t *vpool, const uint64_t *vstart
 // Tokens of at most 16 bytes against MANY terms: the terms (of at most 16 bytes) sorted by their length-masked first dword in
 // four classes (lk[0..4] = class boundaries in keys / tidx; 1, 2, 3, 4+ bytes), every window of a token looked up.
 // bloom: kVocabBloomBits bits, bit vocab_bloom_hash(key, class) set for every (class, key) of the tables.
-constexpr int kVocabBloomBits = 1 << 17;
-#if defined(__HIPCC__)
-__host__ __device__
-#endif
-inline uint32_t vocab_bloom_hash(uint32_t key, uint32_t cls)
-{
-    uint32_t h = (key ^ (cls * 0x9E3779B9u)) * 2654435761u;
-    h ^= h >> 15;
-    return h & (uint32_t)(kVocabBloomBits - 1);
-}
 hipError_t launch_vocab_match_lookup(const uint8_t *vpool, const uint64_t *vstart, const uint32_t *vlen, int64_t n_tokens,
                                      const MatchTerm *terms, const uint32_t *lk, const uint32_t *keys, const uint32_t *tidx,
                                      const uint32_t *bloom, const uint64_t *post_off, unsigned long long *counter, KwHit *hits,

@@ -56,6 +56,7 @@ constexpr int32_t kMaxProbes = 8;                 // == orr::kMaxExactQ: what on
 constexpr double kBandRel = 0x1p-41;              // band_width = kBandRel * max(2, |c|): 2^-40 for |c| <= 2 (derivation above)
 constexpr int64_t kDefaultBandCap = 1 << 16;      // "near_band_cap": 1 MiB of entries; duplicates at the threshold grow it
 constexpr int64_t kMaxBandCap = (int64_t)1 << 31; // 8 probes x 2^28 rows
+constexpr int kMaxWalks = 4;                      // walks of one fill, the first included, before "the band list kept overflowing"
 
 struct BandEntry {                                // what the kernel hands to the host for one undecided pair
     uint32_t pos;                                 // the row's position

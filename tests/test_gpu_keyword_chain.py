@@ -296,7 +296,7 @@ def _corpus_e():
     queries = ["ab %s k03!&+=- %s" % (planted[257].decode(), rnd[500].decode()), "aaaaaaaaaaaaaaaa hg ^07 中"]
     want = [corpus.search([], text, NOW, 10, candidate_limit=NE) for text in queries]
     assert all(len(w[0]) == 10 for w in want)
-    _E.update(idx=idx, ref=ref, terms=terms, queries=queries, want=want, planted=planted, longs=longs)
+    _E.update(idx=idx, ref=ref, terms=terms, queries=queries, want=want, planted=planted, longs=longs, corpus=corpus)
     return _E
 
 
@@ -392,6 +392,32 @@ def test_argument_errors_on_a_real_index():
     assert err.value.code == P.native.ORR_ESTATE                            # not sealed
     raw.close()
     _search_equals_the_oracle(e, "refused calls")
+
+
+def _batch_equals_the_oracle(idx, corpus, texts, n_rows, what):
+    """one hybrid batch: rows and score bits of every query against the oracle's, as _search_equals_the_oracle compares them"""
+    P = pkg()
+    terms = [P.text.query_terms(t) for t in texts]
+    rows, scores, counts = idx.search(None, terms, NOW, 10, candidate_limit=n_rows)
+    for b, text in enumerate(texts):
+        orow, osc, _ = corpus.search([], text, NOW, 10, candidate_limit=n_rows)
+        assert len(orow) == 10, (what, b)
+        assert list(rows[b, :counts[b]]) == list(orow) and np.array_equal(scores[b, :counts[b]], osc), (what, b)
+    return terms
+
+
+def test_edges_batch_with_shared_terms_and_a_query_without_terms():
+    """What the host half of the chain makes of a batch and nothing else looks at: a term that two queries share (one bitmap,
+    two entries of the term map), a query with no terms between queries that have some (two equal query offsets), a term of
+    17 .. 32 bytes and a longer one (the eight-dword image, the term pool).  A term repeated inside one query is the plan's
+    selftest's: the text layer may fold it."""
+    e = _corpus_e()
+    planted = e["planted"]
+    texts = ["ab %s" % planted[257].decode(), "hg ab ^07", "", "%s 中 %s" % (planted[63].decode(), planted[64].decode()), "aaaaaaaaaaaaaaaa k03!&+=-"]
+    terms = _batch_equals_the_oracle(e["idx"], e["corpus"], texts, NE, "corpus E, five queries")
+    assert set(terms[0]) & set(terms[1]) == {b"ab"} and terms[2] == [] and all(len(q) == len(set(q)) for q in terms)
+    assert any(17 <= len(t) <= 32 for t in terms[3]) and any(len(t) > 32 for t in terms[3])
+    _search_equals_the_oracle(e, "behind the batch of five")
 
 
 # ---- the two large corpora: fixed-width rows, the bitmap reference as array compares ---------------------------------------------
@@ -512,6 +538,30 @@ def test_default_form_selection_at_the_threshold(case):
     other = idx.keyword_bitmaps(terms, form=1 - form)                       # ... and the other form agrees on this vocabulary
     assert other["form"] == 1 - form
     _exact(other, ref, terms, ("corpus T", case, "the form not chosen"))
+
+
+def test_batch_of_many_distinct_terms_takes_the_lookup_form():
+    """The lookup form's tables and Bloom bits as a SEARCH uploads them: two queries that together hold four terms more than the
+    default selection's threshold, the same four terms in both (150 terms a query at most, as tests/test_gpu_count_words.py has)."""
+    P = pkg()
+    t = _corpus_t()
+    idx, ref = t["idx"], t["ref"]
+    pool = [x for x in t["terms"] if len(x) >= 3]
+    shared, own = pool[:4], pool[4:]
+    need = t["at"] + 4
+    n0 = 150 - 4
+    queries = [shared[:2] + own[:n0] + shared[2:], own[n0:need - 4] + shared]
+    assert len(queries) == 2 and max(len(q) for q in queries) <= 150 and len(own) >= need - 4
+    texts = [b" ".join(q).decode() for q in queries]
+    distinct = list(dict.fromkeys(x for text in texts for x in P.text.query_terms(text)))
+    assert len(distinct) >= need and all(set(shared) <= set(P.text.query_terms(text)) for text in texts), len(distinct)
+    got = idx.keyword_bitmaps(distinct)                                     # form -1: as the search below chooses
+    assert got["form"] == 1 and got["runs"] == 1, (len(distinct), got["form"])
+    _exact(got, ref, distinct, ("corpus T", len(distinct), "terms of two queries"))
+    if "corpus" not in t:
+        created = (NOW - np.arange(NT_ROWS, dtype=np.int64) * 1000).astype(np.int64)       # _build's
+        t["corpus"] = orc.OracleCorpus([None] * NT_ROWS, created, ref.rows)
+    _batch_equals_the_oracle(idx, t["corpus"], texts, NT_ROWS, "corpus T, two queries past the threshold")
 
 
 # ---- corpus A: stored token bitmaps ----------------------------------------------------------------------------------------------

@@ -30,7 +30,12 @@ def test_entry_point_is_declared_exported_bound_and_documented():
     # the two overrides are per-call state read ahead of the environment switches, which stay
     api = open(os.path.join(ROOT, "omni-recall-rag_amd", "csrc", "orr_api.hip")).read()
     assert 'getenv("ORR_VOCAB_LOOKUP")' in api and 'getenv("ORR_VOCAB_MID")' in api
-    assert "idx->kw_force_form >= 0" in api and "idx->kw_force_mid >= 0" in api
+    # (the precedence itself is keyword::short_form's and keyword::mid_tokens': the driver hands them the override, then the
+    # environment's value, and the plan's selftest goes through all nine combinations of the two)
+    assert re.search(r"keyword::short_form\([^;]*, idx->kw_force_form, kw_env\(\)\.lookup\);", api)
+    assert re.search(r"keyword::mid_tokens\([^;]*, idx->kw_force_mid, kw_env\(\)\.mid_off\);", api)
+    from test_keyword_plan_cpu import run_selftest
+    assert "forced x env combinations checked: 9" in run_selftest()
 
 
 def test_argument_errors_before_any_device_call():

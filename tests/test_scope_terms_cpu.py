@@ -45,7 +45,8 @@ def test_the_kernel_and_the_selftest_share_the_inlines():
     # the cleanup behind a keyword chain is ONE function, which the search's last stage and the term scope both call
     assert len(re.findall(r"^int clean_keyword_side\(", api, flags=re.M)) == 1
     assert api.count("clean_keyword_side(") >= 3
-    assert api.count("idx->bitmaps_clean = std::max(") == 1 and api.count("idx->kw_counters_clean = true;") == 1
+    assert api.count("idx->kw_clean.grant_bitmaps(") == 1 and api.count("idx->kw_clean.grant_counters(") == 1
+    assert api.count("grant_bitmaps(") == 2 and api.count("grant_counters(") == 2      # each: KwVouchers' definition and that one call
 
 
 def _declared(header):

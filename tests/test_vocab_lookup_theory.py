@@ -89,7 +89,7 @@ def check(tokens, terms):
         assert len(got) == len(set(got)), (tok, got)              # one hit per (token, term)
 
 
-def test_random_vocabulary_and_substring_terms():
+def random_case():
     rng = random.Random(5)
     syll = [b"ka", b"re", b"mi", b"to", b"ne", b"su", b"lo", b"vi", b"da", b"po", b"er", b"in", b"a", b"e", b"x1", b"\xc3\xa9"]
     tokens = list({b"".join(rng.choice(syll) for _ in range(rng.randint(1, 8)))[:16] for _ in range(3000)})
@@ -99,24 +99,58 @@ def test_random_vocabulary_and_substring_terms():
         a = rng.randrange(len(t))
         terms.add(t[a:a + rng.randint(1, 16)])
     terms |= {b"zzz", b"q", b"kareka", b"ererer", rng.choice(tokens)}
-    terms = [t for t in terms if t]
-    check(tokens, terms)
+    return tokens, [t for t in terms if t]
 
 
-def test_engineered_cases():
+def engineered_case():
     tokens = [b"aaaaaaaaaaaaaaaa", b"abababababababab", b"a", b"ab", b"abc", b"abcd", b"abcde", b"abcdefghijklmnop",
               b"xabcdefghijklmno", b"kubernetes", b"netnetnet", b"helm", b"mlehhelm", b"zzzzzzzzzzzzzzzz", b"0123456789abcdef"]
     terms = [b"a", b"aa", b"aaa", b"aaaa", b"aaaaa", b"aaaaaaaaaaaaaaaa", b"ab", b"aba", b"abab", b"b", b"ba", b"abc", b"abcd", b"abcde",
              b"bcde", b"cde", b"de", b"e", b"abcdefghijklmnop", b"bcdefghijklmnop", b"mnop", b"nop", b"op", b"p", b"net", b"tne", b"etn",
              b"helm", b"elm", b"lm", b"m", b"hhelm", b"zzzz", b"zzzzzzzzzzzzzzzz", b"zzzzzzzzzzzzzzzzz", b"0123", b"cdef", b"9abc", b"",
              b"abcdefghijklmnopq", b"kubernetes", b"kubernetesx", b"ubernete"]
-    terms = [t for t in terms]
-    check(tokens, terms)
+    return tokens, terms
+
+
+def short_alphabet_case():
+    alpha = [b"a", b"b"]
+    tokens = [b"".join(p) for n in range(1, 8) for p in itertools.product(alpha, repeat=n)]
+    terms = [b"".join(p) for n in range(1, 6) for p in itertools.product(alpha, repeat=n)]
+    return tokens, terms
+
+
+def test_random_vocabulary_and_substring_terms():
+    check(*random_case())
+
+
+def test_engineered_cases():
+    check(*engineered_case())
 
 
 def test_every_split_of_short_alphabets():
     """Exhaustive over a two-letter alphabet: every token of up to 7 bytes against every term of up to 5."""
-    alpha = [b"a", b"b"]
-    tokens = [b"".join(p) for n in range(1, 8) for p in itertools.product(alpha, repeat=n)]
-    terms = [b"".join(p) for n in range(1, 6) for p in itertools.product(alpha, repeat=n)]
-    check(tokens, terms)
+    check(*short_alphabet_case())
+
+
+def test_build_tables_is_what_the_library_uploads():
+    """The three term sets above through keyword::fill_meta (csrc/orr_keyword_plan.h, by its selftest's --dump): the class
+    boundaries, keys, term numbers and Bloom bits the chain uploads are the ones build_tables restates."""
+    import os
+    import subprocess
+
+    from helpers import ROOT
+
+    selftest = os.path.join(ROOT, "omni-recall-rag_amd", "csrc", "host", "orr_keyword_plan_selftest")
+    assert os.path.exists(selftest), "build() makes it (csrc/Makefile, target host/orr_keyword_plan_selftest)"
+    for case in (random_case, engineered_case, short_alphabet_case):
+        _, terms = case()
+        order, lk, bloom = build_tables(terms)
+        text = "%d\n" % len(terms) + "".join(t.hex() + "\n" for t in terms)
+        r = subprocess.run([selftest, "--dump"], input=text, capture_output=True, text=True, timeout=60)
+        assert r.returncode == 0, r.stdout + r.stderr
+        got = {line.split()[0]: [int(x) for x in line.split()[1:]] for line in r.stdout.splitlines()}
+        assert got["lk"] == lk + [0, 0, 0], case.__name__
+        assert got["keys"] == [k for _, k, _ in order], case.__name__
+        assert got["terms"] == [t for _, _, t in order], case.__name__
+        assert got["bloom"] == sorted(bloom), case.__name__
+        assert len(order) > 0 and len(order) == lk[4]
