@@ -659,7 +659,8 @@ int orr_search_range_cosine_bulk(orr_index *idx, int32_t B, int32_t dim, const f
 /* ---- diverse search: the results compared WITH EACH OTHER ------------------------------------------------------------------
  * Every search above compares a query with rows.  This one also compares the best rows of a query with each other and returns
  * topk of them that are not near-copies of one another: a near-duplicate collapse of the ranked list, or maximal marginal
- * relevance (MMR).  The cluster form and pools beyond 56 are not offered; a per-document cap is
+ * relevance (MMR).  The cluster form is orr_cluster_search_batch_diverse (with the other cluster calls, below); pools beyond 56
+ * are not offered; a per-document cap is
  * orr_search_batch_per_key below.
  *
  * 1. The pool.  within == NULL: exactly what orr_search_batch returns for topk = pool; with a scope: exactly what
@@ -1140,6 +1141,43 @@ int orr_cluster_search_range_cosine(orr_cluster *c, int32_t B, int32_t dim, cons
 int orr_cluster_search_range_cosine_bulk(orr_cluster *c, int32_t B, int32_t dim, const float *q_host, const double *min_cosine /* host [B] */,
                                     const orr_cluster_scope *within /* or NULL */, int32_t max_hits, orr_range_hit *out_hits,
                                     int32_t *out_n, int64_t *out_total);
+
+/* ---- diverse search over the shards ------------------------------------------------------------------------------------------
+ * orr_search_batch_diverse on a cluster: exactly what that call returns on ONE index holding all the cluster's rows in the global
+ * candidate order (with `within`: an index holding the same rows, scoped to the same set) -- rows, unrounded fused score bits,
+ * counts, pool ranks, unused slots and every rule of the greedy pass.
+ *   The pool is orr_cluster_search_batch (with a scope: orr_cluster_search_batch_in_scope) for topk = pool, with all their rules:
+ *   the global candidate_limit, the ladder, an id carried by rows of several shards.  q_host is host memory.
+ *   The cosines need two stored rows on one device, and a pool usually spans shards.  Each query's HOME shard is the one that
+ *   holds most of its pool (a tie: the lowest shard); the other members' rows are gathered on their shards (kernel statistic
+ *   rows_gather, at most one launch per source shard and group), travel through pinned host memory into the home's staging
+ *   buffer, and ONE pair_dots launch per home shard and group reads each row where it lies.  A pool of n members over G shards
+ *   moves at most n - ceil(n / G) rows, a pool on one shard none.  A group is the consecutive queries whose staged rows fit
+ *   64 MiB (at most 1024 per home).  Every sum is the single index's: a pair's dot does not depend on where its rows lie.
+ *   max_cosine = +inf, lambda == 1, a pool of fewer than 2 rows and a cluster of dim 0 read no cosine, launch nothing beyond the
+ *   pool's search and give the cluster search's first max(1, topk) rows bit for bit.
+ * ORR_EINVAL before any handle is looked at, the outputs untouched, in orr_search_batch_diverse's order; then a NULL cluster;
+ * then, unless B == 0 (which writes nothing): an unsealed cluster (ORR_ESTATE), a scope of another cluster (ORR_EINVAL) or an
+ * orphaned one (ORR_ESTATE), the errors of the underlying cluster search.  The cluster's search statistics move as for one
+ * search of B queries.  The call holds the cluster shared from the pool's search to the last matrix (orr_cluster_compact and
+ * orr_cluster_insert_rows wait for it).  Not offered: the cluster per-key search, the record (shard) form, pools above 56, a
+ * peer-to-peer or RCCL transport of the rows. */
+int orr_cluster_search_batch_diverse(orr_cluster *c, int32_t B, int32_t dim, const float *q_host,
+                                     const uint8_t *terms_utf8, const uint32_t *term_off, const uint32_t *query_term_off,
+                                     int64_t now_ticks, int32_t topk, int64_t candidate_limit,
+                                     const orr_cluster_scope *within /* or NULL: every live row */,
+                                     int32_t pool, int32_t mode, double param,
+                                     int64_t *out_rows, double *out_scores, int32_t *out_counts,
+                                     int32_t *out_pool_rank /* [B][max(1,topk)], may be NULL */);
+
+/* Diagnostic: orr_index_pair_dots over a cluster (tests/test_gpu_cluster_diverse.py).  The lists are of GLOBAL order keys
+ * (row_base of the shard + position); every list goes through the plan and the two kernels of orr_cluster_search_batch_diverse,
+ * and out is what orr_index_pair_dots writes on one index holding all the rows, bit for bit.  ORR_EINVAL from the host, before
+ * any launch, in that call's order; then a NULL cluster, a malformed list_off, an unsealed cluster (ORR_ESTATE), an order key
+ * outside every shard.  A cluster of dim 0: zeros. */
+int orr_cluster_pair_dots(orr_cluster *c, int32_t n_lists, const uint32_t *list_off /* host [n_lists+1] */,
+                          const int64_t *order_keys /* host */, int32_t stride /* >= the longest list, <= 56 */,
+                          double *out /* host [n_lists][stride][stride] */);
 
 #ifdef __cplusplus
 }

@@ -251,6 +251,10 @@ hip.orr_cluster_search_range_cosine.restype = C.c_int
 hip.orr_cluster_search_range_cosine.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp]
 hip.orr_cluster_search_range_cosine_bulk.restype = C.c_int
 hip.orr_cluster_search_range_cosine_bulk.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp]
+hip.orr_cluster_search_batch_diverse.restype = C.c_int
+hip.orr_cluster_search_batch_diverse.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _vp, _i32, _i32, C.c_double, _vp, _vp, _vp, _vp]
+hip.orr_cluster_pair_dots.restype = C.c_int
+hip.orr_cluster_pair_dots.argtypes = [_vp, _i32, _vp, _vp, _i32, _vp]
 
 host.orrh_is_blank.restype = _i32
 host.orrh_is_blank.argtypes = [C.c_char_p, _i64]
@@ -341,6 +345,7 @@ EXPORTED_HIP_SYMBOLS = [
     "orr_cluster_scope_create", "orr_cluster_scope_create_ticks", "orr_cluster_scope_create_terms", "orr_cluster_scope_create_near", "orr_cluster_scope_add_ids", "orr_cluster_scope_combine",
     "orr_cluster_scope_rows", "orr_cluster_scope_row_ids", "orr_cluster_scope_shard", "orr_cluster_scope_destroy", "orr_cluster_search_batch_in_scope",
     "orr_cluster_search_batch_in_scopes", "orr_cluster_search_range_cosine", "orr_cluster_search_range_cosine_bulk",
+    "orr_cluster_search_batch_diverse", "orr_cluster_pair_dots",
 ]
 EXPORTED_HOST_SYMBOLS = ["orrh_is_blank", "orrh_lower_invariant", "orrh_query_terms", "orrh_build_snippet",
                          "orrh_round4", "orrh_has_sufficient_evidence", "orrh_format_score_f4", "orrh_last_error", "orrh_store_create", "orrh_store_destroy",

@@ -46,6 +46,7 @@
 #include "orr_cluster_handle_plan.h"
 #include "orr_cluster_group_plan.h"
 #include "orr_cluster_scope_plan.h"
+#include "orr_cluster_diverse_plan.h"
 #include "orr_token_index.h"
 
 namespace {
@@ -284,6 +285,10 @@ struct orr_index {
     // pinned: the staging of the first two and the matrices as they come back
     DevBuf ws_diverse_pos, ws_diverse_cnt, ws_diverse_out;
     PinnedBuf pin_diverse;
+    // ... over a cluster (orr_cluster_search_batch_diverse, orr_cluster_pair_dots), a lane's: as a source the positions it gathers
+    // and the gathered rows, pinned: the rows on their way to the other shards; as a home the rows the others sent, the lists' masks
+    DevBuf ws_diverse_gpos, ws_diverse_gather, ws_diverse_foreign, ws_diverse_mask;
+    PinnedBuf pin_diverse_rows;
     int opt_range_gemm = range_bulk::Auto;                 // "range_gemm" (orr_search_range_cosine_bulk): 0 the GEMM screen from 65 walked queries up, 1 wherever it applies, 2 never
     int opt_range_form = range::Auto;                      // "range_form": 0 the screen where it applies, 1 the same, 2 the exact form only
     int64_t opt_range_pair_cap = range::kDefaultPairCap;   // "range_pair_cap": kept pairs of one query beyond which the call is ORR_ELIMIT
@@ -826,8 +831,9 @@ void orr_index_destroy(orr_index *idx)
     for (DevBuf *b : {&idx->ws_range_allowed, &idx->ws_range_q, &idx->ws_range_qp, &idx->ws_range_norm, &idx->ws_range_consts, &idx->ws_range_cnt,
                       &idx->ws_range_buf, &idx->ws_range_bdot, &idx->ws_range_list, &idx->ws_range_dots, &idx->ws_range_args}) b->release();
     for (DevBuf *b : {&idx->ws_mask_bm, &idx->ws_mask_chunks, &idx->ws_mask_cnt, &idx->ws_mask_meta}) b->release();
-    for (DevBuf *b : {&idx->ws_diverse_pos, &idx->ws_diverse_cnt, &idx->ws_diverse_out}) b->release();
+    for (DevBuf *b : {&idx->ws_diverse_pos, &idx->ws_diverse_cnt, &idx->ws_diverse_out, &idx->ws_diverse_gpos, &idx->ws_diverse_gather, &idx->ws_diverse_foreign, &idx->ws_diverse_mask}) b->release();
     idx->pin_diverse.release();
+    idx->pin_diverse_rows.release();
     idx->pin_mask.release();
     for (DevBuf *b : {&idx->ws_group_bm, &idx->ws_group_chunks, &idx->ws_group_meta}) b->release();
     idx->pin_group.release();
@@ -6945,8 +6951,10 @@ static_assert(diverse::kMaxPool == ORR_DIVERSE_MAX_POOL && diverse::Collapse == 
 // The exact pair matrices of n_lists lists on the lane the caller holds: list l is cnt[l] <= stride positions pos[l * stride + i],
 // every one of them checked against the shard's rows by the caller.  mats [n_lists][stride][stride]: the elements with i and j
 // below cnt[l] are the kernel's, the others are whatever the workspace held.  Positions and lengths go up and the matrices come
-// back through pinned memory, kListsPerLaunch lists a launch.
-static int pair_dots_on_lane(orr_index *lane, int32_t n_lists, int32_t stride, const uint32_t *pos, const uint32_t *cnt, double *mats)
+// back through pinned memory, kListsPerLaunch lists a launch.  With `foreign` (the cluster's pair step): bit i of foreign[l] set
+// says that pos[l * stride + i] is a row of the lane's ws_diverse_foreign, which holds n_foreign rows the other shards sent.
+static int pair_dots_on_lane(orr_index *lane, int32_t n_lists, int32_t stride, const uint32_t *pos, const uint32_t *cnt, double *mats,
+                             const uint64_t *foreign = nullptr, int64_t n_foreign = 0)
 {
     constexpr int32_t kListsPerLaunch = 1024;
     if (n_lists <= 0) return ORR_OK;
@@ -6956,7 +6964,9 @@ static int pair_dots_on_lane(orr_index *lane, int32_t n_lists, int32_t stride, c
     const size_t per_pos = (size_t)stride, per_mat = (size_t)stride * (size_t)stride;
     const size_t group = (size_t)std::min<int32_t>(n_lists, kListsPerLaunch);
     const size_t pos_bytes = sizeof(uint32_t) * group * per_pos, cnt_bytes = sizeof(uint32_t) * group, mat_bytes = sizeof(double) * group * per_mat;
-    const size_t pin_mat_at = (pos_bytes + cnt_bytes + 15) / 16 * 16;
+    const size_t msk_bytes = foreign ? sizeof(uint64_t) * group : 0, pin_msk_at = (pos_bytes + cnt_bytes + 7) / 8 * 8;
+    const size_t pin_mat_at = (pin_msk_at + msk_bytes + 15) / 16 * 16;
+    if (foreign) ORR_TRY(lane->ws_diverse_mask.reserve(msk_bytes));
     ORR_TRY(lane->ws_diverse_pos.reserve(pos_bytes));
     ORR_TRY(lane->ws_diverse_cnt.reserve(cnt_bytes));
     ORR_TRY(lane->ws_diverse_out.reserve(mat_bytes));
@@ -6970,10 +6980,19 @@ static int pair_dots_on_lane(orr_index *lane, int32_t n_lists, int32_t stride, c
         memcpy(pin + pos_bytes, cnt + l0, sizeof(uint32_t) * nl);
         HIP_TRY(hipMemcpyAsync(lane->ws_diverse_pos.p, pin, sizeof(uint32_t) * nl * per_pos, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(lane->ws_diverse_cnt.p, pin + pos_bytes, sizeof(uint32_t) * nl, hipMemcpyHostToDevice, s));
+        if (foreign) {
+            memcpy(pin + pin_msk_at, foreign + l0, sizeof(uint64_t) * nl);
+            HIP_TRY(hipMemcpyAsync(lane->ws_diverse_mask.p, pin + pin_msk_at, sizeof(uint64_t) * nl, hipMemcpyHostToDevice, s));
+        }
         {
             Timed t(lane, "pair_dots", 4.0 * rows_read * (double)D + 16.0 * pairs);
-            HIP_TRY(orr::launch_pair_dots(lane->d_emb, lane->n_rows, D, lane->ws_diverse_pos.as<uint32_t>(), lane->ws_diverse_cnt.as<uint32_t>(),
-                                          (int32_t)nl, stride, lane->ws_diverse_out.as<double>(), s));
+            if (foreign)
+                HIP_TRY(orr::launch_pair_dots_two(lane->d_emb, lane->n_rows, lane->ws_diverse_foreign.as<float>(), n_foreign, D, lane->ws_diverse_pos.as<uint32_t>(),
+                                                  lane->ws_diverse_cnt.as<uint32_t>(), lane->ws_diverse_mask.as<unsigned long long>(), (int32_t)nl, stride,
+                                                  lane->ws_diverse_out.as<double>(), s));
+            else
+                HIP_TRY(orr::launch_pair_dots(lane->d_emb, lane->n_rows, D, lane->ws_diverse_pos.as<uint32_t>(), lane->ws_diverse_cnt.as<uint32_t>(),
+                                              (int32_t)nl, stride, lane->ws_diverse_out.as<double>(), s));
         }
         HIP_TRY(hipMemcpyAsync(pin + pin_mat_at, lane->ws_diverse_out.p, sizeof(double) * nl * per_mat, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -8454,6 +8473,8 @@ int cluster_scope_call(orr_cluster *c, const char *fn, const BatchArgs &a, const
 
 }  // namespace
 
+static int cluster_plain_search(orr_cluster *c, const BatchArgs &a, int64_t *out_rows, double *out_scores, int32_t *out_counts);
+
 extern "C" {
 
 int orr_cluster_create(const int32_t *devices, int32_t n_shards, int32_t dim, int64_t capacity_rows_per_shard, orr_cluster **out)
@@ -8627,6 +8648,16 @@ int orr_cluster_search_batch(orr_cluster *c, int32_t B, int32_t dim, const float
     if (dim > 0 && is_device_pointer(q_host)) return fail(ORR_EINVAL, "orr_cluster_search_batch: the query vectors must be in host memory (every shard's device reads them)");
     std::shared_lock<std::shared_mutex> lock(c->mu);   // searches run side by side; seal and destroy are exclusive
     if (!c->sealed) return fail(ORR_ESTATE, "orr_cluster_search_batch: the cluster is not sealed");
+    return cluster_plain_search(c, a, out_rows, out_scores, out_counts);
+}
+
+}  // extern "C"
+
+// orr_cluster_search_batch behind its checks, the cluster held shared (orr_cluster_search_batch_diverse runs its pool through it)
+static int cluster_plain_search(orr_cluster *c, const BatchArgs &a, int64_t *out_rows, double *out_scores, int32_t *out_counts)
+{
+    const int32_t B = a.B, topk = a.topk;
+    const int64_t candidate_limit = a.candidate_limit;
     {   // rows deleted from a shard since the seal (orr_index_delete_rows on orr_cluster_shard(i)) shift the candidate_limit prefix
         // of every shard behind it: when the dead-row prefix sums changed they are set again (an option of the shard: every lane
         // of it is idle while it changes)
@@ -8648,6 +8679,8 @@ int orr_cluster_search_batch(orr_cluster *c, int32_t B, int32_t dim, const float
     // k' per shard as orr_search_batch picks it for one shard: any shard may hold the whole top-k
     return escalate(be, a, escalation::initial_kprime(take, be.n_total, orr::kSelWidth), out_rows, out_scores, out_counts);
 }
+
+extern "C" {
 
 int orr_cluster_search_batch_scoped(orr_cluster *c, int32_t B, int32_t dim, const float *q_host, const uint8_t *terms_utf8,
                                     const uint32_t *term_off, const uint32_t *query_term_off, int64_t now_ticks, int32_t topk,
@@ -9049,6 +9082,238 @@ int orr_cluster_search_range_cosine_bulk(orr_cluster *c, int32_t B, int32_t dim,
                                          const orr_cluster_scope *within, int32_t max_hits, orr_range_hit *out_hits, int32_t *out_n, int64_t *out_total)
 {
     return cluster_range_search(c, RangeArgs{B, dim, q_host, min_cosine, max_hits, true, "orr_cluster_search_range_cosine_bulk"}, within, out_hits, out_n, out_total);
+}
+
+}  // extern "C"
+
+// ---- diverse search over the shards (orr_cluster_search_batch_diverse, orr_cluster_pair_dots) -------------------------------
+// The pool is the cluster's plain search (the in-scope search with a scope) for topk = pool, unchanged, which hands back every
+// result's order_key through BatchArgs::out_keys; the cosine and the greedy pass are the single index's (orr_diverse_plan.h).
+// What lies between is the pair step: the two rows of a pair may lie on different shards, and orr_cluster_diverse_plan.h says
+// which rows go where.  Per group of the plan, on the lanes the call holds:
+//   1. every source shard at once: ONE rows_gather of its listed positions into a dense buffer, which goes to pinned host memory;
+//   2. every home shard at once: the runs meant for it go from the sources' pinned buffers into its staging buffer on its own
+//      stream, then ONE two-source pair-dot launch over its lists, and the matrices come back.
+// Nothing here reads another device's memory from a kernel; the rows travel as the records of a cluster search do by default.
+
+namespace {
+
+// The pair matrices of the plan's lists, mats [lists][stride][stride] (the elements at or beyond a list's length are not set).
+int cluster_pair_step(orr_cluster *c, std::vector<Lane> &lanes, const cdiverse::Plan &plan, std::vector<double> &mats)
+{
+    const int32_t G = (int32_t)c->shards.size(), stride = plan.stride;
+    const size_t per_mat = (size_t)stride * (size_t)stride, row_bytes = sizeof(float) * (size_t)c->dim;
+    mats.assign(plan.lists.size() * per_mat, 0.0);
+    for (const cdiverse::Group &grp : plan.groups) {
+        // ---- the sources: gather, then down to pinned memory
+        ORR_TRY(for_each_shard(G, [&](int32_t g) -> int {
+            const std::vector<uint32_t> &want = grp.gather[(size_t)g];
+            if (want.empty()) return ORR_OK;
+            orr_index *lane = lanes[(size_t)g].lane;
+            std::lock_guard<std::mutex> lock(lane->mu);
+            for (uint32_t p : want)                                           // before the launch: the kernel is never handed a row it cannot read
+                if ((int64_t)p >= lane->n_rows) return fail(ORR_EDEVICE, "orr_cluster: the pair step lists position %u of shard %d, which holds %lld rows", p, g, (long long)lane->n_rows);
+            ORR_TRY(bind_device(lane));
+            hipStream_t s = lane->stream;
+            const size_t n = want.size(), rows_at = (sizeof(uint32_t) * n + 15) / 16 * 16;
+            ORR_TRY(lane->ws_diverse_gpos.reserve(sizeof(uint32_t) * n));
+            ORR_TRY(lane->ws_diverse_gather.reserve(row_bytes * n));
+            ORR_TRY(lane->pin_diverse_rows.reserve(rows_at + row_bytes * n));
+            uint8_t *pin = lane->pin_diverse_rows.as<uint8_t>();
+            memcpy(pin, want.data(), sizeof(uint32_t) * n);
+            HIP_TRY(hipMemcpyAsync(lane->ws_diverse_gpos.p, pin, sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
+            {
+                Timed t(lane, "rows_gather", 8.0 * (double)c->dim * (double)n);
+                HIP_TRY(orr::launch_rows_gather(lane->d_emb, lane->n_rows, c->dim, lane->ws_diverse_gpos.as<uint32_t>(), (int64_t)n, lane->ws_diverse_gather.as<float>(), s));
+            }
+            HIP_TRY(hipMemcpyAsync(pin + rows_at, lane->ws_diverse_gather.p, row_bytes * n, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            collect_events(lane);
+            return ORR_OK;
+        }));
+        // ---- the homes: the runs up into the staging buffer, then the dots
+        ORR_TRY(for_each_shard(G, [&](int32_t h) -> int {
+            const std::vector<int32_t> &mine = grp.lists[(size_t)h];
+            if (mine.empty()) return ORR_OK;
+            orr_index *lane = lanes[(size_t)h].lane;
+            std::lock_guard<std::mutex> lock(lane->mu);
+            ORR_TRY(bind_device(lane));
+            ORR_TRY(lane->ws_diverse_foreign.reserve(std::max<size_t>(row_bytes * (size_t)grp.staged[(size_t)h], 16)));
+            for (const cdiverse::Run &run : grp.runs) {
+                if (run.home != h) continue;
+                const orr_index *src = lanes[(size_t)run.src].lane;       // (held by this call: nobody writes its pinned buffer now)
+                const size_t rows_at = (sizeof(uint32_t) * grp.gather[(size_t)run.src].size() + 15) / 16 * 16;
+                HIP_TRY(hipMemcpyAsync(lane->ws_diverse_foreign.as<uint8_t>() + row_bytes * (size_t)run.home_at,
+                                       src->pin_diverse_rows.as<uint8_t>() + rows_at + row_bytes * (size_t)run.src_at, row_bytes * (size_t)run.rows,
+                                       hipMemcpyHostToDevice, lane->stream));
+            }
+            const size_t nl = mine.size();
+            std::vector<uint32_t> pos(nl * (size_t)stride, 0u), cnt(nl, 0u);
+            std::vector<uint64_t> foreign(nl, 0);
+            for (size_t i = 0; i < nl; ++i) {
+                const cdiverse::List &l = plan.lists[(size_t)mine[i]];
+                cnt[i] = (uint32_t)l.n;
+                foreign[i] = l.foreign;
+                for (int32_t k = 0; k < l.n; ++k) {
+                    const int64_t limit = ((l.foreign >> k) & 1) ? grp.staged[(size_t)h] : lane->n_rows;
+                    if ((int64_t)l.at[(size_t)k] >= limit) return fail(ORR_EDEVICE, "orr_cluster: the pair step lists row %u of shard %d beyond its %lld rows", l.at[(size_t)k], h, (long long)limit);
+                    pos[i * (size_t)stride + (size_t)k] = l.at[(size_t)k];
+                }
+            }
+            std::vector<double> got(nl * per_mat);
+            ORR_TRY(pair_dots_on_lane(lane, (int32_t)nl, stride, pos.data(), cnt.data(), got.data(), foreign.data(), grp.staged[(size_t)h]));   // (its stream: behind the copies)
+            for (size_t i = 0; i < nl; ++i) memcpy(mats.data() + (size_t)mine[i] * per_mat, got.data() + i * per_mat, sizeof(double) * per_mat);
+            return ORR_OK;
+        }));
+    }
+    return ORR_OK;
+}
+
+// where the shards lie in the global candidate order, read from the lanes the call holds
+void cluster_extents(const std::vector<Lane> &lanes, std::vector<int64_t> &base, std::vector<int64_t> &rows)
+{
+    for (const Lane &ln : lanes) { base.push_back(ln.lane->row_base); rows.push_back(ln.lane->n_rows); }
+}
+
+int cluster_scope_of(const orr_cluster *c, const orr_cluster_scope *s, const char *fn)
+{
+    orr_cluster *own = nullptr;
+    ORR_TRY(cluster_scope_owner(s, fn, &own));
+    if (own != c || s->parts.size() != c->shards.size()) return fail(ORR_EINVAL, "%s: the scope belongs to another cluster", fn);
+    return ORR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int orr_cluster_search_batch_diverse(orr_cluster *c, int32_t B, int32_t dim, const float *q_host, const uint8_t *terms_utf8,
+                                     const uint32_t *term_off, const uint32_t *query_term_off, int64_t now_ticks, int32_t topk,
+                                     int64_t candidate_limit, const orr_cluster_scope *within, int32_t pool, int32_t mode, double param,
+                                     int64_t *out_rows, double *out_scores, int32_t *out_counts, int32_t *out_pool_rank)
+{
+    static const char *fn = "orr_cluster_search_batch_diverse";
+    switch (diverse::first_invalid(!out_rows || !out_scores || !out_counts, topk, pool, mode, param)) {
+    case 0: break;
+    case 1: return fail(ORR_EINVAL, "%s: out_rows, out_scores and out_counts are required", fn);
+    case 2: return fail(ORR_EINVAL, "%s: pool must be in 1 .. %d", fn, diverse::kMaxPool);
+    case 3: return fail(ORR_EINVAL, "%s: topk %d exceeds the pool of %d", fn, topk, pool);
+    case 4: return fail(ORR_EINVAL, "%s: mode must be ORR_DIVERSE_COLLAPSE (0) or ORR_DIVERSE_MMR (1)", fn);
+    case 5: return fail(ORR_EINVAL, "%s: param is NaN", fn);
+    default: return fail(ORR_EINVAL, "%s: lambda must be in [0, 1]", fn);
+    }
+    if (!c) return fail(ORR_EINVAL, "%s: null cluster", fn);
+    if (B == 0) return ORR_OK;
+    std::shared_lock<std::shared_mutex> lock(c->mu);   // from the pool's search to the last matrix: no compaction or insertion moves a row in between
+    if (!c->sealed) return fail(ORR_ESTATE, "%s: the cluster is not sealed", fn);
+    if (within) ORR_TRY(cluster_scope_of(c, within, fn));
+    // ---- the pool: the cluster's own search for topk = pool, with each result's order_key
+    const int32_t take = diverse::take_of(topk);
+    BatchArgs pa{B, dim, q_host, terms_utf8, term_off, query_term_off, now_ticks, candidate_limit, pool};
+    ORR_TRY(check_batch(c->shards[0], pa, fn));
+    if (dim > 0 && is_device_pointer(q_host)) return fail(ORR_EINVAL, "%s: the query vectors must be in host memory (every shard's device reads them)", fn);
+    std::vector<int64_t> p_rows((size_t)B * pool, -1), keys((size_t)B * pool, -1);
+    std::vector<double> p_scores((size_t)B * pool, 0.0);
+    std::vector<int32_t> p_cnt((size_t)B, 0);
+    pa.out_keys = keys.data();
+    std::vector<Lane> lanes;                            // one per shard, ascending: with a scope from the pool's search on, else for the pair step
+    if (within) {
+        ClusterScope cs{true, 0, nullptr, nullptr};
+        cs.handle = within;
+        cluster_scope_begin(c, pa, p_rows.data(), p_scores.data(), p_cnt.data());
+        cluster_scope_lanes(c, lanes);
+        ORR_TRY(cluster_scope_on_lanes(c, fn, pa, cs, lanes, false, false, p_rows.data(), p_scores.data(), p_cnt.data()));
+    } else {
+        ORR_TRY(cluster_plain_search(c, pa, p_rows.data(), p_scores.data(), p_cnt.data()));
+    }
+    // ---- the pair step: only the queries whose greedy pass reads a cosine
+    std::vector<uint8_t> needs((size_t)B, 0);
+    bool any = false;
+    for (int32_t b = 0; b < B; ++b) any = (needs[(size_t)b] = diverse::needs_dots(mode, param, p_cnt[(size_t)b], c->dim)) || any;
+    cdiverse::Plan plan;
+    std::vector<double> mats;
+    if (any) {
+        if (lanes.empty()) acquire_cluster_lanes(c, lanes);
+        std::vector<int64_t> base, rows;
+        cluster_extents(lanes, base, rows);
+        plan = cdiverse::make_plan(base, rows, B, pool, keys.data(), p_cnt.data(), needs.data(), c->dim);
+        if (!plan.ok) return fail(ORR_EDEVICE, "%s: query %d's result with order_key %lld lies outside every shard", fn, plan.bad_query, (long long)plan.bad_key);
+        ORR_TRY(cluster_pair_step(c, lanes, plan, mats));
+    }
+    lanes.clear();
+    // ---- the greedy pass and the outputs, as on one index
+    const int32_t stride = plan.stride;
+    std::vector<int32_t> picks((size_t)take);
+    for (int32_t b = 0; b < B; ++b) {
+        const int32_t n = p_cnt[(size_t)b], l = any ? plan.list_of[(size_t)b] : -1;
+        const double *m = l >= 0 ? mats.data() + (size_t)l * stride * stride : nullptr;
+        auto cosine = [m, stride](int32_t i, int32_t j) -> double {
+            if (!m) return 0.0;
+            return scope_near::cosine_of(m[diverse::mat_index(stride, i, j)], m[diverse::mat_index(stride, i, i)], m[diverse::mat_index(stride, j, j)]);
+        };
+        const int32_t kept = mode == diverse::Collapse ? diverse::select_collapse(n, take, param, cosine, picks.data())
+                                                       : diverse::select_mmr(n, take, param, p_scores.data() + (size_t)b * pool, cosine, picks.data());
+        for (int32_t i = 0; i < take; ++i) {
+            const size_t o = (size_t)b * take + i;
+            const bool have = i < kept;
+            out_rows[o] = have ? p_rows[(size_t)b * pool + picks[(size_t)i]] : -1;
+            out_scores[o] = have ? p_scores[(size_t)b * pool + picks[(size_t)i]] : 0.0;
+            if (out_pool_rank) out_pool_rank[o] = have ? picks[(size_t)i] : -1;
+        }
+        out_counts[b] = kept;
+    }
+    return ORR_OK;
+}
+
+int orr_cluster_pair_dots(orr_cluster *c, int32_t n_lists, const uint32_t *list_off, const int64_t *order_keys, int32_t stride, double *out)
+{
+    static const char *fn = "orr_cluster_pair_dots";
+    switch (diverse::first_invalid_pairs(!out, n_lists, !list_off, !order_keys, stride)) {
+    case 0: break;
+    case 1: return fail(ORR_EINVAL, "%s: out is NULL", fn);
+    case 2: return fail(ORR_EINVAL, "%s: n_lists is negative", fn);
+    case 3: return fail(ORR_EINVAL, "%s: stride must be in 1 .. %d", fn, diverse::kMaxPool);
+    case 4: return fail(ORR_EINVAL, "%s: list_off is NULL", fn);
+    default: return fail(ORR_EINVAL, "%s: order_keys is NULL", fn);
+    }
+    if (!c) return fail(ORR_EINVAL, "%s: null cluster", fn);
+    if (list_off[0] != 0) return fail(ORR_EINVAL, "%s: list_off must start at 0", fn);
+    for (int32_t l = 0; l < n_lists; ++l) {
+        if (list_off[l + 1] < list_off[l]) return fail(ORR_EINVAL, "%s: list_off decreases at list %d", fn, l);
+        if (list_off[l + 1] - list_off[l] > (uint32_t)stride) return fail(ORR_EINVAL, "%s: list %d holds %u order keys, stride is %d", fn, l, list_off[l + 1] - list_off[l], stride);
+    }
+    std::shared_lock<std::shared_mutex> lock(c->mu);
+    if (!c->sealed) return fail(ORR_ESTATE, "%s: the cluster is not sealed", fn);
+    std::vector<Lane> lanes;
+    acquire_cluster_lanes(c, lanes);
+    std::vector<int64_t> base, rows;
+    cluster_extents(lanes, base, rows);
+    for (uint32_t e = 0; e < list_off[n_lists]; ++e) {                        // before any launch
+        cdiverse::Place pl;
+        if (!cdiverse::locate(base, rows, order_keys[e], &pl)) return fail(ORR_EINVAL, "%s: order_keys[%u] = %lld is outside every shard", fn, e, (long long)order_keys[e]);
+    }
+    if (n_lists == 0) return ORR_OK;
+    std::vector<int64_t> keys((size_t)n_lists * stride, -1);
+    std::vector<int32_t> cnt((size_t)n_lists, 0);
+    std::vector<uint8_t> needs((size_t)n_lists, 0);
+    for (int32_t l = 0; l < n_lists; ++l) {
+        cnt[(size_t)l] = (int32_t)(list_off[l + 1] - list_off[l]);
+        needs[(size_t)l] = c->dim > 0 && cnt[(size_t)l] > 0;
+        for (int32_t i = 0; i < cnt[(size_t)l]; ++i) keys[(size_t)l * stride + i] = order_keys[list_off[l] + (uint32_t)i];
+    }
+    const cdiverse::Plan plan = cdiverse::make_plan(base, rows, n_lists, stride, keys.data(), cnt.data(), needs.data(), c->dim);
+    if (!plan.ok) return fail(ORR_EINVAL, "%s: order key %lld of list %d is outside every shard", fn, (long long)plan.bad_key, plan.bad_query);
+    std::vector<double> mats;
+    ORR_TRY(cluster_pair_step(c, lanes, plan, mats));
+    for (int32_t l = 0; l < n_lists; ++l) {                                   // (what lies at or beyond a list's length stays as the caller left it)
+        const int32_t at = plan.list_of[(size_t)l];
+        for (int32_t i = 0; i < cnt[(size_t)l]; ++i) {
+            double *dst = out + ((size_t)l * stride + i) * stride;
+            if (at < 0) { for (int32_t j = 0; j < cnt[(size_t)l]; ++j) dst[j] = 0.0; continue; }          // a cluster without a dimension: zero rows
+            memcpy(dst, mats.data() + ((size_t)at * plan.stride + i) * plan.stride, sizeof(double) * cnt[(size_t)l]);
+        }
+    }
+    return ORR_OK;
 }
 
 }  // extern "C"

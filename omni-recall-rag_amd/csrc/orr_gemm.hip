@@ -1516,16 +1516,21 @@ hipError_t launch_rescore_exact(const float *E, int32_t D, const float *Q, int32
 // rounded to binary32, added in binary64, in index order.  Any D > 0: the staging loads are 16 bytes wide where D % 4 == 0
 // and E is 16-byte aligned (VEC), single floats otherwise; the last slab is walked to its own width.  A slot of the tile
 // beyond cnt, a column beyond the slab's width and a position at or above n_rows are never read from E.
+// TWO (orr_cluster_search_batch_diverse, orr_cluster_pair_dots; the plan is orr_cluster_diverse_plan.h's): a slot whose bit is
+// set in the list's 64-bit mask reads row pos of the dense buffer F ([n_foreign][D], the rows other shards sent) instead of
+// the shard's E; a row at or above n_foreign is never read.  Nothing else differs: the tile, the pairs and every sum are the
+// same, so a pair's dot does not depend on where its two rows came from.
 // ---------------------------------------------------------------------------
 constexpr int kPairSlab = 256;                    // columns of one slab
 constexpr int kPairLds = kPairSlab + 4;           // floats of one row of the tile
 static_assert(diverse::kMaxPool * kPairLds * 4 <= 64 * 1024, "the tile is static LDS");
 static_assert(diverse::kPairThreads * diverse::kPairsPerThread >= diverse::kMaxPairs, "every pair of the longest list has an owner");
 
-template <bool VEC>
+template <bool VEC, bool TWO>
 __global__ __launch_bounds__(diverse::kPairThreads) void pair_dots_kernel(const float *__restrict__ E, int64_t n_rows, int32_t D,
                                                                           const uint32_t *__restrict__ pos, const uint32_t *__restrict__ cnt,
-                                                                          int32_t stride, double *__restrict__ out)
+                                                                          int32_t stride, double *__restrict__ out, const float *__restrict__ F,
+                                                                          int64_t n_foreign, const unsigned long long *__restrict__ foreign)
 {
     constexpr int NP = diverse::kPairsPerThread;
     __shared__ __attribute__((aligned(16))) float tile[diverse::kMaxPool * kPairLds];
@@ -1537,6 +1542,8 @@ __global__ __launch_bounds__(diverse::kPairThreads) void pair_dots_kernel(const 
     if (t < n) {
         const int64_t p = (int64_t)pos[l * stride + t];
         row_of[t] = p < n_rows ? p : -1;                                    // (never: the host checks every position)
+        if constexpr (TWO)                                                  // a row of F is kept as -2 - row
+            if ((foreign[l] >> t) & 1ull) row_of[t] = p < n_foreign ? -2 - p : -1;
     }
     const int32_t np = diverse::pair_count(n);
     int32_t pi[NP], pj[NP];                                                 // the owned pairs' rows as offsets into the tile
@@ -1563,13 +1570,17 @@ __global__ __launch_bounds__(diverse::kPairThreads) void pair_dots_kernel(const 
                 const int64_t row = row_of[r];
                 float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (row >= 0) v = *reinterpret_cast<const float4 *>(E + row * (int64_t)D + c0 + k);
+                else if (TWO && row < -1) v = *reinterpret_cast<const float4 *>(F + (-2 - row) * (int64_t)D + c0 + k);
                 *reinterpret_cast<float4 *>(&tile[r * kPairLds + k]) = v;
             }
         } else {
             for (int32_t e = t; e < n * w; e += diverse::kPairThreads) {
                 const int32_t r = e / w, k = e - r * w;
                 const int64_t row = row_of[r];
-                tile[r * kPairLds + k] = row >= 0 ? E[row * (int64_t)D + c0 + k] : 0.f;
+                float v = 0.f;
+                if (row >= 0) v = E[row * (int64_t)D + c0 + k];
+                else if (TWO && row < -1) v = F[(-2 - row) * (int64_t)D + c0 + k];
+                tile[r * kPairLds + k] = v;
             }
         }
         __syncthreads();
@@ -1611,9 +1622,61 @@ hipError_t launch_pair_dots(const float *E, int64_t n_rows, int32_t D, const uin
     if (D <= 0 || stride < 1 || stride > diverse::kMaxPool) return hipErrorInvalidValue;
     const dim3 grid((unsigned)n_lists), block((unsigned)diverse::kPairThreads);
     if (D % 4 == 0 && (reinterpret_cast<uintptr_t>(E) & 15) == 0)
-        hipLaunchKernelGGL(pair_dots_kernel<true>, grid, block, 0, s, E, n_rows, D, pos, cnt, stride, out);
+        hipLaunchKernelGGL((pair_dots_kernel<true, false>), grid, block, 0, s, E, n_rows, D, pos, cnt, stride, out, nullptr, 0, nullptr);
     else
-        hipLaunchKernelGGL(pair_dots_kernel<false>, grid, block, 0, s, E, n_rows, D, pos, cnt, stride, out);
+        hipLaunchKernelGGL((pair_dots_kernel<false, false>), grid, block, 0, s, E, n_rows, D, pos, cnt, stride, out, nullptr, 0, nullptr);
+    return hipGetLastError();
+}
+
+// The two-source form: 16-byte staging only where BOTH bases are 16-byte aligned.
+hipError_t launch_pair_dots_two(const float *E, int64_t n_rows, const float *F, int64_t n_foreign, int32_t D, const uint32_t *pos,
+                                const uint32_t *cnt, const unsigned long long *foreign, int32_t n_lists, int32_t stride, double *out, hipStream_t s)
+{
+    if (n_lists <= 0) return hipSuccess;
+    if (D <= 0 || stride < 1 || stride > diverse::kMaxPool || n_foreign < 0 || !foreign || (n_foreign > 0 && !F)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)n_lists), block((unsigned)diverse::kPairThreads);
+    if (D % 4 == 0 && ((reinterpret_cast<uintptr_t>(E) | reinterpret_cast<uintptr_t>(F)) & 15) == 0)
+        hipLaunchKernelGGL((pair_dots_kernel<true, true>), grid, block, 0, s, E, n_rows, D, pos, cnt, stride, out, F, n_foreign, foreign);
+    else
+        hipLaunchKernelGGL((pair_dots_kernel<false, true>), grid, block, 0, s, E, n_rows, D, pos, cnt, stride, out, F, n_foreign, foreign);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// K7g  rows_gather: out[i][0 .. D) = E[pos[i]][0 .. D) for the n listed positions of a shard, the dense buffer the cluster's
+// pair step sends to another shard.  The elements of the whole [n][D] buffer are dealt to the threads in order, so a
+// workgroup reads and writes whole rows coalesced; 16 bytes a thread where D % 4 == 0 and both bases are 16-byte aligned
+// (VEC), single floats otherwise.  A position at or above n_rows is never read (the host has checked it): zeros are written.
+// ---------------------------------------------------------------------------
+template <bool VEC>
+__global__ __launch_bounds__(256) void rows_gather_kernel(const float *__restrict__ E, int64_t n_rows, int32_t D, const uint32_t *__restrict__ pos,
+                                                          int64_t n, float *__restrict__ out)
+{
+    const int32_t w = VEC ? D >> 2 : D;                                     // elements of a row: float4s or floats
+    const int64_t total = n * (int64_t)w, step = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += step) {
+        const int64_t i = e / w;
+        const int32_t k = (int32_t)(e - i * w);
+        const int64_t p = (int64_t)pos[i];
+        if constexpr (VEC) {
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (p < n_rows) v = *reinterpret_cast<const float4 *>(E + p * (int64_t)D + 4 * k);
+            *reinterpret_cast<float4 *>(out + i * (int64_t)D + 4 * k) = v;
+        } else {
+            out[i * (int64_t)D + k] = p < n_rows ? E[p * (int64_t)D + k] : 0.f;
+        }
+    }
+}
+
+hipError_t launch_rows_gather(const float *E, int64_t n_rows, int32_t D, const uint32_t *pos, int64_t n, float *out, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    if (D <= 0) return hipErrorInvalidValue;
+    const bool vec = D % 4 == 0 && ((reinterpret_cast<uintptr_t>(E) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+    const int64_t total = n * (int64_t)(vec ? D >> 2 : D);
+    const dim3 grid((unsigned)std::min<int64_t>((total + 255) / 256, 1 << 16)), block(256);
+    if (vec) hipLaunchKernelGGL(rows_gather_kernel<true>, grid, block, 0, s, E, n_rows, D, pos, n, out);
+    else hipLaunchKernelGGL(rows_gather_kernel<false>, grid, block, 0, s, E, n_rows, D, pos, n, out);
     return hipGetLastError();
 }
 

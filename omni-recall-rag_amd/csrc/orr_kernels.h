@@ -564,4 +564,17 @@ hipError_t launch_pair_dots(const float *E, int64_t n_rows, int32_t D, const uin
                             const uint32_t *cnt /* [n_lists] */, int32_t n_lists, int32_t stride, double *out /* [n_lists][stride][stride] */,
                             hipStream_t s);
 
+// ---- the cluster's pair step (orr_cluster_search_batch_diverse, orr_cluster_pair_dots; the plan is orr_cluster_diverse_plan.h's)
+// launch_pair_dots with two sources: slot i of list l reads row pos[l][i] of the dense buffer F ([n_foreign][D]) where bit i of
+// foreign[l] is set, and row pos[l][i] of E otherwise.  A row at or above n_foreign (n_rows) is treated as a zero row, never
+// read.  The sums are launch_pair_dots's: a pair's dot does not depend on where its rows lie.
+hipError_t launch_pair_dots_two(const float *E, int64_t n_rows, const float *F, int64_t n_foreign, int32_t D,
+                                const uint32_t *pos /* [n_lists][stride] */, const uint32_t *cnt /* [n_lists] */,
+                                const unsigned long long *foreign /* [n_lists] */, int32_t n_lists, int32_t stride,
+                                double *out /* [n_lists][stride][stride] */, hipStream_t s);
+// out[i][0 .. D) = E[pos[i]][0 .. D), i < n: the rows a shard sends to other shards, dense.  A position at or above n_rows is
+// never read: zeros are written.  D > 0.
+hipError_t launch_rows_gather(const float *E, int64_t n_rows, int32_t D, const uint32_t *pos /* [n] */, int64_t n, float *out /* [n][D] */,
+                              hipStream_t s);
+
 }  // namespace orr

@@ -1158,6 +1158,42 @@ class RecallCluster:
                                                          _ptr(qs), _ptr(rows), _ptr(scores), _ptr(counts)))
         return rows, scores, counts
 
+    def search_diverse(self, qvecs, queries_terms, now_ticks: int, topk: int, pool: int, mode: str = "collapse", param: float = 0.95,
+                       within: Optional[RecallClusterScope] = None, candidate_limit: int = 300):
+        """orr_cluster_search_batch_diverse: RecallIndex.search_diverse over all shards, as one index holding all the rows would
+        answer -- the pool is search (search_in_scope with `within`) for topk = pool, and the pool's rows that lie on other
+        shards than the query's home shard travel there for the pair cosines.  qvecs in host memory (numpy) or None.
+        Returns (rows [B,k] int64, fused scores [B,k] float64, counts [B] int32, pool_rank [B,k] int32) in pick order."""
+        modes = {"collapse": 0, "mmr": 1}
+        if mode not in modes:
+            raise ValueError("mode must be 'collapse' or 'mmr'")
+        B = len(queries_terms)
+        dim, q = self._host_query_args(qvecs, B)
+        tpool, toff, qoff = pack_terms(queries_terms)
+        k = max(1, int(topk))
+        rows = np.full((B, k), -1, dtype=np.int64)
+        scores = np.zeros((B, k), dtype=np.float64)
+        counts = np.zeros(B, dtype=np.int32)
+        ranks = np.full((B, k), -1, dtype=np.int32)
+        N.check(N.hip.orr_cluster_search_batch_diverse(self._h, B, dim, _ptr(q), _ptr(tpool), _ptr(toff), _ptr(qoff), now_ticks, int(topk),
+                                                       int(candidate_limit), within._h if within is not None else None, int(pool),
+                                                       modes[mode], float(param), _ptr(rows), _ptr(scores), _ptr(counts), _ptr(ranks)))
+        return rows, scores, counts, ranks
+
+    def pair_dots(self, lists) -> np.ndarray:
+        """orr_cluster_pair_dots: RecallIndex.pair_dots over all shards; the lists hold GLOBAL order keys (a shard's row_base +
+        position), up to 56 each.  Returns [n_lists, stride, stride] float64, stride the longest list's length; what lies
+        beyond a list's own length is NaN."""
+        lists = [np.ascontiguousarray(l, dtype=np.int64).reshape(-1) for l in lists]
+        stride = max([1] + [len(l) for l in lists])
+        off = np.zeros(len(lists) + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(l) for l in lists])
+        keys = np.concatenate(lists) if lists else np.zeros(0, np.int64)
+        keys = np.ascontiguousarray(keys if len(keys) else np.zeros(1, np.int64), dtype=np.int64)
+        out = np.full((len(lists), stride, stride), np.nan, dtype=np.float64)
+        N.check(N.hip.orr_cluster_pair_dots(self._h, len(lists), _ptr(off), _ptr(keys), stride, _ptr(out)))
+        return out
+
     def set_option(self, name: str, value: int) -> None:
         """orr_cluster_set_option ("exchange": 0 pinned host memory, 1 RCCL all-gather)."""
         N.check(N.hip.orr_cluster_set_option(self._h, name.encode(), int(value)))
