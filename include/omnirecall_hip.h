@@ -742,7 +742,8 @@ int orr_search_batch_diverse(orr_index *idx, int32_t B, int32_t dim, const float
  * NULL; pool outside 1 .. 56; max(1, topk) > pool; max_per_key < 1; keys NULL; then a NULL index, and, unless B == 0 (which
  * writes nothing), the errors of the underlying search.  Then ORR_EINVAL for a scope or keys of another shard, ORR_ESTATE for an
  * orphaned scope or keys.
- * Out of scope: the cluster forms and sharded.py, the record (shard) form, the service mirror and the micro-batcher, saving
+ * Out of scope: the cluster forms (built since: orr_cluster_keys and orr_cluster_search_batch_per_key with the other cluster
+ * calls, below) and sharded.py, the record (shard) form, the service mirror and the micro-batcher, saving
  * keys in the shard file, pools above 56, and combining with the diverse search. */
 #define ORR_KEY_NONE INT64_MIN
 typedef struct orr_keys orr_keys;
@@ -1160,8 +1161,8 @@ int orr_cluster_search_range_cosine_bulk(orr_cluster *c, int32_t B, int32_t dim,
  * then, unless B == 0 (which writes nothing): an unsealed cluster (ORR_ESTATE), a scope of another cluster (ORR_EINVAL) or an
  * orphaned one (ORR_ESTATE), the errors of the underlying cluster search.  The cluster's search statistics move as for one
  * search of B queries.  The call holds the cluster shared from the pool's search to the last matrix (orr_cluster_compact and
- * orr_cluster_insert_rows wait for it).  Not offered: the cluster per-key search, the record (shard) form, pools above 56, a
- * peer-to-peer or RCCL transport of the rows. */
+ * orr_cluster_insert_rows wait for it).  Not offered: the record (shard) form, pools above 56, a peer-to-peer or RCCL transport
+ * of the rows (the cluster per-key search: built since, orr_cluster_search_batch_per_key below). */
 int orr_cluster_search_batch_diverse(orr_cluster *c, int32_t B, int32_t dim, const float *q_host,
                                      const uint8_t *terms_utf8, const uint32_t *term_off, const uint32_t *query_term_off,
                                      int64_t now_ticks, int32_t topk, int64_t candidate_limit,
@@ -1178,6 +1179,64 @@ int orr_cluster_search_batch_diverse(orr_cluster *c, int32_t B, int32_t dim, con
 int orr_cluster_pair_dots(orr_cluster *c, int32_t n_lists, const uint32_t *list_off /* host [n_lists+1] */,
                           const int64_t *order_keys /* host */, int32_t stride /* >= the longest list, <= 56 */,
                           double *out /* host [n_lists][stride][stride] */);
+
+/* ---- row keys and the per-key search over the shards ----------------------------------------------------------------------------
+ * An orr_cluster_keys is to orr_keys what orr_cluster_scope is to orr_scope: one orr_keys per shard of one sealed cluster, each
+ * made on its shard and registered there, so orr_index_delete_rows / orr_index_update_rows on a shard, orr_cluster_compact and
+ * orr_cluster_insert_rows carry it with no code of their own (a new row reads ORR_KEY_NONE until the host sets it).  The cluster
+ * owns the handle: orr_cluster_destroy orphans it (ORR_ESTATE from then on, rows -1), and both destroy orders are legal.
+ *
+ *   orr_cluster_keys_create  row_ids and keys are HOST memory (every shard's device reads them); every row starts at ORR_KEY_NONE,
+ *                            then what orr_cluster_keys_set does.
+ *   orr_cluster_keys_set     the whole list goes to every shard at once; a shard passes over the ids it does not hold.  *out_set
+ *                            (may be NULL) is the SUM of the shards' counts: AN ID THAT IS LIVE ON TWO SHARDS COUNTS TWICE (every
+ *                            row of it gets the key).  All parts are taken under one hold, so a search sees an edit on every shard
+ *                            or on none; an edit that fails on some shards orphans the handle.
+ *   orr_cluster_keys_get     host ids -> host keys: per id the answer of the LOWEST shard whose answer is not ORR_KEY_NONE, else
+ *                            ORR_KEY_NONE.
+ *   orr_cluster_keys_rows    the sum of the parts' orr_keys_rows; -1 on NULL or an orphaned handle.
+ *   orr_cluster_keys_shard   shard i's part, borrowed (like orr_cluster_shard): never destroy it; NULL for a bad index.
+ *   orr_cluster_keys_destroy NULL is allowed.
+ *   orr_cluster_scope_create_keys  orr_scope_create_keys on every part; the result is an ordinary orr_cluster_scope.  ORR_EINVAL
+ *                            in that call's order (out NULL, n_keys outside 0 .. 65,536, keys NULL with n_keys > 0, a NULL keys
+ *                            handle), then a NULL cluster, keys of another cluster (ORR_EINVAL) or orphaned (ORR_ESTATE).
+ *
+ * orr_cluster_search_batch_per_key returns what orr_search_batch_per_key returns on ONE index holding all the cluster's rows in
+ * the global candidate order: rows, unrounded fused score bits, keys, counts, out_rounds, unused slots -1 / 0.0 / ORR_KEY_NONE,
+ * and every rule of that call -- it looks outside the pool, so out_counts[b] < take only when the candidates ran out.
+ *   Round 1 is orr_cluster_search_batch (with `within`: orr_cluster_search_batch_in_scope) for topk = pool.  Every pool member is
+ *   a global order key; each shard that holds members reads their keys with ONE keys_gather, and a batch that finishes here
+ *   launches nothing else.  The frozen candidate set of round 1 is built per shard, once, when a second round is first needed:
+ *   without a scope the shard's part of the global candidate_limit prefix, with one the shard's share of max(1, candidate_limit)
+ *   scoped live rows (the split of the in-scope cluster search), a partly covered shard clipped at its share.  A later round, per
+ *   slice of at most 64 unfinished queries: the union table of the slice's closed keys goes to EVERY shard (a key closes
+ *   cluster-wide: its rows may lie anywhere), each seen position to the shard that holds it; every shard at once runs one
+ *   keys_exclude, at most one keys_clear_seen, one scope_counts and one mask_clip_slots; ONE grouped cluster search (the in-scope
+ *   search for a slice of one query) runs over the slice's temporary scopes at topk = pool with no further limit.  The rules that
+ *   are new are csrc/orr_cluster_per_key_plan.h's.
+ *   The call holds the cluster shared from round 1 to the last round (orr_cluster_compact and orr_cluster_insert_rows wait for
+ *   it), ONE set of lanes, taken in ascending shard order, for everything behind round 1 (with `within`: from round 1 on), and
+ *   behind the lanes the keys' and the scope's parts shared in one total order.  The cluster's search statistics move by one
+ *   search of B queries for round 1 and by one search of S queries per slice and round after that.
+ * ORR_EINVAL before any handle is looked at, the outputs untouched, in orr_search_batch_per_key's order (an output NULL; pool
+ * outside 1 .. 56; max(1, topk) > pool; max_per_key < 1; keys NULL); then a NULL cluster; then, unless B == 0 (which writes
+ * nothing): an unsealed cluster (ORR_ESTATE), keys or a scope of another cluster (ORR_EINVAL), orphaned keys or scope
+ * (ORR_ESTATE), q_host in device memory (ORR_EINVAL: every shard's device reads it), the errors of the underlying search.
+ * Out of scope: sharded.py, the record (shard) form, the service mirror and the micro-batcher, keys in the shard file, pools above
+ * 56, combining with the diverse search, de-duplicating the union table per shard. */
+typedef struct orr_cluster_keys orr_cluster_keys;
+int       orr_cluster_keys_create(orr_cluster *c, int64_t n, const int64_t *row_ids /* HOST */, const int64_t *keys /* HOST */, orr_cluster_keys **out);
+int       orr_cluster_keys_set(orr_cluster_keys *k, int64_t n, const int64_t *row_ids, const int64_t *keys, int64_t *out_set /* may be NULL */);
+int       orr_cluster_keys_get(orr_cluster_keys *k, int64_t n, const int64_t *row_ids, int64_t *out_keys);
+int64_t   orr_cluster_keys_rows(const orr_cluster_keys *k);
+orr_keys *orr_cluster_keys_shard(orr_cluster_keys *k, int32_t shard);          /* borrowed, like orr_cluster_scope_shard */
+void      orr_cluster_keys_destroy(orr_cluster_keys *k);
+int       orr_cluster_scope_create_keys(orr_cluster *c, const orr_cluster_keys *k, int32_t n_keys, const int64_t *keys /* HOST */, orr_cluster_scope **out);
+int       orr_cluster_search_batch_per_key(orr_cluster *c, int32_t B, int32_t dim, const float *q_host,
+              const uint8_t *terms_utf8, const uint32_t *term_off, const uint32_t *query_term_off,
+              int64_t now_ticks, int32_t topk, int64_t candidate_limit,
+              const orr_cluster_scope *within /* or NULL */, const orr_cluster_keys *keys, int32_t max_per_key, int32_t pool,
+              int64_t *out_rows, double *out_scores, int64_t *out_keys, int32_t *out_counts, int32_t *out_rounds /* may be NULL */);
 
 #ifdef __cplusplus
 }

@@ -255,6 +255,22 @@ hip.orr_cluster_search_batch_diverse.restype = C.c_int
 hip.orr_cluster_search_batch_diverse.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _vp, _i32, _i32, C.c_double, _vp, _vp, _vp, _vp]
 hip.orr_cluster_pair_dots.restype = C.c_int
 hip.orr_cluster_pair_dots.argtypes = [_vp, _i32, _vp, _vp, _i32, _vp]
+hip.orr_cluster_keys_create.restype = C.c_int
+hip.orr_cluster_keys_create.argtypes = [_vp, _i64, _vp, _vp, C.POINTER(_vp)]
+hip.orr_cluster_keys_set.restype = C.c_int
+hip.orr_cluster_keys_set.argtypes = [_vp, _i64, _vp, _vp, _vp]
+hip.orr_cluster_keys_get.restype = C.c_int
+hip.orr_cluster_keys_get.argtypes = [_vp, _i64, _vp, _vp]
+hip.orr_cluster_keys_rows.restype = _i64
+hip.orr_cluster_keys_rows.argtypes = [_vp]
+hip.orr_cluster_keys_shard.restype = _vp
+hip.orr_cluster_keys_shard.argtypes = [_vp, _i32]
+hip.orr_cluster_keys_destroy.restype = None
+hip.orr_cluster_keys_destroy.argtypes = [_vp]
+hip.orr_cluster_scope_create_keys.restype = C.c_int
+hip.orr_cluster_scope_create_keys.argtypes = [_vp, _vp, _i32, _vp, C.POINTER(_vp)]
+hip.orr_cluster_search_batch_per_key.restype = C.c_int
+hip.orr_cluster_search_batch_per_key.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]
 
 host.orrh_is_blank.restype = _i32
 host.orrh_is_blank.argtypes = [C.c_char_p, _i64]
@@ -346,6 +362,8 @@ EXPORTED_HIP_SYMBOLS = [
     "orr_cluster_scope_rows", "orr_cluster_scope_row_ids", "orr_cluster_scope_shard", "orr_cluster_scope_destroy", "orr_cluster_search_batch_in_scope",
     "orr_cluster_search_batch_in_scopes", "orr_cluster_search_range_cosine", "orr_cluster_search_range_cosine_bulk",
     "orr_cluster_search_batch_diverse", "orr_cluster_pair_dots",
+    "orr_cluster_keys_create", "orr_cluster_keys_set", "orr_cluster_keys_get", "orr_cluster_keys_rows", "orr_cluster_keys_shard", "orr_cluster_keys_destroy",
+    "orr_cluster_scope_create_keys", "orr_cluster_search_batch_per_key",
 ]
 EXPORTED_HOST_SYMBOLS = ["orrh_is_blank", "orrh_lower_invariant", "orrh_query_terms", "orrh_build_snippet",
                          "orrh_round4", "orrh_has_sufficient_evidence", "orrh_format_score_f4", "orrh_last_error", "orrh_store_create", "orrh_store_destroy",

@@ -47,6 +47,7 @@
 #include "orr_cluster_group_plan.h"
 #include "orr_cluster_scope_plan.h"
 #include "orr_cluster_diverse_plan.h"
+#include "orr_cluster_per_key_plan.h"
 #include "orr_token_index.h"
 
 namespace {
@@ -2579,15 +2580,8 @@ int check_batch(const orr_index *idx, const BatchArgs &a, const char *fn)
 // Deleted rows do not count: the prefix ends behind the shard's local_live-th live row.
 int64_t participating_rows(const orr_index *idx, int64_t candidate_limit)
 {
-    const int64_t limit = std::max<int64_t>(1, candidate_limit);     // Take(Math.Max(1, maxCount))
-    const int64_t local_live = limit - (idx->row_base - idx->dead_before);
-    if (local_live <= 0) return 0;
-    int64_t p = local_live;                                          // smallest p with p - dead(< p) == local_live
-    for (int64_t d : owner_of(idx)->dead) {
-        if (d < p) ++p; else break;
-        if (p >= idx->n_rows) break;
-    }
-    return std::min<int64_t>(p, idx->n_rows);
+    const std::vector<int64_t> &dead = owner_of(idx)->dead;
+    return cper_key::prefix_rows(candidate_limit, idx->row_base, idx->dead_before, idx->n_rows, dead.data(), dead.size());
 }
 
 bool is_device_pointer(const void *p)
@@ -7254,19 +7248,9 @@ int orr_keys_set(orr_keys *k, int64_t n, const int64_t *row_ids, const int64_t *
     return keys_set_held(lane, k, n, row_ids, keys, out_set);
 }
 
-int orr_keys_get(orr_keys *k, int64_t n, const int64_t *row_ids, int64_t *out_keys)
+// orr_keys_get behind its locks (the lane, its lock, the column shared): own is the column's shard.
+static int keys_get_held(orr_index *lane, const orr_keys *k, const orr_index *own, int64_t n, const int64_t *row_ids, int64_t *out_keys)
 {
-    static const char *fn = "orr_keys_get";
-    if (n < 0) return fail(ORR_EINVAL, "%s: n is negative", fn);
-    if (n > 0 && (!row_ids || !out_keys)) return fail(ORR_EINVAL, "%s: row_ids or out_keys is NULL with %lld entries", fn, (long long)n);
-    if (!k) return fail(ORR_EINVAL, "%s: null keys", fn);
-    orr_index *own = nullptr;
-    ORR_TRY(keys_owner(k, nullptr, fn, &own));
-    Lane ln = acquire_lane(own);
-    orr_index *lane = ln.lane;
-    std::lock_guard<std::mutex> lock(lane->mu);
-    std::shared_lock<std::shared_mutex> rd(k->mu);
-    ORR_TRY(keys_owner(k, nullptr, fn, &own));
     if (n == 0) return ORR_OK;
     if (lane->n_rows <= 0) { for (int64_t i = 0; i < n; ++i) out_keys[i] = ORR_KEY_NONE; return ORR_OK; }
     ORR_TRY(bind_device(lane));
@@ -7291,6 +7275,22 @@ int orr_keys_get(orr_keys *k, int64_t n, const int64_t *row_ids, int64_t *out_ke
     if (r != ORR_OK) (void)hipStreamSynchronize(s);
     io.release();
     return r;
+}
+
+int orr_keys_get(orr_keys *k, int64_t n, const int64_t *row_ids, int64_t *out_keys)
+{
+    static const char *fn = "orr_keys_get";
+    if (n < 0) return fail(ORR_EINVAL, "%s: n is negative", fn);
+    if (n > 0 && (!row_ids || !out_keys)) return fail(ORR_EINVAL, "%s: row_ids or out_keys is NULL with %lld entries", fn, (long long)n);
+    if (!k) return fail(ORR_EINVAL, "%s: null keys", fn);
+    orr_index *own = nullptr;
+    ORR_TRY(keys_owner(k, nullptr, fn, &own));
+    Lane ln = acquire_lane(own);
+    orr_index *lane = ln.lane;
+    std::lock_guard<std::mutex> lock(lane->mu);
+    std::shared_lock<std::shared_mutex> rd(k->mu);
+    ORR_TRY(keys_owner(k, nullptr, fn, &own));
+    return keys_get_held(lane, k, own, n, row_ids, out_keys);
 }
 
 int64_t orr_keys_rows(const orr_keys *k)
@@ -7424,8 +7424,9 @@ int per_key_gather(orr_index *lane, const orr_keys *keys, DevBuf &io, const std:
 }
 
 // The frozen candidate set C of a call as a bitmap, built once when a second round is first needed: the rows that took part in
-// round 1 -- `within`'s bits (or the live rows) below the clip position of the call's candidate_limit.
-int per_key_freeze(orr_index *lane, const BatchArgs &a, const orr_scope *within, PerKeyWork &w)
+// round 1 -- `within`'s bits (or the live rows) below the clip position of the call's candidate_limit.  scope_took >= 0: the
+// first scope_took rows of `within` instead (a cluster's shard: its share of the limit, orr_cluster_per_key_plan.h).
+int per_key_freeze(orr_index *lane, const BatchArgs &a, const orr_scope *within, PerKeyWork &w, int64_t scope_took = -1)
 {
     if (w.frozen) return ORR_OK;
     const orr_index *own = owner_of(lane);
@@ -7436,8 +7437,8 @@ int per_key_freeze(orr_index *lane, const BatchArgs &a, const orr_scope *within,
     if (!within) {
         n_clip = participating_rows(lane, a.candidate_limit);
     } else {
-        const int64_t live = within->live.load(), took = std::min<int64_t>(live, std::max<int64_t>(1, a.candidate_limit));
-        n_clip = within->n_clip_all;
+        const int64_t live = within->live.load(), took = scope_took >= 0 ? std::min<int64_t>(live, scope_took) : std::min<int64_t>(live, std::max<int64_t>(1, a.candidate_limit));
+        n_clip = took > 0 ? within->n_clip_all : 0;
         if (took < live && took > 0) {
             ORR_TRY(lane->pin_mask.reserve(sizeof(int64_t)));
             {
@@ -7465,6 +7466,9 @@ int per_key_freeze(orr_index *lane, const BatchArgs &a, const orr_scope *within,
     return ORR_OK;
 }
 
+int per_key_slice_scopes(orr_index *lane, const orr_keys *keys, int32_t S, const std::vector<int64_t> &tk, const std::vector<uint64_t> &tm,
+                         const std::vector<int64_t> &seen_pos, const std::vector<int32_t> &seen_slot, PerKeyWork &w, std::unique_ptr<orr_scope[]> &tmp);
+
 // One round beyond the first for the unfinished queries `ids` (ascending, at most per_key::kMaxSlots) of the call `a` (vectors in
 // host memory): ONE keys_exclude launch into the call's temporary scope bitmaps, at most one keys_clear_seen behind it, the
 // counts the grouped stages ask of a scope, ONE search through grouped_batch (masked_batch for a slice of one query) over
@@ -7474,20 +7478,53 @@ int per_key_round(orr_index *lane, const BatchArgs &a, const orr_keys *keys, int
                   std::vector<int64_t> &r_pos, std::vector<int32_t> &r_cnt)
 {
     const int32_t S = (int32_t)ids.size();
-    hipStream_t s = lane->stream;
-    const int64_t words = w.words;
-    const int32_t n_chunks = orr::scope_chunks(words);
     // ---- the union table of the slots' closed keys, the seen pairs
     std::vector<const std::set<int64_t> *> closed((size_t)S);
     for (int32_t i = 0; i < S; ++i) closed[(size_t)i] = &st[(size_t)ids[(size_t)i]].closed;
     std::vector<int64_t> tk;
     std::vector<uint64_t> tm;
     per_key::build_table(closed, tk, tm);
-    const size_t n_tab = tk.size();
     std::vector<int64_t> seen_pos;
     std::vector<int32_t> seen_slot;
     for (int32_t i = 0; i < S; ++i)
         for (int64_t p : st[(size_t)ids[(size_t)i]].seen) { seen_pos.push_back(p); seen_slot.push_back(i); }
+    std::unique_ptr<orr_scope[]> tmp;
+    ORR_TRY(per_key_slice_scopes(lane, keys, S, tk, tm, seen_pos, seen_slot, w, tmp));
+    std::vector<const orr_scope *> ptrs((size_t)S);
+    for (int32_t i = 0; i < S; ++i) ptrs[(size_t)i] = &tmp[(size_t)i];
+    // ---- the search: C minus the exclusions, with no further limit
+    SubBatch sb;
+    BatchArgs cur;
+    ORR_TRY(build_subset(lane, a, ids, sb, cur));
+    cur.topk = pool;
+    cur.candidate_limit = std::max<int64_t>(1, lane->n_rows);
+    r_rows.assign((size_t)S * pool, -1); r_scores.assign((size_t)S * pool, 0.0); r_pos.assign((size_t)S * pool, -1); r_cnt.assign((size_t)S, 0);
+    cur.out_keys = r_pos.data();
+    lane->sstats.searches += 1;
+    lane->sstats.queries += S;
+    if (S == 1) {
+        ORR_TRY(masked_batch(lane, cur, ScopeSource{nullptr, ptrs[0]}, r_rows.data(), r_scores.data(), r_cnt.data()));
+    } else {
+        std::vector<int32_t> qg((size_t)S);
+        std::iota(qg.begin(), qg.end(), 0);
+        GroupArgs ga{S, 0, nullptr, nullptr, qg.data()};
+        ga.scopes = ptrs.data();
+        ORR_TRY(grouped_batch(lane, cur, ga, r_rows.data(), r_scores.data(), r_cnt.data()));
+    }
+    return ORR_OK;
+}
+
+// The temporary scopes of a slice of S unfinished queries on one shard (the lane held, the frozen set built): the union table
+// (tk, tm) of the slots' closed keys and the slots' seen positions (local to this shard) come to the device; ONE keys_exclude
+// launch into the call's bitmaps, at most one keys_clear_seen behind it, the counts the grouped stages ask of a scope; one
+// synchronise.  tmp[i]: slot i's scope, never registered with the index, valid while `w` is.
+int per_key_slice_scopes(orr_index *lane, const orr_keys *keys, int32_t S, const std::vector<int64_t> &tk, const std::vector<uint64_t> &tm,
+                         const std::vector<int64_t> &seen_pos, const std::vector<int32_t> &seen_slot, PerKeyWork &w, std::unique_ptr<orr_scope[]> &tmp)
+{
+    hipStream_t s = lane->stream;
+    const int64_t words = w.words;
+    const int32_t n_chunks = orr::scope_chunks(words);
+    const size_t n_tab = tk.size();
     const size_t n_seen = seen_pos.size();
     ORR_TRY(w.ex_bm.reserve(sizeof(uint32_t) * (size_t)S * (size_t)words));
     ORR_TRY(w.ex_chunks.reserve(sizeof(uint32_t) * (size_t)S * (size_t)n_chunks));
@@ -7533,8 +7570,7 @@ int per_key_round(orr_index *lane, const BatchArgs &a, const orr_keys *keys, int
     HIP_TRY(hipMemcpyAsync(h_live, d_live, sizeof(uint32_t) * (size_t)S, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     collect_events(lane);
-    std::unique_ptr<orr_scope[]> tmp(new orr_scope[(size_t)S]);
-    std::vector<const orr_scope *> ptrs((size_t)S);
+    tmp.reset(new orr_scope[(size_t)S]);
     for (int32_t i = 0; i < S; ++i) {
         orr_scope &sc = tmp[(size_t)i];
         sc.owner.store(const_cast<orr_index *>(owner_of(lane)));
@@ -7542,26 +7578,6 @@ int per_key_round(orr_index *lane, const BatchArgs &a, const orr_keys *keys, int
         sc.bm = ex + (size_t)i * (size_t)words; sc.chunks = exc + (size_t)i * (size_t)n_chunks;
         sc.live.store((int64_t)h_live[i]);
         sc.n_clip_all = std::min<int64_t>(h_clip[i], lane->n_rows);
-        ptrs[(size_t)i] = &sc;
-    }
-    // ---- the search: C minus the exclusions, with no further limit
-    SubBatch sb;
-    BatchArgs cur;
-    ORR_TRY(build_subset(lane, a, ids, sb, cur));
-    cur.topk = pool;
-    cur.candidate_limit = std::max<int64_t>(1, lane->n_rows);
-    r_rows.assign((size_t)S * pool, -1); r_scores.assign((size_t)S * pool, 0.0); r_pos.assign((size_t)S * pool, -1); r_cnt.assign((size_t)S, 0);
-    cur.out_keys = r_pos.data();
-    lane->sstats.searches += 1;
-    lane->sstats.queries += S;
-    if (S == 1) {
-        ORR_TRY(masked_batch(lane, cur, ScopeSource{nullptr, ptrs[0]}, r_rows.data(), r_scores.data(), r_cnt.data()));
-    } else {
-        std::vector<int32_t> qg((size_t)S);
-        std::iota(qg.begin(), qg.end(), 0);
-        GroupArgs ga{S, 0, nullptr, nullptr, qg.data()};
-        ga.scopes = ptrs.data();
-        ORR_TRY(grouped_batch(lane, cur, ga, r_rows.data(), r_scores.data(), r_cnt.data()));
     }
     return ORR_OK;
 }
@@ -7895,6 +7911,7 @@ struct orr_cluster {
     PinnedBuf xhost;
     int64_t rccl_exchanges = 0;        // all-gathers done (orr_cluster_search_stats reports them in reserved[0])
     std::vector<orr_cluster_scope *> cscopes;   // cluster scope handles that are alive, under g_scope_life_mu: orr_cluster_destroy orphans them
+    std::vector<orr_cluster_keys *> ckeys;      // cluster keys handles, likewise
 };
 
 // A cluster scope handle: one orr_scope per shard of one sealed cluster, each made on its shard and registered there, so the
@@ -7902,6 +7919,13 @@ struct orr_cluster {
 struct orr_cluster_scope {
     std::atomic<orr_cluster *> owner{nullptr};   // nullptr: orphaned (the cluster was destroyed, or an edit ended on some shards only)
     std::vector<orr_scope *> parts;              // [shards]
+};
+
+// A cluster keys handle: one orr_keys per shard of one sealed cluster, each made on its shard and registered there
+// (orr_index::key_cols), so the shards' maintenance carries them.
+struct orr_cluster_keys {
+    std::atomic<orr_cluster *> owner{nullptr};   // nullptr: orphaned (the cluster was destroyed, or an edit ended on some shards only)
+    std::vector<orr_keys *> parts;               // [shards]
 };
 
 namespace {
@@ -8326,9 +8350,12 @@ int cluster_scope_sub(orr_cluster *c, const char *fn, const BatchArgs &orig, con
     std::vector<int64_t> rows(nb * (size_t)take, -1);
     std::vector<double> scores(nb * (size_t)take, 0.0);
     std::vector<int32_t> counts(nb, 0);
+    std::vector<int64_t> keys(orig.out_keys ? nb * (size_t)take : 0, -1);      // (out_keys is in the numbering of the call that receives it)
+    if (orig.out_keys) cur.out_keys = keys.data();
     ORR_TRY(cluster_scope_on_lanes(c, fn, cur, cs, lanes, true, requery, rows.data(), scores.data(), counts.data()));
     for (size_t i = 0; i < nb; ++i) {
         const size_t b = (size_t)ids[i];
+        if (orig.out_keys) memcpy(orig.out_keys + b * take, keys.data() + i * take, sizeof(int64_t) * take);
         memcpy(out_rows + b * take, rows.data() + i * take, sizeof(int64_t) * take);
         memcpy(out_scores + b * take, scores.data() + i * take, sizeof(double) * take);
         if (out_counts) out_counts[b] = counts[i];
@@ -8336,14 +8363,25 @@ int cluster_scope_sub(orr_cluster *c, const char *fn, const BatchArgs &orig, con
     return ORR_OK;
 }
 
+int cluster_grouped_on_lanes(orr_cluster *c, const char *fn, const BatchArgs &orig, int32_t n_scopes, const orr_cluster_scope *const *scopes,
+                             const int32_t *query_scope, std::vector<Lane> &lanes, int64_t *out_rows, double *out_scores, int32_t *out_counts);
+
 int cluster_grouped_search(orr_cluster *c, const char *fn, const BatchArgs &orig, int32_t n_scopes, const orr_cluster_scope *const *scopes,
                            const int32_t *query_scope, int64_t *out_rows, double *out_scores, int32_t *out_counts)
 {
-    const int32_t G = (int32_t)c->shards.size(), B = orig.B, take = std::max<int32_t>(1, orig.topk);
-    const bool use_cos = orig.dim > 0 && orig.dim == c->dim;
     cluster_scope_begin(c, orig, out_rows, out_scores, out_counts);
     std::vector<Lane> lanes;
     cluster_scope_lanes(c, lanes);
+    return cluster_grouped_on_lanes(c, fn, orig, n_scopes, scopes, query_scope, lanes, out_rows, out_scores, out_counts);
+}
+
+// The grouped search on the lanes the caller took (orr_cluster_search_batch_per_key runs its later rounds through it on the one
+// set of lanes it holds).  The outputs are the caller's, emptied; orig.out_keys, if set, receives each result's order_key.
+int cluster_grouped_on_lanes(orr_cluster *c, const char *fn, const BatchArgs &orig, int32_t n_scopes, const orr_cluster_scope *const *scopes,
+                             const int32_t *query_scope, std::vector<Lane> &lanes, int64_t *out_rows, double *out_scores, int32_t *out_counts)
+{
+    const int32_t G = (int32_t)c->shards.size(), B = orig.B, take = std::max<int32_t>(1, orig.topk);
+    const bool use_cos = orig.dim > 0 && orig.dim == c->dim;
     // ---- the groups: the distinct handles; their parts shared, in one total order, behind the lanes
     std::vector<uintptr_t> addr((size_t)n_scopes);
     for (int32_t i = 0; i < n_scopes; ++i) addr[(size_t)i] = reinterpret_cast<uintptr_t>(scopes[i]);
@@ -8514,6 +8552,8 @@ void orr_cluster_destroy(orr_cluster *c)
         std::lock_guard<std::mutex> life(g_scope_life_mu);
         for (orr_cluster_scope *s : c->cscopes) s->owner.store(nullptr);
         c->cscopes.clear();
+        for (orr_cluster_keys *k : c->ckeys) k->owner.store(nullptr);
+        c->ckeys.clear();
     }
     for (orr_index *sh : c->shards) orr_index_destroy(sh);
     delete c;
@@ -9314,6 +9354,435 @@ int orr_cluster_pair_dots(orr_cluster *c, int32_t n_lists, const uint32_t *list_
         }
     }
     return ORR_OK;
+}
+
+}  // extern "C"
+
+// ---- row keys and the per-key search over the shards (orr_cluster_keys, orr_cluster_search_batch_per_key) ---------------------
+// The answer, the rounds, the walk and the union table are the single index's (orr_per_key_plan.h, per_key_run above); the
+// device work is the single index's kernels, run on every shard at once (per_key_gather, per_key_freeze, per_key_slice_scopes).
+// What the cluster adds is orr_cluster_per_key_plan.h's: which shard gathers which pool members, the seen order keys as each
+// shard's local positions, each shard's share of the limit, the order of the holds.  A key closes cluster-wide: the slice's
+// union table goes to every shard as it is.
+
+namespace {
+
+// The cluster of a cluster keys handle, or ORR_ESTATE: orphaned.
+int cluster_keys_owner(const orr_cluster_keys *k, const char *fn, orr_cluster **c)
+{
+    *c = k->owner.load();
+    if (!*c) return fail(ORR_ESTATE, "%s: the cluster keys are orphaned: their cluster was destroyed, or an edit of them failed on some shards", fn);
+    return ORR_OK;
+}
+
+// Every part belongs to its shard of `c` still (none was orphaned on its own); the caller holds the parts.
+int cluster_keys_parts_alive(const orr_cluster *c, const orr_cluster_keys *k, const char *fn)
+{
+    for (size_t g = 0; g < k->parts.size(); ++g) {
+        orr_index *own = nullptr;
+        ORR_TRY(keys_owner(k->parts[g], c->shards[g], fn, &own));
+    }
+    return ORR_OK;
+}
+
+void orphan_cluster_keys(orr_cluster_keys *k)
+{
+    std::lock_guard<std::mutex> life(g_scope_life_mu);
+    orr_cluster *c = k->owner.load();
+    if (!c) return;
+    c->ckeys.erase(std::remove(c->ckeys.begin(), c->ckeys.end(), k), c->ckeys.end());
+    k->owner.store(nullptr);
+}
+
+// What the shards of a cluster per-key call own from its first gather on; each is released with its shard's device bound.
+struct ClusterPerKeyWork {
+    std::vector<std::unique_ptr<PerKeyWork>> w;
+    std::vector<int> device;
+    explicit ClusterPerKeyWork(const orr_cluster *c)
+    {
+        for (const orr_index *sh : c->shards) { w.emplace_back(new PerKeyWork()); device.push_back(sh->device); }
+    }
+    ~ClusterPerKeyWork()
+    {
+        for (size_t g = 0; g < w.size(); ++g) { (void)hipSetDevice(device[g]); w[g].reset(); }
+    }
+};
+
+// orr_cluster_search_batch_per_key behind its checks, the cluster held shared.
+int cluster_per_key_run(orr_cluster *c, const char *fn, const BatchArgs &a, const orr_cluster_scope *within, const orr_cluster_keys *keys,
+                        int32_t max_per_key, int32_t pool, int64_t *out_rows, double *out_scores, int64_t *out_row_keys, int32_t *out_counts,
+                        int32_t *out_rounds)
+{
+    const int32_t G = (int32_t)c->shards.size(), B = a.B, take = per_key::take_of(a.topk);
+    for (size_t i = 0; i < (size_t)B * take; ++i) { out_rows[i] = -1; out_scores[i] = 0.0; out_row_keys[i] = ORR_KEY_NONE; }
+    for (int32_t b = 0; b < B; ++b) { out_counts[b] = 0; if (out_rounds) out_rounds[b] = 0; }
+    std::vector<int64_t> r_rows((size_t)B * pool, -1), r_keys((size_t)B * pool, -1);    // r_keys: each result's global order key
+    std::vector<double> r_scores((size_t)B * pool, 0.0);
+    std::vector<int32_t> r_cnt((size_t)B, 0);
+    // ONE set of lanes (ascending shard order) for everything behind round 1, with a scope from round 1 on; behind the lanes the
+    // keys' and the scope's parts shared, in the one order of cper_key::holds.  The call never takes a second set.
+    std::vector<Lane> lanes;
+    std::vector<std::shared_lock<std::shared_mutex>> held;
+    auto hold_parts = [&]() -> int {
+        std::vector<uintptr_t> ka, sa;
+        for (int32_t g = 0; g < G; ++g) {
+            ka.push_back(reinterpret_cast<uintptr_t>(keys->parts[(size_t)g]));
+            if (within) sa.push_back(reinterpret_cast<uintptr_t>(within->parts[(size_t)g]));
+        }
+        const std::vector<cper_key::Hold> order = cper_key::holds(ka, sa);
+        held.reserve(order.size());
+        for (const cper_key::Hold &h : order) {
+            if (h.which) held.emplace_back(within->parts[(size_t)h.shard]->mu);
+            else held.emplace_back(keys->parts[(size_t)h.shard]->mu);
+        }
+        orr_cluster *own = nullptr;
+        ORR_TRY(cluster_keys_owner(keys, fn, &own));
+        ORR_TRY(cluster_keys_parts_alive(c, keys, fn));
+        for (int32_t g = 0; g < G; ++g)
+            if (keys->parts[(size_t)g]->n_rows != lanes[(size_t)g].lane->n_rows)
+                return fail(ORR_ESTATE, "%s: the keys cover %lld rows of shard %d, the shard holds %lld", fn, (long long)keys->parts[(size_t)g]->n_rows, g,
+                            (long long)lanes[(size_t)g].lane->n_rows);
+        if (within) {
+            ORR_TRY(cluster_scope_owner(within, fn, &own));
+            ORR_TRY(cluster_scope_parts_alive(c, within, fn));
+        }
+        return ORR_OK;
+    };
+    // ---- round 1: the pool, exactly the call the cluster's diverse search makes for its own
+    {
+        BatchArgs pa = a;
+        pa.topk = pool;
+        pa.out_keys = r_keys.data();
+        if (within) {
+            ClusterScope cs{true, 0, nullptr, nullptr};
+            cs.handle = within;
+            cluster_scope_begin(c, pa, r_rows.data(), r_scores.data(), r_cnt.data());
+            cluster_scope_lanes(c, lanes);
+            ORR_TRY(hold_parts());
+            ORR_TRY(cluster_scope_on_lanes(c, fn, pa, cs, lanes, true, false, r_rows.data(), r_scores.data(), r_cnt.data()));
+        } else {
+            ORR_TRY(cluster_plain_search(c, pa, r_rows.data(), r_scores.data(), r_cnt.data()));
+            cluster_scope_lanes(c, lanes);
+            ORR_TRY(hold_parts());
+        }
+    }
+    std::vector<int64_t> base, rows;
+    cluster_extents(lanes, base, rows);
+    int64_t all_rows = 0;
+    for (int64_t r : rows) all_rows += r;
+    ClusterPerKeyWork work(c);
+    std::vector<per_key::State> st((size_t)B);          // (State::seen holds global order keys here)
+    std::vector<int32_t> ids((size_t)B);                // the queries of the round in flight: [i] of r_* is query ids[i]
+    std::iota(ids.begin(), ids.end(), 0);
+    bool frozen = false;
+    for (int32_t round = 1; !ids.empty(); ++round) {
+        if (round > take) return fail(ORR_EDEVICE, "%s: a round kept no row", fn);      // (every round keeps at least one)
+        // ---- the round's keys: every shard that holds a member reads its own members' keys with ONE keys_gather
+        const size_t nq = ids.size();
+        const cper_key::Gather gp = cper_key::gather_plan(base, rows, (int32_t)nq, pool, r_keys.data(), r_cnt.data());
+        if (!gp.ok) return fail(ORR_EDEVICE, "%s: a result with order_key %lld lies outside every shard", fn, (long long)gp.bad_key);
+        std::vector<int64_t> rk(nq * (size_t)pool, ORR_KEY_NONE);
+        ORR_TRY(for_each_shard(G, [&](int32_t g) -> int {
+            const std::vector<int64_t> &pos = gp.pos[(size_t)g];
+            if (pos.empty()) return ORR_OK;
+            orr_index *lane = lanes[(size_t)g].lane;
+            std::lock_guard<std::mutex> lock(lane->mu);
+            for (int64_t p : pos)                                             // before the launch: the kernel is never handed a row it cannot read
+                if (p < 0 || p >= lane->n_rows) return fail(ORR_EDEVICE, "%s: the gather lists position %lld of shard %d, which holds %lld rows", fn, (long long)p, g, (long long)lane->n_rows);
+            ORR_TRY(bind_device(lane));
+            std::vector<int64_t> got;
+            ORR_TRY(per_key_gather(lane, keys->parts[(size_t)g], work.w[(size_t)g]->gio, pos, got));
+            for (size_t i = 0; i < pos.size(); ++i) rk[(size_t)gp.at[(size_t)g][i]] = got[i];
+            return ORR_OK;
+        }));
+        // ---- the walk
+        std::vector<int32_t> unfinished;
+        std::vector<int32_t> number((size_t)pool);
+        std::iota(number.begin(), number.end(), 0);
+        for (size_t i = 0; i < nq; ++i) {
+            const int32_t b = ids[i];
+            per_key::State &s = st[(size_t)b];
+            const size_t had = s.kept.size();
+            per_key::walk_round(s, r_cnt[i], rk.data() + i * pool, r_keys.data() + i * pool, number.data(), take, max_per_key, pool);
+            for (size_t t = had; t < s.kept.size(); ++t) {
+                const size_t o = (size_t)b * take + t, from = i * pool + (size_t)s.kept[t];
+                out_rows[o] = r_rows[from]; out_scores[o] = r_scores[from]; out_row_keys[o] = rk[from];
+            }
+            out_counts[b] = (int32_t)s.kept.size();
+            if (out_rounds) out_rounds[b] = s.rounds;
+            if (!s.finished) {
+                if (s.kept.size() == had) return fail(ORR_EDEVICE, "%s: a round kept no row", fn);
+                unfinished.push_back(b);
+            }
+        }
+        if (unfinished.empty()) break;
+        // ---- the frozen set, once: on every shard its part of the rows that took part in round 1
+        if (!frozen) {
+            std::vector<int64_t> took((size_t)G, -1);
+            if (within) {
+                std::vector<int64_t> live((size_t)G);
+                for (int32_t g = 0; g < G; ++g) live[(size_t)g] = within->parts[(size_t)g]->live.load();
+                const cscope::Split split = cscope::split_limit(live, a.candidate_limit);
+                for (int32_t g = 0; g < G; ++g) {
+                    const cper_key::Share sh = cper_key::scope_share(split, g, live[(size_t)g]);
+                    took[(size_t)g] = sh.part == cper_key::Part::Empty ? 0 : sh.took;
+                }
+            }
+            ORR_TRY(for_each_shard(G, [&](int32_t g) -> int {
+                orr_index *lane = lanes[(size_t)g].lane;
+                if (lane->n_rows <= 0) return ORR_OK;
+                std::lock_guard<std::mutex> lock(lane->mu);
+                ORR_TRY(bind_device(lane));
+                return per_key_freeze(lane, a, within ? within->parts[(size_t)g] : nullptr, *work.w[(size_t)g], took[(size_t)g]);
+            }));
+            frozen = true;
+        }
+        // ---- the next round, in slices of at most 64 queries
+        const size_t nu = unfinished.size();
+        std::vector<int64_t> n_rows(nu * (size_t)pool, -1), n_keys(nu * (size_t)pool, -1);
+        std::vector<double> n_scores(nu * (size_t)pool, 0.0);
+        std::vector<int32_t> n_cnt(nu, 0);
+        for (size_t b0 = 0; b0 < nu; b0 += (size_t)per_key::kMaxSlots) {
+            const int32_t S = (int32_t)std::min<size_t>((size_t)per_key::kMaxSlots, nu - b0);
+            const std::vector<int32_t> slice(unfinished.begin() + b0, unfinished.begin() + b0 + S);
+            std::vector<const std::set<int64_t> *> closed((size_t)S);
+            std::vector<const std::vector<int64_t> *> seen((size_t)S);
+            for (int32_t i = 0; i < S; ++i) { closed[(size_t)i] = &st[(size_t)slice[(size_t)i]].closed; seen[(size_t)i] = &st[(size_t)slice[(size_t)i]].seen; }
+            std::vector<int64_t> tk;                    // the SAME table on every shard: a key closes cluster-wide
+            std::vector<uint64_t> tm;
+            per_key::build_table(closed, tk, tm);
+            std::vector<std::unique_ptr<orr_scope[]>> tmp((size_t)G);
+            ORR_TRY(for_each_shard(G, [&](int32_t g) -> int {
+                orr_index *lane = lanes[(size_t)g].lane;
+                if (lane->n_rows <= 0) {                // an empty shard: empty parts, nothing launched
+                    tmp[(size_t)g].reset(new orr_scope[(size_t)S]);
+                    for (int32_t i = 0; i < S; ++i) tmp[(size_t)g][(size_t)i].owner.store(const_cast<orr_index *>(owner_of(lane)));
+                    return ORR_OK;
+                }
+                std::lock_guard<std::mutex> lock(lane->mu);
+                ORR_TRY(bind_device(lane));
+                const cper_key::Seen mine = cper_key::seen_of_shard(base[(size_t)g], rows[(size_t)g], seen);
+                return per_key_slice_scopes(lane, keys->parts[(size_t)g], S, tk, tm, mine.pos, mine.slot, *work.w[(size_t)g], tmp[(size_t)g]);
+            }));
+            // the S temporary per-shard scopes form S temporary cluster scopes, never registered with the cluster
+            std::unique_ptr<orr_cluster_scope[]> cs(new orr_cluster_scope[(size_t)S]);
+            std::vector<const orr_cluster_scope *> ptrs((size_t)S);
+            for (int32_t i = 0; i < S; ++i) {
+                cs[(size_t)i].owner.store(c);
+                for (int32_t g = 0; g < G; ++g) cs[(size_t)i].parts.push_back(&tmp[(size_t)g][(size_t)i]);
+                ptrs[(size_t)i] = &cs[(size_t)i];
+            }
+            // ---- the search: C minus the exclusions, with no further limit
+            SubBatch sb;
+            BatchArgs cur;
+            ORR_TRY(build_subset(lanes[0].lane, a, slice, sb, cur));           // (host-resident vectors: nothing of the lane is used)
+            cur.topk = pool;
+            cur.candidate_limit = std::max<int64_t>(1, all_rows);
+            std::vector<int64_t> s_rows((size_t)S * pool, -1), s_keys((size_t)S * pool, -1);
+            std::vector<double> s_scores((size_t)S * pool, 0.0);
+            std::vector<int32_t> s_cnt((size_t)S, 0);
+            cur.out_keys = s_keys.data();
+            cluster_scope_begin(c, cur, s_rows.data(), s_scores.data(), s_cnt.data());
+            if (S == 1) {
+                ClusterScope one{true, 0, nullptr, nullptr};
+                one.handle = ptrs[0];
+                ORR_TRY(cluster_scope_on_lanes(c, fn, cur, one, lanes, true, false, s_rows.data(), s_scores.data(), s_cnt.data()));
+            } else {
+                std::vector<int32_t> qg((size_t)S);
+                std::iota(qg.begin(), qg.end(), 0);
+                ORR_TRY(cluster_grouped_on_lanes(c, fn, cur, S, ptrs.data(), qg.data(), lanes, s_rows.data(), s_scores.data(), s_cnt.data()));
+            }
+            memcpy(n_rows.data() + b0 * pool, s_rows.data(), sizeof(int64_t) * (size_t)S * pool);
+            memcpy(n_keys.data() + b0 * pool, s_keys.data(), sizeof(int64_t) * (size_t)S * pool);
+            memcpy(n_scores.data() + b0 * pool, s_scores.data(), sizeof(double) * (size_t)S * pool);
+            memcpy(n_cnt.data() + b0, s_cnt.data(), sizeof(int32_t) * (size_t)S);
+        }
+        ids.swap(unfinished);
+        r_rows.swap(n_rows); r_keys.swap(n_keys); r_scores.swap(n_scores); r_cnt.swap(n_cnt);
+    }
+    return ORR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int orr_cluster_keys_create(orr_cluster *c, int64_t n, const int64_t *row_ids, const int64_t *keys, orr_cluster_keys **out)
+{
+    static const char *fn = "orr_cluster_keys_create";
+    if (!out) return fail(ORR_EINVAL, "%s: out is NULL", fn);
+    if (n < 0) return fail(ORR_EINVAL, "%s: n is negative", fn);
+    if (n > 0 && (!row_ids || !keys)) return fail(ORR_EINVAL, "%s: row_ids or keys is NULL with %lld entries", fn, (long long)n);
+    if (!c) return fail(ORR_EINVAL, "%s: null cluster", fn);
+    if (n > 0 && (is_device_pointer(row_ids) || is_device_pointer(keys))) return fail(ORR_EINVAL, "%s: row_ids and keys must be in host memory (every shard's device reads them)", fn);
+    std::shared_lock<std::shared_mutex> lock(c->mu);   // like a search: beside the others; seal, compact, insert are exclusive
+    if (!c->sealed) return fail(ORR_ESTATE, "%s: the cluster is not sealed", fn);
+    const int32_t G = (int32_t)c->shards.size();
+    orr_cluster_keys *k = new (std::nothrow) orr_cluster_keys();
+    if (!k) return fail(ORR_ENOMEM, "out of host memory");
+    k->parts.assign((size_t)G, nullptr);
+    const int r = for_each_shard(G, [&](int32_t g) -> int { return orr_keys_create(c->shards[(size_t)g], n, row_ids, keys, &k->parts[(size_t)g]); });
+    if (r != ORR_OK) {
+        const std::string keep = g_last_error;
+        for (orr_keys *part : k->parts) orr_keys_destroy(part);
+        delete k;
+        g_last_error = keep;
+        return r;
+    }
+    k->owner.store(c);
+    { std::lock_guard<std::mutex> life(g_scope_life_mu); c->ckeys.push_back(k); }
+    *out = k;
+    return ORR_OK;
+}
+
+int orr_cluster_keys_set(orr_cluster_keys *k, int64_t n, const int64_t *row_ids, const int64_t *keys, int64_t *out_set)
+{
+    static const char *fn = "orr_cluster_keys_set";
+    if (n < 0) return fail(ORR_EINVAL, "%s: n is negative", fn);
+    if (n > 0 && (!row_ids || !keys)) return fail(ORR_EINVAL, "%s: row_ids or keys is NULL with %lld entries", fn, (long long)n);
+    if (!k) return fail(ORR_EINVAL, "%s: null keys", fn);
+    if (n > 0 && (is_device_pointer(row_ids) || is_device_pointer(keys))) return fail(ORR_EINVAL, "%s: row_ids and keys must be in host memory (every shard's device reads them)", fn);
+    orr_cluster *c = nullptr;
+    ORR_TRY(cluster_keys_owner(k, fn, &c));
+    std::shared_lock<std::shared_mutex> lock(c->mu);
+    const int32_t G = (int32_t)c->shards.size();
+    std::vector<Lane> lanes;
+    acquire_cluster_lanes(c, lanes);
+    std::vector<std::unique_lock<std::shared_mutex>> held;     // every part exclusively, in ascending shard order
+    held.reserve((size_t)G);
+    for (int32_t g = 0; g < G; ++g) held.emplace_back(k->parts[(size_t)g]->mu);
+    ORR_TRY(cluster_keys_owner(k, fn, &c));
+    ORR_TRY(cluster_keys_parts_alive(c, k, fn));
+    std::vector<int64_t> set((size_t)G, 0);
+    const int r = for_each_shard(G, [&](int32_t g) -> int {
+        orr_index *lane = lanes[(size_t)g].lane;
+        std::lock_guard<std::mutex> l(lane->mu);
+        return keys_set_held(lane, k->parts[(size_t)g], n, row_ids, keys, &set[(size_t)g]);
+    });
+    if (r != ORR_OK) {             // some shards may hold the edit and others not: never searched like that
+        const std::string keep = g_last_error;
+        held.clear();
+        orphan_cluster_keys(k);
+        g_last_error = keep;
+        return r;
+    }
+    if (out_set) { *out_set = 0; for (int64_t s : set) *out_set += s; }
+    return ORR_OK;
+}
+
+int orr_cluster_keys_get(orr_cluster_keys *k, int64_t n, const int64_t *row_ids, int64_t *out_keys)
+{
+    static const char *fn = "orr_cluster_keys_get";
+    if (n < 0) return fail(ORR_EINVAL, "%s: n is negative", fn);
+    if (n > 0 && (!row_ids || !out_keys)) return fail(ORR_EINVAL, "%s: row_ids or out_keys is NULL with %lld entries", fn, (long long)n);
+    if (!k) return fail(ORR_EINVAL, "%s: null keys", fn);
+    if (n > 0 && is_device_pointer(row_ids)) return fail(ORR_EINVAL, "%s: row_ids must be in host memory (every shard's device reads them)", fn);
+    orr_cluster *c = nullptr;
+    ORR_TRY(cluster_keys_owner(k, fn, &c));
+    std::shared_lock<std::shared_mutex> lock(c->mu);
+    const int32_t G = (int32_t)c->shards.size();
+    std::vector<Lane> lanes;
+    acquire_cluster_lanes(c, lanes);
+    std::vector<std::shared_lock<std::shared_mutex>> held;     // every part shared, in ascending shard order
+    held.reserve((size_t)G);
+    for (int32_t g = 0; g < G; ++g) held.emplace_back(k->parts[(size_t)g]->mu);
+    ORR_TRY(cluster_keys_owner(k, fn, &c));
+    ORR_TRY(cluster_keys_parts_alive(c, k, fn));
+    if (n == 0) return ORR_OK;
+    std::vector<int64_t> got((size_t)G * (size_t)n, ORR_KEY_NONE);
+    ORR_TRY(for_each_shard(G, [&](int32_t g) -> int {
+        orr_index *lane = lanes[(size_t)g].lane;
+        std::lock_guard<std::mutex> l(lane->mu);
+        return keys_get_held(lane, k->parts[(size_t)g], c->shards[(size_t)g], n, row_ids, got.data() + (size_t)g * (size_t)n);
+    }));
+    for (int64_t i = 0; i < n; ++i) {                  // the lowest shard that has a key for the id
+        out_keys[i] = ORR_KEY_NONE;
+        for (int32_t g = 0; g < G && out_keys[i] == ORR_KEY_NONE; ++g) out_keys[i] = got[(size_t)g * (size_t)n + (size_t)i];
+    }
+    return ORR_OK;
+}
+
+int64_t orr_cluster_keys_rows(const orr_cluster_keys *k)
+{
+    if (!k || !k->owner.load()) return -1;
+    int64_t n = 0;
+    for (const orr_keys *part : k->parts) {
+        const int64_t rows = orr_keys_rows(part);
+        if (rows < 0) return -1;
+        n += rows;
+    }
+    return n;
+}
+
+orr_keys *orr_cluster_keys_shard(orr_cluster_keys *k, int32_t shard)
+{
+    if (!k || shard < 0 || shard >= (int32_t)k->parts.size()) { (void)fail(ORR_EINVAL, "orr_cluster_keys_shard: no shard %d", shard); return nullptr; }
+    return k->parts[(size_t)shard];
+}
+
+void orr_cluster_keys_destroy(orr_cluster_keys *k)
+{
+    if (!k) return;
+    {   // (the cluster is not destroyed meanwhile; afterwards it no longer knows these keys)
+        std::lock_guard<std::mutex> life(g_scope_life_mu);
+        orr_cluster *c = k->owner.load();
+        if (c) c->ckeys.erase(std::remove(c->ckeys.begin(), c->ckeys.end(), k), c->ckeys.end());
+        k->owner.store(nullptr);
+    }
+    for (orr_keys *part : k->parts) orr_keys_destroy(part);        // each against its own shard's destroy, as a single column
+    delete k;
+}
+
+int orr_cluster_scope_create_keys(orr_cluster *c, const orr_cluster_keys *k, int32_t n_keys, const int64_t *keys, orr_cluster_scope **out)
+{
+    static const char *fn = "orr_cluster_scope_create_keys";
+    switch (per_key::first_invalid_scope_keys(!out, n_keys, !keys, !k)) {
+    case 0: break;
+    case 1: return fail(ORR_EINVAL, "%s: out is NULL", fn);
+    case 2: return fail(ORR_EINVAL, "%s: n_keys must be in 0 .. %d", fn, per_key::kMaxScopeKeys);
+    case 3: return fail(ORR_EINVAL, "%s: keys is NULL with %d keys", fn, n_keys);
+    default: return fail(ORR_EINVAL, "%s: null keys handle", fn);
+    }
+    if (!c) return fail(ORR_EINVAL, "%s: null cluster", fn);
+    orr_cluster *own = k->owner.load();
+    if (own && (own != c || k->parts.size() != c->shards.size())) return fail(ORR_EINVAL, "%s: the keys belong to another cluster", fn);
+    ORR_TRY(cluster_keys_owner(k, fn, &own));
+    if (n_keys > 0 && is_device_pointer(keys)) return fail(ORR_EINVAL, "%s: keys must be in host memory (every shard's device reads them)", fn);
+    return make_cluster_scope(c, fn, out, [&](orr_index *sh, orr_scope **part) -> int {
+        size_t g = 0;
+        while (g < c->shards.size() && c->shards[g] != sh) ++g;
+        if (g >= k->parts.size()) return fail(ORR_ESTATE, "%s: the keys do not cover this shard", fn);
+        return orr_scope_create_keys(sh, k->parts[g], n_keys, keys, part);
+    });
+}
+
+int orr_cluster_search_batch_per_key(orr_cluster *c, int32_t B, int32_t dim, const float *q_host, const uint8_t *terms_utf8, const uint32_t *term_off,
+                                     const uint32_t *query_term_off, int64_t now_ticks, int32_t topk, int64_t candidate_limit,
+                                     const orr_cluster_scope *within, const orr_cluster_keys *keys, int32_t max_per_key, int32_t pool,
+                                     int64_t *out_rows, double *out_scores, int64_t *out_keys, int32_t *out_counts, int32_t *out_rounds)
+{
+    static const char *fn = "orr_cluster_search_batch_per_key";
+    switch (per_key::first_invalid(!out_rows || !out_scores || !out_keys || !out_counts, topk, pool, max_per_key, !keys)) {
+    case 0: break;
+    case 1: return fail(ORR_EINVAL, "%s: out_rows, out_scores, out_keys and out_counts are required", fn);
+    case 2: return fail(ORR_EINVAL, "%s: pool must be in 1 .. %d", fn, per_key::kMaxPool);
+    case 3: return fail(ORR_EINVAL, "%s: topk %d exceeds the pool of %d", fn, topk, pool);
+    case 4: return fail(ORR_EINVAL, "%s: max_per_key must be at least 1", fn);
+    default: return fail(ORR_EINVAL, "%s: null keys", fn);
+    }
+    if (!c) return fail(ORR_EINVAL, "%s: null cluster", fn);
+    if (B == 0) return ORR_OK;
+    std::shared_lock<std::shared_mutex> lock(c->mu);   // from round 1 to the last round: no compaction or insertion moves a row in between
+    if (!c->sealed) return fail(ORR_ESTATE, "%s: the cluster is not sealed", fn);
+    orr_cluster *kown = keys->owner.load(), *sown = within ? within->owner.load() : nullptr;
+    if (kown && (kown != c || keys->parts.size() != c->shards.size())) return fail(ORR_EINVAL, "%s: the keys belong to another cluster", fn);
+    if (sown && (sown != c || within->parts.size() != c->shards.size())) return fail(ORR_EINVAL, "%s: the scope belongs to another cluster", fn);
+    ORR_TRY(cluster_keys_owner(keys, fn, &kown));
+    if (within) ORR_TRY(cluster_scope_owner(within, fn, &sown));
+    if (dim > 0 && is_device_pointer(q_host)) return fail(ORR_EINVAL, "%s: the query vectors must be in host memory (every shard's device reads them)", fn);
+    const BatchArgs a{B, dim, q_host, terms_utf8, term_off, query_term_off, now_ticks, candidate_limit, topk};
+    ORR_TRY(check_batch(c->shards[0], a, fn));
+    return cluster_per_key_run(c, fn, a, within, keys, max_per_key, pool, out_rows, out_scores, out_keys, out_counts, out_rounds);
 }
 
 }  // extern "C"

@@ -25,8 +25,8 @@
 //                 stores them as 16-byte vectors, 256 contiguous bytes per slot; a workgroup none of whose rows is closed copies
 //                 the base words.  The table sits in LDS up to kLdsTable entries (32 KB) and in global memory beyond.
 //
-// Out of scope: the cluster forms, the record (shard) form, the service mirror and the micro-batcher, keys in the shard file,
-// pools above kMaxPool, combining with the diverse search.
+// Out of scope: the cluster forms (built since: orr_cluster_per_key_plan.h), the record (shard) form, the service mirror and the
+// micro-batcher, keys in the shard file, pools above kMaxPool, combining with the diverse search.
 //
 // Host-only C++17 except the inlines marked ORR_PK_HD, which the kernels share (orr_kernels.hip: keys_exclude, keys_member);
 // host/orr_per_key_plan_selftest.cpp checks all of it on a machine without a GPU.

@@ -258,6 +258,79 @@ class RecallKeys:
         return int(N.hip.orr_keys_rows(self._h))
 
 
+class _BorrowedKeys(RecallKeys):
+    """A shard's part of a RecallClusterKeys: usable like a RecallKeys (get, rows, RecallIndex.search_per_key on the shard),
+    never destroyed through this object; it ends with its cluster keys."""
+
+    def close(self) -> None:
+        self._h = None
+
+
+class RecallClusterKeys:
+    """Row keys over a cluster (orr_cluster_keys): one RecallKeys per shard behind one handle.  It follows its rows through
+    delete_rows on a shard, RecallCluster.compact and insert_rows; rows inserted later read KEY_NONE until `set` names them.
+    Made by RecallCluster.keys; close it before or after its cluster (after: only the host part is left to free)."""
+
+    KEY_NONE = N.ORR_KEY_NONE
+
+    def __init__(self, handle, cluster: "RecallCluster"):
+        self._h = handle
+        self._cluster = cluster              # keeps the cluster object alive
+        self._parts = []
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            for part in self._parts:
+                part.close()
+            self._parts = []
+            N.hip.orr_cluster_keys_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _pairs(row_ids, keys):
+        ids = np.ascontiguousarray(row_ids, dtype=np.int64).reshape(-1)
+        ks = np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)
+        if int(ids.shape[0]) != int(ks.shape[0]):
+            raise ValueError("one key per row id")
+        return ids, ks, int(ids.shape[0])
+
+    def set(self, row_ids, keys) -> int:
+        """orr_cluster_keys_set: keys[i] is stored at the live rows that carry row_ids[i], on every shard (numpy, host memory).
+        Returns the SUM of the shards' counts: an id that is live on two shards counts twice."""
+        ids, ks, n = self._pairs(row_ids, keys)
+        done = C.c_int64(0)
+        N.check(N.hip.orr_cluster_keys_set(self._h, n, _ptr(ids) if n else None, _ptr(ks) if n else None, C.cast(C.byref(done), C.c_void_p)))
+        return int(done.value)
+
+    def get(self, row_ids) -> np.ndarray:
+        """orr_cluster_keys_get: the keys of these row ids (host): per id the lowest shard's key that is not KEY_NONE."""
+        ids = np.ascontiguousarray(row_ids, dtype=np.int64).reshape(-1)
+        out = np.full(ids.shape[0], N.ORR_KEY_NONE, dtype=np.int64)
+        n = int(ids.shape[0])
+        N.check(N.hip.orr_cluster_keys_get(self._h, n, _ptr(ids) if n else None, _ptr(out) if n else None))
+        return out
+
+    @property
+    def rows(self) -> int:
+        """orr_cluster_keys_rows: live rows whose key is not KEY_NONE, over all shards; -1 once it is orphaned."""
+        return int(N.hip.orr_cluster_keys_rows(self._h))
+
+    def shard(self, i: int) -> RecallKeys:
+        """orr_cluster_keys_shard: shard i's part, borrowed."""
+        p = N.hip.orr_cluster_keys_shard(self._h, int(i))
+        if not p:
+            N.check(N.ORR_EINVAL)
+        part = _BorrowedKeys(C.c_void_p(p), self)
+        self._parts.append(part)
+        return part
+
+
 class _BorrowedScope(RecallScope):
     """A shard's part of a RecallClusterScope: usable like a RecallScope (rows, row_ids, RecallIndex.search_shard_in_scope),
     never destroyed through this object; it ends with its cluster scope."""
@@ -1179,6 +1252,43 @@ class RecallCluster:
                                                        int(candidate_limit), within._h if within is not None else None, int(pool),
                                                        modes[mode], float(param), _ptr(rows), _ptr(scores), _ptr(counts), _ptr(ranks)))
         return rows, scores, counts, ranks
+
+    def keys(self, row_ids, keys) -> RecallClusterKeys:
+        """orr_cluster_keys_create: a key column over every shard, every row at KEY_NONE, then RecallClusterKeys.set(row_ids,
+        keys).  numpy, host memory."""
+        ids, ks, n = RecallClusterKeys._pairs(row_ids, keys)
+        h = C.c_void_p()
+        N.check(N.hip.orr_cluster_keys_create(self._h, n, _ptr(ids) if n else None, _ptr(ks) if n else None, C.byref(h)))
+        return RecallClusterKeys(h, self)
+
+    def scope_keys(self, keys_handle: RecallClusterKeys, keys) -> RecallClusterScope:
+        """orr_cluster_scope_create_keys: the live rows whose key is one of `keys` (host int64, at most 65,536), on every shard:
+        an ordinary RecallClusterScope."""
+        ks = np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)
+        n = int(ks.shape[0])
+        h = C.c_void_p()
+        N.check(N.hip.orr_cluster_scope_create_keys(self._h, keys_handle._h, n, _ptr(ks) if n else None, C.byref(h)))
+        return RecallClusterScope(h, self)
+
+    def search_per_key(self, qvecs, queries_terms, now_ticks: int, topk: int, keys: RecallClusterKeys, max_per_key: int = 1, pool: int = 24,
+                       within: Optional[RecallClusterScope] = None, candidate_limit: int = 300):
+        """orr_cluster_search_batch_per_key: RecallIndex.search_per_key over all shards, as one index holding all the rows would
+        answer -- a key closes cluster-wide, and the call looks outside the pool on every shard.  qvecs in host memory (numpy)
+        or None.  Returns (rows [B,k] int64, fused scores [B,k] float64, keys [B,k] int64, counts [B] int32, rounds [B] int32)."""
+        B = len(queries_terms)
+        dim, q = self._host_query_args(qvecs, B)
+        tpool, toff, qoff = pack_terms(queries_terms)
+        k = max(1, int(topk))
+        rows = np.full((B, k), -1, dtype=np.int64)
+        scores = np.zeros((B, k), dtype=np.float64)
+        rkeys = np.full((B, k), N.ORR_KEY_NONE, dtype=np.int64)
+        counts = np.zeros(B, dtype=np.int32)
+        rounds = np.zeros(B, dtype=np.int32)
+        N.check(N.hip.orr_cluster_search_batch_per_key(self._h, B, dim, _ptr(q), _ptr(tpool), _ptr(toff), _ptr(qoff), now_ticks, int(topk),
+                                                       int(candidate_limit), within._h if within is not None else None, keys._h,
+                                                       int(max_per_key), int(pool), _ptr(rows), _ptr(scores), _ptr(rkeys), _ptr(counts),
+                                                       _ptr(rounds)))
+        return rows, scores, rkeys, counts, rounds
 
     def pair_dots(self, lists) -> np.ndarray:
         """orr_cluster_pair_dots: RecallIndex.pair_dots over all shards; the lists hold GLOBAL order keys (a shard's row_base +
