@@ -762,6 +762,54 @@ int orr_search_batch_per_key(orr_index *idx, int32_t B, int32_t dim, const float
                              int64_t *out_rows, double *out_scores, int64_t *out_keys, int32_t *out_counts,
                              int32_t *out_rounds /* [B], may be NULL */);
 
+/* ---- key groups: row counts and centroid vectors per key, on the device -----------------------------------------------------
+ * The calls above read a key from the document to its rows (a cap, a filter).  These read it the other way round: which keys a
+ * set of rows carries and how many rows each (the facet list of a scope, with no id crossing the bus), and one vector per key,
+ * the mean of its rows' fp32 embeddings ("documents like this one", routing, a document-level index, a probe for
+ * orr_scope_create_near).  The rules are csrc/orr_key_groups_plan.h's.
+ *
+ * THE RULE, bit for bit.  The MEMBERS of key K are the live rows r with key[r] == K, inside `within` when a scope is given, in
+ * candidate order (position ascending).  The PARTICIPATING members are those whose stored norm satisfies normB > 0.0: rows
+ * without an embedding, zero vectors and rows whose norm is NaN take no part; rows with an infinite norm do.  Let
+ * u_0 < u_1 < ... < u_{n-1} be the participating members, cut into BLOCKS OF 256 consecutive members (ORR_KEY_GROUPS_BLOCK ==
+ * key_groups::kBlock: part of the contract, the bits depend on it):
+ *     P_j[d] = (((+0.0 + (double)e[u_{256j}][d]) + (double)e[u_{256j+1}][d]) + ...)     fp64, in this order
+ *     S[d]   = (((+0.0 + P_0[d]) + P_1[d]) + ...)                                       fp64, in block order
+ *     c[d]   = (float)(S[d] / (double)n)    on the HOST, IEEE division, round to nearest even; n == 0: c[d] = +0.0f, S[d] = +0.0
+ * The device forms S with plain fp64 adds (no FMA, no reassociation); infinities and NaN coordinates follow IEEE.
+ *
+ *   orr_keys_groups     the distinct keys other than ORR_KEY_NONE among the members, ascending as signed integers; out_rows = each
+ *                       key's member count (ALL members, not only the participating ones); *out_total = the distinct keys,
+ *                       *out_n = min(*out_total, cap) entries written.  cap == 0 asks for the total only (the arrays may be NULL).
+ *   orr_keys_centroids  n_keys 0 .. 65,536 (0 writes nothing); listing ORR_KEY_NONE asks for the rows without a key; a key listed
+ *                       twice is answered twice; a key with no participating member gives zeros and out_used 0.  out_used[i] = n.
+ *                       dim must be the index's and greater than 0, else ORR_EDIM.  The fp64 sums are formed in slices of keys
+ *                       (64 MiB of sums; sticky option "key_groups_slice": 0 this rule, 1 .. 65,536 keys per slice; the bits do
+ *                       not depend on it).
+ *   orr_scope_centroid  all rows of the scope as ONE group, under the same rule and with the same kernels.
+ * Kernels: keys_pairs_count / keys_pairs (one pass each over the rows: the selected rows compacted, order kept, by ballot and
+ * prefix), hipCUB's stable radix sort and run-length encode, keys_block_sums (one workgroup per block; reads each participating
+ * row once) and keys_block_fold (keys of several blocks).  No atomics decide an order.
+ * ORR_EINVAL before any handle is looked at, the outputs untouched, in this order -- groups: cap negative; out_n or out_total
+ * NULL; out_keys or out_rows NULL with cap > 0; keys NULL.  centroids: n_keys outside its range; keys NULL with n_keys > 0;
+ * out_used NULL with n_keys > 0; the keys handle NULL.  scope_centroid: out_used NULL; the scope NULL.  Then ORR_EINVAL for a
+ * scope of another shard, ORR_ESTATE for an orphaned handle, ORR_EDIM.  Lifetime and threads are orr_keys_get's: the call takes
+ * a lane, holds keys and scope shared and works through views.  The search statistics do not move; every launch appears in the
+ * kernel statistics under its own name.
+ * Out of scope: the cluster forms (a document cut by a shard border would need the blocked order defined across shards;
+ * orr_cluster_keys_shard lets a host ask each shard meanwhile, but such per-shard sums ARE NOT the single index's bits), a mean
+ * of unit-normalised rows or a weighted mean, sharded.py, the service mirror and the micro-batcher, keys in the shard file, a
+ * search call that ranks documents by centroid. */
+#define ORR_KEY_GROUPS_BLOCK 256
+int orr_keys_groups(orr_keys *k, const orr_scope *within /* or NULL */, int64_t cap,
+                    int64_t *out_keys /* host [cap] */, int64_t *out_rows /* host [cap] */,
+                    int64_t *out_n, int64_t *out_total);
+int orr_keys_centroids(orr_keys *k, const orr_scope *within /* or NULL */, int32_t n_keys, const int64_t *keys /* host */,
+                       int32_t dim, float *out_centroids /* host [n_keys][dim], may be NULL */,
+                       double *out_sums /* host [n_keys][dim], may be NULL */, int64_t *out_used /* host [n_keys] */);
+int orr_scope_centroid(orr_scope *s, int32_t dim, float *out_centroid /* host [dim], may be NULL */,
+                       double *out_sum /* host [dim], may be NULL */, int64_t *out_used);
+
 /* orr_search_shard_masked with the scope taken from a handle: the record form of orr_search_batch_in_scope, the shard half of
  * orr_cluster_search_batch_in_scope.  The contract is orr_search_shard_masked's, unchanged: [B][kprime+1] records and the
  * trailer, `pass` 0 / 1, topk, candidate_limit GLOBAL with scope_before the scope's live rows on the shards in front (read

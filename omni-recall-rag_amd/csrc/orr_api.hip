@@ -311,6 +311,7 @@ struct orr_index {
     std::vector<orr_keys *> key_cols;
     int opt_mask_screen = 0;          // "mask_screen": 0 by the cost rule, 1 whenever eligible, 2 never (orr_mask_plan.h)
     int64_t opt_mask_part_rows = mask::kDefaultPartRows;   // "mask_part_rows": scoped rows per part of the list path
+    int64_t opt_key_groups_slice = 0;                      // "key_groups_slice": keys per slice of orr_keys_centroids' sums; 0 by key_groups::slice_keys
 
     // search workspace
     DevBuf ws_q, ws_dot, ws_dotf, ws_sel, ws_cand, ws_qc, ws_rowc, ws_tau, ws_qsplit, ws_fcnt, ws_fbuf, ws_fqf, ws_fany, ws_tsL, ws_tskey, ws_qtiled, ws_fdot, ws_pbuf, ws_psel, ws_q8, ws_q8s1, ws_q8err, ws_zero, ws_norm_a;
@@ -2153,6 +2154,7 @@ static void copy_options(const orr_index *from, orr_index *to)
     to->near_band_cap = from->near_band_cap;
     to->opt_range_form = from->opt_range_form; to->opt_range_gemm = from->opt_range_gemm; to->opt_range_pair_cap = from->opt_range_pair_cap;
     to->range_buffer = from->range_buffer; to->range_list_cap = from->range_list_cap;
+    to->opt_key_groups_slice = from->opt_key_groups_slice;
 }
 
 // a lane borrows whatever shadows its index has now
@@ -2207,6 +2209,9 @@ int orr_index_set_option(orr_index *idx, const char *name, int64_t value)
         if (!range::buffer_valid(value)) return fail(ORR_EINVAL, "orr_index_set_option: range_buffer must be in 1 .. %lld", (long long)range::kMaxBuffer);
         idx->range_buffer = value;
         idx->range_list_cap = 0;
+    } else if (strcmp(name, "key_groups_slice") == 0) {
+        if (!key_groups::slice_option_valid(value)) return fail(ORR_EINVAL, "orr_index_set_option: key_groups_slice must be in 0 .. %d", key_groups::kMaxKeys);
+        idx->opt_key_groups_slice = value;
     } else if (strcmp(name, "range_gemm") == 0) {
         if (!range_bulk::gemm_valid(value)) return fail(ORR_EINVAL, "orr_index_set_option: range_gemm takes 0, 1 or 2");
         idx->opt_range_gemm = (int)value;
@@ -7384,6 +7389,352 @@ int orr_scope_create_keys(orr_index *idx, const orr_keys *k, int32_t n_keys, con
         tab.release();
         return r;
     });
+}
+
+// ---- key groups (orr_keys_groups, orr_keys_centroids, orr_scope_centroid; the rules are orr_key_groups_plan.h's) ---------------
+
+static_assert(key_groups::kMaxKeys == per_key::kMaxScopeKeys, "orr_keys_centroids lists as many keys as orr_scope_create_keys");
+static_assert(key_groups::kBlock == ORR_KEY_GROUPS_BLOCK, "the header states the block of the sum");
+
+namespace {
+
+// What one key-groups call owns on the device; everything goes with the call.
+struct KeyGroupsWork {
+    DevBuf live_bm, tab, counts, offsets, key_a, key_b, pos_a, pos_b, tmp, run_key, run_len, run_n, blocks, folds, sums, parts;
+    const uint32_t *pos = nullptr;                     // the pairs' positions in their final order
+    const uint64_t *key = nullptr;                     // ... and their keys (modes 0 and 1)
+    ~KeyGroupsWork()
+    {
+        for (DevBuf *b : {&live_bm, &tab, &counts, &offsets, &key_a, &key_b, &pos_a, &pos_b, &tmp, &run_key, &run_len, &run_n, &blocks, &folds, &sums, &parts})
+            b->release();
+    }
+};
+
+// The call's selected rows as pairs in candidate order (launch_keys_pairs: mode 0 the rows with a key, 1 the participating rows
+// whose key is in `table`, 2 the participating rows of `within`), sorted by key for modes 0 and 1 (stable: positions stay
+// ascending within a key).  *out_m = their number; ends synchronised.
+int key_groups_pairs(orr_index *lane, const orr_keys *k, const orr_scope *within, int32_t mode, const std::vector<int64_t> *table,
+                     KeyGroupsWork &w, int64_t *out_m)
+{
+    *out_m = 0;
+    const orr_index *own = owner_of(lane);
+    hipStream_t s = lane->stream;
+    const int64_t n = lane->n_rows;
+    if (n <= 0) return ORR_OK;
+    if (n > (int64_t)0x7FFFFFFF) return fail(ORR_ELIMIT, "key groups: a shard of %lld rows is beyond 2^31 - 1", (long long)n);
+    const uint32_t *bm = nullptr;
+    int64_t words = 0;
+    if (within) {
+        bm = within->bm; words = within->words;
+    } else {                                           // the live rows
+        words = (int64_t)(scope::bitmap_bytes(n) / 4);
+        ORR_TRY(w.live_bm.reserve(sizeof(uint32_t) * (size_t)words));
+        {
+            Timed t(lane, "scope_fill_range", 4.0 * (double)words);
+            HIP_TRY(orr::launch_scope_fill_range(w.live_bm.as<uint32_t>(), words, 0, n, s));
+        }
+        {
+            Timed t(lane, "scope_clear_positions", 12.0 * (double)own->dead.size());
+            HIP_TRY(orr::launch_scope_clear_positions(w.live_bm.as<uint32_t>(), words, own->d_dead.as<int64_t>(), (int64_t)own->dead.size(), s));
+        }
+        bm = w.live_bm.as<uint32_t>();
+    }
+    const int32_t n_tab = table ? (int32_t)table->size() : 0;
+    if (mode == 1) {
+        ORR_TRY(w.tab.reserve(sizeof(int64_t) * (size_t)n_tab));
+        HIP_TRY(hipMemcpyAsync(w.tab.p, table->data(), sizeof(int64_t) * (size_t)n_tab, hipMemcpyHostToDevice, s));
+    }
+    const int64_t *d_key = k ? k->d_key : nullptr;
+    const int64_t nb = orr::key_groups_pair_blocks(n);
+    ORR_TRY(w.counts.reserve(sizeof(uint32_t) * (size_t)(nb + 1)));
+    ORR_TRY(w.offsets.reserve(sizeof(uint32_t) * (size_t)(nb + 1)));
+    HIP_TRY(hipMemsetAsync(w.counts.as<uint32_t>() + nb, 0, sizeof(uint32_t), s));      // the closing entry: its offset is the total
+    const double pass_bytes = (mode == 2 ? 8.0 : 16.0) * (double)n + 4.0 * (double)words;
+    {
+        Timed t(lane, "keys_pairs_count", pass_bytes);
+        HIP_TRY(orr::launch_keys_pairs(mode, false, d_key, lane->d_norm_b, n, bm, words, w.tab.as<int64_t>(), n_tab, w.counts.as<uint32_t>(), nullptr, 0,
+                                       nullptr, nullptr, s));
+    }
+    size_t tmp_bytes = 0;
+    HIP_TRY(orr::keys_pairs_scan(nullptr, tmp_bytes, w.counts.as<uint32_t>(), w.offsets.as<uint32_t>(), nb + 1, s));
+    ORR_TRY(w.tmp.reserve(std::max<size_t>(tmp_bytes, 16)));
+    {
+        Timed t(lane, "keys_pairs_scan", 8.0 * (double)(nb + 1));
+        HIP_TRY(orr::keys_pairs_scan(w.tmp.p, tmp_bytes, w.counts.as<uint32_t>(), w.offsets.as<uint32_t>(), nb + 1, s));
+    }
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, w.offsets.as<uint32_t>() + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const int64_t m = (int64_t)total;
+    if (m > n) return fail(ORR_EDEVICE, "key groups: %lld pairs of %lld rows", (long long)m, (long long)n);
+    *out_m = m;
+    if (m == 0) return ORR_OK;
+    ORR_TRY(w.pos_a.reserve(sizeof(uint32_t) * (size_t)m));
+    if (mode != 2) ORR_TRY(w.key_a.reserve(sizeof(uint64_t) * (size_t)m));
+    {
+        Timed t(lane, "keys_pairs", pass_bytes + (mode == 2 ? 4.0 : 12.0) * (double)m);
+        HIP_TRY(orr::launch_keys_pairs(mode, true, d_key, lane->d_norm_b, n, bm, words, w.tab.as<int64_t>(), n_tab, nullptr, w.offsets.as<uint32_t>(), m,
+                                       w.key_a.as<uint64_t>(), w.pos_a.as<uint32_t>(), s));
+    }
+    w.pos = w.pos_a.as<uint32_t>();
+    w.key = w.key_a.as<uint64_t>();
+    if (mode == 2) return ORR_OK;
+    ORR_TRY(w.pos_b.reserve(sizeof(uint32_t) * (size_t)m));
+    ORR_TRY(w.key_b.reserve(sizeof(uint64_t) * (size_t)m));
+    const int32_t end_bit = mode == 1 ? key_groups::table_bits(n_tab) : 64;
+    tmp_bytes = 0;
+    HIP_TRY(orr::keys_pairs_sort(nullptr, tmp_bytes, w.key_a.as<uint64_t>(), w.key_b.as<uint64_t>(), w.pos_a.as<uint32_t>(), w.pos_b.as<uint32_t>(), m, end_bit, s));
+    ORR_TRY(w.tmp.reserve(std::max<size_t>(tmp_bytes, 16)));
+    {
+        Timed t(lane, "keys_pairs_sort", 24.0 * (double)m * (double)((end_bit + 7) / 8));
+        HIP_TRY(orr::keys_pairs_sort(w.tmp.p, tmp_bytes, w.key_a.as<uint64_t>(), w.key_b.as<uint64_t>(), w.pos_a.as<uint32_t>(), w.pos_b.as<uint32_t>(), m, end_bit, s));
+    }
+    w.pos = w.pos_b.as<uint32_t>();
+    w.key = w.key_b.as<uint64_t>();
+    return ORR_OK;
+}
+
+// The runs of the sorted pairs' keys: run_key / run_len on the device, *out_runs their number; ends synchronised.
+int key_groups_runs(orr_index *lane, KeyGroupsWork &w, int64_t m, int64_t *out_runs)
+{
+    hipStream_t s = lane->stream;
+    *out_runs = 0;
+    if (m <= 0) return ORR_OK;
+    ORR_TRY(w.run_key.reserve(sizeof(uint64_t) * (size_t)m));
+    ORR_TRY(w.run_len.reserve(sizeof(uint32_t) * (size_t)m));
+    ORR_TRY(w.run_n.reserve(sizeof(uint32_t)));
+    size_t tmp_bytes = 0;
+    HIP_TRY(orr::keys_pairs_runs(nullptr, tmp_bytes, w.key, w.run_key.as<uint64_t>(), w.run_len.as<uint32_t>(), w.run_n.as<uint32_t>(), m, s));
+    ORR_TRY(w.tmp.reserve(std::max<size_t>(tmp_bytes, 16)));
+    {
+        Timed t(lane, "keys_runs", 8.0 * (double)m);
+        HIP_TRY(orr::keys_pairs_runs(w.tmp.p, tmp_bytes, w.key, w.run_key.as<uint64_t>(), w.run_len.as<uint32_t>(), w.run_n.as<uint32_t>(), m, s));
+    }
+    uint32_t runs = 0;
+    HIP_TRY(hipMemcpyAsync(&runs, w.run_n.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if ((int64_t)runs > m) return fail(ORR_EDEVICE, "key groups: %u runs of %lld pairs", runs, (long long)m);
+    *out_runs = (int64_t)runs;
+    return ORR_OK;
+}
+
+// One slice's sums: the blocks and folds brought to the device, keys_block_sums, keys_block_fold where a key has several
+// blocks, the n_slots x dim sums back in `host` (a key without a block reads +0.0).  Ends synchronised.
+int key_groups_slice_sums(orr_index *lane, KeyGroupsWork &w, int32_t n_slots, const std::vector<key_groups::Block> &blocks,
+                          const std::vector<key_groups::Fold> &folds, uint32_t n_parts, double *host)
+{
+    hipStream_t s = lane->stream;
+    const int32_t dim = lane->dim;
+    const size_t sum_bytes = sizeof(double) * (size_t)n_slots * (size_t)dim;
+    if (blocks.empty()) { memset(host, 0, sum_bytes); return ORR_OK; }
+    ORR_TRY(w.sums.reserve(sum_bytes));
+    ORR_TRY(w.blocks.reserve(sizeof(key_groups::Block) * blocks.size()));
+    if (n_parts) ORR_TRY(w.parts.reserve(sizeof(double) * (size_t)n_parts * (size_t)dim));
+    if (!folds.empty()) ORR_TRY(w.folds.reserve(sizeof(key_groups::Fold) * folds.size()));
+    HIP_TRY(hipMemsetAsync(w.sums.p, 0, sum_bytes, s));
+    HIP_TRY(hipMemcpyAsync(w.blocks.p, blocks.data(), sizeof(key_groups::Block) * blocks.size(), hipMemcpyHostToDevice, s));
+    if (!folds.empty()) HIP_TRY(hipMemcpyAsync(w.folds.p, folds.data(), sizeof(key_groups::Fold) * folds.size(), hipMemcpyHostToDevice, s));
+    double rows = 0.0;
+    for (const key_groups::Block &b : blocks) rows += (double)b.len;
+    {
+        Timed t(lane, "keys_block_sums", 4.0 * rows * (double)dim + 8.0 * (double)blocks.size() * (double)dim);
+        HIP_TRY(orr::launch_keys_block_sums(lane->d_emb, lane->n_rows, dim, w.pos, w.blocks.as<key_groups::Block>(), (int64_t)blocks.size(),
+                                            w.sums.as<double>(), w.parts.as<double>(), s));
+    }
+    if (!folds.empty()) {
+        Timed t(lane, "keys_block_fold", 8.0 * ((double)n_parts + (double)folds.size()) * (double)dim);
+        HIP_TRY(orr::launch_keys_block_fold(w.folds.as<key_groups::Fold>(), (int64_t)folds.size(), w.parts.as<double>(), dim, w.sums.as<double>(), s));
+    }
+    HIP_TRY(hipMemcpyAsync(host, w.sums.p, sum_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));                  // (the host's blocks and folds go with this frame)
+    return ORR_OK;
+}
+
+// `within` beside the keys of shard `own`, behind the lane's lock and both handles' shared locks
+int key_groups_check_scope(const orr_scope *within, const orr_index *lane, const char *fn)
+{
+    if (!within) return ORR_OK;
+    orr_index *sown = nullptr;
+    ORR_TRY(scope_owner(within, lane, fn, &sown));
+    if (within->n_rows != lane->n_rows)
+        return fail(ORR_ESTATE, "%s: the scope covers %lld rows, the handle %lld", fn, (long long)within->n_rows, (long long)lane->n_rows);
+    return ORR_OK;
+}
+
+}  // namespace
+
+int orr_keys_groups(orr_keys *k, const orr_scope *within, int64_t cap, int64_t *out_keys, int64_t *out_rows, int64_t *out_n, int64_t *out_total)
+{
+    static const char *fn = "orr_keys_groups";
+    switch (key_groups::first_invalid_groups(cap, !out_keys, !out_rows, !out_n, !out_total, !k)) {
+    case 0: break;
+    case 1: return fail(ORR_EINVAL, "%s: cap is negative", fn);
+    case 2: return fail(ORR_EINVAL, "%s: out_n or out_total is NULL", fn);
+    case 3: return fail(ORR_EINVAL, "%s: out_keys or out_rows is NULL with room for %lld keys", fn, (long long)cap);
+    default: return fail(ORR_EINVAL, "%s: null keys", fn);
+    }
+    orr_index *own = nullptr;
+    ORR_TRY(keys_owner(k, nullptr, fn, &own));
+    Lane ln = acquire_lane(own);
+    orr_index *lane = ln.lane;
+    std::lock_guard<std::mutex> lock(lane->mu);
+    std::shared_lock<std::shared_mutex> rs;                            // the scope first, then the keys, as orr_search_batch_per_key
+    if (within) rs = std::shared_lock<std::shared_mutex>(within->mu);
+    std::shared_lock<std::shared_mutex> rd(k->mu);
+    if (within) ORR_TRY(key_groups_check_scope(within, own, fn));      // (another shard: ORR_EINVAL; orphaned: ORR_ESTATE)
+    ORR_TRY(keys_owner(k, nullptr, fn, &own));
+    if (k->n_rows != lane->n_rows) return fail(ORR_ESTATE, "%s: the keys cover %lld rows, the handle %lld", fn, (long long)k->n_rows, (long long)lane->n_rows);
+    ORR_TRY(bind_device(lane));
+    hipStream_t s = lane->stream;
+    KeyGroupsWork w;
+    int64_t runs = 0;
+    auto body = [&]() -> int {
+        int64_t m = 0;
+        ORR_TRY(key_groups_pairs(lane, k, within, 0, nullptr, w, &m));
+        ORR_TRY(key_groups_runs(lane, w, m, &runs));
+        const int64_t take = std::min(runs, cap);
+        if (take > 0) {
+            std::vector<uint32_t> len((size_t)take);
+            HIP_TRY(hipMemcpyAsync(out_keys, w.run_key.p, sizeof(uint64_t) * (size_t)take, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(len.data(), w.run_len.p, sizeof(uint32_t) * (size_t)take, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            for (int64_t i = 0; i < take; ++i) {
+                out_keys[i] = key_groups::key_of_sort((uint64_t)out_keys[i]);
+                out_rows[i] = (int64_t)len[(size_t)i];
+            }
+        }
+        return ORR_OK;
+    };
+    const int r = body();
+    (void)hipStreamSynchronize(s);
+    collect_events(lane);
+    if (r != ORR_OK) return r;
+    *out_total = runs;
+    *out_n = std::min(runs, cap);
+    return ORR_OK;
+}
+
+int orr_keys_centroids(orr_keys *k, const orr_scope *within, int32_t n_keys, const int64_t *keys, int32_t dim, float *out_centroids,
+                       double *out_sums, int64_t *out_used)
+{
+    static const char *fn = "orr_keys_centroids";
+    switch (key_groups::first_invalid_centroids(n_keys, !keys, !out_used, !k)) {
+    case 0: break;
+    case 1: return fail(ORR_EINVAL, "%s: n_keys must be in 0 .. %d", fn, key_groups::kMaxKeys);
+    case 2: return fail(ORR_EINVAL, "%s: keys is NULL with %d keys", fn, n_keys);
+    case 3: return fail(ORR_EINVAL, "%s: out_used is NULL with %d keys", fn, n_keys);
+    default: return fail(ORR_EINVAL, "%s: null keys", fn);
+    }
+    orr_index *own = nullptr;
+    ORR_TRY(keys_owner(k, nullptr, fn, &own));
+    Lane ln = acquire_lane(own);
+    orr_index *lane = ln.lane;
+    std::lock_guard<std::mutex> lock(lane->mu);
+    std::shared_lock<std::shared_mutex> rs;                            // the scope first, then the keys, as orr_search_batch_per_key
+    if (within) rs = std::shared_lock<std::shared_mutex>(within->mu);
+    std::shared_lock<std::shared_mutex> rd(k->mu);
+    if (within) ORR_TRY(key_groups_check_scope(within, own, fn));
+    ORR_TRY(keys_owner(k, nullptr, fn, &own));
+    if (k->n_rows != lane->n_rows) return fail(ORR_ESTATE, "%s: the keys cover %lld rows, the handle %lld", fn, (long long)k->n_rows, (long long)lane->n_rows);
+    if (dim <= 0 || dim != lane->dim) return fail(ORR_EDIM, "%s: dim %d differs from the index dimension %d (and must be greater than 0)", fn, dim, lane->dim);
+    if (n_keys == 0) return ORR_OK;
+    ORR_TRY(bind_device(lane));
+    hipStream_t s = lane->stream;
+    // the sorted table of the distinct keys listed; the listed keys in the table's order (a key listed twice is answered twice)
+    const std::vector<int64_t> table = per_key::member_table(keys, n_keys);
+    const int32_t T = (int32_t)table.size();
+    std::vector<int32_t> slot_of((size_t)n_keys), by_slot((size_t)n_keys);
+    for (int32_t i = 0; i < n_keys; ++i) { slot_of[(size_t)i] = per_key::table_find(table.data(), T, keys[i]); by_slot[(size_t)i] = i; }
+    std::stable_sort(by_slot.begin(), by_slot.end(), [&](int32_t a, int32_t b) { return slot_of[(size_t)a] < slot_of[(size_t)b]; });
+    KeyGroupsWork w;
+    std::vector<int64_t> first((size_t)T, 0), count((size_t)T, 0);
+    std::vector<double> sums;
+    std::vector<float> cent((size_t)dim);
+    auto body = [&]() -> int {
+        int64_t m = 0, runs = 0;
+        ORR_TRY(key_groups_pairs(lane, k, within, 1, &table, w, &m));
+        ORR_TRY(key_groups_runs(lane, w, m, &runs));
+        if (runs > T) return fail(ORR_EDEVICE, "%s: %lld runs of %d keys", fn, (long long)runs, T);
+        if (runs > 0) {
+            std::vector<uint64_t> rk((size_t)runs);
+            std::vector<uint32_t> rl((size_t)runs);
+            HIP_TRY(hipMemcpyAsync(rk.data(), w.run_key.p, sizeof(uint64_t) * (size_t)runs, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(rl.data(), w.run_len.p, sizeof(uint32_t) * (size_t)runs, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            int64_t at = 0;
+            for (int64_t i = 0; i < runs; ++i) {
+                if (rk[(size_t)i] >= (uint64_t)T || at + (int64_t)rl[(size_t)i] > m) return fail(ORR_EDEVICE, "%s: a run outside the table", fn);
+                first[(size_t)rk[(size_t)i]] = at;
+                count[(size_t)rk[(size_t)i]] = (int64_t)rl[(size_t)i];
+                at += (int64_t)rl[(size_t)i];
+            }
+        }
+        const int32_t per_slice = key_groups::slice_keys(dim, lane->opt_key_groups_slice);
+        sums.resize((size_t)std::min(per_slice, T) * (size_t)dim);
+        std::vector<key_groups::Block> blocks;
+        std::vector<key_groups::Fold> folds;
+        size_t next = 0;                               // of by_slot
+        for (int32_t s0 = 0; s0 < T; s0 += per_slice) {
+            const int32_t ns = std::min(per_slice, T - s0);
+            blocks.clear(); folds.clear();
+            uint32_t n_parts = 0;
+            for (int32_t j = 0; j < ns; ++j) key_groups::blocks_of(count[(size_t)(s0 + j)], first[(size_t)(s0 + j)], (uint32_t)j, blocks, folds, n_parts);
+            ORR_TRY(key_groups_slice_sums(lane, w, ns, blocks, folds, n_parts, sums.data()));
+            for (; next < by_slot.size() && slot_of[(size_t)by_slot[next]] < s0 + ns; ++next) {
+                const int32_t i = by_slot[next], j = slot_of[(size_t)i] - s0;
+                const double *S = sums.data() + (size_t)j * (size_t)dim;
+                const int64_t used = count[(size_t)(s0 + j)];
+                out_used[i] = used;
+                if (out_sums) memcpy(out_sums + (size_t)i * (size_t)dim, S, sizeof(double) * (size_t)dim);
+                if (out_centroids) key_groups::finish(S, used, dim, out_centroids + (size_t)i * (size_t)dim);
+            }
+        }
+        return ORR_OK;
+    };
+    const int r = body();
+    (void)hipStreamSynchronize(s);
+    collect_events(lane);
+    return r;
+}
+
+int orr_scope_centroid(orr_scope *sc, int32_t dim, float *out_centroid, double *out_sum, int64_t *out_used)
+{
+    static const char *fn = "orr_scope_centroid";
+    switch (key_groups::first_invalid_scope_centroid(!out_used, !sc)) {
+    case 0: break;
+    case 1: return fail(ORR_EINVAL, "%s: out_used is NULL", fn);
+    default: return fail(ORR_EINVAL, "%s: null scope", fn);
+    }
+    orr_index *own = nullptr;
+    ORR_TRY(scope_owner(sc, nullptr, fn, &own));
+    Lane ln = acquire_lane(own);
+    orr_index *lane = ln.lane;
+    std::lock_guard<std::mutex> lock(lane->mu);
+    std::shared_lock<std::shared_mutex> rd(sc->mu);
+    ORR_TRY(scope_owner(sc, nullptr, fn, &own));
+    if (sc->n_rows != lane->n_rows) return fail(ORR_ESTATE, "%s: the scope covers %lld rows, the handle %lld", fn, (long long)sc->n_rows, (long long)lane->n_rows);
+    if (dim <= 0 || dim != lane->dim) return fail(ORR_EDIM, "%s: dim %d differs from the index dimension %d (and must be greater than 0)", fn, dim, lane->dim);
+    ORR_TRY(bind_device(lane));
+    hipStream_t s = lane->stream;
+    KeyGroupsWork w;
+    std::vector<double> sum((size_t)dim, 0.0);
+    int64_t m = 0;
+    auto body = [&]() -> int {
+        ORR_TRY(key_groups_pairs(lane, nullptr, sc, 2, nullptr, w, &m));
+        std::vector<key_groups::Block> blocks;
+        std::vector<key_groups::Fold> folds;
+        uint32_t n_parts = 0;
+        key_groups::blocks_of(m, 0, 0u, blocks, folds, n_parts);
+        return key_groups_slice_sums(lane, w, 1, blocks, folds, n_parts, sum.data());
+    };
+    const int r = body();
+    (void)hipStreamSynchronize(s);
+    collect_events(lane);
+    if (r != ORR_OK) return r;
+    *out_used = m;
+    if (out_sum) memcpy(out_sum, sum.data(), sizeof(double) * (size_t)dim);
+    if (out_centroid) key_groups::finish(sum.data(), m, dim, out_centroid);
+    return ORR_OK;
 }
 
 namespace {

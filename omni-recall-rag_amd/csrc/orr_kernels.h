@@ -15,6 +15,7 @@
 #include "orr_range_plan.h"
 #include "orr_diverse_plan.h"
 #include "orr_per_key_plan.h"
+#include "orr_key_groups_plan.h"
 #include "orr_keyword_plan.h"
 
 #include <atomic>
@@ -507,6 +508,31 @@ hipError_t launch_keys_remap(const int64_t *src, int64_t first, int64_t n_new, c
 hipError_t launch_keys_fill_none(int64_t *key, int64_t n, hipStream_t s);
 // *out (device, zeroed by the caller) += the rows r < n_rows with a key that are not in dead[] (ascending).
 hipError_t launch_keys_count(const int64_t *key, int64_t n_rows, const int64_t *dead, int32_t n_dead, unsigned long long *out, hipStream_t s);
+
+// ---- key groups (orr_keys_groups, orr_keys_centroids, orr_scope_centroid; the rules are orr_key_groups_plan.h's) ---------------
+// workgroups (and entries of counts / offsets, without the closing one) of launch_keys_pairs over n_rows rows
+inline int64_t key_groups_pair_blocks(int64_t n_rows) { return (n_rows + 255) / 256; }
+// The selected rows of bm (words * 32 bits, bits at or above n_rows clear) as pairs in candidate order.  mode 0: rows with a key,
+// out_key = key_groups::sort_key(key); mode 1: rows whose norm participates and whose key is in tab_keys [n_tab] (ascending,
+// distinct), out_key = the key's index in the table; mode 2: rows whose norm participates, positions only.  write false: the
+// count pass, counts[key_groups_pair_blocks(n_rows)] written; write true: the pairs stored from offsets[] (the exclusive scan of
+// the counts) on, below cap.  No atomics.
+hipError_t launch_keys_pairs(int32_t mode, bool write, const int64_t *key, const double *norm_b, int64_t n_rows, const uint32_t *bm, int64_t words,
+                             const int64_t *tab_keys, int32_t n_tab, uint32_t *counts, const uint32_t *offsets, int64_t cap, uint64_t *out_key,
+                             uint32_t *out_pos, hipStream_t s);
+// hipCUB behind the pairs (temp NULL: temp_bytes is set): the exclusive scan of n counts; the stable radix sort of n pairs on the
+// key bits [0, end_bit); the runs of the sorted keys (run_key / run_len [n] at most, *n_runs their number).  n < 2^31.
+hipError_t keys_pairs_scan(void *temp, size_t &temp_bytes, const uint32_t *counts, uint32_t *offsets, int64_t n, hipStream_t s);
+hipError_t keys_pairs_sort(void *temp, size_t &temp_bytes, const uint64_t *key_in, uint64_t *key_out, const uint32_t *pos_in, uint32_t *pos_out,
+                           int64_t n, int32_t end_bit, hipStream_t s);
+hipError_t keys_pairs_runs(void *temp, size_t &temp_bytes, const uint64_t *key_sorted, uint64_t *run_key, uint32_t *run_len, uint32_t *n_runs,
+                           int64_t n, hipStream_t s);
+// One workgroup per block: the fp64 sums of rows emb[pos[first .. first + len)] (positions below n_rows), in this order from
+// +0.0, into row `slot` of sums [.][dim] (part == key_groups::kDirect) or row `part` of parts [.][dim].
+hipError_t launch_keys_block_sums(const float *emb, int64_t n_rows, int32_t dim, const uint32_t *pos, const key_groups::Block *blocks,
+                                  int64_t n_blocks, double *sums, double *parts, hipStream_t s);
+// sums[slot] = +0.0 + parts[part0] + ... + parts[part0 + n_blocks - 1], in this order, for each of the n_folds keys.
+hipError_t launch_keys_block_fold(const key_groups::Fold *folds, int64_t n_folds, const double *parts, int32_t dim, double *sums, hipStream_t s);
 
 // ---- term scopes (orr_scope_create_terms; the rules are orr_scope_terms_plan.h's) -------------------------------------------
 // term_base[t] (device, and its copy term_base_host in pinned memory when given) = where distinct term t's row bitmap starts, in

@@ -2478,6 +2478,207 @@ hipError_t launch_keys_count(const int64_t *key, int64_t n_rows, const int64_t *
     return hipGetLastError();
 }
 
+// ---- key groups (orr_keys_groups, orr_keys_centroids, orr_scope_centroid; the rules are orr_key_groups_plan.h's) ---------------
+// (The kernel functions are named key_groups_*: the keys_* kernels stay the key column's own.  Their launches appear in the
+// kernel statistics as keys_pairs_count, keys_pairs, keys_block_sums and keys_block_fold.)
+
+// One lane per row, two passes over the same selection.  A row is selected when its bit in bm is set (the live rows, or the
+// call's scope) and, by MODE, 0: it has a key (orr_keys_groups; the pair's key is key_groups::sort_key), 1: its norm participates
+// and its key is in the call's table (per_key::table_find, LDS or global as keys_member; the pair's key is the table index),
+// 2: its norm participates (orr_scope_centroid; positions only).  The count pass (WRITE false) leaves the workgroup's selected
+// rows in counts[blockIdx.x]; behind an exclusive scan of those the write pass compacts the pairs with the order kept: the
+// workgroup's offset, the waves in front (LDS), the lanes in front (ballot and prefix).  No atomics decide an order.
+template <int MODE, bool LDS, bool WRITE>
+__global__ __launch_bounds__(256) void key_groups_pairs_kernel(const int64_t *__restrict__ key, const double *__restrict__ norm_b, int64_t n_rows,
+                                                         const uint32_t *__restrict__ bm, const int64_t *__restrict__ tab_keys, int32_t n_tab,
+                                                         uint32_t *__restrict__ counts, const uint32_t *__restrict__ offsets, int64_t cap,
+                                                         uint64_t *__restrict__ out_key, uint32_t *__restrict__ out_pos)
+{
+    __shared__ int64_t sh_keys[(MODE == 1 && LDS) ? per_key::kLdsTable : 1];
+    __shared__ uint32_t wave_cnt[4];
+    const int tid = threadIdx.x;
+    if (MODE == 1 && LDS) {
+        for (int i = tid; i < n_tab; i += 256) sh_keys[i] = tab_keys[i];
+        __syncthreads();
+    }
+    const int64_t *tk = (MODE == 1 && LDS) ? sh_keys : tab_keys;
+    const int64_t r = (int64_t)blockIdx.x * 256 + tid;
+    bool sel = false;
+    uint64_t sk = 0;
+    if (r < n_rows && ((bm[r >> 5] >> (uint32_t)(r & 31)) & 1u)) {
+        if (MODE == 0) {
+            const int64_t k = key[r];
+            sel = k != per_key::kNone;
+            sk = key_groups::sort_key(k);
+        } else if (MODE == 1) {
+            if (key_groups::participates(norm_b[r])) {
+                const int32_t i = per_key::table_find(tk, n_tab, key[r]);
+                sel = i >= 0;
+                sk = (uint64_t)(uint32_t)i;
+            }
+        } else {
+            sel = key_groups::participates(norm_b[r]);
+        }
+    }
+    const unsigned long long bits = __ballot(sel);
+    const int wave = tid >> 6, lane = tid & 63;
+    if (lane == 0) wave_cnt[wave] = (uint32_t)__popcll(bits);
+    __syncthreads();
+    if (!WRITE) {
+        if (tid == 0) counts[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+        return;
+    }
+    int64_t at = offsets[blockIdx.x];
+    for (int w = 0; w < wave; ++w) at += wave_cnt[w];
+    at += __popcll(bits & ((1ull << lane) - 1ull));
+    if (sel && at < cap) {
+        if (MODE != 2) out_key[at] = sk;
+        out_pos[at] = (uint32_t)r;
+    }
+}
+
+template <int MODE, bool LDS>
+static hipError_t launch_keys_pairs_form(bool write, unsigned blocks, hipStream_t s, const int64_t *key, const double *norm_b, int64_t n_rows,
+                                         const uint32_t *bm, const int64_t *tab_keys, int32_t n_tab, uint32_t *counts, const uint32_t *offsets,
+                                         int64_t cap, uint64_t *out_key, uint32_t *out_pos)
+{
+    if (write)
+        hipLaunchKernelGGL((key_groups_pairs_kernel<MODE, LDS, true>), dim3(blocks), dim3(256), 0, s, key, norm_b, n_rows, bm, tab_keys, n_tab, counts,
+                           offsets, cap, out_key, out_pos);
+    else
+        hipLaunchKernelGGL((key_groups_pairs_kernel<MODE, LDS, false>), dim3(blocks), dim3(256), 0, s, key, norm_b, n_rows, bm, tab_keys, n_tab, counts,
+                           offsets, cap, out_key, out_pos);
+    return hipGetLastError();
+}
+
+hipError_t launch_keys_pairs(int32_t mode, bool write, const int64_t *key, const double *norm_b, int64_t n_rows, const uint32_t *bm, int64_t words,
+                             const int64_t *tab_keys, int32_t n_tab, uint32_t *counts, const uint32_t *offsets, int64_t cap, uint64_t *out_key,
+                             uint32_t *out_pos, hipStream_t s)
+{
+    if (n_rows <= 0) return hipSuccess;
+    if (mode < 0 || mode > 2 || !bm || n_rows > words * 32 || n_rows > (int64_t)0xFFFFFFFFll || (mode != 2 && !key) || (mode != 0 && !norm_b) ||
+        (mode == 1 && (n_tab <= 0 || !tab_keys)) || (!write && !counts) || (write && (!offsets || !out_pos || cap <= 0 || (mode != 2 && !out_key))))
+        return hipErrorInvalidValue;
+    const unsigned blocks = (unsigned)key_groups_pair_blocks(n_rows);
+    if (mode == 0) return launch_keys_pairs_form<0, false>(write, blocks, s, key, norm_b, n_rows, bm, tab_keys, n_tab, counts, offsets, cap, out_key, out_pos);
+    if (mode == 2) return launch_keys_pairs_form<2, false>(write, blocks, s, key, norm_b, n_rows, bm, tab_keys, n_tab, counts, offsets, cap, out_key, out_pos);
+    if (per_key::table_in_lds(n_tab))
+        return launch_keys_pairs_form<1, true>(write, blocks, s, key, norm_b, n_rows, bm, tab_keys, n_tab, counts, offsets, cap, out_key, out_pos);
+    return launch_keys_pairs_form<1, false>(write, blocks, s, key, norm_b, n_rows, bm, tab_keys, n_tab, counts, offsets, cap, out_key, out_pos);
+}
+
+hipError_t keys_pairs_scan(void *temp, size_t &temp_bytes, const uint32_t *counts, uint32_t *offsets, int64_t n, hipStream_t s)
+{
+    return hipcub::DeviceScan::ExclusiveSum(temp, temp_bytes, counts, offsets, (int)n, s);
+}
+
+hipError_t keys_pairs_sort(void *temp, size_t &temp_bytes, const uint64_t *key_in, uint64_t *key_out, const uint32_t *pos_in, uint32_t *pos_out,
+                           int64_t n, int32_t end_bit, hipStream_t s)
+{
+    // (a stable radix sort: equal keys keep their positions ascending)
+    return hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, key_in, key_out, pos_in, pos_out, (int)n, 0, end_bit, s);
+}
+
+hipError_t keys_pairs_runs(void *temp, size_t &temp_bytes, const uint64_t *key_sorted, uint64_t *run_key, uint32_t *run_len, uint32_t *n_runs,
+                           int64_t n, hipStream_t s)
+{
+    return hipcub::DeviceRunLengthEncode::Encode(temp, temp_bytes, key_sorted, run_key, run_len, n_runs, (int)n, s);
+}
+
+// The hot path: one workgroup per block of at most key_groups::kBlock participating members.  The block's positions are staged
+// in LDS; a lane owns four consecutive coordinates per 1,024 (one 16-byte load per row where dim % 4 == 0, four guarded 4-byte
+// loads otherwise), so a wave reads 1 KB of a row at a time, fully coalesced.  Eight rows' loads are issued before the first is
+// used; the fp64 adds are taken strictly in member order, from +0.0 (key_groups::sum_blocked's P_j).  A key of one block writes
+// its row of the sums, any other block its row of the partials.
+template <bool VEC>
+__global__ __launch_bounds__(256) void key_groups_block_sums_kernel(const float *__restrict__ emb, int32_t dim, const uint32_t *__restrict__ pos,
+                                                              const key_groups::Block *__restrict__ blocks, double *__restrict__ sums,
+                                                              double *__restrict__ parts)
+{
+    __shared__ uint32_t sh_pos[key_groups::kBlock];
+    const key_groups::Block b = blocks[blockIdx.x];
+    const int tid = threadIdx.x;
+    if ((uint32_t)tid < b.len) sh_pos[tid] = pos[(size_t)b.first + tid];
+    __syncthreads();
+    double *out = b.part == key_groups::kDirect ? sums + (size_t)b.slot * dim : parts + (size_t)b.part * dim;
+    for (int32_t d0 = tid * key_groups::kCoordsPerLane; d0 < dim; d0 += key_groups::kCoordsPerPass) {
+        double a0 = +0.0, a1 = +0.0, a2 = +0.0, a3 = +0.0;
+        const bool in1 = d0 + 1 < dim, in2 = d0 + 2 < dim, in3 = d0 + 3 < dim;
+        auto load = [&](uint32_t i) -> float4 {
+            const float *row = emb + (size_t)sh_pos[i] * dim + d0;
+            if (VEC) return *reinterpret_cast<const float4 *>(row);
+            return make_float4(row[0], in1 ? row[1] : 0.f, in2 ? row[2] : 0.f, in3 ? row[3] : 0.f);
+        };
+        uint32_t i = 0;
+        for (; i + 8 <= b.len; i += 8) {
+            float4 v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = load(i + j);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                a0 = a0 + (double)v[j].x; a1 = a1 + (double)v[j].y; a2 = a2 + (double)v[j].z; a3 = a3 + (double)v[j].w;
+            }
+        }
+        for (; i < b.len; ++i) {
+            const float4 v = load(i);
+            a0 = a0 + (double)v.x; a1 = a1 + (double)v.y; a2 = a2 + (double)v.z; a3 = a3 + (double)v.w;
+        }
+        if (VEC) {
+            *reinterpret_cast<double2 *>(out + d0) = make_double2(a0, a1);
+            *reinterpret_cast<double2 *>(out + d0 + 2) = make_double2(a2, a3);
+        } else {
+            out[d0] = a0;
+            if (in1) out[d0 + 1] = a1;
+            if (in2) out[d0 + 2] = a2;
+            if (in3) out[d0 + 3] = a3;
+        }
+    }
+}
+
+hipError_t launch_keys_block_sums(const float *emb, int64_t n_rows, int32_t dim, const uint32_t *pos, const key_groups::Block *blocks,
+                                  int64_t n_blocks, double *sums, double *parts, hipStream_t s)
+{
+    if (n_blocks <= 0) return hipSuccess;
+    if (!emb || n_rows <= 0 || dim <= 0 || !pos || !blocks || !sums || n_blocks > (int64_t)0x7FFFFFFF) return hipErrorInvalidValue;
+    const bool vec = dim % 4 == 0 && reinterpret_cast<uintptr_t>(emb) % 16 == 0 && reinterpret_cast<uintptr_t>(sums) % 16 == 0 &&
+                     reinterpret_cast<uintptr_t>(parts) % 16 == 0;
+    if (vec)
+        hipLaunchKernelGGL(key_groups_block_sums_kernel<true>, dim3((unsigned)n_blocks), dim3(256), 0, s, emb, dim, pos, blocks, sums, parts);
+    else
+        hipLaunchKernelGGL(key_groups_block_sums_kernel<false>, dim3((unsigned)n_blocks), dim3(256), 0, s, emb, dim, pos, blocks, sums, parts);
+    return hipGetLastError();
+}
+
+// A key of several blocks: one thread per coordinate adds its partial rows in block order, from +0.0 (key_groups::sum_blocked's
+// S); eight rows' loads are issued before the first is used.
+__global__ __launch_bounds__(256) void key_groups_block_fold_kernel(const key_groups::Fold *__restrict__ folds, const double *__restrict__ parts,
+                                                              int32_t dim, double *__restrict__ sums)
+{
+    const key_groups::Fold f = folds[blockIdx.x];
+    const int32_t d = (int32_t)blockIdx.y * 256 + threadIdx.x;
+    if (d >= dim) return;
+    const double *p = parts + (size_t)f.part0 * dim + d;
+    double s = +0.0;
+    uint32_t b = 0;
+    for (; b + 8 <= f.n_blocks; b += 8) {
+        double v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = p[(size_t)(b + j) * dim];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s = s + v[j];
+    }
+    for (; b < f.n_blocks; ++b) s = s + p[(size_t)b * dim];
+    sums[(size_t)f.slot * dim + d] = s;
+}
+
+hipError_t launch_keys_block_fold(const key_groups::Fold *folds, int64_t n_folds, const double *parts, int32_t dim, double *sums, hipStream_t s)
+{
+    if (n_folds <= 0) return hipSuccess;
+    if (!folds || !parts || !sums || dim <= 0 || n_folds > (int64_t)0x7FFFFFFF || (dim + 255) / 256 > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(key_groups_block_fold_kernel, dim3((unsigned)n_folds, (unsigned)((dim + 255) / 256)), dim3(256), 0, s, folds, parts, dim, sums);
+    return hipGetLastError();
+}
+
 // ---- term scopes (orr_scope_create_terms; the rules are orr_scope_terms_plan.h's) -------------------------------------------
 
 // where each distinct term's bitmap starts (n <= 256 values: one workgroup)

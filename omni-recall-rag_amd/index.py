@@ -171,6 +171,16 @@ class RecallScope:
         N.check(N.hip.orr_scope_row_ids(self._h, int(out.shape[0]), _ptr(out) if out.shape[0] else None, C.cast(C.byref(n), C.c_void_p)))
         return out[:int(n.value)]
 
+    def centroid(self, sums: bool = False):
+        """orr_scope_centroid: (centroid [dim] float32, used) -- the mean of the scope's rows that have a vector, all of them
+        one group under orr_keys_centroids' rule.  sums=True: (centroid, sum [dim] float64, used)."""
+        dim = int(self._index.dim)
+        cent = np.zeros(dim, dtype=np.float32)
+        S = np.zeros(dim, dtype=np.float64)
+        used = C.c_int64(0)
+        N.check(N.hip.orr_scope_centroid(self._h, dim, _ptr(cent) if dim else None, _ptr(S) if dim else None, C.cast(C.byref(used), C.c_void_p)))
+        return (cent, S, int(used.value)) if sums else (cent, int(used.value))
+
     def add_ids(self, row_ids) -> int:
         """orr_scope_add_ids: the live rows that carry these ids join the scope.  Returns how many were not in it before."""
         ids = row_ids if _is_torch(row_ids) else np.ascontiguousarray(row_ids, dtype=np.int64).reshape(-1)
@@ -256,6 +266,33 @@ class RecallKeys:
     def rows(self) -> int:
         """orr_keys_rows: live rows whose key is not KEY_NONE; -1 once the index was destroyed."""
         return int(N.hip.orr_keys_rows(self._h))
+
+    def groups(self, within: Optional["RecallScope"] = None, cap: Optional[int] = None):
+        """orr_keys_groups: (keys, rows) -- the distinct keys other than KEY_NONE among the live rows (of `within`), ascending,
+        and how many rows carry each.  cap: at most this many entries (the first ones); None: all of them."""
+        wh = within._h if within is not None else None
+        n, total = C.c_int64(0), C.c_int64(0)
+        pn, pt = C.cast(C.byref(n), C.c_void_p), C.cast(C.byref(total), C.c_void_p)
+        if cap is None:
+            N.check(N.hip.orr_keys_groups(self._h, wh, 0, None, None, pn, pt))
+            cap = int(total.value)
+        keys = np.zeros(int(cap), dtype=np.int64)
+        rows = np.zeros(int(cap), dtype=np.int64)
+        N.check(N.hip.orr_keys_groups(self._h, wh, int(cap), _ptr(keys) if cap else None, _ptr(rows) if cap else None, pn, pt))
+        return keys[:int(n.value)], rows[:int(n.value)]
+
+    def centroids(self, keys, within: Optional["RecallScope"] = None, sums: bool = False):
+        """orr_keys_centroids: (centroids [n, dim] float32, used [n] int64) -- per listed key the mean of its live rows (of
+        `within`) that have a vector (normB > 0), summed in fp64 in the blocked order the header states; a key without such a
+        row gives zeros and used 0.  sums=True: (centroids, sums [n, dim] float64, used)."""
+        ks = np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)
+        n, dim = int(ks.shape[0]), int(self._index.dim)
+        cent = np.zeros((n, dim), dtype=np.float32)
+        S = np.zeros((n, dim), dtype=np.float64) if sums else None
+        used = np.zeros(n, dtype=np.int64)
+        N.check(N.hip.orr_keys_centroids(self._h, within._h if within is not None else None, n, _ptr(ks) if n else None, dim,
+                                         _ptr(cent) if cent.size else None, _ptr(S) if sums and S.size else None, _ptr(used) if n else None))
+        return (cent, S, used) if sums else (cent, used)
 
 
 class _BorrowedKeys(RecallKeys):
