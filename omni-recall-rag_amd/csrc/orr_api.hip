@@ -2915,7 +2915,16 @@ constexpr int kRetryPass = 1;          // run_shard_once: a workspace was too sm
 // int8 forms hand rows with 0 < normB < 2^-96 and queries with 0 < max|q| < 2^-48 to the exact pass (orr_screen.hip,
 // kI8MinNormB).  These three have no per-row never-drop value: a host-resident batch that holds such a query takes the exact
 // pass (plan_form, has_tiny_query; without it the bf16 shadow and the in-kernel bf16 conversion lose a winner whose products
-// are subnormal, tests/test_gpu_screen_bounds.py); rows that small, and such queries in device memory, stay out of contract.
+// are subnormal, tests/test_gpu_screen_bounds.py); such a query in device memory is marked from its norm where the device or
+// the host forms it (orr::kQueryKeepAll, launch_consts): every pair of it is kept, the query comes back uncertified and the
+// ladder ends in the exact pass.  Rows that small stay out of contract on these three forms.
+// At the large end the contract reaches as far as the reference's own arithmetic does: while every fp32 square and product is
+// finite (|q_k|, |e_k| up to 1.8e19) the norms and the reference's double sums are ordinary numbers, but the fp32 sums of all
+// three forms overflow to +inf or -inf -- a relative bound says nothing about those.  Such a pair (a dot that is not finite
+// beside finite positive norms: dot_overflowed, and the float epilogues' own tests) is never cut: a ranking keeps it under
+// the all-ones key for the exact re-score, a floor takes nothing from it, and a list that such pairs fill reports a cut-off of
+// +inf, which leaves the query uncertified (tests/test_gpu_overflowing_sums.py).  Rows and queries with a NaN or an infinite
+// coordinate, or with a square that overflows (1e25), have a norm that is NaN or infinite and keep the lowest key.
 constexpr double kU23 = 1.1920928955078125e-07, kU16 = 1.52587890625e-05;
 constexpr double kEpsI8 = 1e-12;
 double cosine_bound(double eps_cos) { return 0.7 * 1.01 * eps_cos + 1e-12; }
@@ -2960,6 +2969,7 @@ struct PassPlan {
     double eps1 = 0.0;              // two-stage: bound of the screen over all rows (0: added inside the kernel)
     bool masked = false;            // the screen runs under a scope mask (run_masked_pass): no prefix, the floor from an in-scope sample
     bool grouped = false;           // ... under the masks of several groups at once (a masked pass with a GroupScopes)
+    bool keep_tiny = false;         // device-resident queries through a float form: orr::kQueryKeepAll is set by the norm (launch_consts)
 
     bool two_stage() const {   // the pass keeps survivors in per-query buffers (idx->h_survivors holds their counts)
         return form == PassForm::TwoStageGemm || form == PassForm::TwoStageStream;
@@ -3101,6 +3111,8 @@ int plan_form(orr_index *idx, const BatchArgs &a, int32_t kprime, int64_t n, con
 int plan_pass(orr_index *idx, const BatchArgs &a, int32_t kprime, int64_t n, const std::vector<uint32_t> &qoff, PassPlan &p)
 {
     ORR_TRY(plan_form(idx, a, kprime, n, qoff, p));
+    // (host-resident batches were looked at: has_tiny_query.  The int8 forms carry a per-pair bound that is infinite for such a query.)
+    p.keep_tiny = p.use_mfma && p.q_on_device && !p.prefix_i8 && p.screen != Screen::GemvI8;
     assert(!p.fused() || !a.no_fuse);
     assert(!p.use_mfma || !a.force_exact);
     assert(!p.two_stage() || p.fused());
@@ -3341,6 +3353,7 @@ int launch_consts(orr_index *idx, const BatchArgs &a, const PassPlan &p, int64_t
     ORR_TRY(idx->pin_qc.reserve(sizeof(orr::QueryConst) * (size_t)B));
     ORR_TRY(idx->ws_qc.reserve(sizeof(orr::QueryConst) * (size_t)B));
     orr::QueryConst *qc = idx->pin_qc.as<orr::QueryConst>();
+    const double tiny_below = p.keep_tiny ? (double)idx->dim * 0x1p-96 : 0.0;      // (max|q| < 2^-48 implies norm_a < D 2^-96)
     if (p.use_cos && !p.dev_norms) {
         if (a.norms_host) memcpy(idx->h_norm_a.data(), a.norms_host, sizeof(double) * (size_t)B);
         else exact_norms(idx->pin_q.as<float>(), B, a.dim, idx->h_norm_a.data());
@@ -3354,12 +3367,13 @@ int launch_consts(orr_index *idx, const BatchArgs &a, const PassPlan &p, int64_t
         if (p.batched_score && p.use_cos && !p.dev_norms) {
             if (qc[b].norm_a <= 0.0) qc[b].use_cos = 0;                    // guard :84 -> cosine 0 for every row
             else qc[b].inv_sqrt_na = 1.0 / std::sqrt(qc[b].norm_a);        // NaN stays NaN
+            if (qc[b].norm_a > 0.0 && qc[b].norm_a < tiny_below) qc[b].use_cos |= orr::kQueryKeepAll;
         }
     }
     if (p.dev_norms) {        // (the kernel that adds the norms reads the host's constants in place: no upload command)
         HIP_TRY(hipStreamWaitEvent(s, idx->ev_q, 0));
         HIP_TRY(orr::launch_patch_query_norms(idx->ws_qc.as<orr::QueryConst>(), idx->ws_norm_a.as<double>(), B, p.batched_score, s,
-                                              idx->pin_norm.as<double>(), qc));
+                                              idx->pin_norm.as<double>(), qc, tiny_below));
     } else {
         HIP_TRY(hipMemcpyAsync(idx->ws_qc.p, qc, sizeof(orr::QueryConst) * (size_t)B, hipMemcpyHostToDevice, s));
     }
@@ -3998,7 +4012,9 @@ int32_t finish_query(const orr_candidate *const *shard_recs, int32_t n_shards, i
         if ((tr.flags & ORR_CAND_TWO_STAGE) && tr.norm_b > need_score) need_score = tr.norm_b;
         if (tr.approx_score != -std::numeric_limits<double>::infinity()) {
             any_cut = true;
-            // NaN cut-off: everything left out is NaN too (NaN sorts last), harmless
+            // NaN cut-off: the worst kept key was a NaN score, so everything left out is NaN too (NaN sorts last), harmless.
+            // A list that pairs kept whatever their score filled to the brim reports +inf instead (cutoff_of_key): what was
+            // left out is unknown there, no k-th score exceeds that cut-off, and the query climbs the ladder.
             if (!(tr.approx_score != tr.approx_score) && tr.approx_score > cutoff) cutoff = tr.approx_score;
         }
     }

@@ -49,6 +49,27 @@ __device__ __forceinline__ double key_score(unsigned long long k)
     return __longlong_as_double((long long)u);
 }
 
+// The all-ones key: a pair that is kept whatever its approximate score, because that score says nothing about the exact one
+// (an approximate dot that is no finite number beside finite positive norms: fp32 sums that overflowed).  It is no score.
+constexpr unsigned long long kKeptKey = ~0ull;
+
+// The cut-off a trailer reports for the worst key a selection kept.  A NaN key (1) means that everything left out scores NaN
+// as well, which costs nothing; the all-ones key means that rows kept whatever their score filled the whole list, so what
+// was left out is unknown: +inf, which no k-th score exceeds, and the query comes back uncertified (finish_query).
+__device__ __forceinline__ double cutoff_of_key(unsigned long long k)
+{
+    return k == kKeptKey ? __builtin_huge_val() : key_score(k);
+}
+
+// Whether a pair's approximate fp32 dot is unusable although its exact score is an ordinary number: the dot is not finite
+// while both norms are finite and positive (|q_k|, |e_k| up to 1.8e19: every product is finite, their fp32 sum is not).  A
+// row or a query with a NaN or an infinite coordinate has a norm that is NaN or infinite (inv_sqrt 0 or NaN): not this case.
+__device__ __forceinline__ bool dot_overflowed(double dot_f32, double inv_sqrt_nb, const QueryConst &qc)
+{
+    return !(fabs(dot_f32) <= 3.4028234663852886e38) && qc.use_cos && inv_sqrt_nb > 0.0 && inv_sqrt_nb <= 1.7976931348623157e308 &&
+           qc.inv_sqrt_na > 0.0 && qc.inv_sqrt_na <= 1.7976931348623157e308;
+}
+
 // Two-stage pass, floor: with s_k = the k-th best sampled score (key tau_k),
 //   L = s_k - eps3           a lower bound of the exact k-th best score of the prefix, hence of the corpus
 //   F = L - eps1 - margin    a row whose screening score is below F has an exact score below L

@@ -206,7 +206,10 @@ __device__ __forceinline__ void fused_epilogue(const ACC (&acc)[NI][NJ], int qba
                         const uint32_t m = (w[j][e >> 2] >> (4 * (e & 3))) & 15u;
                         const float a = acc_as_float<AGPR>(acc[i][j][e]);
                         const float upper = __builtin_fmaf((float)m, qf.z, __builtin_fmaf(a, qf.x * rb[j], __builtin_fmaf(qf.w, eb[j], cj[j])));
-                        hit[e1][j] = __builtin_amdgcn_ballot_w64(!(upper < qf.y));      // NaN bounds (float accumulators that overflowed) are kept
+                        bool keep = !(upper < qf.y);                                    // NaN bounds (float accumulators that overflowed) are kept
+                        // ... and so is a sum that overflowed to -inf, whose bound lies below every floor: pass 1b keeps it
+                        if constexpr (!INT_ACC) keep = keep || !(__builtin_fabsf(a) <= 3.4028234663852886e38f);
+                        hit[e1][j] = __builtin_amdgcn_ballot_w64(keep);
                     }
                 }
 #pragma unroll

@@ -164,13 +164,21 @@ struct QueryConst {
     double inv_sqrt_na;   // 1/sqrt(norm_a) for the batched selection score
     double inv_n_terms;   // 1/queryTerms.Length, 0 without terms
     int32_t n_terms;      // queryTerms.Length (RecallSearchService.cs:112)
-    int32_t use_cos;      // query dim == index dim, dim > 0 (and norm_a > 0 in the batched form)
+    int32_t use_cos;      // query dim == index dim, dim > 0 (and norm_a > 0 in the batched form); | kQueryKeepAll
 };
+
+// Bit of QueryConst::use_cos (which every reader but the two below takes as a truth value): the query's products with the rows
+// are subnormal in fp32 (0 < norm_a < D 2^-96, which holds whenever 0 < max|q| < 2^-48), where the relative product error the
+// float forms charge does not hold.  Set for queries in device memory, which plan_form cannot look at, where the pass has no
+// int8 per-pair bound: fuse_select and the bf16 streaming screen keep every pair of such a query (a floor takes nothing from
+// them), so the query comes back uncertified and climbs the ladder to the exact pass.  No host synchronisation in front of the pass.
+constexpr int32_t kQueryKeepAll = 2;
 
 // qc[b].norm_a / inv_sqrt_na / use_cos from norms computed on the device (launch_dot_exact, self_norm over the queries).
 hipError_t launch_patch_query_norms(QueryConst *qc, const double *norm_a, int32_t B, bool batched, hipStream_t s,
                                     double *norm_host = nullptr,         // norm_host (optional, pinned): the norms for the host as well
-                                    const QueryConst *qc_host = nullptr);   // qc_host (optional, pinned): the constants come from there, not from qc
+                                    const QueryConst *qc_host = nullptr,   // qc_host (optional, pinned): the constants come from there, not from qc
+                                    double tiny_below = 0.0);              // > 0: norms in (0, tiny_below) set kQueryKeepAll
 
 // Per-row selection constants for a batch: out[r] = {1/sqrt(normB) or 0, recency * 0.1}.
 hipError_t launch_row_consts(const double *norm_b, const int64_t *created, int64_t now_ticks, int64_t n_rows,

@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256) void row_consts_kernel(const double *__restric
 // Query norms computed on the device (queries that already live there): fills the norm-dependent fields of the
 // per-query constants exactly as the host does for host-resident queries.
 __global__ void patch_query_norms_kernel(QueryConst *__restrict__ qc, const double *__restrict__ norm_a, int32_t B, int32_t batched,
-                                         double *__restrict__ norm_host, const QueryConst *__restrict__ qc_host)
+                                         double *__restrict__ norm_host, const QueryConst *__restrict__ qc_host, double tiny_below)
 {
     const int32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
@@ -43,15 +43,17 @@ __global__ void patch_query_norms_kernel(QueryConst *__restrict__ qc, const doub
     if (batched && c.use_cos) {
         if (na <= 0.0) c.use_cos = 0;                     // guard :84 -> cosine 0 for every row
         else c.inv_sqrt_na = 1.0 / sqrt(na);              // NaN stays NaN
+        if (na > 0.0 && na < tiny_below) c.use_cos |= kQueryKeepAll;   // (see kQueryKeepAll; tiny_below 0: the pass has no use for it)
     }
     qc[b] = c;
 }
 
 hipError_t launch_patch_query_norms(QueryConst *qc, const double *norm_a, int32_t B, bool batched, hipStream_t s, double *norm_host,
-                                    const QueryConst *qc_host)
+                                    const QueryConst *qc_host, double tiny_below)
 {
     if (B <= 0) return hipSuccess;
-    hipLaunchKernelGGL(patch_query_norms_kernel, dim3((B + 255) / 256), dim3(256), 0, s, qc, norm_a, B, batched ? 1 : 0, norm_host, qc_host);
+    hipLaunchKernelGGL(patch_query_norms_kernel, dim3((B + 255) / 256), dim3(256), 0, s, qc, norm_a, B, batched ? 1 : 0, norm_host, qc_host,
+                       tiny_below);
     return hipGetLastError();
 }
 
@@ -924,6 +926,9 @@ __global__ __launch_bounds__(1024) void fuse_select_kernel(const double *__restr
             } else if (FAST) {
                 const double2 rc = row_consts[r];
                 nk[u] = score_key(fused_score_fast(d, rc.x, rc.y, m, qc));
+                // an fp32 sum that overflowed: a ranking keeps the pair for the exact re-score, a floor takes nothing from it
+                // (likewise every pair of a query whose products with the rows are subnormal: kQueryKeepAll)
+                if (dotf && (dot_overflowed(d, rc.x, qc) || ((qc.use_cos & kQueryKeepAll) && rc.x > 0.0))) nk[u] = LANEMAX ? 1ull : kKeptKey;
             } else {
                 nk[u] = score_key(fused_score(d, norm_b[r], created[r], m, qc, now_ticks));
             }
@@ -1060,7 +1065,11 @@ __global__ __launch_bounds__(1024) void select_final_kernel(const SelEntry *__re
         __syncthreads();
     }
     if (wave == 0 && tau_out) {      // sampling pass: only the k'-th best key of these lists is wanted
-        const unsigned long long kth = __shfl(k, kprime - 1, 64);
+        // (of the keys that are scores: pairs kept whatever their score -- kKeptKey, in front of every score -- say nothing about
+        // the k'-th best; with fewer than k' scores behind them there is no floor)
+        const int n_kept = __popcll(__ballot(k == kKeptKey));
+        const unsigned long long kth_any = __shfl(k, (kprime - 1 + n_kept) & 63, 64);
+        const unsigned long long kth = kprime - 1 + n_kept < 64 ? kth_any : 0ull;
         if (lane == 0) {
             tau_out[b] = kth;                     // 0 (empty slot) if fewer than k' rows: no filtering
             if (floor.floor_key) two_stage_floor_of(kth, floor.eps3, floor.eps1, floor.floor_key + b, floor.L + b);
@@ -1078,7 +1087,7 @@ __global__ __launch_bounds__(1024) void select_final_kernel(const SelEntry *__re
             orr_candidate t;
             // two-stage: every buffered row became a record -> the only rows left out are below L
             const bool kept_all = n_rows <= (int64_t)kprime || (two_stage_L && fused_cnt && fused_cnt[b] <= (uint32_t)kprime);
-            t.approx_score = (kept_all || n_valid == 0) ? -__builtin_huge_val() : key_score(worst_key);
+            t.approx_score = (kept_all || n_valid == 0) ? -__builtin_huge_val() : cutoff_of_key(worst_key);
             t.dot = approx_eps; t.norm_b = 0.0; t.created_ticks = 0;
             t.row_id = -1; t.order_key = n_rows; t.matches = n_valid; t.flags = ORR_CAND_TRAILER;
             if (fused_cnt && fused_cnt[b] > fused_cap) t.flags |= ORR_CAND_OVERFLOW;
@@ -1119,7 +1128,10 @@ __global__ __launch_bounds__(64) void select_floor_heads_kernel(const SelEntry *
         if (better(e.key, e.pos, k, p)) { k = e.key; p = e.pos; }
     }
     wave_sort(k, p, lane);
-    const unsigned long long kth = __shfl(k, kprime - 1, 64);
+    // (heads that are no scores -- kKeptKey -- are passed over: the k-th best of the others still belongs to k distinct rows)
+    const int n_kept = __popcll(__ballot(k == kKeptKey));
+    const unsigned long long kth_any = __shfl(k, (kprime - 1 + n_kept) & 63, 64);
+    const unsigned long long kth = kprime - 1 + n_kept < 64 ? kth_any : 0ull;
     if (lane == 0) {
         tau_out[b] = kth;
         if (floor.floor_key) two_stage_floor_of(kth, floor.eps3, floor.eps1, floor.floor_key + b, floor.L + b);

@@ -1145,7 +1145,7 @@ __global__ __launch_bounds__(256, 2) void screen_gemv_bf16_kernel(const __bf16 *
                 const QueryConst qc = epi.qc[b];
                 const uint32_t mm = qc.n_terms > 0 ? kw_matches(epi.kw, b, (uint32_t)row) : 0u;
                 unsigned long long key = score_key(fused_score_fast((double)a, rc.x, rc.y, mm, qc));
-                if (!(__builtin_fabsf(a) <= 3.4028234663852886e38f)) key = ~0ull;   // never dropped: re-scored exactly later
+                if (!(__builtin_fabsf(a) <= 3.4028234663852886e38f) || (qc.use_cos & kQueryKeepAll)) key = ~0ull;   // never dropped: re-scored exactly later
                 if (key > epi.tau[b]) {
                     const uint32_t slot = atomicAdd(&epi.cnt[b], 1u);
                     if (slot < epi.cap) {

@@ -159,6 +159,14 @@ def _row_families(rng, dim, scale=1.0):
         return {k: (v * scale).astype(np.float32) for k, v in fam.items()}
 
 
+def _huge_families(rng, dim):
+    """Finite rows and queries at the large end: every fp32 square and product of the equal-magnitude one is 2.25e38 (finite), its
+    norms and the reference's double sums are finite, and no fp32 sum of two like-signed products is
+    (tests/test_overflowing_sums_cpu.py); the Gaussian one holds coordinates whose fp32 squares overflow."""
+    return {"gauss 1e19": (rng.standard_normal(dim) * 1e19).astype(np.float32),
+            "equal magnitude 1.5e19": (rng.choice([-1.0, 1.0], dim) * 1.5e19).astype(np.float32)}
+
+
 def _place(rng, n, dim, fam, scale=1.0):
     """Gaussian rows with every family row in the first tile, a middle tile and the partial last tile."""
     emb = (rng.standard_normal((n, dim)) * scale).astype(np.float32)
@@ -194,6 +202,7 @@ def test_int8_row_constants_are_sound_and_tight(dim):
         v = np.zeros(dim, dtype=np.float32)
         v[dim // 2] = s                                                   # normB = 2^-96 exactly / just below it
         fam[name] = v
+    fam.update(_huge_families(rng, dim))
     emb, where = _place(rng, N_CONST, dim, fam)
     idx = _index(P, emb)
     c = idx.screen_i8_consts()
@@ -214,6 +223,7 @@ def test_int8_row_constants_are_sound_and_tight(dim):
         assert zero[where[("zero", t)]] and zero[where[("nan", t)]]
         assert never[where[("inf", t)]] and never[where[("equal magnitude 3e-21", t)]] and never[where[("one-hot below 2^-48", t)]]
         assert plain[where[("one-hot 2^-48", t)]] and plain[where[("equal magnitude 2^-48", t)]]
+        assert plain[where[("equal magnitude 1.5e19", t)]] and np.isfinite(nb[where[("equal magnitude 1.5e19", t)]])
     assert np.all(c["rel_err"][zero] == 0) and np.all(c["rel_hat"][zero] == 0), "zero-norm rows: 0 / 0"
     assert np.all(np.isposinf(c["rel_err"][never])) and np.all(c["rel_hat"][never] == 0), "never-screened-out rows: inf / 0"
     factor = (1 + 1e-6) * (1 + U23)
@@ -245,6 +255,7 @@ def test_int8_query_constants_are_exact_sound_and_tight(dim):
     v = (rng.standard_normal(dim) * 1e-30).astype(np.float32)
     v[3] = np.nextafter(np.float32(2.0 ** -48), np.float32(0))
     fam["largest just below 2^-48"] = v
+    fam.update(_huge_families(rng, dim))
     names = list(fam)
     qs = np.stack([fam[k] for k in names] + [rng.standard_normal(dim).astype(np.float32) for _ in range(4)])
     emb = rng.standard_normal((300, dim)).astype(np.float32)
@@ -261,7 +272,7 @@ def test_int8_query_constants_are_exact_sound_and_tight(dim):
     unbounded = bad | ((mx > 0) & (mx < MIN_QUERY_MAX))
     for k in ("inf", "nan", "equal magnitude 3e-21", "gauss 1e-19", "largest just below 2^-48"):
         assert unbounded[names.index(k)], k
-    for k in ("zero", "one-hot 0", f"one-hot {dim - 1}", "one-hot 2^-48", "gauss 1e-3", "half steps"):
+    for k in ("zero", "one-hot 0", f"one-hot {dim - 1}", "one-hot 2^-48", "gauss 1e-3", "half steps", "gauss 1e19", "equal magnitude 1.5e19"):
         assert not unbounded[names.index(k)], k
     assert np.all(np.isposinf(c["err2"][unbounded])) and np.all(np.isposinf(c["err2_level1"][unbounded]))
     factor = (1 + 1e-6) * (1 + 2.0 ** -52 * dim)
@@ -455,6 +466,7 @@ def test_per_pair_bound_covers_the_reference_cosine(scale):
     dim = 128
     rng = np.random.default_rng(5000)
     fam = _row_families(rng, dim, scale)
+    fam.update(_huge_families(rng, dim))                                  # (whatever the scale of the rest)
     emb, where = _place(rng, N_CONST, dim, fam, scale)
     names = list(fam)
     with np.errstate(all="ignore"):
@@ -484,6 +496,8 @@ def test_per_pair_bound_covers_the_reference_cosine(scale):
         judged = np.isfinite(cos_ref) & (na > 0)[:, None] & np.isfinite(inv_a)[:, None]   # (use_cos is off for a query of norm 0)
         own = (names.index("equal magnitude"), where[("equal magnitude", 1)])     # the pair the relative charge fails first
         assert judged[own] and abs(cos_ref[own] - 1) < 1e-12
+        huge = (names.index("equal magnitude 1.5e19"), where[("equal magnitude 1.5e19", 1)])   # finite norms, a dot no fp32 sum holds
+        assert judged[huge] and abs(cos_ref[huge] - 1) < 1e-12
         for form, (approx, bound) in forms.items():
             diff = np.abs(0.7 * cos_ref - np.where(inv_b[None, :] == 0, 0.0, approx))
             ok = ~judged | (diff <= bound) | ~(bound <= 1.7976931348623157e308)   # (a bound that is not finite: the pair is kept)
@@ -532,7 +546,9 @@ def test_winner_with_subnormal_products_survives_the_screen(dim, two_stage):
     (128, 1) is the int8 shadow, where the thresholds hand the query's pairs to the exact re-score.  The other combinations run
     the bf16 shadow, the in-kernel bf16 conversion, the f32-MFMA stream and the split GEMM, which have no such value: there
     plan_form sends a host-resident batch with such a query down the exact pass (without that, (128, 2), (192, 1) and (192, 2)
-    return rows 0..9 for 6 and 130 queries)."""
+    return rows 0..9 for 6 and 130 queries).  Every batch runs a second time with the queries in device memory, where the plan
+    cannot look at them: the norm the device computes (below 16 queries: the host's, of the downloaded copy) marks the query,
+    every pair of it is kept, and the query climbs the escalation ladder to the exact pass."""
     P = pkg()
     rng = np.random.default_rng(6000 + dim)
     n, k = E2E_N, E2E_K
@@ -574,11 +590,14 @@ def test_winner_with_subnormal_products_survives_the_screen(dim, two_stage):
     want = [corpus.search(qs[b], "", NOW, k, candidate_limit=n, threads=8) for b in range(len(qs))]
     assert want[0][0][0] == x_row
     terms = [P.text.query_terms("")] * len(qs)
+    import torch
+    qd = torch.from_numpy(qs).to("cuda:0")
     for B in (1, 4, 6, 130):
-        got_rows, got_scores, counts = idx.search(qs[:B], terms[:B], NOW, k, candidate_limit=n)
-        for b in range(B):
-            orow, osc, _ = want[b]
-            assert counts[b] == len(orow)
-            assert list(got_rows[b, :counts[b]]) == list(orow), (B, b, got_rows[b], orow)
-            assert np.array_equal(got_scores[b, :counts[b]], osc), (B, b)
+        for where_q, q in (("host", qs[:B]), ("device", qd[:B])):
+            got_rows, got_scores, counts = idx.search(q, terms[:B], NOW, k, candidate_limit=n)
+            for b in range(B):
+                orow, osc, _ = want[b]
+                assert counts[b] == len(orow)
+                assert list(got_rows[b, :counts[b]]) == list(orow), (B, where_q, b, got_rows[b], orow)
+                assert np.array_equal(got_scores[b, :counts[b]], osc), (B, where_q, b)
     idx.close()
