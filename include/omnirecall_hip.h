@@ -796,8 +796,9 @@ int orr_search_batch_per_key(orr_index *idx, int32_t B, int32_t dim, const float
  * scope of another shard, ORR_ESTATE for an orphaned handle, ORR_EDIM.  Lifetime and threads are orr_keys_get's: the call takes
  * a lane, holds keys and scope shared and works through views.  The search statistics do not move; every launch appears in the
  * kernel statistics under its own name.
- * Out of scope: the cluster forms (a document cut by a shard border would need the blocked order defined across shards;
- * orr_cluster_keys_shard lets a host ask each shard meanwhile, but such per-shard sums ARE NOT the single index's bits), a mean
+ * Out of scope: the cluster forms (built since: §8w, orr_cluster_keys_groups / orr_cluster_keys_centroids /
+ * orr_cluster_scope_centroid below define the blocked order across shards; a host may still ask each shard through
+ * orr_cluster_keys_shard, but such per-shard sums added up ARE NOT the single index's bits), a mean
  * of unit-normalised rows or a weighted mean, sharded.py, the service mirror and the micro-batcher, keys in the shard file, a
  * search call that ranks documents by centroid. */
 #define ORR_KEY_GROUPS_BLOCK 256
@@ -1285,6 +1286,58 @@ int       orr_cluster_search_batch_per_key(orr_cluster *c, int32_t B, int32_t di
               int64_t now_ticks, int32_t topk, int64_t candidate_limit,
               const orr_cluster_scope *within /* or NULL */, const orr_cluster_keys *keys, int32_t max_per_key, int32_t pool,
               int64_t *out_rows, double *out_scores, int64_t *out_keys, int32_t *out_counts, int32_t *out_rounds /* may be NULL */);
+
+/* ---- cluster key groups: row counts and centroid vectors per key across the shards ----------------------------------------------
+ * The three key-groups calls for an orr_cluster.  The contract is the earlier cluster forms': THE ANSWERS OF THE SINGLE-INDEX CALL
+ * ON ONE INDEX HOLDING ALL THE CLUSTER'S ROWS IN THE GLOBAL CANDIDATE ORDER (shard 0's rows, then shard 1's, ...), BIT FOR BIT --
+ * keys, counts, fp64 sums, fp32 centroids, out_used.  A document cut by a shard border is the normal case (the cuts fall by row
+ * count), and per-shard sums added up are not these bits, so the library carries the blocked order across the borders itself.
+ * The rules that are new are csrc/orr_cluster_key_groups_plan.h's.
+ *
+ * THE RULE ACROSS SHARDS, bit for bit.  The single-index rule stays: the participating members (normB > 0.0) of key K, in order,
+ * are cut into blocks of 256; P_j is the fp64 sum of block j in member order from +0.0; S is the fp64 sum of the P_j in block order
+ * from +0.0; c = (float)(S / n) on the host.  On a cluster K's members are shard 0's in position order, then shard 1's, ...; for
+ * shard g, count_g is K's participating members there, before_g their number on the shards in front, total their sum.  BLOCKS ARE
+ * COUNTED FROM THE KEY'S FIRST MEMBER ANYWHERE, so a block may straddle a border:
+ *   head      before_g % 256 != 0: the first min(count_g, 256 - before_g % 256) members continue the block left open in front of
+ *             this shard; their running sum starts from that block's carry P, not from +0.0.
+ *   free      the members behind the head are cut into blocks of 256 from +0.0 (exactly keys_block_sums' blocks).
+ *   closing   a block closes on the shard where its 256th member lies, or the key's last member.  Closed blocks are added to the
+ *             running S in block order; S starts at +0.0 on the key's first shard and otherwise continues from the S the shard in
+ *             front left.  A block still open at the end of a shard is not folded: its partial sum is the carry P for the next
+ *             shard that holds a member.  A shard without a member of K is skipped; the carry passes over it.
+ * Both carries are real data dependencies (fp64 addition is not associative); they concern one block and one running row per
+ * spanning key and border.  Everything else -- all free blocks, every key that lies on one shard -- runs on every shard at once
+ * through the single index's kernels and records.
+ *
+ *   orr_cluster_keys_groups     orr_keys_groups per shard, the shards' ascending lists merged on the host (rows of equal keys added).
+ *   orr_cluster_keys_centroids  keys is HOST memory.  Every shard at once: keys_pairs_count / keys_pairs / the sort / keys_runs, one
+ *                               sorted table for the call.  Per slice of keys ("key_groups_slice" of shard 0; the bits do not
+ *                               depend on it), every shard at once: keys_block_sums, and keys_block_fold for keys wholly there; then
+ *                               the shards in ascending order, only where a spanning key of the slice has members: ONE
+ *                               keys_chain_step, its state (S and P, 2 x dim fp64 per spanning key) through one pinned host buffer.
+ *                               A cluster cut between documents launches no keys_chain_step.  The finish is the host's, n = total.
+ *   orr_cluster_scope_centroid  all rows of the cluster scope as ONE group, the same way.
+ * Outputs, limits and special cases are the single-index calls': 0 .. 65,536 keys, ORR_KEY_NONE asks for the rows without a key, a
+ * key listed twice is answered twice, no participating member gives zeros and out_used 0, cap == 0 asks for the total, out_used
+ * is the key's participating count over the whole cluster.
+ * Errors, in this order: ORR_EINVAL in the single-index calls' order before any handle is looked at, the outputs untouched; an
+ * orphaned handle: ORR_ESTATE; keys and scope of different clusters: ORR_EINVAL; a foreign or non-positive dim: ORR_EDIM.
+ * The call holds the cluster shared, one lane per shard taken in ascending shard order before any shard starts, and on each shard
+ * the scope part's lock, then the keys part's shared lock.  The search statistics do not move; every launch appears in its shard's
+ * kernel statistics under its own name.
+ * Out of scope: sharded.py, the record (shard) form, the service mirror and the micro-batcher, keys in the shard file, a device-side
+ * finish or a pinned return path for the sums, overlapping the chain of one slice with the free blocks of the next, a search that
+ * ranks documents by centroid.  A key assignment that puts every key on every shard is answered correctly, at 2 x dim x 8 bytes of
+ * state per key and border each way. */
+int orr_cluster_keys_groups(orr_cluster_keys *k, const orr_cluster_scope *within /* or NULL */, int64_t cap,
+                            int64_t *out_keys /* host [cap] */, int64_t *out_rows /* host [cap] */,
+                            int64_t *out_n, int64_t *out_total);
+int orr_cluster_keys_centroids(orr_cluster_keys *k, const orr_cluster_scope *within /* or NULL */, int32_t n_keys,
+                               const int64_t *keys /* HOST */, int32_t dim, float *out_centroids /* host [n_keys][dim], may be NULL */,
+                               double *out_sums /* host [n_keys][dim], may be NULL */, int64_t *out_used /* host [n_keys] */);
+int orr_cluster_scope_centroid(orr_cluster_scope *s, int32_t dim, float *out_centroid /* host [dim], may be NULL */,
+                               double *out_sum /* host [dim], may be NULL */, int64_t *out_used);
 
 #ifdef __cplusplus
 }

@@ -277,6 +277,12 @@ hip.orr_cluster_scope_create_keys.restype = C.c_int
 hip.orr_cluster_scope_create_keys.argtypes = [_vp, _vp, _i32, _vp, C.POINTER(_vp)]
 hip.orr_cluster_search_batch_per_key.restype = C.c_int
 hip.orr_cluster_search_batch_per_key.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]
+hip.orr_cluster_keys_groups.restype = C.c_int
+hip.orr_cluster_keys_groups.argtypes = [_vp, _vp, _i64, _vp, _vp, _vp, _vp]
+hip.orr_cluster_keys_centroids.restype = C.c_int
+hip.orr_cluster_keys_centroids.argtypes = [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp]
+hip.orr_cluster_scope_centroid.restype = C.c_int
+hip.orr_cluster_scope_centroid.argtypes = [_vp, _i32, _vp, _vp, _vp]
 
 host.orrh_is_blank.restype = _i32
 host.orrh_is_blank.argtypes = [C.c_char_p, _i64]
@@ -371,6 +377,7 @@ EXPORTED_HIP_SYMBOLS = [
     "orr_cluster_search_batch_diverse", "orr_cluster_pair_dots",
     "orr_cluster_keys_create", "orr_cluster_keys_set", "orr_cluster_keys_get", "orr_cluster_keys_rows", "orr_cluster_keys_shard", "orr_cluster_keys_destroy",
     "orr_cluster_scope_create_keys", "orr_cluster_search_batch_per_key",
+    "orr_cluster_keys_groups", "orr_cluster_keys_centroids", "orr_cluster_scope_centroid",
 ]
 EXPORTED_HOST_SYMBOLS = ["orrh_is_blank", "orrh_lower_invariant", "orrh_query_terms", "orrh_build_snippet",
                          "orrh_round4", "orrh_has_sufficient_evidence", "orrh_format_score_f4", "orrh_last_error", "orrh_store_create", "orrh_store_destroy",

@@ -7534,15 +7534,15 @@ int key_groups_runs(orr_index *lane, KeyGroupsWork &w, int64_t m, int64_t *out_r
     return ORR_OK;
 }
 
-// One slice's sums: the blocks and folds brought to the device, keys_block_sums, keys_block_fold where a key has several
-// blocks, the n_slots x dim sums back in `host` (a key without a block reads +0.0).  Ends synchronised.
-int key_groups_slice_sums(orr_index *lane, KeyGroupsWork &w, int32_t n_slots, const std::vector<key_groups::Block> &blocks,
-                          const std::vector<key_groups::Fold> &folds, uint32_t n_parts, double *host)
+// The launch half of one slice's sums: the blocks (at least one) and folds brought to the device, keys_block_sums,
+// keys_block_fold where a key has several blocks; the n_slots x dim sums stay on the device (a key without a block reads +0.0).
+// Nothing is waited for: the host's blocks and folds live until the caller has synchronised.
+int key_groups_slice_launch(orr_index *lane, KeyGroupsWork &w, int32_t n_slots, const std::vector<key_groups::Block> &blocks,
+                            const std::vector<key_groups::Fold> &folds, uint32_t n_parts)
 {
     hipStream_t s = lane->stream;
     const int32_t dim = lane->dim;
-    const size_t sum_bytes = sizeof(double) * (size_t)n_slots * (size_t)dim;
-    if (blocks.empty()) { memset(host, 0, sum_bytes); return ORR_OK; }
+    const size_t sum_bytes = sizeof(double) * (size_t)std::max(n_slots, 1) * (size_t)dim;
     ORR_TRY(w.sums.reserve(sum_bytes));
     ORR_TRY(w.blocks.reserve(sizeof(key_groups::Block) * blocks.size()));
     if (n_parts) ORR_TRY(w.parts.reserve(sizeof(double) * (size_t)n_parts * (size_t)dim));
@@ -7561,6 +7561,17 @@ int key_groups_slice_sums(orr_index *lane, KeyGroupsWork &w, int32_t n_slots, co
         Timed t(lane, "keys_block_fold", 8.0 * ((double)n_parts + (double)folds.size()) * (double)dim);
         HIP_TRY(orr::launch_keys_block_fold(w.folds.as<key_groups::Fold>(), (int64_t)folds.size(), w.parts.as<double>(), dim, w.sums.as<double>(), s));
     }
+    return ORR_OK;
+}
+
+// One slice's sums: key_groups_slice_launch, then the n_slots x dim sums back in `host`.  Ends synchronised.
+int key_groups_slice_sums(orr_index *lane, KeyGroupsWork &w, int32_t n_slots, const std::vector<key_groups::Block> &blocks,
+                          const std::vector<key_groups::Fold> &folds, uint32_t n_parts, double *host)
+{
+    hipStream_t s = lane->stream;
+    const size_t sum_bytes = sizeof(double) * (size_t)n_slots * (size_t)lane->dim;
+    if (blocks.empty()) { memset(host, 0, sum_bytes); return ORR_OK; }
+    ORR_TRY(key_groups_slice_launch(lane, w, n_slots, blocks, folds, n_parts));
     HIP_TRY(hipMemcpyAsync(host, w.sums.p, sum_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));                  // (the host's blocks and folds go with this frame)
     return ORR_OK;
@@ -10150,6 +10161,355 @@ int orr_cluster_search_batch_per_key(orr_cluster *c, int32_t B, int32_t dim, con
     const BatchArgs a{B, dim, q_host, terms_utf8, term_off, query_term_off, now_ticks, candidate_limit, topk};
     ORR_TRY(check_batch(c->shards[0], a, fn));
     return cluster_per_key_run(c, fn, a, within, keys, max_per_key, pool, out_rows, out_scores, out_keys, out_counts, out_rounds);
+}
+
+}  // extern "C"
+
+// ---- cluster key groups (orr_cluster_keys_groups, orr_cluster_keys_centroids, orr_cluster_scope_centroid) ----------------------
+// The answers of the single-index calls on ONE index holding all the cluster's rows in the global candidate order, bit for bit.
+// The pairs, the runs, the free blocks and every key that lies on one shard are the single index's helpers and records, run on
+// every shard at once; what the cluster adds is orr_cluster_key_groups_plan.h's: a key's blocks of 256 are counted from its first
+// member anywhere, so a spanning key's open block (P) and running sum (S) are carried from shard to shard in ascending order by
+// keys_chain_step, through one pinned host buffer.
+
+namespace {
+
+// What a cluster key-groups call owns: every shard's work, chain records and state rows, and the pinned state of the slice in
+// flight ([spanning keys][2][dim] fp64).  Each shard's buffers are released with its device bound.
+struct ClusterKeyGroupsWork {
+    std::vector<std::unique_ptr<KeyGroupsWork>> w;
+    std::vector<DevBuf> chains, state;
+    PinnedBuf pin;
+    std::vector<int> device;
+    explicit ClusterKeyGroupsWork(const orr_cluster *c) : chains(c->shards.size()), state(c->shards.size())
+    {
+        for (const orr_index *sh : c->shards) { w.emplace_back(new KeyGroupsWork()); device.push_back(sh->device); }
+    }
+    ~ClusterKeyGroupsWork()
+    {
+        for (size_t g = 0; g < w.size(); ++g) {
+            (void)hipSetDevice(device[g]);
+            w[g].reset();
+            chains[g].release();
+            state[g].release();
+        }
+        pin.release();
+    }
+};
+
+// What the three calls hold: one lane per shard, all taken before any shard starts and in ascending shard order
+// (acquire_in_order says why); behind them, on each shard, the scope part's lock, then the keys part's shared lock, as the single
+// call takes them.  Then the handles looked at again: alive, of this cluster's shards, covering their shards' rows.
+int cluster_key_groups_hold(orr_cluster *c, const char *fn, const orr_cluster_keys *k, const orr_cluster_scope *sc, std::vector<Lane> &lanes,
+                            std::vector<std::shared_lock<std::shared_mutex>> &held)
+{
+    const size_t G = c->shards.size();
+    std::vector<LanePool *> pools;
+    std::vector<LanePool::Make> makes;
+    for (orr_index *sh : c->shards) { pools.push_back(&sh->lanes); makes.push_back(lane_maker(sh)); }
+    acquire_in_order(pools, makes, lanes);
+    held.reserve(2 * G);
+    for (size_t g = 0; g < G; ++g) {
+        if (sc) held.emplace_back(sc->parts[g]->mu);
+        if (k) held.emplace_back(k->parts[g]->mu);
+    }
+    orr_cluster *own = nullptr;
+    if (k) {
+        ORR_TRY(cluster_keys_owner(k, fn, &own));
+        ORR_TRY(cluster_keys_parts_alive(c, k, fn));
+    }
+    if (sc) {
+        ORR_TRY(cluster_scope_owner(sc, fn, &own));
+        ORR_TRY(cluster_scope_parts_alive(c, sc, fn));
+    }
+    for (size_t g = 0; g < G; ++g) {
+        const int64_t rows = lanes[g].lane->n_rows;
+        if (k && k->parts[g]->n_rows != rows)
+            return fail(ORR_ESTATE, "%s: the keys cover %lld rows of shard %d, the shard holds %lld", fn, (long long)k->parts[g]->n_rows, (int)g, (long long)rows);
+        if (sc && sc->parts[g]->n_rows != rows)
+            return fail(ORR_ESTATE, "%s: the scope covers %lld rows of shard %d, the shard holds %lld", fn, (long long)sc->parts[g]->n_rows, (int)g, (long long)rows);
+    }
+    return ORR_OK;
+}
+
+// Every lane's stream waited for and its launches folded into its shard's kernel statistics.
+void cluster_key_groups_end(std::vector<Lane> &lanes)
+{
+    for (Lane &ln : lanes) {
+        orr_index *lane = ln.lane;
+        std::lock_guard<std::mutex> lock(lane->mu);
+        if (bind_device(lane) != ORR_OK) continue;
+        (void)hipStreamSynchronize(lane->stream);
+        collect_events(lane);
+    }
+}
+
+// The fp64 sums of the T keys of `table` (mode 1; the participating rows whose key it lists) or of the one group that is the scope
+// (mode 2, T == 1) over all shards, slice by slice: emit(s0, ns, rows, total) receives per key of the slice where its dim sums lie
+// (a spanning key's S in the pinned state, a home shard's row, a row of +0.0) with the keys' participating counts over the whole
+// cluster.  The lanes and the handles' parts are held by the caller.
+int cluster_key_groups_sums(orr_cluster *c, const char *fn, const orr_cluster_keys *k, const orr_cluster_scope *sc, int32_t mode,
+                            const std::vector<int64_t> *table, int32_t T, int32_t dim, std::vector<Lane> &lanes, ClusterKeyGroupsWork &work,
+                            const std::function<void(int32_t, int32_t, const double *const *, const int64_t *)> &emit)
+{
+    namespace ckg = cluster_key_groups;
+    const int32_t G = (int32_t)c->shards.size();
+    const size_t D = (size_t)dim;
+    // ---- every shard at once: its pairs in candidate order, sorted by key, and its run table
+    std::vector<std::vector<int64_t>> first((size_t)G, std::vector<int64_t>((size_t)T, 0)), count((size_t)G, std::vector<int64_t>((size_t)T, 0));
+    ORR_TRY(for_each_shard(G, [&](int32_t g) -> int {
+        orr_index *lane = lanes[(size_t)g].lane;
+        if (lane->n_rows <= 0) return ORR_OK;
+        std::lock_guard<std::mutex> lock(lane->mu);
+        ORR_TRY(bind_device(lane));
+        hipStream_t s = lane->stream;
+        KeyGroupsWork &w = *work.w[(size_t)g];
+        int64_t m = 0, runs = 0;
+        ORR_TRY(key_groups_pairs(lane, k ? k->parts[(size_t)g] : nullptr, sc ? sc->parts[(size_t)g] : nullptr, mode, table, w, &m));
+        if (mode == 2) { count[(size_t)g][0] = m; return ORR_OK; }
+        ORR_TRY(key_groups_runs(lane, w, m, &runs));
+        if (runs > T) return fail(ORR_EDEVICE, "%s: %lld runs of %d keys on shard %d", fn, (long long)runs, T, g);
+        if (runs == 0) return ORR_OK;
+        std::vector<uint64_t> rk((size_t)runs);
+        std::vector<uint32_t> rl((size_t)runs);
+        HIP_TRY(hipMemcpyAsync(rk.data(), w.run_key.p, sizeof(uint64_t) * (size_t)runs, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(rl.data(), w.run_len.p, sizeof(uint32_t) * (size_t)runs, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        int64_t at = 0;
+        for (int64_t i = 0; i < runs; ++i) {
+            if (rk[(size_t)i] >= (uint64_t)T || at + (int64_t)rl[(size_t)i] > m) return fail(ORR_EDEVICE, "%s: a run outside the table on shard %d", fn, g);
+            first[(size_t)g][(size_t)rk[(size_t)i]] = at;
+            count[(size_t)g][(size_t)rk[(size_t)i]] = (int64_t)rl[(size_t)i];
+            at += (int64_t)rl[(size_t)i];
+        }
+        return ORR_OK;
+    }));
+    // ---- the host: where each key's members on a shard lie among its members anywhere
+    std::vector<std::vector<int64_t>> before((size_t)G, std::vector<int64_t>((size_t)T, 0));
+    std::vector<int64_t> total((size_t)T, 0);
+    for (int32_t t = 0; t < T; ++t)
+        for (int32_t g = 0; g < G; ++g) { before[(size_t)g][(size_t)t] = total[(size_t)t]; total[(size_t)t] += count[(size_t)g][(size_t)t]; }
+    // ---- the slices: the same keys of the call's table on every shard (the size changes no bit)
+    const int32_t per_slice = key_groups::slice_keys(dim, lanes[0].lane->opt_key_groups_slice);
+    const int32_t most = std::min(per_slice, T);
+    const std::vector<double> zeros(D, 0.0);
+    std::vector<const double *> rows((size_t)most);
+    std::vector<int32_t> state((size_t)most), slot((size_t)most), home((size_t)most);
+    std::vector<ckg::Records> rec((size_t)G);
+    std::vector<double> sums((size_t)most * D);          // the home shards' rows of the slice in flight: shard g's from row local0[g] on
+    std::vector<int64_t> local0((size_t)G + 1, 0);
+    for (int32_t s0 = 0; s0 < T; s0 += per_slice) {
+        const int32_t ns = std::min(per_slice, T - s0);
+        // a key spans where some shard holds some but not all of its members; any other key with members has one home shard,
+        // which keeps a row of sums for it
+        int32_t n_span = 0;
+        std::vector<int32_t> n_local((size_t)G, 0);
+        for (int32_t j = 0; j < ns; ++j) {
+            state[(size_t)j] = -1; slot[(size_t)j] = -1; home[(size_t)j] = -1;
+            for (int32_t g = 0; g < G; ++g) {
+                const int64_t n = count[(size_t)g][(size_t)(s0 + j)];
+                if (ckg::spans(n, total[(size_t)(s0 + j)])) { state[(size_t)j] = n_span++; break; }
+                if (n > 0) { home[(size_t)j] = g; slot[(size_t)j] = n_local[(size_t)g]++; break; }
+            }
+        }
+        for (int32_t g = 0; g < G; ++g) local0[(size_t)g + 1] = local0[(size_t)g] + n_local[(size_t)g];
+        const size_t state_bytes = sizeof(double) * 2 * D * (size_t)n_span;
+        if (n_span) {
+            ORR_TRY(work.pin.reserve(state_bytes));
+            memset(work.pin.p, 0, state_bytes);
+        }
+        // ---- every shard at once: the free blocks, and the fold of the keys wholly there -- the single index's launches
+        ORR_TRY(for_each_shard(G, [&](int32_t g) -> int {
+            ckg::Records &r = rec[(size_t)g];
+            r.clear();
+            ckg::records_of(ns, count[(size_t)g].data() + s0, first[(size_t)g].data() + s0, before[(size_t)g].data() + s0, total.data() + s0, state.data(),
+                            slot.data(), r);
+            if (r.blocks.empty()) return ORR_OK;
+            orr_index *lane = lanes[(size_t)g].lane;
+            std::lock_guard<std::mutex> lock(lane->mu);
+            ORR_TRY(bind_device(lane));
+            hipStream_t s = lane->stream;
+            KeyGroupsWork &w = *work.w[(size_t)g];
+            ORR_TRY(key_groups_slice_launch(lane, w, n_local[(size_t)g], r.blocks, r.folds, r.n_parts));
+            const size_t bytes = sizeof(double) * (size_t)n_local[(size_t)g] * D;
+            if (bytes) HIP_TRY(hipMemcpyAsync(sums.data() + (size_t)local0[(size_t)g] * D, w.sums.p, bytes, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            return ORR_OK;
+        }));
+        // ---- the chain: shards in ascending order, only where a spanning key of the slice has members
+        for (int32_t g = 0; g < G && n_span; ++g) {
+            const ckg::Records &r = rec[(size_t)g];
+            if (r.chains.empty()) continue;             // (the carry passes over this shard)
+            orr_index *lane = lanes[(size_t)g].lane;
+            std::lock_guard<std::mutex> lock(lane->mu);
+            ORR_TRY(bind_device(lane));
+            hipStream_t s = lane->stream;
+            KeyGroupsWork &w = *work.w[(size_t)g];
+            uint32_t lo = r.chains[0].state, hi = lo;
+            double head_rows = 0.0, part_rows = 0.0;
+            for (const ckg::Chain &ch : r.chains) {
+                lo = std::min(lo, ch.state); hi = std::max(hi, ch.state);
+                head_rows += (double)ch.head_len;
+                part_rows += (double)ch.n_close + 4.0;
+                if (ch.state >= (uint32_t)n_span || ch.head_len >= (uint32_t)key_groups::kBlock ||
+                    (size_t)ch.part0 + ch.n_close + (ckg::chain_open(ch.flags) == ckg::kOpenFree ? 1u : 0u) > (size_t)r.n_parts)
+                    return fail(ORR_EDEVICE, "%s: a chain record outside its slice on shard %d", fn, g);
+            }
+            ORR_TRY(work.chains[(size_t)g].reserve(sizeof(ckg::Chain) * r.chains.size()));
+            ORR_TRY(work.state[(size_t)g].reserve(state_bytes));
+            // the state rows of the shard's spanning keys (one range of slots) go up, the step runs, the same rows come back
+            const size_t off = sizeof(double) * 2 * D * (size_t)lo, len = sizeof(double) * 2 * D * (size_t)(hi - lo + 1);
+            HIP_TRY(hipMemcpyAsync(work.chains[(size_t)g].p, r.chains.data(), sizeof(ckg::Chain) * r.chains.size(), hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(work.state[(size_t)g].as<char>() + off, work.pin.as<char>() + off, len, hipMemcpyHostToDevice, s));
+            {
+                Timed t(lane, "keys_chain_step", 4.0 * head_rows * (double)dim + 8.0 * part_rows * (double)dim);
+                HIP_TRY(orr::launch_keys_chain_step(lane->d_emb, lane->n_rows, dim, w.pos, work.chains[(size_t)g].as<ckg::Chain>(), (int64_t)r.chains.size(),
+                                                    w.parts.as<double>(), work.state[(size_t)g].as<double>(), s));
+            }
+            HIP_TRY(hipMemcpyAsync(work.pin.as<char>() + off, work.state[(size_t)g].as<char>() + off, len, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+        // ---- the slice's rows: a spanning key's S, a home shard's row, +0.0 for a key without a participating member
+        for (int32_t j = 0; j < ns; ++j) {
+            if (state[(size_t)j] >= 0) rows[(size_t)j] = work.pin.as<double>() + (size_t)state[(size_t)j] * 2 * D;
+            else if (home[(size_t)j] >= 0) rows[(size_t)j] = sums.data() + (size_t)(local0[(size_t)home[(size_t)j]] + slot[(size_t)j]) * D;
+            else rows[(size_t)j] = zeros.data();
+        }
+        emit(s0, ns, rows.data(), total.data() + s0);
+    }
+    return ORR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int orr_cluster_keys_groups(orr_cluster_keys *k, const orr_cluster_scope *within, int64_t cap, int64_t *out_keys, int64_t *out_rows, int64_t *out_n,
+                            int64_t *out_total)
+{
+    static const char *fn = "orr_cluster_keys_groups";
+    switch (cluster_key_groups::first_invalid_groups(cap, !out_keys, !out_rows, !out_n, !out_total, !k)) {
+    case 0: break;
+    case 1: return fail(ORR_EINVAL, "%s: cap is negative", fn);
+    case 2: return fail(ORR_EINVAL, "%s: out_n or out_total is NULL", fn);
+    case 3: return fail(ORR_EINVAL, "%s: out_keys or out_rows is NULL with room for %lld keys", fn, (long long)cap);
+    default: return fail(ORR_EINVAL, "%s: null keys", fn);
+    }
+    orr_cluster *c = nullptr, *sown = nullptr;
+    ORR_TRY(cluster_keys_owner(k, fn, &c));
+    if (within) ORR_TRY(cluster_scope_owner(within, fn, &sown));
+    if (within && (sown != c || within->parts.size() != k->parts.size())) return fail(ORR_EINVAL, "%s: the scope belongs to another cluster", fn);
+    std::shared_lock<std::shared_mutex> lock(c->mu);   // like a search: beside the others; seal, compact, insert are exclusive
+    const int32_t G = (int32_t)c->shards.size();
+    std::vector<Lane> lanes;
+    std::vector<std::shared_lock<std::shared_mutex>> held;
+    ORR_TRY(cluster_key_groups_hold(c, fn, k, within, lanes, held));
+    ClusterKeyGroupsWork work(c);
+    std::vector<std::vector<int64_t>> gk((size_t)G), gn((size_t)G);
+    const int r = for_each_shard(G, [&](int32_t g) -> int {
+        orr_index *lane = lanes[(size_t)g].lane;
+        if (lane->n_rows <= 0) return ORR_OK;
+        std::lock_guard<std::mutex> l(lane->mu);
+        ORR_TRY(bind_device(lane));
+        hipStream_t s = lane->stream;
+        KeyGroupsWork &w = *work.w[(size_t)g];
+        int64_t m = 0, runs = 0;
+        ORR_TRY(key_groups_pairs(lane, k->parts[(size_t)g], within ? within->parts[(size_t)g] : nullptr, 0, nullptr, w, &m));
+        ORR_TRY(key_groups_runs(lane, w, m, &runs));
+        if (runs == 0) return ORR_OK;
+        std::vector<uint32_t> len((size_t)runs);
+        gk[(size_t)g].resize((size_t)runs);
+        HIP_TRY(hipMemcpyAsync(gk[(size_t)g].data(), w.run_key.p, sizeof(uint64_t) * (size_t)runs, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(len.data(), w.run_len.p, sizeof(uint32_t) * (size_t)runs, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        gn[(size_t)g].resize((size_t)runs);
+        for (int64_t i = 0; i < runs; ++i) {
+            gk[(size_t)g][(size_t)i] = key_groups::key_of_sort((uint64_t)gk[(size_t)g][(size_t)i]);
+            gn[(size_t)g][(size_t)i] = (int64_t)len[(size_t)i];
+        }
+        return ORR_OK;
+    });
+    cluster_key_groups_end(lanes);
+    if (r != ORR_OK) return r;
+    std::vector<int64_t> mk, mn;
+    const int64_t total = cluster_key_groups::merge_groups(gk, gn, cap, mk, mn);
+    for (size_t i = 0; i < mk.size(); ++i) { out_keys[i] = mk[i]; out_rows[i] = mn[i]; }
+    *out_total = total;
+    *out_n = (int64_t)mk.size();
+    return ORR_OK;
+}
+
+int orr_cluster_keys_centroids(orr_cluster_keys *k, const orr_cluster_scope *within, int32_t n_keys, const int64_t *keys, int32_t dim,
+                               float *out_centroids, double *out_sums, int64_t *out_used)
+{
+    static const char *fn = "orr_cluster_keys_centroids";
+    switch (cluster_key_groups::first_invalid_centroids(n_keys, !keys, !out_used, !k)) {
+    case 0: break;
+    case 1: return fail(ORR_EINVAL, "%s: n_keys must be in 0 .. %d", fn, key_groups::kMaxKeys);
+    case 2: return fail(ORR_EINVAL, "%s: keys is NULL with %d keys", fn, n_keys);
+    case 3: return fail(ORR_EINVAL, "%s: out_used is NULL with %d keys", fn, n_keys);
+    default: return fail(ORR_EINVAL, "%s: null keys", fn);
+    }
+    orr_cluster *c = nullptr, *sown = nullptr;
+    ORR_TRY(cluster_keys_owner(k, fn, &c));
+    if (within) ORR_TRY(cluster_scope_owner(within, fn, &sown));
+    if (within && (sown != c || within->parts.size() != k->parts.size())) return fail(ORR_EINVAL, "%s: the scope belongs to another cluster", fn);
+    std::shared_lock<std::shared_mutex> lock(c->mu);
+    std::vector<Lane> lanes;
+    std::vector<std::shared_lock<std::shared_mutex>> held;
+    ORR_TRY(cluster_key_groups_hold(c, fn, k, within, lanes, held));
+    if (dim <= 0 || dim != lanes[0].lane->dim) return fail(ORR_EDIM, "%s: dim %d differs from the index dimension %d (and must be greater than 0)", fn, dim, lanes[0].lane->dim);
+    if (n_keys == 0) return ORR_OK;
+    if (is_device_pointer(keys)) return fail(ORR_EINVAL, "%s: keys must be in host memory (every shard's device reads them)", fn);
+    // the sorted table of the distinct keys listed; the listed keys in the table's order (a key listed twice is answered twice)
+    const std::vector<int64_t> table = per_key::member_table(keys, n_keys);
+    const int32_t T = (int32_t)table.size();
+    std::vector<int32_t> slot_of((size_t)n_keys), by_slot((size_t)n_keys);
+    for (int32_t i = 0; i < n_keys; ++i) { slot_of[(size_t)i] = per_key::table_find(table.data(), T, keys[i]); by_slot[(size_t)i] = i; }
+    std::stable_sort(by_slot.begin(), by_slot.end(), [&](int32_t a, int32_t b) { return slot_of[(size_t)a] < slot_of[(size_t)b]; });
+    ClusterKeyGroupsWork work(c);
+    size_t next = 0;                                   // of by_slot
+    const int r = cluster_key_groups_sums(c, fn, k, within, 1, &table, T, dim, lanes, work, [&](int32_t s0, int32_t ns, const double *const *rows, const int64_t *total) {
+        for (; next < by_slot.size() && slot_of[(size_t)by_slot[next]] < s0 + ns; ++next) {
+            const int32_t i = by_slot[next], j = slot_of[(size_t)i] - s0;
+            const double *S = rows[j];
+            out_used[i] = total[j];
+            if (out_sums) memcpy(out_sums + (size_t)i * (size_t)dim, S, sizeof(double) * (size_t)dim);
+            if (out_centroids) key_groups::finish(S, total[j], dim, out_centroids + (size_t)i * (size_t)dim);
+        }
+    });
+    cluster_key_groups_end(lanes);
+    return r;
+}
+
+int orr_cluster_scope_centroid(orr_cluster_scope *sc, int32_t dim, float *out_centroid, double *out_sum, int64_t *out_used)
+{
+    static const char *fn = "orr_cluster_scope_centroid";
+    switch (cluster_key_groups::first_invalid_scope_centroid(!out_used, !sc)) {
+    case 0: break;
+    case 1: return fail(ORR_EINVAL, "%s: out_used is NULL", fn);
+    default: return fail(ORR_EINVAL, "%s: null scope", fn);
+    }
+    orr_cluster *c = nullptr;
+    ORR_TRY(cluster_scope_owner(sc, fn, &c));
+    std::shared_lock<std::shared_mutex> lock(c->mu);
+    std::vector<Lane> lanes;
+    std::vector<std::shared_lock<std::shared_mutex>> held;
+    ORR_TRY(cluster_key_groups_hold(c, fn, nullptr, sc, lanes, held));
+    if (dim <= 0 || dim != lanes[0].lane->dim) return fail(ORR_EDIM, "%s: dim %d differs from the index dimension %d (and must be greater than 0)", fn, dim, lanes[0].lane->dim);
+    ClusterKeyGroupsWork work(c);
+    std::vector<double> sum((size_t)dim, 0.0);
+    int64_t used = 0;
+    const int r = cluster_key_groups_sums(c, fn, nullptr, sc, 2, nullptr, 1, dim, lanes, work, [&](int32_t, int32_t, const double *const *rows, const int64_t *total) {
+        memcpy(sum.data(), rows[0], sizeof(double) * (size_t)dim);
+        used = total[0];
+    });
+    cluster_key_groups_end(lanes);
+    if (r != ORR_OK) return r;
+    *out_used = used;
+    if (out_sum) memcpy(out_sum, sum.data(), sizeof(double) * (size_t)dim);
+    if (out_centroid) key_groups::finish(sum.data(), used, dim, out_centroid);
+    return ORR_OK;
 }
 
 }  // extern "C"

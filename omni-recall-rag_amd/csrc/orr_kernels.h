@@ -16,6 +16,7 @@
 #include "orr_diverse_plan.h"
 #include "orr_per_key_plan.h"
 #include "orr_key_groups_plan.h"
+#include "orr_cluster_key_groups_plan.h"
 #include "orr_keyword_plan.h"
 
 #include <atomic>
@@ -541,6 +542,12 @@ hipError_t launch_keys_block_sums(const float *emb, int64_t n_rows, int32_t dim,
                                   int64_t n_blocks, double *sums, double *parts, hipStream_t s);
 // sums[slot] = +0.0 + parts[part0] + ... + parts[part0 + n_blocks - 1], in this order, for each of the n_folds keys.
 hipError_t launch_keys_block_fold(const key_groups::Fold *folds, int64_t n_folds, const double *parts, int32_t dim, double *sums, hipStream_t s);
+// keys_chain_step: one workgroup per Chain record and 1,024 coordinates.  The record's key continues on this shard from its state
+// rows (S: row 2 * state, P: row 2 * state + 1 of state [.][dim]): the head fragment pos[head_first .. + head_len) on top of the
+// carried P, the closed blocks (the head's, then rows part0 .. part0 + n_close - 1 of parts) on top of the carried S, in this
+// order; S and the open block's partial are written back (cluster_key_groups::Chain says it add for add).
+hipError_t launch_keys_chain_step(const float *emb, int64_t n_rows, int32_t dim, const uint32_t *pos, const cluster_key_groups::Chain *chains,
+                                  int64_t n_chains, const double *parts, double *state, hipStream_t s);
 
 // ---- term scopes (orr_scope_create_terms; the rules are orr_scope_terms_plan.h's) -------------------------------------------
 // term_base[t] (device, and its copy term_base_host in pinned memory when given) = where distinct term t's row bitmap starts, in

@@ -2691,6 +2691,118 @@ hipError_t launch_keys_block_fold(const key_groups::Fold *folds, int64_t n_folds
     return hipGetLastError();
 }
 
+// ---- cluster key groups (orr_cluster_keys_centroids, orr_cluster_scope_centroid; the rules are orr_cluster_key_groups_plan.h's) --
+// keys_chain_step: one shard's step of the keys that span shards.  One workgroup per Chain record and 1,024 coordinates, the lane
+// layout of keys_block_sums (a lane owns four consecutive coordinates; one 16-byte load per head row where VEC).  Per coordinate,
+// strictly in this order, all fp64: P from the carried P row (or +0.0) over the head fragment in member order; S from the carried S
+// row (or +0.0), plus P where the head's block closes here, plus the partial rows of the free blocks that close here in block order
+// (double2 loads, eight ahead, as keys_block_fold); S and the open block's partial go to the key's state rows.
+template <bool VEC>
+__global__ __launch_bounds__(256) void key_groups_chain_kernel(const float *__restrict__ emb, int32_t dim, const uint32_t *__restrict__ pos,
+                                                         const cluster_key_groups::Chain *__restrict__ chains,
+                                                         const double *__restrict__ parts, double *__restrict__ state)
+{
+    __shared__ uint32_t sh_pos[key_groups::kBlock];
+    const cluster_key_groups::Chain c = chains[blockIdx.x];
+    const int tid = threadIdx.x;
+    if ((uint32_t)tid < c.head_len) sh_pos[tid] = pos[(size_t)c.head_first + tid];
+    __syncthreads();
+    const int32_t d0 = (int32_t)blockIdx.y * key_groups::kCoordsPerPass + tid * key_groups::kCoordsPerLane;
+    if (d0 >= dim) return;
+    const bool in1 = d0 + 1 < dim, in2 = d0 + 2 < dim, in3 = d0 + 3 < dim;
+    double *s_row = state + (size_t)c.state * 2 * dim + d0, *p_row = s_row + dim;
+    auto load_row = [&](const double *row, double &x0, double &x1, double &x2, double &x3) {
+        if (VEC) {
+            const double2 lo = *reinterpret_cast<const double2 *>(row), hi = *reinterpret_cast<const double2 *>(row + 2);
+            x0 = lo.x; x1 = lo.y; x2 = hi.x; x3 = hi.y;
+        } else {
+            x0 = row[0]; x1 = in1 ? row[1] : +0.0; x2 = in2 ? row[2] : +0.0; x3 = in3 ? row[3] : +0.0;
+        }
+    };
+    auto store_row = [&](double *row, double x0, double x1, double x2, double x3) {
+        if (VEC) {
+            *reinterpret_cast<double2 *>(row) = make_double2(x0, x1);
+            *reinterpret_cast<double2 *>(row + 2) = make_double2(x2, x3);
+        } else {
+            row[0] = x0;
+            if (in1) row[1] = x1;
+            if (in2) row[2] = x2;
+            if (in3) row[3] = x3;
+        }
+    };
+    // 1, 2: the head fragment continues the open block
+    double p0 = +0.0, p1 = +0.0, p2 = +0.0, p3 = +0.0;
+    if (cluster_key_groups::chain_seed_p(c.flags)) load_row(p_row, p0, p1, p2, p3);
+    auto load = [&](uint32_t i) -> float4 {
+        const float *row = emb + (size_t)sh_pos[i] * dim + d0;
+        if (VEC) return *reinterpret_cast<const float4 *>(row);
+        return make_float4(row[0], in1 ? row[1] : 0.f, in2 ? row[2] : 0.f, in3 ? row[3] : 0.f);
+    };
+    uint32_t i = 0;
+    for (; i + 8 <= c.head_len; i += 8) {
+        float4 v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = load(i + j);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            p0 = p0 + (double)v[j].x; p1 = p1 + (double)v[j].y; p2 = p2 + (double)v[j].z; p3 = p3 + (double)v[j].w;
+        }
+    }
+    for (; i < c.head_len; ++i) {
+        const float4 v = load(i);
+        p0 = p0 + (double)v.x; p1 = p1 + (double)v.y; p2 = p2 + (double)v.z; p3 = p3 + (double)v.w;
+    }
+    // 3: the running sum, and the head's block where it closes here
+    double s0 = +0.0, s1 = +0.0, s2 = +0.0, s3 = +0.0;
+    if (cluster_key_groups::chain_seed_s(c.flags)) load_row(s_row, s0, s1, s2, s3);
+    if (cluster_key_groups::chain_head_closes(c.flags)) {
+        s0 = s0 + p0; s1 = s1 + p1; s2 = s2 + p2; s3 = s3 + p3;
+    }
+    // 4: the free blocks that close here, in block order
+    const double *q = parts + (size_t)c.part0 * dim + d0;
+    uint32_t b = 0;
+    for (; b + 8 <= c.n_close; b += 8) {
+        double w[8][4];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) load_row(q + (size_t)(b + j) * dim, w[j][0], w[j][1], w[j][2], w[j][3]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            s0 = s0 + w[j][0]; s1 = s1 + w[j][1]; s2 = s2 + w[j][2]; s3 = s3 + w[j][3];
+        }
+    }
+    for (; b < c.n_close; ++b) {
+        double w0, w1, w2, w3;
+        load_row(q + (size_t)b * dim, w0, w1, w2, w3);
+        s0 = s0 + w0; s1 = s1 + w1; s2 = s2 + w2; s3 = s3 + w3;
+    }
+    // 5: the state the next shard with a member continues from
+    store_row(s_row, s0, s1, s2, s3);
+    const uint32_t open = cluster_key_groups::chain_open(c.flags);
+    if (open == cluster_key_groups::kOpenHead) {
+        store_row(p_row, p0, p1, p2, p3);
+    } else if (open == cluster_key_groups::kOpenFree) {
+        double w0, w1, w2, w3;
+        load_row(q + (size_t)c.n_close * dim, w0, w1, w2, w3);
+        store_row(p_row, w0, w1, w2, w3);
+    }
+}
+
+hipError_t launch_keys_chain_step(const float *emb, int64_t n_rows, int32_t dim, const uint32_t *pos, const cluster_key_groups::Chain *chains,
+                                  int64_t n_chains, const double *parts, double *state, hipStream_t s)
+{
+    if (n_chains <= 0) return hipSuccess;
+    const int64_t tiles = ((int64_t)dim + key_groups::kCoordsPerPass - 1) / key_groups::kCoordsPerPass;
+    if (!emb || n_rows <= 0 || dim <= 0 || !pos || !chains || !state || n_chains > (int64_t)0x7FFFFFFF || tiles > 65535) return hipErrorInvalidValue;
+    const bool vec = dim % 4 == 0 && reinterpret_cast<uintptr_t>(emb) % 16 == 0 && reinterpret_cast<uintptr_t>(state) % 16 == 0 &&
+                     reinterpret_cast<uintptr_t>(parts) % 16 == 0;
+    const dim3 grid((unsigned)n_chains, (unsigned)tiles);
+    if (vec)
+        hipLaunchKernelGGL(key_groups_chain_kernel<true>, grid, dim3(256), 0, s, emb, dim, pos, chains, parts, state);
+    else
+        hipLaunchKernelGGL(key_groups_chain_kernel<false>, grid, dim3(256), 0, s, emb, dim, pos, chains, parts, state);
+    return hipGetLastError();
+}
+
 // ---- term scopes (orr_scope_create_terms; the rules are orr_scope_terms_plan.h's) -------------------------------------------
 
 // where each distinct term's bitmap starts (n <= 256 values: one workgroup)

@@ -22,8 +22,8 @@
 //   slices        the fp64 sums of a call are formed in slices of slice_keys(dim, option) keys: kSliceBytes of sums at most,
 //                 whatever the call lists ("key_groups_slice": 0 this rule, 1 .. kMaxKeys forces a size).
 //
-// Out of scope: the cluster forms (a document cut by a shard border would need the blocked order defined across shards; a host
-// may ask each shard through orr_cluster_keys_shard, but such per-shard sums are not the single index's bits), a mean of
+// Out of scope: the cluster forms (built since: orr_cluster_key_groups_plan.h defines the blocked order across shards; a host
+// may still ask each shard through orr_cluster_keys_shard, but such per-shard sums are not the single index's bits), a mean of
 // unit-normalised rows or a weighted mean, sharded.py, the service mirror and the micro-batcher, keys in the shard file, a search
 // that ranks documents by centroid.
 //

@@ -358,6 +358,33 @@ class RecallClusterKeys:
         """orr_cluster_keys_rows: live rows whose key is not KEY_NONE, over all shards; -1 once it is orphaned."""
         return int(N.hip.orr_cluster_keys_rows(self._h))
 
+    def groups(self, within: Optional["RecallClusterScope"] = None, cap: Optional[int] = None):
+        """orr_cluster_keys_groups: (keys, rows) -- RecallKeys.groups of one index holding all the cluster's rows: the distinct
+        keys other than KEY_NONE among the live rows (of `within`), ascending, and how many rows carry each, over all shards."""
+        wh = within._h if within is not None else None
+        n, total = C.c_int64(0), C.c_int64(0)
+        pn, pt = C.cast(C.byref(n), C.c_void_p), C.cast(C.byref(total), C.c_void_p)
+        if cap is None:
+            N.check(N.hip.orr_cluster_keys_groups(self._h, wh, 0, None, None, pn, pt))
+            cap = int(total.value)
+        keys = np.zeros(int(cap), dtype=np.int64)
+        rows = np.zeros(int(cap), dtype=np.int64)
+        N.check(N.hip.orr_cluster_keys_groups(self._h, wh, int(cap), _ptr(keys) if cap else None, _ptr(rows) if cap else None, pn, pt))
+        return keys[:int(n.value)], rows[:int(n.value)]
+
+    def centroids(self, keys, within: Optional["RecallClusterScope"] = None, sums: bool = False):
+        """orr_cluster_keys_centroids: (centroids [n, dim] float32, used [n] int64) -- RecallKeys.centroids of one index holding
+        all the cluster's rows in the global candidate order, bit for bit: a key's blocks of 256 are counted from its first
+        member on any shard.  sums=True: (centroids, sums [n, dim] float64, used)."""
+        ks = np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)
+        n, dim = int(ks.shape[0]), int(self._cluster.dim)
+        cent = np.zeros((n, dim), dtype=np.float32)
+        S = np.zeros((n, dim), dtype=np.float64) if sums else None
+        used = np.zeros(n, dtype=np.int64)
+        N.check(N.hip.orr_cluster_keys_centroids(self._h, within._h if within is not None else None, n, _ptr(ks) if n else None, dim,
+                                                 _ptr(cent) if cent.size else None, _ptr(S) if sums and S.size else None, _ptr(used) if n else None))
+        return (cent, S, used) if sums else (cent, used)
+
     def shard(self, i: int) -> RecallKeys:
         """orr_cluster_keys_shard: shard i's part, borrowed."""
         p = N.hip.orr_cluster_keys_shard(self._h, int(i))
@@ -412,6 +439,16 @@ class RecallClusterScope:
         out = np.zeros(max(self.rows, 0), dtype=np.int64)
         N.check(N.hip.orr_cluster_scope_row_ids(self._h, int(out.shape[0]), _ptr(out) if out.shape[0] else None, C.cast(C.byref(n), C.c_void_p)))
         return out[:int(n.value)]
+
+    def centroid(self, sums: bool = False):
+        """orr_cluster_scope_centroid: (centroid [dim] float32, used) -- RecallScope.centroid of one index holding all the
+        cluster's rows in the global candidate order, bit for bit.  sums=True: (centroid, sum [dim] float64, used)."""
+        dim = int(self._cluster.dim)
+        cent = np.zeros(dim, dtype=np.float32)
+        S = np.zeros(dim, dtype=np.float64)
+        used = C.c_int64(0)
+        N.check(N.hip.orr_cluster_scope_centroid(self._h, dim, _ptr(cent) if dim else None, _ptr(S) if dim else None, C.cast(C.byref(used), C.c_void_p)))
+        return (cent, S, int(used.value)) if sums else (cent, int(used.value))
 
     def add_ids(self, row_ids) -> int:
         """orr_cluster_scope_add_ids: the live rows that carry these ids (numpy, host memory) join the scope on every shard.
