@@ -800,7 +800,8 @@ int orr_search_batch_per_key(orr_index *idx, int32_t B, int32_t dim, const float
  * orr_cluster_scope_centroid below define the blocked order across shards; a host may still ask each shard through
  * orr_cluster_keys_shard, but such per-shard sums added up ARE NOT the single index's bits), a mean
  * of unit-normalised rows or a weighted mean, sharded.py, the service mirror and the micro-batcher, keys in the shard file, a
- * search call that ranks documents by centroid. */
+ * search call that ranks documents by centroid (built since: §8x, orr_keys_centroid_index below makes the centroids of all keys
+ * the rows of an ordinary orr_index, which every search call then ranks). */
 #define ORR_KEY_GROUPS_BLOCK 256
 int orr_keys_groups(orr_keys *k, const orr_scope *within /* or NULL */, int64_t cap,
                     int64_t *out_keys /* host [cap] */, int64_t *out_rows /* host [cap] */,
@@ -810,6 +811,49 @@ int orr_keys_centroids(orr_keys *k, const orr_scope *within /* or NULL */, int32
                        double *out_sums /* host [n_keys][dim], may be NULL */, int64_t *out_used /* host [n_keys] */);
 int orr_scope_centroid(orr_scope *s, int32_t dim, float *out_centroid /* host [dim], may be NULL */,
                        double *out_sum /* host [dim], may be NULL */, int64_t *out_used);
+
+/* ---- document index: one centroid row per key, built on the device; stored rows read back -----------------------------------
+ * orr_keys_centroid_index builds a sealed orr_index whose rows are the centroids of ALL keys of a key column, entirely on the
+ * device; search, range search, cosine scopes, diverse search, save / load and the maintenance calls then work on documents
+ * unchanged: the result is an ordinary orr_index.  The rules are csrc/orr_centroid_index_plan.h's.
+ *
+ * THE CONTRACT IS A TWIN.  The returned index answers every call bit for bit like the index a host would build this way, on
+ * the same device:
+ *   1. orr_keys_groups(k, within, ...) for all distinct keys, ascending; ORR_KEY_NONE is never among them.
+ *   2. orr_keys_centroids(k, within, those keys, ...), in as many calls as the 65,536 limit needs: the float centroids and out_used.
+ *   3. Every key with out_used == 0 is dropped: *out_skipped counts the dropped keys, *out_docs the kept ones.
+ *   4. For each kept key in ascending key order one row: embedding = that centroid, the bits of THE RULE above,
+ *      (float)(S[d] / (double)n); created_ticks = the CreatedAt ticks of the key's first participating member in candidate order,
+ *      the newest chunk that takes part; row_id = the key itself; content = empty, so a document's keyword score is 0.
+ *   5. orr_index_create with the source's device and dim, orr_index_append of those rows, orr_index_seal.
+ * Lifetime: the result is an independent, caller-owned index, freed with orr_index_destroy.  It is a snapshot: it is registered
+ * with nothing, does not follow later maintenance of the source, and outlives the source.  The ordinary maintenance calls
+ * refresh it.  On any error the partial index is destroyed and *out is not written.
+ * ORR_EINVAL before any handle is looked at, in this order: out NULL; k NULL.  After that the errors of orr_keys_centroids, in
+ * its order: ORR_EINVAL for a scope of another shard, ORR_ESTATE for an orphaned handle, ORR_EDIM for a source with dim == 0.
+ * Locks and lanes are orr_keys_centroids'; the call works through views.
+ * On the device: no sum and no centroid crosses the bus.  Only small per-key tables go to the host -- run keys, run lengths and
+ * ticks, 8 bytes per key each.  The pairs (a mode of their own: the participating members, sorted by the key itself), the sort
+ * and the run-length steps are orr_keys_centroids'; keys_block_sums and keys_block_fold run in slices of keys
+ * (key_groups::slice_keys, "key_groups_slice"; the 65,536 limit does not apply); keys_centroid_finish divides a slice's fp64
+ * sums by the member counts (plain IEEE fp64 division, round to nearest even: key_groups::finish_one, the host's expression),
+ * writes the fp32 centroids of the kept keys densely and gathers their ticks (keys_first_ticks, folded into the launch); a
+ * finished slice goes into the result through orr_index_append, device to device.
+ * Out of scope: a cluster form (the host route over orr_cluster_keys_centroids remains), caller-supplied content per document
+ * (titles for the keyword score), a routed two-level call (top-r documents, then search inside them: it composes from this
+ * index, orr_scope_create_keys and orr_search_batch_in_scopes), keeping the derived index in step with the source
+ * automatically, sharded.py, the service mirror and the micro-batcher, keys in the shard file, a pinned return path for
+ * orr_keys_centroids.
+ *
+ * orr_index_get_rows returns the stored fp32 embedding of each listed live row, bit for bit (a sealed index or a view).  An
+ * unknown or deleted id gives zeros and found 0; a row without an embedding gives the stored zeros and found 1.  A wrong dim, or
+ * a dim of 0, is ORR_EDIM.  The id lookup is orr_keys_get's, the gather is rows_gather in slices of at most 64 MiB of workspace;
+ * the call takes a lane like orr_keys_get.  ORR_EINVAL before the handle is looked at: n negative; row_ids or out_emb NULL with
+ * n > 0; idx NULL. */
+int orr_keys_centroid_index(orr_keys *k, const orr_scope *within /* or NULL */, orr_index **out,
+                            int64_t *out_docs /* may be NULL */, int64_t *out_skipped /* may be NULL */);
+int orr_index_get_rows(orr_index *idx, int64_t n, const int64_t *row_ids /* host */, int32_t dim,
+                       float *out_emb /* host [n][dim] */, uint8_t *out_found /* host [n], may be NULL */);
 
 /* orr_search_shard_masked with the scope taken from a handle: the record form of orr_search_batch_in_scope, the shard half of
  * orr_cluster_search_batch_in_scope.  The contract is orr_search_shard_masked's, unchanged: [B][kprime+1] records and the

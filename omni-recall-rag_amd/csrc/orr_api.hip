@@ -7427,8 +7427,8 @@ struct KeyGroupsWork {
 };
 
 // The call's selected rows as pairs in candidate order (launch_keys_pairs: mode 0 the rows with a key, 1 the participating rows
-// whose key is in `table`, 2 the participating rows of `within`), sorted by key for modes 0 and 1 (stable: positions stay
-// ascending within a key).  *out_m = their number; ends synchronised.
+// whose key is in `table`, 2 the participating rows of `within`, 3 the participating rows with a key), sorted by key for modes
+// 0, 1 and 3 (stable: positions stay ascending within a key).  *out_m = their number; ends synchronised.
 int key_groups_pairs(orr_index *lane, const orr_keys *k, const orr_scope *within, int32_t mode, const std::vector<int64_t> *table,
                      KeyGroupsWork &w, int64_t *out_m)
 {
@@ -7762,6 +7762,191 @@ int orr_scope_centroid(orr_scope *sc, int32_t dim, float *out_centroid, double *
     if (out_sum) memcpy(out_sum, sum.data(), sizeof(double) * (size_t)dim);
     if (out_centroid) key_groups::finish(sum.data(), m, dim, out_centroid);
     return ORR_OK;
+}
+
+// ---- the document index (orr_keys_centroid_index, orr_index_get_rows; the rules are orr_centroid_index_plan.h's) ----------------
+
+namespace {
+
+// What orr_keys_centroid_index owns on the device besides its key-groups work: a slice's kept keys, their fp32 centroids and ticks.
+struct CentroidIndexWork {
+    DevBuf kept, cent, ticks;
+    ~CentroidIndexWork()
+    {
+        for (DevBuf *b : {&kept, &cent, &ticks}) b->release();
+    }
+};
+
+// The body of orr_keys_centroid_index behind its locks: `res` is the fresh index the slices are appended to.  No sum and no
+// centroid leaves the device: the host sees the keys, the run lengths and (inside orr_index_append) the ticks.
+int centroid_index_fill(orr_index *lane, const orr_keys *k, const orr_scope *within, orr_index *res, int64_t *docs, int64_t *skipped)
+{
+    static const char *fn = "orr_keys_centroid_index";
+    hipStream_t s = lane->stream;
+    const int32_t dim = lane->dim;
+    // everything a queued copy or launch may still touch lives until the stream is synchronised below, on every path
+    KeyGroupsWork wa, w;
+    CentroidIndexWork cw;
+    std::vector<uint64_t> all, rk, no_content;
+    std::vector<uint32_t> rl;
+    std::vector<int64_t> used, first, ids;
+    std::vector<key_groups::Block> blocks;
+    std::vector<key_groups::Fold> folds;
+    std::vector<centroid_index::Kept> kept;
+    auto body = [&]() -> int {
+        // all distinct keys of the members, ascending (orr_keys_groups' list) ...
+        int64_t m0 = 0, T = 0;
+        ORR_TRY(key_groups_pairs(lane, k, within, 0, nullptr, wa, &m0));
+        ORR_TRY(key_groups_runs(lane, wa, m0, &T));
+        all.resize((size_t)T);
+        if (T > 0) {
+            HIP_TRY(hipMemcpyAsync(all.data(), wa.run_key.p, sizeof(uint64_t) * (size_t)T, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+        // ... and the participating members sorted by the same key: each key's count and the pair its run starts at
+        int64_t m = 0, runs = 0;
+        ORR_TRY(key_groups_pairs(lane, k, within, 3, nullptr, w, &m));
+        ORR_TRY(key_groups_runs(lane, w, m, &runs));
+        rk.resize((size_t)runs);
+        rl.resize((size_t)runs);
+        if (runs > 0) {
+            HIP_TRY(hipMemcpyAsync(rk.data(), w.run_key.p, sizeof(uint64_t) * (size_t)runs, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(rl.data(), w.run_len.p, sizeof(uint32_t) * (size_t)runs, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+        if (!centroid_index::merge_runs(all.data(), T, rk.data(), rl.data(), runs, m, used, first))
+            return fail(ORR_EDEVICE, "%s: the participating runs do not fit the keys", fn);
+        const int32_t per_slice = key_groups::slice_keys(dim, lane->opt_key_groups_slice);
+        for (const centroid_index::Slice &sl : centroid_index::walk(used.data(), T, per_slice)) {
+            if (sl.n_kept == 0) continue;              // (every key of the slice is skipped: nothing to launch, nothing to append)
+            blocks.clear(); folds.clear(); kept.clear(); ids.clear();
+            uint32_t n_parts = 0;
+            for (int32_t j = 0; j < sl.n_keys; ++j)
+                key_groups::blocks_of(used[(size_t)(sl.key0 + j)], first[(size_t)(sl.key0 + j)], (uint32_t)j, blocks, folds, n_parts);
+            centroid_index::slice_kept(used.data(), first.data(), sl.key0, sl.n_keys, kept);
+            for (const centroid_index::Kept &kk : kept) ids.push_back(key_groups::key_of_sort(all[(size_t)sl.key0 + kk.slot]));
+            const size_t nk = kept.size();
+            ORR_TRY(key_groups_slice_launch(lane, w, sl.n_keys, blocks, folds, n_parts));
+            ORR_TRY(cw.kept.reserve(sizeof(centroid_index::Kept) * nk));
+            ORR_TRY(cw.cent.reserve(sizeof(float) * nk * (size_t)dim));
+            ORR_TRY(cw.ticks.reserve(sizeof(int64_t) * nk));
+            HIP_TRY(hipMemcpyAsync(cw.kept.p, kept.data(), sizeof(centroid_index::Kept) * nk, hipMemcpyHostToDevice, s));
+            {
+                Timed t(lane, "keys_centroid_finish", (8.0 + 4.0) * (double)dim * (double)nk);
+                HIP_TRY(orr::launch_keys_centroid_finish(w.sums.as<double>(), dim, cw.kept.as<centroid_index::Kept>(), (int64_t)nk, w.pos, lane->d_created,
+                                                         cw.cent.as<float>(), cw.ticks.as<int64_t>(), s));
+            }
+            HIP_TRY(hipStreamSynchronize(s));          // (the append runs on the result's stream; the next slice reuses the host's tables)
+            no_content.assign(nk + 1, 0);
+            ORR_TRY(orr_index_append(res, (int64_t)nk, dim, cw.cent.as<float>(), cw.ticks.as<int64_t>(), nullptr, no_content.data(), ids.data()));
+            *docs += (int64_t)nk;
+        }
+        *skipped = T - *docs;
+        return ORR_OK;
+    };
+    const int r = body();
+    (void)hipStreamSynchronize(s);                     // (an early return may have left copies and launches queued)
+    return r;
+}
+
+}  // namespace
+
+int orr_keys_centroid_index(orr_keys *k, const orr_scope *within, orr_index **out, int64_t *out_docs, int64_t *out_skipped)
+{
+    static const char *fn = "orr_keys_centroid_index";
+    switch (centroid_index::first_invalid(!out, !k)) {
+    case 0: break;
+    case 1: return fail(ORR_EINVAL, "%s: out is NULL", fn);
+    default: return fail(ORR_EINVAL, "%s: null keys", fn);
+    }
+    orr_index *own = nullptr;
+    ORR_TRY(keys_owner(k, nullptr, fn, &own));
+    Lane ln = acquire_lane(own);
+    orr_index *lane = ln.lane;
+    std::lock_guard<std::mutex> lock(lane->mu);
+    std::shared_lock<std::shared_mutex> rs;                            // the scope first, then the keys, as orr_keys_centroids
+    if (within) rs = std::shared_lock<std::shared_mutex>(within->mu);
+    std::shared_lock<std::shared_mutex> rd(k->mu);
+    if (within) ORR_TRY(key_groups_check_scope(within, own, fn));
+    ORR_TRY(keys_owner(k, nullptr, fn, &own));
+    if (k->n_rows != lane->n_rows) return fail(ORR_ESTATE, "%s: the keys cover %lld rows, the handle %lld", fn, (long long)k->n_rows, (long long)lane->n_rows);
+    if (lane->dim <= 0) return fail(ORR_EDIM, "%s: the index has no embeddings (dim 0)", fn);
+    ORR_TRY(bind_device(lane));
+    orr_config cfg{};
+    cfg.struct_size = (int32_t)sizeof(orr_config);
+    cfg.device = own->device;
+    cfg.dim = own->dim;
+    orr_index *res = nullptr;
+    ORR_TRY(orr_index_create(&cfg, &res));
+    int64_t docs = 0, skipped = 0;
+    int r = centroid_index_fill(lane, k, within, res, &docs, &skipped);
+    (void)hipStreamSynchronize(lane->stream);
+    collect_events(lane);
+    if (r == ORR_OK) r = orr_index_seal(res);
+    if (r != ORR_OK) {                                 // (the partial index goes; *out is not written)
+        orr_index_destroy(res);
+        return r;
+    }
+    *out = res;
+    if (out_docs) *out_docs = docs;
+    if (out_skipped) *out_skipped = skipped;
+    return ORR_OK;
+}
+
+int orr_index_get_rows(orr_index *idx, int64_t n, const int64_t *row_ids, int32_t dim, float *out_emb, uint8_t *out_found)
+{
+    static const char *fn = "orr_index_get_rows";
+    switch (centroid_index::first_invalid_get_rows(n, !row_ids, !out_emb, !idx)) {
+    case 0: break;
+    case 1: return fail(ORR_EINVAL, "%s: n is negative", fn);
+    case 2: return fail(ORR_EINVAL, "%s: row_ids or out_emb is NULL with %lld entries", fn, (long long)n);
+    default: return fail(ORR_EINVAL, "%s: null index", fn);
+    }
+    Lane ln = acquire_lane(idx);
+    orr_index *lane = ln.lane;
+    std::lock_guard<std::mutex> lock(lane->mu);
+    if (!lane->sealed) return fail(ORR_ESTATE, "%s: the index is not sealed", fn);
+    if (dim <= 0 || dim != lane->dim) return fail(ORR_EDIM, "%s: dim %d differs from the index dimension %d (and must be greater than 0)", fn, dim, lane->dim);
+    if (n == 0) return ORR_OK;
+    if (lane->n_rows <= 0) {
+        memset(out_emb, 0, sizeof(float) * (size_t)n * (size_t)dim);
+        if (out_found) memset(out_found, 0, (size_t)n);
+        return ORR_OK;
+    }
+    ORR_TRY(bind_device(lane));
+    ORR_TRY(ensure_scope_table(lane));
+    const orr_index *own = owner_of(lane);
+    hipStream_t s = lane->stream;
+    const int64_t per = std::min<int64_t>(n, centroid_index::get_rows_slice(dim));
+    DevBuf ids, pos, found, rows;
+    auto body = [&]() -> int {
+        ORR_TRY(ids.reserve(sizeof(int64_t) * (size_t)per));
+        ORR_TRY(pos.reserve(sizeof(uint32_t) * (size_t)per));
+        ORR_TRY(found.reserve((size_t)per));
+        ORR_TRY(rows.reserve(sizeof(float) * (size_t)per * (size_t)dim));
+        for (int64_t i0 = 0; i0 < n; i0 += per) {
+            const int64_t c = std::min(per, n - i0);
+            HIP_TRY(hipMemcpyAsync(ids.p, row_ids + i0, sizeof(int64_t) * (size_t)c, hipMemcpyHostToDevice, s));
+            {
+                Timed t(lane, "rows_find", 21.0 * (double)c);
+                HIP_TRY(orr::launch_rows_find(own->scope_tab_ids, own->scope_tab_pos, lane->n_rows, ids.as<int64_t>(), c, own->d_dead.as<int64_t>(),
+                                              (int32_t)own->dead.size(), pos.as<uint32_t>(), found.as<uint8_t>(), s));
+            }
+            {
+                Timed t(lane, "rows_gather", 8.0 * (double)dim * (double)c);
+                HIP_TRY(orr::launch_rows_gather(lane->d_emb, lane->n_rows, dim, pos.as<uint32_t>(), c, rows.as<float>(), s));
+            }
+            HIP_TRY(hipMemcpyAsync(out_emb + (size_t)i0 * (size_t)dim, rows.p, sizeof(float) * (size_t)c * (size_t)dim, hipMemcpyDeviceToHost, s));
+            if (out_found) HIP_TRY(hipMemcpyAsync(out_found + i0, found.p, (size_t)c, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));          // (the workspace is the next slice's)
+        }
+        return ORR_OK;
+    };
+    const int r = body();
+    (void)hipStreamSynchronize(s);
+    collect_events(lane);
+    for (DevBuf *b : {&ids, &pos, &found, &rows}) b->release();
+    return r;
 }
 
 namespace {

@@ -17,6 +17,7 @@
 #include "orr_per_key_plan.h"
 #include "orr_key_groups_plan.h"
 #include "orr_cluster_key_groups_plan.h"
+#include "orr_centroid_index_plan.h"
 #include "orr_keyword_plan.h"
 
 #include <atomic>
@@ -542,6 +543,16 @@ hipError_t launch_keys_block_sums(const float *emb, int64_t n_rows, int32_t dim,
                                   int64_t n_blocks, double *sums, double *parts, hipStream_t s);
 // sums[slot] = +0.0 + parts[part0] + ... + parts[part0 + n_blocks - 1], in this order, for each of the n_folds keys.
 hipError_t launch_keys_block_fold(const key_groups::Fold *folds, int64_t n_folds, const double *parts, int32_t dim, double *sums, hipStream_t s);
+// keys_centroid_finish (orr_keys_centroid_index; the rules are orr_centroid_index_plan.h's): out[i][0 .. dim) =
+// key_groups::finish_one(sums[kept[i].slot][.], kept[i].n) and out_ticks[i] = created[pos[kept[i].first]] for the n_kept kept keys
+// of a slice, densely.  Every kept[i].n > 0, every kept[i].first a pair of pos, every position of pos a row of created.
+hipError_t launch_keys_centroid_finish(const double *sums, int32_t dim, const centroid_index::Kept *kept, int64_t n_kept, const uint32_t *pos,
+                                       const int64_t *created, float *out /* [n_kept][dim] */, int64_t *out_ticks /* [n_kept] */, hipStream_t s);
+// orr_index_get_rows: out_pos[i] = the position of the first live row with id ids[i] (launch_keys_gather's lookup through the id
+// table), found[i] = 1; kRowsFindNone and 0 when there is none.  n_rows < kRowsFindNone.
+constexpr uint32_t kRowsFindNone = 0xFFFFFFFFu;
+hipError_t launch_rows_find(const int64_t *table_ids, const uint32_t *table_pos, int64_t n_rows, const int64_t *ids, int64_t n, const int64_t *dead,
+                            int32_t n_dead, uint32_t *out_pos, uint8_t *found, hipStream_t s);
 // keys_chain_step: one workgroup per Chain record and 1,024 coordinates.  The record's key continues on this shard from its state
 // rows (S: row 2 * state, P: row 2 * state + 1 of state [.][dim]): the head fragment pos[head_first .. + head_len) on top of the
 // carried P, the closed blocks (the head's, then rows part0 .. part0 + n_close - 1 of parts) on top of the carried S, in this

@@ -2372,6 +2372,20 @@ __device__ __forceinline__ bool keys_row_dead(const int64_t *__restrict__ dead, 
     return dl < n_dead && dead[dl] == p;
 }
 
+// the position of the first live row that carries id `want` (scope_lookup's search over the id table), -1 when there is none
+__device__ __forceinline__ int64_t first_live_row(const int64_t *__restrict__ table_ids, const uint32_t *__restrict__ table_pos, int64_t n_rows,
+                                                  const int64_t *__restrict__ dead, int32_t n_dead, int64_t want)
+{
+    int64_t lo = 0, hi = n_rows;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (table_ids[mid] < want) lo = mid + 1; else hi = mid;
+    }
+    for (; lo < n_rows && table_ids[lo] == want; ++lo)
+        if (!keys_row_dead(dead, n_dead, (int64_t)table_pos[lo])) return (int64_t)table_pos[lo];
+    return -1;
+}
+
 __global__ __launch_bounds__(256) void keys_gather_kernel(const int64_t *__restrict__ key, int64_t n_rows, const int64_t *__restrict__ pos, int64_t n,
                                                           const int64_t *__restrict__ table_ids, const uint32_t *__restrict__ table_pos,
                                                           const int64_t *__restrict__ dead, int32_t n_dead, int64_t *__restrict__ out)
@@ -2379,18 +2393,33 @@ __global__ __launch_bounds__(256) void keys_gather_kernel(const int64_t *__restr
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     int64_t p = pos[i];
-    if (table_ids) {                                   // pos[i] is a row id: its first live row (scope_lookup's search)
-        const int64_t want = p;
-        int64_t lo = 0, hi = n_rows;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (table_ids[mid] < want) lo = mid + 1; else hi = mid;
-        }
-        p = -1;
-        for (; lo < n_rows && table_ids[lo] == want; ++lo)
-            if (!keys_row_dead(dead, n_dead, (int64_t)table_pos[lo])) { p = (int64_t)table_pos[lo]; break; }
-    }
+    if (table_ids) p = first_live_row(table_ids, table_pos, n_rows, dead, n_dead, p);   // pos[i] is a row id
     out[i] = (p >= 0 && p < n_rows) ? key[p] : per_key::kNone;
+}
+
+// orr_index_get_rows: out_pos[i] = the position of the first live row that carries id ids[i] (first_live_row: orr_keys_get's
+// lookup), found[i] = 1; an unknown or deleted id: kRowsFindNone (at or above every n_rows: rows_gather writes zeros for it and
+// reads nothing) and found[i] = 0.
+__global__ __launch_bounds__(256) void rows_find_kernel(const int64_t *__restrict__ table_ids, const uint32_t *__restrict__ table_pos, int64_t n_rows,
+                                                        const int64_t *__restrict__ ids, int64_t n, const int64_t *__restrict__ dead, int32_t n_dead,
+                                                        uint32_t *__restrict__ out_pos, uint8_t *__restrict__ found)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t p = first_live_row(table_ids, table_pos, n_rows, dead, n_dead, ids[i]);
+    out_pos[i] = p >= 0 ? (uint32_t)p : kRowsFindNone;
+    found[i] = p >= 0 ? 1 : 0;
+}
+
+hipError_t launch_rows_find(const int64_t *table_ids, const uint32_t *table_pos, int64_t n_rows, const int64_t *ids, int64_t n, const int64_t *dead,
+                            int32_t n_dead, uint32_t *out_pos, uint8_t *found, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    if (!table_ids || !table_pos || !ids || !out_pos || !found || n_rows < 0 || n_rows >= (int64_t)kRowsFindNone || (n_dead > 0 && !dead))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rows_find_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, table_ids, table_pos, n_rows, ids, n, dead, n_dead, out_pos,
+                       found);
+    return hipGetLastError();
 }
 
 hipError_t launch_keys_gather(const int64_t *key, int64_t n_rows, const int64_t *pos, int64_t n, const int64_t *table_ids,
@@ -2497,7 +2526,8 @@ hipError_t launch_keys_count(const int64_t *key, int64_t n_rows, const int64_t *
 // One lane per row, two passes over the same selection.  A row is selected when its bit in bm is set (the live rows, or the
 // call's scope) and, by MODE, 0: it has a key (orr_keys_groups; the pair's key is key_groups::sort_key), 1: its norm participates
 // and its key is in the call's table (per_key::table_find, LDS or global as keys_member; the pair's key is the table index),
-// 2: its norm participates (orr_scope_centroid; positions only).  The count pass (WRITE false) leaves the workgroup's selected
+// 2: its norm participates (orr_scope_centroid; positions only), 3: its norm participates and it has a key
+// (orr_keys_centroid_index; the pair's key is key_groups::sort_key).  The count pass (WRITE false) leaves the workgroup's selected
 // rows in counts[blockIdx.x]; behind an exclusive scan of those the write pass compacts the pairs with the order kept: the
 // workgroup's offset, the waves in front (LDS), the lanes in front (ballot and prefix).  No atomics decide an order.
 template <int MODE, bool LDS, bool WRITE>
@@ -2527,6 +2557,12 @@ __global__ __launch_bounds__(256) void key_groups_pairs_kernel(const int64_t *__
                 const int32_t i = per_key::table_find(tk, n_tab, key[r]);
                 sel = i >= 0;
                 sk = (uint64_t)(uint32_t)i;
+            }
+        } else if (MODE == 3) {
+            if (key_groups::participates(norm_b[r])) {
+                const int64_t k = key[r];
+                sel = k != per_key::kNone;
+                sk = key_groups::sort_key(k);
             }
         } else {
             sel = key_groups::participates(norm_b[r]);
@@ -2568,12 +2604,13 @@ hipError_t launch_keys_pairs(int32_t mode, bool write, const int64_t *key, const
                              uint32_t *out_pos, hipStream_t s)
 {
     if (n_rows <= 0) return hipSuccess;
-    if (mode < 0 || mode > 2 || !bm || n_rows > words * 32 || n_rows > (int64_t)0xFFFFFFFFll || (mode != 2 && !key) || (mode != 0 && !norm_b) ||
+    if (mode < 0 || mode > 3 || !bm || n_rows > words * 32 || n_rows > (int64_t)0xFFFFFFFFll || (mode != 2 && !key) || (mode != 0 && !norm_b) ||
         (mode == 1 && (n_tab <= 0 || !tab_keys)) || (!write && !counts) || (write && (!offsets || !out_pos || cap <= 0 || (mode != 2 && !out_key))))
         return hipErrorInvalidValue;
     const unsigned blocks = (unsigned)key_groups_pair_blocks(n_rows);
     if (mode == 0) return launch_keys_pairs_form<0, false>(write, blocks, s, key, norm_b, n_rows, bm, tab_keys, n_tab, counts, offsets, cap, out_key, out_pos);
     if (mode == 2) return launch_keys_pairs_form<2, false>(write, blocks, s, key, norm_b, n_rows, bm, tab_keys, n_tab, counts, offsets, cap, out_key, out_pos);
+    if (mode == 3) return launch_keys_pairs_form<3, false>(write, blocks, s, key, norm_b, n_rows, bm, tab_keys, n_tab, counts, offsets, cap, out_key, out_pos);
     if (per_key::table_in_lds(n_tab))
         return launch_keys_pairs_form<1, true>(write, blocks, s, key, norm_b, n_rows, bm, tab_keys, n_tab, counts, offsets, cap, out_key, out_pos);
     return launch_keys_pairs_form<1, false>(write, blocks, s, key, norm_b, n_rows, bm, tab_keys, n_tab, counts, offsets, cap, out_key, out_pos);
@@ -2688,6 +2725,54 @@ hipError_t launch_keys_block_fold(const key_groups::Fold *folds, int64_t n_folds
     if (n_folds <= 0) return hipSuccess;
     if (!folds || !parts || !sums || dim <= 0 || n_folds > (int64_t)0x7FFFFFFF || (dim + 255) / 256 > 65535) return hipErrorInvalidValue;
     hipLaunchKernelGGL(key_groups_block_fold_kernel, dim3((unsigned)n_folds, (unsigned)((dim + 255) / 256)), dim3(256), 0, s, folds, parts, dim, sums);
+    return hipGetLastError();
+}
+
+// ---- the document index (orr_keys_centroid_index; the rules are orr_centroid_index_plan.h's) ----------------------------------
+// keys_centroid_finish: a streaming kernel, one lane per kept key and four consecutive coordinates (two 16-byte loads of the
+// key's fp64 sums, one 16-byte store of its fp32 centroid where VEC; guarded 8-byte loads and 4-byte stores otherwise).  Lanes
+// run along a key's coordinates first, so a wave reads 2 KB of sums and writes 1 KB of centroids, both contiguous.  The
+// expression is key_groups::finish_one, the host's.  The lane of a key's first coordinates also gathers the key's ticks
+// (keys_first_ticks, folded into this launch): created[pos[first]], its first participating member's.  No LDS, no atomics.
+template <bool VEC>
+__global__ __launch_bounds__(256) void key_groups_centroid_finish_kernel(const double *__restrict__ sums, int32_t dim, int32_t quads,
+                                                                   const centroid_index::Kept *__restrict__ kept, int64_t n_kept,
+                                                                   const uint32_t *__restrict__ pos, const int64_t *__restrict__ created,
+                                                                   float *__restrict__ out, int64_t *__restrict__ out_ticks)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t i = t / quads;
+    if (i >= n_kept) return;
+    const int32_t d0 = (int32_t)(t - i * quads) * 4;
+    const centroid_index::Kept k = kept[i];
+    if (d0 == 0) out_ticks[i] = created[pos[k.first]];
+    const double *S = sums + (size_t)k.slot * dim + d0;
+    float *c = out + (size_t)i * dim + d0;
+    const int64_t n = (int64_t)k.n;
+    if (VEC) {
+        const double2 a = *reinterpret_cast<const double2 *>(S), b = *reinterpret_cast<const double2 *>(S + 2);
+        *reinterpret_cast<float4 *>(c) = make_float4(key_groups::finish_one(a.x, n), key_groups::finish_one(a.y, n), key_groups::finish_one(b.x, n),
+                                                     key_groups::finish_one(b.y, n));
+    } else {
+        for (int32_t j = 0; j < 4 && d0 + j < dim; ++j) c[j] = key_groups::finish_one(S[j], n);
+    }
+}
+
+hipError_t launch_keys_centroid_finish(const double *sums, int32_t dim, const centroid_index::Kept *kept, int64_t n_kept, const uint32_t *pos,
+                                       const int64_t *created, float *out, int64_t *out_ticks, hipStream_t s)
+{
+    if (n_kept <= 0) return hipSuccess;
+    if (!sums || dim <= 0 || !kept || !pos || !created || !out || !out_ticks) return hipErrorInvalidValue;
+    const int32_t quads = (dim + 3) / 4;
+    const int64_t blocks = (n_kept * quads + 255) / 256;
+    if (blocks > (int64_t)0x7FFFFFFF) return hipErrorInvalidValue;
+    const bool vec = dim % 4 == 0 && reinterpret_cast<uintptr_t>(sums) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
+    if (vec)
+        hipLaunchKernelGGL(key_groups_centroid_finish_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, sums, dim, quads, kept, n_kept, pos, created,
+                           out, out_ticks);
+    else
+        hipLaunchKernelGGL(key_groups_centroid_finish_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, sums, dim, quads, kept, n_kept, pos,
+                           created, out, out_ticks);
     return hipGetLastError();
 }
 

@@ -25,10 +25,11 @@
 // Out of scope: the cluster forms (built since: orr_cluster_key_groups_plan.h defines the blocked order across shards; a host
 // may still ask each shard through orr_cluster_keys_shard, but such per-shard sums are not the single index's bits), a mean of
 // unit-normalised rows or a weighted mean, sharded.py, the service mirror and the micro-batcher, keys in the shard file, a search
-// that ranks documents by centroid.
+// that ranks documents by centroid (built since: orr_centroid_index_plan.h makes the centroids of all keys the rows of an
+// ordinary index, which every search call then ranks).
 //
 // Host-only C++17 except the inlines marked ORR_KG_HD, which the kernels share (orr_kernels.hip: keys_pairs, keys_block_sums,
-// keys_block_fold); host/orr_key_groups_plan_selftest.cpp checks all of it on a machine without a GPU.
+// keys_block_fold, keys_centroid_finish); host/orr_key_groups_plan_selftest.cpp checks all of it on a machine without a GPU.
 #pragma once
 
 #include <cstddef>
@@ -146,10 +147,14 @@ inline void sum_blocked(const float *emb, int32_t dim, const int64_t *member, in
     }
 }
 
+// One coordinate of the finish, n > 0: IEEE fp64 division, then round to nearest even.  The ONE definition: the host's finish
+// and the device's (keys_centroid_finish) both call it.
+ORR_KG_HD inline float finish_one(double S, int64_t n) { return (float)(S / (double)n); }
+
 // The finish: c = (float)(S / n), n == 0: +0.0f (and S is +0.0 then: sum_blocked of no rows)
 inline void finish(const double *S, int64_t n, int32_t dim, float *c)
 {
-    for (int32_t d = 0; d < dim; ++d) c[d] = n > 0 ? (float)(S[d] / (double)n) : +0.0f;
+    for (int32_t d = 0; d < dim; ++d) c[d] = n > 0 ? finish_one(S[d], n) : +0.0f;
 }
 
 }  // namespace key_groups

@@ -294,6 +294,22 @@ class RecallKeys:
                                          _ptr(cent) if cent.size else None, _ptr(S) if sums and S.size else None, _ptr(used) if n else None))
         return (cent, S, used) if sums else (cent, used)
 
+    def centroid_index(self, within: Optional["RecallScope"] = None) -> "RecallIndex":
+        """orr_keys_centroid_index: a sealed, owned RecallIndex with one row per key that has a row with a vector (of `within`):
+        the key's centroid (centroids' bits) as its embedding, the key as its row id, the ticks of its newest such row, no
+        content.  A snapshot, independent of this column and its index; `docs` and `skipped` (keys dropped for having no row
+        with a vector) are attributes of the result."""
+        h = C.c_void_p()
+        docs, skipped = C.c_int64(0), C.c_int64(0)
+        N.check(N.hip.orr_keys_centroid_index(self._h, within._h if within is not None else None, C.byref(h),
+                                              C.cast(C.byref(docs), C.c_void_p), C.cast(C.byref(skipped), C.c_void_p)))
+        out = RecallIndex.__new__(RecallIndex)
+        out._h = h
+        out.dim = int(N.hip.orr_index_dim(h))
+        out.row_base = 0
+        out.docs, out.skipped = int(docs.value), int(skipped.value)
+        return out
+
 
 class _BorrowedKeys(RecallKeys):
     """A shard's part of a RecallClusterKeys: usable like a RecallKeys (get, rows, RecallIndex.search_per_key on the shard),
@@ -554,6 +570,16 @@ class RecallIndex:
         done = C.c_int64(0)
         N.check(N.hip.orr_index_update_rows(self._h, n, _ptr(row_ids), dim, _ptr(emb), C.cast(C.byref(done), C.c_void_p)))
         return int(done.value)
+
+    def get_rows(self, row_ids) -> Tuple[np.ndarray, np.ndarray]:
+        """orr_index_get_rows: (emb [n, dim] float32, found [n] bool) -- the stored vectors of the live rows with these ids, bit
+        for bit; an unknown or deleted id gives zeros and found False, a row without an embedding zeros and found True."""
+        ids = np.ascontiguousarray(row_ids, dtype=np.int64).reshape(-1)
+        n, dim = int(ids.shape[0]), int(self.dim)
+        emb = np.zeros((n, dim), dtype=np.float32)
+        found = np.zeros(n, dtype=np.uint8)
+        N.check(N.hip.orr_index_get_rows(self._h, n, _ptr(ids) if n else None, dim, _ptr(emb) if n else None, _ptr(found) if n else None))
+        return emb, found.astype(bool)
 
     @staticmethod
     def _row_args(emb, created_ticks, content_lower, content_off, row_ids):
