@@ -841,8 +841,8 @@ int orr_scope_centroid(orr_scope *s, int32_t dim, float *out_centroid /* host [d
  * finished slice goes into the result through orr_index_append, device to device.
  * Out of scope: a cluster form (the host route over orr_cluster_keys_centroids remains), caller-supplied content per document
  * (titles for the keyword score), a routed two-level call (top-r documents, then search inside them: it composes from this
- * index, orr_scope_create_keys and orr_search_batch_in_scopes), keeping the derived index in step with the source
- * automatically, sharded.py, the service mirror and the micro-batcher, keys in the shard file, a pinned return path for
+ * index, orr_scope_create_keys and orr_search_batch_in_scopes; built since: §8y, orr_search_batch_routed below), keeping
+ * the derived index in step with the source automatically, sharded.py, the service mirror and the micro-batcher, keys in the shard file, a pinned return path for
  * orr_keys_centroids.
  *
  * orr_index_get_rows returns the stored fp32 embedding of each listed live row, bit for bit (a sealed index or a view).  An
@@ -854,6 +854,46 @@ int orr_keys_centroid_index(orr_keys *k, const orr_scope *within /* or NULL */, 
                             int64_t *out_docs /* may be NULL */, int64_t *out_skipped /* may be NULL */);
 int orr_index_get_rows(orr_index *idx, int64_t n, const int64_t *row_ids /* host */, int32_t dim,
                        float *out_emb /* host [n][dim] */, uint8_t *out_found /* host [n], may be NULL */);
+
+/* ---- routed search: the top documents by centroid, then the best chunks inside them --------------------------------------------
+ * orr_search_batch_routed ranks the rows of `docs` (any sealed index whose row ids are keys of `keys`: normally the result of
+ * orr_keys_centroid_index; it may live on another device, be a view, or be idx itself) for every query, keeps the best `route`
+ * of them, and searches idx (the chunk index, `keys` a key column of it) only inside the rows that carry one of those keys.
+ * The rules are csrc/orr_routed_plan.h's.
+ *
+ * THE CONTRACT IS A TWIN.  For each query b, rows, order, fp64 score bits and counts are exactly what a host gets this way:
+ *   1. Route: orr_search_batch(docs, 1, dim, q_b, the query's own terms, now_ticks, topk = route, candidate_limit = every row of
+ *      docs) gives D_b, the returned row ids in rank order, and n_b, their number.  out_route_keys[b][0 .. n_b) = D_b, the
+ *      entries behind ORR_KEY_NONE; out_route_n[b] = n_b.  A document index without content gives keyword score 0; a host-built
+ *      docs with titles as content routes by them too.
+ *   2. Scope: S_b = orr_scope_create_keys(idx, keys, D_b without ORR_KEY_NONE), ANDed with `within` when one is given.  An id
+ *      equal to ORR_KEY_NONE is reported in out_route_keys but selects no row.
+ *   3. Search: orr_search_batch_in_scope(idx, 1, dim, q_b, terms_b, now_ticks, topk, candidate_limit, S_b): candidate_limit
+ *      counts the live rows of S_b; an empty S_b gives count 0.
+ * Outputs: out_rows / out_scores [B][max(1, topk)], out_counts [B], unused slots -1 / 0.0; out_route_keys [B][route] and
+ * out_route_n [B] may be NULL.  route is 1 .. 1024.  B == 0 returns ORR_OK and writes nothing.
+ * ORR_EINVAL before any handle is looked at, in this order: an output among out_rows, out_scores, out_counts NULL; route outside
+ * its range; keys NULL; docs NULL.  Then the errors of the search's own arguments in their order, then ORR_EINVAL for a `keys` or
+ * `within` of another shard than idx and ORR_ESTATE for an orphaned handle.  On any error no output is written.
+ * Locks: the route step runs through orr_search_batch on docs and takes and releases its own lane before a lane of idx is taken:
+ * the call never holds both, and docs == idx cannot deadlock.  The chunk step holds one lane of idx with `within` and `keys`
+ * shared, as orr_search_batch_per_key does.
+ * On the device: queries with the same set of routed keys share one slot; per slice of at most 64 distinct slots the sorted
+ * union table of the slots' keys (16 bytes per entry) goes up, ONE keys_include launch writes the slots' bitmaps (a workgroup of
+ * 2,048 rows none of which is routed stores zeros without reading the base), one scope_counts, one mask_clip_slots and one
+ * synchronise make them temporary scopes that are never registered with the index, and ONE grouped pass (the masked pass for a
+ * slice of one slot) searches them.  No keys_member pass, no registered scope and no per-query synchronise runs.  The search
+ * statistics count the call as one grouped call.
+ * Out of scope: a cluster form, the service mirror and the micro-batcher, a record (shard) form, caller-supplied document
+ * content built on the device, keeping a document index in step with its source, combining with the diverse or the per-key
+ * search, a public call that makes many key scopes at once. */
+int orr_search_batch_routed(orr_index *docs, orr_index *idx, const orr_keys *keys, int32_t B, int32_t dim, const float *q,
+                            const uint8_t *terms_utf8, const uint32_t *term_off, const uint32_t *query_term_off,
+                            int64_t now_ticks, int32_t route, int32_t topk, int64_t candidate_limit,
+                            const orr_scope *within /* a scope of idx, or NULL */,
+                            int64_t *out_rows, double *out_scores, int32_t *out_counts,
+                            int64_t *out_route_keys /* host [B][route], may be NULL */,
+                            int32_t *out_route_n /* host [B], may be NULL */);
 
 /* orr_search_shard_masked with the scope taken from a handle: the record form of orr_search_batch_in_scope, the shard half of
  * orr_cluster_search_batch_in_scope.  The contract is orr_search_shard_masked's, unchanged: [B][kprime+1] records and the

@@ -153,6 +153,8 @@ hip.orr_scope_centroid.restype = C.c_int
 hip.orr_scope_centroid.argtypes = [_vp, _i32, _vp, _vp, _vp]
 hip.orr_keys_centroid_index.restype = C.c_int
 hip.orr_keys_centroid_index.argtypes = [_vp, _vp, C.POINTER(_vp), _vp, _vp]
+hip.orr_search_batch_routed.restype = C.c_int
+hip.orr_search_batch_routed.argtypes = [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]
 hip.orr_index_get_rows.restype = C.c_int
 hip.orr_index_get_rows.argtypes = [_vp, _i64, _vp, _i32, _vp, _vp]
 hip.orr_search_shard_in_scope.restype = C.c_int
@@ -375,7 +377,7 @@ EXPORTED_HIP_SYMBOLS = [
     "orr_search_batch_diverse", "orr_index_pair_dots",
     "orr_keys_create", "orr_keys_set", "orr_keys_get", "orr_keys_rows", "orr_keys_destroy", "orr_scope_create_keys", "orr_search_batch_per_key",
     "orr_keys_groups", "orr_keys_centroids", "orr_scope_centroid",
-    "orr_keys_centroid_index", "orr_index_get_rows",
+    "orr_keys_centroid_index", "orr_index_get_rows", "orr_search_batch_routed",
     "orr_cluster_scope_create", "orr_cluster_scope_create_ticks", "orr_cluster_scope_create_terms", "orr_cluster_scope_create_near", "orr_cluster_scope_add_ids", "orr_cluster_scope_combine",
     "orr_cluster_scope_rows", "orr_cluster_scope_row_ids", "orr_cluster_scope_shard", "orr_cluster_scope_destroy", "orr_cluster_search_batch_in_scope",
     "orr_cluster_search_batch_in_scopes", "orr_cluster_search_range_cosine", "orr_cluster_search_range_cosine_bulk",

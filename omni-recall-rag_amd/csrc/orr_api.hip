@@ -48,6 +48,7 @@
 #include "orr_cluster_scope_plan.h"
 #include "orr_cluster_diverse_plan.h"
 #include "orr_cluster_per_key_plan.h"
+#include "orr_routed_plan.h"
 #include "orr_token_index.h"
 
 namespace {
@@ -8029,6 +8030,8 @@ int per_key_freeze(orr_index *lane, const BatchArgs &a, const orr_scope *within,
     return ORR_OK;
 }
 
+int slice_scopes_reserve(int32_t S, int64_t words, PerKeyWork &w);
+int slice_scopes_finish(orr_index *lane, int32_t S, PerKeyWork &w, std::unique_ptr<orr_scope[]> &tmp);
 int per_key_slice_scopes(orr_index *lane, const orr_keys *keys, int32_t S, const std::vector<int64_t> &tk, const std::vector<uint64_t> &tm,
                          const std::vector<int64_t> &seen_pos, const std::vector<int32_t> &seen_slot, PerKeyWork &w, std::unique_ptr<orr_scope[]> &tmp);
 
@@ -8086,15 +8089,11 @@ int per_key_slice_scopes(orr_index *lane, const orr_keys *keys, int32_t S, const
 {
     hipStream_t s = lane->stream;
     const int64_t words = w.words;
-    const int32_t n_chunks = orr::scope_chunks(words);
     const size_t n_tab = tk.size();
     const size_t n_seen = seen_pos.size();
-    ORR_TRY(w.ex_bm.reserve(sizeof(uint32_t) * (size_t)S * (size_t)words));
-    ORR_TRY(w.ex_chunks.reserve(sizeof(uint32_t) * (size_t)S * (size_t)n_chunks));
+    ORR_TRY(slice_scopes_reserve(S, words, w));
     ORR_TRY(w.tab.reserve(16 * std::max<size_t>(n_tab, 1)));
     ORR_TRY(w.seen.reserve(12 * std::max<size_t>(n_seen, 1)));
-    ORR_TRY(w.limits.reserve(sizeof(int64_t) * per_key::kMaxSlots + 2 * sizeof(uint32_t) * per_key::kMaxSlots));      // [limit][live][took]
-    ORR_TRY(w.pin.reserve((4 + 4 + 8) * (size_t)per_key::kMaxSlots));
     int64_t *d_tk = w.tab.as<int64_t>();
     uint64_t *d_tm = reinterpret_cast<uint64_t *>(d_tk + n_tab);
     int64_t *d_seen_pos = w.seen.as<int64_t>();
@@ -8107,9 +8106,7 @@ int per_key_slice_scopes(orr_index *lane, const orr_keys *keys, int32_t S, const
         HIP_TRY(hipMemcpyAsync(d_seen_pos, seen_pos.data(), sizeof(int64_t) * n_seen, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(d_seen_slot, seen_slot.data(), sizeof(int32_t) * n_seen, hipMemcpyHostToDevice, s));
     }
-    const std::vector<int64_t> no_limit((size_t)per_key::kMaxSlots, std::numeric_limits<int64_t>::max());
-    HIP_TRY(hipMemcpyAsync(w.limits.p, no_limit.data(), sizeof(int64_t) * no_limit.size(), hipMemcpyHostToDevice, s));
-    uint32_t *ex = w.ex_bm.as<uint32_t>(), *exc = w.ex_chunks.as<uint32_t>();
+    uint32_t *ex = w.ex_bm.as<uint32_t>();
     {
         Timed t(lane, "keys_exclude", 8.0 * (double)lane->n_rows + 4.0 * (double)words * (double)(S + 1));
         HIP_TRY(orr::launch_keys_exclude(keys->d_key, lane->n_rows, w.c_bm.as<uint32_t>(), words, d_tk, d_tm, (int32_t)n_tab, S, ex, s));
@@ -8118,7 +8115,33 @@ int per_key_slice_scopes(orr_index *lane, const orr_keys *keys, int32_t S, const
         Timed t(lane, "keys_clear_seen", 16.0 * (double)n_seen);
         HIP_TRY(orr::launch_keys_clear_seen(ex, words, S, d_seen_slot, d_seen_pos, (int64_t)n_seen, s));
     }
-    // ---- what a scope keeps beside its bitmap (refresh_scope's two steps, each ONE launch for the S bitmaps; one synchronise)
+    return slice_scopes_finish(lane, S, w, tmp);
+}
+
+// The room a slice of S temporary scopes over `words` words takes in `w`: the bitmaps, their chunk counts, the limits, the
+// pinned counts.
+int slice_scopes_reserve(int32_t S, int64_t words, PerKeyWork &w)
+{
+    ORR_TRY(w.ex_bm.reserve(sizeof(uint32_t) * (size_t)S * (size_t)words));
+    ORR_TRY(w.ex_chunks.reserve(sizeof(uint32_t) * (size_t)S * (size_t)orr::scope_chunks(words)));
+    ORR_TRY(w.limits.reserve(sizeof(int64_t) * per_key::kMaxSlots + 2 * sizeof(uint32_t) * per_key::kMaxSlots));      // [limit][live][took]
+    ORR_TRY(w.pin.reserve((4 + 4 + 8) * (size_t)per_key::kMaxSlots));
+    return ORR_OK;
+}
+
+// What the S bitmaps in w.ex_bm (w.words words each, their launches queued on the lane's stream) still lack to be scopes the
+// masked and grouped stages take: refresh_scope's two steps, each ONE launch for the S bitmaps (no limit: a scope keeps the
+// count and the clip of ALL its rows; the stages apply the call's candidate_limit themselves), and one synchronise.
+// tmp[i]: slot i's scope, never registered with the index, valid while `w` is.  Shared by the per-key rounds (keys_exclude)
+// and the routed search (keys_include).
+int slice_scopes_finish(orr_index *lane, int32_t S, PerKeyWork &w, std::unique_ptr<orr_scope[]> &tmp)
+{
+    hipStream_t s = lane->stream;
+    const int64_t words = w.words;
+    const int32_t n_chunks = orr::scope_chunks(words);
+    uint32_t *ex = w.ex_bm.as<uint32_t>(), *exc = w.ex_chunks.as<uint32_t>();
+    const std::vector<int64_t> no_limit((size_t)per_key::kMaxSlots, std::numeric_limits<int64_t>::max());
+    HIP_TRY(hipMemcpyAsync(w.limits.p, no_limit.data(), sizeof(int64_t) * no_limit.size(), hipMemcpyHostToDevice, s));
     uint32_t *h_live = w.pin.as<uint32_t>();
     int64_t *h_clip = reinterpret_cast<int64_t *>(h_live + 2 * per_key::kMaxSlots);
     uint32_t *d_live = reinterpret_cast<uint32_t *>(w.limits.as<int64_t>() + per_key::kMaxSlots), *d_took = d_live + per_key::kMaxSlots;
@@ -8279,6 +8302,155 @@ int orr_search_batch_per_key(orr_index *idx, int32_t B, int32_t dim, const float
     const int r = per_key_run(idx, fn, a, within, keys, max_per_key, pool, out_rows, out_scores, out_keys, out_counts, out_rounds);
     g_ht.done();
     return r;
+}
+
+// ---- routed search (orr_search_batch_routed; the rules are orr_routed_plan.h's) -----------------------------------------------
+// The route step is the public orr_search_batch on `docs`; the chunk step reuses the per-key rounds' machinery with the opposite
+// kernel: per slice of at most 64 distinct routes ONE keys_include launch into temporary bitmaps, slice_scopes_finish, ONE
+// grouped_batch (masked_batch for a slice of one slot) over temporary scopes that are never registered with the index.
+
+namespace {
+
+// The chunk step on the lane the caller holds (keys and `within`, if any, held shared): route_keys [B][route] and route_n [B] are
+// the route step's answer; rows / scores [B][take] and counts [B] receive the call's.
+int routed_run(orr_index *lane, const BatchArgs &a, const orr_keys *keys, const orr_scope *within, int32_t route, const int64_t *route_keys,
+               const int32_t *route_n, int64_t *rows, double *scores, int32_t *counts)
+{
+    const int32_t B = a.B, take = std::max<int32_t>(1, a.topk);
+    for (size_t i = 0; i < (size_t)B * take; ++i) { rows[i] = -1; scores[i] = 0.0; }
+    for (int32_t b = 0; b < B; ++b) counts[b] = 0;
+    if (lane->n_rows <= 0 || (within && within->live.load() <= 0)) return ORR_OK;
+    const routed::Slots slots = routed::slots(B, route, route_keys, route_n);
+    const std::vector<routed::Slice> slices = routed::slices(slots);
+    if (slices.empty()) return ORR_OK;                 // no query routed anywhere: nothing is launched
+    ORR_TRY(bind_device(lane));
+    hipStream_t s = lane->stream;
+    PerKeyWork w;
+    // ---- the base the in-scope twin would AND with: `within`'s bitmap where it lies, or the live rows
+    const uint32_t *base = nullptr;
+    if (within) {
+        w.words = within->words;
+        base = within->bm;
+    } else {
+        BatchArgs all = a;
+        all.candidate_limit = lane->row_base + lane->n_rows;           // every row of the shard
+        ORR_TRY(per_key_freeze(lane, all, nullptr, w));
+        base = w.c_bm.as<uint32_t>();
+    }
+    const int64_t words = w.words;
+    BatchArgs host_a = a;
+    if (a.dim > 0 && is_device_pointer(a.q)) {         // (sub-batches are gathered on the host: device-resident vectors come down once)
+        w.q_down.resize((size_t)B * (size_t)a.dim);
+        HIP_TRY(hipMemcpy(w.q_down.data(), a.q, sizeof(float) * w.q_down.size(), hipMemcpyDeviceToHost));
+        host_a.q = w.q_down.data();
+    }
+    std::vector<int64_t> tk, s_rows;
+    std::vector<uint64_t> tm;
+    std::vector<double> s_scores;
+    std::vector<int32_t> s_cnt;
+    for (const routed::Slice &c : slices) {
+        const int32_t S = c.n_slots;
+        routed::slice_table(slots, c, tk, tm);
+        const size_t n_tab = tk.size();
+        ORR_TRY(slice_scopes_reserve(S, words, w));
+        ORR_TRY(w.tab.reserve(16 * std::max<size_t>(n_tab, 1)));
+        int64_t *d_tk = w.tab.as<int64_t>();
+        uint64_t *d_tm = reinterpret_cast<uint64_t *>(d_tk + n_tab);
+        HIP_TRY(hipMemcpyAsync(d_tk, tk.data(), sizeof(int64_t) * n_tab, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_tm, tm.data(), sizeof(uint64_t) * n_tab, hipMemcpyHostToDevice, s));
+        {
+            // the keys, every word of the S bitmaps written; the base words of the workgroups that hold a routed row are read too,
+            // but how many those are only the device knows: they are not counted
+            Timed t(lane, "keys_include", 8.0 * (double)lane->n_rows + 4.0 * (double)words * (double)S);
+            HIP_TRY(orr::launch_keys_include(keys->d_key, lane->n_rows, base, words, d_tk, d_tm, (int32_t)n_tab, S, w.ex_bm.as<uint32_t>(), s));
+        }
+        std::unique_ptr<orr_scope[]> tmp;
+        ORR_TRY(slice_scopes_finish(lane, S, w, tmp));
+        std::vector<const orr_scope *> ptrs((size_t)S);
+        for (int32_t i = 0; i < S; ++i) ptrs[(size_t)i] = &tmp[(size_t)i];
+        // ---- the search: every query inside its slot's scope, the call's own topk and candidate_limit
+        const size_t nq = c.queries.size();
+        SubBatch sb;
+        BatchArgs cur;
+        ORR_TRY(build_subset(lane, host_a, c.queries, sb, cur));
+        s_rows.assign(nq * (size_t)take, -1); s_scores.assign(nq * (size_t)take, 0.0); s_cnt.assign(nq, 0);
+        if (S == 1) {
+            ORR_TRY(masked_batch(lane, cur, ScopeSource{nullptr, ptrs[0]}, s_rows.data(), s_scores.data(), s_cnt.data()));
+        } else {
+            GroupArgs ga{S, 0, nullptr, nullptr, c.query_slot.data()};
+            ga.scopes = ptrs.data();
+            ORR_TRY(grouped_batch(lane, cur, ga, s_rows.data(), s_scores.data(), s_cnt.data()));
+        }
+        for (size_t i = 0; i < nq; ++i) {
+            const size_t b = (size_t)c.queries[i];
+            memcpy(rows + b * take, s_rows.data() + i * take, sizeof(int64_t) * (size_t)take);
+            memcpy(scores + b * take, s_scores.data() + i * take, sizeof(double) * (size_t)take);
+            counts[b] = s_cnt[i];
+        }
+    }
+    return ORR_OK;
+}
+
+}  // namespace
+
+int orr_search_batch_routed(orr_index *docs, orr_index *idx, const orr_keys *keys, int32_t B, int32_t dim, const float *q,
+                            const uint8_t *terms_utf8, const uint32_t *term_off, const uint32_t *query_term_off, int64_t now_ticks,
+                            int32_t route, int32_t topk, int64_t candidate_limit, const orr_scope *within, int64_t *out_rows,
+                            double *out_scores, int32_t *out_counts, int64_t *out_route_keys, int32_t *out_route_n)
+{
+    static const char *fn = "orr_search_batch_routed";
+    switch (routed::first_invalid(!out_rows || !out_scores || !out_counts, route, !keys, !docs)) {
+    case 0: break;
+    case 1: return fail(ORR_EINVAL, "%s: out_rows, out_scores and out_counts are required", fn);
+    case 2: return fail(ORR_EINVAL, "%s: route must be in 1 .. %d", fn, routed::kMaxRoute);
+    case 3: return fail(ORR_EINVAL, "%s: null keys", fn);
+    default: return fail(ORR_EINVAL, "%s: null document index", fn);
+    }
+    if (!idx) return fail(ORR_EINVAL, "%s: null index", fn);
+    if (B == 0) return ORR_OK;
+    BatchArgs a{B, dim, q, terms_utf8, term_off, query_term_off, now_ticks, candidate_limit, topk};
+    ORR_TRY(check_batch(idx, a, fn));
+    orr_index *own = nullptr;
+    if (within) ORR_TRY(scope_owner(within, idx, fn, &own));
+    ORR_TRY(keys_owner(keys, idx, fn, &own));
+    // ---- route: the public search on docs, its own lane taken and released before a lane of idx is (docs may be idx)
+    const int32_t take = std::max<int32_t>(1, topk);
+    std::vector<int64_t> r_keys((size_t)B * (size_t)route, ORR_KEY_NONE);
+    std::vector<double> r_scores((size_t)B * (size_t)route, 0.0);
+    std::vector<int32_t> r_n((size_t)B, 0);
+    ORR_TRY(orr_search_batch(docs, B, dim, q, terms_utf8, term_off, query_term_off, now_ticks, route, std::max<int64_t>(1, orr_index_rows(docs)),
+                             r_keys.data(), r_scores.data(), r_n.data()));
+    for (int32_t b = 0; b < B; ++b)                     // (a row id may be any key, -1 included: the count tells what was returned)
+        for (int32_t j = std::max<int32_t>(0, r_n[(size_t)b]); j < route; ++j) r_keys[(size_t)b * route + j] = ORR_KEY_NONE;
+    // ---- chunks: one lane of idx, the scope first, then the keys, as orr_search_batch_per_key
+    std::vector<int64_t> rows((size_t)B * (size_t)take);
+    std::vector<double> scores((size_t)B * (size_t)take);
+    std::vector<int32_t> counts((size_t)B);
+    {
+        Lane ln = acquire_lane(idx);
+        orr_index *lane = ln.lane;
+        std::lock_guard<std::mutex> lock(lane->mu);
+        std::shared_lock<std::shared_mutex> rd;
+        if (within) {
+            rd = std::shared_lock<std::shared_mutex>(within->mu);
+            ORR_TRY(scope_owner(within, lane, fn, &own));
+            if (within->n_rows != lane->n_rows) return fail(ORR_ESTATE, "%s: the scope covers %lld rows, the handle %lld", fn, (long long)within->n_rows, (long long)lane->n_rows);
+        }
+        std::shared_lock<std::shared_mutex> rk(keys->mu);
+        ORR_TRY(keys_owner(keys, lane, fn, &own));
+        if (keys->n_rows != lane->n_rows) return fail(ORR_ESTATE, "%s: the keys cover %lld rows, the handle %lld", fn, (long long)keys->n_rows, (long long)lane->n_rows);
+        lane->sstats.searches += 1;                    // as one grouped call
+        lane->sstats.queries += B;
+        const int r = routed_run(lane, a, keys, within, route, r_keys.data(), r_n.data(), rows.data(), scores.data(), counts.data());
+        g_ht.done();
+        if (r != ORR_OK) return r;
+    }
+    memcpy(out_rows, rows.data(), sizeof(int64_t) * rows.size());
+    memcpy(out_scores, scores.data(), sizeof(double) * scores.size());
+    memcpy(out_counts, counts.data(), sizeof(int32_t) * counts.size());
+    if (out_route_keys) memcpy(out_route_keys, r_keys.data(), sizeof(int64_t) * r_keys.size());
+    if (out_route_n) memcpy(out_route_n, r_n.data(), sizeof(int32_t) * r_n.size());
+    return ORR_OK;
 }
 
 int orr_search_shard_scoped(orr_index *idx, int32_t B, int32_t dim, const float *q, const uint8_t *terms_utf8,

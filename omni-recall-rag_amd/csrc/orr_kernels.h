@@ -18,6 +18,7 @@
 #include "orr_key_groups_plan.h"
 #include "orr_cluster_key_groups_plan.h"
 #include "orr_centroid_index_plan.h"
+#include "orr_routed_plan.h"
 #include "orr_keyword_plan.h"
 
 #include <atomic>
@@ -494,6 +495,11 @@ hipError_t launch_scope_entry_ids(const SelEntry *buf, int64_t n, const int64_t 
 // column, tab_keys / tab_masks [n_tab] the sorted union table (per_key::build_table; LDS up to per_key::kLdsTable entries, global
 // memory beyond).  base: words % 4 == 0, 16-byte aligned, bits at or above n_rows clear; out 16-byte aligned.  No atomics.
 hipError_t launch_keys_exclude(const int64_t *key, int64_t n_rows, const uint32_t *base, int64_t words, const int64_t *tab_keys,
+                               const uint64_t *tab_masks, int32_t n_tab, int32_t n_slots, uint32_t *out, hipStream_t s);
+// The opposite rule (orr_search_batch_routed; orr_routed_plan.h): out[s][words] for s < n_slots (all words written) = base AND the
+// rows whose key slot s routed to.  The arguments and what is refused are launch_keys_exclude's; base is read only by the
+// workgroups that hold a routed row.
+hipError_t launch_keys_include(const int64_t *key, int64_t n_rows, const uint32_t *base, int64_t words, const int64_t *tab_keys,
                                const uint64_t *tab_masks, int32_t n_tab, int32_t n_slots, uint32_t *out, hipStream_t s);
 // The bit of position pos[i] cleared in bitmap slot[i] of bitmaps[.][words], for n (slot, position) pairs (device).
 hipError_t launch_keys_clear_seen(uint32_t *bitmaps, int64_t words, int32_t n_slots, const int32_t *slot, const int64_t *pos, int64_t n,

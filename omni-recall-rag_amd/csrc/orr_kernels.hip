@@ -2306,6 +2306,95 @@ hipError_t launch_keys_exclude(const int64_t *key, int64_t n_rows, const uint32_
     return hipGetLastError();
 }
 
+// The sibling of keys_exclude with the opposite rule (orr_search_batch_routed; the rules are orr_routed_plan.h's): slot s's
+// bitmap holds the rows of `base` whose key the slot routed to.  The same ownership, loads and table search.  A workgroup none of
+// whose rows is routed -- by far the common case: a few documents out of millions of rows -- stores zeros into its words of
+// every slot as 16-byte vectors and does not read the base at all.  Any other workgroup builds the slots' words in an LDS tile
+// that starts as zero: a wave with a routed row forms, for every slot in the OR of its lanes' masks, the slot's 64 bits with one
+// ballot and stores routed::include_bits(base word pair, ballot); the tile leaves as 16-byte vectors, 256 contiguous bytes per
+// slot.  Every word of the n_slots bitmaps is written; rows at or above n_rows are clear (their key reads as kNone).  No atomics.
+template <bool LDS>
+__global__ __launch_bounds__(256) void routed_include_kernel(const int64_t *__restrict__ key, int64_t n_rows, const uint32_t *__restrict__ base,
+                                                           int64_t words, const int64_t *__restrict__ tab_keys,
+                                                           const uint64_t *__restrict__ tab_masks, int32_t n_tab, int32_t n_slots,
+                                                           uint32_t *__restrict__ out)
+{
+    __shared__ int64_t sh_keys[LDS ? per_key::kLdsTable : 1];
+    __shared__ uint64_t sh_masks[LDS ? per_key::kLdsTable : 1];
+    __shared__ __attribute__((aligned(16))) uint32_t tile[per_key::kMaxSlots][per_key::kBlockWords];
+    const int tid = threadIdx.x;
+    if (LDS) {
+        for (int i = tid; i < n_tab; i += 256) { sh_keys[i] = tab_keys[i]; sh_masks[i] = tab_masks[i]; }
+        __syncthreads();
+    }
+    const int64_t *tk = LDS ? sh_keys : tab_keys;
+    const uint64_t *tm = LDS ? sh_masks : tab_masks;
+    const int64_t w0 = (int64_t)blockIdx.x * per_key::kBlockWords;
+    if (w0 >= words) return;                           // (workgroup-uniform)
+    const int wc = (int)(words - w0 < per_key::kBlockWords ? words - w0 : per_key::kBlockWords);      // a multiple of 4
+    const int64_t row0 = w0 * 32;
+    uint64_t m[8];
+    int any = 0;
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+        const int64_t r = row0 + it * 256 + tid;
+        const int64_t k = r < n_rows ? key[r] : per_key::kNone;
+        m[it] = per_key::table_mask(tk, tm, n_tab, k);
+        any |= m[it] != 0ull;
+    }
+    const int hit = __syncthreads_or(any);
+    const int vec = wc >> 2;                           // 16-byte vectors per slot
+    if (!hit) {
+        const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+        for (int i = tid; i < n_slots * vec; i += 256) {
+            const int s = i / vec, j = i - s * vec;
+            reinterpret_cast<uint4 *>(out + (int64_t)s * words + w0)[j] = zero;
+        }
+        return;
+    }
+    for (int i = tid; i < n_slots * per_key::kBlockWords; i += 256) tile[i >> 6][i & 63] = 0u;
+    __syncthreads();
+    const int wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+        uint64_t o = wave_or_u64(m[it]);               // the same in every lane of the wave
+        const int wi = it * 8 + wave * 2;              // the wave's 64 rows: words wi, wi + 1 of the workgroup's
+        if (o == 0ull || wi >= wc) continue;
+        const uint64_t b = (uint64_t)base[w0 + wi] | ((uint64_t)base[w0 + wi + 1] << 32);
+        while (o) {
+            const int s = __ffsll((long long)o) - 1;
+            o &= o - 1ull;
+            const uint64_t in = __ballot(per_key::slot_closed(m[it], s));
+            if (lane == 0 && s < n_slots) {
+                const uint64_t v = routed::include_bits(b, in);
+                tile[s][wi] = (uint32_t)v;
+                tile[s][wi + 1] = (uint32_t)(v >> 32);
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < n_slots * vec; i += 256) {
+        const int s = i / vec, j = i - s * vec;
+        reinterpret_cast<uint4 *>(out + (int64_t)s * words + w0)[j] = *reinterpret_cast<const uint4 *>(&tile[s][j * 4]);
+    }
+}
+
+hipError_t launch_keys_include(const int64_t *key, int64_t n_rows, const uint32_t *base, int64_t words, const int64_t *tab_keys,
+                               const uint64_t *tab_masks, int32_t n_tab, int32_t n_slots, uint32_t *out, hipStream_t s)
+{
+    if (n_slots <= 0) return hipSuccess;
+    if (words <= 0 || words % 4 != 0 || n_rows < 0 || n_rows > words * 32 || n_slots > per_key::kMaxSlots || n_tab < 0 || !key || !base || !out ||
+        (n_tab > 0 && (!tab_keys || !tab_masks)))
+        return hipErrorInvalidValue;
+    if (reinterpret_cast<uintptr_t>(base) % 16 != 0 || reinterpret_cast<uintptr_t>(out) % 16 != 0) return hipErrorInvalidValue;
+    const unsigned blocks = (unsigned)((words + per_key::kBlockWords - 1) / per_key::kBlockWords);
+    if (per_key::table_in_lds(n_tab))
+        hipLaunchKernelGGL(routed_include_kernel<true>, dim3(blocks), dim3(256), 0, s, key, n_rows, base, words, tab_keys, tab_masks, n_tab, n_slots, out);
+    else
+        hipLaunchKernelGGL(routed_include_kernel<false>, dim3(blocks), dim3(256), 0, s, key, n_rows, base, words, tab_keys, tab_masks, n_tab, n_slots, out);
+    return hipGetLastError();
+}
+
 // scope_clear_positions with a slot: pair i clears bit pos[i] of bitmap slot[i] (pairs outside the bitmaps are passed over)
 __global__ __launch_bounds__(256) void keys_clear_seen_kernel(uint32_t *__restrict__ bitmaps, int64_t words, int32_t n_slots,
                                                               const int32_t *__restrict__ slot, const int64_t *__restrict__ pos, int64_t n)

@@ -878,6 +878,27 @@ class RecallIndex:
                                                _ptr(rounds)))
         return rows, scores, rkeys, counts, rounds
 
+    def search_routed(self, docs: "RecallIndex", keys: RecallKeys, qvecs, queries_terms, now_ticks: int, topk: int, route: int,
+                      within: Optional[RecallScope] = None, candidate_limit: int = 300):
+        """orr_search_batch_routed: per query the best `route` (1 .. 1024) rows of `docs` (a sealed index whose row ids are keys
+        of `keys`, normally keys.centroid_index()), then the search inside the rows of this index that carry one of those keys
+        (and lie in `within`, when given).  Bit for bit what docs.search, scope_keys(.and_(within)) and search_in_scope give per
+        query.  Returns (rows [B,k] int64, fused scores [B,k] float64, counts [B] int32, route_keys [B,route] int64 -- KEY_NONE
+        behind the routed ones --, route_n [B] int32)."""
+        B = len(queries_terms)
+        dim, q, _keep = self._query_args(qvecs, B)
+        tpool, toff, qoff = pack_terms(queries_terms)
+        k, r = max(1, int(topk)), max(1, int(route))
+        rows = np.full((B, k), -1, dtype=np.int64)
+        scores = np.zeros((B, k), dtype=np.float64)
+        counts = np.zeros(B, dtype=np.int32)
+        route_keys = np.full((B, r), N.ORR_KEY_NONE, dtype=np.int64)
+        route_n = np.zeros(B, dtype=np.int32)
+        N.check(N.hip.orr_search_batch_routed(docs._h, self._h, keys._h, B, dim, _ptr(q), _ptr(tpool), _ptr(toff), _ptr(qoff), now_ticks,
+                                              int(route), int(topk), int(candidate_limit), within._h if within is not None else None,
+                                              _ptr(rows), _ptr(scores), _ptr(counts), _ptr(route_keys), _ptr(route_n)))
+        return rows, scores, counts, route_keys, route_n
+
     def search_in_scope(self, qvecs, queries_terms, now_ticks: int, topk: int, scope: RecallScope, candidate_limit: int = 300):
         """orr_search_batch_in_scope: search_masked with the scope taken from a handle -- nothing is resolved per call.
         Returns (rows [B,k] int64, scores [B,k] float64, counts [B] int32)."""
